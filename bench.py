@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the two hot paths on MI355X (contract: see the task statement / DESIGN.md).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Headline (BASELINE.json metric, config "1M persons x 100k places, K=50, KNN cosine + top-K on 1
@@ -10,7 +10,10 @@ ALL persons (cosine over place + category vectors, combine, per-query top-K), wi
 resident in HBM and the results left in HBM.  Ranks hold the full candidate set (built from
 per-rank shards exchanged with one RCCL all-gather at set-up) and shard the QUERIES: no
 collective in the timed region, weak scaling.
-The same JSON line carries the SG figure (config "~5M edges, 100 power iterations") under "sg".
+A plain run sets up, warms up, times --steps steps and prints the headline line (with the roofline of
+the timed launches).  --full adds every other leg to the same JSON line: the oracle check of the last
+step, the request latencies, the host-inclusive, large-K, other-format and wide-row legs, the CPU
+baselines, and the SG figure (config "~5M edges, 100 power iterations") under "sg".
 """
 import argparse
 import json
@@ -89,6 +92,10 @@ def parse():
     ap.add_argument("--sg-sweeps", type=int, default=100)
     ap.add_argument("--no-aggregate", action="store_true",
                     help="KNN step = neighbours only (skip makeRecommendations0's aggregation kernel)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float64; rank 0's queries)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (the options below apply to those legs)")
     ap.add_argument("--no-sg", action="store_true")
     ap.add_argument("--sg-graphs", type=int, default=8,
                     help="graphs per GPU of the batched SG leg (cfg5: 64 graphs over 8 GPUs); 0 = skip")
@@ -97,7 +104,10 @@ def parse():
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg (and the oracle sample check)")
     ap.add_argument("--no-formats", action="store_true", help="skip the PACK32 / GENERIC secondary legs")
     ap.add_argument("--cpu-queries", type=int, default=0, help="0 = 2 per core")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def build_knn_input(args, rank, world, device):
@@ -164,6 +174,38 @@ def check_last_step(ix, d, first, nq, k, ids, sims, counts, rec, nsample=16):
             assert np.allclose(est[off[q]:off[q + 1]], oe, rtol=1e-6, atol=0), f"ratings of query {q} differ"
             nrec += 1
     return {"queries": int(len(sample)), "with_ratings": nrec, "ids_and_similarities": "bit-exact", "ratings_rtol": 1e-6}
+
+
+DUMP_BYTES = 60 << 20   # all --dump-outputs files together stay below 64 MB
+
+
+def dump_outputs(out_dir, ids, sims, counts, rec):
+    """What a caller of the timed path receives for the last timed step, as float64 .npy files (person and place ids
+    are below 2**53, so float64 holds them exactly): neighbour ids, similarities and counts per query, and with the
+    aggregation the number of recommendation rows per query plus the rows of 1,024 sampled queries.  Batches beyond
+    the budget are cut to a seeded sample of queries (topk_queries) that depends on the arguments only, so runs with
+    the same arguments (same seeded inputs, same query batches) can be compared file for file."""
+    os.makedirs(out_dir, exist_ok=True)
+    nq, k = ids.shape
+    fit = max(1, DUMP_BYTES // 2 // (8 * (2 * k + 3)))   # per query: k ids, k similarities, count, index, row count
+    q = np.arange(nq) if nq <= fit else np.sort(np.random.default_rng(0x5EED0D01).choice(nq, fit, replace=False))
+    filled = np.arange(k)[None, :] < counts[q, None]   # slots past a query's count hold no result
+    arrays = {"topk_queries": q, "topk_counts": counts[q], "topk_ids": np.where(filled, ids[q], 0),
+              "topk_similarities": np.where(filled, sims[q], 0.0)}
+    if rec is not None:
+        off, places, est = rec
+        arrays["recommend_rows"] = np.diff(off)[q]
+        rq = np.sort(np.random.default_rng(0x5EED0D02).choice(nq, min(nq, 1024), replace=False))
+        left = max(0, DUMP_BYTES - 8 * sum(a.size for a in arrays.values()) - 8 * len(rq)) // 16
+        sel = []
+        for i in rq:
+            m = min(int(off[i + 1] - off[i]), left)
+            sel.append(np.arange(off[i], off[i] + m))
+            left -= m
+        sel = np.concatenate(sel)
+        arrays.update(recommend_queries=rq, recommend_places=places[sel], recommend_ratings=est[sel])
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def secondary_format_leg(pkg, d, args, env, label):
@@ -423,27 +465,31 @@ def main():
     scan_ms, launches = ix.profile_read()
     replayed = ix.replayed_intervals()  # statistics only: handled inside the kernel, nothing is redone later
     plan_name, plan_qt = ix.scan_kernel_name(), ix.query_tile()
-    # read the last step back once (outside the timed region): results exist and are complete
-    last_ids, last_sims, last_counts = ix.fetch_topk(batch, args.k)
-    assert int(last_counts.min()) == min(args.k, n - 1), "a query of the last step has fewer neighbours than K"
+    assert launches == args.steps, (launches, args.steps)
     rec_rows, last_rec = None, None
-    if not args.no_aggregate:
-        last_rec = ix.fetch_recommend(batch)
-        roff, _, rest = last_rec
-        # a weighted mean of ratings 1..5 (up to rounding of sum(r*s) / sum(s))
-        assert np.all(np.diff(roff) > 0), "a query of the last step has no recommendation rows"
-        assert rest.min() >= 1.0 - 1e-9 and rest.max() <= 5.0 + 1e-9, (rest.min(), rest.max())
-        rec_rows = int(roff[-1])
-    # ... and CORRECT: a sample of the last timed step's queries against the oracle (the checker,
+    if args.full or args.dump_outputs:
+        # read the last step back once (outside the timed region): results exist and are complete
+        last_ids, last_sims, last_counts = ix.fetch_topk(batch, args.k)
+        assert int(last_counts.min()) == min(args.k, n - 1), "a query of the last step has fewer neighbours than K"
+        if not args.no_aggregate:
+            last_rec = ix.fetch_recommend(batch)
+            roff, _, rest = last_rec
+            # a weighted mean of ratings 1..5 (up to rounding of sum(r*s) / sum(s))
+            assert np.all(np.diff(roff) > 0), "a query of the last step has no recommendation rows"
+            assert rest.min() >= 1.0 - 1e-9 and rest.max() <= 5.0 + 1e-9, (rest.min(), rest.max())
+            rec_rows = int(roff[-1])
+        # the timed launches were final: reading results back must not have launched another scan
+        _, extra_launches = ix.profile_read()
+        assert extra_launches == 0, extra_launches
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, last_ids, last_sims, last_counts, last_rec)
+    ix.profile_enable(False)
+    # ... and CORRECT (--full): a sample of the last timed step's queries against the oracle (the checker,
     # outside the timed region; rank 0 at N = 1 only, with the cpu_baseline leg)
     # (every CPU leg - this check, the two cpu_baseline figures - runs at the very END of the program: dozens of OpenMP
     # threads on the box's CPU share left the host stalling for tens of milliseconds in the legs that followed them,
     # e.g. one 56 ms step among 21 ms ones in knn_wide_rows, 57 instead of 10.5 ms in knn_large_k_batched)
     oracle_checked = None
-    # the timed launches were final: reading results back must not have launched another scan
-    _, extra_launches = ix.profile_read()
-    ix.profile_enable(False)
-    assert launches == args.steps and extra_launches == 0, (launches, extra_launches)
     dt = max_over_ranks(dt)
     pairs = world * args.steps * batch * (n - 1)
     knn_value = pairs / dt
@@ -486,126 +532,127 @@ def main():
     # (latency figure beside the batched headline; at N > 1 also with the candidate scan split over
     # the ranks, SURVEY.md 8e "latency mode")
     knn_request = None
-    try:
-        pid = int(ix.row_person_ids(n // 2, 1)[0])
-        ix.recommend(pid, 0.5, 0.5, args.k)
-        reqs = 20
-        lat = []
-        for _ in range(reqs):
-            t0 = time.perf_counter()
+    if args.full:
+        try:
+            pid = int(ix.row_person_ids(n // 2, 1)[0])
             ix.recommend(pid, 0.5, 0.5, args.k)
-            lat.append(time.perf_counter() - t0)
-        one = float(np.median(lat))
-        ix.query(pid, 0.5, 0.5, args.k)
-        t0 = time.perf_counter()
-        for _ in range(reqs):
+            reqs = 20
+            lat = []
+            for _ in range(reqs):
+                t0 = time.perf_counter()
+                ix.recommend(pid, 0.5, 0.5, args.k)
+                lat.append(time.perf_counter() - t0)
+            one = float(np.median(lat))
             ix.query(pid, 0.5, 0.5, args.k)
-        one_q = (time.perf_counter() - t0) / reqs
-        # the single-request scan reads every candidate row exactly once: the per-query streaming model
-        # of SURVEY 8d taken literally, so its bandwidth is a plain (not "effective") HBM figure
-        ix.profile_enable(True)
-        for _ in range(reqs):
-            ix.query(pid, 0.5, 0.5, args.k)
-        s1_ms, s1_n = ix.profile_read()
-        ix.profile_enable(False)
-        s1 = s1_ms / max(1, s1_n) * 1e-3
-        knn_request = {"metric": "KnnRecommender.makeRecommendations latency, host buffers in and out",
-                       "ms_per_request": one * 1e3, "pairs_per_s": (n - 1) / one,
-                       "ms_min_max": [min(lat) * 1e3, max(lat) * 1e3], "find_similar_persons_ms": one_q * 1e3,
-                       "scan_roofline": {"bound": "hbm",
-                                         "kernel": "knn_scan1_direct8 (byte tables; knn_scan1 when they do not fit)",
-                                         "avg_launch_ms": s1 * 1e3,
-                                         "achieved": info["scan_bytes"] / s1 / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                         "frac": info["scan_bytes"] / s1 / 1e9 / HBM_PEAK_GBS,
-                                         "traffic": (pmc_record("knn_scan1", persons=n, places=args.places, k=args.k) or {}).get("hbm_bytes"),
-                                         "note": "every candidate row read once per request: real, not effective, bandwidth"}}
-        # the SHIPPED parameter (bin/knn_recommender.sh:35: --k-nearest 2000000 = every person with a
-        # positive similarity is a neighbour): stream scan -> device radix sort of all candidates /
-        # place-major aggregation
-        big_k = 2_000_000
-        ix.recommend(pid, 0.5, 0.5, big_k)
-        lat_big = []
-        for _ in range(5):
-            t0 = time.perf_counter()
-            bp, _be = ix.recommend(pid, 0.5, 0.5, big_k)
-            lat_big.append(time.perf_counter() - t0)
-        ix.query(pid, 0.5, 0.5, big_k)
-        lat_bigq = []
-        for _ in range(5):
-            t0 = time.perf_counter()
-            bi, _bs = ix.query(pid, 0.5, 0.5, big_k)
-            lat_bigq.append(time.perf_counter() - t0)
-        knn_request["large_k"] = {"k_nearest": big_k, "recommend_ms": float(np.median(lat_big)) * 1e3,
-                                  "recommendation_rows": int(len(bp)),
-                                  "find_similar_persons_ms": float(np.median(lat_bigq)) * 1e3,
-                                  "neighbours_returned": int(len(bi)),
-                                  "note": "host buffers in and out; find_similar_persons returns every "
-                                          "positive-similarity person (16 B each over PCIe)"}
-        # The request as the UNCHANGED main issues it (KnnRecommenderMain.scala:53-67): name the region pair's three
-        # Parquet sets, construct a recommender, ask it, forget it.  The constructor takes the device index from the
-        # library's process-wide handle cache, keyed by the files (name + size + mtime; here three stand-in files):
-        # cold = key + miss + locrec_knn_create from the host arrays + the request; warm = key + hit + the request.
-        if rank == 0:
-            import tempfile
-            from locations_recommender_amd import _cache
-            with tempfile.TemporaryDirectory() as td:
-                paths = []
-                for name in ("place_rating_vectors_region0", "category_rating_vectors_region0", "place_ratings_region0"):
-                    paths.append(os.path.join(td, name))
-                    with open(paths[-1], "wb") as f:
-                        f.write(name.encode())
-
-                def through_constructor():
-                    key = _cache.files_key(paths)
-                    h = pkg.KnnIndex.through_cache(key, lambda: pkg.KnnIndex(
-                        d["person_ids"], d["p_rowptr"], d["p_idx"], d["p_val"], d["p_dim"], d["c_rowptr"], d["c_idx"],
-                        d["c_val"], d["c_dim"], d["r_rowptr"], d["r_place"], d["r_rating"]))
-                    with h.lock:
-                        out = h.recommend(pid, 0.5, 0.5, args.k)
-                    h.close()   # drops the reference; the reference's main never even does that
-                    return out
-
-                if not on_device:
-                    st0 = L.cache_stats()
-                    t0 = time.perf_counter()
-                    cp, ce = through_constructor()
-                    cold = time.perf_counter() - t0
-                    through_constructor()
-                    allocs1 = L.device_allocations()
-                    warm = []
-                    for _ in range(50):
-                        t0 = time.perf_counter()
-                        wp, we = through_constructor()
-                        warm.append(time.perf_counter() - t0)
-                    st1 = L.cache_stats()
-                    up, ue = ix.recommend(pid, 0.5, 0.5, args.k)
-                    knn_request["through_constructor"] = {
-                        "cold_ms": cold * 1e3, "warm_ms": float(np.median(warm)) * 1e3,
-                        "warm_over_bare_request": float(np.median(warm)) / one,
-                        "creates": st1["misses"] - st0["misses"], "cache_hits": st1["hits"] - st0["hits"],
-                        "device_allocations_while_warm": L.device_allocations() - allocs1,
-                        "matches_bare_request": bool(np.array_equal(wp, up) and np.array_equal(we, ue) and np.array_equal(cp, up)),
-                        "note": "KnnRecommenderMain.makeRecommendations' per-request body through the handle cache "
-                                "(include/locrec.h); the second index of the same data is destroyed again below"}
-                    _cache.clear()
-        if world > 1:
-            req = shard.ShardedKnnRequest(ix, rank, world)
-            req.recommend(pid, 0.5, 0.5, args.k)
-            barrier()
             t0 = time.perf_counter()
             for _ in range(reqs):
-                places, est = req.recommend(pid, 0.5, 0.5, args.k)
-            sharded = max_over_ranks((time.perf_counter() - t0) / reqs)
-            up, ue = ix.recommend(pid, 0.5, 0.5, args.k)
-            knn_request["candidate_sharded"] = {"ms_per_request": sharded * 1e3, "shards": world,
-                                                "matches_unsharded": bool(np.array_equal(places, up) and np.array_equal(est, ue))}
-    except Exception as e:  # the headline line must still be printed
-        knn_request = {"error": f"{type(e).__name__}: {e}"}
+                ix.query(pid, 0.5, 0.5, args.k)
+            one_q = (time.perf_counter() - t0) / reqs
+            # the single-request scan reads every candidate row exactly once: the per-query streaming model
+            # of SURVEY 8d taken literally, so its bandwidth is a plain (not "effective") HBM figure
+            ix.profile_enable(True)
+            for _ in range(reqs):
+                ix.query(pid, 0.5, 0.5, args.k)
+            s1_ms, s1_n = ix.profile_read()
+            ix.profile_enable(False)
+            s1 = s1_ms / max(1, s1_n) * 1e-3
+            knn_request = {"metric": "KnnRecommender.makeRecommendations latency, host buffers in and out",
+                           "ms_per_request": one * 1e3, "pairs_per_s": (n - 1) / one,
+                           "ms_min_max": [min(lat) * 1e3, max(lat) * 1e3], "find_similar_persons_ms": one_q * 1e3,
+                           "scan_roofline": {"bound": "hbm",
+                                             "kernel": "knn_scan1_direct8 (byte tables; knn_scan1 when they do not fit)",
+                                             "avg_launch_ms": s1 * 1e3,
+                                             "achieved": info["scan_bytes"] / s1 / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                             "frac": info["scan_bytes"] / s1 / 1e9 / HBM_PEAK_GBS,
+                                             "traffic": (pmc_record("knn_scan1", persons=n, places=args.places, k=args.k) or {}).get("hbm_bytes"),
+                                             "note": "every candidate row read once per request: real, not effective, bandwidth"}}
+            # the SHIPPED parameter (bin/knn_recommender.sh:35: --k-nearest 2000000 = every person with a
+            # positive similarity is a neighbour): stream scan -> device radix sort of all candidates /
+            # place-major aggregation
+            big_k = 2_000_000
+            ix.recommend(pid, 0.5, 0.5, big_k)
+            lat_big = []
+            for _ in range(5):
+                t0 = time.perf_counter()
+                bp, _be = ix.recommend(pid, 0.5, 0.5, big_k)
+                lat_big.append(time.perf_counter() - t0)
+            ix.query(pid, 0.5, 0.5, big_k)
+            lat_bigq = []
+            for _ in range(5):
+                t0 = time.perf_counter()
+                bi, _bs = ix.query(pid, 0.5, 0.5, big_k)
+                lat_bigq.append(time.perf_counter() - t0)
+            knn_request["large_k"] = {"k_nearest": big_k, "recommend_ms": float(np.median(lat_big)) * 1e3,
+                                      "recommendation_rows": int(len(bp)),
+                                      "find_similar_persons_ms": float(np.median(lat_bigq)) * 1e3,
+                                      "neighbours_returned": int(len(bi)),
+                                      "note": "host buffers in and out; find_similar_persons returns every "
+                                              "positive-similarity person (16 B each over PCIe)"}
+            # The request as the UNCHANGED main issues it (KnnRecommenderMain.scala:53-67): name the region pair's three
+            # Parquet sets, construct a recommender, ask it, forget it.  The constructor takes the device index from the
+            # library's process-wide handle cache, keyed by the files (name + size + mtime; here three stand-in files):
+            # cold = key + miss + locrec_knn_create from the host arrays + the request; warm = key + hit + the request.
+            if rank == 0:
+                import tempfile
+                from locations_recommender_amd import _cache
+                with tempfile.TemporaryDirectory() as td:
+                    paths = []
+                    for name in ("place_rating_vectors_region0", "category_rating_vectors_region0", "place_ratings_region0"):
+                        paths.append(os.path.join(td, name))
+                        with open(paths[-1], "wb") as f:
+                            f.write(name.encode())
+
+                    def through_constructor():
+                        key = _cache.files_key(paths)
+                        h = pkg.KnnIndex.through_cache(key, lambda: pkg.KnnIndex(
+                            d["person_ids"], d["p_rowptr"], d["p_idx"], d["p_val"], d["p_dim"], d["c_rowptr"], d["c_idx"],
+                            d["c_val"], d["c_dim"], d["r_rowptr"], d["r_place"], d["r_rating"]))
+                        with h.lock:
+                            out = h.recommend(pid, 0.5, 0.5, args.k)
+                        h.close()   # drops the reference; the reference's main never even does that
+                        return out
+
+                    if not on_device:
+                        st0 = L.cache_stats()
+                        t0 = time.perf_counter()
+                        cp, ce = through_constructor()
+                        cold = time.perf_counter() - t0
+                        through_constructor()
+                        allocs1 = L.device_allocations()
+                        warm = []
+                        for _ in range(50):
+                            t0 = time.perf_counter()
+                            wp, we = through_constructor()
+                            warm.append(time.perf_counter() - t0)
+                        st1 = L.cache_stats()
+                        up, ue = ix.recommend(pid, 0.5, 0.5, args.k)
+                        knn_request["through_constructor"] = {
+                            "cold_ms": cold * 1e3, "warm_ms": float(np.median(warm)) * 1e3,
+                            "warm_over_bare_request": float(np.median(warm)) / one,
+                            "creates": st1["misses"] - st0["misses"], "cache_hits": st1["hits"] - st0["hits"],
+                            "device_allocations_while_warm": L.device_allocations() - allocs1,
+                            "matches_bare_request": bool(np.array_equal(wp, up) and np.array_equal(we, ue) and np.array_equal(cp, up)),
+                            "note": "KnnRecommenderMain.makeRecommendations' per-request body through the handle cache "
+                                    "(include/locrec.h); the second index of the same data is destroyed again below"}
+                        _cache.clear()
+            if world > 1:
+                req = shard.ShardedKnnRequest(ix, rank, world)
+                req.recommend(pid, 0.5, 0.5, args.k)
+                barrier()
+                t0 = time.perf_counter()
+                for _ in range(reqs):
+                    places, est = req.recommend(pid, 0.5, 0.5, args.k)
+                sharded = max_over_ranks((time.perf_counter() - t0) / reqs)
+                up, ue = ix.recommend(pid, 0.5, 0.5, args.k)
+                knn_request["candidate_sharded"] = {"ms_per_request": sharded * 1e3, "shards": world,
+                                                    "matches_unsharded": bool(np.array_equal(places, up) and np.array_equal(est, ue))}
+        except Exception as e:  # the headline line must still be printed
+            knn_request = {"error": f"{type(e).__name__}: {e}"}
 
     # ---------------- SG (second figure of the metric) ----------------
     sg_out = None
     sg_cpu_inputs = None
-    if not args.no_sg:
+    if args.full and not args.no_sg:
         from locations_recommender_amd import synth
         g = synth.sg_dataset(seed=0x5EED0003 + rank)  # one independent graph per rank (cfg5's natural form)
         t0 = time.perf_counter()
@@ -726,7 +773,7 @@ def main():
 
     # ---------------- host-inclusive and large-K legs (rank 0) ----------------
     host_incl, large_k_batched = None, None
-    if rank == 0 and not on_device:
+    if args.full and rank == 0 and not on_device:
         try:
             import ctypes as C
             first = shard.query_batch_of(args.warmup, rank, world, nbatches) * batch
@@ -797,7 +844,7 @@ def main():
     cpu = None
     # the other two stored formats, so that the headline's dependence on PACK16 is visible
     formats = None
-    if rank == 0 and world == 1 and not args.no_formats:
+    if args.full and rank == 0 and world == 1 and not args.no_formats:
         formats = []
         for env, label in (({"LOCREC_KNN_NO_PACK16": "1"}, "PACK32 (u32 dots)"),
                            ({"LOCREC_KNN_FORCE_GENERIC": "1"}, "GENERIC (fp64 values, the reference's width)")):
@@ -808,7 +855,7 @@ def main():
     # the same step on an index with 0.1 % WIDE rows (a count of 300: does not fit the head / tail element's byte): the
     # per-row format fallback keeps the head / tail kernel and scores the wide rows from the plain CSR
     wide_leg = None
-    if rank == 0 and world == 1 and not args.no_formats and not on_device:
+    if args.full and rank == 0 and world == 1 and not args.no_formats and not on_device:
         try:
             rng_w = np.random.default_rng(77)
             wide = np.sort(rng_w.choice(n, max(1, n // 1000), replace=False))
@@ -838,16 +885,13 @@ def main():
         except Exception as e:  # the headline line must still be printed
             wide_leg = {"error": f"{type(e).__name__}: {e}"}
     # ---------------- the CPU legs, after every GPU leg ----------------
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         last_b = shard.query_batch_of(args.warmup + args.steps - 1, rank, world, nbatches)
         oracle_checked = check_last_step(ix, d, last_b * batch, batch, args.k, last_ids, last_sims, last_counts, last_rec)
         cpu = cpu_baseline_knn(d, args)
         if sg_out is not None and sg_cpu_inputs is not None:
             sg_out["cpu_baseline"] = cpu_baseline_sg(sg_cpu_inputs[0], sg_cpu_inputs[1], args)
     ix.close()
-    import shutil
-    spark = "unavailable on this host" if not (shutil.which("spark-submit") and shutil.which("java")) else \
-        "present but not run: the reference jar is not part of this repository"
 
     if rank == 0:
         out = {
@@ -863,10 +907,15 @@ def main():
                        "recommendation_rows_last_step": rec_rows,
                        "scan_launches": launches, "device_allocations_in_timed_region": allocs_timed, "flush_intervals_replayed_in_kernel": replayed,
                        "create_s": create_s, "checked_against_oracle": oracle_checked},
-            "roofline": roofline, "cpu_baseline": cpu, "spark": spark, "knn_request": knn_request,
-            "knn_host_inclusive": host_incl, "knn_large_k_batched": large_k_batched,
-            "knn_other_formats": formats, "knn_wide_rows": wide_leg, "sg": sg_out,
+            "roofline": roofline,
         }
+        if args.full:
+            import shutil
+            spark = "unavailable on this host" if not (shutil.which("spark-submit") and shutil.which("java")) else \
+                "present but not run: the reference jar is not part of this repository"
+            out.update({"cpu_baseline": cpu, "spark": spark, "knn_request": knn_request,
+                        "knn_host_inclusive": host_incl, "knn_large_k_batched": large_k_batched,
+                        "knn_other_formats": formats, "knn_wide_rows": wide_leg, "sg": sg_out})
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.destroy_process_group()

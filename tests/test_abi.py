@@ -3,6 +3,8 @@ include/locrec.h declares, and refuses to compute without a GPU (no CPU fallback
 import ctypes as C
 import os
 import re
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -49,7 +51,23 @@ def test_device_allocation_counter_is_readable_without_a_gpu(pkg):
 
 
 def test_no_cpu_fallback_without_gpu(pkg):
-    """The product path must fail loudly when the device is missing."""
+    """The product path must fail loudly when the device is missing.  Where a GPU is present the same checks run in a
+    fresh process that sees none (HIP_VISIBLE_DEVICES=-1 is no valid ordinal, so HIP enumerates no device)."""
+    if not HAVE_GPU:
+        refuses_without_gpu(pkg)
+        return
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
+    code = ("import sys; sys.path[:0] = [sys.argv[1], sys.argv[2]]; import __graft_entry__ as g, test_abi; "
+            "test_abi.refuses_without_gpu(g.load_package())")
+    r = subprocess.run([sys.executable, "-c", code, ROOT, os.path.dirname(os.path.abspath(__file__))], env=env,
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+
+
+def refuses_without_gpu(pkg):
+    n = C.c_int32(-1)
+    pkg.lib().locrec_device_count(C.byref(n))
+    assert n.value == 0, "a device is visible: this is not the no-GPU case"
     from locations_recommender_amd import synth
     d = synth.small_knn_dataset(n=20, p_dim=30, seed=1)
     with pytest.raises(pkg.LocrecRuntimeError):

@@ -1,14 +1,14 @@
 #!/bin/bash
 # full -m gpu suite, then the bench (no cpu leg) - the usual check after a kernel change
 cd "$GRAFT_REPO_ROOT" || exit 1
-mkdir -p gpurun_out; export TMPDIR=/tmp
-timeout -k 10 900 python -m pytest tests -m gpu -x -q --durations=8 > gpurun_out/pytest_gpu.log 2>&1; rc=$?
-tail -n 16 gpurun_out/pytest_gpu.log
+: "${OUT:?set OUT to the output directory}"; mkdir -p "$OUT"; export TMPDIR=/tmp
+timeout -k 10 900 python -m pytest tests -m gpu -x -q --durations=8 > $OUT/pytest_gpu.log 2>&1; rc=$?
+tail -n 16 $OUT/pytest_gpu.log
 [ $rc -ne 0 ] && exit $rc
-timeout -k 10 500 python bench.py --no-cpu --steps 3 > gpurun_out/bench_quick.log 2> gpurun_out/bench_quick.err; rc=$?
+timeout -k 10 500 python bench.py --full --no-cpu --steps 3 > $OUT/bench_quick.log 2> $OUT/bench_quick.err; rc=$?
 python - <<'PY'
-import json
-for line in open("gpurun_out/bench_quick.log"):
+import json, os
+for line in open(os.environ["OUT"] + "/bench_quick.log"):
     if line.startswith("{"):
         d = json.loads(line); r = d["knn_request"]; sg = d.get("sg") or {}
         print("KNN G pairs/s", round(d["value"] / 1e9, 1), "step ms", round(d["ms_per_step"], 2), "scan ms", round(d["roofline"]["avg_launch_ms"], 2),

@@ -5,7 +5,7 @@ mkdir -p gpurun_out/r3b; export TMPDIR=/tmp
 O=gpurun_out/r3b
 timeout -k 10 700 python -m pytest tests -x -q -m gpu > $O/tests.log 2>&1; rc=$?
 tail -8 $O/tests.log; [ $rc -ne 0 ] && exit $rc
-timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err; rc=$?
+timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err; rc=$?
 tail -3 $O/bench.err; python - <<'PY'
 import json
 d=json.load(open("gpurun_out/r3b/bench.json"))

@@ -1,8 +1,8 @@
 #!/bin/bash
 cd "$GRAFT_REPO_ROOT" || exit 1
-mkdir -p gpurun_out
-timeout -k 10 800 python bench.py --no-cpu "$@" > gpurun_out/bench_env.log 2>&1
-echo "rc=$?"; tail -n 1 gpurun_out/bench_env.log | python -c "
+: "${OUT:?set OUT to the output directory}"; mkdir -p "$OUT"
+timeout -k 10 800 python bench.py --full --no-cpu "$@" > $OUT/bench_env.log 2>&1
+echo "rc=$?"; tail -n 1 $OUT/bench_env.log | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 print('knn', d['value'] / 1e9, 'G pairs/s; request', d['knn_request'])

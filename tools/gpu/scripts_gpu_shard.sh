@@ -10,4 +10,4 @@ run() {
 }
 run 400 t_sg.log python -m pytest tests/test_gpu_sg.py -x -q -m gpu
 run 300 rccl1.log python tools/rccl_one_rank.py
-LOCREC_BENCH_BACKEND=gloo run 600 bench_mp.log python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 2 --warmup 1 --persons 200000 --batch 8192 --no-cpu
+LOCREC_BENCH_BACKEND=gloo run 600 bench_mp.log python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 2 --steps 2 --warmup 1 --persons 200000 --batch 8192 --no-cpu

@@ -1,10 +1,10 @@
 #!/bin/bash
 cd "$GRAFT_REPO_ROOT" || exit 1
-mkdir -p gpurun_out; export TMPDIR=/tmp
-rm -rf gpurun_out/prof_tr
-timeout -k 10 600 rocprofv3 --kernel-trace --output-format csv -d gpurun_out/prof_tr -- python bench.py --no-cpu --no-sg --steps 2 > gpurun_out/prof_tr.log 2>&1
+: "${OUT:?set OUT to the output directory}"; mkdir -p "$OUT"; export TMPDIR=/tmp
+rm -rf $OUT/prof_tr
+timeout -k 10 600 rocprofv3 --kernel-trace --output-format csv -d $OUT/prof_tr -- python bench.py --full --no-cpu --no-sg --steps 2 > $OUT/prof_tr.log 2>&1
 echo "rc=$?"
-f=$(find gpurun_out/prof_tr -name "*kernel_trace.csv" | head -1)
+f=$(find $OUT/prof_tr -name "*kernel_trace.csv" | head -1)
 python - "$f" 2>&1 <<'PY'
 import csv, sys, collections
 agg = collections.defaultdict(list)
@@ -17,4 +17,4 @@ for k, v in sorted(agg.items()):
     if k[0] != "other":
         print(k, "n", len(v), "avg us", sum(v) / len(v) / 1e3, "min", min(v) / 1e3, "max", max(v) / 1e3)
 PY
-find gpurun_out/prof_tr -name "*kernel_trace.csv" -delete
+find $OUT/prof_tr -name "*kernel_trace.csv" -delete
