@@ -360,6 +360,26 @@ int32_t locrec_sg_recommend(
     int64_t *out_ids, double *out_probabilities, int64_t *inout_count,
     int64_t *out_iterations, int32_t *out_converged);
 
+/*
+ * makeRecommendations (StochasticRecommender.scala:66-141) for n_targets vertices of ONE graph.
+ * Rows of target i are [out_offsets[i], out_offsets[i+1]) of out_ids / out_probabilities, with the same
+ * rows, order and values locrec_sg_recommend returns for that vertex alone; out_offsets has n_targets + 1
+ * entries, out_iterations / out_converged n_targets (either may be NULL).
+ * *inout_capacity: in = room in the two row arrays, out = rows needed; when the room is too small only
+ * out_offsets (and the counters) are filled and the call is repeated with larger arrays.
+ * Every id is checked before any device work (LOCREC_E_NOT_FOUND, "No such vertex in the graph: <id>",
+ * nothing written); a repeated id is computed once.  Up to 16 distinct targets share each sweep of the
+ * graph; each stops at its own isConverged, and every result equals the single request's bit for bit.
+ * Afterwards the handle serves single requests exactly as before.  Refused (LOCREC_E_INVALID_ARG) on
+ * sharded handles and on handles created under the fused or persistent experiment
+ * (LOCREC_SG_FUSED / LOCREC_SG_PERSIST); every other switch is served.
+ */
+int32_t locrec_sg_recommend_batch(
+    locrec_sg_graph *graph, int64_t n_targets, const int64_t *vertex_ids,
+    double alpha, double epsilon, int64_t max_iterations,
+    int64_t *out_offsets, int64_t *out_ids, double *out_probabilities, int64_t *inout_capacity,
+    int64_t *out_iterations, int32_t *out_converged);
+
 /* Device-resident form (bench.py): enqueue the iteration, read back later. */
 int32_t locrec_sg_iterate_async(
     locrec_sg_graph *graph, int64_t vertex_id,

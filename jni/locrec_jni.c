@@ -411,6 +411,60 @@ JNIEXPORT jlong JNICALL JNI_FN(sgRecommend)(JNIEnv *env, jobject self, jlong han
     return st == LOCREC_OK ? (jlong)count : 0;
 }
 
+/* sgRecommendBatch(handle, vertexIds, alpha, epsilon, maxIterations, outOffsets[n + 1], outIds, outProbabilities,
+ * outIterationsConverged[2 n]): Long = rows needed.  Rows of vertex i are [outOffsets(i), outOffsets(i + 1));
+ * outIterationsConverged(2 i) = its 0-based iteration counter, (2 i + 1) = 1 if converged.  outIds / outProbabilities
+ * null or too short: only outOffsets and outIterationsConverged are filled - call again with room for the return value. */
+JNIEXPORT jlong JNICALL JNI_FN(sgRecommendBatch)(JNIEnv *env, jobject self, jlong handle, jlongArray vertexIds, jdouble alpha,
+                                                 jdouble epsilon, jlong maxIterations, jlongArray outOffsets, jlongArray outIds,
+                                                 jdoubleArray outProbabilities, jlongArray outIterationsConverged)
+{
+    (void)self;
+    if (!handle || !vertexIds || !outOffsets || !outIterationsConverged) return iae(env, "null handle or array");
+    const int64_t n = alen(env, vertexIds);
+    if (alen(env, outOffsets) < n + 1) return iae(env, "outOffsets needs vertexIds.length + 1 entries");
+    if (alen(env, outIterationsConverged) < 2 * n) return iae(env, "outIterationsConverged needs 2 * vertexIds.length entries");
+    int64_t cap = 0;
+    if (outIds && outProbabilities) {
+        const int64_t c1 = alen(env, outIds), c2 = alen(env, outProbabilities);
+        cap = c1 < c2 ? c1 : c2;
+    }
+    const int64_t room = cap;
+    bufs b = {{0}, 0};
+    int32_t st = LOCREC_E_OOM;
+    int64_t *v = in_longs(env, &b, vertexIds, n);
+    int64_t *off = v ? (int64_t *)buf_new(env, &b, n + 1, sizeof *off) : NULL;
+    int64_t *its = off ? (int64_t *)buf_new(env, &b, n, sizeof *its) : NULL;
+    int32_t *conv = its ? (int32_t *)buf_new(env, &b, n, sizeof *conv) : NULL;
+    int64_t *ids = conv && room ? (int64_t *)buf_new(env, &b, room, sizeof *ids) : NULL;
+    double *pr = ids ? (double *)buf_new(env, &b, room, sizeof *pr) : NULL;
+    if (conv && (!room || pr)) {
+        st = locrec_sg_recommend_batch((locrec_sg_graph *)(intptr_t)handle, n, v, alpha, epsilon, (int64_t)maxIterations, off, ids,
+                                       pr, &cap, its, conv);
+        if (st != LOCREC_OK) {
+            throw_status(env, st);
+        } else {
+            out_longs(env, outOffsets, off, n + 1);
+            int64_t *ic = (int64_t *)buf_new(env, &b, 2 * n, sizeof *ic);
+            if (ic) {
+                for (int64_t i = 0; i < n; ++i) {
+                    ic[2 * i] = its[i];
+                    ic[2 * i + 1] = conv[i];
+                }
+                out_longs(env, outIterationsConverged, ic, 2 * n);
+            } else {
+                st = LOCREC_E_OOM;
+            }
+            if (room && cap <= room) { /* the rows were written */
+                out_longs(env, outIds, ids, cap);
+                out_doubles(env, outProbabilities, pr, cap);
+            }
+        }
+    }
+    bufs_free(&b);
+    return st == LOCREC_OK ? (jlong)cap : 0;
+}
+
 /* ----------------------------------------------------------------- misc */
 
 JNIEXPORT jstring JNICALL JNI_FN(version)(JNIEnv *env, jobject self)

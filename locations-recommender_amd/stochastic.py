@@ -66,6 +66,30 @@ class SgGraph:
         self.iterate_async(vertex_id, alpha, epsilon, max_iterations)
         return self.fetch()
 
+    def recommend_batch(self, vertex_ids, alpha, epsilon, max_iterations):
+        """makeRecommendations for many vertices of this graph (locrec_sg_recommend_batch):
+        (offsets[n + 1], ids, probabilities, iterations[n], converged[n]); rows of vertex i are
+        offsets[i]:offsets[i + 1], each exactly what recommend() returns for that vertex."""
+        v = L.as_i64(vertex_ids)
+        off = np.zeros(len(v) + 1, np.int64)
+        its, conv = np.zeros(len(v), np.int64), np.zeros(len(v), np.int32)
+        # room for what one call can return (a target has at most its live vertices once a sweep ran, all vertices
+        # before), up to a bound: the retry below sizes anything larger
+        per = self.info()["vertices"] if int(max_iterations) == 0 else self.live_count()
+        room = min(len(v) * max(1, per), 1 << 24)
+        cap = C.c_int64(room)
+        ids, probs = np.empty(room, np.int64), np.empty(room, np.float64)
+        for _ in range(2):  # a call whose room is too small sizes the result, the second fills it
+            L.check(L.lib().locrec_sg_recommend_batch(self._h, len(v), L.ptr(v, C.c_int64), float(alpha), float(epsilon),
+                                                      int(max_iterations), L.ptr(off, C.c_int64), L.ptr(ids, C.c_int64),
+                                                      L.ptr(probs, C.c_double), C.byref(cap), L.ptr(its, C.c_int64),
+                                                      L.ptr(conv, C.c_int32)))
+            if cap.value <= len(ids):
+                break
+            ids, probs = np.empty(cap.value, np.int64), np.empty(cap.value, np.float64)
+            cap = C.c_int64(len(ids))
+        return off, ids[:off[-1]], probs[:off[-1]], its, conv.astype(bool)
+
     def iterate_async(self, vertex_id, alpha, epsilon, max_iterations):
         L.check(L.lib().locrec_sg_iterate_async(self._h, int(vertex_id), float(alpha), float(epsilon),
                                                 int(max_iterations)))
@@ -186,3 +210,18 @@ class StochasticRecommender:
             else:
                 print(f"Number of iterations {iterations} reached the maximum {self.maxIterations}")
         return pd.DataFrame({"id": ids, "probability": probs})
+
+    def makeRecommendationsBatch(self, vertexIds):
+        """Additive: makeRecommendations for many vertices of this graph in shared sweeps ->
+        (vertex_id, id, probability); the rows of each vertex are exactly makeRecommendations' rows."""
+        import pandas as pd
+        v = L.as_i64(vertexIds)
+        with self._graph.lock:
+            off, ids, probs, iterations, converged = self._graph.recommend_batch(v, ALPHA, self.epsilon, self.maxIterations)
+        if not self.quiet:  # step()'s line (:94,100) for every vertex, in input order
+            for it, conv in zip(iterations, converged):
+                if conv:
+                    print(f"Converged in {it} iterations")
+                else:
+                    print(f"Number of iterations {it} reached the maximum {self.maxIterations}")
+        return pd.DataFrame({"vertex_id": np.repeat(v, np.diff(off)), "id": ids, "probability": probs})

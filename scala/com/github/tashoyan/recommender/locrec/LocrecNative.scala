@@ -96,6 +96,15 @@ object LocrecNative {
       outIds: Array[Long], outProbabilities: Array[Double], outIterationsConverged: Array[Long]
   ): Long
 
+  /** makeRecommendations for many vertices of one graph (shared sweeps); returns the rows needed.
+    * Rows of vertex i are [outOffsets(i), outOffsets(i + 1)) of outIds / outProbabilities;
+    * outIterationsConverged(2 i) = its 0-based counter, (2 i + 1) = 1 if converged.  With outIds /
+    * outProbabilities null or too short only outOffsets and outIterationsConverged are filled. */
+  @native def sgRecommendBatch(
+      handle: Long, vertexIds: Array[Long], alpha: Double, epsilon: Double, maxIterations: Long,
+      outOffsets: Array[Long], outIds: Array[Long], outProbabilities: Array[Double], outIterationsConverged: Array[Long]
+  ): Long
+
   /** One graph with its rows sharded over several devices; byTarget = rows of P^T, all-gather, bit-identical to one device. */
   @native def sgShardedCreate(deviceIds: Array[Int], sourceIds: Array[Long], targetIds: Array[Long], balancedWeights: Array[Double], byTarget: Boolean): Long
 

@@ -74,6 +74,31 @@ class StochasticRecommender(
     spark.createDataFrame(spark.sparkContext.parallelize(rows, 1), outputSchema)
   }
 
+  /** Additive: makeRecommendations for many vertices of this graph in shared sweeps -> (vertex_id, id, probability);
+    * the rows of each vertex are exactly makeRecommendations' rows, and step()'s line is printed per vertex in input order. */
+  def makeRecommendationsBatch(vertexIds: Seq[Long]): DataFrame = LocrecBackend.lockOf(handle).synchronized {
+    require(!LocrecBackend.useSpark, "makeRecommendationsBatch exists only in the gpu backend")
+    val ids = vertexIds.toArray
+    val offsets = new Array[Long](ids.length + 1)
+    val iterationsConverged = new Array[Long](2 * ids.length)
+    // throws IllegalArgumentException(s"No such vertex in the graph: $vertexId") exactly as :70, before any work
+    val needed = LocrecNative.sgRecommendBatch(handle, ids, alpha, epsilon, maxIterations.toLong, offsets, null, null, iterationsConverged)
+    val out = new Array[Long](math.max(needed, 1L).toInt)
+    val probabilities = new Array[Double](out.length)
+    LocrecNative.sgRecommendBatch(handle, ids, alpha, epsilon, maxIterations.toLong, offsets, out, probabilities, iterationsConverged)
+    ids.indices.foreach { q =>
+      if (iterationsConverged(2 * q + 1) != 0L)
+        Console.out.println(s"Converged in ${iterationsConverged(2 * q)} iterations")
+      else
+        Console.out.println(s"Number of iterations ${iterationsConverged(2 * q)} reached the maximum $maxIterations")
+    }
+    val rows = ids.indices.flatMap { q =>
+      (offsets(q).toInt until offsets(q + 1).toInt).map(i => Row(ids(q), out(i), probabilities(i)))
+    }
+    val schema = StructType(StructField("vertex_id", LongType, nullable = false) +: outputSchema.fields)
+    spark.createDataFrame(spark.sparkContext.parallelize(rows, 1), schema)
+  }
+
   /** Drops this object's reference (idempotent); the device graph stays cached for the next constructor. */
   override def close(): Unit = if (!LocrecBackend.useSpark) cleanable.clean()
 
