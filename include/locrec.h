@@ -220,7 +220,6 @@ int32_t locrec_knn_recommend(
  * out_place_ids / out_estimated_ratings, ordered by place id; out_offsets has nq + 1 entries.
  * *inout_capacity: in = room in the two output arrays, out = rows needed; when the room is too
  * small only out_offsets is filled and the call is repeated with larger arrays.
- * k_nearest <= LOCREC_KNN_BATCH_MAX_K.
  */
 int32_t locrec_knn_recommend_batch(
     locrec_knn_index *index, int64_t nq, const int64_t *person_ids,
@@ -243,8 +242,8 @@ int32_t locrec_knn_fetch_recommend(
  *     all-gather of the local lists   by the caller (K * 16 bytes per GPU), merge by
  *                                     (similarity desc, person_id asc) -> the K nearest
  *     locrec_knn_recommend_neighbours makeRecommendations0 (:51-70) for that list, on any one GPU
- * k_nearest is limited to LOCREC_KNN_BATCH_MAX_K here.  The union over all shards of the local
- * lists contains the unsharded answer, so the merged result is identical to locrec_knn_query's.
+ * The union over all shards of the local lists contains the unsharded answer, so the merged
+ * result is identical to locrec_knn_query's.
  * locrec_knn_recommend_neighbours rejects a neighbour id that is listed twice (LOCREC_E_INVALID_ARG).
  */
 int32_t locrec_knn_query_shard(
@@ -260,8 +259,12 @@ int32_t locrec_knn_recommend_neighbours(
 /*
  * Batched findSimilarPersons: the additive "all-pairs" surface.
  * out_person_ids / out_similarities are [nq * k_nearest] row-major, padded with
- * id -1 / similarity 0.0; out_counts[nq] is the number of valid entries.
- * Requires k_nearest <= LOCREC_KNN_BATCH_MAX_K.
+ * id -1 / similarity 0.0; out_counts[nq] is the number of valid entries (at most
+ * min(k_nearest, N - 1)).
+ * LOCREC_KNN_BATCH_MAX_K is the largest K the per-query LDS lists of a batch serve.  A larger K
+ * takes the tiled top-K (tiles of 16 queries, the candidates at or above each query's deciding
+ * similarity sorted on the device) with identical results; the synchronous forms work through the
+ * queries in chunks whose device result arrays stay within 2 GiB.
  */
 #define LOCREC_KNN_BATCH_MAX_K 1024
 int32_t locrec_knn_query_batch(
@@ -286,7 +289,8 @@ int32_t locrec_knn_all_pairs_topk(
  * Kernels are enqueued on the handle's stream and the result stays in HBM until
  * locrec_knn_fetch_topk().  locrec_knn_row_person_ids() names the persons.
  * Rows that are not valid queries (an empty place or category vector) get count -1, as above;
- * the batched aggregation gives them zero recommendation rows.
+ * the batched aggregation gives them zero recommendation rows.  Beyond LOCREC_KNN_BATCH_MAX_K the
+ * whole range's nq x k_nearest result stays resident until the fetch: the caller bounds it by nq.
  */
 int32_t locrec_knn_row_person_ids(locrec_knn_index *index, int64_t first_row, int64_t nq,
                                   int64_t *out_person_ids);

@@ -709,15 +709,13 @@ static void lkb_bitmap_of(locrec_knn_index *ix, uint32_t **bits, uint32_t *mask)
     *mask = nbits - 1u;
 }
 
-int32_t knn_large_recommend_batch(locrec_knn_index *ix, const int32_t *rows, int64_t nq, double pw, double cw)
+// the workspaces of a batched recommendation (grow-only, kept with the handle)
+static int32_t lkb_reserve(locrec_knn_index *ix, int tiles)
 {
     hipStream_t s = ix->stream;
     const int32_t n = (int32_t)ix->n;
     const int32_t np = (int32_t)ix->cplace_ids.size();
-    ix->have_lkb = false;
-    ix->lkb_off.assign((size_t)nq + 1, 0);
     LOCREC_TRY(ensure_segments(ix));
-    const int tiles = std::max(1, (np + kFinishTile - 1) / kFinishTile);
     LOCREC_TRY(ix->lkb_S.reserve((size_t)n * kLkbQt));
     if (!ix->lkb_qd_p.p) {
         LOCREC_TRY(ix->lkb_qd_p.alloc((size_t)std::max(1, ix->fp.dim) * kLkbQt + kLkbBitmapBits / 64));  // (+ the presence bitmap)
@@ -731,6 +729,74 @@ int32_t knn_large_recommend_batch(locrec_knn_index *ix, const int32_t *rows, int
     LOCREC_TRY(ix->lkb_ws.reserve((size_t)std::max(1, np) * kLkbQt));
     LOCREC_TRY(ix->lkb_ss.reserve((size_t)std::max(1, np) * kLkbQt));
     LOCREC_TRY(ix->lkb_tile_cnt.reserve((size_t)tiles * kLkbQt));
+    return LOCREC_OK;
+}
+
+// The place-major aggregation of one tile: S row-major [row][kLkbQt], column t = the weights of query q0 + t (0 = not a
+// neighbour); qrow[t] < 0 marks a slot that is not a valid query.  Appends the tile's rows behind `total` in
+// ix->lkb_place / lkb_est and sets their offsets in ix->lkb_off.
+static int32_t lkb_aggregate_tile(locrec_knn_index *ix, const double *S, const int32_t *qrow, int64_t q0, int nt, int tiles,
+                                  std::vector<int32_t> &tc, int64_t &total)
+{
+    hipStream_t s = ix->stream;
+    const int32_t np = (int32_t)ix->cplace_ids.size();
+    if (np > 0) {
+        if (ix->lk_nsegs > 0)
+            hipLaunchKernelGGL(lkb_aggregate_segments, dim3((unsigned)((ix->lk_nsegs + 3) / 4)), dim3(256), 0, s,
+                               ix->lk_seg_begin.p, ix->lk_seg_end.p, ix->lk_nsegs, ix->cp_row.p, ix->cp_rating.p,
+                               S, ix->lkb_seg_ws.p, ix->lkb_seg_ss.p);
+        hipLaunchKernelGGL(lkb_sum_segments, dim3((unsigned)(((int64_t)np * kLkbQt + 255) / 256)), dim3(256), 0, s,
+                           ix->lk_place_seg0.p, np, ix->lkb_seg_ws.p, ix->lkb_seg_ss.p, ix->lkb_ws.p, ix->lkb_ss.p);
+        hipLaunchKernelGGL(lkb_finish_count, dim3((unsigned)tiles, kLkbQt), dim3(256), 0, s, ix->lkb_ss.p, np, tiles,
+                           ix->lkb_tile_cnt.p);
+        LOCREC_HIP_TRY(hipGetLastError());
+        LOCREC_HIP_TRY(hipMemcpyAsync(tc.data(), ix->lkb_tile_cnt.p, tc.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        LOCREC_HIP_TRY(hipStreamSynchronize(s));
+        LkbBases B{};
+        for (int t = 0; t < kLkbQt; ++t) {
+            int64_t c = 0;
+            if (t < nt && qrow[t] >= 0)
+                for (int i = 0; i < tiles; ++i) c += tc[(size_t)t * tiles + i];
+            B.base[t] = t < nt ? total : -1;
+            if (t < nt) {
+                ix->lkb_off[(size_t)(q0 + t)] = total;
+                total += c;
+            }
+        }
+        // grow-only output with headroom: the rows of the tiles emitted so far must survive a growth
+        if ((size_t)total > ix->lkb_place.n) {
+            DevBuf<int64_t> np_buf;
+            DevBuf<double> ne_buf;
+            const size_t want = (size_t)total + (size_t)total / 2 + 1024;
+            LOCREC_TRY(np_buf.alloc(want));
+            LOCREC_TRY(ne_buf.alloc(want));
+            const int64_t keep = ix->lkb_off[(size_t)q0];
+            if (keep > 0) {
+                LOCREC_HIP_TRY(hipMemcpyAsync(np_buf.p, ix->lkb_place.p, (size_t)keep * 8, hipMemcpyDeviceToDevice, s));
+                LOCREC_HIP_TRY(hipMemcpyAsync(ne_buf.p, ix->lkb_est.p, (size_t)keep * 8, hipMemcpyDeviceToDevice, s));
+                LOCREC_HIP_TRY(hipStreamSynchronize(s));
+            }
+            std::swap(ix->lkb_place.p, np_buf.p); std::swap(ix->lkb_place.n, np_buf.n);
+            std::swap(ix->lkb_est.p, ne_buf.p); std::swap(ix->lkb_est.n, ne_buf.n);
+        }
+        hipLaunchKernelGGL(lkb_finish_emit, dim3((unsigned)tiles, kLkbQt), dim3(256), 0, s, ix->lkb_ws.p, ix->lkb_ss.p, np,
+                           tiles, ix->lkb_tile_cnt.p, ix->cplace_dev.p, B, ix->lkb_place.p, ix->lkb_est.p);
+        LOCREC_HIP_TRY(hipGetLastError());
+    } else {
+        for (int t = 0; t < nt; ++t) ix->lkb_off[(size_t)(q0 + t)] = total;
+    }
+    return LOCREC_OK;
+}
+
+int32_t knn_large_recommend_batch(locrec_knn_index *ix, const int32_t *rows, int64_t nq, double pw, double cw)
+{
+    hipStream_t s = ix->stream;
+    const int32_t n = (int32_t)ix->n;
+    const int32_t np = (int32_t)ix->cplace_ids.size();
+    ix->have_lkb = false;
+    ix->lkb_off.assign((size_t)nq + 1, 0);
+    const int tiles = std::max(1, (np + kFinishTile - 1) / kFinishTile);
+    LOCREC_TRY(lkb_reserve(ix, tiles));
     std::vector<int32_t> tc((size_t)tiles * kLkbQt);
     int64_t total = 0;
     for (int64_t q0 = 0; q0 < nq; q0 += kLkbQt) {
@@ -769,51 +835,7 @@ int32_t knn_large_recommend_batch(locrec_knn_index *ix, const int32_t *rows, int
         fp.set = fc.set = 0;  // the dense tables go back to all zero for the next tile
         hipLaunchKernelGGL(lkb_fill, gp, dim3(256), 0, s, fp);
         hipLaunchKernelGGL(lkb_fill, gc, dim3(256), 0, s, fc);
-        if (np > 0) {
-            if (ix->lk_nsegs > 0)
-                hipLaunchKernelGGL(lkb_aggregate_segments, dim3((unsigned)((ix->lk_nsegs + 3) / 4)), dim3(256), 0, s,
-                                   ix->lk_seg_begin.p, ix->lk_seg_end.p, ix->lk_nsegs, ix->cp_row.p, ix->cp_rating.p,
-                                   ix->lkb_S.p, ix->lkb_seg_ws.p, ix->lkb_seg_ss.p);
-            hipLaunchKernelGGL(lkb_sum_segments, dim3((unsigned)(((int64_t)np * kLkbQt + 255) / 256)), dim3(256), 0, s,
-                               ix->lk_place_seg0.p, np, ix->lkb_seg_ws.p, ix->lkb_seg_ss.p, ix->lkb_ws.p, ix->lkb_ss.p);
-            hipLaunchKernelGGL(lkb_finish_count, dim3((unsigned)tiles, kLkbQt), dim3(256), 0, s, ix->lkb_ss.p, np, tiles,
-                               ix->lkb_tile_cnt.p);
-            LOCREC_HIP_TRY(hipGetLastError());
-            LOCREC_HIP_TRY(hipMemcpyAsync(tc.data(), ix->lkb_tile_cnt.p, tc.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            LOCREC_HIP_TRY(hipStreamSynchronize(s));
-            LkbBases B{};
-            for (int t = 0; t < kLkbQt; ++t) {
-                int64_t c = 0;
-                if (t < nt && P.qrow[t] >= 0)
-                    for (int i = 0; i < tiles; ++i) c += tc[(size_t)t * tiles + i];
-                B.base[t] = t < nt ? total : -1;
-                if (t < nt) {
-                    ix->lkb_off[(size_t)(q0 + t)] = total;
-                    total += c;
-                }
-            }
-            // grow-only output with headroom: the rows of the tiles emitted so far must survive a growth
-            if ((size_t)total > ix->lkb_place.n) {
-                DevBuf<int64_t> np_buf;
-                DevBuf<double> ne_buf;
-                const size_t want = (size_t)total + (size_t)total / 2 + 1024;
-                LOCREC_TRY(np_buf.alloc(want));
-                LOCREC_TRY(ne_buf.alloc(want));
-                const int64_t keep = ix->lkb_off[(size_t)q0];
-                if (keep > 0) {
-                    LOCREC_HIP_TRY(hipMemcpyAsync(np_buf.p, ix->lkb_place.p, (size_t)keep * 8, hipMemcpyDeviceToDevice, s));
-                    LOCREC_HIP_TRY(hipMemcpyAsync(ne_buf.p, ix->lkb_est.p, (size_t)keep * 8, hipMemcpyDeviceToDevice, s));
-                    LOCREC_HIP_TRY(hipStreamSynchronize(s));
-                }
-                std::swap(ix->lkb_place.p, np_buf.p); std::swap(ix->lkb_place.n, np_buf.n);
-                std::swap(ix->lkb_est.p, ne_buf.p); std::swap(ix->lkb_est.n, ne_buf.n);
-            }
-            hipLaunchKernelGGL(lkb_finish_emit, dim3((unsigned)tiles, kLkbQt), dim3(256), 0, s, ix->lkb_ws.p, ix->lkb_ss.p, np,
-                               tiles, ix->lkb_tile_cnt.p, ix->cplace_dev.p, B, ix->lkb_place.p, ix->lkb_est.p);
-            LOCREC_HIP_TRY(hipGetLastError());
-        } else {
-            for (int t = 0; t < nt; ++t) ix->lkb_off[(size_t)(q0 + t)] = total;
-        }
+        LOCREC_TRY(lkb_aggregate_tile(ix, ix->lkb_S.p, P.qrow, q0, nt, tiles, tc, total));
     }
     ix->lkb_off[(size_t)nq] = total;
     ix->have_lkb = true;
@@ -889,6 +911,425 @@ int32_t knn_large_tile_hists(locrec_knn_index *ix, int nt, uint32_t *hist, const
     hipLaunchKernelGGL(lkb_column_hist, dim3((unsigned)std::min(512, (n + 255) / 256), (unsigned)nt), dim3(256), 0, s, ix->lkb_S.p, n,
                        hist);
     LOCREC_HIP_TRY(hipGetLastError());
+    return LOCREC_OK;
+}
+
+}  // namespace locrec
+
+// =====================================================================================================
+// Batched top-K at any K (K > LOCREC_KNN_BATCH_MAX_K, beyond the per-query LDS lists; knn_anyk.h).  A tile of up to
+// kLkbQt queries:
+//   knn_large_scan_tile  S[t][row] (transposed: one contiguous column per query, what the selection reads)
+//   lkb_column_hist      one histogram per column, lkt_select the deciding bin b* of each (knn_select1's walk; it also
+//                        reports the population of b*, which sizes the column's segment)
+//   lkt_collect          every candidate with bin(s) >= b* -> its column's segment as (similarity bits, id rank); the
+//                        segments of the tile are laid end to end, sized from the counts read back once per tile
+//   lkt_sort_runs        runs of kLktRun entries sorted in LDS (bitonic), cut to K
+//   lkt_merge_pass       pairs of runs merged in global memory (merge path: every output finds its own split), cut to K,
+//                        until one run per column is left: its first min(K, candidates) entries are the column's top-K
+//   lkt_emit             -> the query's result slot (ids, similarities, rows, count), padded with (-1, 0.0, -1)
+//   lkt_mask_rows        (recommendations) S masked to each column's selected set, written row-major [row][kLkbQt] for
+//                        lkb_aggregate_segments: one 128-byte line per rater, the order of the single request's sums
+// The order is (similarity desc, id rank asc), a total order: the result does not depend on the order in which the
+// collect's atomics fill a segment, and a tie group of any size needs no special case.  No library sort, no host loop
+// over queries.  VGPRs (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): lkt_select 12, lkt_collect 14,
+// lkt_sort_runs 19 (96 KB dynamic LDS), lkt_merge_pass 32, lkt_emit 14, lkt_mask_rows 40; no scratch.
+namespace {
+
+constexpr int kLktRun = 8192;       // entries one block sorts in LDS (12 B each: 96 KB)
+constexpr int kLktThreads = 1024;
+
+struct LktTile {
+    int64_t off[kLkbQt];    // column t's segment in the ping-pong arrays
+    int64_t slot[kLkbQt];   // result slot of column t (lkt_emit), or -1
+    int32_t n[kLkbQt];      // entries of the segment: candidates with bin(s) >= bin[t]
+    int32_t bin[kLkbQt];    // deciding bin b*
+    int32_t m[kLkbQt];      // neighbours: min(K_eff, candidates)
+    int32_t all[kLkbQt];    // every candidate is a neighbour (candidates <= K)
+    int32_t absent[kLkbQt]; // not a valid query: count -1 (the range forms)
+};
+
+// (similarity bits desc, id rank asc): similarities are > 0, so the bit patterns order like the values; the
+// knn_device.h better() order
+__device__ __forceinline__ bool lkt_better(uint64_t ka, uint32_t ra, uint64_t kb, uint32_t rb)
+{
+    return ka > kb || (ka == kb && ra < rb);
+}
+
+// lkb_column_hist's bin
+__device__ __forceinline__ int lkt_bin(double s)
+{
+    const int b = (int)(s * (double)kLkHistBins);
+    return b < kLkHistBins - 1 ? b : kLkHistBins - 1;
+}
+
+// knn_select1 for column blockIdx.x (same walk from the top bin down); sel[t * 8 + ...] = b*, above, total, 0 (the
+// collect counter), the segment size (above + the population of b*, or total when total <= K).  Leaves the histogram
+// zeroed for the next tile.
+__global__ __launch_bounds__(1024) void lkt_select(uint32_t *hist, int64_t K, int32_t *sel)
+{
+    __shared__ uint32_t suf[2][1024];
+    const int t = threadIdx.x;
+    hist += (size_t)blockIdx.x * kLkHistBins;
+    sel += blockIdx.x * 8;
+    constexpr int per = kLkHistBins / 1024;
+    uint32_t mine = 0;
+    for (int i = 0; i < per; ++i) mine += hist[t * per + i];
+    suf[0][t] = mine;
+    __syncthreads();
+    int cur = 0;
+    for (int d = 1; d < 1024; d <<= 1) {
+        suf[cur ^ 1][t] = suf[cur][t] + (t + d < 1024 ? suf[cur][t + d] : 0u);
+        cur ^= 1;
+        __syncthreads();
+    }
+    const uint32_t incl = suf[cur][t];
+    const uint32_t above_me = incl - mine;
+    const uint32_t total = suf[cur][0];
+    if ((int64_t)total <= K) {
+        if (t == 0) {
+            sel[0] = 0;
+            sel[1] = (int32_t)(total - hist[0]);
+            sel[2] = (int32_t)total;
+            sel[4] = (int32_t)total;
+        }
+    } else if ((int64_t)above_me < K && (int64_t)incl >= K) {  // exactly one thread: the K-th value is in its range
+        uint32_t above = above_me;
+        int b = t * per + per - 1;
+        for (; b > t * per; --b) {
+            if ((int64_t)(above + hist[b]) >= K) break;
+            above += hist[b];
+        }
+        sel[0] = b;
+        sel[1] = (int32_t)above;
+        sel[2] = (int32_t)total;
+        sel[4] = (int32_t)(above + hist[b]);
+    }
+    if (t == 0) sel[3] = 0;
+    __syncthreads();
+    for (int i = 0; i < per; ++i) hist[t * per + i] = 0u;
+}
+
+// grid (row blocks, columns): a block takes `per` rows per thread (strided, coalesced), counts its takers, claims their
+// positions with ONE atomic per block and column, then writes them (a second read of its rows); at most a few hundred
+// atomics per column (one per wave put every column's counter - one cache line for the tile - at 1.3 ms per tile)
+__global__ __launch_bounds__(256) void lkt_collect(const double *S, int32_t nrows, int32_t per, const uint32_t *rid,
+                                                   const LktTile T, int32_t *sel, uint64_t *keys, uint32_t *vals)
+{
+    __shared__ int s_wave[4];
+    __shared__ int s_base;
+    const int t = blockIdx.y;
+    const double *col = S + (size_t)t * nrows;
+    const int64_t row0 = (int64_t)blockIdx.x * 256 * per + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int bin = T.bin[t];
+    int c = 0;
+    for (int i = 0; i < per; ++i) {
+        const int64_t row = row0 + (int64_t)i * 256;
+        if (row < nrows) {
+            const double s = col[row];
+            c += s > 0 && lkt_bin(s) >= bin ? 1 : 0;
+        }
+    }
+    int incl = c;  // inclusive scan within the wave, then over the four waves
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int v = __shfl_up(incl, d);
+        if (lane >= d) incl += v;
+    }
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int tot = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+        s_base = tot ? atomicAdd(&sel[t * 8 + 3], tot) : 0;
+    }
+    __syncthreads();
+    if (c == 0) return;
+    int pos = s_base + (incl - c);
+    for (int w = 0; w < wave; ++w) pos += s_wave[w];
+    for (int i = 0; i < per; ++i) {
+        const int64_t row = row0 + (int64_t)i * 256;
+        if (row < nrows) {
+            const double s = col[row];
+            if (s > 0 && lkt_bin(s) >= bin) {
+                if (pos < T.n[t]) {
+                    keys[T.off[t] + pos] = (uint64_t)__double_as_longlong(s);
+                    vals[T.off[t] + pos] = rid[row];
+                }
+                ++pos;
+            }
+        }
+    }
+}
+
+// grid (runs, columns): run blockIdx.x of column t sorted in place, best first; only its first K entries are kept
+__global__ __launch_bounds__(kLktThreads) void lkt_sort_runs(const LktTile T, int64_t K, uint64_t *keys, uint32_t *vals)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    uint64_t *sk = reinterpret_cast<uint64_t *>(smem);
+    uint32_t *sr = reinterpret_cast<uint32_t *>(sk + kLktRun);
+    const int t = blockIdx.y;
+    const int64_t b0 = (int64_t)blockIdx.x * kLktRun;
+    const int len = (int)std::min<int64_t>(kLktRun, (int64_t)T.n[t] - b0);
+    if (len <= 0) return;  // (block-uniform)
+    int n2 = 2;
+    while (n2 < len) n2 <<= 1;
+    uint64_t *gk = keys + T.off[t] + b0;
+    uint32_t *gr = vals + T.off[t] + b0;
+    for (int i = threadIdx.x; i < n2; i += blockDim.x) {
+        sk[i] = i < len ? gk[i] : 0ull;           // (padding sorts behind every candidate: s > 0)
+        sr[i] = i < len ? gr[i] : 0xFFFFFFFFu;
+    }
+    __syncthreads();
+    for (int k = 2; k <= n2; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int u = threadIdx.x; u < (n2 >> 1); u += blockDim.x) {
+                const int i = 2 * u - (u & (j - 1));
+                const int l = i + j;
+                const bool first_better = (i & k) == 0;
+                const uint64_t ki = sk[i], kl = sk[l];
+                const uint32_t ri = sr[i], rl = sr[l];
+                if (lkt_better(kl, rl, ki, ri) == first_better) {
+                    sk[i] = kl; sk[l] = ki;
+                    sr[i] = rl; sr[l] = ri;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    const int keep = (int)std::min<int64_t>(len, K);
+    for (int i = threadIdx.x; i < keep; i += blockDim.x) {
+        gk[i] = sk[i];
+        gr[i] = sr[i];
+    }
+}
+
+// One merge pass: runs of R entries (each holding min(K, its entries) sorted) pairwise into runs of 2R at the first
+// run's place, cut to K.  Thread = output position d of a pair: it finds how many of the first d outputs come from the
+// first run (binary search along the merge path), then writes the better of the two heads.  grid (outputs, columns).
+__global__ __launch_bounds__(256) void lkt_merge_pass(const LktTile T, int64_t K, int64_t R, const uint64_t *ik,
+                                                      const uint32_t *ir, uint64_t *ok, uint32_t *orr)
+{
+    const int t = blockIdx.y;
+    const int64_t n = T.n[t];
+    const int64_t full = std::min<int64_t>(K, 2 * R);  // outputs of a pair whose runs are both full
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t pair = g / full, d = g - pair * full;
+    const int64_t base = pair * 2 * R;
+    if (base >= n) return;
+    const int64_t na = std::min<int64_t>(K, std::min<int64_t>(R, n - base));
+    const int64_t nb = std::min<int64_t>(K, std::max<int64_t>(0, std::min<int64_t>(R, n - base - R)));
+    if (d >= std::min<int64_t>(K, na + nb)) return;
+    const uint64_t *ak = ik + T.off[t] + base, *bk = ak + R;
+    const uint32_t *ar = ir + T.off[t] + base, *br = ar + R;
+    int64_t lo = std::max<int64_t>(0, d - nb), hi = std::min<int64_t>(d, na);
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (lkt_better(ak[mid], ar[mid], bk[d - 1 - mid], br[d - 1 - mid])) lo = mid + 1;
+        else hi = mid;
+    }
+    const int64_t a = lo, b = d - lo;
+    const bool from_a = a < na && (b >= nb || lkt_better(ak[a], ar[a], bk[b], br[b]));
+    ok[T.off[t] + base + d] = from_a ? ak[a] : bk[b];
+    orr[T.off[t] + base + d] = from_a ? ar[a] : br[b];
+}
+
+// grid (positions of a slot, columns): the column's neighbours into result slot T.slot[t] (stride k), the rest padded
+__global__ __launch_bounds__(256) void lkt_emit(const LktTile T, int64_t k, const uint64_t *keys, const uint32_t *vals,
+                                                const int64_t *ids_by_rank, const int32_t *row_of_rid, int64_t *out_ids,
+                                                double *out_sims, int32_t *out_rows, int64_t *out_cnt)
+{
+    const int t = blockIdx.y;
+    const int64_t slot = T.slot[t];
+    if (slot < 0) return;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) out_cnt[slot] = T.absent[t] ? -1 : T.m[t];
+    if (i >= k) return;
+    const int64_t o = slot * k + i;
+    if (i < T.m[t]) {
+        const uint32_t rr = vals[T.off[t] + i];
+        out_ids[o] = ids_by_rank[rr];
+        out_sims[o] = __longlong_as_double((long long)keys[T.off[t] + i]);
+        out_rows[o] = row_of_rid[rr];
+    } else {
+        out_ids[o] = -1;
+        out_sims[o] = 0.0;
+        out_rows[o] = -1;
+    }
+}
+
+// SR[row][t] = ST[t][row] when (s, rank) is better than or equal to column t's K-th entry (every candidate when the
+// column has no more than K), else 0: the weights of the single request's lk_scatter_weights, per column
+__global__ __launch_bounds__(256) void lkt_mask_rows(const double *ST, int32_t nrows, const uint32_t *rid, const LktTile T,
+                                                     int64_t K, const uint64_t *keys, const uint32_t *vals, double *SR)
+{
+    const int row = blockIdx.x * 256 + threadIdx.x;
+    if (row >= nrows) return;
+    const uint32_t r = rid[row];
+    double w[kLkbQt];
+#pragma unroll
+    for (int t = 0; t < kLkbQt; ++t) {
+        const double s = ST[(size_t)t * nrows + row];
+        bool keep = s > 0;
+        if (keep && !T.all[t]) {
+            const int64_t c = T.off[t] + K - 1;  // the K-th entry of the column's sorted run
+            keep = !lkt_better(keys[c], vals[c], (uint64_t)__double_as_longlong(s), r);
+        }
+        w[t] = keep ? s : 0.0;
+    }
+#pragma unroll
+    for (int t = 0; t < kLkbQt; ++t) SR[(size_t)row * kLkbQt + t] = w[t];
+}
+
+}  // namespace
+
+namespace locrec {
+
+// the per-column workspaces of a tile, as enqueue_topk (knn.hip) allocates them for its special queries: histograms
+// and selection records are left clean by every selection
+static int32_t lkt_tile_workspaces(locrec_knn_index *ix)
+{
+    hipStream_t s = ix->stream;
+    if (!ix->tile_hist.p) {
+        LOCREC_TRY(ix->tile_hist.alloc((size_t)16 * kLkHistBins));
+        LOCREC_TRY(ix->tile_sel.alloc(16 * 8));
+        LOCREC_TRY(ix->tile_list_s.alloc((size_t)16 * 8192));
+        LOCREC_TRY(ix->tile_list_r.alloc((size_t)16 * 8192));
+        LOCREC_TRY(ix->tile_slots.alloc(16));
+        LOCREC_TRY(ix->tile_ovf.alloc(16));
+        LOCREC_HIP_TRY(hipMemsetAsync(ix->tile_hist.p, 0, ix->tile_hist.bytes(), s));
+        LOCREC_HIP_TRY(hipMemsetAsync(ix->tile_sel.p, 0, ix->tile_sel.bytes(), s));
+    }
+    LOCREC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(lkt_sort_runs), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       kLktRun * 12));
+    return LOCREC_OK;
+}
+
+// The top-K of the nt columns of the tile knn_large_scan_tile just left in ix->lkb_S: selection, collect, sort, merge.
+// On return column t's first min(K, candidates) entries lie sorted at T.off[t] of *keys / *vals.
+static int32_t lkt_topk_tile(locrec_knn_index *ix, int nt, int64_t K, LktTile &T, const uint64_t **keys, const uint32_t **vals)
+{
+    hipStream_t s = ix->stream;
+    const int32_t n = (int32_t)ix->n;
+    const double *cols = nullptr;
+    LOCREC_TRY(knn_large_tile_hists(ix, nt, ix->tile_hist.p, &cols));
+    hipLaunchKernelGGL(lkt_select, dim3((unsigned)nt), dim3(1024), 0, s, ix->tile_hist.p, K, ix->tile_sel.p);
+    LOCREC_HIP_TRY(hipGetLastError());
+    int32_t sel[kLkbQt * 8];
+    LOCREC_HIP_TRY(hipMemcpyAsync(sel, ix->tile_sel.p, (size_t)nt * 8 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    int64_t total = 0, most = 0;
+    for (int t = 0; t < kLkbQt; ++t) {
+        const bool live = t < nt;
+        T.off[t] = total;
+        T.n[t] = live ? sel[t * 8 + 4] : 0;
+        T.bin[t] = live ? sel[t * 8 + 0] : kLkHistBins;
+        const int64_t cand = live ? sel[t * 8 + 2] : 0;
+        T.m[t] = (int32_t)std::min<int64_t>(K, cand);
+        T.all[t] = cand <= K ? 1 : 0;
+        total += T.n[t];
+        most = std::max<int64_t>(most, T.n[t]);
+    }
+    LOCREC_TRY(ix->lk_keys.reserve((size_t)std::max<int64_t>(1, total)));
+    LOCREC_TRY(ix->lk_vals.reserve((size_t)std::max<int64_t>(1, total)));
+    LOCREC_TRY(ix->lk_keys_out.reserve((size_t)std::max<int64_t>(1, total)));
+    LOCREC_TRY(ix->lk_vals_out.reserve((size_t)std::max<int64_t>(1, total)));
+    uint64_t *k0 = ix->lk_keys.p, *k1 = ix->lk_keys_out.p;
+    uint32_t *v0 = ix->lk_vals.p, *v1 = ix->lk_vals_out.p;
+    if (most > 0) {
+        const int32_t per = std::max<int32_t>(16, (int32_t)(((int64_t)n + 256 * 256 - 1) / (256 * 256)));  // <= ~256 blocks a column
+        const int64_t cblocks = ((int64_t)n + 256 * per - 1) / (256 * per);
+        hipLaunchKernelGGL(lkt_collect, dim3((unsigned)cblocks, (unsigned)nt), dim3(256), 0, s, cols, n, per, ix->rid.p, T,
+                           ix->tile_sel.p, k0, v0);
+        hipLaunchKernelGGL(lkt_sort_runs, dim3((unsigned)((most + kLktRun - 1) / kLktRun), (unsigned)nt), dim3(kLktThreads),
+                           (size_t)kLktRun * 12, s, T, K, k0, v0);
+        for (int64_t R = kLktRun; R < most; R *= 2) {
+            const int64_t full = std::min<int64_t>(K, 2 * R);
+            const int64_t outs = (most + 2 * R - 1) / (2 * R) * full;
+            hipLaunchKernelGGL(lkt_merge_pass, dim3((unsigned)((outs + 255) / 256), (unsigned)nt), dim3(256), 0, s, T, K, R, k0, v0,
+                               k1, v1);
+            std::swap(k0, k1);
+            std::swap(v0, v1);
+        }
+    }
+    LOCREC_HIP_TRY(hipGetLastError());
+    *keys = k0;
+    *vals = v0;
+    return LOCREC_OK;
+}
+
+// the up to kLkbQt query rows of a tile; a person without a place or category vector is no query (-1)
+static int lkt_tile_rows(const locrec_knn_index *ix, const int32_t *rows, int64_t nq, int64_t q0, int32_t *tr, bool *invalid)
+{
+    const int nt = (int)std::min<int64_t>(kLkbQt, nq - q0);
+    for (int t = 0; t < kLkbQt; ++t) {
+        const int32_t r = t < nt ? rows[q0 + t] : -1;
+        invalid[t] = t < nt && (r < 0 || ix->fp.nnz[(size_t)r] == 0 || ix->fc.nnz[(size_t)r] == 0);
+        tr[t] = invalid[t] ? -1 : r;
+    }
+    return nt;
+}
+
+int32_t knn_topk_tiled(locrec_knn_index *ix, const int32_t *rows, int64_t nq, double pw, double cw, int64_t k, bool mark_absent)
+{
+    hipStream_t s = ix->stream;
+    const int64_t keff = std::min<int64_t>(k, std::max<int64_t>(1, ix->n - 1));  // (H4)
+    LOCREC_TRY(ix->out_ids.reserve((size_t)(nq * k)));
+    LOCREC_TRY(ix->out_sims.reserve((size_t)(nq * k)));
+    LOCREC_TRY(ix->out_rows.reserve((size_t)(nq * k)));
+    LOCREC_TRY(ix->out_cnt.reserve((size_t)nq));
+    LOCREC_TRY(lkt_tile_workspaces(ix));
+    for (int64_t q0 = 0; q0 < nq; q0 += kLkbQt) {
+        int32_t tr[kLkbQt];
+        bool invalid[kLkbQt];
+        const int nt = lkt_tile_rows(ix, rows, nq, q0, tr, invalid);
+        LOCREC_TRY(knn_large_scan_tile(ix, tr, nt, pw, cw));
+        LktTile T{};
+        const uint64_t *keys = nullptr;
+        const uint32_t *vals = nullptr;
+        LOCREC_TRY(lkt_topk_tile(ix, nt, keff, T, &keys, &vals));
+        for (int t = 0; t < kLkbQt; ++t) {
+            T.slot[t] = t < nt ? q0 + t : -1;
+            T.absent[t] = t < nt && invalid[t] && mark_absent ? 1 : 0;
+        }
+        hipLaunchKernelGGL(lkt_emit, dim3((unsigned)((k + 255) / 256), (unsigned)nt), dim3(256), 0, s, T, k, keys, vals,
+                           ix->ids_by_rank.p, ix->row_of_rid.p, ix->out_ids.p, ix->out_sims.p, ix->out_rows.p, ix->out_cnt.p);
+        LOCREC_HIP_TRY(hipGetLastError());
+    }
+    return LOCREC_OK;
+}
+
+int32_t knn_topk_recommend_batch(locrec_knn_index *ix, const int32_t *rows, int64_t nq, double pw, double cw, int64_t k)
+{
+    hipStream_t s = ix->stream;
+    const int32_t n = (int32_t)ix->n;
+    const int32_t np = (int32_t)ix->cplace_ids.size();
+    ix->have_lkb = false;
+    ix->lkb_off.assign((size_t)nq + 1, 0);
+    const int tiles = std::max(1, (np + kFinishTile - 1) / kFinishTile);
+    LOCREC_TRY(lkb_reserve(ix, tiles));
+    // lkb_S: the transposed tile of the scan, then the masked row-major tile of the aggregation behind it
+    LOCREC_TRY(ix->lkb_S.reserve((size_t)n * kLkbQt * 2));
+    LOCREC_TRY(lkt_tile_workspaces(ix));
+    std::vector<int32_t> tc((size_t)tiles * kLkbQt);
+    int64_t total = 0;
+    for (int64_t q0 = 0; q0 < nq; q0 += kLkbQt) {
+        int32_t tr[kLkbQt];
+        bool invalid[kLkbQt];
+        const int nt = lkt_tile_rows(ix, rows, nq, q0, tr, invalid);
+        LOCREC_TRY(knn_large_scan_tile(ix, tr, nt, pw, cw));
+        LktTile T{};
+        const uint64_t *keys = nullptr;
+        const uint32_t *vals = nullptr;
+        LOCREC_TRY(lkt_topk_tile(ix, nt, k, T, &keys, &vals));
+        double *SR = ix->lkb_S.p + (size_t)n * kLkbQt;
+        hipLaunchKernelGGL(lkt_mask_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ix->lkb_S.p, n, ix->rid.p, T, k,
+                           keys, vals, SR);
+        LOCREC_HIP_TRY(hipGetLastError());
+        LOCREC_TRY(lkb_aggregate_tile(ix, SR, tr, q0, nt, tiles, tc, total));
+    }
+    ix->lkb_off[(size_t)nq] = total;
+    ix->have_lkb = true;
     return LOCREC_OK;
 }
 
