@@ -567,6 +567,47 @@ int32_t locrec_build_balanced_edges(int32_t n_families, const double *betas, con
                                     int64_t *out_target_ids, double *out_balanced_weights);
 
 /*
+ * The counted edge families of the stochastic graph (StochasticGraphBuilderMain.scala:47-66):
+ * PersonLikesPlace.calcPersonLikesPlaceEdges (stochastic/PersonLikesPlace.scala:12-37) with
+ * (person_id, place_id), PersonLikesCategory with (person_id, category_id), CategorySelectedPlace
+ * with (category_id, place_id) as (source, target) columns of the place visits:
+ * count("*") per (source, target) -> SQL rank() by count descending within the source -> keep
+ * rank <= top_n (a tie straddling top_n is kept whole) -> weight = count / (sum of the KEPT counts
+ * of that source), as double / double, so every source's weights sum to 1 up to rounding.
+ * top_n <= 0 keeps nothing.  Rows come back ordered by (source, target) ascending - the same rows
+ * in the same order as locrec_calc_ratings.  The three outputs need room for n rows;
+ * *out_count = rows written.
+ */
+int32_t locrec_calc_count_edges(int64_t n, const int64_t *source_ids, const int64_t *target_ids, int64_t top_n,
+                                int32_t mem, int64_t *out_source_ids, int64_t *out_target_ids, double *out_weights,
+                                int64_t *out_count);
+
+/*
+ * PlaceSimilarPlace.calcPlaceSimilarPlaceEdges (stochastic/PlaceSimilarPlace.scala:18-63): every
+ * ORDERED pair of visit rows (a, b) of one person with place[a] != place[b] and
+ * |timestamp[a] - timestamp[b]| <= interval counts once for (place[a], place[b]) - count("person_id")
+ * counts row pairs, not distinct persons, and both (a, b) and (b, a) are pairs; then rank / keep /
+ * normalise per source place exactly as locrec_calc_count_edges does.  `interval` is in the unit of
+ * the timestamps (the reference: 7 days in milliseconds, :13-14,27); a negative interval or
+ * top_n <= 0 gives no rows.  The difference of any two timestamps must fit in int64.  Pair counts
+ * are 64-bit.  The candidate pairs are produced and reduced in chunks of at most
+ * LOCREC_PREP_PAIR_BUDGET (default 2^28) pairs, so device memory stays bounded however dense the
+ * visits are; the result does not depend on the budget.  Rows ordered by (source, target)
+ * ascending.  *inout_count: capacity in, rows the result HAS out (may exceed the capacity, then
+ * only the first `capacity` rows are written; call with 0 to size the buffers).
+ */
+int32_t locrec_calc_similar_place_edges(int64_t n, const int64_t *person_ids, const int64_t *place_ids,
+                                        const int64_t *timestamps, int64_t interval, int64_t top_n, int32_t mem,
+                                        int64_t *out_source_ids, int64_t *out_target_ids, double *out_weights,
+                                        int64_t *inout_count);
+
+/* What this thread's last locrec_calc_similar_place_edges did (measurement): candidate pairs produced,
+ * chunks they were produced in, and HIP-event milliseconds of its sort / pair-emission / merge-and-rank
+ * phases.  Every pointer may be NULL. */
+int32_t locrec_similar_place_edges_stats(int64_t *out_pairs, int64_t *out_chunks, double *out_sort_ms,
+                                         double *out_emit_ms, double *out_merge_ms);
+
+/*
  * PlaceVisits.calcPlaceVisits (PlaceVisits.scala:11-46): location visits with timestamp >=
  * visits_from (:24) joined with the places of the same region_id (:31) and kept where
  * Location.distanceMeters (Location.scala:30-38, haversine on a 6371 km sphere) <= max_meters

@@ -87,6 +87,17 @@ inline hipError_t run_length_encode(void *temp, size_t &bytes, In in, size_t n, 
     return rocprim::run_length_encode(temp, bytes, in, (unsigned int)n, unique_out, counts_out, runs_out, s);
 }
 
+// sums of the values of every run of equal keys (in the values' type), the first key of every run, the number of runs
+template <class Keys, class Values, class UniqueOut, class SumsOut, class RunsOut>
+inline hipError_t sum_by_key(void *temp, size_t &bytes, Keys keys, Values values, size_t n, UniqueOut unique_out, SumsOut sums_out,
+                             RunsOut runs_out, hipStream_t s)
+{
+    using K = typename std::iterator_traits<Keys>::value_type;
+    using V = typename std::iterator_traits<Values>::value_type;
+    return rocprim::reduce_by_key(temp, bytes, keys, values, n, unique_out, sums_out, runs_out, rocprim::plus<V>(),
+                                  rocprim::equal_to<K>(), s);
+}
+
 template <class T>
 using counting_iterator = rocprim::counting_iterator<T>;
 

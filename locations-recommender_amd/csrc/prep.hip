@@ -4,6 +4,9 @@
 //        RatingVectorsBuilder.calcRatingVectors  knn/RatingVectorsBuilder.scala:10-25,52-84
 //        StochasticGraphBuilder.buildWithBalancedWeights   stochastic/StochasticGraphBuilder.scala:8-28
 //   f-4  PlaceVisits.calcPlaceVisits             PlaceVisits.scala:11-46 (+ Location.scala:7-8,30-43)
+//   between them, StochasticGraphBuilderMain.generateStochasticGraph's four edge families (:47-66):
+//        PersonLikesPlace / PersonLikesCategory / CategorySelectedPlace   stochastic/PersonLikesPlace.scala:12-37
+//        PlaceSimilarPlace.calcPlaceSimilarPlaceEdges                      stochastic/PlaceSimilarPlace.scala:18-63
 //
 // Every function takes either host arrays (copied in and out) or device arrays of the current
 // device (mem = LOCREC_MEM_DEVICE): the device form lets visits -> ratings -> rating vectors ->
@@ -124,7 +127,7 @@ int32_t sort_person_entity(int64_t n, const int64_t *person, const int64_t *enti
     return LOCREC_OK;
 }
 
-// ---- calcRatings ---------------------------------------------------------------------------------
+// ---- calcRatings and the counted edge families -----------------------------------------------------
 
 // flags of the sorted rows: a new (person, entity) group / a new person
 __global__ void pr_group_flags(int64_t n, const int64_t *person, const int64_t *entity, const uint32_t *rows,
@@ -143,23 +146,47 @@ __global__ void pr_group_flags(int64_t n, const int64_t *person, const int64_t *
     pfirst[i] = np ? 1u : 0u;
 }
 
-// per group: its visit count and the key (person rank, count descending)
-__global__ void pr_group_keys(int64_t g, int64_t n, const uint32_t *gstart, const uint32_t *prank_of_pos, uint32_t *cnt,
-                              uint64_t *keys, uint32_t *gid)
+// per group: its visit count and the dense rank of its person (the "source" of the rank step)
+__global__ void pr_group_counts(int64_t g, int64_t n, const uint32_t *gstart, const uint32_t *prank_of_pos, uint64_t *cnt,
+                                uint32_t *srank)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= g) return;
     const uint32_t b = gstart[i];
     const uint32_t e = i + 1 < g ? gstart[i + 1] : (uint32_t)n;
-    const uint32_t c = e - b;
-    cnt[i] = c;
-    keys[i] = ((uint64_t)(prank_of_pos[b] - 1u) << 32) | (uint32_t)(~c);
+    cnt[i] = e - b;
+    srank[i] = prank_of_pos[b] - 1u;
+}
+
+// ---- the rank step every counted family shares: rank() over (partition by source order by count desc) <= topN ----
+// Groups arrive ordered by (source, target) with the source as a non-decreasing u32 rank.  Counts below 2^32 (visit
+// counts: at most n) sort with the source in one 64-bit key; co-visit counts are 64-bit and take two stable passes.
+
+__global__ void pr_rank_keys(int64_t g, const uint32_t *srank, const uint64_t *cnt, uint64_t *keys, uint32_t *gid)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= g) return;
+    keys[i] = ((uint64_t)srank[i] << 32) | (uint32_t)(~(uint32_t)cnt[i]);
     gid[i] = (uint32_t)i;
 }
 
-// over the groups sorted by (person, count desc): position of the person's first group and of the
-// first group of the run of equal counts (as values for two running maxima)
-__global__ void pr_run_marks(int64_t g, const uint64_t *keys, uint32_t *pmark, uint32_t *rmark)
+__global__ void pr_rank_keys_wide(int64_t g, const uint64_t *cnt, uint64_t *keys, uint32_t *gid)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= g) return;
+    keys[i] = ~cnt[i];
+    gid[i] = (uint32_t)i;
+}
+
+__global__ void pr_rank_source_keys(int64_t g, const uint32_t *srank, const uint32_t *gid, uint32_t *keys)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < g) keys[i] = srank[gid[i]];
+}
+
+// over the groups sorted by (source, count desc): position of the source's first group and of the
+// first group of the run of equal counts (as values for two running maxima); from the packed keys ...
+__global__ void pr_run_marks_packed(int64_t g, const uint64_t *keys, uint32_t *pmark, uint32_t *rmark)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= g) return;
@@ -169,8 +196,24 @@ __global__ void pr_run_marks(int64_t g, const uint64_t *keys, uint32_t *pmark, u
     rmark[i] = nr ? (uint32_t)i : 0u;
 }
 
+// ... or, where source and 64-bit count do not fit one key, from the groups themselves
+__global__ void pr_run_marks(int64_t g, const uint32_t *gid, const uint32_t *srank, const uint64_t *cnt, uint32_t *pmark,
+                             uint32_t *rmark)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= g) return;
+    bool np = true, nr = true;
+    if (i > 0) {
+        const uint32_t a = gid[i], b = gid[i - 1];
+        np = srank[a] != srank[b];
+        nr = np || cnt[a] != cnt[b];
+    }
+    pmark[i] = np ? (uint32_t)i : 0u;
+    rmark[i] = nr ? (uint32_t)i : 0u;
+}
+
 // SQL rank() = 1 + rows of the partition sorting strictly before = 1 + (first of the run - first of
-// the person); where(rank <= topN)
+// the source); where(rank <= topN)
 __global__ void pr_keep_top(int64_t g, const uint32_t *pstart, const uint32_t *rstart, const uint32_t *gid, int64_t top_n,
                             uint32_t *keep)
 {
@@ -180,20 +223,88 @@ __global__ void pr_keep_top(int64_t g, const uint32_t *pstart, const uint32_t *r
     keep[gid[i]] = rank <= top_n ? 1u : 0u;
 }
 
+// keep[i] = group i survives the rank filter; pos[i] = its output row; *out_count = rows kept
+int32_t rank_keep(int64_t g, const uint32_t *srank, const uint64_t *cnt, int64_t top_n, bool wide_counts, uint32_t *keep,
+                  uint32_t *pos, int64_t *out_count, Temp &tmp, hipStream_t s)
+{
+    DevBuf<uint32_t> gid0, gid1, pmark, rmark, pstart, rstart;
+    DevBuf<uint64_t> key0, key1;
+    LOCREC_TRY(gid0.alloc((size_t)g));
+    LOCREC_TRY(gid1.alloc((size_t)g));
+    LOCREC_TRY(key0.alloc((size_t)g));
+    LOCREC_TRY(key1.alloc((size_t)g));
+    LOCREC_TRY(pmark.alloc((size_t)g));
+    LOCREC_TRY(rmark.alloc((size_t)g));
+    LOCREC_TRY(pstart.alloc((size_t)g));
+    LOCREC_TRY(rstart.alloc((size_t)g));
+    const uint32_t *sorted = gid1.p;
+    if (!wide_counts) {
+        hipLaunchKernelGGL(pr_rank_keys, grid_for(g), dim3(256), 0, s, g, srank, cnt, key0.p, gid0.p);
+        PR_PRIM(tmp, prim::sort_pairs(p_, bytes_, key0.p, key1.p, gid0.p, gid1.p, (int)g, 0, 64, s));
+    } else {  // stable LSD: by count descending, then by source (pmark / rmark serve as the 32-bit key buffers)
+        hipLaunchKernelGGL(pr_rank_keys_wide, grid_for(g), dim3(256), 0, s, g, cnt, key0.p, gid0.p);
+        PR_PRIM(tmp, prim::sort_pairs(p_, bytes_, key0.p, key1.p, gid0.p, gid1.p, (int)g, 0, 64, s));
+        hipLaunchKernelGGL(pr_rank_source_keys, grid_for(g), dim3(256), 0, s, g, srank, gid1.p, pmark.p);
+        PR_PRIM(tmp, prim::sort_pairs(p_, bytes_, pmark.p, rmark.p, gid1.p, gid0.p, (int)g, 0, 32, s));
+        sorted = gid0.p;
+    }
+    if (!wide_counts)
+        hipLaunchKernelGGL(pr_run_marks_packed, grid_for(g), dim3(256), 0, s, g, key1.p, pmark.p, rmark.p);
+    else
+        hipLaunchKernelGGL(pr_run_marks, grid_for(g), dim3(256), 0, s, g, sorted, srank, cnt, pmark.p, rmark.p);
+    PR_PRIM(tmp, prim::inclusive_max(p_, bytes_, pmark.p, pstart.p, (int)g, s));
+    PR_PRIM(tmp, prim::inclusive_max(p_, bytes_, rmark.p, rstart.p, (int)g, s));
+    hipLaunchKernelGGL(pr_keep_top, grid_for(g), dim3(256), 0, s, g, pstart.p, rstart.p, sorted, top_n, keep);
+    PR_PRIM(tmp, prim::exclusive_sum(p_, bytes_, keep, pos, (int)g, s));
+    uint32_t last_pos = 0, last_keep = 0;
+    LOCREC_HIP_TRY(hipMemcpyAsync(&last_pos, pos + (g - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    LOCREC_HIP_TRY(hipMemcpyAsync(&last_keep, keep + (g - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    *out_count = (int64_t)last_pos + last_keep;
+    return LOCREC_OK;
+}
+
+// groupBy(source).agg(sum(count)) over the KEPT groups (PersonLikesPlace.scala:25-27): totals[source rank]
+__global__ void pr_kept_counts(int64_t g, const uint32_t *keep, const uint64_t *cnt, uint64_t *kept)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < g) kept[i] = keep[i] ? cnt[i] : 0ull;
+}
+
+int32_t kept_totals(int64_t g, const uint32_t *srank, const uint64_t *cnt, const uint32_t *keep, DevBuf<uint64_t> &totals,
+                    Temp &tmp, hipStream_t s)
+{
+    DevBuf<uint64_t> kept;
+    DevBuf<uint32_t> sources, nsources;
+    LOCREC_TRY(kept.alloc((size_t)g));
+    LOCREC_TRY(sources.alloc((size_t)g));
+    LOCREC_TRY(nsources.alloc(1));
+    LOCREC_TRY(totals.alloc((size_t)g));
+    hipLaunchKernelGGL(pr_kept_counts, grid_for(g), dim3(256), 0, s, g, keep, cnt, kept.p);
+    PR_PRIM(tmp, prim::sum_by_key(p_, bytes_, srank, kept.p, (size_t)g, sources.p, totals.p, nsources.p, s));
+    LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (kept / sources are released on return)
+    return LOCREC_OK;
+}
+
+// a kept group's row: calcRatings writes the count (out_rating), the edge families the count over the
+// source's total of kept counts, as double / double (out_weight)
 __global__ void pr_emit_ratings(int64_t g, const uint32_t *keep, const uint32_t *pos, const uint32_t *gstart,
-                                const uint32_t *rows, const int64_t *person, const int64_t *entity, const uint32_t *cnt,
-                                int64_t *out_person, int64_t *out_entity, int64_t *out_rating)
+                                const uint32_t *rows, const int64_t *person, const int64_t *entity, const uint64_t *cnt,
+                                const uint32_t *srank, const uint64_t *totals, int64_t *out_person, int64_t *out_entity,
+                                int64_t *out_rating, double *out_weight)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= g || !keep[i]) return;
     const uint32_t r = rows[gstart[i]], at = pos[i];
     out_person[at] = person[r];
     out_entity[at] = entity[r];
-    out_rating[at] = (int64_t)cnt[i];
+    if (out_rating) out_rating[at] = (int64_t)cnt[i];
+    if (out_weight) out_weight[at] = (double)cnt[i] / (double)totals[srank[i]];
 }
 
+// calcRatings (out_rating) and calcPersonLikesPlaceEdges and its two siblings (out_weight): one body
 int32_t calc_ratings(int64_t n, const int64_t *person, const int64_t *entity, int64_t top_n, int64_t *out_person,
-                     int64_t *out_entity, int64_t *out_rating, int64_t *out_count, hipStream_t s)
+                     int64_t *out_entity, int64_t *out_rating, double *out_weight, int64_t *out_count, hipStream_t s)
 {
     Temp tmp;
     SortedRows S;
@@ -214,33 +325,18 @@ int32_t calc_ratings(int64_t n, const int64_t *person, const int64_t *entity, in
     LOCREC_HIP_TRY(hipStreamSynchronize(s));
     const int64_t g = g32;
 
-    DevBuf<uint32_t> cnt, gid0, gid1, pmark, rmark, pstart, rstart, keep, pos;
-    DevBuf<uint64_t> key0, key1;
+    DevBuf<uint32_t> srank, keep, pos;
+    DevBuf<uint64_t> cnt, totals;
     LOCREC_TRY(cnt.alloc((size_t)g));
-    LOCREC_TRY(gid0.alloc((size_t)g));
-    LOCREC_TRY(gid1.alloc((size_t)g));
-    LOCREC_TRY(key0.alloc((size_t)g));
-    LOCREC_TRY(key1.alloc((size_t)g));
-    LOCREC_TRY(pmark.alloc((size_t)g));
-    LOCREC_TRY(rmark.alloc((size_t)g));
-    LOCREC_TRY(pstart.alloc((size_t)g));
-    LOCREC_TRY(rstart.alloc((size_t)g));
+    LOCREC_TRY(srank.alloc((size_t)g));
     LOCREC_TRY(keep.alloc((size_t)g));
-    LOCREC_TRY(pos.alloc((size_t)g + 1));
-    hipLaunchKernelGGL(pr_group_keys, grid_for(g), dim3(256), 0, s, g, n, gstart.p, prank.p, cnt.p, key0.p, gid0.p);
-    PR_PRIM(tmp, prim::sort_pairs(p_, bytes_, key0.p, key1.p, gid0.p, gid1.p, (int)g, 0, 64, s));
-    hipLaunchKernelGGL(pr_run_marks, grid_for(g), dim3(256), 0, s, g, key1.p, pmark.p, rmark.p);
-    PR_PRIM(tmp, prim::inclusive_max(p_, bytes_, pmark.p, pstart.p, (int)g, s));
-    PR_PRIM(tmp, prim::inclusive_max(p_, bytes_, rmark.p, rstart.p, (int)g, s));
-    hipLaunchKernelGGL(pr_keep_top, grid_for(g), dim3(256), 0, s, g, pstart.p, rstart.p, gid1.p, top_n, keep.p);
-    PR_PRIM(tmp, prim::exclusive_sum(p_, bytes_, keep.p, pos.p, (int)g, s));
+    LOCREC_TRY(pos.alloc((size_t)g));
+    hipLaunchKernelGGL(pr_group_counts, grid_for(g), dim3(256), 0, s, g, n, gstart.p, prank.p, cnt.p, srank.p);
+    LOCREC_TRY(rank_keep(g, srank.p, cnt.p, top_n, false, keep.p, pos.p, out_count, tmp, s));
+    if (out_weight) LOCREC_TRY(kept_totals(g, srank.p, cnt.p, keep.p, totals, tmp, s));
     hipLaunchKernelGGL(pr_emit_ratings, grid_for(g), dim3(256), 0, s, g, keep.p, pos.p, gstart.p, S.rows, person, entity,
-                       cnt.p, out_person, out_entity, out_rating);
-    uint32_t last_pos = 0, last_keep = 0;
-    LOCREC_HIP_TRY(hipMemcpyAsync(&last_pos, pos.p + (g - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    LOCREC_HIP_TRY(hipMemcpyAsync(&last_keep, keep.p + (g - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+                       cnt.p, srank.p, totals.p, out_person, out_entity, out_rating, out_weight);
     LOCREC_HIP_TRY(hipStreamSynchronize(s));
-    *out_count = (int64_t)last_pos + last_keep;
     return LOCREC_OK;
 }
 
@@ -578,7 +674,7 @@ try {
     LOCREC_TRY(op.bind(out_person_ids, n, mem));
     LOCREC_TRY(oe.bind(out_entity_ids, n, mem));
     LOCREC_TRY(orat.bind(out_ratings, n, mem));
-    LOCREC_TRY(calc_ratings(n, p.p, e.p, top_n, op.p, oe.p, orat.p, out_count, s));
+    LOCREC_TRY(calc_ratings(n, p.p, e.p, top_n, op.p, oe.p, orat.p, nullptr, out_count, s));
     LOCREC_TRY(op.deliver(*out_count, s));
     LOCREC_TRY(oe.deliver(*out_count, s));
     LOCREC_TRY(orat.deliver(*out_count, s));
@@ -983,3 +1079,433 @@ try {
     return LOCREC_OK;
 }
 LOCREC_CATCH_ALL
+
+// ---- the stochastic graph's edge families (StochasticGraphBuilderMain.scala:47-66) ----------------
+// PersonLikesPlace / PersonLikesCategory / CategorySelectedPlace are calcRatings' body with a weight;
+// PlaceSimilarPlace is a per-person self-join of the visits within a time interval, counted per ordered
+// place pair and then ranked and normalised per source place in the same way.
+
+extern "C" int32_t locrec_calc_count_edges(int64_t n, const int64_t *source_ids, const int64_t *target_ids, int64_t top_n,
+                                           int32_t mem, int64_t *out_source_ids, int64_t *out_target_ids, double *out_weights,
+                                           int64_t *out_count)
+try {
+    LOCREC_TRY(mem_ok(mem));
+    if (!out_count) return fail(LOCREC_E_INVALID_ARG, "out_count is required");
+    *out_count = 0;
+    if (n < 0 || n >= kMaxRows) return fail(LOCREC_E_INVALID_ARG, "visit count %lld out of range [0, 2^31)", (long long)n);
+    if (n == 0) return LOCREC_OK;
+    if (!source_ids || !target_ids || !out_source_ids || !out_target_ids || !out_weights)
+        return fail(LOCREC_E_INVALID_ARG, "null array");
+    LOCREC_TRY(ensure_device());
+    hipStream_t s = nullptr;
+    In<int64_t> a, b;
+    Out<int64_t> oa, ob;
+    Out<double> ow;
+    LOCREC_TRY(a.bind(source_ids, n, mem, s));
+    LOCREC_TRY(b.bind(target_ids, n, mem, s));
+    LOCREC_TRY(oa.bind(out_source_ids, n, mem));
+    LOCREC_TRY(ob.bind(out_target_ids, n, mem));
+    LOCREC_TRY(ow.bind(out_weights, n, mem));
+    LOCREC_TRY(calc_ratings(n, a.p, b.p, top_n, oa.p, ob.p, nullptr, ow.p, out_count, s));
+    LOCREC_TRY(oa.deliver(*out_count, s));
+    LOCREC_TRY(ob.deliver(*out_count, s));
+    LOCREC_TRY(ow.deliver(*out_count, s));
+    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    return LOCREC_OK;
+}
+LOCREC_CATCH_ALL
+
+namespace {
+
+constexpr int kPairTile = 2048;                       // pair keys one block of pr_covisit_emit writes
+constexpr int64_t kDefaultPairBudget = (int64_t)1 << 28;  // candidate pairs per chunk: 2 GiB of keys
+constexpr int64_t kMaxPairBudget = (int64_t)1 << 30;      // (a chunk's pair count travels as a 32-bit size)
+
+// LOCREC_PREP_PAIR_BUDGET: candidate pairs per chunk of the co-visit join (read once; the result does not depend on it)
+int64_t pair_budget()
+{
+    static const int64_t budget = [] {
+        int64_t b = kDefaultPairBudget;
+        if (const char *e = std::getenv("LOCREC_PREP_PAIR_BUDGET")) b = atoll(e);
+        return std::min(std::max<int64_t>(b, 1), kMaxPairBudget);
+    }();
+    return budget;
+}
+
+// what the last locrec_calc_similar_place_edges of this thread did (locrec_similar_place_edges_stats)
+struct CovisitStats {
+    int64_t pairs = 0, chunks = 0;
+    double ms[3] = {0, 0, 0};  // sort, emit, merge
+};
+thread_local CovisitStats g_covisit_stats;
+
+enum { kPhaseSort = 0, kPhaseEmit = 1, kPhaseMerge = 2, kPhaseEnd = -1 };
+
+// HIP events at the phase changes of one call; read() adds every interval to its phase
+struct PhaseClock {
+    hipStream_t s = nullptr;
+    std::vector<hipEvent_t> ev;
+    std::vector<int> phase;
+    ~PhaseClock()
+    {
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    }
+    int32_t mark(int ph)
+    {
+        hipEvent_t e;
+        LOCREC_HIP_TRY(hipEventCreate(&e));
+        ev.push_back(e);
+        phase.push_back(ph);
+        LOCREC_HIP_TRY(hipEventRecord(e, s));
+        return LOCREC_OK;
+    }
+    int32_t read(double ms[3])
+    {
+        LOCREC_HIP_TRY(hipStreamSynchronize(s));
+        for (size_t i = 0; i + 1 < ev.size(); ++i) {
+            float t = 0;
+            LOCREC_HIP_TRY(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
+            if (phase[i] >= 0) ms[phase[i]] += t;
+        }
+        return LOCREC_OK;
+    }
+};
+
+// the rows in (person, timestamp) order: timestamp and dense place rank of sorted position i
+__global__ void pr_covisit_gather(int64_t n, const uint32_t *rows, const int64_t *place, const int64_t *ts, const uint64_t *uniq,
+                                  int64_t np, int64_t *sorted_ts, uint32_t *sorted_rank)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t r = rows[i];
+    sorted_ts[i] = ts[r];
+    sorted_rank[i] = (uint32_t)lower_bound_key(uniq, np, ordered_key(place[r]));
+}
+
+// The window of sorted row i: the rows [lo, hi] of the same person whose timestamp is within `interval` of row i's
+// (isInPlaceSimilarityIntervalUdf, PlaceSimilarPlace.scala:26-28).  Rows are ordered by (person, timestamp), so both
+// ends are binary searches over a monotone predicate; a difference of two timestamps fits in int64 (locrec.h), so
+// neither subtraction overflows.  width = hi - lo: the partners of row i, itself excluded, same-place rows included.
+__global__ void pr_covisit_windows(int64_t n, const uint64_t *person_keys, const int64_t *ts, int64_t interval, uint32_t *lo_out,
+                                   unsigned long long *width)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t p = person_keys[i];
+    const int64_t t = ts[i];
+    int64_t a = 0, b = i;  // first j in [0, i] that is in the window (i itself is)
+    while (a < b) {
+        const int64_t mid = (a + b) >> 1;
+        if (person_keys[mid] == p && t - ts[mid] <= interval) b = mid; else a = mid + 1;
+    }
+    const int64_t lo = a;
+    a = i;
+    b = n - 1;             // last j in [i, n) that is in the window
+    while (a < b) {
+        const int64_t mid = (a + b + 1) >> 1;
+        if (person_keys[mid] == p && ts[mid] - t <= interval) a = mid; else b = mid - 1;
+    }
+    lo_out[i] = (uint32_t)lo;
+    width[i] = (unsigned long long)(a - lo);
+}
+
+// the last row of the chunk that starts at row r0: the largest r1 in (r0, n] with off[r1] - off[r0] <= budget, and at
+// least r0 + 1 (a row whose own window exceeds the budget is a chunk of its own)
+__global__ void pr_chunk_end(int64_t n, const unsigned long long *off, int64_t r0, unsigned long long budget,
+                             unsigned long long *out)
+{
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const unsigned long long base = off[r0];
+    int64_t a = r0 + 1, b = n;
+    while (a < b) {
+        const int64_t mid = (a + b + 1) >> 1;
+        if (off[mid] - base <= budget) a = mid; else b = mid - 1;
+    }
+    out[0] = (unsigned long long)a;
+    out[1] = off[a] - base;
+}
+
+// The self-join of the rows [r0, r1): pair q of the chunk belongs to the row a with off[a] <= off[r0] + q < off[a + 1]
+// and is that row's (q - off[a])-th partner.  The PAIR index space is what is split evenly: a block writes kPairTile
+// consecutive keys (coalesced 8-byte stores, partners read from consecutive positions), whatever the lengths of the
+// windows; two lanes find the rows of the tile's ends, every thread then searches only between them.
+__global__ __launch_bounds__(256) void pr_covisit_emit(int64_t r0, int64_t r1, const unsigned long long *off, const uint32_t *lo,
+                                                       const uint32_t *rank, int nb, unsigned long long npairs, uint64_t *keys)
+{
+    __shared__ int64_t ends[2];
+    const unsigned long long base = off[r0];
+    const unsigned long long t0 = (unsigned long long)blockIdx.x * kPairTile;
+    const unsigned long long t1 = min(t0 + (unsigned long long)kPairTile, npairs);
+    if (t0 >= t1) return;
+    if (threadIdx.x < 2) {
+        const unsigned long long p = base + (threadIdx.x == 0 ? t0 : t1 - 1);
+        int64_t a = r0, b = r1;  // off[a] <= p < off[b]
+        while (b - a > 1) {
+            const int64_t mid = (a + b) >> 1;
+            if (off[mid] <= p) a = mid; else b = mid;
+        }
+        ends[threadIdx.x] = a;
+    }
+    __syncthreads();
+    const int64_t first = ends[0], last = ends[1];
+    for (unsigned long long q = t0 + threadIdx.x; q < t1; q += blockDim.x) {
+        const unsigned long long p = base + q;
+        int64_t a = first, b = last + 1;
+        while (b - a > 1) {
+            const int64_t mid = (a + b) >> 1;
+            if (off[mid] <= p) a = mid; else b = mid;
+        }
+        int64_t j = (int64_t)lo[a] + (int64_t)(p - off[a]);
+        if (j >= a) ++j;  // the row itself is no partner
+        keys[q] = ((uint64_t)rank[a] << nb) | (uint64_t)rank[j];
+    }
+}
+
+// runs of the chunk's sorted keys: a pair of two different places stays (col("place_id") =!= col("that_place_id"))
+__global__ void pr_pair_flags(int64_t c, const uint64_t *keys, int nb, uint32_t *flag)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < c) flag[i] = (keys[i] >> nb) != (keys[i] & ((1ull << nb) - 1)) ? 1u : 0u;
+}
+
+__global__ void pr_pair_append(int64_t c, const uint64_t *keys, const uint32_t *counts, const uint32_t *flag, const uint32_t *pos,
+                               uint64_t *out_keys, uint64_t *out_counts)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= c || !flag[i]) return;
+    out_keys[pos[i]] = keys[i];
+    out_counts[pos[i]] = counts[i];
+}
+
+// 0 for the first pair of every source place but the first, so that the inclusive sum is the dense source rank
+__global__ void pr_pair_source_steps(int64_t m, const uint64_t *keys, int nb, uint32_t *step)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < m) step[i] = i > 0 && (keys[i] >> nb) != (keys[i - 1] >> nb) ? 1u : 0u;
+}
+
+__global__ void pr_emit_similar(int64_t m, const uint32_t *keep, const uint32_t *pos, const uint64_t *keys, int nb,
+                                const uint64_t *uniq, const uint64_t *cnt, const uint32_t *srank, const uint64_t *totals,
+                                int64_t cap, int64_t *out_source, int64_t *out_target, double *out_weight)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m || !keep[i] || (int64_t)pos[i] >= cap) return;
+    const uint32_t at = pos[i];
+    out_source[at] = (int64_t)(uniq[keys[i] >> nb] ^ 0x8000000000000000ull);
+    out_target[at] = (int64_t)(uniq[keys[i] & ((1ull << nb) - 1)] ^ 0x8000000000000000ull);
+    out_weight[at] = (double)cnt[i] / (double)totals[srank[i]];
+}
+
+// (pair key, count) of every ordered pair of different places co-visited within the interval, keys ascending
+struct PairCounts {
+    DevBuf<uint64_t> keys, counts;
+    int64_t m = 0;
+};
+
+int32_t covisit_counts(int64_t n, const int64_t *person, const int64_t *place, const int64_t *ts, int64_t interval,
+                       DevBuf<uint64_t> &uniq, int *nb_out, PairCounts &R, PhaseClock &clock, CovisitStats &stats, Temp &tmp,
+                       hipStream_t s)
+{
+    LOCREC_TRY(clock.mark(kPhaseSort));
+    // distinct places, ascending: a place's rank is order-preserving, so rank order is id order
+    DevBuf<uint64_t> pk;
+    DevBuf<uint32_t> scratch_rows;
+    DevBuf<int32_t> np_dev;
+    LOCREC_TRY(pk.alloc((size_t)n));
+    LOCREC_TRY(uniq.alloc((size_t)n));
+    LOCREC_TRY(scratch_rows.alloc((size_t)n));
+    LOCREC_TRY(np_dev.alloc(1));
+    hipLaunchKernelGGL(pr_iota_keys, grid_for(n), dim3(256), 0, s, n, place, uniq.p, scratch_rows.p);
+    PR_PRIM(tmp, prim::sort_keys(p_, bytes_, uniq.p, pk.p, (int)n, 0, 64, s));
+    PR_PRIM(tmp, prim::unique(p_, bytes_, pk.p, uniq.p, np_dev.p, (int)n, s));
+    int32_t np = 0;
+    LOCREC_HIP_TRY(hipMemcpyAsync(&np, np_dev.p, sizeof np, hipMemcpyDeviceToHost, s));
+    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    pk.release();
+    scratch_rows.release();
+    if (np < 2) return LOCREC_OK;  // one place: every pair is a same-place pair
+    int nb = 1;
+    while (((int64_t)1 << nb) < np) ++nb;
+    *nb_out = nb;
+
+    SortedRows S;
+    LOCREC_TRY(sort_person_entity(n, person, ts, S, tmp, s));  // S.k1 = the persons' keys in sorted order
+    DevBuf<int64_t> sts;
+    DevBuf<uint32_t> srk, lo;
+    DevBuf<unsigned long long> width, off, chunk_dev;
+    LOCREC_TRY(sts.alloc((size_t)n));
+    LOCREC_TRY(srk.alloc((size_t)n));
+    LOCREC_TRY(lo.alloc((size_t)n));
+    LOCREC_TRY(width.alloc((size_t)n + 1));
+    LOCREC_TRY(off.alloc((size_t)n + 1));
+    LOCREC_TRY(chunk_dev.alloc(2));
+    hipLaunchKernelGGL(pr_covisit_gather, grid_for(n), dim3(256), 0, s, n, S.rows, place, ts, uniq.p, (int64_t)np, sts.p, srk.p);
+    LOCREC_TRY(clock.mark(kPhaseEmit));
+    LOCREC_HIP_TRY(hipMemsetAsync(width.p + n, 0, sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(pr_covisit_windows, grid_for(n), dim3(256), 0, s, n, S.k1.p, sts.p, interval, lo.p, width.p);
+    PR_PRIM(tmp, prim::exclusive_sum(p_, bytes_, width.p, off.p, (size_t)n + 1, s));  // off[n] = all candidate pairs
+    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    S.k0.release();
+    S.r0.release();
+    S.r1.release();
+    width.release();
+
+    const int64_t budget = pair_budget();
+    DevBuf<uint64_t> ka, kb;
+    DevBuf<uint32_t> run_counts, flag, pos, nruns_dev;
+    LOCREC_TRY(nruns_dev.alloc(1));
+    for (int64_t r0 = 0; r0 < n;) {
+        LOCREC_TRY(clock.mark(kPhaseEmit));
+        hipLaunchKernelGGL(pr_chunk_end, dim3(1), dim3(64), 0, s, n, off.p, r0, (unsigned long long)budget, chunk_dev.p);
+        unsigned long long ce[2] = {0, 0};
+        LOCREC_HIP_TRY(hipMemcpyAsync(ce, chunk_dev.p, sizeof ce, hipMemcpyDeviceToHost, s));
+        LOCREC_HIP_TRY(hipStreamSynchronize(s));
+        const int64_t r1 = (int64_t)ce[0], npairs = (int64_t)ce[1];
+        if (npairs == 0) {
+            r0 = r1;
+            continue;
+        }
+        if (npairs >= kMaxRows) return fail(LOCREC_E_INVALID_ARG, "a chunk of %lld candidate pairs: at most 2^31 - 1", (long long)npairs);
+        stats.pairs += npairs;
+        stats.chunks += 1;
+        LOCREC_TRY(ka.reserve((size_t)npairs));
+        LOCREC_TRY(kb.reserve((size_t)npairs));
+        LOCREC_TRY(run_counts.reserve((size_t)npairs));
+        hipLaunchKernelGGL(pr_covisit_emit, grid_for(npairs, kPairTile), dim3(256), 0, s, r0, r1, off.p, lo.p, srk.p, nb,
+                           (unsigned long long)npairs, ka.p);
+        LOCREC_TRY(clock.mark(kPhaseSort));
+        PR_PRIM(tmp, prim::sort_keys(p_, bytes_, ka.p, kb.p, (size_t)npairs, 0, (unsigned)(2 * nb), s));
+        PR_PRIM(tmp, prim::run_length_encode(p_, bytes_, kb.p, (size_t)npairs, ka.p, run_counts.p, nruns_dev.p, s));
+        uint32_t c32 = 0;
+        LOCREC_HIP_TRY(hipMemcpyAsync(&c32, nruns_dev.p, sizeof c32, hipMemcpyDeviceToHost, s));
+        LOCREC_HIP_TRY(hipStreamSynchronize(s));
+        const int64_t c = c32;
+
+        // the runs of two different places, appended to the result so far; sorted and summed per pair if there was one
+        LOCREC_TRY(clock.mark(kPhaseMerge));
+        LOCREC_TRY(flag.reserve((size_t)c));
+        LOCREC_TRY(pos.reserve((size_t)c));
+        hipLaunchKernelGGL(pr_pair_flags, grid_for(c), dim3(256), 0, s, c, ka.p, nb, flag.p);
+        PR_PRIM(tmp, prim::exclusive_sum(p_, bytes_, flag.p, pos.p, (size_t)c, s));
+        uint32_t last_pos = 0, last_flag = 0;
+        LOCREC_HIP_TRY(hipMemcpyAsync(&last_pos, pos.p + (c - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        LOCREC_HIP_TRY(hipMemcpyAsync(&last_flag, flag.p + (c - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        LOCREC_HIP_TRY(hipStreamSynchronize(s));
+        const int64_t add = (int64_t)last_pos + last_flag;
+        r0 = r1;
+        if (add == 0) continue;
+        const int64_t cat = R.m + add;
+        if (cat >= kMaxRows) return fail(LOCREC_E_INVALID_ARG, "%lld distinct place pairs: at most 2^31 - 1", (long long)cat);
+        DevBuf<uint64_t> ck, cc;
+        LOCREC_TRY(ck.alloc((size_t)cat));
+        LOCREC_TRY(cc.alloc((size_t)cat));
+        if (R.m > 0) {
+            LOCREC_HIP_TRY(hipMemcpyAsync(ck.p, R.keys.p, (size_t)R.m * 8, hipMemcpyDeviceToDevice, s));
+            LOCREC_HIP_TRY(hipMemcpyAsync(cc.p, R.counts.p, (size_t)R.m * 8, hipMemcpyDeviceToDevice, s));
+        }
+        hipLaunchKernelGGL(pr_pair_append, grid_for(c), dim3(256), 0, s, c, ka.p, run_counts.p, flag.p, pos.p, ck.p + R.m,
+                           cc.p + R.m);
+        if (R.m == 0) {
+            LOCREC_HIP_TRY(hipStreamSynchronize(s));
+            std::swap(R.keys.p, ck.p);
+            std::swap(R.keys.n, ck.n);
+            std::swap(R.counts.p, cc.p);
+            std::swap(R.counts.n, cc.n);
+            R.m = cat;
+            continue;
+        }
+        DevBuf<uint64_t> sk, sc;
+        LOCREC_TRY(sk.alloc((size_t)cat));
+        LOCREC_TRY(sc.alloc((size_t)cat));
+        PR_PRIM(tmp, prim::sort_pairs(p_, bytes_, ck.p, sk.p, cc.p, sc.p, (size_t)cat, 0, (unsigned)(2 * nb), s));
+        PR_PRIM(tmp, prim::sum_by_key(p_, bytes_, sk.p, sc.p, (size_t)cat, ck.p, cc.p, nruns_dev.p, s));
+        LOCREC_HIP_TRY(hipMemcpyAsync(&c32, nruns_dev.p, sizeof c32, hipMemcpyDeviceToHost, s));
+        LOCREC_HIP_TRY(hipStreamSynchronize(s));
+        std::swap(R.keys.p, ck.p);
+        std::swap(R.keys.n, ck.n);
+        std::swap(R.counts.p, cc.p);
+        std::swap(R.counts.n, cc.n);
+        R.m = c32;
+    }
+    return LOCREC_OK;
+}
+
+}  // namespace
+
+extern "C" int32_t locrec_calc_similar_place_edges(int64_t n, const int64_t *person_ids, const int64_t *place_ids,
+                                                   const int64_t *timestamps, int64_t interval, int64_t top_n, int32_t mem,
+                                                   int64_t *out_source_ids, int64_t *out_target_ids, double *out_weights,
+                                                   int64_t *inout_count)
+try {
+    LOCREC_TRY(mem_ok(mem));
+    if (!inout_count) return fail(LOCREC_E_INVALID_ARG, "inout_count is required");
+    const int64_t cap = *inout_count;
+    *inout_count = 0;
+    g_covisit_stats = CovisitStats();
+    if (cap < 0) return fail(LOCREC_E_INVALID_ARG, "negative capacity");
+    if (n < 0 || n >= kMaxRows) return fail(LOCREC_E_INVALID_ARG, "visit count %lld out of range [0, 2^31)", (long long)n);
+    if (n == 0 || interval < 0 || top_n <= 0) return LOCREC_OK;  // |dt| <= a negative interval never holds; rank >= 1
+    if (!person_ids || !place_ids || !timestamps) return fail(LOCREC_E_INVALID_ARG, "null array");
+    if (cap > 0 && (!out_source_ids || !out_target_ids || !out_weights)) return fail(LOCREC_E_INVALID_ARG, "null output array");
+    LOCREC_TRY(ensure_device());
+    hipStream_t s = nullptr;
+    Temp tmp;
+    In<int64_t> pe, pl, ts;
+    LOCREC_TRY(pe.bind(person_ids, n, mem, s));
+    LOCREC_TRY(pl.bind(place_ids, n, mem, s));
+    LOCREC_TRY(ts.bind(timestamps, n, mem, s));
+
+    PhaseClock clock;
+    clock.s = s;
+    CovisitStats stats;
+    DevBuf<uint64_t> uniq;
+    PairCounts R;
+    int nb = 0;
+    LOCREC_TRY(covisit_counts(n, pe.p, pl.p, ts.p, interval, uniq, &nb, R, clock, stats, tmp, s));
+    const int64_t m = R.m;
+    int64_t total = 0;
+    if (m > 0) {
+        LOCREC_TRY(clock.mark(kPhaseMerge));
+        DevBuf<uint32_t> step, srank, keep, pos;
+        DevBuf<uint64_t> totals;
+        LOCREC_TRY(step.alloc((size_t)m));
+        LOCREC_TRY(srank.alloc((size_t)m));
+        LOCREC_TRY(keep.alloc((size_t)m));
+        LOCREC_TRY(pos.alloc((size_t)m));
+        hipLaunchKernelGGL(pr_pair_source_steps, grid_for(m), dim3(256), 0, s, m, R.keys.p, nb, step.p);
+        PR_PRIM(tmp, prim::inclusive_sum(p_, bytes_, step.p, srank.p, (size_t)m, s));
+        LOCREC_TRY(rank_keep(m, srank.p, R.counts.p, top_n, true, keep.p, pos.p, &total, tmp, s));
+        const int64_t rows = std::min(total, cap);
+        if (rows > 0) {
+            LOCREC_TRY(kept_totals(m, srank.p, R.counts.p, keep.p, totals, tmp, s));
+            Out<int64_t> oa, ob;
+            Out<double> ow;
+            LOCREC_TRY(oa.bind(out_source_ids, rows, mem));
+            LOCREC_TRY(ob.bind(out_target_ids, rows, mem));
+            LOCREC_TRY(ow.bind(out_weights, rows, mem));
+            hipLaunchKernelGGL(pr_emit_similar, grid_for(m), dim3(256), 0, s, m, keep.p, pos.p, R.keys.p, nb, uniq.p, R.counts.p,
+                               srank.p, totals.p, rows, oa.p, ob.p, ow.p);
+            LOCREC_TRY(oa.deliver(rows, s));
+            LOCREC_TRY(ob.deliver(rows, s));
+            LOCREC_TRY(ow.deliver(rows, s));
+            LOCREC_HIP_TRY(hipStreamSynchronize(s));
+        }
+    }
+    LOCREC_TRY(clock.mark(kPhaseEnd));
+    LOCREC_TRY(clock.read(stats.ms));
+    g_covisit_stats = stats;
+    *inout_count = total;
+    return LOCREC_OK;
+}
+LOCREC_CATCH_ALL
+
+extern "C" int32_t locrec_similar_place_edges_stats(int64_t *out_pairs, int64_t *out_chunks, double *out_sort_ms,
+                                                    double *out_emit_ms, double *out_merge_ms)
+{
+    if (out_pairs) *out_pairs = g_covisit_stats.pairs;
+    if (out_chunks) *out_chunks = g_covisit_stats.chunks;
+    if (out_sort_ms) *out_sort_ms = g_covisit_stats.ms[kPhaseSort];
+    if (out_emit_ms) *out_emit_ms = g_covisit_stats.ms[kPhaseEmit];
+    if (out_merge_ms) *out_merge_ms = g_covisit_stats.ms[kPhaseMerge];
+    return LOCREC_OK;
+}

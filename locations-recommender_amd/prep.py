@@ -8,6 +8,12 @@ SURVEY.md 8f rows f-2 and f-4) behind the names of the reference's builder objec
     calc_place_visits            PlaceVisits.calcPlaceVisits              PlaceVisits.scala:11-46
     distance_meters              Location.distanceMeters                  Location.scala:30-38
     rank_recommendations         printRecommendations of both mains       knn/KnnRecommenderMain.scala:90-101
+    calc_person_likes_place_edges / calc_person_likes_category_edges / calc_category_selected_place_edges
+                                 the three counted edge families          stochastic/PersonLikesPlace.scala:12-37 (and siblings)
+    calc_place_similar_place_edges  PlaceSimilarPlace.calcPlaceSimilarPlaceEdges
+                                                                          stochastic/PlaceSimilarPlace.scala:18-63
+    generate_stochastic_graph    StochasticGraphBuilderMain.generateStochasticGraph
+                                                                          stochastic/StochasticGraphBuilderMain.scala:47-66
 
 Every function takes numpy arrays (host in, host out) or torch CUDA tensors (device in, device out:
 nothing passes through the host, and the outputs of calc_rating_vectors go straight into
@@ -22,6 +28,14 @@ from . import _lib as L
 DISTANCE_ACCURACY_METERS = 100.0   # PlaceVisits.scala:127
 VISITED_PLACES_TOP_N = 100         # RatingsBuilder.scala:9
 VISITED_CATEGORIES_TOP_N = 10      # RatingsBuilder.scala:10
+# the stochastic graph's edge families
+LIKED_PLACES_TOP_N = 100           # stochastic/PersonLikesPlace.scala:10
+LIKED_CATEGORIES_TOP_N = 100       # stochastic/PersonLikesCategory.scala:10
+SELECTED_PLACES_TOP_N = 100        # stochastic/CategorySelectedPlace.scala:10
+SIMILAR_PLACES_TOP_N = 50          # stochastic/PlaceSimilarPlace.scala:16
+PLACE_SIMILARITY_INTERVAL_MS = 7 * 86_400_000   # stochastic/PlaceSimilarPlace.scala:13-14
+BETA_PLACE_PLACE = 1.0             # stochastic/StochasticGraphBuilderMain.scala:8
+BETA_CATEGORY_PLACE = 1.0          # stochastic/StochasticGraphBuilderMain.scala:9
 
 
 def _is_tensor(a):
@@ -187,3 +201,99 @@ def knn_index_from_visits(person_ids, place_ids, category_ids, places_top_n=VISI
                                     c_ptr.contiguous(), c_idx.contiguous(), c_val.contiguous(), c_dim,
                                     p_ptr.contiguous(), pe.contiguous(), pr.contiguous())
     return KnnIndex(ids, p_ptr, p_idx, p_val, p_dim, c_ptr, c_idx, c_val, c_dim, p_ptr, pe, pr)
+
+
+# ---- the stochastic graph from place visits (StochasticGraphBuilderMain.scala:47-66) ----------------------
+
+def calc_count_edges(source_ids, target_ids, top_n):
+    """One counted edge family: count per (source, target), SQL rank() by count descending within the
+    source, keep rank <= top_n (ties kept whole), weight = count / the source's total of KEPT counts.
+    -> (source_id, target_id, weight), ordered by (source, target): the rows of calc_ratings, weighted."""
+    c = _Cols(source_ids, target_ids)
+    n = len(source_ids)
+    assert len(target_ids) == n
+    a, b = c.col(source_ids, np.int64), c.col(target_ids, np.int64)
+    (os_, osp), (ot, otp), (ow, owp) = c.out(n, np.int64), c.out(n, np.int64), c.out(n, np.float64)
+    cnt = C.c_int64()
+    L.check(L.lib().locrec_calc_count_edges(n, a, b, int(top_n), c.mem, osp, otp, owp, C.byref(cnt)))
+    m = cnt.value
+    return os_[:m], ot[:m], ow[:m]
+
+
+def calc_similar_place_edges(person_ids, place_ids, timestamps, interval=PLACE_SIMILARITY_INTERVAL_MS,
+                             top_n=SIMILAR_PLACES_TOP_N):
+    """PlaceSimilarPlace.calcPlaceSimilarPlaceEdges: every ordered pair of visit rows of one person at two
+    different places at most `interval` apart (in the timestamps' unit) counts for (place, that place); then
+    rank / keep / normalise per source place as calc_count_edges.  -> (source_id, target_id, weight), ordered
+    by (source, target)."""
+    c = _Cols(person_ids, place_ids, timestamps)
+    n = len(person_ids)
+    assert len(place_ids) == n and len(timestamps) == n
+    cols = [c.col(person_ids, np.int64), c.col(place_ids, np.int64), c.col(timestamps, np.int64)]
+    cap = 1 << 20   # most results fit a first guess; the count says when a second, exact call is needed
+    while True:
+        (os_, osp), (ot, otp), (ow, owp) = c.out(cap, np.int64), c.out(cap, np.int64), c.out(cap, np.float64)
+        cnt = C.c_int64(cap)
+        L.check(L.lib().locrec_calc_similar_place_edges(n, *cols, int(interval), int(top_n), c.mem, osp, otp, owp,
+                                                        C.byref(cnt)))
+        m = cnt.value
+        if m <= cap:
+            return os_[:m], ot[:m], ow[:m]
+        cap = m
+
+
+def similar_place_edges_stats():
+    """What this thread's last calc_similar_place_edges did: candidate pairs, chunks, and HIP-event milliseconds
+    of its sort / emit / merge phases (locrec_similar_place_edges_stats)."""
+    pairs, chunks = C.c_int64(), C.c_int64()
+    ms = [C.c_double() for _ in range(3)]
+    L.check(L.lib().locrec_similar_place_edges_stats(C.byref(pairs), C.byref(chunks), *[C.byref(x) for x in ms]))
+    return dict(pairs=pairs.value, chunks=chunks.value, sort_ms=ms[0].value, emit_ms=ms[1].value, merge_ms=ms[2].value)
+
+
+def _edges(cols):
+    return dict(zip(("source_id", "target_id", "weight"), cols))
+
+
+def calc_person_likes_place_edges(place_visits, top_n=LIKED_PLACES_TOP_N):
+    """PersonLikesPlace.calcPersonLikesPlaceEdges (stochastic/PersonLikesPlace.scala:12-37)."""
+    return _edges(calc_count_edges(place_visits["person_id"], place_visits["place_id"], top_n))
+
+
+def calc_person_likes_category_edges(place_visits, top_n=LIKED_CATEGORIES_TOP_N):
+    """PersonLikesCategory.calcPersonLikesCategoryEdges (stochastic/PersonLikesCategory.scala:12-37)."""
+    return _edges(calc_count_edges(place_visits["person_id"], place_visits["category_id"], top_n))
+
+
+def calc_category_selected_place_edges(place_visits, top_n=SELECTED_PLACES_TOP_N):
+    """CategorySelectedPlace.calcCategorySelectedPlaceEdges (stochastic/CategorySelectedPlace.scala:12-37)."""
+    return _edges(calc_count_edges(place_visits["category_id"], place_visits["place_id"], top_n))
+
+
+def calc_place_similar_place_edges(place_visits, interval=PLACE_SIMILARITY_INTERVAL_MS, top_n=SIMILAR_PLACES_TOP_N):
+    """PlaceSimilarPlace.calcPlaceSimilarPlaceEdges (stochastic/PlaceSimilarPlace.scala:18-63)."""
+    return _edges(calc_similar_place_edges(place_visits["person_id"], place_visits["place_id"], place_visits["timestamp"],
+                                           interval, top_n))
+
+
+def generate_stochastic_graph(place_visits, beta_person_place, beta_person_category):
+    """StochasticGraphBuilderMain.generateStochasticGraph (:47-66): the four edge families of the place visits
+    of one region (or region pair) in the reference's order - place-place, category-place, person-place,
+    person-category - balanced with the betas (1.0, 1.0, beta_person_place, beta_person_category).
+    place_visits: the mapping calc_place_visits returns.  -> (source_id, target_id, balanced_weight); with
+    CUDA tensors nothing passes through the host."""
+    families = [calc_place_similar_place_edges(place_visits), calc_category_selected_place_edges(place_visits),
+                calc_person_likes_place_edges(place_visits), calc_person_likes_category_edges(place_visits)]
+    betas = [BETA_PLACE_PLACE, BETA_CATEGORY_PLACE, float(beta_person_place), float(beta_person_category)]
+    return build_with_balanced_weights(betas, families)
+
+
+def sg_graph_from_visits(place_visits, beta_person_place, beta_person_category):
+    """Place visits -> the four edge families -> balanced edge list -> SgGraph: the SG counterpart of
+    knn_index_from_visits.  The edge list is computed on the device; locrec_sg_create builds its layout on the
+    host, so the list is copied to the host once here (a device-side sg_create is out of scope)."""
+    from .stochastic import SgGraph
+    s, t, w = generate_stochastic_graph(place_visits, beta_person_place, beta_person_category)
+    if _is_tensor(s):
+        s, t, w = s.cpu().numpy(), t.cpu().numpy(), w.cpu().numpy()
+    return SgGraph(s, t, w)
