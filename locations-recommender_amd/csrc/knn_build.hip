@@ -654,7 +654,8 @@ int32_t knn_build_device(int64_t n, const int64_t *ids, const int64_t *p_ptr, co
     std::vector<unsigned char> h_wide;
     int64_t n_wide = 0;
     const bool any_wide = pvmax >= 256.0 || cvmax >= 256.0 || pss >= 65536.0 || css >= 65536.0;
-    if (any_wide && integral && !force_generic && !ix->no_row_fallback && !ix->no_pack16 && !ix->no_ht && n < ((int64_t)1 << 24) && c_dim <= cfg::kHtCatRows) {
+    if (any_wide && integral && !force_generic && !ix->no_row_fallback && !ix->no_pack16 && !ix->no_ht && n < ((int64_t)1 << 24) && c_dim <= cfg::kHtCatRows &&
+        p_dim < (1 << 20) - 1) {  // (a place dimension no packed format holds: GENERIC keeps every row in its image)
         h_wide.resize((size_t)n);
         LOCREC_HIP_TRY(hipMemcpy(h_wide.data(), wide_in.p, (size_t)n, hipMemcpyDeviceToHost));
         for (unsigned char w : h_wide) n_wide += w ? 1 : 0;

@@ -3,6 +3,19 @@
 // A fragment of knn.hip's translation unit: included by knn.hip at file scope, after its helper namespaces.
 #pragma once
 
+// Per-row format fallback (see knn_build.hip): the wide rows are all padding in the packed SELL images.  The image is
+// built from every row (build_family_device) and the wide rows' element groups are blanked afterwards.
+__global__ void knn_host_blank_rows(int32_t nw, const int32_t *wide_rows, const int64_t *sell_off, const int32_t *sell_w, uint32_t *sell)
+{
+    const int w = blockIdx.x;
+    if (w >= nw) return;
+    const int32_t r = wide_rows[w];
+    uint32_t *base = sell + sell_off[r >> 6] + (r & 63) * 4;
+    const int groups = sell_w[r >> 6] / 4;
+    for (int g = threadIdx.x; g < groups; g += blockDim.x)
+        for (int k = 0; k < 4; ++k) base[(int64_t)g * 256 + k] = 0u;
+}
+
 // The index built on the HOST (the first implementation, single-threaded): kept behind
 // LOCREC_KNN_HOST_BUILD=1 as the A/B partner of knn_build.hip's device build (tests/test_gpu_build.py).
 static int32_t knn_create_host(
@@ -39,13 +52,18 @@ static int32_t knn_create_host(
         t_last = now;
     };
     // ---- validation (SparseVector invariants, RatingVectorsBuilder.scala:74-77)
+    // wide_in[r] (OR-ed over both families), lvmax / lssmax (the maxima over the rows that are not wide): as kb_validate
+    std::vector<unsigned char> wide_in((size_t)n, 0);
     auto check_family = [&](const char *name, const int64_t *ptr, const int32_t *idx, const double *val,
-                            int32_t dim, bool &integral, double &vmax, double &ssmax) -> int32_t {
+                            int32_t dim, bool &integral, double &vmax, double &ssmax, double &lvmax, double &lssmax) -> int32_t {
         if (n == 0) return LOCREC_OK;
         if (ptr[0] != 0) return fail(LOCREC_E_INVALID_ARG, "%s rowptr must start at 0", name);
         for (int64_t r = 0; r < n; ++r) {
             if (ptr[r + 1] < ptr[r]) return fail(LOCREC_E_INVALID_ARG, "%s rowptr not monotone at %lld", name, (long long)r);
-            double ss = 0;
+            // (the device build's row-order sort key packs three 21-bit counts: both builds refuse such a row)
+            if (ptr[r + 1] - ptr[r] >= (1 << 21))
+                return fail(LOCREC_E_INVALID_ARG, "%s vector of person %lld has 2^21 or more entries", name, (long long)person_ids[r]);
+            double ss = 0, rvmax = 0;
             for (int64_t e = ptr[r]; e < ptr[r + 1]; ++e) {
                 if (idx[e] < 0 || idx[e] >= dim)
                     return fail(LOCREC_E_INVALID_ARG, "%s index %d out of range [0,%d)", name, idx[e], dim);
@@ -55,20 +73,44 @@ static int32_t knn_create_host(
                 const double v = val[e];
                 if (!std::isfinite(v)) return fail(LOCREC_E_INVALID_ARG, "%s value is not finite", name);
                 if (!(v >= 1.0) || v != std::floor(v)) integral = false;
-                vmax = std::max(vmax, std::fabs(v));
+                rvmax = std::max(rvmax, std::fabs(v));
                 ss += v * v;
             }
+            vmax = std::max(vmax, rvmax);
             if (ptr[r + 1] > ptr[r] && !(ss > 0))
                 return fail(LOCREC_E_INVALID_ARG, "%s vector of person %lld has zero norm", name,
                             (long long)person_ids[r]);
             ssmax = std::max(ssmax, ss);
+            if (rvmax >= 256.0 || ss >= 65536.0) {
+                wide_in[(size_t)r] = 1;
+            } else {
+                lvmax = std::max(lvmax, rvmax);
+                lssmax = std::max(lssmax, ss);
+            }
         }
         return LOCREC_OK;
     };
     bool integral = true;
-    double pvmax = 0, cvmax = 0, pss = 0, css = 0;
-    LOCREC_TRY(check_family("place", p_rowptr, p_idx, p_val, p_dim, integral, pvmax, pss));
-    LOCREC_TRY(check_family("category", c_rowptr, c_idx, c_val, c_dim, integral, cvmax, css));
+    double pvmax = 0, cvmax = 0, pss = 0, css = 0, plvmax = 0, clvmax = 0, plss = 0, clss = 0;
+    LOCREC_TRY(check_family("place", p_rowptr, p_idx, p_val, p_dim, integral, pvmax, pss, plvmax, plss));
+    LOCREC_TRY(check_family("category", c_rowptr, c_idx, c_val, c_dim, integral, cvmax, css, clvmax, clss));
+    // ---- per-row format fallback: the same decision as knn_build.hip (at most min(4096, max(256, n / 512)) wide rows,
+    // and fewer than n), so that both builds give one index
+    int64_t n_wide = 0;
+    const bool any_wide = pvmax >= 256.0 || cvmax >= 256.0 || pss >= 65536.0 || css >= 65536.0;
+    if (any_wide && integral && !force_generic && !ix->no_row_fallback && !ix->no_pack16 && !ix->no_ht && n < ((int64_t)1 << 24) && c_dim <= kHtCatRows &&
+        p_dim < (1 << 20) - 1) {  // (a place dimension no packed format holds: GENERIC keeps every row in its image)
+        for (unsigned char w : wide_in) n_wide += w ? 1 : 0;
+        const int64_t cap = std::min<int64_t>(4096, std::max<int64_t>(256, n / 512));
+        if (n_wide > 0 && n_wide <= cap && n_wide < n) {
+            pvmax = plvmax;
+            cvmax = clvmax;
+            pss = plss;
+            css = clss;
+        } else {
+            n_wide = 0;
+        }
+    }
     const int p_vbits = std::min(24, 32 - ceil_log2i(p_dim));
     const int c_vbits = std::min(24, 32 - ceil_log2i(c_dim));
     // exact u32 dots need every dot < 2^32; |dot| <= sqrt(ss_a * ss_b) <= max ss
@@ -140,6 +182,49 @@ static int32_t knn_create_host(
         if (dupit != ix->ids_sorted.end()) return fail(LOCREC_E_INVALID_ARG, "duplicate person_id %lld", (long long)*dupit);
     }
     lap("row order + id map");
+    if (n_wide > 0) {
+        ix->is_wide.resize((size_t)n);
+        for (int64_t r = 0; r < n; ++r) {
+            ix->is_wide[(size_t)r] = wide_in[(size_t)order[r]];
+            if (ix->is_wide[(size_t)r]) ix->wide_rows.push_back((int32_t)r);
+        }
+        LOCREC_TRY(ix->wide_rows_dev.upload(ix->wide_rows, ix->stream));
+        LOCREC_HIP_TRY(hipStreamSynchronize(ix->stream));
+    }
+    // the wide rows leave a packed image (all padding) ...
+    auto blank_wide = [&](DevFamily &f) -> int32_t {
+        if (n_wide == 0) return LOCREC_OK;
+        hipLaunchKernelGGL(knn_host_blank_rows, dim3((unsigned)ix->wide_rows.size()), dim3(64), 0, ix->stream, (int32_t)ix->wide_rows.size(),
+                           ix->wide_rows_dev.p, f.sell_off.p, f.sell_w.p, f.sell.p);
+        LOCREC_HIP_TRY(hipGetLastError());
+        LOCREC_HIP_TRY(hipStreamSynchronize(ix->stream));
+        return LOCREC_OK;
+    };
+    // ... and enter the side kernels' lane-major copy (knn_index.h, side_p / side_c) instead
+    auto side_of = [&](const HostFamily &h, DevBuf<int2> &img, DevBuf<int32_t> &off_d, DevBuf<int32_t> &w_d) -> int32_t {
+        const int32_t nw = (int32_t)ix->wide_rows.size(), ns = (nw + 63) / 64;
+        std::vector<int32_t> off((size_t)ns + 1, 0), wv((size_t)ns, 0);
+        for (int32_t sl = 0; sl < ns; ++sl) {
+            int64_t m = 0;
+            for (int32_t w = sl * 64; w < std::min(nw, sl * 64 + 64); ++w) {
+                const int32_t r = ix->wide_rows[(size_t)w];
+                m = std::max(m, h.ptr[r + 1] - h.ptr[r]);
+            }
+            wv[(size_t)sl] = (int32_t)m;
+            off[(size_t)sl + 1] = off[(size_t)sl] + (int32_t)m * 64;
+        }
+        std::vector<int2> host_img((size_t)std::max(1, off[(size_t)ns]), make_int2(-1, -1));  // index -1 = padding
+        for (int32_t w = 0; w < nw; ++w) {
+            const int32_t r = ix->wide_rows[(size_t)w];
+            for (int64_t e = h.ptr[r], j = 0; e < h.ptr[r + 1]; ++e, ++j)
+                host_img[(size_t)(off[(size_t)(w >> 6)] + j * 64 + (w & 63))] = make_int2(h.idx[e], (int)h.val[e]);
+        }
+        LOCREC_TRY(img.upload(host_img, ix->stream));
+        LOCREC_TRY(off_d.upload(off, ix->stream));
+        LOCREC_TRY(w_d.upload(wv, ix->stream));
+        LOCREC_HIP_TRY(hipStreamSynchronize(ix->stream));
+        return LOCREC_OK;
+    };
     auto gather = [&](const int64_t *ptr, const int32_t *idx, const double *val, int32_t dim, int vbits,
                       HostFamily &h) {
         h.dim = dim;
@@ -174,8 +259,31 @@ static int32_t knn_create_host(
                 }
             }
             LOCREC_TRY(build_family_device(ix.get(), hq, ix->fp, ix->packed));
-            if (want_ht) {
+            LOCREC_TRY(blank_wide(ix->fp));
+            if (want_ht && n_wide == 0) {
                 LOCREC_TRY(build_ht(ix.get(), hq, hc, ht_h, ht_qt));
+                lap("head / tail image");
+            } else if (want_ht) {
+                // the head / tail image without the wide rows: no head elements, no postings, ss = 0; their category
+                // elements are padding (index 0, value 0) in slices as wide as if they were there
+                HostFamily tq, tc = hc;
+                tq.dim = hq.dim;
+                tq.vbits = hq.vbits;
+                tq.ptr.assign((size_t)n + 1, 0);
+                for (int64_t r = 0; r < n; ++r) {
+                    const bool w = ix->is_wide[(size_t)r] != 0;
+                    tq.ptr[r + 1] = tq.ptr[r] + (w ? 0 : hq.ptr[r + 1] - hq.ptr[r]);
+                    if (!w) {
+                        tq.idx.insert(tq.idx.end(), hq.idx.begin() + hq.ptr[r], hq.idx.begin() + hq.ptr[r + 1]);
+                        tq.val.insert(tq.val.end(), hq.val.begin() + hq.ptr[r], hq.val.begin() + hq.ptr[r + 1]);
+                    } else {
+                        std::fill(tc.idx.begin() + tc.ptr[r], tc.idx.begin() + tc.ptr[r + 1], 0);
+                        std::fill(tc.val.begin() + tc.ptr[r], tc.val.begin() + tc.ptr[r + 1], 0.0);
+                    }
+                }
+                LOCREC_TRY(build_ht(ix.get(), tq, tc, ht_h, ht_qt));
+                LOCREC_TRY(side_of(hq, ix->side_p, ix->side_off_p, ix->side_w_p));
+                LOCREC_TRY(side_of(hc, ix->side_c, ix->side_off_c, ix->side_w_c));
                 lap("head / tail image");
             }
             // leading element groups (dwordx4 = 4 elements) that are popular in EVERY lane of the slice;
@@ -200,6 +308,7 @@ static int32_t knn_create_host(
             LOCREC_TRY(build_family_device(ix.get(), hp, ix->fp, ix->packed));
         }
         LOCREC_TRY(build_family_device(ix.get(), hc, ix->fc, ix->packed));
+        LOCREC_TRY(blank_wide(ix->fc));
         lap("families (gather, SELL, upload)");
         // ratings CSR in row order
         std::vector<int64_t> rp((size_t)n + 1, 0), rplace;
