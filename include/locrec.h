@@ -615,7 +615,8 @@ int32_t locrec_similar_place_edges_stats(int64_t *out_pairs, int64_t *out_chunks
  * (:48-58), computed by the caller in its session time zone; timestamps are opaque int64.
  * Output columns as :40-46 (person_id, timestamp, place_id, region_id, category_id), ordered by
  * (visit row, place row) - the reference leaves the order undefined.  *inout_count: capacity in,
- * number of matches out (may exceed the capacity; call with 0 to size the buffers).
+ * number of matches out (may exceed the capacity, then the first `capacity` rows of the full result
+ * are written, also where the capacity ends inside one visit's matches; call with 0 to size the buffers).
  * A latitude / longitude outside its range (or NaN) in a row that takes part in the join fails as
  * Location's require does: LOCREC_E_INVALID_ARG with the reference's message, *inout_count =
  * -(1 + visit row) or -(1 + n_visits + place row).
@@ -640,7 +641,8 @@ int32_t locrec_distance_meters(int64_t n, const double *lat1, const double *lon1
  * places.where(region_id === target_region_id) JOIN recommendations ON id, ORDER BY score DESC,
  * LIMIT max_recommendations.  Rows whose id is not a place of the target region (persons,
  * categories, places elsewhere) drop out in the join; a place listed twice counts once; ties
- * (Spark: undefined) are ordered by id ascending; NaN sorts above every number, as in Spark.
+ * (Spark: undefined) are ordered by id ascending, then by input row.  Scores compare as Spark SQL
+ * compares doubles: every NaN (either sign, any payload) is one value above +inf, -0.0 equals 0.0.
  * Outputs need room for min(n, max_recommendations) rows; *out_count = rows written.
  */
 int32_t locrec_rank_recommendations(int64_t n, const int64_t *ids, const double *scores, int64_t n_places,

@@ -585,6 +585,9 @@ __device__ __forceinline__ int64_t lower_bound_key(const uint64_t *keys, int64_t
 // One thread per visit: the places of the (at most) 3 bands x 3 cells around it, exact distance each.
 // WRITE = false counts the matches; WRITE = true stores the place rows at the visit's offset (ascending
 // place row: the candidates of a visit are few, an insertion sort orders them) and fills the columns.
+// The matches arrive in scan order (band, then cell), so a visit that the capacity cuts stores ALL of
+// them, sorts, and only then writes the first `cap - base`: the rows written are the prefix of the
+// full result.  scratch_rows has room to the end of that one visit (pr_cut_end).
 template <bool WRITE>
 __global__ void pr_join(int64_t nv, const int64_t *v_person, const int64_t *v_ts, const double *v_lat, const double *v_lon,
                         const int64_t *v_region, int64_t visits_from, const int64_t *regions, int32_t nr, Grid g,
@@ -615,7 +618,7 @@ __global__ void pr_join(int64_t nv, const int64_t *v_person, const int64_t *v_ts
                     for (int64_t at = lower_bound_key(keys, np, key); at < np && keys[at] == key; ++at) {
                         const uint32_t j = place_rows[at];
                         if (distance_meters(lat, lon, p_lat[j], p_lon[j]) <= max_meters) {  // (:15-21,127)
-                            if (WRITE && base + found < (unsigned long long)cap) scratch_rows[base + found] = j;
+                            if (WRITE && base < (unsigned long long)cap) scratch_rows[base + found] = j;
                             ++found;
                         }
                     }
@@ -629,8 +632,9 @@ __global__ void pr_join(int64_t nv, const int64_t *v_person, const int64_t *v_ts
     }
     const unsigned long long room = base < (unsigned long long)cap ? (unsigned long long)cap - base : 0ull;
     const unsigned long long m = min(found, room);
+    const unsigned long long stored = room ? found : 0ull;
     uint32_t *mine = scratch_rows + base;
-    for (unsigned long long a = 1; a < m; ++a) {
+    for (unsigned long long a = 1; a < stored; ++a) {
         const uint32_t v = mine[a];
         unsigned long long b = a;
         for (; b > 0 && mine[b - 1] > v; --b) mine[b] = mine[b - 1];
@@ -644,6 +648,20 @@ __global__ void pr_join(int64_t nv, const int64_t *v_person, const int64_t *v_ts
         out_region[base + a] = v_region[i];
         out_category[base + a] = p_category[j];
     }
+}
+
+// where the visit that the capacity cuts ends: offsets[i] + counts[i] of the last visit that starts below cap
+// (cap >= 1; offsets[0] = 0, non-decreasing).  Every other visit that starts below cap ends at or below it.
+__global__ void pr_cut_end(int64_t nv, const unsigned long long *offsets, const unsigned long long *counts, int64_t cap,
+                           unsigned long long *out)
+{
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    int64_t a = 0, b = nv - 1;
+    while (a < b) {
+        const int64_t mid = (a + b + 1) >> 1;
+        if (offsets[mid] < (unsigned long long)cap) a = mid; else b = mid - 1;
+    }
+    out[0] = offsets[a] + counts[a];
 }
 
 int32_t mem_ok(int32_t mem)
@@ -897,7 +915,17 @@ try {
     LOCREC_TRY(opl.bind(out_place_ids, rows, mem));
     LOCREC_TRY(org.bind(out_region_ids, rows, mem));
     LOCREC_TRY(oca.bind(out_category_ids, rows, mem));
-    LOCREC_TRY(scratch.alloc((size_t)rows));
+    int64_t scratch_rows = rows;
+    if (total > cap) {  // the one visit that the capacity cuts keeps all its matches until they are sorted
+        DevBuf<unsigned long long> cut_dev;
+        unsigned long long cut_end = 0;
+        LOCREC_TRY(cut_dev.alloc(1));
+        hipLaunchKernelGGL(pr_cut_end, dim3(1), dim3(64), 0, s, n_visits, offsets.p, counts.p, cap, cut_dev.p);
+        LOCREC_HIP_TRY(hipMemcpyAsync(&cut_end, cut_dev.p, 8, hipMemcpyDeviceToHost, s));
+        LOCREC_HIP_TRY(hipStreamSynchronize(s));
+        scratch_rows = std::max(rows, (int64_t)cut_end);
+    }
+    LOCREC_TRY(scratch.alloc((size_t)scratch_rows));
     hipLaunchKernelGGL((pr_join<true>), grid_for(n_visits), dim3(256), 0, s, n_visits, vp.p, vt.p, vlat.p, vlon.p, vr.p,
                        visits_from, regions.p, nr, g, max_meters, n_places, k1.p, r1.p, pi.p, plat.p, plon.p, pc.p, nullptr,
                        offsets.p, rows, scratch.p, op.p, ots.p, opl.p, org.p, oca.p);
@@ -972,10 +1000,14 @@ __global__ void pr_rank_flags(int64_t n, const int64_t *ids, const uint64_t *all
     keep[i] = lo < nallowed && allowed[lo] == k ? 1 : 0;
 }
 
+// Spark SQL's order of doubles: every NaN, whatever its sign and payload, is one value above
+// +inf, and -0.0 equals 0.0 - so both are made one bit pattern before the usual monotone map
 __device__ __forceinline__ uint64_t score_desc_key(double s)
 {
     uint64_t b = (uint64_t)__double_as_longlong(s);
-    b = (b >> 63) ? ~b : b | 0x8000000000000000ull;  // ascending order of the doubles (NaN sorts above +inf, as in Spark)
+    if (s != s) b = 0x7FF8000000000000ull;
+    else if (s == 0.0) b = 0ull;
+    b = (b >> 63) ? ~b : b | 0x8000000000000000ull;  // ascending order of the doubles
     return ~b;                                       // ... descending
 }
 

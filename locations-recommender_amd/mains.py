@@ -173,12 +173,14 @@ def rank_recommendations(ids, scores, place_ids, place_region_ids, target_region
     """printRecommendations of both mains: places.where(region_id == target) JOIN recommendations
     ON id, ORDER BY score DESC, LIMIT maxRecommendations.  Rows whose id is not a place of the target
     region (persons, categories, places elsewhere) drop out in the join.  Ties: Spark leaves the
-    order undefined; here (score desc, id asc)."""
+    order undefined; here (score desc, id asc, input order), NaN first and the two zeros tied."""
     ids, scores = np.asarray(ids, np.int64), np.asarray(scores, np.float64)
     allowed = np.unique(np.asarray(place_ids, np.int64)[np.asarray(place_region_ids, np.int64) == int(target_region_id)])
     keep = np.isin(ids, allowed)
     ids, scores = ids[keep], scores[keep]
-    order = np.lexsort((ids, -scores))[:max(0, int(max_recommendations))]
+    # Spark SQL's order of doubles: every NaN is one value above +inf, -0.0 equals 0.0 (lexsort compares with <)
+    nan = np.isnan(scores)
+    order = np.lexsort((ids, np.where(nan, 0.0, -scores), ~nan))[:max(0, int(max_recommendations))]
     return ids[order], scores[order]
 
 

@@ -655,8 +655,19 @@ int32_t oracle_place_visits(int64_t nv, const int64_t *v_ts, const double *v_lat
  * stochastic/StochasticRecommenderMain.scala:64-75): the target region's places JOIN the
  * recommendations ON id (inner join: a row that is not a place of the region drops out; a place
  * listed twice is taken once here - the reference's places table has unique ids), ORDER BY score
- * DESC (ties, undefined in Spark: id ascending), LIMIT max_recommendations.  No reference test.
+ * DESC (score_desc_cmp; ties, undefined in Spark: id ascending, then input order), LIMIT max_recommendations.
+ * No reference test.
  * Plain O(n * places) membership + insertion sort: deliberately not the sort-based product code. */
+/* ORDER BY score DESC as Spark SQL 3.1 orders doubles ("NaN Semantics" of the SQL reference: NaN = NaN, and NaN is
+ * larger than any other value; migration guide 2.4 -> 3.0: -0.0 and 0.0 are equal): < 0 if a comes first.  Sign and
+ * payload of a NaN and the sign of a zero do not take part, so this is a total preorder and (it, id) a total order.  */
+static int score_desc_cmp(double a, double b)
+{
+    int an = a != a, bn = b != b;
+    if (an || bn) return bn - an;
+    return a > b ? -1 : a < b ? 1 : 0;
+}
+
 int32_t oracle_rank_recommendations(int64_t n, const int64_t *ids, const double *scores, int64_t np,
                                     const int64_t *place_ids, const int64_t *place_regions, int64_t target_region,
                                     int64_t max_recommendations, int64_t *out_ids, double *out_scores, int64_t *out_count)
@@ -667,7 +678,8 @@ int32_t oracle_rank_recommendations(int64_t n, const int64_t *ids, const double 
         for (int64_t j = 0; j < np && !member; ++j) member = place_ids[j] == ids[i] && place_regions[j] == target_region;
         if (!member) continue;
         int64_t at = m++;                                  /* insertion: score desc, id asc */
-        while (at > 0 && (out_scores[at - 1] < scores[i] || (out_scores[at - 1] == scores[i] && out_ids[at - 1] > ids[i]))) {
+        while (at > 0 && (score_desc_cmp(out_scores[at - 1], scores[i]) > 0 ||
+                          (score_desc_cmp(out_scores[at - 1], scores[i]) == 0 && out_ids[at - 1] > ids[i]))) {
             out_scores[at] = out_scores[at - 1]; out_ids[at] = out_ids[at - 1]; --at;
         }
         out_scores[at] = scores[i]; out_ids[at] = ids[i];
