@@ -650,6 +650,61 @@ int32_t locrec_rank_recommendations(int64_t n, const int64_t *ids, const double 
                                     int64_t target_region_id, int64_t max_recommendations, int32_t mem,
                                     int64_t *out_ids, double *out_scores, int64_t *out_count);
 
+/* ===================================================================== */
+/* The place deduplicator (deduplicator/PlaceDeduplicator.scala,          */
+/* deduplicator/Levenshtein.scala).  Stateless, on the current device,    */
+/* with the producers' conventions for `mem` and counts.                  */
+/* Names are CSR: int64 offsets[n + 1] (offsets[0] >= 0, never decreasing) */
+/* plus uint16 UTF-16 code units, ALREADY LOWER-CASED by the caller:      */
+/* toLowerCase is the host language's own, locale rules included, so the  */
+/* library compares the units as given (a surrogate pair is two units,    */
+/* as Java chars are).  Names have no length limit.                       */
+
+/*
+ * Levenshtein.lev (deduplicator/Levenshtein.scala:18-57) of n pairs (a[i], b[i]).
+ * max_difference < 0: the exact distance.  max_difference >= 0: min(lev, max_difference + 1),
+ * computed by the very kernel locrec_find_duplicate_places uses for that threshold - this function
+ * is to the deduplicator what locrec_distance_meters is to the visit join.  n in [0, 2^31).
+ */
+int32_t locrec_lev_distances(int64_t n, const int64_t *a_offsets, const uint16_t *a_units, const int64_t *b_offsets,
+                             const uint16_t *b_units, int32_t max_difference, int32_t mem, int32_t *out_distances);
+
+/*
+ * PlaceDeduplicator(maxPlaceDistanceMeters, maxNameDifference).dropDuplicates
+ * (deduplicator/PlaceDeduplicator.scala:13-54).  A pair is (place p, confirmed place c) with equal
+ * region_id (:39) and different id (:40).  It is SAME when distanceMeters(p, c) <= max_meters and
+ * lev(p.name, c.name) <= max_name_difference (:34-35, negated).  The same pairs come back as
+ * (place row, confirmed row, exact name difference), ordered by (place row, confirmed row).
+ * *inout_count: capacity in, number of same pairs out (may exceed the capacity, then the first
+ * `capacity` rows of the full result are written; call with 0 to size the buffers).
+ * out_not_same_counts (n_places entries, may be NULL): (confirmed rows of place i's region whose id
+ * differs from p_ids[i]) - (same pairs of place i) - how often the reference's literal inner join
+ * (:38-53) returns place i.  A place whose region has no confirmed place gets 0.
+ * max_meters < 0 or max_name_difference < 0 is legal: no pair can be same.
+ * Limits of this implementation (not reference behaviour): max_meters NaN or >= the earth radius
+ * (6371 km) fails with LOCREC_E_INVALID_ARG - the grid cannot prune there, as in
+ * locrec_calc_place_visits; at most 2^24 - 1 distinct regions; row counts in [0, 2^31).
+ * A latitude / longitude outside its range (or NaN) in a row whose region has at least one row on
+ * the other side fails as Location's require does (Location.scala:7-8): LOCREC_E_INVALID_ARG with
+ * the reference's message, *inout_count = -(1 + place row) or -(1 + n_places + confirmed row).
+ * The candidates (pairs within the radius) are produced and compared in chunks of places of at most
+ * LOCREC_DEDUP_PAIR_BUDGET (default 2^26) pairs; the result does not depend on the budget.
+ */
+int32_t locrec_find_duplicate_places(
+    int64_t n_places, const int64_t *p_ids, const int64_t *p_region_ids, const double *p_latitudes,
+    const double *p_longitudes, const int64_t *p_name_offsets, const uint16_t *p_name_units,
+    int64_t n_confirmed, const int64_t *c_ids, const int64_t *c_region_ids, const double *c_latitudes,
+    const double *c_longitudes, const int64_t *c_name_offsets, const uint16_t *c_name_units,
+    double max_meters, int32_t max_name_difference, int32_t mem,
+    int64_t *out_place_rows, int64_t *out_confirmed_rows, int32_t *out_name_differences, int64_t *inout_count,
+    int64_t *out_not_same_counts);
+
+/* What this thread's last locrec_find_duplicate_places did (measurement): candidate pairs (within the
+ * radius, ids differ), same pairs, chunks, and HIP-event milliseconds of its grid (keys, sorts, walks),
+ * Levenshtein and compaction phases.  Every pointer may be NULL. */
+int32_t locrec_find_duplicate_places_stats(int64_t *out_candidates, int64_t *out_same, int64_t *out_chunks,
+                                           double *out_grid_ms, double *out_lev_ms, double *out_compact_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -745,6 +745,98 @@ JNIEXPORT jlong JNICALL JNI_FN(rankRecommendations)(JNIEnv *env, jobject self, j
     return st == LOCREC_OK ? (jlong)count : 0;
 }
 
+/* one side of dedupFindDuplicates: the five columns and the names' CSR, checked and copied */
+typedef struct {
+    int64_t n;
+    int64_t *ids, *regions, *offsets;
+    double *lat, *lon;
+    uint16_t *units;
+} dedup_side;
+
+/* 1 if the side is ready; 0 with an exception pending.  Name units cross as int[] (the shim moves long / int /
+ * double arrays only): each is range-checked to [0, 65535] and narrowed. */
+static int dedup_side_in(JNIEnv *env, bufs *b, const char *what, jlongArray ids, jlongArray regions, jdoubleArray lat,
+                         jdoubleArray lon, jlongArray offsets, jintArray units, dedup_side *s)
+{
+    s->n = alen(env, ids);
+    if (alen(env, regions) != s->n || alen(env, lat) != s->n || alen(env, lon) != s->n)
+        return iae(env, "dedupFindDuplicates: %s columns of different lengths", what);
+    if (alen(env, offsets) != s->n + 1)
+        return iae(env, "dedupFindDuplicates: %s name offsets need ids.length + 1 = %lld entries", what, (long long)(s->n + 1));
+    const int64_t nu = alen(env, units);
+    s->offsets = in_longs(env, b, offsets, s->n + 1);
+    if (!s->offsets) return 0;
+    for (int64_t i = 0; i <= s->n; ++i)
+        if (s->offsets[i] < 0 || s->offsets[i] > nu || (i > 0 && s->offsets[i] < s->offsets[i - 1]))
+            return iae(env, "dedupFindDuplicates: %s name offsets must ascend within [0, nameUnits.length = %lld]", what, (long long)nu);
+    int32_t *wide = in_ints(env, b, units, nu);
+    if (!wide) return 0;
+    s->units = (uint16_t *)buf_new(env, b, nu, sizeof(uint16_t));
+    if (!s->units) return 0;
+    for (int64_t i = 0; i < nu; ++i) {
+        if (wide[i] < 0 || wide[i] > 65535)
+            return iae(env, "dedupFindDuplicates: %s name unit %lld is %d, not a UTF-16 code unit in [0, 65535]", what, (long long)i,
+                       (int)wide[i]);
+        s->units[i] = (uint16_t)wide[i];
+    }
+    s->ids = in_longs(env, b, ids, s->n);
+    s->regions = s->ids ? in_longs(env, b, regions, s->n) : NULL;
+    s->lat = s->regions ? in_doubles(env, b, lat, s->n) : NULL;
+    s->lon = s->lat ? in_doubles(env, b, lon, s->n) : NULL;
+    return s->lon != NULL;
+}
+
+/* dedupFindDuplicates(place columns x4 + name offsets + name units, confirmed-place columns likewise, maxMeters,
+ * maxNameDifference, outPlaceRows, outConfirmedRows, outNameDifferences, outNotSameCounts): Long = the pairs that are the
+ * same place (may exceed the output arrays' length: call again with larger ones; pass arrays of length 0 to size them).
+ * outNotSameCounts (places.length entries, or null) = how often dropDuplicates' join returns each place.  Names are
+ * lower-cased by the caller.  PlaceDeduplicator.dropDuplicates, deduplicator/PlaceDeduplicator.scala:13-54 */
+JNIEXPORT jlong JNICALL JNI_FN(dedupFindDuplicates)(JNIEnv *env, jobject self, jlongArray pIds, jlongArray pRegionIds,
+                                                    jdoubleArray pLat, jdoubleArray pLon, jlongArray pNameOffsets,
+                                                    jintArray pNameUnits, jlongArray cIds, jlongArray cRegionIds,
+                                                    jdoubleArray cLat, jdoubleArray cLon, jlongArray cNameOffsets,
+                                                    jintArray cNameUnits, jdouble maxMeters, jint maxNameDifference,
+                                                    jlongArray outPlaceRows, jlongArray outConfirmedRows,
+                                                    jintArray outNameDifferences, jlongArray outNotSameCounts)
+{
+    (void)self;
+    if (!pIds || !pRegionIds || !pLat || !pLon || !pNameOffsets || !pNameUnits || !cIds || !cRegionIds || !cLat || !cLon ||
+        !cNameOffsets || !cNameUnits || !outPlaceRows || !outConfirmedRows || !outNameDifferences)
+        return iae(env, "dedupFindDuplicates: null array");
+    if (outNotSameCounts && alen(env, outNotSameCounts) < alen(env, pIds))
+        return iae(env, "dedupFindDuplicates: outNotSameCounts needs pIds.length = %lld entries", (long long)alen(env, pIds));
+    /* the capacity is what ALL three output columns can hold */
+    int64_t room = alen(env, outPlaceRows);
+    if (alen(env, outConfirmedRows) < room) room = alen(env, outConfirmedRows);
+    if (alen(env, outNameDifferences) < room) room = alen(env, outNameDifferences);
+    bufs b = {{0}, 0};
+    dedup_side p, c;
+    int64_t count = room;
+    int32_t st = LOCREC_E_OOM;
+    if (dedup_side_in(env, &b, "place", pIds, pRegionIds, pLat, pLon, pNameOffsets, pNameUnits, &p) &&
+        dedup_side_in(env, &b, "confirmed place", cIds, cRegionIds, cLat, cLon, cNameOffsets, cNameUnits, &c)) {
+        int64_t *o0 = (int64_t *)buf_new(env, &b, room, 8), *o1 = o0 ? (int64_t *)buf_new(env, &b, room, 8) : NULL;
+        int32_t *o2 = o1 ? (int32_t *)buf_new(env, &b, room, 4) : NULL;
+        int64_t *ns = (o2 && outNotSameCounts) ? (int64_t *)buf_new(env, &b, p.n, 8) : NULL;
+        if (o2 && (ns || !outNotSameCounts)) {
+            st = locrec_find_duplicate_places(p.n, p.ids, p.regions, p.lat, p.lon, p.offsets, p.units, c.n, c.ids, c.regions, c.lat,
+                                              c.lon, c.offsets, c.units, maxMeters, (int32_t)maxNameDifference, LOCREC_MEM_HOST, o0,
+                                              o1, o2, &count, ns);
+            if (st != LOCREC_OK) {
+                throw_status(env, st);
+            } else {
+                const int64_t wrote = count < room ? count : room;
+                out_longs(env, outPlaceRows, o0, wrote);
+                out_longs(env, outConfirmedRows, o1, wrote);
+                out_ints(env, outNameDifferences, o2, wrote);
+                if (ns) out_longs(env, outNotSameCounts, ns, p.n);
+            }
+        }
+    }
+    bufs_free(&b);
+    return st == LOCREC_OK ? (jlong)count : 0;
+}
+
 /* sgGroupCreate(graphHandles): Long; sgGroupSweeps(group, vertexIds, alpha, sweeps); sgGroupSynchronize; sgGroupDestroy -
  * the per-region / per-region-pair graphs of StochasticRecommenderMain iterated together (include/locrec.h).
  * The group remembers its size so that the vertexIds arrays of later calls can be checked. */

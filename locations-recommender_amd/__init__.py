@@ -8,3 +8,5 @@ from .knn import KnnIndex, KnnRecommender, SparseVector  # noqa: F401
 from .stochastic import ALPHA, SgGraph, SgGroup, StochasticRecommender  # noqa: F401
 from .multi import KnnReplicas, SgSharded, set_devices  # noqa: F401
 from . import prep  # noqa: F401,E402  (calc_ratings, calc_rating_vectors, build_with_balanced_weights, calc_place_visits)
+from . import deduplicator  # noqa: F401,E402
+from .deduplicator import PlaceDeduplicator, lev  # noqa: F401,E402

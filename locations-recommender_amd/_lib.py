@@ -134,6 +134,13 @@ SIGNATURES = {
     "locrec_distance_meters": [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p],
     "locrec_rank_recommendations": [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                     C.c_int32, C.c_void_p, C.c_void_p, _i64p],
+    # the place deduplicator (dedup.hip)
+    "locrec_lev_distances": [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p],
+    "locrec_find_duplicate_places": [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_double, C.c_int32, C.c_int32,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, _i64p, C.c_void_p],
+    "locrec_find_duplicate_places_stats": [_i64p, _i64p, _i64p, _f64p, _f64p, _f64p],
 }
 _RESTYPE = {"locrec_last_error": C.c_char_p, "locrec_version": C.c_char_p, "locrec_knn_replicas_destroy": None,
             "locrec_sg_sharded_destroy": None, "locrec_sg_group_destroy": None}

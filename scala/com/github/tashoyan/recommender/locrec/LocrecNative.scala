@@ -166,4 +166,17 @@ object LocrecNative {
       targetRegionId: Long, maxRecommendations: Long, outIds: Array[Long], outScores: Array[Double]
   ): Long
 
+  /** PlaceDeduplicator.dropDuplicates (deduplicator/PlaceDeduplicator.scala:13-54): the (place row, confirmed row, name
+    * difference) of every pair that is the same place, ordered by (place row, confirmed row); returns their number (may
+    * exceed the arrays' length). Names are CSR (offsets of length n + 1, UTF-16 code units as Int), lower-cased by the
+    * caller. outNotSameCounts (places.length entries or null) = how often the reference's join returns each place. */
+  @native def dedupFindDuplicates(
+      pIds: Array[Long], pRegionIds: Array[Long], pLatitudes: Array[Double], pLongitudes: Array[Double],
+      pNameOffsets: Array[Long], pNameUnits: Array[Int],
+      cIds: Array[Long], cRegionIds: Array[Long], cLatitudes: Array[Double], cLongitudes: Array[Double],
+      cNameOffsets: Array[Long], cNameUnits: Array[Int],
+      maxMeters: Double, maxNameDifference: Int,
+      outPlaceRows: Array[Long], outConfirmedRows: Array[Long], outNameDifferences: Array[Int], outNotSameCounts: Array[Long]
+  ): Long
+
 }
