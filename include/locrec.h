@@ -334,6 +334,43 @@ int32_t locrec_sg_create(
     int64_t n_edges, const int64_t *source_ids, const int64_t *target_ids,
     const double *balanced_weights, locrec_sg_graph **out_graph);
 
+/*
+ * The same handle from an edge list that already lives in DEVICE memory (the current HIP device), e.g. the
+ * output of locrec_build_balanced_edges with mem = device: the SG counterpart of locrec_knn_create_from_device.
+ * The three arrays are only read and the caller keeps them; no array of n_edges elements crosses to the host.
+ *
+ * The handle is an ordinary, unsharded locrec_sg_graph, and its layout equals the one locrec_sg_create builds
+ * from the same edge list element for element: the same ascending vertex ids, live order, piece plan, slot of
+ * every edge (edge-list order inside a row), weight interleave, partial-slot maps, dead-slot lists, column
+ * width and weight dictionary.  A row's sum runs in slot order, so every request, batch and group answers bit
+ * for bit what it answers on the host-built handle; info / device_bytes / weight_dictionary / live_count agree.
+ *
+ * Built by kernels on the handle's stream (csrc/sg_create_device.hip; DESIGN.md 4, "Device build"): vertex
+ * ranking through a table over [min id, max id] or a sort of the 2 E ids (the rule of locrec_sg_create,
+ * LOCREC_SG_NO_DENSE_IDS included), one stable radix sort of the edges by target vertex, scans for the live
+ * order and the piece plan, a second stable sort for the out-edges of source-only vertices.  No position comes
+ * from an atomic, so the layout does not depend on scheduling.  Only vertex-sized arrays (vertex ids, live
+ * order, dead-slot row pointers) are read back; temporaries are freed before the call returns, and it returns
+ * when the handle is complete.
+ *
+ * n_edges in [0, 2^31), else LOCREC_E_INVALID_ARG; n_edges == 0 behaves as locrec_sg_create(0, ...); NULL
+ * arrays with n_edges > 0, arrays that are not device memory of the current device, and out_graph == NULL are
+ * LOCREC_E_INVALID_ARG; "too many vertices" and "graph too large for int32 slot ids / partial slots" are
+ * reported as by locrec_sg_create.  The create-time switches LOCREC_SG_NO_COL16, NO_DICT, NO_DENSE_IDS, GS,
+ * PPW, DICT_*, NO_GRAPH and NO_PACK are honoured as there.  The two experiments (LOCREC_SG_FUSED,
+ * LOCREC_SG_PERSIST) keep their host-only extra layouts: a handle created under either switch copies the three
+ * columns to the host once and goes through the host build.
+ */
+int32_t locrec_sg_create_from_device(
+    int64_t n_edges, const int64_t *source_ids, const int64_t *target_ids,
+    const double *balanced_weights, locrec_sg_graph **out_graph);
+
+/* HIP-event milliseconds of the phases of this thread's last locrec_sg_create_from_device (measurement): vertex
+ * ranking, live order + piece plan + maps, the two sorts + the scatter, the weight dictionary.  Zeros after a
+ * call that took the host build.  Every pointer may be NULL. */
+int32_t locrec_sg_create_from_device_stats(double *out_ranking_ms, double *out_plan_ms, double *out_scatter_ms,
+                                           double *out_dictionary_ms);
+
 int32_t locrec_sg_destroy(locrec_sg_graph *graph);
 
 /* vertexCount (:51); edges; bytes one sweep x -> x' streams (algorithmic). */

@@ -76,6 +76,8 @@ SIGNATURES = {
     "locrec_knn_profile_enable": [C.c_void_p, C.c_int32],
     "locrec_knn_profile_read": [C.c_void_p, _f64p, _i64p],
     "locrec_sg_create": [C.c_int64, _i64p, _i64p, _f64p, C.POINTER(C.c_void_p)],
+    "locrec_sg_create_from_device": [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)],
+    "locrec_sg_create_from_device_stats": [_f64p, _f64p, _f64p, _f64p],
     "locrec_sg_destroy": [C.c_void_p],
     "locrec_sg_info": [C.c_void_p, _i64p, _i64p, _i64p],
     "locrec_sg_device_bytes": [C.c_void_p, _i64p],

@@ -290,10 +290,11 @@ def generate_stochastic_graph(place_visits, beta_person_place, beta_person_categ
 
 def sg_graph_from_visits(place_visits, beta_person_place, beta_person_category):
     """Place visits -> the four edge families -> balanced edge list -> SgGraph: the SG counterpart of
-    knn_index_from_visits.  The edge list is computed on the device; locrec_sg_create builds its layout on the
-    host, so the list is copied to the host once here (a device-side sg_create is out of scope)."""
+    knn_index_from_visits.  With CUDA tensors the edge list stays in device memory and the graph's layout is built
+    from it by kernels (SgGraph.from_device): nothing passes through the host.  With numpy arrays the list comes
+    back to the host and goes through SgGraph (locrec_sg_create)."""
     from .stochastic import SgGraph
     s, t, w = generate_stochastic_graph(place_visits, beta_person_place, beta_person_category)
     if _is_tensor(s):
-        s, t, w = s.cpu().numpy(), t.cpu().numpy(), w.cpu().numpy()
+        return SgGraph.from_device(s.contiguous(), t.contiguous(), w.contiguous())
     return SgGraph(s, t, w)

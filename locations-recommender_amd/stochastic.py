@@ -28,6 +28,43 @@ class SgGraph:
                            int(shard_index), int(shard_count), C.byref(self._h)))
 
     @classmethod
+    def from_device(cls, source_ids, target_ids, balanced_weights):
+        """The same graph from an edge list that already lives in DEVICE memory (torch CUDA tensors on the current
+        GPU: int64, int64, float64): the layout is built by kernels (locrec_sg_create_from_device) and equals the
+        host-built one element for element, so every request answers the same bits.  The tensors are only read."""
+        import torch
+        cols = (source_ids, target_ids, balanced_weights)
+        for t, dtype, name in zip(cols, (torch.int64, torch.int64, torch.float64),
+                                  ("source_ids", "target_ids", "balanced_weights")):
+            if not isinstance(t, torch.Tensor):
+                raise L.IllegalArgumentException(f"requirement failed: {name} must be a torch tensor, got {type(t).__name__}")
+            if t.dtype != dtype or t.dim() != 1:
+                raise L.IllegalArgumentException(f"requirement failed: {name} must be a 1-d {dtype} tensor, got "
+                                                 f"{t.dim()}-d {t.dtype}")
+        if not (len(cols[0]) == len(cols[1]) == len(cols[2])):
+            raise L.IllegalArgumentException("edge columns of different lengths")
+        if not all(t.is_cuda for t in cols):
+            if not torch.cuda.is_available():
+                raise L.LocrecRuntimeError("no usable GPU: SgGraph.from_device has no CPU fallback")
+            raise L.IllegalArgumentException("requirement failed: the edge columns must be CUDA tensors")
+        L.require_current_device(cols)
+        cols = [t.contiguous() for t in cols]
+        torch.cuda.current_stream().synchronize()  # the library reads the arrays on its own stream
+        self = cls.__new__(cls)
+        self._h = C.c_void_p()
+        n = int(cols[0].numel())
+        ptr = [C.c_void_p(t.data_ptr()) if n else None for t in cols]
+        L.check(L.lib().locrec_sg_create_from_device(n, ptr[0], ptr[1], ptr[2], C.byref(self._h)))
+        return self
+
+    @staticmethod
+    def device_build_stats():
+        """HIP-event milliseconds of the phases of this thread's last from_device (locrec_sg_create_from_device_stats)."""
+        ms = [C.c_double() for _ in range(4)]
+        L.check(L.lib().locrec_sg_create_from_device_stats(*[C.byref(x) for x in ms]))
+        return dict(zip(("ranking_ms", "plan_ms", "scatter_ms", "dictionary_ms"), (x.value for x in ms)))
+
+    @classmethod
     def through_cache(cls, key, build):
         """The process-wide cached graph for `key` (include/locrec.h, "Handle cache"); build() -> SgGraph runs
         on a miss only.  close() / garbage collection drop a reference, the device graph stays."""
