@@ -234,6 +234,30 @@ int32_t locrec_knn_fetch_recommend(
     int64_t *out_offsets, int64_t *out_place_ids, double *out_estimated_ratings, int64_t *inout_capacity);
 
 /*
+ * The batched request to its end: makeRecommendations for nq persons, then printRecommendations per
+ * person (the places of target_region_ids[i] JOIN the person's rows ON id, ORDER BY score DESC, LIMIT
+ * max_recommendations; see locrec_rank_recommendations_batch for the order) - ranked on the device
+ * where the rows are, so only max_recommendations rows a person reach the host.  Row i of
+ * out_place_ids / out_estimated_ratings (host, row-major, stride max(0, max_recommendations)) belongs
+ * to person_ids[i], padded with id -1 and rating 0.0; out_counts[i] = rows written.  A repeated
+ * person gets identical rows.  Errors as locrec_knn_recommend_batch.  place_ids / place_region_ids /
+ * target_region_ids are host arrays.  locrec_knn_fetch_ranked is the same last stage for the range
+ * left by locrec_knn_recommend_range_async (target_region_ids[i] for internal row first + i; a row
+ * that is no valid query gets count 0).  locrec_rank_recommendations_batch_stats describes the call.
+ */
+int32_t locrec_knn_recommend_ranked_batch(
+    locrec_knn_index *index, int64_t nq, const int64_t *person_ids,
+    double place_weight, double category_weight, int64_t k_nearest,
+    int64_t n_places, const int64_t *place_ids, const int64_t *place_region_ids,
+    const int64_t *target_region_ids, int64_t max_recommendations,
+    int64_t *out_place_ids, double *out_estimated_ratings, int64_t *out_counts);
+int32_t locrec_knn_fetch_ranked(
+    locrec_knn_index *index, int64_t nq,
+    int64_t n_places, const int64_t *place_ids, const int64_t *place_region_ids,
+    const int64_t *target_region_ids, int64_t max_recommendations,
+    int64_t *out_place_ids, double *out_estimated_ratings, int64_t *out_counts);
+
+/*
  * One request with its candidate scan split over several GPUs (SURVEY.md 8e "KNN single request,
  * latency mode").  Every GPU holds the whole index (132 MB at cfg2, 1.3 GB at cfg4: nothing next to
  * 288 GB) and scans candidate shard shard_index of shard_count, a contiguous range of the
@@ -686,6 +710,36 @@ int32_t locrec_rank_recommendations(int64_t n, const int64_t *ids, const double 
                                     const int64_t *place_ids, const int64_t *place_region_ids,
                                     int64_t target_region_id, int64_t max_recommendations, int32_t mem,
                                     int64_t *out_ids, double *out_scores, int64_t *out_count);
+
+/*
+ * The same ranking for many row ranges of one (ids, scores) pair at once - the last stage of a batched
+ * request (locrec_knn_recommend_batch, locrec_sg_recommend_batch hand back every person's rows as one
+ * CSR).  Segment s is rows [offsets[s], offsets[s + 1]); row s of out_ids / out_scores (row-major,
+ * stride max(0, max_recommendations)) is exactly what locrec_rank_recommendations returns for those
+ * rows with target_region_ids[s], padded with id -1 and score 0.0; out_counts[s] = rows written.
+ * `mem` covers every array, offsets, target_region_ids and out_counts included.  offsets must be
+ * non-decreasing with offsets[0] >= 0 and offsets[n_segments] <= n (rows outside the segments are
+ * ignored); n, n_places and n_segments are < 2^31.  This is checked - for device memory on the device -
+ * before anything reads through the offsets: LOCREC_E_INVALID_ARG, nothing written.
+ * max_recommendations <= 0, n_segments == 0 or n_places == 0: counts 0, no row is read.
+ * Up to LOCREC_RANK_BATCH_MAX_N rows a segment are selected in LDS lists (one block per segment, or per
+ * chunk of a long segment plus a merge); a larger limit takes three radix passes over the kept rows.
+ * Any limit gives the same answer.  The number of host synchronisations does not depend on n_segments.
+ */
+#define LOCREC_RANK_BATCH_MAX_N 256
+int32_t locrec_rank_recommendations_batch(int64_t n_segments, const int64_t *offsets, int64_t n, const int64_t *ids,
+                                          const double *scores, int64_t n_places, const int64_t *place_ids,
+                                          const int64_t *place_region_ids, const int64_t *target_region_ids,
+                                          int64_t max_recommendations, int32_t mem, int64_t *out_ids,
+                                          double *out_scores, int64_t *out_counts);
+
+/* What the last ranked batch of this thread did (locrec_rank_recommendations_batch and the ranked KNN
+ * batches): segments served by one block, segments split into chunks, those chunks, segments that took
+ * the radix sort, the membership form (0: binary search in the sorted (region, place id) table),
+ * segments ranked from rows the host assembled, and the host synchronisations of the call. */
+int32_t locrec_rank_recommendations_batch_stats(int64_t *out_one_block, int64_t *out_split, int64_t *out_chunks,
+                                                int64_t *out_sorted, int64_t *out_membership_form,
+                                                int64_t *out_host_assembled, int64_t *out_host_syncs);
 
 /* ===================================================================== */
 /* The place deduplicator (deduplicator/PlaceDeduplicator.scala,          */

@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("LOCREC_LIB_PATH") or os.path.join(_HERE, "liblocrec.s
 OK, E_INVALID_ARG, E_NOT_FOUND, E_DEVICE, E_OOM, E_ARITHMETIC = 0, 1, 2, 3, 4, 5
 MEM_HOST, MEM_DEVICE = 0, 1
 KNN_BATCH_MAX_K = 1024
+RANK_BATCH_MAX_N = 256
 
 
 class IllegalArgumentException(ValueError):
@@ -62,6 +63,9 @@ SIGNATURES = {
                                    _i64p, _i64p, _f64p, _i64p],
     "locrec_knn_recommend_range_async": [C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int64],
     "locrec_knn_fetch_recommend": [C.c_void_p, C.c_int64, _i64p, _i64p, _f64p, _i64p],
+    "locrec_knn_recommend_ranked_batch": [C.c_void_p, C.c_int64, _i64p, C.c_double, C.c_double, C.c_int64,
+                                          C.c_int64, _i64p, _i64p, _i64p, C.c_int64, _i64p, _f64p, _i64p],
+    "locrec_knn_fetch_ranked": [C.c_void_p, C.c_int64, C.c_int64, _i64p, _i64p, _i64p, C.c_int64, _i64p, _f64p, _i64p],
     "locrec_knn_query_shard": [C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int64, C.c_int32, C.c_int32,
                                _i64p, _f64p, _i64p],
     "locrec_knn_recommend_neighbours": [C.c_void_p, C.c_int64, _i64p, _f64p, _i64p, _f64p, _i64p],
@@ -136,6 +140,10 @@ SIGNATURES = {
     "locrec_distance_meters": [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p],
     "locrec_rank_recommendations": [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                     C.c_int32, C.c_void_p, C.c_void_p, _i64p],
+    # the segmented ranker (rank_batch.hip)
+    "locrec_rank_recommendations_batch": [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
+    "locrec_rank_recommendations_batch_stats": [_i64p, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p],
     # the place deduplicator (dedup.hip)
     "locrec_lev_distances": [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p],
     "locrec_find_duplicate_places": [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -206,3 +206,6 @@ extern "C" int32_t locrec_knn_recommend_batch(locrec_knn_index *ix, int64_t nq, 
     LOCREC_TRY(enqueue_any_k_recommend(ix, rows, pw, cw, k));
     return locrec_knn_fetch_recommend(ix, nq, out_offsets, out_places, out_ratings, inout_capacity);
 } LOCREC_CATCH_ALL
+
+// the ranked forms of the two recommend calls above (and locrec_knn_fetch_ranked for the range form)
+#include "knn_ranked.h"

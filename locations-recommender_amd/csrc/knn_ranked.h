@@ -1,0 +1,195 @@
+// knn_ranked.h -- the ranked KNN batches (included by knn_batch.hip behind knn.hip): the rows a batched
+// makeRecommendations left on the device are ranked where they are by the segmented ranker (rank_batch.h), and only
+// max_recommendations rows a person travel to the host.  Two resident forms:
+//   [nq x agg_M] agg_place / agg_est with agg_n    K <= LOCREC_KNN_BATCH_MAX_K (enqueue_aggregate)
+//   lkb_place / lkb_est with lkb_off               every other K (knn_large.hip)
+// The sizes come from locrec_knn_fetch_recommend itself, called for the offsets only (by locrec_knn_recommend_batch in
+// the batch form, here in the range form): that call carries the redo after a survivor-queue overflow, so the rows are
+// settled when it returns.  Queries whose aggregation overflowed its block (agg_overflow) have no resident rows:
+// knn_large_recommend assembles them on the host, as the row fetch does - in one pass, their row counts being known
+// from the fetch - and they are uploaded and ranked as segments of a second ranker call (counted as host-assembled in
+// the stats).  (The fetch's own count-and-discard passes over those queries are inside knn.hip, whose bytes are hashed.)
+#pragma once
+
+#include "rank_batch.h"
+
+namespace {
+
+// segment c of the result = the resident rows of processing slot slots[c], ranked for targets[c] (host arrays).
+// known_len: the segments' row counts where the caller has them from a fetch that already settled the rows (the batch
+// form: locrec_knn_recommend_batch sizes its result through locrec_knn_fetch_recommend); NULL: that fetch is made here.
+int32_t knn_rank_resident(locrec_knn_index *ix, const std::vector<int64_t> &slots, const int64_t *known_len, int64_t n_places,
+                          const int64_t *place_ids, const int64_t *place_region_ids, const int64_t *targets,
+                          int64_t max_recommendations, int64_t *out_ids, double *out_scores, int64_t *out_counts)
+{
+    const int64_t nseg = (int64_t)slots.size(), nq = ix->last_nq;
+    const int64_t N = std::max<int64_t>(0, max_recommendations);
+    if (n_places < 0 || n_places >= ((int64_t)1 << 31)) return fail(LOCREC_E_INVALID_ARG, "place count out of range [0, 2^31)");
+    if (!out_counts || !targets || (N > 0 && (!out_ids || !out_scores)) || (n_places > 0 && (!place_ids || !place_region_ids)))
+        return fail(LOCREC_E_INVALID_ARG, "NULL argument");
+    std::vector<int64_t> off((size_t)nq + 1, 0);
+    if (!known_len) {
+        int64_t cap = 0;
+        LOCREC_TRY(locrec_knn_fetch_recommend(ix, nq, off.data(), nullptr, nullptr, &cap));  // sizes only; settles the rows
+    }
+    LOCREC_HIP_TRY(hipSetDevice(ix->device));
+    hipStream_t s = ix->stream;
+    const bool lkb = ix->have_lkb;
+    if (lkb && ix->lkb_deferred) return fail(LOCREC_E_INVALID_ARG, "the batch's rows are not resident");
+    std::vector<int32_t> ovf((size_t)nq, 0);
+    if (!lkb) {
+        LOCREC_HIP_TRY(hipMemcpyAsync(ovf.data(), ix->agg_overflow.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+        LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    }
+    std::vector<int64_t> hb((size_t)nseg), hl((size_t)nseg), hosted;
+    for (int64_t c = 0; c < nseg; ++c) {
+        const int64_t q = slots[(size_t)c];
+        const int64_t len = known_len ? known_len[c] : off[(size_t)q + 1] - off[(size_t)q];
+        hl[(size_t)c] = len;
+        if (ovf[(size_t)q]) {
+            hb[(size_t)c] = 0;
+            hosted.push_back(c);
+        } else {
+            hb[(size_t)c] = lkb ? ix->lkb_off[(size_t)q] : q * (int64_t)ix->agg_M;
+        }
+    }
+    std::vector<int64_t> host_len;  // of the host-assembled segments, known from the fetch
+    for (int64_t c : hosted) {
+        host_len.push_back(hl[(size_t)c]);
+        hl[(size_t)c] = 0;
+    }
+    std::fill(out_counts, out_counts + nseg, 0);
+    if (nseg == 0) return LOCREC_OK;
+    // one allocation for the call's inputs and one for its outputs (every hipMalloc / hipFree costs a wait)
+    DevBuf<int64_t> d_in, d_out;
+    LOCREC_TRY(d_in.alloc(2 * (size_t)n_places + 3 * (size_t)nseg));
+    LOCREC_TRY(d_out.alloc(2 * (size_t)(nseg * N) + (size_t)nseg));
+    struct I64 {
+        int64_t *p;
+    } d_pid = {d_in.p}, d_preg = {d_in.p + n_places}, d_tgt = {d_in.p + 2 * n_places}, d_b = {d_tgt.p + nseg},
+      d_l = {d_b.p + nseg}, d_oid = {d_out.p}, d_ocnt = {d_out.p + 2 * nseg * N};
+    struct {
+        double *p;
+    } d_osc = {reinterpret_cast<double *>(d_out.p + nseg * N)};
+    if (n_places > 0) {
+        LOCREC_HIP_TRY(hipMemcpyAsync(d_pid.p, place_ids, (size_t)n_places * 8, hipMemcpyHostToDevice, s));
+        LOCREC_HIP_TRY(hipMemcpyAsync(d_preg.p, place_region_ids, (size_t)n_places * 8, hipMemcpyHostToDevice, s));
+    }
+    LOCREC_HIP_TRY(hipMemcpyAsync(d_tgt.p, targets, (size_t)nseg * 8, hipMemcpyHostToDevice, s));
+    LOCREC_HIP_TRY(hipMemcpyAsync(d_b.p, hb.data(), (size_t)nseg * 8, hipMemcpyHostToDevice, s));
+    LOCREC_HIP_TRY(hipMemcpyAsync(d_l.p, hl.data(), (size_t)nseg * 8, hipMemcpyHostToDevice, s));
+    LOCREC_TRY(rank_segments_device(nseg, d_b.p, d_l.p, lkb ? ix->lkb_place.p : ix->agg_place.p, lkb ? ix->lkb_est.p : ix->agg_est.p,
+                                    n_places, d_pid.p, d_preg.p, d_tgt.p, N, d_oid.p, d_osc.p, d_ocnt.p, nullptr, 0, s));
+    if (N > 0) {
+        LOCREC_HIP_TRY(hipMemcpyAsync(out_ids, d_oid.p, (size_t)(nseg * N) * 8, hipMemcpyDeviceToHost, s));
+        LOCREC_HIP_TRY(hipMemcpyAsync(out_scores, d_osc.p, (size_t)(nseg * N) * 8, hipMemcpyDeviceToHost, s));
+    }
+    LOCREC_HIP_TRY(hipMemcpyAsync(out_counts, d_ocnt.p, (size_t)nseg * 8, hipMemcpyDeviceToHost, s));
+    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    RankBatchStats total = rank_batch_stats();
+    ++total.host_syncs;
+    if (!hosted.empty()) {
+        // rows of the overflow queries: assembled on the host once per slot, uploaded, ranked as their own segments
+        const int64_t nh = (int64_t)hosted.size();
+        std::vector<int64_t> rp, tb((size_t)nh), tl((size_t)nh), tt((size_t)nh);
+        std::vector<double> re;
+        std::vector<int64_t> slot_begin((size_t)nq, -1), slot_len((size_t)nq, 0);
+        for (int64_t i = 0; i < nh; ++i) {
+            const int64_t q = slots[(size_t)hosted[(size_t)i]];
+            if (slot_begin[(size_t)q] < 0) {
+                const int32_t row = ix->agg_rows.empty() ? ix->agg_first + (int32_t)q : ix->agg_rows[(size_t)q];
+                int64_t c = host_len[(size_t)i];  // one pass: the fetch has counted the rows
+                const size_t at = rp.size();
+                rp.resize(at + (size_t)c);
+                re.resize(at + (size_t)c);
+                LOCREC_TRY(knn_large_recommend(ix, row, ix->agg_pw, ix->agg_cw, ix->last_k, rp.data() + at, re.data() + at, &c));
+                if (c != host_len[(size_t)i]) return fail(LOCREC_E_DEVICE, "internal: an overflow query changed its row count");
+                slot_begin[(size_t)q] = (int64_t)at;
+                slot_len[(size_t)q] = c;
+            }
+            tb[(size_t)i] = slot_begin[(size_t)q];
+            tl[(size_t)i] = slot_len[(size_t)q];
+            tt[(size_t)i] = targets[hosted[(size_t)i]];
+        }
+        DevBuf<int64_t> d_rp, d_tb, d_tl, d_tt, d_hid, d_hcnt;
+        DevBuf<double> d_re, d_hsc;
+        LOCREC_TRY(d_rp.upload(rp, s));
+        LOCREC_TRY(d_re.upload(re, s));
+        LOCREC_TRY(d_tb.upload(tb, s));
+        LOCREC_TRY(d_tl.upload(tl, s));
+        LOCREC_TRY(d_tt.upload(tt, s));
+        LOCREC_TRY(d_hid.alloc((size_t)(nh * N)));
+        LOCREC_TRY(d_hsc.alloc((size_t)(nh * N)));
+        LOCREC_TRY(d_hcnt.alloc((size_t)nh));
+        LOCREC_TRY(rank_segments_device(nh, d_tb.p, d_tl.p, d_rp.p, d_re.p, n_places, d_pid.p, d_preg.p, d_tt.p, N, d_hid.p,
+                                        d_hsc.p, d_hcnt.p, nullptr, nh, s));
+        std::vector<int64_t> hid((size_t)(nh * N)), hcnt((size_t)nh);
+        std::vector<double> hsc((size_t)(nh * N));
+        if (N > 0) {
+            LOCREC_HIP_TRY(hipMemcpyAsync(hid.data(), d_hid.p, (size_t)(nh * N) * 8, hipMemcpyDeviceToHost, s));
+            LOCREC_HIP_TRY(hipMemcpyAsync(hsc.data(), d_hsc.p, (size_t)(nh * N) * 8, hipMemcpyDeviceToHost, s));
+        }
+        LOCREC_HIP_TRY(hipMemcpyAsync(hcnt.data(), d_hcnt.p, (size_t)nh * 8, hipMemcpyDeviceToHost, s));
+        LOCREC_HIP_TRY(hipStreamSynchronize(s));
+        for (int64_t i = 0; i < nh; ++i) {
+            const int64_t c = hosted[(size_t)i];
+            std::copy(hid.begin() + i * N, hid.begin() + (i + 1) * N, out_ids + c * N);
+            std::copy(hsc.begin() + i * N, hsc.begin() + (i + 1) * N, out_scores + c * N);
+            out_counts[c] = hcnt[(size_t)i];
+        }
+        const RankBatchStats &h = rank_batch_stats();
+        // (the overflow queries were empty one-block segments of the first call: counted where their rows were ranked)
+        if (!h.sorted) {
+            total.one_block += h.one_block - nh;
+            total.split += h.split;
+            total.chunks += h.chunks;
+        }
+        total.host_assembled = nh;
+        total.host_syncs += h.host_syncs + 1;
+    }
+    rank_batch_stats() = total;
+    return LOCREC_OK;
+}
+
+}  // namespace
+
+extern "C" int32_t locrec_knn_fetch_ranked(locrec_knn_index *ix, int64_t nq, int64_t n_places, const int64_t *place_ids,
+                                           const int64_t *place_region_ids, const int64_t *target_region_ids,
+                                           int64_t max_recommendations, int64_t *out_place_ids, double *out_estimated_ratings,
+                                           int64_t *out_counts) try
+{
+    if (!ix) return fail(LOCREC_E_INVALID_ARG, "index is NULL");
+    if (nq != ix->last_nq || nq <= 0 || !(ix->have_lkb || (ix->have_agg && ix->have_result)))
+        return fail(LOCREC_E_INVALID_ARG, "no matching batched recommendation to fetch");
+    std::vector<int64_t> slots((size_t)nq);
+    std::iota(slots.begin(), slots.end(), (int64_t)0);
+    return knn_rank_resident(ix, slots, nullptr, n_places, place_ids, place_region_ids, target_region_ids, max_recommendations,
+                             out_place_ids, out_estimated_ratings, out_counts);
+} LOCREC_CATCH_ALL
+
+extern "C" int32_t locrec_knn_recommend_ranked_batch(locrec_knn_index *ix, int64_t nq, const int64_t *person_ids, double pw,
+                                                     double cw, int64_t k, int64_t n_places, const int64_t *place_ids,
+                                                     const int64_t *place_region_ids, const int64_t *target_region_ids,
+                                                     int64_t max_recommendations, int64_t *out_place_ids,
+                                                     double *out_estimated_ratings, int64_t *out_counts) try
+{
+    // the batch itself, with its requires and "No such person": the rows stay on the device (capacity 0: sizes only)
+    std::vector<int64_t> off((size_t)std::max<int64_t>(nq, 0) + 1, 0);
+    int64_t cap = 0;
+    LOCREC_TRY(locrec_knn_recommend_batch(ix, nq, person_ids, pw, cw, k, off.data(), nullptr, nullptr, &cap));
+    if (nq == 0) return LOCREC_OK;
+    // the caller's order: every person's segment is the processing slot that holds its row (a repeated person: the same)
+    std::vector<std::pair<int32_t, int64_t>> by_row((size_t)nq);
+    for (int64_t i = 0; i < nq; ++i) by_row[(size_t)i] = {ix->agg_rows[(size_t)i], i};
+    std::sort(by_row.begin(), by_row.end());
+    std::vector<int64_t> slots((size_t)nq);
+    for (int64_t i = 0; i < nq; ++i) {
+        int32_t row = 0;
+        LOCREC_TRY(find_query_row(ix, person_ids[i], &row));
+        slots[(size_t)i] = std::lower_bound(by_row.begin(), by_row.end(), std::make_pair(row, (int64_t)-1))->second;
+    }
+    std::vector<int64_t> len((size_t)nq);
+    for (int64_t i = 0; i < nq; ++i) len[(size_t)i] = off[(size_t)i + 1] - off[(size_t)i];
+    return knn_rank_resident(ix, slots, len.data(), n_places, place_ids, place_region_ids, target_region_ids,
+                             max_recommendations, out_place_ids, out_estimated_ratings, out_counts);
+} LOCREC_CATCH_ALL

@@ -1,5 +1,5 @@
 // place_grid.h -- what the two spatial joins share (prep.hip: calcPlaceVisits; dedup.hip: the place deduplicator):
-// the column helpers of the producers, Location.scala's haversine and range check, and the per-region
+// Location.scala's haversine and range check, and the per-region
 // band / cell grid whose cells are at least one search radius wide.  Included by both translation units;
 // everything lives in an unnamed namespace, so each unit gets its own copy.
 #pragma once
@@ -10,79 +10,11 @@
 #include <cmath>
 
 #include "common.h"
+#include "prep_cols.h"
 
 namespace {
 
 using namespace locrec;
-
-struct Temp {
-    DevBuf<unsigned char> buf;
-};
-
-#define PR_PRIM(tmp, call_with_args)                   \
-    do {                                              \
-        size_t bytes_ = 0;                            \
-        void *p_ = nullptr;                           \
-        LOCREC_HIP_TRY((call_with_args));             \
-        LOCREC_TRY((tmp).buf.reserve(bytes_ + 256));  \
-        p_ = (tmp).buf.p;                             \
-        LOCREC_HIP_TRY((call_with_args));             \
-    } while (0)
-
-dim3 grid_for(int64_t n, int threads = 256) { return dim3((unsigned)std::max<int64_t>(1, (n + threads - 1) / threads)); }
-
-constexpr int64_t kMaxRows = (int64_t)1 << 31;  // row numbers travel as u32 sort payloads
-
-// An input column: the caller's array, on the device.  Host arrays are uploaded into `own`.
-template <class T>
-struct In {
-    DevBuf<T> own;
-    const T *p = nullptr;
-    int32_t bind(const T *src, int64_t n, int32_t mem, hipStream_t s)
-    {
-        if (mem == LOCREC_MEM_DEVICE || n == 0) {
-            p = src;
-            return LOCREC_OK;
-        }
-        LOCREC_TRY(own.upload(src, (size_t)n, s));
-        p = own.p;
-        return LOCREC_OK;
-    }
-};
-
-// An output column: the caller's device array, or a staging buffer copied back to the host array.
-template <class T>
-struct Out {
-    DevBuf<T> own;
-    T *p = nullptr;
-    T *host = nullptr;
-    int32_t bind(T *dst, int64_t cap, int32_t mem)
-    {
-        if (mem == LOCREC_MEM_DEVICE) {
-            p = dst;
-            return LOCREC_OK;
-        }
-        host = dst;
-        LOCREC_TRY(own.alloc((size_t)std::max<int64_t>(cap, 1)));
-        p = own.p;
-        return LOCREC_OK;
-    }
-    int32_t deliver(int64_t count, hipStream_t s)
-    {
-        if (host && count > 0) LOCREC_HIP_TRY(hipMemcpyAsync(host, p, (size_t)count * sizeof(T), hipMemcpyDeviceToHost, s));
-        return LOCREC_OK;
-    }
-};
-
-__device__ __forceinline__ uint64_t ordered_key(int64_t v) { return (uint64_t)v ^ 0x8000000000000000ull; }  // signed order
-
-__global__ void pr_iota_keys(int64_t n, const int64_t *col, uint64_t *keys, uint32_t *rows)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    keys[i] = ordered_key(col[i]);
-    rows[i] = (uint32_t)i;
-}
 
 constexpr double kEarthRadiusMeters = 6371.0 * 1000.0;  // Location.scala:28
 constexpr double kPi = 3.14159265358979323846;
@@ -182,22 +114,6 @@ __global__ void pr_place_keys(int64_t np, const double *lat, const double *lon, 
     const double w = 360.0 / nx;
     const int32_t cx = min(max((int32_t)floor((lon[j] + 180.0) / w), 0), nx - 1);
     keys[j] = ((uint64_t)r << (2 * kCellBits)) | ((uint64_t)b << kCellBits) | (uint64_t)cx;
-}
-
-__device__ __forceinline__ int64_t lower_bound_key(const uint64_t *keys, int64_t n, uint64_t key)
-{
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (keys[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-int32_t mem_ok(int32_t mem)
-{
-    if (mem != LOCREC_MEM_HOST && mem != LOCREC_MEM_DEVICE) return fail(LOCREC_E_INVALID_ARG, "mem must be LOCREC_MEM_HOST or LOCREC_MEM_DEVICE");
-    return LOCREC_OK;
 }
 
 }  // namespace

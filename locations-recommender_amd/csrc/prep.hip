@@ -823,17 +823,6 @@ __global__ void pr_rank_flags(int64_t n, const int64_t *ids, const uint64_t *all
     keep[i] = lo < nallowed && allowed[lo] == k ? 1 : 0;
 }
 
-// Spark SQL's order of doubles: every NaN, whatever its sign and payload, is one value above
-// +inf, and -0.0 equals 0.0 - so both are made one bit pattern before the usual monotone map
-__device__ __forceinline__ uint64_t score_desc_key(double s)
-{
-    uint64_t b = (uint64_t)__double_as_longlong(s);
-    if (s != s) b = 0x7FF8000000000000ull;
-    else if (s == 0.0) b = 0ull;
-    b = (b >> 63) ? ~b : b | 0x8000000000000000ull;  // ascending order of the doubles
-    return ~b;                                       // ... descending
-}
-
 __global__ void pr_rank_keys_by_id(int64_t m, const uint32_t *rows, const int64_t *ids, uint64_t *keys)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

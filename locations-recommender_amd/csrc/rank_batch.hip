@@ -1,0 +1,671 @@
+// rank_batch.hip -- the last stage of a batched request, where the rows already are: per segment of one (ids, scores)
+// pair, "places of the target region JOIN rows ON id, ORDER BY score DESC, LIMIT N" (printRecommendations of both mains,
+// knn/KnnRecommenderMain.scala:90-101, stochastic/StochasticRecommenderMain.scala:64-75) - exactly what
+// locrec_rank_recommendations (prep.hip) returns for each segment on its own, at 16 N bytes a segment.
+//
+//   region table, once per call   the (region, place id) pairs sorted by two stable radix passes; a segment finds its
+//                                 region's range once (rb_plan), a row's membership test is a binary search inside it.
+//                                 Duplicates stay in the table: a search finds a place listed twice once.
+//   rb_select                     one block per (segment, chunk of LOCREC_RANK_BATCH_CHUNK rows): streams the rows
+//                                 coalesced, drops non-members and rows not below the threshold, appends the rest to an
+//                                 LDS buffer of 1024 entries; a full buffer is compacted by a block-wide bitonic sort
+//                                 that keeps the best N and raises the threshold (the pattern of the KNN lists,
+//                                 knn_device.h).  The order is the 3-part key (score_desc_key, id, row in the segment):
+//                                 unique per row, so the result does not depend on the arrival order in the buffer.
+//                                 A segment of one chunk writes its output row; a chunk of a split segment its partial.
+//   rb_merge                      launched only when a segment was split, one block per segment (a block of an unsplit
+//                                 segment returns at once): the chunks' partial lists through the same list.
+//   N > LOCREC_RANK_BATCH_MAX_N   (or LOCREC_RANK_BATCH_SORT=1) the global path: the kept rows of all segments are
+//                                 compacted in order (rb_count, scan, rb_scatter), sorted by three stable radix passes
+//                                 (id, score key, segment) and the first N of every segment emitted (rb_emit_sorted).
+//
+// A call waits for the stream once (the plan's totals and the validity of the segments, before any kernel reads a row)
+// and, on the global path, once more for the number of kept rows - whatever the number of segments.  Its work buffers
+// are local to the call: each hipFree at the end waits for the device as well (about twenty a call, again whatever the
+// number of segments; the partial lists of the split segments live until theirs).
+//
+// hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage (VGPRs / LDS bytes / scratch / waves per SIMD):
+//   rb_select       27 / 20512 / 0 / 7
+//   rb_merge        27 / 20512 / 0 / 7
+//   rb_count        12 / 4 / 0 / 8
+//   rb_scatter      24 / 16 / 0 / 8
+//   rb_emit_sorted  14 / 16 / 0 / 8
+// The list is 20 bytes an entry: 20.5 KB of LDS a block, seven blocks of 256 threads a CU by LDS.
+
+#include "dev_prims.h"
+
+#include <algorithm>
+
+#include "common.h"
+#include "prep_cols.h"
+#include "rank_batch.h"
+
+namespace locrec {
+
+RankBatchStats &rank_batch_stats()
+{
+    thread_local RankBatchStats st;
+    return st;
+}
+
+}  // namespace locrec
+
+namespace {
+
+using namespace locrec;
+
+constexpr int kRbThreads = 256;
+constexpr int kRbCap = 1024;               // entries of the LDS buffer
+constexpr int64_t kRbDefaultChunk = 4096;  // rows per chunk of a split segment
+static_assert(LOCREC_RANK_BATCH_MAX_N <= kRbCap - kRbThreads, "a compacted list plus one tile must fit the buffer");
+
+// LOCREC_RANK_BATCH_CHUNK: rows per chunk; LOCREC_RANK_BATCH_SORT=1: the global path for every N (both read per call)
+int64_t rb_chunk_rows()
+{
+    int64_t c = kRbDefaultChunk;
+    if (const char *e = std::getenv("LOCREC_RANK_BATCH_CHUNK")) c = atoll(e);
+    return std::min<int64_t>(std::max<int64_t>(c, 1), (int64_t)1 << 30);
+}
+
+bool rb_force_sort()
+{
+    const char *e = std::getenv("LOCREC_RANK_BATCH_SORT");
+    return e && atoi(e) != 0;
+}
+
+__global__ void rb_gather_keys(int64_t n, const int64_t *col, const uint32_t *rows, uint64_t *keys)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) keys[i] = ordered_key(col[rows[i]]);
+}
+
+// offsets -> (begin, length) per segment; flag: a negative or decreasing offset, or one beyond n.  Reads the offsets
+// only, never through them.
+__global__ void rb_prepare(int64_t n_seg, const int64_t *offsets, int64_t n, int64_t *seg_begin, int64_t *seg_len,
+                           unsigned long long *invalid)
+{
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n_seg) return;
+    const int64_t b = offsets[s], e = offsets[s + 1];
+    const bool ok = b >= 0 && e >= b && e <= n;
+    seg_begin[s] = ok ? b : 0;
+    seg_len[s] = ok ? e - b : 0;
+    if (!ok) atomicOr(invalid, 1ull);
+}
+
+// hdr: [0] invalid, [1] work items, [2] split segments, [3] their chunks
+__global__ void rb_plan(int64_t n_seg, const int64_t *seg_begin, const int64_t *seg_len, const int64_t *targets, int64_t np,
+                        const uint64_t *table_regions, int64_t chunk, const unsigned long long *invalid_in, uint32_t *nch,
+                        uint32_t *split_nch, int32_t *lo, int32_t *hi, unsigned long long *hdr)
+{
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s == 0 && invalid_in && *invalid_in) atomicOr(&hdr[0], 1ull);
+    if (s > n_seg) return;
+    if (s == n_seg) {  // the scans' last element
+        nch[s] = 0;
+        split_nch[s] = 0;
+        return;
+    }
+    const int64_t len = seg_len[s];
+    const bool ok = len >= 0 && len < kMaxRows && seg_begin[s] >= 0;
+    if (!ok) atomicOr(&hdr[0], 1ull);
+    const uint64_t rk = ordered_key(targets[s]);
+    const int64_t a = lower_bound_key(table_regions, np, rk);
+    const int64_t b = rk == ~0ull ? np : lower_bound_key(table_regions, np, rk + 1);
+    lo[s] = (int32_t)a;
+    hi[s] = (int32_t)b;
+    uint32_t c = 1;
+    if (ok && b > a && len > chunk) c = (uint32_t)((len + chunk - 1) / chunk);
+    nch[s] = c;
+    split_nch[s] = c > 1 ? c : 0;
+    atomicAdd(&hdr[1], (unsigned long long)c);
+    if (c > 1) {
+        atomicAdd(&hdr[2], 1ull);
+        atomicAdd(&hdr[3], (unsigned long long)c);
+    }
+}
+
+// ---- the list of one block -------------------------------------------------------------------------------------------
+
+struct RbList {
+    uint64_t k[kRbCap];    // score_desc_key
+    uint64_t id[kRbCap];   // ordered_key of the id
+    uint32_t row[kRbCap];  // row inside the segment
+    uint64_t thr_k, thr_id;
+    uint32_t thr_row;
+    int count, have_thr;
+};
+
+__device__ __forceinline__ bool rb_less(uint64_t ka, uint64_t ia, uint32_t ra, uint64_t kb, uint64_t ib, uint32_t rb)
+{
+    if (ka != kb) return ka < kb;
+    if (ia != ib) return ia < ib;
+    return ra < rb;
+}
+
+// ascending bitonic sort of entries [0, P), P a power of two <= kRbCap; every thread of the block
+__device__ void rb_sort(RbList &L, int P)
+{
+    for (int k = 2; k <= P; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = threadIdx.x; t < (P >> 1); t += kRbThreads) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+                const int p = i | j;
+                const uint64_t ka = L.k[i], kb = L.k[p], ia = L.id[i], ib = L.id[p];
+                const uint32_t ra = L.row[i], rb = L.row[p];
+                const bool up = (i & k) == 0;
+                const bool sw = up ? rb_less(kb, ib, rb, ka, ia, ra) : rb_less(ka, ia, ra, kb, ib, rb);
+                if (sw) {
+                    L.k[i] = kb; L.k[p] = ka;
+                    L.id[i] = ib; L.id[p] = ia;
+                    L.row[i] = rb; L.row[p] = ra;
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// sorts the buffer; with at least N entries keeps the best N and makes the N-th the threshold.  -> entries kept.
+// Every thread of the block, after a barrier behind the last append.
+__device__ int rb_compact(RbList &L, int N)
+{
+    const int cnt = L.count;
+    int P = 2;
+    while (P < cnt) P <<= 1;
+    for (int i = cnt + threadIdx.x; i < P; i += kRbThreads) {  // above every real entry (no score has the key ~0)
+        L.k[i] = ~0ull;
+        L.id[i] = ~0ull;
+        L.row[i] = ~0u;
+    }
+    __syncthreads();
+    rb_sort(L, P);
+    const int w = min(cnt, N);
+    if (threadIdx.x == 0 && cnt >= N) {
+        L.count = N;
+        L.thr_k = L.k[N - 1];
+        L.thr_id = L.id[N - 1];
+        L.thr_row = L.row[N - 1];
+        L.have_thr = 1;
+    }
+    __syncthreads();
+    return w;
+}
+
+__device__ __forceinline__ void rb_push(RbList &L, uint64_t k, uint64_t id, uint32_t row)
+{
+    if (L.have_thr && !rb_less(k, id, row, L.thr_k, L.thr_id, L.thr_row)) return;
+    const int slot = atomicAdd(&L.count, 1);  // < kRbCap: at most kRbCap - kRbThreads before a tile
+    L.k[slot] = k;
+    L.id[slot] = id;
+    L.row[slot] = row;
+}
+
+// before a tile's appends: the count is read by all between two barriers, so the decision to compact is uniform
+__device__ __forceinline__ void rb_make_room(RbList &L, int N)
+{
+    __syncthreads();
+    const int cnt = L.count;
+    __syncthreads();
+    if (cnt > kRbCap - kRbThreads) rb_compact(L, N);
+}
+
+// the segment of work item w: the last s with first[s] <= w (first[] strictly increasing, first[0] = 0)
+__device__ __forceinline__ int64_t rb_segment_of(const uint32_t *first, int64_t n_seg, uint32_t w)
+{
+    int64_t a = 0, b = n_seg;
+    while (a < b) {
+        const int64_t mid = (a + b) >> 1;
+        if (first[mid] <= w) a = mid + 1; else b = mid;
+    }
+    return a - 1;
+}
+
+// the sorted list's first w entries -> output row s (padded to N)
+__device__ __forceinline__ void rb_emit_row(const RbList &L, int w, int N, int64_t s, int64_t begin, const double *scores,
+                                            int64_t *out_ids, double *out_scores, int64_t *out_counts)
+{
+    for (int j = threadIdx.x; j < N; j += kRbThreads) {
+        const int64_t o = s * (int64_t)N + j;
+        out_ids[o] = j < w ? (int64_t)(L.id[j] ^ 0x8000000000000000ull) : -1;
+        out_scores[o] = j < w ? scores[begin + L.row[j]] : 0.0;
+    }
+    if (threadIdx.x == 0) out_counts[s] = w;
+}
+
+__global__ __launch_bounds__(kRbThreads) void rb_select(int64_t n_seg, const uint32_t *first, const uint32_t *pfirst,
+                                                        const int64_t *seg_begin, const int64_t *seg_len, const int32_t *lo,
+                                                        const int32_t *hi, const uint64_t *table_ids, const int64_t *ids,
+                                                        const double *scores, int64_t chunk, int N, uint64_t *pk,
+                                                        uint64_t *pid, uint32_t *prow, int32_t *pcount, int64_t *out_ids,
+                                                        double *out_scores, int64_t *out_counts)
+{
+    __shared__ RbList L;
+    const uint32_t w = blockIdx.x;
+    const int64_t s = rb_segment_of(first, n_seg, w);
+    const uint32_t nch = first[s + 1] - first[s], c = w - first[s];
+    const int64_t begin = seg_begin[s], len = seg_len[s];
+    const int32_t tlo = lo[s], thi = hi[s];
+    const int64_t r0 = (int64_t)c * chunk;
+    const int64_t r1 = thi > tlo ? min(len, nch == 1 ? len : r0 + chunk) : 0;  // no place in the region: nothing to read
+    if (threadIdx.x == 0) {
+        L.count = 0;
+        L.have_thr = 0;
+    }
+    for (int64_t t0 = r0; t0 < r1; t0 += kRbThreads) {
+        rb_make_room(L, N);
+        const int64_t r = t0 + threadIdx.x;
+        if (r < r1) {
+            const uint64_t key = ordered_key(ids[begin + r]);
+            int32_t a = tlo, b = thi;
+            while (a < b) {
+                const int32_t mid = (int32_t)(((uint32_t)a + (uint32_t)b) >> 1);
+                if (table_ids[mid] < key) a = mid + 1; else b = mid;
+            }
+            if (a < thi && table_ids[a] == key) rb_push(L, score_desc_key(scores[begin + r]), key, (uint32_t)r);
+        }
+    }
+    __syncthreads();
+    const int wn = rb_compact(L, N);
+    if (nch == 1) {
+        rb_emit_row(L, wn, N, s, begin, scores, out_ids, out_scores, out_counts);
+        return;
+    }
+    const int64_t slot = (int64_t)pfirst[s] + c;
+    for (int j = threadIdx.x; j < wn; j += kRbThreads) {
+        pk[slot * N + j] = L.k[j];
+        pid[slot * N + j] = L.id[j];
+        prow[slot * N + j] = L.row[j];
+    }
+    if (threadIdx.x == 0) pcount[slot] = wn;
+}
+
+__global__ __launch_bounds__(kRbThreads) void rb_merge(const uint32_t *first, const uint32_t *pfirst, const int64_t *seg_begin,
+                                                       const double *scores, int N, const uint64_t *pk, const uint64_t *pid,
+                                                       const uint32_t *prow, const int32_t *pcount, int64_t *out_ids,
+                                                       double *out_scores, int64_t *out_counts)
+{
+    __shared__ RbList L;
+    const int64_t s = blockIdx.x;
+    const uint32_t nch = first[s + 1] - first[s];
+    if (nch <= 1) return;
+    const int64_t slot0 = pfirst[s], total = (int64_t)nch * N;
+    if (threadIdx.x == 0) {
+        L.count = 0;
+        L.have_thr = 0;
+    }
+    for (int64_t t0 = 0; t0 < total; t0 += kRbThreads) {
+        rb_make_room(L, N);
+        const int64_t t = t0 + threadIdx.x;
+        if (t < total) {
+            const int64_t c = t / N;
+            const int j = (int)(t - c * N);
+            if (j < pcount[slot0 + c]) rb_push(L, pk[slot0 * N + t], pid[slot0 * N + t], prow[slot0 * N + t]);
+        }
+    }
+    __syncthreads();
+    const int wn = rb_compact(L, N);
+    rb_emit_row(L, wn, N, s, seg_begin[s], scores, out_ids, out_scores, out_counts);
+}
+
+// ---- the global path --------------------------------------------------------------------------------------------------
+
+// kept rows of one work item
+__global__ __launch_bounds__(kRbThreads) void rb_count(int64_t n_seg, const uint32_t *first, const int64_t *seg_begin,
+                                                       const int64_t *seg_len, const int32_t *lo, const int32_t *hi,
+                                                       const uint64_t *table_ids, const int64_t *ids, int64_t chunk,
+                                                       uint32_t *cnt, uint32_t n_items)
+{
+    __shared__ uint32_t total;
+    const uint32_t w = blockIdx.x;
+    if (threadIdx.x == 0) total = 0;
+    __syncthreads();
+    if (w == n_items) {  // the scan's last element
+        if (threadIdx.x == 0) cnt[w] = 0;
+        return;
+    }
+    const int64_t s = rb_segment_of(first, n_seg, w);
+    const uint32_t nch = first[s + 1] - first[s], c = w - first[s];
+    const int64_t begin = seg_begin[s], len = seg_len[s];
+    const int32_t tlo = lo[s], thi = hi[s];
+    const int64_t r0 = (int64_t)c * chunk;
+    const int64_t r1 = thi > tlo ? min(len, nch == 1 ? len : r0 + chunk) : 0;
+    uint32_t mine = 0;
+    for (int64_t r = r0 + threadIdx.x; r < r1; r += kRbThreads) {
+        const uint64_t key = ordered_key(ids[begin + r]);
+        int32_t a = tlo, b = thi;
+        while (a < b) {
+            const int32_t mid = (int32_t)(((uint32_t)a + (uint32_t)b) >> 1);
+            if (table_ids[mid] < key) a = mid + 1; else b = mid;
+        }
+        if (a < thi && table_ids[a] == key) ++mine;
+    }
+    if (mine) atomicAdd(&total, mine);
+    __syncthreads();
+    if (threadIdx.x == 0) cnt[w] = total;
+}
+
+// the kept rows of one work item, in row order, at base[w] ..: segment, row, id key, and the row's own position as the
+// payload of the first sort
+__global__ __launch_bounds__(kRbThreads) void rb_scatter(int64_t n_seg, const uint32_t *first, const int64_t *seg_begin,
+                                                         const int64_t *seg_len, const int32_t *lo, const int32_t *hi,
+                                                         const uint64_t *table_ids, const int64_t *ids, int64_t chunk,
+                                                         const uint32_t *base, uint32_t *kseg, uint32_t *krow,
+                                                         uint64_t *keys, uint32_t *vals)
+{
+    __shared__ uint32_t wave_cnt[kRbThreads / 64];
+    const uint32_t w = blockIdx.x;
+    const int64_t s = rb_segment_of(first, n_seg, w);
+    const uint32_t nch = first[s + 1] - first[s], c = w - first[s];
+    const int64_t begin = seg_begin[s], len = seg_len[s];
+    const int32_t tlo = lo[s], thi = hi[s];
+    const int64_t r0 = (int64_t)c * chunk;
+    const int64_t r1 = thi > tlo ? min(len, nch == 1 ? len : r0 + chunk) : 0;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t pos = base[w];
+    for (int64_t t0 = r0; t0 < r1; t0 += kRbThreads) {
+        const int64_t r = t0 + threadIdx.x;
+        bool keep = false;
+        uint64_t key = 0;
+        if (r < r1) {
+            key = ordered_key(ids[begin + r]);
+            int32_t a = tlo, b = thi;
+            while (a < b) {
+                const int32_t mid = (int32_t)(((uint32_t)a + (uint32_t)b) >> 1);
+                if (table_ids[mid] < key) a = mid + 1; else b = mid;
+            }
+            keep = a < thi && table_ids[a] == key;
+        }
+        const unsigned long long m = __ballot(keep);
+        __syncthreads();  // the previous tile's wave_cnt has been read
+        if (lane == 0) wave_cnt[wave] = (uint32_t)__popcll(m);
+        __syncthreads();
+        uint32_t before = 0, all = 0;
+        for (int v = 0; v < kRbThreads / 64; ++v) {
+            if (v < wave) before += wave_cnt[v];
+            all += wave_cnt[v];
+        }
+        if (keep) {
+            const uint32_t p = pos + before + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+            kseg[p] = (uint32_t)s;
+            krow[p] = (uint32_t)r;
+            keys[p] = key;
+            vals[p] = p;
+        }
+        pos += all;
+    }
+}
+
+__global__ void rb_score_keys(int64_t m, const uint32_t *vals, const uint32_t *kseg, const uint32_t *krow,
+                              const int64_t *seg_begin, const double *scores, uint64_t *keys)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const uint32_t v = vals[i];
+    keys[i] = score_desc_key(scores[seg_begin[kseg[v]] + krow[v]]);
+}
+
+__global__ void rb_segment_keys(int64_t m, const uint32_t *vals, const uint32_t *kseg, uint32_t *keys)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < m) keys[i] = kseg[vals[i]];
+}
+
+// output row s, slots [256 jt, 256 jt + 256): the first N of the segment's run in the sorted rows, then the padding
+__global__ __launch_bounds__(kRbThreads) void rb_emit_sorted(int64_t tiles, int64_t N, int64_t m, const uint32_t *seg_sorted,
+                                                             const uint32_t *vals, const uint32_t *krow,
+                                                             const int64_t *seg_begin, const int64_t *ids,
+                                                             const double *scores, int64_t *out_ids, double *out_scores,
+                                                             int64_t *out_counts)
+{
+    __shared__ int64_t range[2];
+    const int64_t s = blockIdx.x / tiles, jt = blockIdx.x % tiles;
+    if (threadIdx.x < 2) {  // lower bound of s and of s + 1
+        const uint64_t want = (uint64_t)s + threadIdx.x;
+        int64_t a = 0, b = m;
+        while (a < b) {
+            const int64_t mid = (a + b) >> 1;
+            if ((uint64_t)seg_sorted[mid] < want) a = mid + 1; else b = mid;
+        }
+        range[threadIdx.x] = a;
+    }
+    __syncthreads();
+    const int64_t lb = range[0], have = range[1] - range[0];
+    const int64_t j = jt * kRbThreads + threadIdx.x;
+    if (j < N) {
+        const int64_t o = s * N + j;
+        if (j < have) {
+            const int64_t r = seg_begin[s] + krow[vals[lb + j]];
+            out_ids[o] = ids[r];
+            out_scores[o] = scores[r];
+        } else {
+            out_ids[o] = -1;
+            out_scores[o] = 0.0;
+        }
+    }
+    if (jt == 0 && threadIdx.x == 0) out_counts[s] = min(have, N);
+}
+
+}  // namespace
+
+namespace locrec {
+
+int32_t rank_segments_device(int64_t n_seg, const int64_t *seg_begin, const int64_t *seg_len, const int64_t *ids,
+                             const double *scores, int64_t n_places, const int64_t *place_ids,
+                             const int64_t *place_region_ids, const int64_t *target_region_ids, int64_t max_recommendations,
+                             int64_t *out_ids, double *out_scores, int64_t *out_counts,
+                             const unsigned long long *invalid_flag, int64_t host_assembled, hipStream_t s)
+{
+    RankBatchStats &st = rank_batch_stats();
+    st = RankBatchStats();
+    st.host_assembled = host_assembled;
+    if (n_seg < 0 || n_seg >= kMaxRows || n_places < 0 || n_places >= kMaxRows)
+        return fail(LOCREC_E_INVALID_ARG, "segment or place count out of range [0, 2^31)");
+    if (n_seg == 0) return LOCREC_OK;
+    const int64_t N = std::max<int64_t>(0, max_recommendations);
+    if (N > 0 && n_seg > ((int64_t)1 << 60) / N) return fail(LOCREC_E_INVALID_ARG, "n_segments * max_recommendations overflows");
+    if (N == 0) {  // limit(n <= 0) is empty: the caller's verdict on the offsets, the counts, nothing else
+        unsigned long long bad = 0;
+        if (invalid_flag) {
+            LOCREC_HIP_TRY(hipMemcpyAsync(&bad, invalid_flag, sizeof bad, hipMemcpyDeviceToHost, s));
+            LOCREC_HIP_TRY(hipStreamSynchronize(s));
+            ++st.host_syncs;
+        }
+        if (bad) return fail(LOCREC_E_INVALID_ARG, "segments must be non-decreasing offsets inside [0, n]");
+        LOCREC_HIP_TRY(hipMemsetAsync(out_counts, 0, (size_t)n_seg * sizeof(int64_t), s));
+        return LOCREC_OK;
+    }
+    const int64_t chunk = rb_chunk_rows();
+    const bool global = N > LOCREC_RANK_BATCH_MAX_N || rb_force_sort();
+    Temp tmp;
+    // the region table: (region, place id) sorted - two stable passes, by id and then by region
+    // (one allocation each for the table and the plan: every hipMalloc / hipFree of a call costs a wait)
+    DevBuf<uint64_t> table, plan;
+    uint64_t *k0 = nullptr, *k1 = nullptr;
+    if (n_places > 0) {
+        const size_t np8 = ((size_t)n_places + 1) / 2;  // u32[n_places] in 8-byte units
+        LOCREC_TRY(table.alloc(2 * (size_t)n_places + 2 * np8));
+        k0 = table.p;
+        k1 = k0 + n_places;
+        uint32_t *r0 = reinterpret_cast<uint32_t *>(k1 + n_places), *r1 = r0 + 2 * np8;
+        hipLaunchKernelGGL(pr_iota_keys, grid_for(n_places), dim3(256), 0, s, n_places, place_ids, k0, r0);
+        PR_PRIM(tmp, prim::sort_pairs(p_, bytes_, k0, k1, r0, r1, (int)n_places, 0, 64, s));
+        hipLaunchKernelGGL(rb_gather_keys, grid_for(n_places), dim3(256), 0, s, n_places, place_region_ids, r1, k0);
+        PR_PRIM(tmp, prim::sort_pairs(p_, bytes_, k0, k1, r1, r0, (int)n_places, 0, 64, s));
+        hipLaunchKernelGGL(rb_gather_keys, grid_for(n_places), dim3(256), 0, s, n_places, place_ids, r0, k0);
+    }
+    const uint64_t *table_regions = k1, *table_ids = k0;
+    // the plan: every segment's range of the table and its chunks
+    const size_t seg8 = ((size_t)n_seg + 2) / 2;  // u32[n_seg + 1] in 8-byte units
+    LOCREC_TRY(plan.alloc(4 + 6 * seg8));
+    struct {
+        unsigned long long *p;
+    } hdr = {reinterpret_cast<unsigned long long *>(plan.p)};
+    struct U32 {
+        uint32_t *p;
+    } nch = {reinterpret_cast<uint32_t *>(plan.p + 4)}, split_nch = {nch.p + 2 * seg8}, first = {nch.p + 4 * seg8},
+      pfirst = {nch.p + 6 * seg8};
+    struct {
+        int32_t *p;
+    } lo = {reinterpret_cast<int32_t *>(nch.p + 8 * seg8)}, hi = {lo.p + 2 * seg8};
+    LOCREC_HIP_TRY(hipMemsetAsync(hdr.p, 0, 4 * sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(rb_plan, grid_for(n_seg + 1), dim3(256), 0, s, n_seg, seg_begin, seg_len, target_region_ids, n_places,
+                       table_regions, chunk, invalid_flag, nch.p, split_nch.p, lo.p, hi.p, hdr.p);
+    unsigned long long h[4] = {0, 0, 0, 0};
+    LOCREC_HIP_TRY(hipMemcpyAsync(h, hdr.p, sizeof h, hipMemcpyDeviceToHost, s));
+    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    ++st.host_syncs;
+    if (h[0]) return fail(LOCREC_E_INVALID_ARG, "segments must be non-decreasing offsets inside [0, n], each shorter than 2^31 rows");
+    if (h[1] >= (unsigned long long)kMaxRows - 1)
+        return fail(LOCREC_E_INVALID_ARG, "%llu chunks: raise LOCREC_RANK_BATCH_CHUNK or split the batch", h[1]);
+    const uint32_t items = (uint32_t)h[1];
+    PR_PRIM(tmp, prim::exclusive_sum(p_, bytes_, nch.p, first.p, (size_t)n_seg + 1, s));
+    if (!global) {
+        st.split = (int64_t)h[2];
+        st.chunks = (int64_t)h[3];
+        st.one_block = n_seg - st.split;
+        DevBuf<uint64_t> partial;  // the split segments' lists: keys, ids, rows, counts
+        struct {
+            uint64_t *p = nullptr;
+        } pk, pid;
+        struct {
+            uint32_t *p = nullptr;
+        } prow;
+        struct {
+            int32_t *p = nullptr;
+        } pcount;
+        if (h[3] > 0) {
+            PR_PRIM(tmp, prim::exclusive_sum(p_, bytes_, split_nch.p, pfirst.p, (size_t)n_seg + 1, s));
+            const size_t pn = (size_t)h[3] * (size_t)N, pn8 = (pn + 1) / 2, pc8 = ((size_t)h[3] + 1) / 2;
+            LOCREC_TRY(partial.alloc(2 * pn + pn8 + pc8));
+            pk.p = partial.p;
+            pid.p = pk.p + pn;
+            prow.p = reinterpret_cast<uint32_t *>(pid.p + pn);
+            pcount.p = reinterpret_cast<int32_t *>(pid.p + pn + pn8);
+        }
+        hipLaunchKernelGGL(rb_select, dim3(items), dim3(kRbThreads), 0, s, n_seg, first.p, pfirst.p, seg_begin, seg_len, lo.p,
+                           hi.p, table_ids, ids, scores, chunk, (int)N, pk.p, pid.p, prow.p, pcount.p, out_ids, out_scores,
+                           out_counts);
+        if (h[3] > 0)
+            hipLaunchKernelGGL(rb_merge, dim3((unsigned)n_seg), dim3(kRbThreads), 0, s, first.p, pfirst.p, seg_begin, scores,
+                               (int)N, pk.p, pid.p, prow.p, pcount.p, out_ids, out_scores, out_counts);
+        LOCREC_HIP_TRY(hipGetLastError());
+        // (the partial lists are freed below: hipFree waits for the kernels that read them)
+        return LOCREC_OK;
+    }
+    // the global path
+    st.sorted = n_seg;
+    const int64_t tiles = (N + kRbThreads - 1) / kRbThreads;
+    if (n_seg * tiles >= kMaxRows) return fail(LOCREC_E_INVALID_ARG, "n_segments * max_recommendations too large for one call");
+    DevBuf<uint32_t> cnt, base;
+    LOCREC_TRY(cnt.alloc((size_t)items + 1));
+    LOCREC_TRY(base.alloc((size_t)items + 1));
+    hipLaunchKernelGGL(rb_count, dim3(items + 1), dim3(kRbThreads), 0, s, n_seg, first.p, seg_begin, seg_len, lo.p, hi.p,
+                       table_ids, ids, chunk, cnt.p, items);
+    // (kept rows in all: a u32 sum; more than 2^31 - 1 are refused below, and 2^32 or more cannot come from segments that
+    // the callers cut out of fewer than 2^31 rows)
+    PR_PRIM(tmp, prim::exclusive_sum(p_, bytes_, cnt.p, base.p, (size_t)items + 1, s));
+    uint32_t m32 = 0;
+    LOCREC_HIP_TRY(hipMemcpyAsync(&m32, base.p + items, sizeof m32, hipMemcpyDeviceToHost, s));
+    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    ++st.host_syncs;
+    const int64_t m = m32;
+    if (m >= kMaxRows) return fail(LOCREC_E_INVALID_ARG, "more than 2^31 rows to sort: split the batch");
+    DevBuf<uint32_t> kseg, krow, v0, v1, s0, s1;
+    DevBuf<uint64_t> q0, q1;
+    const size_t mm = (size_t)std::max<int64_t>(m, 1);
+    LOCREC_TRY(kseg.alloc(mm));
+    LOCREC_TRY(krow.alloc(mm));
+    LOCREC_TRY(v0.alloc(mm));
+    LOCREC_TRY(v1.alloc(mm));
+    LOCREC_TRY(s0.alloc(mm));
+    LOCREC_TRY(s1.alloc(mm));
+    LOCREC_TRY(q0.alloc(mm));
+    LOCREC_TRY(q1.alloc(mm));
+    if (m > 0) {
+        hipLaunchKernelGGL(rb_scatter, dim3(items), dim3(kRbThreads), 0, s, n_seg, first.p, seg_begin, seg_len, lo.p, hi.p,
+                           table_ids, ids, chunk, base.p, kseg.p, krow.p, q0.p, v0.p);
+        // three stable passes: id, score key, segment
+        PR_PRIM(tmp, prim::sort_pairs(p_, bytes_, q0.p, q1.p, v0.p, v1.p, (int)m, 0, 64, s));
+        hipLaunchKernelGGL(rb_score_keys, grid_for(m), dim3(256), 0, s, m, v1.p, kseg.p, krow.p, seg_begin, scores, q0.p);
+        PR_PRIM(tmp, prim::sort_pairs(p_, bytes_, q0.p, q1.p, v1.p, v0.p, (int)m, 0, 64, s));
+        hipLaunchKernelGGL(rb_segment_keys, grid_for(m), dim3(256), 0, s, m, v0.p, kseg.p, s0.p);
+        PR_PRIM(tmp, prim::sort_pairs(p_, bytes_, s0.p, s1.p, v0.p, v1.p, (int)m, 0, 32, s));
+    }
+    hipLaunchKernelGGL(rb_emit_sorted, dim3((unsigned)(n_seg * tiles)), dim3(kRbThreads), 0, s, tiles, N, m, s1.p, v1.p, krow.p,
+                       seg_begin, ids, scores, out_ids, out_scores, out_counts);
+    LOCREC_HIP_TRY(hipGetLastError());
+    return LOCREC_OK;
+}
+
+}  // namespace locrec
+
+extern "C" int32_t locrec_rank_recommendations_batch(int64_t n_segments, const int64_t *offsets, int64_t n, const int64_t *ids,
+                                                     const double *scores, int64_t n_places, const int64_t *place_ids,
+                                                     const int64_t *place_region_ids, const int64_t *target_region_ids,
+                                                     int64_t max_recommendations, int32_t mem, int64_t *out_ids,
+                                                     double *out_scores, int64_t *out_counts)
+try {
+    rank_batch_stats() = RankBatchStats();
+    LOCREC_TRY(mem_ok(mem));
+    if (n < 0 || n >= kMaxRows || n_places < 0 || n_places >= kMaxRows || n_segments < 0 || n_segments >= kMaxRows)
+        return fail(LOCREC_E_INVALID_ARG, "row, place or segment count out of range [0, 2^31)");
+    if (n_segments == 0) return LOCREC_OK;
+    const int64_t N = std::max<int64_t>(0, max_recommendations);  // limit(n <= 0) is empty
+    if (N > 0 && n_segments > ((int64_t)1 << 60) / N) return fail(LOCREC_E_INVALID_ARG, "n_segments * max_recommendations overflows");
+    if (!offsets || !target_region_ids || !out_counts || (n > 0 && (!ids || !scores)) ||
+        (n_places > 0 && (!place_ids || !place_region_ids)) || (N > 0 && (!out_ids || !out_scores)))
+        return fail(LOCREC_E_INVALID_ARG, "null array");
+    if (mem == LOCREC_MEM_HOST) {
+        bool ok = offsets[0] >= 0 && offsets[n_segments] <= n;
+        for (int64_t i = 0; ok && i < n_segments; ++i) ok = offsets[i] <= offsets[i + 1];
+        if (!ok) return fail(LOCREC_E_INVALID_ARG, "offsets must be non-decreasing inside [0, n]");
+    }
+    LOCREC_TRY(ensure_device());
+    hipStream_t s = nullptr;
+    In<int64_t> off, tgt, rid, pid, preg;
+    In<double> rsc;
+    LOCREC_TRY(off.bind(offsets, n_segments + 1, mem, s));
+    LOCREC_TRY(tgt.bind(target_region_ids, n_segments, mem, s));
+    LOCREC_TRY(rid.bind(ids, n, mem, s));
+    LOCREC_TRY(rsc.bind(scores, n, mem, s));
+    LOCREC_TRY(pid.bind(place_ids, n_places, mem, s));
+    LOCREC_TRY(preg.bind(place_region_ids, n_places, mem, s));
+    Out<int64_t> oid, ocnt;
+    Out<double> osc;
+    LOCREC_TRY(oid.bind(out_ids, n_segments * N, mem));
+    LOCREC_TRY(osc.bind(out_scores, n_segments * N, mem));
+    LOCREC_TRY(ocnt.bind(out_counts, n_segments, mem));
+    DevBuf<int64_t> seg_begin, seg_len;
+    DevBuf<unsigned long long> invalid;
+    LOCREC_TRY(seg_begin.alloc((size_t)n_segments));
+    LOCREC_TRY(seg_len.alloc((size_t)n_segments));
+    LOCREC_TRY(invalid.alloc(1));
+    LOCREC_HIP_TRY(hipMemsetAsync(invalid.p, 0, sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(rb_prepare, grid_for(n_segments), dim3(256), 0, s, n_segments, off.p, n, seg_begin.p, seg_len.p, invalid.p);
+    LOCREC_TRY(rank_segments_device(n_segments, seg_begin.p, seg_len.p, rid.p, rsc.p, n_places, pid.p, preg.p, tgt.p, N, oid.p,
+                                    osc.p, ocnt.p, invalid.p, 0, s));
+    LOCREC_TRY(oid.deliver(n_segments * N, s));
+    LOCREC_TRY(osc.deliver(n_segments * N, s));
+    LOCREC_TRY(ocnt.deliver(n_segments, s));
+    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    ++rank_batch_stats().host_syncs;
+    return LOCREC_OK;
+}
+LOCREC_CATCH_ALL
+
+extern "C" int32_t locrec_rank_recommendations_batch_stats(int64_t *out_one_block, int64_t *out_split, int64_t *out_chunks,
+                                                           int64_t *out_sorted, int64_t *out_membership_form,
+                                                           int64_t *out_host_assembled, int64_t *out_host_syncs)
+try {
+    const RankBatchStats &st = rank_batch_stats();
+    if (out_one_block) *out_one_block = st.one_block;
+    if (out_split) *out_split = st.split;
+    if (out_chunks) *out_chunks = st.chunks;
+    if (out_sorted) *out_sorted = st.sorted;
+    if (out_membership_form) *out_membership_form = st.membership_form;
+    if (out_host_assembled) *out_host_assembled = st.host_assembled;
+    if (out_host_syncs) *out_host_syncs = st.host_syncs;
+    return LOCREC_OK;
+}
+LOCREC_CATCH_ALL

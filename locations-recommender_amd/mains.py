@@ -184,6 +184,67 @@ def rank_recommendations(ids, scores, place_ids, place_region_ids, target_region
     return ids[order], scores[order]
 
 
+def rank_recommendations_batch(offsets, ids, scores, place_ids, place_region_ids, target_region_ids, max_recommendations):
+    """rank_recommendations for every segment offsets[s]:offsets[s + 1] of one (ids, scores) pair with
+    target_region_ids[s]: the numpy restatement of prep.rank_recommendations_batch, with its result layout
+    (ids[S, W], scores[S, W], counts[S]; padding id -1 / score 0.0; W = the limit cut to the longest segment)."""
+    offsets, ids, scores = np.asarray(offsets, np.int64), np.asarray(ids, np.int64), np.asarray(scores, np.float64)
+    nseg = len(target_region_ids)
+    if len(offsets) != nseg + 1 or (nseg and (offsets[0] < 0 or offsets[-1] > len(ids) or np.any(np.diff(offsets) < 0))):
+        raise L.IllegalArgumentException("offsets must be non-decreasing inside [0, n]")
+    longest = int(np.diff(offsets).max()) if nseg else 0
+    width = max(0, min(int(max_recommendations), longest))
+    out_ids, out_scores = np.full((nseg, width), -1, np.int64), np.zeros((nseg, width), np.float64)
+    counts = np.zeros(nseg, np.int64)
+    for s in range(nseg):
+        a, b = offsets[s], offsets[s + 1]
+        ri, rs = rank_recommendations(ids[a:b], scores[a:b], place_ids, place_region_ids, target_region_ids[s], width)
+        counts[s] = len(ri)
+        out_ids[s, :len(ri)], out_scores[s, :len(ri)] = ri, rs
+    return out_ids, out_scores, counts
+
+
+def knn_recommend_places_batch(data_dir, region_ids, requests, place_weight, category_weight, k_nearest,
+                               max_recommendations=10):
+    """Many requests of one region pair to their end (KnnRecommenderMain.scala:53-67 and :90-101): requests is a
+    sequence of (person_id, target_region_id); the index comes from the handle cache, the places from load_places.
+    -> (place_ids[n, W], estimated_ratings[n, W], counts[n]), ranked on the device."""
+    from . import _cache
+    from .knn import KnnIndex
+    _cache.require_gpu_backend("knn_recommend_places_batch")
+    persons = np.asarray([r[0] for r in requests], np.int64)
+    targets = np.asarray([r[1] for r in requests], np.int64)
+    place_ids, place_regions = load_places(data_dir)
+    key = _cache.files_key([generate_file_name(region_ids, data_dir, f)
+                            for f in ("place_rating_vectors", "category_rating_vectors", "place_ratings")])
+    ix = KnnIndex.through_cache(key, lambda: knn_index_from_parquet(data_dir, region_ids))
+    try:
+        with ix.lock:
+            return ix.recommend_ranked_batch(persons, place_weight, category_weight, k_nearest, place_ids, place_regions,
+                                             targets, max_recommendations)
+    finally:
+        ix.close()  # drops the reference only
+
+
+def sg_recommend_places_batch(data_dir, region_ids, requests, epsilon, max_iterations, alpha=0.15, max_recommendations=10):
+    """Many requests of one region pair (StochasticRecommenderMain.scala:53-75): requests is a sequence of
+    (vertex_id, target_region_id).  -> (ids[n, W], probabilities[n, W], counts[n], iterations[n], converged[n])."""
+    from . import _cache
+    from .stochastic import SgGraph
+    _cache.require_gpu_backend("sg_recommend_places_batch")
+    vertices = np.asarray([r[0] for r in requests], np.int64)
+    targets = np.asarray([r[1] for r in requests], np.int64)
+    place_ids, place_regions = load_places(data_dir)
+    key = _cache.files_key([generate_file_name(region_ids, data_dir, "stochastic_graph")])
+    g = SgGraph.through_cache(key, lambda: sg_graph_from_parquet(data_dir, region_ids))
+    try:
+        with g.lock:
+            return g.recommend_ranked_batch(vertices, alpha, epsilon, max_iterations, place_ids, place_regions, targets,
+                                            max_recommendations)
+    finally:
+        g.close()
+
+
 def build_with_balanced_weights(betas, all_edges):
     """StochasticGraphBuilder.buildWithBalancedWeights (StochasticGraphBuilder.scala:8-28), the
     producer of the SG path's input: every family's `weight` times its beta,

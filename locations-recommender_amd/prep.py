@@ -8,6 +8,7 @@ SURVEY.md 8f rows f-2 and f-4) behind the names of the reference's builder objec
     calc_place_visits            PlaceVisits.calcPlaceVisits              PlaceVisits.scala:11-46
     distance_meters              Location.distanceMeters                  Location.scala:30-38
     rank_recommendations         printRecommendations of both mains       knn/KnnRecommenderMain.scala:90-101
+    rank_recommendations_batch   ... for every segment of a batch's rows   (the same lines, per person)
     calc_person_likes_place_edges / calc_person_likes_category_edges / calc_category_selected_place_edges
                                  the three counted edge families          stochastic/PersonLikesPlace.scala:12-37 (and siblings)
     calc_place_similar_place_edges  PlaceSimilarPlace.calcPlaceSimilarPlaceEdges
@@ -180,6 +181,39 @@ def rank_recommendations(ids, scores, place_ids, place_region_ids, target_region
     L.check(L.lib().locrec_rank_recommendations(n, a[0], a[1], npl, p[0], p[1], int(target_region_id), int(max_recommendations),
                                                 c.mem, oip, oscp, C.byref(cnt)))
     return oi[:cnt.value], osc[:cnt.value]
+
+
+RANK_BATCH_STATS = ("one_block", "split", "chunks", "sorted", "membership_form", "host_assembled", "host_syncs")
+
+
+def rank_recommendations_batch(offsets, ids, scores, place_ids, place_region_ids, target_region_ids, max_recommendations):
+    """rank_recommendations for many row ranges of one (ids, scores) pair at once (locrec_rank_recommendations_batch):
+    segment s is rows offsets[s]:offsets[s + 1] and is ranked for target_region_ids[s].
+    -> (ids[S, W], scores[S, W], counts[S]); row s holds counts[s] rows, then id -1 / score 0.0.  W is
+    max_recommendations, cut to the longest segment (no segment can return more)."""
+    if not _is_tensor(offsets):
+        offsets = np.asarray(offsets, np.int64)
+    c = _Cols(offsets, ids, scores, place_ids, place_region_ids, target_region_ids)
+    nseg, n, npl = len(target_region_ids), len(ids), len(place_ids)
+    assert len(offsets) == nseg + 1 and len(scores) == n and len(place_region_ids) == npl
+    longest = int((offsets[1:] - offsets[:-1]).max()) if nseg else 0
+    width = max(0, min(int(max_recommendations), longest, n))
+    o = c.col(offsets, np.int64)
+    a = [c.col(ids, np.int64), c.col(scores, np.float64)]
+    p = [c.col(place_ids, np.int64), c.col(place_region_ids, np.int64)]
+    t = c.col(target_region_ids, np.int64)
+    (oi, oip), (osc, oscp), (oc, ocp) = c.out(nseg * width, np.int64), c.out(nseg * width, np.float64), c.out(nseg, np.int64)
+    L.check(L.lib().locrec_rank_recommendations_batch(nseg, o, n, a[0], a[1], npl, p[0], p[1], t, width, c.mem, oip, oscp, ocp))
+    if nseg == 0 or width == 0:
+        oc[:nseg] = 0
+    return oi[:nseg * width].reshape(nseg, width), osc[:nseg * width].reshape(nseg, width), oc[:nseg]
+
+
+def rank_recommendations_batch_stats():
+    """What the last ranked batch of this thread did (locrec_rank_recommendations_batch_stats), as a dict."""
+    v = [C.c_int64() for _ in RANK_BATCH_STATS]
+    L.check(L.lib().locrec_rank_recommendations_batch_stats(*[C.byref(x) for x in v]))
+    return dict(zip(RANK_BATCH_STATS, (x.value for x in v)))
 
 
 def knn_index_from_visits(person_ids, place_ids, category_ids, places_top_n=VISITED_PLACES_TOP_N,

@@ -127,6 +127,17 @@ class SgGraph:
             cap = C.c_int64(len(ids))
         return off, ids[:off[-1]], probs[:off[-1]], its, conv.astype(bool)
 
+    def recommend_ranked_batch(self, vertex_ids, alpha, epsilon, max_iterations, place_ids, place_region_ids,
+                               target_region_ids, max_recommendations):
+        """recommend_batch, then per vertex the places of its target region, top max_recommendations by probability
+        (prep.rank_recommendations_batch on the batch's rows; locrec_sg_recommend_batch returns host rows).
+        -> (ids[n, W], probabilities[n, W], counts[n], iterations[n], converged[n]), rows padded with -1 / 0.0."""
+        from . import prep
+        off, ids, probs, its, conv = self.recommend_batch(vertex_ids, alpha, epsilon, max_iterations)
+        oi, op, cnt = prep.rank_recommendations_batch(off, ids, probs, place_ids, place_region_ids, target_region_ids,
+                                                      max_recommendations)
+        return oi, op, cnt, its, conv
+
     def iterate_async(self, vertex_id, alpha, epsilon, max_iterations):
         L.check(L.lib().locrec_sg_iterate_async(self._h, int(vertex_id), float(alpha), float(epsilon),
                                                 int(max_iterations)))
