@@ -445,6 +445,39 @@ int32_t locrec_sg_recommend_batch(
     int64_t *out_offsets, int64_t *out_ids, double *out_probabilities, int64_t *inout_capacity,
     int64_t *out_iterations, int32_t *out_converged);
 
+/*
+ * The batched request to its end (StochasticRecommenderMain.scala:53-75): makeRecommendations for n_targets
+ * vertices of ONE graph, then per request the places of ITS target region, top max_recommendations by
+ * probability - emitted and ranked on the device; x is never read back.  All arrays are host arrays.
+ * Row i of out_ids / out_probabilities (row-major, stride max(0, max_recommendations)) holds bit for bit what
+ * locrec_rank_recommendations returns for the rows locrec_sg_recommend returns for vertex_ids[i], with
+ * target_region_ids[i]; padded with id -1 / probability 0.0.  out_counts[i]: rows written.  out_row_counts[i]
+ * (may be NULL): the rows makeRecommendations itself has for that vertex (id != vertex and p > 0, before the
+ * region join), counted on the device.  out_iterations / out_converged as in locrec_sg_recommend_batch
+ * (either may be NULL).  A repeated vertex is iterated once; each of its positions is ranked with its own
+ * region.  Errors and refusals are those of locrec_sg_recommend_batch (LOCREC_E_NOT_FOUND for any unknown
+ * vertex before any device work, nothing written); n_places, n_targets and max_recommendations take the checks
+ * of locrec_rank_recommendations_batch.  max_recommendations <= 0 or n_places == 0: the iteration still runs,
+ * every count is 0.  Afterwards the handle serves single requests and locrec_sg_recommend_batch as before.
+ * The segments of a group of requests are ranked by one call of the segmented ranker; a group ends where its
+ * rows would pass LOCREC_SG_RANKED_ROW_BUDGET (default 2^24 rows; the result does not depend on it).
+ */
+int32_t locrec_sg_recommend_ranked_batch(
+    locrec_sg_graph *graph, int64_t n_targets, const int64_t *vertex_ids,
+    double alpha, double epsilon, int64_t max_iterations,
+    int64_t n_places, const int64_t *place_ids, const int64_t *place_region_ids,
+    const int64_t *target_region_ids, int64_t max_recommendations,
+    int64_t *out_ids, double *out_probabilities, int64_t *out_counts,
+    int64_t *out_row_counts, int64_t *out_iterations, int32_t *out_converged);
+/*
+ * What this thread's last locrec_sg_recommend_ranked_batch did (any pointer may be NULL): tiles iterated,
+ * ranker calls (groups), rows emitted into segments, and every byte the call copied to host memory or had the
+ * device write there (state, block sums, polls, results), with the number of waits for the stream.
+ */
+int32_t locrec_sg_recommend_ranked_batch_stats(
+    int64_t *out_tiles, int64_t *out_groups, int64_t *out_emitted_rows,
+    int64_t *out_readback_bytes, int64_t *out_host_syncs);
+
 /* Device-resident form (bench.py): enqueue the iteration, read back later. */
 int32_t locrec_sg_iterate_async(
     locrec_sg_graph *graph, int64_t vertex_id,

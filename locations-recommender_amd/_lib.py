@@ -89,6 +89,9 @@ SIGNATURES = {
     "locrec_sg_recommend": [C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int64, _i64p, _f64p, _i64p, _i64p, _i32p],
     "locrec_sg_recommend_batch": [C.c_void_p, C.c_int64, _i64p, C.c_double, C.c_double, C.c_int64,
                                   _i64p, _i64p, _f64p, _i64p, _i64p, _i32p],
+    "locrec_sg_recommend_ranked_batch": [C.c_void_p, C.c_int64, _i64p, C.c_double, C.c_double, C.c_int64,
+                                         C.c_int64, _i64p, _i64p, _i64p, C.c_int64, _i64p, _f64p, _i64p, _i64p, _i64p, _i32p],
+    "locrec_sg_recommend_ranked_batch_stats": [_i64p, _i64p, _i64p, _i64p, _i64p],
     "locrec_sg_iterate_async": [C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int64],
     "locrec_sg_sweeps_async": [C.c_void_p, C.c_int64, C.c_double, C.c_int64],
     "locrec_sg_fetch": [C.c_void_p, _i64p, _f64p, _i64p, _i64p, _i32p],

@@ -353,17 +353,23 @@ struct SlotRange {
     int32_t off, cnt, val;
 };
 
-}  // namespace
+// What the batched entries share (locrec_sg_recommend_batch below, locrec_sg_recommend_ranked_batch in sg_ranked.h): the
+// requires and refusals, the distinct targets, the verdict on a column and the tile loop.
+struct SgBatchCtx {
+    hipStream_t s = nullptr;
+    int32_t T = 0;
+    int64_t xstride = 0;             // one parity of x
+    SgBatchState *bstate = nullptr;  // the tile's state, on the device
+    double eps2 = 0;
+    int64_t max_iterations = 0;  // (cut to INT32_MAX)
+    int64_t polls = 0;           // convergence words read so far
+};
 
-extern "C" int32_t locrec_sg_recommend_batch(locrec_sg_graph *g, int64_t n_targets, const int64_t *vertex_ids, double alpha,
-                                             double epsilon, int64_t max_iterations, int64_t *out_offsets, int64_t *out_ids,
-                                             double *out_probs, int64_t *inout_capacity, int64_t *out_iterations,
-                                             int32_t *out_converged) try
+// require()s of the constructor (StochasticRecommender.scala:33-34), the handles a batch refuses, and isVertexExist
+// (:70-77) for every target before any device work; a repeated target is computed once
+int32_t sg_batch_targets(locrec_sg_graph *g, int64_t n_targets, const int64_t *vertex_ids, double epsilon,
+                         int64_t max_iterations, std::vector<int32_t> &uniq, std::vector<int32_t> &uniq_of)
 {
-    if (!g) return fail(LOCREC_E_INVALID_ARG, "graph is NULL");
-    if (n_targets < 0 || (n_targets > 0 && !vertex_ids) || !out_offsets || !inout_capacity)
-        return fail(LOCREC_E_INVALID_ARG, "bad arguments");
-    // require()s of the constructor, StochasticRecommender.scala:33-34
     if (!(epsilon >= 0)) return fail(LOCREC_E_INVALID_ARG, "requirement failed: epsilon must be non-negative");
     if (max_iterations < 0)
         return fail(LOCREC_E_INVALID_ARG, "requirement failed: max iterations number must be non-negative");
@@ -371,34 +377,55 @@ extern "C" int32_t locrec_sg_recommend_batch(locrec_sg_graph *g, int64_t n_targe
         return fail(LOCREC_E_INVALID_ARG, "a sharded graph is iterated with locrec_sg_shard_* (it holds only part of the edges)");
     if (g->env_fused || g->env_persist)  // (other kernels serve their single requests; the fused one's buffers are the batch's)
         return fail(LOCREC_E_INVALID_ARG, "batched requests are not served on a handle of the fused or persistent experiment");
-    // isVertexExist (:70-77) for every target before any device work; a repeated target is computed once
-    std::vector<int32_t> uniq;                        // vertex index of each distinct target, in order of appearance
-    std::vector<int32_t> uniq_of((size_t)n_targets);  // input position -> its entry of uniq
-    {
-        std::unordered_map<int32_t, int32_t> seen;
-        for (int64_t i = 0; i < n_targets; ++i) {
-            auto it = std::lower_bound(g->vid.begin(), g->vid.end(), vertex_ids[i]);
-            if (it == g->vid.end() || *it != vertex_ids[i])
-                return fail(LOCREC_E_NOT_FOUND, "No such vertex in the graph: %lld", (long long)vertex_ids[i]);
-            const int32_t tv = (int32_t)(it - g->vid.begin());
-            auto ins = seen.emplace(tv, (int32_t)uniq.size());
-            if (ins.second) uniq.push_back(tv);
-            uniq_of[(size_t)i] = ins.first->second;
-        }
+    uniq.clear();                          // vertex index of each distinct target, in order of appearance
+    uniq_of.assign((size_t)n_targets, 0);  // input position -> its entry of uniq
+    std::unordered_map<int32_t, int32_t> seen;
+    for (int64_t i = 0; i < n_targets; ++i) {
+        auto it = std::lower_bound(g->vid.begin(), g->vid.end(), vertex_ids[i]);
+        if (it == g->vid.end() || *it != vertex_ids[i])
+            return fail(LOCREC_E_NOT_FOUND, "No such vertex in the graph: %lld", (long long)vertex_ids[i]);
+        const int32_t tv = (int32_t)(it - g->vid.begin());
+        auto ins = seen.emplace(tv, (int32_t)uniq.size());
+        if (ins.second) uniq.push_back(tv);
+        uniq_of[(size_t)i] = ins.first->second;
     }
-    if (n_targets == 0) {
-        out_offsets[0] = 0;
-        *inout_capacity = 0;
-        return LOCREC_OK;
+    return LOCREC_OK;
+}
+
+// targets of a tile: uint16 columns address rows up to 65535, so a graph with T close to that takes fewer private rows
+inline int sg_batch_tile_max(const locrec_sg_graph *g) { return g->use16 ? std::min(kBatchB, 65535 - g->nlive) : kBatchB; }
+
+// step(), :92-106: which of the two exits a column took (as locrec_sg_fetch decides it).  total() is the sum of the block
+// sums of the column's last executed sweep, added as the finalize adds them; it is asked for only when a sweep ran.
+template <class Total>
+int32_t sg_batch_verdict(int64_t sweeps, Total &&total, double eps2, int64_t max_iterations, int64_t *iterations,
+                         int32_t *converged)
+{
+    *converged = 0;
+    *iterations = max_iterations;
+    if (sweeps > 0 && total() <= eps2) {
+        *converged = 1;
+        *iterations = sweeps - 1;
     }
+    if (!*converged && sweeps != max_iterations)
+        return fail(LOCREC_E_DEVICE, "internal: %lld sweeps executed, %lld expected", (long long)sweeps,
+                    (long long)max_iterations);
+    return LOCREC_OK;
+}
+
+// Every tile of the distinct targets: its set-up, its rounds and polls, then consume(ctx, t0, nb) - after the tile's last
+// round and before the next tile's set-up overwrites x.  At the end the last tile's slots go back to D.
+template <class Consume>
+int32_t sg_batch_tiles(locrec_sg_graph *g, const std::vector<int32_t> &uniq, double alpha, double epsilon,
+                       int64_t max_iterations, SgBatchCtx &ctx, Consume &&consume)
+{
     if (max_iterations > INT32_MAX) max_iterations = INT32_MAX;
     LOCREC_HIP_TRY(hipSetDevice(g->device));
     hipStream_t s = g->stream;
     const int32_t T = g->nlive;
     const int64_t rows = (int64_t)T + 1 + kBatchB;
     const int64_t xstride = rows * kBatchB;  // one parity of x
-    // uint16 columns address rows up to 65535: a graph with T close to that takes fewer private rows per tile
-    const int tile_max = g->use16 ? std::min(kBatchB, 65535 - T) : kBatchB;
+    const int tile_max = sg_batch_tile_max(g);
     if (!g->PA4.p) {
         LOCREC_TRY(g->PA4.alloc((size_t)(2 * xstride)));
         LOCREC_TRY(g->XL.alloc((size_t)std::max(1, g->pa_stride) * kBatchB));
@@ -416,13 +443,13 @@ extern "C" int32_t locrec_sg_recommend_batch(locrec_sg_graph *g, int64_t n_targe
     const v2d *wv2 = reinterpret_cast<const v2d *>(g->w2.p);
     const v4h *wi = reinterpret_cast<const v4h *>(g->widx.p);
     const size_t lds = g->ndict > 0 ? (size_t)g->ndict * sizeof(double) : 0;
-    const size_t pack_bytes = kBatchPackHead + (size_t)2 * kParts * kBatchB * 8 + (size_t)(T + 1) * kBatchB * 8;
-
     const size_t nu = uniq.size();
-    std::vector<std::vector<int64_t>> res_ids(nu);
-    std::vector<std::vector<double>> res_probs(nu);
-    std::vector<int64_t> res_it(nu);
-    std::vector<int32_t> res_conv(nu);
+    ctx.s = s;
+    ctx.T = T;
+    ctx.xstride = xstride;
+    ctx.bstate = bstate;
+    ctx.eps2 = eps2;
+    ctx.max_iterations = max_iterations;
     // slot ranges that point at a private row (or at the single request's Q) and go back to D next
     std::vector<SlotRange> pointed;
     if (g->n_patched > 0) pointed.push_back(SlotRange{(int32_t)g->patched_off, g->n_patched, T});
@@ -507,11 +534,62 @@ extern "C" int32_t locrec_sg_recommend_batch(locrec_sg_graph *g, int64_t n_targe
                     LOCREC_HIP_TRY(hipMemcpyAsync(&all_done, &bstate->all_done, sizeof all_done, hipMemcpyDeviceToHost, s));
                     LOCREC_HIP_TRY(hipStreamSynchronize(s));
                 }
+                ++ctx.polls;
                 if (all_done) break;
                 next_check += next_check < 8 ? 2 : (next_check < 16 ? 4 : kCheckEvery);
             }
         }
-        // read-back: one pack launch into pinned memory
+        return consume(ctx, t0, nb);
+    };
+    int32_t status = LOCREC_OK;
+    for (size_t t0 = 0; t0 < nu && status == LOCREC_OK; t0 += (size_t)tile_max)
+        status = run_tile(t0, (int)std::min<size_t>((size_t)tile_max, nu - t0));
+    // the last tile's slots back at D: the handle's column array is as a fresh handle's (nothing points at Q)
+    if (!pointed.empty()) {
+        SgBatchBegin b{};
+        b.col = const_cast<void *>(colv);
+        b.slots = g->dead_slots_dev.p;
+        b.col16 = g->use16 ? 1 : 0;
+        for (const SlotRange &r : pointed) {
+            b.off[b.nranges] = r.off;
+            b.cnt[b.nranges] = r.cnt;
+            b.val[b.nranges++] = T;
+        }
+        hipLaunchKernelGGL(sg_begin_batch, dim3(kBeginBlocks), dim3(256), 0, s, b);
+        LOCREC_HIP_TRY(hipGetLastError());
+    }
+    return status;
+}
+
+}  // namespace
+
+extern "C" int32_t locrec_sg_recommend_batch(locrec_sg_graph *g, int64_t n_targets, const int64_t *vertex_ids, double alpha,
+                                             double epsilon, int64_t max_iterations, int64_t *out_offsets, int64_t *out_ids,
+                                             double *out_probs, int64_t *inout_capacity, int64_t *out_iterations,
+                                             int32_t *out_converged) try
+{
+    if (!g) return fail(LOCREC_E_INVALID_ARG, "graph is NULL");
+    if (n_targets < 0 || (n_targets > 0 && !vertex_ids) || !out_offsets || !inout_capacity)
+        return fail(LOCREC_E_INVALID_ARG, "bad arguments");
+    std::vector<int32_t> uniq, uniq_of;
+    LOCREC_TRY(sg_batch_targets(g, n_targets, vertex_ids, epsilon, max_iterations, uniq, uniq_of));
+    if (n_targets == 0) {
+        out_offsets[0] = 0;
+        *inout_capacity = 0;
+        return LOCREC_OK;
+    }
+    const size_t nu = uniq.size();
+    std::vector<std::vector<int64_t>> res_ids(nu);
+    std::vector<std::vector<double>> res_probs(nu);
+    std::vector<int64_t> res_it(nu);
+    std::vector<int32_t> res_conv(nu);
+    // a tile's read-back: one pack launch into pinned memory, then the rows of every column (:84-88)
+    auto read_back = [&](SgBatchCtx &ctx, size_t t0, int nb) -> int32_t {
+        hipStream_t s = ctx.s;
+        const int32_t T = ctx.T;
+        const int64_t xstride = ctx.xstride;
+        SgBatchState *bstate = ctx.bstate;
+        const size_t pack_bytes = kBatchPackHead + (size_t)2 * kParts * kBatchB * 8 + (size_t)(T + 1) * kBatchB * 8;
         unsigned char *stg = g->no_pack ? nullptr : g->stage(pack_bytes);
         void *stg_dev = nullptr;
         std::vector<unsigned char> own;
@@ -555,21 +633,12 @@ extern "C" int32_t locrec_sg_recommend_batch(locrec_sg_graph *g, int64_t n_targe
         for (int j = 0; j < nb; ++j) {
             const size_t u = t0 + (size_t)j;
             const int64_t sweeps = hs.sweeps[j];
-            int32_t converged = 0;
-            int64_t iterations = max_iterations;
-            if (sweeps > 0) {
+            auto total = [&]() {
                 double parts[kParts];
                 for (int q = 0; q < kParts; ++q) parts[q] = hparts[(size_t)((sweeps - 1) & 1) * kParts * kBatchB + (size_t)q * kBatchB + j];
-                if (host_total_d2(parts) <= eps2) {
-                    converged = 1;
-                    iterations = sweeps - 1;
-                }
-            }
-            if (!converged && sweeps != max_iterations)
-                return fail(LOCREC_E_DEVICE, "internal: %lld sweeps executed, %lld expected", (long long)sweeps,
-                            (long long)max_iterations);
-            res_it[u] = iterations;
-            res_conv[u] = converged;
+                return host_total_d2(parts);
+            };
+            LOCREC_TRY(sg_batch_verdict(sweeps, total, ctx.eps2, ctx.max_iterations, &res_it[u], &res_conv[u]));
         }
         // :84-88  id != vertexId and probability > 0, ascending id.  A source-only vertex holds D's value: 1/V before the
         // first sweep (then every vertex is walked, column by column), 0 after it (then only the live ones can appear,
@@ -608,24 +677,8 @@ extern "C" int32_t locrec_sg_recommend_batch(locrec_sg_graph *g, int64_t n_targe
         }
         return LOCREC_OK;
     };
-    int32_t status = LOCREC_OK;
-    for (size_t t0 = 0; t0 < nu && status == LOCREC_OK; t0 += (size_t)tile_max)
-        status = run_tile(t0, (int)std::min<size_t>((size_t)tile_max, nu - t0));
-    // the last tile's slots back at D: the handle's column array is as a fresh handle's (nothing points at Q)
-    if (!pointed.empty()) {
-        SgBatchBegin b{};
-        b.col = const_cast<void *>(colv);
-        b.slots = g->dead_slots_dev.p;
-        b.col16 = g->use16 ? 1 : 0;
-        for (const SlotRange &r : pointed) {
-            b.off[b.nranges] = r.off;
-            b.cnt[b.nranges] = r.cnt;
-            b.val[b.nranges++] = T;
-        }
-        hipLaunchKernelGGL(sg_begin_batch, dim3(kBeginBlocks), dim3(256), 0, s, b);
-        LOCREC_HIP_TRY(hipGetLastError());
-    }
-    if (status != LOCREC_OK) return status;
+    SgBatchCtx ctx;
+    LOCREC_TRY(sg_batch_tiles(g, uniq, alpha, epsilon, max_iterations, ctx, read_back));
     // the rows in input order; a repeated target's rows are copies
     int64_t total = 0;
     out_offsets[0] = 0;
@@ -647,3 +700,5 @@ extern "C" int32_t locrec_sg_recommend_batch(locrec_sg_graph *g, int64_t n_targe
     }
     return LOCREC_OK;
 } LOCREC_CATCH_ALL
+
+#include "sg_ranked.h"

@@ -1,0 +1,480 @@
+// sg_ranked.h -- the ranked SG batch (included at the end of sg_batch.hip, behind sg.hip): the batched makeRecommendations
+// to its end, printRecommendations of StochasticRecommenderMain.scala:64-75, without x ever leaving the device
+// (locrec_sg_recommend_ranked_batch).  The handle gets no new member (sg.hip stays as it is): every buffer here is local to
+// the call, and their number does not depend on the number of targets.
+//
+//   emit rows       what a request can return, numbered once per call: rows 0 .. T-1 are x's live rows; when D can still
+//                   be positive (no sweep ran) the source-only vertices follow in ascending vertex order.  eid[e] is the
+//                   vertex id of emit row e.
+//   membership      once per (distinct target region, vertex): a bitmap over the emit rows per region.  sg_rk_members, one
+//                   thread per row of the places table: its region among the distinct target regions, its id among the
+//                   sorted vertex ids (two binary searches), one 64-bit atomic OR.  A place listed twice sets one bit, a
+//                   place listed in two regions one bit in each - as the ranker's join counts them.  The popcount of a
+//                   region's bitmap (sg_rk_popcount) is the exact room a request for that region needs.
+//   sg_rk_emit      per tile, after its last round: one lane per emit row, a wave reads its 64 rows of x as whole 128-byte
+//                   lines (all 16 columns, each from the parity of its own last sweep; a source-only vertex reads D's
+//                   row) and parks them in LDS.  Then per request of the tile: the region's bitmap word of these 64 rows
+//                   (wave-uniform; zero for most waves), p > 0, not the request's own target; a ballot, ONE atomic add per
+//                   wave and request on the segment's length, the lane prefix, and (id, p) goes to the request's segment.
+//                   The same pass counts per column the rows makeRecommendations has (p > 0, not the target).
+//   sg_rk_state     the tile's read-back: its SgBatchState and per column the sum of the last sweep's block sums, added
+//                   by the butterfly the finalize itself decides with - 384 bytes a tile.
+//   ranking         rank_segments_device (rank_batch.hip) once per group of requests; a group ends where the room of its
+//                   segments would pass LOCREC_SG_RANKED_ROW_BUDGET rows (a tile's requests may straddle groups: the
+//                   emit runs once per part).  The group's N rows a request then travel to the host.
+//
+// hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage (VGPRs / LDS bytes / scratch):
+//   sg_rk_emit      82 / 32832 / 0
+//   sg_rk_members   14 / 0 / 0
+//   sg_rk_popcount  8 / 4 / 0
+//   sg_rk_row_ids   4 / 0 / 0
+//   sg_rk_state     14 / 0 / 0
+#pragma once
+
+#include "rank_batch.h"
+
+namespace {
+
+constexpr int kRkThreads = 256;
+constexpr size_t kRkStateBytes = kBatchPackHead + kBatchB * sizeof(double);  // SgBatchState at 0, the columns' totals behind
+constexpr int64_t kRkDefaultBudget = (int64_t)1 << 24;
+static_assert(sizeof(SgBatchState) <= kBatchPackHead, "the state sits in front of the totals");
+
+// what this thread's last ranked batch did (locrec_sg_recommend_ranked_batch_stats)
+struct SgRankedStats {
+    int64_t tiles = 0, groups = 0, emitted_rows = 0, readback_bytes = 0, host_syncs = 0;
+};
+
+SgRankedStats &sg_ranked_stats()
+{
+    thread_local SgRankedStats st;
+    return st;
+}
+
+// LOCREC_SG_RANKED_ROW_BUDGET: rows of segment room one ranker call takes (read per call; a group has at least one request)
+int64_t sg_ranked_row_budget()
+{
+    int64_t b = kRkDefaultBudget;
+    if (const char *e = std::getenv("LOCREC_SG_RANKED_ROW_BUDGET")) b = atoll(e);
+    return std::min<int64_t>(std::max<int64_t>(b, 1), (int64_t)1 << 30);
+}
+
+inline dim3 rk_grid(int64_t n) { return dim3((unsigned)std::max<int64_t>(1, (n + kRkThreads - 1) / kRkThreads)); }
+
+// eid[srow[i]] = sid[i]: the vertex id of every emit row
+__global__ __launch_bounds__(kRkThreads) void sg_rk_row_ids(int64_t m, const int64_t *__restrict__ sid,
+                                                           const int32_t *__restrict__ srow, int64_t *__restrict__ eid)
+{
+    const int64_t i = (int64_t)blockIdx.x * kRkThreads + threadIdx.x;
+    if (i < m) eid[srow[i]] = sid[i];
+}
+
+// first index of a[0 .. n) that is not below key (a ascending)
+__device__ __forceinline__ int64_t rk_lower_bound(const int64_t *__restrict__ a, int64_t n, int64_t key)
+{
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (a[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// one thread per row of the places table: the bit (its region, its emit row), when it has both
+__global__ __launch_bounds__(kRkThreads) void sg_rk_members(int64_t n_places, const int64_t *__restrict__ place_ids,
+                                                           const int64_t *__restrict__ place_regions, int64_t n_regions,
+                                                           const int64_t *__restrict__ regions, int64_t m,
+                                                           const int64_t *__restrict__ sid, const int32_t *__restrict__ srow,
+                                                           int64_t words, unsigned long long *bits)
+{
+    const int64_t i = (int64_t)blockIdx.x * kRkThreads + threadIdx.x;
+    if (i >= n_places) return;
+    const int64_t reg = place_regions[i], id = place_ids[i];
+    const int64_t r = rk_lower_bound(regions, n_regions, reg);
+    if (r >= n_regions || regions[r] != reg) return;
+    const int64_t j = rk_lower_bound(sid, m, id);
+    if (j >= m || sid[j] != id) return;
+    const int32_t e = srow[j];  // < 64 * words
+    atomicOr(&bits[r * words + (e >> 6)], 1ull << (e & 63));
+}
+
+// caps[r] = bits set in region r's bitmap; one block per region
+__global__ __launch_bounds__(kRkThreads) void sg_rk_popcount(int64_t words, const unsigned long long *__restrict__ bits,
+                                                            unsigned long long *__restrict__ caps)
+{
+    __shared__ unsigned int total;
+    if (threadIdx.x == 0) total = 0;
+    __syncthreads();
+    const unsigned long long *row = bits + (int64_t)blockIdx.x * words;
+    unsigned int mine = 0;
+    for (int64_t w = threadIdx.x; w < words; w += kRkThreads) mine += (unsigned int)__popcll(row[w]);
+    if (mine) atomicAdd(&total, mine);
+    __syncthreads();
+    if (threadIdx.x == 0) caps[blockIdx.x] = total;
+}
+
+// The tile's read-back: the state, and per column the total of its last executed sweep's block sums (the butterfly of
+// sg_finalize_batch's own decision; host_total_d2 is the same sum).  One wave per column.
+__global__ __launch_bounds__(64 * kBatchB) void sg_rk_state(const SgBatchState *__restrict__ st, const double *__restrict__ parts,
+                                                           unsigned char *out)
+{
+    const int lane = threadIdx.x & 63, b = threadIdx.x >> 6;
+    const int sweeps = st->sweeps[b];
+    double tot = 0.0;
+    if (sweeps > 0) tot = wave_butterfly_sum(parts[(size_t)((sweeps - 1) & 1) * kParts * kBatchB + (size_t)lane * kBatchB + b]);
+    if (lane == 0) reinterpret_cast<double *>(out + kBatchPackHead)[b] = tot;
+    if (threadIdx.x < sizeof(SgBatchState) / 4)
+        reinterpret_cast<int32_t *>(out)[threadIdx.x] = reinterpret_cast<const int32_t *>(st)[threadIdx.x];
+}
+static_assert(kParts == 64, "one lane per block sum");
+
+struct SgEmitTile {
+    int32_t col_trow[kBatchB];  // emit row of column b's target (-1: it has none), never a row of that column's result
+    int32_t nb, T, ne;          // ne: emit rows
+    int32_t count_cols;         // this launch also counts the columns' rows (the first launch of a tile)
+    int64_t xstride;
+};
+
+__global__ __launch_bounds__(kRkThreads) void sg_rk_emit(
+    const SgEmitTile tl, const SgBatchState *__restrict__ st, const double *__restrict__ xbuf, const int64_t *__restrict__ eid,
+    const unsigned long long *__restrict__ bits, const int64_t words, const int32_t k0, const int32_t k1,
+    const int32_t *__restrict__ req_col, const int32_t *__restrict__ req_trow, const int32_t *__restrict__ req_bm,
+    const int64_t *__restrict__ seg_begin, unsigned long long *seg_len, const int64_t rows_cap, int64_t *__restrict__ seg_ids,
+    double *__restrict__ seg_probs, unsigned long long *col_rows)
+{
+    __shared__ double xs[kRkThreads / 64][kBatchB][64];  // [wave][column][lane]: each lane reads back only what it wrote
+    __shared__ unsigned int colcnt[kBatchB];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int e0 = (blockIdx.x * (kRkThreads / 64) + wave) * 64;  // (a multiple of 64: one bitmap word per wave)
+    const int e = e0 + lane;
+    if (threadIdx.x < kBatchB) colcnt[threadIdx.x] = 0;
+    __syncthreads();
+    if (e0 < tl.ne) {
+        uint32_t pm = 0;  // the columns whose x is in the second buffer
+#pragma unroll
+        for (int b = 0; b < kBatchB; ++b) pm |= (uint32_t)(st->sweeps[b] & 1) << b;
+        pm = (uint32_t)__builtin_amdgcn_readfirstlane((int)pm);
+        const bool in = e < tl.ne;
+        // a source-only vertex holds D's value in every column but its own, where it is the target
+        const v2d *r0 = reinterpret_cast<const v2d *>(xbuf + (size_t)(e < tl.T ? e : tl.T) * kBatchB);
+        const v2d *r1 = reinterpret_cast<const v2d *>(xbuf + tl.xstride + (size_t)(e < tl.T ? e : tl.T) * kBatchB);
+        double v[kBatchB];
+        if (pm == 0u || pm == 0xFFFFu) {
+            const v2d *r = pm ? r1 : r0;
+#pragma unroll
+            for (int k = 0; k < kBatchB / 2; ++k) {
+                const v2d a = r[k];
+                v[2 * k] = a.x;
+                v[2 * k + 1] = a.y;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < kBatchB / 2; ++k) {
+                const v2d a = r0[k], c = r1[k];
+                v[2 * k] = ((pm >> (2 * k)) & 1u) ? c.x : a.x;
+                v[2 * k + 1] = ((pm >> (2 * k + 1)) & 1u) ? c.y : a.y;
+            }
+        }
+#pragma unroll
+        for (int b = 0; b < kBatchB; ++b) xs[wave][b][lane] = v[b];
+        if (tl.count_cols) {
+            // :84-88 per column: id != vertexId and probability > 0
+#pragma unroll
+            for (int b = 0; b < kBatchB; ++b) {
+                const unsigned long long m = __ballot(in && b < tl.nb && v[b] > 0 && e != tl.col_trow[b]);
+                if (lane == 0 && m) atomicAdd(&colcnt[b], (unsigned int)__popcll(m));
+            }
+        }
+        for (int k = k0; k < k1; ++k) {
+            const unsigned long long word = bits[(int64_t)req_bm[k] * words + (e0 >> 6)];  // (wave-uniform)
+            if (word == 0) continue;
+            const double p = xs[wave][req_col[k]][lane];
+            const bool ok = ((word >> lane) & 1ull) && p > 0 && e != req_trow[k];  // (a set bit is an emit row)
+            const unsigned long long m = __ballot(ok);
+            if (m == 0) continue;
+            unsigned long long base = 0;
+            if (lane == 0) base = atomicAdd(&seg_len[k], (unsigned long long)__popcll(m));
+            const uint32_t blo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
+            const uint32_t bhi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32));
+            if (ok) {
+                const int64_t pos = seg_begin[k] + (int64_t)(((unsigned long long)bhi << 32) | blo) +
+                                    __popcll(m & ((1ull << lane) - 1ull));
+                if (pos < rows_cap) {  // (the popcount of the bitmap is the room: always)
+                    seg_ids[pos] = eid[e];
+                    seg_probs[pos] = p;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (tl.count_cols && threadIdx.x < kBatchB && colcnt[threadIdx.x])
+        atomicAdd(&col_rows[threadIdx.x], (unsigned long long)colcnt[threadIdx.x]);
+}
+
+}  // namespace
+
+extern "C" int32_t locrec_sg_recommend_ranked_batch(locrec_sg_graph *g, int64_t n_targets, const int64_t *vertex_ids, double alpha,
+                                                    double epsilon, int64_t max_iterations, int64_t n_places,
+                                                    const int64_t *place_ids, const int64_t *place_region_ids,
+                                                    const int64_t *target_region_ids, int64_t max_recommendations,
+                                                    int64_t *out_ids, double *out_probabilities, int64_t *out_counts,
+                                                    int64_t *out_row_counts, int64_t *out_iterations, int32_t *out_converged) try
+{
+    SgRankedStats &stats = sg_ranked_stats();
+    stats = SgRankedStats();
+    if (!g) return fail(LOCREC_E_INVALID_ARG, "graph is NULL");
+    if (n_targets < 0 || (n_targets > 0 && !vertex_ids)) return fail(LOCREC_E_INVALID_ARG, "bad arguments");
+    // the checks of locrec_rank_recommendations_batch
+    if (n_places < 0 || n_places >= ((int64_t)1 << 31) || n_targets >= ((int64_t)1 << 31))
+        return fail(LOCREC_E_INVALID_ARG, "place or target count out of range [0, 2^31)");
+    const int64_t N = std::max<int64_t>(0, max_recommendations);  // limit(n <= 0) is empty
+    if (N > 0 && n_targets > ((int64_t)1 << 60) / N) return fail(LOCREC_E_INVALID_ARG, "n_targets * max_recommendations overflows");
+    if (n_targets > 0 && (!target_region_ids || !out_counts || (N > 0 && (!out_ids || !out_probabilities)) ||
+                          (n_places > 0 && (!place_ids || !place_region_ids))))
+        return fail(LOCREC_E_INVALID_ARG, "null array");
+    std::vector<int32_t> uniq, uniq_of;
+    LOCREC_TRY(sg_batch_targets(g, n_targets, vertex_ids, epsilon, max_iterations, uniq, uniq_of));
+    if (n_targets == 0) return LOCREC_OK;
+    LOCREC_HIP_TRY(hipSetDevice(g->device));
+    hipStream_t s = g->stream;
+    const int64_t n = n_targets;
+    const size_t nu = uniq.size();
+    const int32_t T = g->nlive;
+    const int tile_max = sg_batch_tile_max(g);
+
+    // ---- the emit rows.  D's value after a sweep is sg_next_x(0, false): never positive; before the first it is 1/V.
+    const double xd = 0.0 * alpha + 0.0 * (1 - alpha);
+    const bool dead_rows = max_iterations == 0 || xd > 0;
+    if (g->live_sorted.size() != (size_t)T) {
+        g->live_sorted.clear();
+        for (int64_t v = 0; v < g->nv; ++v)
+            if (g->live_of[v] >= 0) g->live_sorted.push_back((int32_t)v);
+    }
+    const int64_t m = dead_rows ? g->nv : (int64_t)T;  // emit rows = searchable ids
+    std::vector<int64_t> sid_own;
+    std::vector<int32_t> srow((size_t)m);
+    const int64_t *sid = g->vid.data();
+    if (dead_rows) {
+        int32_t next_dead = T;
+        for (int64_t v = 0; v < m; ++v) srow[(size_t)v] = g->live_of[v] >= 0 ? g->live_of[v] : next_dead++;
+    } else {
+        sid_own.resize((size_t)m);
+        for (int64_t i = 0; i < m; ++i) {
+            sid_own[(size_t)i] = g->vid[g->live_sorted[(size_t)i]];
+            srow[(size_t)i] = g->live_of[g->live_sorted[(size_t)i]];
+        }
+        sid = sid_own.data();
+    }
+    auto emit_row_of = [&](int32_t tv) -> int32_t {
+        if (g->live_of[tv] >= 0) return g->live_of[tv];
+        return dead_rows ? srow[(size_t)tv] : -1;
+    };
+    const int64_t words = std::max<int64_t>(1, (m + 63) / 64);
+
+    // ---- the requests in emit order (by tile, then input position) and the distinct target regions
+    std::vector<int64_t> regions(target_region_ids, target_region_ids + n);
+    std::sort(regions.begin(), regions.end());
+    regions.erase(std::unique(regions.begin(), regions.end()), regions.end());
+    const int64_t R = (int64_t)regions.size();
+    std::vector<int64_t> first_k(nu + 1, 0);  // requests of distinct target u: ord[first_k[u] .. first_k[u + 1])
+    for (int64_t i = 0; i < n; ++i) ++first_k[(size_t)uniq_of[(size_t)i] + 1];
+    for (size_t u = 0; u < nu; ++u) first_k[u + 1] += first_k[u];
+    std::vector<int64_t> ord((size_t)n);
+    {
+        std::vector<int64_t> at(first_k.begin(), first_k.end() - 1);
+        for (int64_t i = 0; i < n; ++i) ord[(size_t)at[(size_t)uniq_of[(size_t)i]]++] = i;
+    }
+    std::vector<int32_t> req((size_t)(3 * n));  // column, target's emit row, bitmap
+    std::vector<int64_t> tgt_k((size_t)n);
+    for (int64_t k = 0; k < n; ++k) {
+        const int64_t i = ord[(size_t)k];
+        const int32_t u = uniq_of[(size_t)i];
+        req[(size_t)k] = u % tile_max;
+        req[(size_t)(n + k)] = emit_row_of(uniq[(size_t)u]);
+        req[(size_t)(2 * n + k)] = (int32_t)(std::lower_bound(regions.begin(), regions.end(), target_region_ids[i]) - regions.begin());
+        tgt_k[(size_t)k] = target_region_ids[i];
+    }
+
+    // ---- device buffers: the 8-byte inputs and counters, the 4-byte inputs, the bitmaps
+    //   d64: place ids, place regions | distinct regions | sid | eid | targets | seg_begin | seg_len | col_rows | caps
+    DevBuf<int64_t> d64;
+    DevBuf<int32_t> d32;
+    DevBuf<unsigned long long> d_bits;
+    LOCREC_TRY(d64.alloc((size_t)(2 * n_places + 2 * R + 2 * m + 3 * n) + nu));
+    LOCREC_TRY(d32.alloc((size_t)(m + 3 * n)));
+    LOCREC_TRY(d_bits.alloc((size_t)(R * words)));
+    int64_t *d_pid = d64.p, *d_preg = d_pid + n_places, *d_regions = d_preg + n_places, *d_sid = d_regions + R, *d_eid = d_sid + m,
+            *d_tgt = d_eid + m, *d_seg_begin = d_tgt + n, *d_seg_len = d_seg_begin + n, *d_col_rows = d_seg_len + n,
+            *d_caps = d_col_rows + nu;
+    int32_t *d_srow = d32.p, *d_req = d_srow + m;
+    if (n_places > 0) {
+        LOCREC_HIP_TRY(hipMemcpyAsync(d_pid, place_ids, (size_t)n_places * 8, hipMemcpyHostToDevice, s));
+        LOCREC_HIP_TRY(hipMemcpyAsync(d_preg, place_region_ids, (size_t)n_places * 8, hipMemcpyHostToDevice, s));
+    }
+    LOCREC_HIP_TRY(hipMemcpyAsync(d_regions, regions.data(), (size_t)R * 8, hipMemcpyHostToDevice, s));
+    if (m > 0) {
+        LOCREC_HIP_TRY(hipMemcpyAsync(d_sid, sid, (size_t)m * 8, hipMemcpyHostToDevice, s));
+        LOCREC_HIP_TRY(hipMemcpyAsync(d_srow, srow.data(), (size_t)m * 4, hipMemcpyHostToDevice, s));
+    }
+    LOCREC_HIP_TRY(hipMemcpyAsync(d_tgt, tgt_k.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
+    LOCREC_HIP_TRY(hipMemcpyAsync(d_req, req.data(), (size_t)(3 * n) * 4, hipMemcpyHostToDevice, s));
+    LOCREC_HIP_TRY(hipMemsetAsync(d_seg_len, 0, ((size_t)n + nu) * 8, s));  // the segments' lengths and the columns' rows
+    LOCREC_HIP_TRY(hipMemsetAsync(d_bits.p, 0, (size_t)(R * words) * 8, s));
+    if (m > 0) hipLaunchKernelGGL(sg_rk_row_ids, rk_grid(m), dim3(kRkThreads), 0, s, m, d_sid, d_srow, d_eid);
+    if (n_places > 0 && m > 0)
+        hipLaunchKernelGGL(sg_rk_members, rk_grid(n_places), dim3(kRkThreads), 0, s, n_places, d_pid, d_preg, R, d_regions, m, d_sid,
+                           d_srow, words, d_bits.p);
+    hipLaunchKernelGGL(sg_rk_popcount, dim3((unsigned)R), dim3(kRkThreads), 0, s, words, d_bits.p,
+                       reinterpret_cast<unsigned long long *>(d_caps));
+    std::vector<int64_t> caps((size_t)R);
+    LOCREC_HIP_TRY(hipMemcpyAsync(caps.data(), d_caps, (size_t)R * 8, hipMemcpyDeviceToHost, s));
+    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    LOCREC_HIP_TRY(hipGetLastError());
+    ++stats.host_syncs;
+    stats.readback_bytes += R * 8;
+
+    // ---- the groups: request k's segment has room caps[its region]; a group's segments share the row buffer
+    const int64_t budget = sg_ranked_row_budget();
+    std::vector<int64_t> seg_begin((size_t)n), group_end;  // group_end[i]: one past the last request of group i
+    int64_t max_rows = 1, max_req = 1, max_cap = 0, cur_rows = 0, cur_first = 0;
+    for (int64_t k = 0; k < n; ++k) {
+        const int64_t c = caps[(size_t)req[(size_t)(2 * n + k)]];
+        if (k > cur_first && cur_rows + c > budget) {
+            group_end.push_back(k);
+            cur_first = k;
+            cur_rows = 0;
+        }
+        seg_begin[(size_t)k] = cur_rows;
+        cur_rows += c;
+        max_rows = std::max(max_rows, cur_rows);
+        max_req = std::max(max_req, k + 1 - cur_first);
+        max_cap = std::max(max_cap, c);
+    }
+    group_end.push_back(n);
+    if (max_rows >= ((int64_t)1 << 31)) return fail(LOCREC_E_INVALID_ARG, "a request's region has 2^31 places or more");
+    const int64_t Nd = std::min(N, max_cap);  // no request has more rows than the largest region: the rest is padding
+    LOCREC_HIP_TRY(hipMemcpyAsync(d_seg_begin, seg_begin.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
+    DevBuf<int64_t> d_rows, d_out;  // ids, then probabilities: the emitted rows of a group; its ranked rows and counts
+    DevBuf<unsigned char> d_state;
+    LOCREC_TRY(d_rows.alloc(2 * (size_t)max_rows));
+    LOCREC_TRY(d_out.alloc((size_t)(2 * max_req * Nd + max_req)));
+    LOCREC_TRY(d_state.alloc(kRkStateBytes));
+    int64_t *d_row_ids = d_rows.p;
+    double *d_row_probs = reinterpret_cast<double *>(d_rows.p + max_rows);
+    int64_t *d_oid = d_out.p, *d_ocnt = d_out.p + 2 * max_req * Nd;
+    double *d_osc = reinterpret_cast<double *>(d_out.p + max_req * Nd);
+    std::vector<int64_t> h_oid((size_t)(n * Nd)), h_cnt((size_t)n, 0);
+    std::vector<double> h_osc((size_t)(n * Nd));
+    size_t group = 0;  // the group that is being filled
+    auto group_first = [&](size_t gi) { return gi == 0 ? (int64_t)0 : group_end[gi - 1]; };
+    // ranks the filled group and brings its rows to the host
+    auto flush_group = [&]() -> int32_t {
+        const int64_t ka = group_first(group), nseg = group_end[group] - ka;
+        ++group;
+        ++stats.groups;
+        if (Nd == 0) return LOCREC_OK;  // every count is 0
+        LOCREC_TRY(rank_segments_device(nseg, d_seg_begin + ka, d_seg_len + ka, d_row_ids, d_row_probs, n_places, d_pid, d_preg,
+                                        d_tgt + ka, Nd, d_oid, d_osc, d_ocnt, nullptr, 0, s));
+        const RankBatchStats &rs = rank_batch_stats();
+        stats.host_syncs += rs.host_syncs;
+        stats.readback_bytes += 32 + (rs.sorted ? 4 : 0);  // the ranker's plan header, the global path's row count
+        LOCREC_HIP_TRY(hipMemcpyAsync(h_oid.data() + ka * Nd, d_oid, (size_t)(nseg * Nd) * 8, hipMemcpyDeviceToHost, s));
+        LOCREC_HIP_TRY(hipMemcpyAsync(h_osc.data() + ka * Nd, d_osc, (size_t)(nseg * Nd) * 8, hipMemcpyDeviceToHost, s));
+        LOCREC_HIP_TRY(hipMemcpyAsync(h_cnt.data() + ka, d_ocnt, (size_t)nseg * 8, hipMemcpyDeviceToHost, s));
+        LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (the next group's rows overwrite these)
+        ++stats.host_syncs;
+        stats.readback_bytes += nseg * (16 * Nd + 8);
+        return LOCREC_OK;
+    };
+
+    std::vector<int64_t> res_it(nu);
+    std::vector<int32_t> res_conv(nu);
+    const unsigned emit_blocks = (unsigned)std::max<int64_t>(1, (m + kRkThreads - 1) / kRkThreads);
+    auto after_tile = [&](SgBatchCtx &ctx, size_t t0, int nb) -> int32_t {
+        ++stats.tiles;
+        // the state first: it does not wait for the emit
+        unsigned char *stg = g->no_pack ? nullptr : g->stage(kRkStateBytes);
+        void *stg_dev = nullptr;
+        const bool pinned = stg && hipHostGetDevicePointer(&stg_dev, stg, 0) == hipSuccess;
+        if (!pinned) (void)hipGetLastError();
+        hipLaunchKernelGGL(sg_rk_state, dim3(1), dim3(64 * kBatchB), 0, s, ctx.bstate, g->D2W.p,
+                           pinned ? static_cast<unsigned char *>(stg_dev) : d_state.p);
+        unsigned char own[kRkStateBytes];
+        if (!pinned) LOCREC_HIP_TRY(hipMemcpyAsync(own, d_state.p, kRkStateBytes, hipMemcpyDeviceToHost, s));
+        SgEmitTile tl{};
+        tl.nb = nb;
+        tl.T = T;
+        tl.ne = (int32_t)m;
+        tl.xstride = ctx.xstride;
+        tl.count_cols = 1;
+        for (int j = 0; j < kBatchB; ++j) tl.col_trow[j] = j < nb ? emit_row_of(uniq[t0 + (size_t)j]) : -1;
+        // the tile's requests, group by group
+        int64_t k = first_k[t0];
+        const int64_t kb = first_k[t0 + (size_t)nb];
+        while (k < kb) {
+            const int64_t ke = std::min(kb, group_end[group]);
+            hipLaunchKernelGGL(sg_rk_emit, dim3(emit_blocks), dim3(kRkThreads), 0, s, tl, ctx.bstate, g->PA4.p, d_eid, d_bits.p,
+                               words, (int32_t)k, (int32_t)ke, d_req, d_req + n, d_req + 2 * n, d_seg_begin,
+                               reinterpret_cast<unsigned long long *>(d_seg_len), max_rows, d_row_ids, d_row_probs,
+                               reinterpret_cast<unsigned long long *>(d_col_rows) + t0);
+            tl.count_cols = 0;
+            k = ke;
+            if (k == group_end[group]) LOCREC_TRY(flush_group());
+        }
+        LOCREC_HIP_TRY(hipStreamSynchronize(s));
+        LOCREC_HIP_TRY(hipGetLastError());
+        ++stats.host_syncs;
+        stats.readback_bytes += (int64_t)kRkStateBytes;
+        const unsigned char *host = pinned ? stg : own;
+        SgBatchState hs;
+        std::memcpy(&hs, host, sizeof hs);
+        const double *totals = reinterpret_cast<const double *>(host + kBatchPackHead);
+        for (int j = 0; j < nb; ++j) {
+            const size_t u = t0 + (size_t)j;
+            LOCREC_TRY(sg_batch_verdict(hs.sweeps[j], [&]() { return totals[j]; }, ctx.eps2, ctx.max_iterations, &res_it[u],
+                                        &res_conv[u]));
+        }
+        return LOCREC_OK;
+    };
+    SgBatchCtx ctx;
+    const int32_t status = sg_batch_tiles(g, uniq, alpha, epsilon, max_iterations, ctx, after_tile);
+    stats.readback_bytes += ctx.polls * 4;
+    stats.host_syncs += ctx.polls;
+    if (status != LOCREC_OK) return status;
+    // the columns' row counts and what the segments took
+    std::vector<int64_t> tail((size_t)n + nu);  // seg_len, col_rows
+    LOCREC_HIP_TRY(hipMemcpyAsync(tail.data(), d_seg_len, tail.size() * 8, hipMemcpyDeviceToHost, s));
+    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    ++stats.host_syncs;
+    stats.readback_bytes += (int64_t)tail.size() * 8;
+    for (int64_t k = 0; k < n; ++k) stats.emitted_rows += tail[(size_t)k];
+    // the caller's order and stride
+    for (int64_t k = 0; k < n; ++k) {
+        const int64_t i = ord[(size_t)k];
+        const size_t u = (size_t)uniq_of[(size_t)i];
+        const int64_t c = Nd > 0 ? h_cnt[(size_t)k] : 0;
+        out_counts[i] = c;
+        if (N > 0) {
+            std::copy(h_oid.begin() + k * Nd, h_oid.begin() + k * Nd + c, out_ids + i * N);
+            std::copy(h_osc.begin() + k * Nd, h_osc.begin() + k * Nd + c, out_probabilities + i * N);
+            std::fill(out_ids + i * N + c, out_ids + (i + 1) * N, (int64_t)-1);
+            std::fill(out_probabilities + i * N + c, out_probabilities + (i + 1) * N, 0.0);
+        }
+        if (out_row_counts) out_row_counts[i] = tail[(size_t)n + u];
+        if (out_iterations) out_iterations[i] = res_it[u];
+        if (out_converged) out_converged[i] = res_conv[u];
+    }
+    return LOCREC_OK;
+} LOCREC_CATCH_ALL
+
+extern "C" int32_t locrec_sg_recommend_ranked_batch_stats(int64_t *out_tiles, int64_t *out_groups, int64_t *out_emitted_rows,
+                                                          int64_t *out_readback_bytes, int64_t *out_host_syncs) try
+{
+    const SgRankedStats &st = sg_ranked_stats();
+    if (out_tiles) *out_tiles = st.tiles;
+    if (out_groups) *out_groups = st.groups;
+    if (out_emitted_rows) *out_emitted_rows = st.emitted_rows;
+    if (out_readback_bytes) *out_readback_bytes = st.readback_bytes;
+    if (out_host_syncs) *out_host_syncs = st.host_syncs;
+    return LOCREC_OK;
+} LOCREC_CATCH_ALL

@@ -226,9 +226,11 @@ def knn_recommend_places_batch(data_dir, region_ids, requests, place_weight, cat
         ix.close()  # drops the reference only
 
 
-def sg_recommend_places_batch(data_dir, region_ids, requests, epsilon, max_iterations, alpha=0.15, max_recommendations=10):
+def sg_recommend_places_batch(data_dir, region_ids, requests, epsilon, max_iterations, alpha=0.15, max_recommendations=10,
+                              on_device=True):
     """Many requests of one region pair (StochasticRecommenderMain.scala:53-75): requests is a sequence of
-    (vertex_id, target_region_id).  -> (ids[n, W], probabilities[n, W], counts[n], iterations[n], converged[n])."""
+    (vertex_id, target_region_id).  -> (ids[n, W], probabilities[n, W], counts[n], iterations[n], converged[n]),
+    emitted and ranked on the device (on_device=False: the host rows through the segmented ranker, the same result)."""
     from . import _cache
     from .stochastic import SgGraph
     _cache.require_gpu_backend("sg_recommend_places_batch")
@@ -240,7 +242,7 @@ def sg_recommend_places_batch(data_dir, region_ids, requests, epsilon, max_itera
     try:
         with g.lock:
             return g.recommend_ranked_batch(vertices, alpha, epsilon, max_iterations, place_ids, place_regions, targets,
-                                            max_recommendations)
+                                            max_recommendations, on_device=on_device)
     finally:
         g.close()
 

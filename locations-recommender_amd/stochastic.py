@@ -127,16 +127,44 @@ class SgGraph:
             cap = C.c_int64(len(ids))
         return off, ids[:off[-1]], probs[:off[-1]], its, conv.astype(bool)
 
+    RANKED_BATCH_STATS = ("tiles", "groups", "emitted_rows", "readback_bytes", "host_syncs")
+
     def recommend_ranked_batch(self, vertex_ids, alpha, epsilon, max_iterations, place_ids, place_region_ids,
-                               target_region_ids, max_recommendations):
-        """recommend_batch, then per vertex the places of its target region, top max_recommendations by probability
-        (prep.rank_recommendations_batch on the batch's rows; locrec_sg_recommend_batch returns host rows).
-        -> (ids[n, W], probabilities[n, W], counts[n], iterations[n], converged[n]), rows padded with -1 / 0.0."""
-        from . import prep
-        off, ids, probs, its, conv = self.recommend_batch(vertex_ids, alpha, epsilon, max_iterations)
-        oi, op, cnt = prep.rank_recommendations_batch(off, ids, probs, place_ids, place_region_ids, target_region_ids,
-                                                      max_recommendations)
-        return oi, op, cnt, its, conv
+                               target_region_ids, max_recommendations, on_device=True):
+        """The batched request to its end: per vertex the places of its target region, top max_recommendations by
+        probability.  on_device=True (locrec_sg_recommend_ranked_batch): the rows are emitted into per-request
+        segments and ranked on the device, x never leaves it and max_recommendations rows a request come back.
+        on_device=False: recommend_batch's host rows through prep.rank_recommendations_batch (the same result; the
+        A/B partner).
+        -> (ids[n, W], probabilities[n, W], counts[n], iterations[n], converged[n]), rows padded with -1 / 0.0;
+        W = max_recommendations cut to the longest row count of a vertex."""
+        if not on_device:
+            from . import prep
+            off, ids, probs, its, conv = self.recommend_batch(vertex_ids, alpha, epsilon, max_iterations)
+            oi, op, cnt = prep.rank_recommendations_batch(off, ids, probs, place_ids, place_region_ids, target_region_ids,
+                                                          max_recommendations)
+            return oi, op, cnt, its, conv
+        v, pl, reg, tgt = L.as_i64(vertex_ids), L.as_i64(place_ids), L.as_i64(place_region_ids), L.as_i64(target_region_ids)
+        n = len(v)
+        if len(reg) != len(pl) or len(tgt) != n:
+            raise L.IllegalArgumentException("one region per place and one target region per vertex are required")
+        # no vertex has more rows than the graph has vertices: the stride of the call, cut to W afterwards
+        stride = max(0, min(int(max_recommendations), self.info()["vertices"]))
+        oi, op = np.full((n, stride), -1, np.int64), np.zeros((n, stride), np.float64)
+        cnt, rows, its, conv = (np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, np.int32))
+        L.check(L.lib().locrec_sg_recommend_ranked_batch(
+            self._h, n, L.ptr(v, C.c_int64), float(alpha), float(epsilon), int(max_iterations), len(pl), L.ptr(pl, C.c_int64),
+            L.ptr(reg, C.c_int64), L.ptr(tgt, C.c_int64), stride, L.ptr(oi, C.c_int64), L.ptr(op, C.c_double),
+            L.ptr(cnt, C.c_int64), L.ptr(rows, C.c_int64), L.ptr(its, C.c_int64), L.ptr(conv, C.c_int32)))
+        width = max(0, min(stride, int(rows.max()) if n else 0))
+        return (np.ascontiguousarray(oi[:, :width]), np.ascontiguousarray(op[:, :width]), cnt, its, conv.astype(bool))
+
+    @classmethod
+    def ranked_batch_stats(cls):
+        """What this thread's last on-device recommend_ranked_batch did (locrec_sg_recommend_ranked_batch_stats)."""
+        x = [C.c_int64() for _ in cls.RANKED_BATCH_STATS]
+        L.check(L.lib().locrec_sg_recommend_ranked_batch_stats(*[C.byref(i) for i in x]))
+        return dict(zip(cls.RANKED_BATCH_STATS, (i.value for i in x)))
 
     def iterate_async(self, vertex_id, alpha, epsilon, max_iterations):
         L.check(L.lib().locrec_sg_iterate_async(self._h, int(vertex_id), float(alpha), float(epsilon),
@@ -273,3 +301,23 @@ class StochasticRecommender:
                 else:
                     print(f"Number of iterations {it} reached the maximum {self.maxIterations}")
         return pd.DataFrame({"vertex_id": np.repeat(v, np.diff(off)), "id": ids, "probability": probs})
+
+    def makeRecommendationsRankedBatch(self, vertexIds, places, targetRegionIds, maxRecommendations):
+        """Additive: makeRecommendationsBatch and printRecommendations' query (StochasticRecommenderMain.scala:64-75)
+        in one call on the device.  places: frame with columns id, region_id; targetRegionIds: one per vertex.
+        -> (vertex_id, id, probability): per vertex, in input order, the places of its target region, at most
+        maxRecommendations of them, by probability descending (ties: id ascending)."""
+        import pandas as pd
+        v = L.as_i64(vertexIds)
+        with self._graph.lock:
+            oi, op, cnt, iterations, converged = self._graph.recommend_ranked_batch(
+                v, ALPHA, self.epsilon, self.maxIterations, np.asarray(places["id"]), np.asarray(places["region_id"]),
+                targetRegionIds, maxRecommendations)
+        if not self.quiet:  # step()'s line (:94,100) for every vertex, in input order
+            for it, conv in zip(iterations, converged):
+                if conv:
+                    print(f"Converged in {it} iterations")
+                else:
+                    print(f"Number of iterations {it} reached the maximum {self.maxIterations}")
+        keep = np.arange(oi.shape[1])[None, :] < cnt[:, None]
+        return pd.DataFrame({"vertex_id": np.repeat(v, cnt), "id": oi[keep], "probability": op[keep]})
