@@ -11,6 +11,7 @@ switched off (LOCREC_SG_NO_COL16 / LOCREC_SG_NO_DICT)."""
 import numpy as np
 import pytest
 
+import sg_build_limit_cases as limits
 from test_gpu_sg_batch import ALPHA, RTOL, check_against_single, rows_of, same_bits
 
 pytestmark = pytest.mark.gpu
@@ -50,17 +51,10 @@ def test_uint16_columns_at_their_limit(pkg, oracle, monkeypatch, t_plus_2):
     """Bites: `T + 2 <= 65536` read as `<= 65537` keeps uint16 columns at T = 65535, where the batch's first private row
     T + 1 = 65536 wraps to column 0 (the sweep bytes stay below the int32 form's: asserted first); read as `<= 65535`
     the middle graph loses the form (its sweep bytes equal the int32 form's)."""
-    T, n_persons = t_plus_2 - 2, 1_500
-    live = np.arange(T, dtype=np.int64)
-    persons = 100_000 + np.arange(n_persons, dtype=np.int64)           # sources only: their edges read column T
-    src = np.concatenate([persons[live % n_persons], live, persons[:40]])
-    dst = np.concatenate([live, (live * 7 + 1) % T, np.arange(40, dtype=np.int64)])
+    T = t_plus_2 - 2
+    c = limits.uint16_limit(t_plus_2)                                   # (tests/sg_build_limit_cases.py)
+    src, dst, w, targets, persons = c["source"], c["target"], c["weight"], c["requests"], c["persons"]
     assert (T - 1) in src[T:2 * T] and persons[0] in src[:T]           # columns T - 1 and T are used by real edges
-    uniq, inv = np.unique(src, return_inverse=True)
-    w = 1.0 / np.bincount(inv)[inv]
-    # persons (a private row each: column T + 1 onwards in a batch), the first and the last live vertex
-    targets = np.array([100_000, 5, T - 1, 100_001, 0, 100_039, 100_002, 100_003, T - 1, 100_004, 7, 100_005, 100_000,
-                        100_006, 100_007, 100_008, 100_009, 100_010, 100_011], np.int64)
     (on, off), live_count = both_forms(pkg, oracle, monkeypatch, "LOCREC_SG_NO_COL16", src, dst, w, targets)
     assert live_count == T
     if t_plus_2 <= 65536:
@@ -73,14 +67,9 @@ def test_uint16_columns_at_their_limit(pkg, oracle, monkeypatch, t_plus_2):
 def test_weight_dictionary_at_its_limit(pkg, oracle, monkeypatch, distinct):
     """Bites: `nu <= kDictMax` read as `<` reports no dictionary at 8192; kDictMax = 8193 reports one at 8193, whose
     last value lies behind the 64 KB table of the sweep's LDS."""
-    rng = np.random.default_rng(23)
-    ne, m = 24_000, distinct - 1                                        # m edge weights + the padding's +0.0
-    values = (1.0 + np.arange(m)) / 2.0 ** 19                           # distinct, exact, sums stay below 1
-    w = values[np.r_[np.arange(m), rng.integers(0, m, ne - m)]]
-    src = rng.integers(1000, 1300, ne).astype(np.int64)
-    dst = rng.integers(0, 40, ne).astype(np.int64)
+    c = limits.dictionary_limit(distinct)                               # (tests/sg_build_limit_cases.py)
+    src, dst, w, targets, m = c["source"], c["target"], c["weight"], c["requests"], c["edge_weights"]
     assert len(np.unique(w)) == m and not np.any(w == 0.0)
-    targets = np.r_[rng.choice(np.arange(1000, 1300), 20, replace=False), np.arange(0, 40, 4), [1000, 0]].astype(np.int64)
     (on, off), _ = both_forms(pkg, oracle, monkeypatch, "LOCREC_SG_NO_DICT", src, dst, w, targets)
     assert off["weight_dictionary"] == 0
     assert on["weight_dictionary"] == (distinct if distinct <= 8192 else 0), "the dictionary holds 8192 values, +0.0 included"
