@@ -724,6 +724,49 @@ int32_t locrec_calc_place_visits(int64_t n_visits, const int64_t *v_person_ids, 
                                  int64_t *out_person_ids, int64_t *out_timestamps, int64_t *out_place_ids,
                                  int64_t *out_region_ids, int64_t *out_category_ids, int64_t *inout_count);
 
+/*
+ * The steps around the per-set work of the two builder mains (knn/RatingVectorsBuilderMain.scala:33-76,
+ * stochastic/StochasticGraphBuilderMain.scala:36-45), csrc/region_sets.hip.
+ *
+ * max(timestamp) of PlaceVisits.calcVisitsFromTimestamp (PlaceVisits.scala:50-61); the day arithmetic in the
+ * session's time zone stays with the caller.  n == 0 -> LOCREC_E_INVALID_ARG (the reference dereferences a
+ * null there); n in [1, 2^31).
+ */
+int32_t locrec_visits_max_timestamp(int64_t n, const int64_t *timestamps, int32_t mem, int64_t *out_max);
+
+/*
+ * PlaceVisits.extractRegionIds (PlaceVisits.scala:69-78): the distinct values of a region_id column,
+ * ASCENDING (Spark leaves the order of distinct().collect() undefined; this project defines it).
+ * *inout_count: capacity of out_ids in, number of distinct ids out (may exceed the capacity, then the first
+ * `capacity` ids are written); out_ids == NULL only counts.  n in [0, 2^31).
+ */
+int32_t locrec_extract_region_ids(int64_t n, const int64_t *region_ids, int32_t mem, int64_t *out_ids,
+                                  int64_t *inout_count);
+
+/*
+ * The rows of a table grouped by region, once for all region sets (PlaceVisits.scala:63-67,80-87).
+ * region_ids: the n_regions listed regions, strictly ascending (else LOCREC_E_INVALID_ARG), in `mem`.
+ * out_rows (n_rows entries, in `mem`): the row numbers 0 .. n_rows - 1 grouped by the rank of their region in
+ * region_ids, ascending inside a group.  out_offsets (ALWAYS host memory, n_regions + 2 entries): group g is
+ * out_rows[out_offsets[g] : out_offsets[g + 1]]; the last group, g = n_regions, holds the rows whose region is
+ * not listed - they belong to no set.  n_rows in [0, 2^31), n_regions in [0, 2^24).
+ */
+int32_t locrec_region_partition(int64_t n_rows, const int64_t *row_region_ids, int64_t n_regions,
+                                const int64_t *region_ids, int32_t mem, int32_t *out_rows, int64_t *out_offsets);
+
+/*
+ * The rows of one region set: where(region_id === a or region_id === b) in input order, as the stable merge of
+ * the two ascending runs rows[a_begin : a_end] and rows[b_begin : b_end] of locrec_region_partition's out_rows
+ * (n_rows entries), with every column gathered through it.  The second run is empty for a single region.
+ * cols / out_cols: HOST arrays of n_cols (1 to 8) pointers to int64 columns in `mem`: n_rows entries in, room
+ * for (a_end - a_begin) + (b_end - b_begin) entries out.  Before anything is read through `rows` the runs are
+ * checked: each strictly ascending, every entry in [0, n_rows), the two ranges inside [0, n_rows] and not
+ * overlapping - else LOCREC_E_INVALID_ARG, and nothing is written.
+ */
+int32_t locrec_region_set_gather(int64_t n_rows, int32_t n_cols, const int64_t *const *cols, const int32_t *rows,
+                                 int64_t a_begin, int64_t a_end, int64_t b_begin, int64_t b_end, int32_t mem,
+                                 int64_t *const *out_cols);
+
 /* Location.distanceMeters (Location.scala:30-38) of n pairs with the join's own device code
  * (LocationTest.scala:8-27 runs against it); NaN for a pair with an out-of-range coordinate. */
 int32_t locrec_distance_meters(int64_t n, const double *lat1, const double *lon1, const double *lat2,

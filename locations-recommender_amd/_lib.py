@@ -143,6 +143,12 @@ SIGNATURES = {
     "locrec_distance_meters": [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p],
     "locrec_rank_recommendations": [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                     C.c_int32, C.c_void_p, C.c_void_p, _i64p],
+    # the region sets of the builder mains (region_sets.hip)
+    "locrec_visits_max_timestamp": [C.c_int64, C.c_void_p, C.c_int32, _i64p],
+    "locrec_extract_region_ids": [C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, _i64p],
+    "locrec_region_partition": [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, _i64p],
+    "locrec_region_set_gather": [C.c_int64, C.c_int32, C.POINTER(C.c_void_p), C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                 C.c_int64, C.c_int32, C.POINTER(C.c_void_p)],
     # the segmented ranker (rank_batch.hip)
     "locrec_rank_recommendations_batch": [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],

@@ -310,3 +310,180 @@ def calc_rating_vectors(person_ids, entity_ids, ratings):
     rowptr = np.zeros(len(ids) + 1, np.int64)
     np.cumsum(counts, out=rowptr[1:])
     return ids, rowptr, e.astype(np.int32), r.astype(np.float64), max_id + 1
+
+
+# ---- the builder mains' bodies (knn/RatingVectorsBuilderMain.scala:15-76, stochastic/StochasticGraphBuilderMain.scala:
+# 18-45): the two sample tables -> place visits -> every region set's Parquet sets, computed on the device ---------------
+
+def _column_i64(col):
+    """A Parquet column as int64: integers of any width are widened (DataUtils.scala:14-31 casts region_id to long, and
+    it may arrive as a dictionary-encoded Hive partition column); a timestamp of any unit becomes epoch milliseconds
+    (floor), an INT96 / date-time the reader maps to a timestamp included."""
+    import pyarrow as pa
+    import pyarrow.compute as pc
+    arr = col.combine_chunks() if isinstance(col, pa.ChunkedArray) else col
+    if pa.types.is_dictionary(arr.type):
+        arr = arr.dictionary_decode()
+    if arr.null_count:
+        raise L.IllegalArgumentException("null entry in an id / timestamp column")
+    if pa.types.is_timestamp(arr.type):
+        per_ms = {"s": None, "ms": 1, "us": 1_000, "ns": 1_000_000}[arr.type.unit]
+        raw = np.asarray(arr.cast(pa.int64()).to_numpy(zero_copy_only=False), dtype=np.int64)
+        return raw * 1000 if per_ms is None else raw // per_ms
+    if pa.types.is_string(arr.type) or pa.types.is_large_string(arr.type):
+        arr = pc.cast(arr, pa.int64())   # a partition value read without a schema
+    return np.asarray(arr.to_numpy(zero_copy_only=False), dtype=np.int64)
+
+
+def _column_f64(col):
+    return np.asarray(col.to_numpy(), dtype=np.float64)
+
+
+def load_location_visits(data_dir):
+    """DataUtils.loadLocationVisits (:25-31): location_visits_sample -> dict(person_id, timestamp (epoch ms), latitude,
+    longitude, region_id), the mapping prep.calc_place_visits takes."""
+    t = _read(os.path.join(data_dir, "location_visits_sample"), ["person_id", "timestamp", "latitude", "longitude", "region_id"])
+    return {"person_id": _column_i64(t["person_id"]), "timestamp": _column_i64(t["timestamp"]),
+            "latitude": _column_f64(t["latitude"]), "longitude": _column_f64(t["longitude"]),
+            "region_id": _column_i64(t["region_id"])}
+
+
+def load_places_full(data_dir):
+    """DataUtils.loadPlaces (:17-23) with every column the builders use: places_sample -> dict(id, latitude, longitude,
+    region_id, category_id)."""
+    t = _read(os.path.join(data_dir, "places_sample"), ["id", "latitude", "longitude", "region_id", "category_id"])
+    return {"id": _column_i64(t["id"]), "latitude": _column_f64(t["latitude"]), "longitude": _column_f64(t["longitude"]),
+            "region_id": _column_i64(t["region_id"]), "category_id": _column_i64(t["category_id"])}
+
+
+def load_place_visits(path):
+    """What write_place_visits wrote (PlaceVisits.scala:40-46,116-121) -> dict of five int64 columns."""
+    names = ("person_id", "timestamp", "place_id", "region_id", "category_id")
+    t = _read(path, list(names))
+    return {k: _column_i64(t[k]) for k in names}
+
+
+def _host(a, dtype):
+    """A numpy array of a column that may be a CUDA tensor (the one copy to the host a file needs)."""
+    if hasattr(a, "detach"):
+        a = a.detach().cpu().numpy()
+    return np.ascontiguousarray(a, dtype)
+
+
+def _write_dir(path, table):
+    """df.write.mode(SaveMode.Overwrite).parquet(path) with one part file: a directory holding part-00000.parquet and
+    _SUCCESS.  Overwrite removes the part files of an earlier write, nothing else."""
+    import pyarrow.parquet as pq
+    os.makedirs(path, exist_ok=True)
+    for name in os.listdir(path):
+        if name.startswith("part-") or name == "_SUCCESS":
+            os.remove(os.path.join(path, name))
+    pq.write_table(table, os.path.join(path, "part-00000.parquet"))
+    open(os.path.join(path, "_SUCCESS"), "w").close()
+
+
+def write_place_visits(path, place_visits):
+    """PlaceVisits.writePlaceVisits (:116-121): (person_id, timestamp, place_id, region_id, category_id); the timestamp
+    as a Parquet timestamp of milliseconds."""
+    import pyarrow as pa
+    cols = {k: _host(place_visits[k], np.int64) for k in ("person_id", "timestamp", "place_id", "region_id", "category_id")}
+    arrays = [pa.array(cols["person_id"], pa.int64()), pa.array(cols["timestamp"], pa.int64()).cast(pa.timestamp("ms")),
+              pa.array(cols["place_id"], pa.int64()), pa.array(cols["region_id"], pa.int64()),
+              pa.array(cols["category_id"], pa.int64())]
+    _write_dir(path, pa.table(arrays, names=["person_id", "timestamp", "place_id", "region_id", "category_id"]))
+
+
+def write_rating_vectors(path, person_ids, rowptr, indices, values, size, vector_column="rating_vector"):
+    """(person_id: long, rating_vector: VectorUDT) (RatingVectorsBuilder.scala:10-25) in the struct layout the readers
+    follow: type 0 (sparse), size, indices: array<int>, values: array<double>.  No person: an empty file of that schema."""
+    import pyarrow as pa
+    pid, idx, val = _host(person_ids, np.int64), _host(indices, np.int32), _host(values, np.float64)
+    n = len(pid)
+    ptr = np.zeros(1, np.int64) if rowptr is None or n == 0 else _host(rowptr, np.int64)
+    if len(ptr) != n + 1 or ptr[-1] != len(idx) or len(val) != len(idx) or ptr[-1] >= 2**31:
+        raise L.IllegalArgumentException("rowptr does not describe the indices / values (below 2^31 entries)")
+    offs = pa.array((ptr - ptr[0]).astype(np.int32), pa.int32())
+    vec = pa.StructArray.from_arrays(
+        [pa.array(np.zeros(n, np.int8), pa.int8()), pa.array(np.full(n, int(size), np.int32), pa.int32()),
+         pa.ListArray.from_arrays(offs, pa.array(idx, pa.int32())), pa.ListArray.from_arrays(offs, pa.array(val, pa.float64()))],
+        fields=[pa.field("type", pa.int8()), pa.field("size", pa.int32()), pa.field("indices", pa.list_(pa.int32())),
+                pa.field("values", pa.list_(pa.float64()))])
+    _write_dir(path, pa.table([pa.array(pid, pa.int64()), vec], names=["person_id", vector_column]))
+
+
+def write_place_ratings(path, person_ids, place_ids, ratings):
+    """(person_id, place_id, rating: long) (RatingsBuilder.scala:38-47)."""
+    import pyarrow as pa
+    _write_dir(path, pa.table([pa.array(_host(person_ids, np.int64), pa.int64()), pa.array(_host(place_ids, np.int64), pa.int64()),
+                               pa.array(_host(ratings, np.int64), pa.int64())], names=["person_id", "place_id", "rating"]))
+
+
+def write_stochastic_graph(path, source_ids, target_ids, balanced_weights):
+    """(source_id, target_id, balanced_weight) (StochasticGraphBuilder.scala:12-16), rows in the given order."""
+    import pyarrow as pa
+    _write_dir(path, pa.table([pa.array(_host(source_ids, np.int64), pa.int64()), pa.array(_host(target_ids, np.int64), pa.int64()),
+                               pa.array(_host(balanced_weights, np.float64), pa.float64())],
+                              names=["source_id", "target_id", "balanced_weight"]))
+
+
+def _device_place_visits(data_dir, last_days_count, tz):
+    """The common head of both builder mains (doMain): load the two tables, calcPlaceVisits on the device, write
+    place_visits.  -> (place visits as CUDA tensors, the distinct region ids of the places, ascending)."""
+    import torch
+    from . import _cache, prep
+    _cache.require_gpu_backend("the builder mains")
+    visits, places = load_location_visits(data_dir), load_places_full(data_dir)
+    dv = {k: torch.from_numpy(np.array(v)).cuda() for k, v in visits.items()}   # (a copy: arrow's buffers are read-only)
+    dp = {k: torch.from_numpy(np.array(v)).cuda() for k, v in places.items()}
+    visits_from = prep.visits_from_timestamp(prep.max_timestamp(dv["timestamp"]), last_days_count, tz)
+    place_visits = prep.calc_place_visits(dv, dp, visits_from)
+    write_place_visits(os.path.join(data_dir, "place_visits"), place_visits)
+    return place_visits, prep.extract_region_ids(dp["region_id"]).tolist()
+
+
+def rating_vectors_builder_main(data_dir, last_days_count, max_rated_places, max_rated_categories, tz=None):
+    """RatingVectorsBuilderMain.doMain (:15-76) without Spark: location_visits_sample + places_sample -> place_visits and,
+    for every region and every pair of regions, place_rating_vectors / category_rating_vectors / place_ratings under
+    the names the recommender main reads back (DataUtils.scala:42-60).  Every step between the loads and the files
+    runs on the device, the per-set rows coming from one prep.RegionSetPlan.  tz: the session time zone of
+    calcVisitsFromTimestamp (UTC by default).  -> the region sets written, in order."""
+    from . import prep
+    place_visits, region_ids = _device_place_visits(data_dir, last_days_count, tz)
+    plan = prep.RegionSetPlan(place_visits, region_ids)
+    none = np.empty(0, np.int64)
+    written = []
+    for rs in prep.region_sets(region_ids):
+        names = [generate_file_name(rs, data_dir, f) for f in ("place_rating_vectors", "category_rating_vectors", "place_ratings")]
+        if plan.count(rs) == 0:
+            write_rating_vectors(names[0], none, None, none, none, 0)
+            write_rating_vectors(names[1], none, None, none, none, 0)
+            write_place_ratings(names[2], none, none, none)
+        else:
+            pv = plan.place_visits(rs)
+            pp, pe, pr = prep.calc_ratings(pv["person_id"], pv["place_id"], max_rated_places)
+            cp, ce, cr = prep.calc_ratings(pv["person_id"], pv["category_id"], max_rated_categories)
+            write_rating_vectors(names[0], *prep.calc_rating_vectors(pp, pe, pr))
+            write_rating_vectors(names[1], *prep.calc_rating_vectors(cp, ce, cr))
+            write_place_ratings(names[2], pp, pe, pr)
+        written.append(rs)
+    return written
+
+
+def stochastic_graph_builder_main(data_dir, last_days_count, beta_person_place, beta_person_category, tz=None):
+    """StochasticGraphBuilderMain.doMain (:18-45) without Spark: the two sample tables -> place_visits and one
+    stochastic_graph set per region and per pair of regions (DataUtils.scala:33-35), every set's four edge families
+    and their balancing computed on the device from one prep.RegionSetPlan.  -> the region sets written, in order."""
+    from . import prep
+    place_visits, region_ids = _device_place_visits(data_dir, last_days_count, tz)
+    plan = prep.RegionSetPlan(place_visits, region_ids)
+    none = np.empty(0, np.int64)
+    written = []
+    for rs in prep.region_sets(region_ids):
+        name = generate_file_name(rs, data_dir, "stochastic_graph")
+        if plan.count(rs) == 0:
+            write_stochastic_graph(name, none, none, np.empty(0, np.float64))
+        else:
+            write_stochastic_graph(name, *prep.generate_stochastic_graph(plan.place_visits(rs), beta_person_place,
+                                                                         beta_person_category))
+        written.append(rs)
+    return written

@@ -15,6 +15,10 @@ SURVEY.md 8f rows f-2 and f-4) behind the names of the reference's builder objec
                                                                           stochastic/PlaceSimilarPlace.scala:18-63
     generate_stochastic_graph    StochasticGraphBuilderMain.generateStochasticGraph
                                                                           stochastic/StochasticGraphBuilderMain.scala:47-66
+    max_timestamp / visits_from_timestamp   PlaceVisits.calcVisitsFromTimestamp   PlaceVisits.scala:50-61
+    extract_region_ids           PlaceVisits.extractRegionIds             PlaceVisits.scala:69-78
+    region_sets / RegionSetPlan  PlaceVisits.extractRegionsPlaceVisits    PlaceVisits.scala:63-67,80-87
+    knn_indexes_by_region_set / sg_graphs_by_region_set   the per-set loops of both builder mains
 
 Every function takes numpy arrays (host in, host out) or torch CUDA tensors (device in, device out:
 nothing passes through the host, and the outputs of calc_rating_vectors go straight into
@@ -332,3 +336,155 @@ def sg_graph_from_visits(place_visits, beta_person_place, beta_person_category):
     if _is_tensor(s):
         return SgGraph.from_device(s.contiguous(), t.contiguous(), w.contiguous())
     return SgGraph(s, t, w)
+
+
+# ---- every region set of the builder mains from one place-visit table (csrc/region_sets.hip) -------------------
+
+PLACE_VISIT_COLUMNS = ("person_id", "timestamp", "place_id", "region_id", "category_id")   # PlaceVisits.scala:40-46
+
+
+def max_timestamp(timestamps):
+    """max(timestamp) of PlaceVisits.calcVisitsFromTimestamp (PlaceVisits.scala:53-56) as an int.  No visits:
+    IllegalArgumentException (the reference dereferences a null there)."""
+    c = _Cols(timestamps)
+    out = C.c_int64()
+    L.check(L.lib().locrec_visits_max_timestamp(len(timestamps), c.col(timestamps, np.int64), c.mem, C.byref(out)))
+    return int(out.value)
+
+
+def extract_region_ids(region_ids):
+    """PlaceVisits.extractRegionIds (PlaceVisits.scala:69-78): the distinct region ids, ascending (Spark leaves the
+    order of distinct().collect() undefined; this project defines it, as it does for ties)."""
+    c = _Cols(region_ids)
+    n = len(region_ids)
+    r = c.col(region_ids, np.int64)
+    cnt = C.c_int64(0)   # first call: count only
+    L.check(L.lib().locrec_extract_region_ids(n, r, c.mem, None, C.byref(cnt)))
+    m = cnt.value
+    out, outp = c.out(m, np.int64)
+    if m:
+        cnt = C.c_int64(m)
+        L.check(L.lib().locrec_extract_region_ids(n, r, c.mem, outp, C.byref(cnt)))
+    return out[:m]
+
+
+def visits_from_timestamp(max_timestamp_ms, last_days_count, tz=None):
+    """The day arithmetic of PlaceVisits.calcVisitsFromTimestamp (PlaceVisits.scala:57-60),
+    Timestamp.valueOf(maxTimestamp.toLocalDateTime.minusDays(lastDaysCount)), on the host: epoch milliseconds ->
+    the wall-clock time of `tz` (a datetime.tzinfo, UTC by default: the reference uses the JVM's default zone) ->
+    minus whole days on that wall clock -> epoch milliseconds.  In UTC or at a fixed offset this is
+    max - days * 86,400,000.  In a zone with daylight saving the wall-clock day keeps its time of day across a
+    switch; a wall-clock result that falls into a DST gap or overlap is *parity unpinned*: java.sql.Timestamp
+    resolves it through the legacy calendar, here it is datetime's fold=0 reading (the offset before the switch)."""
+    from datetime import datetime, timedelta, timezone
+    tz = timezone.utc if tz is None else tz
+    epoch = datetime(1970, 1, 1, tzinfo=timezone.utc)
+    local = (epoch + timedelta(milliseconds=int(max_timestamp_ms))).astimezone(tz).replace(tzinfo=None)
+    back = (local - timedelta(days=int(last_days_count))).replace(tzinfo=tz)
+    return (back - epoch) // timedelta(milliseconds=1)
+
+
+def region_sets(region_ids):
+    """PlaceVisits.extractRegionsPlaceVisits' sets (PlaceVisits.scala:64-65): regionIds.map(Seq(_)) ++
+    regionIds.combinations(2) - every single region in the given order, then every pair.  -> list of tuples."""
+    import itertools
+    ids = [int(r) for r in region_ids]
+    return [(r,) for r in ids] + list(itertools.combinations(ids, 2))
+
+
+class RegionSetPlan:
+    """The place visits of every region set from ONE partition of the table (locrec_region_partition): the row
+    numbers grouped by region, ascending inside a group, so the rows of a set are one group or the stable merge of
+    two (locrec_region_set_gather) - exactly placeVisits.where(region_id === a or region_id === b) in input order.
+    place_visits: the mapping calc_place_visits returns; region_ids: the listed regions (any order, distinct).
+    With CUDA tensors nothing but the len(region_ids) + 2 group offsets reaches the host."""
+
+    def __init__(self, place_visits, region_ids):
+        ids = sorted(int(r) for r in region_ids)
+        if any(a == b for a, b in zip(ids, ids[1:])):
+            raise L.IllegalArgumentException("region_ids must be distinct")
+        cols = [place_visits[k] for k in PLACE_VISIT_COLUMNS]
+        c = _Cols(*cols)
+        self.device, self.mem, self.n = c.device, c.mem, len(cols[0])
+        assert all(len(a) == self.n for a in cols)
+        if c.device:
+            self._torch = c.torch
+            self._dev = c.dev
+            self.columns = [a.to(c.torch.int64).contiguous() for a in cols]
+            listed = c.torch.tensor(ids, dtype=c.torch.int64, device=c.dev)
+            c.torch.cuda.current_stream(c.dev).synchronize()   # the upload and the casts above, before the library's stream
+        else:
+            self.columns = [np.ascontiguousarray(a, np.int64) for a in cols]
+            listed = np.asarray(ids, np.int64)
+        self.region_ids = ids
+        self._rank = {r: i for i, r in enumerate(ids)}
+        self.rows, rowsp = c.out(self.n, np.int32)
+        offsets = (C.c_int64 * (len(ids) + 2))()
+        L.check(L.lib().locrec_region_partition(self.n, c.col(self.columns[3], np.int64), len(ids), c.col(listed, np.int64),
+                                                c.mem, rowsp, offsets))
+        self.offsets = list(offsets)
+
+    def _ptr(self, a):
+        return a.data_ptr() if self.device else a.ctypes.data
+
+    def count(self, region_set):
+        """Rows of the set, from the offsets alone."""
+        return sum(self.offsets[g + 1] - self.offsets[g] for g in self._groups(region_set))
+
+    def _groups(self, region_set):
+        regs = sorted(set(int(r) for r in region_set))
+        if not 1 <= len(regs) <= 2:
+            raise L.IllegalArgumentException("a region set is one region or a pair of regions")
+        for r in regs:
+            if r not in self._rank:
+                raise L.IllegalArgumentException(f"region {r} is not one of the plan's regions")
+        return [self._rank[r] for r in regs]
+
+    def place_visits(self, region_set):
+        """The mapping calc_place_visits returns, cut to the rows of the region set (one region or a pair)."""
+        g = self._groups(region_set)
+        a0, a1 = self.offsets[g[0]], self.offsets[g[0] + 1]
+        b0, b1 = (self.offsets[g[1]], self.offsets[g[1] + 1]) if len(g) == 2 else (0, 0)
+        total = (a1 - a0) + (b1 - b0)
+        if self.device:
+            L.require_current_device(self.columns)
+            self._torch.cuda.current_stream(self._dev).synchronize()
+            outs = [self._torch.empty(max(total, 1), dtype=self._torch.int64, device=self._dev) for _ in self.columns]
+        else:
+            outs = [np.empty(max(total, 1), np.int64) for _ in self.columns]
+        nc = len(self.columns)
+        if total:
+            cin = (C.c_void_p * nc)(*[self._ptr(a) for a in self.columns])
+            cout = (C.c_void_p * nc)(*[self._ptr(a) for a in outs])
+            L.check(L.lib().locrec_region_set_gather(self.n, nc, cin, C.c_void_p(self._ptr(self.rows)), a0, a1, b0, b1, self.mem,
+                                                     cout))
+        return {k: o[:total] for k, o in zip(PLACE_VISIT_COLUMNS, outs)}
+
+
+def _plan_of(place_visits, region_ids):
+    return place_visits if isinstance(place_visits, RegionSetPlan) else RegionSetPlan(place_visits, region_ids)
+
+
+def knn_indexes_by_region_set(place_visits, region_ids, places_top_n=VISITED_PLACES_TOP_N,
+                              categories_top_n=VISITED_CATEGORIES_TOP_N):
+    """RatingVectorsBuilderMain.generateRegionRatingVectors (:33-76) to device handles: yields (region_set, KnnIndex)
+    for every set of region_sets(region_ids), each through knn_index_from_visits on the set's rows of one
+    RegionSetPlan (place_visits may be a plan already).  A set without visits yields None for the handle."""
+    plan = _plan_of(place_visits, region_ids)
+    for rs in region_sets(region_ids):
+        if plan.count(rs) == 0:
+            yield rs, None
+            continue
+        pv = plan.place_visits(rs)
+        yield rs, knn_index_from_visits(pv["person_id"], pv["place_id"], pv["category_id"], places_top_n, categories_top_n)
+
+
+def sg_graphs_by_region_set(place_visits, region_ids, beta_person_place, beta_person_category):
+    """StochasticGraphBuilderMain.generateRegionGraphs (:36-45) to device handles: yields (region_set, SgGraph) for
+    every set of region_sets(region_ids) through sg_graph_from_visits; None for a set without visits."""
+    plan = _plan_of(place_visits, region_ids)
+    for rs in region_sets(region_ids):
+        if plan.count(rs) == 0:
+            yield rs, None
+            continue
+        yield rs, sg_graph_from_visits(plan.place_visits(rs), beta_person_place, beta_person_category)
