@@ -57,35 +57,6 @@ thread_local DedupStats g_dedup_stats;
 
 enum { kPhaseGrid = 0, kPhaseLev = 1, kPhaseCompact = 2, kPhaseEnd = -1 };
 
-struct PhaseClock {
-    hipStream_t s = nullptr;
-    std::vector<hipEvent_t> ev;
-    std::vector<int> phase;
-    ~PhaseClock()
-    {
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-    }
-    int32_t mark(int ph)
-    {
-        hipEvent_t e;
-        LOCREC_HIP_TRY(hipEventCreate(&e));
-        ev.push_back(e);
-        phase.push_back(ph);
-        LOCREC_HIP_TRY(hipEventRecord(e, s));
-        return LOCREC_OK;
-    }
-    int32_t read(double *ms)
-    {
-        LOCREC_HIP_TRY(hipStreamSynchronize(s));
-        for (size_t i = 0; i + 1 < ev.size(); ++i) {
-            float t = 0;
-            LOCREC_HIP_TRY(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
-            if (phase[i] >= 0) ms[phase[i]] += t;
-        }
-        return LOCREC_OK;
-    }
-};
-
 #define DD_LAUNCHED() LOCREC_HIP_TRY(hipGetLastError())
 
 // ---- names ------------------------------------------------------------------------------------------------------------
@@ -369,53 +340,11 @@ int32_t lev_pairs(int64_t m, const uint32_t *pa, const uint32_t *pb, const int64
 
 // ---- the join of PlaceDeduplicator.scala:38-50 ----------------------------------------------------------------------------
 
-struct DedupError {
-    unsigned long long first_bad_place, first_bad_confirmed;  // ~0 = none
-};
-
-// a place whose region has confirmed places takes part in the join (:39): mark its region, and its Location must be
-// valid (the UDF constructs it for every joined pair, :31-32)
-__global__ void dd_check_places(int64_t np, const double *lat, const double *lon, const int64_t *region, const int64_t *regions,
-                                int32_t nr, uint32_t *region_has_place, DedupError *err)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= np) return;
-    const int64_t r = rank_of_region(regions, nr, region[i]);
-    if (r < 0) return;
-    region_has_place[r] = 1u;
-    if (!location_ok(lat[i], lon[i])) atomicMin(&err->first_bad_place, (unsigned long long)i);
-}
-
-__global__ void dd_check_confirmed(int64_t nc, const double *lat, const double *lon, const int64_t *region, const int64_t *regions,
-                                   int32_t nr, const uint32_t *region_has_place, DedupError *err)
-{
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= nc) return;
-    const int64_t r = rank_of_region(regions, nr, region[j]);
-    if (r >= 0 && region_has_place[r] && !location_ok(lat[j], lon[j])) atomicMin(&err->first_bad_confirmed, (unsigned long long)j);
-}
-
 __global__ void dd_region_rank_keys(int64_t nc, const int64_t *region, const uint32_t *rows, const int64_t *regions, int32_t nr,
                                     uint32_t *keys)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < nc) keys[i] = (uint32_t)rank_of_region(regions, nr, region[rows[i]]);
-}
-
-__global__ void dd_gather_id_keys(int64_t nc, const int64_t *ids, const uint32_t *rows, uint64_t *keys)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < nc) keys[i] = ordered_key(ids[rows[i]]);
-}
-
-template <class T>
-__device__ __forceinline__ int64_t lower_bound_in(const T *keys, int64_t lo, int64_t hi, T key)
-{
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (keys[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
 }
 
 // partners of place i: the confirmed rows of its region (:39) minus those with its own id (:40).  The confirmed rows are
@@ -428,12 +357,12 @@ __global__ void dd_partners(int64_t np, const int64_t *p_id, const int64_t *p_re
     const int64_t r = rank_of_region(regions, nr, p_region[i]);
     int64_t n = 0;
     if (r >= 0) {
-        const int64_t lo = lower_bound_in<uint32_t>(sorted_rank, 0, nc, (uint32_t)r);
-        const int64_t hi = lower_bound_in<uint32_t>(sorted_rank, lo, nc, (uint32_t)r + 1u);
+        const int64_t lo = lower_bound<uint32_t>(sorted_rank, 0, nc, (uint32_t)r);
+        const int64_t hi = lower_bound<uint32_t>(sorted_rank, lo, nc, (uint32_t)r + 1u);
         const uint64_t key = ordered_key(p_id[i]);
-        const int64_t a = lower_bound_in<uint64_t>(sorted_id, lo, hi, key);
+        const int64_t a = lower_bound<uint64_t>(sorted_id, lo, hi, key);
         int64_t b = a;
-        if (key != ~0ull) b = lower_bound_in<uint64_t>(sorted_id, a, hi, key + 1ull);
+        if (key != ~0ull) b = lower_bound<uint64_t>(sorted_id, a, hi, key + 1ull);
         else b = hi;
         n = (hi - lo) - (b - a);
     }
@@ -442,7 +371,7 @@ __global__ void dd_partners(int64_t np, const int64_t *p_id, const int64_t *p_re
 
 // One thread per place of [p_begin, p_end): the confirmed places of the (at most) 3 bands x 3 cells around it.  A
 // candidate is within max_meters (the first half of :34) and has another id (:40).  WRITE = false counts them;
-// WRITE = true stores the confirmed rows at the place's offset, ascending (an insertion sort: a place has few).
+// WRITE = true stores the confirmed rows at the place's offset, ascending.
 template <bool WRITE>
 __global__ void dd_walk(int64_t p_begin, int64_t p_end, const int64_t *p_id, const double *p_lat, const double *p_lon,
                         const int64_t *p_region, const int64_t *regions, int32_t nr, Grid g, double max_meters, int64_t nc,
@@ -458,37 +387,18 @@ __global__ void dd_walk(int64_t p_begin, int64_t p_end, const int64_t *p_id, con
     const double lat = p_lat[i], lon = p_lon[i];
     if (r >= 0 && location_ok(lat, lon)) {
         const int64_t id = p_id[i];
-        const int32_t bv = band_of(g, lat);
-        for (int32_t b = max(bv - 1, 0); b <= min(bv + 1, g.nbands - 1); ++b) {
-            double win;
-            int32_t nx;
-            band_cells(g, b, &win, &nx);
-            const double w = 360.0 / nx;
-            const int64_t c_lo = (int64_t)floor((lon - win + 180.0) / w), c_hi = (int64_t)floor((lon + win + 180.0) / w);
-            const int64_t ncell = min(c_hi - c_lo + 1, (int64_t)nx);
-            for (int64_t t = 0; t < ncell; ++t) {
-                const int64_t cx = ((c_lo + t) % nx + nx) % nx;  // cells wrap around the antimeridian
-                const uint64_t key = ((uint64_t)r << (2 * kCellBits)) | ((uint64_t)b << kCellBits) | (uint64_t)cx;
-                for (int64_t at = lower_bound_key(keys, nc, key); at < nc && keys[at] == key; ++at) {
-                    const uint32_t j = conf_rows[at];
-                    if (c_id[j] != id && distance_meters(lat, lon, c_lat[j], c_lon[j]) <= max_meters) {
-                        if (WRITE) mine[found] = j;
-                        ++found;
-                    }
-                }
+        for_each_grid_candidate(g, r, lat, lon, keys, nc, conf_rows, [&](uint32_t j) {
+            if (c_id[j] != id && distance_meters(lat, lon, c_lat[j], c_lon[j]) <= max_meters) {
+                if (WRITE) mine[found] = j;
+                ++found;
             }
-        }
+        });
     }
     if (!WRITE) {
         counts[i] = found;
         return;
     }
-    for (unsigned long long a = 1; a < found; ++a) {
-        const uint32_t v = mine[a];
-        unsigned long long b = a;
-        for (; b > 0 && mine[b - 1] > v; --b) mine[b] = mine[b - 1];
-        mine[b] = v;
-    }
+    sort_ascending(mine, found);
     uint32_t *who = cand_place + (offsets[i] - base);
     for (unsigned long long a = 0; a < found; ++a) who[a] = (uint32_t)i;
 }
@@ -629,70 +539,44 @@ try {
     LOCREC_TRY(clock.mark(kPhaseGrid));
 
     // distinct regions of the confirmed places, ascending
+    DevBuf<int64_t> regions;
+    int32_t nr = 0;
+    LOCREC_TRY(distinct_ids(cr.p, n_confirmed, tmp, s, regions, &nr));
+    if (nr >= (1 << 24)) return fail(LOCREC_E_INVALID_ARG, "%d distinct regions: at most 2^24 - 1 are supported", nr);
+
+    // Location's require (Location.scala:7-8) for every row that meets a row of the other side
+    DevBuf<uint32_t> has_place;
+    DevBuf<LocationError> err;
+    LOCREC_TRY(has_place.alloc((size_t)nr));
+    LOCREC_TRY(err.alloc(1));
+    LOCREC_HIP_TRY(hipMemsetAsync(has_place.p, 0, (size_t)nr * 4, s));
+    LOCREC_HIP_TRY(hipMemsetAsync(err.p, 0xFF, sizeof(LocationError), s));
+    hipLaunchKernelGGL(check_side_a, grid_for(n_places), dim3(256), 0, s, n_places, (const int64_t *)nullptr, (int64_t)0, plat.p,
+                       plon.p, pr.p, regions.p, nr, has_place.p, err.p);
+    hipLaunchKernelGGL(check_side_b, grid_for(n_confirmed), dim3(256), 0, s, n_confirmed, clat.p, clon.p, cr.p, regions.p, nr,
+                       has_place.p, err.p);
+    DD_LAUNCHED();
+    LocationError le;
+    LOCREC_HIP_TRY(hipMemcpyAsync(&le, err.p, sizeof le, hipMemcpyDeviceToHost, s));
+    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    LOCREC_TRY(location_error(le, plat.p, plon.p, "place", n_places, clat.p, clon.p, "confirmed place", inout_count));
+
     DevBuf<uint64_t> k0, k1;
     DevBuf<uint32_t> r0, r1;
-    DevBuf<int64_t> regions;
-    DevBuf<int32_t> nr_dev;
     LOCREC_TRY(k0.alloc((size_t)n_confirmed));
     LOCREC_TRY(k1.alloc((size_t)n_confirmed));
     LOCREC_TRY(r0.alloc((size_t)n_confirmed));
     LOCREC_TRY(r1.alloc((size_t)n_confirmed));
-    LOCREC_TRY(regions.alloc((size_t)n_confirmed));
-    LOCREC_TRY(nr_dev.alloc(1));
-    hipLaunchKernelGGL(pr_iota_keys, grid_for(n_confirmed), dim3(256), 0, s, n_confirmed, cr.p, k0.p, r0.p);
-    PR_PRIM(tmp, prim::sort_keys(p_, bytes_, k0.p, k1.p, (int)n_confirmed, 0, 64, s));
-    PR_PRIM(tmp, prim::unique(p_, bytes_, k1.p, k0.p, nr_dev.p, (int)n_confirmed, s));
-    int32_t nr = 0;
-    LOCREC_HIP_TRY(hipMemcpyAsync(&nr, nr_dev.p, sizeof nr, hipMemcpyDeviceToHost, s));
-    LOCREC_HIP_TRY(hipStreamSynchronize(s));
-    if (nr >= (1 << 24)) return fail(LOCREC_E_INVALID_ARG, "%d distinct regions: at most 2^24 - 1 are supported", nr);
-    {   // ordered_key() back to the signed ids
-        std::vector<uint64_t> hk((size_t)nr);
-        LOCREC_HIP_TRY(hipMemcpy(hk.data(), k0.p, (size_t)nr * 8, hipMemcpyDeviceToHost));
-        std::vector<int64_t> hr((size_t)nr);
-        for (int32_t i = 0; i < nr; ++i) hr[(size_t)i] = (int64_t)(hk[(size_t)i] ^ 0x8000000000000000ull);
-        LOCREC_HIP_TRY(hipMemcpy(regions.p, hr.data(), (size_t)nr * 8, hipMemcpyHostToDevice));
-    }
-
-    // Location's require (Location.scala:7-8) for every row that meets a row of the other side
-    DevBuf<uint32_t> has_place;
-    DevBuf<DedupError> err;
-    LOCREC_TRY(has_place.alloc((size_t)nr));
-    LOCREC_TRY(err.alloc(1));
-    LOCREC_HIP_TRY(hipMemsetAsync(has_place.p, 0, (size_t)nr * 4, s));
-    LOCREC_HIP_TRY(hipMemsetAsync(err.p, 0xFF, sizeof(DedupError), s));
-    hipLaunchKernelGGL(dd_check_places, grid_for(n_places), dim3(256), 0, s, n_places, plat.p, plon.p, pr.p, regions.p, nr,
-                       has_place.p, err.p);
-    hipLaunchKernelGGL(dd_check_confirmed, grid_for(n_confirmed), dim3(256), 0, s, n_confirmed, clat.p, clon.p, cr.p, regions.p,
-                       nr, has_place.p, err.p);
-    DD_LAUNCHED();
-    DedupError de;
-    LOCREC_HIP_TRY(hipMemcpyAsync(&de, err.p, sizeof de, hipMemcpyDeviceToHost, s));
-    LOCREC_HIP_TRY(hipStreamSynchronize(s));
-    if (de.first_bad_place != ~0ull || de.first_bad_confirmed != ~0ull) {
-        const bool place = de.first_bad_place != ~0ull;
-        const int64_t row = (int64_t)(place ? de.first_bad_place : de.first_bad_confirmed);
-        double lat = 0, lon = 0;
-        LOCREC_HIP_TRY(hipMemcpy(&lat, (place ? plat.p : clat.p) + row, 8, hipMemcpyDeviceToHost));
-        LOCREC_HIP_TRY(hipMemcpy(&lon, (place ? plon.p : clon.p) + row, 8, hipMemcpyDeviceToHost));
-        *inout_count = place ? -(1 + row) : -(1 + n_places + row);
-        if (!(lat >= -90.0 && lat <= 90.0))  // the reference's messages (Location.scala:7-8)
-            return fail(LOCREC_E_INVALID_ARG, "requirement failed: Latitude %.17g must be within range [-90.0, 90.0] (%s %lld)", lat,
-                        place ? "place" : "confirmed place", (long long)row);
-        return fail(LOCREC_E_INVALID_ARG, "requirement failed: Longitude %.17g must be within range [-180.0, 180.0] (%s %lld)", lon,
-                    place ? "place" : "confirmed place", (long long)row);
-    }
-
     if (out_not_same_counts) {  // the confirmed rows by (region rank, id): two stable passes
         DevBuf<uint32_t> rk0, rk1;
         LOCREC_TRY(rk0.alloc((size_t)n_confirmed));
         LOCREC_TRY(rk1.alloc((size_t)n_confirmed));
-        hipLaunchKernelGGL(pr_iota_keys, grid_for(n_confirmed), dim3(256), 0, s, n_confirmed, ci.p, k0.p, r0.p);
-        PR_PRIM(tmp, prim::sort_pairs(p_, bytes_, k0.p, k1.p, r0.p, r1.p, (int)n_confirmed, 0, 64, s));
+        hipLaunchKernelGGL(iota_keys, grid_for(n_confirmed), dim3(256), 0, s, n_confirmed, ci.p, k0.p, r0.p);
+        LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, k0.p, k1.p, r0.p, r1.p, (int)n_confirmed, 0, 64, s));
         hipLaunchKernelGGL(dd_region_rank_keys, grid_for(n_confirmed), dim3(256), 0, s, n_confirmed, cr.p, r1.p, regions.p, nr,
                            rk0.p);
-        PR_PRIM(tmp, prim::sort_pairs(p_, bytes_, rk0.p, rk1.p, r1.p, r0.p, (int)n_confirmed, 0, 24, s));
-        hipLaunchKernelGGL(dd_gather_id_keys, grid_for(n_confirmed), dim3(256), 0, s, n_confirmed, ci.p, r0.p, k0.p);
+        LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, rk0.p, rk1.p, r1.p, r0.p, (int)n_confirmed, 0, 24, s));
+        hipLaunchKernelGGL(gather_id_keys, grid_for(n_confirmed), dim3(256), 0, s, n_confirmed, ci.p, r0.p, k0.p);
         hipLaunchKernelGGL(dd_partners, grid_for(n_places), dim3(256), 0, s, n_places, pi.p, pr.p, regions.p, nr, n_confirmed,
                            rk1.p, k0.p, ons.p);
         DD_LAUNCHED();
@@ -705,7 +589,7 @@ try {
         const Grid g = make_grid(max_meters);
         hipLaunchKernelGGL(pr_place_keys, grid_for(n_confirmed), dim3(256), 0, s, n_confirmed, clat.p, clon.p, cr.p, regions.p, nr,
                            g, k0.p, r0.p);
-        PR_PRIM(tmp, prim::sort_pairs(p_, bytes_, k0.p, k1.p, r0.p, r1.p, (int)n_confirmed, 0, 64, s));
+        LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, k0.p, k1.p, r0.p, r1.p, (int)n_confirmed, 0, 64, s));
 
         DevBuf<unsigned long long> counts, offsets;
         LOCREC_TRY(counts.alloc((size_t)n_places));
@@ -714,7 +598,7 @@ try {
                            regions.p, nr, g, max_meters, n_confirmed, k1.p, r1.p, ci.p, clat.p, clon.p, counts.p, nullptr, 0ull,
                            nullptr, nullptr);
         DD_LAUNCHED();
-        PR_PRIM(tmp, prim::exclusive_sum(p_, bytes_, counts.p, offsets.p, (int)n_places, s));
+        LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, counts.p, offsets.p, (int)n_places, s));
         unsigned long long last_off = 0, last_cnt = 0;
         LOCREC_HIP_TRY(hipMemcpyAsync(&last_off, offsets.p + (n_places - 1), 8, hipMemcpyDeviceToHost, s));
         LOCREC_HIP_TRY(hipMemcpyAsync(&last_cnt, counts.p + (n_places - 1), 8, hipMemcpyDeviceToHost, s));
@@ -759,7 +643,7 @@ try {
                 LOCREC_TRY(lev_pairs(m, cand_place.p, cand_conf.p, PN.off.p, PN.units.p, CN.off.p, CN.units.p, k, full_dp, dist.p, s));
                 LOCREC_TRY(clock.mark(kPhaseCompact));
                 hipLaunchKernelGGL(dd_same_flags, grid_for(m), dim3(256), 0, s, m, dist.p, k, flags.p);
-                PR_PRIM(tmp, prim::exclusive_sum(p_, bytes_, flags.p, pos.p, (int)m, s));
+                LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, flags.p, pos.p, (int)m, s));
                 hipLaunchKernelGGL(dd_emit_same, grid_for(m), dim3(256), 0, s, m, flags.p, pos.p, cand_place.p, cand_conf.p, dist.p,
                                    total_same, cap, op.p, oc.p, od.p);
                 if (out_not_same_counts)

@@ -29,6 +29,7 @@
 #include <numeric>
 
 #include "knn_index.h"
+#include "offline.h"
 
 namespace {
 
@@ -36,28 +37,12 @@ using namespace locrec;
 
 // ---- small helpers ---------------------------------------------------------------------------
 
-struct Temp {  // rocPRIM temporary storage, reused
-    DevBuf<unsigned char> buf;
-};
-
-#define KB_PRIM(tmp, stream, call_with_args)                                           \
-    do {                                                                              \
-        size_t bytes_ = 0;                                                            \
-        void *p_ = nullptr;                                                           \
-        LOCREC_HIP_TRY((call_with_args));                                             \
-        LOCREC_TRY((tmp).buf.reserve(bytes_ + 256));                                  \
-        p_ = (tmp).buf.p;                                                             \
-        LOCREC_HIP_TRY((call_with_args));                                             \
-    } while (0)
-
 int ceil_log2_64(int64_t v)
 {
     int l = 0;
     while (((int64_t)1 << l) < v) ++l;
     return l;
 }
-
-dim3 grid_for(int64_t n, int threads = 256) { return dim3((unsigned)std::max<int64_t>(1, (n + threads - 1) / threads)); }
 
 // ---- validation ------------------------------------------------------------------------------
 
@@ -218,7 +203,7 @@ __global__ void kb_apply_order(int64_t n, const uint64_t *keys_sorted, const uin
     len_p[r] = np;
     len_c[r] = nc;
     if (len_r) len_r[r] = r_ptr ? r_ptr[src + 1] - r_ptr[src] : np;
-    id_keys[r] = (uint64_t)id ^ 0x8000000000000000ull;  // signed order as unsigned order
+    id_keys[r] = ordered_key(id);
     id_vals[r] = (uint32_t)r;
 }
 
@@ -229,7 +214,7 @@ __global__ void kb_rank_ids(int64_t n, const uint64_t *id_keys_sorted, const uin
     if (k >= n) return;
     const uint32_t row = rows_sorted[k];
     rid[row] = (uint32_t)k;
-    ids_by_rank[k] = (int64_t)(id_keys_sorted[k] ^ 0x8000000000000000ull);
+    ids_by_rank[k] = id_of_key(id_keys_sorted[k]);
     row_of_rid[k] = (int32_t)row;
     if (k > 0 && id_keys_sorted[k] == id_keys_sorted[k - 1]) atomicMin(dup, (unsigned long long)k);
 }
@@ -449,18 +434,6 @@ __global__ void kb_default_ratings(int64_t ne, const int32_t *orig_idx, int64_t 
     if (i < ne) place[i] = orig_idx[i];
 }
 
-__global__ void kb_place_sortkeys(int64_t ne, const int64_t *place, uint64_t *keys)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < ne) keys[i] = (uint64_t)place[i] ^ 0x8000000000000000ull;
-}
-
-__global__ void kb_unbias(int64_t nc, const uint64_t *keys, int64_t *ids)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < nc) ids[i] = (int64_t)(keys[i] ^ 0x8000000000000000ull);
-}
-
 // pidx_of[e] = index of the rating's place among the distinct places; transpose keys (place index, row)
 __global__ void kb_place_index(int64_t n, const int64_t *r_ptr, const int64_t *place, const int64_t *cplace, int64_t ncp,
                                int32_t *pidx_of, uint64_t *tkeys, uint32_t *tvals)
@@ -494,13 +467,7 @@ __global__ void kb_cp_ptr(int64_t ncp, int64_t ne, const uint64_t *tkeys, int64_
 {
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p > ncp) return;
-    const uint64_t want = (uint64_t)p << 32;
-    int64_t a = 0, b = ne;
-    while (a < b) {
-        const int64_t m = (a + b) >> 1;
-        if (tkeys[m] < want) a = m + 1; else b = m;
-    }
-    cp_ptr[p] = a;
+    cp_ptr[p] = lower_bound<uint64_t>(tkeys, 0, ne, (uint64_t)p << 32);
 }
 
 struct MaxI64 {
@@ -523,7 +490,7 @@ int32_t build_family(locrec_knn_index *ix, DevFamily &d, int32_t dim, int32_t vb
     LOCREC_HIP_TRY(hipMemsetAsync(w64.p, 0, ((size_t)nslices + 1) * 8, s));
     if (nslices > 0)
         hipLaunchKernelGGL(kb_slice_width, grid_for(nslices), dim3(256), 0, s, n, nslices, nnz_dev.p, packed ? 1 : 0, d.sell_w.p, w64.p);
-    KB_PRIM(tmp, s, prim::exclusive_sum(p_, bytes_, w64.p, d.sell_off.p, nslices + 1, s));
+    LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, w64.p, d.sell_off.p, nslices + 1, s));
     int64_t total = 0;
     LOCREC_HIP_TRY(hipMemcpyAsync(&total, d.sell_off.p + nslices, 8, hipMemcpyDeviceToHost, s));
     LOCREC_HIP_TRY(hipStreamSynchronize(s));
@@ -701,7 +668,7 @@ int32_t knn_build_device(int64_t n, const int64_t *ids, const int64_t *p_ptr, co
         LOCREC_TRY(dk.alloc((size_t)p_dim));
         LOCREC_TRY(dk2.alloc((size_t)p_dim));
         hipLaunchKernelGGL(kb_dim_keys, grid_for(p_dim), dim3(256), 0, s, p_dim, freq.p, dk.p);
-        KB_PRIM(tmp, s, prim::sort_keys(p_, bytes_, dk.p, dk2.p, p_dim, 0, 64, s));
+        LOCREC_PRIM(tmp, prim::sort_keys(p_, bytes_, dk.p, dk2.p, p_dim, 0, 64, s));
         hipLaunchKernelGGL(kb_new_of_old, grid_for(p_dim), dim3(256), 0, s, p_dim, dk2.p, new_of_old.p, freq_new.p);
         pop_h = std::min<int32_t>(p_dim, cfg::kPopTable);
         if (ix->env_pop_h > 0) pop_h = std::min<int32_t>(p_dim, ix->env_pop_h);
@@ -738,7 +705,7 @@ int32_t knn_build_device(int64_t n, const int64_t *ids, const int64_t *p_ptr, co
     if (n > 0) {
         hipLaunchKernelGGL(kb_row_keys, grid_for(n), dim3(256), 0, s, n, p_ptr, p_idx, c_ptr, use_pop ? new_of_old.p : nullptr, key_h,
                            rk.p, rv.p);
-        KB_PRIM(tmp, s, prim::sort_pairs(p_, bytes_, rk.p, rk2.p, rv.p, order.p, (int)n, 0, 64, s));
+        LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, rk.p, rk2.p, rv.p, order.p, (int)n, 0, 64, s));
         hipLaunchKernelGGL(kb_apply_order, grid_for(n), dim3(256), 0, s, n, rk2.p, order.p, ids, r_ptr, ids_row.p, row_of_input.p,
                            nnz_p.p, nnz_c.p, npop.p, len_p.p, len_c.p, len_r.p, idk.p, idv.p);
     }
@@ -750,7 +717,7 @@ int32_t knn_build_device(int64_t n, const int64_t *ids, const int64_t *p_ptr, co
     LOCREC_TRY(ix->ids_by_rank.alloc(nn));
     LOCREC_TRY(ix->row_of_rid.alloc(nn));
     if (n > 0) {
-        KB_PRIM(tmp, s, prim::sort_pairs(p_, bytes_, idk.p, idk2.p, idv.p, idv2.p, (int)n, 0, 64, s));
+        LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, idk.p, idk2.p, idv.p, idv2.p, (int)n, 0, 64, s));
         hipLaunchKernelGGL(kb_rank_ids, grid_for(n), dim3(256), 0, s, n, idk2.p, idv2.p, ix->rid.p, ix->ids_by_rank.p,
                            ix->row_of_rid.p, dup.p);
     }
@@ -792,7 +759,7 @@ int32_t knn_build_device(int64_t n, const int64_t *ids, const int64_t *p_ptr, co
     auto csr_of = [&](DevFamily &d, const int64_t *in_ptr, const int32_t *in_idx, const double *in_val, int64_t ne,
                       DevBuf<int64_t> &len, const int32_t *renumber, DevBuf<int32_t> *orig_idx) -> int32_t {
         LOCREC_TRY(d.csr_ptr.alloc(nn + 1));
-        KB_PRIM(tmp, s, prim::exclusive_sum(p_, bytes_, len.p, d.csr_ptr.p, (int)(n + 1), s));
+        LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, len.p, d.csr_ptr.p, (int)(n + 1), s));
         const size_t nee = (size_t)std::max<int64_t>(1, ne);
         LOCREC_TRY(d.csr_idx.alloc(nee));
         LOCREC_TRY(d.csr_val.alloc(nee));
@@ -809,8 +776,8 @@ int32_t knn_build_device(int64_t n, const int64_t *ids, const int64_t *p_ptr, co
         if (renumber) {  // the renumbered indices of a row are no longer ascending: sort by (row, new index)
             LOCREC_TRY(k2.alloc(nee));
             LOCREC_TRY(v2.alloc(nee));
-            KB_PRIM(tmp, s, prim::sort_pairs(p_, bytes_, k1.p, k2.p, v1.p, v2.p, (int)ne, 0,
-                                                              32 + std::max(1, ceil_log2_64(n + 1)), s));
+            LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, k1.p, k2.p, v1.p, v2.p, (int)ne, 0,
+                                                               32 + std::max(1, ceil_log2_64(n + 1)), s));
             ks = k2.p;
             vs = v2.p;
         }
@@ -876,7 +843,7 @@ int32_t knn_build_device(int64_t n, const int64_t *ids, const int64_t *p_ptr, co
         if (skip) hipLaunchKernelGGL(kb_freq_drop_rows, grid_for(n), dim3(256), 0, s, n, ix->fp.csr_ptr.p, ix->fp.csr_idx.p, skip, freq_new.p);
         hipLaunchKernelGGL(kb_ht_rows, grid_for(n), dim3(256), 0, s, n, ix->fp.csr_ptr.p, ix->fp.csr_idx.p, ix->fp.csr_val.p,
                            ix->fc.csr_ptr.p, ix->fc.csr_val.p, ht_h, freq_new.p, nhead.p, tail_nnz.p, tail_len.p, ht.tail_hits.p, ht.ss.p, skip);
-        KB_PRIM(tmp, s, prim::exclusive_sum(p_, bytes_, tail_len.p, tail_ptr.p, (int)(n + 1), s));
+        LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, tail_len.p, tail_ptr.p, (int)(n + 1), s));
         // head rows and category rows in the head / tail element format
         auto ht_sell = [&](const DevFamily &src, const DevBuf<int32_t> &lens, const int32_t *limit, DevBuf<uint32_t> &sell,
                            DevBuf<int64_t> &off, DevBuf<int32_t> &w, int64_t &elements) -> int32_t {
@@ -886,7 +853,7 @@ int32_t knn_build_device(int64_t n, const int64_t *ids, const int64_t *p_ptr, co
             LOCREC_TRY(off.alloc((size_t)ix->nslices + 1));
             LOCREC_HIP_TRY(hipMemsetAsync(w64.p, 0, ((size_t)ix->nslices + 1) * 8, s));
             hipLaunchKernelGGL(kb_slice_width, grid_for(ix->nslices), dim3(256), 0, s, n, ix->nslices, lens.p, 1, w.p, w64.p);
-            KB_PRIM(tmp, s, prim::exclusive_sum(p_, bytes_, w64.p, off.p, ix->nslices + 1, s));
+            LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, w64.p, off.p, ix->nslices + 1, s));
             LOCREC_HIP_TRY(hipMemcpyAsync(&elements, off.p + ix->nslices, 8, hipMemcpyDeviceToHost, s));
             LOCREC_HIP_TRY(hipStreamSynchronize(s));
             const size_t padded = (size_t)elements + (size_t)cfg::kHtNP * 256;  // knn_scan_ht always loads kHtNP groups
@@ -916,7 +883,7 @@ int32_t knn_build_device(int64_t n, const int64_t *ids, const int64_t *p_ptr, co
                 LOCREC_TRY(cnt.alloc((size_t)ntail + 1));
                 LOCREC_HIP_TRY(hipMemsetAsync(cnt.p, 0, ((size_t)ntail + 1) * 8, s));
                 if (ntail > 0) hipLaunchKernelGGL(kb_tail_freq, grid_for(ntail), dim3(256), 0, s, ntail, freq_new.p, ht_h, cnt.p);
-                KB_PRIM(tmp, s, prim::exclusive_sum(p_, bytes_, cnt.p, ht.post_ptr.p, (int)(ntail + 1), s));
+                LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, cnt.p, ht.post_ptr.p, (int)(ntail + 1), s));
                 LOCREC_HIP_TRY(hipStreamSynchronize(s));
             }
             if (nt_el > 0) {
@@ -928,8 +895,8 @@ int32_t knn_build_device(int64_t n, const int64_t *ids, const int64_t *p_ptr, co
                 LOCREC_TRY(v2.alloc((size_t)nt_el));
                 hipLaunchKernelGGL(kb_tail_keys, grid_for(n), dim3(256), 0, s, n, ix->fp.csr_ptr.p, ix->fp.csr_idx.p, ix->fp.csr_val.p,
                                    nhead.p, tail_ptr.p, ht_h, k1.p, v1.p, skip);
-                KB_PRIM(tmp, s, prim::sort_pairs(p_, bytes_, k1.p, k2.p, v1.p, v2.p, (int)nt_el, 0,
-                                                                  32 + std::max(1, ceil_log2_64(std::max<int64_t>(2, ntail))), s));
+                LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, k1.p, k2.p, v1.p, v2.p, (int)nt_el, 0,
+                                                                   32 + std::max(1, ceil_log2_64(std::max<int64_t>(2, ntail))), s));
                 hipLaunchKernelGGL(kb_postings, grid_for(nt_el), dim3(256), 0, s, nt_el, k2.p, v2.p, ht.post.p);
                 LOCREC_HIP_TRY(hipStreamSynchronize(s));
             }
@@ -958,7 +925,7 @@ int32_t knn_build_device(int64_t n, const int64_t *ids, const int64_t *p_ptr, co
         const int64_t ne = r_ptr ? re : pe;
         const size_t nee = (size_t)std::max<int64_t>(1, ne);
         LOCREC_TRY(ix->r_ptr.alloc(nn + 1));
-        KB_PRIM(tmp, s, prim::exclusive_sum(p_, bytes_, len_r.p, ix->r_ptr.p, (int)(n + 1), s));
+        LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, len_r.p, ix->r_ptr.p, (int)(n + 1), s));
         LOCREC_TRY(ix->r_place.alloc(nee));
         LOCREC_TRY(ix->r_rating.alloc(nee));
         if (n > 0 && ne > 0) {
@@ -985,7 +952,7 @@ int32_t knn_build_device(int64_t n, const int64_t *ids, const int64_t *p_ptr, co
             LOCREC_TRY(mxb.alloc(1));
             mx = mxb.p;
             if (n > 0) {
-                KB_PRIM(tmp, s, prim::reduce(p_, bytes_, len_r.p, mx, (int)n, MaxI64(), (int64_t)0, s));
+                LOCREC_PRIM(tmp, prim::reduce(p_, bytes_, len_r.p, mx, (int)n, MaxI64(), (int64_t)0, s));
                 LOCREC_HIP_TRY(hipMemcpyAsync(&ix->max_r_nnz, mx, 8, hipMemcpyDeviceToHost, s));
                 LOCREC_HIP_TRY(hipStreamSynchronize(s));
             }
@@ -999,14 +966,14 @@ int32_t knn_build_device(int64_t n, const int64_t *ids, const int64_t *p_ptr, co
         LOCREC_TRY(nuniq.alloc(1));
         int64_t ncp = 0;
         if (ne > 0) {
-            hipLaunchKernelGGL(kb_place_sortkeys, grid_for(ne), dim3(256), 0, s, ne, ix->r_place.p, pk.p);
-            KB_PRIM(tmp, s, prim::sort_keys(p_, bytes_, pk.p, pk2.p, (int)ne, 0, 64, s));
-            KB_PRIM(tmp, s, prim::unique(p_, bytes_, pk2.p, uk.p, nuniq.p, (int)ne, s));
+            hipLaunchKernelGGL(iota_keys, grid_for(ne), dim3(256), 0, s, ne, ix->r_place.p, pk.p, (uint32_t *)nullptr);
+            LOCREC_PRIM(tmp, prim::sort_keys(p_, bytes_, pk.p, pk2.p, (int)ne, 0, 64, s));
+            LOCREC_PRIM(tmp, prim::unique(p_, bytes_, pk2.p, uk.p, nuniq.p, (int)ne, s));
             LOCREC_HIP_TRY(hipMemcpyAsync(&ncp, nuniq.p, 8, hipMemcpyDeviceToHost, s));
             LOCREC_HIP_TRY(hipStreamSynchronize(s));
         }
         LOCREC_TRY(ix->cplace_dev.alloc((size_t)std::max<int64_t>(1, ncp)));
-        if (ncp > 0) hipLaunchKernelGGL(kb_unbias, grid_for(ncp), dim3(256), 0, s, ncp, uk.p, ix->cplace_dev.p);
+        if (ncp > 0) hipLaunchKernelGGL(unkey_ids, grid_for(ncp), dim3(256), 0, s, ncp, uk.p, ix->cplace_dev.p);
         ix->cplace_ids.resize((size_t)ncp);
         if (ncp > 0) LOCREC_HIP_TRY(hipMemcpyAsync(ix->cplace_ids.data(), ix->cplace_dev.p, (size_t)ncp * 8, hipMemcpyDeviceToHost, s));
         // place index of every rating row, and the transpose (rows ascending inside a place: a fixed order)
@@ -1020,7 +987,7 @@ int32_t knn_build_device(int64_t n, const int64_t *ids, const int64_t *p_ptr, co
             LOCREC_TRY(tv2.alloc(nee));
             hipLaunchKernelGGL(kb_place_index, grid_for(n), dim3(256), 0, s, n, ix->r_ptr.p, ix->r_place.p, ix->cplace_dev.p, ncp,
                                ix->r_pidx.p, pk.p, tv.p);
-            KB_PRIM(tmp, s, prim::sort_pairs(p_, bytes_, pk.p, pk2.p, tv.p, tv2.p, (int)ne, 0, 64, s));
+            LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, pk.p, pk2.p, tv.p, tv2.p, (int)ne, 0, 64, s));
             hipLaunchKernelGGL(kb_transpose_out, grid_for(ne), dim3(256), 0, s, ne, pk2.p, tv2.p, ix->r_rating.p, ix->cp_row.p,
                                ix->cp_rating.p);
             hipLaunchKernelGGL(kb_cp_ptr, grid_for(ncp + 1), dim3(256), 0, s, ncp, ne, pk2.p, ix->cp_ptr.p);

@@ -32,12 +32,6 @@ using namespace locrec;
 
 // ---- sort rows by (person, entity), stable in the input order ------------------------------------
 
-__global__ void pr_gather_keys(int64_t n, const int64_t *col, const uint32_t *rows, uint64_t *keys)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) keys[i] = ordered_key(col[rows[i]]);
-}
-
 struct SortedRows {
     DevBuf<uint64_t> k0, k1;
     DevBuf<uint32_t> r0, r1;
@@ -51,10 +45,10 @@ int32_t sort_person_entity(int64_t n, const int64_t *person, const int64_t *enti
     LOCREC_TRY(S.k1.alloc((size_t)n));
     LOCREC_TRY(S.r0.alloc((size_t)n));
     LOCREC_TRY(S.r1.alloc((size_t)n));
-    hipLaunchKernelGGL(pr_iota_keys, grid_for(n), dim3(256), 0, s, n, entity, S.k0.p, S.r0.p);
-    PR_PRIM(tmp, prim::sort_pairs(p_, bytes_, S.k0.p, S.k1.p, S.r0.p, S.r1.p, (int)n, 0, 64, s));
-    hipLaunchKernelGGL(pr_gather_keys, grid_for(n), dim3(256), 0, s, n, person, S.r1.p, S.k0.p);
-    PR_PRIM(tmp, prim::sort_pairs(p_, bytes_, S.k0.p, S.k1.p, S.r1.p, S.r0.p, (int)n, 0, 64, s));
+    hipLaunchKernelGGL(iota_keys, grid_for(n), dim3(256), 0, s, n, entity, S.k0.p, S.r0.p);
+    LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, S.k0.p, S.k1.p, S.r0.p, S.r1.p, (int)n, 0, 64, s));
+    hipLaunchKernelGGL(gather_id_keys, grid_for(n), dim3(256), 0, s, n, person, S.r1.p, S.k0.p);
+    LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, S.k0.p, S.k1.p, S.r1.p, S.r0.p, (int)n, 0, 64, s));
     S.rows = S.r0.p;
     return LOCREC_OK;
 }
@@ -172,22 +166,22 @@ int32_t rank_keep(int64_t g, const uint32_t *srank, const uint64_t *cnt, int64_t
     const uint32_t *sorted = gid1.p;
     if (!wide_counts) {
         hipLaunchKernelGGL(pr_rank_keys, grid_for(g), dim3(256), 0, s, g, srank, cnt, key0.p, gid0.p);
-        PR_PRIM(tmp, prim::sort_pairs(p_, bytes_, key0.p, key1.p, gid0.p, gid1.p, (int)g, 0, 64, s));
+        LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, key0.p, key1.p, gid0.p, gid1.p, (int)g, 0, 64, s));
     } else {  // stable LSD: by count descending, then by source (pmark / rmark serve as the 32-bit key buffers)
         hipLaunchKernelGGL(pr_rank_keys_wide, grid_for(g), dim3(256), 0, s, g, cnt, key0.p, gid0.p);
-        PR_PRIM(tmp, prim::sort_pairs(p_, bytes_, key0.p, key1.p, gid0.p, gid1.p, (int)g, 0, 64, s));
+        LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, key0.p, key1.p, gid0.p, gid1.p, (int)g, 0, 64, s));
         hipLaunchKernelGGL(pr_rank_source_keys, grid_for(g), dim3(256), 0, s, g, srank, gid1.p, pmark.p);
-        PR_PRIM(tmp, prim::sort_pairs(p_, bytes_, pmark.p, rmark.p, gid1.p, gid0.p, (int)g, 0, 32, s));
+        LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, pmark.p, rmark.p, gid1.p, gid0.p, (int)g, 0, 32, s));
         sorted = gid0.p;
     }
     if (!wide_counts)
         hipLaunchKernelGGL(pr_run_marks_packed, grid_for(g), dim3(256), 0, s, g, key1.p, pmark.p, rmark.p);
     else
         hipLaunchKernelGGL(pr_run_marks, grid_for(g), dim3(256), 0, s, g, sorted, srank, cnt, pmark.p, rmark.p);
-    PR_PRIM(tmp, prim::inclusive_max(p_, bytes_, pmark.p, pstart.p, (int)g, s));
-    PR_PRIM(tmp, prim::inclusive_max(p_, bytes_, rmark.p, rstart.p, (int)g, s));
+    LOCREC_PRIM(tmp, prim::inclusive_max(p_, bytes_, pmark.p, pstart.p, (int)g, s));
+    LOCREC_PRIM(tmp, prim::inclusive_max(p_, bytes_, rmark.p, rstart.p, (int)g, s));
     hipLaunchKernelGGL(pr_keep_top, grid_for(g), dim3(256), 0, s, g, pstart.p, rstart.p, sorted, top_n, keep);
-    PR_PRIM(tmp, prim::exclusive_sum(p_, bytes_, keep, pos, (int)g, s));
+    LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, keep, pos, (int)g, s));
     uint32_t last_pos = 0, last_keep = 0;
     LOCREC_HIP_TRY(hipMemcpyAsync(&last_pos, pos + (g - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     LOCREC_HIP_TRY(hipMemcpyAsync(&last_keep, keep + (g - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -213,7 +207,7 @@ int32_t kept_totals(int64_t g, const uint32_t *srank, const uint64_t *cnt, const
     LOCREC_TRY(nsources.alloc(1));
     LOCREC_TRY(totals.alloc((size_t)g));
     hipLaunchKernelGGL(pr_kept_counts, grid_for(g), dim3(256), 0, s, g, keep, cnt, kept.p);
-    PR_PRIM(tmp, prim::sum_by_key(p_, bytes_, srank, kept.p, (size_t)g, sources.p, totals.p, nsources.p, s));
+    LOCREC_PRIM(tmp, prim::sum_by_key(p_, bytes_, srank, kept.p, (size_t)g, sources.p, totals.p, nsources.p, s));
     LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (kept / sources are released on return)
     return LOCREC_OK;
 }
@@ -249,9 +243,9 @@ int32_t calc_ratings(int64_t n, const int64_t *person, const int64_t *entity, in
     LOCREC_TRY(gstart.alloc((size_t)n));
     LOCREC_TRY(ng_dev.alloc(1));
     hipLaunchKernelGGL(pr_group_flags, grid_for(n), dim3(256), 0, s, n, person, entity, S.rows, gfirst.p, pfirst.p);
-    PR_PRIM(tmp, prim::inclusive_sum(p_, bytes_, pfirst.p, prank.p, (int)n, s));
+    LOCREC_PRIM(tmp, prim::inclusive_sum(p_, bytes_, pfirst.p, prank.p, (int)n, s));
     prim::counting_iterator<uint32_t> iota(0u);
-    PR_PRIM(tmp, prim::select_flagged(p_, bytes_, iota, gfirst.p, gstart.p, ng_dev.p, (int)n, s));
+    LOCREC_PRIM(tmp, prim::select_flagged(p_, bytes_, iota, gfirst.p, gstart.p, ng_dev.p, (int)n, s));
     uint32_t g32 = 0;
     LOCREC_HIP_TRY(hipMemcpyAsync(&g32, ng_dev.p, sizeof g32, hipMemcpyDeviceToHost, s));
     LOCREC_HIP_TRY(hipStreamSynchronize(s));
@@ -339,7 +333,7 @@ int32_t calc_rating_vectors(int64_t n, const int64_t *person, const int64_t *ent
     RangeOut got;
     LOCREC_HIP_TRY(hipMemcpyAsync(&got, range.p, sizeof got, hipMemcpyDeviceToHost, s));
     LOCREC_HIP_TRY(hipStreamSynchronize(s));
-    const int64_t max_id = (int64_t)(got.max_key ^ 0x8000000000000000ull), min_id = (int64_t)(got.min_key ^ 0x8000000000000000ull);
+    const int64_t max_id = id_of_key(got.max_key), min_id = id_of_key(got.min_key);
     // checkedCast (RatingVectorsBuilder.scala:36-41): of max(id) first (:27-34), then of every id (:69)
     if (max_id > std::numeric_limits<int32_t>::max() || max_id < std::numeric_limits<int32_t>::min())
         return fail(LOCREC_E_ARITHMETIC, "Index out of Int range: %lld", (long long)max_id);
@@ -358,8 +352,8 @@ int32_t calc_rating_vectors(int64_t n, const int64_t *person, const int64_t *ent
     LOCREC_TRY(prank.alloc((size_t)n));
     LOCREC_TRY(pos.alloc((size_t)n));
     hipLaunchKernelGGL(pr_vector_flags, grid_for(n), dim3(256), 0, s, n, person, entity, S.rows, pfirst.p, keep.p);
-    PR_PRIM(tmp, prim::inclusive_sum(p_, bytes_, pfirst.p, prank.p, (int)n, s));
-    PR_PRIM(tmp, prim::exclusive_sum(p_, bytes_, keep.p, pos.p, (int)n, s));
+    LOCREC_PRIM(tmp, prim::inclusive_sum(p_, bytes_, pfirst.p, prank.p, (int)n, s));
+    LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, keep.p, pos.p, (int)n, s));
     hipLaunchKernelGGL(pr_emit_vectors, grid_for(n), dim3(256), 0, s, n, S.rows, pfirst.p, keep.p, prank.p, pos.p, person,
                        entity, rating, out_ids, out_rowptr, out_idx, out_val);
     uint32_t tail[3] = {0, 0, 0};
@@ -388,36 +382,9 @@ __global__ void pr_balance(int64_t n, const int64_t *src, const int64_t *dst, co
 
 // ---- calcPlaceVisits -----------------------------------------------------------------------------
 
-struct JoinError {
-    unsigned long long first_bad_visit, first_bad_place;  // ~0 = none
-};
-
-// a visit that passes the time filter and whose region has places takes part in the join: mark its region,
-// and its Location must be valid (the reference's UDF constructs it for every joined pair)
-__global__ void pr_check_visits(int64_t nv, const int64_t *ts, const double *lat, const double *lon, const int64_t *region,
-                                int64_t visits_from, const int64_t *regions, int32_t nr, uint32_t *region_visited,
-                                JoinError *err)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nv || ts[i] < visits_from) return;
-    const int64_t r = rank_of_region(regions, nr, region[i]);
-    if (r < 0) return;
-    region_visited[r] = 1u;
-    if (!location_ok(lat[i], lon[i])) atomicMin(&err->first_bad_visit, (unsigned long long)i);
-}
-
-__global__ void pr_check_places(int64_t np, const double *lat, const double *lon, const int64_t *region, const int64_t *regions,
-                                int32_t nr, const uint32_t *region_visited, JoinError *err)
-{
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= np) return;
-    const int64_t r = rank_of_region(regions, nr, region[j]);
-    if (r >= 0 && region_visited[r] && !location_ok(lat[j], lon[j])) atomicMin(&err->first_bad_place, (unsigned long long)j);
-}
-
 // One thread per visit: the places of the (at most) 3 bands x 3 cells around it, exact distance each.
 // WRITE = false counts the matches; WRITE = true stores the place rows at the visit's offset (ascending
-// place row: the candidates of a visit are few, an insertion sort orders them) and fills the columns.
+// place row) and fills the columns.
 // The matches arrive in scan order (band, then cell), so a visit that the capacity cuts stores ALL of
 // them, sorts, and only then writes the first `cap - base`: the rows written are the prefix of the
 // full result.  scratch_rows has room to the end of that one visit (pr_cut_end).
@@ -437,26 +404,12 @@ __global__ void pr_join(int64_t nv, const int64_t *v_person, const int64_t *v_ts
         const int64_t r = rank_of_region(regions, nr, v_region[i]);  // join(places, "region_id") (:31)
         const double lat = v_lat[i], lon = v_lon[i];
         if (r >= 0 && location_ok(lat, lon)) {
-            const int32_t bv = band_of(g, lat);
-            for (int32_t b = max(bv - 1, 0); b <= min(bv + 1, g.nbands - 1); ++b) {
-                double win;
-                int32_t nx;
-                band_cells(g, b, &win, &nx);
-                const double w = 360.0 / nx;
-                const int64_t c_lo = (int64_t)floor((lon - win + 180.0) / w), c_hi = (int64_t)floor((lon + win + 180.0) / w);
-                const int64_t ncell = min(c_hi - c_lo + 1, (int64_t)nx);
-                for (int64_t t = 0; t < ncell; ++t) {
-                    const int64_t cx = ((c_lo + t) % nx + nx) % nx;  // cells wrap around the antimeridian
-                    const uint64_t key = ((uint64_t)r << (2 * kCellBits)) | ((uint64_t)b << kCellBits) | (uint64_t)cx;
-                    for (int64_t at = lower_bound_key(keys, np, key); at < np && keys[at] == key; ++at) {
-                        const uint32_t j = place_rows[at];
-                        if (distance_meters(lat, lon, p_lat[j], p_lon[j]) <= max_meters) {  // (:15-21,127)
-                            if (WRITE && base < (unsigned long long)cap) scratch_rows[base + found] = j;
-                            ++found;
-                        }
-                    }
+            for_each_grid_candidate(g, r, lat, lon, keys, np, place_rows, [&](uint32_t j) {
+                if (distance_meters(lat, lon, p_lat[j], p_lon[j]) <= max_meters) {  // (:15-21,127)
+                    if (WRITE && base < (unsigned long long)cap) scratch_rows[base + found] = j;
+                    ++found;
                 }
-            }
+            });
         }
     }
     if (!WRITE) {
@@ -467,12 +420,7 @@ __global__ void pr_join(int64_t nv, const int64_t *v_person, const int64_t *v_ts
     const unsigned long long m = min(found, room);
     const unsigned long long stored = room ? found : 0ull;
     uint32_t *mine = scratch_rows + base;
-    for (unsigned long long a = 1; a < stored; ++a) {
-        const uint32_t v = mine[a];
-        unsigned long long b = a;
-        for (; b > 0 && mine[b - 1] > v; --b) mine[b] = mine[b - 1];
-        mine[b] = v;
-    }
+    sort_ascending(mine, stored);
     for (unsigned long long a = 0; a < m; ++a) {  // select(person_id, timestamp, id as place_id, region_id, category_id) (:40-46)
         const uint32_t j = mine[a];
         out_person[base + a] = v_person[i];
@@ -657,63 +605,38 @@ try {
     LOCREC_TRY(pc.bind(p_category_ids, n_places, mem, s));
 
     // distinct place regions, ascending
-    DevBuf<uint64_t> k0, k1;
-    DevBuf<uint32_t> r0, r1;
     DevBuf<int64_t> regions;
-    DevBuf<int32_t> nr_dev;
-    LOCREC_TRY(k0.alloc((size_t)n_places));
-    LOCREC_TRY(k1.alloc((size_t)n_places));
-    LOCREC_TRY(r0.alloc((size_t)n_places));
-    LOCREC_TRY(r1.alloc((size_t)n_places));
-    LOCREC_TRY(regions.alloc((size_t)n_places));
-    LOCREC_TRY(nr_dev.alloc(1));
-    hipLaunchKernelGGL(pr_iota_keys, grid_for(n_places), dim3(256), 0, s, n_places, pr.p, k0.p, r0.p);
-    PR_PRIM(tmp, prim::sort_keys(p_, bytes_, k0.p, k1.p, (int)n_places, 0, 64, s));
-    PR_PRIM(tmp, prim::unique(p_, bytes_, k1.p, k0.p, nr_dev.p, (int)n_places, s));
     int32_t nr = 0;
-    LOCREC_HIP_TRY(hipMemcpyAsync(&nr, nr_dev.p, sizeof nr, hipMemcpyDeviceToHost, s));
-    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    LOCREC_TRY(distinct_ids(pr.p, n_places, tmp, s, regions, &nr));
     if (nr >= (1 << 24)) return fail(LOCREC_E_INVALID_ARG, "%d distinct regions: at most 2^24 - 1 are supported", nr);
-    {   // ordered_key() back to the signed ids (x ^ sign bit is its own inverse and keeps the order)
-        std::vector<uint64_t> hk((size_t)nr);
-        LOCREC_HIP_TRY(hipMemcpy(hk.data(), k0.p, (size_t)nr * 8, hipMemcpyDeviceToHost));
-        std::vector<int64_t> hr((size_t)nr);
-        for (int32_t i = 0; i < nr; ++i) hr[(size_t)i] = (int64_t)(hk[(size_t)i] ^ 0x8000000000000000ull);
-        LOCREC_HIP_TRY(hipMemcpy(regions.p, hr.data(), (size_t)nr * 8, hipMemcpyHostToDevice));
-    }
 
     const Grid g = make_grid(max_meters);
 
     DevBuf<uint32_t> visited;
-    DevBuf<JoinError> err;
+    DevBuf<LocationError> err;
     LOCREC_TRY(visited.alloc((size_t)nr));
     LOCREC_TRY(err.alloc(1));
     LOCREC_HIP_TRY(hipMemsetAsync(visited.p, 0, (size_t)nr * 4, s));
-    LOCREC_HIP_TRY(hipMemsetAsync(err.p, 0xFF, sizeof(JoinError), s));
-    hipLaunchKernelGGL(pr_check_visits, grid_for(n_visits), dim3(256), 0, s, n_visits, vt.p, vlat.p, vlon.p, vr.p, visits_from,
+    LOCREC_HIP_TRY(hipMemsetAsync(err.p, 0xFF, sizeof(LocationError), s));
+    hipLaunchKernelGGL(check_side_a, grid_for(n_visits), dim3(256), 0, s, n_visits, vt.p, visits_from, vlat.p, vlon.p, vr.p,
                        regions.p, nr, visited.p, err.p);
-    hipLaunchKernelGGL(pr_check_places, grid_for(n_places), dim3(256), 0, s, n_places, plat.p, plon.p, pr.p, regions.p, nr,
+    hipLaunchKernelGGL(check_side_b, grid_for(n_places), dim3(256), 0, s, n_places, plat.p, plon.p, pr.p, regions.p, nr,
                        visited.p, err.p);
-    JoinError je;
-    LOCREC_HIP_TRY(hipMemcpyAsync(&je, err.p, sizeof je, hipMemcpyDeviceToHost, s));
+    LOCREC_HIP_TRY(hipGetLastError());
+    LocationError le;
+    LOCREC_HIP_TRY(hipMemcpyAsync(&le, err.p, sizeof le, hipMemcpyDeviceToHost, s));
     LOCREC_HIP_TRY(hipStreamSynchronize(s));
-    if (je.first_bad_visit != ~0ull || je.first_bad_place != ~0ull) {
-        const bool visit = je.first_bad_visit != ~0ull;
-        const int64_t row = (int64_t)(visit ? je.first_bad_visit : je.first_bad_place);
-        double lat = 0, lon = 0;
-        LOCREC_HIP_TRY(hipMemcpy(&lat, (visit ? vlat.p : plat.p) + row, 8, hipMemcpyDeviceToHost));
-        LOCREC_HIP_TRY(hipMemcpy(&lon, (visit ? vlon.p : plon.p) + row, 8, hipMemcpyDeviceToHost));
-        *inout_count = visit ? -(1 + row) : -(1 + n_visits + row);
-        if (!(lat >= -90.0 && lat <= 90.0))  // the reference's messages (Location.scala:7-8)
-            return fail(LOCREC_E_INVALID_ARG, "requirement failed: Latitude %.17g must be within range [-90.0, 90.0] (%s %lld)", lat,
-                        visit ? "location visit" : "place", (long long)row);
-        return fail(LOCREC_E_INVALID_ARG, "requirement failed: Longitude %.17g must be within range [-180.0, 180.0] (%s %lld)", lon,
-                    visit ? "location visit" : "place", (long long)row);
-    }
+    LOCREC_TRY(location_error(le, vlat.p, vlon.p, "location visit", n_visits, plat.p, plon.p, "place", inout_count));
 
+    DevBuf<uint64_t> k0, k1;
+    DevBuf<uint32_t> r0, r1;
+    LOCREC_TRY(k0.alloc((size_t)n_places));
+    LOCREC_TRY(k1.alloc((size_t)n_places));
+    LOCREC_TRY(r0.alloc((size_t)n_places));
+    LOCREC_TRY(r1.alloc((size_t)n_places));
     hipLaunchKernelGGL(pr_place_keys, grid_for(n_places), dim3(256), 0, s, n_places, plat.p, plon.p, pr.p, regions.p, nr, g, k0.p,
                        r0.p);
-    PR_PRIM(tmp, prim::sort_pairs(p_, bytes_, k0.p, k1.p, r0.p, r1.p, (int)n_places, 0, 64, s));
+    LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, k0.p, k1.p, r0.p, r1.p, (int)n_places, 0, 64, s));
 
     DevBuf<unsigned long long> counts, offsets;
     LOCREC_TRY(counts.alloc((size_t)n_visits));
@@ -721,7 +644,7 @@ try {
     hipLaunchKernelGGL((pr_join<false>), grid_for(n_visits), dim3(256), 0, s, n_visits, vp.p, vt.p, vlat.p, vlon.p, vr.p,
                        visits_from, regions.p, nr, g, max_meters, n_places, k1.p, r1.p, pi.p, plat.p, plon.p, pc.p, counts.p,
                        nullptr, (int64_t)0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-    PR_PRIM(tmp, prim::exclusive_sum(p_, bytes_, counts.p, offsets.p, (int)n_visits, s));
+    LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, counts.p, offsets.p, (int)n_visits, s));
     unsigned long long last_off = 0, last_cnt = 0;
     LOCREC_HIP_TRY(hipMemcpyAsync(&last_off, offsets.p + (n_visits - 1), 8, hipMemcpyDeviceToHost, s));
     LOCREC_HIP_TRY(hipMemcpyAsync(&last_cnt, counts.p + (n_visits - 1), 8, hipMemcpyDeviceToHost, s));
@@ -815,18 +738,8 @@ __global__ void pr_rank_flags(int64_t n, const int64_t *ids, const uint64_t *all
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint64_t k = ordered_key(ids[i]);
-    int32_t lo = 0, hi = nallowed;
-    while (lo < hi) {
-        const int32_t mid = (lo + hi) >> 1;
-        if (allowed[mid] < k) lo = mid + 1; else hi = mid;
-    }
+    const int64_t lo = lower_bound_key(allowed, nallowed, k);
     keep[i] = lo < nallowed && allowed[lo] == k ? 1 : 0;
-}
-
-__global__ void pr_rank_keys_by_id(int64_t m, const uint32_t *rows, const int64_t *ids, uint64_t *keys)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < m) keys[i] = ordered_key(ids[rows[i]]);
 }
 
 __global__ void pr_rank_keys_by_score(int64_t m, const uint32_t *rows, const double *scores, uint64_t *keys)
@@ -876,13 +789,13 @@ try {
     LOCREC_TRY(cnt_dev.alloc(1));
     hipLaunchKernelGGL(pr_region_place_keys, grid_for(n_places), dim3(256), 0, s, n_places, pid.p, preg.p, target_region_id, a0.p,
                        in_region.p);
-    PR_PRIM(tmp, prim::select_flagged(p_, bytes_, a0.p, in_region.p, a1.p, cnt_dev.p, (int)n_places, s));
+    LOCREC_PRIM(tmp, prim::select_flagged(p_, bytes_, a0.p, in_region.p, a1.p, cnt_dev.p, (int)n_places, s));
     int32_t nallowed = 0;
     LOCREC_HIP_TRY(hipMemcpyAsync(&nallowed, cnt_dev.p, sizeof nallowed, hipMemcpyDeviceToHost, s));
     LOCREC_HIP_TRY(hipStreamSynchronize(s));
     if (nallowed > 0) {
-        PR_PRIM(tmp, prim::sort_keys(p_, bytes_, a1.p, a0.p, nallowed, 0, 64, s));
-        PR_PRIM(tmp, prim::unique(p_, bytes_, a0.p, a1.p, cnt_dev.p, nallowed, s));
+        LOCREC_PRIM(tmp, prim::sort_keys(p_, bytes_, a1.p, a0.p, nallowed, 0, 64, s));
+        LOCREC_PRIM(tmp, prim::unique(p_, bytes_, a0.p, a1.p, cnt_dev.p, nallowed, s));
         LOCREC_HIP_TRY(hipMemcpyAsync(&nallowed, cnt_dev.p, sizeof nallowed, hipMemcpyDeviceToHost, s));
         LOCREC_HIP_TRY(hipStreamSynchronize(s));
         std::swap(a0.p, a1.p);  // a0 = the distinct sorted keys
@@ -898,7 +811,7 @@ try {
     LOCREC_TRY(r1.alloc((size_t)n));
     hipLaunchKernelGGL(pr_rank_flags, grid_for(n), dim3(256), 0, s, n, rid.p, a0.p, nallowed, keep.p);
     prim::counting_iterator<uint32_t> iota(0u);
-    PR_PRIM(tmp, prim::select_flagged(p_, bytes_, iota, keep.p, r0.p, cnt_dev.p, (int)n, s));
+    LOCREC_PRIM(tmp, prim::select_flagged(p_, bytes_, iota, keep.p, r0.p, cnt_dev.p, (int)n, s));
     int32_t m = 0;
     LOCREC_HIP_TRY(hipMemcpyAsync(&m, cnt_dev.p, sizeof m, hipMemcpyDeviceToHost, s));
     LOCREC_HIP_TRY(hipStreamSynchronize(s));
@@ -906,10 +819,10 @@ try {
     // order by (score desc, id asc): stable LSD - by id, then by score
     LOCREC_TRY(k0.alloc((size_t)m));
     LOCREC_TRY(k1.alloc((size_t)m));
-    hipLaunchKernelGGL(pr_rank_keys_by_id, grid_for(m), dim3(256), 0, s, (int64_t)m, r0.p, rid.p, k0.p);
-    PR_PRIM(tmp, prim::sort_pairs(p_, bytes_, k0.p, k1.p, r0.p, r1.p, m, 0, 64, s));
+    hipLaunchKernelGGL(gather_id_keys, grid_for(m), dim3(256), 0, s, (int64_t)m, rid.p, r0.p, k0.p);
+    LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, k0.p, k1.p, r0.p, r1.p, m, 0, 64, s));
     hipLaunchKernelGGL(pr_rank_keys_by_score, grid_for(m), dim3(256), 0, s, (int64_t)m, r1.p, rsc.p, k0.p);
-    PR_PRIM(tmp, prim::sort_pairs(p_, bytes_, k0.p, k1.p, r1.p, r0.p, m, 0, 64, s));
+    LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, k0.p, k1.p, r1.p, r0.p, m, 0, 64, s));
     const int64_t w = std::min<int64_t>(m, limit);
     Out<int64_t> oid;
     Out<double> osc;
@@ -984,36 +897,6 @@ struct CovisitStats {
 thread_local CovisitStats g_covisit_stats;
 
 enum { kPhaseSort = 0, kPhaseEmit = 1, kPhaseMerge = 2, kPhaseEnd = -1 };
-
-// HIP events at the phase changes of one call; read() adds every interval to its phase
-struct PhaseClock {
-    hipStream_t s = nullptr;
-    std::vector<hipEvent_t> ev;
-    std::vector<int> phase;
-    ~PhaseClock()
-    {
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-    }
-    int32_t mark(int ph)
-    {
-        hipEvent_t e;
-        LOCREC_HIP_TRY(hipEventCreate(&e));
-        ev.push_back(e);
-        phase.push_back(ph);
-        LOCREC_HIP_TRY(hipEventRecord(e, s));
-        return LOCREC_OK;
-    }
-    int32_t read(double ms[3])
-    {
-        LOCREC_HIP_TRY(hipStreamSynchronize(s));
-        for (size_t i = 0; i + 1 < ev.size(); ++i) {
-            float t = 0;
-            LOCREC_HIP_TRY(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
-            if (phase[i] >= 0) ms[phase[i]] += t;
-        }
-        return LOCREC_OK;
-    }
-};
 
 // the rows in (person, timestamp) order: timestamp and dense place rank of sorted position i
 __global__ void pr_covisit_gather(int64_t n, const uint32_t *rows, const int64_t *place, const int64_t *ts, const uint64_t *uniq,
@@ -1135,8 +1018,8 @@ __global__ void pr_emit_similar(int64_t m, const uint32_t *keep, const uint32_t 
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= m || !keep[i] || (int64_t)pos[i] >= cap) return;
     const uint32_t at = pos[i];
-    out_source[at] = (int64_t)(uniq[keys[i] >> nb] ^ 0x8000000000000000ull);
-    out_target[at] = (int64_t)(uniq[keys[i] & ((1ull << nb) - 1)] ^ 0x8000000000000000ull);
+    out_source[at] = id_of_key(uniq[keys[i] >> nb]);
+    out_target[at] = id_of_key(uniq[keys[i] & ((1ull << nb) - 1)]);
     out_weight[at] = (double)cnt[i] / (double)totals[srank[i]];
 }
 
@@ -1153,20 +1036,17 @@ int32_t covisit_counts(int64_t n, const int64_t *person, const int64_t *place, c
     LOCREC_TRY(clock.mark(kPhaseSort));
     // distinct places, ascending: a place's rank is order-preserving, so rank order is id order
     DevBuf<uint64_t> pk;
-    DevBuf<uint32_t> scratch_rows;
     DevBuf<int32_t> np_dev;
     LOCREC_TRY(pk.alloc((size_t)n));
     LOCREC_TRY(uniq.alloc((size_t)n));
-    LOCREC_TRY(scratch_rows.alloc((size_t)n));
     LOCREC_TRY(np_dev.alloc(1));
-    hipLaunchKernelGGL(pr_iota_keys, grid_for(n), dim3(256), 0, s, n, place, uniq.p, scratch_rows.p);
-    PR_PRIM(tmp, prim::sort_keys(p_, bytes_, uniq.p, pk.p, (int)n, 0, 64, s));
-    PR_PRIM(tmp, prim::unique(p_, bytes_, pk.p, uniq.p, np_dev.p, (int)n, s));
+    hipLaunchKernelGGL(iota_keys, grid_for(n), dim3(256), 0, s, n, place, uniq.p, (uint32_t *)nullptr);
+    LOCREC_PRIM(tmp, prim::sort_keys(p_, bytes_, uniq.p, pk.p, (int)n, 0, 64, s));
+    LOCREC_PRIM(tmp, prim::unique(p_, bytes_, pk.p, uniq.p, np_dev.p, (int)n, s));
     int32_t np = 0;
     LOCREC_HIP_TRY(hipMemcpyAsync(&np, np_dev.p, sizeof np, hipMemcpyDeviceToHost, s));
     LOCREC_HIP_TRY(hipStreamSynchronize(s));
     pk.release();
-    scratch_rows.release();
     if (np < 2) return LOCREC_OK;  // one place: every pair is a same-place pair
     int nb = 1;
     while (((int64_t)1 << nb) < np) ++nb;
@@ -1187,8 +1067,8 @@ int32_t covisit_counts(int64_t n, const int64_t *person, const int64_t *place, c
     LOCREC_TRY(clock.mark(kPhaseEmit));
     LOCREC_HIP_TRY(hipMemsetAsync(width.p + n, 0, sizeof(unsigned long long), s));
     hipLaunchKernelGGL(pr_covisit_windows, grid_for(n), dim3(256), 0, s, n, S.k1.p, sts.p, interval, lo.p, width.p);
-    PR_PRIM(tmp, prim::exclusive_sum(p_, bytes_, width.p, off.p, (size_t)n + 1, s));  // off[n] = all candidate pairs
-    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, width.p, off.p, (size_t)n + 1, s));  // off[n] = all candidate pairs
+        LOCREC_HIP_TRY(hipStreamSynchronize(s));
     S.k0.release();
     S.r0.release();
     S.r1.release();
@@ -1218,8 +1098,8 @@ int32_t covisit_counts(int64_t n, const int64_t *person, const int64_t *place, c
         hipLaunchKernelGGL(pr_covisit_emit, grid_for(npairs, kPairTile), dim3(256), 0, s, r0, r1, off.p, lo.p, srk.p, nb,
                            (unsigned long long)npairs, ka.p);
         LOCREC_TRY(clock.mark(kPhaseSort));
-        PR_PRIM(tmp, prim::sort_keys(p_, bytes_, ka.p, kb.p, (size_t)npairs, 0, (unsigned)(2 * nb), s));
-        PR_PRIM(tmp, prim::run_length_encode(p_, bytes_, kb.p, (size_t)npairs, ka.p, run_counts.p, nruns_dev.p, s));
+        LOCREC_PRIM(tmp, prim::sort_keys(p_, bytes_, ka.p, kb.p, (size_t)npairs, 0, (unsigned)(2 * nb), s));
+        LOCREC_PRIM(tmp, prim::run_length_encode(p_, bytes_, kb.p, (size_t)npairs, ka.p, run_counts.p, nruns_dev.p, s));
         uint32_t c32 = 0;
         LOCREC_HIP_TRY(hipMemcpyAsync(&c32, nruns_dev.p, sizeof c32, hipMemcpyDeviceToHost, s));
         LOCREC_HIP_TRY(hipStreamSynchronize(s));
@@ -1230,7 +1110,7 @@ int32_t covisit_counts(int64_t n, const int64_t *person, const int64_t *place, c
         LOCREC_TRY(flag.reserve((size_t)c));
         LOCREC_TRY(pos.reserve((size_t)c));
         hipLaunchKernelGGL(pr_pair_flags, grid_for(c), dim3(256), 0, s, c, ka.p, nb, flag.p);
-        PR_PRIM(tmp, prim::exclusive_sum(p_, bytes_, flag.p, pos.p, (size_t)c, s));
+        LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, flag.p, pos.p, (size_t)c, s));
         uint32_t last_pos = 0, last_flag = 0;
         LOCREC_HIP_TRY(hipMemcpyAsync(&last_pos, pos.p + (c - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         LOCREC_HIP_TRY(hipMemcpyAsync(&last_flag, flag.p + (c - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -1261,8 +1141,8 @@ int32_t covisit_counts(int64_t n, const int64_t *person, const int64_t *place, c
         DevBuf<uint64_t> sk, sc;
         LOCREC_TRY(sk.alloc((size_t)cat));
         LOCREC_TRY(sc.alloc((size_t)cat));
-        PR_PRIM(tmp, prim::sort_pairs(p_, bytes_, ck.p, sk.p, cc.p, sc.p, (size_t)cat, 0, (unsigned)(2 * nb), s));
-        PR_PRIM(tmp, prim::sum_by_key(p_, bytes_, sk.p, sc.p, (size_t)cat, ck.p, cc.p, nruns_dev.p, s));
+        LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, ck.p, sk.p, cc.p, sc.p, (size_t)cat, 0, (unsigned)(2 * nb), s));
+        LOCREC_PRIM(tmp, prim::sum_by_key(p_, bytes_, sk.p, sc.p, (size_t)cat, ck.p, cc.p, nruns_dev.p, s));
         LOCREC_HIP_TRY(hipMemcpyAsync(&c32, nruns_dev.p, sizeof c32, hipMemcpyDeviceToHost, s));
         LOCREC_HIP_TRY(hipStreamSynchronize(s));
         std::swap(R.keys.p, ck.p);
@@ -1317,7 +1197,7 @@ try {
         LOCREC_TRY(keep.alloc((size_t)m));
         LOCREC_TRY(pos.alloc((size_t)m));
         hipLaunchKernelGGL(pr_pair_source_steps, grid_for(m), dim3(256), 0, s, m, R.keys.p, nb, step.p);
-        PR_PRIM(tmp, prim::inclusive_sum(p_, bytes_, step.p, srank.p, (size_t)m, s));
+        LOCREC_PRIM(tmp, prim::inclusive_sum(p_, bytes_, step.p, srank.p, (size_t)m, s));
         LOCREC_TRY(rank_keep(m, srank.p, R.counts.p, top_n, true, keep.p, pos.p, &total, tmp, s));
         const int64_t rows = std::min(total, cap);
         if (rows > 0) {

@@ -73,12 +73,6 @@ bool rb_force_sort()
     return e && atoi(e) != 0;
 }
 
-__global__ void rb_gather_keys(int64_t n, const int64_t *col, const uint32_t *rows, uint64_t *keys)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) keys[i] = ordered_key(col[rows[i]]);
-}
-
 // offsets -> (begin, length) per segment; flag: a negative or decreasing offset, or one beyond n.  Reads the offsets
 // only, never through them.
 __global__ void rb_prepare(int64_t n_seg, const int64_t *offsets, int64_t n, int64_t *seg_begin, int64_t *seg_len,
@@ -227,7 +221,7 @@ __device__ __forceinline__ void rb_emit_row(const RbList &L, int w, int N, int64
 {
     for (int j = threadIdx.x; j < N; j += kRbThreads) {
         const int64_t o = s * (int64_t)N + j;
-        out_ids[o] = j < w ? (int64_t)(L.id[j] ^ 0x8000000000000000ull) : -1;
+        out_ids[o] = j < w ? id_of_key(L.id[j]) : -1;
         out_scores[o] = j < w ? scores[begin + L.row[j]] : 0.0;
     }
     if (threadIdx.x == 0) out_counts[s] = w;
@@ -488,11 +482,11 @@ int32_t rank_segments_device(int64_t n_seg, const int64_t *seg_begin, const int6
         k0 = table.p;
         k1 = k0 + n_places;
         uint32_t *r0 = reinterpret_cast<uint32_t *>(k1 + n_places), *r1 = r0 + 2 * np8;
-        hipLaunchKernelGGL(pr_iota_keys, grid_for(n_places), dim3(256), 0, s, n_places, place_ids, k0, r0);
-        PR_PRIM(tmp, prim::sort_pairs(p_, bytes_, k0, k1, r0, r1, (int)n_places, 0, 64, s));
-        hipLaunchKernelGGL(rb_gather_keys, grid_for(n_places), dim3(256), 0, s, n_places, place_region_ids, r1, k0);
-        PR_PRIM(tmp, prim::sort_pairs(p_, bytes_, k0, k1, r1, r0, (int)n_places, 0, 64, s));
-        hipLaunchKernelGGL(rb_gather_keys, grid_for(n_places), dim3(256), 0, s, n_places, place_ids, r0, k0);
+        hipLaunchKernelGGL(iota_keys, grid_for(n_places), dim3(256), 0, s, n_places, place_ids, k0, r0);
+        LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, k0, k1, r0, r1, (int)n_places, 0, 64, s));
+        hipLaunchKernelGGL(gather_id_keys, grid_for(n_places), dim3(256), 0, s, n_places, place_region_ids, r1, k0);
+        LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, k0, k1, r1, r0, (int)n_places, 0, 64, s));
+        hipLaunchKernelGGL(gather_id_keys, grid_for(n_places), dim3(256), 0, s, n_places, place_ids, r0, k0);
     }
     const uint64_t *table_regions = k1, *table_ids = k0;
     // the plan: every segment's range of the table and its chunks
@@ -519,7 +513,7 @@ int32_t rank_segments_device(int64_t n_seg, const int64_t *seg_begin, const int6
     if (h[1] >= (unsigned long long)kMaxRows - 1)
         return fail(LOCREC_E_INVALID_ARG, "%llu chunks: raise LOCREC_RANK_BATCH_CHUNK or split the batch", h[1]);
     const uint32_t items = (uint32_t)h[1];
-    PR_PRIM(tmp, prim::exclusive_sum(p_, bytes_, nch.p, first.p, (size_t)n_seg + 1, s));
+    LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, nch.p, first.p, (size_t)n_seg + 1, s));
     if (!global) {
         st.split = (int64_t)h[2];
         st.chunks = (int64_t)h[3];
@@ -535,7 +529,7 @@ int32_t rank_segments_device(int64_t n_seg, const int64_t *seg_begin, const int6
             int32_t *p = nullptr;
         } pcount;
         if (h[3] > 0) {
-            PR_PRIM(tmp, prim::exclusive_sum(p_, bytes_, split_nch.p, pfirst.p, (size_t)n_seg + 1, s));
+            LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, split_nch.p, pfirst.p, (size_t)n_seg + 1, s));
             const size_t pn = (size_t)h[3] * (size_t)N, pn8 = (pn + 1) / 2, pc8 = ((size_t)h[3] + 1) / 2;
             LOCREC_TRY(partial.alloc(2 * pn + pn8 + pc8));
             pk.p = partial.p;
@@ -564,7 +558,7 @@ int32_t rank_segments_device(int64_t n_seg, const int64_t *seg_begin, const int6
                        table_ids, ids, chunk, cnt.p, items);
     // (kept rows in all: a u32 sum; more than 2^31 - 1 are refused below, and 2^32 or more cannot come from segments that
     // the callers cut out of fewer than 2^31 rows)
-    PR_PRIM(tmp, prim::exclusive_sum(p_, bytes_, cnt.p, base.p, (size_t)items + 1, s));
+    LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, cnt.p, base.p, (size_t)items + 1, s));
     uint32_t m32 = 0;
     LOCREC_HIP_TRY(hipMemcpyAsync(&m32, base.p + items, sizeof m32, hipMemcpyDeviceToHost, s));
     LOCREC_HIP_TRY(hipStreamSynchronize(s));
@@ -586,11 +580,11 @@ int32_t rank_segments_device(int64_t n_seg, const int64_t *seg_begin, const int6
         hipLaunchKernelGGL(rb_scatter, dim3(items), dim3(kRbThreads), 0, s, n_seg, first.p, seg_begin, seg_len, lo.p, hi.p,
                            table_ids, ids, chunk, base.p, kseg.p, krow.p, q0.p, v0.p);
         // three stable passes: id, score key, segment
-        PR_PRIM(tmp, prim::sort_pairs(p_, bytes_, q0.p, q1.p, v0.p, v1.p, (int)m, 0, 64, s));
+        LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, q0.p, q1.p, v0.p, v1.p, (int)m, 0, 64, s));
         hipLaunchKernelGGL(rb_score_keys, grid_for(m), dim3(256), 0, s, m, v1.p, kseg.p, krow.p, seg_begin, scores, q0.p);
-        PR_PRIM(tmp, prim::sort_pairs(p_, bytes_, q0.p, q1.p, v1.p, v0.p, (int)m, 0, 64, s));
+        LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, q0.p, q1.p, v1.p, v0.p, (int)m, 0, 64, s));
         hipLaunchKernelGGL(rb_segment_keys, grid_for(m), dim3(256), 0, s, m, v0.p, kseg.p, s0.p);
-        PR_PRIM(tmp, prim::sort_pairs(p_, bytes_, s0.p, s1.p, v0.p, v1.p, (int)m, 0, 32, s));
+        LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, s0.p, s1.p, v0.p, v1.p, (int)m, 0, 32, s));
     }
     hipLaunchKernelGGL(rb_emit_sorted, dim3((unsigned)(n_seg * tiles)), dim3(kRbThreads), 0, s, tiles, N, m, s1.p, v1.p, krow.p,
                        seg_begin, ids, scores, out_ids, out_scores, out_counts);

@@ -31,14 +31,6 @@ constexpr int kRsTile = 2048;                    // output rows of one block of 
 constexpr int kRsMaxCols = 8;
 constexpr int64_t kRsMaxRegions = (int64_t)1 << 24;  // as locrec_calc_place_visits: at most 2^24 - 1 regions
 
-// ---- max(timestamp), distinct region ids ------------------------------------------------------------------------
-
-__global__ void rs_unkey(int64_t m, const uint64_t *keys, int64_t *out)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < m) out[i] = (int64_t)(keys[i] ^ 0x8000000000000000ull);  // ordered_key() is its own inverse
-}
-
 // ---- the partition ----------------------------------------------------------------------------------------------
 
 __global__ void rs_check_ascending(int64_t n, const int64_t *ids, uint32_t *invalid)
@@ -54,11 +46,7 @@ __global__ void rs_rank_rows(int64_t n, const int64_t *row_regions, int64_t n_re
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int64_t v = row_regions[i];
-    int64_t lo = 0, hi = n_regions;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (regions[mid] < v) lo = mid + 1; else hi = mid;
-    }
+    const int64_t lo = lower_bound<int64_t>(regions, 0, n_regions, v);
     rank[i] = (uint32_t)(lo < n_regions && regions[lo] == v ? lo : n_regions);
     rows[i] = (uint32_t)i;
 }
@@ -72,12 +60,7 @@ __global__ void rs_group_offsets(int64_t n, const uint32_t *sorted_rank, int64_t
         offsets[g] = n;
         return;
     }
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if ((int64_t)sorted_rank[mid] < g) lo = mid + 1; else hi = mid;
-    }
-    offsets[g] = lo;
+    offsets[g] = lower_bound<uint32_t>(sorted_rank, 0, n, (uint32_t)g);  // (g < n_groups <= 2^24)
 }
 
 // ---- one set's rows: check, then merge and gather ---------------------------------------------------------------
@@ -180,8 +163,8 @@ try {
     DevBuf<int64_t> out;
     LOCREC_TRY(ts.bind(timestamps, n, mem, s));
     LOCREC_TRY(out.alloc(1));
-    PR_PRIM(tmp, prim::reduce(p_, bytes_, ts.p, out.p, (size_t)n, rocprim::maximum<int64_t>(),
-                              std::numeric_limits<int64_t>::min(), s));
+    LOCREC_PRIM(tmp, prim::reduce(p_, bytes_, ts.p, out.p, (size_t)n, rocprim::maximum<int64_t>(),
+                                  std::numeric_limits<int64_t>::min(), s));
     LOCREC_HIP_TRY(hipMemcpyAsync(out_max, out.p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
     LOCREC_HIP_TRY(hipStreamSynchronize(s));
     return LOCREC_OK;
@@ -203,27 +186,15 @@ try {
     hipStream_t s = nullptr;
     Temp tmp;
     In<int64_t> r;
-    DevBuf<uint64_t> k0, k1;
-    DevBuf<uint32_t> rows;
-    DevBuf<int32_t> nr_dev;
-    LOCREC_TRY(r.bind(region_ids, n, mem, s));
-    LOCREC_TRY(k0.alloc((size_t)n));
-    LOCREC_TRY(k1.alloc((size_t)n));
-    LOCREC_TRY(rows.alloc((size_t)n));
-    LOCREC_TRY(nr_dev.alloc(1));
-    hipLaunchKernelGGL(pr_iota_keys, grid_for(n), dim3(256), 0, s, n, r.p, k0.p, rows.p);
-    PR_PRIM(tmp, prim::sort_keys(p_, bytes_, k0.p, k1.p, (size_t)n, 0, 64, s));
-    PR_PRIM(tmp, prim::unique(p_, bytes_, k1.p, k0.p, nr_dev.p, (size_t)n, s));
+    DevBuf<int64_t> ids;
     int32_t nr = 0;
-    LOCREC_HIP_TRY(hipMemcpyAsync(&nr, nr_dev.p, sizeof nr, hipMemcpyDeviceToHost, s));
-    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    LOCREC_TRY(r.bind(region_ids, n, mem, s));
+    LOCREC_TRY(distinct_ids(r.p, n, tmp, s, ids, &nr));
     *inout_count = nr;
     const int64_t m = std::min<int64_t>(nr, cap);
     if (m == 0) return LOCREC_OK;
-    Out<int64_t> out;
-    LOCREC_TRY(out.bind(out_ids, m, mem));
-    hipLaunchKernelGGL(rs_unkey, grid_for(m), dim3(256), 0, s, m, k0.p, out.p);
-    LOCREC_TRY(out.deliver(m, s));
+    const hipMemcpyKind to_caller = mem == LOCREC_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    LOCREC_HIP_TRY(hipMemcpyAsync(out_ids, ids.p, (size_t)m * sizeof(int64_t), to_caller, s));
     LOCREC_HIP_TRY(hipStreamSynchronize(s));
     return LOCREC_OK;
 }
@@ -277,8 +248,8 @@ try {
         LOCREC_HIP_TRY(hipMemcpyAsync(rows.p, rows0.p, (size_t)n_rows * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
     } else {
         LOCREC_TRY(rank1.alloc((size_t)n_rows));
-        PR_PRIM(tmp, prim::sort_pairs(p_, bytes_, rank0.p, rank1.p, rows0.p, reinterpret_cast<uint32_t *>(rows.p),
-                                      (size_t)n_rows, 0, bits, s));
+        LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, rank0.p, rank1.p, rows0.p, reinterpret_cast<uint32_t *>(rows.p),
+                                          (size_t)n_rows, 0, bits, s));
         sorted_rank = rank1.p;
     }
     hipLaunchKernelGGL(rs_group_offsets, grid_for(n_regions + 2), dim3(256), 0, s, n_rows, sorted_rank, n_regions + 1, offsets.p);

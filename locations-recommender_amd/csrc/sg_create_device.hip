@@ -12,14 +12,11 @@
 
 #include "sg_batch.hip"
 
+#include "offline.h"
+
 namespace {
 
 constexpr int kDbThreads = 256;
-
-inline dim3 db_grid(int64_t n) { return dim3((unsigned)std::max<int64_t>(1, (n + kDbThreads - 1) / kDbThreads)); }
-
-// signed id -> unsigned key of the same order
-__host__ __device__ inline unsigned long long db_key(int64_t id) { return (unsigned long long)id ^ 0x8000000000000000ull; }
 
 __device__ __forceinline__ unsigned long long db_min(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
 __device__ __forceinline__ unsigned long long db_max(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
@@ -62,7 +59,7 @@ __global__ __launch_bounds__(kDbThreads) void sg_db_minmax(int64_t ne, const int
     __shared__ unsigned long long slo[kDbThreads], shi[kDbThreads];
     unsigned long long lo = ~0ull, hi = 0ull;
     for (int64_t e = (int64_t)blockIdx.x * kDbThreads + threadIdx.x; e < ne; e += (int64_t)gridDim.x * kDbThreads) {
-        const unsigned long long a = db_key(src[e]), b = db_key(dst[e]);
+        const unsigned long long a = ordered_key(src[e]), b = ordered_key(dst[e]);
         lo = db_min(lo, db_min(a, b));
         hi = db_max(hi, db_max(a, b));
     }
@@ -119,23 +116,13 @@ __global__ __launch_bounds__(kDbThreads) void sg_db_interleave(int64_t ne, const
     ids[2 * e + 1] = dst[e];
 }
 
-__device__ __forceinline__ int32_t db_lower_bound(const int64_t *a, int64_t n, int64_t x)
-{
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (a[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return (int32_t)lo;
-}
-
 __global__ __launch_bounds__(kDbThreads) void sg_db_bisect(int64_t ne, const int64_t *src, const int64_t *dst, const int64_t *vid,
                                                            int64_t nv, int32_t *cs, uint32_t *ct, uint32_t *eidx)
 {
     const int64_t e = (int64_t)blockIdx.x * kDbThreads + threadIdx.x;
     if (e >= ne) return;
-    cs[e] = db_lower_bound(vid, nv, src[e]);
-    ct[e] = (uint32_t)db_lower_bound(vid, nv, dst[e]);
+    cs[e] = (int32_t)lower_bound<int64_t>(vid, 0, nv, src[e]);
+    ct[e] = (uint32_t)lower_bound<int64_t>(vid, 0, nv, dst[e]);
     eidx[e] = (uint32_t)e;
 }
 
@@ -323,12 +310,7 @@ __global__ __launch_bounds__(kDbThreads) void sg_db_dead_ptr(int64_t nv, const u
 {
     const int64_t v = (int64_t)blockIdx.x * kDbThreads + threadIdx.x;
     if (v > nv) return;
-    int64_t lo = 0, hi = nd;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if ((int64_t)dk[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    dead_ptr[v] = lo;
+    dead_ptr[v] = lower_bound<uint32_t>(dk, 0, nd, (uint32_t)v);  // (v <= nv < 2^31)
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------
@@ -340,47 +322,6 @@ struct DbStats {
     double ms[kDbPhases] = {0, 0, 0, 0};
 };
 thread_local DbStats g_db_stats;
-
-// events at the phase changes of one build; read() adds every interval to the phase that began it
-struct DbClock {
-    hipStream_t s = nullptr;
-    std::vector<hipEvent_t> ev;
-    std::vector<int> phase;
-    ~DbClock()
-    {
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-    }
-    int32_t mark(int ph)
-    {
-        hipEvent_t e;
-        LOCREC_HIP_TRY(hipEventCreate(&e));
-        ev.push_back(e);
-        phase.push_back(ph);
-        LOCREC_HIP_TRY(hipEventRecord(e, s));
-        return LOCREC_OK;
-    }
-    int32_t read(DbStats &st)
-    {
-        LOCREC_HIP_TRY(hipStreamSynchronize(s));
-        for (size_t i = 0; i + 1 < ev.size(); ++i) {
-            float t = 0;
-            LOCREC_HIP_TRY(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
-            if (phase[i] >= 0) st.ms[phase[i]] += t;
-        }
-        return LOCREC_OK;
-    }
-};
-
-// rocPRIM's two-phase protocol over one grow-only temporary
-template <class F>
-int32_t db_prim(DevBuf<unsigned char> &tmp, F call)
-{
-    size_t bytes = 0;
-    LOCREC_HIP_TRY(call(nullptr, bytes));
-    LOCREC_TRY(tmp.reserve(std::max<size_t>(bytes, 1)));
-    LOCREC_HIP_TRY(call(tmp.p, bytes));
-    return LOCREC_OK;
-}
 
 int db_bits(int64_t n)  // radix bits that hold every key below n
 {
@@ -417,7 +358,7 @@ int32_t db_dictionary(locrec_sg_graph *g, int64_t np)
     LOCREC_TRY(counts.alloc(nslots));
     LOCREC_TRY(nuniq.alloc(1));
     LOCREC_HIP_TRY(hipMemcpyAsync(ka.p, g->w2.p, nslots * 8, hipMemcpyDeviceToDevice, s));
-    size_t b1 = 0, b2 = 0;
+    size_t b1 = 0, b2 = 0;  // (not LOCREC_PRIM: both calls are sized before the one allocation, as sg_create_impl does)
     LOCREC_HIP_TRY(prim::sort_keys(nullptr, b1, ka.p, kb.p, nslots, 0u, 64u, s));
     LOCREC_HIP_TRY(prim::run_length_encode(nullptr, b2, kb.p, nslots, ka.p, counts.p, nuniq.p, s));
     LOCREC_TRY(tmp.alloc(std::max(b1, b2)));
@@ -491,9 +432,9 @@ int32_t sg_create_device_impl(int64_t ne, const int64_t *src, const int64_t *dst
     g->ne = ne;
     hipStream_t s = g->stream;
     g_db_stats = DbStats();
-    DbClock clock;
+    PhaseClock clock;
     clock.s = s;
-    DevBuf<unsigned char> tmp;
+    Temp tmp;
     const dim3 B(kDbThreads);
 
     // ---- vertex ranking: vid (ascending distinct ids), cs / ct (vertex index of every edge's source / target) ----
@@ -515,7 +456,7 @@ int32_t sg_create_device_impl(int64_t ne, const int64_t *src, const int64_t *dst
         LOCREC_HIP_TRY(hipGetLastError());
         LOCREC_HIP_TRY(hipMemcpyAsync(h, lohi.p, sizeof h, hipMemcpyDeviceToHost, s));
         LOCREC_HIP_TRY(hipStreamSynchronize(s));
-        const uint64_t id_lo = h[0] ^ 0x8000000000000000ull;  // (the id's bits; differences are exact in unsigned arithmetic)
+        const uint64_t id_lo = (uint64_t)id_of_key(h[0]);  // (the id's bits; differences are exact in unsigned arithmetic)
         const uint64_t id_span = h[1] - h[0];
         const bool dense_ids = id_span < (uint64_t)(8 * ne) + (1u << 20) && !g->env_no_dense_ids;
         if (dense_ids) {
@@ -523,17 +464,17 @@ int32_t sg_create_device_impl(int64_t ne, const int64_t *src, const int64_t *dst
             DevBuf<int32_t> r;
             LOCREC_TRY(r.alloc((size_t)n + 1));
             LOCREC_HIP_TRY(hipMemsetAsync(r.p, 0, ((size_t)n + 1) * 4, s));
-            hipLaunchKernelGGL(sg_db_mark, db_grid(ne), B, 0, s, ne, src, dst, id_lo, r.p);
+            hipLaunchKernelGGL(sg_db_mark, grid_for(ne), B, 0, s, ne, src, dst, id_lo, r.p);
             LOCREC_HIP_TRY(hipGetLastError());
-            LOCREC_TRY(db_prim(tmp, [&](void *t, size_t &b) { return prim::exclusive_sum(t, b, r.p, r.p, (size_t)n + 1, s); }));
+            LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, r.p, r.p, (size_t)n + 1, s));
             int32_t k = 0;
             LOCREC_HIP_TRY(hipMemcpyAsync(&k, r.p + n, 4, hipMemcpyDeviceToHost, s));
             LOCREC_HIP_TRY(hipStreamSynchronize(s));
             nv = k;
             LOCREC_TRY(vid.alloc((size_t)nv));
-            hipLaunchKernelGGL(sg_db_dense_vid, db_grid(n), B, 0, s, n, r.p, id_lo, vid.p);
+            hipLaunchKernelGGL(sg_db_dense_vid, grid_for(n), B, 0, s, n, r.p, id_lo, vid.p);
             LOCREC_HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(sg_db_dense_rank, db_grid(ne), B, 0, s, ne, src, dst, id_lo, r.p, cs.p, ct.p, eidx.p);
+            hipLaunchKernelGGL(sg_db_dense_rank, grid_for(ne), B, 0, s, ne, src, dst, id_lo, r.p, cs.p, ct.p, eidx.p);
             LOCREC_HIP_TRY(hipGetLastError());
             LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (r is a local)
         } else {
@@ -542,10 +483,10 @@ int32_t sg_create_device_impl(int64_t ne, const int64_t *src, const int64_t *dst
             LOCREC_TRY(ids.alloc((size_t)(2 * ne)));
             LOCREC_TRY(sorted.alloc((size_t)(2 * ne)));
             LOCREC_TRY(nuniq.alloc(1));
-            hipLaunchKernelGGL(sg_db_interleave, db_grid(ne), B, 0, s, ne, src, dst, ids.p);
+            hipLaunchKernelGGL(sg_db_interleave, grid_for(ne), B, 0, s, ne, src, dst, ids.p);
             LOCREC_HIP_TRY(hipGetLastError());
-            LOCREC_TRY(db_prim(tmp, [&](void *t, size_t &b) { return prim::sort_keys(t, b, ids.p, sorted.p, (size_t)(2 * ne), 0u, 64u, s); }));
-            LOCREC_TRY(db_prim(tmp, [&](void *t, size_t &b) { return prim::unique(t, b, sorted.p, ids.p, nuniq.p, (size_t)(2 * ne), s); }));
+            LOCREC_PRIM(tmp, prim::sort_keys(p_, bytes_, ids.p, sorted.p, (size_t)(2 * ne), 0u, 64u, s));
+            LOCREC_PRIM(tmp, prim::unique(p_, bytes_, sorted.p, ids.p, nuniq.p, (size_t)(2 * ne), s));
             unsigned long long k = 0;
             LOCREC_HIP_TRY(hipMemcpyAsync(&k, nuniq.p, 8, hipMemcpyDeviceToHost, s));
             LOCREC_HIP_TRY(hipStreamSynchronize(s));
@@ -553,7 +494,7 @@ int32_t sg_create_device_impl(int64_t ne, const int64_t *src, const int64_t *dst
             sorted.release();
             LOCREC_TRY(vid.alloc((size_t)nv));
             LOCREC_HIP_TRY(hipMemcpyAsync(vid.p, ids.p, (size_t)nv * 8, hipMemcpyDeviceToDevice, s));
-            hipLaunchKernelGGL(sg_db_bisect, db_grid(ne), B, 0, s, ne, src, dst, vid.p, nv, cs.p, ct.p, eidx.p);
+            hipLaunchKernelGGL(sg_db_bisect, grid_for(ne), B, 0, s, ne, src, dst, vid.p, nv, cs.p, ct.p, eidx.p);
             LOCREC_HIP_TRY(hipGetLastError());
             LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (ids is a local)
         }
@@ -569,12 +510,10 @@ int32_t sg_create_device_impl(int64_t ne, const int64_t *src, const int64_t *dst
     LOCREC_TRY(es.alloc((size_t)ne));
     LOCREC_TRY(vbeg.alloc((size_t)nv));
     LOCREC_TRY(vend.alloc((size_t)nv));
-    LOCREC_TRY(db_prim(tmp, [&](void *t, size_t &b) {
-        return prim::sort_pairs(t, b, ct.p, kt.p, eidx.p, es.p, (size_t)ne, 0u, (unsigned)db_bits(nv), s);
-    }));
+    LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, ct.p, kt.p, eidx.p, es.p, (size_t)ne, 0u, (unsigned)db_bits(nv), s));
     LOCREC_HIP_TRY(hipMemsetAsync(vbeg.p, 0, (size_t)nv * 4, s));
     LOCREC_HIP_TRY(hipMemsetAsync(vend.p, 0, (size_t)nv * 4, s));
-    hipLaunchKernelGGL(sg_db_row_bounds, db_grid(ne), B, 0, s, ne, kt.p, vbeg.p, vend.p);
+    hipLaunchKernelGGL(sg_db_row_bounds, grid_for(ne), B, 0, s, ne, kt.p, vbeg.p, vend.p);
     LOCREC_HIP_TRY(hipGetLastError());
     LOCREC_HIP_TRY(hipStreamSynchronize(s));
     ct.release();
@@ -588,16 +527,16 @@ int32_t sg_create_device_impl(int64_t ne, const int64_t *src, const int64_t *dst
         DevBuf<unsigned long long> fl;
         LOCREC_TRY(fl.alloc((size_t)nv + 1));
         LOCREC_TRY(live_of.alloc((size_t)nv));
-        hipLaunchKernelGGL(sg_db_live_flags, db_grid(nv + 1), B, 0, s, nv, vbeg.p, vend.p, fl.p);
+        hipLaunchKernelGGL(sg_db_live_flags, grid_for(nv + 1), B, 0, s, nv, vbeg.p, vend.p, fl.p);
         LOCREC_HIP_TRY(hipGetLastError());
-        LOCREC_TRY(db_prim(tmp, [&](void *t, size_t &b) { return prim::exclusive_sum(t, b, fl.p, fl.p, (size_t)nv + 1, s); }));
+        LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, fl.p, fl.p, (size_t)nv + 1, s));
         unsigned long long tot = 0;
         LOCREC_HIP_TRY(hipMemcpyAsync(&tot, fl.p + nv, 8, hipMemcpyDeviceToHost, s));
         LOCREC_HIP_TRY(hipStreamSynchronize(s));
         n_short = (int32_t)(tot & 0xFFFFFFFFull);
         T = n_short + (int32_t)(tot >> 32);
         LOCREC_TRY(live_vertex.alloc((size_t)T));
-        hipLaunchKernelGGL(sg_db_live, db_grid(nv), B, 0, s, nv, vbeg.p, vend.p, fl.p, n_short, live_of.p, live_vertex.p);
+        hipLaunchKernelGGL(sg_db_live, grid_for(nv), B, 0, s, nv, vbeg.p, vend.p, fl.p, n_short, live_of.p, live_vertex.p);
         LOCREC_HIP_TRY(hipGetLastError());
         LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (fl is a local)
     }
@@ -608,11 +547,10 @@ int32_t sg_create_device_impl(int64_t ne, const int64_t *src, const int64_t *dst
     DevBuf<DbCnt> sc;
     DbCnt tot, at_short;
     LOCREC_TRY(sc.alloc((size_t)T + 1));
-    hipLaunchKernelGGL(sg_db_row_counts, db_grid((int64_t)T + 1), B, 0, s, T, live_vertex.p, vbeg.p, vend.p, sc.p);
+    hipLaunchKernelGGL(sg_db_row_counts, grid_for((int64_t)T + 1), B, 0, s, T, live_vertex.p, vbeg.p, vend.p, sc.p);
     LOCREC_HIP_TRY(hipGetLastError());
-    LOCREC_TRY(db_prim(tmp, [&](void *t, size_t &b) {
-        return rocprim::exclusive_scan(t, b, sc.p, sc.p, DbCnt{{0, 0, 0, 0, 0, 0, 0, 0}}, (size_t)T + 1, DbCntPlus(), s);
-    }));
+    LOCREC_PRIM(tmp, rocprim::exclusive_scan(p_, bytes_, sc.p, sc.p, DbCnt{{0, 0, 0, 0, 0, 0, 0, 0}}, (size_t)T + 1,
+                                             DbCntPlus(), s));
     LOCREC_HIP_TRY(hipMemcpyAsync(&tot, sc.p + T, sizeof tot, hipMemcpyDeviceToHost, s));
     LOCREC_HIP_TRY(hipMemcpyAsync(&at_short, sc.p + n_short, sizeof at_short, hipMemcpyDeviceToHost, s));
     LOCREC_HIP_TRY(hipStreamSynchronize(s));
@@ -670,19 +608,19 @@ int32_t sg_create_device_impl(int64_t ne, const int64_t *src, const int64_t *dst
     LOCREC_HIP_TRY(hipMemsetAsync(crow.p, 0, crow.bytes(), s));
     LOCREC_HIP_TRY(hipMemsetAsync(g->PA.p, 0, (size_t)(2 * pa) * sizeof(double), s));
     if (T > 0) {
-        hipLaunchKernelGGL(sg_db_row_maps, db_grid(T), B, 0, s, P, live_vertex.p, vbeg.p, vend.p, sc.p, rowinfo.p, g->seg_out.p,
+        hipLaunchKernelGGL(sg_db_row_maps, grid_for(T), B, 0, s, P, live_vertex.p, vbeg.p, vend.p, sc.p, rowinfo.p, g->seg_out.p,
                            lrows_in_order.p, crow.p);
         LOCREC_HIP_TRY(hipGetLastError());
     }
     int32_t n_crows = 0;
     if (nl > 0) {
-        LOCREC_TRY(db_prim(tmp, [&](void *t, size_t &b) { return prim::exclusive_sum(t, b, crow.p, crow.p, (size_t)nl + 1, s); }));
-        hipLaunchKernelGGL(sg_db_lrows_partition, db_grid(nl), B, 0, s, nl, lrows_in_order.p, crow.p, g->lrows.p);
+        LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, crow.p, crow.p, (size_t)nl + 1, s));
+        hipLaunchKernelGGL(sg_db_lrows_partition, grid_for(nl), B, 0, s, nl, lrows_in_order.p, crow.p, g->lrows.p);
         LOCREC_HIP_TRY(hipGetLastError());
         LOCREC_HIP_TRY(hipMemcpyAsync(&n_crows, crow.p + nl, 4, hipMemcpyDeviceToHost, s));
     }
     if (np > 0) {
-        hipLaunchKernelGGL(sg_db_pinfo, db_grid(np), B, 0, s, (int32_t)np, P, g->pinfo.p);
+        hipLaunchKernelGGL(sg_db_pinfo, grid_for(np), B, 0, s, (int32_t)np, P, g->pinfo.p);
         LOCREC_HIP_TRY(hipGetLastError());
     }
     LOCREC_HIP_TRY(hipStreamSynchronize(s));
@@ -702,15 +640,15 @@ int32_t sg_create_device_impl(int64_t ne, const int64_t *src, const int64_t *dst
     LOCREC_HIP_TRY(hipMemsetAsync(bad.p, 0, 4, s));
     LOCREC_HIP_TRY(hipMemsetAsync(g->w2.p, 0, (size_t)nslots * 8, s));
     if (g->use16) {
-        hipLaunchKernelGGL(sg_db_fill<unsigned short>, db_grid(nslots), B, 0, s, nslots, (unsigned short)T, g->col16.p);
+        hipLaunchKernelGGL(sg_db_fill<unsigned short>, grid_for(nslots), B, 0, s, nslots, (unsigned short)T, g->col16.p);
         LOCREC_HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(sg_db_scatter<unsigned short>, db_grid(ne), B, 0, s, ne, kt.p, es.p, vbeg.p, vend.p, live_of.p, rowinfo.p,
+        hipLaunchKernelGGL(sg_db_scatter<unsigned short>, grid_for(ne), B, 0, s, ne, kt.p, es.p, vbeg.p, vend.p, live_of.p, rowinfo.p,
                            cs.p, w, T, nslots, g->col16.p, reinterpret_cast<double *>(g->w2.p), slot_of_edge.p, bad.p);
     } else {
         int32_t *col = reinterpret_cast<int32_t *>(g->col4.p);
-        hipLaunchKernelGGL(sg_db_fill<int32_t>, db_grid(nslots), B, 0, s, nslots, T, col);
+        hipLaunchKernelGGL(sg_db_fill<int32_t>, grid_for(nslots), B, 0, s, nslots, T, col);
         LOCREC_HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(sg_db_scatter<int32_t>, db_grid(ne), B, 0, s, ne, kt.p, es.p, vbeg.p, vend.p, live_of.p, rowinfo.p, cs.p, w,
+        hipLaunchKernelGGL(sg_db_scatter<int32_t>, grid_for(ne), B, 0, s, ne, kt.p, es.p, vbeg.p, vend.p, live_of.p, rowinfo.p, cs.p, w,
                            T, nslots, col, reinterpret_cast<double *>(g->w2.p), slot_of_edge.p, bad.p);
     }
     LOCREC_HIP_TRY(hipGetLastError());
@@ -734,11 +672,10 @@ int32_t sg_create_device_impl(int64_t ne, const int64_t *src, const int64_t *dst
         LOCREC_TRY(flag.alloc((size_t)ne));
         LOCREC_TRY(didx.alloc((size_t)ne));
         LOCREC_TRY(ndead.alloc(1));
-        hipLaunchKernelGGL(sg_db_dead_flag, db_grid(ne), B, 0, s, ne, cs.p, live_of.p, flag.p);
+        hipLaunchKernelGGL(sg_db_dead_flag, grid_for(ne), B, 0, s, ne, cs.p, live_of.p, flag.p);
         LOCREC_HIP_TRY(hipGetLastError());
-        LOCREC_TRY(db_prim(tmp, [&](void *t, size_t &b) {
-            return prim::select_flagged(t, b, prim::counting_iterator<uint32_t>(0), flag.p, didx.p, ndead.p, (size_t)ne, s);
-        }));
+        LOCREC_PRIM(tmp, prim::select_flagged(p_, bytes_, prim::counting_iterator<uint32_t>(0), flag.p, didx.p, ndead.p,
+                                              (size_t)ne, s));
         unsigned long long k = 0;
         LOCREC_HIP_TRY(hipMemcpyAsync(&k, ndead.p, 8, hipMemcpyDeviceToHost, s));
         LOCREC_HIP_TRY(hipStreamSynchronize(s));
@@ -751,19 +688,18 @@ int32_t sg_create_device_impl(int64_t ne, const int64_t *src, const int64_t *dst
         LOCREC_TRY(dk2.alloc((size_t)nd));
         LOCREC_TRY(dv.alloc((size_t)nd));
         if (nd > 0) {
-            hipLaunchKernelGGL(sg_db_dead_gather, db_grid(nd), B, 0, s, nd, didx.p, cs.p, slot_of_edge.p, dk.p, dv.p);
+            hipLaunchKernelGGL(sg_db_dead_gather, grid_for(nd), B, 0, s, nd, didx.p, cs.p, slot_of_edge.p, dk.p, dv.p);
             LOCREC_HIP_TRY(hipGetLastError());
-            LOCREC_TRY(db_prim(tmp, [&](void *t, size_t &b) {
-                return prim::sort_pairs(t, b, dk.p, dk2.p, dv.p, g->dead_slots_dev.p, (size_t)nd, 0u, (unsigned)db_bits(nv), s);
-            }));
+            LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, dk.p, dk2.p, dv.p, g->dead_slots_dev.p, (size_t)nd, 0u,
+                                              (unsigned)db_bits(nv), s));
         }
-        hipLaunchKernelGGL(sg_db_dead_ptr, db_grid(nv + 1), B, 0, s, nv, dk2.p, nd, dead_ptr.p);
+        hipLaunchKernelGGL(sg_db_dead_ptr, grid_for(nv + 1), B, 0, s, nv, dk2.p, nd, dead_ptr.p);
         LOCREC_HIP_TRY(hipGetLastError());
         LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (locals)
     }
     slot_of_edge.release();
     cs.release();
-    tmp.release();
+    tmp.buf.release();
 
     // ---- what the handle keeps on the host (V-sized): begin_request and fetch use it ----
     g->vid.resize((size_t)nv);
@@ -805,7 +741,7 @@ int32_t sg_create_device_impl(int64_t ne, const int64_t *src, const int64_t *dst
     const int64_t need = waves > 0 ? (np + waves - 1) / waves : 1 << 30;
     g->persist_pw = need <= 4 ? 4 : need <= 12 ? 12 : 0;
     g->persist_ok = false;  // (LOCREC_SG_PERSIST handles come from the host build)
-    LOCREC_TRY(clock.read(g_db_stats));
+    LOCREC_TRY(clock.read(g_db_stats.ms));
     *out = g.release();
     return LOCREC_OK;
 }

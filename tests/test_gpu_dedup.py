@@ -387,3 +387,84 @@ def test_quarter_size_perf_case(pkg):
     assert got_rows == want_rows and len(want_rows) > 50
     want_same = np.bincount([r[0] for r in want_rows], minlength=len(partners))[sample]
     assert np.array_equal(not_same[sample], partners[sample] - want_same)
+
+
+# ---- one grid walk, two consumers -----------------------------------------------------------------------------------------
+
+WALK_RADIUS = 60.0
+WALK_SEED = 13   # the first seed whose case meets check_grid_walk_case with five matches across the antimeridian
+
+
+def grid_walk_case(seed=WALK_SEED):
+    """About 200 points and 60 anchors with disjoint ids in three regions, every point 0 - 120 m from an anchor of its
+    region.  The regions sit on the walk's edges (csrc/place_grid.h): anchors on both sides of the antimeridian, anchors
+    in the single-cell band at the pole, and mid-latitude anchors on both sides of a band boundary of the 60 m grid."""
+    rng = np.random.default_rng(seed)
+    band_deg = WALK_RADIUS / dc.EARTH_RADIUS_METERS * (180.0 / np.pi) * (1.0 + 1e-9) + 1e-12   # make_grid(60).band_deg
+    boundary = -90.0 + np.floor((55.75 + 90.0) / band_deg) * band_deg
+    k = np.arange(20)
+    a_lat = np.concatenate([-17.0 + (k // 2) * 0.0007, np.full(20, 89.9995), boundary + np.where(k % 2 == 0, 9e-5, -9e-5)])
+    a_lon = np.concatenate([np.where(k % 2 == 0, 179.9995, -179.9995), -180.0 + 18.0 * k, 37.6 + (k // 2) * 0.0012])
+    a_region = np.repeat(np.array([-7, 3, 2 ** 40], np.int64), 20)
+    n = 201
+    near = np.arange(n) % 60
+    p_lat, p_lon = np.empty(n), np.empty(n)
+    for i in range(n):
+        p_lat[i], p_lon[i] = dc.destination(a_lat[near[i]], a_lon[near[i]], rng.uniform(0, 2 * np.pi), rng.uniform(0, 120.0))
+    points = dict(id=1000 + np.arange(n, dtype=np.int64), region_id=a_region[near], latitude=p_lat, longitude=p_lon)
+    anchors = dict(id=1 + np.arange(60, dtype=np.int64), region_id=a_region, latitude=a_lat, longitude=a_lon)
+    return points, anchors, boundary
+
+
+def grid_walk_brute_force(points, anchors):
+    """-> (the (point id, anchor id) pairs within the radius in (point row, anchor row) order, the distances of all
+    in-region pairs [n_points, n_anchors] with NaN elsewhere)"""
+    d = haversine_numpy(points["latitude"][:, None], points["longitude"][:, None], anchors["latitude"][None, :],
+                        anchors["longitude"][None, :])
+    d = np.where(points["region_id"][:, None] == anchors["region_id"][None, :], d, np.nan)
+    rows, cols = np.nonzero(d <= WALK_RADIUS)
+    return list(zip(points["id"][rows].tolist(), anchors["id"][cols].tolist())), d
+
+
+def check_grid_walk_case(points, anchors, boundary):
+    """The input condition (no decision within 1e-3 m of the radius: DESIGN.md section 2 allows device and libm distances
+    to differ in the last ulps only) and that the case does reach the walk's edges.  Needs no GPU."""
+    want, d = grid_walk_brute_force(points, anchors)
+    assert np.nanmin(np.abs(d - WALK_RADIUS)) > 1e-3
+    assert len(points["id"]) >= 200 and len(anchors["id"]) == 60 and not set(points["id"]) & set(anchors["id"])
+    assert np.nanmax(np.nanmin(d, axis=1)) <= 120.0 and len(want) > len(points["id"]) // 4
+    row_of_point = {int(v): r for r, v in enumerate(points["id"])}
+    row_of_anchor = {int(v): r for r, v in enumerate(anchors["id"])}
+    pr = np.array([row_of_point[p] for p, _ in want])
+    ar = np.array([row_of_anchor[a] for _, a in want])
+    plat, plon, alat, alon = points["latitude"][pr], points["longitude"][pr], anchors["latitude"][ar], anchors["longitude"][ar]
+    wrap = anchors["region_id"][ar] == -7
+    assert (wrap & (plon * alon < 0)).sum() >= 3                                  # matches across the antimeridian (53 m from each anchor)
+    pole = anchors["region_id"][ar] == 3
+    assert (pole & (np.abs(plon - alon) > 90.0)).sum() >= 5                       # matches across the pole's one cell
+    band = anchors["region_id"][ar] == 2 ** 40
+    assert (band & ((plat < boundary) != (alat < boundary))).sum() >= 5           # matches across the band boundary
+    return want
+
+
+def test_grid_walk_serves_both_joins_alike(pkg):
+    """calc_place_visits (points as visits, anchors as places) and find_duplicate_places (points as places, anchors as
+    confirmed places, empty names, no name difference allowed) walk the grid with one function: their (point, anchor)
+    pairs are the same list, and it is the brute force's, in host and in device memory."""
+    points, anchors, boundary = grid_walk_case()
+    want = check_grid_walk_case(points, anchors, boundary)
+    n, m = len(points["id"]), len(anchors["id"])
+    visits = dict(person_id=points["id"], timestamp=5000 + (np.arange(n, dtype=np.int64) * 37) % 101,
+                  latitude=points["latitude"], longitude=points["longitude"], region_id=points["region_id"])
+    places = dict(anchors, category_id=np.zeros(m, np.int64))
+    nameless = lambda side, count: dict(side, name_offsets=np.zeros(count + 1, np.int64), name_units=np.zeros(0, np.uint16))
+    dp, dcf = nameless(points, n), nameless(anchors, m)
+    for device in (False, True):
+        v, p, a, b = ((to_device(x) if device else x) for x in (visits, places, dp, dcf))
+        joined = pkg.prep.calc_place_visits(v, p, int(visits["timestamp"].min()), WALK_RADIUS)
+        got_join = list(zip(to_host(joined["person_id"]).tolist(), to_host(joined["place_id"]).tolist()))
+        prow, crow, diff, _ = (to_host(x) for x in pkg.deduplicator.find_duplicate_places(a, b, WALK_RADIUS, 0))
+        got_dedup = list(zip(points["id"][prow].tolist(), anchors["id"][crow].tolist()))
+        assert not diff.any()
+        assert got_join == got_dedup
+        assert got_join == want
