@@ -872,6 +872,100 @@ int32_t locrec_find_duplicate_places(
 int32_t locrec_find_duplicate_places_stats(int64_t *out_candidates, int64_t *out_same, int64_t *out_chunks,
                                            double *out_grid_ms, double *out_lev_ms, double *out_compact_ms);
 
+/* ===================================================================== */
+/* The sample generator (sample/LocationVisitsSampleGenerator.scala,      */
+/* sample/PlacesSampleGenerator.scala, sample/SampleGeneratorMain.scala), */
+/* csrc/sample.hip.  Stateless, on the current device, with the           */
+/* producers' conventions: `mem` names where the COLUMN arrays live;      */
+/* region tables (ids, boxes), category-name tables and counts are always */
+/* host memory; a call returns when its outputs are complete.             */
+/* Regions: n_regions in [1, 2^24) distinct non-negative ids; boxes are   */
+/* [n_regions][4] = minLatitude, maxLatitude, minLongitude, maxLongitude, */
+/* finite, min <= max, inside [-90, 90] x [-180, 180].                    */
+/* Random numbers: Spark's rand(seed) depends on the partition layout and */
+/* cannot be reproduced (parity unpinned).  Every factor here is          */
+/* u01(seed, stream, row, slot) of the package's counter-based generator  */
+/* (synth.u01: three splitmix64 steps, (k >> 11) * 2^-53), bit-identical  */
+/* on host and device; DESIGN.md section 9b gives the keying.             */
+
+/*
+ * generatePersons (LocationVisitsSampleGenerator.scala:55-68): ppr = person_count / n_regions (integer
+ * division, the remainder is dropped); region r of the list, in the GIVEN order, gets the ids
+ * min_person_id + r.id * ppr ... min_person_id + (r.id + 1) * ppr - 1 ascending - the formula uses the region's
+ * id, not its position - with home_region_id = r.id.  The outputs need room for ppr * n_regions rows;
+ * *out_count = rows written.  An id range that leaves int64: LOCREC_E_INVALID_ARG.
+ */
+int32_t locrec_sample_persons(int32_t n_regions, const int64_t *region_ids, int64_t person_count,
+                              int64_t min_person_id, int32_t mem, int64_t *out_ids, int64_t *out_home_region_ids,
+                              int64_t *out_count);
+
+/*
+ * withVisits / withGeoLocations / withTimestamps (LocationVisitsSampleGenerator.scala:78-133) for the persons
+ * table (person_ids, home_region_ids; n_persons rows in `mem`).  Person row p has the index
+ * person_index_base + p, and its rows depend on (seed, that index) alone: a shard of the persons generated
+ * with its own base reproduces the rows of the whole table.  The person gets
+ * (int)(f * max_visits_per_person) + 1 rows, f = u01(seed, 1, index, 0); row k of it carries
+ *   person_id, region_id = the home region,
+ *   latitude  = minLat + (maxLat - minLat) * g_lat, longitude likewise (fp64, three separate operations),
+ *   timestamp = from_timestamp_ms + (long)(interval_hours * g_t) * 3,600,000   (epoch milliseconds),
+ *   year_month = year * 100 + month of the timestamp (int32, e.g. 201803), by a civil-from-days computation
+ *   in UTC with floor division (right before 1970, leap years with the century rules).  Spark's year() and
+ *   month() would use the session time zone; the reference's launcher leaves it at the JVM's default.
+ * shared_factor = 1: g_lat = g_lon = g_t = u01(seed, 2, index, 3k) - in the reference the three columns are
+ * rand(0) over the same rows, one stream, so a visit lies on its region's diagonal.  shared_factor = 0:
+ * g_lat, g_lon, g_t = u01(seed, 2, index, 3k / 3k + 1 / 3k + 2).
+ * Rows are ordered by (person row, k).  *inout_count: capacity in, rows the result HAS out (may exceed the
+ * capacity, then the first `capacity` rows of the full result are written; call with 0 to size the buffers,
+ * the outputs may then be NULL).  Counts and offsets are 64-bit: the generator has no 2^31 limit (the
+ * producers downstream have).  A person whose home region is not listed fails with LOCREC_E_INVALID_ARG
+ * naming the first such row, as regions.find(...).get throws (:33-36).  max_visits_per_person in [1, 2^31),
+ * interval_hours >= 0, and the whole interval within 100,000,000 days of 1970.
+ */
+int32_t locrec_sample_location_visits(int64_t n_persons, const int64_t *person_ids, const int64_t *home_region_ids,
+                                      int64_t person_index_base, int32_t n_regions, const int64_t *region_ids,
+                                      const double *region_boxes, int64_t from_timestamp_ms, int64_t interval_hours,
+                                      int64_t max_visits_per_person, uint64_t seed, int32_t shared_factor,
+                                      int32_t mem, int64_t *out_person_ids, int64_t *out_region_ids,
+                                      double *out_latitudes, double *out_longitudes, int64_t *out_timestamps,
+                                      int32_t *out_year_months, int64_t *inout_count);
+
+/* What this thread's last locrec_sample_location_visits did (measurement): rows written, bytes written
+ * (44 a row), and HIP-event milliseconds of its count-and-scan phase and of its fill phase.  Every pointer
+ * may be NULL. */
+int32_t locrec_sample_location_visits_stats(int64_t *out_rows, int64_t *out_bytes, double *out_count_ms,
+                                            double *out_fill_ms);
+
+/*
+ * withGeo / withCategories (PlacesSampleGenerator.scala:41-77): ppr = place_count / n_regions,
+ * c = floor(sqrt(ppr)) (computed on the host; ppr == 0 gives no places and no division); every region of the
+ * list, in the given order, gets a c x c grid, latitude index outer, both indices from 1:
+ *   latitude = minLat + latStep * latIdx with latStep = (maxLat - minLat) / c, longitude likewise,
+ *   id = min_place_id + r.id * c^2 + (latIdx - 1) * c + (lonIdx - 1),
+ *   category_id = min_category_id + (long)(f * n_categories), f = u01(seed, 3, place row, 0).
+ * The outputs need room for c^2 * n_regions rows; *out_count = rows written.  place_count in [0, 2^52],
+ * n_categories in [1, 2^31); an id range that leaves int64: LOCREC_E_INVALID_ARG.
+ */
+int32_t locrec_sample_places(int32_t n_regions, const int64_t *region_ids, const double *region_boxes,
+                             int64_t place_count, int64_t min_place_id, int64_t n_categories,
+                             int64_t min_category_id, uint64_t seed, int32_t mem, int64_t *out_ids,
+                             double *out_latitudes, double *out_longitudes, int64_t *out_region_ids,
+                             int64_t *out_category_ids, int64_t *out_count);
+
+/*
+ * withNames (PlacesSampleGenerator.scala:79-90): name = description = "<category name>-<id>" of n places as
+ * the CSR locrec_find_duplicate_places takes: out_offsets int64[n + 1] plus UTF-16 code units.  The category
+ * names are a HOST CSR of n_categories names (offsets[n_categories + 1], units), entry category_id -
+ * min_category_id; their units are copied as they are.  Ids are non-negative (up to 19 digits); a negative id
+ * or a category outside the table fails with LOCREC_E_INVALID_ARG naming the first such row.  Two phases:
+ * lengths, a scan, the fill.  *inout_units: capacity of out_units in, units the result HAS out (may exceed the
+ * capacity, then the first `capacity` units are written; with capacity 0 out_offsets and out_units may be
+ * NULL).  out_offsets, when given, is always written whole.
+ */
+int32_t locrec_sample_place_names(int64_t n, const int64_t *place_ids, const int64_t *category_ids,
+                                  int64_t min_category_id, int64_t n_categories,
+                                  const int64_t *category_name_offsets, const uint16_t *category_name_units,
+                                  int32_t mem, int64_t *out_offsets, uint16_t *out_units, int64_t *inout_units);
+
 #ifdef __cplusplus
 }
 #endif

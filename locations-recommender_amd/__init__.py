@@ -10,3 +10,5 @@ from .multi import KnnReplicas, SgSharded, set_devices  # noqa: F401
 from . import prep  # noqa: F401,E402  (calc_ratings, calc_rating_vectors, build_with_balanced_weights, calc_place_visits)
 from . import deduplicator  # noqa: F401,E402
 from .deduplicator import PlaceDeduplicator, lev  # noqa: F401,E402
+from . import sample  # noqa: F401,E402  (the sample generator: generate_persons, generate_location_visits, generate_places, place_names)
+from .sample import Region  # noqa: F401,E402

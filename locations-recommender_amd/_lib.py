@@ -160,6 +160,16 @@ SIGNATURES = {
                                      C.c_double, C.c_int32, C.c_int32,
                                      C.c_void_p, C.c_void_p, C.c_void_p, _i64p, C.c_void_p],
     "locrec_find_duplicate_places_stats": [_i64p, _i64p, _i64p, _f64p, _f64p, _f64p],
+    # the sample generator (sample.hip): region and category tables are host arrays, the columns void*
+    "locrec_sample_persons": [C.c_int32, _i64p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, _i64p],
+    "locrec_sample_location_visits": [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, _i64p, _f64p,
+                                      C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_int32, C.c_int32,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _i64p],
+    "locrec_sample_location_visits_stats": [_i64p, _i64p, _f64p, _f64p],
+    "locrec_sample_places": [C.c_int32, _i64p, _f64p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_int32,
+                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _i64p],
+    "locrec_sample_place_names": [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, _i64p, C.POINTER(C.c_uint16),
+                                  C.c_int32, C.c_void_p, C.c_void_p, _i64p],
 }
 _RESTYPE = {"locrec_last_error": C.c_char_p, "locrec_version": C.c_char_p, "locrec_knn_replicas_destroy": None,
             "locrec_sg_sharded_destroy": None, "locrec_sg_group_destroy": None}

@@ -487,3 +487,109 @@ def stochastic_graph_builder_main(data_dir, last_days_count, beta_person_place, 
                                                                          beta_person_category))
         written.append(rs)
     return written
+
+
+# ---- the head of the chain: SampleGeneratorMain.doMain (sample-generator/.../SampleGeneratorMain.scala:46-72) ---------------
+
+def sample_generator_main(data_dir, place_count, person_count, regions, categories, seed=0, shared_factor=True, year=2018):
+    """SampleGeneratorMain.doMain without Spark: persons_sample, location_visits_sample, places_sample and categories_sample
+    under data_dir, generated on the device (sample.generate) and written with one part file each, the reference's
+    partition columns as plain columns: timestamp as a Parquet timestamp of milliseconds, region_id / home_region_id as
+    int32 (what Spark infers for a partition value), year_month as a string such as "201803"; places carry name and
+    description.  The regions and category names are the caller's (the reference's own are literals of its program).
+    -> the tables as sample.generate returns them (CUDA tensors), ready for prep.calc_place_visits."""
+    import pyarrow as pa
+    from . import _cache, sample
+    _cache.require_gpu_backend("sample_generator_main")
+    t = sample.generate(place_count, person_count, regions, categories, seed=seed, shared_factor=shared_factor, year=year,
+                        device=True)
+    persons, visits, places, cats = t["persons"], t["location_visits"], t["places"], t["categories"]
+    _write_dir(os.path.join(data_dir, "persons_sample"),
+               pa.table([pa.array(_host(persons["id"], np.int64), pa.int64()),
+                         pa.array(_host(persons["home_region_id"], np.int32), pa.int32())], names=["id", "home_region_id"]))
+    ym = _host(visits["year_month"], np.int32)
+    _write_dir(os.path.join(data_dir, "location_visits_sample"),
+               pa.table([pa.array(_host(visits["person_id"], np.int64), pa.int64()),
+                         pa.array(_host(visits["latitude"], np.float64), pa.float64()),
+                         pa.array(_host(visits["longitude"], np.float64), pa.float64()),
+                         pa.array(_host(visits["timestamp"], np.int64), pa.int64()).cast(pa.timestamp("ms")),
+                         pa.array(_host(visits["region_id"], np.int32), pa.int32()),
+                         pa.array(np.char.zfill(ym.astype(str), 6) if len(ym) else np.empty(0, str), pa.string())],
+                        names=["person_id", "latitude", "longitude", "timestamp", "region_id", "year_month"]))
+    names = sample.decode_names(places["name_offsets"], places["name_units"])
+    _write_dir(os.path.join(data_dir, "places_sample"),
+               pa.table([pa.array(_host(places["id"], np.int64), pa.int64()),
+                         pa.array(_host(places["latitude"], np.float64), pa.float64()),
+                         pa.array(_host(places["longitude"], np.float64), pa.float64()),
+                         pa.array(_host(places["category_id"], np.int64), pa.int64()),
+                         pa.array(names, pa.string()), pa.array(names, pa.string()),
+                         pa.array(_host(places["region_id"], np.int32), pa.int32())],
+                        names=["id", "latitude", "longitude", "category_id", "name", "description", "region_id"]))
+    _write_dir(os.path.join(data_dir, "categories_sample"),
+               pa.table([pa.array(cats["category"], pa.string()), pa.array(cats["category_id"], pa.int64())],
+                        names=["category", "category_id"]))
+    return t
+
+
+# ---- the tail of the chain: one request line of the recommender mains (RecommenderMainCommon.scala:16-56) -------------------
+
+class NoSuchElementException(LookupError):
+    """java.util.NoSuchElementException: the person of a request is not in persons_sample (RecommenderMainCommon.scala:54)."""
+
+
+_INPUT_REGEX = r"(\d+)\s*(\d+)?"   # RecommenderMainCommon.scala:16; matched whole, ASCII digits and white space
+_LONG_MAX = 2 ** 63 - 1
+
+
+def parse_input(line):
+    """RecommenderMainCommon.parseInput (:18-25): "person [region]" -> (person_id, region_id or None).  A line that does
+    not match as a whole, or a number that does not fit a Long (String.toLong throws NumberFormatException, itself an
+    IllegalArgumentException): IllegalArgumentException("Failed to parse input: ...")."""
+    import re
+    m = re.fullmatch(_INPUT_REGEX, line, flags=re.ASCII) if isinstance(line, str) else None
+    if m is None:
+        raise L.IllegalArgumentException(f"Failed to parse input: {line}")
+    person, region = int(m.group(1)), (None if m.group(2) is None else int(m.group(2)))
+    if person > _LONG_MAX or (region is not None and region > _LONG_MAX):
+        raise L.IllegalArgumentException(f"Failed to parse input: {line}")
+    return person, region
+
+
+def load_persons(data_dir):
+    """persons_sample (LocationVisitsSampleGenerator.scala:70-76; read by KnnRecommenderMain / StochasticRecommenderMain)
+    -> dict(id, home_region_id) of int64 columns."""
+    t = _read(os.path.join(data_dir, "persons_sample"), ["id", "home_region_id"])
+    return {"id": _column_i64(t["id"]), "home_region_id": _column_i64(t["home_region_id"])}
+
+
+def calc_recommender_target(persons, person_id_input_region_id):
+    """RecommenderMainCommon.calcRecommenderTarget (:27-56): (person_id, region or None) -> (person_id, home_region_id,
+    target_region_id), the target falling back to the person's home region.  A person that persons (dict(id,
+    home_region_id)) does not hold: NoSuchElementException("Person not found: <id>")."""
+    person_id, input_region = person_id_input_region_id
+    rows = np.flatnonzero(_host(persons["id"], np.int64) == int(person_id))
+    if len(rows) == 0:
+        raise NoSuchElementException(f"Person not found: {person_id}")
+    home = int(_host(persons["home_region_id"], np.int64)[rows[0]])   # where(id === personId).limit(1)
+    return int(person_id), home, home if input_region is None else int(input_region)
+
+
+def knn_recommender_request(data_dir, persons, line, place_weight, category_weight, k_nearest, max_recommendations=10):
+    """The body of KnnRecommenderMain's loop for one input line (KnnRecommenderMain.scala:36-51,90-101): parse, resolve
+    the target, recommend from the region set [home, target], rank against the target region's places on the device.
+    -> ((person_id, home_region_id, target_region_id), place_ids, estimated_ratings)."""
+    from . import prep
+    target = calc_recommender_target(persons, parse_input(line))
+    ids, scores = knn_make_recommendations(data_dir, [target[1], target[2]], target[0], place_weight, category_weight, k_nearest)
+    place_ids, place_regions = load_places(data_dir)
+    return (target,) + tuple(prep.rank_recommendations(ids, scores, place_ids, place_regions, target[2], max_recommendations))
+
+
+def sg_recommender_request(data_dir, persons, line, epsilon, max_iterations, max_recommendations=10):
+    """The body of StochasticRecommenderMain's loop for one input line (StochasticRecommenderMain.scala:36-51,64-75).
+    -> ((person_id, home_region_id, target_region_id), ids, probabilities)."""
+    from . import prep
+    target = calc_recommender_target(persons, parse_input(line))
+    ids, scores, _, _ = sg_make_recommendations(data_dir, [target[1], target[2]], target[0], epsilon, max_iterations)
+    place_ids, place_regions = load_places(data_dir)
+    return (target,) + tuple(prep.rank_recommendations(ids, scores, place_ids, place_regions, target[2], max_recommendations))
