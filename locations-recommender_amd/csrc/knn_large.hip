@@ -9,6 +9,10 @@
 //                        pass over the transposed ratings: est[p] = sum r*s / sum s over the selected
 //                        raters of p, each place summed by one wave in a fixed order.
 // A library sort is used here on purpose: this is the rare large-K corner, not the hot path.
+// The place-major pass is ONE set of kernels (lk_aggregate_segments, lk_sum_segments, lk_finish_count, lk_finish_emit)
+// templated on the number of query columns of the weights S[row][QT]: QT = 1 is the single request (and the
+// host-given weights of knn_large_aggregate), QT = kLkbQt a tile of a batch (below: "Batched large K", "Batched top-K
+// at any K") - so a batch's estimates are the single request's bit for bit by construction.
 
 #include "dev_prims.h"
 
@@ -19,6 +23,35 @@
 namespace {
 
 using namespace locrec;
+
+constexpr int kLkHistBins = 4096;  // kHistBins of knn.hip
+
+// the sum of v over the wave (xor butterfly: every lane ends with the same bits)
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v)
+{
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) v = v + __shfl_xor(v, d);
+    return v;
+}
+
+// exclusive prefix of c over the 256 threads of a block: within the wave, then over the four waves, whose totals
+// it leaves in wtot[4] (LDS); holds a __syncthreads
+__device__ __forceinline__ int block_scan_256(int c, int *wtot)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int incl = c;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int v = __shfl_up(incl, d);
+        if (lane >= d) incl += v;
+    }
+    if (lane == 63) wtot[wave] = incl;
+    __syncthreads();
+    int off = incl - c;
+    for (int w = 0; w < wave; ++w) off += wtot[w];
+    return off;
+}
 
 // keys[r] = bit pattern of the similarity of the person with id-rank r (all similarities are >= +0,
 // so the unsigned order of the bits is the numeric order); vals[r] = r
@@ -67,133 +100,146 @@ __global__ void lk_scatter_weights(const uint64_t *keys, const uint32_t *vals, i
 // Place-major aggregation in two steps.  A popular place has hundreds of thousands of raters (874 k at
 // cfg2): one wave walking all of them was the whole cost of a large-K request (~10 ms).  The raters
 // of a place are therefore cut into SEGMENTS of at most kSegRaters entries (a table built once per
-// index): one wave per segment (lanes stride it, butterfly), then one thread per place adds its
+// index): one wave per segment (lanes stride it, butterfly), then one thread per (place, query) adds its
 // segments' sums in segment order - a fixed order, so the result is reproducible.
 constexpr int kSegRaters = 4096;
 
+// S[row][QT]: column t = the weights of query t (0 = not a neighbour).  Lane l takes raters l, l + 64, ... of the
+// segment in ascending order, U of them in flight: the row loads, then the U dependent gathers of S (one after the
+// other this loop was a chain of 64 memory round trips per segment); added in the same order as a plain loop.  With
+// QT = 16 a rater's weights are one 128-byte line that serves sixteen queries, and two raters in flight fill the
+// registers (150 VGPRs); the single column has room for eight.
+template <int QT, int U>
 __global__ __launch_bounds__(256) void lk_aggregate_segments(const int64_t *seg_begin, const int64_t *seg_end, int32_t nsegs,
-                                                             const int32_t *cp_row, const double *cp_rating, const double *w,
+                                                             const int32_t *cp_row, const double *cp_rating, const double *S,
                                                              double *seg_ws, double *seg_ss)
 {
     const int lane = threadIdx.x & 63;
     const int sg = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (sg >= nsegs) return;
-    double ws = 0.0, ss = 0.0;
-    // eight raters per lane in flight: the row loads, then the eight dependent gathers of w[] (one after
-    // the other this loop was a chain of 64 memory round trips per segment); added in the same ascending
-    // order as a plain loop
-    const int64_t end = seg_end[sg];
-    for (int64_t e0 = seg_begin[sg] + lane; e0 < end; e0 += 64 * 8) {
-        int32_t rr[8];
-        double rt[8], sv[8];
+    double ws[QT], ss[QT];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
+    for (int t = 0; t < QT; ++t) ws[t] = ss[t] = 0.0;
+    const int64_t end = seg_end[sg];
+    for (int64_t e0 = seg_begin[sg] + lane; e0 < end; e0 += 64 * U) {
+        int32_t rr[U];
+        double rt[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
             const int64_t e = e0 + 64 * u;
             rr[u] = e < end ? cp_row[e] : -1;
             rt[u] = e < end ? cp_rating[e] : 0.0;
         }
+        double sv[U][QT];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) sv[u] = rr[u] >= 0 ? w[rr[u]] : 0.0;
+        for (int u = 0; u < U; ++u)
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            if (sv[u] > 0) {
-                const double wr = rt[u] * sv[u];  // col("rating") * col("similarity") (:59)
-                ws = ws + wr;
-                ss = ss + sv[u];
-            }
-        }
+            for (int t = 0; t < QT; ++t) sv[u][t] = rr[u] >= 0 ? S[(int64_t)rr[u] * QT + t] : 0.0;
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int t = 0; t < QT; ++t)
+                if (sv[u][t] > 0) {
+                    const double wr = rt[u] * sv[u][t];  // col("rating") * col("similarity") (:59)
+                    ws[t] = ws[t] + wr;
+                    ss[t] = ss[t] + sv[u][t];
+                }
     }
 #pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        ws = ws + __shfl_xor(ws, d);
-        ss = ss + __shfl_xor(ss, d);
+    for (int t = 0; t < QT; ++t) {
+        ws[t] = wave_sum(ws[t]);
+        ss[t] = wave_sum(ss[t]);
     }
     if (lane == 0) {
-        seg_ws[sg] = ws;
-        seg_ss[sg] = ss;
+#pragma unroll
+        for (int t = 0; t < QT; ++t) {
+            seg_ws[(int64_t)sg * QT + t] = ws[t];
+            seg_ss[(int64_t)sg * QT + t] = ss[t];
+        }
     }
 }
 
+// thread per (place, query): the place's segments in segment order; output query-major [query][place]
+template <int QT>
 __global__ void lk_sum_segments(const int32_t *place_seg0, int32_t nplaces, const double *seg_ws, const double *seg_ss,
                                 double *out_ws, double *out_ss)
 {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= nplaces) return;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)nplaces * QT) return;
+    const int p = (int)(i / QT), t = (int)(i % QT);
     double ws = 0.0, ss = 0.0;
     for (int sg = place_seg0[p]; sg < place_seg0[p + 1]; ++sg) {
-        ws = ws + seg_ws[sg];
-        ss = ss + seg_ss[sg];
+        ws = ws + seg_ws[(int64_t)sg * QT + t];
+        ss = ss + seg_ss[(int64_t)sg * QT + t];
     }
-    out_ws[p] = ws;
-    out_ss[p] = ss;
+    out_ws[(int64_t)t * nplaces + p] = ws;
+    out_ss[(int64_t)t * nplaces + p] = ss;
 }
 
 // The end of the place-major pass on the device: the places somebody among the neighbours rated (ss > 0), in
 // ascending place order, with est = ws / ss (:67).  This was a host loop over all places after copying ws and ss
-// back - 100 k iterations with a division each, 0.2 ms of a 0.5 ms request at cfg2.  Two small launches: the rated
-// places of every tile of kFinishTile are counted, then every tile writes its rows behind the tiles before it (the
-// prefix over at most a few hundred tile counts is recomputed by each block).
+// back - 100 k iterations with a division each, 0.2 ms of a 0.5 ms request at cfg2.  Two small launches on a grid
+// (tiles, queries): the rated places of every tile of kFinishTile are counted, then every tile writes its rows behind
+// the tiles before it (the prefix over at most a few hundred tile counts is recomputed by each block).
 constexpr int kFinishTile = 2048;  // places per block: 256 threads x 8 consecutive places
 
 __global__ __launch_bounds__(256) void lk_finish_count(const double *ss, int32_t nplaces, int32_t *tile_cnt)
 {
     __shared__ int wsum[4];
+    const double *sq = ss + (int64_t)blockIdx.y * nplaces;
     const int p0 = blockIdx.x * kFinishTile + threadIdx.x * 8;
     int c = 0;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) c += (p0 + i < nplaces && ss[p0 + i] > 0) ? 1 : 0;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) c += __shfl_xor(c, d);
+    for (int i = 0; i < 8; ++i) c += (p0 + i < nplaces && sq[p0 + i] > 0) ? 1 : 0;
+    c = wave_sum(c);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
     __syncthreads();
-    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    if (threadIdx.x == 0) tile_cnt[blockIdx.y * gridDim.x + blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
 }
 
+// where query t's rows begin in the output; < 0: the slot holds no query, nothing is written for it
+template <int QT>
+struct LkBases {
+    int64_t base[QT];
+};
+
+// out_n (with host_n, a pinned word the host reads without a copy): the single request's row count, or null
+template <int QT>
 __global__ __launch_bounds__(256) void lk_finish_emit(const double *ws, const double *ss, int32_t nplaces,
-                                                      const int32_t *tile_cnt, const int64_t *cplace_ids, int64_t *out_place,
-                                                      double *out_est, int64_t *out_n, int64_t *host_n)
+                                                      const int32_t *tile_cnt, const int64_t *cplace_ids,
+                                                      const LkBases<QT> bases, int64_t *out_place, double *out_est,
+                                                      int64_t *out_n, int64_t *host_n)
 {
-    __shared__ int64_t base_s;
+    __shared__ int64_t bsum[4];
     __shared__ int wtot[4];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x, q = blockIdx.y;
+    if (bases.base[q] < 0) return;
+    const double *wq = ws + (int64_t)q * nplaces, *sq = ss + (int64_t)q * nplaces;
+    const int32_t *tc = tile_cnt + q * gridDim.x;
     // rows of the tiles before this one
     int64_t before = 0;
-    for (int i = t; i < (int)blockIdx.x; i += 256) before += tile_cnt[i];
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) before += __shfl_xor(before, d);
-    __shared__ int64_t bsum[4];
-    if (lane == 0) bsum[wave] = before;
+    for (int i = t; i < (int)blockIdx.x; i += 256) before += tc[i];
+    before = wave_sum(before);
+    if ((t & 63) == 0) bsum[t >> 6] = before;
     const int p0 = blockIdx.x * kFinishTile + t * 8;
     bool keep[8];
     int c = 0;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-        keep[i] = p0 + i < nplaces && ss[p0 + i] > 0;
+        keep[i] = p0 + i < nplaces && sq[p0 + i] > 0;
         c += keep[i] ? 1 : 0;
     }
-    // exclusive scan of c over the block: within the wave, then over the four waves
-    int incl = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int v = __shfl_up(incl, d);
-        if (lane >= d) incl += v;
-    }
-    if (lane == 63) wtot[wave] = incl;
-    __syncthreads();
-    if (t == 0) base_s = bsum[0] + bsum[1] + bsum[2] + bsum[3];
-    __syncthreads();
-    int woff = 0;
-    for (int w = 0; w < wave; ++w) woff += wtot[w];
-    int64_t o = base_s + woff + (incl - c);
+    int64_t o = block_scan_256(c, wtot);
+    o += bases.base[q] + bsum[0] + bsum[1] + bsum[2] + bsum[3];
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         if (keep[i]) {
             out_place[o] = cplace_ids[p0 + i];
-            out_est[o] = ws[p0 + i] / ss[p0 + i];  // :67
+            out_est[o] = wq[p0 + i] / sq[p0 + i];  // :67
             ++o;
         }
     }
-    if (blockIdx.x == gridDim.x - 1 && t == 255) {  // the last thread of the last tile knows the total
+    if (out_n && blockIdx.x == gridDim.x - 1 && t == 255) {  // the last thread of the last tile knows the total
         *out_n = o;
         if (host_n) *host_n = o;
     }
@@ -226,6 +272,36 @@ int32_t ensure_segments(locrec_knn_index *ix)
     return LOCREC_OK;
 }
 
+// Enqueues aggregate -> sum -> count over the weights S[row][QT] (at least one place, the segment table built): the
+// segments' sums [seg][QT], the places' sums [query][place] and the rated places of every finish tile [query][tiles]
+template <int QT, int U>
+int32_t enqueue_aggregation(locrec_knn_index *ix, const double *S, double *seg_ws, double *seg_ss, double *ws, double *ss,
+                            int tiles, int32_t *tile_cnt)
+{
+    hipStream_t s = ix->stream;
+    const int32_t np = (int32_t)ix->cplace_ids.size();
+    if (ix->lk_nsegs > 0)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(lk_aggregate_segments<QT, U>), dim3((unsigned)((ix->lk_nsegs + 3) / 4)), dim3(256), 0, s,
+                           ix->lk_seg_begin.p, ix->lk_seg_end.p, ix->lk_nsegs, ix->cp_row.p, ix->cp_rating.p, S, seg_ws, seg_ss);
+    hipLaunchKernelGGL(lk_sum_segments<QT>, dim3((unsigned)(((int64_t)np * QT + 255) / 256)), dim3(256), 0, s,
+                       ix->lk_place_seg0.p, np, seg_ws, seg_ss, ws, ss);
+    hipLaunchKernelGGL(lk_finish_count, dim3((unsigned)tiles, QT), dim3(256), 0, s, ss, np, tile_cnt);
+    LOCREC_HIP_TRY(hipGetLastError());
+    return LOCREC_OK;
+}
+
+// number of candidates (similarity > 0) of the scan that was just enqueued: the total of its histogram
+int32_t candidate_count(locrec_knn_index *ix, int64_t *m)
+{
+    std::vector<uint32_t> hist(kLkHistBins);
+    LOCREC_HIP_TRY(hipMemcpyAsync(hist.data(), ix->hist1.p, hist.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ix->stream));
+    LOCREC_HIP_TRY(hipStreamSynchronize(ix->stream));
+    int64_t total = 0;
+    for (uint32_t h : hist) total += h;
+    *m = total;
+    return LOCREC_OK;
+}
+
 // Sorted (similarity desc, id asc) list of ALL rows in ix->lk_keys_out / lk_vals_out; *m = number of
 // candidates (similarity > 0).
 int32_t sort_all(locrec_knn_index *ix, int32_t qrow, double pw, double cw, int64_t *m, bool scanned = false)
@@ -249,13 +325,7 @@ int32_t sort_all(locrec_knn_index *ix, int32_t qrow, double pw, double cw, int64
                                                                 0, 64, s));
     // number of candidates = histogram total = position of the first zero key: binary search on the host
     // would need the keys; count on the device side instead via the histogram the scan already filled
-    std::vector<uint32_t> hist(4096);  // kHistBins of knn.hip
-    LOCREC_HIP_TRY(hipMemcpyAsync(hist.data(), ix->hist1.p, hist.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    LOCREC_HIP_TRY(hipStreamSynchronize(s));
-    int64_t total = 0;
-    for (uint32_t h : hist) total += h;
-    *m = total;
-    return LOCREC_OK;
+    return candidate_count(ix, m);
 }
 
 // =====================================================================================================
@@ -269,7 +339,7 @@ int32_t sort_all(locrec_knn_index *ix, int32_t qrow, double pw, double cw, int64
 // Dots: every candidate walks its plain CSR row against DENSE query tables qd[index][query] in global memory,
 // sum += qd * value left to right in ascending index order - BLAS.dot's order, a product with an absent query
 // entry adds +-0.0 - so similarities are the reference's bit for bit in EVERY stored format (the GENERIC fp64
-// one included); the sums of the aggregation run in lk_aggregate_segments' order, so a batch's estimates equal
+// one included); the aggregation is the single request's kernels with kLkbQt columns, so a batch's estimates equal
 // the single request's bit for bit.
 constexpr int kLkbQt = 16;
 
@@ -398,144 +468,8 @@ __global__ __launch_bounds__(256) void lkb_scan(const LkbScan P)
     if (threadIdx.x < kLkbQt && s_cand[threadIdx.x]) atomicAdd(&P.cand[threadIdx.x], s_cand[threadIdx.x]);
 }
 
-// lk_aggregate_segments for a tile of queries: one wave per segment of <= kSegRaters raters of a place, lane l takes
-// raters l, l + 64, ... in ascending order (the single request's order), one 128-byte line of S per rater
-__global__ __launch_bounds__(256) void lkb_aggregate_segments(const int64_t *seg_begin, const int64_t *seg_end, int32_t nsegs,
-                                                              const int32_t *cp_row, const double *cp_rating, const double *S,
-                                                              double *seg_ws, double *seg_ss)
-{
-    const int lane = threadIdx.x & 63;
-    const int sg = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (sg >= nsegs) return;
-    double ws[kLkbQt], ss[kLkbQt];
-#pragma unroll
-    for (int t = 0; t < kLkbQt; ++t) ws[t] = ss[t] = 0.0;
-    const int64_t end = seg_end[sg];
-    for (int64_t e0 = seg_begin[sg] + lane; e0 < end; e0 += 64 * 2) {
-        int32_t rr[2];
-        double rt[2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int64_t e = e0 + 64 * u;
-            rr[u] = e < end ? cp_row[e] : -1;
-            rt[u] = e < end ? cp_rating[e] : 0.0;
-        }
-        double sv[2][kLkbQt];
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int t = 0; t < kLkbQt; ++t) sv[u][t] = rr[u] >= 0 ? S[(int64_t)rr[u] * kLkbQt + t] : 0.0;
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int t = 0; t < kLkbQt; ++t)
-                if (sv[u][t] > 0) {
-                    const double wr = rt[u] * sv[u][t];  // col("rating") * col("similarity") (:59)
-                    ws[t] = ws[t] + wr;
-                    ss[t] = ss[t] + sv[u][t];
-                }
-    }
-#pragma unroll
-    for (int t = 0; t < kLkbQt; ++t) {
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            ws[t] = ws[t] + __shfl_xor(ws[t], d);
-            ss[t] = ss[t] + __shfl_xor(ss[t], d);
-        }
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int t = 0; t < kLkbQt; ++t) {
-            seg_ws[(int64_t)sg * kLkbQt + t] = ws[t];
-            seg_ss[(int64_t)sg * kLkbQt + t] = ss[t];
-        }
-    }
-}
-
-// thread per (place, query): the place's segments in segment order; output query-major [query][place]
-__global__ void lkb_sum_segments(const int32_t *place_seg0, int32_t nplaces, const double *seg_ws, const double *seg_ss,
-                                 double *out_ws, double *out_ss)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)nplaces * kLkbQt) return;
-    const int p = (int)(i / kLkbQt), t = (int)(i % kLkbQt);
-    double ws = 0.0, ss = 0.0;
-    for (int sg = place_seg0[p]; sg < place_seg0[p + 1]; ++sg) {
-        ws = ws + seg_ws[(int64_t)sg * kLkbQt + t];
-        ss = ss + seg_ss[(int64_t)sg * kLkbQt + t];
-    }
-    out_ws[(int64_t)t * nplaces + p] = ws;
-    out_ss[(int64_t)t * nplaces + p] = ss;
-}
-
-struct LkbBases {
-    int64_t base[kLkbQt];
-};
-
-// the single request's lk_finish_count / lk_finish_emit per query of the tile: grid (tiles, kLkbQt)
-__global__ __launch_bounds__(256) void lkb_finish_count(const double *ss, int32_t nplaces, int32_t tiles, int32_t *tile_cnt)
-{
-    __shared__ int wsum[4];
-    const double *sq = ss + (int64_t)blockIdx.y * nplaces;
-    const int p0 = blockIdx.x * kFinishTile + threadIdx.x * 8;
-    int c = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) c += (p0 + i < nplaces && sq[p0 + i] > 0) ? 1 : 0;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) c += __shfl_xor(c, d);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) tile_cnt[blockIdx.y * tiles + blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-}
-
-__global__ __launch_bounds__(256) void lkb_finish_emit(const double *ws, const double *ss, int32_t nplaces, int32_t tiles,
-                                                       const int32_t *tile_cnt, const int64_t *cplace_ids, const LkbBases bases,
-                                                       int64_t *out_place, double *out_est)
-{
-    __shared__ int64_t bsum[4];
-    __shared__ int wtot[4];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, q = blockIdx.y;
-    if (bases.base[q] < 0) return;
-    const double *wq = ws + (int64_t)q * nplaces, *sq = ss + (int64_t)q * nplaces;
-    const int32_t *tc = tile_cnt + q * tiles;
-    int64_t before = 0;
-    for (int i = t; i < (int)blockIdx.x; i += 256) before += tc[i];
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) before += __shfl_xor(before, d);
-    if (lane == 0) bsum[wave] = before;
-    const int p0 = blockIdx.x * kFinishTile + t * 8;
-    bool keep[8];
-    int c = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        keep[i] = p0 + i < nplaces && sq[p0 + i] > 0;
-        c += keep[i] ? 1 : 0;
-    }
-    int incl = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int v = __shfl_up(incl, d);
-        if (lane >= d) incl += v;
-    }
-    if (lane == 63) wtot[wave] = incl;
-    __syncthreads();
-    int woff = 0;
-    for (int w = 0; w < wave; ++w) woff += wtot[w];
-    int64_t o = bases.base[q] + bsum[0] + bsum[1] + bsum[2] + bsum[3] + woff + (incl - c);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        if (keep[i]) {
-            out_place[o] = cplace_ids[p0 + i];
-            out_est[o] = wq[p0 + i] / sq[p0 + i];  // :67
-            ++o;
-        }
-    }
-}
-
 // the histogram of one query's column of a TRANSPOSED tile (what knn_select1 of knn.hip reads; knn_collect1 then
 // reads the column itself): how a batch serves the few queries that cannot ride a packed tile
-constexpr int kLkHistBins = 4096;  // kHistBins of knn.hip
-
 __global__ __launch_bounds__(256) void lkb_column_hist(const double *col, int32_t nrows, uint32_t *hist)
 {
     __shared__ uint32_t s_hist[kLkHistBins];
@@ -609,18 +543,9 @@ static int32_t aggregate_places(locrec_knn_index *ix, const double *w, int64_t *
     LOCREC_TRY(ix->lk_ws.reserve((size_t)np));
     LOCREC_TRY(ix->lk_ss.reserve((size_t)np));
     LOCREC_TRY(ensure_segments(ix));
-    if (np > 0) {
-        if (ix->lk_nsegs > 0)
-            hipLaunchKernelGGL(lk_aggregate_segments, dim3((unsigned)((ix->lk_nsegs + 3) / 4)), dim3(256), 0, s, ix->lk_seg_begin.p,
-                               ix->lk_seg_end.p, ix->lk_nsegs, ix->cp_row.p, ix->cp_rating.p, w, ix->lk_seg_ws.p, ix->lk_seg_ss.p);
-        hipLaunchKernelGGL(lk_sum_segments, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, ix->lk_place_seg0.p, np,
-                           ix->lk_seg_ws.p, ix->lk_seg_ss.p, ix->lk_ws.p, ix->lk_ss.p);
-    }
-    LOCREC_HIP_TRY(hipGetLastError());
     const int64_t cap = *inout_count;
     int64_t outn = 0;
     if (np > 0) {
-        // the rated places, compacted in ascending order, with their estimates: on the device (lk_finish_*)
         const int tiles = (np + kFinishTile - 1) / kFinishTile;
         LOCREC_TRY(ix->lk_tile_cnt.reserve((size_t)tiles));
         LOCREC_TRY(ix->lk_out_place.reserve((size_t)np));
@@ -631,9 +556,11 @@ static int32_t aggregate_places(locrec_knn_index *ix, const double *w, int64_t *
             pinned_n = reinterpret_cast<int64_t *>(ix->h_stage);
             pinned_n_dev = reinterpret_cast<int64_t *>(ix->h_stage_dev);
         }
-        hipLaunchKernelGGL(lk_finish_count, dim3((unsigned)tiles), dim3(256), 0, s, ix->lk_ss.p, np, ix->lk_tile_cnt.p);
-        hipLaunchKernelGGL(lk_finish_emit, dim3((unsigned)tiles), dim3(256), 0, s, ix->lk_ws.p, ix->lk_ss.p, np, ix->lk_tile_cnt.p,
-                           ix->cplace_dev.p, ix->lk_out_place.p, ix->lk_out_est.p, ix->lk_out_n.p, pinned_n_dev);
+        LOCREC_TRY((enqueue_aggregation<1, 8>(ix, w, ix->lk_seg_ws.p, ix->lk_seg_ss.p, ix->lk_ws.p, ix->lk_ss.p, tiles,
+                                              ix->lk_tile_cnt.p)));
+        // the rated places, compacted in ascending order, with their estimates and their number
+        hipLaunchKernelGGL(lk_finish_emit<1>, dim3((unsigned)tiles), dim3(256), 0, s, ix->lk_ws.p, ix->lk_ss.p, np, ix->lk_tile_cnt.p,
+                           ix->cplace_dev.p, LkBases<1>{}, ix->lk_out_place.p, ix->lk_out_est.p, ix->lk_out_n.p, pinned_n_dev);
         LOCREC_HIP_TRY(hipGetLastError());
         if (!pinned_n) LOCREC_HIP_TRY(hipMemcpyAsync(&outn, ix->lk_out_n.p, 8, hipMemcpyDeviceToHost, s));
         LOCREC_HIP_TRY(hipStreamSynchronize(s));
@@ -657,18 +584,6 @@ int32_t knn_large_aggregate(locrec_knn_index *ix, const double *w_host, int64_t 
     LOCREC_HIP_TRY(hipMemcpyAsync(ix->lk_w.p, w_host, (size_t)ix->n * sizeof(double), hipMemcpyHostToDevice, ix->stream));
     LOCREC_HIP_TRY(hipStreamSynchronize(ix->stream));  // w_host may be freed by the caller
     return aggregate_places(ix, ix->lk_w.p, out_places, out_ratings, inout_count);
-}
-
-// number of candidates (similarity > 0) of the scan that was just enqueued: the total of its histogram
-static int32_t candidate_count(locrec_knn_index *ix, int64_t *m)
-{
-    std::vector<uint32_t> hist(4096);  // kHistBins of knn.hip
-    LOCREC_HIP_TRY(hipMemcpyAsync(hist.data(), ix->hist1.p, hist.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ix->stream));
-    LOCREC_HIP_TRY(hipStreamSynchronize(ix->stream));
-    int64_t total = 0;
-    for (uint32_t h : hist) total += h;
-    *m = total;
-    return LOCREC_OK;
 }
 
 int32_t knn_large_recommend(locrec_knn_index *ix, int32_t qrow, double pw, double cw, int64_t k,
@@ -696,10 +611,6 @@ int32_t knn_large_recommend(locrec_knn_index *ix, int32_t qrow, double pw, doubl
 
 namespace locrec {
 
-// makeRecommendations for the persons at the internal rows rows[0 .. nq) with K >= the number of other persons
-// ("every positive-similarity person is a neighbour").  Results stay on the device: ix->lkb_place / lkb_est, rows
-// of query i at [lkb_off[i], lkb_off[i + 1]) ordered by place id.  A row that is not a valid query (an empty place
-// or category vector: KnnRecommender.scala:77-83 throws for it) gets no rows.
 // the presence bitmap of the place table lives behind the table itself (kLkbBitmapBits bits, zero between tiles)
 static void lkb_bitmap_of(locrec_knn_index *ix, uint32_t **bits, uint32_t *mask)
 {
@@ -709,14 +620,12 @@ static void lkb_bitmap_of(locrec_knn_index *ix, uint32_t **bits, uint32_t *mask)
     *mask = nbits - 1u;
 }
 
-// the workspaces of a batched recommendation (grow-only, kept with the handle)
-static int32_t lkb_reserve(locrec_knn_index *ix, int tiles)
+// the workspaces of a tile scan (lazy, kept with the handle): the tile, the dense query tables (all zero between
+// tiles) and the candidate counters
+static int32_t lkb_scan_workspaces(locrec_knn_index *ix)
 {
     hipStream_t s = ix->stream;
-    const int32_t n = (int32_t)ix->n;
-    const int32_t np = (int32_t)ix->cplace_ids.size();
-    LOCREC_TRY(ensure_segments(ix));
-    LOCREC_TRY(ix->lkb_S.reserve((size_t)n * kLkbQt));
+    LOCREC_TRY(ix->lkb_S.reserve((size_t)ix->n * kLkbQt));
     if (!ix->lkb_qd_p.p) {
         LOCREC_TRY(ix->lkb_qd_p.alloc((size_t)std::max(1, ix->fp.dim) * kLkbQt + kLkbBitmapBits / 64));  // (+ the presence bitmap)
         LOCREC_TRY(ix->lkb_qd_c.alloc((size_t)std::max(1, ix->fc.dim) * kLkbQt));
@@ -724,11 +633,82 @@ static int32_t lkb_reserve(locrec_knn_index *ix, int tiles)
         LOCREC_HIP_TRY(hipMemsetAsync(ix->lkb_qd_c.p, 0, ix->lkb_qd_c.bytes(), s));
     }
     LOCREC_TRY(ix->lkb_cand.reserve(kLkbQt));
+    return LOCREC_OK;
+}
+
+// the workspaces of a batched recommendation (grow-only, kept with the handle)
+static int32_t lkb_reserve(locrec_knn_index *ix, int tiles)
+{
+    const int32_t np = (int32_t)ix->cplace_ids.size();
+    LOCREC_TRY(ensure_segments(ix));
+    LOCREC_TRY(lkb_scan_workspaces(ix));
     LOCREC_TRY(ix->lkb_seg_ws.reserve((size_t)std::max(1, ix->lk_nsegs) * kLkbQt));
     LOCREC_TRY(ix->lkb_seg_ss.reserve((size_t)std::max(1, ix->lk_nsegs) * kLkbQt));
     LOCREC_TRY(ix->lkb_ws.reserve((size_t)std::max(1, np) * kLkbQt));
     LOCREC_TRY(ix->lkb_ss.reserve((size_t)std::max(1, np) * kLkbQt));
     LOCREC_TRY(ix->lkb_tile_cnt.reserve((size_t)tiles * kLkbQt));
+    return LOCREC_OK;
+}
+
+// the up to kLkbQt query rows of a tile; a person without a place or category vector is no query (-1)
+static int lkt_tile_rows(const locrec_knn_index *ix, const int32_t *rows, int64_t nq, int64_t q0, int32_t *tr, bool *invalid)
+{
+    const int nt = (int)std::min<int64_t>(kLkbQt, nq - q0);
+    for (int t = 0; t < kLkbQt; ++t) {
+        const int32_t r = t < nt ? rows[q0 + t] : -1;
+        invalid[t] = t < nt && (r < 0 || ix->fp.nnz[(size_t)r] == 0 || ix->fc.nnz[(size_t)r] == 0);
+        tr[t] = invalid[t] ? -1 : r;
+    }
+    return nt;
+}
+
+// One tile of the scan: the similarities of the queries rows[0 .. nt) against every row -> ix->lkb_S, [row][kLkbQt] or
+// transposed [kLkbQt][row] (dense fp64 query tables, every candidate walks its plain CSR row: exact in every stored
+// format and for every row, wide ones included).  The queries' vectors are scattered into the dense tables, lkb_scan
+// runs, the tables are wiped for the next tile.
+static int32_t lkb_scan_tile(locrec_knn_index *ix, const int32_t *rows, int nt, double pw, double cw, bool transposed, bool profiled)
+{
+    hipStream_t s = ix->stream;
+    const int32_t n = (int32_t)ix->n;
+    LkbScan P{};
+    LkbFill fp{}, fc{};
+    bool invalid[kLkbQt];
+    lkt_tile_rows(ix, rows, nt, 0, P.qrow, invalid);
+    int maxp = 1, maxc = 1;
+    for (int t = 0; t < kLkbQt; ++t) {
+        const int32_t r = fp.qrow[t] = fc.qrow[t] = P.qrow[t];
+        if (r >= 0) {
+            maxp = std::max(maxp, ix->fp.nnz[(size_t)r]);
+            maxc = std::max(maxc, ix->fc.nnz[(size_t)r]);
+        }
+    }
+    fp.ptr = ix->fp.csr_ptr.p; fp.idx = ix->fp.csr_idx.p; fp.val = ix->fp.csr_val.p; fp.qd = ix->lkb_qd_p.p;
+    lkb_bitmap_of(ix, &fp.bits, &fp.bit_mask);
+    P.bits = fp.bits;
+    P.bit_mask = fp.bit_mask;
+    fc.ptr = ix->fc.csr_ptr.p; fc.idx = ix->fc.csr_idx.p; fc.val = ix->fc.csr_val.p; fc.qd = ix->lkb_qd_c.p;
+    const dim3 gp((unsigned)((maxp + 255) / 256), kLkbQt), gc((unsigned)((maxc + 255) / 256), kLkbQt);
+    fp.set = fc.set = 1;
+    hipLaunchKernelGGL(lkb_fill, gp, dim3(256), 0, s, fp);
+    hipLaunchKernelGGL(lkb_fill, gc, dim3(256), 0, s, fc);
+    P.p_ptr = ix->fp.csr_ptr.p; P.p_idx = ix->fp.csr_idx.p; P.p_val = ix->fp.csr_val.p;
+    P.c_ptr = ix->fc.csr_ptr.p; P.c_idx = ix->fc.csr_idx.p; P.c_val = ix->fc.csr_val.p;
+    P.norm_p = ix->fp.norm.p; P.norm_c = ix->fc.norm.p;
+    P.qd_p = ix->lkb_qd_p.p; P.qd_c = ix->lkb_qd_c.p;
+    P.nrows = n;
+    P.pw = pw; P.cw = cw;
+    P.S = ix->lkb_S.p;
+    P.cand = ix->lkb_cand.p;
+    P.transposed = transposed ? 1 : 0;
+    LOCREC_HIP_TRY(hipMemsetAsync(ix->lkb_cand.p, 0, kLkbQt * sizeof(int32_t), s));
+    const dim3 grid((unsigned)((n + 255) / 256));
+    const size_t lds = (P.bit_mask + 1u) / 8u;
+    if (profiled) LOCREC_LAUNCH_PROFILED(ix->prof, lkb_scan, grid, dim3(256), lds, s, P);
+    else hipLaunchKernelGGL(lkb_scan, grid, dim3(256), lds, s, P);
+    fp.set = fc.set = 0;  // the dense tables go back to all zero for the next tile
+    hipLaunchKernelGGL(lkb_fill, gp, dim3(256), 0, s, fp);
+    hipLaunchKernelGGL(lkb_fill, gc, dim3(256), 0, s, fc);
+    LOCREC_HIP_TRY(hipGetLastError());
     return LOCREC_OK;
 }
 
@@ -741,18 +721,11 @@ static int32_t lkb_aggregate_tile(locrec_knn_index *ix, const double *S, const i
     hipStream_t s = ix->stream;
     const int32_t np = (int32_t)ix->cplace_ids.size();
     if (np > 0) {
-        if (ix->lk_nsegs > 0)
-            hipLaunchKernelGGL(lkb_aggregate_segments, dim3((unsigned)((ix->lk_nsegs + 3) / 4)), dim3(256), 0, s,
-                               ix->lk_seg_begin.p, ix->lk_seg_end.p, ix->lk_nsegs, ix->cp_row.p, ix->cp_rating.p,
-                               S, ix->lkb_seg_ws.p, ix->lkb_seg_ss.p);
-        hipLaunchKernelGGL(lkb_sum_segments, dim3((unsigned)(((int64_t)np * kLkbQt + 255) / 256)), dim3(256), 0, s,
-                           ix->lk_place_seg0.p, np, ix->lkb_seg_ws.p, ix->lkb_seg_ss.p, ix->lkb_ws.p, ix->lkb_ss.p);
-        hipLaunchKernelGGL(lkb_finish_count, dim3((unsigned)tiles, kLkbQt), dim3(256), 0, s, ix->lkb_ss.p, np, tiles,
-                           ix->lkb_tile_cnt.p);
-        LOCREC_HIP_TRY(hipGetLastError());
+        LOCREC_TRY((enqueue_aggregation<kLkbQt, 2>(ix, S, ix->lkb_seg_ws.p, ix->lkb_seg_ss.p, ix->lkb_ws.p, ix->lkb_ss.p, tiles,
+                                                   ix->lkb_tile_cnt.p)));
         LOCREC_HIP_TRY(hipMemcpyAsync(tc.data(), ix->lkb_tile_cnt.p, tc.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         LOCREC_HIP_TRY(hipStreamSynchronize(s));
-        LkbBases B{};
+        LkBases<kLkbQt> B{};
         for (int t = 0; t < kLkbQt; ++t) {
             int64_t c = 0;
             if (t < nt && qrow[t] >= 0)
@@ -779,8 +752,9 @@ static int32_t lkb_aggregate_tile(locrec_knn_index *ix, const double *S, const i
             std::swap(ix->lkb_place.p, np_buf.p); std::swap(ix->lkb_place.n, np_buf.n);
             std::swap(ix->lkb_est.p, ne_buf.p); std::swap(ix->lkb_est.n, ne_buf.n);
         }
-        hipLaunchKernelGGL(lkb_finish_emit, dim3((unsigned)tiles, kLkbQt), dim3(256), 0, s, ix->lkb_ws.p, ix->lkb_ss.p, np,
-                           tiles, ix->lkb_tile_cnt.p, ix->cplace_dev.p, B, ix->lkb_place.p, ix->lkb_est.p);
+        hipLaunchKernelGGL(lk_finish_emit<kLkbQt>, dim3((unsigned)tiles, kLkbQt), dim3(256), 0, s, ix->lkb_ws.p, ix->lkb_ss.p, np,
+                           ix->lkb_tile_cnt.p, ix->cplace_dev.p, B, ix->lkb_place.p, ix->lkb_est.p, (int64_t *)nullptr,
+                           (int64_t *)nullptr);
         LOCREC_HIP_TRY(hipGetLastError());
     } else {
         for (int t = 0; t < nt; ++t) ix->lkb_off[(size_t)(q0 + t)] = total;
@@ -788,10 +762,12 @@ static int32_t lkb_aggregate_tile(locrec_knn_index *ix, const double *S, const i
     return LOCREC_OK;
 }
 
+// makeRecommendations for the persons at the internal rows rows[0 .. nq) with K >= the number of other persons
+// ("every positive-similarity person is a neighbour").  Results stay on the device: ix->lkb_place / lkb_est, rows
+// of query i at [lkb_off[i], lkb_off[i + 1]) ordered by place id.  A row that is not a valid query (an empty place
+// or category vector: KnnRecommender.scala:77-83 throws for it) gets no rows.
 int32_t knn_large_recommend_batch(locrec_knn_index *ix, const int32_t *rows, int64_t nq, double pw, double cw)
 {
-    hipStream_t s = ix->stream;
-    const int32_t n = (int32_t)ix->n;
     const int32_t np = (int32_t)ix->cplace_ids.size();
     ix->have_lkb = false;
     ix->lkb_off.assign((size_t)nq + 1, 0);
@@ -800,103 +776,23 @@ int32_t knn_large_recommend_batch(locrec_knn_index *ix, const int32_t *rows, int
     std::vector<int32_t> tc((size_t)tiles * kLkbQt);
     int64_t total = 0;
     for (int64_t q0 = 0; q0 < nq; q0 += kLkbQt) {
-        const int nt = (int)std::min<int64_t>(kLkbQt, nq - q0);
-        LkbScan P{};
-        LkbFill fp{}, fc{};
-        int maxp = 1, maxc = 1;
-        for (int t = 0; t < kLkbQt; ++t) {
-            int32_t r = t < nt ? rows[q0 + t] : -1;
-            if (r >= 0 && (ix->fp.nnz[(size_t)r] == 0 || ix->fc.nnz[(size_t)r] == 0)) r = -1;  // not a valid query
-            P.qrow[t] = fp.qrow[t] = fc.qrow[t] = r;
-            if (r >= 0) {
-                maxp = std::max(maxp, ix->fp.nnz[(size_t)r]);
-                maxc = std::max(maxc, ix->fc.nnz[(size_t)r]);
-            }
-        }
-        fp.ptr = ix->fp.csr_ptr.p; fp.idx = ix->fp.csr_idx.p; fp.val = ix->fp.csr_val.p; fp.qd = ix->lkb_qd_p.p;
-        lkb_bitmap_of(ix, &fp.bits, &fp.bit_mask);
-        P.bits = fp.bits;
-        P.bit_mask = fp.bit_mask;
-        fc.ptr = ix->fc.csr_ptr.p; fc.idx = ix->fc.csr_idx.p; fc.val = ix->fc.csr_val.p; fc.qd = ix->lkb_qd_c.p;
-        const dim3 gp((unsigned)((maxp + 255) / 256), kLkbQt), gc((unsigned)((maxc + 255) / 256), kLkbQt);
-        fp.set = fc.set = 1;
-        hipLaunchKernelGGL(lkb_fill, gp, dim3(256), 0, s, fp);
-        hipLaunchKernelGGL(lkb_fill, gc, dim3(256), 0, s, fc);
-        P.p_ptr = ix->fp.csr_ptr.p; P.p_idx = ix->fp.csr_idx.p; P.p_val = ix->fp.csr_val.p;
-        P.c_ptr = ix->fc.csr_ptr.p; P.c_idx = ix->fc.csr_idx.p; P.c_val = ix->fc.csr_val.p;
-        P.norm_p = ix->fp.norm.p; P.norm_c = ix->fc.norm.p;
-        P.qd_p = ix->lkb_qd_p.p; P.qd_c = ix->lkb_qd_c.p;
-        P.nrows = n;
-        P.pw = pw; P.cw = cw;
-        P.S = ix->lkb_S.p;
-        P.cand = ix->lkb_cand.p;
-        LOCREC_HIP_TRY(hipMemsetAsync(ix->lkb_cand.p, 0, kLkbQt * sizeof(int32_t), s));
-        LOCREC_LAUNCH_PROFILED(ix->prof, lkb_scan, dim3((unsigned)((n + 255) / 256)), dim3(256), (P.bit_mask + 1u) / 8u, s, P);
-        fp.set = fc.set = 0;  // the dense tables go back to all zero for the next tile
-        hipLaunchKernelGGL(lkb_fill, gp, dim3(256), 0, s, fp);
-        hipLaunchKernelGGL(lkb_fill, gc, dim3(256), 0, s, fc);
-        LOCREC_TRY(lkb_aggregate_tile(ix, ix->lkb_S.p, P.qrow, q0, nt, tiles, tc, total));
+        int32_t tr[kLkbQt];
+        bool invalid[kLkbQt];
+        const int nt = lkt_tile_rows(ix, rows, nq, q0, tr, invalid);
+        LOCREC_TRY(lkb_scan_tile(ix, tr, nt, pw, cw, false, true));
+        LOCREC_TRY(lkb_aggregate_tile(ix, ix->lkb_S.p, tr, q0, nt, tiles, tc, total));
     }
     ix->lkb_off[(size_t)nq] = total;
     ix->have_lkb = true;
     return LOCREC_OK;
 }
 
-}  // namespace locrec
-
-namespace locrec {
-
-// The similarities of up to kLkbQt (16) queries against every row -> ix->lkb_S[row][16] (dense fp64 query tables, every
-// candidate walks its plain CSR row: exact in every stored format and for every row, wide ones included).
+// The tile scan for the selection kernels: transposed, one contiguous column per query
 int32_t knn_large_scan_tile(locrec_knn_index *ix, const int32_t *rows, int nt, double pw, double cw)
 {
-    hipStream_t s = ix->stream;
-    const int32_t n = (int32_t)ix->n;
     if (nt < 1 || nt > kLkbQt) return fail(LOCREC_E_INVALID_ARG, "a tile holds 1 .. %d queries", kLkbQt);
-    LOCREC_TRY(ix->lkb_S.reserve((size_t)n * kLkbQt));
-    if (!ix->lkb_qd_p.p) {
-        LOCREC_TRY(ix->lkb_qd_p.alloc((size_t)std::max(1, ix->fp.dim) * kLkbQt + kLkbBitmapBits / 64));  // (+ the presence bitmap)
-        LOCREC_TRY(ix->lkb_qd_c.alloc((size_t)std::max(1, ix->fc.dim) * kLkbQt));
-        LOCREC_HIP_TRY(hipMemsetAsync(ix->lkb_qd_p.p, 0, ix->lkb_qd_p.bytes(), s));
-        LOCREC_HIP_TRY(hipMemsetAsync(ix->lkb_qd_c.p, 0, ix->lkb_qd_c.bytes(), s));
-    }
-    LOCREC_TRY(ix->lkb_cand.reserve(kLkbQt));
-    LkbScan P{};
-    LkbFill fp{}, fc{};
-    int maxp = 1, maxc = 1;
-    for (int t = 0; t < kLkbQt; ++t) {
-        int32_t r = t < nt ? rows[t] : -1;
-        if (r >= 0 && (ix->fp.nnz[(size_t)r] == 0 || ix->fc.nnz[(size_t)r] == 0)) r = -1;
-        P.qrow[t] = fp.qrow[t] = fc.qrow[t] = r;
-        if (r >= 0) {
-            maxp = std::max(maxp, ix->fp.nnz[(size_t)r]);
-            maxc = std::max(maxc, ix->fc.nnz[(size_t)r]);
-        }
-    }
-    fp.ptr = ix->fp.csr_ptr.p; fp.idx = ix->fp.csr_idx.p; fp.val = ix->fp.csr_val.p; fp.qd = ix->lkb_qd_p.p;
-    lkb_bitmap_of(ix, &fp.bits, &fp.bit_mask);
-    P.bits = fp.bits;
-    P.bit_mask = fp.bit_mask;
-    fc.ptr = ix->fc.csr_ptr.p; fc.idx = ix->fc.csr_idx.p; fc.val = ix->fc.csr_val.p; fc.qd = ix->lkb_qd_c.p;
-    const dim3 gp((unsigned)((maxp + 255) / 256), kLkbQt), gc((unsigned)((maxc + 255) / 256), kLkbQt);
-    fp.set = fc.set = 1;
-    hipLaunchKernelGGL(lkb_fill, gp, dim3(256), 0, s, fp);
-    hipLaunchKernelGGL(lkb_fill, gc, dim3(256), 0, s, fc);
-    P.p_ptr = ix->fp.csr_ptr.p; P.p_idx = ix->fp.csr_idx.p; P.p_val = ix->fp.csr_val.p;
-    P.c_ptr = ix->fc.csr_ptr.p; P.c_idx = ix->fc.csr_idx.p; P.c_val = ix->fc.csr_val.p;
-    P.norm_p = ix->fp.norm.p; P.norm_c = ix->fc.norm.p;
-    P.qd_p = ix->lkb_qd_p.p; P.qd_c = ix->lkb_qd_c.p;
-    P.nrows = n;
-    P.pw = pw; P.cw = cw;
-    P.S = ix->lkb_S.p;
-    P.cand = ix->lkb_cand.p;
-    P.transposed = 1;
-    LOCREC_HIP_TRY(hipMemsetAsync(ix->lkb_cand.p, 0, kLkbQt * sizeof(int32_t), s));
-    hipLaunchKernelGGL(lkb_scan, dim3((unsigned)((n + 255) / 256)), dim3(256), (P.bit_mask + 1u) / 8u, s, P);
-    fp.set = fc.set = 0;  // the dense tables go back to all zero
-    hipLaunchKernelGGL(lkb_fill, gp, dim3(256), 0, s, fp);
-    hipLaunchKernelGGL(lkb_fill, gc, dim3(256), 0, s, fc);
-    LOCREC_HIP_TRY(hipGetLastError());
+    LOCREC_TRY(lkb_scan_workspaces(ix));
+    LOCREC_TRY(lkb_scan_tile(ix, rows, nt, pw, cw, true, false));
     ix->have_lkb = false;  // (a resident large-K batch shares these workspaces)
     return LOCREC_OK;
 }
@@ -929,10 +825,10 @@ int32_t knn_large_tile_hists(locrec_knn_index *ix, int nt, uint32_t *hist, const
 //                        until one run per column is left: its first min(K, candidates) entries are the column's top-K
 //   lkt_emit             -> the query's result slot (ids, similarities, rows, count), padded with (-1, 0.0, -1)
 //   lkt_mask_rows        (recommendations) S masked to each column's selected set, written row-major [row][kLkbQt] for
-//                        lkb_aggregate_segments: one 128-byte line per rater, the order of the single request's sums
+//                        lk_aggregate_segments<kLkbQt, 2>: one 128-byte line per rater, the single request's kernels
 // The order is (similarity desc, id rank asc), a total order: the result does not depend on the order in which the
 // collect's atomics fill a segment, and a tie group of any size needs no special case.  No library sort, no host loop
-// over queries.  VGPRs (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): lkt_select 12, lkt_collect 14,
+// over queries.  VGPRs (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): lkt_select 12, lkt_collect 16,
 // lkt_sort_runs 19 (96 KB dynamic LDS), lkt_merge_pass 32, lkt_emit 14, lkt_mask_rows 40; no scratch.
 namespace {
 
@@ -1021,7 +917,6 @@ __global__ __launch_bounds__(256) void lkt_collect(const double *S, int32_t nrow
     const int t = blockIdx.y;
     const double *col = S + (size_t)t * nrows;
     const int64_t row0 = (int64_t)blockIdx.x * 256 * per + threadIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int bin = T.bin[t];
     int c = 0;
     for (int i = 0; i < per; ++i) {
@@ -1031,22 +926,14 @@ __global__ __launch_bounds__(256) void lkt_collect(const double *S, int32_t nrow
             c += s > 0 && lkt_bin(s) >= bin ? 1 : 0;
         }
     }
-    int incl = c;  // inclusive scan within the wave, then over the four waves
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int v = __shfl_up(incl, d);
-        if (lane >= d) incl += v;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
+    int pos = block_scan_256(c, s_wave);
     if (threadIdx.x == 0) {
         const int tot = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
         s_base = tot ? atomicAdd(&sel[t * 8 + 3], tot) : 0;
     }
     __syncthreads();
     if (c == 0) return;
-    int pos = s_base + (incl - c);
-    for (int w = 0; w < wave; ++w) pos += s_wave[w];
+    pos += s_base;
     for (int i = 0; i < per; ++i) {
         const int64_t row = row0 + (int64_t)i * 256;
         if (row < nrows) {
@@ -1256,18 +1143,6 @@ static int32_t lkt_topk_tile(locrec_knn_index *ix, int nt, int64_t K, LktTile &T
     *keys = k0;
     *vals = v0;
     return LOCREC_OK;
-}
-
-// the up to kLkbQt query rows of a tile; a person without a place or category vector is no query (-1)
-static int lkt_tile_rows(const locrec_knn_index *ix, const int32_t *rows, int64_t nq, int64_t q0, int32_t *tr, bool *invalid)
-{
-    const int nt = (int)std::min<int64_t>(kLkbQt, nq - q0);
-    for (int t = 0; t < kLkbQt; ++t) {
-        const int32_t r = t < nt ? rows[q0 + t] : -1;
-        invalid[t] = t < nt && (r < 0 || ix->fp.nnz[(size_t)r] == 0 || ix->fc.nnz[(size_t)r] == 0);
-        tr[t] = invalid[t] ? -1 : r;
-    }
-    return nt;
 }
 
 int32_t knn_topk_tiled(locrec_knn_index *ix, const int32_t *rows, int64_t nq, double pw, double cw, int64_t k, bool mark_absent)

@@ -194,6 +194,26 @@ def test_aggregation_segments_and_finish_tiles(main):
         check_recommend(main, [rows[j] for j in order], lc.HALF, 8193)
 
 
+def test_host_given_neighbours_on_the_same_limits(main):
+    """The third caller of the place-major aggregation: weights given on the host (recommend_neighbours with more than
+    1,024 neighbours -> knn_large_aggregate).  The query of test_aggregation_segments_and_finish_tiles at K = 16,384 -
+    all 16,384 candidates, so every limit place keeps all of its 4,095 .. 8,193 raters - has
+    its neighbour list taken from `query` and handed back.  Catches: a host-weights path that sums in another order or
+    misses a segment or the one-place finish tile where the request itself does not (places and estimates must equal
+    `recommend` at the same K bit for bit), and a count or rows that the single-column kernels lose."""
+    _, meta = lc.main_index()
+    q, k = meta["query"][lc.AGG_FAMILY], 16384
+    pid = int(main.d["person_ids"][q])
+    ids, sims = main.ix.query(pid, 0.5, 0.5, k)
+    assert len(ids) == k > 1024
+    places, est = main.ix.recommend_neighbours(ids, sims)
+    rplaces, rest = main.ix.recommend(pid, 0.5, 0.5, k)
+    assert np.array_equal(places, rplaces) and np.array_equal(est, rest), "not the single request's bits"
+    op, oe = main.recommend(q, lc.HALF, k)
+    assert np.array_equal(places, op), "places differ from the oracle"
+    np.testing.assert_allclose(est, oe, rtol=RTOL, atol=0)
+
+
 def small_rows(d, pids):
     at = {int(p): r for r, p in enumerate(d["person_ids"])}
     return np.array([at[int(p)] for p in pids])
