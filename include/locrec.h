@@ -546,6 +546,41 @@ int32_t locrec_sg_group_iterate_async(locrec_sg_group *group, const int64_t *ver
                                       int64_t max_iterations);
 int32_t locrec_sg_group_synchronize(locrec_sg_group *group);
 
+/*
+ * A pool of resident graphs that serves ONE mixed batch of (graph, vertex) requests - the queue of
+ * StochasticRecommenderMain's loop, whose lines fan out over the graphs of sorted{home, target}
+ * (StochasticRecommenderMain.scala:53-62) - with every graph's current tile of up to 16 targets sharing the
+ * launches of a round: per tile wave one set-up launch and one read-back, per round one sweep launch per layout
+ * class present (column width x weight form: at most four, one for a pool of one kind) and one finalize launch,
+ * on the pool's own stream.
+ * create: 1 .. 65535 distinct graphs on one device; the pool does not own them: destroy it before them.  Refused
+ * (LOCREC_E_INVALID_ARG, the message names the member): NULL, a graph listed twice, sharded handles, handles of
+ * the fused or persistent experiment (the refusals of locrec_sg_recommend_batch) and handles created with
+ * LOCREC_SG_PPW / LOCREC_SG_GS (the refusal of locrec_sg_group_create).  Column widths and weight forms may be
+ * mixed.  The pool's tables and pinned buffer are sized at create: a repeated call of the same shape makes no
+ * device allocation.
+ * recommend_batch: request i asks graph graph_index[i] (a position of create's list) for vertex_ids[i].  Rows,
+ * offsets, the capacity protocol, the counters and the NULL rules are those of locrec_sg_recommend_batch;
+ * request i's rows equal bit for bit what locrec_sg_recommend returns for that vertex on that graph.  A repeated
+ * (graph, vertex) pair is iterated once; the same vertex id in two graphs is two requests.  Before any device
+ * work every graph index is checked (LOCREC_E_INVALID_ARG), then every vertex (LOCREC_E_NOT_FOUND, "No such
+ * vertex in the graph: <id>"); on either failure nothing is written except *out_bad_request (may be NULL): the
+ * position of the first offending request; -1 on success.  n_requests == 0: out_offsets[0] = 0, capacity 0.
+ * Afterwards every member serves single requests, locrec_sg_recommend_batch and group runs as a fresh handle.
+ * stats: this thread's last recommend_batch (any pointer may be NULL): tile waves, rounds, sweep and finalize
+ * kernel launches (launches, not graphs), convergence polls, bytes read back.
+ */
+typedef struct locrec_sg_pool locrec_sg_pool;
+int32_t locrec_sg_pool_create(locrec_sg_graph *const *graphs, int32_t n_graphs, locrec_sg_pool **out_pool);
+void locrec_sg_pool_destroy(locrec_sg_pool *pool);
+int32_t locrec_sg_pool_recommend_batch(
+    locrec_sg_pool *pool, int64_t n_requests, const int32_t *graph_index, const int64_t *vertex_ids,
+    double alpha, double epsilon, int64_t max_iterations,
+    int64_t *out_offsets, int64_t *out_ids, double *out_probabilities, int64_t *inout_capacity,
+    int64_t *out_iterations, int32_t *out_converged, int64_t *out_bad_request);
+int32_t locrec_sg_pool_stats(int64_t *out_tile_waves, int64_t *out_rounds, int64_t *out_sweep_launches,
+                             int64_t *out_finalize_launches, int64_t *out_polls, int64_t *out_readback_bytes);
+
 int32_t locrec_sg_set_stream(locrec_sg_graph *graph, void *hip_stream);
 int32_t locrec_sg_synchronize(locrec_sg_graph *graph);
 int32_t locrec_sg_profile_enable(locrec_sg_graph *graph, int32_t on);

@@ -19,7 +19,7 @@
 namespace {
 
 // 16 fp64 columns = one 128-byte line per gathered x row.  VGPRs (hipcc -Rpass-analysis=kernel-resource-usage, gfx950):
-// sg_sweep_batch 92 / 93 (uint16 columns, dictionary / fp64 weights), 80 / 130 (int32 columns), sg_finalize_batch 152;
+// sg_sweep_batch 92 / 60 (uint16 columns, dictionary / fp64 weights), 80 / 130 (int32 columns), sg_finalize_batch 153;
 // no scratch.
 constexpr int kBatchB = 16;
 
@@ -68,15 +68,17 @@ __device__ __forceinline__ void segment_butterfly_sum_all(double (&s)[kBatchB], 
 }
 
 // Batched sg_sweep / sg_sweep_dict: one wave per piece, its column and weight (index) loads once for all columns.
+// bx is the block's index among the blocks of ITS graph (sg_sweep_batch: blockIdx.x; sg_sweep_pool, sg_pool.h: behind the
+// graph's block base), as sg_sweep_body serves sg_sweep and sg_sweep_group.
 template <bool COL16, bool DICT>
-__global__ __launch_bounds__(256) void sg_sweep_batch(
+__device__ __forceinline__ void sg_sweep_batch_body(
     const void *__restrict__ colv, const v2d *__restrict__ w2, const v4h *__restrict__ widx, const double *__restrict__ dict,
     const int32_t ndict, const int2 *__restrict__ pinfo, const int32_t *__restrict__ seg_out, const double *__restrict__ x_in,
-    double *__restrict__ partial, const int32_t npieces, const SgBatchState *__restrict__ st)
+    double *__restrict__ partial, const int32_t npieces, const SgBatchState *__restrict__ st, const int bx)
 {
     extern __shared__ double tbl[];
     const int lane = threadIdx.x & 63;
-    const int p0 = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+    const int p0 = __builtin_amdgcn_readfirstlane(bx * 4 + (threadIdx.x >> 6));
     const int p = min(p0, npieces - 1);  // (npieces >= 1: the launch has no blocks otherwise)
     int c[4];
     if constexpr (COL16) {
@@ -133,7 +135,17 @@ __global__ __launch_bounds__(256) void sg_sweep_batch(
     }
 }
 
-// What a tile's finalize needs per column (by value: the launches are issued directly, not replayed)
+template <bool COL16, bool DICT>
+__global__ __launch_bounds__(256) void sg_sweep_batch(
+    const void *__restrict__ colv, const v2d *__restrict__ w2, const v4h *__restrict__ widx, const double *__restrict__ dict,
+    const int32_t ndict, const int2 *__restrict__ pinfo, const int32_t *__restrict__ seg_out, const double *__restrict__ x_in,
+    double *__restrict__ partial, const int32_t npieces, const SgBatchState *__restrict__ st)
+{
+    sg_sweep_batch_body<COL16, DICT>(colv, w2, widx, dict, ndict, pinfo, seg_out, x_in, partial, npieces, st, (int)blockIdx.x);
+}
+
+// What a tile's finalize needs per column (sg_finalize_batch takes it by value: its launches are issued directly, not
+// replayed; sg_finalize_pool reads it from its graph's row of a device table)
 struct SgBatchReq {
     int32_t target_x[kBatchB];      // row of column b's target: its live index, or T + 1 + b when it is source-only
     int32_t n_plain_dead[kBatchB];  // source-only vertices other than column b's target (they hold D's value)
@@ -179,15 +191,15 @@ __device__ __forceinline__ void batch_combine(const SgBatchReq &rq, uint32_t act
     }
 }
 
-// Batched sg_finalize_body: the same rows per thread / wave, the same order of every sum, per column.
-__global__ __launch_bounds__(256) void sg_finalize_batch(
-    const SgBatchReq rq, int32_t n_short, const int4 *__restrict__ lrows, int32_t nlrows, int32_t n_crows,
+// Batched sg_finalize_body: the same rows per thread / wave, the same order of every sum, per column.  bx is the block's
+// index among the kParts blocks of its graph.
+__device__ __forceinline__ void sg_finalize_batch_body(
+    const SgBatchReq &rq, const int bx, int32_t n_short, const int4 *__restrict__ lrows, int32_t nlrows, int32_t n_crows,
     const double *__restrict__ partial, const double *__restrict__ x_in, double *__restrict__ x_out,
     const double *__restrict__ parts_prev, double *__restrict__ parts_out, SgBatchState *st, int32_t first)
 {
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
-    const int bx = blockIdx.x;
     // the columns this launch advances: isConverged of each column's PREVIOUS sweep (:99), decided by every wave from
     // the same block sums in the same order as sg_finalize; a done column is never written again
     uint32_t act = 0;
@@ -287,6 +299,15 @@ __global__ __launch_bounds__(256) void sg_finalize_batch(
     }
 }
 
+__global__ __launch_bounds__(256) void sg_finalize_batch(
+    const SgBatchReq rq, int32_t n_short, const int4 *__restrict__ lrows, int32_t nlrows, int32_t n_crows,
+    const double *__restrict__ partial, const double *__restrict__ x_in, double *__restrict__ x_out,
+    const double *__restrict__ parts_prev, double *__restrict__ parts_out, SgBatchState *st, int32_t first)
+{
+    sg_finalize_batch_body(rq, (int)blockIdx.x, n_short, lrows, nlrows, n_crows, partial, x_in, x_out, parts_prev, parts_out, st,
+                           first);
+}
+
 // A tile's set-up in one launch: x0 (:51-54) in every row and column of the first x buffer, the state and block sums
 // reset, and the out-edge slots of listed source-only vertices re-pointed (the previous tile's back at D, this tile's at
 // their private rows).  nx = 0: the slot ranges only (the end of a batch).
@@ -302,7 +323,7 @@ struct SgBatchBegin {
     int32_t off[kBatchRanges], cnt[kBatchRanges], val[kBatchRanges];  // (the ranges belong to different vertices: disjoint)
 };
 
-__global__ __launch_bounds__(256) void sg_begin_batch(const SgBatchBegin b)
+__device__ __forceinline__ void sg_begin_batch_body(const SgBatchBegin &b)
 {
     const int i = blockIdx.x * 256 + (int)threadIdx.x;
     const int stride = gridDim.x * 256;
@@ -325,6 +346,8 @@ __global__ __launch_bounds__(256) void sg_begin_batch(const SgBatchBegin b)
     }
 }
 
+__global__ __launch_bounds__(256) void sg_begin_batch(const SgBatchBegin b) { sg_begin_batch_body(b); }
+
 __global__ void sg_poll_batch(const SgBatchState *__restrict__ st, int32_t *host_word)
 {
     if (threadIdx.x == 0) *host_word = st->all_done;
@@ -332,9 +355,9 @@ __global__ void sg_poll_batch(const SgBatchState *__restrict__ st, int32_t *host
 
 // The tile's read-back in one launch: the state at 0, both parities' block sums at kBatchPackHead, then rows 0 .. T
 // (the live vertices and D) of x, every column from the parity its last executed sweep wrote, row-major.
-__global__ __launch_bounds__(256) void sg_pack_batch(const SgBatchState *__restrict__ st, const double *__restrict__ parts,
-                                                     const double *__restrict__ xbuf, int64_t x_parity_stride, int32_t nrows,
-                                                     unsigned char *out)
+__device__ __forceinline__ void sg_pack_batch_body(const SgBatchState *__restrict__ st, const double *__restrict__ parts,
+                                                   const double *__restrict__ xbuf, int64_t x_parity_stride, int32_t nrows,
+                                                   unsigned char *out)
 {
     __shared__ int32_t par[kBatchB];
     if (threadIdx.x < kBatchB) par[threadIdx.x] = st->sweeps[threadIdx.x] & 1;
@@ -349,12 +372,20 @@ __global__ __launch_bounds__(256) void sg_pack_batch(const SgBatchState *__restr
     for (int64_t i = t; i < n; i += stride) hx[i] = xbuf[par[i & (kBatchB - 1)] * x_parity_stride + i];
 }
 
+__global__ __launch_bounds__(256) void sg_pack_batch(const SgBatchState *__restrict__ st, const double *__restrict__ parts,
+                                                     const double *__restrict__ xbuf, int64_t x_parity_stride, int32_t nrows,
+                                                     unsigned char *out)
+{
+    sg_pack_batch_body(st, parts, xbuf, x_parity_stride, nrows, out);
+}
+
 struct SlotRange {
     int32_t off, cnt, val;
 };
 
-// What the batched entries share (locrec_sg_recommend_batch below, locrec_sg_recommend_ranked_batch in sg_ranked.h): the
-// requires and refusals, the distinct targets, the verdict on a column and the tile loop.
+// What the batched entries share (locrec_sg_recommend_batch below, locrec_sg_recommend_ranked_batch in sg_ranked.h,
+// locrec_sg_pool_recommend_batch in sg_pool.h): the requires and refusals, the distinct targets, a tile's set-up rows, the
+// verdict on a column, the tile loop and the host's side of a tile's read-back.
 struct SgBatchCtx {
     hipStream_t s = nullptr;
     int32_t T = 0;
@@ -365,26 +396,44 @@ struct SgBatchCtx {
     int64_t polls = 0;           // convergence words read so far
 };
 
-// require()s of the constructor (StochasticRecommender.scala:33-34), the handles a batch refuses, and isVertexExist
-// (:70-77) for every target before any device work; a repeated target is computed once
-int32_t sg_batch_targets(locrec_sg_graph *g, int64_t n_targets, const int64_t *vertex_ids, double epsilon,
-                         int64_t max_iterations, std::vector<int32_t> &uniq, std::vector<int32_t> &uniq_of)
+// require()s of the constructor (StochasticRecommender.scala:33-34)
+int32_t sg_batch_requires(double epsilon, int64_t max_iterations)
 {
     if (!(epsilon >= 0)) return fail(LOCREC_E_INVALID_ARG, "requirement failed: epsilon must be non-negative");
     if (max_iterations < 0)
         return fail(LOCREC_E_INVALID_ARG, "requirement failed: max iterations number must be non-negative");
-    if (g->shard_count != 1)
-        return fail(LOCREC_E_INVALID_ARG, "a sharded graph is iterated with locrec_sg_shard_* (it holds only part of the edges)");
+    return LOCREC_OK;
+}
+
+// why a handle serves no batched request (NULL: it does)
+const char *sg_batch_refusal(const locrec_sg_graph *g)
+{
+    if (g->shard_count != 1) return "a sharded graph is iterated with locrec_sg_shard_* (it holds only part of the edges)";
     if (g->env_fused || g->env_persist)  // (other kernels serve their single requests; the fused one's buffers are the batch's)
-        return fail(LOCREC_E_INVALID_ARG, "batched requests are not served on a handle of the fused or persistent experiment");
+        return "batched requests are not served on a handle of the fused or persistent experiment";
+    return nullptr;
+}
+
+// isVertexExist (:70-77): the vertex's index, or -1
+inline int32_t sg_vertex_index(const locrec_sg_graph *g, int64_t vertex_id)
+{
+    auto it = std::lower_bound(g->vid.begin(), g->vid.end(), vertex_id);
+    return it == g->vid.end() || *it != vertex_id ? -1 : (int32_t)(it - g->vid.begin());
+}
+
+// The requires, the handles a batch refuses, and isVertexExist for every target before any device work; a repeated target
+// is computed once
+int32_t sg_batch_targets(locrec_sg_graph *g, int64_t n_targets, const int64_t *vertex_ids, double epsilon,
+                         int64_t max_iterations, std::vector<int32_t> &uniq, std::vector<int32_t> &uniq_of)
+{
+    LOCREC_TRY(sg_batch_requires(epsilon, max_iterations));
+    if (const char *why = sg_batch_refusal(g)) return fail(LOCREC_E_INVALID_ARG, "%s", why);
     uniq.clear();                          // vertex index of each distinct target, in order of appearance
     uniq_of.assign((size_t)n_targets, 0);  // input position -> its entry of uniq
     std::unordered_map<int32_t, int32_t> seen;
     for (int64_t i = 0; i < n_targets; ++i) {
-        auto it = std::lower_bound(g->vid.begin(), g->vid.end(), vertex_ids[i]);
-        if (it == g->vid.end() || *it != vertex_ids[i])
-            return fail(LOCREC_E_NOT_FOUND, "No such vertex in the graph: %lld", (long long)vertex_ids[i]);
-        const int32_t tv = (int32_t)(it - g->vid.begin());
+        const int32_t tv = sg_vertex_index(g, vertex_ids[i]);
+        if (tv < 0) return fail(LOCREC_E_NOT_FOUND, "No such vertex in the graph: %lld", (long long)vertex_ids[i]);
         auto ins = seen.emplace(tv, (int32_t)uniq.size());
         if (ins.second) uniq.push_back(tv);
         uniq_of[(size_t)i] = ins.first->second;
@@ -394,6 +443,99 @@ int32_t sg_batch_targets(locrec_sg_graph *g, int64_t n_targets, const int64_t *v
 
 // targets of a tile: uint16 columns address rows up to 65535, so a graph with T close to that takes fewer private rows
 inline int sg_batch_tile_max(const locrec_sg_graph *g) { return g->use16 ? std::min(kBatchB, 65535 - g->nlive) : kBatchB; }
+
+inline int64_t sg_batch_xstride(const locrec_sg_graph *g) { return ((int64_t)g->nlive + 1 + kBatchB) * kBatchB; }  // one parity of x
+
+// The batch's device buffers (the head of this file), allocated at the handle's first batch; s orders the clearing
+int32_t sg_batch_buffers(locrec_sg_graph *g, hipStream_t s)
+{
+    if (g->PA4.p) return LOCREC_OK;
+    LOCREC_TRY(g->PA4.alloc((size_t)(2 * sg_batch_xstride(g))));
+    LOCREC_TRY(g->XL.alloc((size_t)std::max(1, g->pa_stride) * kBatchB));
+    LOCREC_TRY(g->D2W.alloc(2 * kParts * kBatchB));
+    LOCREC_TRY(g->fused_conv.alloc(sizeof(SgBatchState) / sizeof(int32_t)));
+    // (partial slots no sweep writes - a short row's missing full pieces or remainder - stay 0.0 for good)
+    LOCREC_HIP_TRY(hipMemsetAsync(g->XL.p, 0, g->XL.bytes(), s));
+    return LOCREC_OK;
+}
+
+inline const void *sg_batch_columns(const locrec_sg_graph *g)
+{
+    return g->use16 ? static_cast<const void *>(g->col16.p) : static_cast<const void *>(g->col4.p);
+}
+
+// The slot ranges of a handle that point at the single request's Q and go back to D next: taken over by the batch
+inline void sg_batch_take_patched(locrec_sg_graph *g, std::vector<SlotRange> &pointed)
+{
+    pointed.clear();
+    if (g->n_patched > 0) pointed.push_back(SlotRange{(int32_t)g->patched_off, g->n_patched, g->nlive});
+    g->patched_off = 0;
+    g->n_patched = 0;
+}
+
+// The set-up and finalize rows of the tile uniq[t0 .. t0 + nb): `pointed` lists the slot ranges that point at a private
+// row (or at the single request's Q) now and leaves as this tile's
+void sg_batch_tile_rows(const locrec_sg_graph *g, const std::vector<int32_t> &uniq, size_t t0, int nb, double alpha, double eps2,
+                        std::vector<SlotRange> &pointed, SgBatchBegin &b, SgBatchReq &rq)
+{
+    const int32_t T = g->nlive;
+    b = SgBatchBegin{};
+    b.x = g->PA4.p;
+    b.parts = g->D2W.p;
+    b.st = reinterpret_cast<SgBatchState *>(g->fused_conv.p);
+    b.col = const_cast<void *>(sg_batch_columns(g));
+    b.slots = g->dead_slots_dev.p;
+    b.x0 = 1.0 / (double)g->nv;  // :51-54
+    b.nx = sg_batch_xstride(g);
+    b.col16 = g->use16 ? 1 : 0;
+    b.nb = nb;
+    rq = SgBatchReq{};
+    rq.nb = nb;
+    rq.T = T;
+    rq.alpha = alpha;
+    rq.oma = 1 - alpha;  // :121
+    rq.eps2 = eps2;
+    std::vector<SlotRange> fresh;
+    for (int j = 0; j < nb; ++j) {
+        const int32_t tv = uniq[t0 + (size_t)j];
+        const bool dead = g->live_of[tv] < 0;
+        rq.target_x[j] = dead ? T + 1 + j : g->live_of[tv];
+        rq.n_plain_dead[j] = (int32_t)(g->nv - T) - (dead ? 1 : 0);
+        rq.q_in_use[j] = dead ? 1 : 0;
+        const int32_t n = dead ? (int32_t)(g->dead_ptr[tv + 1] - g->dead_ptr[tv]) : 0;
+        if (n > 0) fresh.push_back(SlotRange{(int32_t)g->dead_ptr[tv], n, T + 1 + j});
+    }
+    for (const SlotRange &r : pointed) {
+        bool again = false;  // the same vertex is re-pointed by this tile: one write per slot
+        for (const SlotRange &f : fresh) again |= f.off == r.off;
+        if (!again) {
+            b.off[b.nranges] = r.off;
+            b.cnt[b.nranges] = r.cnt;
+            b.val[b.nranges++] = T;
+        }
+    }
+    for (const SlotRange &f : fresh) {
+        b.off[b.nranges] = f.off;
+        b.cnt[b.nranges] = f.cnt;
+        b.val[b.nranges++] = f.val;
+    }
+    pointed = fresh;
+}
+
+// The set-up row that only points the last tile's slots back at D: the handle's column array is as a fresh handle's
+// (nothing points at Q)
+void sg_batch_restore_row(const locrec_sg_graph *g, const std::vector<SlotRange> &pointed, SgBatchBegin &b)
+{
+    b = SgBatchBegin{};
+    b.col = const_cast<void *>(sg_batch_columns(g));
+    b.slots = g->dead_slots_dev.p;
+    b.col16 = g->use16 ? 1 : 0;
+    for (const SlotRange &r : pointed) {
+        b.off[b.nranges] = r.off;
+        b.cnt[b.nranges] = r.cnt;
+        b.val[b.nranges++] = g->nlive;
+    }
+}
 
 // step(), :92-106: which of the two exits a column took (as locrec_sg_fetch decides it).  total() is the sum of the block
 // sums of the column's last executed sweep, added as the finalize adds them; it is asked for only when a sweep ran.
@@ -423,23 +565,15 @@ int32_t sg_batch_tiles(locrec_sg_graph *g, const std::vector<int32_t> &uniq, dou
     LOCREC_HIP_TRY(hipSetDevice(g->device));
     hipStream_t s = g->stream;
     const int32_t T = g->nlive;
-    const int64_t rows = (int64_t)T + 1 + kBatchB;
-    const int64_t xstride = rows * kBatchB;  // one parity of x
+    const int64_t xstride = sg_batch_xstride(g);
     const int tile_max = sg_batch_tile_max(g);
-    if (!g->PA4.p) {
-        LOCREC_TRY(g->PA4.alloc((size_t)(2 * xstride)));
-        LOCREC_TRY(g->XL.alloc((size_t)std::max(1, g->pa_stride) * kBatchB));
-        LOCREC_TRY(g->D2W.alloc(2 * kParts * kBatchB));
-        LOCREC_TRY(g->fused_conv.alloc(sizeof(SgBatchState) / sizeof(int32_t)));
-        // (partial slots no sweep writes - a short row's missing full pieces or remainder - stay 0.0 for good)
-        LOCREC_HIP_TRY(hipMemsetAsync(g->XL.p, 0, g->XL.bytes(), s));
-    }
+    LOCREC_TRY(sg_batch_buffers(g, s));
     SgBatchState *bstate = reinterpret_cast<SgBatchState *>(g->fused_conv.p);
     const double eps2 = epsilon * epsilon;  // :40
     const bool poll = epsilon > 0 && max_iterations > 4;
     const bool poll_by_kernel = g->h_poll_dev != nullptr && !g->no_pack;
     const int sweep_blocks = (g->npieces + 3) / 4;
-    const void *colv = g->use16 ? static_cast<const void *>(g->col16.p) : static_cast<const void *>(g->col4.p);
+    const void *colv = sg_batch_columns(g);
     const v2d *wv2 = reinterpret_cast<const v2d *>(g->w2.p);
     const v4h *wi = reinterpret_cast<const v4h *>(g->widx.p);
     const size_t lds = g->ndict > 0 ? (size_t)g->ndict * sizeof(double) : 0;
@@ -452,53 +586,13 @@ int32_t sg_batch_tiles(locrec_sg_graph *g, const std::vector<int32_t> &uniq, dou
     ctx.max_iterations = max_iterations;
     // slot ranges that point at a private row (or at the single request's Q) and go back to D next
     std::vector<SlotRange> pointed;
-    if (g->n_patched > 0) pointed.push_back(SlotRange{(int32_t)g->patched_off, g->n_patched, T});
-    g->patched_off = 0;
-    g->n_patched = 0;
+    sg_batch_take_patched(g, pointed);
 
     auto run_tile = [&](size_t t0, int nb) -> int32_t {
-        SgBatchBegin b{};
-        b.x = g->PA4.p;
-        b.parts = g->D2W.p;
-        b.st = bstate;
-        b.col = const_cast<void *>(colv);
-        b.slots = g->dead_slots_dev.p;
-        b.x0 = 1.0 / (double)g->nv;  // :51-54
-        b.nx = xstride;
-        b.col16 = g->use16 ? 1 : 0;
-        b.nb = nb;
-        SgBatchReq rq{};
-        rq.nb = nb;
-        rq.T = T;
-        rq.alpha = alpha;
-        rq.oma = 1 - alpha;  // :121
-        rq.eps2 = eps2;
-        std::vector<SlotRange> fresh;
-        for (int j = 0; j < nb; ++j) {
-            const int32_t tv = uniq[t0 + (size_t)j];
-            const bool dead = g->live_of[tv] < 0;
-            rq.target_x[j] = dead ? T + 1 + j : g->live_of[tv];
-            rq.n_plain_dead[j] = (int32_t)(g->nv - T) - (dead ? 1 : 0);
-            rq.q_in_use[j] = dead ? 1 : 0;
-            const int32_t n = dead ? (int32_t)(g->dead_ptr[tv + 1] - g->dead_ptr[tv]) : 0;
-            if (n > 0) fresh.push_back(SlotRange{(int32_t)g->dead_ptr[tv], n, T + 1 + j});
-        }
-        for (const SlotRange &r : pointed) {
-            bool again = false;  // the same vertex is re-pointed by this tile: one write per slot
-            for (const SlotRange &f : fresh) again |= f.off == r.off;
-            if (!again) {
-                b.off[b.nranges] = r.off;
-                b.cnt[b.nranges] = r.cnt;
-                b.val[b.nranges++] = T;
-            }
-        }
-        for (const SlotRange &f : fresh) {
-            b.off[b.nranges] = f.off;
-            b.cnt[b.nranges] = f.cnt;
-            b.val[b.nranges++] = f.val;
-        }
+        SgBatchBegin b;
+        SgBatchReq rq;
+        sg_batch_tile_rows(g, uniq, t0, nb, alpha, eps2, pointed, b, rq);
         hipLaunchKernelGGL(sg_begin_batch, dim3(kBeginBlocks), dim3(256), 0, s, b);
-        pointed = fresh;
         // step() (:92-106) for every column; the host looks at "all columns done" on the single request's schedule
         auto launch_round = [&](int64_t i) {
             const int par = (int)(i & 1);
@@ -544,21 +638,156 @@ int32_t sg_batch_tiles(locrec_sg_graph *g, const std::vector<int32_t> &uniq, dou
     int32_t status = LOCREC_OK;
     for (size_t t0 = 0; t0 < nu && status == LOCREC_OK; t0 += (size_t)tile_max)
         status = run_tile(t0, (int)std::min<size_t>((size_t)tile_max, nu - t0));
-    // the last tile's slots back at D: the handle's column array is as a fresh handle's (nothing points at Q)
     if (!pointed.empty()) {
-        SgBatchBegin b{};
-        b.col = const_cast<void *>(colv);
-        b.slots = g->dead_slots_dev.p;
-        b.col16 = g->use16 ? 1 : 0;
-        for (const SlotRange &r : pointed) {
-            b.off[b.nranges] = r.off;
-            b.cnt[b.nranges] = r.cnt;
-            b.val[b.nranges++] = T;
-        }
+        SgBatchBegin b;
+        sg_batch_restore_row(g, pointed, b);
         hipLaunchKernelGGL(sg_begin_batch, dim3(kBeginBlocks), dim3(256), 0, s, b);
         LOCREC_HIP_TRY(hipGetLastError());
     }
     return status;
+}
+
+// ---- the host's side of a tile's read-back: the packed image (the state at 0, the block sums at kBatchPackHead, then
+// rows 0 .. T of x, every column from the parity of its last executed sweep), the verdicts and the rows ----
+
+inline size_t sg_batch_pack_bytes(int32_t T) { return kBatchPackHead + (size_t)2 * kParts * kBatchB * 8 + (size_t)(T + 1) * kBatchB * 8; }
+
+inline unsigned sg_batch_pack_blocks(int32_t T) { return (unsigned)std::min<int64_t>(64, ((int64_t)(T + 1) * kBatchB + 2047) / 2048); }
+
+// (no pinned staging, or LOCREC_SG_NO_PACK) the same image from plain copies: enqueued here, assembled by
+// sg_batch_copy_assemble once the stream has been synchronised.  dst and both stay where they are until then.
+int32_t sg_batch_copy_enqueue(const locrec_sg_graph *g, hipStream_t s, unsigned char *dst, std::vector<double> &both)
+{
+    const int64_t xstride = sg_batch_xstride(g);
+    const size_t nxc = (size_t)(g->nlive + 1) * kBatchB;
+    both.resize(2 * nxc);
+    LOCREC_HIP_TRY(hipMemcpyAsync(dst, g->fused_conv.p, sizeof(SgBatchState), hipMemcpyDeviceToHost, s));
+    LOCREC_HIP_TRY(hipMemcpyAsync(dst + kBatchPackHead, g->D2W.p, (size_t)2 * kParts * kBatchB * sizeof(double),
+                                  hipMemcpyDeviceToHost, s));
+    for (int par = 0; par < 2; ++par)
+        LOCREC_HIP_TRY(hipMemcpyAsync(both.data() + par * nxc, g->PA4.p + (size_t)par * xstride, nxc * sizeof(double),
+                                      hipMemcpyDeviceToHost, s));
+    return LOCREC_OK;
+}
+
+void sg_batch_copy_assemble(int32_t T, unsigned char *dst, const std::vector<double> &both)
+{
+    const size_t nxc = (size_t)(T + 1) * kBatchB;
+    SgBatchState st0;
+    std::memcpy(&st0, dst, sizeof st0);
+    double *hx0 = reinterpret_cast<double *>(dst + kBatchPackHead) + 2 * kParts * kBatchB;
+    for (size_t i = 0; i < nxc; ++i) hx0[i] = both[(size_t)(st0.sweeps[i % kBatchB] & 1) * nxc + i];
+}
+
+// What a batch collects per distinct target
+struct SgBatchRows {
+    std::vector<std::vector<int64_t>> ids;
+    std::vector<std::vector<double>> probs;
+    std::vector<int64_t> it;
+    std::vector<int32_t> conv;
+    void resize(size_t nu)
+    {
+        ids.assign(nu, {});
+        probs.assign(nu, {});
+        it.assign(nu, 0);
+        conv.assign(nu, 0);
+    }
+};
+
+// The verdicts and rows (:84-88) of the tile uniq[t0 .. t0 + nb) from its packed image
+int32_t sg_batch_host_rows(locrec_sg_graph *g, const unsigned char *host, const std::vector<int32_t> &uniq, size_t t0, int nb,
+                           double eps2, int64_t max_iterations, SgBatchRows &res)
+{
+    const int32_t T = g->nlive;
+    SgBatchState hs;
+    std::memcpy(&hs, host, sizeof hs);
+    const double *hparts = reinterpret_cast<const double *>(host + kBatchPackHead);
+    const double *hx = hparts + 2 * kParts * kBatchB;
+    if (g->live_sorted.size() != (size_t)T) {
+        g->live_sorted.clear();
+        for (int64_t v = 0; v < g->nv; ++v)
+            if (g->live_of[v] >= 0) g->live_sorted.push_back((int32_t)v);
+    }
+    // step(), :92-106: which of the two exits each column took (as locrec_sg_fetch decides it)
+    for (int j = 0; j < nb; ++j) {
+        const size_t u = t0 + (size_t)j;
+        const int64_t sweeps = hs.sweeps[j];
+        auto total = [&]() {
+            double parts[kParts];
+            for (int q = 0; q < kParts; ++q) parts[q] = hparts[(size_t)((sweeps - 1) & 1) * kParts * kBatchB + (size_t)q * kBatchB + j];
+            return host_total_d2(parts);
+        };
+        LOCREC_TRY(sg_batch_verdict(sweeps, total, eps2, max_iterations, &res.it[u], &res.conv[u]));
+    }
+    // :84-88  id != vertexId and probability > 0, ascending id.  A source-only vertex holds D's value: 1/V before the
+    // first sweep (then every vertex is walked, column by column), 0 after it (then only the live ones can appear,
+    // and one pass over them serves every column: each x row is one contiguous line)
+    int swept[kBatchB];
+    int nswept = 0;
+    for (int j = 0; j < nb; ++j) {
+        const size_t u = t0 + (size_t)j;
+        const int32_t tv = uniq[u];
+        const double xdead = hx[(size_t)T * kBatchB + j];
+        if (!(xdead > 0)) {
+            swept[nswept++] = j;
+            res.ids[u].reserve((size_t)T);
+            res.probs[u].reserve((size_t)T);
+            continue;
+        }
+        for (int64_t v = 0; v < g->nv; ++v) {
+            const int32_t l = g->live_of[v];
+            const double xv = l >= 0 ? hx[(size_t)l * kBatchB + j] : xdead;
+            if (v == tv || !(xv > 0)) continue;
+            res.ids[u].push_back(g->vid[v]);
+            res.probs[u].push_back(xv);
+        }
+    }
+    if (nswept > 0) {
+        for (const int32_t v : g->live_sorted) {
+            const double *row = hx + (size_t)g->live_of[v] * kBatchB;
+            for (int k = 0; k < nswept; ++k) {
+                const int j = swept[k];
+                const size_t u = t0 + (size_t)j;
+                if (v == uniq[u] || !(row[j] > 0)) continue;
+                res.ids[u].push_back(g->vid[v]);
+                res.probs[u].push_back(row[j]);
+            }
+        }
+    }
+    return LOCREC_OK;
+}
+
+// One request's share of what a batch collected
+struct SgBatchRowRef {
+    const SgBatchRows *res;
+    size_t u;
+};
+
+// The rows in input order (a repeated target's rows are copies) under the capacity protocol: offsets and counters always,
+// *inout_capacity = the need, the rows when the room suffices.  at(i) -> request i's SgBatchRowRef.
+template <class At>
+int32_t sg_batch_output(int64_t n_targets, At &&at, int64_t *out_offsets, int64_t *out_ids, double *out_probs,
+                        int64_t *inout_capacity, int64_t *out_iterations, int32_t *out_converged)
+{
+    int64_t total = 0;
+    out_offsets[0] = 0;
+    for (int64_t i = 0; i < n_targets; ++i) {
+        const SgBatchRowRef r = at(i);
+        total += (int64_t)r.res->ids[r.u].size();
+        out_offsets[i + 1] = total;
+        if (out_iterations) out_iterations[i] = r.res->it[r.u];
+        if (out_converged) out_converged[i] = r.res->conv[r.u];
+    }
+    const int64_t cap = *inout_capacity;
+    *inout_capacity = total;
+    if (total > cap || total == 0) return LOCREC_OK;
+    if (!out_ids || !out_probs) return fail(LOCREC_E_INVALID_ARG, "NULL output buffer");
+    for (int64_t i = 0; i < n_targets; ++i) {
+        const SgBatchRowRef r = at(i);
+        std::copy(r.res->ids[r.u].begin(), r.res->ids[r.u].end(), out_ids + out_offsets[i]);
+        std::copy(r.res->probs[r.u].begin(), r.res->probs[r.u].end(), out_probs + out_offsets[i]);
+    }
+    return LOCREC_OK;
 }
 
 }  // namespace
@@ -578,127 +807,39 @@ extern "C" int32_t locrec_sg_recommend_batch(locrec_sg_graph *g, int64_t n_targe
         *inout_capacity = 0;
         return LOCREC_OK;
     }
-    const size_t nu = uniq.size();
-    std::vector<std::vector<int64_t>> res_ids(nu);
-    std::vector<std::vector<double>> res_probs(nu);
-    std::vector<int64_t> res_it(nu);
-    std::vector<int32_t> res_conv(nu);
+    SgBatchRows res;
+    res.resize(uniq.size());
     // a tile's read-back: one pack launch into pinned memory, then the rows of every column (:84-88)
     auto read_back = [&](SgBatchCtx &ctx, size_t t0, int nb) -> int32_t {
         hipStream_t s = ctx.s;
         const int32_t T = ctx.T;
-        const int64_t xstride = ctx.xstride;
-        SgBatchState *bstate = ctx.bstate;
-        const size_t pack_bytes = kBatchPackHead + (size_t)2 * kParts * kBatchB * 8 + (size_t)(T + 1) * kBatchB * 8;
+        const size_t pack_bytes = sg_batch_pack_bytes(T);
         unsigned char *stg = g->no_pack ? nullptr : g->stage(pack_bytes);
         void *stg_dev = nullptr;
         std::vector<unsigned char> own;
         const unsigned char *host = nullptr;
-        const unsigned pack_blocks = (unsigned)std::min<int64_t>(64, ((int64_t)(T + 1) * kBatchB + 2047) / 2048);
         if (stg && hipHostGetDevicePointer(&stg_dev, stg, 0) == hipSuccess) {
-            hipLaunchKernelGGL(sg_pack_batch, dim3(pack_blocks), dim3(256), 0, s, bstate, g->D2W.p, g->PA4.p, xstride,
-                               T + 1, static_cast<unsigned char *>(stg_dev));
+            hipLaunchKernelGGL(sg_pack_batch, dim3(sg_batch_pack_blocks(T)), dim3(256), 0, s, ctx.bstate, g->D2W.p, g->PA4.p,
+                               ctx.xstride, T + 1, static_cast<unsigned char *>(stg_dev));
             LOCREC_HIP_TRY(hipStreamSynchronize(s));
             host = stg;
         } else {
             (void)hipGetLastError();
-            // (no pinned staging, or LOCREC_SG_NO_PACK) the same layout, assembled on the host from plain copies
             own.resize(pack_bytes);
-            const size_t nxc = (size_t)(T + 1) * kBatchB;
-            std::vector<double> both(2 * nxc);
-            LOCREC_HIP_TRY(hipMemcpyAsync(own.data(), bstate, sizeof(SgBatchState), hipMemcpyDeviceToHost, s));
-            LOCREC_HIP_TRY(hipMemcpyAsync(own.data() + kBatchPackHead, g->D2W.p, (size_t)2 * kParts * kBatchB * sizeof(double),
-                                          hipMemcpyDeviceToHost, s));
-            for (int par = 0; par < 2; ++par)
-                LOCREC_HIP_TRY(hipMemcpyAsync(both.data() + par * nxc, g->PA4.p + (size_t)par * xstride, nxc * sizeof(double),
-                                              hipMemcpyDeviceToHost, s));
+            std::vector<double> both;
+            LOCREC_TRY(sg_batch_copy_enqueue(g, s, own.data(), both));
             LOCREC_HIP_TRY(hipStreamSynchronize(s));
-            SgBatchState st0;
-            std::memcpy(&st0, own.data(), sizeof st0);
-            double *hx0 = reinterpret_cast<double *>(own.data() + kBatchPackHead) + 2 * kParts * kBatchB;
-            for (size_t i = 0; i < nxc; ++i) hx0[i] = both[(size_t)(st0.sweeps[i % kBatchB] & 1) * nxc + i];
+            sg_batch_copy_assemble(T, own.data(), both);
             host = own.data();
         }
         LOCREC_HIP_TRY(hipGetLastError());
-        SgBatchState hs;
-        std::memcpy(&hs, host, sizeof hs);
-        const double *hparts = reinterpret_cast<const double *>(host + kBatchPackHead);
-        const double *hx = hparts + 2 * kParts * kBatchB;
-        if (g->live_sorted.size() != (size_t)T) {
-            g->live_sorted.clear();
-            for (int64_t v = 0; v < g->nv; ++v)
-                if (g->live_of[v] >= 0) g->live_sorted.push_back((int32_t)v);
-        }
-        // step(), :92-106: which of the two exits each column took (as locrec_sg_fetch decides it)
-        for (int j = 0; j < nb; ++j) {
-            const size_t u = t0 + (size_t)j;
-            const int64_t sweeps = hs.sweeps[j];
-            auto total = [&]() {
-                double parts[kParts];
-                for (int q = 0; q < kParts; ++q) parts[q] = hparts[(size_t)((sweeps - 1) & 1) * kParts * kBatchB + (size_t)q * kBatchB + j];
-                return host_total_d2(parts);
-            };
-            LOCREC_TRY(sg_batch_verdict(sweeps, total, ctx.eps2, ctx.max_iterations, &res_it[u], &res_conv[u]));
-        }
-        // :84-88  id != vertexId and probability > 0, ascending id.  A source-only vertex holds D's value: 1/V before the
-        // first sweep (then every vertex is walked, column by column), 0 after it (then only the live ones can appear,
-        // and one pass over them serves every column: each x row is one contiguous line)
-        int swept[kBatchB];
-        int nswept = 0;
-        for (int j = 0; j < nb; ++j) {
-            const size_t u = t0 + (size_t)j;
-            const int32_t tv = uniq[u];
-            const double xdead = hx[(size_t)T * kBatchB + j];
-            if (!(xdead > 0)) {
-                swept[nswept++] = j;
-                res_ids[u].reserve((size_t)T);
-                res_probs[u].reserve((size_t)T);
-                continue;
-            }
-            for (int64_t v = 0; v < g->nv; ++v) {
-                const int32_t l = g->live_of[v];
-                const double xv = l >= 0 ? hx[(size_t)l * kBatchB + j] : xdead;
-                if (v == tv || !(xv > 0)) continue;
-                res_ids[u].push_back(g->vid[v]);
-                res_probs[u].push_back(xv);
-            }
-        }
-        if (nswept > 0) {
-            for (const int32_t v : g->live_sorted) {
-                const double *row = hx + (size_t)g->live_of[v] * kBatchB;
-                for (int k = 0; k < nswept; ++k) {
-                    const int j = swept[k];
-                    const size_t u = t0 + (size_t)j;
-                    if (v == uniq[u] || !(row[j] > 0)) continue;
-                    res_ids[u].push_back(g->vid[v]);
-                    res_probs[u].push_back(row[j]);
-                }
-            }
-        }
-        return LOCREC_OK;
+        return sg_batch_host_rows(g, host, uniq, t0, nb, ctx.eps2, ctx.max_iterations, res);
     };
     SgBatchCtx ctx;
     LOCREC_TRY(sg_batch_tiles(g, uniq, alpha, epsilon, max_iterations, ctx, read_back));
-    // the rows in input order; a repeated target's rows are copies
-    int64_t total = 0;
-    out_offsets[0] = 0;
-    for (int64_t i = 0; i < n_targets; ++i) {
-        const size_t u = (size_t)uniq_of[(size_t)i];
-        total += (int64_t)res_ids[u].size();
-        out_offsets[i + 1] = total;
-        if (out_iterations) out_iterations[i] = res_it[u];
-        if (out_converged) out_converged[i] = res_conv[u];
-    }
-    const int64_t cap = *inout_capacity;
-    *inout_capacity = total;
-    if (total > cap || total == 0) return LOCREC_OK;
-    if (!out_ids || !out_probs) return fail(LOCREC_E_INVALID_ARG, "NULL output buffer");
-    for (int64_t i = 0; i < n_targets; ++i) {
-        const size_t u = (size_t)uniq_of[(size_t)i];
-        std::copy(res_ids[u].begin(), res_ids[u].end(), out_ids + out_offsets[i]);
-        std::copy(res_probs[u].begin(), res_probs[u].end(), out_probs + out_offsets[i]);
-    }
-    return LOCREC_OK;
+    return sg_batch_output(n_targets, [&](int64_t i) { return SgBatchRowRef{&res, (size_t)uniq_of[(size_t)i]}; }, out_offsets,
+                           out_ids, out_probs, inout_capacity, out_iterations, out_converged);
 } LOCREC_CATCH_ALL
 
 #include "sg_ranked.h"
+#include "sg_pool.h"

@@ -593,3 +593,94 @@ def sg_recommender_request(data_dir, persons, line, epsilon, max_iterations, max
     ids, scores, _, _ = sg_make_recommendations(data_dir, [target[1], target[2]], target[0], epsilon, max_iterations)
     place_ids, place_regions = load_places(data_dir)
     return (target,) + tuple(prep.rank_recommendations(ids, scores, place_ids, place_regions, target[2], max_recommendations))
+
+
+def sg_recommender_requests(data_dir, persons, lines, epsilon, max_iterations, max_recommendations=10, pooled=True):
+    """The body of StochasticRecommenderMain's loop (StochasticRecommenderMain.scala:36-62,64-75) for a LIST of input
+    lines: every line is parsed and resolved on its own, the graph of [home, target] comes from the handle cache (one
+    handle per distinct region set), ONE pool call (stochastic.SgPool) serves all lines, and the rows are ranked per line
+    against its own target region by one call of the segmented ranker.
+    -> a list aligned with lines: ((person_id, home_region_id, target_region_id), ids, probabilities), exactly what
+    sg_recommender_request returns for that line, or the exception instance that function would have raised (the
+    reference wraps each line in Try, :44-49).  pooled=False: one SgGraph.recommend_batch call per distinct graph instead
+    of the pool call (the same result; the A/B partner)."""
+    from . import _cache, prep
+    from .stochastic import ALPHA, SgGraph, SgPool
+    _cache.require_gpu_backend("sg_recommender_requests")
+    out = [None] * len(lines)
+    targets, graph_of, graphs, failed = {}, {}, [], {}
+    try:
+        for i, line in enumerate(lines):
+            try:
+                target = calc_recommender_target(persons, parse_input(line))
+                name = generate_file_name([target[1], target[2]], data_dir, "stochastic_graph")
+                if name in failed:
+                    raise failed[name]
+                if name not in graph_of:
+                    try:
+                        key = _cache.files_key([name])
+                        g = SgGraph.through_cache(key, lambda: sg_graph_from_parquet(data_dir, [target[1], target[2]]))
+                    except Exception as e:
+                        failed[name] = e
+                        raise
+                    graph_of[name] = len(graphs)
+                    graphs.append(g)
+                targets[i] = (target, graph_of[name])
+            except Exception as e:  # Try { ... } per line
+                out[i] = e
+        live = sorted(targets)
+        rows = None
+        while live and rows is None:
+            gi = np.asarray([targets[i][1] for i in live], np.int32)
+            v = np.asarray([targets[i][0][0] for i in live], np.int64)
+            try:
+                if pooled:
+                    pool = SgPool(graphs)
+                    try:
+                        rows = pool.recommend_batch(gi, v, ALPHA, epsilon, max_iterations)
+                    finally:
+                        pool.close()
+                else:
+                    rows = _sg_requests_per_graph(graphs, gi, v, ALPHA, epsilon, max_iterations)
+            except L.IllegalArgumentException as e:
+                bad = getattr(e, "bad_request", -1)
+                if bad < 0:
+                    raise
+                out[live.pop(bad)] = e  # the line's vertex is not in its graph: recorded, the call repeated without it
+        if live:
+            off, ids, probs, _, _ = rows
+            place_ids, place_regions = load_places(data_dir)
+            regions = np.asarray([targets[i][0][2] for i in live], np.int64)
+            oi, op, cnt = prep.rank_recommendations_batch(off, ids, probs, place_ids, place_regions, regions, max_recommendations)
+            for k, i in enumerate(live):
+                out[i] = (targets[i][0], np.array(oi[k, :cnt[k]]), np.array(op[k, :cnt[k]]))
+    finally:
+        for g in graphs:
+            g.close()  # drops the reference only
+    return out
+
+
+def _sg_requests_per_graph(graphs, graph_index, vertex_ids, alpha, epsilon, max_iterations):
+    """SgPool.recommend_batch's result from one SgGraph.recommend_batch call per distinct graph; an unknown vertex raises
+    with bad_request = the position of a request that names it, as the pool call does."""
+    n = len(vertex_ids)
+    parts = [None] * n
+    its, conv = np.zeros(n, np.int64), np.zeros(n, bool)
+    for k in np.unique(graph_index):
+        at = np.flatnonzero(graph_index == k)
+        try:
+            with graphs[k].lock:
+                off, ids, probs, it, cv = graphs[k].recommend_batch(vertex_ids[at], alpha, epsilon, max_iterations)
+        except L.IllegalArgumentException as e:
+            head, _, unknown = str(e).rpartition(": ")
+            if head == "No such vertex in the graph":  # (the library checks the ids in order and names the first)
+                e.bad_request = int(at[np.flatnonzero(vertex_ids[at] == int(unknown))[0]])
+            raise
+        for j, i in enumerate(at):
+            parts[i] = (ids[off[j]:off[j + 1]], probs[off[j]:off[j + 1]])
+        its[at], conv[at] = it, cv
+    off = np.zeros(n + 1, np.int64)
+    np.cumsum([len(p[0]) for p in parts], out=off[1:])
+    ids = np.concatenate([p[0] for p in parts]) if n else np.empty(0, np.int64)
+    probs = np.concatenate([p[1] for p in parts]) if n else np.empty(0, np.float64)
+    return off, ids, probs, its, conv

@@ -253,6 +253,77 @@ class SgGroup:
         L.check(L.lib().locrec_sg_group_synchronize(self._h))
 
 
+class SgPool:
+    """Resident graphs that serve one mixed batch of (graph, vertex) requests (locrec_sg_pool_*): every graph's
+    current tile of up to 16 targets shares the launches of a round.  The graphs stay owned by the caller."""
+
+    STATS = ("tile_waves", "rounds", "sweep_launches", "finalize_launches", "polls", "readback_bytes")
+
+    def __init__(self, graphs):
+        self.graphs = list(graphs)
+        arr = (C.c_void_p * len(self.graphs))(*[g._h for g in self.graphs])
+        self._h = C.c_void_p()
+        L.check(L.lib().locrec_sg_pool_create(arr, len(self.graphs), C.byref(self._h)))
+        self._sizes = None
+
+    def close(self):
+        if getattr(self, "_h", None):
+            L.lib().locrec_sg_pool_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def recommend_batch(self, graph_index, vertex_ids, alpha, epsilon, max_iterations):
+        """makeRecommendations of graphs[graph_index[i]] for vertex_ids[i], every i in one call:
+        (offsets[n + 1], ids, probabilities, iterations[n], converged[n]), request i's rows exactly what
+        graphs[graph_index[i]].recommend() returns for that vertex.  A failed call raises with `bad_request` set on the
+        exception: the position of the first request that names no graph of the pool or no vertex of its graph."""
+        import contextlib
+        gi, v = L.as_i32(graph_index), L.as_i64(vertex_ids)
+        if len(gi) != len(v):
+            raise L.IllegalArgumentException("one graph index per vertex is required")
+        n = len(v)
+        off = np.zeros(n + 1, np.int64)
+        its, conv = np.zeros(n, np.int64), np.zeros(n, np.int32)
+        with contextlib.ExitStack() as held:
+            for g in self.graphs:  # every member's lock, in member order
+                if getattr(g, "lock", None) is not None:
+                    held.enter_context(g.lock)
+            # room for what one call can return, as SgGraph.recommend_batch sizes it, up to a bound: the retry below
+            # sizes anything larger
+            known = (gi >= 0) & (gi < len(self.graphs))
+            counts = np.bincount(gi[known], minlength=len(self.graphs))
+            if self._sizes is None:  # (a handle's vertex and live counts never change)
+                self._sizes = (np.array([g.info()["vertices"] for g in self.graphs], np.int64),
+                               np.array([g.live_count() for g in self.graphs], np.int64))
+            per = self._sizes[0 if int(max_iterations) == 0 else 1]
+            room = min(max(int(np.dot(counts, np.maximum(per, 1))), 1), 1 << 24)
+            cap = C.c_int64(room)
+            ids, probs = np.empty(room, np.int64), np.empty(room, np.float64)
+            bad = C.c_int64(-1)
+            for _ in range(2):  # a call whose room is too small sizes the result, the second fills it
+                try:
+                    L.check(L.lib().locrec_sg_pool_recommend_batch(
+                        self._h, n, L.ptr(gi, C.c_int32), L.ptr(v, C.c_int64), float(alpha), float(epsilon), int(max_iterations),
+                        L.ptr(off, C.c_int64), L.ptr(ids, C.c_int64), L.ptr(probs, C.c_double), C.byref(cap),
+                        L.ptr(its, C.c_int64), L.ptr(conv, C.c_int32), C.byref(bad)))
+                except L.IllegalArgumentException as e:
+                    e.bad_request = bad.value
+                    raise
+                if cap.value <= len(ids):
+                    break
+                ids, probs = np.empty(cap.value, np.int64), np.empty(cap.value, np.float64)
+                cap = C.c_int64(len(ids))
+        return off, ids[:off[-1]], probs[:off[-1]], its, conv.astype(bool)
+
+    @classmethod
+    def stats(cls):
+        """What this thread's last recommend_batch did (locrec_sg_pool_stats)."""
+        x = [C.c_int64() for _ in cls.STATS]
+        L.check(L.lib().locrec_sg_pool_stats(*[C.byref(i) for i in x]))
+        return dict(zip(cls.STATS, (i.value for i in x)))
+
+
 class StochasticRecommender:
     """new StochasticRecommender(stochasticEdges, epsilon, maxIterations).makeRecommendations(vertexId)
 
