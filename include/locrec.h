@@ -155,11 +155,22 @@ int32_t locrec_knn_info(const locrec_knn_index *index, int64_t *out_n,
 int32_t locrec_knn_batch_scan_bytes(const locrec_knn_index *index, int64_t *out_scan_bytes);
 
 /* Measurement only: sizes of the head / tail image (knn_ht.h) - 32-bit element words of the SELL head rows of both
- * families incl. padding (every word costs one tile 8 v_pk_mad_u16 and one address add: the exact multiply-add count
- * of a launch is tiles x words / 8 wave instructions, which the roofline derivation in profiles/ uses), postings of the
- * inverted tail, and the number of rows kept out of the image by the per-row format fallback.  Zeros without the image. */
+ * families as STORED, incl. the padding to whole groups of four, postings of the inverted tail, and the number of rows
+ * kept out of the image by the per-row format fallback.  Zeros without the image. */
 int32_t locrec_knn_ht_image_info(const locrec_knn_index *index, int64_t *out_head_words, int64_t *out_tail_postings,
                                  int64_t *out_wide_rows);
+
+/* Measurement only: the words of that image knn_scan_ht MULTIPLIES per query tile - per slice 64 lanes x the exact
+ * element count of its widest row, both families (all of them rounded up to four under LOCREC_KNN_HT_ROUND4).  Every
+ * such word costs one tile 8 v_pk_mad_u16 and one address v_and: the multiply-add count of a launch is tiles x words / 8
+ * wave instructions, which the roofline derivation in profiles/ uses.  real elements <= this <= head_words. */
+int32_t locrec_knn_ht_multiplied_words(const locrec_knn_index *index, int64_t *out_words);
+
+/* Measurement and tests only: the per-slice element counts behind that figure, in slice order - out_place[s] and
+ * out_category[s] for the first min(capacity, *out_slices) slices; *out_slices = the number of slices (0 without the
+ * image).  Call with capacity 0 to size the arrays. */
+int32_t locrec_knn_ht_slice_counts(const locrec_knn_index *index, int64_t capacity, int32_t *out_place, int32_t *out_category,
+                                   int64_t *out_slices);
 
 /*
  * Plan of the last batched scan enqueued on this handle (measurement only; bench.py prints it):

@@ -245,7 +245,7 @@ int32_t build_ht(locrec_knn_index *ix, const HostFamily &hq, const HostFamily &h
         ht.tail_nnz[r] = (int32_t)(e - b) - nh[r];
     }
     std::vector<int64_t> h_off[2];
-    std::vector<int32_t> h_w[2];
+    std::vector<int32_t> h_w[2], h_ex[2];  // (h_ex: exact element count of the slice's widest row)
     int which = 0;
     auto sell_of = [&](const HostFamily &h, const std::vector<int32_t> *limit, DevBuf<uint32_t> &d_sell,
                        DevBuf<int64_t> &d_off, DevBuf<int32_t> &d_w, int64_t &elements) -> int32_t {
@@ -254,10 +254,16 @@ int32_t build_ht(locrec_knn_index *ix, const HostFamily &hq, const HostFamily &h
         ++which;
         off.assign((size_t)nslices + 1, 0);
         wv.assign((size_t)nslices, 0);
+        std::vector<int32_t> &ex = h_ex[which - 1];
+        ex.assign((size_t)nslices, 0);
         auto len_of = [&](int64_t r) { return limit ? (*limit)[r] : (int32_t)(h.ptr[r + 1] - h.ptr[r]); };
         for (int32_t sl = 0; sl < nslices; ++sl) {
-            int w = 0;
-            for (int64_t r = (int64_t)sl * 64; r < std::min<int64_t>(n, (int64_t)sl * 64 + 64); ++r) w = std::max(w, len_of(r));
+            int w = 0, x = 0;
+            for (int64_t r = (int64_t)sl * 64; r < std::min<int64_t>(n, (int64_t)sl * 64 + 64); ++r) {
+                w = std::max(w, len_of(r));
+                if (!ix->row_is_wide((int32_t)r)) x = std::max(x, len_of(r));  // (a wide row's stand-in is padding only)
+            }
+            ex[sl] = ix->ht_round4 ? (x + 3) & ~3 : x;
             w = (w + 3) & ~3;
             wv[sl] = w;
             off[sl + 1] = off[sl] + (int64_t)w * 64;
@@ -285,9 +291,15 @@ int32_t build_ht(locrec_knn_index *ix, const HostFamily &hq, const HostFamily &h
     if (pe / 4 >= ((int64_t)1 << 32) || ce / 4 >= ((int64_t)1 << 32)) return LOCREC_OK;  // descriptor offsets are 32-bit: no head / tail form
     {
         std::vector<uint4> desc((size_t)nslices);
-        for (int32_t sl = 0; sl < nslices; ++sl)
+        ht.mult_words = 0;
+        ht.slice_cnt.clear();
+        for (int32_t sl = 0; sl < nslices; ++sl) {
             desc[sl] = make_uint4((uint32_t)(h_off[0][sl] / 4), (uint32_t)(h_off[1][sl] / 4),
-                                  (uint32_t)(h_w[0][sl] / 4) | ((uint32_t)(h_w[1][sl] / 4) << 16), 0u);
+                                  (uint32_t)(h_w[0][sl] / 4) | ((uint32_t)(h_w[1][sl] / 4) << 16),
+                                  (uint32_t)h_ex[0][sl] | ((uint32_t)h_ex[1][sl] << 16));
+            ht.mult_words += 64 * (int64_t)(h_ex[0][sl] + h_ex[1][sl]);
+            ht.slice_cnt.push_back(desc[sl].w);
+        }
         LOCREC_TRY(ht.desc.upload(desc, s));
         LOCREC_TRY(ht.cold.alloc(sizeof(HtCold)));
         LOCREC_HIP_TRY(hipStreamSynchronize(s));
@@ -1446,6 +1458,7 @@ void knn_read_env(locrec_knn_index *ix)
     ix->no_direct8 = std::getenv("LOCREC_KNN_NO_DIRECT8") != nullptr;  // A/B: a single request through the hashed panel (knn_scan1<1>)
     ix->no_pack = std::getenv("LOCREC_KNN_NO_PACK") != nullptr;
     ix->no_seed = std::getenv("LOCREC_KNN_NO_SEED") != nullptr;  // A/B: knn_scan_ht without the threshold-seeding pass
+    ix->ht_round4 = std::getenv("LOCREC_KNN_HT_ROUND4") != nullptr;  // A/B: knn_scan_ht multiplies whole groups of four again
     ix->no_tile_special = std::getenv("LOCREC_KNN_NO_TILE_SPECIAL") != nullptr;  // A/B: special queries of a batch one by one
     if (const char *e = std::getenv("LOCREC_KNN_SEED_MIN_SLICES")) ix->seed_min_slices = std::max(1, std::atoi(e));  // tests
     if (const char *e = std::getenv("LOCREC_KNN_SEED_SAMPLE")) ix->seed_sample_slices = std::max(8, std::atoi(e));     // tuning
@@ -1573,6 +1586,28 @@ extern "C" int32_t locrec_knn_ht_image_info(const locrec_knn_index *ix, int64_t 
     if (out_head_words) *out_head_words = have ? (int64_t)ix->ht.p_sell.n + (int64_t)ix->ht.c_sell.n - 2 * pad : 0;
     if (out_tail_postings) *out_tail_postings = have && !ix->ht.tail_hits_ps.empty() ? (int64_t)ix->ht.post.n : 0;
     if (out_wide_rows) *out_wide_rows = (int64_t)ix->wide_rows.size();
+    return LOCREC_OK;
+} LOCREC_CATCH_ALL
+
+extern "C" int32_t locrec_knn_ht_multiplied_words(const locrec_knn_index *ix, int64_t *out_words) try
+{
+    if (!ix || !out_words) return fail(LOCREC_E_INVALID_ARG, "NULL argument");
+    *out_words = ix->ht.ready && !ix->no_ht ? ix->ht.mult_words : 0;
+    return LOCREC_OK;
+} LOCREC_CATCH_ALL
+
+extern "C" int32_t locrec_knn_ht_slice_counts(const locrec_knn_index *ix, int64_t capacity, int32_t *out_place, int32_t *out_category,
+                                              int64_t *out_slices) try
+{
+    if (!ix || !out_slices || capacity < 0 || (capacity > 0 && (!out_place || !out_category)))
+        return fail(LOCREC_E_INVALID_ARG, "NULL argument");
+    const bool have = ix->ht.ready && !ix->no_ht;
+    const int64_t ns = have ? (int64_t)ix->ht.slice_cnt.size() : 0;
+    *out_slices = ns;
+    for (int64_t sl = 0; sl < std::min(ns, capacity); ++sl) {
+        out_place[sl] = (int32_t)(ix->ht.slice_cnt[(size_t)sl] & 0xFFFFu);
+        out_category[sl] = (int32_t)(ix->ht.slice_cnt[(size_t)sl] >> 16);
+    }
     return LOCREC_OK;
 } LOCREC_CATCH_ALL
 

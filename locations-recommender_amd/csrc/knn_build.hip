@@ -400,12 +400,25 @@ __global__ void kb_tail_freq(int64_t ntail, const uint32_t *freq_new, int32_t h,
     if (t < ntail) cnt[t] = freq_new[h + t];
 }
 
-__global__ void kb_desc(int32_t nslices, const int64_t *off_p, const int32_t *w_p, const int64_t *off_c, const int32_t *w_c,
-                        uint4 *desc)
+// fourth word: the EXACT element counts of the slice's widest row (len_p = head places, len_c = categories; a row
+// flagged in skip holds padding only), rounded up to whole groups under round4 (LOCREC_KNN_HT_ROUND4)
+__global__ void kb_desc(int64_t n, int32_t nslices, const int64_t *off_p, const int32_t *w_p, const int64_t *off_c, const int32_t *w_c,
+                        const int32_t *len_p, const int32_t *len_c, const unsigned char *skip, int32_t round4, uint4 *desc)
 {
     const int sl = blockIdx.x * blockDim.x + threadIdx.x;
     if (sl >= nslices) return;
-    desc[sl] = make_uint4((uint32_t)(off_p[sl] / 4), (uint32_t)(off_c[sl] / 4), (uint32_t)(w_p[sl] / 4) | ((uint32_t)(w_c[sl] / 4) << 16), 0u);
+    int mp = 0, mc = 0;
+    for (int64_t r = (int64_t)sl * 64; r < min(n, (int64_t)sl * 64 + 64); ++r) {
+        if (skip && skip[r]) continue;
+        mp = max(mp, len_p[r]);
+        mc = max(mc, len_c[r]);
+    }
+    if (round4) {
+        mp = (mp + 3) & ~3;
+        mc = (mc + 3) & ~3;
+    }
+    desc[sl] = make_uint4((uint32_t)(off_p[sl] / 4), (uint32_t)(off_c[sl] / 4), (uint32_t)(w_p[sl] / 4) | ((uint32_t)(w_c[sl] / 4) << 16),
+                          (uint32_t)mp | ((uint32_t)mc << 16));
 }
 
 __global__ void kb_pad_rid(int64_t n, int64_t npad, const uint32_t *rid, uint32_t *out)
@@ -868,8 +881,20 @@ int32_t knn_build_device(int64_t n, const int64_t *ids, const int64_t *p_ptr, co
         LOCREC_TRY(ht_sell(ix->fc, nnz_c, nullptr, ht.c_sell, ht.c_off, ht.c_w, hce));
         if (hpe / 4 < ((int64_t)1 << 32) && hce / 4 < ((int64_t)1 << 32)) {
             LOCREC_TRY(ht.desc.alloc((size_t)std::max(1, ix->nslices)));
-            hipLaunchKernelGGL(kb_desc, grid_for(ix->nslices), dim3(256), 0, s, ix->nslices, ht.p_off.p, ht.p_w.p, ht.c_off.p, ht.c_w.p,
-                               ht.desc.p);
+            hipLaunchKernelGGL(kb_desc, grid_for(ix->nslices), dim3(256), 0, s, n, ix->nslices, ht.p_off.p, ht.p_w.p, ht.c_off.p, ht.c_w.p,
+                               nhead.p, nnz_c.p, skip, ix->ht_round4 ? 1 : 0, ht.desc.p);
+            {
+                // words per tile knn_scan_ht multiplies (locrec_knn_ht_multiplied_words): 64 lanes x the slices' counts
+                std::vector<uint4> hd((size_t)ix->nslices);
+                LOCREC_HIP_TRY(hipMemcpyAsync(hd.data(), ht.desc.p, (size_t)ix->nslices * sizeof(uint4), hipMemcpyDeviceToHost, s));
+                LOCREC_HIP_TRY(hipStreamSynchronize(s));
+                ht.mult_words = 0;
+                ht.slice_cnt.clear();
+                for (const uint4 &d : hd) {
+                    ht.mult_words += 64 * (int64_t)((d.w & 0xFFFFu) + (d.w >> 16));
+                    ht.slice_cnt.push_back(d.w);
+                }
+            }
             LOCREC_TRY(ht.cold.alloc(cfg::kHtColdBytes));
             // postings of the tail places: (place, row) keys, radix-sorted -> rows ascending inside a place
             int64_t nt_el = 0;

@@ -321,8 +321,10 @@ __device__ __forceinline__ void ht_family_dots(const unsigned char *panel, int s
 struct HtSliceDesc {   // per candidate slice, built at create time (one 16-byte scalar load per slice)
     uint32_t off_p4;   // first dwordx4 of the slice's place-head image (in units of 16 bytes)
     uint32_t off_c4;   // ... of its category image
-    uint32_t w4;       // dwordx4 groups per lane: place | category << 16
-    uint32_t pad;
+    uint32_t w4;       // dwordx4 groups per lane the image STORES: place | category << 16
+    uint32_t cnt;      // elements of the slice's widest row, exactly: place | category << 16.  knn_scan_ht multiplies
+                       // these and no more: every word behind them is zero in all 64 lanes (0 = a slice of padding or
+                       // wide-row stand-ins only; rounded up to 4 under LOCREC_KNN_HT_ROUND4, the A/B switch)
 };
 
 struct HtCold {        // parameters of the rare paths, read from memory where they are needed
@@ -408,20 +410,56 @@ __device__ __forceinline__ void ht_mul_elem(const u32x4 (&pv)[QT / 8], uint32_t 
     }
 }
 
-// one dwordx4 group = four elements; the panel rows of element t + 1 are read while element t is multiplied
-template <int QT, int STRIDE, bool FIRST = false>
-__device__ __forceinline__ void ht_group(const unsigned char *panel, const u32x4 g, uint32_t (&acc)[QT / 2])
+// A wave-uniform base the compiler cannot see through: p[lane] is then a load from a scalar base plus the lane's 32-bit
+// offset.  (Left alone, the compiler keeps base + lane as a 64-bit pointer per lane across the whole slice loop - two
+// registers per array that the loop does not have - and adds the slice's offset with a vector instruction.)
+template <class T>
+__device__ __forceinline__ const T *ht_uniform(const T *p)
 {
-    u32x4 a[QT / 8], b[QT / 8];
-    ht_read_row<QT, STRIDE>(panel, g.x, a);
-    ht_read_row<QT, STRIDE>(panel, g.y, b);
-    if constexpr (FIRST) ht_mul_elem<QT>(a, g.x, acc);
-    else ht_mad_elem<QT>(a, g.x, acc);
-    ht_read_row<QT, STRIDE>(panel, g.z, a);
-    ht_mad_elem<QT>(b, g.y, acc);
-    ht_read_row<QT, STRIDE>(panel, g.w, b);
-    ht_mad_elem<QT>(a, g.z, acc);
-    ht_mad_elem<QT>(b, g.w, acc);
+    const __attribute__((address_space(1))) T *g = (const __attribute__((address_space(1))) T *)p;  // (stays a GLOBAL pointer)
+    asm("" : "+s"(g));
+    return (const T *)g;
+}
+
+// a panel row that was read AHEAD of an exit stays read there: without this the compiler sinks the ds_read_b128 behind
+// the branch, next to their only use, and every step becomes read - wait for the LDS - multiply
+template <int QT>
+__device__ __forceinline__ void ht_pin_row(u32x4 (&pv)[QT / 8])
+{
+#pragma unroll
+    for (int i = 0; i < QT / 8; ++i) asm volatile("" : "+v"(pv[i]));
+}
+
+// One dwordx4 group = four elements of a family, of which `left` (wave-uniform: the exact count of the slice's widest
+// row minus the groups in front) are still to be multiplied.  The panel rows of element t + 1 are read while element t
+// is multiplied; the sequence is left by a scalar branch after the step at which the count ends: the words behind it
+// are zero in all 64 lanes.  (The row read ahead of an exit that is taken is a read of panel row 0: harmless.)  FIRST = the
+// family's group 0, which starts the accumulators - with zeros where the slice has no element of the family at all.
+template <int QT, int STRIDE, bool FIRST = false>
+__device__ __forceinline__ void ht_group_n(const unsigned char *panel, const u32x4 g, uint32_t (&acc)[QT / 2], int left)
+{
+    if (left > 0) {
+        u32x4 a[QT / 8], b[QT / 8];
+        ht_read_row<QT, STRIDE>(panel, g.x, a);
+        ht_read_row<QT, STRIDE>(panel, g.y, b);
+        if constexpr (FIRST) ht_mul_elem<QT>(a, g.x, acc);
+        else ht_mad_elem<QT>(a, g.x, acc);
+        ht_pin_row<QT>(b);
+        if (left > 1) {
+            ht_read_row<QT, STRIDE>(panel, g.z, a);
+            ht_mad_elem<QT>(b, g.y, acc);
+            ht_pin_row<QT>(a);
+            if (left > 2) {
+                ht_read_row<QT, STRIDE>(panel, g.w, b);
+                ht_mad_elem<QT>(a, g.z, acc);
+                ht_pin_row<QT>(b);
+                if (left > 3) ht_mad_elem<QT>(b, g.w, acc);
+            }
+        }
+    } else if constexpr (FIRST) {
+#pragma unroll
+        for (int i = 0; i < QT / 2; ++i) acc[i] = 0u;
+    }
 }
 
 // ---- survivors.  About K*ln(N/K) candidates per query enter its list over a scan - roughly one pair per
@@ -589,8 +627,8 @@ __global__ __launch_bounds__(W * 64, W == 8 ? 4 : 3) void knn_scan_ht(
     int primed = -1;
     u32x4 gp[kHtNP], gc[kHtNC];
     uint32_t ssrow = 0u, ridrow = 0u;               // sums of squares (place | category << 16) and id rank of the lane's row
-    uint32_t dcur_p4 = 0, dcur_c4 = 0, dcur_w4 = 0;   // descriptor of the current slice
-    uint32_t dnxt_p4 = 0, dnxt_c4 = 0, dnxt_w4 = 0;   // ... of the wave's next slice
+    uint32_t dcur_p4 = 0, dcur_c4 = 0, dcur_cnt = 0;   // descriptor of the current slice (offsets, exact element counts)
+    uint32_t dnxt_p4 = 0, dnxt_c4 = 0, dnxt_cnt = 0;   // ... of the wave's next slice
     uint32_t hc0 = 0, hc1 = 0, hcur = 0, hn0 = 0, hn1 = 0;
 #pragma unroll
     for (int g = 0; g < kHtNP; ++g) gp[g] = u32x4{0u, 0u, 0u, 0u};
@@ -625,25 +663,27 @@ __global__ __launch_bounds__(W * 64, W == 8 ? 4 : 3) void knn_scan_ht(
                 const HtSliceDesc d = desc[slice];
                 dcur_p4 = __builtin_amdgcn_readfirstlane(d.off_p4);
                 dcur_c4 = __builtin_amdgcn_readfirstlane(d.off_c4);
-                dcur_w4 = __builtin_amdgcn_readfirstlane(d.w4);
+                dcur_cnt = __builtin_amdgcn_readfirstlane(d.cnt);
                 const u32x4 *sp = sell_p + dcur_p4, *sc = sell_c + dcur_c4;  // uniform bases: 32-bit lane offsets below
 #pragma unroll
                 for (int g = 0; g < kHtNP; ++g) gp[g] = sp[g * 64 + lane];
 #pragma unroll
                 for (int g = 0; g < kHtNC; ++g) gc[g] = sc[g * 64 + lane];
-                ssrow = (ss_all + slice * 64)[lane];
-                ridrow = (rid_all + slice * 64)[lane];
+                ssrow = ht_uniform(ss_all + slice * 64)[lane];
+                ridrow = ht_uniform(rid_all + slice * 64)[lane];
                 hc0 = __builtin_amdgcn_readfirstlane(hoff_row[slice]);
                 hc1 = __builtin_amdgcn_readfirstlane(hoff_row[slice + 1]);
                 hcur = (hits + hc0)[min((uint32_t)lane, max(hc1 - hc0, 1u) - 1u)];
                 const HtSliceDesc dn = desc[pf];
                 dnxt_p4 = __builtin_amdgcn_readfirstlane(dn.off_p4);
                 dnxt_c4 = __builtin_amdgcn_readfirstlane(dn.off_c4);
-                dnxt_w4 = __builtin_amdgcn_readfirstlane(dn.w4);
+                dnxt_cnt = __builtin_amdgcn_readfirstlane(dn.cnt);
                 hn0 = __builtin_amdgcn_readfirstlane(hoff_row[pf]);
                 hn1 = __builtin_amdgcn_readfirstlane(hoff_row[pf + 1]);
             }
-            const int w4p = (int)(dcur_w4 & 0xFFFFu), w4c = (int)(dcur_w4 >> 16);
+            // elements the slice's widest row holds in each family (SGPRs): whole groups are multiplied up to the one
+            // the count ends in, and of that one only the elements in front of the count
+            const int np = (int)(dcur_cnt & 0xFFFFu), nc = (int)(dcur_cnt >> 16);
             const u32x4 *spn = sell_p + dnxt_p4, *scn = sell_c + dnxt_c4;  // the prefetched slice's images (uniform)
             // Load order of one iteration: [descriptor, hit range, hits] (3), place groups (kHtNP), category
             // groups (kHtNC), [ss, rid] (2).  The first place group was followed by kHtNP - 1 + kHtNC + 2 loads
@@ -664,40 +704,26 @@ __global__ __launch_bounds__(W * 64, W == 8 ? 4 : 3) void knn_scan_ht(
                 // group g (g >= 1) is followed by the previous iteration's later groups, its [ss, rid], this
                 // iteration's three leading loads and g reloads: kHtNP + kHtNC + 4 in all; one less, to be safe
                 if (g > 0) ht_wait_vm<kHtNP + kHtNC + 3>();
-                if (g == 0) {
-                    if (0 < w4p && !LOCREC_HT_DBG(1)) {
-                        ht_group<QT, kPlaceStride, true>(pan_p, gp[0], ap);
-                    } else {
-#pragma unroll
-                        for (int i = 0; i < QT / 2; ++i) ap[i] = 0u;
-                    }
-                } else if (g < w4p && !LOCREC_HT_DBG(1)) {
-                    ht_group<QT, kPlaceStride>(pan_p, gp[g], ap);
-                }
+                const int left = LOCREC_HT_DBG(1) ? 0 : np - 4 * g;
+                if (g == 0) ht_group_n<QT, kPlaceStride, true>(pan_p, gp[0], ap, left);
+                else ht_group_n<QT, kPlaceStride>(pan_p, gp[g], ap, left);
                 gp[g] = spn[g * 64 + lane];
             }
-            for (int g = kHtNP; g < w4p; ++g)  // a slice of long rows: the remaining groups, loaded on demand
-                ht_group<QT, kPlaceStride>(pan_p, (sell_p + dcur_p4)[g * 64 + lane], ap);
+            for (int g = kHtNP; 4 * g < np; ++g)  // a slice of long rows: the remaining groups, loaded on demand
+                ht_group_n<QT, kPlaceStride>(pan_p, (sell_p + dcur_p4)[g * 64 + lane], ap, np - 4 * g);
 #pragma unroll
             for (int g = 0; g < kHtNC; ++g) {
                 ht_wait_vm<kHtNP + kHtNC + 3>();
-                if (g == 0) {
-                    if (0 < w4c && !LOCREC_HT_DBG(2)) {
-                        ht_group<QT, kCatStride, true>(pan_c, gc[0], ac);
-                    } else {
-#pragma unroll
-                        for (int i = 0; i < QT / 2; ++i) ac[i] = 0u;
-                    }
-                } else if (g < w4c && !LOCREC_HT_DBG(2)) {
-                    ht_group<QT, kCatStride>(pan_c, gc[g], ac);
-                }
+                const int left = LOCREC_HT_DBG(2) ? 0 : nc - 4 * g;
+                if (g == 0) ht_group_n<QT, kCatStride, true>(pan_c, gc[0], ac, left);
+                else ht_group_n<QT, kCatStride>(pan_c, gc[g], ac, left);
                 gc[g] = scn[g * 64 + lane];
             }
-            for (int g = kHtNC; g < w4c; ++g)
-                ht_group<QT, kCatStride>(pan_c, (sell_c + dcur_c4)[g * 64 + lane], ac);
+            for (int g = kHtNC; 4 * g < nc; ++g)
+                ht_group_n<QT, kCatStride>(pan_c, (sell_c + dcur_c4)[g * 64 + lane], ac, nc - 4 * g);
             const uint32_t ss = ssrow, myrid = ridrow;
-            ssrow = (ss_all + pf * 64)[lane];   // (padded to whole slices: 0 = no row)
-            ridrow = (rid_all + pf * 64)[lane];
+            ssrow = ht_uniform(ss_all + pf * 64)[lane];   // (padded to whole slices: 0 = no row)
+            ridrow = ht_uniform(rid_all + pf * 64)[lane];
             // everything older than this iteration's kHtNP + kHtNC + 2 reloads has arrived: the previous [ss, rid],
             // the hits of this slice, the descriptor / hit range fetched above
             ht_wait_vm<kHtNP + kHtNC + 2>();
@@ -721,17 +747,22 @@ __global__ __launch_bounds__(W * 64, W == 8 ? 4 : 3) void knn_scan_ht(
                     }
                 }
                 constexpr uint32_t chunks = QT / 8;
-                const uint32_t sw = chunks == 2 ? (((uint32_t)lane >> 3) & 1u) : (((uint32_t)lane >> 2) & 3u);
+                // (the lane's row addresses are formed HERE, from a lane number the compiler cannot see through: hoisted
+                // out of the slice loop they cost two registers the loop does not have - they went to scratch memory,
+                // and each reload waited with vmcnt(0) for the prefetches in flight)
+                uint32_t tl = (uint32_t)lane;
+                asm volatile("" : "+v"(tl));
+                const uint32_t sw = chunks == 2 ? ((tl >> 3) & 1u) : ((tl >> 2) & 3u);
                 u32x4 trow[chunks];
 #pragma unroll
                 for (uint32_t c = 0; c < chunks; ++c)
-                    trow[c] = *reinterpret_cast<const u32x4 *>(my_tail + lane * (QT * 2) + (((c ^ sw) & (chunks - 1)) << 4));
+                    trow[c] = *reinterpret_cast<const u32x4 *>(my_tail + tl * (QT * 2) + (((c ^ sw) & (chunks - 1)) << 4));
                 if (hn <= 64u) {
                     if ((uint32_t)lane < hn) *reinterpret_cast<uint32_t *>(my_tail + waddr) = 0u;
                 } else {
 #pragma unroll
                     for (uint32_t c = 0; c < chunks; ++c)
-                        *reinterpret_cast<u32x4 *>(my_tail + lane * (QT * 2) + (c << 4)) = u32x4{0u, 0u, 0u, 0u};
+                        *reinterpret_cast<u32x4 *>(my_tail + tl * (QT * 2) + (c << 4)) = u32x4{0u, 0u, 0u, 0u};
                 }
 #pragma unroll
                 for (uint32_t c = 0; c < chunks; ++c) {
@@ -874,14 +905,15 @@ __global__ __launch_bounds__(W * 64, W == 8 ? 4 : 3) void knn_scan_ht(
             // ---- rotate the pipeline
             dcur_p4 = dnxt_p4;
             dcur_c4 = dnxt_c4;
-            dcur_w4 = dnxt_w4;
-            // (the descriptor's fourth word is dead, and the compiler would reuse its register right behind the load - a
-            // write-after-write hazard it guards with s_waitcnt vmcnt(0), i.e. every iteration waiting for the loads it
-            // has just issued: keeping the word "used" until here keeps the register, and the counted waits, intact)
-            asm volatile("" ::"v"(vd2.w));
+            dcur_cnt = dnxt_cnt;
+            // (the descriptor's third word - the stored group counts - is not needed here, and the compiler would reuse
+            // its register right behind the load - a write-after-write hazard it guards with s_waitcnt vmcnt(0), i.e.
+            // every iteration waiting for the loads it has just issued: keeping the word "used" until here keeps the
+            // register, and the counted waits, intact)
+            asm volatile("" ::"v"(vd2.z));
             dnxt_p4 = __builtin_amdgcn_readfirstlane(vd2.x);
             dnxt_c4 = __builtin_amdgcn_readfirstlane(vd2.y);
-            dnxt_w4 = __builtin_amdgcn_readfirstlane(vd2.z);
+            dnxt_cnt = __builtin_amdgcn_readfirstlane(vd2.w);
             hc0 = hn0;
             hc1 = hn1;
             hcur = hnext;

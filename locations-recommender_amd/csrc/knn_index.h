@@ -54,6 +54,8 @@ struct HtIndex {
     DevBuf<int64_t> post_ptr;             // [p_dim - h + 1]
     DevBuf<uint32_t> post;                // row << 8 | value, rows ascending inside a place
     DevBuf<uint4> desc;                   // per slice: HtSliceDesc (knn_ht.h)
+    int64_t mult_words = 0;               // 64 x the descriptors' exact element counts: words per tile knn_scan_ht multiplies
+    std::vector<uint32_t> slice_cnt;      // host copy of the descriptors' fourth word (locrec_knn_ht_slice_counts)
     DevBuf<uint32_t> rid;                 // ix->rid padded to whole slices
     DevBuf<uint32_t> ss;                  // per row: sum of squares of the place vector | of the category vector << 16
     DevBuf<unsigned char> cold;           // HtCold of the launch in flight
@@ -167,6 +169,7 @@ struct locrec_knn_index {
     bool force_dense_query = false;
     bool no_direct8 = false, direct8_attr = false;  // knn_scan1_direct8 (LOCREC_KNN_NO_DIRECT8)
     bool no_seed = false;         // LOCREC_KNN_NO_SEED
+    bool ht_round4 = false;       // LOCREC_KNN_HT_ROUND4: A/B, the descriptors' element counts rounded up to whole groups
     // read by knn_read_env like the ones above (the only place of the KNN sources that looks at the environment)
     bool force_generic = false;   // LOCREC_KNN_FORCE_GENERIC
     bool no_pack16 = false;       // LOCREC_KNN_NO_PACK16

@@ -141,6 +141,23 @@ class KnnIndex:
         L.check(L.lib().locrec_knn_ht_image_info(self._h, *[C.byref(x) for x in v]))
         return {"head_words": v[0].value, "tail_postings": v[1].value, "wide_rows": v[2].value}
 
+    def ht_multiplied_words(self):
+        """Words of the head / tail image knn_scan_ht multiplies per query tile: 64 x the exact element counts of every
+        slice's widest row (locrec_knn_ht_multiplied_words); head_words of ht_image_info() counts the stored ones."""
+        v = C.c_int64()
+        L.check(L.lib().locrec_knn_ht_multiplied_words(self._h, C.byref(v)))
+        return v.value
+
+    def ht_slice_counts(self):
+        """(place, category) element counts of every slice's widest row, as knn_scan_ht reads them: int32 array [slices, 2]."""
+        ns = C.c_int64()
+        L.check(L.lib().locrec_knn_ht_slice_counts(self._h, 0, None, None, C.byref(ns)))
+        p, c = np.zeros(ns.value, np.int32), np.zeros(ns.value, np.int32)
+        if ns.value:
+            L.check(L.lib().locrec_knn_ht_slice_counts(self._h, ns.value, p.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                       c.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(ns)))
+        return np.stack([p, c], axis=1)
+
     def scan_plan(self):
         """Plan of the last batched scan: kernel (1 = knn_scan, 2 = knn_scan_ht, 3 = knn_scan in head/tail mode), mode, query tile, waves."""
         v = [C.c_int32() for _ in range(4)]

@@ -5,6 +5,8 @@
                                instruction CLASS split of the batched scan and the measured issue cost of every class
   <out>/<round>_pmc_<leg>.txt  the per-kernel counter means of every pass, human readable
   <out>/<round>_valu_classes.txt  the derivation of the mix-weighted issue peak, as a table
+  <out>/<round>_opcode_classes.json  which class counter each microbenchmark opcode lands in: written when the pmc dir
+                               has the ubench/ passes, read (with <round>_ubench_valu.log) when it has not
 
 usage: make_pmc_json.py <pmc dir with knn/ sg/ scan1/ [ubench/] sub-directories> <out dir> [round tag, default r03]
 """
@@ -66,7 +68,7 @@ def ubench_table(out, tag):
     return tab
 
 
-def valu_mix(means_knn, kernel, ub_means, cycles, fh, image=None):
+def valu_mix(means_knn, kernel, ub_means, cycles, fh, image=None, landed_before=None):
     """The VALU instructions of one launch split by the SQ's class counters, each class priced with the issue cost the
     microbenchmark measured for the opcodes of that class the scan uses; -> dict for the json.
     Which counter an opcode lands in is read off the same counters on the microbenchmark's own kernels."""
@@ -83,6 +85,8 @@ def valu_mix(means_knn, kernel, ub_means, cycles, fh, image=None):
             continue
         landed[name] = {c: round(v.get("SQ_INSTS_VALU_" + c, 0.0) / tot, 3) for c in CLASS_COUNTERS
                         if v.get("SQ_INSTS_VALU_" + c, 0.0) > 0.02 * tot}
+    if not landed and landed_before:     # no counter passes of the microbenchmark this time: the committed table
+        landed = landed_before
     # the opcodes of each class that knn_scan_ht issues (csrc/knn_ht.h; static census of its ISA in DESIGN.md section 3)
     # and the issue cost taken for the class: the scan's integer work is v_pk_mad_u16 / SDWA adds / v_alignbit /
     # v_pk_add_u16 (all in the ~4.6-cycle group), its converts are the SDWA v_cvt_f16_u16, MUL_F16 = v_pk_mul_f16,
@@ -100,11 +104,13 @@ def valu_mix(means_knn, kernel, ub_means, cycles, fh, image=None):
     other = max(0.0, total - sum(counts.values()))
     # No class counter counts v_pk_mad_u16, v_pk_add_u16, v_alignbit, v_and, v_mov or v_readlane (see "lands in" below),
     # so the scan's multiply-adds sit in "other".  Their number is exact from the image: every 32-bit word of the head
-    # rows (padding included - the kernel multiplies it too) costs a tile 8 v_pk_mad_u16, i.e. tiles x words / 8 wave
+    # rows that the kernel MULTIPLIES (per slice, the elements of its widest row: locrec_knn_ht_multiplied_words - not
+    # the padding to whole groups of four, which it skips) costs a tile 8 v_pk_mad_u16, i.e. tiles x words / 8 wave
     # instructions per launch; one v_alignbit per bound evaluation = the MUL_F16 count (one v_pk_mul_f16 each).
     extra = {}
-    if image and image.get("head_words"):
-        extra["PK_MAD_U16"] = (min(other, image["tiles"] * image["head_words"] / 8.0), pick("v_pk_mad_u16"))
+    words = (image or {}).get("multiplied_words") or (image or {}).get("head_words")   # (records before the exact counts)
+    if words:
+        extra["PK_MAD_U16"] = (min(other, image["tiles"] * words / 8.0), pick("v_pk_mad_u16"))
         extra["ALIGNBIT"] = (min(other - extra["PK_MAD_U16"][0], counts.get("MUL_F16", 0.0)), pick("v_alignbit_b32"))
         other -= extra["PK_MAD_U16"][0] + extra["ALIGNBIT"][0]
     busy = sum(counts[c] * cost[c] for c in CLASS_COUNTERS) + other * plain + sum(n * cy for n, cy in extra.values())
@@ -137,6 +143,18 @@ def main():
            "how": "rocprofv3 --pmc, one pass per counter set (tools/gpu/r3_profile.sh); means per dispatch"}
     cycles = ubench_table(out, tag)
     ub_means = reduce_leg(os.path.join(src, "ubench"))[0] if os.path.isdir(os.path.join(src, "ubench")) else {}
+    landed_before = None
+    if not ub_means:
+        # The per-opcode issue costs and the class counter every opcode lands in are properties of the chip, not of the
+        # kernel sources: without a run of tools/ubench_valu.hip the committed <tag>_ubench_valu.log and
+        # <tag>_opcode_classes.json (both copied into <out> by the caller) are taken as they are, and the record says so.
+        rec["how"] += (f"; per-opcode issue costs and the opcode -> class table: the committed profiles/{tag}_ubench_valu.log "
+                       f"and profiles/{tag}_opcode_classes.json, not measured again")
+        try:
+            with open(os.path.join(out, f"{tag}_opcode_classes.json")) as fh:
+                landed_before = json.load(fh)
+        except (OSError, ValueError):
+            pass
     for leg, (prefix, key, workload) in LEGS.items():
         d = os.path.join(src, leg)
         if not os.path.isdir(d):
@@ -170,9 +188,12 @@ def main():
                         image = json.load(ih)
                 except OSError:
                     pass
-                mix = valu_mix(means, k, ub_means, cycles, fh, image)
+                mix = valu_mix(means, k, ub_means, cycles, fh, image, landed_before)
             if mix:
                 rec[key]["valu_mix"] = mix
+                if ub_means:     # measured in this run: the table's own file, for the runs that do not measure it
+                    with open(os.path.join(out, f"{tag}_opcode_classes.json"), "w") as fh:
+                        json.dump(mix["opcode_lands_in"], fh, indent=1, sort_keys=True)
     with open(os.path.join(out, f"{tag}_pmc.json"), "w") as fh:
         json.dump(rec, fh, indent=1)
     print(json.dumps(rec, indent=1))

@@ -23,7 +23,8 @@ if what == "knn":
     if os.environ.get("PROBE_OUT"):
         import json
         with open(os.path.join(os.environ["PROBE_OUT"], "image.json"), "w") as f:
-            json.dump({**ix.ht_image_info(), "tiles": (batch + ix.query_tile() - 1) // ix.query_tile()}, f)
+            json.dump({**ix.ht_image_info(), "multiplied_words": ix.ht_multiplied_words(),
+                       "tiles": (batch + ix.query_tile() - 1) // ix.query_tile()}, f)
     ix.close()
 else:
     g = synth.sg_dataset()
