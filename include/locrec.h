@@ -591,6 +591,36 @@ int32_t locrec_sg_pool_recommend_batch(
     int64_t *out_iterations, int32_t *out_converged, int64_t *out_bad_request);
 int32_t locrec_sg_pool_stats(int64_t *out_tile_waves, int64_t *out_rounds, int64_t *out_sweep_launches,
                              int64_t *out_finalize_launches, int64_t *out_polls, int64_t *out_readback_bytes);
+/*
+ * The pool's batch to its end (StochasticRecommenderMain.scala:53-75): request i asks graph graph_index[i] for
+ * vertex_ids[i] and gets the places of target_region_ids[i], top max_recommendations by probability - every member's
+ * tile emitted and ranked on the device in shared launches; no member's x is read back.  ONE places table serves all
+ * members.  The requires, the order of the checks and *out_bad_request are locrec_sg_pool_recommend_batch's (every
+ * graph index, then every vertex, before any device work; on a refusal nothing is written but the position); the
+ * checks on n_places, the request count, max_recommendations and the arrays, and the outputs - rows of stride
+ * max(0, max_recommendations) padded with id -1 / probability 0.0, out_counts, out_row_counts (makeRecommendations'
+ * own row count), out_iterations, out_converged, the last three may be NULL - are
+ * locrec_sg_recommend_ranked_batch's: request i's values equal bit for bit what that call returns for the request on
+ * its member alone, and what locrec_sg_pool_recommend_batch's rows give through locrec_rank_recommendations_batch.
+ * The requests are emitted by tile wave, then member, then the ranked batch's order within a tile; a group of that
+ * order within LOCREC_SG_RANKED_ROW_BUDGET rows is ranked by one call of the segmented ranker (the result does not
+ * depend on the budget).  The pool keeps each member's emit-row image resident from its first ranked call.
+ * Afterwards every member is as after locrec_sg_pool_recommend_batch.
+ * stats: this thread's last ranked pool call (any pointer may be NULL): tile waves, member tiles, rounds, ranker
+ * calls (groups), emit launches, rows emitted into segments, every byte that reached host memory (caps, polls,
+ * states, the ranker's headers, ranked rows, the final tail) and the waits for the stream.
+ */
+int32_t locrec_sg_pool_recommend_ranked_batch(
+    locrec_sg_pool *pool, int64_t n_requests, const int32_t *graph_index, const int64_t *vertex_ids,
+    double alpha, double epsilon, int64_t max_iterations,
+    int64_t n_places, const int64_t *place_ids, const int64_t *place_region_ids,
+    const int64_t *target_region_ids, int64_t max_recommendations,
+    int64_t *out_ids, double *out_probabilities, int64_t *out_counts,
+    int64_t *out_row_counts, int64_t *out_iterations, int32_t *out_converged,
+    int64_t *out_bad_request);
+int32_t locrec_sg_pool_recommend_ranked_batch_stats(
+    int64_t *out_tile_waves, int64_t *out_tiles, int64_t *out_rounds, int64_t *out_groups,
+    int64_t *out_emit_launches, int64_t *out_emitted_rows, int64_t *out_readback_bytes, int64_t *out_host_syncs);
 
 int32_t locrec_sg_set_stream(locrec_sg_graph *graph, void *hip_stream);
 int32_t locrec_sg_synchronize(locrec_sg_graph *graph);

@@ -17,7 +17,8 @@
 //   finalize      ONE sg_finalize_pool launch per round, grid (kParts, graphs of the wave)
 //   poll          ONE sg_poll_pool launch on sg_batch_tiles' schedule: every tile's all_done, ANDed, into a pinned word
 //   read-back     ONE sg_pack_pool launch per tile wave: every graph's packed image (sg_pack_batch's) at the graph's offset
-//                 of the pool's pinned buffer, one synchronisation; then sg_batch_host_rows per graph
+//                 of the pool's pinned buffer, one synchronisation; then sg_batch_host_rows per graph.  What happens to a
+//                 finished wave is a parameter of sg_pool_waves: the ranked pool (sg_pool_ranked.h) emits and ranks instead
 //
 // The bodies are sg_batch.hip's (sg_sweep_batch_body and friends), on each graph's own batch buffers (PA4 / XL / D2W /
 // fused_conv) - the order of operations per column is the batch's, which is the single request's: request i's rows are
@@ -127,6 +128,7 @@ struct locrec_sg_pool {
     int32_t *h_poll = nullptr;  // pinned: sg_poll_pool's answer
     int32_t *h_poll_dev = nullptr;
     DevBuf<int32_t> poll_word;  // ... where the pinned word has no device address
+    std::shared_ptr<void> ranked;  // the members' resident emit-row images (sg_pool_ranked.h), built at their first ranked call
     ~locrec_sg_pool()
     {
         if (done) (void)hipEventDestroy(done);
@@ -230,14 +232,26 @@ struct SgPoolMember {
     std::vector<double> both;  // the plain-copy path's two parities of x
 };
 
-// Every tile wave of a call: set-up, rounds and polls, read-back.  `act` lists the members with requests.
+// A tile wave whose last round has been launched: what its consumer gets
+struct SgPoolWave {
+    size_t k;                             // the wave: member j iterates its targets uniq[k * tile_max ..)
+    const std::vector<int32_t> &members;  // in member order
+    const std::vector<int> &nb;           // targets of each member's tile
+    const SgPoolTile *tiles, *tiles_dev;  // the wave's table, a row per member
+    size_t pack_bytes;                    // of all packed images side by side
+    unsigned pack_blocks;
+};
+
+// Every tile wave of a call: set-up, rounds and polls, then consume(wave) - after the wave's last round and before the
+// next wave's set-up overwrites x and the tables; it returns with the stream synchronised.  `act` lists the members with
+// requests.
+template <class Consume>
 int32_t sg_pool_waves(locrec_sg_pool *pool, const std::vector<int32_t> &act, std::vector<SgPoolMember> &mem, double alpha,
-                      double epsilon, int64_t max_iterations, SgPoolStats &stats)
+                      double epsilon, int64_t max_iterations, SgPoolStats &stats, Consume &&consume)
 {
     hipStream_t s = pool->stream;
     const double eps2 = epsilon * epsilon;  // :40
     const bool poll = epsilon > 0 && max_iterations > 4;
-    const bool packed = !pool->no_pack && pool->h_pack_dev != nullptr;
     size_t nwaves = 0;
     for (const int32_t gi : act) {
         const size_t tm = (size_t)sg_batch_tile_max(pool->graphs[(size_t)gi]);
@@ -249,8 +263,7 @@ int32_t sg_pool_waves(locrec_sg_pool *pool, const std::vector<int32_t> &act, std
     const SgPoolTile *tiles_dev = reinterpret_cast<const SgPoolTile *>(pool->tab_dev.p);
     const SgBatchBegin *begins_dev = reinterpret_cast<const SgBatchBegin *>(pool->tab_dev.p + pool->off_begin);
     const SgPoolView *views_dev = reinterpret_cast<const SgPoolView *>(pool->tab_dev.p + pool->off_views);
-    std::vector<unsigned char> own;  // the plain-copy path's images
-    std::vector<int32_t> wave;       // the members of this tile wave
+    std::vector<int32_t> wave;  // the members of this tile wave
     std::vector<int> wave_nb;
     for (size_t k = 0; k < nwaves; ++k) {
         wave.clear();
@@ -359,32 +372,87 @@ int32_t sg_pool_waves(locrec_sg_pool *pool, const std::vector<int32_t> &act, std
                 next_check += next_check < 8 ? 2 : (next_check < 16 ? 4 : kCheckEvery);
             }
         }
-        // the wave's read-back: one pack launch and one synchronisation for all its graphs
-        const unsigned char *host = nullptr;
-        if (packed && pool->h_pack_bytes >= pack_bytes) {
-            hipLaunchKernelGGL(sg_pack_pool, dim3(pack_blocks, nw), dim3(256), 0, s, tiles_dev, pool->h_pack_dev);
-            LOCREC_HIP_TRY(hipStreamSynchronize(s));
-            host = pool->h_pack;
-        } else {
-            own.resize(pack_bytes);
-            for (unsigned j = 0; j < nw; ++j)
-                LOCREC_TRY(sg_batch_copy_enqueue(pool->graphs[(size_t)wave[j]], s, own.data() + tiles[j].pack_off,
-                                                 mem[(size_t)wave[j]].both));
-            LOCREC_HIP_TRY(hipStreamSynchronize(s));
-            for (unsigned j = 0; j < nw; ++j)
-                sg_batch_copy_assemble(pool->graphs[(size_t)wave[j]]->nlive, own.data() + tiles[j].pack_off,
-                                       mem[(size_t)wave[j]].both);
-            host = own.data();
+        LOCREC_TRY(consume(SgPoolWave{k, wave, wave_nb, tiles, tiles_dev, pack_bytes, pack_blocks}));
+    }
+    return LOCREC_OK;
+}
+
+// Every graph index, then isVertexExist (:70-77) for every request, before any device work: the members' distinct
+// targets, the members with requests (`act`, in order of appearance) and request -> its entry of its member's uniq.  On a
+// refusal nothing is written but *out_bad_request (when given): the position of the first offending request; else -1.
+int32_t sg_pool_requests(const locrec_sg_pool *pool, int64_t n_requests, const int32_t *graph_index, const int64_t *vertex_ids,
+                         std::vector<SgPoolMember> &mem, std::vector<int32_t> &act, std::vector<int32_t> &uniq_of,
+                         int64_t *out_bad_request)
+{
+    const int32_t ng = (int32_t)pool->graphs.size();
+    for (int64_t i = 0; i < n_requests; ++i)
+        if (graph_index[i] < 0 || graph_index[i] >= ng) {
+            if (out_bad_request) *out_bad_request = i;
+            return fail(LOCREC_E_INVALID_ARG, "request %lld names graph %d: the pool holds graphs 0 .. %d", (long long)i,
+                        graph_index[i], ng - 1);
         }
-        LOCREC_HIP_TRY(hipGetLastError());
-        stats.readback_bytes += (int64_t)pack_bytes;
-        for (unsigned j = 0; j < nw; ++j) {
-            locrec_sg_graph *g = pool->graphs[(size_t)wave[j]];
-            SgPoolMember &m = mem[(size_t)wave[j]];
-            LOCREC_TRY(sg_batch_host_rows(g, host + tiles[j].pack_off, m.uniq, k * (size_t)sg_batch_tile_max(g), wave_nb[j], eps2,
-                                          max_iterations, m.res));
+    mem = std::vector<SgPoolMember>((size_t)ng);
+    act.clear();
+    uniq_of.assign((size_t)n_requests, 0);
+    for (int64_t i = 0; i < n_requests; ++i) {
+        const int32_t tv = sg_vertex_index(pool->graphs[(size_t)graph_index[i]], vertex_ids[i]);
+        if (tv < 0) {
+            if (out_bad_request) *out_bad_request = i;
+            return fail(LOCREC_E_NOT_FOUND, "No such vertex in the graph: %lld", (long long)vertex_ids[i]);
+        }
+        SgPoolMember &m = mem[(size_t)graph_index[i]];
+        if (m.uniq.empty()) act.push_back(graph_index[i]);
+        auto ins = m.seen.emplace(tv, (int32_t)m.uniq.size());
+        if (ins.second) m.uniq.push_back(tv);
+        uniq_of[(size_t)i] = ins.first->second;
+    }
+    if (out_bad_request) *out_bad_request = -1;
+    return LOCREC_OK;
+}
+
+// In front of a call's waves: the members' own work is over, `act` is in member order, its members have their batch
+// buffers and their patched slots are the call's
+int32_t sg_pool_begin_call(locrec_sg_pool *pool, std::vector<int32_t> &act, std::vector<SgPoolMember> &mem)
+{
+    LOCREC_HIP_TRY(hipSetDevice(pool->device));
+    // whatever the members were doing on their own streams is over before the pool's first launch
+    for (locrec_sg_graph *g : pool->graphs) LOCREC_HIP_TRY(hipStreamSynchronize(g->stream));
+    std::sort(act.begin(), act.end());  // member order: the tables' rows and the launches' blocks follow it
+    for (const int32_t gi : act) {
+        locrec_sg_graph *g = pool->graphs[(size_t)gi];
+        LOCREC_TRY(sg_batch_buffers(g, pool->stream));
+        sg_batch_take_patched(g, mem[(size_t)gi].pointed);
+    }
+    return LOCREC_OK;
+}
+
+// Behind a call's waves, whatever their status: every member's slots back at D, the members' streams behind the pool's
+int32_t sg_pool_end_call(locrec_sg_pool *pool, const std::vector<int32_t> &act, const std::vector<SgPoolMember> &mem,
+                         int32_t status)
+{
+    hipStream_t s = pool->stream;
+    // every member's slots back at D in one more set-up launch: its column array is as a fresh handle's
+    {
+        SgBatchBegin *begins = reinterpret_cast<SgBatchBegin *>(pool->tab_host.data() + pool->off_begin);
+        unsigned nr = 0;
+        for (const int32_t gi : act)
+            if (!mem[(size_t)gi].pointed.empty()) sg_batch_restore_row(pool->graphs[(size_t)gi], mem[(size_t)gi].pointed, begins[nr++]);
+        if (nr > 0) {
+            // (the last wave's consumer has synchronised the stream: nothing reads the tables any more)
+            const hipError_t e = hipMemcpyAsync(pool->tab_dev.p + pool->off_begin, begins, nr * sizeof(SgBatchBegin),
+                                                hipMemcpyHostToDevice, s);
+            if (e == hipSuccess)
+                hipLaunchKernelGGL(sg_begin_pool, dim3(kBeginBlocks, nr), dim3(256), 0, s,
+                                   reinterpret_cast<const SgBatchBegin *>(pool->tab_dev.p + pool->off_begin));
+            else if (status == LOCREC_OK)
+                status = fail(LOCREC_E_DEVICE, "hipMemcpyAsync failed: %s", hipGetErrorName(e));
         }
     }
+    // a request on a member synchronises ITS stream: make that stream wait for the pool's launches (as group_run does)
+    LOCREC_HIP_TRY(hipEventRecord(pool->done, s));
+    for (locrec_sg_graph *g : pool->graphs) LOCREC_HIP_TRY(hipStreamWaitEvent(g->stream, pool->done, 0));
+    LOCREC_TRY(status);
+    LOCREC_HIP_TRY(hipGetLastError());
     return LOCREC_OK;
 }
 
@@ -400,30 +468,9 @@ extern "C" int32_t locrec_sg_pool_recommend_batch(locrec_sg_pool *pool, int64_t 
     if (n_requests < 0 || (n_requests > 0 && (!graph_index || !vertex_ids)) || !out_offsets || !inout_capacity)
         return fail(LOCREC_E_INVALID_ARG, "bad arguments");
     LOCREC_TRY(sg_batch_requires(epsilon, max_iterations));
-    // every graph index, then isVertexExist (:70-77) for every request, before any device work
-    const int32_t ng = (int32_t)pool->graphs.size();
-    for (int64_t i = 0; i < n_requests; ++i)
-        if (graph_index[i] < 0 || graph_index[i] >= ng) {
-            if (out_bad_request) *out_bad_request = i;
-            return fail(LOCREC_E_INVALID_ARG, "request %lld names graph %d: the pool holds graphs 0 .. %d", (long long)i,
-                        graph_index[i], ng - 1);
-        }
-    std::vector<SgPoolMember> mem((size_t)ng);
-    std::vector<int32_t> act;                    // members with requests, in order of appearance
-    std::vector<int32_t> uniq_of((size_t)n_requests);  // request -> its entry of its member's uniq
-    for (int64_t i = 0; i < n_requests; ++i) {
-        const int32_t tv = sg_vertex_index(pool->graphs[(size_t)graph_index[i]], vertex_ids[i]);
-        if (tv < 0) {
-            if (out_bad_request) *out_bad_request = i;
-            return fail(LOCREC_E_NOT_FOUND, "No such vertex in the graph: %lld", (long long)vertex_ids[i]);
-        }
-        SgPoolMember &m = mem[(size_t)graph_index[i]];
-        if (m.uniq.empty()) act.push_back(graph_index[i]);
-        auto ins = m.seen.emplace(tv, (int32_t)m.uniq.size());
-        if (ins.second) m.uniq.push_back(tv);
-        uniq_of[(size_t)i] = ins.first->second;
-    }
-    if (out_bad_request) *out_bad_request = -1;
+    std::vector<SgPoolMember> mem;
+    std::vector<int32_t> act, uniq_of;
+    LOCREC_TRY(sg_pool_requests(pool, n_requests, graph_index, vertex_ids, mem, act, uniq_of, out_bad_request));
     SgPoolStats &stats = sg_pool_stats();
     stats = SgPoolStats{};
     if (n_requests == 0) {
@@ -432,40 +479,43 @@ extern "C" int32_t locrec_sg_pool_recommend_batch(locrec_sg_pool *pool, int64_t 
         return LOCREC_OK;
     }
     if (max_iterations > INT32_MAX) max_iterations = INT32_MAX;
-    LOCREC_HIP_TRY(hipSetDevice(pool->device));
+    LOCREC_TRY(sg_pool_begin_call(pool, act, mem));
+    for (const int32_t gi : act) mem[(size_t)gi].res.resize(mem[(size_t)gi].uniq.size());
     hipStream_t s = pool->stream;
-    // whatever the members were doing on their own streams is over before the pool's first launch
-    for (locrec_sg_graph *g : pool->graphs) LOCREC_HIP_TRY(hipStreamSynchronize(g->stream));
-    std::sort(act.begin(), act.end());  // member order: the tables' rows and the launches' blocks follow it
-    for (const int32_t gi : act) {
-        locrec_sg_graph *g = pool->graphs[(size_t)gi];
-        LOCREC_TRY(sg_batch_buffers(g, s));
-        sg_batch_take_patched(g, mem[(size_t)gi].pointed);
-        mem[(size_t)gi].res.resize(mem[(size_t)gi].uniq.size());
-    }
-    int32_t status = sg_pool_waves(pool, act, mem, alpha, epsilon, max_iterations, stats);
-    // every member's slots back at D in one more set-up launch: its column array is as a fresh handle's
-    {
-        SgBatchBegin *begins = reinterpret_cast<SgBatchBegin *>(pool->tab_host.data() + pool->off_begin);
-        unsigned nr = 0;
-        for (const int32_t gi : act)
-            if (!mem[(size_t)gi].pointed.empty()) sg_batch_restore_row(pool->graphs[(size_t)gi], mem[(size_t)gi].pointed, begins[nr++]);
-        if (nr > 0) {
-            // (the last wave's read-back has synchronised the stream: nothing reads the tables any more)
-            const hipError_t e = hipMemcpyAsync(pool->tab_dev.p + pool->off_begin, begins, nr * sizeof(SgBatchBegin),
-                                                hipMemcpyHostToDevice, s);
-            if (e == hipSuccess)
-                hipLaunchKernelGGL(sg_begin_pool, dim3(kBeginBlocks, nr), dim3(256), 0, s,
-                                   reinterpret_cast<const SgBatchBegin *>(pool->tab_dev.p + pool->off_begin));
-            else if (status == LOCREC_OK)
-                status = fail(LOCREC_E_DEVICE, "hipMemcpyAsync failed: %s", hipGetErrorName(e));
+    const double eps2 = epsilon * epsilon;  // :40
+    const bool packed = !pool->no_pack && pool->h_pack_dev != nullptr;
+    std::vector<unsigned char> own;  // the plain-copy path's images
+    // the wave's read-back: one pack launch and one synchronisation for all its graphs
+    auto read_back = [&](const SgPoolWave &w) -> int32_t {
+        const unsigned nw = (unsigned)w.members.size();
+        const unsigned char *host = nullptr;
+        if (packed && pool->h_pack_bytes >= w.pack_bytes) {
+            hipLaunchKernelGGL(sg_pack_pool, dim3(w.pack_blocks, nw), dim3(256), 0, s, w.tiles_dev, pool->h_pack_dev);
+            LOCREC_HIP_TRY(hipStreamSynchronize(s));
+            host = pool->h_pack;
+        } else {
+            own.resize(w.pack_bytes);
+            for (unsigned j = 0; j < nw; ++j)
+                LOCREC_TRY(sg_batch_copy_enqueue(pool->graphs[(size_t)w.members[j]], s, own.data() + w.tiles[j].pack_off,
+                                                 mem[(size_t)w.members[j]].both));
+            LOCREC_HIP_TRY(hipStreamSynchronize(s));
+            for (unsigned j = 0; j < nw; ++j)
+                sg_batch_copy_assemble(pool->graphs[(size_t)w.members[j]]->nlive, own.data() + w.tiles[j].pack_off,
+                                       mem[(size_t)w.members[j]].both);
+            host = own.data();
         }
-    }
-    // a request on a member synchronises ITS stream: make that stream wait for the pool's launches (as group_run does)
-    LOCREC_HIP_TRY(hipEventRecord(pool->done, s));
-    for (locrec_sg_graph *g : pool->graphs) LOCREC_HIP_TRY(hipStreamWaitEvent(g->stream, pool->done, 0));
-    LOCREC_TRY(status);
-    LOCREC_HIP_TRY(hipGetLastError());
+        LOCREC_HIP_TRY(hipGetLastError());
+        stats.readback_bytes += (int64_t)w.pack_bytes;
+        for (unsigned j = 0; j < nw; ++j) {
+            locrec_sg_graph *g = pool->graphs[(size_t)w.members[j]];
+            SgPoolMember &m = mem[(size_t)w.members[j]];
+            LOCREC_TRY(sg_batch_host_rows(g, host + w.tiles[j].pack_off, m.uniq, w.k * (size_t)sg_batch_tile_max(g), w.nb[j], eps2,
+                                          max_iterations, m.res));
+        }
+        return LOCREC_OK;
+    };
+    const int32_t status = sg_pool_waves(pool, act, mem, alpha, epsilon, max_iterations, stats, read_back);
+    LOCREC_TRY(sg_pool_end_call(pool, act, mem, status));
     return sg_batch_output(
         n_requests, [&](int64_t i) { return SgBatchRowRef{&mem[(size_t)graph_index[i]].res, (size_t)uniq_of[(size_t)i]}; },
         out_offsets, out_ids, out_probs, inout_capacity, out_iterations, out_converged);

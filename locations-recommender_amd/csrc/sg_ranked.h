@@ -29,9 +29,11 @@
 //   sg_rk_popcount  8 / 4 / 0
 //   sg_rk_row_ids   4 / 0 / 0
 //   sg_rk_state     14 / 0 / 0
+// (the bodies are __device__ functions that the pool's kernels in sg_pool_ranked.h share: the figures did not move)
 #pragma once
 
 #include "rank_batch.h"
+#include "sg_rk_plan.h"
 
 namespace {
 
@@ -80,12 +82,13 @@ __device__ __forceinline__ int64_t rk_lower_bound(const int64_t *__restrict__ a,
     return lo;
 }
 
-// one thread per row of the places table: the bit (its region, its emit row), when it has both
-__global__ __launch_bounds__(kRkThreads) void sg_rk_members(int64_t n_places, const int64_t *__restrict__ place_ids,
-                                                           const int64_t *__restrict__ place_regions, int64_t n_regions,
-                                                           const int64_t *__restrict__ regions, int64_t m,
-                                                           const int64_t *__restrict__ sid, const int32_t *__restrict__ srow,
-                                                           int64_t words, unsigned long long *bits)
+// one thread per row of the places table: the bit (its region, its emit row), when it has both.  The bodies of this
+// file's kernels are __device__ functions that the pool's kernels (sg_pool_ranked.h) call too.
+__device__ __forceinline__ void sg_rk_members_body(int64_t n_places, const int64_t *__restrict__ place_ids,
+                                                   const int64_t *__restrict__ place_regions, int64_t n_regions,
+                                                   const int64_t *__restrict__ regions, int64_t m,
+                                                   const int64_t *__restrict__ sid, const int32_t *__restrict__ srow,
+                                                   int64_t words, unsigned long long *bits)
 {
     const int64_t i = (int64_t)blockIdx.x * kRkThreads + threadIdx.x;
     if (i >= n_places) return;
@@ -98,25 +101,40 @@ __global__ __launch_bounds__(kRkThreads) void sg_rk_members(int64_t n_places, co
     atomicOr(&bits[r * words + (e >> 6)], 1ull << (e & 63));
 }
 
-// caps[r] = bits set in region r's bitmap; one block per region
-__global__ __launch_bounds__(kRkThreads) void sg_rk_popcount(int64_t words, const unsigned long long *__restrict__ bits,
-                                                            unsigned long long *__restrict__ caps)
+__global__ __launch_bounds__(kRkThreads) void sg_rk_members(int64_t n_places, const int64_t *__restrict__ place_ids,
+                                                           const int64_t *__restrict__ place_regions, int64_t n_regions,
+                                                           const int64_t *__restrict__ regions, int64_t m,
+                                                           const int64_t *__restrict__ sid, const int32_t *__restrict__ srow,
+                                                           int64_t words, unsigned long long *bits)
+{
+    sg_rk_members_body(n_places, place_ids, place_regions, n_regions, regions, m, sid, srow, words, bits);
+}
+
+// *cap = bits set in row[0 .. words): one block
+__device__ __forceinline__ void sg_rk_popcount_body(int64_t words, const unsigned long long *__restrict__ row,
+                                                    unsigned long long *__restrict__ cap)
 {
     __shared__ unsigned int total;
     if (threadIdx.x == 0) total = 0;
     __syncthreads();
-    const unsigned long long *row = bits + (int64_t)blockIdx.x * words;
     unsigned int mine = 0;
     for (int64_t w = threadIdx.x; w < words; w += kRkThreads) mine += (unsigned int)__popcll(row[w]);
     if (mine) atomicAdd(&total, mine);
     __syncthreads();
-    if (threadIdx.x == 0) caps[blockIdx.x] = total;
+    if (threadIdx.x == 0) *cap = total;
+}
+
+// caps[r] = bits set in region r's bitmap; one block per region
+__global__ __launch_bounds__(kRkThreads) void sg_rk_popcount(int64_t words, const unsigned long long *__restrict__ bits,
+                                                            unsigned long long *__restrict__ caps)
+{
+    sg_rk_popcount_body(words, bits + (int64_t)blockIdx.x * words, caps + blockIdx.x);
 }
 
 // The tile's read-back: the state, and per column the total of its last executed sweep's block sums (the butterfly of
 // sg_finalize_batch's own decision; host_total_d2 is the same sum).  One wave per column.
-__global__ __launch_bounds__(64 * kBatchB) void sg_rk_state(const SgBatchState *__restrict__ st, const double *__restrict__ parts,
-                                                           unsigned char *out)
+__device__ __forceinline__ void sg_rk_state_body(const SgBatchState *__restrict__ st, const double *__restrict__ parts,
+                                                 unsigned char *out)
 {
     const int lane = threadIdx.x & 63, b = threadIdx.x >> 6;
     const int sweeps = st->sweeps[b];
@@ -126,7 +144,63 @@ __global__ __launch_bounds__(64 * kBatchB) void sg_rk_state(const SgBatchState *
     if (threadIdx.x < sizeof(SgBatchState) / 4)
         reinterpret_cast<int32_t *>(out)[threadIdx.x] = reinterpret_cast<const int32_t *>(st)[threadIdx.x];
 }
+
+__global__ __launch_bounds__(64 * kBatchB) void sg_rk_state(const SgBatchState *__restrict__ st, const double *__restrict__ parts,
+                                                           unsigned char *out)
+{
+    sg_rk_state_body(st, parts, out);
+}
 static_assert(kParts == 64, "one lane per block sum");
+
+// The emit rows of a graph: m searchable ids, ascending (sid), and the emit row of each (srow).  With dead_rows the
+// source-only vertices follow the T live rows in ascending vertex order, and sid is the handle's own vertex list.
+struct SgRkRows {
+    std::vector<int64_t> sid_own;
+    std::vector<int32_t> srow;
+    const int64_t *sid = nullptr;
+    int64_t m = 0;
+    bool dead_rows = false;
+};
+
+void sg_rk_rows(locrec_sg_graph *g, bool dead_rows, SgRkRows &r)
+{
+    const int32_t T = g->nlive;
+    if (g->live_sorted.size() != (size_t)T) {
+        g->live_sorted.clear();
+        for (int64_t v = 0; v < g->nv; ++v)
+            if (g->live_of[v] >= 0) g->live_sorted.push_back((int32_t)v);
+    }
+    r.dead_rows = dead_rows;
+    r.m = dead_rows ? g->nv : (int64_t)T;  // emit rows = searchable ids
+    r.sid_own.clear();
+    r.srow.assign((size_t)r.m, 0);
+    r.sid = g->vid.data();
+    if (dead_rows) {
+        int32_t next_dead = T;
+        for (int64_t v = 0; v < r.m; ++v) r.srow[(size_t)v] = g->live_of[v] >= 0 ? g->live_of[v] : next_dead++;
+    } else {
+        r.sid_own.resize((size_t)r.m);
+        for (int64_t i = 0; i < r.m; ++i) {
+            r.sid_own[(size_t)i] = g->vid[g->live_sorted[(size_t)i]];
+            r.srow[(size_t)i] = g->live_of[g->live_sorted[(size_t)i]];
+        }
+        r.sid = r.sid_own.data();
+    }
+}
+
+// the emit row of vertex tv (-1: it has none)
+inline int32_t sg_rk_row_of(const locrec_sg_graph *g, const SgRkRows &r, int32_t tv)
+{
+    if (g->live_of[tv] >= 0) return g->live_of[tv];
+    return r.dead_rows ? r.srow[(size_t)tv] : -1;
+}
+
+// D's value after a sweep is sg_next_x(0, false): never positive; before the first it is 1/V
+inline bool sg_rk_dead_rows(double alpha, int64_t max_iterations)
+{
+    const double xd = 0.0 * alpha + 0.0 * (1 - alpha);
+    return max_iterations == 0 || xd > 0;
+}
 
 struct SgEmitTile {
     int32_t col_trow[kBatchB];  // emit row of column b's target (-1: it has none), never a row of that column's result
@@ -135,17 +209,18 @@ struct SgEmitTile {
     int64_t xstride;
 };
 
-__global__ __launch_bounds__(kRkThreads) void sg_rk_emit(
-    const SgEmitTile tl, const SgBatchState *__restrict__ st, const double *__restrict__ xbuf, const int64_t *__restrict__ eid,
+// bx: the block's position among the emit blocks of its graph
+__device__ __forceinline__ void sg_rk_emit_body(
+    const SgEmitTile &tl, const SgBatchState *__restrict__ st, const double *__restrict__ xbuf, const int64_t *__restrict__ eid,
     const unsigned long long *__restrict__ bits, const int64_t words, const int32_t k0, const int32_t k1,
     const int32_t *__restrict__ req_col, const int32_t *__restrict__ req_trow, const int32_t *__restrict__ req_bm,
     const int64_t *__restrict__ seg_begin, unsigned long long *seg_len, const int64_t rows_cap, int64_t *__restrict__ seg_ids,
-    double *__restrict__ seg_probs, unsigned long long *col_rows)
+    double *__restrict__ seg_probs, unsigned long long *col_rows, const int bx)
 {
     __shared__ double xs[kRkThreads / 64][kBatchB][64];  // [wave][column][lane]: each lane reads back only what it wrote
     __shared__ unsigned int colcnt[kBatchB];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int e0 = (blockIdx.x * (kRkThreads / 64) + wave) * 64;  // (a multiple of 64: one bitmap word per wave)
+    const int e0 = (bx * (kRkThreads / 64) + wave) * 64;  // (a multiple of 64: one bitmap word per wave)
     const int e = e0 + lane;
     if (threadIdx.x < kBatchB) colcnt[threadIdx.x] = 0;
     __syncthreads();
@@ -211,6 +286,17 @@ __global__ __launch_bounds__(kRkThreads) void sg_rk_emit(
         atomicAdd(&col_rows[threadIdx.x], (unsigned long long)colcnt[threadIdx.x]);
 }
 
+__global__ __launch_bounds__(kRkThreads) void sg_rk_emit(
+    const SgEmitTile tl, const SgBatchState *__restrict__ st, const double *__restrict__ xbuf, const int64_t *__restrict__ eid,
+    const unsigned long long *__restrict__ bits, const int64_t words, const int32_t k0, const int32_t k1,
+    const int32_t *__restrict__ req_col, const int32_t *__restrict__ req_trow, const int32_t *__restrict__ req_bm,
+    const int64_t *__restrict__ seg_begin, unsigned long long *seg_len, const int64_t rows_cap, int64_t *__restrict__ seg_ids,
+    double *__restrict__ seg_probs, unsigned long long *col_rows)
+{
+    sg_rk_emit_body(tl, st, xbuf, eid, bits, words, k0, k1, req_col, req_trow, req_bm, seg_begin, seg_len, rows_cap, seg_ids,
+                    seg_probs, col_rows, (int)blockIdx.x);
+}
+
 }  // namespace
 
 extern "C" int32_t locrec_sg_recommend_ranked_batch(locrec_sg_graph *g, int64_t n_targets, const int64_t *vertex_ids, double alpha,
@@ -242,33 +328,13 @@ extern "C" int32_t locrec_sg_recommend_ranked_batch(locrec_sg_graph *g, int64_t 
     const int32_t T = g->nlive;
     const int tile_max = sg_batch_tile_max(g);
 
-    // ---- the emit rows.  D's value after a sweep is sg_next_x(0, false): never positive; before the first it is 1/V.
-    const double xd = 0.0 * alpha + 0.0 * (1 - alpha);
-    const bool dead_rows = max_iterations == 0 || xd > 0;
-    if (g->live_sorted.size() != (size_t)T) {
-        g->live_sorted.clear();
-        for (int64_t v = 0; v < g->nv; ++v)
-            if (g->live_of[v] >= 0) g->live_sorted.push_back((int32_t)v);
-    }
-    const int64_t m = dead_rows ? g->nv : (int64_t)T;  // emit rows = searchable ids
-    std::vector<int64_t> sid_own;
-    std::vector<int32_t> srow((size_t)m);
-    const int64_t *sid = g->vid.data();
-    if (dead_rows) {
-        int32_t next_dead = T;
-        for (int64_t v = 0; v < m; ++v) srow[(size_t)v] = g->live_of[v] >= 0 ? g->live_of[v] : next_dead++;
-    } else {
-        sid_own.resize((size_t)m);
-        for (int64_t i = 0; i < m; ++i) {
-            sid_own[(size_t)i] = g->vid[g->live_sorted[(size_t)i]];
-            srow[(size_t)i] = g->live_of[g->live_sorted[(size_t)i]];
-        }
-        sid = sid_own.data();
-    }
-    auto emit_row_of = [&](int32_t tv) -> int32_t {
-        if (g->live_of[tv] >= 0) return g->live_of[tv];
-        return dead_rows ? srow[(size_t)tv] : -1;
-    };
+    // ---- the emit rows
+    SgRkRows er;
+    sg_rk_rows(g, sg_rk_dead_rows(alpha, max_iterations), er);
+    const int64_t m = er.m;
+    const int64_t *sid = er.sid;
+    const std::vector<int32_t> &srow = er.srow;
+    auto emit_row_of = [&](int32_t tv) -> int32_t { return sg_rk_row_of(g, er, tv); };
     const int64_t words = std::max<int64_t>(1, (m + 63) / 64);
 
     // ---- the requests in emit order (by tile, then input position) and the distinct target regions
@@ -334,23 +400,12 @@ extern "C" int32_t locrec_sg_recommend_ranked_batch(locrec_sg_graph *g, int64_t 
     stats.readback_bytes += R * 8;
 
     // ---- the groups: request k's segment has room caps[its region]; a group's segments share the row buffer
-    const int64_t budget = sg_ranked_row_budget();
-    std::vector<int64_t> seg_begin((size_t)n), group_end;  // group_end[i]: one past the last request of group i
-    int64_t max_rows = 1, max_req = 1, max_cap = 0, cur_rows = 0, cur_first = 0;
-    for (int64_t k = 0; k < n; ++k) {
-        const int64_t c = caps[(size_t)req[(size_t)(2 * n + k)]];
-        if (k > cur_first && cur_rows + c > budget) {
-            group_end.push_back(k);
-            cur_first = k;
-            cur_rows = 0;
-        }
-        seg_begin[(size_t)k] = cur_rows;
-        cur_rows += c;
-        max_rows = std::max(max_rows, cur_rows);
-        max_req = std::max(max_req, k + 1 - cur_first);
-        max_cap = std::max(max_cap, c);
-    }
-    group_end.push_back(n);
+    std::vector<int64_t> cap_k((size_t)n);
+    for (int64_t k = 0; k < n; ++k) cap_k[(size_t)k] = caps[(size_t)req[(size_t)(2 * n + k)]];
+    SgRkGroups groups;
+    sg_rk_form_groups(cap_k, sg_ranked_row_budget(), groups);
+    const std::vector<int64_t> &seg_begin = groups.seg_begin, &group_end = groups.group_end;  // one past a group's last request
+    const int64_t max_rows = groups.max_rows, max_req = groups.max_req, max_cap = groups.max_cap;
     if (max_rows >= ((int64_t)1 << 31)) return fail(LOCREC_E_INVALID_ARG, "a request's region has 2^31 places or more");
     const int64_t Nd = std::min(N, max_cap);  // no request has more rows than the largest region: the rest is padding
     LOCREC_HIP_TRY(hipMemcpyAsync(d_seg_begin, seg_begin.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));

@@ -605,8 +605,73 @@ def sg_recommender_requests(data_dir, persons, lines, epsilon, max_iterations, m
     reference wraps each line in Try, :44-49).  pooled=False: one SgGraph.recommend_batch call per distinct graph instead
     of the pool call (the same result; the A/B partner)."""
     from . import _cache, prep
-    from .stochastic import ALPHA, SgGraph, SgPool
+    from .stochastic import ALPHA, SgPool
     _cache.require_gpu_backend("sg_recommender_requests")
+    out, targets, graphs = _sg_resolve_request_lines(data_dir, persons, lines)
+    try:
+        def call(gi, v, live):
+            if not pooled:
+                return _sg_requests_per_graph(graphs, gi, v, ALPHA, epsilon, max_iterations)
+            pool = SgPool(graphs)
+            try:
+                return pool.recommend_batch(gi, v, ALPHA, epsilon, max_iterations)
+            finally:
+                pool.close()
+        live, rows = _sg_call_without_bad_lines(out, targets, call)
+        if live:
+            off, ids, probs, _, _ = rows
+            place_ids, place_regions = load_places(data_dir)
+            regions = np.asarray([targets[i][0][2] for i in live], np.int64)
+            oi, op, cnt = prep.rank_recommendations_batch(off, ids, probs, place_ids, place_regions, regions, max_recommendations)
+            for k, i in enumerate(live):
+                out[i] = (targets[i][0], np.array(oi[k, :cnt[k]]), np.array(op[k, :cnt[k]]))
+    finally:
+        for g in graphs:
+            g.close()  # drops the reference only
+    return out
+
+
+def sg_recommender_requests_ranked(data_dir, persons, lines, epsilon, max_iterations, max_recommendations=10):
+    """sg_recommender_requests with the ranking on the device: the same per-line contract (every line parsed and resolved
+    on its own, graphs from the handle cache, the exception instance per bad line, a line whose vertex its graph lacks
+    recorded and the call repeated without it), served by ONE SgPool.recommend_ranked_batch call with the places table
+    passed once - no graph's probabilities leave the device, max_recommendations rows a line come back.
+    -> the list sg_recommender_requests returns."""
+    from . import _cache
+    from .stochastic import ALPHA, SgPool
+    _cache.require_gpu_backend("sg_recommender_requests_ranked")
+    out, targets, graphs = _sg_resolve_request_lines(data_dir, persons, lines)
+    try:
+        if targets:
+            place_ids, place_regions = load_places(data_dir)
+            pool = SgPool(graphs)
+            try:
+                def call(gi, v, live):
+                    regions = np.asarray([targets[i][0][2] for i in live], np.int64)
+                    return pool.recommend_ranked_batch(gi, v, ALPHA, epsilon, max_iterations, place_ids, place_regions, regions,
+                                                       max_recommendations)
+                live, rows = _sg_call_without_bad_lines(out, targets, call)
+            finally:
+                pool.close()
+            if live:
+                oi, op, cnt, _, _ = rows
+                for k, i in enumerate(live):
+                    out[i] = (targets[i][0], np.array(oi[k, :cnt[k]]), np.array(op[k, :cnt[k]]))
+    finally:
+        for g in graphs:
+            g.close()  # drops the reference only
+    return out
+
+
+def _sg_resolve_request_lines(data_dir, persons, lines):
+    """The line-resolution loop of sg_recommender_requests and sg_recommender_requests_ranked: every line is parsed and
+    resolved on its own (Try { ... } per line, :44-49) and the graph of [home, target] comes from the handle cache, one
+    handle per distinct region set.
+    -> (out, targets, graphs): out aligned with lines, the exception instance at every bad line and None elsewhere;
+    targets[i] = ((person_id, home_region_id, target_region_id), index into graphs) for every good line i.  The caller
+    closes the graphs."""
+    from . import _cache
+    from .stochastic import SgGraph
     out = [None] * len(lines)
     targets, graph_of, graphs, failed = {}, {}, [], {}
     try:
@@ -628,36 +693,29 @@ def sg_recommender_requests(data_dir, persons, lines, epsilon, max_iterations, m
                 targets[i] = (target, graph_of[name])
             except Exception as e:  # Try { ... } per line
                 out[i] = e
-        live = sorted(targets)
-        rows = None
-        while live and rows is None:
-            gi = np.asarray([targets[i][1] for i in live], np.int32)
-            v = np.asarray([targets[i][0][0] for i in live], np.int64)
-            try:
-                if pooled:
-                    pool = SgPool(graphs)
-                    try:
-                        rows = pool.recommend_batch(gi, v, ALPHA, epsilon, max_iterations)
-                    finally:
-                        pool.close()
-                else:
-                    rows = _sg_requests_per_graph(graphs, gi, v, ALPHA, epsilon, max_iterations)
-            except L.IllegalArgumentException as e:
-                bad = getattr(e, "bad_request", -1)
-                if bad < 0:
-                    raise
-                out[live.pop(bad)] = e  # the line's vertex is not in its graph: recorded, the call repeated without it
-        if live:
-            off, ids, probs, _, _ = rows
-            place_ids, place_regions = load_places(data_dir)
-            regions = np.asarray([targets[i][0][2] for i in live], np.int64)
-            oi, op, cnt = prep.rank_recommendations_batch(off, ids, probs, place_ids, place_regions, regions, max_recommendations)
-            for k, i in enumerate(live):
-                out[i] = (targets[i][0], np.array(oi[k, :cnt[k]]), np.array(op[k, :cnt[k]]))
-    finally:
+    except BaseException:
         for g in graphs:
-            g.close()  # drops the reference only
-    return out
+            g.close()
+        raise
+    return out, targets, graphs
+
+
+def _sg_call_without_bad_lines(out, targets, call):
+    """call(graph_index, vertex_ids, live) for the good lines `live`; a line whose vertex is not in its graph (the call
+    raises with bad_request set) is recorded in out and the call repeated without it.  -> (live, the call's result)."""
+    live = sorted(targets)
+    rows = None
+    while live and rows is None:
+        gi = np.asarray([targets[i][1] for i in live], np.int32)
+        v = np.asarray([targets[i][0][0] for i in live], np.int64)
+        try:
+            rows = call(gi, v, live)
+        except L.IllegalArgumentException as e:
+            bad = getattr(e, "bad_request", -1)
+            if bad < 0:
+                raise
+            out[live.pop(bad)] = e  # the line's vertex is not in its graph: recorded, the call repeated without it
+    return live, rows
 
 
 def _sg_requests_per_graph(graphs, graph_index, vertex_ids, alpha, epsilon, max_iterations):

@@ -265,6 +265,7 @@ class SgPool:
         self._h = C.c_void_p()
         L.check(L.lib().locrec_sg_pool_create(arr, len(self.graphs), C.byref(self._h)))
         self._sizes = None
+        self.row_counts = None  # of the last recommend_ranked_batch
 
     def close(self):
         if getattr(self, "_h", None):
@@ -322,6 +323,57 @@ class SgPool:
         x = [C.c_int64() for _ in cls.STATS]
         L.check(L.lib().locrec_sg_pool_stats(*[C.byref(i) for i in x]))
         return dict(zip(cls.STATS, (i.value for i in x)))
+
+    RANKED_STATS = ("tile_waves", "tiles", "rounds", "groups", "emit_launches", "emitted_rows", "readback_bytes", "host_syncs")
+
+    def recommend_ranked_batch(self, graph_index, vertex_ids, alpha, epsilon, max_iterations, place_ids, place_region_ids,
+                               target_region_ids, max_recommendations):
+        """The pool's batch to its end (locrec_sg_pool_recommend_ranked_batch): request i gets the places of
+        target_region_ids[i] that graphs[graph_index[i]] reaches from vertex_ids[i], top max_recommendations by
+        probability; every member's tile is emitted and ranked on the device, no x leaves it.
+        -> (ids[n, W], probabilities[n, W], counts[n], iterations[n], converged[n] bool), rows padded with -1 / 0.0 and
+        W = max_recommendations cut to the longest row count of a request, as SgGraph.recommend_ranked_batch returns
+        them; request i equals that call on its member alone.  self.row_counts holds makeRecommendations' own row count
+        per request of the last call.  A failed call raises with `bad_request` set, as recommend_batch does."""
+        import contextlib
+        gi, v = L.as_i32(graph_index), L.as_i64(vertex_ids)
+        pl, reg, tgt = L.as_i64(place_ids), L.as_i64(place_region_ids), L.as_i64(target_region_ids)
+        n = len(v)
+        if len(gi) != n:
+            raise L.IllegalArgumentException("one graph index per vertex is required")
+        if len(reg) != len(pl) or len(tgt) != n:
+            raise L.IllegalArgumentException("one region per place and one target region per vertex are required")
+        with contextlib.ExitStack() as held:
+            for g in self.graphs:  # every member's lock, in member order
+                if getattr(g, "lock", None) is not None:
+                    held.enter_context(g.lock)
+            if self._sizes is None:  # (a handle's vertex and live counts never change)
+                self._sizes = (np.array([g.info()["vertices"] for g in self.graphs], np.int64),
+                               np.array([g.live_count() for g in self.graphs], np.int64))
+            # no request has more rows than its graph has vertices: the stride of the call, cut to W afterwards
+            stride = max(0, min(int(max_recommendations), int(self._sizes[0].max())))
+            oi, op = np.full((n, stride), -1, np.int64), np.zeros((n, stride), np.float64)
+            cnt, rows, its, conv = (np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, np.int32))
+            bad = C.c_int64(-1)
+            try:
+                L.check(L.lib().locrec_sg_pool_recommend_ranked_batch(
+                    self._h, n, L.ptr(gi, C.c_int32), L.ptr(v, C.c_int64), float(alpha), float(epsilon), int(max_iterations),
+                    len(pl), L.ptr(pl, C.c_int64), L.ptr(reg, C.c_int64), L.ptr(tgt, C.c_int64), stride, L.ptr(oi, C.c_int64),
+                    L.ptr(op, C.c_double), L.ptr(cnt, C.c_int64), L.ptr(rows, C.c_int64), L.ptr(its, C.c_int64),
+                    L.ptr(conv, C.c_int32), C.byref(bad)))
+            except L.IllegalArgumentException as e:
+                e.bad_request = bad.value
+                raise
+        self.row_counts = rows
+        width = max(0, min(stride, int(rows.max()) if n else 0))
+        return (np.ascontiguousarray(oi[:, :width]), np.ascontiguousarray(op[:, :width]), cnt, its, conv.astype(bool))
+
+    @classmethod
+    def ranked_stats(cls):
+        """What this thread's last recommend_ranked_batch did (locrec_sg_pool_recommend_ranked_batch_stats)."""
+        x = [C.c_int64() for _ in cls.RANKED_STATS]
+        L.check(L.lib().locrec_sg_pool_recommend_ranked_batch_stats(*[C.byref(i) for i in x]))
+        return dict(zip(cls.RANKED_STATS, (i.value for i in x)))
 
 
 class StochasticRecommender:
