@@ -269,6 +269,57 @@ int32_t locrec_knn_fetch_ranked(
     int64_t *out_place_ids, double *out_estimated_ratings, int64_t *out_counts);
 
 /*
+ * A pool of resident indexes that serves ONE mixed batch of (index, person[, target region]) requests - the queue of
+ * KnnRecommenderMain's loop, whose lines fan out over the indexes of sorted{home, target}
+ * (KnnRecommenderMain.scala:53-67).  A member in the "every positive neighbour" regime (k_nearest >
+ * LOCREC_KNN_BATCH_MAX_K and k_nearest >= its person count - 1: the shipped --k-nearest 2000000) shares its launches
+ * with the others: its distinct requests are cut into tiles of 16, wave w holds the w-th tile of every such member, and
+ * every kernel of the large-K batch is launched ONCE per wave for all of them, on the pool's own stream, with one
+ * read-back of tile counts and one wait per wave.  Any other member's requests go to its own
+ * locrec_knn_recommend_batch / locrec_knn_recommend_ranked_batch call.  All calls are synchronous.
+ * create: 1 .. 65535 distinct indexes on one device; the pool does not own them: destroy it before them.  Refused
+ * (LOCREC_E_INVALID_ARG, the message names the member): a NULL list, a NULL member, a member listed twice, members on
+ * different devices.
+ * recommend_batch: request i asks index index_of_request[i] (a position of create's list) for person_ids[i].  Rows
+ * (ordered by place id), offsets, the capacity protocol and the NULL rules are those of locrec_knn_recommend_batch;
+ * request i's rows equal bit for bit what that call returns for the person on the member alone.  A repeated (index,
+ * person) pair is computed once; the same person id in two members is two requests.  Before any device work: every
+ * index position (LOCREC_E_INVALID_ARG, "... names index <k> ..."), then the requires on the weights and k_nearest with
+ * their messages, then every person (LOCREC_E_NOT_FOUND, "No such person: <id>"; a person without a place or category
+ * vector is not found).  On a failure nothing is written except *out_bad_request (may be NULL): the position of the
+ * first offending request; -1 on success.  n_requests == 0: out_offsets[0] = 0, capacity 0.
+ * recommend_ranked_batch: request i gets the places of target_region_ids[i], top max_recommendations by estimated
+ * rating.  Outputs, padding (-1 / 0.0) and the checks on n_places, the arrays and max_recommendations are those of
+ * locrec_knn_recommend_ranked_batch; request i's values equal that call's on the member alone bit for bit.  ONE places
+ * table serves all members, uploaded once; the sharing members' rows are ranked by one call of the segmented ranker
+ * where they lie, and max_recommendations rows a request reach the host.
+ * After any pool call every member serves single requests and its own batches as a fresh handle does, and nothing is
+ * resident for locrec_knn_fetch_*.
+ * stats: this thread's last pool call (any pointer may be NULL): tile waves, member tiles (tiles of 16 over all members
+ * and waves), launches of the fill kernel (set and wipe: 2 a wave), of the scan kernel (1), of the segment aggregation
+ * (1) and of the sum / count / emit kernels (3), members served by their own call, rows emitted on the device, bytes
+ * read back, waits for the pool's stream.
+ */
+typedef struct locrec_knn_pool locrec_knn_pool;
+int32_t locrec_knn_pool_create(locrec_knn_index *const *indexes, int32_t n_indexes, locrec_knn_pool **out_pool);
+void locrec_knn_pool_destroy(locrec_knn_pool *pool);
+int32_t locrec_knn_pool_recommend_batch(
+    locrec_knn_pool *pool, int64_t n_requests, const int32_t *index_of_request, const int64_t *person_ids,
+    double place_weight, double category_weight, int64_t k_nearest,
+    int64_t *out_offsets, int64_t *out_place_ids, double *out_estimated_ratings, int64_t *inout_capacity,
+    int64_t *out_bad_request);
+int32_t locrec_knn_pool_recommend_ranked_batch(
+    locrec_knn_pool *pool, int64_t n_requests, const int32_t *index_of_request, const int64_t *person_ids,
+    double place_weight, double category_weight, int64_t k_nearest,
+    int64_t n_places, const int64_t *place_ids, const int64_t *place_region_ids,
+    const int64_t *target_region_ids, int64_t max_recommendations,
+    int64_t *out_place_ids, double *out_estimated_ratings, int64_t *out_counts, int64_t *out_bad_request);
+int32_t locrec_knn_pool_stats(int64_t *out_waves, int64_t *out_member_tiles, int64_t *out_fill_launches,
+                              int64_t *out_scan_launches, int64_t *out_aggregate_launches, int64_t *out_finish_launches,
+                              int64_t *out_delegated_members, int64_t *out_emitted_rows, int64_t *out_readback_bytes,
+                              int64_t *out_host_syncs);
+
+/*
  * One request with its candidate scan split over several GPUs (SURVEY.md 8e "KNN single request,
  * latency mode").  Every GPU holds the whole index (132 MB at cfg2, 1.3 GB at cfg4: nothing next to
  * 288 GB) and scans candidate shard shard_index of shard_count, a contiguous range of the

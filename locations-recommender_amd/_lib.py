@@ -119,6 +119,13 @@ SIGNATURES = {
                                               C.c_int64, _i64p, _i64p, _i64p, C.c_int64, _i64p, _f64p, _i64p, _i64p, _i64p, _i32p,
                                               _i64p],
     "locrec_sg_pool_recommend_ranked_batch_stats": [_i64p, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p],
+    "locrec_knn_pool_create": [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p)],
+    "locrec_knn_pool_destroy": [C.c_void_p],
+    "locrec_knn_pool_recommend_batch": [C.c_void_p, C.c_int64, _i32p, _i64p, C.c_double, C.c_double, C.c_int64,
+                                        _i64p, _i64p, _f64p, _i64p, _i64p],
+    "locrec_knn_pool_recommend_ranked_batch": [C.c_void_p, C.c_int64, _i32p, _i64p, C.c_double, C.c_double, C.c_int64,
+                                               C.c_int64, _i64p, _i64p, _i64p, C.c_int64, _i64p, _f64p, _i64p, _i64p],
+    "locrec_knn_pool_stats": [_i64p, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p],
     "locrec_set_devices": [C.c_int32, _i32p],
     "locrec_knn_replicas_create": [C.c_int32, _i32p, C.c_int64, _i64p, _i64p, _i32p, _f64p, C.c_int32, _i64p, _i32p, _f64p, C.c_int32,
                                    _i64p, _i64p, _i64p, C.POINTER(C.c_void_p)],
@@ -183,7 +190,8 @@ SIGNATURES = {
                                   C.c_int32, C.c_void_p, C.c_void_p, _i64p],
 }
 _RESTYPE = {"locrec_last_error": C.c_char_p, "locrec_version": C.c_char_p, "locrec_knn_replicas_destroy": None,
-            "locrec_sg_sharded_destroy": None, "locrec_sg_group_destroy": None, "locrec_sg_pool_destroy": None}
+            "locrec_sg_sharded_destroy": None, "locrec_sg_group_destroy": None, "locrec_sg_pool_destroy": None,
+            "locrec_knn_pool_destroy": None}
 
 _lib = None
 

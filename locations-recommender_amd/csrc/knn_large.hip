@@ -109,13 +109,15 @@ constexpr int kSegRaters = 4096;
 // other this loop was a chain of 64 memory round trips per segment); added in the same order as a plain loop.  With
 // QT = 16 a rater's weights are one 128-byte line that serves sixteen queries, and two raters in flight fill the
 // registers (150 VGPRs); the single column has room for eight.
+// (the bodies of this pass are __device__ functions: the kernels below launch them for one index, knn_pool.h for the
+// members of a pool side by side - the same operations in the same order, so the same bits)
 template <int QT, int U>
-__global__ __launch_bounds__(256) void lk_aggregate_segments(const int64_t *seg_begin, const int64_t *seg_end, int32_t nsegs,
-                                                             const int32_t *cp_row, const double *cp_rating, const double *S,
-                                                             double *seg_ws, double *seg_ss)
+__device__ __forceinline__ void lk_aggregate_segments_body(const int64_t *seg_begin, const int64_t *seg_end, int32_t nsegs,
+                                                           const int32_t *cp_row, const double *cp_rating, const double *S,
+                                                           double *seg_ws, double *seg_ss, int bx)
 {
     const int lane = threadIdx.x & 63;
-    const int sg = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int sg = bx * 4 + (threadIdx.x >> 6);
     if (sg >= nsegs) return;
     double ws[QT], ss[QT];
 #pragma unroll
@@ -159,12 +161,20 @@ __global__ __launch_bounds__(256) void lk_aggregate_segments(const int64_t *seg_
     }
 }
 
+template <int QT, int U>
+__global__ __launch_bounds__(256) void lk_aggregate_segments(const int64_t *seg_begin, const int64_t *seg_end, int32_t nsegs,
+                                                             const int32_t *cp_row, const double *cp_rating, const double *S,
+                                                             double *seg_ws, double *seg_ss)
+{
+    lk_aggregate_segments_body<QT, U>(seg_begin, seg_end, nsegs, cp_row, cp_rating, S, seg_ws, seg_ss, (int)blockIdx.x);
+}
+
 // thread per (place, query): the place's segments in segment order; output query-major [query][place]
 template <int QT>
-__global__ void lk_sum_segments(const int32_t *place_seg0, int32_t nplaces, const double *seg_ws, const double *seg_ss,
-                                double *out_ws, double *out_ss)
+__device__ __forceinline__ void lk_sum_segments_body(const int32_t *place_seg0, int32_t nplaces, const double *seg_ws,
+                                                     const double *seg_ss, double *out_ws, double *out_ss, uint32_t bx)
 {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = (int64_t)bx * blockDim.x + threadIdx.x;
     if (i >= (int64_t)nplaces * QT) return;
     const int p = (int)(i / QT), t = (int)(i % QT);
     double ws = 0.0, ss = 0.0;
@@ -176,6 +186,13 @@ __global__ void lk_sum_segments(const int32_t *place_seg0, int32_t nplaces, cons
     out_ss[(int64_t)t * nplaces + p] = ss;
 }
 
+template <int QT>
+__global__ void lk_sum_segments(const int32_t *place_seg0, int32_t nplaces, const double *seg_ws, const double *seg_ss,
+                                double *out_ws, double *out_ss)
+{
+    lk_sum_segments_body<QT>(place_seg0, nplaces, seg_ws, seg_ss, out_ws, out_ss, blockIdx.x);
+}
+
 // The end of the place-major pass on the device: the places somebody among the neighbours rated (ss > 0), in
 // ascending place order, with est = ws / ss (:67).  This was a host loop over all places after copying ws and ss
 // back - 100 k iterations with a division each, 0.2 ms of a 0.5 ms request at cfg2.  Two small launches on a grid
@@ -183,18 +200,24 @@ __global__ void lk_sum_segments(const int32_t *place_seg0, int32_t nplaces, cons
 // the tiles before it (the prefix over at most a few hundred tile counts is recomputed by each block).
 constexpr int kFinishTile = 2048;  // places per block: 256 threads x 8 consecutive places
 
-__global__ __launch_bounds__(256) void lk_finish_count(const double *ss, int32_t nplaces, int32_t *tile_cnt)
+// tile bx of ntiles, query column q
+__device__ __forceinline__ void lk_finish_count_body(const double *ss, int32_t nplaces, int32_t *tile_cnt, int bx, int q, int ntiles)
 {
     __shared__ int wsum[4];
-    const double *sq = ss + (int64_t)blockIdx.y * nplaces;
-    const int p0 = blockIdx.x * kFinishTile + threadIdx.x * 8;
+    const double *sq = ss + (int64_t)q * nplaces;
+    const int p0 = bx * kFinishTile + threadIdx.x * 8;
     int c = 0;
 #pragma unroll
     for (int i = 0; i < 8; ++i) c += (p0 + i < nplaces && sq[p0 + i] > 0) ? 1 : 0;
     c = wave_sum(c);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
     __syncthreads();
-    if (threadIdx.x == 0) tile_cnt[blockIdx.y * gridDim.x + blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    if (threadIdx.x == 0) tile_cnt[q * ntiles + bx] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+__global__ __launch_bounds__(256) void lk_finish_count(const double *ss, int32_t nplaces, int32_t *tile_cnt)
+{
+    lk_finish_count_body(ss, nplaces, tile_cnt, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x);
 }
 
 // where query t's rows begin in the output; < 0: the slot holds no query, nothing is written for it
@@ -205,23 +228,22 @@ struct LkBases {
 
 // out_n (with host_n, a pinned word the host reads without a copy): the single request's row count, or null
 template <int QT>
-__global__ __launch_bounds__(256) void lk_finish_emit(const double *ws, const double *ss, int32_t nplaces,
-                                                      const int32_t *tile_cnt, const int64_t *cplace_ids,
-                                                      const LkBases<QT> bases, int64_t *out_place, double *out_est,
-                                                      int64_t *out_n, int64_t *host_n)
+__device__ __forceinline__ void lk_finish_emit_body(const double *ws, const double *ss, int32_t nplaces, const int32_t *tile_cnt,
+                                                    const int64_t *cplace_ids, const LkBases<QT> &bases, int64_t *out_place,
+                                                    double *out_est, int64_t *out_n, int64_t *host_n, int bx, int q, int ntiles)
 {
     __shared__ int64_t bsum[4];
     __shared__ int wtot[4];
-    const int t = threadIdx.x, q = blockIdx.y;
+    const int t = threadIdx.x;
     if (bases.base[q] < 0) return;
     const double *wq = ws + (int64_t)q * nplaces, *sq = ss + (int64_t)q * nplaces;
-    const int32_t *tc = tile_cnt + q * gridDim.x;
+    const int32_t *tc = tile_cnt + q * ntiles;
     // rows of the tiles before this one
     int64_t before = 0;
-    for (int i = t; i < (int)blockIdx.x; i += 256) before += tc[i];
+    for (int i = t; i < bx; i += 256) before += tc[i];
     before = wave_sum(before);
     if ((t & 63) == 0) bsum[t >> 6] = before;
-    const int p0 = blockIdx.x * kFinishTile + t * 8;
+    const int p0 = bx * kFinishTile + t * 8;
     bool keep[8];
     int c = 0;
 #pragma unroll
@@ -239,10 +261,20 @@ __global__ __launch_bounds__(256) void lk_finish_emit(const double *ws, const do
             ++o;
         }
     }
-    if (out_n && blockIdx.x == gridDim.x - 1 && t == 255) {  // the last thread of the last tile knows the total
+    if (out_n && bx == ntiles - 1 && t == 255) {  // the last thread of the last tile knows the total
         *out_n = o;
         if (host_n) *host_n = o;
     }
+}
+
+template <int QT>
+__global__ __launch_bounds__(256) void lk_finish_emit(const double *ws, const double *ss, int32_t nplaces,
+                                                      const int32_t *tile_cnt, const int64_t *cplace_ids,
+                                                      const LkBases<QT> bases, int64_t *out_place, double *out_est,
+                                                      int64_t *out_n, int64_t *host_n)
+{
+    lk_finish_emit_body<QT>(ws, ss, nplaces, tile_cnt, cplace_ids, bases, out_place, out_est, out_n, host_n, (int)blockIdx.x,
+                            (int)blockIdx.y, (int)gridDim.x);
 }
 
 // segment table of the place-major ratings (lazy, once per index)
@@ -392,23 +424,25 @@ struct LkbFill {
     int32_t set;
 };
 
-// grid (element blocks, kLkbQt): query t's vector scattered into (or wiped from) column t of the dense table
-__global__ void lkb_fill(const LkbFill a)
+// element block bx of query t: the vector scattered into (set) or wiped from column t of the dense table
+__device__ __forceinline__ void lkb_fill_body(const LkbFill &a, int set, int bx, int t)
 {
-    const int t = blockIdx.y;
     const int r = a.qrow[t];
     if (r < 0) return;
-    const int64_t e = a.ptr[r] + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t e = a.ptr[r] + (int64_t)bx * blockDim.x + threadIdx.x;
     if (e < a.ptr[r + 1]) {
         const int32_t i = a.idx[e];
-        a.qd[(int64_t)i * kLkbQt + t] = a.set ? a.val[e] : 0.0;
+        a.qd[(int64_t)i * kLkbQt + t] = set ? a.val[e] : 0.0;
         if (a.bits) {
             const uint32_t b = (uint32_t)i & a.bit_mask;
-            if (a.set) atomicOr(&a.bits[b >> 5], 1u << (b & 31u));
+            if (set) atomicOr(&a.bits[b >> 5], 1u << (b & 31u));
             else a.bits[b >> 5] = 0u;  // (wiping: whole words, by whoever comes)
         }
     }
 }
+
+// grid (element blocks, kLkbQt)
+__global__ void lkb_fill(const LkbFill a) { lkb_fill_body(a, a.set, (int)blockIdx.x, (int)blockIdx.y); }
 
 // The tile's 16 queries hold a few hundred of the place dimensions between them, a candidate row is mostly OTHER places:
 // the 128-byte line of the dense table (16 fp64 query values, nearly always all zero) was fetched from L2 for every
@@ -417,14 +451,15 @@ __global__ void lkb_fill(const LkbFill a)
 // clear adds value * (+0.0) to every dot - nothing, for finite values - and is skipped without touching the table.
 constexpr uint32_t kLkbBitmapBits = 1u << 18;
 
-__global__ __launch_bounds__(256) void lkb_scan(const LkbScan P)
+// row block bx of the tile P (cand: the tile's candidate counters)
+__device__ __forceinline__ void lkb_scan_body(const LkbScan &P, int32_t *cand, int bx)
 {
     __shared__ int s_cand[kLkbQt];
     extern __shared__ uint32_t s_bits[];
     if (threadIdx.x < kLkbQt) s_cand[threadIdx.x] = 0;
     for (uint32_t i = threadIdx.x; i < (P.bit_mask + 1u) / 32u; i += blockDim.x) s_bits[i] = P.bits[i];
     __syncthreads();
-    const int row = blockIdx.x * blockDim.x + threadIdx.x;
+    const int row = bx * blockDim.x + threadIdx.x;
     if (row < P.nrows) {
         double dp[kLkbQt], dc[kLkbQt];
 #pragma unroll
@@ -465,8 +500,10 @@ __global__ __launch_bounds__(256) void lkb_scan(const LkbScan P)
         }
     }
     __syncthreads();
-    if (threadIdx.x < kLkbQt && s_cand[threadIdx.x]) atomicAdd(&P.cand[threadIdx.x], s_cand[threadIdx.x]);
+    if (threadIdx.x < kLkbQt && s_cand[threadIdx.x]) atomicAdd(&cand[threadIdx.x], s_cand[threadIdx.x]);
 }
+
+__global__ __launch_bounds__(256) void lkb_scan(const LkbScan P) { lkb_scan_body(P, P.cand, (int)blockIdx.x); }
 
 // the histogram of one query's column of a TRANSPOSED tile (what knn_select1 of knn.hip reads; knn_collect1 then
 // reads the column itself): how a batch serves the few queries that cannot ride a packed tile
@@ -1209,3 +1246,6 @@ int32_t knn_topk_recommend_batch(locrec_knn_index *ix, const int32_t *rows, int6
 }
 
 }  // namespace locrec
+
+// a pool of indexes: the kernels above for every member's tile in shared launches (locrec_knn_pool_*, knn_batch.hip)
+#include "knn_pool.h"

@@ -359,6 +359,99 @@ class KnnIndex:
         return ms.value, n.value
 
 
+class KnnPool:
+    """Resident indexes that serve one mixed batch of (index, person) requests (locrec_knn_pool_*): at the shipped
+    K ("every person of positive similarity is a neighbour") every member's current tile of 16 requests shares the
+    launches of a wave; any other member is served by its own batch call.  The indexes stay owned by the caller."""
+
+    STATS = ("waves", "member_tiles", "fill_launches", "scan_launches", "aggregate_launches", "finish_launches",
+             "delegated_members", "emitted_rows", "readback_bytes", "host_syncs")
+
+    def __init__(self, indexes):
+        self.indexes = list(indexes)
+        arr = (C.c_void_p * len(self.indexes))(*[ix._h for ix in self.indexes])
+        self._h = C.c_void_p()
+        L.check(L.lib().locrec_knn_pool_create(arr, len(self.indexes), C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            L.lib().locrec_knn_pool_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def _locked(self):
+        import contextlib
+        held = contextlib.ExitStack()
+        for ix in self.indexes:  # every member's lock, in member order
+            if getattr(ix, "lock", None) is not None:
+                held.enter_context(ix.lock)
+        return held
+
+    def recommend_batch(self, index_of, person_ids, pw, cw, k):
+        """makeRecommendations of indexes[index_of[i]] for person_ids[i], every i in one call:
+        (offsets[n + 1], place_ids, estimated_ratings), request i's rows exactly what
+        indexes[index_of[i]].recommend_batch returns for that person.  A refused call raises with `bad_request` set on
+        the exception: the position of the first request that names no index of the pool or no person of its index
+        (-1 when the refusal is about no single request)."""
+        gi, q = L.as_i32(index_of), L.as_i64(person_ids)
+        if len(gi) != len(q):
+            raise L.IllegalArgumentException("one index position per person is required")
+        off = np.zeros(len(q) + 1, np.int64)
+        room = max(getattr(self, "_room", 0), 1 << 16)  # what the largest call so far returned: one pass as a rule
+        cap = C.c_int64(room)
+        places, est = np.empty(room, np.int64), np.empty(room, np.float64)
+        bad = C.c_int64(-1)
+        with self._locked():
+            for _ in range(2):  # a call whose room is too small sizes the result, the second fills it
+                try:
+                    L.check(L.lib().locrec_knn_pool_recommend_batch(
+                        self._h, len(q), L.ptr(gi, C.c_int32), L.ptr(q, C.c_int64), float(pw), float(cw), int(k),
+                        L.ptr(off, C.c_int64), L.ptr(places, C.c_int64), L.ptr(est, C.c_double), C.byref(cap), C.byref(bad)))
+                except L.IllegalArgumentException as e:
+                    e.bad_request = bad.value
+                    raise
+                if cap.value <= len(places):
+                    break
+                places, est = np.empty(cap.value, np.int64), np.empty(cap.value, np.float64)
+                cap = C.c_int64(len(places))
+        self._room = max(room, int(off[-1]))
+        return off, places[:off[-1]].copy(), est[:off[-1]].copy()
+
+    def recommend_ranked_batch(self, index_of, person_ids, pw, cw, k, place_ids, place_region_ids, target_region_ids,
+                               max_recommendations):
+        """The pool's batch to its end (locrec_knn_pool_recommend_ranked_batch): request i gets the places of
+        target_region_ids[i], top max_recommendations by estimated rating, ranked on the device.
+        -> (place_ids[n, W], estimated_ratings[n, W], counts[n]) in KnnIndex.recommend_ranked_batch's layout; request i
+        equals that call on its member alone.  A refused call raises with `bad_request` set, as recommend_batch does."""
+        gi, q = L.as_i32(index_of), L.as_i64(person_ids)
+        if len(gi) != len(q):
+            raise L.IllegalArgumentException("one index position per person is required")
+        pl, reg, tgt = L.as_i64(place_ids), L.as_i64(place_region_ids), L.as_i64(target_region_ids)
+        if len(reg) != len(pl) or len(tgt) != len(q):
+            raise L.IllegalArgumentException("one region per place and one target region per person are required")
+        width = max(0, min(int(max_recommendations), len(pl)))   # a person has at most one row per place
+        oi, osc, cnt = np.empty((len(q), width), np.int64), np.empty((len(q), width), np.float64), np.zeros(len(q), np.int64)
+        bad = C.c_int64(-1)
+        with self._locked():
+            try:
+                L.check(L.lib().locrec_knn_pool_recommend_ranked_batch(
+                    self._h, len(q), L.ptr(gi, C.c_int32), L.ptr(q, C.c_int64), float(pw), float(cw), int(k), len(pl),
+                    L.ptr(pl, C.c_int64), L.ptr(reg, C.c_int64), L.ptr(tgt, C.c_int64), width, L.ptr(oi, C.c_int64),
+                    L.ptr(osc, C.c_double), L.ptr(cnt, C.c_int64), C.byref(bad)))
+            except L.IllegalArgumentException as e:
+                e.bad_request = bad.value
+                raise
+        return oi, osc, cnt
+
+    @classmethod
+    def stats(cls):
+        """What this thread's last pool call did (locrec_knn_pool_stats)."""
+        x = [C.c_int64() for _ in cls.STATS]
+        L.check(L.lib().locrec_knn_pool_stats(*[C.byref(i) for i in x]))
+        return dict(zip(cls.STATS, (i.value for i in x)))
+
+
 class KnnRecommender:
     """new KnnRecommender(placeRatingVectors, categoryRatingVectors, placeRatings,
     placeWeight, categoryWeight, kNearest).makeRecommendations(personId)"""

@@ -585,6 +585,68 @@ def knn_recommender_request(data_dir, persons, line, place_weight, category_weig
     return (target,) + tuple(prep.rank_recommendations(ids, scores, place_ids, place_regions, target[2], max_recommendations))
 
 
+def knn_recommender_requests(data_dir, persons, lines, place_weight, category_weight, k_nearest, max_recommendations=10,
+                             pooled=True):
+    """The body of KnnRecommenderMain's loop (KnnRecommenderMain.scala:36-67,90-101) for a LIST of input lines, under
+    sg_recommender_requests' contract: every line is parsed and resolved on its own, the index of [home, target] comes
+    from the handle cache (one handle per distinct region set, knn_make_recommendations' key), and ONE
+    KnnPool.recommend_ranked_batch call serves the good lines with the places table passed once - ranked on the device,
+    max_recommendations rows a line come back.  A line whose person its index lacks is recorded and the call repeated
+    without it.
+    -> a list aligned with lines: ((person_id, home_region_id, target_region_id), place_ids, estimated_ratings), exactly
+    what knn_recommender_request returns for that line, or the exception instance that function would have raised.
+    pooled=False: one KnnIndex.recommend_ranked_batch call per distinct index instead of the pool call (the same
+    result; what a queue cost before the pool)."""
+    from . import _cache
+    from .knn import KnnPool
+    _cache.require_gpu_backend("knn_recommender_requests")
+    out, targets, indexes = _knn_resolve_request_lines(data_dir, persons, lines)
+    try:
+        if targets:
+            place_ids, place_regions = load_places(data_dir)
+            pool = KnnPool(indexes) if pooled else None
+            try:
+                def call(gi, v, live):
+                    regions = np.asarray([targets[i][0][2] for i in live], np.int64)
+                    if pool is None:
+                        return _knn_requests_per_index(indexes, gi, v, place_weight, category_weight, k_nearest, place_ids,
+                                                       place_regions, regions, max_recommendations)
+                    return pool.recommend_ranked_batch(gi, v, place_weight, category_weight, k_nearest, place_ids, place_regions,
+                                                       regions, max_recommendations)
+                live, rows = _call_without_bad_lines(out, targets, call)
+            finally:
+                if pool is not None:
+                    pool.close()
+            if live:
+                oi, osc, cnt = rows
+                for k, i in enumerate(live):
+                    out[i] = (targets[i][0], np.array(oi[k, :cnt[k]]), np.array(osc[k, :cnt[k]]))
+    finally:
+        for ix in indexes:
+            ix.close()  # drops the reference only
+    return out
+
+
+def _knn_requests_per_index(indexes, index_of, person_ids, pw, cw, k, place_ids, place_regions, regions, max_recommendations):
+    """KnnPool.recommend_ranked_batch's result from one KnnIndex.recommend_ranked_batch call per distinct index; an unknown
+    person raises with bad_request = the position of a request that names it, as the pool call does."""
+    n = len(person_ids)
+    width = max(0, min(int(max_recommendations), len(place_ids)))
+    oi, osc, cnt = np.full((n, width), -1, np.int64), np.zeros((n, width), np.float64), np.zeros(n, np.int64)
+    for k_ix in np.unique(index_of):
+        at = np.flatnonzero(index_of == k_ix)
+        try:
+            with indexes[k_ix].lock:
+                oi[at], osc[at], cnt[at] = indexes[k_ix].recommend_ranked_batch(person_ids[at], pw, cw, k, place_ids, place_regions,
+                                                                                regions[at], max_recommendations)
+        except L.IllegalArgumentException as e:
+            head, _, unknown = str(e).rpartition(": ")
+            if head == "No such person":  # (the library checks the ids in order and names the first)
+                e.bad_request = int(at[np.flatnonzero(person_ids[at] == int(unknown))[0]])
+            raise
+    return oi, osc, cnt
+
+
 def sg_recommender_request(data_dir, persons, line, epsilon, max_iterations, max_recommendations=10):
     """The body of StochasticRecommenderMain's loop for one input line (StochasticRecommenderMain.scala:36-51,64-75).
     -> ((person_id, home_region_id, target_region_id), ids, probabilities)."""
@@ -617,7 +679,7 @@ def sg_recommender_requests(data_dir, persons, lines, epsilon, max_iterations, m
                 return pool.recommend_batch(gi, v, ALPHA, epsilon, max_iterations)
             finally:
                 pool.close()
-        live, rows = _sg_call_without_bad_lines(out, targets, call)
+        live, rows = _call_without_bad_lines(out, targets, call)
         if live:
             off, ids, probs, _, _ = rows
             place_ids, place_regions = load_places(data_dir)
@@ -650,7 +712,7 @@ def sg_recommender_requests_ranked(data_dir, persons, lines, epsilon, max_iterat
                     regions = np.asarray([targets[i][0][2] for i in live], np.int64)
                     return pool.recommend_ranked_batch(gi, v, ALPHA, epsilon, max_iterations, place_ids, place_regions, regions,
                                                        max_recommendations)
-                live, rows = _sg_call_without_bad_lines(out, targets, call)
+                live, rows = _call_without_bad_lines(out, targets, call)
             finally:
                 pool.close()
             if live:
@@ -672,37 +734,62 @@ def _sg_resolve_request_lines(data_dir, persons, lines):
     closes the graphs."""
     from . import _cache
     from .stochastic import SgGraph
+
+    def open_graph(region_ids):
+        name = generate_file_name(region_ids, data_dir, "stochastic_graph")
+        return name, lambda: SgGraph.through_cache(_cache.files_key([name]), lambda: sg_graph_from_parquet(data_dir, region_ids))
+    return _resolve_request_lines(persons, lines, open_graph)
+
+
+def _knn_resolve_request_lines(data_dir, persons, lines):
+    """_sg_resolve_request_lines for the KNN main: the index of [home, target] from the handle cache under
+    knn_make_recommendations' key, one handle per distinct region set.  -> (out, targets, indexes)."""
+    from . import _cache
+    from .knn import KnnIndex
+
+    def open_index(region_ids):
+        names = tuple(generate_file_name(region_ids, data_dir, f)
+                      for f in ("place_rating_vectors", "category_rating_vectors", "place_ratings"))
+        return names, lambda: KnnIndex.through_cache(_cache.files_key(list(names)),
+                                                     lambda: knn_index_from_parquet(data_dir, region_ids))
+    return _resolve_request_lines(persons, lines, open_index)
+
+
+def _resolve_request_lines(persons, lines, open_handle):
+    """Every line parsed and resolved on its own; open_handle([home, target]) -> (the region set's name, a function that
+    takes its handle from the cache), called once per distinct name - a failure is remembered and raised for every line
+    of that region set.  -> (out, targets, handles) as _sg_resolve_request_lines describes them."""
     out = [None] * len(lines)
-    targets, graph_of, graphs, failed = {}, {}, [], {}
+    targets, handle_of, handles, failed = {}, {}, [], {}
     try:
         for i, line in enumerate(lines):
             try:
                 target = calc_recommender_target(persons, parse_input(line))
-                name = generate_file_name([target[1], target[2]], data_dir, "stochastic_graph")
+                name, take = open_handle([target[1], target[2]])
                 if name in failed:
                     raise failed[name]
-                if name not in graph_of:
+                if name not in handle_of:
                     try:
-                        key = _cache.files_key([name])
-                        g = SgGraph.through_cache(key, lambda: sg_graph_from_parquet(data_dir, [target[1], target[2]]))
+                        h = take()
                     except Exception as e:
                         failed[name] = e
                         raise
-                    graph_of[name] = len(graphs)
-                    graphs.append(g)
-                targets[i] = (target, graph_of[name])
+                    handle_of[name] = len(handles)
+                    handles.append(h)
+                targets[i] = (target, handle_of[name])
             except Exception as e:  # Try { ... } per line
                 out[i] = e
     except BaseException:
-        for g in graphs:
-            g.close()
+        for h in handles:
+            h.close()
         raise
-    return out, targets, graphs
+    return out, targets, handles
 
 
-def _sg_call_without_bad_lines(out, targets, call):
-    """call(graph_index, vertex_ids, live) for the good lines `live`; a line whose vertex is not in its graph (the call
-    raises with bad_request set) is recorded in out and the call repeated without it.  -> (live, the call's result)."""
+def _call_without_bad_lines(out, targets, call):
+    """call(graph_index, vertex_ids, live) for the good lines `live`; a line whose vertex is not in its graph - or whose
+    person is not in its index - (the call raises with bad_request set) is recorded in out and the call repeated without
+    it.  -> (live, the call's result)."""
     live = sorted(targets)
     rows = None
     while live and rows is None:
