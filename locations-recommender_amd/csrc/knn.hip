@@ -589,10 +589,25 @@ int32_t enqueue_ht_prepass(locrec_knn_index *ix, const int32_t *qrows_dev, int32
     PP.off = ht.off.p;
     PP.off_stride = off_stride;
     PP.error = ht.err.p;
-    if (qt == 32)
-        hipLaunchKernelGGL(ht_build_hits<32>, dim3((unsigned)ntiles), dim3(kHtPreThreads), 0, s, PP);
-    else
-        hipLaunchKernelGGL(ht_build_hits<16>, dim3((unsigned)ntiles), dim3(kHtPreThreads), 0, s, PP);
+    PP.stage = ht.pre_stage > 0 ? ht.pre_stage : kHtPreStageDefault;
+    // the staged form keeps 32-bit posting cursors and steps them by up to a wave's 64 postings: an index whose
+    // posting count leaves no room for that step below 2^32 takes the first form
+    if (ht.pre_v1 || ht.post.n + 64 > 0xFFFFFFFFull) {
+        if (qt == 32)
+            hipLaunchKernelGGL(ht_build_hits_v1<32>, dim3((unsigned)ntiles), dim3(kHtPreThreads), 0, s, PP);
+        else
+            hipLaunchKernelGGL(ht_build_hits_v1<16>, dim3((unsigned)ntiles), dim3(kHtPreThreads), 0, s, PP);
+    } else {
+        const size_t lds = ht_pre_stage_bytes(PP.stage);
+        const dim3 grid((unsigned)ntiles), block(kHtPreThreads);
+        if (qt == 32) {
+            if (PP.stage <= kHtPreStageSmall) hipLaunchKernelGGL((ht_build_hits<32, 8>), grid, block, lds, s, PP);
+            else hipLaunchKernelGGL((ht_build_hits<32, 16>), grid, block, lds, s, PP);
+        } else {
+            if (PP.stage <= kHtPreStageSmall) hipLaunchKernelGGL((ht_build_hits<16, 8>), grid, block, lds, s, PP);
+            else hipLaunchKernelGGL((ht_build_hits<16, 16>), grid, block, lds, s, PP);
+        }
+    }
     LOCREC_HIP_TRY(hipGetLastError());
     return LOCREC_OK;
 }
@@ -1469,6 +1484,9 @@ void knn_read_env(locrec_knn_index *ix)
         if (w == 6 || w == 8 || w == 12) ix->ht.waves = w;
     }
     if (ix->ht.v1) ix->ht.waves = 8;
+    ix->ht.pre_v1 = std::getenv("LOCREC_KNN_HT_PRE_V1") != nullptr;  // A/B: the two-pass hit pre-pass for everything
+    if (const char *e = std::getenv("LOCREC_KNN_HT_PRE_STAGE"))      // tuning, tests: hits of the pre-pass's LDS stage
+        ix->ht.pre_stage = std::min(kHtPreStageMax, std::max(kHtPreStageMin, std::atoi(e)));
     ix->force_generic = std::getenv("LOCREC_KNN_FORCE_GENERIC") != nullptr;
     ix->no_pack16 = std::getenv("LOCREC_KNN_NO_PACK16") != nullptr;
     ix->no_pop = std::getenv("LOCREC_KNN_NO_POP") != nullptr;

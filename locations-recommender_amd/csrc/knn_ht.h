@@ -14,10 +14,12 @@
 //                       v_and) and the multiplier is its high half (read in place by v_pk_mad_u16
 //                       through op_sel): 1 + QT/2 VALU and QT/8 ds_read_b128 per element, no hash.
 //   TAIL  (index >= H): stored INVERTED, one posting list per place (row << 8 | value, rows
-//                       ascending).  Before a batch is scanned, ht_build_hits walks, for every
-//                       tail element of every query of a tile, that place's posting list and emits
-//                       one HIT (candidate lane, query, product) per posting, counting-sorted by
-//                       candidate slice.  The scan adds a slice's hits (a handful per slice and
+//                       ascending).  Before a batch is scanned, the hit pre-pass (ht_build_hits,
+//                       knn_ht_prepass.h) walks, for every tail element of every query of a tile,
+//                       that place's posting list - once - and emits one HIT (candidate lane,
+//                       query, product) per posting, grouped by candidate slice: staged and
+//                       counting-sorted in LDS one sub-range of slices at a time, written out in
+//                       whole lines.  The scan adds a slice's hits (a handful per slice and
 //                       tile) into a wave-private LDS accumulator that each lane then folds into
 //                       its head dots - the tail costs a few instructions per SLICE instead of
 //                       ~40 per element and lane.
@@ -29,17 +31,12 @@
 // Replaces the same reference lines as knn_scan: KnnRecommender.scala:27-49,76-96, Distance.scala:7-9.
 
 constexpr int kHtCatRows = 64;        // rows reserved for the category panel (c_dim <= 64)
-constexpr int kHtMaxEntries = 1024;   // (query, tail place) pairs of one tile the pre-pass holds in LDS
-constexpr int kHtSubSlices = 4096;    // candidate slices one counting pass covers (u32 counters in LDS)
-constexpr int kHtPreThreads = 512;
 
 // (struct HtParams - the scan-side parameters - is declared in knn.hip in front of ScanParams)
 
-// ---- element / hit formats -------------------------------------------------------------------
-__host__ __device__ __forceinline__ uint32_t ht_pack_hit(uint32_t lane, uint32_t q, uint32_t prod)
-{
-    return (lane << 21) | (q << 16) | prod;
-}
+// ---- pre-pass: hit format, tile bases, hits of one tile ---------------------------------------
+#include "knn_ht_prepass.h"
+
 
 // byte offset, inside one wave's tail accumulator, of the 32-bit word that holds queries (2w, 2w+1)
 // of candidate lane r.  Rows are QT*2 bytes; the 16-byte chunks of a row are XOR-swizzled with bits
@@ -53,198 +50,6 @@ __device__ __forceinline__ uint32_t ht_tail_word(uint32_t r, uint32_t w)
     return r * (QT * 2) + ((((w >> 2) ^ sw) & (chunks - 1)) << 4) + ((w & 3u) << 2);
 }
 
-// ---- pre-pass: hits of one tile ---------------------------------------------------------------
-struct HtPreParams {
-    const int64_t *csr_ptr;     // place family, renumbered indices, ascending inside a row
-    const int32_t *csr_idx;
-    const double *csr_val;
-    const int64_t *post_ptr;    // [p_dim - h + 1]
-    const uint32_t *post;       // row << 8 | value
-    const int32_t *qrows;       // or nullptr: rows qrow0 ..
-    int32_t qrow0, nq;
-    int32_t h;
-    int32_t slice0, nslices;    // scanned candidate slices [slice0, nslices)
-    const int64_t *tile_base;
-    uint32_t *hits;
-    uint32_t *off;
-    int32_t off_stride;
-    int32_t *error;             // set when a tile has more than kHtMaxEntries entries (host checks first; tripwire)
-};
-
-// tile_base[t] = number of hits of the tiles before t: a posting of a tail place is one hit for every
-// query of the tile that holds the place.  One block; tail_hits[row] is precomputed at create time.
-__global__ __launch_bounds__(1024) void ht_tile_bases(const int64_t *tail_hits, const int32_t *qrows, int32_t qrow0,
-                                                      int32_t nq, int32_t qt, int32_t ntiles, int64_t *tile_base)
-{
-    __shared__ int64_t wsum[16];
-    __shared__ int64_t carry;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) carry = 0;
-    __syncthreads();
-    for (int t0 = 0; t0 < ntiles; t0 += 1024) {
-        const int t = t0 + tid;
-        int64_t mine = 0;
-        if (t < ntiles)
-            for (int q = t * qt; q < min(nq, (t + 1) * qt); ++q) mine += tail_hits[qrows ? qrows[q] : qrow0 + q];
-        int64_t inc = mine;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int64_t o = __shfl_up(inc, d);
-            if (lane >= d) inc += o;
-        }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        int64_t before = carry;
-        for (int w = 0; w < wave; ++w) before += wsum[w];
-        if (t < ntiles) tile_base[t] = before + inc - mine;
-        __syncthreads();
-        if (tid == 1023) carry = before + inc;
-        __syncthreads();
-    }
-    if (tid == 0) tile_base[ntiles] = carry;
-}
-
-// Measured at cfg2 (136 M hits per 16,384-query batch, 8.5 per slice and tile): 1.55 ms per launch =
-// 35 us of entry set-up, 75 us of zeroing / prefix scans, 450 us per pass of LDS atomics (~2 cycles per
-// lane-atomic per CU: the LDS's atomic rate, not latency - a version with four 64-posting loads of a wave in
-// flight over a flattened work list was no faster) and 535 us for the scattered 4-byte stores of pass B.
-template <int QT>
-__global__ __launch_bounds__(kHtPreThreads) void ht_build_hits(const HtPreParams P)
-{
-    __shared__ int64_t e_cur[kHtMaxEntries];   // next posting of the entry
-    __shared__ int64_t e_end[kHtMaxEntries];
-    __shared__ uint32_t e_qv[kHtMaxEntries];   // q << 16 | query value
-    __shared__ uint32_t cnt[kHtSubSlices];     // per slice of the current sub-range: count, then cursor
-    __shared__ uint32_t wtot[kHtPreThreads / 64 + 1];
-    __shared__ int s_ne;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    constexpr int NW = kHtPreThreads / 64;
-    const int tile = blockIdx.x;
-    const int q0 = tile * QT;
-    const int nqt = min(QT, P.nq - q0);
-    if (tid == 0) s_ne = 0;
-    __syncthreads();
-    // entries: one per (query of the tile, tail element of its place vector)
-    for (int q = 0; q < nqt; ++q) {
-        const int row = P.qrows ? P.qrows[q0 + q] : P.qrow0 + q0 + q;
-        for (int64_t e = P.csr_ptr[row] + tid; e < P.csr_ptr[row + 1]; e += kHtPreThreads) {
-            const int idx = P.csr_idx[e];
-            if (idx >= P.h) {
-                const int slot = atomicAdd(&s_ne, 1);
-                if (slot < kHtMaxEntries) {
-                    const int64_t b = P.post_ptr[idx - P.h];
-                    e_cur[slot] = b;
-                    e_end[slot] = P.post_ptr[idx - P.h + 1];
-                    e_qv[slot] = ((uint32_t)q << 16) | (uint32_t)P.csr_val[e];
-                }
-            }
-        }
-    }
-    __syncthreads();
-    const int ne = min(s_ne, kHtMaxEntries);
-    if (s_ne > kHtMaxEntries && tid == 0 && P.error) atomicAdd(P.error, 1);
-    // the scan may cover a candidate shard only: skip the postings before its first row
-    if (P.slice0 > 0) {
-        const uint32_t first_row = (uint32_t)P.slice0 * 64u;
-        for (int e = tid; e < ne; e += kHtPreThreads) {
-            int64_t a = e_cur[e], b = e_end[e];
-            while (a < b) {  // lower bound of first_row
-                const int64_t m = (a + b) >> 1;
-                if ((P.post[m] >> 8) < first_row) a = m + 1; else b = m;
-            }
-            e_cur[e] = a;
-        }
-        __syncthreads();
-    }
-    uint32_t *off_row = P.off + (int64_t)tile * P.off_stride;
-    uint32_t *hits = P.hits + P.tile_base[tile];
-    uint32_t run = 0;  // hits of this tile before the current sub-range (same value in every thread)
-    for (int sl0 = P.slice0; sl0 < P.nslices; sl0 += kHtSubSlices) {
-        const int nsl = min(kHtSubSlices, P.nslices - sl0);
-        const uint32_t row_end = (uint32_t)(sl0 + nsl) * 64u;
-        for (int i = tid; i < nsl; i += kHtPreThreads) cnt[i] = 0u;
-        __syncthreads();
-        // pass A: count the postings of every entry that fall into this sub-range, per slice
-        for (int e = wave; e < ne; e += NW) {
-            const int64_t end = e_end[e];
-            for (int64_t p = e_cur[e]; p < end; p += 64) {
-                const bool in = p + lane < end;
-                const uint32_t row = in ? (P.post[p + lane] >> 8) : 0xFFFFFFFFu;
-                const bool mine = in && row < row_end;
-                if (mine) atomicAdd(&cnt[(row >> 6) - sl0], 1u);
-                if (!__all(mine)) break;
-            }
-        }
-        __syncthreads();
-        // exclusive prefix of the counts -> offsets; every thread owns nsl / threads consecutive slices
-        constexpr int PER = kHtSubSlices / kHtPreThreads;
-        uint32_t local[PER];
-        uint32_t sum = 0;
-#pragma unroll
-        for (int j = 0; j < PER; ++j) {
-            const int i = tid * PER + j;
-            local[j] = i < nsl ? cnt[i] : 0u;
-            sum += local[j];
-        }
-        uint32_t inc = sum;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t o = __shfl_up(inc, d);
-            if (lane >= d) inc += o;
-        }
-        if (lane == 63) wtot[wave] = inc;
-        __syncthreads();
-        if (tid == 0) {
-            uint32_t acc = 0;
-            for (int w = 0; w < NW; ++w) {
-                const uint32_t t = wtot[w];
-                wtot[w] = acc;
-                acc += t;
-            }
-            wtot[NW] = acc;
-        }
-        __syncthreads();
-        uint32_t excl = run + wtot[wave] + inc - sum;
-        const uint32_t total = wtot[NW];
-#pragma unroll
-        for (int j = 0; j < PER; ++j) {
-            const int i = tid * PER + j;
-            if (i < nsl) {
-                cnt[i] = excl;                           // becomes the slice's write cursor
-                off_row[(sl0 - P.slice0) + i] = excl;
-            }
-            excl += local[j];
-        }
-        __syncthreads();
-        // pass B: the hits themselves, and the entries' cursors move past this sub-range
-        for (int e = wave; e < ne; e += NW) {
-            const int64_t end = e_end[e];
-            const uint32_t qv = e_qv[e];
-            const uint32_t q = qv >> 16, qval = qv & 0xFFFFu;
-            int64_t p = e_cur[e];
-            for (; p < end; p += 64) {
-                const bool in = p + lane < end;
-                const uint32_t pv = in ? P.post[p + lane] : 0xFFFFFFFFu;
-                const uint32_t row = pv >> 8;
-                const bool mine = in && row < row_end;
-                if (mine) {
-                    const uint32_t pos = atomicAdd(&cnt[(row >> 6) - sl0], 1u);
-                    hits[pos] = ht_pack_hit(row & 63u, q, (pv & 0xFFu) * qval);
-                }
-                const uint64_t m = __ballot(mine);
-                if (m != ~0ull) {  // postings are sorted by row: the lanes inside the sub-range form a prefix
-                    p += __popcll(m);
-                    break;
-                }
-            }
-            if (lane == 0) e_cur[e] = p < end ? p : end;
-        }
-        run += total;
-        __syncthreads();
-    }
-    if (tid == 0) off_row[P.nslices - P.slice0] = run;
-}
 
 // ---- scan side ---------------------------------------------------------------------------------
 

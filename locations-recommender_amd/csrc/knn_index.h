@@ -61,6 +61,8 @@ struct HtIndex {
     DevBuf<unsigned char> cold;           // HtCold of the launch in flight
     DevBuf<double> seed;                  // [nq] threshold seeds of the launch (knn_scan_ht), or unused
     bool v1 = false;                      // LOCREC_KNN_HT_V1: the first form (knn_scan MODE 3) instead of knn_scan_ht
+    bool pre_v1 = false;                  // LOCREC_KNN_HT_PRE_V1: the hit pre-pass in its first, two-pass form (knn_ht_prepass.h)
+    int32_t pre_stage = 0;                // LOCREC_KNN_HT_PRE_STAGE: hits the pre-pass stages in LDS per sub-range (0: its default)
     DevBuf<int64_t> tail_hits;            // per row: postings its tail places hold in total
     std::vector<int64_t> tail_hits_ps;    // host prefix sums [n + 1]
     std::vector<int32_t> tail_nnz;        // host, per row
