@@ -172,6 +172,22 @@ int32_t locrec_knn_ht_multiplied_words(const locrec_knn_index *index, int64_t *o
 int32_t locrec_knn_ht_slice_counts(const locrec_knn_index *index, int64_t capacity, int32_t *out_place, int32_t *out_category,
                                    int64_t *out_slices);
 
+/* Measurement and tests only: what the hit pre-pass of the last batched head / tail scan on this handle left on the
+ * device (csrc/knn_ht_prepass.h).  nq names that batch, as for locrec_knn_fetch_topk; call directly after the batch.
+ * *out_query_tile, *out_tiles, [*out_slice0, *out_nslices) = the handle's candidate slices (the off rows have one entry
+ * per slice and a closing one), *out_total = hit words of all tiles; out_tile_base[t] = first hit word of tile t
+ * (*out_tiles + 1 entries, the last one the total), out_off[t * (*out_nslices - *out_slice0 + 1) + s - *out_slice0] =
+ * start of slice s inside tile t's hits (the closing entry is the tile's total), out_hits = the hit words
+ * (lane << 21 | query of the tile << 16 | product), grouped by slice, in any order inside a slice.  At most
+ * tile_capacity / off_capacity / hit_capacity entries of the three arrays are written: call with capacities 0 to size
+ * them.  Synchronises the handle's stream.  Refused ("no matching hit pre-pass to read") when the last scan recorded
+ * on the handle was not a batched head / tail scan of nq queries (scan plan kernel 2 or 3): none yet, another size,
+ * or a scan without a pre-pass. */
+int32_t locrec_knn_ht_last_hits(locrec_knn_index *index, int64_t nq, int64_t tile_capacity, int64_t off_capacity,
+                                int64_t hit_capacity, int32_t *out_query_tile, int64_t *out_tiles, int32_t *out_slice0,
+                                int32_t *out_nslices, int64_t *out_tile_base, uint32_t *out_off, uint32_t *out_hits,
+                                int64_t *out_total);
+
 /*
  * Plan of the last batched scan enqueued on this handle (measurement only; bench.py prints it):
  * kernel 1 = knn_scan (row scan over a query panel in LDS), 2 = knn_scan_ht (head / tail form: dense

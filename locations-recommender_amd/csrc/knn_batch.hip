@@ -564,3 +564,45 @@ extern "C" int32_t locrec_knn_pool_stats(int64_t *out_waves, int64_t *out_member
     if (out_host_syncs) *out_host_syncs = st.host_syncs;
     return LOCREC_OK;
 }
+
+// Measurement and tests only (include/locrec.h): what the hit pre-pass of the last batched head / tail scan left in the
+// handle's workspaces (knn_ht_prepass.h).  knn.hip and the handle's layout are hashed (see the head of this file), so
+// enqueue_ht_prepass records nothing of its own: the shape is what the handle already says about its last scan - the
+// plan (kernel 2 or 3: the batch took the head / tail form, so its pre-pass ran), the number of queries, the query tile
+// and the candidate slices - and the caller names the batch by its size, as it does for locrec_knn_fetch_topk.  Those
+// workspaces are written by the pre-pass alone, so what is copied is always a pre-pass's own output.
+extern "C" int32_t locrec_knn_ht_last_hits(locrec_knn_index *ix, int64_t nq, int64_t tile_capacity, int64_t off_capacity,
+                                           int64_t hit_capacity, int32_t *out_query_tile, int64_t *out_tiles, int32_t *out_slice0,
+                                           int32_t *out_nslices, int64_t *out_tile_base, uint32_t *out_off, uint32_t *out_hits,
+                                           int64_t *out_total) try
+{
+    if (!ix || !out_tiles || !out_total || tile_capacity < 0 || off_capacity < 0 || hit_capacity < 0 ||
+        (tile_capacity > 0 && !out_tile_base) || (off_capacity > 0 && !out_off) || (hit_capacity > 0 && !out_hits))
+        return fail(LOCREC_E_INVALID_ARG, "NULL argument");
+    const locrec::HtIndex &ht = ix->ht;
+    const int qt = ix->last_plan_qt;
+    const bool ran = ht.ready && !ix->no_ht && ix->have_result && !ix->single_pending && nq > 0 && ix->last_nq == nq &&
+                     (ix->last_plan_kernel == 2 || ix->last_plan_kernel == 3) && qt > 0 && ht.tile_base.p && ht.off.p;
+    const int64_t ntiles = ran ? (nq + qt - 1) / qt : 0;
+    const int64_t off_stride = (int64_t)ix->cand_slice1 - ix->cand_slice0 + 1;
+    if (!ran || (size_t)ntiles + 1 > ht.tile_base.n || (size_t)(ntiles * off_stride) > ht.off.n)
+        return fail(LOCREC_E_INVALID_ARG, "no matching hit pre-pass to read");
+    LOCREC_HIP_TRY(hipSetDevice(ix->device));
+    hipStream_t s = ix->stream;
+    int64_t total = 0;
+    LOCREC_HIP_TRY(hipMemcpyAsync(&total, ht.tile_base.p + ntiles, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    if (total < 0 || (size_t)total > ht.hits.n) return fail(LOCREC_E_INVALID_ARG, "no matching hit pre-pass to read");
+    if (out_query_tile) *out_query_tile = qt;
+    if (out_slice0) *out_slice0 = ix->cand_slice0;
+    if (out_nslices) *out_nslices = ix->cand_slice1;
+    *out_tiles = ntiles;
+    *out_total = total;
+    const int64_t nb = std::min(tile_capacity, ntiles + 1), no = std::min(off_capacity, ntiles * off_stride),
+                  nh = std::min(hit_capacity, total);
+    if (nb > 0) LOCREC_HIP_TRY(hipMemcpyAsync(out_tile_base, ht.tile_base.p, (size_t)nb * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    if (no > 0) LOCREC_HIP_TRY(hipMemcpyAsync(out_off, ht.off.p, (size_t)no * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (nh > 0) LOCREC_HIP_TRY(hipMemcpyAsync(out_hits, ht.hits.p, (size_t)nh * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    return LOCREC_OK;
+} LOCREC_CATCH_ALL

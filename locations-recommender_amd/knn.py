@@ -158,6 +158,23 @@ class KnnIndex:
                                                        c.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(ns)))
         return np.stack([p, c], axis=1)
 
+    def ht_last_hits(self, nq):
+        """What the hit pre-pass of the last batched head / tail scan - of nq queries - left on the device
+        (locrec_knn_ht_last_hits): {query_tile, tiles, slice0, nslices, tile_base int64[tiles + 1],
+        off uint32[tiles, nslices - slice0 + 1], hits uint32[tile_base[-1]]}.  Raises when the last scan had no pre-pass."""
+        qt, s0, s1 = C.c_int32(), C.c_int32(), C.c_int32()
+        nt, total = C.c_int64(), C.c_int64()
+        u32p = C.POINTER(C.c_uint32)
+        head = [C.byref(x) for x in (qt, nt, s0, s1)]
+        L.check(L.lib().locrec_knn_ht_last_hits(self._h, int(nq), 0, 0, 0, *head, None, None, None, C.byref(total)))
+        base = np.zeros(nt.value + 1, np.int64)
+        off = np.zeros((nt.value, s1.value - s0.value + 1), np.uint32)
+        hits = np.zeros(total.value, np.uint32)
+        L.check(L.lib().locrec_knn_ht_last_hits(self._h, int(nq), base.size, off.size, hits.size, *head, L.ptr(base, C.c_int64),
+                                                off.ctypes.data_as(u32p), hits.ctypes.data_as(u32p), C.byref(total)))
+        return {"query_tile": qt.value, "tiles": nt.value, "slice0": s0.value, "nslices": s1.value, "tile_base": base,
+                "off": off, "hits": hits}
+
     def scan_plan(self):
         """Plan of the last batched scan: kernel (1 = knn_scan, 2 = knn_scan_ht, 3 = knn_scan in head/tail mode), mode, query tile, waves."""
         v = [C.c_int32() for _ in range(4)]

@@ -30,6 +30,7 @@ No switch of the tree selects the 32-query tile (cfg::kHtQt is a constant), so t
 import numpy as np
 import pytest
 
+from knn_prepass_model import width
 from test_gpu_knn import make_index, sharded_request
 
 pytestmark = pytest.mark.gpu
@@ -97,15 +98,6 @@ def hits_per_tile_and_slice(d, rows):
             if p >= HOT:
                 out[j // 16] += np.bincount(np.array(holders[int(p)]) // 64, minlength=slices)
     return out
-
-
-def width(stage, slices, total):
-    """The sub-range width of a tile: the power of two nearest, in ratio, to the slices that hold stage / 2 hits."""
-    target = (stage // 2) * slices // max(total, 1)
-    w = 1
-    while w < WIDTH_MAX and w * 10 <= target * 7:
-        w *= 2
-    return w
 
 
 def case(oracle):
