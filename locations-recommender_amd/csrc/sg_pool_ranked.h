@@ -1,8 +1,8 @@
 // sg_pool_ranked.h -- the ranked pool (locrec_sg_pool_recommend_ranked_batch): one mixed batch of (graph, vertex, target
 // region) requests over a pool's resident graphs, emitted and ranked on the device.  Included at the end of sg_batch.hip,
 // behind sg_ranked.h and sg_pool.h: the sweeps, finalizes, set-up, polls and the restore launch are sg_pool_waves', the
-// emit, state, membership and popcount bodies are sg_ranked.h's - per column and per request the order of operations is
-// the ranked batch's, so request i equals locrec_sg_recommend_ranked_batch on its member alone bit for bit.
+// emit, state, membership and popcount bodies and the host's SgRkCall are sg_ranked.h's - per column and per request the order
+// of operations is the ranked batch's, so request i equals locrec_sg_recommend_ranked_batch on its member alone bit for bit.
 //
 //   emit rows       per member with requests its own numbering (sg_rk_rows): sorted ids, their emit rows and eid, kept
 //                   resident by the pool per member and numbering (with / without the source-only vertices), built at the
@@ -20,14 +20,13 @@
 //   sg_rk_state_pool  ONE launch per wave, blockIdx.x = the member: 384 bytes a member at its offset of the pool's pinned
 //                   buffer (a device buffer and one plain copy where that has no device address or a member was created
 //                   under LOCREC_SG_NO_PACK); one synchronisation covers the wave
-//   ranking         rank_segments_device once per full group; its N rows a request come to the host once
+//   ranking         SgRkCall::flush_group once per full group; its N rows a request come to the host once
 //
 // hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage (VGPRs / LDS bytes / scratch):
 //   sg_rk_emit_pool      82 / 32832 / 0
 //   sg_rk_state_pool     14 / 0 / 0
 //   sg_rk_members_pool   14 / 0 / 0
 //   sg_rk_popcount_pool  8 / 4 / 0
-// (sg_rk_emit and sg_rk_state keep 82 / 32832 / 0 and 14 / 0 / 0 with their bodies shared.)
 #pragma once
 
 #include <array>
@@ -99,9 +98,9 @@ __global__ __launch_bounds__(64 * kBatchB) void sg_rk_state_pool(const SgRkPoolR
 constexpr size_t kRkPoolStateStride = 512;  // a member's 384 bytes of state, on a line of their own
 static_assert(kRkStateBytes <= kRkPoolStateStride, "a member's state fits its slot");
 
-struct SgRkPoolStats {
-    int64_t tile_waves = 0, tiles = 0, rounds = 0, groups = 0, emit_launches = 0, emitted_rows = 0, readback_bytes = 0,
-            host_syncs = 0;
+// the ranked batch's counters (tiles: member tiles), and the pool's own
+struct SgRkPoolStats : SgRankedStats {
+    int64_t tile_waves = 0, rounds = 0, emit_launches = 0;
 };
 
 SgRkPoolStats &sg_rk_pool_stats()
@@ -169,14 +168,9 @@ extern "C" int32_t locrec_sg_pool_recommend_ranked_batch(
     stats = SgRkPoolStats();
     if (!pool) return fail(LOCREC_E_INVALID_ARG, "pool is NULL");
     if (n_requests < 0 || (n_requests > 0 && (!graph_index || !vertex_ids))) return fail(LOCREC_E_INVALID_ARG, "bad arguments");
-    // the checks of locrec_sg_recommend_ranked_batch (locrec_rank_recommendations_batch's)
-    if (n_places < 0 || n_places >= ((int64_t)1 << 31) || n_requests >= ((int64_t)1 << 31))
-        return fail(LOCREC_E_INVALID_ARG, "place or target count out of range [0, 2^31)");
-    const int64_t N = std::max<int64_t>(0, max_recommendations);  // limit(n <= 0) is empty
-    if (N > 0 && n_requests > ((int64_t)1 << 60) / N) return fail(LOCREC_E_INVALID_ARG, "n_targets * max_recommendations overflows");
-    if (n_requests > 0 && (!target_region_ids || !out_counts || (N > 0 && (!out_ids || !out_probabilities)) ||
-                           (n_places > 0 && (!place_ids || !place_region_ids))))
-        return fail(LOCREC_E_INVALID_ARG, "null array");
+    int64_t N = 0;
+    LOCREC_TRY(sg_rk_check_args(n_requests, n_places, place_ids, place_region_ids, target_region_ids, max_recommendations, out_ids,
+                                out_probabilities, out_counts, N));
     LOCREC_TRY(sg_batch_requires(epsilon, max_iterations));
     std::vector<SgPoolMember> mem;
     std::vector<int32_t> act, uniq_of;
@@ -225,7 +219,7 @@ extern "C" int32_t locrec_sg_pool_recommend_ranked_batch(
         sg_rk_pool_order(nu, tile_max, member_of, uniq_of, order);
         const size_t NU = order.ubase[na];
         std::vector<int32_t> req((size_t)(3 * n));  // column, target's emit row, bitmap (among its member's)
-        std::vector<size_t> pair_k((size_t)n);
+        std::vector<int32_t> pair_k((size_t)n);
         for (int64_t k = 0; k < n; ++k) {
             const int64_t i = order.ord[(size_t)k];
             const SgRkPoolActive &x = am[(size_t)member_of[(size_t)i]];
@@ -234,7 +228,7 @@ extern "C" int32_t locrec_sg_pool_recommend_ranked_batch(
             req[(size_t)k] = u % x.tile_max;
             req[(size_t)(n + k)] = sg_rk_row_of(pool->graphs[(size_t)x.gi], x.im->rows, mem[(size_t)x.gi].uniq[(size_t)u]);
             req[(size_t)(2 * n + k)] = (int32_t)r;
-            pair_k[(size_t)k] = x.pair_base + r;
+            pair_k[(size_t)k] = (int32_t)(x.pair_base + r);
         }
 
         // ---- device buffers.  d64, in 8-byte units; the head is ONE upload:
@@ -282,97 +276,36 @@ extern "C" int32_t locrec_sg_pool_recommend_ranked_batch(
                                d_preg, d_memtab);
         hipLaunchKernelGGL(sg_rk_popcount_pool, dim3((unsigned)P), dim3(kRkThreads), 0, s, d_pairs, d_bits.p,
                            reinterpret_cast<unsigned long long *>(d_caps));
-        std::vector<int64_t> caps(P);
-        LOCREC_HIP_TRY(hipMemcpyAsync(caps.data(), d_caps, P * 8, hipMemcpyDeviceToHost, s));
-        LOCREC_HIP_TRY(hipStreamSynchronize(s));
-        LOCREC_HIP_TRY(hipGetLastError());
-        ++stats.host_syncs;
-        stats.readback_bytes += (int64_t)P * 8;
 
-        // ---- the groups: request k's segment has room caps[its pair]; a group's segments share the row buffer
-        std::vector<int64_t> cap_k((size_t)n);
-        for (int64_t k = 0; k < n; ++k) cap_k[(size_t)k] = caps[pair_k[(size_t)k]];
-        SgRkGroups groups;
-        sg_rk_form_groups(cap_k, sg_ranked_row_budget(), groups);
-        const std::vector<int64_t> &group_end = groups.group_end;
-        const int64_t max_rows = groups.max_rows, max_req = groups.max_req;
-        if (max_rows >= ((int64_t)1 << 31)) return fail(LOCREC_E_INVALID_ARG, "a request's region has 2^31 places or more");
-        const int64_t Nd = std::min(N, groups.max_cap);  // no request has more rows than the largest region: the rest is padding
-        LOCREC_HIP_TRY(hipMemcpyAsync(d_seg_begin, groups.seg_begin.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
-        // a wave's row table holds a row per member and group part: the largest wave's
-        size_t max_tab = 1;
-        for (size_t k = 0; k < order.waves; ++k) {
-            size_t nw = 0;
-            int64_t lo = INT64_MAX, hi = 0;
-            for (size_t a = 0; a < na; ++a)
-                if (k * (size_t)tile_max[a] < nu[a]) {
-                    ++nw;
-                    lo = std::min(lo, order.tile_begin(a, k, tile_max[a]));
-                    hi = std::max(hi, order.tile_end(a, k, tile_max[a]));
-                }
-            size_t parts = 1;
-            for (const int64_t ge : group_end) parts += ge > lo && ge < hi ? 1 : 0;
-            max_tab = std::max(max_tab, nw * parts);
-        }
-        DevBuf<int64_t> d_rows, d_out;  // ids, then probabilities: the emitted rows of a group; its ranked rows and counts
+        // ---- the groups (request k's room: its pair's cap); a wave's row table has a row per member and group part
+        SgRkCall rc{.stats = stats, .s = s, .n = n, .N = N, .n_places = n_places, .d_pid = d_pid, .d_preg = d_preg, .d_tgt = d_tgt,
+                    .d_seg_begin = d_seg_begin, .d_seg_len = d_seg_len};
+        LOCREC_TRY(rc.plan(d_caps, P, pair_k.data(), NU));
+        const std::vector<int64_t> &group_end = rc.groups.group_end;
         DevBuf<unsigned char> d_state, d_tab;
-        LOCREC_TRY(d_rows.alloc(2 * (size_t)max_rows));
-        LOCREC_TRY(d_out.alloc((size_t)(2 * max_req * Nd + max_req)));
-        LOCREC_TRY(d_tab.alloc(max_tab * sizeof(SgRkPoolRow)));
+        LOCREC_TRY(d_tab.alloc(sg_rk_pool_table_rows(nu, tile_max, order, group_end) * sizeof(SgRkPoolRow)));
         const bool pinned = !pool->no_pack && pool->h_pack_dev != nullptr && pool->h_pack_bytes >= na * kRkPoolStateStride;
         if (!pinned) LOCREC_TRY(d_state.alloc(na * kRkPoolStateStride));
         std::vector<unsigned char> own_state(pinned ? 0 : na * kRkPoolStateStride);
-        int64_t *d_row_ids = d_rows.p;
-        double *d_row_probs = reinterpret_cast<double *>(d_rows.p + max_rows);
-        int64_t *d_oid = d_out.p, *d_ocnt = d_out.p + 2 * max_req * Nd;
-        double *d_osc = reinterpret_cast<double *>(d_out.p + max_req * Nd);
-        std::vector<int64_t> h_oid((size_t)(n * Nd)), h_cnt((size_t)n, 0);
-        std::vector<double> h_osc((size_t)(n * Nd));
-        size_t group = 0;  // the group that is being filled
-        // ranks the filled group and brings its rows to the host
-        auto flush_group = [&]() -> int32_t {
-            const int64_t ka = group == 0 ? (int64_t)0 : group_end[group - 1], nseg = group_end[group] - ka;
-            ++group;
-            ++stats.groups;
-            if (Nd == 0) return LOCREC_OK;  // every count is 0
-            LOCREC_TRY(rank_segments_device(nseg, d_seg_begin + ka, d_seg_len + ka, d_row_ids, d_row_probs, n_places, d_pid, d_preg,
-                                            d_tgt + ka, Nd, d_oid, d_osc, d_ocnt, nullptr, 0, s));
-            const RankBatchStats &rs = rank_batch_stats();
-            stats.host_syncs += rs.host_syncs;
-            stats.readback_bytes += 32 + (rs.sorted ? 4 : 0);  // the ranker's plan header, the global path's row count
-            LOCREC_HIP_TRY(hipMemcpyAsync(h_oid.data() + ka * Nd, d_oid, (size_t)(nseg * Nd) * 8, hipMemcpyDeviceToHost, s));
-            LOCREC_HIP_TRY(hipMemcpyAsync(h_osc.data() + ka * Nd, d_osc, (size_t)(nseg * Nd) * 8, hipMemcpyDeviceToHost, s));
-            LOCREC_HIP_TRY(hipMemcpyAsync(h_cnt.data() + ka, d_ocnt, (size_t)nseg * 8, hipMemcpyDeviceToHost, s));
-            LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (the next group's rows overwrite these)
-            ++stats.host_syncs;
-            stats.readback_bytes += nseg * (16 * Nd + 8);
-            return LOCREC_OK;
-        };
 
-        std::vector<int64_t> res_it(NU);
-        std::vector<int32_t> res_conv(NU);
         std::vector<SgRkPoolRow> tab;  // the wave's rows: part p's at tab[p * nw ..)
         std::vector<int64_t> cuts;
+        std::vector<size_t> present;  // the wave's members, as positions of act
         auto emit_and_rank = [&](const SgPoolWave &w) -> int32_t {
             const unsigned nw = (unsigned)w.members.size();
             stats.tiles += nw;
             // the wave's requests are one run of the emit order; the groups that end inside it cut it into parts
-            int64_t lo = INT64_MAX, hi = 0;
             unsigned emit_blocks = 1;
-            for (unsigned j = 0; j < nw; ++j) {
-                const size_t a = (size_t)act_of[(size_t)w.members[j]];
-                lo = std::min(lo, order.tile_begin(a, w.k, tile_max[a]));
-                hi = std::max(hi, order.tile_end(a, w.k, tile_max[a]));
-                emit_blocks = std::max(emit_blocks, (unsigned)((am[a].im->rows.m + kRkThreads - 1) / kRkThreads));
+            present.clear();
+            for (const int32_t gi : w.members) {
+                present.push_back((size_t)act_of[(size_t)gi]);
+                emit_blocks = std::max(emit_blocks, (unsigned)((am[present.back()].im->rows.m + kRkThreads - 1) / kRkThreads));
             }
-            cuts.assign(1, lo);
-            for (size_t gq = group; gq < group_end.size() && group_end[gq] < hi; ++gq)
-                if (group_end[gq] > lo) cuts.push_back(group_end[gq]);
-            cuts.push_back(hi);
+            sg_rk_wave_cuts(present, w.k, tile_max, order, group_end, cuts);
             const size_t parts = cuts.size() - 1;
             tab.assign(parts * nw, SgRkPoolRow{});
             for (unsigned j = 0; j < nw; ++j) {
-                const size_t a = (size_t)act_of[(size_t)w.members[j]];
+                const size_t a = present[j];
                 const SgRkPoolActive &x = am[a];
                 const locrec_sg_graph *g = pool->graphs[(size_t)x.gi];
                 const std::vector<int32_t> &uniq = mem[(size_t)x.gi].uniq;
@@ -408,10 +341,10 @@ extern "C" int32_t locrec_sg_pool_recommend_ranked_batch(
                 LOCREC_HIP_TRY(hipMemcpyAsync(own_state.data(), d_state.p, nw * kRkPoolStateStride, hipMemcpyDeviceToHost, s));
             for (size_t p = 0; p < parts; ++p) {
                 hipLaunchKernelGGL(sg_rk_emit_pool, dim3(emit_blocks, nw), dim3(kRkThreads), 0, s, d_rows_tab + p * nw, d_req, d_req + n,
-                                   d_req + 2 * n, d_seg_begin, reinterpret_cast<unsigned long long *>(d_seg_len), max_rows, d_row_ids,
-                                   d_row_probs);
+                                   d_req + 2 * n, d_seg_begin, reinterpret_cast<unsigned long long *>(d_seg_len), rc.groups.max_rows,
+                                   rc.d_row_ids, rc.d_row_probs);
                 ++stats.emit_launches;
-                if (cuts[p + 1] == group_end[group]) LOCREC_TRY(flush_group());
+                if (cuts[p + 1] == group_end[rc.group]) LOCREC_TRY(rc.flush_group());
             }
             LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (also: nothing reads the wave's tables any more)
             LOCREC_HIP_TRY(hipGetLastError());
@@ -419,15 +352,8 @@ extern "C" int32_t locrec_sg_pool_recommend_ranked_batch(
             stats.readback_bytes += (int64_t)(nw * kRkStateBytes);
             const unsigned char *host = pinned ? pool->h_pack : own_state.data();
             for (unsigned j = 0; j < nw; ++j) {
-                const size_t a = (size_t)act_of[(size_t)w.members[j]];
-                SgBatchState hs;
-                std::memcpy(&hs, host + j * kRkPoolStateStride, sizeof hs);
-                const double *totals = reinterpret_cast<const double *>(host + j * kRkPoolStateStride + kBatchPackHead);
-                for (int c = 0; c < w.nb[j]; ++c) {
-                    const size_t f = order.ubase[a] + w.k * (size_t)tile_max[a] + (size_t)c;
-                    LOCREC_TRY(sg_batch_verdict(hs.sweeps[c], [&]() { return totals[c]; }, eps2, max_iterations, &res_it[f],
-                                                &res_conv[f]));
-                }
+                const size_t f = order.ubase[present[j]] + w.k * (size_t)tile_max[present[j]];  // the tile's first column
+                LOCREC_TRY(sg_rk_verdicts(host + j * kRkPoolStateStride, w.nb[j], eps2, max_iterations, &rc.res_it[f], &rc.res_conv[f]));
             }
             return LOCREC_OK;
         };
@@ -435,33 +361,8 @@ extern "C" int32_t locrec_sg_pool_recommend_ranked_batch(
         const int32_t status = sg_pool_waves(pool, act, mem, alpha, epsilon, max_iterations, ps, emit_and_rank);
         stats.tile_waves = ps.tile_waves;
         stats.rounds = ps.rounds;
-        stats.readback_bytes += ps.polls * 4;
-        stats.host_syncs += ps.polls;
-        LOCREC_TRY(status);
-        // the columns' row counts and what the segments took
-        std::vector<int64_t> tail((size_t)n + NU);  // seg_len, col_rows
-        LOCREC_HIP_TRY(hipMemcpyAsync(tail.data(), d_seg_len, tail.size() * 8, hipMemcpyDeviceToHost, s));
-        LOCREC_HIP_TRY(hipStreamSynchronize(s));
-        ++stats.host_syncs;
-        stats.readback_bytes += (int64_t)tail.size() * 8;
-        for (int64_t k = 0; k < n; ++k) stats.emitted_rows += tail[(size_t)k];
-        // the caller's order and stride
-        for (int64_t k = 0; k < n; ++k) {
-            const int64_t i = order.ord[(size_t)k];
-            const size_t f = order.ubase[(size_t)member_of[(size_t)i]] + (size_t)uniq_of[(size_t)i];
-            const int64_t c = Nd > 0 ? h_cnt[(size_t)k] : 0;
-            out_counts[i] = c;
-            if (N > 0) {
-                std::copy(h_oid.begin() + k * Nd, h_oid.begin() + k * Nd + c, out_ids + i * N);
-                std::copy(h_osc.begin() + k * Nd, h_osc.begin() + k * Nd + c, out_probabilities + i * N);
-                std::fill(out_ids + i * N + c, out_ids + (i + 1) * N, (int64_t)-1);
-                std::fill(out_probabilities + i * N + c, out_probabilities + (i + 1) * N, 0.0);
-            }
-            if (out_row_counts) out_row_counts[i] = tail[(size_t)n + f];
-            if (out_iterations) out_iterations[i] = res_it[f];
-            if (out_converged) out_converged[i] = res_conv[f];
-        }
-        return LOCREC_OK;
+        return rc.finish(status, ps.polls, order, member_of, uniq_of, out_ids, out_probabilities, out_counts, out_row_counts,
+                         out_iterations, out_converged);
     };
     const int32_t status = run();
     // (a failed run may have left launches in flight that read the call's buffers, freed at run's end by hipFree, which

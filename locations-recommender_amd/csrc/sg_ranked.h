@@ -22,6 +22,8 @@
 //   ranking         rank_segments_device (rank_batch.hip) once per group of requests; a group ends where the room of its
 //                   segments would pass LOCREC_SG_RANKED_ROW_BUDGET rows (a tile's requests may straddle groups: the
 //                   emit runs once per part).  The group's N rows a request then travel to the host.
+//   host            the pool's entry (sg_pool_ranked.h) shares sg_rk_check_args, sg_rk_verdicts, SgRkCall (groups, ranker
+//                   call, read-backs, scatter) and sg_rk_plan.h's order and groups: this entry is a pool of one member
 //
 // hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage (VGPRs / LDS bytes / scratch):
 //   sg_rk_emit      82 / 32832 / 0
@@ -29,7 +31,6 @@
 //   sg_rk_popcount  8 / 4 / 0
 //   sg_rk_row_ids   4 / 0 / 0
 //   sg_rk_state     14 / 0 / 0
-// (the bodies are __device__ functions that the pool's kernels in sg_pool_ranked.h share: the figures did not move)
 #pragma once
 
 #include "rank_batch.h"
@@ -297,6 +298,135 @@ __global__ __launch_bounds__(kRkThreads) void sg_rk_emit(
                     seg_probs, col_rows, (int)blockIdx.x);
 }
 
+// The ranker surface's argument checks (locrec_rank_recommendations_batch's), the same for both entries.  N: the row limit
+int32_t sg_rk_check_args(int64_t n, int64_t n_places, const int64_t *place_ids, const int64_t *place_region_ids,
+                         const int64_t *target_region_ids, int64_t max_recommendations, const int64_t *out_ids,
+                         const double *out_probabilities, const int64_t *out_counts, int64_t &N)
+{
+    if (n_places < 0 || n_places >= ((int64_t)1 << 31) || n >= ((int64_t)1 << 31))
+        return fail(LOCREC_E_INVALID_ARG, "place or target count out of range [0, 2^31)");
+    N = std::max<int64_t>(0, max_recommendations);  // limit(n <= 0) is empty
+    if (N > 0 && n > ((int64_t)1 << 60) / N) return fail(LOCREC_E_INVALID_ARG, "n_targets * max_recommendations overflows");
+    if (n > 0 && (!target_region_ids || !out_counts || (N > 0 && (!out_ids || !out_probabilities)) ||
+                  (n_places > 0 && (!place_ids || !place_region_ids))))
+        return fail(LOCREC_E_INVALID_ARG, "null array");
+    return LOCREC_OK;
+}
+
+// A tile's verdicts from its state image (sg_rk_state's 384 bytes): column j of nb -> res_it[j], res_conv[j]
+int32_t sg_rk_verdicts(const unsigned char *image, int nb, double eps2, int64_t max_iterations, int64_t *res_it, int32_t *res_conv)
+{
+    SgBatchState hs;
+    std::memcpy(&hs, image, sizeof hs);
+    const double *totals = reinterpret_cast<const double *>(image + kBatchPackHead);
+    for (int j = 0; j < nb; ++j)
+        LOCREC_TRY(sg_batch_verdict(hs.sweeps[j], [&]() { return totals[j]; }, eps2, max_iterations, &res_it[j], &res_conv[j]));
+    return LOCREC_OK;
+}
+
+// What both ranked entries hold from the caps' read-back to the call's end.  The first members are the entry's: its
+// stream and, in its own buffer, the places table, the targets, the segments' begins and lengths (the columns' row
+// counts lie behind the lengths).
+struct SgRkCall {
+    SgRankedStats &stats;
+    hipStream_t s;
+    int64_t n, N, n_places;
+    const int64_t *d_pid, *d_preg, *d_tgt;
+    int64_t *d_seg_begin, *d_seg_len;
+    int64_t Nd = 0;
+    SgRkGroups groups;
+    size_t group = 0;               // the group that is being filled
+    DevBuf<int64_t> d_rows, d_out;  // ids, then probabilities: the emitted rows of a group; its ranked rows and counts
+    int64_t *d_row_ids = nullptr;
+    double *d_row_probs = nullptr;
+    std::vector<int64_t> h_oid, h_cnt, res_it;  // the ranked rows in emit order; res_*: per distinct target, flat
+    std::vector<double> h_osc;
+    std::vector<int32_t> res_conv;
+
+    // Reads the n_caps caps back and forms the groups: request k's segment has room caps[cap_of[k]], a group's segments
+    // share the row buffer.  nu: distinct targets.
+    int32_t plan(const int64_t *d_caps, size_t n_caps, const int32_t *cap_of, size_t nu)
+    {
+        std::vector<int64_t> caps(n_caps), cap_k((size_t)n);
+        LOCREC_HIP_TRY(hipMemcpyAsync(caps.data(), d_caps, n_caps * 8, hipMemcpyDeviceToHost, s));
+        LOCREC_HIP_TRY(hipStreamSynchronize(s));
+        LOCREC_HIP_TRY(hipGetLastError());
+        ++stats.host_syncs;
+        stats.readback_bytes += (int64_t)n_caps * 8;
+        for (int64_t k = 0; k < n; ++k) cap_k[(size_t)k] = caps[(size_t)cap_of[k]];
+        sg_rk_form_groups(cap_k, sg_ranked_row_budget(), groups);
+        if (groups.max_rows >= ((int64_t)1 << 31)) return fail(LOCREC_E_INVALID_ARG, "a request's region has 2^31 places or more");
+        Nd = std::min(N, groups.max_cap);  // no request has more rows than the largest region: the rest is padding
+        LOCREC_HIP_TRY(hipMemcpyAsync(d_seg_begin, groups.seg_begin.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
+        LOCREC_TRY(d_rows.alloc(2 * (size_t)groups.max_rows));
+        LOCREC_TRY(d_out.alloc((size_t)(2 * groups.max_req * Nd + groups.max_req)));
+        d_row_ids = d_rows.p;
+        d_row_probs = reinterpret_cast<double *>(d_rows.p + groups.max_rows);
+        h_oid.resize((size_t)(n * Nd));
+        h_osc.resize((size_t)(n * Nd));
+        h_cnt.assign((size_t)n, 0);
+        res_it.resize(nu);
+        res_conv.resize(nu);
+        return LOCREC_OK;
+    }
+
+    // ranks the filled group and brings its rows to the host
+    int32_t flush_group()
+    {
+        const int64_t ka = group == 0 ? (int64_t)0 : groups.group_end[group - 1], nseg = groups.group_end[group] - ka;
+        ++group;
+        ++stats.groups;
+        if (Nd == 0) return LOCREC_OK;  // every count is 0
+        int64_t *d_oid = d_out.p, *d_ocnt = d_out.p + 2 * groups.max_req * Nd;
+        double *d_osc = reinterpret_cast<double *>(d_out.p + groups.max_req * Nd);
+        LOCREC_TRY(rank_segments_device(nseg, d_seg_begin + ka, d_seg_len + ka, d_row_ids, d_row_probs, n_places, d_pid, d_preg,
+                                        d_tgt + ka, Nd, d_oid, d_osc, d_ocnt, nullptr, 0, s));
+        const RankBatchStats &rs = rank_batch_stats();
+        stats.host_syncs += rs.host_syncs;
+        stats.readback_bytes += 32 + (rs.sorted ? 4 : 0);  // the ranker's plan header, the global path's row count
+        LOCREC_HIP_TRY(hipMemcpyAsync(h_oid.data() + ka * Nd, d_oid, (size_t)(nseg * Nd) * 8, hipMemcpyDeviceToHost, s));
+        LOCREC_HIP_TRY(hipMemcpyAsync(h_osc.data() + ka * Nd, d_osc, (size_t)(nseg * Nd) * 8, hipMemcpyDeviceToHost, s));
+        LOCREC_HIP_TRY(hipMemcpyAsync(h_cnt.data() + ka, d_ocnt, (size_t)nseg * 8, hipMemcpyDeviceToHost, s));
+        LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (the next group's rows overwrite these)
+        ++stats.host_syncs;
+        stats.readback_bytes += nseg * (16 * Nd + 8);
+        return LOCREC_OK;
+    }
+
+    // After the tile loop (its status, its polls of 4 bytes each): the columns' row counts and what the segments took,
+    // then the caller's order and stride.  Input position i asks member member_of[i] for its distinct target uniq_of[i].
+    int32_t finish(int32_t status, int64_t polls, const SgRkPoolOrder &order, const std::vector<int32_t> &member_of,
+                   const std::vector<int32_t> &uniq_of, int64_t *out_ids, double *out_probabilities, int64_t *out_counts,
+                   int64_t *out_row_counts, int64_t *out_iterations, int32_t *out_converged)
+    {
+        stats.readback_bytes += polls * 4;
+        stats.host_syncs += polls;
+        LOCREC_TRY(status);
+        std::vector<int64_t> tail((size_t)n + res_it.size());  // seg_len, col_rows
+        LOCREC_HIP_TRY(hipMemcpyAsync(tail.data(), d_seg_len, tail.size() * 8, hipMemcpyDeviceToHost, s));
+        LOCREC_HIP_TRY(hipStreamSynchronize(s));
+        ++stats.host_syncs;
+        stats.readback_bytes += (int64_t)tail.size() * 8;
+        for (int64_t k = 0; k < n; ++k) {
+            stats.emitted_rows += tail[(size_t)k];
+            const int64_t i = order.ord[(size_t)k];
+            const size_t f = order.ubase[(size_t)member_of[(size_t)i]] + (size_t)uniq_of[(size_t)i];
+            const int64_t c = Nd > 0 ? h_cnt[(size_t)k] : 0;
+            out_counts[i] = c;
+            if (N > 0) {
+                std::copy(h_oid.begin() + k * Nd, h_oid.begin() + k * Nd + c, out_ids + i * N);
+                std::copy(h_osc.begin() + k * Nd, h_osc.begin() + k * Nd + c, out_probabilities + i * N);
+                std::fill(out_ids + i * N + c, out_ids + (i + 1) * N, (int64_t)-1);
+                std::fill(out_probabilities + i * N + c, out_probabilities + (i + 1) * N, 0.0);
+            }
+            if (out_row_counts) out_row_counts[i] = tail[(size_t)n + f];
+            if (out_iterations) out_iterations[i] = res_it[f];
+            if (out_converged) out_converged[i] = res_conv[f];
+        }
+        return LOCREC_OK;
+    }
+};
+
 }  // namespace
 
 extern "C" int32_t locrec_sg_recommend_ranked_batch(locrec_sg_graph *g, int64_t n_targets, const int64_t *vertex_ids, double alpha,
@@ -310,14 +440,9 @@ extern "C" int32_t locrec_sg_recommend_ranked_batch(locrec_sg_graph *g, int64_t 
     stats = SgRankedStats();
     if (!g) return fail(LOCREC_E_INVALID_ARG, "graph is NULL");
     if (n_targets < 0 || (n_targets > 0 && !vertex_ids)) return fail(LOCREC_E_INVALID_ARG, "bad arguments");
-    // the checks of locrec_rank_recommendations_batch
-    if (n_places < 0 || n_places >= ((int64_t)1 << 31) || n_targets >= ((int64_t)1 << 31))
-        return fail(LOCREC_E_INVALID_ARG, "place or target count out of range [0, 2^31)");
-    const int64_t N = std::max<int64_t>(0, max_recommendations);  // limit(n <= 0) is empty
-    if (N > 0 && n_targets > ((int64_t)1 << 60) / N) return fail(LOCREC_E_INVALID_ARG, "n_targets * max_recommendations overflows");
-    if (n_targets > 0 && (!target_region_ids || !out_counts || (N > 0 && (!out_ids || !out_probabilities)) ||
-                          (n_places > 0 && (!place_ids || !place_region_ids))))
-        return fail(LOCREC_E_INVALID_ARG, "null array");
+    int64_t N = 0;
+    LOCREC_TRY(sg_rk_check_args(n_targets, n_places, place_ids, place_region_ids, target_region_ids, max_recommendations, out_ids,
+                                out_probabilities, out_counts, N));
     std::vector<int32_t> uniq, uniq_of;
     LOCREC_TRY(sg_batch_targets(g, n_targets, vertex_ids, epsilon, max_iterations, uniq, uniq_of));
     if (n_targets == 0) return LOCREC_OK;
@@ -337,19 +462,15 @@ extern "C" int32_t locrec_sg_recommend_ranked_batch(locrec_sg_graph *g, int64_t 
     auto emit_row_of = [&](int32_t tv) -> int32_t { return sg_rk_row_of(g, er, tv); };
     const int64_t words = std::max<int64_t>(1, (m + 63) / 64);
 
-    // ---- the requests in emit order (by tile, then input position) and the distinct target regions
+    // ---- the requests in emit order (by tile, then input position: a pool's with one member), the distinct target regions
     std::vector<int64_t> regions(target_region_ids, target_region_ids + n);
     std::sort(regions.begin(), regions.end());
     regions.erase(std::unique(regions.begin(), regions.end()), regions.end());
     const int64_t R = (int64_t)regions.size();
-    std::vector<int64_t> first_k(nu + 1, 0);  // requests of distinct target u: ord[first_k[u] .. first_k[u + 1])
-    for (int64_t i = 0; i < n; ++i) ++first_k[(size_t)uniq_of[(size_t)i] + 1];
-    for (size_t u = 0; u < nu; ++u) first_k[u + 1] += first_k[u];
-    std::vector<int64_t> ord((size_t)n);
-    {
-        std::vector<int64_t> at(first_k.begin(), first_k.end() - 1);
-        for (int64_t i = 0; i < n; ++i) ord[(size_t)at[(size_t)uniq_of[(size_t)i]]++] = i;
-    }
+    const std::vector<int32_t> member_of((size_t)n, 0);
+    SgRkPoolOrder order;
+    sg_rk_pool_order({nu}, {tile_max}, member_of, uniq_of, order);
+    const std::vector<int64_t> &ord = order.ord;
     std::vector<int32_t> req((size_t)(3 * n));  // column, target's emit row, bitmap
     std::vector<int64_t> tgt_k((size_t)n);
     for (int64_t k = 0; k < n; ++k) {
@@ -392,58 +513,14 @@ extern "C" int32_t locrec_sg_recommend_ranked_batch(locrec_sg_graph *g, int64_t 
                            d_srow, words, d_bits.p);
     hipLaunchKernelGGL(sg_rk_popcount, dim3((unsigned)R), dim3(kRkThreads), 0, s, words, d_bits.p,
                        reinterpret_cast<unsigned long long *>(d_caps));
-    std::vector<int64_t> caps((size_t)R);
-    LOCREC_HIP_TRY(hipMemcpyAsync(caps.data(), d_caps, (size_t)R * 8, hipMemcpyDeviceToHost, s));
-    LOCREC_HIP_TRY(hipStreamSynchronize(s));
-    LOCREC_HIP_TRY(hipGetLastError());
-    ++stats.host_syncs;
-    stats.readback_bytes += R * 8;
 
-    // ---- the groups: request k's segment has room caps[its region]; a group's segments share the row buffer
-    std::vector<int64_t> cap_k((size_t)n);
-    for (int64_t k = 0; k < n; ++k) cap_k[(size_t)k] = caps[(size_t)req[(size_t)(2 * n + k)]];
-    SgRkGroups groups;
-    sg_rk_form_groups(cap_k, sg_ranked_row_budget(), groups);
-    const std::vector<int64_t> &seg_begin = groups.seg_begin, &group_end = groups.group_end;  // one past a group's last request
-    const int64_t max_rows = groups.max_rows, max_req = groups.max_req, max_cap = groups.max_cap;
-    if (max_rows >= ((int64_t)1 << 31)) return fail(LOCREC_E_INVALID_ARG, "a request's region has 2^31 places or more");
-    const int64_t Nd = std::min(N, max_cap);  // no request has more rows than the largest region: the rest is padding
-    LOCREC_HIP_TRY(hipMemcpyAsync(d_seg_begin, seg_begin.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
-    DevBuf<int64_t> d_rows, d_out;  // ids, then probabilities: the emitted rows of a group; its ranked rows and counts
+    // ---- the groups (request k's room: its region's cap), the group's buffers
+    SgRkCall rc{.stats = stats, .s = s, .n = n, .N = N, .n_places = n_places, .d_pid = d_pid, .d_preg = d_preg, .d_tgt = d_tgt,
+                .d_seg_begin = d_seg_begin, .d_seg_len = d_seg_len};
+    LOCREC_TRY(rc.plan(d_caps, (size_t)R, req.data() + 2 * n, nu));
     DevBuf<unsigned char> d_state;
-    LOCREC_TRY(d_rows.alloc(2 * (size_t)max_rows));
-    LOCREC_TRY(d_out.alloc((size_t)(2 * max_req * Nd + max_req)));
     LOCREC_TRY(d_state.alloc(kRkStateBytes));
-    int64_t *d_row_ids = d_rows.p;
-    double *d_row_probs = reinterpret_cast<double *>(d_rows.p + max_rows);
-    int64_t *d_oid = d_out.p, *d_ocnt = d_out.p + 2 * max_req * Nd;
-    double *d_osc = reinterpret_cast<double *>(d_out.p + max_req * Nd);
-    std::vector<int64_t> h_oid((size_t)(n * Nd)), h_cnt((size_t)n, 0);
-    std::vector<double> h_osc((size_t)(n * Nd));
-    size_t group = 0;  // the group that is being filled
-    auto group_first = [&](size_t gi) { return gi == 0 ? (int64_t)0 : group_end[gi - 1]; };
-    // ranks the filled group and brings its rows to the host
-    auto flush_group = [&]() -> int32_t {
-        const int64_t ka = group_first(group), nseg = group_end[group] - ka;
-        ++group;
-        ++stats.groups;
-        if (Nd == 0) return LOCREC_OK;  // every count is 0
-        LOCREC_TRY(rank_segments_device(nseg, d_seg_begin + ka, d_seg_len + ka, d_row_ids, d_row_probs, n_places, d_pid, d_preg,
-                                        d_tgt + ka, Nd, d_oid, d_osc, d_ocnt, nullptr, 0, s));
-        const RankBatchStats &rs = rank_batch_stats();
-        stats.host_syncs += rs.host_syncs;
-        stats.readback_bytes += 32 + (rs.sorted ? 4 : 0);  // the ranker's plan header, the global path's row count
-        LOCREC_HIP_TRY(hipMemcpyAsync(h_oid.data() + ka * Nd, d_oid, (size_t)(nseg * Nd) * 8, hipMemcpyDeviceToHost, s));
-        LOCREC_HIP_TRY(hipMemcpyAsync(h_osc.data() + ka * Nd, d_osc, (size_t)(nseg * Nd) * 8, hipMemcpyDeviceToHost, s));
-        LOCREC_HIP_TRY(hipMemcpyAsync(h_cnt.data() + ka, d_ocnt, (size_t)nseg * 8, hipMemcpyDeviceToHost, s));
-        LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (the next group's rows overwrite these)
-        ++stats.host_syncs;
-        stats.readback_bytes += nseg * (16 * Nd + 8);
-        return LOCREC_OK;
-    };
 
-    std::vector<int64_t> res_it(nu);
-    std::vector<int32_t> res_conv(nu);
     const unsigned emit_blocks = (unsigned)std::max<int64_t>(1, (m + kRkThreads - 1) / kRkThreads);
     auto after_tile = [&](SgBatchCtx &ctx, size_t t0, int nb) -> int32_t {
         ++stats.tiles;
@@ -464,62 +541,28 @@ extern "C" int32_t locrec_sg_recommend_ranked_batch(locrec_sg_graph *g, int64_t 
         tl.count_cols = 1;
         for (int j = 0; j < kBatchB; ++j) tl.col_trow[j] = j < nb ? emit_row_of(uniq[t0 + (size_t)j]) : -1;
         // the tile's requests, group by group
-        int64_t k = first_k[t0];
-        const int64_t kb = first_k[t0 + (size_t)nb];
+        int64_t k = order.first[t0];
+        const int64_t kb = order.tile_end(0, t0 / (size_t)tile_max, tile_max);
         while (k < kb) {
-            const int64_t ke = std::min(kb, group_end[group]);
+            const int64_t ke = std::min(kb, rc.groups.group_end[rc.group]);
             hipLaunchKernelGGL(sg_rk_emit, dim3(emit_blocks), dim3(kRkThreads), 0, s, tl, ctx.bstate, g->PA4.p, d_eid, d_bits.p,
                                words, (int32_t)k, (int32_t)ke, d_req, d_req + n, d_req + 2 * n, d_seg_begin,
-                               reinterpret_cast<unsigned long long *>(d_seg_len), max_rows, d_row_ids, d_row_probs,
+                               reinterpret_cast<unsigned long long *>(d_seg_len), rc.groups.max_rows, rc.d_row_ids, rc.d_row_probs,
                                reinterpret_cast<unsigned long long *>(d_col_rows) + t0);
             tl.count_cols = 0;
             k = ke;
-            if (k == group_end[group]) LOCREC_TRY(flush_group());
+            if (k == rc.groups.group_end[rc.group]) LOCREC_TRY(rc.flush_group());
         }
         LOCREC_HIP_TRY(hipStreamSynchronize(s));
         LOCREC_HIP_TRY(hipGetLastError());
         ++stats.host_syncs;
         stats.readback_bytes += (int64_t)kRkStateBytes;
-        const unsigned char *host = pinned ? stg : own;
-        SgBatchState hs;
-        std::memcpy(&hs, host, sizeof hs);
-        const double *totals = reinterpret_cast<const double *>(host + kBatchPackHead);
-        for (int j = 0; j < nb; ++j) {
-            const size_t u = t0 + (size_t)j;
-            LOCREC_TRY(sg_batch_verdict(hs.sweeps[j], [&]() { return totals[j]; }, ctx.eps2, ctx.max_iterations, &res_it[u],
-                                        &res_conv[u]));
-        }
-        return LOCREC_OK;
+        return sg_rk_verdicts(pinned ? stg : own, nb, ctx.eps2, ctx.max_iterations, &rc.res_it[t0], &rc.res_conv[t0]);
     };
     SgBatchCtx ctx;
     const int32_t status = sg_batch_tiles(g, uniq, alpha, epsilon, max_iterations, ctx, after_tile);
-    stats.readback_bytes += ctx.polls * 4;
-    stats.host_syncs += ctx.polls;
-    if (status != LOCREC_OK) return status;
-    // the columns' row counts and what the segments took
-    std::vector<int64_t> tail((size_t)n + nu);  // seg_len, col_rows
-    LOCREC_HIP_TRY(hipMemcpyAsync(tail.data(), d_seg_len, tail.size() * 8, hipMemcpyDeviceToHost, s));
-    LOCREC_HIP_TRY(hipStreamSynchronize(s));
-    ++stats.host_syncs;
-    stats.readback_bytes += (int64_t)tail.size() * 8;
-    for (int64_t k = 0; k < n; ++k) stats.emitted_rows += tail[(size_t)k];
-    // the caller's order and stride
-    for (int64_t k = 0; k < n; ++k) {
-        const int64_t i = ord[(size_t)k];
-        const size_t u = (size_t)uniq_of[(size_t)i];
-        const int64_t c = Nd > 0 ? h_cnt[(size_t)k] : 0;
-        out_counts[i] = c;
-        if (N > 0) {
-            std::copy(h_oid.begin() + k * Nd, h_oid.begin() + k * Nd + c, out_ids + i * N);
-            std::copy(h_osc.begin() + k * Nd, h_osc.begin() + k * Nd + c, out_probabilities + i * N);
-            std::fill(out_ids + i * N + c, out_ids + (i + 1) * N, (int64_t)-1);
-            std::fill(out_probabilities + i * N + c, out_probabilities + (i + 1) * N, 0.0);
-        }
-        if (out_row_counts) out_row_counts[i] = tail[(size_t)n + u];
-        if (out_iterations) out_iterations[i] = res_it[u];
-        if (out_converged) out_converged[i] = res_conv[u];
-    }
-    return LOCREC_OK;
+    return rc.finish(status, ctx.polls, order, member_of, uniq_of, out_ids, out_probabilities, out_counts, out_row_counts,
+                     out_iterations, out_converged);
 } LOCREC_CATCH_ALL
 
 extern "C" int32_t locrec_sg_recommend_ranked_batch_stats(int64_t *out_tiles, int64_t *out_groups, int64_t *out_emitted_rows,

@@ -1,6 +1,6 @@
-// sg_rk_plan.h -- the host's planning of the ranked SG entries (sg_ranked.h, sg_pool_ranked.h): the emit order of a pool
-// call's requests and the groups of requests whose segments share one row buffer and one ranker call.  Plain C++ without
-// a device call, so that a stand-alone program can run it under a host sanitizer.
+// sg_rk_plan.h -- the host's planning of the ranked SG entries (sg_ranked.h, sg_pool_ranked.h): the emit order of a call's
+// requests, the groups whose segments share one row buffer and one ranker call, the parts they cut a tile wave into.
+// Plain C++ without a device call: tests/host/sg_rk_plan_check.cpp runs it stand-alone, under a host sanitizer too.
 #pragma once
 
 #include <algorithm>
@@ -83,6 +83,38 @@ inline void sg_rk_pool_order(const std::vector<size_t> &nu, const std::vector<in
     out.ord.assign(n, 0);
     std::vector<int64_t> next(out.first);
     for (size_t i = 0; i < n; ++i) out.ord[(size_t)next[out.ubase[(size_t)member_of[i]] + (size_t)uniq_of[i]]++] = (int64_t)i;
+}
+
+// A tile wave's requests are one run [lo, hi) of the emit order; the groups that end inside it cut it into parts, one
+// emit launch each.  members: those with a tile in wave k, not empty.  cuts: lo, the group ends inside (lo, hi), hi.
+inline void sg_rk_wave_cuts(const std::vector<size_t> &members, size_t k, const std::vector<int> &tile_max, const SgRkPoolOrder &order,
+                            const std::vector<int64_t> &group_end, std::vector<int64_t> &cuts)
+{
+    int64_t lo = INT64_MAX, hi = 0;
+    for (const size_t a : members) {
+        lo = std::min(lo, order.tile_begin(a, k, tile_max[a]));
+        hi = std::max(hi, order.tile_end(a, k, tile_max[a]));
+    }
+    cuts.assign(1, lo);
+    for (auto ge = std::upper_bound(group_end.begin(), group_end.end(), lo); ge != group_end.end() && *ge < hi; ++ge) cuts.push_back(*ge);
+    cuts.push_back(hi);
+}
+
+// The rows of a pool call's table: a row per member and part, of the wave that has the most
+inline size_t sg_rk_pool_table_rows(const std::vector<size_t> &nu, const std::vector<int> &tile_max, const SgRkPoolOrder &order,
+                                    const std::vector<int64_t> &group_end)
+{
+    size_t rows = 1;
+    std::vector<size_t> members;
+    std::vector<int64_t> cuts;
+    for (size_t k = 0; k < order.waves; ++k) {
+        members.clear();
+        for (size_t a = 0; a < nu.size(); ++a)
+            if (k * (size_t)tile_max[a] < nu[a]) members.push_back(a);
+        sg_rk_wave_cuts(members, k, tile_max, order, group_end, cuts);
+        rows = std::max(rows, members.size() * (cuts.size() - 1));
+    }
+    return rows;
 }
 
 }  // namespace locrec

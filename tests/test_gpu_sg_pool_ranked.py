@@ -233,6 +233,104 @@ def test_row_budget_does_not_change_the_result(mixed, monkeypatch, budget):
         assert st["emit_launches"] == len({(k, grp) for k, _, grp in plan})   # one per tile wave and group part
 
 
+COMMON_STATS = ("tiles", "groups", "emitted_rows", "readback_bytes", "host_syncs")
+ONE_MEMBER_LIMITS = (0, 1, 10, 2 ** 40)
+
+
+def one_member_world(pkg, which):
+    """A graph, the pool of that graph alone and requests for it.  "synth": 17 distinct targets (two tiles, the second
+    holds a single column), the first asked three times with three regions, one request for a region nobody is in.
+    "kat": the reference's test graph has five vertices - all five, vertex 1 three times, one request for nobody's region.
+    One places table serves both: the synthetic graph's places, and the KAT graph's vertices in three regions."""
+    from locations_recommender_amd import synth
+    if which == "kat":
+        edges = kat_edges(kat())
+        v = np.array([1, 2, 3, 4, 5, 1, 1], np.int64)
+        t = np.array([0, 1, 2, NOBODYS_REGION, 1, 1, 2], np.int64)
+    else:
+        g = synth.sg_dataset(200, 30, 5, seed=79)
+        edges = edges_of(g)
+        p0 = int(g["first_person"])
+        first = np.r_[p0 + np.array([0, 3, 11, 50, 51, 120, 199, 60, 61]), PLACE0 + np.array([0, 5, 6, 7, 29]), [0, 2, 4]]
+        v = np.r_[first[:6], first[0], first[6:], first[0]].astype(np.int64)     # first[0] three times ...
+        t = (np.arange(len(v)) % 3).astype(np.int64)
+        t[[0, 6, len(v) - 1]] = [0, 1, 2]                                         # ... with regions 0, 1, 2
+        t[3] = NOBODYS_REGION
+        assert len(np.unique(v)) == TILE + 1 and len(v) == 19
+    pl, reg = places_table(30)
+    pl, reg = np.r_[pl, np.arange(1, 6)].astype(np.int64), np.r_[reg, [0, 1, 2, 0, 1]].astype(np.int64)
+    sg = pkg.SgGraph(*edges)
+    return dict(which=which, edges=edges, sg=sg, pool=pkg.SgPool([sg]), v=v, t=t, gi=np.zeros(len(v), np.int32), pl=pl, reg=reg)
+
+
+def check_one_member(pkg, w, eps, max_it, monkeypatch, budgets=(None, 1, 97), limits=ONE_MEMBER_LIMITS):
+    """A pool of one member and the ranked batch on that member, the same requests: equal results
+    (check_against_members) and equal bookkeeping - the five counters both entries report.  Term by term: the caps
+    (R * 8 = P * 8 bytes, one wait), 384 bytes and one wait per tile, 4 bytes and one wait per poll on the same schedule,
+    the ranker's header and waits per group, the ranked rows per group, the (n + nu) * 8 bytes of the tail."""
+    sg, pool, gi, v, t, pl, reg = w["sg"], w["pool"], w["gi"], w["v"], w["t"], w["pl"], w["reg"]
+    src, dst = w["edges"][0], w["edges"][1]
+    # the room of a request: its region's places among the emit rows - the live vertices, and every vertex when no sweep ran
+    caps = region_popcounts({"source_id": src if max_it == 0 else dst, "target_id": dst}, pl, reg, t)
+    assert caps.max() > 0 and not caps[t == NOBODYS_REGION].any()
+    for budget in budgets:
+        plan = emit_plan(gi, v, caps, 2 ** 62 if budget is None else budget)
+        n_groups = plan[-1][2] + 1
+        if budget is None:
+            assert n_groups == 1
+        if budget == 1:
+            assert n_groups >= np.count_nonzero(caps) > 1       # a group per request with room
+        if budget == 97 and w["which"] == "synth":              # groups of several requests; one ends inside the first tile
+            assert 1 < n_groups < np.count_nonzero(caps) and len({grp for k, _, grp in plan if k == 0}) > 1
+        for limit in limits:
+            if budget is not None:
+                monkeypatch.setenv("LOCREC_SG_RANKED_ROW_BUDGET", str(budget))
+            got = pool.recommend_ranked_batch(gi, v, ALPHA, eps, max_it, pl, reg, t, limit)
+            pst = pool.ranked_stats()
+            check_against_members(pool, gi, v, t, eps, max_it, pl, reg, limit, got)   # (the member's call: the same requests)
+            sst = pkg.SgGraph.ranked_batch_stats()
+            if budget is not None:
+                monkeypatch.delenv("LOCREC_SG_RANKED_ROW_BUDGET")
+            case = (eps, max_it, budget, limit)
+            assert {k: pst[k] for k in COMMON_STATS} == sst, (case, pst, sst)
+            assert pst["groups"] == sst["groups"] == n_groups, case
+            assert pst["tiles"] == member_tiles(gi, v) == pst["tile_waves"], case
+            if limit == 0:
+                assert got[0].shape == (len(v), 0) and not got[2].any()
+            else:
+                assert got[2].max() > 0 and not got[2][t == NOBODYS_REGION].any()
+
+
+@pytest.fixture(scope="module", params=["kat", "synth"])
+def one_member(pkg, request):
+    w = one_member_world(pkg, request.param)
+    yield w
+    w["pool"].close()
+    w["sg"].close()
+
+
+@pytest.mark.parametrize("eps,max_it", [(0.01, 20), (0.01, 0)])
+def test_one_member_pool_keeps_the_ranked_batch_s_books(pkg, one_member, monkeypatch, eps, max_it):
+    """The two entries share one host scaffold: for a pool of exactly one member the pool call and the ranked batch on
+    the member agree in tiles, groups, emitted_rows, readback_bytes and host_syncs, under every row budget (one group, a
+    group per request, groups that end inside a tile) and every limit, with (max_it = 0) and without the source-only
+    rows."""
+    check_one_member(pkg, one_member, eps, max_it, monkeypatch)
+
+
+def test_one_member_pool_keeps_the_books_with_plain_copy_states(pkg, monkeypatch):
+    """The same with the member (and so the pool) created under LOCREC_SG_NO_PACK, which is read when a graph is
+    created: both entries read their states back through a device buffer and a plain copy."""
+    monkeypatch.setenv("LOCREC_SG_NO_PACK", "1")
+    w = one_member_world(pkg, "synth")
+    monkeypatch.delenv("LOCREC_SG_NO_PACK")
+    try:
+        check_one_member(pkg, w, 0.01, 20, monkeypatch, limits=(10,))
+    finally:
+        w["pool"].close()
+        w["sg"].close()
+
+
 def test_layout_classes_share_a_ranked_pool(pkg, monkeypatch):
     """uint16 / int32 columns x dictionary / fp64 weights in one pool (the pool of test_layout_classes_share_a_pool)."""
     from locations_recommender_amd import mains, synth
