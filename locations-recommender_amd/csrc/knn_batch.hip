@@ -232,21 +232,25 @@ struct locrec_knn_pool {
 
 namespace {
 
-// One pool call after its checks: the distinct (member, row) requests, the shared members' batches, the others
-struct KnnPoolPlan {
-    std::vector<int64_t> distinct_of;      // request -> its distinct request, or -1 (a delegated member's)
-    std::vector<int32_t> rows;             // the distinct requests' rows, member after member
+// One pool call: its requests sorted out (knn_pool_plan.h), the sharing members' batches and their rows in the pool's buffers
+struct KnnPoolCall : locrec::KnnPoolRequests {
     std::vector<locrec::KnnPoolBatch> batches;
-    std::vector<int32_t> delegated;        // members served by their own call, ascending
-    std::vector<std::vector<int64_t>> requests_of;  // per delegated member: its requests, in input order
+    std::vector<int64_t> base, len;  // per distinct request: its rows in d_place / d_est
+    const int64_t *d_place = nullptr;
+    const double *d_est = nullptr;
 };
 
 bool knn_pool_shares(const locrec_knn_index *ix, int64_t k) { return k > LOCREC_KNN_BATCH_MAX_K && k >= ix->n - 1; }
 
-// The checks of a pool call, before any device work: every index position, check_params' requires, every person.
-int32_t knn_pool_plan(locrec_knn_pool *pool, int64_t n, const int32_t *index_of, const int64_t *persons, double pw, double cw,
-                      int64_t k, int64_t *out_bad, KnnPoolPlan &plan)
+// The beginning of both pool entries, before any device work: the arguments they share (outputs_ok: the entry's own),
+// the stats, then the checks in this order - every index position, check_params' requires, every person - and the plan.
+int32_t knn_pool_begin(locrec_knn_pool *pool, int64_t n, const int32_t *index_of, const int64_t *persons, double pw, double cw,
+                       int64_t k, bool outputs_ok, int64_t *out_bad, KnnPoolCall &call)
 {
+    if (!pool) return fail(LOCREC_E_INVALID_ARG, "pool is NULL");
+    if (out_bad) *out_bad = -1;
+    locrec::knn_pool_stats() = locrec::KnnPoolStats();
+    if (n < 0 || (n > 0 && (!index_of || !persons)) || !outputs_ok) return fail(LOCREC_E_INVALID_ARG, "bad arguments");
     const int32_t nm = (int32_t)pool->members.size();
     for (int64_t i = 0; i < n; ++i)
         if (index_of[i] < 0 || index_of[i] >= nm) {
@@ -262,52 +266,22 @@ int32_t knn_pool_plan(locrec_knn_pool *pool, int64_t n, const int32_t *index_of,
             return st;
         }
     }
-    // the requests by (member, row): a repeated pair is computed once
-    std::vector<int64_t> ord((size_t)n);
-    std::iota(ord.begin(), ord.end(), (int64_t)0);
-    std::sort(ord.begin(), ord.end(), [&](int64_t a, int64_t b) {
-        return index_of[a] != index_of[b] ? index_of[a] < index_of[b] : row[(size_t)a] != row[(size_t)b] ? row[(size_t)a] < row[(size_t)b] : a < b;
-    });
-    plan.distinct_of.assign((size_t)n, -1);
-    plan.rows.reserve((size_t)n);
-    std::vector<std::pair<int32_t, int64_t>> first_of;  // shared member -> its first distinct request
-    for (int64_t j = 0; j < n; ++j) {
-        const int64_t i = ord[(size_t)j];
-        const int32_t m = index_of[i];
-        if (!knn_pool_shares(pool->members[(size_t)m], k)) {
-            if (plan.delegated.empty() || plan.delegated.back() != m) {
-                plan.delegated.push_back(m);
-                plan.requests_of.emplace_back();
-            }
-            plan.requests_of.back().push_back(i);
-            continue;
-        }
-        const bool same = j > 0 && index_of[ord[(size_t)j - 1]] == m && row[(size_t)ord[(size_t)j - 1]] == row[(size_t)i];
-        if (!same) {
-            if (first_of.empty() || first_of.back().first != m) first_of.push_back({m, (int64_t)plan.rows.size()});
-            plan.rows.push_back(row[(size_t)i]);
-        }
-        plan.distinct_of[(size_t)i] = (int64_t)plan.rows.size() - 1;
-    }
-    for (std::vector<int64_t> &r : plan.requests_of) std::sort(r.begin(), r.end());
-    for (size_t b = 0; b < first_of.size(); ++b) {
-        const int64_t first = first_of[b].second;
-        const int64_t end = b + 1 < first_of.size() ? first_of[b + 1].second : (int64_t)plan.rows.size();
-        plan.batches.push_back({pool->members[(size_t)first_of[b].first], plan.rows.data() + first, end - first, first});
-    }
+    std::vector<char> shares((size_t)nm);
+    for (int32_t m = 0; m < nm; ++m) shares[(size_t)m] = knn_pool_shares(pool->members[(size_t)m], k);
+    locrec::knn_pool_requests(n, index_of, row.data(), shares, call);
+    for (const auto &c : call.cuts) call.batches.push_back({pool->members[(size_t)c.member], call.rows.data() + c.first, c.n, c.first});
     return LOCREC_OK;
 }
 
 // the shared members' part of a call: rows resident in the pool's buffers
-int32_t knn_pool_run_shared(locrec_knn_pool *pool, const KnnPoolPlan &plan, double pw, double cw, std::vector<int64_t> &base,
-                            std::vector<int64_t> &len, const int64_t **place, const double **est)
+int32_t knn_pool_run_shared(locrec_knn_pool *pool, KnnPoolCall &call, double pw, double cw)
 {
-    base.assign(plan.rows.size(), 0);
-    len.assign(plan.rows.size(), 0);
-    *place = nullptr;
-    *est = nullptr;
-    if (plan.batches.empty()) return LOCREC_OK;
-    return locrec::knn_pool_shared_run(pool->shared, pool->stream, plan.batches, pw, cw, base.data(), len.data(), place, est);
+    LOCREC_HIP_TRY(hipSetDevice(pool->device));
+    call.base.assign(call.rows.size(), 0);
+    call.len.assign(call.rows.size(), 0);
+    if (call.batches.empty()) return LOCREC_OK;
+    return locrec::knn_pool_shared_run(pool->shared, pool->stream, call.batches, pw, cw, call.base.data(), call.len.data(),
+                                       &call.d_place, &call.d_est);
 }
 
 // nothing stays resident in a member for locrec_knn_fetch_*
@@ -316,6 +290,22 @@ void knn_pool_forget(locrec_knn_index *ix)
     ix->have_result = false;
     ix->have_agg = false;
     ix->have_lkb = false;
+}
+
+// the other members: f(d, member, its requests in input order, their persons) = its own public call and the scatter
+template <class F>
+int32_t knn_pool_each_delegated(locrec_knn_pool *pool, const KnnPoolCall &call, const int64_t *person_ids, F f)
+{
+    locrec::knn_pool_stats().delegated_members = (int64_t)call.delegated.size();
+    for (size_t d = 0; d < call.delegated.size(); ++d) {
+        locrec_knn_index *ix = pool->members[(size_t)call.delegated[d]];
+        std::vector<int64_t> ids;
+        for (int64_t i : call.requests_of[d]) ids.push_back(person_ids[i]);
+        const int32_t rc = f(d, ix, call.requests_of[d], ids);
+        knn_pool_forget(ix);
+        if (rc != LOCREC_OK) return rc;
+    }
+    return LOCREC_OK;
 }
 
 }  // namespace
@@ -359,91 +349,69 @@ extern "C" int32_t locrec_knn_pool_recommend_batch(locrec_knn_pool *pool, int64_
                                                    int64_t *out_offsets, int64_t *out_places, double *out_ratings,
                                                    int64_t *inout_capacity, int64_t *out_bad_request) try
 {
-    if (!pool) return fail(LOCREC_E_INVALID_ARG, "pool is NULL");
-    if (out_bad_request) *out_bad_request = -1;
-    locrec::knn_pool_stats() = locrec::KnnPoolStats();
     const int64_t n = n_requests;
-    if (n < 0 || (n > 0 && (!index_of_request || !person_ids)) || !out_offsets || !inout_capacity)
-        return fail(LOCREC_E_INVALID_ARG, "bad arguments");
-    KnnPoolPlan plan;
-    LOCREC_TRY(knn_pool_plan(pool, n, index_of_request, person_ids, pw, cw, k, out_bad_request, plan));
+    KnnPoolCall call;
+    LOCREC_TRY(knn_pool_begin(pool, n, index_of_request, person_ids, pw, cw, k, out_offsets && inout_capacity, out_bad_request, call));
     if (n == 0) {
         out_offsets[0] = 0;
         *inout_capacity = 0;
         return LOCREC_OK;
     }
-    LOCREC_HIP_TRY(hipSetDevice(pool->device));
+    LOCREC_TRY(knn_pool_run_shared(pool, call, pw, cw));
     locrec::KnnPoolStats &st = locrec::knn_pool_stats();
     hipStream_t s = pool->stream;
-    std::vector<int64_t> base, len, rlen((size_t)n, 0);
-    const int64_t *d_place = nullptr;
-    const double *d_est = nullptr;
-    LOCREC_TRY(knn_pool_run_shared(pool, plan, pw, cw, base, len, &d_place, &d_est));
+    const std::vector<int64_t> &base = call.base, &len = call.len;
+    std::vector<int64_t> rlen((size_t)n, 0);
     for (int64_t i = 0; i < n; ++i)
-        if (plan.distinct_of[(size_t)i] >= 0) rlen[(size_t)i] = len[(size_t)plan.distinct_of[(size_t)i]];
+        if (call.distinct_of[(size_t)i] >= 0) rlen[(size_t)i] = len[(size_t)call.distinct_of[(size_t)i]];
     // the other members: their own call on their own persons, sizes first
-    st.delegated_members = (int64_t)plan.delegated.size();
-    std::vector<std::vector<int64_t>> d_ids(plan.delegated.size()), d_off(plan.delegated.size());
-    for (size_t d = 0; d < plan.delegated.size(); ++d) {
-        locrec_knn_index *ix = pool->members[(size_t)plan.delegated[d]];
-        const std::vector<int64_t> &rq = plan.requests_of[d];
-        for (int64_t i : rq) d_ids[d].push_back(person_ids[i]);
+    std::vector<std::vector<int64_t>> d_off(call.delegated.size());
+    const auto sizes = [&](size_t d, locrec_knn_index *ix, const auto &rq, const auto &ids) -> int32_t {
         d_off[d].assign(rq.size() + 1, 0);
         int64_t cap = 0;
-        const int32_t rc = locrec_knn_recommend_batch(ix, (int64_t)rq.size(), d_ids[d].data(), pw, cw, k, d_off[d].data(), nullptr,
-                                                      nullptr, &cap);
-        knn_pool_forget(ix);
-        if (rc != LOCREC_OK) return rc;
+        LOCREC_TRY(locrec_knn_recommend_batch(ix, (int64_t)rq.size(), ids.data(), pw, cw, k, d_off[d].data(), nullptr, nullptr, &cap));
         for (size_t j = 0; j < rq.size(); ++j) rlen[(size_t)rq[j]] = d_off[d][j + 1] - d_off[d][j];
-    }
-    int64_t total = 0;
-    for (int64_t i = 0; i < n; ++i) total += rlen[(size_t)i];
-    const int64_t cap = *inout_capacity;
-    if (total > cap || total == 0) {  // (nothing but the offsets and the total)
-        out_offsets[0] = 0;
-        for (int64_t i = 0; i < n; ++i) out_offsets[i + 1] = out_offsets[i] + rlen[(size_t)i];
-        *inout_capacity = total;
         return LOCREC_OK;
-    }
-    if (!out_places || !out_ratings) return fail(LOCREC_E_INVALID_ARG, "NULL output buffer");
+    };
+    LOCREC_TRY(knn_pool_each_delegated(pool, call, person_ids, sizes));
+    const int64_t total = std::accumulate(rlen.begin(), rlen.end(), (int64_t)0);
+    const bool sizes_only = total > *inout_capacity || total == 0;  // (nothing but the offsets and the total)
+    if (!sizes_only && (!out_places || !out_ratings)) return fail(LOCREC_E_INVALID_ARG, "NULL output buffer");
     out_offsets[0] = 0;
     for (int64_t i = 0; i < n; ++i) out_offsets[i + 1] = out_offsets[i] + rlen[(size_t)i];
     *inout_capacity = total;
+    if (sizes_only) return LOCREC_OK;
     // the shared rows: one copy of the pool's row buffer, handed out in input order
     int64_t resident = 0;
     for (size_t u = 0; u < len.size(); ++u) resident = std::max(resident, base[u] + len[u]);
     std::vector<int64_t> hp((size_t)resident);
     std::vector<double> he((size_t)resident);
     if (resident > 0) {
-        LOCREC_HIP_TRY(hipMemcpyAsync(hp.data(), d_place, (size_t)resident * 8, hipMemcpyDeviceToHost, s));
-        LOCREC_HIP_TRY(hipMemcpyAsync(he.data(), d_est, (size_t)resident * 8, hipMemcpyDeviceToHost, s));
+        LOCREC_HIP_TRY(hipMemcpyAsync(hp.data(), call.d_place, (size_t)resident * 8, hipMemcpyDeviceToHost, s));
+        LOCREC_HIP_TRY(hipMemcpyAsync(he.data(), call.d_est, (size_t)resident * 8, hipMemcpyDeviceToHost, s));
         LOCREC_HIP_TRY(hipStreamSynchronize(s));
         st.readback_bytes += resident * 16;
         ++st.host_syncs;
     }
     for (int64_t i = 0; i < n; ++i) {
-        const int64_t u = plan.distinct_of[(size_t)i];
+        const int64_t u = call.distinct_of[(size_t)i];
         if (u < 0 || len[(size_t)u] == 0) continue;
         std::copy(hp.begin() + base[(size_t)u], hp.begin() + base[(size_t)u] + len[(size_t)u], out_places + out_offsets[i]);
         std::copy(he.begin() + base[(size_t)u], he.begin() + base[(size_t)u] + len[(size_t)u], out_ratings + out_offsets[i]);
     }
-    for (size_t d = 0; d < plan.delegated.size(); ++d) {
-        locrec_knn_index *ix = pool->members[(size_t)plan.delegated[d]];
-        const std::vector<int64_t> &rq = plan.requests_of[d];
+    const auto rows = [&](size_t d, locrec_knn_index *ix, const auto &rq, const auto &ids) -> int32_t {
         int64_t mcap = d_off[d].back();
-        if (mcap == 0) continue;
+        if (mcap == 0) return LOCREC_OK;
         std::vector<int64_t> mp((size_t)mcap);
         std::vector<double> me((size_t)mcap);
-        const int32_t rc = locrec_knn_recommend_batch(ix, (int64_t)rq.size(), d_ids[d].data(), pw, cw, k, d_off[d].data(), mp.data(),
-                                                      me.data(), &mcap);
-        knn_pool_forget(ix);
-        if (rc != LOCREC_OK) return rc;
+        LOCREC_TRY(locrec_knn_recommend_batch(ix, (int64_t)rq.size(), ids.data(), pw, cw, k, d_off[d].data(), mp.data(), me.data(), &mcap));
         for (size_t j = 0; j < rq.size(); ++j) {
             std::copy(mp.begin() + d_off[d][j], mp.begin() + d_off[d][j + 1], out_places + out_offsets[rq[j]]);
             std::copy(me.begin() + d_off[d][j], me.begin() + d_off[d][j + 1], out_ratings + out_offsets[rq[j]]);
         }
-    }
-    return LOCREC_OK;
+        return LOCREC_OK;
+    };
+    return knn_pool_each_delegated(pool, call, person_ids, rows);
 } LOCREC_CATCH_ALL
 
 extern "C" int32_t locrec_knn_pool_recommend_ranked_batch(locrec_knn_pool *pool, int64_t n_requests, const int32_t *index_of_request,
@@ -454,96 +422,62 @@ extern "C" int32_t locrec_knn_pool_recommend_ranked_batch(locrec_knn_pool *pool,
                                                           double *out_estimated_ratings, int64_t *out_counts,
                                                           int64_t *out_bad_request) try
 {
-    if (!pool) return fail(LOCREC_E_INVALID_ARG, "pool is NULL");
-    if (out_bad_request) *out_bad_request = -1;
-    locrec::knn_pool_stats() = locrec::KnnPoolStats();
     const int64_t n = n_requests, N = std::max<int64_t>(0, max_recommendations);
-    if (n < 0 || (n > 0 && (!index_of_request || !person_ids))) return fail(LOCREC_E_INVALID_ARG, "bad arguments");
-    KnnPoolPlan plan;
-    LOCREC_TRY(knn_pool_plan(pool, n, index_of_request, person_ids, pw, cw, k, out_bad_request, plan));
+    KnnPoolCall call;
+    LOCREC_TRY(knn_pool_begin(pool, n, index_of_request, person_ids, pw, cw, k, true, out_bad_request, call));
     if (n == 0) return LOCREC_OK;
-    // (knn_rank_resident's checks, here before any device work)
-    if (n_places < 0 || n_places >= ((int64_t)1 << 31)) return fail(LOCREC_E_INVALID_ARG, "place count out of range [0, 2^31)");
-    if (!out_counts || !target_region_ids || (N > 0 && (!out_place_ids || !out_estimated_ratings)) ||
-        (n_places > 0 && (!place_ids || !place_region_ids)))
-        return fail(LOCREC_E_INVALID_ARG, "NULL argument");
-    LOCREC_HIP_TRY(hipSetDevice(pool->device));
+    LOCREC_TRY(knn_rank_check_args(n_places, place_ids, place_region_ids, target_region_ids, N, out_place_ids, out_estimated_ratings,
+                                   out_counts));
+    LOCREC_TRY(knn_pool_run_shared(pool, call, pw, cw));
     locrec::KnnPoolStats &st = locrec::knn_pool_stats();
     hipStream_t s = pool->stream;
-    std::vector<int64_t> base, len;
-    const int64_t *d_place = nullptr;
-    const double *d_est = nullptr;
-    LOCREC_TRY(knn_pool_run_shared(pool, plan, pw, cw, base, len, &d_place, &d_est));
     // one segment per request of a shared member: duplicates share a row range and keep their own targets
     std::vector<int64_t> seg_req, hin;
     for (int64_t i = 0; i < n; ++i)
-        if (plan.distinct_of[(size_t)i] >= 0) seg_req.push_back(i);
+        if (call.distinct_of[(size_t)i] >= 0) seg_req.push_back(i);
     const int64_t nseg = (int64_t)seg_req.size();
     if (nseg > 0) {
         // ONE upload of the places table, the targets and the segments; one ranker call over the pool's row buffer
-        hin.resize(2 * (size_t)n_places + 3 * (size_t)nseg);
+        hin.resize(RankIo::in_words(n_places, nseg));
         if (n_places > 0) {
             std::copy(place_ids, place_ids + n_places, hin.begin());
             std::copy(place_region_ids, place_region_ids + n_places, hin.begin() + n_places);
         }
         for (int64_t c = 0; c < nseg; ++c) {
-            const int64_t u = plan.distinct_of[(size_t)seg_req[(size_t)c]];
+            const int64_t u = call.distinct_of[(size_t)seg_req[(size_t)c]];
             hin[(size_t)(2 * n_places + c)] = target_region_ids[seg_req[(size_t)c]];
-            hin[(size_t)(2 * n_places + nseg + c)] = base[(size_t)u];
-            hin[(size_t)(2 * n_places + 2 * nseg + c)] = len[(size_t)u];
+            hin[(size_t)(2 * n_places + nseg + c)] = call.base[(size_t)u];
+            hin[(size_t)(2 * n_places + 2 * nseg + c)] = call.len[(size_t)u];
         }
         LOCREC_TRY(pool->rk_in.reserve(hin.size()));
-        LOCREC_TRY(pool->rk_out.reserve(2 * (size_t)(nseg * N) + (size_t)nseg));
-        int64_t *d_in = pool->rk_in.p, *d_tgt = d_in + 2 * n_places, *d_b = d_tgt + nseg, *d_l = d_b + nseg;
-        int64_t *d_oid = pool->rk_out.p, *d_ocnt = d_oid + 2 * nseg * N;
-        double *d_osc = reinterpret_cast<double *>(d_oid + nseg * N);
-        LOCREC_HIP_TRY(hipMemcpyAsync(d_in, hin.data(), hin.size() * 8, hipMemcpyHostToDevice, s));
-        const int32_t rc = rank_segments_device(nseg, d_b, d_l, d_place, d_est, n_places, d_in, d_in + n_places, d_tgt, N, d_oid, d_osc,
-                                                d_ocnt, nullptr, 0, s);
+        LOCREC_TRY(pool->rk_out.reserve(RankIo::out_words(nseg, N)));
+        const RankIo io(pool->rk_in.p, pool->rk_out.p, n_places, nseg, N);
+        LOCREC_HIP_TRY(hipMemcpyAsync(pool->rk_in.p, hin.data(), hin.size() * 8, hipMemcpyHostToDevice, s));
+        const int32_t rc = io.rank(call.d_place, call.d_est, 0, s);
         if (rc != LOCREC_OK) {
             (void)hipStreamSynchronize(s);
             return rc;
         }
-        std::vector<int64_t> hid((size_t)(nseg * N)), hcnt((size_t)nseg);
-        std::vector<double> hsc((size_t)(nseg * N));
-        if (N > 0) {
-            LOCREC_HIP_TRY(hipMemcpyAsync(hid.data(), d_oid, (size_t)(nseg * N) * 8, hipMemcpyDeviceToHost, s));
-            LOCREC_HIP_TRY(hipMemcpyAsync(hsc.data(), d_osc, (size_t)(nseg * N) * 8, hipMemcpyDeviceToHost, s));
-        }
-        LOCREC_HIP_TRY(hipMemcpyAsync(hcnt.data(), d_ocnt, (size_t)nseg * 8, hipMemcpyDeviceToHost, s));
-        LOCREC_HIP_TRY(hipStreamSynchronize(s));
+        LOCREC_TRY(io.read_back_to(seg_req, out_place_ids, out_estimated_ratings, out_counts, s));
         st.readback_bytes += nseg * N * 16 + nseg * 8;
         st.host_syncs += rank_batch_stats().host_syncs + 1;
-        for (int64_t c = 0; c < nseg; ++c) {
-            const int64_t i = seg_req[(size_t)c];
-            std::copy(hid.begin() + c * N, hid.begin() + (c + 1) * N, out_place_ids + i * N);
-            std::copy(hsc.begin() + c * N, hsc.begin() + (c + 1) * N, out_estimated_ratings + i * N);
-            out_counts[i] = hcnt[(size_t)c];
-        }
     }
     // the other members: their own ranked call on their own requests
-    st.delegated_members = (int64_t)plan.delegated.size();
-    for (size_t d = 0; d < plan.delegated.size(); ++d) {
-        locrec_knn_index *ix = pool->members[(size_t)plan.delegated[d]];
-        const std::vector<int64_t> &rq = plan.requests_of[d];
+    const auto ranked = [&](size_t, locrec_knn_index *ix, const auto &rq, const auto &ids) -> int32_t {
         const int64_t nq = (int64_t)rq.size();
-        std::vector<int64_t> ids((size_t)nq), tgt((size_t)nq), oid((size_t)(nq * N)), ocnt((size_t)nq);
+        std::vector<int64_t> tgt((size_t)nq), oid((size_t)(nq * N)), ocnt((size_t)nq);
         std::vector<double> osc((size_t)(nq * N));
-        for (int64_t j = 0; j < nq; ++j) {
-            ids[(size_t)j] = person_ids[rq[(size_t)j]];
-            tgt[(size_t)j] = target_region_ids[rq[(size_t)j]];
-        }
-        const int32_t rc = locrec_knn_recommend_ranked_batch(ix, nq, ids.data(), pw, cw, k, n_places, place_ids, place_region_ids,
-                                                             tgt.data(), max_recommendations, oid.data(), osc.data(), ocnt.data());
-        knn_pool_forget(ix);
-        if (rc != LOCREC_OK) return rc;
+        for (int64_t j = 0; j < nq; ++j) tgt[(size_t)j] = target_region_ids[rq[(size_t)j]];
+        LOCREC_TRY(locrec_knn_recommend_ranked_batch(ix, nq, ids.data(), pw, cw, k, n_places, place_ids, place_region_ids, tgt.data(),
+                                                     max_recommendations, oid.data(), osc.data(), ocnt.data()));
         for (int64_t j = 0; j < nq; ++j) {
             std::copy(oid.begin() + j * N, oid.begin() + (j + 1) * N, out_place_ids + rq[(size_t)j] * N);
             std::copy(osc.begin() + j * N, osc.begin() + (j + 1) * N, out_estimated_ratings + rq[(size_t)j] * N);
             out_counts[rq[(size_t)j]] = ocnt[(size_t)j];
         }
-    }
-    return LOCREC_OK;
+        return LOCREC_OK;
+    };
+    return knn_pool_each_delegated(pool, call, person_ids, ranked);
 } LOCREC_CATCH_ALL
 
 extern "C" int32_t locrec_knn_pool_stats(int64_t *out_waves, int64_t *out_member_tiles, int64_t *out_fill_launches,

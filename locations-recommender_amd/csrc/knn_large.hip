@@ -19,6 +19,7 @@
 #include <algorithm>
 
 #include "knn_index.h"
+#include "knn_pool_plan.h"
 
 namespace {
 
@@ -372,8 +373,7 @@ int32_t sort_all(locrec_knn_index *ix, int32_t qrow, double pw, double cw, int64
 // sum += qd * value left to right in ascending index order - BLAS.dot's order, a product with an absent query
 // entry adds +-0.0 - so similarities are the reference's bit for bit in EVERY stored format (the GENERIC fp64
 // one included); the aggregation is the single request's kernels with kLkbQt columns, so a batch's estimates equal
-// the single request's bit for bit.
-constexpr int kLkbQt = 16;
+// the single request's bit for bit.  (kLkbQt, the tile's queries: knn_pool_plan.h)
 
 struct LkbScan {
     const int64_t *p_ptr, *c_ptr;
@@ -699,19 +699,14 @@ static int lkt_tile_rows(const locrec_knn_index *ix, const int32_t *rows, int64_
     return nt;
 }
 
-// One tile of the scan: the similarities of the queries rows[0 .. nt) against every row -> ix->lkb_S, [row][kLkbQt] or
-// transposed [kLkbQt][row] (dense fp64 query tables, every candidate walks its plain CSR row: exact in every stored
-// format and for every row, wide ones included).  The queries' vectors are scattered into the dense tables, lkb_scan
-// runs, the tables are wiped for the next tile.
-static int32_t lkb_scan_tile(locrec_knn_index *ix, const int32_t *rows, int nt, double pw, double cw, bool transposed, bool profiled)
+// What the fill and scan kernels get for the tile of the queries rows[0 .. nt) of ix (their `set` is the launch's): the
+// dense tables and the bitmap, the CSR rows, the weights, the layout of S, the tile's candidate counters.  maxp / maxc:
+// the longest place and category vector among the tile's queries.
+static void lkb_describe_tile(locrec_knn_index *ix, const int32_t *rows, int nt, double pw, double cw, bool transposed, int32_t *cand,
+                              LkbFill &fp, LkbFill &fc, LkbScan &P, int &maxp, int &maxc)
 {
-    hipStream_t s = ix->stream;
-    const int32_t n = (int32_t)ix->n;
-    LkbScan P{};
-    LkbFill fp{}, fc{};
     bool invalid[kLkbQt];
     lkt_tile_rows(ix, rows, nt, 0, P.qrow, invalid);
-    int maxp = 1, maxc = 1;
     for (int t = 0; t < kLkbQt; ++t) {
         const int32_t r = fp.qrow[t] = fc.qrow[t] = P.qrow[t];
         if (r >= 0) {
@@ -724,21 +719,34 @@ static int32_t lkb_scan_tile(locrec_knn_index *ix, const int32_t *rows, int nt, 
     P.bits = fp.bits;
     P.bit_mask = fp.bit_mask;
     fc.ptr = ix->fc.csr_ptr.p; fc.idx = ix->fc.csr_idx.p; fc.val = ix->fc.csr_val.p; fc.qd = ix->lkb_qd_c.p;
-    const dim3 gp((unsigned)((maxp + 255) / 256), kLkbQt), gc((unsigned)((maxc + 255) / 256), kLkbQt);
-    fp.set = fc.set = 1;
-    hipLaunchKernelGGL(lkb_fill, gp, dim3(256), 0, s, fp);
-    hipLaunchKernelGGL(lkb_fill, gc, dim3(256), 0, s, fc);
     P.p_ptr = ix->fp.csr_ptr.p; P.p_idx = ix->fp.csr_idx.p; P.p_val = ix->fp.csr_val.p;
     P.c_ptr = ix->fc.csr_ptr.p; P.c_idx = ix->fc.csr_idx.p; P.c_val = ix->fc.csr_val.p;
     P.norm_p = ix->fp.norm.p; P.norm_c = ix->fc.norm.p;
     P.qd_p = ix->lkb_qd_p.p; P.qd_c = ix->lkb_qd_c.p;
-    P.nrows = n;
+    P.nrows = (int32_t)ix->n;
     P.pw = pw; P.cw = cw;
     P.S = ix->lkb_S.p;
-    P.cand = ix->lkb_cand.p;
+    P.cand = cand;
     P.transposed = transposed ? 1 : 0;
+}
+
+// One tile of the scan: the similarities of the queries rows[0 .. nt) against every row -> ix->lkb_S, [row][kLkbQt] or
+// transposed [kLkbQt][row] (dense fp64 query tables, every candidate walks its plain CSR row: exact in every stored
+// format and for every row, wide ones included).  The queries' vectors are scattered into the dense tables, lkb_scan
+// runs, the tables are wiped for the next tile.
+static int32_t lkb_scan_tile(locrec_knn_index *ix, const int32_t *rows, int nt, double pw, double cw, bool transposed, bool profiled)
+{
+    hipStream_t s = ix->stream;
+    LkbScan P{};
+    LkbFill fp{}, fc{};
+    int maxp = 1, maxc = 1;
+    lkb_describe_tile(ix, rows, nt, pw, cw, transposed, ix->lkb_cand.p, fp, fc, P, maxp, maxc);
+    const dim3 gp((unsigned)((maxp + 255) / 256), kLkbQt), gc((unsigned)((maxc + 255) / 256), kLkbQt);
+    fp.set = fc.set = 1;
+    hipLaunchKernelGGL(lkb_fill, gp, dim3(256), 0, s, fp);
+    hipLaunchKernelGGL(lkb_fill, gc, dim3(256), 0, s, fc);
     LOCREC_HIP_TRY(hipMemsetAsync(ix->lkb_cand.p, 0, kLkbQt * sizeof(int32_t), s));
-    const dim3 grid((unsigned)((n + 255) / 256));
+    const dim3 grid((unsigned)((P.nrows + 255) / 256));
     const size_t lds = (P.bit_mask + 1u) / 8u;
     if (profiled) LOCREC_LAUNCH_PROFILED(ix->prof, lkb_scan, grid, dim3(256), lds, s, P);
     else hipLaunchKernelGGL(lkb_scan, grid, dim3(256), lds, s, P);
@@ -746,6 +754,24 @@ static int32_t lkb_scan_tile(locrec_knn_index *ix, const int32_t *rows, int nt, 
     hipLaunchKernelGGL(lkb_fill, gp, dim3(256), 0, s, fp);
     hipLaunchKernelGGL(lkb_fill, gc, dim3(256), 0, s, fc);
     LOCREC_HIP_TRY(hipGetLastError());
+    return LOCREC_OK;
+}
+
+// The first `keep` rows of a grow-only row buffer (place, est) survive its growth to hold `total` rows; the copy is waited
+// for (only when keep > 0: the caller counts that wait) before the old pair is freed.
+static int32_t lkb_grow_rows(DevBuf<int64_t> &place, DevBuf<double> &est, int64_t total, int64_t keep, hipStream_t s)
+{
+    DevBuf<int64_t> np_buf;
+    DevBuf<double> ne_buf;
+    LOCREC_TRY(np_buf.alloc(knn_rows_room(total)));
+    LOCREC_TRY(ne_buf.alloc(knn_rows_room(total)));
+    if (keep > 0) {
+        LOCREC_HIP_TRY(hipMemcpyAsync(np_buf.p, place.p, (size_t)keep * 8, hipMemcpyDeviceToDevice, s));
+        LOCREC_HIP_TRY(hipMemcpyAsync(ne_buf.p, est.p, (size_t)keep * 8, hipMemcpyDeviceToDevice, s));
+        LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    }
+    std::swap(place.p, np_buf.p); std::swap(place.n, np_buf.n);
+    std::swap(est.p, ne_buf.p); std::swap(est.n, ne_buf.n);
     return LOCREC_OK;
 }
 
@@ -763,32 +789,11 @@ static int32_t lkb_aggregate_tile(locrec_knn_index *ix, const double *S, const i
         LOCREC_HIP_TRY(hipMemcpyAsync(tc.data(), ix->lkb_tile_cnt.p, tc.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         LOCREC_HIP_TRY(hipStreamSynchronize(s));
         LkBases<kLkbQt> B{};
-        for (int t = 0; t < kLkbQt; ++t) {
-            int64_t c = 0;
-            if (t < nt && qrow[t] >= 0)
-                for (int i = 0; i < tiles; ++i) c += tc[(size_t)t * tiles + i];
-            B.base[t] = t < nt ? total : -1;
-            if (t < nt) {
-                ix->lkb_off[(size_t)(q0 + t)] = total;
-                total += c;
-            }
-        }
-        // grow-only output with headroom: the rows of the tiles emitted so far must survive a growth
-        if ((size_t)total > ix->lkb_place.n) {
-            DevBuf<int64_t> np_buf;
-            DevBuf<double> ne_buf;
-            const size_t want = (size_t)total + (size_t)total / 2 + 1024;
-            LOCREC_TRY(np_buf.alloc(want));
-            LOCREC_TRY(ne_buf.alloc(want));
-            const int64_t keep = ix->lkb_off[(size_t)q0];
-            if (keep > 0) {
-                LOCREC_HIP_TRY(hipMemcpyAsync(np_buf.p, ix->lkb_place.p, (size_t)keep * 8, hipMemcpyDeviceToDevice, s));
-                LOCREC_HIP_TRY(hipMemcpyAsync(ne_buf.p, ix->lkb_est.p, (size_t)keep * 8, hipMemcpyDeviceToDevice, s));
-                LOCREC_HIP_TRY(hipStreamSynchronize(s));
-            }
-            std::swap(ix->lkb_place.p, np_buf.p); std::swap(ix->lkb_place.n, np_buf.n);
-            std::swap(ix->lkb_est.p, ne_buf.p); std::swap(ix->lkb_est.n, ne_buf.n);
-        }
+        int64_t len[kLkbQt];
+        total = knn_tile_bases(tc.data(), tiles, nt, qrow, total, B.base, len);
+        for (int t = 0; t < nt; ++t) ix->lkb_off[(size_t)(q0 + t)] = B.base[t];
+        // grow-only output with headroom: the rows of the tiles emitted so far (B.base[0] of them) must survive a growth
+        if ((size_t)total > ix->lkb_place.n) LOCREC_TRY(lkb_grow_rows(ix->lkb_place, ix->lkb_est, total, B.base[0], s));
         hipLaunchKernelGGL(lk_finish_emit<kLkbQt>, dim3((unsigned)tiles, kLkbQt), dim3(256), 0, s, ix->lkb_ws.p, ix->lkb_ss.p, np,
                            ix->lkb_tile_cnt.p, ix->cplace_dev.p, B, ix->lkb_place.p, ix->lkb_est.p, (int64_t *)nullptr,
                            (int64_t *)nullptr);

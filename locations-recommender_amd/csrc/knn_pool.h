@@ -9,7 +9,8 @@
 //
 //   wave w        the w-th tile (kLkbQt distinct requests) of every member that still has one.  A query's column does
 //                 not depend on its tile-mates, so how a member's requests are cut into tiles is free
-//   table         one KpRow per member of the wave (what lkb_scan_tile and lkb_aggregate_tile pass by value), one copy
+//   table         one KpRow per member of the wave: the tile as lkb_describe_tile (knn_large.hip) describes it to the
+//                 member's own launches, and the aggregation's arguments; one copy
 //   launches      ONE per kernel and wave, the member = a block index:
 //                   lkb_fill_pool               (element blocks of the wave's longest query, 2 families x kLkbQt, members)
 //                   lkb_scan_pool               (row blocks of the largest member, members); a block past its member's
@@ -24,7 +25,8 @@
 // The bodies are knn_large.hip's (lkb_fill_body, lkb_scan_body, lk_*_body) on each member's own workspaces (lkb_S, the
 // dense tables, the segment and place sums): the order of operations per (member, query) is that of the member's own
 // batch, so request i's rows are bit for bit what locrec_knn_recommend_batch returns for it.  A member without a rated
-// place (or without segments) joins no wave: its requests have no rows.
+// place (or without segments) joins no wave: its requests have no rows.  The host arithmetic is the per-index batch's
+// too (knn_pool_plan.h: waves, a tile's bases), and so is the growth of the row buffer (lkb_grow_rows).
 //
 // hipcc -Rpass-analysis=kernel-resource-usage, gfx950: VGPRs / LDS bytes (static) / scratch.  The kernels of
 // knn_large.hip have the figures they had before their bodies became functions; the pool's kernels have the same.
@@ -189,7 +191,7 @@ int32_t kp_run(KnnPoolShared *ws, hipStream_t s, const std::vector<KnnPoolBatch>
         if (np == 0 || ix->lk_nsegs <= 0 || b.n == 0) continue;  // nobody rated anything: no rows
         live.push_back({&b, tiles});
         tc_words += (size_t)tiles * kLkbQt;
-        nwaves = std::max<int64_t>(nwaves, (b.n + kLkbQt - 1) / kLkbQt);
+        nwaves = std::max(nwaves, knn_waves_of(b.n));
     }
     if (live.empty()) return LOCREC_OK;
     const size_t nl = live.size();
@@ -213,7 +215,7 @@ int32_t kp_run(KnnPoolShared *ws, hipStream_t s, const std::vector<KnnPoolBatch>
     for (int64_t w = 0; w < nwaves; ++w) {
         wave.clear();
         for (const KpLive &m : live)
-            if (m.b->n > w * kLkbQt) wave.push_back(&m);
+            if (knn_wave_tile(m.b->n, w) > 0) wave.push_back(&m);
         const size_t nw = wave.size();
         int max_nnz = 1, max_tiles = 1;
         int64_t max_rows = 1, max_segs = 1, max_np = 1;
@@ -221,30 +223,13 @@ int32_t kp_run(KnnPoolShared *ws, hipStream_t s, const std::vector<KnnPoolBatch>
         for (size_t i = 0; i < nw; ++i) {
             const KpLive &m = *wave[i];
             locrec_knn_index *ix = m.b->ix;
-            const int nt = (int)std::min<int64_t>(kLkbQt, m.b->n - w * kLkbQt);
+            const int nt = knn_wave_tile(m.b->n, w);
             KpRow r{};
-            bool invalid[kLkbQt];
-            lkt_tile_rows(ix, m.b->rows + w * kLkbQt, nt, 0, r.P.qrow, invalid);
-            for (int t = 0; t < kLkbQt; ++t) {
-                const int32_t q = r.fp.qrow[t] = r.fc.qrow[t] = r.P.qrow[t];
-                if (q >= 0) max_nnz = std::max(max_nnz, std::max(ix->fp.nnz[(size_t)q], ix->fc.nnz[(size_t)q]));
-            }
-            // (as lkb_scan_tile sets a tile up)
-            r.fp.ptr = ix->fp.csr_ptr.p; r.fp.idx = ix->fp.csr_idx.p; r.fp.val = ix->fp.csr_val.p; r.fp.qd = ix->lkb_qd_p.p;
-            lkb_bitmap_of(ix, &r.fp.bits, &r.fp.bit_mask);
-            r.fc.ptr = ix->fc.csr_ptr.p; r.fc.idx = ix->fc.csr_idx.p; r.fc.val = ix->fc.csr_val.p; r.fc.qd = ix->lkb_qd_c.p;
-            r.P.bits = r.fp.bits;
-            r.P.bit_mask = r.fp.bit_mask;
-            r.P.p_ptr = ix->fp.csr_ptr.p; r.P.p_idx = ix->fp.csr_idx.p; r.P.p_val = ix->fp.csr_val.p;
-            r.P.c_ptr = ix->fc.csr_ptr.p; r.P.c_idx = ix->fc.csr_idx.p; r.P.c_val = ix->fc.csr_val.p;
-            r.P.norm_p = ix->fp.norm.p; r.P.norm_c = ix->fc.norm.p;
-            r.P.qd_p = ix->lkb_qd_p.p; r.P.qd_c = ix->lkb_qd_c.p;
-            r.P.nrows = (int32_t)ix->n;
-            r.P.pw = pw; r.P.cw = cw;
-            r.P.S = ix->lkb_S.p;
-            r.P.transposed = 0;
-            r.cand = r.P.cand = ws->cand.p + i * kLkbQt;
-            // (as enqueue_aggregation<kLkbQt, 2> and lkb_aggregate_tile pass them)
+            int maxp = 1, maxc = 1;
+            lkb_describe_tile(ix, m.b->rows + w * kLkbQt, nt, pw, cw, false, ws->cand.p + i * kLkbQt, r.fp, r.fc, r.P, maxp, maxc);
+            max_nnz = std::max(max_nnz, std::max(maxp, maxc));
+            r.cand = r.P.cand;
+            // the aggregation's arguments (enqueue_aggregation<kLkbQt, 2>'s, and the finish kernels')
             r.seg_begin = ix->lk_seg_begin.p; r.seg_end = ix->lk_seg_end.p;
             r.cp_row = ix->cp_row.p; r.cp_rating = ix->cp_rating.p;
             r.seg_ws = ix->lkb_seg_ws.p; r.seg_ss = ix->lkb_seg_ss.p;
@@ -282,36 +267,20 @@ int32_t kp_run(KnnPoolShared *ws, hipStream_t s, const std::vector<KnnPoolBatch>
         tc_used = 0;
         for (size_t i = 0; i < nw; ++i) {
             const KpLive &m = *wave[i];
-            const int nt = (int)std::min<int64_t>(kLkbQt, m.b->n - w * kLkbQt);
-            LkBases<kLkbQt> B{};
-            for (int t = 0; t < kLkbQt; ++t) {
-                B.base[t] = -1;
-                if (t >= nt) continue;
-                int64_t c = 0;
-                for (int k = 0; k < m.tiles; ++k) c += htc[tc_used + (size_t)t * m.tiles + k];
+            const int nt = knn_wave_tile(m.b->n, w);
+            int64_t len[kLkbQt];
+            total = knn_tile_bases(htc + tc_used, m.tiles, nt, htab[i].P.qrow, total, hbases[i].base, len);
+            for (int t = 0; t < nt; ++t) {
                 const int64_t u = m.b->first + w * kLkbQt + t;
-                B.base[t] = row_base[u] = total;
-                row_len[u] = c;
-                total += c;
+                row_base[u] = hbases[i].base[t];
+                row_len[u] = len[t];
             }
-            hbases[i] = B;
             tc_used += (size_t)m.tiles * kLkbQt;
         }
-        // grow-only output with headroom: the rows of the waves emitted so far survive a growth (as lkb_place's do)
+        // grow-only output with headroom: the rows of the waves emitted so far survive a growth
         if ((size_t)total > ws->place.n || !ws->place.p) {
-            DevBuf<int64_t> np_buf;
-            DevBuf<double> ne_buf;
-            const size_t want = (size_t)total + (size_t)total / 2 + 1024;
-            LOCREC_TRY(np_buf.alloc(want));
-            LOCREC_TRY(ne_buf.alloc(want));
-            if (keep > 0) {
-                LOCREC_HIP_TRY(hipMemcpyAsync(np_buf.p, ws->place.p, (size_t)keep * 8, hipMemcpyDeviceToDevice, s));
-                LOCREC_HIP_TRY(hipMemcpyAsync(ne_buf.p, ws->est.p, (size_t)keep * 8, hipMemcpyDeviceToDevice, s));
-                LOCREC_HIP_TRY(hipStreamSynchronize(s));
-                ++st.host_syncs;
-            }
-            std::swap(ws->place.p, np_buf.p); std::swap(ws->place.n, np_buf.n);
-            std::swap(ws->est.p, ne_buf.p); std::swap(ws->est.n, ne_buf.n);
+            LOCREC_TRY(lkb_grow_rows(ws->place, ws->est, total, keep, s));
+            if (keep > 0) ++st.host_syncs;
         }
         LOCREC_HIP_TRY(hipMemcpyAsync(ws->tab.p + off_bases, hbases, nw * sizeof(LkBases<kLkbQt>), hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(lk_finish_emit_pool, gfin, dim3(256), 0, s, dtab, dbases, ws->place.p, ws->est.p);

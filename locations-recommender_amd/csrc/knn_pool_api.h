@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "knn_index.h"
+#include "knn_pool_plan.h"
 
 namespace locrec {
 

@@ -15,6 +15,16 @@
 
 namespace {
 
+// the ranked calls' own arguments (the pool's entry checks them before any device work)
+int32_t knn_rank_check_args(int64_t n_places, const int64_t *place_ids, const int64_t *place_region_ids, const int64_t *targets,
+                            int64_t N, const int64_t *out_ids, const double *out_scores, const int64_t *out_counts)
+{
+    if (n_places < 0 || n_places >= ((int64_t)1 << 31)) return fail(LOCREC_E_INVALID_ARG, "place count out of range [0, 2^31)");
+    if (!out_counts || !targets || (N > 0 && (!out_ids || !out_scores)) || (n_places > 0 && (!place_ids || !place_region_ids)))
+        return fail(LOCREC_E_INVALID_ARG, "NULL argument");
+    return LOCREC_OK;
+}
+
 // segment c of the result = the resident rows of processing slot slots[c], ranked for targets[c] (host arrays).
 // known_len: the segments' row counts where the caller has them from a fetch that already settled the rows (the batch
 // form: locrec_knn_recommend_batch sizes its result through locrec_knn_fetch_recommend); NULL: that fetch is made here.
@@ -24,9 +34,7 @@ int32_t knn_rank_resident(locrec_knn_index *ix, const std::vector<int64_t> &slot
 {
     const int64_t nseg = (int64_t)slots.size(), nq = ix->last_nq;
     const int64_t N = std::max<int64_t>(0, max_recommendations);
-    if (n_places < 0 || n_places >= ((int64_t)1 << 31)) return fail(LOCREC_E_INVALID_ARG, "place count out of range [0, 2^31)");
-    if (!out_counts || !targets || (N > 0 && (!out_ids || !out_scores)) || (n_places > 0 && (!place_ids || !place_region_ids)))
-        return fail(LOCREC_E_INVALID_ARG, "NULL argument");
+    LOCREC_TRY(knn_rank_check_args(n_places, place_ids, place_region_ids, targets, N, out_ids, out_scores, out_counts));
     std::vector<int64_t> off((size_t)nq + 1, 0);
     if (!known_len) {
         int64_t cap = 0;
@@ -62,30 +70,18 @@ int32_t knn_rank_resident(locrec_knn_index *ix, const std::vector<int64_t> &slot
     if (nseg == 0) return LOCREC_OK;
     // one allocation for the call's inputs and one for its outputs (every hipMalloc / hipFree costs a wait)
     DevBuf<int64_t> d_in, d_out;
-    LOCREC_TRY(d_in.alloc(2 * (size_t)n_places + 3 * (size_t)nseg));
-    LOCREC_TRY(d_out.alloc(2 * (size_t)(nseg * N) + (size_t)nseg));
-    struct I64 {
-        int64_t *p;
-    } d_pid = {d_in.p}, d_preg = {d_in.p + n_places}, d_tgt = {d_in.p + 2 * n_places}, d_b = {d_tgt.p + nseg},
-      d_l = {d_b.p + nseg}, d_oid = {d_out.p}, d_ocnt = {d_out.p + 2 * nseg * N};
-    struct {
-        double *p;
-    } d_osc = {reinterpret_cast<double *>(d_out.p + nseg * N)};
+    LOCREC_TRY(d_in.alloc(RankIo::in_words(n_places, nseg)));
+    LOCREC_TRY(d_out.alloc(RankIo::out_words(nseg, N)));
+    const RankIo io(d_in.p, d_out.p, n_places, nseg, N);
     if (n_places > 0) {
-        LOCREC_HIP_TRY(hipMemcpyAsync(d_pid.p, place_ids, (size_t)n_places * 8, hipMemcpyHostToDevice, s));
-        LOCREC_HIP_TRY(hipMemcpyAsync(d_preg.p, place_region_ids, (size_t)n_places * 8, hipMemcpyHostToDevice, s));
+        LOCREC_HIP_TRY(hipMemcpyAsync(io.pid, place_ids, (size_t)n_places * 8, hipMemcpyHostToDevice, s));
+        LOCREC_HIP_TRY(hipMemcpyAsync(io.preg, place_region_ids, (size_t)n_places * 8, hipMemcpyHostToDevice, s));
     }
-    LOCREC_HIP_TRY(hipMemcpyAsync(d_tgt.p, targets, (size_t)nseg * 8, hipMemcpyHostToDevice, s));
-    LOCREC_HIP_TRY(hipMemcpyAsync(d_b.p, hb.data(), (size_t)nseg * 8, hipMemcpyHostToDevice, s));
-    LOCREC_HIP_TRY(hipMemcpyAsync(d_l.p, hl.data(), (size_t)nseg * 8, hipMemcpyHostToDevice, s));
-    LOCREC_TRY(rank_segments_device(nseg, d_b.p, d_l.p, lkb ? ix->lkb_place.p : ix->agg_place.p, lkb ? ix->lkb_est.p : ix->agg_est.p,
-                                    n_places, d_pid.p, d_preg.p, d_tgt.p, N, d_oid.p, d_osc.p, d_ocnt.p, nullptr, 0, s));
-    if (N > 0) {
-        LOCREC_HIP_TRY(hipMemcpyAsync(out_ids, d_oid.p, (size_t)(nseg * N) * 8, hipMemcpyDeviceToHost, s));
-        LOCREC_HIP_TRY(hipMemcpyAsync(out_scores, d_osc.p, (size_t)(nseg * N) * 8, hipMemcpyDeviceToHost, s));
-    }
-    LOCREC_HIP_TRY(hipMemcpyAsync(out_counts, d_ocnt.p, (size_t)nseg * 8, hipMemcpyDeviceToHost, s));
-    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    LOCREC_HIP_TRY(hipMemcpyAsync(io.tgt, targets, (size_t)nseg * 8, hipMemcpyHostToDevice, s));
+    LOCREC_HIP_TRY(hipMemcpyAsync(io.base, hb.data(), (size_t)nseg * 8, hipMemcpyHostToDevice, s));
+    LOCREC_HIP_TRY(hipMemcpyAsync(io.len, hl.data(), (size_t)nseg * 8, hipMemcpyHostToDevice, s));
+    LOCREC_TRY(io.rank(lkb ? ix->lkb_place.p : ix->agg_place.p, lkb ? ix->lkb_est.p : ix->agg_est.p, 0, s));
+    LOCREC_TRY(io.read_back(out_ids, out_scores, out_counts, s));
     RankBatchStats total = rank_batch_stats();
     ++total.host_syncs;
     if (!hosted.empty()) {
@@ -111,32 +107,18 @@ int32_t knn_rank_resident(locrec_knn_index *ix, const std::vector<int64_t> &slot
             tl[(size_t)i] = slot_len[(size_t)q];
             tt[(size_t)i] = targets[hosted[(size_t)i]];
         }
-        DevBuf<int64_t> d_rp, d_tb, d_tl, d_tt, d_hid, d_hcnt;
-        DevBuf<double> d_re, d_hsc;
+        DevBuf<int64_t> d_rp, d_hin, d_hout;
+        DevBuf<double> d_re;
         LOCREC_TRY(d_rp.upload(rp, s));
         LOCREC_TRY(d_re.upload(re, s));
-        LOCREC_TRY(d_tb.upload(tb, s));
-        LOCREC_TRY(d_tl.upload(tl, s));
-        LOCREC_TRY(d_tt.upload(tt, s));
-        LOCREC_TRY(d_hid.alloc((size_t)(nh * N)));
-        LOCREC_TRY(d_hsc.alloc((size_t)(nh * N)));
-        LOCREC_TRY(d_hcnt.alloc((size_t)nh));
-        LOCREC_TRY(rank_segments_device(nh, d_tb.p, d_tl.p, d_rp.p, d_re.p, n_places, d_pid.p, d_preg.p, d_tt.p, N, d_hid.p,
-                                        d_hsc.p, d_hcnt.p, nullptr, nh, s));
-        std::vector<int64_t> hid((size_t)(nh * N)), hcnt((size_t)nh);
-        std::vector<double> hsc((size_t)(nh * N));
-        if (N > 0) {
-            LOCREC_HIP_TRY(hipMemcpyAsync(hid.data(), d_hid.p, (size_t)(nh * N) * 8, hipMemcpyDeviceToHost, s));
-            LOCREC_HIP_TRY(hipMemcpyAsync(hsc.data(), d_hsc.p, (size_t)(nh * N) * 8, hipMemcpyDeviceToHost, s));
-        }
-        LOCREC_HIP_TRY(hipMemcpyAsync(hcnt.data(), d_hcnt.p, (size_t)nh * 8, hipMemcpyDeviceToHost, s));
-        LOCREC_HIP_TRY(hipStreamSynchronize(s));
-        for (int64_t i = 0; i < nh; ++i) {
-            const int64_t c = hosted[(size_t)i];
-            std::copy(hid.begin() + i * N, hid.begin() + (i + 1) * N, out_ids + c * N);
-            std::copy(hsc.begin() + i * N, hsc.begin() + (i + 1) * N, out_scores + c * N);
-            out_counts[c] = hcnt[(size_t)i];
-        }
+        LOCREC_TRY(d_hin.alloc(RankIo::in_words(0, nh)));
+        LOCREC_TRY(d_hout.alloc(RankIo::out_words(nh, N)));
+        const RankIo hio(d_hin.p, d_hout.p, n_places, nh, N, &io);  // (the places table is already there)
+        LOCREC_HIP_TRY(hipMemcpyAsync(hio.tgt, tt.data(), (size_t)nh * 8, hipMemcpyHostToDevice, s));
+        LOCREC_HIP_TRY(hipMemcpyAsync(hio.base, tb.data(), (size_t)nh * 8, hipMemcpyHostToDevice, s));
+        LOCREC_HIP_TRY(hipMemcpyAsync(hio.len, tl.data(), (size_t)nh * 8, hipMemcpyHostToDevice, s));
+        LOCREC_TRY(hio.rank(d_rp.p, d_re.p, nh, s));
+        LOCREC_TRY(hio.read_back_to(hosted, out_ids, out_scores, out_counts, s));
         const RankBatchStats &h = rank_batch_stats();
         // (the overflow queries were empty one-block segments of the first call: counted where their rows were ranked)
         if (!h.sorted) {

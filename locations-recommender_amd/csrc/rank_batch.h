@@ -3,6 +3,9 @@
 // and the ranked KNN batches call it; every pointer is a device pointer of the current device.
 #pragma once
 
+#include <algorithm>
+#include <vector>
+
 #include "common.h"
 
 namespace locrec {
@@ -29,5 +32,51 @@ int32_t rank_segments_device(int64_t n_segments, const int64_t *seg_begin, const
                              const int64_t *place_region_ids, const int64_t *target_region_ids, int64_t max_recommendations,
                              int64_t *out_ids, double *out_scores, int64_t *out_counts,
                              const unsigned long long *invalid_flag, int64_t host_assembled, hipStream_t s);
+
+// One ranker call's device arrays, carved out of one input and one output allocation of 8-byte words:
+//   in   [place ids | place regions | targets | bases | lengths]   (without the places table when it is places_of's)
+//   out  [ids | scores | counts]
+// The caller fills `in` (in one copy or several) and brings the rows; the ranking, its read-back and the scatter are here.
+struct RankIo {
+    int64_t n_places, nseg, N;
+    int64_t *pid, *preg, *tgt, *base, *len, *oid, *ocnt;
+    double *osc;
+    static size_t in_words(int64_t n_places, int64_t nseg) { return 2 * (size_t)n_places + 3 * (size_t)nseg; }
+    static size_t out_words(int64_t nseg, int64_t N) { return 2 * (size_t)(nseg * N) + (size_t)nseg; }
+    RankIo(int64_t *in, int64_t *out, int64_t n_places_, int64_t nseg_, int64_t N_, const RankIo *places_of = nullptr)
+        : n_places(n_places_), nseg(nseg_), N(N_), pid(places_of ? places_of->pid : in), preg(places_of ? places_of->preg : in + n_places),
+          tgt(places_of ? in : in + 2 * n_places), base(tgt + nseg), len(base + nseg), oid(out), ocnt(out + 2 * nseg * N),
+          osc(reinterpret_cast<double *>(out + nseg * N))
+    {
+    }
+    int32_t rank(const int64_t *ids, const double *scores, int64_t host_assembled, hipStream_t s) const
+    {
+        return rank_segments_device(nseg, base, len, ids, scores, n_places, pid, preg, tgt, N, oid, osc, ocnt, nullptr, host_assembled, s);
+    }
+    // nseg x N ids and scores and nseg counts to host arrays of that shape, then the call's one wait
+    int32_t read_back(int64_t *ids, double *scores, int64_t *counts, hipStream_t s) const
+    {
+        if (N > 0) {
+            LOCREC_HIP_TRY(hipMemcpyAsync(ids, oid, (size_t)(nseg * N) * 8, hipMemcpyDeviceToHost, s));
+            LOCREC_HIP_TRY(hipMemcpyAsync(scores, osc, (size_t)(nseg * N) * 8, hipMemcpyDeviceToHost, s));
+        }
+        LOCREC_HIP_TRY(hipMemcpyAsync(counts, ocnt, (size_t)nseg * 8, hipMemcpyDeviceToHost, s));
+        LOCREC_HIP_TRY(hipStreamSynchronize(s));
+        return LOCREC_OK;
+    }
+    // the same, segment c's N rows and count going to position to[c] of the caller's arrays
+    int32_t read_back_to(const std::vector<int64_t> &to, int64_t *ids, double *scores, int64_t *counts, hipStream_t s) const
+    {
+        std::vector<int64_t> hid((size_t)(nseg * N)), hcnt((size_t)nseg);
+        std::vector<double> hsc((size_t)(nseg * N));
+        LOCREC_TRY(read_back(hid.data(), hsc.data(), hcnt.data(), s));
+        for (int64_t c = 0; c < nseg; ++c) {
+            std::copy(hid.begin() + c * N, hid.begin() + (c + 1) * N, ids + to[(size_t)c] * N);
+            std::copy(hsc.begin() + c * N, hsc.begin() + (c + 1) * N, scores + to[(size_t)c] * N);
+            counts[to[(size_t)c]] = hcnt[(size_t)c];
+        }
+        return LOCREC_OK;
+    }
+};
 
 }  // namespace locrec

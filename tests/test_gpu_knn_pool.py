@@ -288,6 +288,42 @@ def test_a_repeated_call_allocates_nothing(pkg, members):
     assert all(a.tobytes() == b.tobytes() for a, b in zip(first, again))
 
 
+def test_the_row_buffer_grows_mid_call_and_keeps_its_rows(pkg, members):
+    """33 distinct persons of dataset 2 at K = 2,000,000 on FRESH handles - a KnnIndex, and a KnnPool of another: three
+    tiles; the first sizes the empty row buffer, the second outgrows it while the first tile's rows are in it.  Both
+    paths process a member's queries in row order, and an index's rows ascend by (place count, category count): the
+    persons are given in that order with distinct keys, so the returned offsets are the running totals the growth rule
+    saw: buffer of off[16] + off[16] // 2 + 1024 rows after tile 0, off[32] rows wanted after tile 1."""
+    ds, ixs, _ = members
+    d = ds[2]
+    n_p, n_c = np.diff(d["p_rowptr"]), np.diff(d["c_rowptr"])
+    first_of_key = {}
+    for r in valid_rows(d):
+        first_of_key.setdefault((int(n_p[r]), int(n_c[r])), int(r))
+    rows = [first_of_key[key] for key in sorted(first_of_key)[:33]]
+    assert len(rows) == 33
+    pid = d["person_ids"][rows]
+    k = 2_000_000
+    alone_ix, pooled_ix = make_index(pkg, d), make_index(pkg, d)
+    pool = pkg.KnnPool([pooled_ix])
+    try:
+        got = {"index": alone_ix.recommend_batch(pid, PW, CW, k),
+               "pool": pool.recommend_batch(np.zeros(33, np.int32), pid, PW, CW, k)}
+        assert pool.stats()["waves"] == 3
+    finally:
+        pool.close()
+        alone_ix.close()
+        pooled_ix.close()
+    for name, (off, p, e) in got.items():
+        assert off[16] > 0 and off[32] > off[16] + off[16] // 2 + 1024, (name, off[16], off[32])   # a growth with rows to keep
+        for i in (0, 15, 16, 31, 32):                          # either side of each tile boundary
+            wp, we = ixs[2].recommend(int(pid[i]), PW, CW, k)
+            assert np.array_equal(p[off[i]:off[i + 1]], wp), (name, i)
+            assert np.array_equal(bits(e[off[i]:off[i + 1]]), bits(we)), (name, i)
+    assert all(np.array_equal(a, b) for a, b in zip(got["index"][:2], got["pool"][:2]))
+    assert np.array_equal(bits(got["index"][2]), bits(got["pool"][2]))
+
+
 def raw_call(pool, gi, pid, pw, cw, k, room):
     """locrec_knn_pool_recommend_batch on sentinel-filled outputs -> (status, offsets, places, ratings, capacity, bad)."""
     from locations_recommender_amd import _lib as L
