@@ -57,8 +57,6 @@ thread_local DedupStats g_dedup_stats;
 
 enum { kPhaseGrid = 0, kPhaseLev = 1, kPhaseCompact = 2, kPhaseEnd = -1 };
 
-#define DD_LAUNCHED() LOCREC_HIP_TRY(hipGetLastError())
-
 // ---- names ------------------------------------------------------------------------------------------------------------
 
 // CSR offsets must start at or above 0 and never decrease: every kernel below trusts them as array bounds
@@ -82,8 +80,7 @@ int32_t bind_names(Names &N, int64_t n, const int64_t *offsets, const uint16_t *
     DevBuf<uint32_t> bad;
     LOCREC_TRY(bad.alloc(1));
     LOCREC_HIP_TRY(hipMemsetAsync(bad.p, 0, 4, s));
-    hipLaunchKernelGGL(dd_check_offsets, grid_for(n + 1), dim3(256), 0, s, n, N.off.p, bad.p);
-    DD_LAUNCHED();
+    LOCREC_LAUNCH(dd_check_offsets, grid_for(n + 1), dim3(256), 0, s, n, N.off.p, bad.p);
     uint32_t is_bad = 0;
     int64_t total = 0;
     LOCREC_HIP_TRY(hipMemcpyAsync(&is_bad, bad.p, 4, hipMemcpyDeviceToHost, s));
@@ -293,12 +290,11 @@ int32_t lev_pairs(int64_t m, const uint32_t *pa, const uint32_t *pb, const int64
     if (m == 0) return LOCREC_OK;
     if (k >= 0 && !full_dp && k <= 15) {
         if (k <= 3)
-            hipLaunchKernelGGL((dd_lev_band<3>), grid_for(m), dim3(256), 0, s, m, pa, pb, a_off, a_units, b_off, b_units, k, out);
+            LOCREC_LAUNCH((dd_lev_band<3>), grid_for(m), dim3(256), 0, s, m, pa, pb, a_off, a_units, b_off, b_units, k, out);
         else if (k <= 7)
-            hipLaunchKernelGGL((dd_lev_band<7>), grid_for(m), dim3(256), 0, s, m, pa, pb, a_off, a_units, b_off, b_units, k, out);
+            LOCREC_LAUNCH((dd_lev_band<7>), grid_for(m), dim3(256), 0, s, m, pa, pb, a_off, a_units, b_off, b_units, k, out);
         else
-            hipLaunchKernelGGL((dd_lev_band<15>), grid_for(m), dim3(256), 0, s, m, pa, pb, a_off, a_units, b_off, b_units, k, out);
-        DD_LAUNCHED();
+            LOCREC_LAUNCH((dd_lev_band<15>), grid_for(m), dim3(256), 0, s, m, pa, pb, a_off, a_units, b_off, b_units, k, out);
         return LOCREC_OK;
     }
     const int32_t limit = full_dp ? -1 : k;
@@ -307,20 +303,17 @@ int32_t lev_pairs(int64_t m, const uint32_t *pa, const uint32_t *pb, const int64
     LOCREC_TRY(plan.alloc(1));
     LOCREC_TRY(long_list.alloc((size_t)m));
     LOCREC_HIP_TRY(hipMemsetAsync(plan.p, 0, sizeof(LevPlan), s));
-    hipLaunchKernelGGL(dd_lev_plan, grid_for(m), dim3(256), 0, s, m, pa, pb, a_off, b_off, plan.p, long_list.p);
-    DD_LAUNCHED();
+    LOCREC_LAUNCH(dd_lev_plan, grid_for(m), dim3(256), 0, s, m, pa, pb, a_off, b_off, plan.p, long_list.p);
     LevPlan lp;
-    LOCREC_HIP_TRY(hipMemcpyAsync(&lp, plan.p, sizeof lp, hipMemcpyDeviceToHost, s));
-    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    LOCREC_READ_BACK(lp, plan.p, s);
     if ((int64_t)lp.long_pairs < m) {
         const int32_t cells = (int32_t)lp.max_short + 1;
         const size_t lds = (size_t)cells * 64 * sizeof(uint16_t);
         if (lds > 64 * 1024)
             LOCREC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(dd_lev_lds), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                (int)(kLdsCells * 64 * sizeof(uint16_t))));
-        hipLaunchKernelGGL(dd_lev_lds, grid_for(m, 64), dim3(64), lds, s, m, pa, pb, a_off, a_units, b_off, b_units, limit, k, cells,
-                           out);
-        DD_LAUNCHED();
+        LOCREC_LAUNCH(dd_lev_lds, grid_for(m, 64), dim3(64), lds, s, m, pa, pb, a_off, a_units, b_off, b_units, limit, k, cells,
+                      out);
     }
     if (lp.long_pairs) {
         const int64_t row_bytes = (int64_t)lp.long_cells * 4;
@@ -329,9 +322,8 @@ int32_t lev_pairs(int64_t m, const uint32_t *pa, const uint32_t *pb, const int64
         LOCREC_TRY(scratch.alloc((size_t)(per_launch * (int64_t)lp.long_cells)));
         for (int64_t first = 0; first < (int64_t)lp.long_pairs; first += per_launch) {
             const int64_t count = std::min<int64_t>(per_launch, (int64_t)lp.long_pairs - first);
-            hipLaunchKernelGGL(dd_lev_global, grid_for(count, 64), dim3(64), 0, s, first, count, long_list.p, pa, pb, a_off, a_units,
-                               b_off, b_units, limit, k, scratch.p, out);
-            DD_LAUNCHED();
+            LOCREC_LAUNCH(dd_lev_global, grid_for(count, 64), dim3(64), 0, s, first, count, long_list.p, pa, pb, a_off, a_units,
+                          b_off, b_units, limit, k, scratch.p, out);
         }
         LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (scratch is released on return)
     }
@@ -551,14 +543,12 @@ try {
     LOCREC_TRY(err.alloc(1));
     LOCREC_HIP_TRY(hipMemsetAsync(has_place.p, 0, (size_t)nr * 4, s));
     LOCREC_HIP_TRY(hipMemsetAsync(err.p, 0xFF, sizeof(LocationError), s));
-    hipLaunchKernelGGL(check_side_a, grid_for(n_places), dim3(256), 0, s, n_places, (const int64_t *)nullptr, (int64_t)0, plat.p,
-                       plon.p, pr.p, regions.p, nr, has_place.p, err.p);
-    hipLaunchKernelGGL(check_side_b, grid_for(n_confirmed), dim3(256), 0, s, n_confirmed, clat.p, clon.p, cr.p, regions.p, nr,
-                       has_place.p, err.p);
-    DD_LAUNCHED();
+    LOCREC_LAUNCH(check_side_a, grid_for(n_places), dim3(256), 0, s, n_places, (const int64_t *)nullptr, (int64_t)0, plat.p,
+                  plon.p, pr.p, regions.p, nr, has_place.p, err.p);
+    LOCREC_LAUNCH(check_side_b, grid_for(n_confirmed), dim3(256), 0, s, n_confirmed, clat.p, clon.p, cr.p, regions.p, nr,
+                  has_place.p, err.p);
     LocationError le;
-    LOCREC_HIP_TRY(hipMemcpyAsync(&le, err.p, sizeof le, hipMemcpyDeviceToHost, s));
-    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    LOCREC_READ_BACK(le, err.p, s);
     LOCREC_TRY(location_error(le, plat.p, plon.p, "place", n_places, clat.p, clon.p, "confirmed place", inout_count));
 
     DevBuf<uint64_t> k0, k1;
@@ -571,15 +561,14 @@ try {
         DevBuf<uint32_t> rk0, rk1;
         LOCREC_TRY(rk0.alloc((size_t)n_confirmed));
         LOCREC_TRY(rk1.alloc((size_t)n_confirmed));
-        hipLaunchKernelGGL(iota_keys, grid_for(n_confirmed), dim3(256), 0, s, n_confirmed, ci.p, k0.p, r0.p);
+        LOCREC_LAUNCH(iota_keys, grid_for(n_confirmed), dim3(256), 0, s, n_confirmed, ci.p, k0.p, r0.p);
         LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, k0.p, k1.p, r0.p, r1.p, (int)n_confirmed, 0, 64, s));
-        hipLaunchKernelGGL(dd_region_rank_keys, grid_for(n_confirmed), dim3(256), 0, s, n_confirmed, cr.p, r1.p, regions.p, nr,
-                           rk0.p);
+        LOCREC_LAUNCH(dd_region_rank_keys, grid_for(n_confirmed), dim3(256), 0, s, n_confirmed, cr.p, r1.p, regions.p, nr,
+                      rk0.p);
         LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, rk0.p, rk1.p, r1.p, r0.p, (int)n_confirmed, 0, 24, s));
-        hipLaunchKernelGGL(gather_id_keys, grid_for(n_confirmed), dim3(256), 0, s, n_confirmed, ci.p, r0.p, k0.p);
-        hipLaunchKernelGGL(dd_partners, grid_for(n_places), dim3(256), 0, s, n_places, pi.p, pr.p, regions.p, nr, n_confirmed,
-                           rk1.p, k0.p, ons.p);
-        DD_LAUNCHED();
+        LOCREC_LAUNCH(gather_id_keys, grid_for(n_confirmed), dim3(256), 0, s, n_confirmed, ci.p, r0.p, k0.p);
+        LOCREC_LAUNCH(dd_partners, grid_for(n_places), dim3(256), 0, s, n_places, pi.p, pr.p, regions.p, nr, n_confirmed,
+                      rk1.p, k0.p, ons.p);
         LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (rk0 / rk1 are released here)
     }
 
@@ -587,17 +576,16 @@ try {
     int64_t total_same = 0;
     if (max_meters >= 0.0 && k >= 0) {
         const Grid g = make_grid(max_meters);
-        hipLaunchKernelGGL(pr_place_keys, grid_for(n_confirmed), dim3(256), 0, s, n_confirmed, clat.p, clon.p, cr.p, regions.p, nr,
-                           g, k0.p, r0.p);
+        LOCREC_LAUNCH(pr_place_keys, grid_for(n_confirmed), dim3(256), 0, s, n_confirmed, clat.p, clon.p, cr.p, regions.p, nr,
+                      g, k0.p, r0.p);
         LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, k0.p, k1.p, r0.p, r1.p, (int)n_confirmed, 0, 64, s));
 
         DevBuf<unsigned long long> counts, offsets;
         LOCREC_TRY(counts.alloc((size_t)n_places));
         LOCREC_TRY(offsets.alloc((size_t)n_places));
-        hipLaunchKernelGGL((dd_walk<false>), grid_for(n_places), dim3(256), 0, s, (int64_t)0, n_places, pi.p, plat.p, plon.p, pr.p,
-                           regions.p, nr, g, max_meters, n_confirmed, k1.p, r1.p, ci.p, clat.p, clon.p, counts.p, nullptr, 0ull,
-                           nullptr, nullptr);
-        DD_LAUNCHED();
+        LOCREC_LAUNCH((dd_walk<false>), grid_for(n_places), dim3(256), 0, s, (int64_t)0, n_places, pi.p, plat.p, plon.p, pr.p,
+                      regions.p, nr, g, max_meters, n_confirmed, k1.p, r1.p, ci.p, clat.p, clon.p, counts.p, nullptr, 0ull,
+                      nullptr, nullptr);
         LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, counts.p, offsets.p, (int)n_places, s));
         unsigned long long last_off = 0, last_cnt = 0;
         LOCREC_HIP_TRY(hipMemcpyAsync(&last_off, offsets.p + (n_places - 1), 8, hipMemcpyDeviceToHost, s));
@@ -620,7 +608,7 @@ try {
         LOCREC_TRY(chunk_dev.alloc(1));
         for (int64_t begin = 0; total_cand > 0 && begin < n_places;) {
             LOCREC_TRY(clock.mark(kPhaseGrid));
-            hipLaunchKernelGGL(dd_chunk_end, dim3(1), dim3(64), 0, s, n_places, offsets.p, total_cand, begin, budget, chunk_dev.p);
+            LOCREC_LAUNCH(dd_chunk_end, dim3(1), dim3(64), 0, s, n_places, offsets.p, total_cand, begin, budget, chunk_dev.p);
             ChunkEnd ce;
             unsigned long long base = 0;
             LOCREC_HIP_TRY(hipMemcpyAsync(&ce, chunk_dev.p, sizeof ce, hipMemcpyDeviceToHost, s));
@@ -635,21 +623,19 @@ try {
                 LOCREC_TRY(flags.reserve((size_t)m));
                 LOCREC_TRY(pos.reserve((size_t)m));
                 LOCREC_TRY(dist.reserve((size_t)m));
-                hipLaunchKernelGGL((dd_walk<true>), grid_for(end - begin), dim3(256), 0, s, begin, end, pi.p, plat.p, plon.p, pr.p,
-                                   regions.p, nr, g, max_meters, n_confirmed, k1.p, r1.p, ci.p, clat.p, clon.p, nullptr, offsets.p,
-                                   base, cand_place.p, cand_conf.p);
-                DD_LAUNCHED();
+                LOCREC_LAUNCH((dd_walk<true>), grid_for(end - begin), dim3(256), 0, s, begin, end, pi.p, plat.p, plon.p, pr.p,
+                              regions.p, nr, g, max_meters, n_confirmed, k1.p, r1.p, ci.p, clat.p, clon.p, nullptr, offsets.p,
+                              base, cand_place.p, cand_conf.p);
                 LOCREC_TRY(clock.mark(kPhaseLev));
                 LOCREC_TRY(lev_pairs(m, cand_place.p, cand_conf.p, PN.off.p, PN.units.p, CN.off.p, CN.units.p, k, full_dp, dist.p, s));
                 LOCREC_TRY(clock.mark(kPhaseCompact));
-                hipLaunchKernelGGL(dd_same_flags, grid_for(m), dim3(256), 0, s, m, dist.p, k, flags.p);
+                LOCREC_LAUNCH(dd_same_flags, grid_for(m), dim3(256), 0, s, m, dist.p, k, flags.p);
                 LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, flags.p, pos.p, (int)m, s));
-                hipLaunchKernelGGL(dd_emit_same, grid_for(m), dim3(256), 0, s, m, flags.p, pos.p, cand_place.p, cand_conf.p, dist.p,
-                                   total_same, cap, op.p, oc.p, od.p);
+                LOCREC_LAUNCH(dd_emit_same, grid_for(m), dim3(256), 0, s, m, flags.p, pos.p, cand_place.p, cand_conf.p, dist.p,
+                              total_same, cap, op.p, oc.p, od.p);
                 if (out_not_same_counts)
-                    hipLaunchKernelGGL(dd_subtract_same, grid_for(end - begin), dim3(256), 0, s, begin, end, offsets.p, counts.p, base,
-                                       flags.p, ons.p);
-                DD_LAUNCHED();
+                    LOCREC_LAUNCH(dd_subtract_same, grid_for(end - begin), dim3(256), 0, s, begin, end, offsets.p, counts.p, base,
+                                  flags.p, ons.p);
                 uint32_t last_pos = 0, last_flag = 0;
                 LOCREC_HIP_TRY(hipMemcpyAsync(&last_pos, pos.p + (m - 1), 4, hipMemcpyDeviceToHost, s));
                 LOCREC_HIP_TRY(hipMemcpyAsync(&last_flag, flags.p + (m - 1), 4, hipMemcpyDeviceToHost, s));

@@ -28,21 +28,13 @@
 #include <new>
 #include <numeric>
 
+#include "knn_build_open.h"
 #include "knn_index.h"
 #include "offline.h"
 
 namespace {
 
 using namespace locrec;
-
-// ---- small helpers ---------------------------------------------------------------------------
-
-int ceil_log2_64(int64_t v)
-{
-    int l = 0;
-    while (((int64_t)1 << l) < v) ++l;
-    return l;
-}
 
 // ---- validation ------------------------------------------------------------------------------
 
@@ -487,88 +479,101 @@ struct MaxI64 {
     __host__ __device__ int64_t operator()(int64_t a, int64_t b) const { return a > b ? a : b; }
 };
 
-// one family's images from its CSR in row order (device)
-int32_t build_family(locrec_knn_index *ix, DevFamily &d, int32_t dim, int32_t vbits, bool packed, const DevBuf<int32_t> &nnz_dev,
-                     Temp &tmp, const unsigned char *skip)
+// ---- the build's phases ----------------------------------------------------------------------
+// knn_build_device below runs them in this order as members of one Build: what a phase leaves for later ones is a
+// member, what only it needs is a local of its own and is released when it returns.
+
+struct CsrKeys {
+    DevBuf<uint64_t> k1, k2;
+    DevBuf<uint32_t> v1, v2;
+};
+
+struct Build {
+    // the caller's DEVICE arrays
+    int64_t n;
+    const int64_t *ids, *p_ptr, *c_ptr, *r_ptr, *r_place, *r_rating;
+    const int32_t *p_idx, *c_idx;
+    const double *p_val, *c_val;
+    int32_t p_dim, c_dim;
+    size_t nn = (size_t)std::max<int64_t>(1, n);
+    locrec_knn_index *ix = nullptr;  // the handle under construction, and its stream
+    hipStream_t s = nullptr;
+    Temp tmp;
+    int64_t pe = 0, ce = 0, re = 0;  // elements of the place, category and rating arrays
+    KnnFormatInput in;               // knn_format_plan.h: the decision's input ...
+    KnnFormatPlan plan;              // ... and the decision
+    DevBuf<unsigned char> wide_in;   // per INPUT row: breaks the head / tail legality by itself (kb_validate)
+    DevBuf<int32_t> new_of_old;      // popularity renumbering of the place dimensions (plan.use_pop)
+    DevBuf<uint32_t> freq_new;       // place frequencies by renumbered dimension
+    DevBuf<uint32_t> order;          // input row of every row
+    DevBuf<int32_t> nnz_p, nnz_c;
+    DevBuf<int64_t> len_p, len_c, len_r;
+    DevBuf<unsigned char> wide_row;  // per ROW (non-empty only in the per-row fallback)
+    const unsigned char *skip = nullptr;
+
+    // the phases, in the order knn_build_device runs them, and the steps they share
+    int32_t validate_and_plan(), renumber_by_popularity(), order_rows_and_rank_ids(), list_wide_rows();
+    int32_t csr_of(DevFamily &d, const int64_t *in_ptr, const int32_t *in_idx, const double *in_val, int64_t ne, DevBuf<int64_t> &len,
+                   const int32_t *renumber);
+    int32_t sell_and_side_images(), head_tail_image(), ratings_and_transpose();
+    int32_t slice_layout(const DevBuf<int32_t> &lens, bool whole_groups, DevBuf<int32_t> &w, DevBuf<int64_t> &off, int64_t &total);
+    int32_t build_family(DevFamily &d, int32_t dim, int32_t vbits, const DevBuf<int32_t> &nnz_dev);
+    int32_t keys_to_csr(CsrKeys &keys, const int64_t *in_ptr, const int32_t *in_idx, const double *in_val, int64_t ne,
+                        const int64_t *out_ptr, const int32_t *renumber, DevBuf<int32_t> &out_idx, bool alloc_idx, double *out_val);
+    int32_t side_image(const DevFamily &src, DevBuf<int2> &img, DevBuf<int32_t> &off_d, DevBuf<int32_t> &w_d);
+    int32_t ht_sell(const DevFamily &src, const DevBuf<int32_t> &lens, const int32_t *limit, DevBuf<uint32_t> &sell, DevBuf<int64_t> &off,
+                    DevBuf<int32_t> &w, int64_t &elements);
+};
+
+// A SELL-64 image's slice layout from its rows' lengths: every slice's width (w), the slices' offsets (off, in
+// elements) and their end.  whole_groups: widths are whole dwordx4 groups (the packed element formats).
+int32_t Build::slice_layout(const DevBuf<int32_t> &lens, bool whole_groups, DevBuf<int32_t> &w, DevBuf<int64_t> &off, int64_t &total)
 {
-    const int64_t n = ix->n;
     const int32_t nslices = ix->nslices;
-    hipStream_t s = ix->stream;
-    d.dim = dim;
-    d.vbits = vbits;
     DevBuf<int64_t> w64;
-    LOCREC_TRY(d.sell_w.alloc((size_t)nslices));
-    LOCREC_TRY(w64.alloc((size_t)nslices + 1));
-    LOCREC_TRY(d.sell_off.alloc((size_t)nslices + 1));
+    LOCREC_TRY(w.alloc((size_t)nslices));
+    LOCREC_TRY(alloc_each((size_t)nslices + 1, w64, off));
     LOCREC_HIP_TRY(hipMemsetAsync(w64.p, 0, ((size_t)nslices + 1) * 8, s));
     if (nslices > 0)
-        hipLaunchKernelGGL(kb_slice_width, grid_for(nslices), dim3(256), 0, s, n, nslices, nnz_dev.p, packed ? 1 : 0, d.sell_w.p, w64.p);
-    LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, w64.p, d.sell_off.p, nslices + 1, s));
+        LOCREC_LAUNCH(kb_slice_width, grid_for(nslices), dim3(256), 0, s, n, nslices, lens.p, whole_groups ? 1 : 0, w.p, w64.p);
+    LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, w64.p, off.p, nslices + 1, s));
+    LOCREC_READ_BACK(total, off.p + nslices, s);
+    return LOCREC_OK;
+}
+
+// one family's images from its CSR in row order (device)
+int32_t Build::build_family(DevFamily &d, int32_t dim, int32_t vbits, const DevBuf<int32_t> &nnz_dev)
+{
+    const bool packed = ix->packed;
+    d.dim = dim;
+    d.vbits = vbits;
     int64_t total = 0;
-    LOCREC_HIP_TRY(hipMemcpyAsync(&total, d.sell_off.p + nslices, 8, hipMemcpyDeviceToHost, s));
-    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    LOCREC_TRY(slice_layout(nnz_dev, packed, d.sell_w, d.sell_off, total));
     LOCREC_TRY(d.sell.alloc((size_t)total));
     LOCREC_HIP_TRY(hipMemsetAsync(d.sell.p, 0, (size_t)std::max<int64_t>(1, total) * 4, s));
     if (packed) {
         if (n > 0)
-            hipLaunchKernelGGL(kb_sell_packed, grid_for(n), dim3(256), 0, s, n, d.csr_ptr.p, d.csr_idx.p, d.csr_val.p, nullptr,
-                               d.sell_off.p, vbits, 0, d.sell.p, skip);
+            LOCREC_LAUNCH(kb_sell_packed, grid_for(n), dim3(256), 0, s, n, d.csr_ptr.p, d.csr_idx.p, d.csr_val.p, nullptr,
+                          d.sell_off.p, vbits, 0, d.sell.p, skip);
     } else {
         LOCREC_TRY(d.sell_val.alloc((size_t)total));
         LOCREC_HIP_TRY(hipMemsetAsync(d.sell_val.p, 0, (size_t)std::max<int64_t>(1, total) * 8, s));
         if (n > 0)
-            hipLaunchKernelGGL(kb_sell_generic, grid_for(n), dim3(256), 0, s, n, d.csr_ptr.p, d.csr_idx.p, d.csr_val.p, d.sell_off.p,
-                               d.sell.p, d.sell_val.p);
+            LOCREC_LAUNCH(kb_sell_generic, grid_for(n), dim3(256), 0, s, n, d.csr_ptr.p, d.csr_idx.p, d.csr_val.p, d.sell_off.p,
+                          d.sell.p, d.sell_val.p);
     }
-    LOCREC_TRY(d.norm.alloc((size_t)n));
-    LOCREC_TRY(d.inorm32.alloc((size_t)n));
-    if (n > 0) hipLaunchKernelGGL(kb_norms, grid_for(n), dim3(256), 0, s, d.csr_ptr.p, d.csr_val.p, n, d.norm.p, d.inorm32.p);
-    d.scan_bytes = total * (packed ? 4 : 12) + (int64_t)nslices * 12 + n * (packed ? 4 : 8);
-    LOCREC_HIP_TRY(hipGetLastError());
+    LOCREC_TRY(alloc_each((size_t)n, d.norm, d.inorm32));
+    if (n > 0) LOCREC_LAUNCH(kb_norms, grid_for(n), dim3(256), 0, s, d.csr_ptr.p, d.csr_val.p, n, d.norm.p, d.inorm32.p);
+    d.scan_bytes = total * (packed ? 4 : 12) + (int64_t)ix->nslices * 12 + n * (packed ? 4 : 8);
     return LOCREC_OK;
 }
 
-}  // namespace
-
-namespace locrec {
-
-// The whole build.  Every pointer is a DEVICE pointer valid on the current device; r_ptr may be null
-// (ratings = the place vectors themselves, what RatingVectorsBuilderMain.scala:41-73 writes).
-int32_t knn_build_device(int64_t n, const int64_t *ids, const int64_t *p_ptr, const int32_t *p_idx, const double *p_val,
-                         int32_t p_dim, const int64_t *c_ptr, const int32_t *c_idx, const double *c_val, int32_t c_dim,
-                         const int64_t *r_ptr, const int64_t *r_place, const int64_t *r_rating, locrec_knn_index **out)
+// the element counts, validation (SparseVector invariants, RatingVectorsBuilder.scala:74-77) and, from the
+// maxima it finds, the index's format and kernel path (knn_format_plan.h: the decision knn_host_build.h takes too)
+int32_t Build::validate_and_plan()
 {
-    if (!out) return fail(LOCREC_E_INVALID_ARG, "out_index is NULL");
-    *out = nullptr;
-    if (n < 0 || n >= ((int64_t)1 << 31) - 64) return fail(LOCREC_E_INVALID_ARG, "bad person count");
-    if (n > 0 && (!ids || !p_ptr || !c_ptr)) return fail(LOCREC_E_INVALID_ARG, "NULL input array");
-    if (p_dim <= 0 || c_dim <= 0) return fail(LOCREC_E_INVALID_ARG, "vector sizes must be positive");
-    LOCREC_TRY(ensure_device());
-    std::unique_ptr<locrec_knn_index> ix(new (std::nothrow) locrec_knn_index);
-    if (!ix) return fail(LOCREC_E_OOM, "host allocation failed");
-    LOCREC_HIP_TRY(hipGetDevice(&ix->device));
-    LOCREC_HIP_TRY(hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking));
-    ix->own_stream = true;
-    hipStream_t s = ix->stream;
-    ix->n = n;
-    ix->nslices = (int32_t)((n + 63) / 64);
-    ix->cand_slice0 = 0;
-    ix->cand_slice1 = ix->nslices;
-    knn_read_env(ix.get());
-    const bool force_generic = ix->force_generic;
-    const bool dbg_t = debug_env("LOCREC_DEBUG_TIMING") != nullptr;
-    auto t_last = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (!dbg_t) return;
-        (void)hipStreamSynchronize(s);
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[locrec knn_build_device] %-30s %.3f s\n", what, std::chrono::duration<double>(now - t_last).count());
-        t_last = now;
-    };
-    Temp tmp;
-
-    // ---- sizes of the element arrays: the last row pointers
-    int64_t pe = 0, ce = 0, re = 0, p0 = 0, c0 = 0;
+    // sizes of the element arrays: the last row pointers
+    int64_t p0 = 0, c0 = 0;
     if (n > 0) {
         LOCREC_HIP_TRY(hipMemcpyAsync(&pe, p_ptr + n, 8, hipMemcpyDeviceToHost, s));
         LOCREC_HIP_TRY(hipMemcpyAsync(&ce, c_ptr + n, 8, hipMemcpyDeviceToHost, s));
@@ -582,22 +587,18 @@ int32_t knn_build_device(int64_t n, const int64_t *ids, const int64_t *p_ptr, co
             return fail(LOCREC_E_INVALID_ARG, "element count out of range (the build sorts 32-bit positions)");
         if (r_ptr && re > 0 && (!r_place || !r_rating)) return fail(LOCREC_E_INVALID_ARG, "NULL ratings array");
     }
-
-    // ---- validation (SparseVector invariants, RatingVectorsBuilder.scala:74-77)
     DevBuf<CheckOut> chk;
     LOCREC_TRY(chk.alloc(2));
     CheckOut init{~0ull, 0ull, 0ull, 0, 0, 0ull, 0ull};
     CheckOut h_chk[2] = {init, init};
     LOCREC_HIP_TRY(hipMemcpyAsync(chk.p, h_chk, sizeof h_chk, hipMemcpyHostToDevice, s));
-    DevBuf<unsigned char> wide_in;  // per INPUT row: breaks the head / tail legality by itself (kb_validate)
     LOCREC_TRY(wide_in.alloc((size_t)std::max<int64_t>(1, n)));
     LOCREC_HIP_TRY(hipMemsetAsync(wide_in.p, 0, (size_t)std::max<int64_t>(1, n), s));
     if (n > 0) {
-        hipLaunchKernelGGL(kb_validate, grid_for(n), dim3(256), 0, s, n, p_ptr, p_idx, p_val, p_dim, chk.p, wide_in.p);
-        hipLaunchKernelGGL(kb_validate, grid_for(n), dim3(256), 0, s, n, c_ptr, c_idx, c_val, c_dim, chk.p + 1, wide_in.p);
+        LOCREC_LAUNCH(kb_validate, grid_for(n), dim3(256), 0, s, n, p_ptr, p_idx, p_val, p_dim, chk.p, wide_in.p);
+        LOCREC_LAUNCH(kb_validate, grid_for(n), dim3(256), 0, s, n, c_ptr, c_idx, c_val, c_dim, chk.p + 1, wide_in.p);
     }
-    LOCREC_HIP_TRY(hipMemcpyAsync(h_chk, chk.p, sizeof h_chk, hipMemcpyDeviceToHost, s));
-    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    LOCREC_READ_BACK(h_chk, chk.p, s);
     for (int f = 0; f < 2; ++f) {
         const char *name = f == 0 ? "place" : "category";
         if (h_chk[f].first_error == ~0ull) continue;
@@ -615,124 +616,67 @@ int32_t knn_build_device(int64_t n, const int64_t *ids, const int64_t *p_ptr, co
         default: return fail(LOCREC_E_INVALID_ARG, "%s vector of person %lld has zero norm", name, (long long)pid);
         }
     }
-    auto as_double = [](unsigned long long bits) {
-        double d;
-        std::memcpy(&d, &bits, 8);
-        return d;
-    };
-    const bool integral = !h_chk[0].non_integral && !h_chk[1].non_integral;
-    double pvmax = as_double(h_chk[0].vmax_bits), cvmax = as_double(h_chk[1].vmax_bits);
-    double pss = as_double(h_chk[0].ssmax_bits), css = as_double(h_chk[1].ssmax_bits);
-    // ---- per-row format fallback.  Counts are unbounded in the reference's data (RatingVectorsBuilder.scala:69
-    // `rating.toDouble` of count("*")): ONE person with 256 visits to a place, or one row with a sum of squares of
-    // 65,536, used to demote the WHOLE index from the head / tail form to PACK32 (3.6 x slower per pair).  When such
-    // "wide" rows are few - at most max(256, n / 512), capped at 4096: the side kernels of knn.hip score every
-    // (query, wide row) pair by merging two CSR rows - they are kept out of the packed images (all padding, ss = 0),
-    // the rest of the index is judged on its own maxima, and knn.hip adds the wide rows back: as candidates through
-    // knn_side_topk / knn_side_scan1, as queries through the dense CSR scan.  Integer data only: a non-integer value
-    // still selects the GENERIC format for everybody (the reference's builders never produce one).
-    std::vector<unsigned char> h_wide;
-    int64_t n_wide = 0;
-    const bool any_wide = pvmax >= 256.0 || cvmax >= 256.0 || pss >= 65536.0 || css >= 65536.0;
-    if (any_wide && integral && !force_generic && !ix->no_row_fallback && !ix->no_pack16 && !ix->no_ht && n < ((int64_t)1 << 24) && c_dim <= cfg::kHtCatRows &&
-        p_dim < (1 << 20) - 1) {  // (a place dimension no packed format holds: GENERIC keeps every row in its image)
-        h_wide.resize((size_t)n);
+    in.integral = !h_chk[0].non_integral && !h_chk[1].non_integral;
+    auto val = [](unsigned long long bits) { double d; std::memcpy(&d, &bits, 8); return d; };
+    in.all = {val(h_chk[0].vmax_bits), val(h_chk[1].vmax_bits), val(h_chk[0].ssmax_bits), val(h_chk[1].ssmax_bits)};
+    in.narrow = {val(h_chk[0].lvmax_bits), val(h_chk[1].lvmax_bits), val(h_chk[0].lssmax_bits), val(h_chk[1].lssmax_bits)};
+    int64_t wide_count = 0;
+    if (knn_row_fallback_eligible(in)) {  // (only then do the per-row flags travel to the host)
+        std::vector<unsigned char> h_wide((size_t)n);
         LOCREC_HIP_TRY(hipMemcpy(h_wide.data(), wide_in.p, (size_t)n, hipMemcpyDeviceToHost));
-        for (unsigned char w : h_wide) n_wide += w ? 1 : 0;
-        const int64_t cap = std::min<int64_t>(4096, std::max<int64_t>(256, n / 512));
-        if (n_wide > 0 && n_wide <= cap && n_wide < n) {
-            pvmax = as_double(h_chk[0].lvmax_bits);
-            cvmax = as_double(h_chk[1].lvmax_bits);
-            pss = as_double(h_chk[0].lssmax_bits);
-            css = as_double(h_chk[1].lssmax_bits);
-        } else {
-            n_wide = 0;
-        }
+        for (unsigned char w : h_wide) wide_count += w ? 1 : 0;
     }
-    // (the SELL image's own limits - values below 2^vbits, sums of squares below 2^32 - hold for the non-wide rows a
-    // fortiori; the wide rows never enter it)
-    const int p_vbits = std::min(24, 32 - ceil_log2_64(p_dim));
-    const int c_vbits = std::min(24, 32 - ceil_log2_64(c_dim));
-    ix->packed = !force_generic && integral && p_dim < (1 << 20) - 1 && c_dim < (1 << 20) - 1 &&
-                 pvmax < (double)(1u << p_vbits) && cvmax < (double)(1u << c_vbits) && pss < 4294967296.0 && css < 4294967296.0;
-    ix->pack16 = ix->packed && pss < 65536.0 && css < 65536.0 && pvmax < 65536.0 && cvmax < 65536.0 &&
-                 !ix->no_pack16;
-    lap("validation");
+    plan = knn_format_plan(in, wide_count);
+    ix->packed = plan.packed;
+    ix->pack16 = plan.pack16;
+    return LOCREC_OK;
+}
 
-    // ---- popularity renumbering of the place dimensions (see knn.hip / knn_ht.h)
-    const int ht_qt = cfg::kHtQt;
-    int32_t ht_h = std::min<int32_t>(p_dim, cfg::kHtHead);
-    if (ix->env_ht_h > 0) ht_h = std::min<int32_t>(p_dim, ix->env_ht_h);
-    ht_h = std::min<int32_t>(ht_h, 65536 / (2 * ht_qt));
-    const bool want_ht = ix->pack16 && !ix->no_ht && !force_generic && n > 0 && n < ((int64_t)1 << 24) && pvmax < 256.0 &&
-                         cvmax < 256.0 && c_dim <= cfg::kHtCatRows;
-    const bool use_pop = ix->packed && !ix->no_pop && n > 0 &&
-                         (ix->force_hash || (size_t)p_dim * 2 > (size_t)cfg::kDirectMaxBytes || want_ht);
-    int32_t pop_h = 0;
-    DevBuf<int32_t> new_of_old;
-    DevBuf<uint32_t> freq, freq_new;
-    if (use_pop) {
-        LOCREC_TRY(freq.alloc((size_t)p_dim));
-        LOCREC_TRY(freq_new.alloc((size_t)p_dim));
-        LOCREC_TRY(new_of_old.alloc((size_t)p_dim));
-        LOCREC_HIP_TRY(hipMemsetAsync(freq.p, 0, (size_t)p_dim * 4, s));
-        if (pe > 0) hipLaunchKernelGGL(kb_hist, grid_for(pe, kHistChunk), dim3(256), 0, s, pe, p_idx, freq.p);
-        DevBuf<uint64_t> dk, dk2;
-        LOCREC_TRY(dk.alloc((size_t)p_dim));
-        LOCREC_TRY(dk2.alloc((size_t)p_dim));
-        hipLaunchKernelGGL(kb_dim_keys, grid_for(p_dim), dim3(256), 0, s, p_dim, freq.p, dk.p);
-        LOCREC_PRIM(tmp, prim::sort_keys(p_, bytes_, dk.p, dk2.p, p_dim, 0, 64, s));
-        hipLaunchKernelGGL(kb_new_of_old, grid_for(p_dim), dim3(256), 0, s, p_dim, dk2.p, new_of_old.p, freq_new.p);
-        pop_h = std::min<int32_t>(p_dim, cfg::kPopTable);
-        if (ix->env_pop_h > 0) pop_h = std::min<int32_t>(p_dim, ix->env_pop_h);
-        LOCREC_HIP_TRY(hipStreamSynchronize(s));
-    }
-    const int32_t key_h = want_ht ? ht_h : pop_h;
-    lap("popularity");
+// popularity renumbering of the place dimensions (see knn.hip / knn_ht.h)
+int32_t Build::renumber_by_popularity()
+{
+    if (!plan.use_pop) return LOCREC_OK;
+    DevBuf<uint32_t> freq;
+    LOCREC_TRY(alloc_each((size_t)p_dim, freq, freq_new, new_of_old));
+    LOCREC_HIP_TRY(hipMemsetAsync(freq.p, 0, (size_t)p_dim * 4, s));
+    if (pe > 0) LOCREC_LAUNCH(kb_hist, grid_for(pe, kHistChunk), dim3(256), 0, s, pe, p_idx, freq.p);
+    DevBuf<uint64_t> dk, dk2;
+    LOCREC_TRY(alloc_each((size_t)p_dim, dk, dk2));
+    LOCREC_LAUNCH(kb_dim_keys, grid_for(p_dim), dim3(256), 0, s, p_dim, freq.p, dk.p);
+    LOCREC_PRIM(tmp, prim::sort_keys(p_, bytes_, dk.p, dk2.p, p_dim, 0, 64, s));
+    LOCREC_LAUNCH(kb_new_of_old, grid_for(p_dim), dim3(256), 0, s, p_dim, dk2.p, new_of_old.p, freq_new.p);
+    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    return LOCREC_OK;
+}
 
-    // ---- row order: ascending (nnz_place, nnz_category[, head / popular count]), stable
+// row order: ascending (nnz_place, nnz_category[, head / popular count]), stable; then rid, the rank of each row's
+// person id (tie-break person_id asc), and what request planning needs of both on the host
+int32_t Build::order_rows_and_rank_ids()
+{
     DevBuf<uint64_t> rk, rk2, idk, idk2;
-    DevBuf<uint32_t> rv, order, idv, idv2;
-    DevBuf<int64_t> ids_row, len_p, len_c, len_r;
-    DevBuf<int32_t> row_of_input, nnz_p, nnz_c, npop;
-    const size_t nn = (size_t)std::max<int64_t>(1, n);
-    LOCREC_TRY(rk.alloc(nn));
-    LOCREC_TRY(rk2.alloc(nn));
-    LOCREC_TRY(rv.alloc(nn));
-    LOCREC_TRY(order.alloc(nn));
-    LOCREC_TRY(idk.alloc(nn));
-    LOCREC_TRY(idk2.alloc(nn));
-    LOCREC_TRY(idv.alloc(nn));
-    LOCREC_TRY(idv2.alloc(nn));
-    LOCREC_TRY(ids_row.alloc(nn));
-    LOCREC_TRY(row_of_input.alloc(nn));
-    LOCREC_TRY(nnz_p.alloc(nn));
-    LOCREC_TRY(nnz_c.alloc(nn));
-    LOCREC_TRY(npop.alloc(nn));
-    LOCREC_TRY(len_p.alloc(nn + 1));
-    LOCREC_TRY(len_c.alloc(nn + 1));
-    LOCREC_TRY(len_r.alloc(nn + 1));
+    DevBuf<uint32_t> rv, idv, idv2;
+    DevBuf<int64_t> ids_row;
+    DevBuf<int32_t> row_of_input, npop;
+    LOCREC_TRY(alloc_each(nn, rk, rk2, rv, order, idk, idk2, idv, idv2, ids_row, row_of_input, nnz_p, nnz_c, npop));
+    LOCREC_TRY(alloc_each(nn + 1, len_p, len_c, len_r));
     LOCREC_HIP_TRY(hipMemsetAsync(len_p.p, 0, (nn + 1) * 8, s));
     LOCREC_HIP_TRY(hipMemsetAsync(len_c.p, 0, (nn + 1) * 8, s));
     LOCREC_HIP_TRY(hipMemsetAsync(len_r.p, 0, (nn + 1) * 8, s));
     if (n > 0) {
-        hipLaunchKernelGGL(kb_row_keys, grid_for(n), dim3(256), 0, s, n, p_ptr, p_idx, c_ptr, use_pop ? new_of_old.p : nullptr, key_h,
-                           rk.p, rv.p);
+        LOCREC_LAUNCH(kb_row_keys, grid_for(n), dim3(256), 0, s, n, p_ptr, p_idx, c_ptr, plan.use_pop ? new_of_old.p : nullptr,
+                      plan.key_h, rk.p, rv.p);
         LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, rk.p, rk2.p, rv.p, order.p, (int)n, 0, 64, s));
-        hipLaunchKernelGGL(kb_apply_order, grid_for(n), dim3(256), 0, s, n, rk2.p, order.p, ids, r_ptr, ids_row.p, row_of_input.p,
-                           nnz_p.p, nnz_c.p, npop.p, len_p.p, len_c.p, len_r.p, idk.p, idv.p);
+        LOCREC_LAUNCH(kb_apply_order, grid_for(n), dim3(256), 0, s, n, rk2.p, order.p, ids, r_ptr, ids_row.p, row_of_input.p,
+                      nnz_p.p, nnz_c.p, npop.p, len_p.p, len_c.p, len_r.p, idk.p, idv.p);
     }
-    // ---- rid: rank of each row's person id (tie-break person_id asc)
     DevBuf<unsigned long long> dup;
     LOCREC_TRY(dup.alloc(1));
     LOCREC_HIP_TRY(hipMemsetAsync(dup.p, 0xFF, 8, s));
-    LOCREC_TRY(ix->rid.alloc(nn));
-    LOCREC_TRY(ix->ids_by_rank.alloc(nn));
-    LOCREC_TRY(ix->row_of_rid.alloc(nn));
+    LOCREC_TRY(alloc_each(nn, ix->rid, ix->ids_by_rank, ix->row_of_rid));
     if (n > 0) {
         LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, idk.p, idk2.p, idv.p, idv2.p, (int)n, 0, 64, s));
-        hipLaunchKernelGGL(kb_rank_ids, grid_for(n), dim3(256), 0, s, n, idk2.p, idv2.p, ix->rid.p, ix->ids_by_rank.p,
-                           ix->row_of_rid.p, dup.p);
+        LOCREC_LAUNCH(kb_rank_ids, grid_for(n), dim3(256), 0, s, n, idk2.p, idv2.p, ix->rid.p, ix->ids_by_rank.p,
+                      ix->row_of_rid.p, dup.p);
     }
     unsigned long long h_dup = ~0ull;
     LOCREC_HIP_TRY(hipMemcpyAsync(&h_dup, dup.p, 8, hipMemcpyDeviceToHost, s));
@@ -752,276 +696,298 @@ int32_t knn_build_device(int64_t n, const int64_t *ids, const int64_t *p_ptr, co
     }
     LOCREC_HIP_TRY(hipStreamSynchronize(s));
     if (h_dup != ~0ull) return fail(LOCREC_E_INVALID_ARG, "duplicate person_id %lld", (long long)ix->ids_sorted[(size_t)h_dup]);
-    lap("row order + id rank");
-    DevBuf<unsigned char> wide_row;  // per ROW (non-empty only in the per-row fallback)
-    const unsigned char *skip = nullptr;
-    if (n_wide > 0) {
-        LOCREC_TRY(wide_row.alloc((size_t)n));
-        hipLaunchKernelGGL(kb_wide_rows, grid_for(n), dim3(256), 0, s, n, order.p, wide_in.p, wide_row.p);
-        ix->is_wide.resize((size_t)n);
-        LOCREC_HIP_TRY(hipMemcpyAsync(ix->is_wide.data(), wide_row.p, (size_t)n, hipMemcpyDeviceToHost, s));
-        LOCREC_HIP_TRY(hipStreamSynchronize(s));
-        for (int64_t r = 0; r < n; ++r)
-            if (ix->is_wide[(size_t)r]) ix->wide_rows.push_back((int32_t)r);
-        LOCREC_TRY(ix->wide_rows_dev.upload(ix->wide_rows, s));
-        LOCREC_HIP_TRY(hipStreamSynchronize(s));
-        skip = wide_row.p;
+    return LOCREC_OK;
+}
+
+// the per-row fallback's wide rows: their flags in row order, their list on both sides
+int32_t Build::list_wide_rows()
+{
+    if (plan.n_wide == 0) return LOCREC_OK;
+    LOCREC_TRY(wide_row.alloc((size_t)n));
+    LOCREC_LAUNCH(kb_wide_rows, grid_for(n), dim3(256), 0, s, n, order.p, wide_in.p, wide_row.p);
+    ix->is_wide.resize((size_t)n);
+    LOCREC_HIP_TRY(hipMemcpyAsync(ix->is_wide.data(), wide_row.p, (size_t)n, hipMemcpyDeviceToHost, s));
+    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    for (int64_t r = 0; r < n; ++r)
+        if (ix->is_wide[(size_t)r]) ix->wide_rows.push_back((int32_t)r);
+    LOCREC_TRY(ix->wide_rows_dev.upload(ix->wide_rows, s));
+    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    skip = wide_row.p;
+    return LOCREC_OK;
+}
+
+// The elements of the caller's rows in row order: keyed (row, [renumbered] index), sorted when renumbered (the new
+// indices of a row are no longer ascending), written out as indices and values.  alloc_idx: out_idx is allocated
+// here, after the keys (the default ratings).  The caller waits for the stream before `keys` (CsrKeys) goes out of scope.
+int32_t Build::keys_to_csr(CsrKeys &keys, const int64_t *in_ptr, const int32_t *in_idx, const double *in_val, int64_t ne,
+                    const int64_t *out_ptr, const int32_t *renumber, DevBuf<int32_t> &out_idx, bool alloc_idx, double *out_val)
+{
+    const size_t nee = (size_t)std::max<int64_t>(1, ne);
+    LOCREC_TRY(alloc_each(nee, keys.k1, keys.v1));
+    LOCREC_LAUNCH(kb_place_keys, grid_for(n), dim3(256), 0, s, n, order.p, in_ptr, out_ptr, in_idx, renumber, keys.k1.p, keys.v1.p,
+                  nullptr);
+    const uint64_t *ks = keys.k1.p;
+    const uint32_t *vs = keys.v1.p;
+    if (renumber) {
+        LOCREC_TRY(alloc_each(nee, keys.k2, keys.v2));
+        LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, keys.k1.p, keys.k2.p, keys.v1.p, keys.v2.p, (int)ne, 0,
+                                            32 + std::max(1, ceil_log2_64(n + 1)), s));
+        ks = keys.k2.p;
+        vs = keys.v2.p;
     }
+    if (alloc_idx) LOCREC_TRY(out_idx.alloc(nee));
+    LOCREC_LAUNCH(kb_finish_csr, grid_for(ne), dim3(256), 0, s, ne, ks, vs, in_val, out_idx.p, out_val);
+    return LOCREC_OK;
+}
 
-    // ---- CSR of both families in row order (place: renumbered and re-sorted inside every row)
-    auto csr_of = [&](DevFamily &d, const int64_t *in_ptr, const int32_t *in_idx, const double *in_val, int64_t ne,
-                      DevBuf<int64_t> &len, const int32_t *renumber, DevBuf<int32_t> *orig_idx) -> int32_t {
-        LOCREC_TRY(d.csr_ptr.alloc(nn + 1));
-        LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, len.p, d.csr_ptr.p, (int)(n + 1), s));
-        const size_t nee = (size_t)std::max<int64_t>(1, ne);
-        LOCREC_TRY(d.csr_idx.alloc(nee));
-        LOCREC_TRY(d.csr_val.alloc(nee));
-        if (orig_idx) LOCREC_TRY(orig_idx->alloc(nee));
-        if (ne == 0 || n == 0) return LOCREC_OK;
-        DevBuf<uint64_t> k1, k2;
-        DevBuf<uint32_t> v1, v2;
-        LOCREC_TRY(k1.alloc(nee));
-        LOCREC_TRY(v1.alloc(nee));
-        hipLaunchKernelGGL(kb_place_keys, grid_for(n), dim3(256), 0, s, n, order.p, in_ptr, d.csr_ptr.p, in_idx, renumber, k1.p, v1.p,
-                           orig_idx ? orig_idx->p : nullptr);
-        const uint64_t *ks = k1.p;
-        const uint32_t *vs = v1.p;
-        if (renumber) {  // the renumbered indices of a row are no longer ascending: sort by (row, new index)
-            LOCREC_TRY(k2.alloc(nee));
-            LOCREC_TRY(v2.alloc(nee));
-            LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, k1.p, k2.p, v1.p, v2.p, (int)ne, 0,
-                                                               32 + std::max(1, ceil_log2_64(n + 1)), s));
-            ks = k2.p;
-            vs = v2.p;
-        }
-        hipLaunchKernelGGL(kb_finish_csr, grid_for(ne), dim3(256), 0, s, ne, ks, vs, in_val, d.csr_idx.p, d.csr_val.p);
-        LOCREC_HIP_TRY(hipStreamSynchronize(s));  // k / v go out of scope
-        return LOCREC_OK;
-    };
-    LOCREC_TRY(csr_of(ix->fp, p_ptr, p_idx, p_val, pe, len_p, use_pop ? new_of_old.p : nullptr, nullptr));
-    LOCREC_TRY(csr_of(ix->fc, c_ptr, c_idx, c_val, ce, len_c, nullptr, nullptr));
-    lap("CSR (gather, renumber, sort)");
+// one family's CSR in row order (place: renumbered and re-sorted inside every row)
+int32_t Build::csr_of(DevFamily &d, const int64_t *in_ptr, const int32_t *in_idx, const double *in_val, int64_t ne,
+               DevBuf<int64_t> &len, const int32_t *renumber)
+{
+    LOCREC_TRY(d.csr_ptr.alloc(nn + 1));
+    LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, len.p, d.csr_ptr.p, (int)(n + 1), s));
+    const size_t nee = (size_t)std::max<int64_t>(1, ne);
+    LOCREC_TRY(alloc_each(nee, d.csr_idx, d.csr_val));
+    if (ne == 0 || n == 0) return LOCREC_OK;
+    CsrKeys keys;
+    LOCREC_TRY(keys_to_csr(keys, in_ptr, in_idx, in_val, ne, d.csr_ptr.p, renumber, d.csr_idx, false, d.csr_val.p));
+    LOCREC_HIP_TRY(hipStreamSynchronize(s));  // the keys go out of scope
+    return LOCREC_OK;
+}
 
-    // ---- SELL-64 images, norms
-    LOCREC_TRY(build_family(ix.get(), ix->fp, p_dim, p_vbits, ix->packed, nnz_p, tmp, skip));
-    LOCREC_TRY(build_family(ix.get(), ix->fc, c_dim, c_vbits, ix->packed, nnz_c, tmp, skip));
-    if (use_pop) {
+// the side kernels' lane-major copy of the wide rows of one family (values are integer counts)
+int32_t Build::side_image(const DevFamily &src, DevBuf<int2> &img, DevBuf<int32_t> &off_d, DevBuf<int32_t> &w_d)
+{
+    const int32_t nw = (int32_t)ix->wide_rows.size(), ns = (nw + 63) / 64;
+    std::vector<int32_t> off((size_t)ns + 1, 0), wv((size_t)ns, 0);
+    for (int32_t sl = 0; sl < ns; ++sl) {
+        int m = 0;
+        for (int32_t w = sl * 64; w < std::min(nw, sl * 64 + 64); ++w) m = std::max(m, src.nnz[(size_t)ix->wide_rows[(size_t)w]]);
+        wv[(size_t)sl] = m;
+        off[(size_t)sl + 1] = off[(size_t)sl] + m * 64;
+    }
+    const size_t total = (size_t)std::max(1, off[(size_t)ns]);
+    LOCREC_TRY(img.alloc(total));
+    LOCREC_HIP_TRY(hipMemsetAsync(img.p, 0xFF, total * sizeof(int2), s));  // index -1 = padding
+    LOCREC_TRY(off_d.upload(off, s));
+    LOCREC_TRY(w_d.upload(wv, s));
+    LOCREC_LAUNCH(kb_side_fill, grid_for(nw), dim3(256), 0, s, nw, ix->wide_rows_dev.p, src.csr_ptr.p, src.csr_idx.p,
+                  src.csr_val.p, off_d.p, img.p);
+    LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (off / wv are locals)
+    return LOCREC_OK;
+}
+
+// SELL-64 images and norms of both families, the popular-prefix split, the wide rows' side images
+int32_t Build::sell_and_side_images()
+{
+    LOCREC_TRY(build_family(ix->fp, p_dim, plan.p_vbits, nnz_p));
+    LOCREC_TRY(build_family(ix->fc, c_dim, plan.c_vbits, nnz_c));
+    if (plan.use_pop) {
         LOCREC_TRY(ix->fp.sell_split.alloc((size_t)std::max(1, ix->nslices)));
         if (ix->nslices > 0)
-            hipLaunchKernelGGL(kb_split, grid_for(ix->nslices), dim3(256), 0, s, n, ix->nslices, ix->fp.csr_ptr.p, ix->fp.csr_idx.p, pop_h,
-                               ix->fp.sell_w.p, ix->fp.sell_split.p);
-        ix->fp.pop_h = pop_h;
+            LOCREC_LAUNCH(kb_split, grid_for(ix->nslices), dim3(256), 0, s, n, ix->nslices, ix->fp.csr_ptr.p, ix->fp.csr_idx.p,
+                          plan.pop_h, ix->fp.sell_w.p, ix->fp.sell_split.p);
+        ix->fp.pop_h = plan.pop_h;
         ix->fp.scan_bytes += (int64_t)ix->nslices * 4;
     }
-    if (n_wide > 0) {
-        // the side kernels' lane-major copy of the wide rows (both families; values are integer counts)
-        auto side_of = [&](const DevFamily &src, DevBuf<int2> &img, DevBuf<int32_t> &off_d, DevBuf<int32_t> &w_d) -> int32_t {
-            const int32_t nw = (int32_t)ix->wide_rows.size(), ns = (nw + 63) / 64;
-            std::vector<int32_t> off((size_t)ns + 1, 0), wv((size_t)ns, 0);
-            for (int32_t sl = 0; sl < ns; ++sl) {
-                int m = 0;
-                for (int32_t w = sl * 64; w < std::min(nw, sl * 64 + 64); ++w) m = std::max(m, src.nnz[(size_t)ix->wide_rows[(size_t)w]]);
-                wv[(size_t)sl] = m;
-                off[(size_t)sl + 1] = off[(size_t)sl] + m * 64;
-            }
-            const size_t total = (size_t)std::max(1, off[(size_t)ns]);
-            LOCREC_TRY(img.alloc(total));
-            LOCREC_HIP_TRY(hipMemsetAsync(img.p, 0xFF, total * sizeof(int2), s));  // index -1 = padding
-            LOCREC_TRY(off_d.upload(off, s));
-            LOCREC_TRY(w_d.upload(wv, s));
-            hipLaunchKernelGGL(kb_side_fill, grid_for(nw), dim3(256), 0, s, nw, ix->wide_rows_dev.p, src.csr_ptr.p, src.csr_idx.p,
-                               src.csr_val.p, off_d.p, img.p);
-            LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (off / wv are locals)
-            return LOCREC_OK;
-        };
-        LOCREC_TRY(side_of(ix->fp, ix->side_p, ix->side_off_p, ix->side_w_p));
-        LOCREC_TRY(side_of(ix->fc, ix->side_c, ix->side_off_c, ix->side_w_c));
+    if (plan.n_wide > 0) {
+        LOCREC_TRY(side_image(ix->fp, ix->side_p, ix->side_off_p, ix->side_w_p));
+        LOCREC_TRY(side_image(ix->fc, ix->side_c, ix->side_off_c, ix->side_w_c));
     }
-    lap("SELL images + norms");
+    return LOCREC_OK;
+}
 
-    // ---- head / tail image (knn_ht.h)
-    if (want_ht) {
-        HtIndex &ht = ix->ht;
-        const int rsh = 4;  // byte offset of a 16-byte plane row (knn_ht.h)
-        DevBuf<int32_t> nhead, tail_nnz;
-        DevBuf<int64_t> tail_len, tail_ptr;
-        LOCREC_TRY(nhead.alloc(nn));
-        LOCREC_TRY(tail_nnz.alloc(nn));
-        LOCREC_TRY(tail_len.alloc(nn + 1));
-        LOCREC_TRY(tail_ptr.alloc(nn + 1));
-        LOCREC_TRY(ht.tail_hits.alloc(nn));
-        LOCREC_TRY(ht.ss.alloc((size_t)ix->nslices * 64));
-        LOCREC_HIP_TRY(hipMemsetAsync(tail_len.p, 0, (nn + 1) * 8, s));
-        LOCREC_HIP_TRY(hipMemsetAsync(ht.ss.p, 0, (size_t)ix->nslices * 64 * 4, s));
-        if (skip) hipLaunchKernelGGL(kb_freq_drop_rows, grid_for(n), dim3(256), 0, s, n, ix->fp.csr_ptr.p, ix->fp.csr_idx.p, skip, freq_new.p);
-        hipLaunchKernelGGL(kb_ht_rows, grid_for(n), dim3(256), 0, s, n, ix->fp.csr_ptr.p, ix->fp.csr_idx.p, ix->fp.csr_val.p,
-                           ix->fc.csr_ptr.p, ix->fc.csr_val.p, ht_h, freq_new.p, nhead.p, tail_nnz.p, tail_len.p, ht.tail_hits.p, ht.ss.p, skip);
-        LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, tail_len.p, tail_ptr.p, (int)(n + 1), s));
-        // head rows and category rows in the head / tail element format
-        auto ht_sell = [&](const DevFamily &src, const DevBuf<int32_t> &lens, const int32_t *limit, DevBuf<uint32_t> &sell,
-                           DevBuf<int64_t> &off, DevBuf<int32_t> &w, int64_t &elements) -> int32_t {
-            DevBuf<int64_t> w64;
-            LOCREC_TRY(w.alloc((size_t)ix->nslices));
-            LOCREC_TRY(w64.alloc((size_t)ix->nslices + 1));
-            LOCREC_TRY(off.alloc((size_t)ix->nslices + 1));
-            LOCREC_HIP_TRY(hipMemsetAsync(w64.p, 0, ((size_t)ix->nslices + 1) * 8, s));
-            hipLaunchKernelGGL(kb_slice_width, grid_for(ix->nslices), dim3(256), 0, s, n, ix->nslices, lens.p, 1, w.p, w64.p);
-            LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, w64.p, off.p, ix->nslices + 1, s));
-            LOCREC_HIP_TRY(hipMemcpyAsync(&elements, off.p + ix->nslices, 8, hipMemcpyDeviceToHost, s));
-            LOCREC_HIP_TRY(hipStreamSynchronize(s));
-            const size_t padded = (size_t)elements + (size_t)cfg::kHtNP * 256;  // knn_scan_ht always loads kHtNP groups
-            LOCREC_TRY(sell.alloc(padded));
-            LOCREC_HIP_TRY(hipMemsetAsync(sell.p, 0, padded * 4, s));
-            hipLaunchKernelGGL(kb_sell_packed, grid_for(n), dim3(256), 0, s, n, src.csr_ptr.p, src.csr_idx.p, src.csr_val.p, limit,
-                               off.p, 0, rsh, sell.p, skip);
-            return LOCREC_OK;
-        };
-        int64_t hpe = 0, hce = 0;
-        LOCREC_TRY(ht_sell(ix->fp, nhead, nhead.p, ht.p_sell, ht.p_off, ht.p_w, hpe));
-        LOCREC_TRY(ht_sell(ix->fc, nnz_c, nullptr, ht.c_sell, ht.c_off, ht.c_w, hce));
-        if (hpe / 4 < ((int64_t)1 << 32) && hce / 4 < ((int64_t)1 << 32)) {
-            LOCREC_TRY(ht.desc.alloc((size_t)std::max(1, ix->nslices)));
-            hipLaunchKernelGGL(kb_desc, grid_for(ix->nslices), dim3(256), 0, s, n, ix->nslices, ht.p_off.p, ht.p_w.p, ht.c_off.p, ht.c_w.p,
-                               nhead.p, nnz_c.p, skip, ix->ht_round4 ? 1 : 0, ht.desc.p);
-            {
-                // words per tile knn_scan_ht multiplies (locrec_knn_ht_multiplied_words): 64 lanes x the slices' counts
-                std::vector<uint4> hd((size_t)ix->nslices);
-                LOCREC_HIP_TRY(hipMemcpyAsync(hd.data(), ht.desc.p, (size_t)ix->nslices * sizeof(uint4), hipMemcpyDeviceToHost, s));
-                LOCREC_HIP_TRY(hipStreamSynchronize(s));
-                ht.mult_words = 0;
-                ht.slice_cnt.clear();
-                for (const uint4 &d : hd) {
-                    ht.mult_words += 64 * (int64_t)((d.w & 0xFFFFu) + (d.w >> 16));
-                    ht.slice_cnt.push_back(d.w);
-                }
-            }
-            LOCREC_TRY(ht.cold.alloc(cfg::kHtColdBytes));
-            // postings of the tail places: (place, row) keys, radix-sorted -> rows ascending inside a place
-            int64_t nt_el = 0;
-            LOCREC_HIP_TRY(hipMemcpyAsync(&nt_el, tail_ptr.p + n, 8, hipMemcpyDeviceToHost, s));
-            LOCREC_HIP_TRY(hipStreamSynchronize(s));
-            const int64_t ntail = std::max<int64_t>(0, (int64_t)p_dim - ht_h);
-            LOCREC_TRY(ht.post.alloc((size_t)std::max<int64_t>(1, nt_el)));
-            LOCREC_TRY(ht.post_ptr.alloc((size_t)ntail + 1));
-            {
-                DevBuf<int64_t> cnt;
-                LOCREC_TRY(cnt.alloc((size_t)ntail + 1));
-                LOCREC_HIP_TRY(hipMemsetAsync(cnt.p, 0, ((size_t)ntail + 1) * 8, s));
-                if (ntail > 0) hipLaunchKernelGGL(kb_tail_freq, grid_for(ntail), dim3(256), 0, s, ntail, freq_new.p, ht_h, cnt.p);
-                LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, cnt.p, ht.post_ptr.p, (int)(ntail + 1), s));
-                LOCREC_HIP_TRY(hipStreamSynchronize(s));
-            }
-            if (nt_el > 0) {
-                DevBuf<uint64_t> k1, k2;
-                DevBuf<uint32_t> v1, v2;
-                LOCREC_TRY(k1.alloc((size_t)nt_el));
-                LOCREC_TRY(k2.alloc((size_t)nt_el));
-                LOCREC_TRY(v1.alloc((size_t)nt_el));
-                LOCREC_TRY(v2.alloc((size_t)nt_el));
-                hipLaunchKernelGGL(kb_tail_keys, grid_for(n), dim3(256), 0, s, n, ix->fp.csr_ptr.p, ix->fp.csr_idx.p, ix->fp.csr_val.p,
-                                   nhead.p, tail_ptr.p, ht_h, k1.p, v1.p, skip);
-                LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, k1.p, k2.p, v1.p, v2.p, (int)nt_el, 0,
-                                                                   32 + std::max(1, ceil_log2_64(std::max<int64_t>(2, ntail))), s));
-                hipLaunchKernelGGL(kb_postings, grid_for(nt_el), dim3(256), 0, s, nt_el, k2.p, v2.p, ht.post.p);
-                LOCREC_HIP_TRY(hipStreamSynchronize(s));
-            }
-            LOCREC_TRY(ht.rid.alloc((size_t)ix->nslices * 64));
-            hipLaunchKernelGGL(kb_pad_rid, grid_for((int64_t)ix->nslices * 64), dim3(256), 0, s, n, (int64_t)ix->nslices * 64, ix->rid.p,
-                               ht.rid.p);
-            // what request planning needs on the host: tail sizes per row
-            ht.tail_nnz.resize((size_t)n);
-            std::vector<int64_t> th((size_t)n);
-            LOCREC_HIP_TRY(hipMemcpyAsync(ht.tail_nnz.data(), tail_nnz.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-            LOCREC_HIP_TRY(hipMemcpyAsync(th.data(), ht.tail_hits.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-            LOCREC_HIP_TRY(hipStreamSynchronize(s));
-            ht.tail_hits_ps.assign((size_t)n + 1, 0);
-            for (int64_t r = 0; r < n; ++r) ht.tail_hits_ps[(size_t)r + 1] = ht.tail_hits_ps[(size_t)r] + th[(size_t)r];
-            ht.scan_bytes = (hpe + hce) * 4 + nt_el * 4 + (int64_t)ix->nslices * 24 + n * 8;
-            ht.h = ht_h;
-            ht.qt = ht_qt;
-            ht.ready = true;
+// head rows or category rows in the head / tail element format (knn_ht.h)
+int32_t Build::ht_sell(const DevFamily &src, const DevBuf<int32_t> &lens, const int32_t *limit, DevBuf<uint32_t> &sell,
+                DevBuf<int64_t> &off, DevBuf<int32_t> &w, int64_t &elements)
+{
+    const int rsh = 4;  // byte offset of a 16-byte plane row (knn_ht.h)
+    LOCREC_TRY(slice_layout(lens, true, w, off, elements));
+    const size_t padded = (size_t)elements + (size_t)cfg::kHtNP * 256;  // knn_scan_ht always loads kHtNP groups
+    LOCREC_TRY(sell.alloc(padded));
+    LOCREC_HIP_TRY(hipMemsetAsync(sell.p, 0, padded * 4, s));
+    LOCREC_LAUNCH(kb_sell_packed, grid_for(n), dim3(256), 0, s, n, src.csr_ptr.p, src.csr_idx.p, src.csr_val.p, limit, off.p, 0,
+                  rsh, sell.p, skip);
+    return LOCREC_OK;
+}
+
+// head / tail image (knn_ht.h) and the postings of the tail places
+int32_t Build::head_tail_image()
+{
+    const int32_t ht_h = plan.ht_h;
+    HtIndex &ht = ix->ht;
+    DevBuf<int32_t> nhead, tail_nnz;
+    DevBuf<int64_t> tail_len, tail_ptr;
+    LOCREC_TRY(alloc_each(nn, nhead, tail_nnz));
+    LOCREC_TRY(alloc_each(nn + 1, tail_len, tail_ptr));
+    LOCREC_TRY(ht.tail_hits.alloc(nn));
+    LOCREC_TRY(ht.ss.alloc((size_t)ix->nslices * 64));
+    LOCREC_HIP_TRY(hipMemsetAsync(tail_len.p, 0, (nn + 1) * 8, s));
+    LOCREC_HIP_TRY(hipMemsetAsync(ht.ss.p, 0, (size_t)ix->nslices * 64 * 4, s));
+    if (skip) LOCREC_LAUNCH(kb_freq_drop_rows, grid_for(n), dim3(256), 0, s, n, ix->fp.csr_ptr.p, ix->fp.csr_idx.p, skip, freq_new.p);
+    LOCREC_LAUNCH(kb_ht_rows, grid_for(n), dim3(256), 0, s, n, ix->fp.csr_ptr.p, ix->fp.csr_idx.p, ix->fp.csr_val.p,
+                  ix->fc.csr_ptr.p, ix->fc.csr_val.p, ht_h, freq_new.p, nhead.p, tail_nnz.p, tail_len.p, ht.tail_hits.p, ht.ss.p, skip);
+    LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, tail_len.p, tail_ptr.p, (int)(n + 1), s));
+    int64_t hpe = 0, hce = 0;
+    LOCREC_TRY(ht_sell(ix->fp, nhead, nhead.p, ht.p_sell, ht.p_off, ht.p_w, hpe));
+    LOCREC_TRY(ht_sell(ix->fc, nnz_c, nullptr, ht.c_sell, ht.c_off, ht.c_w, hce));
+    if (hpe / 4 >= ((int64_t)1 << 32) || hce / 4 >= ((int64_t)1 << 32)) return LOCREC_OK;  // (the handle stays without the form)
+    LOCREC_TRY(ht.desc.alloc((size_t)std::max(1, ix->nslices)));
+    LOCREC_LAUNCH(kb_desc, grid_for(ix->nslices), dim3(256), 0, s, n, ix->nslices, ht.p_off.p, ht.p_w.p, ht.c_off.p, ht.c_w.p,
+                  nhead.p, nnz_c.p, skip, ix->ht_round4 ? 1 : 0, ht.desc.p);
+    {
+        // words per tile knn_scan_ht multiplies (locrec_knn_ht_multiplied_words): 64 lanes x the slices' counts
+        std::vector<uint4> hd((size_t)ix->nslices);
+        LOCREC_HIP_TRY(hipMemcpyAsync(hd.data(), ht.desc.p, (size_t)ix->nslices * sizeof(uint4), hipMemcpyDeviceToHost, s));
+        LOCREC_HIP_TRY(hipStreamSynchronize(s));
+        ht.mult_words = 0;
+        ht.slice_cnt.clear();
+        for (const uint4 &d : hd) {
+            ht.mult_words += 64 * (int64_t)((d.w & 0xFFFFu) + (d.w >> 16));
+            ht.slice_cnt.push_back(d.w);
         }
-        LOCREC_HIP_TRY(hipGetLastError());
+    }
+    LOCREC_TRY(ht.cold.alloc(cfg::kHtColdBytes));
+    // postings of the tail places: (place, row) keys, radix-sorted -> rows ascending inside a place
+    int64_t nt_el = 0;
+    LOCREC_READ_BACK(nt_el, tail_ptr.p + n, s);
+    const int64_t ntail = std::max<int64_t>(0, (int64_t)p_dim - ht_h);
+    LOCREC_TRY(ht.post.alloc((size_t)std::max<int64_t>(1, nt_el)));
+    LOCREC_TRY(ht.post_ptr.alloc((size_t)ntail + 1));
+    {
+        DevBuf<int64_t> cnt;
+        LOCREC_TRY(cnt.alloc((size_t)ntail + 1));
+        LOCREC_HIP_TRY(hipMemsetAsync(cnt.p, 0, ((size_t)ntail + 1) * 8, s));
+        if (ntail > 0) LOCREC_LAUNCH(kb_tail_freq, grid_for(ntail), dim3(256), 0, s, ntail, freq_new.p, ht_h, cnt.p);
+        LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, cnt.p, ht.post_ptr.p, (int)(ntail + 1), s));
+        LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    }
+    if (nt_el > 0) {
+        DevBuf<uint64_t> k1, k2;
+        DevBuf<uint32_t> v1, v2;
+        LOCREC_TRY(alloc_each((size_t)nt_el, k1, k2, v1, v2));
+        LOCREC_LAUNCH(kb_tail_keys, grid_for(n), dim3(256), 0, s, n, ix->fp.csr_ptr.p, ix->fp.csr_idx.p, ix->fp.csr_val.p,
+                      nhead.p, tail_ptr.p, ht_h, k1.p, v1.p, skip);
+        LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, k1.p, k2.p, v1.p, v2.p, (int)nt_el, 0,
+                                            32 + std::max(1, ceil_log2_64(std::max<int64_t>(2, ntail))), s));
+        LOCREC_LAUNCH(kb_postings, grid_for(nt_el), dim3(256), 0, s, nt_el, k2.p, v2.p, ht.post.p);
+        LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    }
+    LOCREC_TRY(ht.rid.alloc((size_t)ix->nslices * 64));
+    LOCREC_LAUNCH(kb_pad_rid, grid_for((int64_t)ix->nslices * 64), dim3(256), 0, s, n, (int64_t)ix->nslices * 64, ix->rid.p,
+                  ht.rid.p);
+    // what request planning needs on the host: tail sizes per row
+    ht.tail_nnz.resize((size_t)n);
+    std::vector<int64_t> th((size_t)n);
+    LOCREC_HIP_TRY(hipMemcpyAsync(ht.tail_nnz.data(), tail_nnz.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    LOCREC_HIP_TRY(hipMemcpyAsync(th.data(), ht.tail_hits.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    ht.tail_hits_ps.assign((size_t)n + 1, 0);
+    for (int64_t r = 0; r < n; ++r) ht.tail_hits_ps[(size_t)r + 1] = ht.tail_hits_ps[(size_t)r] + th[(size_t)r];
+    ht.scan_bytes = (hpe + hce) * 4 + nt_el * 4 + (int64_t)ix->nslices * 24 + n * 8;
+    ht.h = ht_h;
+    ht.qt = cfg::kHtQt;
+    ht.ready = true;
+    return LOCREC_OK;
+}
+
+// ratings CSR in row order and its place-major transpose
+int32_t Build::ratings_and_transpose()
+{
+    const int64_t ne = r_ptr ? re : pe;
+    const size_t nee = (size_t)std::max<int64_t>(1, ne);
+    LOCREC_TRY(ix->r_ptr.alloc(nn + 1));
+    LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, len_r.p, ix->r_ptr.p, (int)(n + 1), s));
+    LOCREC_TRY(alloc_each(nee, ix->r_place, ix->r_rating));
+    if (n > 0 && ne > 0) {
+        if (r_ptr) {
+            LOCREC_LAUNCH(kb_gather_ratings, grid_for(n), dim3(256), 0, s, n, order.p, r_ptr, ix->r_ptr.p, r_place, r_rating,
+                          ix->r_place.p, ix->r_rating.p);
+        } else {  // the place vectors themselves: caller's indices and values, in row order (the row's ORIGINAL element order)
+            CsrKeys keys;
+            DevBuf<int32_t> oi;
+            LOCREC_TRY(keys_to_csr(keys, p_ptr, p_idx, p_val, ne, ix->r_ptr.p, nullptr, oi, true, ix->r_rating.p));
+            LOCREC_LAUNCH(kb_default_ratings, grid_for(ne), dim3(256), 0, s, ne, oi.p, ix->r_place.p);
+            LOCREC_HIP_TRY(hipStreamSynchronize(s));
+        }
+    }
+    {
+        DevBuf<int64_t> mxb;
+        LOCREC_TRY(mxb.alloc(1));
+        if (n > 0) {
+            LOCREC_PRIM(tmp, prim::reduce(p_, bytes_, len_r.p, mxb.p, (int)n, MaxI64(), (int64_t)0, s));
+            LOCREC_READ_BACK(ix->max_r_nnz, mxb.p, s);
+        }
+    }
+    // distinct places, ascending
+    DevBuf<uint64_t> pk, pk2, uk;
+    DevBuf<int64_t> nuniq;
+    LOCREC_TRY(alloc_each(nee, pk, pk2, uk));
+    LOCREC_TRY(nuniq.alloc(1));
+    int64_t ncp = 0;
+    if (ne > 0) {
+        LOCREC_LAUNCH(iota_keys, grid_for(ne), dim3(256), 0, s, ne, ix->r_place.p, pk.p, (uint32_t *)nullptr);
+        LOCREC_PRIM(tmp, prim::sort_keys(p_, bytes_, pk.p, pk2.p, (int)ne, 0, 64, s));
+        LOCREC_PRIM(tmp, prim::unique(p_, bytes_, pk2.p, uk.p, nuniq.p, (int)ne, s));
+        LOCREC_READ_BACK(ncp, nuniq.p, s);
+    }
+    LOCREC_TRY(ix->cplace_dev.alloc((size_t)std::max<int64_t>(1, ncp)));
+    if (ncp > 0) LOCREC_LAUNCH(unkey_ids, grid_for(ncp), dim3(256), 0, s, ncp, uk.p, ix->cplace_dev.p);
+    ix->cplace_ids.resize((size_t)ncp);
+    if (ncp > 0) LOCREC_HIP_TRY(hipMemcpyAsync(ix->cplace_ids.data(), ix->cplace_dev.p, (size_t)ncp * 8, hipMemcpyDeviceToHost, s));
+    // place index of every rating row, and the transpose (rows ascending inside a place: a fixed order)
+    LOCREC_TRY(ix->r_pidx.alloc(nee));
+    LOCREC_TRY(ix->cp_ptr.alloc((size_t)ncp + 1));
+    LOCREC_TRY(alloc_each(nee, ix->cp_row, ix->cp_rating));
+    if (ne > 0) {
+        DevBuf<uint32_t> tv, tv2;
+        LOCREC_TRY(alloc_each(nee, tv, tv2));
+        LOCREC_LAUNCH(kb_place_index, grid_for(n), dim3(256), 0, s, n, ix->r_ptr.p, ix->r_place.p, ix->cplace_dev.p, ncp,
+                      ix->r_pidx.p, pk.p, tv.p);
+        LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, pk.p, pk2.p, tv.p, tv2.p, (int)ne, 0, 64, s));
+        LOCREC_LAUNCH(kb_transpose_out, grid_for(ne), dim3(256), 0, s, ne, pk2.p, tv2.p, ix->r_rating.p, ix->cp_row.p,
+                      ix->cp_rating.p);
+        LOCREC_LAUNCH(kb_cp_ptr, grid_for(ncp + 1), dim3(256), 0, s, ncp, ne, pk2.p, ix->cp_ptr.p);
+    } else {
+        LOCREC_HIP_TRY(hipMemsetAsync(ix->cp_ptr.p, 0, ((size_t)ncp + 1) * 8, s));
+    }
+    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    return LOCREC_OK;
+}
+
+}  // namespace
+
+namespace locrec {
+
+// The whole build.  Every pointer is a DEVICE pointer valid on the current device; r_ptr may be null
+// (ratings = the place vectors themselves, what RatingVectorsBuilderMain.scala:41-73 writes).
+int32_t knn_build_device(int64_t n, const int64_t *ids, const int64_t *p_ptr, const int32_t *p_idx, const double *p_val,
+                         int32_t p_dim, const int64_t *c_ptr, const int32_t *c_idx, const double *c_val, int32_t c_dim,
+                         const int64_t *r_ptr, const int64_t *r_place, const int64_t *r_rating, locrec_knn_index **out)
+{
+    std::unique_ptr<locrec_knn_index> ix;
+    Build b{n, ids, p_ptr, c_ptr, r_ptr, r_place, r_rating, p_idx, c_idx, p_val, c_val, p_dim, c_dim};
+    LOCREC_TRY(knn_build_open(n, ids, p_ptr, c_ptr, p_dim, c_dim, out, ix, b.in));
+    b.ix = ix.get();
+    b.s = ix->stream;
+    KnnBuildLap lap{"knn_build_device", ix->stream};
+    LOCREC_TRY(b.validate_and_plan());
+    lap("validation");
+    LOCREC_TRY(b.renumber_by_popularity());
+    lap("popularity");
+    LOCREC_TRY(b.order_rows_and_rank_ids());
+    lap("row order + id rank");
+    LOCREC_TRY(b.list_wide_rows());
+    LOCREC_TRY(b.csr_of(ix->fp, p_ptr, p_idx, p_val, b.pe, b.len_p, b.plan.use_pop ? b.new_of_old.p : nullptr));
+    LOCREC_TRY(b.csr_of(ix->fc, c_ptr, c_idx, c_val, b.ce, b.len_c, nullptr));
+    lap("CSR (gather, renumber, sort)");
+    LOCREC_TRY(b.sell_and_side_images());
+    lap("SELL images + norms");
+    if (b.plan.want_ht) {
+        LOCREC_TRY(b.head_tail_image());
         lap("head / tail image + postings");
     }
-
-    // ---- ratings CSR in row order and its place-major transpose
-    {
-        const int64_t ne = r_ptr ? re : pe;
-        const size_t nee = (size_t)std::max<int64_t>(1, ne);
-        LOCREC_TRY(ix->r_ptr.alloc(nn + 1));
-        LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, len_r.p, ix->r_ptr.p, (int)(n + 1), s));
-        LOCREC_TRY(ix->r_place.alloc(nee));
-        LOCREC_TRY(ix->r_rating.alloc(nee));
-        if (n > 0 && ne > 0) {
-            if (r_ptr) {
-                hipLaunchKernelGGL(kb_gather_ratings, grid_for(n), dim3(256), 0, s, n, order.p, r_ptr, ix->r_ptr.p, r_place, r_rating,
-                                   ix->r_place.p, ix->r_rating.p);
-            } else {  // the place vectors themselves: caller's indices and values, in row order (the row's ORIGINAL element order)
-                DevBuf<uint64_t> k1;
-                DevBuf<uint32_t> v1;
-                LOCREC_TRY(k1.alloc(nee));
-                LOCREC_TRY(v1.alloc(nee));
-                hipLaunchKernelGGL(kb_place_keys, grid_for(n), dim3(256), 0, s, n, order.p, p_ptr, ix->r_ptr.p, p_idx, nullptr, k1.p, v1.p,
-                                   nullptr);
-                DevBuf<int32_t> oi;
-                LOCREC_TRY(oi.alloc(nee));
-                hipLaunchKernelGGL(kb_finish_csr, grid_for(ne), dim3(256), 0, s, ne, k1.p, v1.p, p_val, oi.p, ix->r_rating.p);
-                hipLaunchKernelGGL(kb_default_ratings, grid_for(ne), dim3(256), 0, s, ne, oi.p, ix->r_place.p);
-                LOCREC_HIP_TRY(hipStreamSynchronize(s));
-            }
-        }
-        {
-            int64_t *mx = nullptr;
-            DevBuf<int64_t> mxb;
-            LOCREC_TRY(mxb.alloc(1));
-            mx = mxb.p;
-            if (n > 0) {
-                LOCREC_PRIM(tmp, prim::reduce(p_, bytes_, len_r.p, mx, (int)n, MaxI64(), (int64_t)0, s));
-                LOCREC_HIP_TRY(hipMemcpyAsync(&ix->max_r_nnz, mx, 8, hipMemcpyDeviceToHost, s));
-                LOCREC_HIP_TRY(hipStreamSynchronize(s));
-            }
-        }
-        // distinct places, ascending
-        DevBuf<uint64_t> pk, pk2, uk;
-        DevBuf<int64_t> nuniq;
-        LOCREC_TRY(pk.alloc(nee));
-        LOCREC_TRY(pk2.alloc(nee));
-        LOCREC_TRY(uk.alloc(nee));
-        LOCREC_TRY(nuniq.alloc(1));
-        int64_t ncp = 0;
-        if (ne > 0) {
-            hipLaunchKernelGGL(iota_keys, grid_for(ne), dim3(256), 0, s, ne, ix->r_place.p, pk.p, (uint32_t *)nullptr);
-            LOCREC_PRIM(tmp, prim::sort_keys(p_, bytes_, pk.p, pk2.p, (int)ne, 0, 64, s));
-            LOCREC_PRIM(tmp, prim::unique(p_, bytes_, pk2.p, uk.p, nuniq.p, (int)ne, s));
-            LOCREC_HIP_TRY(hipMemcpyAsync(&ncp, nuniq.p, 8, hipMemcpyDeviceToHost, s));
-            LOCREC_HIP_TRY(hipStreamSynchronize(s));
-        }
-        LOCREC_TRY(ix->cplace_dev.alloc((size_t)std::max<int64_t>(1, ncp)));
-        if (ncp > 0) hipLaunchKernelGGL(unkey_ids, grid_for(ncp), dim3(256), 0, s, ncp, uk.p, ix->cplace_dev.p);
-        ix->cplace_ids.resize((size_t)ncp);
-        if (ncp > 0) LOCREC_HIP_TRY(hipMemcpyAsync(ix->cplace_ids.data(), ix->cplace_dev.p, (size_t)ncp * 8, hipMemcpyDeviceToHost, s));
-        // place index of every rating row, and the transpose (rows ascending inside a place: a fixed order)
-        LOCREC_TRY(ix->r_pidx.alloc(nee));
-        LOCREC_TRY(ix->cp_ptr.alloc((size_t)ncp + 1));
-        LOCREC_TRY(ix->cp_row.alloc(nee));
-        LOCREC_TRY(ix->cp_rating.alloc(nee));
-        if (ne > 0) {
-            DevBuf<uint32_t> tv, tv2;
-            LOCREC_TRY(tv.alloc(nee));
-            LOCREC_TRY(tv2.alloc(nee));
-            hipLaunchKernelGGL(kb_place_index, grid_for(n), dim3(256), 0, s, n, ix->r_ptr.p, ix->r_place.p, ix->cplace_dev.p, ncp,
-                               ix->r_pidx.p, pk.p, tv.p);
-            LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, pk.p, pk2.p, tv.p, tv2.p, (int)ne, 0, 64, s));
-            hipLaunchKernelGGL(kb_transpose_out, grid_for(ne), dim3(256), 0, s, ne, pk2.p, tv2.p, ix->r_rating.p, ix->cp_row.p,
-                               ix->cp_rating.p);
-            hipLaunchKernelGGL(kb_cp_ptr, grid_for(ncp + 1), dim3(256), 0, s, ncp, ne, pk2.p, ix->cp_ptr.p);
-        } else {
-            LOCREC_HIP_TRY(hipMemsetAsync(ix->cp_ptr.p, 0, ((size_t)ncp + 1) * 8, s));
-        }
-        LOCREC_HIP_TRY(hipStreamSynchronize(s));
-        LOCREC_HIP_TRY(hipGetLastError());
-    }
+    LOCREC_TRY(b.ratings_and_transpose());
     lap("ratings (CSR + transpose)");
     *out = ix.release();
     return LOCREC_OK;

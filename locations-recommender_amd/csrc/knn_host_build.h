@@ -3,6 +3,8 @@
 // A fragment of knn.hip's translation unit: included by knn.hip at file scope, after its helper namespaces.
 #pragma once
 
+#include "knn_build_open.h"
+
 // Per-row format fallback (see knn_build.hip): the wide rows are all padding in the packed SELL images.  The image is
 // built from every row (build_family_device) and the wide rows' element groups are blanked afterwards.
 __global__ void knn_host_blank_rows(int32_t nw, const int32_t *wide_rows, const int64_t *sell_off, const int32_t *sell_w, uint32_t *sell)
@@ -25,32 +27,10 @@ static int32_t knn_create_host(
     const int64_t *r_rowptr, const int64_t *r_place, const int64_t *r_rating,
     locrec_knn_index **out) try
 {
-    if (!out) return fail(LOCREC_E_INVALID_ARG, "out_index is NULL");
-    *out = nullptr;
-    if (n < 0 || n >= ((int64_t)1 << 31) - 64) return fail(LOCREC_E_INVALID_ARG, "bad person count");
-    if (n > 0 && (!person_ids || !p_rowptr || !c_rowptr)) return fail(LOCREC_E_INVALID_ARG, "NULL input array");
-    if (p_dim <= 0 || c_dim <= 0) return fail(LOCREC_E_INVALID_ARG, "vector sizes must be positive");
-    LOCREC_TRY(ensure_device());
-    std::unique_ptr<locrec_knn_index> ix(new (std::nothrow) locrec_knn_index);
-    if (!ix) return fail(LOCREC_E_OOM, "host allocation failed");
-    LOCREC_HIP_TRY(hipGetDevice(&ix->device));
-    LOCREC_HIP_TRY(hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking));
-    ix->own_stream = true;
-    ix->n = n;
-    ix->nslices = (int32_t)((n + 63) / 64);
-    ix->cand_slice0 = 0;
-    ix->cand_slice1 = ix->nslices;
-    knn_read_env(ix.get());
-    const bool force_generic = ix->force_generic;
-
-    const bool dbg_t = debug_env("LOCREC_DEBUG_TIMING") != nullptr;
-    auto t_last = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (!dbg_t) return;
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[locrec knn_create] %-28s %.3f s\n", what, std::chrono::duration<double>(now - t_last).count());
-        t_last = now;
-    };
+    std::unique_ptr<locrec_knn_index> ix;
+    KnnFormatInput fin;
+    LOCREC_TRY(knn_build_open(n, person_ids, p_rowptr, c_rowptr, p_dim, c_dim, out, ix, fin));
+    KnnBuildLap lap{"knn_create", nullptr};
     // ---- validation (SparseVector invariants, RatingVectorsBuilder.scala:74-77)
     // wide_in[r] (OR-ed over both families), lvmax / lssmax (the maxima over the rows that are not wide): as kb_validate
     std::vector<unsigned char> wide_in((size_t)n, 0);
@@ -90,36 +70,21 @@ static int32_t knn_create_host(
         }
         return LOCREC_OK;
     };
-    bool integral = true;
-    double pvmax = 0, cvmax = 0, pss = 0, css = 0, plvmax = 0, clvmax = 0, plss = 0, clss = 0;
-    LOCREC_TRY(check_family("place", p_rowptr, p_idx, p_val, p_dim, integral, pvmax, pss, plvmax, plss));
-    LOCREC_TRY(check_family("category", c_rowptr, c_idx, c_val, c_dim, integral, cvmax, css, clvmax, clss));
-    // ---- per-row format fallback: the same decision as knn_build.hip (at most min(4096, max(256, n / 512)) wide rows,
-    // and fewer than n), so that both builds give one index
-    int64_t n_wide = 0;
-    const bool any_wide = pvmax >= 256.0 || cvmax >= 256.0 || pss >= 65536.0 || css >= 65536.0;
-    if (any_wide && integral && !force_generic && !ix->no_row_fallback && !ix->no_pack16 && !ix->no_ht && n < ((int64_t)1 << 24) && c_dim <= kHtCatRows &&
-        p_dim < (1 << 20) - 1) {  // (a place dimension no packed format holds: GENERIC keeps every row in its image)
-        for (unsigned char w : wide_in) n_wide += w ? 1 : 0;
-        const int64_t cap = std::min<int64_t>(4096, std::max<int64_t>(256, n / 512));
-        if (n_wide > 0 && n_wide <= cap && n_wide < n) {
-            pvmax = plvmax;
-            cvmax = clvmax;
-            pss = plss;
-            css = clss;
-        } else {
-            n_wide = 0;
-        }
-    }
-    const int p_vbits = std::min(24, 32 - ceil_log2i(p_dim));
-    const int c_vbits = std::min(24, 32 - ceil_log2i(c_dim));
-    // exact u32 dots need every dot < 2^32; |dot| <= sqrt(ss_a * ss_b) <= max ss
-    ix->packed = !force_generic && integral && p_dim < (1 << 20) - 1 && c_dim < (1 << 20) - 1 &&
-                 pvmax < (double)(1u << p_vbits) && cvmax < (double)(1u << c_vbits) &&
-                 pss < 4294967296.0 && css < 4294967296.0;
-
-    ix->pack16 = ix->packed && pss < 65536.0 && css < 65536.0 && pvmax < 65536.0 && cvmax < 65536.0 &&
-                 !ix->no_pack16;
+    KnnMaxima &all = fin.all, &narrow = fin.narrow;
+    LOCREC_TRY(check_family("place", p_rowptr, p_idx, p_val, p_dim, fin.integral, all.pvmax, all.pss, narrow.pvmax, narrow.pss));
+    LOCREC_TRY(check_family("category", c_rowptr, c_idx, c_val, c_dim, fin.integral, all.cvmax, all.css, narrow.cvmax, narrow.css));
+    // ---- format and kernel path: knn_format_plan.h, the decision knn_build.hip takes too, so that both builds give one index
+    int64_t wide_count = 0;
+    if (knn_row_fallback_eligible(fin))
+        for (unsigned char w : wide_in) wide_count += w ? 1 : 0;
+    const KnnFormatPlan plan = knn_format_plan(fin, wide_count);
+    const int64_t n_wide = plan.n_wide;
+    const int p_vbits = plan.p_vbits, c_vbits = plan.c_vbits;
+    const bool want_ht = plan.want_ht;
+    const int32_t ht_h = plan.ht_h, pop_h = plan.pop_h, key_h = plan.key_h;
+    const int ht_qt = cfg::kHtQt;
+    ix->packed = plan.packed;
+    ix->pack16 = plan.pack16;
 
     lap("validation");
     // ---- popularity split of the place family (PACKED formats, hashed panel): place indices are
@@ -127,17 +92,8 @@ static int32_t knn_create_host(
     // unchanged, and integer sums do not depend on the order of the terms), so that a row's popular
     // indices come first.  new_of_old is empty when the split is not used.
     std::vector<int32_t> new_of_old;
-    std::vector<int32_t> npop;  // per input row: number of indices that become < pop_h
-    int32_t pop_h = 0;
-    // head / tail form (knn_ht.h): PACK16 data whose values fit a byte and whose rows fit 24 bits
-    const int ht_qt = 16;
-    int32_t ht_h = std::min<int32_t>(p_dim, 512);
-    if (ix->env_ht_h > 0) ht_h = std::min<int32_t>(p_dim, ix->env_ht_h);  // tuning
-    ht_h = std::min<int32_t>(ht_h, 65536 / (2 * ht_qt));  // the element's low half is the panel row's byte offset
-    const bool want_ht = ix->pack16 && !ix->no_ht && !force_generic && n > 0 && n < ((int64_t)1 << 24) && pvmax < 256.0 &&
-                         cvmax < 256.0 && c_dim <= kHtCatRows;
-    if (ix->packed && !ix->no_pop && n > 0 &&
-        (ix->force_hash || (size_t)p_dim * 2 > (size_t)kDirectMaxBytes || want_ht)) {
+    std::vector<int32_t> npop;  // per input row: number of indices that become < key_h
+    if (plan.use_pop) {
         std::vector<int64_t> freq((size_t)p_dim, 0);
         for (int64_t e = 0; e < p_rowptr[n]; ++e) ++freq[p_idx[e]];
         std::vector<int32_t> by_freq((size_t)p_dim);
@@ -145,11 +101,7 @@ static int32_t knn_create_host(
         std::stable_sort(by_freq.begin(), by_freq.end(), [&](int32_t a, int32_t b) { return freq[a] > freq[b]; });
         new_of_old.resize((size_t)p_dim);
         for (int32_t i = 0; i < p_dim; ++i) new_of_old[by_freq[i]] = i;
-        pop_h = std::min<int32_t>(p_dim, kPopTable);
-        if (ix->env_pop_h > 0) pop_h = std::min<int32_t>(p_dim, ix->env_pop_h);  // tuning
-        // third sort key of the rows: their count of popular indices - of HEAD indices when the head / tail
-        // form is built, so that the head rows of a slice have (nearly) one length
-        const int32_t key_h = want_ht ? ht_h : pop_h;
+        // third sort key of the rows: their count of indices below key_h
         npop.assign((size_t)n, 0);
         for (int64_t r = 0; r < n; ++r)
             for (int64_t e = p_rowptr[r]; e < p_rowptr[r + 1]; ++e) npop[r] += new_of_old[p_idx[e]] < key_h ? 1 : 0;

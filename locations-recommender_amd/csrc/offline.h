@@ -1,13 +1,16 @@
 // offline.h -- what every offline device step shares (knn_build.hip, prep.hip, dedup.hip, rank_batch.hip's host side,
-// region_sets.hip, sg_create_device.hip): the temporary storage of the rocPRIM calls, launch grids, the order-preserving
-// keys of signed ids, the lower-bound bisection, the phase clock and the distinct ids of a column.  Nothing here knows
-// about a caller's columns (prep_cols.h) or about places (place_grid.h).  Everything lives in an unnamed namespace: the
-// text is shared, each translation unit compiles its own instance.  Every helper that launches checks the launch.
+// region_sets.hip, sample.hip, sg_create_device.hip): the checked launch and the one-value read-back, the temporary
+// storage of the rocPRIM calls, launch grids, the order-preserving keys of signed ids, the lower-bound bisection, the
+// phase clock and the distinct ids of a column.  Nothing here knows about a caller's columns (prep_cols.h) or about
+// places (place_grid.h).  Everything lives in an unnamed namespace: the text is shared, each translation unit compiles
+// its own instance.  Every launch here AND in the units above goes through LOCREC_LAUNCH: a rejected launch is an
+// error of the call that made it, not of whichever HIP call comes next (tests/test_offline_launches.py).
 #pragma once
 
 #include "dev_prims.h"
 
 #include <algorithm>
+#include <type_traits>
 
 #include "common.h"
 
@@ -30,6 +33,31 @@ struct Temp {
         p_ = (tmp).buf.p;                             \
         LOCREC_HIP_TRY((call_with_args));             \
     } while (0)
+
+// The one way these units launch a kernel: launch, then return hipGetLastError's verdict with the site's file and line.
+// `kern` may be a template instance.  What a unit tolerates to fail it clears on the spot, so nothing stale ends here.
+#define LOCREC_LAUNCH(kern, grid, block, lds, stream, ...)                      \
+    do {                                                                        \
+        hipLaunchKernelGGL(kern, grid, block, lds, stream, __VA_ARGS__);        \
+        LOCREC_HIP_TRY(hipGetLastError());                                      \
+    } while (0)
+
+// one value (or small struct, or array) from the device to the host, and wait for it
+#define LOCREC_READ_BACK(dest, dev, stream)                                                                    \
+    do {                                                                                                       \
+        static_assert(!std::is_pointer_v<std::remove_reference_t<decltype(dest)>>, "the value, not its address"); \
+        LOCREC_HIP_TRY(hipMemcpyAsync(&(dest), (dev), sizeof(dest), hipMemcpyDeviceToHost, (stream)));         \
+        LOCREC_HIP_TRY(hipStreamSynchronize(stream));                                                          \
+    } while (0)
+
+// count elements in each of the buffers, in the order given; stops at the first failure
+template <class... Bufs>
+int32_t alloc_each(size_t count, Bufs &...bufs)
+{
+    int32_t st = LOCREC_OK;
+    ((st = st == LOCREC_OK ? bufs.alloc(count) : st), ...);
+    return st;
+}
 
 inline dim3 grid_for(int64_t n, int threads = 256) { return dim3((unsigned)std::max<int64_t>(1, (n + threads - 1) / threads)); }
 
@@ -120,15 +148,12 @@ int32_t distinct_ids(const int64_t *col, int64_t n, Temp &tmp, hipStream_t s, De
     LOCREC_TRY(k0.alloc((size_t)n));
     LOCREC_TRY(k1.alloc((size_t)n));
     LOCREC_TRY(count_dev.alloc(1));
-    hipLaunchKernelGGL(iota_keys, grid_for(n), dim3(256), 0, s, n, col, k0.p, (uint32_t *)nullptr);
-    LOCREC_HIP_TRY(hipGetLastError());
+    LOCREC_LAUNCH(iota_keys, grid_for(n), dim3(256), 0, s, n, col, k0.p, (uint32_t *)nullptr);
     LOCREC_PRIM(tmp, prim::sort_keys(p_, bytes_, k0.p, k1.p, (size_t)n, 0, 64, s));
     LOCREC_PRIM(tmp, prim::unique(p_, bytes_, k1.p, k0.p, count_dev.p, (size_t)n, s));
-    LOCREC_HIP_TRY(hipMemcpyAsync(count, count_dev.p, sizeof *count, hipMemcpyDeviceToHost, s));
-    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    LOCREC_READ_BACK(*count, count_dev.p, s);
     LOCREC_TRY(out.alloc((size_t)*count));
-    hipLaunchKernelGGL(unkey_ids, grid_for(*count), dim3(256), 0, s, (int64_t)*count, k0.p, out.p);
-    LOCREC_HIP_TRY(hipGetLastError());
+    LOCREC_LAUNCH(unkey_ids, grid_for(*count), dim3(256), 0, s, (int64_t)*count, k0.p, out.p);
     LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (the keys are released on return)
     return LOCREC_OK;
 }

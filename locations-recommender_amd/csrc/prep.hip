@@ -41,13 +41,10 @@ struct SortedRows {
 // two stable LSD passes: by entity, then by person
 int32_t sort_person_entity(int64_t n, const int64_t *person, const int64_t *entity, SortedRows &S, Temp &tmp, hipStream_t s)
 {
-    LOCREC_TRY(S.k0.alloc((size_t)n));
-    LOCREC_TRY(S.k1.alloc((size_t)n));
-    LOCREC_TRY(S.r0.alloc((size_t)n));
-    LOCREC_TRY(S.r1.alloc((size_t)n));
-    hipLaunchKernelGGL(iota_keys, grid_for(n), dim3(256), 0, s, n, entity, S.k0.p, S.r0.p);
+    LOCREC_TRY(alloc_each((size_t)n, S.k0, S.k1, S.r0, S.r1));
+    LOCREC_LAUNCH(iota_keys, grid_for(n), dim3(256), 0, s, n, entity, S.k0.p, S.r0.p);
     LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, S.k0.p, S.k1.p, S.r0.p, S.r1.p, (int)n, 0, 64, s));
-    hipLaunchKernelGGL(gather_id_keys, grid_for(n), dim3(256), 0, s, n, person, S.r1.p, S.k0.p);
+    LOCREC_LAUNCH(gather_id_keys, grid_for(n), dim3(256), 0, s, n, person, S.r1.p, S.k0.p);
     LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, S.k0.p, S.k1.p, S.r1.p, S.r0.p, (int)n, 0, 64, s));
     S.rows = S.r0.p;
     return LOCREC_OK;
@@ -155,32 +152,25 @@ int32_t rank_keep(int64_t g, const uint32_t *srank, const uint64_t *cnt, int64_t
 {
     DevBuf<uint32_t> gid0, gid1, pmark, rmark, pstart, rstart;
     DevBuf<uint64_t> key0, key1;
-    LOCREC_TRY(gid0.alloc((size_t)g));
-    LOCREC_TRY(gid1.alloc((size_t)g));
-    LOCREC_TRY(key0.alloc((size_t)g));
-    LOCREC_TRY(key1.alloc((size_t)g));
-    LOCREC_TRY(pmark.alloc((size_t)g));
-    LOCREC_TRY(rmark.alloc((size_t)g));
-    LOCREC_TRY(pstart.alloc((size_t)g));
-    LOCREC_TRY(rstart.alloc((size_t)g));
+    LOCREC_TRY(alloc_each((size_t)g, gid0, gid1, key0, key1, pmark, rmark, pstart, rstart));
     const uint32_t *sorted = gid1.p;
     if (!wide_counts) {
-        hipLaunchKernelGGL(pr_rank_keys, grid_for(g), dim3(256), 0, s, g, srank, cnt, key0.p, gid0.p);
+        LOCREC_LAUNCH(pr_rank_keys, grid_for(g), dim3(256), 0, s, g, srank, cnt, key0.p, gid0.p);
         LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, key0.p, key1.p, gid0.p, gid1.p, (int)g, 0, 64, s));
     } else {  // stable LSD: by count descending, then by source (pmark / rmark serve as the 32-bit key buffers)
-        hipLaunchKernelGGL(pr_rank_keys_wide, grid_for(g), dim3(256), 0, s, g, cnt, key0.p, gid0.p);
+        LOCREC_LAUNCH(pr_rank_keys_wide, grid_for(g), dim3(256), 0, s, g, cnt, key0.p, gid0.p);
         LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, key0.p, key1.p, gid0.p, gid1.p, (int)g, 0, 64, s));
-        hipLaunchKernelGGL(pr_rank_source_keys, grid_for(g), dim3(256), 0, s, g, srank, gid1.p, pmark.p);
+        LOCREC_LAUNCH(pr_rank_source_keys, grid_for(g), dim3(256), 0, s, g, srank, gid1.p, pmark.p);
         LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, pmark.p, rmark.p, gid1.p, gid0.p, (int)g, 0, 32, s));
         sorted = gid0.p;
     }
     if (!wide_counts)
-        hipLaunchKernelGGL(pr_run_marks_packed, grid_for(g), dim3(256), 0, s, g, key1.p, pmark.p, rmark.p);
+        LOCREC_LAUNCH(pr_run_marks_packed, grid_for(g), dim3(256), 0, s, g, key1.p, pmark.p, rmark.p);
     else
-        hipLaunchKernelGGL(pr_run_marks, grid_for(g), dim3(256), 0, s, g, sorted, srank, cnt, pmark.p, rmark.p);
+        LOCREC_LAUNCH(pr_run_marks, grid_for(g), dim3(256), 0, s, g, sorted, srank, cnt, pmark.p, rmark.p);
     LOCREC_PRIM(tmp, prim::inclusive_max(p_, bytes_, pmark.p, pstart.p, (int)g, s));
     LOCREC_PRIM(tmp, prim::inclusive_max(p_, bytes_, rmark.p, rstart.p, (int)g, s));
-    hipLaunchKernelGGL(pr_keep_top, grid_for(g), dim3(256), 0, s, g, pstart.p, rstart.p, sorted, top_n, keep);
+    LOCREC_LAUNCH(pr_keep_top, grid_for(g), dim3(256), 0, s, g, pstart.p, rstart.p, sorted, top_n, keep);
     LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, keep, pos, (int)g, s));
     uint32_t last_pos = 0, last_keep = 0;
     LOCREC_HIP_TRY(hipMemcpyAsync(&last_pos, pos + (g - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -202,11 +192,10 @@ int32_t kept_totals(int64_t g, const uint32_t *srank, const uint64_t *cnt, const
 {
     DevBuf<uint64_t> kept;
     DevBuf<uint32_t> sources, nsources;
-    LOCREC_TRY(kept.alloc((size_t)g));
-    LOCREC_TRY(sources.alloc((size_t)g));
+    LOCREC_TRY(alloc_each((size_t)g, kept, sources));
     LOCREC_TRY(nsources.alloc(1));
     LOCREC_TRY(totals.alloc((size_t)g));
-    hipLaunchKernelGGL(pr_kept_counts, grid_for(g), dim3(256), 0, s, g, keep, cnt, kept.p);
+    LOCREC_LAUNCH(pr_kept_counts, grid_for(g), dim3(256), 0, s, g, keep, cnt, kept.p);
     LOCREC_PRIM(tmp, prim::sum_by_key(p_, bytes_, srank, kept.p, (size_t)g, sources.p, totals.p, nsources.p, s));
     LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (kept / sources are released on return)
     return LOCREC_OK;
@@ -237,31 +226,24 @@ int32_t calc_ratings(int64_t n, const int64_t *person, const int64_t *entity, in
     LOCREC_TRY(sort_person_entity(n, person, entity, S, tmp, s));
     DevBuf<unsigned char> gfirst;
     DevBuf<uint32_t> pfirst, prank, gstart, ng_dev;
-    LOCREC_TRY(gfirst.alloc((size_t)n));
-    LOCREC_TRY(pfirst.alloc((size_t)n));
-    LOCREC_TRY(prank.alloc((size_t)n));
-    LOCREC_TRY(gstart.alloc((size_t)n));
+    LOCREC_TRY(alloc_each((size_t)n, gfirst, pfirst, prank, gstart));
     LOCREC_TRY(ng_dev.alloc(1));
-    hipLaunchKernelGGL(pr_group_flags, grid_for(n), dim3(256), 0, s, n, person, entity, S.rows, gfirst.p, pfirst.p);
+    LOCREC_LAUNCH(pr_group_flags, grid_for(n), dim3(256), 0, s, n, person, entity, S.rows, gfirst.p, pfirst.p);
     LOCREC_PRIM(tmp, prim::inclusive_sum(p_, bytes_, pfirst.p, prank.p, (int)n, s));
     prim::counting_iterator<uint32_t> iota(0u);
     LOCREC_PRIM(tmp, prim::select_flagged(p_, bytes_, iota, gfirst.p, gstart.p, ng_dev.p, (int)n, s));
     uint32_t g32 = 0;
-    LOCREC_HIP_TRY(hipMemcpyAsync(&g32, ng_dev.p, sizeof g32, hipMemcpyDeviceToHost, s));
-    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    LOCREC_READ_BACK(g32, ng_dev.p, s);
     const int64_t g = g32;
 
     DevBuf<uint32_t> srank, keep, pos;
     DevBuf<uint64_t> cnt, totals;
-    LOCREC_TRY(cnt.alloc((size_t)g));
-    LOCREC_TRY(srank.alloc((size_t)g));
-    LOCREC_TRY(keep.alloc((size_t)g));
-    LOCREC_TRY(pos.alloc((size_t)g));
-    hipLaunchKernelGGL(pr_group_counts, grid_for(g), dim3(256), 0, s, g, n, gstart.p, prank.p, cnt.p, srank.p);
+    LOCREC_TRY(alloc_each((size_t)g, cnt, srank, keep, pos));
+    LOCREC_LAUNCH(pr_group_counts, grid_for(g), dim3(256), 0, s, g, n, gstart.p, prank.p, cnt.p, srank.p);
     LOCREC_TRY(rank_keep(g, srank.p, cnt.p, top_n, false, keep.p, pos.p, out_count, tmp, s));
     if (out_weight) LOCREC_TRY(kept_totals(g, srank.p, cnt.p, keep.p, totals, tmp, s));
-    hipLaunchKernelGGL(pr_emit_ratings, grid_for(g), dim3(256), 0, s, g, keep.p, pos.p, gstart.p, S.rows, person, entity,
-                       cnt.p, srank.p, totals.p, out_person, out_entity, out_rating, out_weight);
+    LOCREC_LAUNCH(pr_emit_ratings, grid_for(g), dim3(256), 0, s, g, keep.p, pos.p, gstart.p, S.rows, person, entity,
+                  cnt.p, srank.p, totals.p, out_person, out_entity, out_rating, out_weight);
     LOCREC_HIP_TRY(hipStreamSynchronize(s));
     return LOCREC_OK;
 }
@@ -329,10 +311,9 @@ int32_t calc_rating_vectors(int64_t n, const int64_t *person, const int64_t *ent
     LOCREC_TRY(range.alloc(1));
     const RangeOut init{0ull, ~0ull};
     LOCREC_HIP_TRY(hipMemcpyAsync(range.p, &init, sizeof init, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(pr_entity_range, grid_for(n), dim3(256), 0, s, n, entity, range.p);
+    LOCREC_LAUNCH(pr_entity_range, grid_for(n), dim3(256), 0, s, n, entity, range.p);
     RangeOut got;
-    LOCREC_HIP_TRY(hipMemcpyAsync(&got, range.p, sizeof got, hipMemcpyDeviceToHost, s));
-    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    LOCREC_READ_BACK(got, range.p, s);
     const int64_t max_id = id_of_key(got.max_key), min_id = id_of_key(got.min_key);
     // checkedCast (RatingVectorsBuilder.scala:36-41): of max(id) first (:27-34), then of every id (:69)
     if (max_id > std::numeric_limits<int32_t>::max() || max_id < std::numeric_limits<int32_t>::min())
@@ -347,15 +328,12 @@ int32_t calc_rating_vectors(int64_t n, const int64_t *person, const int64_t *ent
     SortedRows S;
     LOCREC_TRY(sort_person_entity(n, person, entity, S, tmp, s));
     DevBuf<uint32_t> pfirst, keep, prank, pos;
-    LOCREC_TRY(pfirst.alloc((size_t)n));
-    LOCREC_TRY(keep.alloc((size_t)n));
-    LOCREC_TRY(prank.alloc((size_t)n));
-    LOCREC_TRY(pos.alloc((size_t)n));
-    hipLaunchKernelGGL(pr_vector_flags, grid_for(n), dim3(256), 0, s, n, person, entity, S.rows, pfirst.p, keep.p);
+    LOCREC_TRY(alloc_each((size_t)n, pfirst, keep, prank, pos));
+    LOCREC_LAUNCH(pr_vector_flags, grid_for(n), dim3(256), 0, s, n, person, entity, S.rows, pfirst.p, keep.p);
     LOCREC_PRIM(tmp, prim::inclusive_sum(p_, bytes_, pfirst.p, prank.p, (int)n, s));
     LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, keep.p, pos.p, (int)n, s));
-    hipLaunchKernelGGL(pr_emit_vectors, grid_for(n), dim3(256), 0, s, n, S.rows, pfirst.p, keep.p, prank.p, pos.p, person,
-                       entity, rating, out_ids, out_rowptr, out_idx, out_val);
+    LOCREC_LAUNCH(pr_emit_vectors, grid_for(n), dim3(256), 0, s, n, S.rows, pfirst.p, keep.p, prank.p, pos.p, person,
+                  entity, rating, out_ids, out_rowptr, out_idx, out_val);
     uint32_t tail[3] = {0, 0, 0};
     LOCREC_HIP_TRY(hipMemcpyAsync(&tail[0], prank.p + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     LOCREC_HIP_TRY(hipMemcpyAsync(&tail[1], pos.p + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -364,7 +342,7 @@ int32_t calc_rating_vectors(int64_t n, const int64_t *person, const int64_t *ent
     *out_npersons = tail[0];
     *out_nnz = (int64_t)tail[1] + tail[2];
     *out_size = max_id + 1;
-    hipLaunchKernelGGL(pr_set_i64, dim3(1), dim3(1), 0, s, out_rowptr + *out_npersons, *out_nnz);
+    LOCREC_LAUNCH(pr_set_i64, dim3(1), dim3(1), 0, s, out_rowptr + *out_npersons, *out_nnz);
     return LOCREC_OK;
 }
 
@@ -490,7 +468,7 @@ try {
     hipStream_t s = nullptr;
     if (n == 0) {
         if (mem == LOCREC_MEM_DEVICE) {
-            hipLaunchKernelGGL(pr_set_i64, dim3(1), dim3(1), 0, s, out_rowptr, (int64_t)0);
+            LOCREC_LAUNCH(pr_set_i64, dim3(1), dim3(1), 0, s, out_rowptr, (int64_t)0);
             LOCREC_HIP_TRY(hipStreamSynchronize(s));
         } else {
             out_rowptr[0] = 0;
@@ -553,7 +531,7 @@ try {
         LOCREC_TRY(a.bind(source_ids[f], m, mem, s));
         LOCREC_TRY(b.bind(target_ids[f], m, mem, s));
         LOCREC_TRY(w.bind(weights[f], m, mem, s));
-        hipLaunchKernelGGL(pr_balance, grid_for(m), dim3(256), 0, s, m, a.p, b.p, w.p, betas[f], os.p + at, ot.p + at, ow.p + at);
+        LOCREC_LAUNCH(pr_balance, grid_for(m), dim3(256), 0, s, m, a.p, b.p, w.p, betas[f], os.p + at, ot.p + at, ow.p + at);
         LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (the family's staging buffers are released at the end of this iteration)
         at += m;
     }
@@ -618,32 +596,26 @@ try {
     LOCREC_TRY(err.alloc(1));
     LOCREC_HIP_TRY(hipMemsetAsync(visited.p, 0, (size_t)nr * 4, s));
     LOCREC_HIP_TRY(hipMemsetAsync(err.p, 0xFF, sizeof(LocationError), s));
-    hipLaunchKernelGGL(check_side_a, grid_for(n_visits), dim3(256), 0, s, n_visits, vt.p, visits_from, vlat.p, vlon.p, vr.p,
-                       regions.p, nr, visited.p, err.p);
-    hipLaunchKernelGGL(check_side_b, grid_for(n_places), dim3(256), 0, s, n_places, plat.p, plon.p, pr.p, regions.p, nr,
-                       visited.p, err.p);
-    LOCREC_HIP_TRY(hipGetLastError());
+    LOCREC_LAUNCH(check_side_a, grid_for(n_visits), dim3(256), 0, s, n_visits, vt.p, visits_from, vlat.p, vlon.p, vr.p,
+                  regions.p, nr, visited.p, err.p);
+    LOCREC_LAUNCH(check_side_b, grid_for(n_places), dim3(256), 0, s, n_places, plat.p, plon.p, pr.p, regions.p, nr,
+                  visited.p, err.p);
     LocationError le;
-    LOCREC_HIP_TRY(hipMemcpyAsync(&le, err.p, sizeof le, hipMemcpyDeviceToHost, s));
-    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    LOCREC_READ_BACK(le, err.p, s);
     LOCREC_TRY(location_error(le, vlat.p, vlon.p, "location visit", n_visits, plat.p, plon.p, "place", inout_count));
 
     DevBuf<uint64_t> k0, k1;
     DevBuf<uint32_t> r0, r1;
-    LOCREC_TRY(k0.alloc((size_t)n_places));
-    LOCREC_TRY(k1.alloc((size_t)n_places));
-    LOCREC_TRY(r0.alloc((size_t)n_places));
-    LOCREC_TRY(r1.alloc((size_t)n_places));
-    hipLaunchKernelGGL(pr_place_keys, grid_for(n_places), dim3(256), 0, s, n_places, plat.p, plon.p, pr.p, regions.p, nr, g, k0.p,
-                       r0.p);
+    LOCREC_TRY(alloc_each((size_t)n_places, k0, k1, r0, r1));
+    LOCREC_LAUNCH(pr_place_keys, grid_for(n_places), dim3(256), 0, s, n_places, plat.p, plon.p, pr.p, regions.p, nr, g, k0.p,
+                  r0.p);
     LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, k0.p, k1.p, r0.p, r1.p, (int)n_places, 0, 64, s));
 
     DevBuf<unsigned long long> counts, offsets;
-    LOCREC_TRY(counts.alloc((size_t)n_visits));
-    LOCREC_TRY(offsets.alloc((size_t)n_visits));
-    hipLaunchKernelGGL((pr_join<false>), grid_for(n_visits), dim3(256), 0, s, n_visits, vp.p, vt.p, vlat.p, vlon.p, vr.p,
-                       visits_from, regions.p, nr, g, max_meters, n_places, k1.p, r1.p, pi.p, plat.p, plon.p, pc.p, counts.p,
-                       nullptr, (int64_t)0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    LOCREC_TRY(alloc_each((size_t)n_visits, counts, offsets));
+    LOCREC_LAUNCH((pr_join<false>), grid_for(n_visits), dim3(256), 0, s, n_visits, vp.p, vt.p, vlat.p, vlon.p, vr.p,
+                  visits_from, regions.p, nr, g, max_meters, n_places, k1.p, r1.p, pi.p, plat.p, plon.p, pc.p, counts.p,
+                  nullptr, (int64_t)0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
     LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, counts.p, offsets.p, (int)n_visits, s));
     unsigned long long last_off = 0, last_cnt = 0;
     LOCREC_HIP_TRY(hipMemcpyAsync(&last_off, offsets.p + (n_visits - 1), 8, hipMemcpyDeviceToHost, s));
@@ -666,15 +638,14 @@ try {
         DevBuf<unsigned long long> cut_dev;
         unsigned long long cut_end = 0;
         LOCREC_TRY(cut_dev.alloc(1));
-        hipLaunchKernelGGL(pr_cut_end, dim3(1), dim3(64), 0, s, n_visits, offsets.p, counts.p, cap, cut_dev.p);
-        LOCREC_HIP_TRY(hipMemcpyAsync(&cut_end, cut_dev.p, 8, hipMemcpyDeviceToHost, s));
-        LOCREC_HIP_TRY(hipStreamSynchronize(s));
+        LOCREC_LAUNCH(pr_cut_end, dim3(1), dim3(64), 0, s, n_visits, offsets.p, counts.p, cap, cut_dev.p);
+        LOCREC_READ_BACK(cut_end, cut_dev.p, s);
         scratch_rows = std::max(rows, (int64_t)cut_end);
     }
     LOCREC_TRY(scratch.alloc((size_t)scratch_rows));
-    hipLaunchKernelGGL((pr_join<true>), grid_for(n_visits), dim3(256), 0, s, n_visits, vp.p, vt.p, vlat.p, vlon.p, vr.p,
-                       visits_from, regions.p, nr, g, max_meters, n_places, k1.p, r1.p, pi.p, plat.p, plon.p, pc.p, nullptr,
-                       offsets.p, rows, scratch.p, op.p, ots.p, opl.p, org.p, oca.p);
+    LOCREC_LAUNCH((pr_join<true>), grid_for(n_visits), dim3(256), 0, s, n_visits, vp.p, vt.p, vlat.p, vlon.p, vr.p,
+                  visits_from, regions.p, nr, g, max_meters, n_places, k1.p, r1.p, pi.p, plat.p, plon.p, pc.p, nullptr,
+                  offsets.p, rows, scratch.p, op.p, ots.p, opl.p, org.p, oca.p);
     LOCREC_TRY(op.deliver(rows, s));
     LOCREC_TRY(ots.deliver(rows, s));
     LOCREC_TRY(opl.deliver(rows, s));
@@ -710,7 +681,7 @@ try {
     LOCREC_TRY(c.bind(lat2, n, mem, s));
     LOCREC_TRY(d.bind(lon2, n, mem, s));
     LOCREC_TRY(o.bind(out_meters, n, mem));
-    hipLaunchKernelGGL(pr_distances, grid_for(n), dim3(256), 0, s, n, a.p, b.p, c.p, d.p, o.p);
+    LOCREC_LAUNCH(pr_distances, grid_for(n), dim3(256), 0, s, n, a.p, b.p, c.p, d.p, o.p);
     LOCREC_TRY(o.deliver(n, s));
     LOCREC_HIP_TRY(hipStreamSynchronize(s));
     return LOCREC_OK;
@@ -783,21 +754,17 @@ try {
     DevBuf<uint64_t> a0, a1;
     DevBuf<unsigned char> in_region;
     DevBuf<int32_t> cnt_dev;
-    LOCREC_TRY(a0.alloc((size_t)n_places));
-    LOCREC_TRY(a1.alloc((size_t)n_places));
-    LOCREC_TRY(in_region.alloc((size_t)n_places));
+    LOCREC_TRY(alloc_each((size_t)n_places, a0, a1, in_region));
     LOCREC_TRY(cnt_dev.alloc(1));
-    hipLaunchKernelGGL(pr_region_place_keys, grid_for(n_places), dim3(256), 0, s, n_places, pid.p, preg.p, target_region_id, a0.p,
-                       in_region.p);
+    LOCREC_LAUNCH(pr_region_place_keys, grid_for(n_places), dim3(256), 0, s, n_places, pid.p, preg.p, target_region_id, a0.p,
+                  in_region.p);
     LOCREC_PRIM(tmp, prim::select_flagged(p_, bytes_, a0.p, in_region.p, a1.p, cnt_dev.p, (int)n_places, s));
     int32_t nallowed = 0;
-    LOCREC_HIP_TRY(hipMemcpyAsync(&nallowed, cnt_dev.p, sizeof nallowed, hipMemcpyDeviceToHost, s));
-    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    LOCREC_READ_BACK(nallowed, cnt_dev.p, s);
     if (nallowed > 0) {
         LOCREC_PRIM(tmp, prim::sort_keys(p_, bytes_, a1.p, a0.p, nallowed, 0, 64, s));
         LOCREC_PRIM(tmp, prim::unique(p_, bytes_, a0.p, a1.p, cnt_dev.p, nallowed, s));
-        LOCREC_HIP_TRY(hipMemcpyAsync(&nallowed, cnt_dev.p, sizeof nallowed, hipMemcpyDeviceToHost, s));
-        LOCREC_HIP_TRY(hipStreamSynchronize(s));
+        LOCREC_READ_BACK(nallowed, cnt_dev.p, s);
         std::swap(a0.p, a1.p);  // a0 = the distinct sorted keys
         std::swap(a0.n, a1.n);
     }
@@ -806,29 +773,25 @@ try {
     DevBuf<unsigned char> keep;
     DevBuf<uint32_t> r0, r1;
     DevBuf<uint64_t> k0, k1;
-    LOCREC_TRY(keep.alloc((size_t)n));
-    LOCREC_TRY(r0.alloc((size_t)n));
-    LOCREC_TRY(r1.alloc((size_t)n));
-    hipLaunchKernelGGL(pr_rank_flags, grid_for(n), dim3(256), 0, s, n, rid.p, a0.p, nallowed, keep.p);
+    LOCREC_TRY(alloc_each((size_t)n, keep, r0, r1));
+    LOCREC_LAUNCH(pr_rank_flags, grid_for(n), dim3(256), 0, s, n, rid.p, a0.p, nallowed, keep.p);
     prim::counting_iterator<uint32_t> iota(0u);
     LOCREC_PRIM(tmp, prim::select_flagged(p_, bytes_, iota, keep.p, r0.p, cnt_dev.p, (int)n, s));
     int32_t m = 0;
-    LOCREC_HIP_TRY(hipMemcpyAsync(&m, cnt_dev.p, sizeof m, hipMemcpyDeviceToHost, s));
-    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    LOCREC_READ_BACK(m, cnt_dev.p, s);
     if (m == 0) return LOCREC_OK;
     // order by (score desc, id asc): stable LSD - by id, then by score
-    LOCREC_TRY(k0.alloc((size_t)m));
-    LOCREC_TRY(k1.alloc((size_t)m));
-    hipLaunchKernelGGL(gather_id_keys, grid_for(m), dim3(256), 0, s, (int64_t)m, rid.p, r0.p, k0.p);
+    LOCREC_TRY(alloc_each((size_t)m, k0, k1));
+    LOCREC_LAUNCH(gather_id_keys, grid_for(m), dim3(256), 0, s, (int64_t)m, rid.p, r0.p, k0.p);
     LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, k0.p, k1.p, r0.p, r1.p, m, 0, 64, s));
-    hipLaunchKernelGGL(pr_rank_keys_by_score, grid_for(m), dim3(256), 0, s, (int64_t)m, r1.p, rsc.p, k0.p);
+    LOCREC_LAUNCH(pr_rank_keys_by_score, grid_for(m), dim3(256), 0, s, (int64_t)m, r1.p, rsc.p, k0.p);
     LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, k0.p, k1.p, r1.p, r0.p, m, 0, 64, s));
     const int64_t w = std::min<int64_t>(m, limit);
     Out<int64_t> oid;
     Out<double> osc;
     LOCREC_TRY(oid.bind(out_ids, w, mem));
     LOCREC_TRY(osc.bind(out_scores, w, mem));
-    hipLaunchKernelGGL(pr_rank_emit, grid_for(w), dim3(256), 0, s, w, r0.p, rid.p, rsc.p, oid.p, osc.p);
+    LOCREC_LAUNCH(pr_rank_emit, grid_for(w), dim3(256), 0, s, w, r0.p, rid.p, rsc.p, oid.p, osc.p);
     LOCREC_TRY(oid.deliver(w, s));
     LOCREC_TRY(osc.deliver(w, s));
     LOCREC_HIP_TRY(hipStreamSynchronize(s));
@@ -1037,15 +1000,13 @@ int32_t covisit_counts(int64_t n, const int64_t *person, const int64_t *place, c
     // distinct places, ascending: a place's rank is order-preserving, so rank order is id order
     DevBuf<uint64_t> pk;
     DevBuf<int32_t> np_dev;
-    LOCREC_TRY(pk.alloc((size_t)n));
-    LOCREC_TRY(uniq.alloc((size_t)n));
+    LOCREC_TRY(alloc_each((size_t)n, pk, uniq));
     LOCREC_TRY(np_dev.alloc(1));
-    hipLaunchKernelGGL(iota_keys, grid_for(n), dim3(256), 0, s, n, place, uniq.p, (uint32_t *)nullptr);
+    LOCREC_LAUNCH(iota_keys, grid_for(n), dim3(256), 0, s, n, place, uniq.p, (uint32_t *)nullptr);
     LOCREC_PRIM(tmp, prim::sort_keys(p_, bytes_, uniq.p, pk.p, (int)n, 0, 64, s));
     LOCREC_PRIM(tmp, prim::unique(p_, bytes_, pk.p, uniq.p, np_dev.p, (int)n, s));
     int32_t np = 0;
-    LOCREC_HIP_TRY(hipMemcpyAsync(&np, np_dev.p, sizeof np, hipMemcpyDeviceToHost, s));
-    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    LOCREC_READ_BACK(np, np_dev.p, s);
     pk.release();
     if (np < 2) return LOCREC_OK;  // one place: every pair is a same-place pair
     int nb = 1;
@@ -1057,16 +1018,13 @@ int32_t covisit_counts(int64_t n, const int64_t *person, const int64_t *place, c
     DevBuf<int64_t> sts;
     DevBuf<uint32_t> srk, lo;
     DevBuf<unsigned long long> width, off, chunk_dev;
-    LOCREC_TRY(sts.alloc((size_t)n));
-    LOCREC_TRY(srk.alloc((size_t)n));
-    LOCREC_TRY(lo.alloc((size_t)n));
-    LOCREC_TRY(width.alloc((size_t)n + 1));
-    LOCREC_TRY(off.alloc((size_t)n + 1));
+    LOCREC_TRY(alloc_each((size_t)n, sts, srk, lo));
+    LOCREC_TRY(alloc_each((size_t)n + 1, width, off));
     LOCREC_TRY(chunk_dev.alloc(2));
-    hipLaunchKernelGGL(pr_covisit_gather, grid_for(n), dim3(256), 0, s, n, S.rows, place, ts, uniq.p, (int64_t)np, sts.p, srk.p);
+    LOCREC_LAUNCH(pr_covisit_gather, grid_for(n), dim3(256), 0, s, n, S.rows, place, ts, uniq.p, (int64_t)np, sts.p, srk.p);
     LOCREC_TRY(clock.mark(kPhaseEmit));
     LOCREC_HIP_TRY(hipMemsetAsync(width.p + n, 0, sizeof(unsigned long long), s));
-    hipLaunchKernelGGL(pr_covisit_windows, grid_for(n), dim3(256), 0, s, n, S.k1.p, sts.p, interval, lo.p, width.p);
+    LOCREC_LAUNCH(pr_covisit_windows, grid_for(n), dim3(256), 0, s, n, S.k1.p, sts.p, interval, lo.p, width.p);
     LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, width.p, off.p, (size_t)n + 1, s));  // off[n] = all candidate pairs
         LOCREC_HIP_TRY(hipStreamSynchronize(s));
     S.k0.release();
@@ -1080,10 +1038,9 @@ int32_t covisit_counts(int64_t n, const int64_t *person, const int64_t *place, c
     LOCREC_TRY(nruns_dev.alloc(1));
     for (int64_t r0 = 0; r0 < n;) {
         LOCREC_TRY(clock.mark(kPhaseEmit));
-        hipLaunchKernelGGL(pr_chunk_end, dim3(1), dim3(64), 0, s, n, off.p, r0, (unsigned long long)budget, chunk_dev.p);
+        LOCREC_LAUNCH(pr_chunk_end, dim3(1), dim3(64), 0, s, n, off.p, r0, (unsigned long long)budget, chunk_dev.p);
         unsigned long long ce[2] = {0, 0};
-        LOCREC_HIP_TRY(hipMemcpyAsync(ce, chunk_dev.p, sizeof ce, hipMemcpyDeviceToHost, s));
-        LOCREC_HIP_TRY(hipStreamSynchronize(s));
+        LOCREC_READ_BACK(ce, chunk_dev.p, s);
         const int64_t r1 = (int64_t)ce[0], npairs = (int64_t)ce[1];
         if (npairs == 0) {
             r0 = r1;
@@ -1095,21 +1052,20 @@ int32_t covisit_counts(int64_t n, const int64_t *person, const int64_t *place, c
         LOCREC_TRY(ka.reserve((size_t)npairs));
         LOCREC_TRY(kb.reserve((size_t)npairs));
         LOCREC_TRY(run_counts.reserve((size_t)npairs));
-        hipLaunchKernelGGL(pr_covisit_emit, grid_for(npairs, kPairTile), dim3(256), 0, s, r0, r1, off.p, lo.p, srk.p, nb,
-                           (unsigned long long)npairs, ka.p);
+        LOCREC_LAUNCH(pr_covisit_emit, grid_for(npairs, kPairTile), dim3(256), 0, s, r0, r1, off.p, lo.p, srk.p, nb,
+                      (unsigned long long)npairs, ka.p);
         LOCREC_TRY(clock.mark(kPhaseSort));
         LOCREC_PRIM(tmp, prim::sort_keys(p_, bytes_, ka.p, kb.p, (size_t)npairs, 0, (unsigned)(2 * nb), s));
         LOCREC_PRIM(tmp, prim::run_length_encode(p_, bytes_, kb.p, (size_t)npairs, ka.p, run_counts.p, nruns_dev.p, s));
         uint32_t c32 = 0;
-        LOCREC_HIP_TRY(hipMemcpyAsync(&c32, nruns_dev.p, sizeof c32, hipMemcpyDeviceToHost, s));
-        LOCREC_HIP_TRY(hipStreamSynchronize(s));
+        LOCREC_READ_BACK(c32, nruns_dev.p, s);
         const int64_t c = c32;
 
         // the runs of two different places, appended to the result so far; sorted and summed per pair if there was one
         LOCREC_TRY(clock.mark(kPhaseMerge));
         LOCREC_TRY(flag.reserve((size_t)c));
         LOCREC_TRY(pos.reserve((size_t)c));
-        hipLaunchKernelGGL(pr_pair_flags, grid_for(c), dim3(256), 0, s, c, ka.p, nb, flag.p);
+        LOCREC_LAUNCH(pr_pair_flags, grid_for(c), dim3(256), 0, s, c, ka.p, nb, flag.p);
         LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, flag.p, pos.p, (size_t)c, s));
         uint32_t last_pos = 0, last_flag = 0;
         LOCREC_HIP_TRY(hipMemcpyAsync(&last_pos, pos.p + (c - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -1121,14 +1077,13 @@ int32_t covisit_counts(int64_t n, const int64_t *person, const int64_t *place, c
         const int64_t cat = R.m + add;
         if (cat >= kMaxRows) return fail(LOCREC_E_INVALID_ARG, "%lld distinct place pairs: at most 2^31 - 1", (long long)cat);
         DevBuf<uint64_t> ck, cc;
-        LOCREC_TRY(ck.alloc((size_t)cat));
-        LOCREC_TRY(cc.alloc((size_t)cat));
+        LOCREC_TRY(alloc_each((size_t)cat, ck, cc));
         if (R.m > 0) {
             LOCREC_HIP_TRY(hipMemcpyAsync(ck.p, R.keys.p, (size_t)R.m * 8, hipMemcpyDeviceToDevice, s));
             LOCREC_HIP_TRY(hipMemcpyAsync(cc.p, R.counts.p, (size_t)R.m * 8, hipMemcpyDeviceToDevice, s));
         }
-        hipLaunchKernelGGL(pr_pair_append, grid_for(c), dim3(256), 0, s, c, ka.p, run_counts.p, flag.p, pos.p, ck.p + R.m,
-                           cc.p + R.m);
+        LOCREC_LAUNCH(pr_pair_append, grid_for(c), dim3(256), 0, s, c, ka.p, run_counts.p, flag.p, pos.p, ck.p + R.m,
+                      cc.p + R.m);
         if (R.m == 0) {
             LOCREC_HIP_TRY(hipStreamSynchronize(s));
             std::swap(R.keys.p, ck.p);
@@ -1139,12 +1094,10 @@ int32_t covisit_counts(int64_t n, const int64_t *person, const int64_t *place, c
             continue;
         }
         DevBuf<uint64_t> sk, sc;
-        LOCREC_TRY(sk.alloc((size_t)cat));
-        LOCREC_TRY(sc.alloc((size_t)cat));
+        LOCREC_TRY(alloc_each((size_t)cat, sk, sc));
         LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, ck.p, sk.p, cc.p, sc.p, (size_t)cat, 0, (unsigned)(2 * nb), s));
         LOCREC_PRIM(tmp, prim::sum_by_key(p_, bytes_, sk.p, sc.p, (size_t)cat, ck.p, cc.p, nruns_dev.p, s));
-        LOCREC_HIP_TRY(hipMemcpyAsync(&c32, nruns_dev.p, sizeof c32, hipMemcpyDeviceToHost, s));
-        LOCREC_HIP_TRY(hipStreamSynchronize(s));
+        LOCREC_READ_BACK(c32, nruns_dev.p, s);
         std::swap(R.keys.p, ck.p);
         std::swap(R.keys.n, ck.n);
         std::swap(R.counts.p, cc.p);
@@ -1192,11 +1145,8 @@ try {
         LOCREC_TRY(clock.mark(kPhaseMerge));
         DevBuf<uint32_t> step, srank, keep, pos;
         DevBuf<uint64_t> totals;
-        LOCREC_TRY(step.alloc((size_t)m));
-        LOCREC_TRY(srank.alloc((size_t)m));
-        LOCREC_TRY(keep.alloc((size_t)m));
-        LOCREC_TRY(pos.alloc((size_t)m));
-        hipLaunchKernelGGL(pr_pair_source_steps, grid_for(m), dim3(256), 0, s, m, R.keys.p, nb, step.p);
+        LOCREC_TRY(alloc_each((size_t)m, step, srank, keep, pos));
+        LOCREC_LAUNCH(pr_pair_source_steps, grid_for(m), dim3(256), 0, s, m, R.keys.p, nb, step.p);
         LOCREC_PRIM(tmp, prim::inclusive_sum(p_, bytes_, step.p, srank.p, (size_t)m, s));
         LOCREC_TRY(rank_keep(m, srank.p, R.counts.p, top_n, true, keep.p, pos.p, &total, tmp, s));
         const int64_t rows = std::min(total, cap);
@@ -1207,8 +1157,8 @@ try {
             LOCREC_TRY(oa.bind(out_source_ids, rows, mem));
             LOCREC_TRY(ob.bind(out_target_ids, rows, mem));
             LOCREC_TRY(ow.bind(out_weights, rows, mem));
-            hipLaunchKernelGGL(pr_emit_similar, grid_for(m), dim3(256), 0, s, m, keep.p, pos.p, R.keys.p, nb, uniq.p, R.counts.p,
-                               srank.p, totals.p, rows, oa.p, ob.p, ow.p);
+            LOCREC_LAUNCH(pr_emit_similar, grid_for(m), dim3(256), 0, s, m, keep.p, pos.p, R.keys.p, nb, uniq.p, R.counts.p,
+                          srank.p, totals.p, rows, oa.p, ob.p, ow.p);
             LOCREC_TRY(oa.deliver(rows, s));
             LOCREC_TRY(ob.deliver(rows, s));
             LOCREC_TRY(ow.deliver(rows, s));

@@ -461,8 +461,7 @@ int32_t rank_segments_device(int64_t n_seg, const int64_t *seg_begin, const int6
     if (N == 0) {  // limit(n <= 0) is empty: the caller's verdict on the offsets, the counts, nothing else
         unsigned long long bad = 0;
         if (invalid_flag) {
-            LOCREC_HIP_TRY(hipMemcpyAsync(&bad, invalid_flag, sizeof bad, hipMemcpyDeviceToHost, s));
-            LOCREC_HIP_TRY(hipStreamSynchronize(s));
+            LOCREC_READ_BACK(bad, invalid_flag, s);
             ++st.host_syncs;
         }
         if (bad) return fail(LOCREC_E_INVALID_ARG, "segments must be non-decreasing offsets inside [0, n]");
@@ -482,11 +481,11 @@ int32_t rank_segments_device(int64_t n_seg, const int64_t *seg_begin, const int6
         k0 = table.p;
         k1 = k0 + n_places;
         uint32_t *r0 = reinterpret_cast<uint32_t *>(k1 + n_places), *r1 = r0 + 2 * np8;
-        hipLaunchKernelGGL(iota_keys, grid_for(n_places), dim3(256), 0, s, n_places, place_ids, k0, r0);
+        LOCREC_LAUNCH(iota_keys, grid_for(n_places), dim3(256), 0, s, n_places, place_ids, k0, r0);
         LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, k0, k1, r0, r1, (int)n_places, 0, 64, s));
-        hipLaunchKernelGGL(gather_id_keys, grid_for(n_places), dim3(256), 0, s, n_places, place_region_ids, r1, k0);
+        LOCREC_LAUNCH(gather_id_keys, grid_for(n_places), dim3(256), 0, s, n_places, place_region_ids, r1, k0);
         LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, k0, k1, r1, r0, (int)n_places, 0, 64, s));
-        hipLaunchKernelGGL(gather_id_keys, grid_for(n_places), dim3(256), 0, s, n_places, place_ids, r0, k0);
+        LOCREC_LAUNCH(gather_id_keys, grid_for(n_places), dim3(256), 0, s, n_places, place_ids, r0, k0);
     }
     const uint64_t *table_regions = k1, *table_ids = k0;
     // the plan: every segment's range of the table and its chunks
@@ -503,11 +502,10 @@ int32_t rank_segments_device(int64_t n_seg, const int64_t *seg_begin, const int6
         int32_t *p;
     } lo = {reinterpret_cast<int32_t *>(nch.p + 8 * seg8)}, hi = {lo.p + 2 * seg8};
     LOCREC_HIP_TRY(hipMemsetAsync(hdr.p, 0, 4 * sizeof(unsigned long long), s));
-    hipLaunchKernelGGL(rb_plan, grid_for(n_seg + 1), dim3(256), 0, s, n_seg, seg_begin, seg_len, target_region_ids, n_places,
-                       table_regions, chunk, invalid_flag, nch.p, split_nch.p, lo.p, hi.p, hdr.p);
+    LOCREC_LAUNCH(rb_plan, grid_for(n_seg + 1), dim3(256), 0, s, n_seg, seg_begin, seg_len, target_region_ids, n_places,
+                  table_regions, chunk, invalid_flag, nch.p, split_nch.p, lo.p, hi.p, hdr.p);
     unsigned long long h[4] = {0, 0, 0, 0};
-    LOCREC_HIP_TRY(hipMemcpyAsync(h, hdr.p, sizeof h, hipMemcpyDeviceToHost, s));
-    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    LOCREC_READ_BACK(h, hdr.p, s);
     ++st.host_syncs;
     if (h[0]) return fail(LOCREC_E_INVALID_ARG, "segments must be non-decreasing offsets inside [0, n], each shorter than 2^31 rows");
     if (h[1] >= (unsigned long long)kMaxRows - 1)
@@ -537,13 +535,12 @@ int32_t rank_segments_device(int64_t n_seg, const int64_t *seg_begin, const int6
             prow.p = reinterpret_cast<uint32_t *>(pid.p + pn);
             pcount.p = reinterpret_cast<int32_t *>(pid.p + pn + pn8);
         }
-        hipLaunchKernelGGL(rb_select, dim3(items), dim3(kRbThreads), 0, s, n_seg, first.p, pfirst.p, seg_begin, seg_len, lo.p,
-                           hi.p, table_ids, ids, scores, chunk, (int)N, pk.p, pid.p, prow.p, pcount.p, out_ids, out_scores,
-                           out_counts);
+        LOCREC_LAUNCH(rb_select, dim3(items), dim3(kRbThreads), 0, s, n_seg, first.p, pfirst.p, seg_begin, seg_len, lo.p,
+                      hi.p, table_ids, ids, scores, chunk, (int)N, pk.p, pid.p, prow.p, pcount.p, out_ids, out_scores,
+                      out_counts);
         if (h[3] > 0)
-            hipLaunchKernelGGL(rb_merge, dim3((unsigned)n_seg), dim3(kRbThreads), 0, s, first.p, pfirst.p, seg_begin, scores,
-                               (int)N, pk.p, pid.p, prow.p, pcount.p, out_ids, out_scores, out_counts);
-        LOCREC_HIP_TRY(hipGetLastError());
+            LOCREC_LAUNCH(rb_merge, dim3((unsigned)n_seg), dim3(kRbThreads), 0, s, first.p, pfirst.p, seg_begin, scores,
+                          (int)N, pk.p, pid.p, prow.p, pcount.p, out_ids, out_scores, out_counts);
         // (the partial lists are freed below: hipFree waits for the kernels that read them)
         return LOCREC_OK;
     }
@@ -554,14 +551,13 @@ int32_t rank_segments_device(int64_t n_seg, const int64_t *seg_begin, const int6
     DevBuf<uint32_t> cnt, base;
     LOCREC_TRY(cnt.alloc((size_t)items + 1));
     LOCREC_TRY(base.alloc((size_t)items + 1));
-    hipLaunchKernelGGL(rb_count, dim3(items + 1), dim3(kRbThreads), 0, s, n_seg, first.p, seg_begin, seg_len, lo.p, hi.p,
-                       table_ids, ids, chunk, cnt.p, items);
+    LOCREC_LAUNCH(rb_count, dim3(items + 1), dim3(kRbThreads), 0, s, n_seg, first.p, seg_begin, seg_len, lo.p, hi.p,
+                  table_ids, ids, chunk, cnt.p, items);
     // (kept rows in all: a u32 sum; more than 2^31 - 1 are refused below, and 2^32 or more cannot come from segments that
     // the callers cut out of fewer than 2^31 rows)
     LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, cnt.p, base.p, (size_t)items + 1, s));
     uint32_t m32 = 0;
-    LOCREC_HIP_TRY(hipMemcpyAsync(&m32, base.p + items, sizeof m32, hipMemcpyDeviceToHost, s));
-    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    LOCREC_READ_BACK(m32, base.p + items, s);
     ++st.host_syncs;
     const int64_t m = m32;
     if (m >= kMaxRows) return fail(LOCREC_E_INVALID_ARG, "more than 2^31 rows to sort: split the batch");
@@ -577,18 +573,17 @@ int32_t rank_segments_device(int64_t n_seg, const int64_t *seg_begin, const int6
     LOCREC_TRY(q0.alloc(mm));
     LOCREC_TRY(q1.alloc(mm));
     if (m > 0) {
-        hipLaunchKernelGGL(rb_scatter, dim3(items), dim3(kRbThreads), 0, s, n_seg, first.p, seg_begin, seg_len, lo.p, hi.p,
-                           table_ids, ids, chunk, base.p, kseg.p, krow.p, q0.p, v0.p);
+        LOCREC_LAUNCH(rb_scatter, dim3(items), dim3(kRbThreads), 0, s, n_seg, first.p, seg_begin, seg_len, lo.p, hi.p,
+                      table_ids, ids, chunk, base.p, kseg.p, krow.p, q0.p, v0.p);
         // three stable passes: id, score key, segment
         LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, q0.p, q1.p, v0.p, v1.p, (int)m, 0, 64, s));
-        hipLaunchKernelGGL(rb_score_keys, grid_for(m), dim3(256), 0, s, m, v1.p, kseg.p, krow.p, seg_begin, scores, q0.p);
+        LOCREC_LAUNCH(rb_score_keys, grid_for(m), dim3(256), 0, s, m, v1.p, kseg.p, krow.p, seg_begin, scores, q0.p);
         LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, q0.p, q1.p, v1.p, v0.p, (int)m, 0, 64, s));
-        hipLaunchKernelGGL(rb_segment_keys, grid_for(m), dim3(256), 0, s, m, v0.p, kseg.p, s0.p);
+        LOCREC_LAUNCH(rb_segment_keys, grid_for(m), dim3(256), 0, s, m, v0.p, kseg.p, s0.p);
         LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, s0.p, s1.p, v0.p, v1.p, (int)m, 0, 32, s));
     }
-    hipLaunchKernelGGL(rb_emit_sorted, dim3((unsigned)(n_seg * tiles)), dim3(kRbThreads), 0, s, tiles, N, m, s1.p, v1.p, krow.p,
-                       seg_begin, ids, scores, out_ids, out_scores, out_counts);
-    LOCREC_HIP_TRY(hipGetLastError());
+    LOCREC_LAUNCH(rb_emit_sorted, dim3((unsigned)(n_seg * tiles)), dim3(kRbThreads), 0, s, tiles, N, m, s1.p, v1.p, krow.p,
+                  seg_begin, ids, scores, out_ids, out_scores, out_counts);
     return LOCREC_OK;
 }
 
@@ -636,7 +631,7 @@ try {
     LOCREC_TRY(seg_len.alloc((size_t)n_segments));
     LOCREC_TRY(invalid.alloc(1));
     LOCREC_HIP_TRY(hipMemsetAsync(invalid.p, 0, sizeof(unsigned long long), s));
-    hipLaunchKernelGGL(rb_prepare, grid_for(n_segments), dim3(256), 0, s, n_segments, off.p, n, seg_begin.p, seg_len.p, invalid.p);
+    LOCREC_LAUNCH(rb_prepare, grid_for(n_segments), dim3(256), 0, s, n_segments, off.p, n, seg_begin.p, seg_len.p, invalid.p);
     LOCREC_TRY(rank_segments_device(n_segments, seg_begin.p, seg_len.p, rid.p, rsc.p, n_places, pid.p, preg.p, tgt.p, N, oid.p,
                                     osc.p, ocnt.p, invalid.p, 0, s));
     LOCREC_TRY(oid.deliver(n_segments * N, s));

@@ -165,8 +165,7 @@ try {
     LOCREC_TRY(out.alloc(1));
     LOCREC_PRIM(tmp, prim::reduce(p_, bytes_, ts.p, out.p, (size_t)n, rocprim::maximum<int64_t>(),
                                   std::numeric_limits<int64_t>::min(), s));
-    LOCREC_HIP_TRY(hipMemcpyAsync(out_max, out.p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    LOCREC_READ_BACK(*out_max, out.p, s);
     return LOCREC_OK;
 }
 LOCREC_CATCH_ALL
@@ -223,10 +222,9 @@ try {
     LOCREC_TRY(regs.bind(region_ids, n_regions, mem, s));
     LOCREC_TRY(invalid.alloc(1));
     LOCREC_HIP_TRY(hipMemsetAsync(invalid.p, 0, sizeof(uint32_t), s));
-    hipLaunchKernelGGL(rs_check_ascending, grid_for(n_regions), dim3(256), 0, s, n_regions, regs.p, invalid.p);
+    LOCREC_LAUNCH(rs_check_ascending, grid_for(n_regions), dim3(256), 0, s, n_regions, regs.p, invalid.p);
     uint32_t bad = 0;
-    LOCREC_HIP_TRY(hipMemcpyAsync(&bad, invalid.p, sizeof bad, hipMemcpyDeviceToHost, s));
-    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    LOCREC_READ_BACK(bad, invalid.p, s);
     if (bad) return fail(LOCREC_E_INVALID_ARG, "region_ids must be strictly ascending");
     if (n_rows == 0) {
         for (int64_t g = 0; g < n_regions + 2; ++g) out_offsets[g] = 0;
@@ -240,7 +238,7 @@ try {
     LOCREC_TRY(rows0.alloc((size_t)n_rows));
     LOCREC_TRY(offsets.alloc((size_t)n_regions + 2));
     LOCREC_TRY(rows.bind(out_rows, n_rows, mem));
-    hipLaunchKernelGGL(rs_rank_rows, grid_for(n_rows), dim3(256), 0, s, n_rows, rr.p, n_regions, regs.p, rank0.p, rows0.p);
+    LOCREC_LAUNCH(rs_rank_rows, grid_for(n_rows), dim3(256), 0, s, n_rows, rr.p, n_regions, regs.p, rank0.p, rows0.p);
     unsigned bits = 0;  // ceil(log2(n_regions + 1)): the ranks are 0 .. n_regions
     while (((int64_t)1 << bits) <= n_regions) ++bits;
     const uint32_t *sorted_rank = rank0.p;
@@ -252,7 +250,7 @@ try {
                                           (size_t)n_rows, 0, bits, s));
         sorted_rank = rank1.p;
     }
-    hipLaunchKernelGGL(rs_group_offsets, grid_for(n_regions + 2), dim3(256), 0, s, n_rows, sorted_rank, n_regions + 1, offsets.p);
+    LOCREC_LAUNCH(rs_group_offsets, grid_for(n_regions + 2), dim3(256), 0, s, n_rows, sorted_rank, n_regions + 1, offsets.p);
     LOCREC_HIP_TRY(hipMemcpyAsync(out_offsets, offsets.p, (size_t)(n_regions + 2) * sizeof(int64_t), hipMemcpyDeviceToHost, s));
     LOCREC_TRY(rows.deliver(n_rows, s));
     LOCREC_HIP_TRY(hipStreamSynchronize(s));
@@ -287,12 +285,11 @@ try {
     LOCREC_TRY(rb.bind(rows + b_begin, lb, mem, s));
     LOCREC_TRY(invalid.alloc(1));
     LOCREC_HIP_TRY(hipMemsetAsync(invalid.p, 0, sizeof(uint32_t), s));
-    hipLaunchKernelGGL(rs_check_runs, grid_for(total), dim3(256), 0, s, ra.p, la, rb.p, lb, n_rows, invalid.p);
+    LOCREC_LAUNCH(rs_check_runs, grid_for(total), dim3(256), 0, s, ra.p, la, rb.p, lb, n_rows, invalid.p);
     RsCols c = {};
     if (mem == LOCREC_MEM_HOST) {  // the staged columns are uploaded only for rows that passed the check
         uint32_t bad = 0;
-        LOCREC_HIP_TRY(hipMemcpyAsync(&bad, invalid.p, sizeof bad, hipMemcpyDeviceToHost, s));
-        LOCREC_HIP_TRY(hipStreamSynchronize(s));
+        LOCREC_READ_BACK(bad, invalid.p, s);
         if (bad) return fail(LOCREC_E_INVALID_ARG, "rows: a run is not strictly ascending or names a row outside [0, n_rows)");
     }
     for (int32_t k = 0; k < n_cols; ++k) {
@@ -302,8 +299,8 @@ try {
         c.out[k] = out[k].p;
     }
     // device memory: the kernel itself reads the flag first, so the call waits for its stream once, at the end
-    hipLaunchKernelGGL(rs_merge_gather, dim3((unsigned)((total + kRsTile - 1) / kRsTile)), dim3(kRsThreads), 0, s, invalid.p, ra.p,
-                       la, rb.p, lb, (int)n_cols, c);
+    LOCREC_LAUNCH(rs_merge_gather, dim3((unsigned)((total + kRsTile - 1) / kRsTile)), dim3(kRsThreads), 0, s, invalid.p, ra.p,
+                  la, rb.p, lb, (int)n_cols, c);
     uint32_t bad = 0;
     LOCREC_HIP_TRY(hipMemcpyAsync(&bad, invalid.p, sizeof bad, hipMemcpyDeviceToHost, s));
     for (int32_t k = 0; k < n_cols; ++k) LOCREC_TRY(out[k].deliver(total, s));

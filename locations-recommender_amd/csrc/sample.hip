@@ -307,8 +307,7 @@ try {
     LOCREC_TRY(regs.upload(region_ids, (size_t)n_regions, s));
     LOCREC_TRY(oid.bind(out_ids, total, mem));
     LOCREC_TRY(ohome.bind(out_home_region_ids, total, mem));
-    hipLaunchKernelGGL(sm_persons, grid_for(total), dim3(256), 0, s, total, ppr, regs.p, min_person_id, oid.p, ohome.p);
-    LOCREC_HIP_TRY(hipGetLastError());
+    LOCREC_LAUNCH(sm_persons, grid_for(total), dim3(256), 0, s, total, ppr, regs.p, min_person_id, oid.p, ohome.p);
     LOCREC_TRY(oid.deliver(total, s));
     LOCREC_TRY(ohome.deliver(total, s));
     LOCREC_HIP_TRY(hipStreamSynchronize(s));
@@ -374,10 +373,9 @@ try {
     LOCREC_HIP_TRY(hipMemsetAsync(bad.p, 0xFF, sizeof(unsigned long long), s));
 
     LOCREC_TRY(clock.mark(0));
-    hipLaunchKernelGGL(sm_visit_counts, grid_for(n_persons), dim3(256), 0, s, n_persons, home.p, person_index_base, regs.p,
-                       n_regions, stream_key(seed, kSmStreamVisitCount), stream_key(seed, kSmStreamVisit),
-                       (double)max_visits_per_person, counts.p, keys.p, rank.p, bad.p);
-    LOCREC_HIP_TRY(hipGetLastError());
+    LOCREC_LAUNCH(sm_visit_counts, grid_for(n_persons), dim3(256), 0, s, n_persons, home.p, person_index_base, regs.p,
+                  n_regions, stream_key(seed, kSmStreamVisitCount), stream_key(seed, kSmStreamVisit),
+                  (double)max_visits_per_person, counts.p, keys.p, rank.p, bad.p);
     LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, counts.p, offsets.p, (size_t)n_persons, s));
     unsigned long long last_off = 0, last_cnt = 0, bad_row = 0;
     LOCREC_HIP_TRY(hipMemcpyAsync(&last_off, offsets.p + (n_persons - 1), 8, hipMemcpyDeviceToHost, s));
@@ -404,10 +402,9 @@ try {
         LOCREC_TRY(ots.bind(out_timestamps, rows, mem));
         LOCREC_TRY(oym.bind(out_year_months, rows, mem));
         LOCREC_TRY(clock.mark(1));
-        hipLaunchKernelGGL(sm_visit_fill, grid_for(rows), dim3(256), 0, s, rows, n_persons, offsets.p, keys.p, rank.p, pid.p, home.p,
-                           boxes.p, from_timestamp_ms, (double)interval_hours, shared_factor, op.p, org.p, olat.p, olon.p, ots.p,
-                           oym.p);
-        LOCREC_HIP_TRY(hipGetLastError());
+        LOCREC_LAUNCH(sm_visit_fill, grid_for(rows), dim3(256), 0, s, rows, n_persons, offsets.p, keys.p, rank.p, pid.p, home.p,
+                      boxes.p, from_timestamp_ms, (double)interval_hours, shared_factor, op.p, org.p, olat.p, olon.p, ots.p,
+                      oym.p);
         LOCREC_TRY(clock.mark(-1));
         LOCREC_TRY(op.deliver(rows, s));
         LOCREC_TRY(org.deliver(rows, s));
@@ -482,9 +479,8 @@ try {
     LOCREC_TRY(olon.bind(out_longitudes, total, mem));
     LOCREC_TRY(org.bind(out_region_ids, total, mem));
     LOCREC_TRY(oca.bind(out_category_ids, total, mem));
-    hipLaunchKernelGGL(sm_places, grid_for(total), dim3(256), 0, s, total, c, regs.p, geo_dev.p, min_place_id, (double)n_categories,
-                       min_category_id, stream_key(seed, kSmStreamCategory), oid.p, olat.p, olon.p, org.p, oca.p);
-    LOCREC_HIP_TRY(hipGetLastError());
+    LOCREC_LAUNCH(sm_places, grid_for(total), dim3(256), 0, s, total, c, regs.p, geo_dev.p, min_place_id, (double)n_categories,
+                  min_category_id, stream_key(seed, kSmStreamCategory), oid.p, olat.p, olon.p, org.p, oca.p);
     LOCREC_TRY(oid.deliver(total, s));
     LOCREC_TRY(olat.deliver(total, s));
     LOCREC_TRY(olon.deliver(total, s));
@@ -525,8 +521,7 @@ try {
     if (out_offsets) LOCREC_TRY(ooff.bind(out_offsets, n + 1, mem));
     if (n == 0) {
         if (out_offsets) {
-            hipLaunchKernelGGL(sm_set_i64, dim3(1), dim3(1), 0, s, ooff.p, (int64_t)0);
-            LOCREC_HIP_TRY(hipGetLastError());
+            LOCREC_LAUNCH(sm_set_i64, dim3(1), dim3(1), 0, s, ooff.p, (int64_t)0);
             LOCREC_TRY(ooff.deliver(1, s));
             LOCREC_HIP_TRY(hipStreamSynchronize(s));
         }
@@ -548,9 +543,8 @@ try {
         LOCREC_TRY(offsets_own.alloc((size_t)n + 1));
         offsets = offsets_own.p;
     }
-    hipLaunchKernelGGL(sm_name_lengths, grid_for(n), dim3(256), 0, s, n, pid.p, cid.p, min_category_id, n_categories, coff.p,
-                       lengths.p, bad.p);
-    LOCREC_HIP_TRY(hipGetLastError());
+    LOCREC_LAUNCH(sm_name_lengths, grid_for(n), dim3(256), 0, s, n, pid.p, cid.p, min_category_id, n_categories, coff.p,
+                  lengths.p, bad.p);
     LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, lengths.p, offsets, (size_t)n, s));
     unsigned long long bad_row = 0;
     int64_t last_off = 0, last_len = 0;
@@ -563,15 +557,13 @@ try {
                     bad_row, (long long)n_categories, (long long)min_category_id);
     const int64_t total = last_off + last_len;
     *inout_units = total;
-    hipLaunchKernelGGL(sm_set_i64, dim3(1), dim3(1), 0, s, offsets + n, total);
-    LOCREC_HIP_TRY(hipGetLastError());
+    LOCREC_LAUNCH(sm_set_i64, dim3(1), dim3(1), 0, s, offsets + n, total);
     const int64_t units = std::min(total, cap);
     Out<uint16_t> ounits;
     if (units > 0) {
         LOCREC_TRY(ounits.bind(out_units, units, mem));
-        hipLaunchKernelGGL(sm_name_fill, grid_for(units), dim3(256), 0, s, units, n, offsets, pid.p, cid.p, min_category_id, coff.p,
-                           cunits.p, ounits.p);
-        LOCREC_HIP_TRY(hipGetLastError());
+        LOCREC_LAUNCH(sm_name_fill, grid_for(units), dim3(256), 0, s, units, n, offsets, pid.p, cid.p, min_category_id, coff.p,
+                      cunits.p, ounits.p);
         LOCREC_TRY(ounits.deliver(units, s));
     }
     if (out_offsets) LOCREC_TRY(ooff.deliver(n + 1, s));

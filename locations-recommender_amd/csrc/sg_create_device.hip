@@ -365,8 +365,7 @@ int32_t db_dictionary(locrec_sg_graph *g, int64_t np)
     LOCREC_HIP_TRY(prim::sort_keys(tmp.p, b1, ka.p, kb.p, nslots, 0u, 64u, s));
     LOCREC_HIP_TRY(prim::run_length_encode(tmp.p, b2, kb.p, nslots, ka.p, counts.p, nuniq.p, s));
     int32_t nu = 0;
-    LOCREC_HIP_TRY(hipMemcpyAsync(&nu, nuniq.p, sizeof(nu), hipMemcpyDeviceToHost, s));
-    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    LOCREC_READ_BACK(nu, nuniq.p, s);
     if (nu >= 1 && nu <= kDictMax) {
         std::vector<uint64_t> vals((size_t)nu);
         std::vector<unsigned int> cnt((size_t)nu);
@@ -385,9 +384,8 @@ int32_t db_dictionary(locrec_sg_graph *g, int64_t np)
         DevBuf<unsigned short> rank;
         LOCREC_HIP_TRY(hipMemcpyAsync(g->dict.p, dict_h.data(), (size_t)nu * 8, hipMemcpyHostToDevice, s));
         LOCREC_TRY(rank.upload(rank_h, s));
-        hipLaunchKernelGGL(sg_build_widx, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, s,
-                           reinterpret_cast<const double *>(g->w2.p), (int64_t)nslots, ka.p, rank.p, nu, g->widx.p);
-        LOCREC_HIP_TRY(hipGetLastError());
+        LOCREC_LAUNCH(sg_build_widx, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, s,
+                      reinterpret_cast<const double *>(g->w2.p), (int64_t)nslots, ka.p, rank.p, nu, g->widx.p);
         LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (locals)
         g->ndict = nu;
     } else {
@@ -451,11 +449,9 @@ int32_t sg_create_device_impl(int64_t ne, const int64_t *src, const int64_t *dst
         unsigned long long h[2] = {~0ull, 0ull};
         LOCREC_TRY(lohi.alloc(2));
         LOCREC_HIP_TRY(hipMemcpyAsync(lohi.p, h, sizeof h, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(sg_db_minmax, dim3((unsigned)std::min<int64_t>(1024, (ne + kDbThreads - 1) / kDbThreads)), B, 0, s, ne,
-                           src, dst, lohi.p);
-        LOCREC_HIP_TRY(hipGetLastError());
-        LOCREC_HIP_TRY(hipMemcpyAsync(h, lohi.p, sizeof h, hipMemcpyDeviceToHost, s));
-        LOCREC_HIP_TRY(hipStreamSynchronize(s));
+        LOCREC_LAUNCH(sg_db_minmax, dim3((unsigned)std::min<int64_t>(1024, (ne + kDbThreads - 1) / kDbThreads)), B, 0, s, ne,
+                      src, dst, lohi.p);
+        LOCREC_READ_BACK(h, lohi.p, s);
         const uint64_t id_lo = (uint64_t)id_of_key(h[0]);  // (the id's bits; differences are exact in unsigned arithmetic)
         const uint64_t id_span = h[1] - h[0];
         const bool dense_ids = id_span < (uint64_t)(8 * ne) + (1u << 20) && !g->env_no_dense_ids;
@@ -464,18 +460,14 @@ int32_t sg_create_device_impl(int64_t ne, const int64_t *src, const int64_t *dst
             DevBuf<int32_t> r;
             LOCREC_TRY(r.alloc((size_t)n + 1));
             LOCREC_HIP_TRY(hipMemsetAsync(r.p, 0, ((size_t)n + 1) * 4, s));
-            hipLaunchKernelGGL(sg_db_mark, grid_for(ne), B, 0, s, ne, src, dst, id_lo, r.p);
-            LOCREC_HIP_TRY(hipGetLastError());
+            LOCREC_LAUNCH(sg_db_mark, grid_for(ne), B, 0, s, ne, src, dst, id_lo, r.p);
             LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, r.p, r.p, (size_t)n + 1, s));
             int32_t k = 0;
-            LOCREC_HIP_TRY(hipMemcpyAsync(&k, r.p + n, 4, hipMemcpyDeviceToHost, s));
-            LOCREC_HIP_TRY(hipStreamSynchronize(s));
+            LOCREC_READ_BACK(k, r.p + n, s);
             nv = k;
             LOCREC_TRY(vid.alloc((size_t)nv));
-            hipLaunchKernelGGL(sg_db_dense_vid, grid_for(n), B, 0, s, n, r.p, id_lo, vid.p);
-            LOCREC_HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(sg_db_dense_rank, grid_for(ne), B, 0, s, ne, src, dst, id_lo, r.p, cs.p, ct.p, eidx.p);
-            LOCREC_HIP_TRY(hipGetLastError());
+            LOCREC_LAUNCH(sg_db_dense_vid, grid_for(n), B, 0, s, n, r.p, id_lo, vid.p);
+            LOCREC_LAUNCH(sg_db_dense_rank, grid_for(ne), B, 0, s, ne, src, dst, id_lo, r.p, cs.p, ct.p, eidx.p);
             LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (r is a local)
         } else {
             DevBuf<int64_t> ids, sorted;
@@ -483,19 +475,16 @@ int32_t sg_create_device_impl(int64_t ne, const int64_t *src, const int64_t *dst
             LOCREC_TRY(ids.alloc((size_t)(2 * ne)));
             LOCREC_TRY(sorted.alloc((size_t)(2 * ne)));
             LOCREC_TRY(nuniq.alloc(1));
-            hipLaunchKernelGGL(sg_db_interleave, grid_for(ne), B, 0, s, ne, src, dst, ids.p);
-            LOCREC_HIP_TRY(hipGetLastError());
+            LOCREC_LAUNCH(sg_db_interleave, grid_for(ne), B, 0, s, ne, src, dst, ids.p);
             LOCREC_PRIM(tmp, prim::sort_keys(p_, bytes_, ids.p, sorted.p, (size_t)(2 * ne), 0u, 64u, s));
             LOCREC_PRIM(tmp, prim::unique(p_, bytes_, sorted.p, ids.p, nuniq.p, (size_t)(2 * ne), s));
             unsigned long long k = 0;
-            LOCREC_HIP_TRY(hipMemcpyAsync(&k, nuniq.p, 8, hipMemcpyDeviceToHost, s));
-            LOCREC_HIP_TRY(hipStreamSynchronize(s));
+            LOCREC_READ_BACK(k, nuniq.p, s);
             nv = (int64_t)k;
             sorted.release();
             LOCREC_TRY(vid.alloc((size_t)nv));
             LOCREC_HIP_TRY(hipMemcpyAsync(vid.p, ids.p, (size_t)nv * 8, hipMemcpyDeviceToDevice, s));
-            hipLaunchKernelGGL(sg_db_bisect, grid_for(ne), B, 0, s, ne, src, dst, vid.p, nv, cs.p, ct.p, eidx.p);
-            LOCREC_HIP_TRY(hipGetLastError());
+            LOCREC_LAUNCH(sg_db_bisect, grid_for(ne), B, 0, s, ne, src, dst, vid.p, nv, cs.p, ct.p, eidx.p);
             LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (ids is a local)
         }
     }
@@ -513,8 +502,7 @@ int32_t sg_create_device_impl(int64_t ne, const int64_t *src, const int64_t *dst
     LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, ct.p, kt.p, eidx.p, es.p, (size_t)ne, 0u, (unsigned)db_bits(nv), s));
     LOCREC_HIP_TRY(hipMemsetAsync(vbeg.p, 0, (size_t)nv * 4, s));
     LOCREC_HIP_TRY(hipMemsetAsync(vend.p, 0, (size_t)nv * 4, s));
-    hipLaunchKernelGGL(sg_db_row_bounds, grid_for(ne), B, 0, s, ne, kt.p, vbeg.p, vend.p);
-    LOCREC_HIP_TRY(hipGetLastError());
+    LOCREC_LAUNCH(sg_db_row_bounds, grid_for(ne), B, 0, s, ne, kt.p, vbeg.p, vend.p);
     LOCREC_HIP_TRY(hipStreamSynchronize(s));
     ct.release();
     eidx.release();
@@ -527,17 +515,14 @@ int32_t sg_create_device_impl(int64_t ne, const int64_t *src, const int64_t *dst
         DevBuf<unsigned long long> fl;
         LOCREC_TRY(fl.alloc((size_t)nv + 1));
         LOCREC_TRY(live_of.alloc((size_t)nv));
-        hipLaunchKernelGGL(sg_db_live_flags, grid_for(nv + 1), B, 0, s, nv, vbeg.p, vend.p, fl.p);
-        LOCREC_HIP_TRY(hipGetLastError());
+        LOCREC_LAUNCH(sg_db_live_flags, grid_for(nv + 1), B, 0, s, nv, vbeg.p, vend.p, fl.p);
         LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, fl.p, fl.p, (size_t)nv + 1, s));
         unsigned long long tot = 0;
-        LOCREC_HIP_TRY(hipMemcpyAsync(&tot, fl.p + nv, 8, hipMemcpyDeviceToHost, s));
-        LOCREC_HIP_TRY(hipStreamSynchronize(s));
+        LOCREC_READ_BACK(tot, fl.p + nv, s);
         n_short = (int32_t)(tot & 0xFFFFFFFFull);
         T = n_short + (int32_t)(tot >> 32);
         LOCREC_TRY(live_vertex.alloc((size_t)T));
-        hipLaunchKernelGGL(sg_db_live, grid_for(nv), B, 0, s, nv, vbeg.p, vend.p, fl.p, n_short, live_of.p, live_vertex.p);
-        LOCREC_HIP_TRY(hipGetLastError());
+        LOCREC_LAUNCH(sg_db_live, grid_for(nv), B, 0, s, nv, vbeg.p, vend.p, fl.p, n_short, live_of.p, live_vertex.p);
         LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (fl is a local)
     }
     g->nlive = T;
@@ -547,8 +532,7 @@ int32_t sg_create_device_impl(int64_t ne, const int64_t *src, const int64_t *dst
     DevBuf<DbCnt> sc;
     DbCnt tot, at_short;
     LOCREC_TRY(sc.alloc((size_t)T + 1));
-    hipLaunchKernelGGL(sg_db_row_counts, grid_for((int64_t)T + 1), B, 0, s, T, live_vertex.p, vbeg.p, vend.p, sc.p);
-    LOCREC_HIP_TRY(hipGetLastError());
+    LOCREC_LAUNCH(sg_db_row_counts, grid_for((int64_t)T + 1), B, 0, s, T, live_vertex.p, vbeg.p, vend.p, sc.p);
     LOCREC_PRIM(tmp, rocprim::exclusive_scan(p_, bytes_, sc.p, sc.p, DbCnt{{0, 0, 0, 0, 0, 0, 0, 0}}, (size_t)T + 1,
                                              DbCntPlus(), s));
     LOCREC_HIP_TRY(hipMemcpyAsync(&tot, sc.p + T, sizeof tot, hipMemcpyDeviceToHost, s));
@@ -608,20 +592,17 @@ int32_t sg_create_device_impl(int64_t ne, const int64_t *src, const int64_t *dst
     LOCREC_HIP_TRY(hipMemsetAsync(crow.p, 0, crow.bytes(), s));
     LOCREC_HIP_TRY(hipMemsetAsync(g->PA.p, 0, (size_t)(2 * pa) * sizeof(double), s));
     if (T > 0) {
-        hipLaunchKernelGGL(sg_db_row_maps, grid_for(T), B, 0, s, P, live_vertex.p, vbeg.p, vend.p, sc.p, rowinfo.p, g->seg_out.p,
-                           lrows_in_order.p, crow.p);
-        LOCREC_HIP_TRY(hipGetLastError());
+        LOCREC_LAUNCH(sg_db_row_maps, grid_for(T), B, 0, s, P, live_vertex.p, vbeg.p, vend.p, sc.p, rowinfo.p, g->seg_out.p,
+                      lrows_in_order.p, crow.p);
     }
     int32_t n_crows = 0;
     if (nl > 0) {
         LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, crow.p, crow.p, (size_t)nl + 1, s));
-        hipLaunchKernelGGL(sg_db_lrows_partition, grid_for(nl), B, 0, s, nl, lrows_in_order.p, crow.p, g->lrows.p);
-        LOCREC_HIP_TRY(hipGetLastError());
+        LOCREC_LAUNCH(sg_db_lrows_partition, grid_for(nl), B, 0, s, nl, lrows_in_order.p, crow.p, g->lrows.p);
         LOCREC_HIP_TRY(hipMemcpyAsync(&n_crows, crow.p + nl, 4, hipMemcpyDeviceToHost, s));
     }
     if (np > 0) {
-        hipLaunchKernelGGL(sg_db_pinfo, grid_for(np), B, 0, s, (int32_t)np, P, g->pinfo.p);
-        LOCREC_HIP_TRY(hipGetLastError());
+        LOCREC_LAUNCH(sg_db_pinfo, grid_for(np), B, 0, s, (int32_t)np, P, g->pinfo.p);
     }
     LOCREC_HIP_TRY(hipStreamSynchronize(s));
     g->nlong = n_crows;  // (rows with more than kLongRow full pieces: all of them sit in the long area)
@@ -640,21 +621,17 @@ int32_t sg_create_device_impl(int64_t ne, const int64_t *src, const int64_t *dst
     LOCREC_HIP_TRY(hipMemsetAsync(bad.p, 0, 4, s));
     LOCREC_HIP_TRY(hipMemsetAsync(g->w2.p, 0, (size_t)nslots * 8, s));
     if (g->use16) {
-        hipLaunchKernelGGL(sg_db_fill<unsigned short>, grid_for(nslots), B, 0, s, nslots, (unsigned short)T, g->col16.p);
-        LOCREC_HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(sg_db_scatter<unsigned short>, grid_for(ne), B, 0, s, ne, kt.p, es.p, vbeg.p, vend.p, live_of.p, rowinfo.p,
-                           cs.p, w, T, nslots, g->col16.p, reinterpret_cast<double *>(g->w2.p), slot_of_edge.p, bad.p);
+        LOCREC_LAUNCH(sg_db_fill<unsigned short>, grid_for(nslots), B, 0, s, nslots, (unsigned short)T, g->col16.p);
+        LOCREC_LAUNCH(sg_db_scatter<unsigned short>, grid_for(ne), B, 0, s, ne, kt.p, es.p, vbeg.p, vend.p, live_of.p, rowinfo.p,
+                      cs.p, w, T, nslots, g->col16.p, reinterpret_cast<double *>(g->w2.p), slot_of_edge.p, bad.p);
     } else {
         int32_t *col = reinterpret_cast<int32_t *>(g->col4.p);
-        hipLaunchKernelGGL(sg_db_fill<int32_t>, grid_for(nslots), B, 0, s, nslots, T, col);
-        LOCREC_HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(sg_db_scatter<int32_t>, grid_for(ne), B, 0, s, ne, kt.p, es.p, vbeg.p, vend.p, live_of.p, rowinfo.p, cs.p, w,
-                           T, nslots, col, reinterpret_cast<double *>(g->w2.p), slot_of_edge.p, bad.p);
+        LOCREC_LAUNCH(sg_db_fill<int32_t>, grid_for(nslots), B, 0, s, nslots, T, col);
+        LOCREC_LAUNCH(sg_db_scatter<int32_t>, grid_for(ne), B, 0, s, ne, kt.p, es.p, vbeg.p, vend.p, live_of.p, rowinfo.p, cs.p, w,
+                      T, nslots, col, reinterpret_cast<double *>(g->w2.p), slot_of_edge.p, bad.p);
     }
-    LOCREC_HIP_TRY(hipGetLastError());
     int32_t bad_h = 0;
-    LOCREC_HIP_TRY(hipMemcpyAsync(&bad_h, bad.p, 4, hipMemcpyDeviceToHost, s));
-    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    LOCREC_READ_BACK(bad_h, bad.p, s);
     if (bad_h) return fail(LOCREC_E_DEVICE, "device build: an edge fell outside the piece plan");
     kt.release();
     es.release();
@@ -672,13 +649,11 @@ int32_t sg_create_device_impl(int64_t ne, const int64_t *src, const int64_t *dst
         LOCREC_TRY(flag.alloc((size_t)ne));
         LOCREC_TRY(didx.alloc((size_t)ne));
         LOCREC_TRY(ndead.alloc(1));
-        hipLaunchKernelGGL(sg_db_dead_flag, grid_for(ne), B, 0, s, ne, cs.p, live_of.p, flag.p);
-        LOCREC_HIP_TRY(hipGetLastError());
+        LOCREC_LAUNCH(sg_db_dead_flag, grid_for(ne), B, 0, s, ne, cs.p, live_of.p, flag.p);
         LOCREC_PRIM(tmp, prim::select_flagged(p_, bytes_, prim::counting_iterator<uint32_t>(0), flag.p, didx.p, ndead.p,
                                               (size_t)ne, s));
         unsigned long long k = 0;
-        LOCREC_HIP_TRY(hipMemcpyAsync(&k, ndead.p, 8, hipMemcpyDeviceToHost, s));
-        LOCREC_HIP_TRY(hipStreamSynchronize(s));
+        LOCREC_READ_BACK(k, ndead.p, s);
         const int64_t nd = (int64_t)k;
         flag.release();
         LOCREC_TRY(g->dead_slots_dev.alloc((size_t)nd));
@@ -688,13 +663,11 @@ int32_t sg_create_device_impl(int64_t ne, const int64_t *src, const int64_t *dst
         LOCREC_TRY(dk2.alloc((size_t)nd));
         LOCREC_TRY(dv.alloc((size_t)nd));
         if (nd > 0) {
-            hipLaunchKernelGGL(sg_db_dead_gather, grid_for(nd), B, 0, s, nd, didx.p, cs.p, slot_of_edge.p, dk.p, dv.p);
-            LOCREC_HIP_TRY(hipGetLastError());
+            LOCREC_LAUNCH(sg_db_dead_gather, grid_for(nd), B, 0, s, nd, didx.p, cs.p, slot_of_edge.p, dk.p, dv.p);
             LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, dk.p, dk2.p, dv.p, g->dead_slots_dev.p, (size_t)nd, 0u,
                                               (unsigned)db_bits(nv), s));
         }
-        hipLaunchKernelGGL(sg_db_dead_ptr, grid_for(nv + 1), B, 0, s, nv, dk2.p, nd, dead_ptr.p);
-        LOCREC_HIP_TRY(hipGetLastError());
+        LOCREC_LAUNCH(sg_db_dead_ptr, grid_for(nv + 1), B, 0, s, nv, dk2.p, nd, dead_ptr.p);
         LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (locals)
     }
     slot_of_edge.release();
@@ -730,7 +703,8 @@ int32_t sg_create_device_impl(int64_t ne, const int64_t *src, const int64_t *dst
         }
     }
     int ncu = 0;
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, g->device);
+    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, g->device) != hipSuccess)
+        (void)hipGetLastError();  // (tolerated: ncu = 0 below; the dictionary's launch check must not report it)
     if (g->env_gs > 0) g->gs_blocks = g->env_gs * std::max(1, ncu);
     LOCREC_TRY(clock.mark(kDbDict));
     if (!g->env_no_dict && np > 0) LOCREC_TRY(db_dictionary(g.get(), np));
