@@ -283,6 +283,24 @@ int32_t locrec_knn_fetch_ranked(
     int64_t n_places, const int64_t *place_ids, const int64_t *place_region_ids,
     const int64_t *target_region_ids, int64_t max_recommendations,
     int64_t *out_place_ids, double *out_estimated_ratings, int64_t *out_counts);
+/*
+ * The unvisited forms of the two calls above - same arguments, outputs, padding, errors and refusals - which
+ * recommend only new places: person i's ranking leaves out every place the index holds a placeRatings row of
+ * that person for (where create was given no ratings: the entries of the person's place vector).  The lists
+ * are read where they lie on the device (locrec_rank_recommendations_batch_excluding's ranker with begins and
+ * lengths into the index's rating rows).  Afterwards the plain calls return what they did before.
+ */
+int32_t locrec_knn_recommend_ranked_batch_unvisited(
+    locrec_knn_index *index, int64_t nq, const int64_t *person_ids,
+    double place_weight, double category_weight, int64_t k_nearest,
+    int64_t n_places, const int64_t *place_ids, const int64_t *place_region_ids,
+    const int64_t *target_region_ids, int64_t max_recommendations,
+    int64_t *out_place_ids, double *out_estimated_ratings, int64_t *out_counts);
+int32_t locrec_knn_fetch_ranked_unvisited(
+    locrec_knn_index *index, int64_t nq,
+    int64_t n_places, const int64_t *place_ids, const int64_t *place_region_ids,
+    const int64_t *target_region_ids, int64_t max_recommendations,
+    int64_t *out_place_ids, double *out_estimated_ratings, int64_t *out_counts);
 
 /*
  * A pool of resident indexes that serves ONE mixed batch of (index, person[, target region]) requests - the queue of
@@ -548,7 +566,25 @@ int32_t locrec_sg_recommend_ranked_batch(
     int64_t *out_ids, double *out_probabilities, int64_t *out_counts,
     int64_t *out_row_counts, int64_t *out_iterations, int32_t *out_converged);
 /*
- * What this thread's last locrec_sg_recommend_ranked_batch did (any pointer may be NULL): tiles iterated,
+ * The same batch with a caller-given list of ids per position to leave out of the ranking (the places a person
+ * has been to: the targets of the vertex's out-edges): position i ranks the rows of vertex_ids[i] whose id is
+ * none of excluded_ids[excluded_offsets[i] .. excluded_offsets[i + 1]), as
+ * locrec_rank_recommendations_batch_excluding does.  Host arrays; excluded_offsets has n_targets + 1 entries,
+ * non-decreasing inside [0, n_excluded], n_excluded < 2^31 - refused with LOCREC_E_INVALID_ARG before any
+ * device work otherwise.  A repeated vertex is iterated once; each of its positions is ranked with its own
+ * region and its own list.  The emit, the segments' room, out_row_counts, iterations and converged are those of
+ * locrec_sg_recommend_ranked_batch, and the result does not depend on LOCREC_SG_RANKED_ROW_BUDGET either.
+ */
+int32_t locrec_sg_recommend_ranked_batch_excluding(
+    locrec_sg_graph *graph, int64_t n_targets, const int64_t *vertex_ids,
+    double alpha, double epsilon, int64_t max_iterations,
+    int64_t n_places, const int64_t *place_ids, const int64_t *place_region_ids,
+    const int64_t *target_region_ids, int64_t max_recommendations,
+    const int64_t *excluded_offsets, int64_t n_excluded, const int64_t *excluded_ids,
+    int64_t *out_ids, double *out_probabilities, int64_t *out_counts,
+    int64_t *out_row_counts, int64_t *out_iterations, int32_t *out_converged);
+/*
+ * What this thread's last locrec_sg_recommend_ranked_batch (or _excluding) did (any pointer may be NULL): tiles iterated,
  * ranker calls (groups), rows emitted into segments, and every byte the call copied to host memory or had the
  * device write there (state, block sums, polls, results), with the number of waits for the stream.
  */
@@ -951,6 +987,26 @@ int32_t locrec_rank_recommendations_batch(int64_t n_segments, const int64_t *off
                                           const int64_t *place_region_ids, const int64_t *target_region_ids,
                                           int64_t max_recommendations, int32_t mem, int64_t *out_ids,
                                           double *out_scores, int64_t *out_counts);
+
+/*
+ * The same with a list of ids per segment to leave out ("recommend only new places"): segment s ranks its
+ * rows whose id is none of excluded_ids[excluded_offsets[s] .. excluded_offsets[s + 1]) - exactly what
+ * locrec_rank_recommendations returns for those rows, which stay in their input order (the ties fall as
+ * before).  Ids match by int64 equality, whatever their region; a list may be unsorted, repeat an id and
+ * name ids the segment lacks.  `mem` covers excluded_offsets (n_segments + 1 entries) and excluded_ids
+ * (n_excluded < 2^31 entries) as well; excluded_offsets takes the rules and the refusal of offsets, inside
+ * [0, n_excluded].  With every list empty the result and the stats are locrec_rank_recommendations_batch's;
+ * the host synchronisations are no more in any case (3 at the most).  On the device the lists become one
+ * table of (segment, id) pairs sorted by two radix passes, searched per row that passed the region join: a
+ * list has no length limit.
+ */
+int32_t locrec_rank_recommendations_batch_excluding(int64_t n_segments, const int64_t *offsets, int64_t n,
+                                                    const int64_t *ids, const double *scores, int64_t n_places,
+                                                    const int64_t *place_ids, const int64_t *place_region_ids,
+                                                    const int64_t *target_region_ids, int64_t max_recommendations,
+                                                    const int64_t *excluded_offsets, int64_t n_excluded,
+                                                    const int64_t *excluded_ids, int32_t mem, int64_t *out_ids,
+                                                    double *out_scores, int64_t *out_counts);
 
 /* What the last ranked batch of this thread did (locrec_rank_recommendations_batch and the ranked KNN
  * batches): segments served by one block, segments split into chunks, those chunks, segments that took

@@ -70,6 +70,9 @@ SIGNATURES = {
     "locrec_knn_recommend_ranked_batch": [C.c_void_p, C.c_int64, _i64p, C.c_double, C.c_double, C.c_int64,
                                           C.c_int64, _i64p, _i64p, _i64p, C.c_int64, _i64p, _f64p, _i64p],
     "locrec_knn_fetch_ranked": [C.c_void_p, C.c_int64, C.c_int64, _i64p, _i64p, _i64p, C.c_int64, _i64p, _f64p, _i64p],
+    "locrec_knn_recommend_ranked_batch_unvisited": [C.c_void_p, C.c_int64, _i64p, C.c_double, C.c_double, C.c_int64,
+                                                    C.c_int64, _i64p, _i64p, _i64p, C.c_int64, _i64p, _f64p, _i64p],
+    "locrec_knn_fetch_ranked_unvisited": [C.c_void_p, C.c_int64, C.c_int64, _i64p, _i64p, _i64p, C.c_int64, _i64p, _f64p, _i64p],
     "locrec_knn_query_shard": [C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int64, C.c_int32, C.c_int32,
                                _i64p, _f64p, _i64p],
     "locrec_knn_recommend_neighbours": [C.c_void_p, C.c_int64, _i64p, _f64p, _i64p, _f64p, _i64p],
@@ -95,6 +98,9 @@ SIGNATURES = {
                                   _i64p, _i64p, _f64p, _i64p, _i64p, _i32p],
     "locrec_sg_recommend_ranked_batch": [C.c_void_p, C.c_int64, _i64p, C.c_double, C.c_double, C.c_int64,
                                          C.c_int64, _i64p, _i64p, _i64p, C.c_int64, _i64p, _f64p, _i64p, _i64p, _i64p, _i32p],
+    "locrec_sg_recommend_ranked_batch_excluding": [C.c_void_p, C.c_int64, _i64p, C.c_double, C.c_double, C.c_int64,
+                                                   C.c_int64, _i64p, _i64p, _i64p, C.c_int64, _i64p, C.c_int64, _i64p,
+                                                   _i64p, _f64p, _i64p, _i64p, _i64p, _i32p],
     "locrec_sg_recommend_ranked_batch_stats": [_i64p, _i64p, _i64p, _i64p, _i64p],
     "locrec_sg_iterate_async": [C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int64],
     "locrec_sg_sweeps_async": [C.c_void_p, C.c_int64, C.c_double, C.c_int64],
@@ -172,6 +178,9 @@ SIGNATURES = {
     # the segmented ranker (rank_batch.hip)
     "locrec_rank_recommendations_batch": [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
+    "locrec_rank_recommendations_batch_excluding": [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p],
     "locrec_rank_recommendations_batch_stats": [_i64p, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p],
     # the place deduplicator (dedup.hip)
     "locrec_lev_distances": [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p],

@@ -9,6 +9,9 @@
 // knn_large_recommend assembles them on the host, as the row fetch does - in one pass, their row counts being known
 // from the fetch - and they are uploaded and ranked as segments of a second ranker call (counted as host-assembled in
 // the stats).  (The fetch's own count-and-discard passes over those queries are inside knn.hip, whose bytes are hashed.)
+// The unvisited forms (locrec_knn_recommend_ranked_batch_unvisited, locrec_knn_fetch_ranked_unvisited) recommend only new
+// places: both ranker calls get, per segment, the place ids of the person's rating rows as an exclusion list - begins and
+// lengths into ix->r_place, filled on the device from ix->r_ptr (knn_rk_rated_ranges, 8 VGPRs, no LDS, no scratch).
 #pragma once
 
 #include "rank_batch.h"
@@ -25,10 +28,44 @@ int32_t knn_rank_check_args(int64_t n_places, const int64_t *place_ids, const in
     return LOCREC_OK;
 }
 
+// The unvisited forms' exclusion lists, read where they lie: segment c's list is the place ids of the rating rows the
+// index holds for internal row rows[c] - r_place[r_ptr[row] .. r_ptr[row + 1]) - so the ranker gets begins and lengths
+// into r_place itself.  No gather, no length travels to the host.
+__global__ void knn_rk_rated_ranges(int64_t nseg, const int32_t *__restrict__ rows, const int64_t *__restrict__ r_ptr,
+                                    int64_t *__restrict__ ex_begin, int64_t *__restrict__ ex_len)
+{
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= nseg) return;
+    const int64_t b = r_ptr[rows[c]];
+    ex_begin[c] = b;
+    ex_len[c] = r_ptr[rows[c] + 1] - b;
+}
+
+// words behind a RankIo's inputs for the lists of nseg segments: begins, lengths, the rows (int32)
+inline size_t knn_rk_ex_words(int64_t nseg) { return 2 * (size_t)nseg + ((size_t)nseg + 1) / 2; }
+
+// fills them at `at` for the segments' internal rows (all < ix->n) -> the ranker's lists
+int32_t knn_rk_rated_lists(locrec_knn_index *ix, const std::vector<int32_t> &rows, int64_t *at, hipStream_t s, RankExclude &ex)
+{
+    const int64_t nseg = (int64_t)rows.size();
+    int32_t *d_rows = reinterpret_cast<int32_t *>(at + 2 * nseg);
+    LOCREC_HIP_TRY(hipMemcpyAsync(d_rows, rows.data(), (size_t)nseg * 4, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(knn_rk_rated_ranges, dim3((unsigned)((nseg + 255) / 256)), dim3(256), 0, s, nseg, d_rows, ix->r_ptr.p, at,
+                       at + nseg);
+    LOCREC_HIP_TRY(hipGetLastError());
+    ex.begin = at;
+    ex.len = at + nseg;
+    ex.ids = ix->r_place.p;
+    ex.n = (int64_t)ix->r_place.n;
+    return LOCREC_OK;
+}
+
 // segment c of the result = the resident rows of processing slot slots[c], ranked for targets[c] (host arrays).
 // known_len: the segments' row counts where the caller has them from a fetch that already settled the rows (the batch
 // form: locrec_knn_recommend_batch sizes its result through locrec_knn_fetch_recommend); NULL: that fetch is made here.
-int32_t knn_rank_resident(locrec_knn_index *ix, const std::vector<int64_t> &slots, const int64_t *known_len, int64_t n_places,
+// unvisited: every segment leaves out the places its person has rated (both ranker calls get the lists).
+int32_t knn_rank_resident(locrec_knn_index *ix, const std::vector<int64_t> &slots, const int64_t *known_len, bool unvisited,
+                          int64_t n_places,
                           const int64_t *place_ids, const int64_t *place_region_ids, const int64_t *targets,
                           int64_t max_recommendations, int64_t *out_ids, double *out_scores, int64_t *out_counts)
 {
@@ -70,7 +107,7 @@ int32_t knn_rank_resident(locrec_knn_index *ix, const std::vector<int64_t> &slot
     if (nseg == 0) return LOCREC_OK;
     // one allocation for the call's inputs and one for its outputs (every hipMalloc / hipFree costs a wait)
     DevBuf<int64_t> d_in, d_out;
-    LOCREC_TRY(d_in.alloc(RankIo::in_words(n_places, nseg)));
+    LOCREC_TRY(d_in.alloc(RankIo::in_words(n_places, nseg) + (unvisited ? knn_rk_ex_words(nseg) : 0)));
     LOCREC_TRY(d_out.alloc(RankIo::out_words(nseg, N)));
     const RankIo io(d_in.p, d_out.p, n_places, nseg, N);
     if (n_places > 0) {
@@ -80,7 +117,14 @@ int32_t knn_rank_resident(locrec_knn_index *ix, const std::vector<int64_t> &slot
     LOCREC_HIP_TRY(hipMemcpyAsync(io.tgt, targets, (size_t)nseg * 8, hipMemcpyHostToDevice, s));
     LOCREC_HIP_TRY(hipMemcpyAsync(io.base, hb.data(), (size_t)nseg * 8, hipMemcpyHostToDevice, s));
     LOCREC_HIP_TRY(hipMemcpyAsync(io.len, hl.data(), (size_t)nseg * 8, hipMemcpyHostToDevice, s));
-    LOCREC_TRY(io.rank(lkb ? ix->lkb_place.p : ix->agg_place.p, lkb ? ix->lkb_est.p : ix->agg_est.p, 0, s));
+    auto row_of_slot = [&](int64_t q) { return ix->agg_rows.empty() ? ix->agg_first + (int32_t)q : ix->agg_rows[(size_t)q]; };
+    RankExclude ex;
+    if (unvisited) {
+        std::vector<int32_t> rows((size_t)nseg);
+        for (int64_t c = 0; c < nseg; ++c) rows[(size_t)c] = row_of_slot(slots[(size_t)c]);
+        LOCREC_TRY(knn_rk_rated_lists(ix, rows, d_in.p + RankIo::in_words(n_places, nseg), s, ex));
+    }
+    LOCREC_TRY(io.rank(lkb ? ix->lkb_place.p : ix->agg_place.p, lkb ? ix->lkb_est.p : ix->agg_est.p, 0, s, ex));
     LOCREC_TRY(io.read_back(out_ids, out_scores, out_counts, s));
     RankBatchStats total = rank_batch_stats();
     ++total.host_syncs;
@@ -93,7 +137,7 @@ int32_t knn_rank_resident(locrec_knn_index *ix, const std::vector<int64_t> &slot
         for (int64_t i = 0; i < nh; ++i) {
             const int64_t q = slots[(size_t)hosted[(size_t)i]];
             if (slot_begin[(size_t)q] < 0) {
-                const int32_t row = ix->agg_rows.empty() ? ix->agg_first + (int32_t)q : ix->agg_rows[(size_t)q];
+                const int32_t row = row_of_slot(q);
                 int64_t c = host_len[(size_t)i];  // one pass: the fetch has counted the rows
                 const size_t at = rp.size();
                 rp.resize(at + (size_t)c);
@@ -111,13 +155,19 @@ int32_t knn_rank_resident(locrec_knn_index *ix, const std::vector<int64_t> &slot
         DevBuf<double> d_re;
         LOCREC_TRY(d_rp.upload(rp, s));
         LOCREC_TRY(d_re.upload(re, s));
-        LOCREC_TRY(d_hin.alloc(RankIo::in_words(0, nh)));
+        LOCREC_TRY(d_hin.alloc(RankIo::in_words(0, nh) + (unvisited ? knn_rk_ex_words(nh) : 0)));
         LOCREC_TRY(d_hout.alloc(RankIo::out_words(nh, N)));
         const RankIo hio(d_hin.p, d_hout.p, n_places, nh, N, &io);  // (the places table is already there)
         LOCREC_HIP_TRY(hipMemcpyAsync(hio.tgt, tt.data(), (size_t)nh * 8, hipMemcpyHostToDevice, s));
         LOCREC_HIP_TRY(hipMemcpyAsync(hio.base, tb.data(), (size_t)nh * 8, hipMemcpyHostToDevice, s));
         LOCREC_HIP_TRY(hipMemcpyAsync(hio.len, tl.data(), (size_t)nh * 8, hipMemcpyHostToDevice, s));
-        LOCREC_TRY(hio.rank(d_rp.p, d_re.p, nh, s));
+        RankExclude hex;
+        if (unvisited) {
+            std::vector<int32_t> rows((size_t)nh);
+            for (int64_t i = 0; i < nh; ++i) rows[(size_t)i] = row_of_slot(slots[(size_t)hosted[(size_t)i]]);
+            LOCREC_TRY(knn_rk_rated_lists(ix, rows, d_hin.p + RankIo::in_words(0, nh), s, hex));
+        }
+        LOCREC_TRY(hio.rank(d_rp.p, d_re.p, nh, s, hex));
         LOCREC_TRY(hio.read_back_to(hosted, out_ids, out_scores, out_counts, s));
         const RankBatchStats &h = rank_batch_stats();
         // (the overflow queries were empty one-block segments of the first call: counted where their rows were ranked)
@@ -135,25 +185,25 @@ int32_t knn_rank_resident(locrec_knn_index *ix, const std::vector<int64_t> &slot
 
 }  // namespace
 
-extern "C" int32_t locrec_knn_fetch_ranked(locrec_knn_index *ix, int64_t nq, int64_t n_places, const int64_t *place_ids,
-                                           const int64_t *place_region_ids, const int64_t *target_region_ids,
-                                           int64_t max_recommendations, int64_t *out_place_ids, double *out_estimated_ratings,
-                                           int64_t *out_counts) try
+namespace {
+
+int32_t knn_fetch_ranked(locrec_knn_index *ix, int64_t nq, bool unvisited, int64_t n_places, const int64_t *place_ids,
+                         const int64_t *place_region_ids, const int64_t *target_region_ids, int64_t max_recommendations,
+                         int64_t *out_place_ids, double *out_estimated_ratings, int64_t *out_counts)
 {
     if (!ix) return fail(LOCREC_E_INVALID_ARG, "index is NULL");
     if (nq != ix->last_nq || nq <= 0 || !(ix->have_lkb || (ix->have_agg && ix->have_result)))
         return fail(LOCREC_E_INVALID_ARG, "no matching batched recommendation to fetch");
     std::vector<int64_t> slots((size_t)nq);
     std::iota(slots.begin(), slots.end(), (int64_t)0);
-    return knn_rank_resident(ix, slots, nullptr, n_places, place_ids, place_region_ids, target_region_ids, max_recommendations,
-                             out_place_ids, out_estimated_ratings, out_counts);
-} LOCREC_CATCH_ALL
+    return knn_rank_resident(ix, slots, nullptr, unvisited, n_places, place_ids, place_region_ids, target_region_ids,
+                             max_recommendations, out_place_ids, out_estimated_ratings, out_counts);
+}
 
-extern "C" int32_t locrec_knn_recommend_ranked_batch(locrec_knn_index *ix, int64_t nq, const int64_t *person_ids, double pw,
-                                                     double cw, int64_t k, int64_t n_places, const int64_t *place_ids,
-                                                     const int64_t *place_region_ids, const int64_t *target_region_ids,
-                                                     int64_t max_recommendations, int64_t *out_place_ids,
-                                                     double *out_estimated_ratings, int64_t *out_counts) try
+int32_t knn_recommend_ranked_batch(locrec_knn_index *ix, int64_t nq, const int64_t *person_ids, double pw, double cw, int64_t k,
+                                   bool unvisited, int64_t n_places, const int64_t *place_ids, const int64_t *place_region_ids,
+                                   const int64_t *target_region_ids, int64_t max_recommendations, int64_t *out_place_ids,
+                                   double *out_estimated_ratings, int64_t *out_counts)
 {
     // the batch itself, with its requires and "No such person": the rows stay on the device (capacity 0: sizes only)
     std::vector<int64_t> off((size_t)std::max<int64_t>(nq, 0) + 1, 0);
@@ -172,6 +222,47 @@ extern "C" int32_t locrec_knn_recommend_ranked_batch(locrec_knn_index *ix, int64
     }
     std::vector<int64_t> len((size_t)nq);
     for (int64_t i = 0; i < nq; ++i) len[(size_t)i] = off[(size_t)i + 1] - off[(size_t)i];
-    return knn_rank_resident(ix, slots, len.data(), n_places, place_ids, place_region_ids, target_region_ids,
+    return knn_rank_resident(ix, slots, len.data(), unvisited, n_places, place_ids, place_region_ids, target_region_ids,
                              max_recommendations, out_place_ids, out_estimated_ratings, out_counts);
+}
+
+}  // namespace
+
+extern "C" int32_t locrec_knn_fetch_ranked(locrec_knn_index *ix, int64_t nq, int64_t n_places, const int64_t *place_ids,
+                                           const int64_t *place_region_ids, const int64_t *target_region_ids,
+                                           int64_t max_recommendations, int64_t *out_place_ids, double *out_estimated_ratings,
+                                           int64_t *out_counts) try
+{
+    return knn_fetch_ranked(ix, nq, false, n_places, place_ids, place_region_ids, target_region_ids, max_recommendations,
+                            out_place_ids, out_estimated_ratings, out_counts);
+} LOCREC_CATCH_ALL
+
+extern "C" int32_t locrec_knn_fetch_ranked_unvisited(locrec_knn_index *ix, int64_t nq, int64_t n_places, const int64_t *place_ids,
+                                                     const int64_t *place_region_ids, const int64_t *target_region_ids,
+                                                     int64_t max_recommendations, int64_t *out_place_ids,
+                                                     double *out_estimated_ratings, int64_t *out_counts) try
+{
+    return knn_fetch_ranked(ix, nq, true, n_places, place_ids, place_region_ids, target_region_ids, max_recommendations,
+                            out_place_ids, out_estimated_ratings, out_counts);
+} LOCREC_CATCH_ALL
+
+extern "C" int32_t locrec_knn_recommend_ranked_batch(locrec_knn_index *ix, int64_t nq, const int64_t *person_ids, double pw,
+                                                     double cw, int64_t k, int64_t n_places, const int64_t *place_ids,
+                                                     const int64_t *place_region_ids, const int64_t *target_region_ids,
+                                                     int64_t max_recommendations, int64_t *out_place_ids,
+                                                     double *out_estimated_ratings, int64_t *out_counts) try
+{
+    return knn_recommend_ranked_batch(ix, nq, person_ids, pw, cw, k, false, n_places, place_ids, place_region_ids,
+                                      target_region_ids, max_recommendations, out_place_ids, out_estimated_ratings, out_counts);
+} LOCREC_CATCH_ALL
+
+extern "C" int32_t locrec_knn_recommend_ranked_batch_unvisited(locrec_knn_index *ix, int64_t nq, const int64_t *person_ids,
+                                                               double pw, double cw, int64_t k, int64_t n_places,
+                                                               const int64_t *place_ids, const int64_t *place_region_ids,
+                                                               const int64_t *target_region_ids, int64_t max_recommendations,
+                                                               int64_t *out_place_ids, double *out_estimated_ratings,
+                                                               int64_t *out_counts) try
+{
+    return knn_recommend_ranked_batch(ix, nq, person_ids, pw, cw, k, true, n_places, place_ids, place_region_ids,
+                                      target_region_ids, max_recommendations, out_place_ids, out_estimated_ratings, out_counts);
 } LOCREC_CATCH_ALL

@@ -33,6 +33,28 @@ int32_t rank_segments_device(int64_t n_segments, const int64_t *seg_begin, const
                              int64_t *out_ids, double *out_scores, int64_t *out_counts,
                              const unsigned long long *invalid_flag, int64_t host_assembled, hipStream_t s);
 
+// The same with a list of ids per segment to leave out: segment s ranks its rows whose id is none of
+// ex_ids[ex_begin[s] .. ex_begin[s] + ex_len[s]) (int64 equality; a list may be unsorted, repeat an id and name ids the
+// segment lacks; lists may overlap or be one range for several segments).  Begin / length and not offsets, so that a
+// caller can point into an array that is already resident: the KNN calls into the index's rating rows, an SG group into
+// the sub-range of its segments.  0 <= ex_len[s], 0 <= ex_begin[s], ex_begin[s] + ex_len[s] <= n_excluded < 2^31, checked
+// on the device with the segments, before anything reads through them.  The kept rows stay in their input order, so
+// the ties fall as in the plain entry; with every list empty the result and the stats are the plain entry's, and the
+// waits are no more in any case.
+int32_t rank_segments_device_excluding(int64_t n_segments, const int64_t *seg_begin, const int64_t *seg_len, const int64_t *ids,
+                                       const double *scores, int64_t n_places, const int64_t *place_ids,
+                                       const int64_t *place_region_ids, const int64_t *target_region_ids,
+                                       int64_t max_recommendations, const int64_t *ex_begin, const int64_t *ex_len,
+                                       int64_t n_excluded, const int64_t *ex_ids, int64_t *out_ids, double *out_scores,
+                                       int64_t *out_counts, const unsigned long long *invalid_flag, int64_t host_assembled,
+                                       hipStream_t s);
+
+// the exclusion lists of one ranker call (begin NULL: none, the plain entry)
+struct RankExclude {
+    const int64_t *begin = nullptr, *len = nullptr, *ids = nullptr;
+    int64_t n = 0;
+};
+
 // One ranker call's device arrays, carved out of one input and one output allocation of 8-byte words:
 //   in   [place ids | place regions | targets | bases | lengths]   (without the places table when it is places_of's)
 //   out  [ids | scores | counts]
@@ -49,8 +71,11 @@ struct RankIo {
           osc(reinterpret_cast<double *>(out + nseg * N))
     {
     }
-    int32_t rank(const int64_t *ids, const double *scores, int64_t host_assembled, hipStream_t s) const
+    int32_t rank(const int64_t *ids, const double *scores, int64_t host_assembled, hipStream_t s, const RankExclude &ex = {}) const
     {
+        if (ex.begin)
+            return rank_segments_device_excluding(nseg, base, len, ids, scores, n_places, pid, preg, tgt, N, ex.begin, ex.len, ex.n,
+                                                  ex.ids, oid, osc, ocnt, nullptr, host_assembled, s);
         return rank_segments_device(nseg, base, len, ids, scores, n_places, pid, preg, tgt, N, oid, osc, ocnt, nullptr, host_assembled, s);
     }
     // nseg x N ids and scores and nseg counts to host arrays of that shape, then the call's one wait

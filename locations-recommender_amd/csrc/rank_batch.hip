@@ -18,6 +18,15 @@
 //   N > LOCREC_RANK_BATCH_MAX_N   (or LOCREC_RANK_BATCH_SORT=1) the global path: the kept rows of all segments are
 //                                 compacted in order (rb_count, scan, rb_scatter), sorted by three stable radix passes
 //                                 (id, score key, segment) and the first N of every segment emitted (rb_emit_sorted).
+//   exclusion lists               (rank_segments_device_excluding, locrec_rank_recommendations_batch_excluding) per
+//                                 segment a list of ids to leave out, in the mould of the region table: rb_plan checks
+//                                 the lists' ranges with the segments' and adds their lengths into one more header
+//                                 word; rb_expand_excluded writes the (segment, id key) pairs, two stable radix passes
+//                                 order them by id and then segment, and segment s's range is the exclusive sum of the
+//                                 lengths.  rb_select_ex / rb_count_ex / rb_scatter_ex drop a row whose key a binary
+//                                 search finds in its segment's range - after the membership test, so only a row that
+//                                 would be kept pays it.  The table is global memory: a list has no length limit.  With
+//                                 every list empty the plain kernels run.
 //
 // A call waits for the stream once (the plan's totals and the validity of the segments, before any kernel reads a row)
 // and, on the global path, once more for the number of kept rows - whatever the number of segments.  Its work buffers
@@ -30,6 +39,9 @@
 //   rb_count        12 / 4 / 0 / 8
 //   rb_scatter      24 / 16 / 0 / 8
 //   rb_emit_sorted  14 / 16 / 0 / 8
+//   rb_select_ex    27 / 20512 / 0 / 7        rb_expand_excluded  11 / 0 / 0 / 8
+//   rb_count_ex     12 / 4 / 0 / 8
+//   rb_scatter_ex   24 / 16 / 0 / 8
 // The list is 20 bytes an entry: 20.5 KB of LDS a block, seven blocks of 256 threads a CU by LDS.
 
 #include "dev_prims.h"
@@ -87,10 +99,13 @@ __global__ void rb_prepare(int64_t n_seg, const int64_t *offsets, int64_t n, int
     if (!ok) atomicOr(invalid, 1ull);
 }
 
-// hdr: [0] invalid, [1] work items, [2] split segments, [3] their chunks
+// hdr: [0] invalid, [1] work items, [2] split segments, [3] their chunks, [4] entries of the exclusion lists.
+// ex_begin (NULL: no lists): segment s leaves out the ids ex_ids[ex_begin[s] .. + ex_len[s]), a range inside [0, n_ex];
+// xlen gets the lengths as the pair table's scan wants them.  Reads the ranges only, never through them.
 __global__ void rb_plan(int64_t n_seg, const int64_t *seg_begin, const int64_t *seg_len, const int64_t *targets, int64_t np,
                         const uint64_t *table_regions, int64_t chunk, const unsigned long long *invalid_in, uint32_t *nch,
-                        uint32_t *split_nch, int32_t *lo, int32_t *hi, unsigned long long *hdr)
+                        uint32_t *split_nch, int32_t *lo, int32_t *hi, unsigned long long *hdr, const int64_t *ex_begin,
+                        const int64_t *ex_len, int64_t n_ex, uint32_t *xlen)
 {
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (s == 0 && invalid_in && *invalid_in) atomicOr(&hdr[0], 1ull);
@@ -98,10 +113,18 @@ __global__ void rb_plan(int64_t n_seg, const int64_t *seg_begin, const int64_t *
     if (s == n_seg) {  // the scans' last element
         nch[s] = 0;
         split_nch[s] = 0;
+        if (ex_begin) xlen[s] = 0;
         return;
     }
     const int64_t len = seg_len[s];
-    const bool ok = len >= 0 && len < kMaxRows && seg_begin[s] >= 0;
+    bool ok = len >= 0 && len < kMaxRows && seg_begin[s] >= 0;
+    if (ex_begin) {
+        const int64_t xb = ex_begin[s], xl = ex_len[s];
+        const bool xok = xb >= 0 && xl >= 0 && xl <= n_ex && xb <= n_ex - xl;
+        xlen[s] = xok ? (uint32_t)xl : 0u;  // (n_ex < 2^31)
+        if (xok && xl > 0) atomicAdd(&hdr[4], (unsigned long long)xl);
+        ok = ok && xok;
+    }
     if (!ok) atomicOr(&hdr[0], 1ull);
     const uint64_t rk = ordered_key(targets[s]);
     const int64_t a = lower_bound_key(table_regions, np, rk);
@@ -227,12 +250,42 @@ __device__ __forceinline__ void rb_emit_row(const RbList &L, int w, int N, int64
     if (threadIdx.x == 0) out_counts[s] = w;
 }
 
-__global__ __launch_bounds__(kRbThreads) void rb_select(int64_t n_seg, const uint32_t *first, const uint32_t *pfirst,
-                                                        const int64_t *seg_begin, const int64_t *seg_len, const int32_t *lo,
-                                                        const int32_t *hi, const uint64_t *table_ids, const int64_t *ids,
-                                                        const double *scores, int64_t chunk, int N, uint64_t *pk,
-                                                        uint64_t *pid, uint32_t *prow, int32_t *pcount, int64_t *out_ids,
-                                                        double *out_scores, int64_t *out_counts)
+// ---- the exclusion lists: the pair table -----------------------------------------------------------------------------
+// (segment, id key) for every entry of every list, sorted by segment and then id: segment s's ids are
+// xkeys[xfirst[s] .. xfirst[s + 1]), ascending, duplicates kept (a search finds an id listed twice once).  The table is
+// global memory whatever a list's length: nothing here assumes a list fits in LDS.
+
+// pair p of the unsorted table: the segment whose range of the lengths' scan holds p (an empty list holds none)
+__global__ void rb_expand_excluded(int64_t n_seg, int64_t total, const uint32_t *xfirst, const int64_t *ex_begin,
+                                   const int64_t *ex_ids, uint64_t *keys, uint32_t *segs)
+{
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= total) return;
+    const int64_t s = rb_segment_of(xfirst, n_seg, (uint32_t)p);
+    keys[p] = ordered_key(ex_ids[ex_begin[s] + (p - (int64_t)xfirst[s])]);
+    segs[p] = (uint32_t)s;
+}
+
+// is key in xkeys[a, b)?
+__device__ __forceinline__ bool rb_excluded(const uint64_t *xkeys, uint32_t a, uint32_t b, uint64_t key)
+{
+    const uint32_t end = b;
+    while (a < b) {
+        const uint32_t mid = a + ((b - a) >> 1);
+        if (xkeys[mid] < key) a = mid + 1; else b = mid;
+    }
+    return a < end && xkeys[a] == key;
+}
+
+// The three kernels that test a row are bodies with the exclusion as a template parameter: the plain kernels keep
+// their signatures and, with EX false, their code; the _ex kernels take the pair table as well.
+template <bool EX>
+__device__ __forceinline__ void rb_select_body(int64_t n_seg, const uint32_t *first, const uint32_t *pfirst,
+                                               const int64_t *seg_begin, const int64_t *seg_len, const int32_t *lo,
+                                               const int32_t *hi, const uint64_t *table_ids, const int64_t *ids,
+                                               const double *scores, int64_t chunk, int N, uint64_t *pk, uint64_t *pid,
+                                               uint32_t *prow, int32_t *pcount, int64_t *out_ids, double *out_scores,
+                                               int64_t *out_counts, const uint32_t *xfirst, const uint64_t *xkeys)
 {
     __shared__ RbList L;
     const uint32_t w = blockIdx.x;
@@ -240,6 +293,11 @@ __global__ __launch_bounds__(kRbThreads) void rb_select(int64_t n_seg, const uin
     const uint32_t nch = first[s + 1] - first[s], c = w - first[s];
     const int64_t begin = seg_begin[s], len = seg_len[s];
     const int32_t tlo = lo[s], thi = hi[s];
+    uint32_t xa = 0, xb = 0;
+    if constexpr (EX) {
+        xa = xfirst[s];
+        xb = xfirst[s + 1];
+    }
     const int64_t r0 = (int64_t)c * chunk;
     const int64_t r1 = thi > tlo ? min(len, nch == 1 ? len : r0 + chunk) : 0;  // no place in the region: nothing to read
     if (threadIdx.x == 0) {
@@ -256,7 +314,9 @@ __global__ __launch_bounds__(kRbThreads) void rb_select(int64_t n_seg, const uin
                 const int32_t mid = (int32_t)(((uint32_t)a + (uint32_t)b) >> 1);
                 if (table_ids[mid] < key) a = mid + 1; else b = mid;
             }
-            if (a < thi && table_ids[a] == key) rb_push(L, score_desc_key(scores[begin + r]), key, (uint32_t)r);
+            bool keep = a < thi && table_ids[a] == key;
+            if constexpr (EX) keep = keep && !rb_excluded(xkeys, xa, xb, key);
+            if (keep) rb_push(L, score_desc_key(scores[begin + r]), key, (uint32_t)r);
         }
     }
     __syncthreads();
@@ -272,6 +332,29 @@ __global__ __launch_bounds__(kRbThreads) void rb_select(int64_t n_seg, const uin
         prow[slot * N + j] = L.row[j];
     }
     if (threadIdx.x == 0) pcount[slot] = wn;
+}
+
+__global__ __launch_bounds__(kRbThreads) void rb_select(int64_t n_seg, const uint32_t *first, const uint32_t *pfirst,
+                                                        const int64_t *seg_begin, const int64_t *seg_len, const int32_t *lo,
+                                                        const int32_t *hi, const uint64_t *table_ids, const int64_t *ids,
+                                                        const double *scores, int64_t chunk, int N, uint64_t *pk,
+                                                        uint64_t *pid, uint32_t *prow, int32_t *pcount, int64_t *out_ids,
+                                                        double *out_scores, int64_t *out_counts)
+{
+    rb_select_body<false>(n_seg, first, pfirst, seg_begin, seg_len, lo, hi, table_ids, ids, scores, chunk, N, pk, pid, prow,
+                          pcount, out_ids, out_scores, out_counts, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(kRbThreads) void rb_select_ex(int64_t n_seg, const uint32_t *first, const uint32_t *pfirst,
+                                                           const int64_t *seg_begin, const int64_t *seg_len, const int32_t *lo,
+                                                           const int32_t *hi, const uint64_t *table_ids, const int64_t *ids,
+                                                           const double *scores, int64_t chunk, int N, uint64_t *pk,
+                                                           uint64_t *pid, uint32_t *prow, int32_t *pcount, int64_t *out_ids,
+                                                           double *out_scores, int64_t *out_counts, const uint32_t *xfirst,
+                                                           const uint64_t *xkeys)
+{
+    rb_select_body<true>(n_seg, first, pfirst, seg_begin, seg_len, lo, hi, table_ids, ids, scores, chunk, N, pk, pid, prow,
+                         pcount, out_ids, out_scores, out_counts, xfirst, xkeys);
 }
 
 __global__ __launch_bounds__(kRbThreads) void rb_merge(const uint32_t *first, const uint32_t *pfirst, const int64_t *seg_begin,
@@ -305,10 +388,11 @@ __global__ __launch_bounds__(kRbThreads) void rb_merge(const uint32_t *first, co
 // ---- the global path --------------------------------------------------------------------------------------------------
 
 // kept rows of one work item
-__global__ __launch_bounds__(kRbThreads) void rb_count(int64_t n_seg, const uint32_t *first, const int64_t *seg_begin,
-                                                       const int64_t *seg_len, const int32_t *lo, const int32_t *hi,
-                                                       const uint64_t *table_ids, const int64_t *ids, int64_t chunk,
-                                                       uint32_t *cnt, uint32_t n_items)
+template <bool EX>
+__device__ __forceinline__ void rb_count_body(int64_t n_seg, const uint32_t *first, const int64_t *seg_begin,
+                                              const int64_t *seg_len, const int32_t *lo, const int32_t *hi,
+                                              const uint64_t *table_ids, const int64_t *ids, int64_t chunk, uint32_t *cnt,
+                                              uint32_t n_items, const uint32_t *xfirst, const uint64_t *xkeys)
 {
     __shared__ uint32_t total;
     const uint32_t w = blockIdx.x;
@@ -324,6 +408,11 @@ __global__ __launch_bounds__(kRbThreads) void rb_count(int64_t n_seg, const uint
     const int32_t tlo = lo[s], thi = hi[s];
     const int64_t r0 = (int64_t)c * chunk;
     const int64_t r1 = thi > tlo ? min(len, nch == 1 ? len : r0 + chunk) : 0;
+    uint32_t xa = 0, xb = 0;
+    if constexpr (EX) {
+        xa = xfirst[s];
+        xb = xfirst[s + 1];
+    }
     uint32_t mine = 0;
     for (int64_t r = r0 + threadIdx.x; r < r1; r += kRbThreads) {
         const uint64_t key = ordered_key(ids[begin + r]);
@@ -332,20 +421,40 @@ __global__ __launch_bounds__(kRbThreads) void rb_count(int64_t n_seg, const uint
             const int32_t mid = (int32_t)(((uint32_t)a + (uint32_t)b) >> 1);
             if (table_ids[mid] < key) a = mid + 1; else b = mid;
         }
-        if (a < thi && table_ids[a] == key) ++mine;
+        bool keep = a < thi && table_ids[a] == key;
+        if constexpr (EX) keep = keep && !rb_excluded(xkeys, xa, xb, key);
+        if (keep) ++mine;
     }
     if (mine) atomicAdd(&total, mine);
     __syncthreads();
     if (threadIdx.x == 0) cnt[w] = total;
 }
 
+__global__ __launch_bounds__(kRbThreads) void rb_count(int64_t n_seg, const uint32_t *first, const int64_t *seg_begin,
+                                                       const int64_t *seg_len, const int32_t *lo, const int32_t *hi,
+                                                       const uint64_t *table_ids, const int64_t *ids, int64_t chunk,
+                                                       uint32_t *cnt, uint32_t n_items)
+{
+    rb_count_body<false>(n_seg, first, seg_begin, seg_len, lo, hi, table_ids, ids, chunk, cnt, n_items, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(kRbThreads) void rb_count_ex(int64_t n_seg, const uint32_t *first, const int64_t *seg_begin,
+                                                          const int64_t *seg_len, const int32_t *lo, const int32_t *hi,
+                                                          const uint64_t *table_ids, const int64_t *ids, int64_t chunk,
+                                                          uint32_t *cnt, uint32_t n_items, const uint32_t *xfirst,
+                                                          const uint64_t *xkeys)
+{
+    rb_count_body<true>(n_seg, first, seg_begin, seg_len, lo, hi, table_ids, ids, chunk, cnt, n_items, xfirst, xkeys);
+}
+
 // the kept rows of one work item, in row order, at base[w] ..: segment, row, id key, and the row's own position as the
 // payload of the first sort
-__global__ __launch_bounds__(kRbThreads) void rb_scatter(int64_t n_seg, const uint32_t *first, const int64_t *seg_begin,
-                                                         const int64_t *seg_len, const int32_t *lo, const int32_t *hi,
-                                                         const uint64_t *table_ids, const int64_t *ids, int64_t chunk,
-                                                         const uint32_t *base, uint32_t *kseg, uint32_t *krow,
-                                                         uint64_t *keys, uint32_t *vals)
+template <bool EX>
+__device__ __forceinline__ void rb_scatter_body(int64_t n_seg, const uint32_t *first, const int64_t *seg_begin,
+                                                const int64_t *seg_len, const int32_t *lo, const int32_t *hi,
+                                                const uint64_t *table_ids, const int64_t *ids, int64_t chunk,
+                                                const uint32_t *base, uint32_t *kseg, uint32_t *krow, uint64_t *keys,
+                                                uint32_t *vals, const uint32_t *xfirst, const uint64_t *xkeys)
 {
     __shared__ uint32_t wave_cnt[kRbThreads / 64];
     const uint32_t w = blockIdx.x;
@@ -356,6 +465,11 @@ __global__ __launch_bounds__(kRbThreads) void rb_scatter(int64_t n_seg, const ui
     const int64_t r0 = (int64_t)c * chunk;
     const int64_t r1 = thi > tlo ? min(len, nch == 1 ? len : r0 + chunk) : 0;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t xa = 0, xb = 0;
+    if constexpr (EX) {
+        xa = xfirst[s];
+        xb = xfirst[s + 1];
+    }
     uint32_t pos = base[w];
     for (int64_t t0 = r0; t0 < r1; t0 += kRbThreads) {
         const int64_t r = t0 + threadIdx.x;
@@ -369,6 +483,7 @@ __global__ __launch_bounds__(kRbThreads) void rb_scatter(int64_t n_seg, const ui
                 if (table_ids[mid] < key) a = mid + 1; else b = mid;
             }
             keep = a < thi && table_ids[a] == key;
+            if constexpr (EX) keep = keep && !rb_excluded(xkeys, xa, xb, key);
         }
         const unsigned long long m = __ballot(keep);
         __syncthreads();  // the previous tile's wave_cnt has been read
@@ -388,6 +503,27 @@ __global__ __launch_bounds__(kRbThreads) void rb_scatter(int64_t n_seg, const ui
         }
         pos += all;
     }
+}
+
+__global__ __launch_bounds__(kRbThreads) void rb_scatter(int64_t n_seg, const uint32_t *first, const int64_t *seg_begin,
+                                                         const int64_t *seg_len, const int32_t *lo, const int32_t *hi,
+                                                         const uint64_t *table_ids, const int64_t *ids, int64_t chunk,
+                                                         const uint32_t *base, uint32_t *kseg, uint32_t *krow,
+                                                         uint64_t *keys, uint32_t *vals)
+{
+    rb_scatter_body<false>(n_seg, first, seg_begin, seg_len, lo, hi, table_ids, ids, chunk, base, kseg, krow, keys, vals, nullptr,
+                           nullptr);
+}
+
+__global__ __launch_bounds__(kRbThreads) void rb_scatter_ex(int64_t n_seg, const uint32_t *first, const int64_t *seg_begin,
+                                                            const int64_t *seg_len, const int32_t *lo, const int32_t *hi,
+                                                            const uint64_t *table_ids, const int64_t *ids, int64_t chunk,
+                                                            const uint32_t *base, uint32_t *kseg, uint32_t *krow,
+                                                            uint64_t *keys, uint32_t *vals, const uint32_t *xfirst,
+                                                            const uint64_t *xkeys)
+{
+    rb_scatter_body<true>(n_seg, first, seg_begin, seg_len, lo, hi, table_ids, ids, chunk, base, kseg, krow, keys, vals, xfirst,
+                          xkeys);
 }
 
 __global__ void rb_score_keys(int64_t m, const uint32_t *vals, const uint32_t *kseg, const uint32_t *krow,
@@ -440,21 +576,20 @@ __global__ __launch_bounds__(kRbThreads) void rb_emit_sorted(int64_t tiles, int6
     if (jt == 0 && threadIdx.x == 0) out_counts[s] = min(have, N);
 }
 
-}  // namespace
-
-namespace locrec {
-
-int32_t rank_segments_device(int64_t n_seg, const int64_t *seg_begin, const int64_t *seg_len, const int64_t *ids,
-                             const double *scores, int64_t n_places, const int64_t *place_ids,
-                             const int64_t *place_region_ids, const int64_t *target_region_ids, int64_t max_recommendations,
-                             int64_t *out_ids, double *out_scores, int64_t *out_counts,
-                             const unsigned long long *invalid_flag, int64_t host_assembled, hipStream_t s)
+// both internal entries; ex_begin NULL: the plain one
+int32_t rank_segments(int64_t n_seg, const int64_t *seg_begin, const int64_t *seg_len, const int64_t *ids, const double *scores,
+                      int64_t n_places, const int64_t *place_ids, const int64_t *place_region_ids,
+                      const int64_t *target_region_ids, int64_t max_recommendations, const int64_t *ex_begin,
+                      const int64_t *ex_len, int64_t n_excluded, const int64_t *ex_ids, int64_t *out_ids, double *out_scores,
+                      int64_t *out_counts, const unsigned long long *invalid_flag, int64_t host_assembled, hipStream_t s)
 {
     RankBatchStats &st = rank_batch_stats();
     st = RankBatchStats();
     st.host_assembled = host_assembled;
     if (n_seg < 0 || n_seg >= kMaxRows || n_places < 0 || n_places >= kMaxRows)
         return fail(LOCREC_E_INVALID_ARG, "segment or place count out of range [0, 2^31)");
+    if (ex_begin && (n_excluded < 0 || n_excluded >= kMaxRows))
+        return fail(LOCREC_E_INVALID_ARG, "excluded id count out of range [0, 2^31)");
     if (n_seg == 0) return LOCREC_OK;
     const int64_t N = std::max<int64_t>(0, max_recommendations);
     if (N > 0 && n_seg > ((int64_t)1 << 60) / N) return fail(LOCREC_E_INVALID_ARG, "n_segments * max_recommendations overflows");
@@ -490,28 +625,62 @@ int32_t rank_segments_device(int64_t n_seg, const int64_t *seg_begin, const int6
     const uint64_t *table_regions = k1, *table_ids = k0;
     // the plan: every segment's range of the table and its chunks
     const size_t seg8 = ((size_t)n_seg + 2) / 2;  // u32[n_seg + 1] in 8-byte units
-    LOCREC_TRY(plan.alloc(4 + 6 * seg8));
+    LOCREC_TRY(plan.alloc(5 + (ex_begin ? 8 : 6) * seg8));
     struct {
         unsigned long long *p;
     } hdr = {reinterpret_cast<unsigned long long *>(plan.p)};
     struct U32 {
         uint32_t *p;
-    } nch = {reinterpret_cast<uint32_t *>(plan.p + 4)}, split_nch = {nch.p + 2 * seg8}, first = {nch.p + 4 * seg8},
-      pfirst = {nch.p + 6 * seg8};
+    } nch = {reinterpret_cast<uint32_t *>(plan.p + 5)}, split_nch = {nch.p + 2 * seg8}, first = {nch.p + 4 * seg8},
+      pfirst = {nch.p + 6 * seg8}, xlen = {nch.p + 12 * seg8}, xfirst = {nch.p + 14 * seg8};  // x*: only with lists
     struct {
         int32_t *p;
     } lo = {reinterpret_cast<int32_t *>(nch.p + 8 * seg8)}, hi = {lo.p + 2 * seg8};
-    LOCREC_HIP_TRY(hipMemsetAsync(hdr.p, 0, 4 * sizeof(unsigned long long), s));
+    LOCREC_HIP_TRY(hipMemsetAsync(hdr.p, 0, 5 * sizeof(unsigned long long), s));
     LOCREC_LAUNCH(rb_plan, grid_for(n_seg + 1), dim3(256), 0, s, n_seg, seg_begin, seg_len, target_region_ids, n_places,
-                  table_regions, chunk, invalid_flag, nch.p, split_nch.p, lo.p, hi.p, hdr.p);
-    unsigned long long h[4] = {0, 0, 0, 0};
-    LOCREC_READ_BACK(h, hdr.p, s);
+                  table_regions, chunk, invalid_flag, nch.p, split_nch.p, lo.p, hi.p, hdr.p, ex_begin, ex_len, n_excluded,
+                  xlen.p);
+    unsigned long long h[5] = {0, 0, 0, 0, 0};  // (the fifth word travels only when there are lists)
+    LOCREC_HIP_TRY(hipMemcpyAsync(h, hdr.p, (ex_begin ? 5 : 4) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    LOCREC_HIP_TRY(hipStreamSynchronize(s));
     ++st.host_syncs;
-    if (h[0]) return fail(LOCREC_E_INVALID_ARG, "segments must be non-decreasing offsets inside [0, n], each shorter than 2^31 rows");
+    if (h[0])
+        return fail(LOCREC_E_INVALID_ARG, ex_begin ? "segments and exclusion lists must be non-decreasing offsets inside their "
+                                                     "arrays, each segment shorter than 2^31 rows"
+                                                   : "segments must be non-decreasing offsets inside [0, n], each shorter than 2^31 rows");
     if (h[1] >= (unsigned long long)kMaxRows - 1)
         return fail(LOCREC_E_INVALID_ARG, "%llu chunks: raise LOCREC_RANK_BATCH_CHUNK or split the batch", h[1]);
+    if (h[4] >= (unsigned long long)kMaxRows) return fail(LOCREC_E_INVALID_ARG, "2^31 excluded ids or more in all: split the batch");
     const uint32_t items = (uint32_t)h[1];
     LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, nch.p, first.p, (size_t)n_seg + 1, s));
+    // the pair table of the exclusion lists (every list empty: the plain kernels, and the plain call's result and stats)
+    const int64_t n_pairs = (int64_t)h[4];
+    DevBuf<uint64_t> pairs;
+    const uint64_t *xkeys = nullptr;
+    if (n_pairs > 0) {
+        // one allocation for the two sorts' temporary storage (in front: aligned) and the pairs: the table costs the call
+        // one hipMalloc and one hipFree, and `tmp`, sized by the region table, is not grown for it
+        const size_t xp8 = ((size_t)n_pairs + 1) / 2;  // u32[n_pairs] in 8-byte units
+        int seg_bits = 1;
+        while (seg_bits < 32 && ((int64_t)1 << seg_bits) < n_seg) ++seg_bits;
+        uint64_t *x0 = nullptr, *x1 = nullptr;
+        uint32_t *g0 = nullptr, *g1 = nullptr;
+        size_t bytes_id = 0, bytes_seg = 0;
+        LOCREC_HIP_TRY(prim::sort_pairs(nullptr, bytes_id, x0, x1, g0, g1, (size_t)n_pairs, 0, 64, s));
+        LOCREC_HIP_TRY(prim::sort_pairs(nullptr, bytes_seg, g1, g0, x1, x0, (size_t)n_pairs, 0, seg_bits, s));
+        const size_t temp8 = (std::max(bytes_id, bytes_seg) + 256) / 256 * 32;  // whole 256-byte lines, at least one
+        LOCREC_TRY(pairs.alloc(temp8 + 2 * (size_t)n_pairs + 2 * xp8));
+        x0 = pairs.p + temp8;
+        x1 = x0 + n_pairs;
+        g0 = reinterpret_cast<uint32_t *>(x1 + n_pairs);
+        g1 = g0 + 2 * xp8;
+        LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, xlen.p, xfirst.p, (size_t)n_seg + 1, s));
+        LOCREC_LAUNCH(rb_expand_excluded, grid_for(n_pairs), dim3(256), 0, s, n_seg, n_pairs, xfirst.p, ex_begin, ex_ids, x0, g0);
+        // two stable passes: id, segment
+        LOCREC_HIP_TRY(prim::sort_pairs(pairs.p, bytes_id, x0, x1, g0, g1, (size_t)n_pairs, 0, 64, s));
+        LOCREC_HIP_TRY(prim::sort_pairs(pairs.p, bytes_seg, g1, g0, x1, x0, (size_t)n_pairs, 0, seg_bits, s));
+        xkeys = x0;
+    }
     if (!global) {
         st.split = (int64_t)h[2];
         st.chunks = (int64_t)h[3];
@@ -535,9 +704,14 @@ int32_t rank_segments_device(int64_t n_seg, const int64_t *seg_begin, const int6
             prow.p = reinterpret_cast<uint32_t *>(pid.p + pn);
             pcount.p = reinterpret_cast<int32_t *>(pid.p + pn + pn8);
         }
-        LOCREC_LAUNCH(rb_select, dim3(items), dim3(kRbThreads), 0, s, n_seg, first.p, pfirst.p, seg_begin, seg_len, lo.p,
-                      hi.p, table_ids, ids, scores, chunk, (int)N, pk.p, pid.p, prow.p, pcount.p, out_ids, out_scores,
-                      out_counts);
+        if (xkeys)
+            LOCREC_LAUNCH(rb_select_ex, dim3(items), dim3(kRbThreads), 0, s, n_seg, first.p, pfirst.p, seg_begin, seg_len, lo.p,
+                          hi.p, table_ids, ids, scores, chunk, (int)N, pk.p, pid.p, prow.p, pcount.p, out_ids, out_scores,
+                          out_counts, xfirst.p, xkeys);
+        else
+            LOCREC_LAUNCH(rb_select, dim3(items), dim3(kRbThreads), 0, s, n_seg, first.p, pfirst.p, seg_begin, seg_len, lo.p,
+                          hi.p, table_ids, ids, scores, chunk, (int)N, pk.p, pid.p, prow.p, pcount.p, out_ids, out_scores,
+                          out_counts);
         if (h[3] > 0)
             LOCREC_LAUNCH(rb_merge, dim3((unsigned)n_seg), dim3(kRbThreads), 0, s, first.p, pfirst.p, seg_begin, scores,
                           (int)N, pk.p, pid.p, prow.p, pcount.p, out_ids, out_scores, out_counts);
@@ -551,8 +725,12 @@ int32_t rank_segments_device(int64_t n_seg, const int64_t *seg_begin, const int6
     DevBuf<uint32_t> cnt, base;
     LOCREC_TRY(cnt.alloc((size_t)items + 1));
     LOCREC_TRY(base.alloc((size_t)items + 1));
-    LOCREC_LAUNCH(rb_count, dim3(items + 1), dim3(kRbThreads), 0, s, n_seg, first.p, seg_begin, seg_len, lo.p, hi.p,
-                  table_ids, ids, chunk, cnt.p, items);
+    if (xkeys)
+        LOCREC_LAUNCH(rb_count_ex, dim3(items + 1), dim3(kRbThreads), 0, s, n_seg, first.p, seg_begin, seg_len, lo.p, hi.p,
+                      table_ids, ids, chunk, cnt.p, items, xfirst.p, xkeys);
+    else
+        LOCREC_LAUNCH(rb_count, dim3(items + 1), dim3(kRbThreads), 0, s, n_seg, first.p, seg_begin, seg_len, lo.p, hi.p,
+                      table_ids, ids, chunk, cnt.p, items);
     // (kept rows in all: a u32 sum; more than 2^31 - 1 are refused below, and 2^32 or more cannot come from segments that
     // the callers cut out of fewer than 2^31 rows)
     LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, cnt.p, base.p, (size_t)items + 1, s));
@@ -573,8 +751,12 @@ int32_t rank_segments_device(int64_t n_seg, const int64_t *seg_begin, const int6
     LOCREC_TRY(q0.alloc(mm));
     LOCREC_TRY(q1.alloc(mm));
     if (m > 0) {
-        LOCREC_LAUNCH(rb_scatter, dim3(items), dim3(kRbThreads), 0, s, n_seg, first.p, seg_begin, seg_len, lo.p, hi.p,
-                      table_ids, ids, chunk, base.p, kseg.p, krow.p, q0.p, v0.p);
+        if (xkeys)
+            LOCREC_LAUNCH(rb_scatter_ex, dim3(items), dim3(kRbThreads), 0, s, n_seg, first.p, seg_begin, seg_len, lo.p, hi.p,
+                          table_ids, ids, chunk, base.p, kseg.p, krow.p, q0.p, v0.p, xfirst.p, xkeys);
+        else
+            LOCREC_LAUNCH(rb_scatter, dim3(items), dim3(kRbThreads), 0, s, n_seg, first.p, seg_begin, seg_len, lo.p, hi.p,
+                          table_ids, ids, chunk, base.p, kseg.p, krow.p, q0.p, v0.p);
         // three stable passes: id, score key, segment
         LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, q0.p, q1.p, v0.p, v1.p, (int)m, 0, 64, s));
         LOCREC_LAUNCH(rb_score_keys, grid_for(m), dim3(256), 0, s, m, v1.p, kseg.p, krow.p, seg_begin, scores, q0.p);
@@ -587,32 +769,42 @@ int32_t rank_segments_device(int64_t n_seg, const int64_t *seg_begin, const int6
     return LOCREC_OK;
 }
 
-}  // namespace locrec
+// host offsets: non-decreasing inside [0, n]
+bool rb_host_offsets_ok(const int64_t *offsets, int64_t n_segments, int64_t n)
+{
+    bool ok = offsets[0] >= 0 && offsets[n_segments] <= n;
+    for (int64_t i = 0; ok && i < n_segments; ++i) ok = offsets[i] <= offsets[i + 1];
+    return ok;
+}
 
-extern "C" int32_t locrec_rank_recommendations_batch(int64_t n_segments, const int64_t *offsets, int64_t n, const int64_t *ids,
-                                                     const double *scores, int64_t n_places, const int64_t *place_ids,
-                                                     const int64_t *place_region_ids, const int64_t *target_region_ids,
-                                                     int64_t max_recommendations, int32_t mem, int64_t *out_ids,
-                                                     double *out_scores, int64_t *out_counts)
-try {
+// both public entries; with_lists false: the plain one (excluded_* unused)
+int32_t rb_public_call(int64_t n_segments, const int64_t *offsets, int64_t n, const int64_t *ids, const double *scores,
+                       int64_t n_places, const int64_t *place_ids, const int64_t *place_region_ids,
+                       const int64_t *target_region_ids, int64_t max_recommendations, bool with_lists,
+                       const int64_t *excluded_offsets, int64_t n_excluded, const int64_t *excluded_ids, int32_t mem,
+                       int64_t *out_ids, double *out_scores, int64_t *out_counts)
+{
     rank_batch_stats() = RankBatchStats();
     LOCREC_TRY(mem_ok(mem));
     if (n < 0 || n >= kMaxRows || n_places < 0 || n_places >= kMaxRows || n_segments < 0 || n_segments >= kMaxRows)
         return fail(LOCREC_E_INVALID_ARG, "row, place or segment count out of range [0, 2^31)");
+    if (with_lists && (n_excluded < 0 || n_excluded >= kMaxRows))
+        return fail(LOCREC_E_INVALID_ARG, "excluded id count out of range [0, 2^31)");
     if (n_segments == 0) return LOCREC_OK;
     const int64_t N = std::max<int64_t>(0, max_recommendations);  // limit(n <= 0) is empty
     if (N > 0 && n_segments > ((int64_t)1 << 60) / N) return fail(LOCREC_E_INVALID_ARG, "n_segments * max_recommendations overflows");
     if (!offsets || !target_region_ids || !out_counts || (n > 0 && (!ids || !scores)) ||
-        (n_places > 0 && (!place_ids || !place_region_ids)) || (N > 0 && (!out_ids || !out_scores)))
+        (n_places > 0 && (!place_ids || !place_region_ids)) || (N > 0 && (!out_ids || !out_scores)) ||
+        (with_lists && (!excluded_offsets || (n_excluded > 0 && !excluded_ids))))
         return fail(LOCREC_E_INVALID_ARG, "null array");
     if (mem == LOCREC_MEM_HOST) {
-        bool ok = offsets[0] >= 0 && offsets[n_segments] <= n;
-        for (int64_t i = 0; ok && i < n_segments; ++i) ok = offsets[i] <= offsets[i + 1];
-        if (!ok) return fail(LOCREC_E_INVALID_ARG, "offsets must be non-decreasing inside [0, n]");
+        if (!rb_host_offsets_ok(offsets, n_segments, n)) return fail(LOCREC_E_INVALID_ARG, "offsets must be non-decreasing inside [0, n]");
+        if (with_lists && !rb_host_offsets_ok(excluded_offsets, n_segments, n_excluded))
+            return fail(LOCREC_E_INVALID_ARG, "excluded_offsets must be non-decreasing inside [0, n_excluded]");
     }
     LOCREC_TRY(ensure_device());
     hipStream_t s = nullptr;
-    In<int64_t> off, tgt, rid, pid, preg;
+    In<int64_t> off, tgt, rid, pid, preg, xoff, xid;
     In<double> rsc;
     LOCREC_TRY(off.bind(offsets, n_segments + 1, mem, s));
     LOCREC_TRY(tgt.bind(target_region_ids, n_segments, mem, s));
@@ -625,21 +817,84 @@ try {
     LOCREC_TRY(oid.bind(out_ids, n_segments * N, mem));
     LOCREC_TRY(osc.bind(out_scores, n_segments * N, mem));
     LOCREC_TRY(ocnt.bind(out_counts, n_segments, mem));
-    DevBuf<int64_t> seg_begin, seg_len;
+    DevBuf<int64_t> seg_begin, seg_len, ex_begin, ex_len;
     DevBuf<unsigned long long> invalid;
     LOCREC_TRY(seg_begin.alloc((size_t)n_segments));
     LOCREC_TRY(seg_len.alloc((size_t)n_segments));
     LOCREC_TRY(invalid.alloc(1));
     LOCREC_HIP_TRY(hipMemsetAsync(invalid.p, 0, sizeof(unsigned long long), s));
     LOCREC_LAUNCH(rb_prepare, grid_for(n_segments), dim3(256), 0, s, n_segments, off.p, n, seg_begin.p, seg_len.p, invalid.p);
-    LOCREC_TRY(rank_segments_device(n_segments, seg_begin.p, seg_len.p, rid.p, rsc.p, n_places, pid.p, preg.p, tgt.p, N, oid.p,
-                                    osc.p, ocnt.p, invalid.p, 0, s));
+    if (with_lists) {
+        LOCREC_TRY(xoff.bind(excluded_offsets, n_segments + 1, mem, s));
+        LOCREC_TRY(xid.bind(excluded_ids, n_excluded, mem, s));
+        LOCREC_TRY(ex_begin.alloc((size_t)n_segments));
+        LOCREC_TRY(ex_len.alloc((size_t)n_segments));
+        LOCREC_LAUNCH(rb_prepare, grid_for(n_segments), dim3(256), 0, s, n_segments, xoff.p, n_excluded, ex_begin.p, ex_len.p,
+                      invalid.p);
+    }
+    LOCREC_TRY(rank_segments(n_segments, seg_begin.p, seg_len.p, rid.p, rsc.p, n_places, pid.p, preg.p, tgt.p, N, ex_begin.p,
+                             ex_len.p, n_excluded, xid.p, oid.p, osc.p, ocnt.p, invalid.p, 0, s));
     LOCREC_TRY(oid.deliver(n_segments * N, s));
     LOCREC_TRY(osc.deliver(n_segments * N, s));
     LOCREC_TRY(ocnt.deliver(n_segments, s));
     LOCREC_HIP_TRY(hipStreamSynchronize(s));
     ++rank_batch_stats().host_syncs;
     return LOCREC_OK;
+}
+
+}  // namespace
+
+namespace locrec {
+
+int32_t rank_segments_device(int64_t n_seg, const int64_t *seg_begin, const int64_t *seg_len, const int64_t *ids,
+                             const double *scores, int64_t n_places, const int64_t *place_ids,
+                             const int64_t *place_region_ids, const int64_t *target_region_ids, int64_t max_recommendations,
+                             int64_t *out_ids, double *out_scores, int64_t *out_counts,
+                             const unsigned long long *invalid_flag, int64_t host_assembled, hipStream_t s)
+{
+    return rank_segments(n_seg, seg_begin, seg_len, ids, scores, n_places, place_ids, place_region_ids, target_region_ids,
+                         max_recommendations, nullptr, nullptr, 0, nullptr, out_ids, out_scores, out_counts, invalid_flag,
+                         host_assembled, s);
+}
+
+int32_t rank_segments_device_excluding(int64_t n_seg, const int64_t *seg_begin, const int64_t *seg_len, const int64_t *ids,
+                                       const double *scores, int64_t n_places, const int64_t *place_ids,
+                                       const int64_t *place_region_ids, const int64_t *target_region_ids,
+                                       int64_t max_recommendations, const int64_t *ex_begin, const int64_t *ex_len,
+                                       int64_t n_excluded, const int64_t *ex_ids, int64_t *out_ids, double *out_scores,
+                                       int64_t *out_counts, const unsigned long long *invalid_flag, int64_t host_assembled,
+                                       hipStream_t s)
+{
+    if (n_seg > 0 && (!ex_begin || !ex_len || (n_excluded > 0 && !ex_ids))) return fail(LOCREC_E_INVALID_ARG, "null exclusion array");
+    return rank_segments(n_seg, seg_begin, seg_len, ids, scores, n_places, place_ids, place_region_ids, target_region_ids,
+                         max_recommendations, ex_begin, ex_len, n_excluded, ex_ids, out_ids, out_scores, out_counts, invalid_flag,
+                         host_assembled, s);
+}
+
+}  // namespace locrec
+
+extern "C" int32_t locrec_rank_recommendations_batch(int64_t n_segments, const int64_t *offsets, int64_t n, const int64_t *ids,
+                                                     const double *scores, int64_t n_places, const int64_t *place_ids,
+                                                     const int64_t *place_region_ids, const int64_t *target_region_ids,
+                                                     int64_t max_recommendations, int32_t mem, int64_t *out_ids,
+                                                     double *out_scores, int64_t *out_counts)
+try {
+    return rb_public_call(n_segments, offsets, n, ids, scores, n_places, place_ids, place_region_ids, target_region_ids,
+                          max_recommendations, false, nullptr, 0, nullptr, mem, out_ids, out_scores, out_counts);
+}
+LOCREC_CATCH_ALL
+
+extern "C" int32_t locrec_rank_recommendations_batch_excluding(int64_t n_segments, const int64_t *offsets, int64_t n,
+                                                               const int64_t *ids, const double *scores, int64_t n_places,
+                                                               const int64_t *place_ids, const int64_t *place_region_ids,
+                                                               const int64_t *target_region_ids, int64_t max_recommendations,
+                                                               const int64_t *excluded_offsets, int64_t n_excluded,
+                                                               const int64_t *excluded_ids, int32_t mem, int64_t *out_ids,
+                                                               double *out_scores, int64_t *out_counts)
+try {
+    return rb_public_call(n_segments, offsets, n, ids, scores, n_places, place_ids, place_region_ids, target_region_ids,
+                          max_recommendations, true, excluded_offsets, n_excluded, excluded_ids, mem, out_ids, out_scores,
+                          out_counts);
 }
 LOCREC_CATCH_ALL
 

@@ -22,6 +22,9 @@
 //   ranking         rank_segments_device (rank_batch.hip) once per group of requests; a group ends where the room of its
 //                   segments would pass LOCREC_SG_RANKED_ROW_BUDGET rows (a tile's requests may straddle groups: the
 //                   emit runs once per part).  The group's N rows a request then travel to the host.
+//   exclusion lists locrec_sg_recommend_ranked_batch_excluding: a caller-given list of ids per position (the places a
+//                   person has been to), uploaded once in emit order; a group's ranker call is the excluding entry with
+//                   the sub-range of its segments.  The emit and the segments' room do not see the lists.
 //   host            the pool's entry (sg_pool_ranked.h) shares sg_rk_check_args, sg_rk_verdicts, SgRkCall (groups, ranker
 //                   call, read-backs, scatter) and sg_rk_plan.h's order and groups: this entry is a pool of one member
 //
@@ -333,6 +336,10 @@ struct SgRkCall {
     int64_t n, N, n_places;
     const int64_t *d_pid, *d_preg, *d_tgt;
     int64_t *d_seg_begin, *d_seg_len;
+    // per-request exclusion lists in emit order (d_ex_begin NULL: none - the pool's entry, the plain batch): request k
+    // leaves out d_ex_ids[d_ex_begin[k] .. + d_ex_len[k]); a group's ranker call gets the sub-range of its segments
+    const int64_t *d_ex_begin = nullptr, *d_ex_len = nullptr, *d_ex_ids = nullptr;
+    int64_t n_ex = 0;
     int64_t Nd = 0;
     SgRkGroups groups;
     size_t group = 0;               // the group that is being filled
@@ -379,11 +386,17 @@ struct SgRkCall {
         if (Nd == 0) return LOCREC_OK;  // every count is 0
         int64_t *d_oid = d_out.p, *d_ocnt = d_out.p + 2 * groups.max_req * Nd;
         double *d_osc = reinterpret_cast<double *>(d_out.p + groups.max_req * Nd);
-        LOCREC_TRY(rank_segments_device(nseg, d_seg_begin + ka, d_seg_len + ka, d_row_ids, d_row_probs, n_places, d_pid, d_preg,
-                                        d_tgt + ka, Nd, d_oid, d_osc, d_ocnt, nullptr, 0, s));
+        if (d_ex_begin)
+            LOCREC_TRY(rank_segments_device_excluding(nseg, d_seg_begin + ka, d_seg_len + ka, d_row_ids, d_row_probs, n_places, d_pid,
+                                                      d_preg, d_tgt + ka, Nd, d_ex_begin + ka, d_ex_len + ka, n_ex, d_ex_ids, d_oid,
+                                                      d_osc, d_ocnt, nullptr, 0, s));
+        else
+            LOCREC_TRY(rank_segments_device(nseg, d_seg_begin + ka, d_seg_len + ka, d_row_ids, d_row_probs, n_places, d_pid, d_preg,
+                                            d_tgt + ka, Nd, d_oid, d_osc, d_ocnt, nullptr, 0, s));
         const RankBatchStats &rs = rank_batch_stats();
         stats.host_syncs += rs.host_syncs;
-        stats.readback_bytes += 32 + (rs.sorted ? 4 : 0);  // the ranker's plan header, the global path's row count
+        // the ranker's plan header (one word more with lists), the global path's row count
+        stats.readback_bytes += (d_ex_begin ? 40 : 32) + (rs.sorted ? 4 : 0);
         LOCREC_HIP_TRY(hipMemcpyAsync(h_oid.data() + ka * Nd, d_oid, (size_t)(nseg * Nd) * 8, hipMemcpyDeviceToHost, s));
         LOCREC_HIP_TRY(hipMemcpyAsync(h_osc.data() + ka * Nd, d_osc, (size_t)(nseg * Nd) * 8, hipMemcpyDeviceToHost, s));
         LOCREC_HIP_TRY(hipMemcpyAsync(h_cnt.data() + ka, d_ocnt, (size_t)nseg * 8, hipMemcpyDeviceToHost, s));
@@ -427,14 +440,14 @@ struct SgRkCall {
     }
 };
 
-}  // namespace
-
-extern "C" int32_t locrec_sg_recommend_ranked_batch(locrec_sg_graph *g, int64_t n_targets, const int64_t *vertex_ids, double alpha,
-                                                    double epsilon, int64_t max_iterations, int64_t n_places,
-                                                    const int64_t *place_ids, const int64_t *place_region_ids,
-                                                    const int64_t *target_region_ids, int64_t max_recommendations,
-                                                    int64_t *out_ids, double *out_probabilities, int64_t *out_counts,
-                                                    int64_t *out_row_counts, int64_t *out_iterations, int32_t *out_converged) try
+// both entries of the ranked batch; with_lists: position i leaves out excluded_ids[excluded_offsets[i] ..
+// excluded_offsets[i + 1]) (host arrays, refused before any device work when they are not offsets into n_excluded ids)
+int32_t sg_recommend_ranked_batch(locrec_sg_graph *g, int64_t n_targets, const int64_t *vertex_ids, double alpha, double epsilon,
+                                  int64_t max_iterations, int64_t n_places, const int64_t *place_ids,
+                                  const int64_t *place_region_ids, const int64_t *target_region_ids, int64_t max_recommendations,
+                                  bool with_lists, const int64_t *excluded_offsets, int64_t n_excluded, const int64_t *excluded_ids,
+                                  int64_t *out_ids, double *out_probabilities, int64_t *out_counts, int64_t *out_row_counts,
+                                  int64_t *out_iterations, int32_t *out_converged)
 {
     SgRankedStats &stats = sg_ranked_stats();
     stats = SgRankedStats();
@@ -443,6 +456,13 @@ extern "C" int32_t locrec_sg_recommend_ranked_batch(locrec_sg_graph *g, int64_t 
     int64_t N = 0;
     LOCREC_TRY(sg_rk_check_args(n_targets, n_places, place_ids, place_region_ids, target_region_ids, max_recommendations, out_ids,
                                 out_probabilities, out_counts, N));
+    if (with_lists) {
+        if (n_excluded < 0 || n_excluded >= ((int64_t)1 << 31)) return fail(LOCREC_E_INVALID_ARG, "excluded id count out of range [0, 2^31)");
+        if (n_targets > 0 && (!excluded_offsets || (n_excluded > 0 && !excluded_ids))) return fail(LOCREC_E_INVALID_ARG, "null array");
+        bool ok = n_targets == 0 || (excluded_offsets[0] >= 0 && excluded_offsets[n_targets] <= n_excluded);
+        for (int64_t i = 0; ok && i < n_targets; ++i) ok = excluded_offsets[i] <= excluded_offsets[i + 1];
+        if (!ok) return fail(LOCREC_E_INVALID_ARG, "excluded_offsets must be non-decreasing inside [0, n_excluded]");
+    }
     std::vector<int32_t> uniq, uniq_of;
     LOCREC_TRY(sg_batch_targets(g, n_targets, vertex_ids, epsilon, max_iterations, uniq, uniq_of));
     if (n_targets == 0) return LOCREC_OK;
@@ -518,6 +538,24 @@ extern "C" int32_t locrec_sg_recommend_ranked_batch(locrec_sg_graph *g, int64_t 
     SgRkCall rc{.stats = stats, .s = s, .n = n, .N = N, .n_places = n_places, .d_pid = d_pid, .d_preg = d_preg, .d_tgt = d_tgt,
                 .d_seg_begin = d_seg_begin, .d_seg_len = d_seg_len};
     LOCREC_TRY(rc.plan(d_caps, (size_t)R, req.data() + 2 * n, nu));
+    DevBuf<int64_t> d_ex;  // the lists, uploaded once: begins and lengths in emit order, then the ids
+    std::vector<int64_t> xr;
+    if (with_lists) {
+        xr.resize((size_t)(2 * n));
+        for (int64_t k = 0; k < n; ++k) {
+            const int64_t i = ord[(size_t)k];
+            xr[(size_t)k] = excluded_offsets[i];
+            xr[(size_t)(n + k)] = excluded_offsets[i + 1] - excluded_offsets[i];
+        }
+        LOCREC_TRY(d_ex.alloc((size_t)(2 * n + n_excluded)));
+        LOCREC_HIP_TRY(hipMemcpyAsync(d_ex.p, xr.data(), (size_t)(2 * n) * 8, hipMemcpyHostToDevice, s));
+        if (n_excluded > 0)
+            LOCREC_HIP_TRY(hipMemcpyAsync(d_ex.p + 2 * n, excluded_ids, (size_t)n_excluded * 8, hipMemcpyHostToDevice, s));
+        rc.d_ex_begin = d_ex.p;
+        rc.d_ex_len = d_ex.p + n;
+        rc.d_ex_ids = d_ex.p + 2 * n;
+        rc.n_ex = n_excluded;
+    }
     DevBuf<unsigned char> d_state;
     LOCREC_TRY(d_state.alloc(kRkStateBytes));
 
@@ -563,6 +601,35 @@ extern "C" int32_t locrec_sg_recommend_ranked_batch(locrec_sg_graph *g, int64_t 
     const int32_t status = sg_batch_tiles(g, uniq, alpha, epsilon, max_iterations, ctx, after_tile);
     return rc.finish(status, ctx.polls, order, member_of, uniq_of, out_ids, out_probabilities, out_counts, out_row_counts,
                      out_iterations, out_converged);
+}
+
+}  // namespace
+
+extern "C" int32_t locrec_sg_recommend_ranked_batch(locrec_sg_graph *g, int64_t n_targets, const int64_t *vertex_ids, double alpha,
+                                                    double epsilon, int64_t max_iterations, int64_t n_places,
+                                                    const int64_t *place_ids, const int64_t *place_region_ids,
+                                                    const int64_t *target_region_ids, int64_t max_recommendations,
+                                                    int64_t *out_ids, double *out_probabilities, int64_t *out_counts,
+                                                    int64_t *out_row_counts, int64_t *out_iterations, int32_t *out_converged) try
+{
+    return sg_recommend_ranked_batch(g, n_targets, vertex_ids, alpha, epsilon, max_iterations, n_places, place_ids, place_region_ids,
+                                     target_region_ids, max_recommendations, false, nullptr, 0, nullptr, out_ids, out_probabilities,
+                                     out_counts, out_row_counts, out_iterations, out_converged);
+} LOCREC_CATCH_ALL
+
+extern "C" int32_t locrec_sg_recommend_ranked_batch_excluding(locrec_sg_graph *g, int64_t n_targets, const int64_t *vertex_ids,
+                                                              double alpha, double epsilon, int64_t max_iterations,
+                                                              int64_t n_places, const int64_t *place_ids,
+                                                              const int64_t *place_region_ids, const int64_t *target_region_ids,
+                                                              int64_t max_recommendations, const int64_t *excluded_offsets,
+                                                              int64_t n_excluded, const int64_t *excluded_ids, int64_t *out_ids,
+                                                              double *out_probabilities, int64_t *out_counts,
+                                                              int64_t *out_row_counts, int64_t *out_iterations,
+                                                              int32_t *out_converged) try
+{
+    return sg_recommend_ranked_batch(g, n_targets, vertex_ids, alpha, epsilon, max_iterations, n_places, place_ids, place_region_ids,
+                                     target_region_ids, max_recommendations, true, excluded_offsets, n_excluded, excluded_ids,
+                                     out_ids, out_probabilities, out_counts, out_row_counts, out_iterations, out_converged);
 } LOCREC_CATCH_ALL
 
 extern "C" int32_t locrec_sg_recommend_ranked_batch_stats(int64_t *out_tiles, int64_t *out_groups, int64_t *out_emitted_rows,

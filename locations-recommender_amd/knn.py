@@ -267,28 +267,30 @@ class KnnIndex:
         return pl, reg, tgt, width, out
 
     def recommend_ranked_batch(self, person_ids, pw, cw, k, place_ids, place_region_ids, target_region_ids,
-                               max_recommendations):
+                               max_recommendations, unvisited=False):
         """The batched request to its end (locrec_knn_recommend_ranked_batch): makeRecommendations for every person,
         then per person the places of its target region, top max_recommendations by estimated rating - ranked on the
         device.  -> (place_ids[nq, W], estimated_ratings[nq, W], counts[nq]), rows padded with -1 / 0.0, in the
-        caller's order; W = min(max_recommendations, number of places)."""
+        caller's order; W = min(max_recommendations, number of places).
+        unvisited=True (locrec_knn_recommend_ranked_batch_unvisited): only new places - a person's ranking leaves out
+        the places the index holds a rating of that person for."""
         q = L.as_i64(person_ids)
         pl, reg, tgt, width, (oi, osc, cnt) = self._ranked_args(len(q), place_ids, place_region_ids, target_region_ids,
                                                                 max_recommendations)
-        L.check(L.lib().locrec_knn_recommend_ranked_batch(self._h, len(q), L.ptr(q, C.c_int64), float(pw), float(cw), int(k),
-                                                          len(pl), L.ptr(pl, C.c_int64), L.ptr(reg, C.c_int64),
-                                                          L.ptr(tgt, C.c_int64), width, L.ptr(oi, C.c_int64),
-                                                          L.ptr(osc, C.c_double), L.ptr(cnt, C.c_int64)))
+        call = L.lib().locrec_knn_recommend_ranked_batch_unvisited if unvisited else L.lib().locrec_knn_recommend_ranked_batch
+        L.check(call(self._h, len(q), L.ptr(q, C.c_int64), float(pw), float(cw), int(k), len(pl), L.ptr(pl, C.c_int64),
+                     L.ptr(reg, C.c_int64), L.ptr(tgt, C.c_int64), width, L.ptr(oi, C.c_int64), L.ptr(osc, C.c_double),
+                     L.ptr(cnt, C.c_int64)))
         return oi, osc, cnt
 
-    def fetch_ranked(self, nq, place_ids, place_region_ids, target_region_ids, max_recommendations):
-        """The same last stage for the range recommend_range_async left on the device (locrec_knn_fetch_ranked):
-        target_region_ids[i] belongs to internal row first + i."""
+    def fetch_ranked(self, nq, place_ids, place_region_ids, target_region_ids, max_recommendations, unvisited=False):
+        """The same last stage for the range recommend_range_async left on the device (locrec_knn_fetch_ranked, or
+        locrec_knn_fetch_ranked_unvisited): target_region_ids[i] belongs to internal row first + i."""
         pl, reg, tgt, width, (oi, osc, cnt) = self._ranked_args(int(nq), place_ids, place_region_ids, target_region_ids,
                                                                 max_recommendations)
-        L.check(L.lib().locrec_knn_fetch_ranked(self._h, int(nq), len(pl), L.ptr(pl, C.c_int64), L.ptr(reg, C.c_int64),
-                                                L.ptr(tgt, C.c_int64), width, L.ptr(oi, C.c_int64), L.ptr(osc, C.c_double),
-                                                L.ptr(cnt, C.c_int64)))
+        call = L.lib().locrec_knn_fetch_ranked_unvisited if unvisited else L.lib().locrec_knn_fetch_ranked
+        L.check(call(self._h, int(nq), len(pl), L.ptr(pl, C.c_int64), L.ptr(reg, C.c_int64), L.ptr(tgt, C.c_int64), width,
+                     L.ptr(oi, C.c_int64), L.ptr(osc, C.c_double), L.ptr(cnt, C.c_int64)))
         return oi, osc, cnt
 
     def query_shard(self, person_id, pw, cw, k, shard_index, shard_count):

@@ -205,10 +205,11 @@ def rank_recommendations_batch(offsets, ids, scores, place_ids, place_region_ids
 
 
 def knn_recommend_places_batch(data_dir, region_ids, requests, place_weight, category_weight, k_nearest,
-                               max_recommendations=10):
+                               max_recommendations=10, new_places=False):
     """Many requests of one region pair to their end (KnnRecommenderMain.scala:53-67 and :90-101): requests is a
     sequence of (person_id, target_region_id); the index comes from the handle cache, the places from load_places.
-    -> (place_ids[n, W], estimated_ratings[n, W], counts[n]), ranked on the device."""
+    -> (place_ids[n, W], estimated_ratings[n, W], counts[n]), ranked on the device.
+    new_places=True: the places a person has a place_ratings row for are left out (the unvisited ranked batch)."""
     from . import _cache
     from .knn import KnnIndex
     _cache.require_gpu_backend("knn_recommend_places_batch")
@@ -221,30 +222,39 @@ def knn_recommend_places_batch(data_dir, region_ids, requests, place_weight, cat
     try:
         with ix.lock:
             return ix.recommend_ranked_batch(persons, place_weight, category_weight, k_nearest, place_ids, place_regions,
-                                             targets, max_recommendations)
+                                             targets, max_recommendations, unvisited=new_places)
     finally:
         ix.close()  # drops the reference only
 
 
 def sg_recommend_places_batch(data_dir, region_ids, requests, epsilon, max_iterations, alpha=0.15, max_recommendations=10,
-                              on_device=True):
+                              on_device=True, new_places=False):
     """Many requests of one region pair (StochasticRecommenderMain.scala:53-75): requests is a sequence of
     (vertex_id, target_region_id).  -> (ids[n, W], probabilities[n, W], counts[n], iterations[n], converged[n]),
-    emitted and ranked on the device (on_device=False: the host rows through the segmented ranker, the same result)."""
+    emitted and ranked on the device (on_device=False: the host rows through the segmented ranker, the same result).
+    new_places=True: the targets of a vertex's out-edges in the region set's edge list are left out of its ranking."""
     from . import _cache
     from .stochastic import SgGraph
     _cache.require_gpu_backend("sg_recommend_places_batch")
     vertices = np.asarray([r[0] for r in requests], np.int64)
     targets = np.asarray([r[1] for r in requests], np.int64)
     place_ids, place_regions = load_places(data_dir)
+    excluded = _sg_visited_lists(data_dir, region_ids, vertices) if new_places else None
     key = _cache.files_key([generate_file_name(region_ids, data_dir, "stochastic_graph")])
     g = SgGraph.through_cache(key, lambda: sg_graph_from_parquet(data_dir, region_ids))
     try:
         with g.lock:
             return g.recommend_ranked_batch(vertices, alpha, epsilon, max_iterations, place_ids, place_regions, targets,
-                                            max_recommendations, on_device=on_device)
+                                            max_recommendations, on_device=on_device, excluded=excluded)
     finally:
         g.close()
+
+
+def _sg_visited_lists(data_dir, region_ids, vertex_ids):
+    """The exclusion lists of new_places for vertices of one region set: out_neighbours over its edge Parquet."""
+    from .stochastic import out_neighbours
+    source_ids, target_ids, _ = load_stochastic_graph(generate_file_name(region_ids, data_dir, "stochastic_graph"))
+    return out_neighbours(source_ids, target_ids, vertex_ids)
 
 
 def build_with_balanced_weights(betas, all_edges):
@@ -574,12 +584,18 @@ def calc_recommender_target(persons, person_id_input_region_id):
     return int(person_id), home, home if input_region is None else int(input_region)
 
 
-def knn_recommender_request(data_dir, persons, line, place_weight, category_weight, k_nearest, max_recommendations=10):
+def knn_recommender_request(data_dir, persons, line, place_weight, category_weight, k_nearest, max_recommendations=10,
+                            new_places=False):
     """The body of KnnRecommenderMain's loop for one input line (KnnRecommenderMain.scala:36-51,90-101): parse, resolve
     the target, recommend from the region set [home, target], rank against the target region's places on the device.
-    -> ((person_id, home_region_id, target_region_id), place_ids, estimated_ratings)."""
+    -> ((person_id, home_region_id, target_region_id), place_ids, estimated_ratings).
+    new_places=True: without the places the person has rated (knn_recommend_places_batch's, for the one request)."""
     from . import prep
     target = calc_recommender_target(persons, parse_input(line))
+    if new_places:
+        oi, osc, cnt = knn_recommend_places_batch(data_dir, [target[1], target[2]], [(target[0], target[2])], place_weight,
+                                                  category_weight, k_nearest, max_recommendations, new_places=True)
+        return target, np.array(oi[0, :cnt[0]]), np.array(osc[0, :cnt[0]])
     ids, scores = knn_make_recommendations(data_dir, [target[1], target[2]], target[0], place_weight, category_weight, k_nearest)
     place_ids, place_regions = load_places(data_dir)
     return (target,) + tuple(prep.rank_recommendations(ids, scores, place_ids, place_regions, target[2], max_recommendations))
@@ -597,6 +613,22 @@ def knn_recommender_requests(data_dir, persons, lines, place_weight, category_we
     what knn_recommender_request returns for that line, or the exception instance that function would have raised.
     pooled=False: one KnnIndex.recommend_ranked_batch call per distinct index instead of the pool call (the same
     result; what a queue cost before the pool)."""
+    return _knn_recommender_requests(data_dir, persons, lines, place_weight, category_weight, k_nearest, max_recommendations,
+                                     pooled, False)
+
+
+def knn_recommender_requests_new_places(data_dir, persons, lines, place_weight, category_weight, k_nearest,
+                                        max_recommendations=10):
+    """knn_recommender_requests recommending only new places (that function's signature is fixed, so this is its sibling,
+    as sg_recommender_requests_ranked is): every line's ranking leaves out the places its person has rated - what
+    knn_recommender_request returns for the line with new_places=True, or the exception instance.  Served through
+    _knn_requests_per_index by one unvisited ranked batch per distinct index; the pool has no unvisited form."""
+    return _knn_recommender_requests(data_dir, persons, lines, place_weight, category_weight, k_nearest, max_recommendations,
+                                     False, True)
+
+
+def _knn_recommender_requests(data_dir, persons, lines, place_weight, category_weight, k_nearest, max_recommendations, pooled,
+                              new_places):
     from . import _cache
     from .knn import KnnPool
     _cache.require_gpu_backend("knn_recommender_requests")
@@ -604,13 +636,13 @@ def knn_recommender_requests(data_dir, persons, lines, place_weight, category_we
     try:
         if targets:
             place_ids, place_regions = load_places(data_dir)
-            pool = KnnPool(indexes) if pooled else None
+            pool = KnnPool(indexes) if pooled and not new_places else None
             try:
                 def call(gi, v, live):
                     regions = np.asarray([targets[i][0][2] for i in live], np.int64)
                     if pool is None:
                         return _knn_requests_per_index(indexes, gi, v, place_weight, category_weight, k_nearest, place_ids,
-                                                       place_regions, regions, max_recommendations)
+                                                       place_regions, regions, max_recommendations, unvisited=new_places)
                     return pool.recommend_ranked_batch(gi, v, place_weight, category_weight, k_nearest, place_ids, place_regions,
                                                        regions, max_recommendations)
                 live, rows = _call_without_bad_lines(out, targets, call)
@@ -627,7 +659,8 @@ def knn_recommender_requests(data_dir, persons, lines, place_weight, category_we
     return out
 
 
-def _knn_requests_per_index(indexes, index_of, person_ids, pw, cw, k, place_ids, place_regions, regions, max_recommendations):
+def _knn_requests_per_index(indexes, index_of, person_ids, pw, cw, k, place_ids, place_regions, regions, max_recommendations,
+                            unvisited=False):
     """KnnPool.recommend_ranked_batch's result from one KnnIndex.recommend_ranked_batch call per distinct index; an unknown
     person raises with bad_request = the position of a request that names it, as the pool call does."""
     n = len(person_ids)
@@ -638,7 +671,8 @@ def _knn_requests_per_index(indexes, index_of, person_ids, pw, cw, k, place_ids,
         try:
             with indexes[k_ix].lock:
                 oi[at], osc[at], cnt[at] = indexes[k_ix].recommend_ranked_batch(person_ids[at], pw, cw, k, place_ids, place_regions,
-                                                                                regions[at], max_recommendations)
+                                                                                regions[at], max_recommendations,
+                                                                                unvisited=unvisited)
         except L.IllegalArgumentException as e:
             head, _, unknown = str(e).rpartition(": ")
             if head == "No such person":  # (the library checks the ids in order and names the first)
@@ -647,11 +681,17 @@ def _knn_requests_per_index(indexes, index_of, person_ids, pw, cw, k, place_ids,
     return oi, osc, cnt
 
 
-def sg_recommender_request(data_dir, persons, line, epsilon, max_iterations, max_recommendations=10):
+def sg_recommender_request(data_dir, persons, line, epsilon, max_iterations, max_recommendations=10, new_places=False):
     """The body of StochasticRecommenderMain's loop for one input line (StochasticRecommenderMain.scala:36-51,64-75).
-    -> ((person_id, home_region_id, target_region_id), ids, probabilities)."""
+    -> ((person_id, home_region_id, target_region_id), ids, probabilities).
+    new_places=True: without the targets of the person's out-edges (sg_recommend_places_batch's, for the one request)."""
     from . import prep
     target = calc_recommender_target(persons, parse_input(line))
+    if new_places:
+        from .stochastic import ALPHA
+        oi, op, cnt, _, _ = sg_recommend_places_batch(data_dir, [target[1], target[2]], [(target[0], target[2])], epsilon,
+                                                      max_iterations, ALPHA, max_recommendations, new_places=True)
+        return target, np.array(oi[0, :cnt[0]]), np.array(op[0, :cnt[0]])
     ids, scores, _, _ = sg_make_recommendations(data_dir, [target[1], target[2]], target[0], epsilon, max_iterations)
     place_ids, place_regions = load_places(data_dir)
     return (target,) + tuple(prep.rank_recommendations(ids, scores, place_ids, place_regions, target[2], max_recommendations))
@@ -666,6 +706,18 @@ def sg_recommender_requests(data_dir, persons, lines, epsilon, max_iterations, m
     sg_recommender_request returns for that line, or the exception instance that function would have raised (the
     reference wraps each line in Try, :44-49).  pooled=False: one SgGraph.recommend_batch call per distinct graph instead
     of the pool call (the same result; the A/B partner)."""
+    return _sg_recommender_requests(data_dir, persons, lines, epsilon, max_iterations, max_recommendations, pooled, False)
+
+
+def sg_recommender_requests_new_places(data_dir, persons, lines, epsilon, max_iterations, max_recommendations=10, pooled=True):
+    """sg_recommender_requests recommending only new places (that function's signature is fixed, so this is its sibling,
+    as sg_recommender_requests_ranked is): every line's ranking leaves out the targets of its person's out-edges in the
+    edge Parquet of its region set (load_stochastic_graph, out_neighbours), ranked by the excluding form of the segmented
+    ranker - what sg_recommender_request returns for the line with new_places=True, or the exception instance."""
+    return _sg_recommender_requests(data_dir, persons, lines, epsilon, max_iterations, max_recommendations, pooled, True)
+
+
+def _sg_recommender_requests(data_dir, persons, lines, epsilon, max_iterations, max_recommendations, pooled, new_places):
     from . import _cache, prep
     from .stochastic import ALPHA, SgPool
     _cache.require_gpu_backend("sg_recommender_requests")
@@ -684,7 +736,24 @@ def sg_recommender_requests(data_dir, persons, lines, epsilon, max_iterations, m
             off, ids, probs, _, _ = rows
             place_ids, place_regions = load_places(data_dir)
             regions = np.asarray([targets[i][0][2] for i in live], np.int64)
-            oi, op, cnt = prep.rank_recommendations_batch(off, ids, probs, place_ids, place_regions, regions, max_recommendations)
+            if new_places:
+                # one edge list per distinct graph; the lists in the lines' order
+                v = np.asarray([targets[i][0][0] for i in live], np.int64)
+                gi = np.asarray([targets[i][1] for i in live], np.int32)
+                lists = [None] * len(live)
+                for g_ix in np.unique(gi):
+                    at = np.flatnonzero(gi == g_ix)
+                    home, region = targets[live[at[0]]][0][1:3]
+                    xoff, xids = _sg_visited_lists(data_dir, [home, region], v[at])
+                    for j, k in enumerate(at):
+                        lists[k] = xids[xoff[j]:xoff[j + 1]]
+                xoff = np.zeros(len(live) + 1, np.int64)
+                np.cumsum([len(x) for x in lists], out=xoff[1:])
+                oi, op, cnt = prep.rank_recommendations_batch_excluding(off, ids, probs, place_ids, place_regions, regions,
+                                                                        max_recommendations, xoff,
+                                                                        np.concatenate(lists).astype(np.int64))
+            else:
+                oi, op, cnt = prep.rank_recommendations_batch(off, ids, probs, place_ids, place_regions, regions, max_recommendations)
             for k, i in enumerate(live):
                 out[i] = (targets[i][0], np.array(oi[k, :cnt[k]]), np.array(op[k, :cnt[k]]))
     finally:

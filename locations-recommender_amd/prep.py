@@ -9,6 +9,7 @@ SURVEY.md 8f rows f-2 and f-4) behind the names of the reference's builder objec
     distance_meters              Location.distanceMeters                  Location.scala:30-38
     rank_recommendations         printRecommendations of both mains       knn/KnnRecommenderMain.scala:90-101
     rank_recommendations_batch   ... for every segment of a batch's rows   (the same lines, per person)
+    rank_recommendations_batch_excluding   ... leaving out a list of ids per segment (no counterpart: only new places)
     calc_person_likes_place_edges / calc_person_likes_category_edges / calc_category_selected_place_edges
                                  the three counted edge families          stochastic/PersonLikesPlace.scala:12-37 (and siblings)
     calc_place_similar_place_edges  PlaceSimilarPlace.calcPlaceSimilarPlaceEdges
@@ -208,6 +209,32 @@ def rank_recommendations_batch(offsets, ids, scores, place_ids, place_region_ids
     t = c.col(target_region_ids, np.int64)
     (oi, oip), (osc, oscp), (oc, ocp) = c.out(nseg * width, np.int64), c.out(nseg * width, np.float64), c.out(nseg, np.int64)
     L.check(L.lib().locrec_rank_recommendations_batch(nseg, o, n, a[0], a[1], npl, p[0], p[1], t, width, c.mem, oip, oscp, ocp))
+    if nseg == 0 or width == 0:
+        oc[:nseg] = 0
+    return oi[:nseg * width].reshape(nseg, width), osc[:nseg * width].reshape(nseg, width), oc[:nseg]
+
+
+def rank_recommendations_batch_excluding(offsets, ids, scores, place_ids, place_region_ids, target_region_ids,
+                                         max_recommendations, excluded_offsets, excluded_ids):
+    """rank_recommendations_batch that leaves out, per segment, the ids of a list
+    (locrec_rank_recommendations_batch_excluding): segment s ranks its rows whose id is not in
+    excluded_ids[excluded_offsets[s]:excluded_offsets[s + 1]].  Host or device arrays, all of one kind; the result has
+    rank_recommendations_batch's layout, and W is cut to the longest segment as there."""
+    if not _is_tensor(offsets):
+        offsets = np.asarray(offsets, np.int64)
+    c = _Cols(offsets, ids, scores, place_ids, place_region_ids, target_region_ids, excluded_offsets, excluded_ids)
+    nseg, n, npl, nex = len(target_region_ids), len(ids), len(place_ids), len(excluded_ids)
+    assert len(offsets) == nseg + 1 and len(scores) == n and len(place_region_ids) == npl and len(excluded_offsets) == nseg + 1
+    longest = int((offsets[1:] - offsets[:-1]).max()) if nseg else 0
+    width = max(0, min(int(max_recommendations), longest, n))
+    o = c.col(offsets, np.int64)
+    a = [c.col(ids, np.int64), c.col(scores, np.float64)]
+    p = [c.col(place_ids, np.int64), c.col(place_region_ids, np.int64)]
+    t = c.col(target_region_ids, np.int64)
+    x = [c.col(excluded_offsets, np.int64), c.col(excluded_ids, np.int64)]
+    (oi, oip), (osc, oscp), (oc, ocp) = c.out(nseg * width, np.int64), c.out(nseg * width, np.float64), c.out(nseg, np.int64)
+    L.check(L.lib().locrec_rank_recommendations_batch_excluding(nseg, o, n, a[0], a[1], npl, p[0], p[1], t, width, x[0], nex, x[1],
+                                                                c.mem, oip, oscp, ocp))
     if nseg == 0 or width == 0:
         oc[:nseg] = 0
     return oi[:nseg * width].reshape(nseg, width), osc[:nseg * width].reshape(nseg, width), oc[:nseg]

@@ -9,6 +9,30 @@ from . import _lib as L
 ALPHA = 0.15  # StochasticRecommender.scala:38
 
 
+def out_neighbours(source_ids, target_ids, vertex_ids):
+    """The targets of each requested vertex's out-edges in the edge list (source_ids, target_ids) - for a person vertex
+    the places and categories it likes, the walk's first hop: the exclusion lists of "only new places".
+    -> (offsets[n + 1], ids): the list of vertex_ids[i] is ids[offsets[i]:offsets[i + 1]], ascending, without
+    duplicates; empty for a vertex without out-edges or unknown to the edge list; a vertex asked twice gets its list
+    twice.  numpy on the host: the edge list is cut down to the requested sources first (np.isin), so only those edges
+    are sorted, never all E."""
+    s, t, v = L.as_i64(source_ids), L.as_i64(target_ids), L.as_i64(vertex_ids)
+    if len(s) != len(t):
+        raise L.IllegalArgumentException("edge columns of different lengths")
+    keep = np.isin(s, v)
+    s, t = s[keep], t[keep]
+    order = np.lexsort((t, s))
+    s, t = s[order], t[order]
+    first = np.ones(len(s), bool)
+    first[1:] = (s[1:] != s[:-1]) | (t[1:] != t[:-1])   # parallel edges: one entry
+    s, t = s[first], t[first]
+    lo, hi = np.searchsorted(s, v, "left"), np.searchsorted(s, v, "right")
+    offsets = np.zeros(len(v) + 1, np.int64)
+    np.cumsum(hi - lo, out=offsets[1:])
+    ids = t[np.repeat(lo - offsets[:-1], hi - lo) + np.arange(offsets[-1])]
+    return offsets, np.ascontiguousarray(ids, np.int64)
+
+
 class SgGraph:
     """Owner of a locrec_sg_graph handle."""
 
@@ -130,19 +154,30 @@ class SgGraph:
     RANKED_BATCH_STATS = ("tiles", "groups", "emitted_rows", "readback_bytes", "host_syncs")
 
     def recommend_ranked_batch(self, vertex_ids, alpha, epsilon, max_iterations, place_ids, place_region_ids,
-                               target_region_ids, max_recommendations, on_device=True):
+                               target_region_ids, max_recommendations, on_device=True, excluded=None):
         """The batched request to its end: per vertex the places of its target region, top max_recommendations by
         probability.  on_device=True (locrec_sg_recommend_ranked_batch): the rows are emitted into per-request
         segments and ranked on the device, x never leaves it and max_recommendations rows a request come back.
         on_device=False: recommend_batch's host rows through prep.rank_recommendations_batch (the same result; the
         A/B partner).
+        excluded=(offsets[n + 1], ids): position i leaves out ids[offsets[i]:offsets[i + 1]] - the places a person has
+        been to, from out_neighbours - (locrec_sg_recommend_ranked_batch_excluding; on the host path
+        prep.rank_recommendations_batch_excluding).
         -> (ids[n, W], probabilities[n, W], counts[n], iterations[n], converged[n]), rows padded with -1 / 0.0;
         W = max_recommendations cut to the longest row count of a vertex."""
+        if excluded is not None:
+            xoff, xids = L.as_i64(excluded[0]), L.as_i64(excluded[1])
+            if len(xoff) != len(vertex_ids) + 1:
+                raise L.IllegalArgumentException("one exclusion list per vertex is required: offsets of n + 1 entries")
         if not on_device:
             from . import prep
             off, ids, probs, its, conv = self.recommend_batch(vertex_ids, alpha, epsilon, max_iterations)
-            oi, op, cnt = prep.rank_recommendations_batch(off, ids, probs, place_ids, place_region_ids, target_region_ids,
-                                                          max_recommendations)
+            if excluded is not None:
+                oi, op, cnt = prep.rank_recommendations_batch_excluding(off, ids, probs, place_ids, place_region_ids,
+                                                                        target_region_ids, max_recommendations, xoff, xids)
+            else:
+                oi, op, cnt = prep.rank_recommendations_batch(off, ids, probs, place_ids, place_region_ids, target_region_ids,
+                                                              max_recommendations)
             return oi, op, cnt, its, conv
         v, pl, reg, tgt = L.as_i64(vertex_ids), L.as_i64(place_ids), L.as_i64(place_region_ids), L.as_i64(target_region_ids)
         n = len(v)
@@ -152,10 +187,15 @@ class SgGraph:
         stride = max(0, min(int(max_recommendations), self.info()["vertices"]))
         oi, op = np.full((n, stride), -1, np.int64), np.zeros((n, stride), np.float64)
         cnt, rows, its, conv = (np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, np.int32))
-        L.check(L.lib().locrec_sg_recommend_ranked_batch(
-            self._h, n, L.ptr(v, C.c_int64), float(alpha), float(epsilon), int(max_iterations), len(pl), L.ptr(pl, C.c_int64),
-            L.ptr(reg, C.c_int64), L.ptr(tgt, C.c_int64), stride, L.ptr(oi, C.c_int64), L.ptr(op, C.c_double),
-            L.ptr(cnt, C.c_int64), L.ptr(rows, C.c_int64), L.ptr(its, C.c_int64), L.ptr(conv, C.c_int32)))
+        head = (self._h, n, L.ptr(v, C.c_int64), float(alpha), float(epsilon), int(max_iterations), len(pl), L.ptr(pl, C.c_int64),
+                L.ptr(reg, C.c_int64), L.ptr(tgt, C.c_int64), stride)
+        outs = (L.ptr(oi, C.c_int64), L.ptr(op, C.c_double), L.ptr(cnt, C.c_int64), L.ptr(rows, C.c_int64),
+                L.ptr(its, C.c_int64), L.ptr(conv, C.c_int32))
+        if excluded is not None:
+            L.check(L.lib().locrec_sg_recommend_ranked_batch_excluding(*head, L.ptr(xoff, C.c_int64), len(xids),
+                                                                       L.ptr(xids, C.c_int64), *outs))
+        else:
+            L.check(L.lib().locrec_sg_recommend_ranked_batch(*head, *outs))
         width = max(0, min(stride, int(rows.max()) if n else 0))
         return (np.ascontiguousarray(oi[:, :width]), np.ascontiguousarray(op[:, :width]), cnt, its, conv.astype(bool))
 
