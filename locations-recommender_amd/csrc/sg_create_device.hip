@@ -7,28 +7,29 @@
 // arrays instead of being shared; the contract is that both builders leave the SAME handle, element for element
 // ("Device build"; tests/test_gpu_sg_device_build.py compares them).
 //
+// The host side is sg_create_device_impl at the end: named phases over one Build, in the order they run.  What the host
+// decides or computes about the layout - the plan from the scan's totals with its two refusals, the id-table and
+// 16-bit-column rules, radix bits, byte figures, persist_pw - is sg_layout_plan.h's (plain C++, checked stand-alone by
+// tests/host/sg_layout_plan_check.cpp against a row-by-row walk of the layout); no phase keeps an expression of its own
+// for any of it, and the kernels take their three per-row rules from the same header.
+//
 // Nothing here takes a position from an atomic: every position is a stable radix sort's or a scan's, so the layout does
 // not depend on scheduling.  The only atomics are the integer min / max of the id range.
 
 #include "sg_batch.hip"
 
 #include "offline.h"
+#include "sg_layout_plan.h"
 
 namespace {
+
+static_assert(kSgPlanSlots == kSlots && kSgPlanLongRow == kLongRow && kSgPlanDictMax == kDictMax,
+              "sg_layout_plan.h carries sg.hip's constants");
 
 constexpr int kDbThreads = 256;
 
 __device__ __forceinline__ unsigned long long db_min(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
 __device__ __forceinline__ unsigned long long db_max(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
-
-// the remainder class of sg_create_impl: ceil_log2((rem + 3) / 4), rem in 1 .. 255
-__device__ __forceinline__ int db_class(int rem)
-{
-    const int v = (rem + 3) / 4;
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return l;
-}
 
 // per-row counters scanned together: c[0..6] = rows of remainder class 0..6 so far, c[7] = full pieces so far
 struct DbCnt {
@@ -44,11 +45,11 @@ struct DbCntPlus {
     }
 };
 
-// what the row, piece and edge kernels need of the plan (host-computed from the eight totals)
+// what the row, piece and edge kernels need of the plan (SgLayoutPlan's 32-bit part)
 struct DbPlan {
     int32_t piece_begin[7], part_begin[7];
     int32_t nfull_total, T, n_short;
-    int32_t long_base;  // long_begin[l] = long_base + full_begin[l] + l
+    int32_t long_base;  // sg_long_begin
 };
 
 // ---- vertex ranking ------------------------------------------------------------------------------------------------
@@ -148,7 +149,7 @@ __global__ __launch_bounds__(kDbThreads) void sg_db_live_flags(int64_t nv, const
     unsigned long long f = 0;
     if (v < nv) {
         const int d = vend[v] - vbeg[v];
-        if (d > 0) f = d / kSlots > 2 ? 1ull << 32 : 1ull;
+        if (d > 0) f = sg_in_long_area(d) ? 1ull << 32 : 1ull;
     }
     fl[v] = f;
 }
@@ -163,7 +164,7 @@ __global__ __launch_bounds__(kDbThreads) void sg_db_live(int64_t nv, const int32
     const int d = vend[v] - vbeg[v];
     int32_t l = -1;
     if (d > 0) {
-        l = d / kSlots > 2 ? n_short + (int32_t)(sc[v] >> 32) : (int32_t)(sc[v] & 0xFFFFFFFFull);
+        l = sg_in_long_area(d) ? n_short + (int32_t)(sc[v] >> 32) : (int32_t)(sc[v] & 0xFFFFFFFFull);
         live_vertex[l] = (int32_t)v;
     }
     live_of[v] = l;
@@ -183,7 +184,7 @@ __global__ __launch_bounds__(kDbThreads) void sg_db_row_counts(int32_t T, const 
         const int rem = d % kSlots;
         c.c[7] = d / kSlots;
         if (rem > 0) {
-            const int k = db_class(rem);
+            const int k = sg_remainder_class(rem);
 #pragma unroll
             for (int i = 0; i < 7; ++i)
                 if (i == k) c.c[i] = 1;
@@ -207,7 +208,7 @@ __global__ __launch_bounds__(kDbThreads) void sg_db_row_maps(DbPlan P, const int
     const int32_t full_begin = s.c[7];
     int32_t rem_part = -1, rem_slot0 = -1;
     if (rem > 0) {
-        const int c = db_class(rem);
+        const int c = sg_remainder_class(rem);
         int32_t k = 0;
 #pragma unroll
         for (int i = 0; i < 7; ++i)
@@ -218,12 +219,12 @@ __global__ __launch_bounds__(kDbThreads) void sg_db_row_maps(DbPlan P, const int
     }
     rowinfo[l] = make_int2(full_begin, rem_slot0);
     const bool in_long_area = l >= P.n_short;
-    const int32_t long_begin = P.long_base + full_begin + l;
+    const int32_t long_begin = sg_long_begin(P.long_base, full_begin, l);
     for (int j = 0; j < nfull; ++j) seg_out[full_begin + j] = in_long_area ? long_begin + j : 3 * l + j;
     if (rem_part >= 0) seg_out[rem_part] = in_long_area ? long_begin + nfull : 3 * l + 2;
     if (in_long_area) {
         lrows_in_order[l - P.n_short] = make_int4(l, long_begin, nfull, rem_part >= 0 ? 1 : 0);
-        crow[l - P.n_short] = nfull > kLongRow ? 1 : 0;
+        crow[l - P.n_short] = sg_wave_row(nfull) ? 1 : 0;
     }
 }
 
@@ -233,7 +234,7 @@ __global__ __launch_bounds__(kDbThreads) void sg_db_lrows_partition(int32_t n, c
     const int32_t i = (int32_t)(blockIdx.x * kDbThreads + threadIdx.x);
     if (i >= n) return;
     const int4 r = in[i];
-    out[r.z > kLongRow ? pos[i] : pos[n] + (i - pos[i])] = r;
+    out[sg_wave_row(r.z) ? pos[i] : pos[n] + (i - pos[i])] = r;
 }
 
 __global__ __launch_bounds__(kDbThreads) void sg_db_pinfo(int32_t np, DbPlan P, int2 *pinfo)
@@ -323,13 +324,6 @@ struct DbStats {
 };
 thread_local DbStats g_db_stats;
 
-int db_bits(int64_t n)  // radix bits that hold every key below n
-{
-    int b = 1;
-    while (((int64_t)1 << b) < n) ++b;
-    return b;
-}
-
 int32_t db_device_array(const void *p, int device, const char *what)
 {
     hipPointerAttribute_t a;
@@ -342,15 +336,381 @@ int32_t db_device_array(const void *p, int device, const char *what)
     return LOCREC_OK;
 }
 
-// the weight dictionary, exactly as sg_create_impl builds it from the uploaded weights (see the comment there)
-int32_t db_dictionary(locrec_sg_graph *g, int64_t np)
+// the experiments keep their host-only extra layouts: one copy of the columns to the host, then the host build
+int32_t db_host_build(int64_t ne, const int64_t *src, const int64_t *dst, const double *w, locrec_sg_graph **out)
 {
-    const size_t nslots = (size_t)np * kSlots;
-    hipStream_t s = g->stream;
+    std::vector<int64_t> hs((size_t)ne), ht((size_t)ne);
+    std::vector<double> hw((size_t)ne);
+    LOCREC_HIP_TRY(hipMemcpy(hs.data(), src, (size_t)ne * 8, hipMemcpyDeviceToHost));
+    LOCREC_HIP_TRY(hipMemcpy(ht.data(), dst, (size_t)ne * 8, hipMemcpyDeviceToHost));
+    LOCREC_HIP_TRY(hipMemcpy(hw.data(), w, (size_t)ne * 8, hipMemcpyDeviceToHost));
+    return sg_create_impl(ne, hs.data(), ht.data(), hw.data(), 0, 1, false, out);
+}
+
+// ---- the build's phases ---------------------------------------------------------------------------------------------
+// sg_create_device_impl below runs them in this order as members of one Build: what a phase leaves for later ones is a
+// member (released by the last phase that reads it), what only it needs is a local of its own and goes when it returns.
+
+struct Build {
+    // the caller's DEVICE columns
+    int64_t ne;
+    const int64_t *src, *dst;
+    const double *w;
+    std::unique_ptr<locrec_sg_graph> g;  // the handle under construction (first: its stream outlives every buffer here)
+    hipStream_t s = nullptr;
+    PhaseClock clock;
+    Temp tmp;
+    const dim3 B{kDbThreads};
+    // rank_vertices: vid (ascending distinct ids), cs / ct (vertex index of every edge's source / target), eidx = 0 .. ne
+    DevBuf<int32_t> cs;
+    DevBuf<uint32_t> ct, eidx;
+    DevBuf<int64_t> vid;
+    int64_t nv = 0;
+    // sort_rows: the edges stably sorted by target vertex (kt) with their indices (es), every vertex's run in them
+    DevBuf<uint32_t> kt, es;
+    DevBuf<int32_t> vbeg, vend;
+    // live_order
+    DevBuf<int32_t> live_of, live_vertex;
+    int32_t n_short = 0, T = 0;
+    // piece_plan: the scanned row counters, the plan (sg_layout_plan.h) and the kernels' part of it
+    DevBuf<DbCnt> sc;
+    SgLayoutPlan plan;
+    DbPlan P;
+    DevBuf<int2> rowinfo;          // row_maps
+    DevBuf<int32_t> slot_of_edge;  // scatter_edges: the slot of every edge whose source is not live
+    DevBuf<int32_t> bad;           // scatter_edges' verdict (lives as long as the Build)
+    DevBuf<int64_t> dead_ptr;      // dead_slots
+    int ncu = 0;                   // poll_word_and_grid
+
+    // the phases, in the order sg_create_device_impl runs them
+    int32_t open(locrec_sg_graph **out, bool *built_on_host);
+    int32_t rank_vertices(), sort_rows(), live_order(), piece_plan(), alloc_resident(), row_maps(), scatter_edges(), dead_slots();
+    int32_t host_tables(), poll_word_and_grid(), dictionary(), finish_handle();
+};
+
+// argument and pointer checks, the handle with its switches and stream.  *built_on_host: the call is already answered
+// by the host build (no edge; one of the two experiments), nothing is left to do
+int32_t Build::open(locrec_sg_graph **out, bool *built_on_host)
+{
+    *built_on_host = false;
+    if (!out) return fail(LOCREC_E_INVALID_ARG, "out_graph is NULL");
+    *out = nullptr;
+    if (ne < 0 || ne >= ((int64_t)1 << 31)) return fail(LOCREC_E_INVALID_ARG, "n_edges must be in [0, 2^31)");
+    if (ne > 0 && (!src || !dst || !w)) return fail(LOCREC_E_INVALID_ARG, "bad edge arrays");
+    if (ne == 0) {  // (no array to read)
+        *built_on_host = true;
+        return sg_create_impl(0, nullptr, nullptr, nullptr, 0, 1, false, out);
+    }
+    LOCREC_TRY(ensure_device());
+    g.reset(new (std::nothrow) locrec_sg_graph);
+    if (!g) return fail(LOCREC_E_OOM, "host allocation failed");
+    LOCREC_HIP_TRY(hipGetDevice(&g->device));
+    LOCREC_TRY(db_device_array(src, g->device, "source_ids"));
+    LOCREC_TRY(db_device_array(dst, g->device, "target_ids"));
+    LOCREC_TRY(db_device_array(w, g->device, "balanced_weights"));
+    sg_read_env(g.get());
+    if (g->env_fused || g->env_persist) {
+        g.reset();
+        *built_on_host = true;
+        return db_host_build(ne, src, dst, w, out);
+    }
+    LOCREC_HIP_TRY(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
+    g->own_stream = true;
+    g->ne = ne;
+    s = g->stream;
+    g_db_stats = DbStats();
+    clock.s = s;
+    return LOCREC_OK;
+}
+
+// min / max of the ids, then the table over [min, max] or the sort of the 2E ids
+int32_t Build::rank_vertices()
+{
+    LOCREC_TRY(cs.alloc((size_t)ne));
+    LOCREC_TRY(ct.alloc((size_t)ne));
+    LOCREC_TRY(eidx.alloc((size_t)ne));
+    DevBuf<unsigned long long> lohi;
+    unsigned long long h[2] = {~0ull, 0ull};
+    LOCREC_TRY(lohi.alloc(2));
+    LOCREC_HIP_TRY(hipMemcpyAsync(lohi.p, h, sizeof h, hipMemcpyHostToDevice, s));
+    LOCREC_LAUNCH(sg_db_minmax, dim3((unsigned)std::min<int64_t>(1024, (ne + kDbThreads - 1) / kDbThreads)), B, 0, s, ne, src,
+                  dst, lohi.p);
+    LOCREC_READ_BACK(h, lohi.p, s);
+    const uint64_t id_lo = (uint64_t)id_of_key(h[0]);  // (the id's bits; differences are exact in unsigned arithmetic)
+    const uint64_t id_span = h[1] - h[0];
+    if (sg_dense_ids(id_span, ne) && !g->env_no_dense_ids) {
+        const int64_t n = (int64_t)id_span + 1;  // table entries; the scan runs over n + 1 (a closing 0)
+        DevBuf<int32_t> r;
+        LOCREC_TRY(r.alloc((size_t)n + 1));
+        LOCREC_HIP_TRY(hipMemsetAsync(r.p, 0, ((size_t)n + 1) * 4, s));
+        LOCREC_LAUNCH(sg_db_mark, grid_for(ne), B, 0, s, ne, src, dst, id_lo, r.p);
+        LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, r.p, r.p, (size_t)n + 1, s));
+        int32_t k = 0;
+        LOCREC_READ_BACK(k, r.p + n, s);
+        nv = k;
+        LOCREC_TRY(vid.alloc((size_t)nv));
+        LOCREC_LAUNCH(sg_db_dense_vid, grid_for(n), B, 0, s, n, r.p, id_lo, vid.p);
+        LOCREC_LAUNCH(sg_db_dense_rank, grid_for(ne), B, 0, s, ne, src, dst, id_lo, r.p, cs.p, ct.p, eidx.p);
+        LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (r is a local)
+    } else {
+        DevBuf<int64_t> ids, sorted;
+        DevBuf<unsigned long long> nuniq;
+        LOCREC_TRY(ids.alloc((size_t)(2 * ne)));
+        LOCREC_TRY(sorted.alloc((size_t)(2 * ne)));
+        LOCREC_TRY(nuniq.alloc(1));
+        LOCREC_LAUNCH(sg_db_interleave, grid_for(ne), B, 0, s, ne, src, dst, ids.p);
+        LOCREC_PRIM(tmp, prim::sort_keys(p_, bytes_, ids.p, sorted.p, (size_t)(2 * ne), 0u, 64u, s));
+        LOCREC_PRIM(tmp, prim::unique(p_, bytes_, sorted.p, ids.p, nuniq.p, (size_t)(2 * ne), s));
+        unsigned long long k = 0;
+        LOCREC_READ_BACK(k, nuniq.p, s);
+        nv = (int64_t)k;
+        sorted.release();
+        LOCREC_TRY(vid.alloc((size_t)nv));
+        LOCREC_HIP_TRY(hipMemcpyAsync(vid.p, ids.p, (size_t)nv * 8, hipMemcpyDeviceToDevice, s));
+        LOCREC_LAUNCH(sg_db_bisect, grid_for(ne), B, 0, s, ne, src, dst, vid.p, nv, cs.p, ct.p, eidx.p);
+        LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (ids is a local)
+    }
+    if (nv >= ((int64_t)1 << 31) - 2) return fail(LOCREC_E_INVALID_ARG, "too many vertices");
+    g->nv = nv;
+    return LOCREC_OK;
+}
+
+// rows: the edges stably sorted by target vertex; a row's order is the edge-list order
+int32_t Build::sort_rows()
+{
+    LOCREC_TRY(kt.alloc((size_t)ne));
+    LOCREC_TRY(es.alloc((size_t)ne));
+    LOCREC_TRY(vbeg.alloc((size_t)nv));
+    LOCREC_TRY(vend.alloc((size_t)nv));
+    LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, ct.p, kt.p, eidx.p, es.p, (size_t)ne, 0u, (unsigned)sg_radix_bits(nv), s));
+    LOCREC_HIP_TRY(hipMemsetAsync(vbeg.p, 0, (size_t)nv * 4, s));
+    LOCREC_HIP_TRY(hipMemsetAsync(vend.p, 0, (size_t)nv * 4, s));
+    LOCREC_LAUNCH(sg_db_row_bounds, grid_for(ne), B, 0, s, ne, kt.p, vbeg.p, vend.p);
+    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    ct.release();
+    eidx.release();
+    return LOCREC_OK;
+}
+
+// live order: rows with at most two full pieces first, ascending vertex inside each class
+int32_t Build::live_order()
+{
+    DevBuf<unsigned long long> fl;
+    LOCREC_TRY(fl.alloc((size_t)nv + 1));
+    LOCREC_TRY(live_of.alloc((size_t)nv));
+    LOCREC_LAUNCH(sg_db_live_flags, grid_for(nv + 1), B, 0, s, nv, vbeg.p, vend.p, fl.p);
+    LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, fl.p, fl.p, (size_t)nv + 1, s));
+    unsigned long long tot = 0;
+    LOCREC_READ_BACK(tot, fl.p + nv, s);
+    n_short = (int32_t)(tot & 0xFFFFFFFFull);
+    T = n_short + (int32_t)(tot >> 32);
+    LOCREC_TRY(live_vertex.alloc((size_t)T));
+    LOCREC_LAUNCH(sg_db_live, grid_for(nv), B, 0, s, nv, vbeg.p, vend.p, fl.p, n_short, live_of.p, live_vertex.p);
+    LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (fl is a local)
+    g->nlive = T;
+    g->n_short = n_short;
+    return LOCREC_OK;
+}
+
+// piece plan: full pieces in row order, then remainder pieces by class 6 down to 0.  One scan of the eight per-row
+// counters; its totals, and the full pieces in front of row n_short, are all the plan takes
+int32_t Build::piece_plan()
+{
+    DbCnt tot, at_short;
+    LOCREC_TRY(sc.alloc((size_t)T + 1));
+    LOCREC_LAUNCH(sg_db_row_counts, grid_for((int64_t)T + 1), B, 0, s, T, live_vertex.p, vbeg.p, vend.p, sc.p);
+    LOCREC_PRIM(tmp, rocprim::exclusive_scan(p_, bytes_, sc.p, sc.p, DbCnt{{0, 0, 0, 0, 0, 0, 0, 0}}, (size_t)T + 1,
+                                             DbCntPlus(), s));
+    LOCREC_HIP_TRY(hipMemcpyAsync(&tot, sc.p + T, sizeof tot, hipMemcpyDeviceToHost, s));
+    LOCREC_HIP_TRY(hipMemcpyAsync(&at_short, sc.p + n_short, sizeof at_short, hipMemcpyDeviceToHost, s));
+    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    plan = sg_layout_plan(tot.c, tot.c[7], at_short.c[7], T, n_short);
+    if (plan.status == SgPlanStatus::too_many_slots) return fail(LOCREC_E_INVALID_ARG, "graph too large for int32 slot ids");
+    if (plan.status == SgPlanStatus::too_many_partials)
+        return fail(LOCREC_E_INVALID_ARG, "graph too large for int32 partial slots");
+    g->npieces = (int32_t)plan.np;
+    for (int c = 0; c < 7; ++c) {
+        P.piece_begin[c] = plan.piece_begin[c];
+        P.part_begin[c] = plan.part_begin[c];
+    }
+    P.nfull_total = plan.nfull_total;
+    P.T = plan.T;
+    P.n_short = plan.n_short;
+    P.long_base = plan.long_base;
+    return LOCREC_OK;
+}
+
+// what stays resident, before the temporaries of the steps below
+int32_t Build::alloc_resident()
+{
+    g->use16 = sg_use16(T) && !g->env_no_col16;
+    if (g->use16)
+        LOCREC_TRY(g->col16.alloc((size_t)plan.nslots()));
+    else
+        LOCREC_TRY(g->col4.alloc((size_t)plan.np * 64));
+    LOCREC_TRY(g->w2.alloc((size_t)plan.np * 128));
+    LOCREC_TRY(g->pinfo.alloc((size_t)plan.np));
+    LOCREC_TRY(g->seg_out.alloc((size_t)plan.npart));
+    LOCREC_TRY(g->lrows.alloc((size_t)plan.long_area_rows()));
+    LOCREC_TRY(g->PA.alloc((size_t)(2 * plan.pa)));
+    LOCREC_TRY(g->xbuf.alloc((size_t)(2 * (T + 2))));
+    LOCREC_TRY(g->parts.alloc(2 * kParts));
+    LOCREC_TRY(g->state.alloc(1));
+    return LOCREC_OK;
+}
+
+// rows, segments, pieces: rowinfo, seg_out, lrows (partitioned: the whole-wave rows first), pinfo
+int32_t Build::row_maps()
+{
+    const int64_t np = plan.np;
+    const int32_t nl = plan.long_area_rows();
+    DevBuf<int32_t> crow;  // (declared in this order: lrows_in_order goes first)
+    DevBuf<int4> lrows_in_order;
+    LOCREC_TRY(rowinfo.alloc((size_t)T));
+    LOCREC_TRY(lrows_in_order.alloc((size_t)nl));
+    LOCREC_TRY(crow.alloc((size_t)nl + 1));
+    LOCREC_HIP_TRY(hipMemsetAsync(g->seg_out.p, 0xFF, g->seg_out.bytes(), s));  // -1: a segment no row owns
+    LOCREC_HIP_TRY(hipMemsetAsync(crow.p, 0, crow.bytes(), s));
+    LOCREC_HIP_TRY(hipMemsetAsync(g->PA.p, 0, (size_t)(2 * plan.pa) * sizeof(double), s));
+    if (T > 0) {
+        LOCREC_LAUNCH(sg_db_row_maps, grid_for(T), B, 0, s, P, live_vertex.p, vbeg.p, vend.p, sc.p, rowinfo.p, g->seg_out.p,
+                      lrows_in_order.p, crow.p);
+    }
+    int32_t n_crows = 0;
+    if (nl > 0) {
+        LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, crow.p, crow.p, (size_t)nl + 1, s));
+        LOCREC_LAUNCH(sg_db_lrows_partition, grid_for(nl), B, 0, s, nl, lrows_in_order.p, crow.p, g->lrows.p);
+        LOCREC_HIP_TRY(hipMemcpyAsync(&n_crows, crow.p + nl, 4, hipMemcpyDeviceToHost, s));
+    }
+    if (np > 0) {
+        LOCREC_LAUNCH(sg_db_pinfo, grid_for(np), B, 0, s, (int32_t)np, P, g->pinfo.p);
+    }
+    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    g->nlong = n_crows;  // (rows with more than kLongRow full pieces: all of them sit in the long area)
+    g->n_crows = n_crows;
+    g->nlrows = nl;
+    g->pa_stride = (int32_t)plan.pa;
+    sc.release();
+    return LOCREC_OK;
+}
+
+// slot of every edge; col and w (through the weight interleave)
+int32_t Build::scatter_edges()
+{
+    const int64_t nslots = plan.nslots();
+    LOCREC_TRY(slot_of_edge.alloc((size_t)ne));
+    LOCREC_TRY(bad.alloc(1));
+    LOCREC_HIP_TRY(hipMemsetAsync(bad.p, 0, 4, s));
+    LOCREC_HIP_TRY(hipMemsetAsync(g->w2.p, 0, (size_t)nslots * 8, s));
+    if (g->use16) {
+        LOCREC_LAUNCH(sg_db_fill<unsigned short>, grid_for(nslots), B, 0, s, nslots, (unsigned short)T, g->col16.p);
+        LOCREC_LAUNCH(sg_db_scatter<unsigned short>, grid_for(ne), B, 0, s, ne, kt.p, es.p, vbeg.p, vend.p, live_of.p, rowinfo.p,
+                      cs.p, w, T, nslots, g->col16.p, reinterpret_cast<double *>(g->w2.p), slot_of_edge.p, bad.p);
+    } else {
+        int32_t *col = reinterpret_cast<int32_t *>(g->col4.p);
+        LOCREC_LAUNCH(sg_db_fill<int32_t>, grid_for(nslots), B, 0, s, nslots, T, col);
+        LOCREC_LAUNCH(sg_db_scatter<int32_t>, grid_for(ne), B, 0, s, ne, kt.p, es.p, vbeg.p, vend.p, live_of.p, rowinfo.p, cs.p, w,
+                      T, nslots, col, reinterpret_cast<double *>(g->w2.p), slot_of_edge.p, bad.p);
+    }
+    int32_t bad_h = 0;
+    LOCREC_READ_BACK(bad_h, bad.p, s);
+    if (bad_h) return fail(LOCREC_E_DEVICE, "device build: an edge fell outside the piece plan");
+    kt.release();
+    es.release();
+    rowinfo.release();
+    vbeg.release();
+    vend.release();
+    return LOCREC_OK;
+}
+
+// dead slots: the out-edges of source-only vertices, by source, edge-list order inside a source
+int32_t Build::dead_slots()
+{
+    LOCREC_TRY(dead_ptr.alloc((size_t)nv + 1));
+    {
+        DevBuf<unsigned char> flag;
+        DevBuf<uint32_t> didx;
+        DevBuf<unsigned long long> ndead;
+        LOCREC_TRY(flag.alloc((size_t)ne));
+        LOCREC_TRY(didx.alloc((size_t)ne));
+        LOCREC_TRY(ndead.alloc(1));
+        LOCREC_LAUNCH(sg_db_dead_flag, grid_for(ne), B, 0, s, ne, cs.p, live_of.p, flag.p);
+        LOCREC_PRIM(tmp, prim::select_flagged(p_, bytes_, prim::counting_iterator<uint32_t>(0), flag.p, didx.p, ndead.p,
+                                              (size_t)ne, s));
+        unsigned long long k = 0;
+        LOCREC_READ_BACK(k, ndead.p, s);
+        const int64_t nd = (int64_t)k;
+        flag.release();
+        LOCREC_TRY(g->dead_slots_dev.alloc((size_t)nd));
+        DevBuf<uint32_t> dk, dk2;
+        DevBuf<int32_t> dv;
+        LOCREC_TRY(dk.alloc((size_t)nd));
+        LOCREC_TRY(dk2.alloc((size_t)nd));
+        LOCREC_TRY(dv.alloc((size_t)nd));
+        if (nd > 0) {
+            LOCREC_LAUNCH(sg_db_dead_gather, grid_for(nd), B, 0, s, nd, didx.p, cs.p, slot_of_edge.p, dk.p, dv.p);
+            LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, dk.p, dk2.p, dv.p, g->dead_slots_dev.p, (size_t)nd, 0u,
+                                              (unsigned)sg_radix_bits(nv), s));
+        }
+        LOCREC_LAUNCH(sg_db_dead_ptr, grid_for(nv + 1), B, 0, s, nv, dk2.p, nd, dead_ptr.p);
+        LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (locals)
+    }
+    slot_of_edge.release();
+    cs.release();
+    tmp.buf.release();
+    return LOCREC_OK;
+}
+
+// what the handle keeps on the host (V-sized): begin_request and fetch use it
+int32_t Build::host_tables()
+{
+    g->vid.resize((size_t)nv);
+    g->live_of.resize((size_t)nv);
+    g->live_vertex.resize((size_t)T);
+    g->dead_ptr.resize((size_t)nv + 1);
+    LOCREC_HIP_TRY(hipMemcpyAsync(g->vid.data(), vid.p, (size_t)nv * 8, hipMemcpyDeviceToHost, s));
+    LOCREC_HIP_TRY(hipMemcpyAsync(g->live_of.data(), live_of.p, (size_t)nv * 4, hipMemcpyDeviceToHost, s));
+    if (T > 0) LOCREC_HIP_TRY(hipMemcpyAsync(g->live_vertex.data(), live_vertex.p, (size_t)T * 4, hipMemcpyDeviceToHost, s));
+    LOCREC_HIP_TRY(hipMemcpyAsync(g->dead_ptr.data(), dead_ptr.p, ((size_t)nv + 1) * 8, hipMemcpyDeviceToHost, s));
+    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    vid.release();
+    live_of.release();
+    live_vertex.release();
+    dead_ptr.release();
+    return LOCREC_OK;
+}
+
+// from here on the rest of sg_create_impl, over the arrays that are already resident: the poll word of the packed
+// requests, the compute units (persist_pw below) and the grid of the grid-stride sweep
+int32_t Build::poll_word_and_grid()
+{
+    g->device_sweep_bytes = 0;
+    if (!g->no_pack) {
+        void *hp = nullptr, *dp = nullptr;
+        if (hipHostMalloc(&hp, 64, hipHostMallocDefault) == hipSuccess && hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) {
+            g->h_poll = static_cast<int32_t *>(hp);
+            g->h_poll_dev = static_cast<int32_t *>(dp);
+        } else {
+            (void)hipGetLastError();
+            if (hp) (void)hipHostFree(hp);
+            g->no_pack = true;
+        }
+    }
+    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, g->device) != hipSuccess)
+        (void)hipGetLastError();  // (tolerated: ncu = 0 below; the dictionary's launch check must not report it)
+    if (g->env_gs > 0) g->gs_blocks = g->env_gs * std::max(1, ncu);
+    return LOCREC_OK;
+}
+
+// the weight dictionary, exactly as sg_create_impl builds it from the uploaded weights (see the comment there)
+int32_t Build::dictionary()
+{
+    if (g->env_no_dict || plan.np == 0) return LOCREC_OK;
+    const size_t nslots = (size_t)plan.nslots();
     DevBuf<uint64_t> ka, kb;
     DevBuf<unsigned int> counts;
     DevBuf<int32_t> nuniq;
-    DevBuf<unsigned char> tmp;
+    DevBuf<unsigned char> storage;
     LOCREC_TRY(g->widx.alloc(nslots));  // (before the temporaries: what stays resident is allocated first)
     LOCREC_TRY(g->dict.alloc(kDictMax));
     LOCREC_TRY(ka.alloc(nslots));
@@ -361,12 +721,12 @@ int32_t db_dictionary(locrec_sg_graph *g, int64_t np)
     size_t b1 = 0, b2 = 0;  // (not LOCREC_PRIM: both calls are sized before the one allocation, as sg_create_impl does)
     LOCREC_HIP_TRY(prim::sort_keys(nullptr, b1, ka.p, kb.p, nslots, 0u, 64u, s));
     LOCREC_HIP_TRY(prim::run_length_encode(nullptr, b2, kb.p, nslots, ka.p, counts.p, nuniq.p, s));
-    LOCREC_TRY(tmp.alloc(std::max(b1, b2)));
-    LOCREC_HIP_TRY(prim::sort_keys(tmp.p, b1, ka.p, kb.p, nslots, 0u, 64u, s));
-    LOCREC_HIP_TRY(prim::run_length_encode(tmp.p, b2, kb.p, nslots, ka.p, counts.p, nuniq.p, s));
+    LOCREC_TRY(storage.alloc(std::max(b1, b2)));
+    LOCREC_HIP_TRY(prim::sort_keys(storage.p, b1, ka.p, kb.p, nslots, 0u, 64u, s));
+    LOCREC_HIP_TRY(prim::run_length_encode(storage.p, b2, kb.p, nslots, ka.p, counts.p, nuniq.p, s));
     int32_t nu = 0;
     LOCREC_READ_BACK(nu, nuniq.p, s);
-    if (nu >= 1 && nu <= kDictMax) {
+    if (sg_dict_fits(nu)) {
         std::vector<uint64_t> vals((size_t)nu);
         std::vector<unsigned int> cnt((size_t)nu);
         LOCREC_HIP_TRY(hipMemcpyAsync(vals.data(), ka.p, (size_t)nu * 8, hipMemcpyDeviceToHost, s));
@@ -395,328 +755,43 @@ int32_t db_dictionary(locrec_sg_graph *g, int64_t np)
     return LOCREC_OK;
 }
 
-// the experiments keep their host-only extra layouts: one copy of the columns to the host, then the host build
-int32_t db_host_build(int64_t ne, const int64_t *src, const int64_t *dst, const double *w, locrec_sg_graph **out)
+// the byte figures bench.py reports, persist_pw, the phase times
+int32_t Build::finish_handle()
 {
-    std::vector<int64_t> hs((size_t)ne), ht((size_t)ne);
-    std::vector<double> hw((size_t)ne);
-    LOCREC_HIP_TRY(hipMemcpy(hs.data(), src, (size_t)ne * 8, hipMemcpyDeviceToHost));
-    LOCREC_HIP_TRY(hipMemcpy(ht.data(), dst, (size_t)ne * 8, hipMemcpyDeviceToHost));
-    LOCREC_HIP_TRY(hipMemcpy(hw.data(), w, (size_t)ne * 8, hipMemcpyDeviceToHost));
-    return sg_create_impl(ne, hs.data(), ht.data(), hw.data(), 0, 1, false, out);
+    g->layout_bytes = sg_layout_bytes(plan.np, T);
+    g->device_sweep_bytes = sg_device_sweep_bytes(plan.np, plan.npart, T, g->use16, g->ndict > 0);
+    g->persist_pw = sg_persist_pw(plan.np, ncu);
+    g->persist_ok = false;  // (LOCREC_SG_PERSIST handles come from the host build)
+    return clock.read(g_db_stats.ms);
 }
 
+// kDbScatter covers the row sort and the scatter with the dead slots and the host tables, kDbPlan the live order
+// through pinfo
 int32_t sg_create_device_impl(int64_t ne, const int64_t *src, const int64_t *dst, const double *w, locrec_sg_graph **out)
 {
-    if (!out) return fail(LOCREC_E_INVALID_ARG, "out_graph is NULL");
-    *out = nullptr;
-    if (ne < 0 || ne >= ((int64_t)1 << 31)) return fail(LOCREC_E_INVALID_ARG, "n_edges must be in [0, 2^31)");
-    if (ne > 0 && (!src || !dst || !w)) return fail(LOCREC_E_INVALID_ARG, "bad edge arrays");
-    if (ne == 0) return sg_create_impl(0, nullptr, nullptr, nullptr, 0, 1, false, out);  // (no array to read)
-    LOCREC_TRY(ensure_device());
-    std::unique_ptr<locrec_sg_graph> g(new (std::nothrow) locrec_sg_graph);
-    if (!g) return fail(LOCREC_E_OOM, "host allocation failed");
-    LOCREC_HIP_TRY(hipGetDevice(&g->device));
-    LOCREC_TRY(db_device_array(src, g->device, "source_ids"));
-    LOCREC_TRY(db_device_array(dst, g->device, "target_ids"));
-    LOCREC_TRY(db_device_array(w, g->device, "balanced_weights"));
-    sg_read_env(g.get());
-    if (g->env_fused || g->env_persist) {
-        g.reset();
-        return db_host_build(ne, src, dst, w, out);
-    }
-    LOCREC_HIP_TRY(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
-    g->own_stream = true;
-    g->ne = ne;
-    hipStream_t s = g->stream;
-    g_db_stats = DbStats();
-    PhaseClock clock;
-    clock.s = s;
-    Temp tmp;
-    const dim3 B(kDbThreads);
-
-    // ---- vertex ranking: vid (ascending distinct ids), cs / ct (vertex index of every edge's source / target) ----
-    LOCREC_TRY(clock.mark(kDbRanking));
-    DevBuf<int32_t> cs;
-    DevBuf<uint32_t> ct, eidx;
-    DevBuf<int64_t> vid;
-    LOCREC_TRY(cs.alloc((size_t)ne));
-    LOCREC_TRY(ct.alloc((size_t)ne));
-    LOCREC_TRY(eidx.alloc((size_t)ne));
-    int64_t nv = 0;
-    {
-        DevBuf<unsigned long long> lohi;
-        unsigned long long h[2] = {~0ull, 0ull};
-        LOCREC_TRY(lohi.alloc(2));
-        LOCREC_HIP_TRY(hipMemcpyAsync(lohi.p, h, sizeof h, hipMemcpyHostToDevice, s));
-        LOCREC_LAUNCH(sg_db_minmax, dim3((unsigned)std::min<int64_t>(1024, (ne + kDbThreads - 1) / kDbThreads)), B, 0, s, ne,
-                      src, dst, lohi.p);
-        LOCREC_READ_BACK(h, lohi.p, s);
-        const uint64_t id_lo = (uint64_t)id_of_key(h[0]);  // (the id's bits; differences are exact in unsigned arithmetic)
-        const uint64_t id_span = h[1] - h[0];
-        const bool dense_ids = id_span < (uint64_t)(8 * ne) + (1u << 20) && !g->env_no_dense_ids;
-        if (dense_ids) {
-            const int64_t n = (int64_t)id_span + 1;  // table entries; the scan runs over n + 1 (a closing 0)
-            DevBuf<int32_t> r;
-            LOCREC_TRY(r.alloc((size_t)n + 1));
-            LOCREC_HIP_TRY(hipMemsetAsync(r.p, 0, ((size_t)n + 1) * 4, s));
-            LOCREC_LAUNCH(sg_db_mark, grid_for(ne), B, 0, s, ne, src, dst, id_lo, r.p);
-            LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, r.p, r.p, (size_t)n + 1, s));
-            int32_t k = 0;
-            LOCREC_READ_BACK(k, r.p + n, s);
-            nv = k;
-            LOCREC_TRY(vid.alloc((size_t)nv));
-            LOCREC_LAUNCH(sg_db_dense_vid, grid_for(n), B, 0, s, n, r.p, id_lo, vid.p);
-            LOCREC_LAUNCH(sg_db_dense_rank, grid_for(ne), B, 0, s, ne, src, dst, id_lo, r.p, cs.p, ct.p, eidx.p);
-            LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (r is a local)
-        } else {
-            DevBuf<int64_t> ids, sorted;
-            DevBuf<unsigned long long> nuniq;
-            LOCREC_TRY(ids.alloc((size_t)(2 * ne)));
-            LOCREC_TRY(sorted.alloc((size_t)(2 * ne)));
-            LOCREC_TRY(nuniq.alloc(1));
-            LOCREC_LAUNCH(sg_db_interleave, grid_for(ne), B, 0, s, ne, src, dst, ids.p);
-            LOCREC_PRIM(tmp, prim::sort_keys(p_, bytes_, ids.p, sorted.p, (size_t)(2 * ne), 0u, 64u, s));
-            LOCREC_PRIM(tmp, prim::unique(p_, bytes_, sorted.p, ids.p, nuniq.p, (size_t)(2 * ne), s));
-            unsigned long long k = 0;
-            LOCREC_READ_BACK(k, nuniq.p, s);
-            nv = (int64_t)k;
-            sorted.release();
-            LOCREC_TRY(vid.alloc((size_t)nv));
-            LOCREC_HIP_TRY(hipMemcpyAsync(vid.p, ids.p, (size_t)nv * 8, hipMemcpyDeviceToDevice, s));
-            LOCREC_LAUNCH(sg_db_bisect, grid_for(ne), B, 0, s, ne, src, dst, vid.p, nv, cs.p, ct.p, eidx.p);
-            LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (ids is a local)
-        }
-    }
-    if (nv >= ((int64_t)1 << 31) - 2) return fail(LOCREC_E_INVALID_ARG, "too many vertices");
-    g->nv = nv;
-
-    // ---- rows: the edges stably sorted by target vertex; a row's order is the edge-list order ----
-    LOCREC_TRY(clock.mark(kDbScatter));
-    DevBuf<uint32_t> kt, es;
-    DevBuf<int32_t> vbeg, vend;
-    LOCREC_TRY(kt.alloc((size_t)ne));
-    LOCREC_TRY(es.alloc((size_t)ne));
-    LOCREC_TRY(vbeg.alloc((size_t)nv));
-    LOCREC_TRY(vend.alloc((size_t)nv));
-    LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, ct.p, kt.p, eidx.p, es.p, (size_t)ne, 0u, (unsigned)db_bits(nv), s));
-    LOCREC_HIP_TRY(hipMemsetAsync(vbeg.p, 0, (size_t)nv * 4, s));
-    LOCREC_HIP_TRY(hipMemsetAsync(vend.p, 0, (size_t)nv * 4, s));
-    LOCREC_LAUNCH(sg_db_row_bounds, grid_for(ne), B, 0, s, ne, kt.p, vbeg.p, vend.p);
-    LOCREC_HIP_TRY(hipStreamSynchronize(s));
-    ct.release();
-    eidx.release();
-
-    // ---- live order: rows with at most two full pieces first, ascending vertex inside each class ----
-    LOCREC_TRY(clock.mark(kDbPlan));
-    DevBuf<int32_t> live_of, live_vertex;
-    int32_t n_short = 0, T = 0;
-    {
-        DevBuf<unsigned long long> fl;
-        LOCREC_TRY(fl.alloc((size_t)nv + 1));
-        LOCREC_TRY(live_of.alloc((size_t)nv));
-        LOCREC_LAUNCH(sg_db_live_flags, grid_for(nv + 1), B, 0, s, nv, vbeg.p, vend.p, fl.p);
-        LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, fl.p, fl.p, (size_t)nv + 1, s));
-        unsigned long long tot = 0;
-        LOCREC_READ_BACK(tot, fl.p + nv, s);
-        n_short = (int32_t)(tot & 0xFFFFFFFFull);
-        T = n_short + (int32_t)(tot >> 32);
-        LOCREC_TRY(live_vertex.alloc((size_t)T));
-        LOCREC_LAUNCH(sg_db_live, grid_for(nv), B, 0, s, nv, vbeg.p, vend.p, fl.p, n_short, live_of.p, live_vertex.p);
-        LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (fl is a local)
-    }
-    g->nlive = T;
-    g->n_short = n_short;
-
-    // ---- piece plan: full pieces in row order, then remainder pieces by class 6 down to 0 ----
-    DevBuf<DbCnt> sc;
-    DbCnt tot, at_short;
-    LOCREC_TRY(sc.alloc((size_t)T + 1));
-    LOCREC_LAUNCH(sg_db_row_counts, grid_for((int64_t)T + 1), B, 0, s, T, live_vertex.p, vbeg.p, vend.p, sc.p);
-    LOCREC_PRIM(tmp, rocprim::exclusive_scan(p_, bytes_, sc.p, sc.p, DbCnt{{0, 0, 0, 0, 0, 0, 0, 0}}, (size_t)T + 1,
-                                             DbCntPlus(), s));
-    LOCREC_HIP_TRY(hipMemcpyAsync(&tot, sc.p + T, sizeof tot, hipMemcpyDeviceToHost, s));
-    LOCREC_HIP_TRY(hipMemcpyAsync(&at_short, sc.p + n_short, sizeof at_short, hipMemcpyDeviceToHost, s));
-    LOCREC_HIP_TRY(hipStreamSynchronize(s));
-    const int64_t nfull_total = tot.c[7];
-    int64_t piece_begin_cls[7], part_begin_cls[7];
-    int64_t np = nfull_total, npart = nfull_total;
-    for (int c = 6; c >= 0; --c) {
-        const int segs_per_piece = 64 >> c;
-        const int64_t pieces = ((int64_t)tot.c[c] + segs_per_piece - 1) / segs_per_piece;
-        piece_begin_cls[c] = np;
-        part_begin_cls[c] = npart;
-        np += pieces;
-        npart += pieces * segs_per_piece;
-    }
-    if (np >= ((int64_t)1 << 31) / kSlots) return fail(LOCREC_E_INVALID_ARG, "graph too large for int32 slot ids");
-    // the long area behind the three slots of every row: a run of nfull + 1 slots per row from n_short on, in row order
-    const int64_t pa = 3 * (int64_t)T + (nfull_total - at_short.c[7]) + (T - n_short);
-    if (pa >= ((int64_t)1 << 30)) return fail(LOCREC_E_INVALID_ARG, "graph too large for int32 partial slots");
-    g->npieces = (int32_t)np;
-    DbPlan P;
-    for (int c = 0; c < 7; ++c) {
-        P.piece_begin[c] = (int32_t)piece_begin_cls[c];
-        P.part_begin[c] = (int32_t)part_begin_cls[c];
-    }
-    P.nfull_total = (int32_t)nfull_total;
-    P.T = T;
-    P.n_short = n_short;
-    P.long_base = (int32_t)(3 * (int64_t)T - at_short.c[7] - n_short);
-    const int64_t nslots = np * kSlots;
-    const int32_t nl = T - n_short;
-
-    // what stays resident, before the temporaries of the steps below
-    g->use16 = T + 2 <= 65536 && !g->env_no_col16;
-    if (g->use16)
-        LOCREC_TRY(g->col16.alloc((size_t)nslots));
-    else
-        LOCREC_TRY(g->col4.alloc((size_t)np * 64));
-    LOCREC_TRY(g->w2.alloc((size_t)np * 128));
-    LOCREC_TRY(g->pinfo.alloc((size_t)np));
-    LOCREC_TRY(g->seg_out.alloc((size_t)npart));
-    LOCREC_TRY(g->lrows.alloc((size_t)nl));
-    LOCREC_TRY(g->PA.alloc((size_t)(2 * pa)));
-    LOCREC_TRY(g->xbuf.alloc((size_t)(2 * (T + 2))));
-    LOCREC_TRY(g->parts.alloc(2 * kParts));
-    LOCREC_TRY(g->state.alloc(1));
-
-    // rows, segments, pieces
-    DevBuf<int2> rowinfo;
-    DevBuf<int4> lrows_in_order;
-    DevBuf<int32_t> crow;
-    LOCREC_TRY(rowinfo.alloc((size_t)T));
-    LOCREC_TRY(lrows_in_order.alloc((size_t)nl));
-    LOCREC_TRY(crow.alloc((size_t)nl + 1));
-    LOCREC_HIP_TRY(hipMemsetAsync(g->seg_out.p, 0xFF, g->seg_out.bytes(), s));  // -1: a segment no row owns
-    LOCREC_HIP_TRY(hipMemsetAsync(crow.p, 0, crow.bytes(), s));
-    LOCREC_HIP_TRY(hipMemsetAsync(g->PA.p, 0, (size_t)(2 * pa) * sizeof(double), s));
-    if (T > 0) {
-        LOCREC_LAUNCH(sg_db_row_maps, grid_for(T), B, 0, s, P, live_vertex.p, vbeg.p, vend.p, sc.p, rowinfo.p, g->seg_out.p,
-                      lrows_in_order.p, crow.p);
-    }
-    int32_t n_crows = 0;
-    if (nl > 0) {
-        LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, crow.p, crow.p, (size_t)nl + 1, s));
-        LOCREC_LAUNCH(sg_db_lrows_partition, grid_for(nl), B, 0, s, nl, lrows_in_order.p, crow.p, g->lrows.p);
-        LOCREC_HIP_TRY(hipMemcpyAsync(&n_crows, crow.p + nl, 4, hipMemcpyDeviceToHost, s));
-    }
-    if (np > 0) {
-        LOCREC_LAUNCH(sg_db_pinfo, grid_for(np), B, 0, s, (int32_t)np, P, g->pinfo.p);
-    }
-    LOCREC_HIP_TRY(hipStreamSynchronize(s));
-    g->nlong = n_crows;  // (rows with more than kLongRow full pieces: all of them sit in the long area)
-    g->n_crows = n_crows;
-    g->nlrows = nl;
-    g->pa_stride = (int32_t)pa;
-    sc.release();
-    lrows_in_order.release();
-    crow.release();
-
-    // ---- slot of every edge; col and w (through the weight interleave) ----
-    LOCREC_TRY(clock.mark(kDbScatter));
-    DevBuf<int32_t> slot_of_edge, bad;
-    LOCREC_TRY(slot_of_edge.alloc((size_t)ne));
-    LOCREC_TRY(bad.alloc(1));
-    LOCREC_HIP_TRY(hipMemsetAsync(bad.p, 0, 4, s));
-    LOCREC_HIP_TRY(hipMemsetAsync(g->w2.p, 0, (size_t)nslots * 8, s));
-    if (g->use16) {
-        LOCREC_LAUNCH(sg_db_fill<unsigned short>, grid_for(nslots), B, 0, s, nslots, (unsigned short)T, g->col16.p);
-        LOCREC_LAUNCH(sg_db_scatter<unsigned short>, grid_for(ne), B, 0, s, ne, kt.p, es.p, vbeg.p, vend.p, live_of.p, rowinfo.p,
-                      cs.p, w, T, nslots, g->col16.p, reinterpret_cast<double *>(g->w2.p), slot_of_edge.p, bad.p);
-    } else {
-        int32_t *col = reinterpret_cast<int32_t *>(g->col4.p);
-        LOCREC_LAUNCH(sg_db_fill<int32_t>, grid_for(nslots), B, 0, s, nslots, T, col);
-        LOCREC_LAUNCH(sg_db_scatter<int32_t>, grid_for(ne), B, 0, s, ne, kt.p, es.p, vbeg.p, vend.p, live_of.p, rowinfo.p, cs.p, w,
-                      T, nslots, col, reinterpret_cast<double *>(g->w2.p), slot_of_edge.p, bad.p);
-    }
-    int32_t bad_h = 0;
-    LOCREC_READ_BACK(bad_h, bad.p, s);
-    if (bad_h) return fail(LOCREC_E_DEVICE, "device build: an edge fell outside the piece plan");
-    kt.release();
-    es.release();
-    rowinfo.release();
-    vbeg.release();
-    vend.release();
-
-    // ---- dead slots: the out-edges of source-only vertices, by source, edge-list order inside a source ----
-    DevBuf<int64_t> dead_ptr;
-    LOCREC_TRY(dead_ptr.alloc((size_t)nv + 1));
-    {
-        DevBuf<unsigned char> flag;
-        DevBuf<uint32_t> didx;
-        DevBuf<unsigned long long> ndead;
-        LOCREC_TRY(flag.alloc((size_t)ne));
-        LOCREC_TRY(didx.alloc((size_t)ne));
-        LOCREC_TRY(ndead.alloc(1));
-        LOCREC_LAUNCH(sg_db_dead_flag, grid_for(ne), B, 0, s, ne, cs.p, live_of.p, flag.p);
-        LOCREC_PRIM(tmp, prim::select_flagged(p_, bytes_, prim::counting_iterator<uint32_t>(0), flag.p, didx.p, ndead.p,
-                                              (size_t)ne, s));
-        unsigned long long k = 0;
-        LOCREC_READ_BACK(k, ndead.p, s);
-        const int64_t nd = (int64_t)k;
-        flag.release();
-        LOCREC_TRY(g->dead_slots_dev.alloc((size_t)nd));
-        DevBuf<uint32_t> dk, dk2;
-        DevBuf<int32_t> dv;
-        LOCREC_TRY(dk.alloc((size_t)nd));
-        LOCREC_TRY(dk2.alloc((size_t)nd));
-        LOCREC_TRY(dv.alloc((size_t)nd));
-        if (nd > 0) {
-            LOCREC_LAUNCH(sg_db_dead_gather, grid_for(nd), B, 0, s, nd, didx.p, cs.p, slot_of_edge.p, dk.p, dv.p);
-            LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, dk.p, dk2.p, dv.p, g->dead_slots_dev.p, (size_t)nd, 0u,
-                                              (unsigned)db_bits(nv), s));
-        }
-        LOCREC_LAUNCH(sg_db_dead_ptr, grid_for(nv + 1), B, 0, s, nv, dk2.p, nd, dead_ptr.p);
-        LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (locals)
-    }
-    slot_of_edge.release();
-    cs.release();
-    tmp.buf.release();
-
-    // ---- what the handle keeps on the host (V-sized): begin_request and fetch use it ----
-    g->vid.resize((size_t)nv);
-    g->live_of.resize((size_t)nv);
-    g->live_vertex.resize((size_t)T);
-    g->dead_ptr.resize((size_t)nv + 1);
-    LOCREC_HIP_TRY(hipMemcpyAsync(g->vid.data(), vid.p, (size_t)nv * 8, hipMemcpyDeviceToHost, s));
-    LOCREC_HIP_TRY(hipMemcpyAsync(g->live_of.data(), live_of.p, (size_t)nv * 4, hipMemcpyDeviceToHost, s));
-    if (T > 0) LOCREC_HIP_TRY(hipMemcpyAsync(g->live_vertex.data(), live_vertex.p, (size_t)T * 4, hipMemcpyDeviceToHost, s));
-    LOCREC_HIP_TRY(hipMemcpyAsync(g->dead_ptr.data(), dead_ptr.p, ((size_t)nv + 1) * 8, hipMemcpyDeviceToHost, s));
-    LOCREC_HIP_TRY(hipStreamSynchronize(s));
-    vid.release();
-    live_of.release();
-    live_vertex.release();
-    dead_ptr.release();
-
-    // ---- the rest of sg_create_impl, over the arrays that are already resident ----
-    g->device_sweep_bytes = 0;
-    if (!g->no_pack) {
-        void *hp = nullptr, *dp = nullptr;
-        if (hipHostMalloc(&hp, 64, hipHostMallocDefault) == hipSuccess && hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) {
-            g->h_poll = static_cast<int32_t *>(hp);
-            g->h_poll_dev = static_cast<int32_t *>(dp);
-        } else {
-            (void)hipGetLastError();
-            if (hp) (void)hipHostFree(hp);
-            g->no_pack = true;
-        }
-    }
-    int ncu = 0;
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, g->device) != hipSuccess)
-        (void)hipGetLastError();  // (tolerated: ncu = 0 below; the dictionary's launch check must not report it)
-    if (g->env_gs > 0) g->gs_blocks = g->env_gs * std::max(1, ncu);
-    LOCREC_TRY(clock.mark(kDbDict));
-    if (!g->env_no_dict && np > 0) LOCREC_TRY(db_dictionary(g.get(), np));
-    LOCREC_TRY(clock.mark(-1));
-    g->layout_bytes = np * kSlots * 12 + np * 8 + (int64_t)T * 12;
-    g->device_sweep_bytes = np * kSlots * (int64_t)((g->use16 ? 2 : 4) + (g->ndict > 0 ? 2 : 8)) + np * 8 + npart * 16 + (int64_t)T * 16;
-    const int64_t waves = (int64_t)ncu * 8;
-    const int64_t need = waves > 0 ? (np + waves - 1) / waves : 1 << 30;
-    g->persist_pw = need <= 4 ? 4 : need <= 12 ? 12 : 0;
-    g->persist_ok = false;  // (LOCREC_SG_PERSIST handles come from the host build)
-    LOCREC_TRY(clock.read(g_db_stats.ms));
-    *out = g.release();
+    Build b{ne, src, dst, w};
+    bool built_on_host = false;
+    LOCREC_TRY(b.open(out, &built_on_host));
+    if (built_on_host) return LOCREC_OK;
+    LOCREC_TRY(b.clock.mark(kDbRanking));
+    LOCREC_TRY(b.rank_vertices());
+    LOCREC_TRY(b.clock.mark(kDbScatter));
+    LOCREC_TRY(b.sort_rows());
+    LOCREC_TRY(b.clock.mark(kDbPlan));
+    LOCREC_TRY(b.live_order());
+    LOCREC_TRY(b.piece_plan());
+    LOCREC_TRY(b.alloc_resident());
+    LOCREC_TRY(b.row_maps());
+    LOCREC_TRY(b.clock.mark(kDbScatter));
+    LOCREC_TRY(b.scatter_edges());
+    LOCREC_TRY(b.dead_slots());
+    LOCREC_TRY(b.host_tables());
+    LOCREC_TRY(b.poll_word_and_grid());
+    LOCREC_TRY(b.clock.mark(kDbDict));
+    LOCREC_TRY(b.dictionary());
+    LOCREC_TRY(b.clock.mark(-1));
+    LOCREC_TRY(b.finish_handle());
+    *out = b.g.release();
     return LOCREC_OK;
 }
 
