@@ -172,6 +172,13 @@ int32_t locrec_knn_ht_multiplied_words(const locrec_knn_index *index, int64_t *o
 int32_t locrec_knn_ht_slice_counts(const locrec_knn_index *index, int64_t capacity, int32_t *out_place, int32_t *out_category,
                                    int64_t *out_slices);
 
+/* Measurement and tests only: the queries the LDS aggregation (csrc/knn_aggregate.h; K <= LOCREC_KNN_BATCH_MAX_K) has
+ * served on this handle since the previous call of this function: out[0] summed by the bucket form
+ * (knn_aggregate_buckets), out[1] summed by the sort form (knn_aggregate: the redo pass of a flagged query, an index with
+ * too many places for the bucket form, LOCREC_KNN_AGG_SORT), out[2] left flagged, their rows being assembled by the
+ * host or the place-major pass.  Device counters: reads and resets them, synchronises the handle's stream. */
+int32_t locrec_knn_aggregate_stats(locrec_knn_index *index, int64_t out[3]);
+
 /* Measurement and tests only: what the hit pre-pass of the last batched head / tail scan on this handle left on the
  * device (csrc/knn_ht_prepass.h).  nq names that batch, as for locrec_knn_fetch_topk; call directly after the batch.
  * *out_query_tile, *out_tiles, [*out_slice0, *out_nslices) = the handle's candidate slices (the off rows have one entry

@@ -50,6 +50,7 @@
 #include <type_traits>
 #include <unordered_map>
 
+#include "knn_agg_plan.h"
 #include "knn_index.h"
 
 namespace {
@@ -1485,6 +1486,7 @@ void knn_read_env(locrec_knn_index *ix)
     }
     if (ix->ht.v1) ix->ht.waves = 8;
     ix->ht.pre_v1 = std::getenv("LOCREC_KNN_HT_PRE_V1") != nullptr;  // A/B: the two-pass hit pre-pass for everything
+    ix->agg_sort = std::getenv("LOCREC_KNN_AGG_SORT") != nullptr;    // A/B: the sorting aggregation for everything
     if (const char *e = std::getenv("LOCREC_KNN_HT_PRE_STAGE"))      // tuning, tests: hits of the pre-pass's LDS stage
         ix->ht.pre_stage = std::min(kHtPreStageMax, std::max(kHtPreStageMin, std::atoi(e)));
     ix->force_generic = std::getenv("LOCREC_KNN_FORCE_GENERIC") != nullptr;
@@ -1626,6 +1628,20 @@ extern "C" int32_t locrec_knn_ht_slice_counts(const locrec_knn_index *ix, int64_
         out_place[sl] = (int32_t)(ix->ht.slice_cnt[(size_t)sl] & 0xFFFFu);
         out_category[sl] = (int32_t)(ix->ht.slice_cnt[(size_t)sl] >> 16);
     }
+    return LOCREC_OK;
+} LOCREC_CATCH_ALL
+
+extern "C" int32_t locrec_knn_aggregate_stats(locrec_knn_index *ix, int64_t out[3]) try
+{
+    if (!ix || !out) return fail(LOCREC_E_INVALID_ARG, "NULL argument");
+    out[0] = out[1] = out[2] = 0;
+    if (!ix->agg_stats.p) return LOCREC_OK;  // no aggregation yet
+    LOCREC_HIP_TRY(hipSetDevice(ix->device));
+    unsigned long long h[3] = {0, 0, 0};
+    LOCREC_HIP_TRY(hipMemcpyAsync(h, ix->agg_stats.p, sizeof h, hipMemcpyDeviceToHost, ix->stream));
+    LOCREC_HIP_TRY(hipMemsetAsync(ix->agg_stats.p, 0, sizeof h, ix->stream));
+    LOCREC_HIP_TRY(hipStreamSynchronize(ix->stream));
+    for (int i = 0; i < 3; ++i) out[i] = (int64_t)h[i];
     return LOCREC_OK;
 } LOCREC_CATCH_ALL
 
@@ -1929,52 +1945,69 @@ extern "C" int32_t locrec_knn_query(locrec_knn_index *ix, int64_t person_id, dou
 
 namespace {
 
+// the plan of an aggregation of K neighbours' rows on this index (knn_agg_plan.h)
+KnnAggPlan aggregate_plan(const locrec_knn_index *ix, int K)
+{
+    return knn_agg_plan(K, ix->max_r_nnz, (int64_t)ix->cplace_ids.size(), kAggCap, ix->agg_sort);
+}
+
+// One launch of a plan over nq queries; host / host_flag_src / host_cap: a single request's staging buffer (knn_aggregate.h).
+// last: no further launch of the plan follows.
+int32_t launch_aggregate(locrec_knn_index *ix, const KnnAggLaunch &l, int64_t nq, int K, int M, int redo, bool last,
+                         unsigned char *host = nullptr, const int32_t *host_flag_src = nullptr, int32_t host_cap = 0)
+{
+    hipStream_t s = ix->stream;
+    if (!ix->agg_stats.p) {
+        LOCREC_TRY(ix->agg_stats.alloc(3));
+        LOCREC_HIP_TRY(hipMemsetAsync(ix->agg_stats.p, 0, 3 * sizeof(unsigned long long), s));
+    }
+    const void *fn = l.form == kAggBuckets ? reinterpret_cast<const void *>(knn_aggregate_buckets)
+                     : l.key32             ? reinterpret_cast<const void *>(knn_aggregate<uint32_t>)
+                                           : reinterpret_cast<const void *>(knn_aggregate<uint64_t>);
+    if (l.lds > 64 * 1024)
+        LOCREC_HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds));
+    const dim3 grid((unsigned)nq), block((unsigned)l.threads);
+    if (l.form == kAggBuckets)
+        hipLaunchKernelGGL(knn_aggregate_buckets, grid, block, l.lds, s, ix->out_rows.p, ix->out_sims.p, ix->out_cnt.p, K,
+                           ix->r_ptr.p, ix->r_pidx.p, ix->r_rating.p, ix->cplace_dev.p, l.cap, (int32_t)ix->cplace_ids.size(),
+                           kAggBucketMax, ix->agg_place.p, ix->agg_est.p, ix->agg_n.p, ix->agg_overflow.p, (int64_t)M, host,
+                           host_flag_src, host_cap, ix->agg_stats.p, (int32_t)last);
+    else if (l.key32)
+        hipLaunchKernelGGL(knn_aggregate<uint32_t>, grid, block, l.lds, s, ix->out_rows.p, ix->out_sims.p, ix->out_cnt.p, K,
+                           ix->r_ptr.p, ix->r_pidx.p, ix->r_rating.p, ix->cplace_dev.p, l.cap, ix->agg_place.p, ix->agg_est.p,
+                           ix->agg_n.p, ix->agg_overflow.p, (int64_t)M, redo, l.fbits, host, host_flag_src, host_cap,
+                           ix->agg_stats.p, (int32_t)last);
+    else
+        hipLaunchKernelGGL(knn_aggregate<uint64_t>, grid, block, l.lds, s, ix->out_rows.p, ix->out_sims.p, ix->out_cnt.p, K,
+                           ix->r_ptr.p, ix->r_pidx.p, ix->r_rating.p, ix->cplace_dev.p, l.cap, ix->agg_place.p, ix->agg_est.p,
+                           ix->agg_n.p, ix->agg_overflow.p, (int64_t)M, redo, l.fbits, host, host_flag_src, host_cap,
+                           ix->agg_stats.p, (int32_t)last);
+    return LOCREC_OK;
+}
+
+// Both launches of a plan.  Two passes: the LDS a block reserves decides how many blocks share a CU, and the typical query
+// needs far less than the worst case - pass 1 runs every query with room for kAggPass1Cap rating rows (in the bucket form
+// where the index's place bitmap fits beside them), the redo pass runs with the full capacity, in the sort form, only the
+// queries pass 1 flagged (its other blocks exit at once).
+int32_t launch_aggregate_plan(locrec_knn_index *ix, const KnnAggPlan &plan, int64_t nq, int K, unsigned char *host = nullptr,
+                              const int32_t *host_flag_src = nullptr, int32_t host_cap = 0)
+{
+    LOCREC_TRY(launch_aggregate(ix, plan.pass1, nq, K, plan.M, 0, !plan.redo_needed, host, host_flag_src, host_cap));
+    if (plan.redo_needed) LOCREC_TRY(launch_aggregate(ix, plan.redo, nq, K, plan.M, 1, true, host, host_flag_src, host_cap));
+    LOCREC_HIP_TRY(hipGetLastError());
+    return LOCREC_OK;
+}
+
 // makeRecommendations0 (:51-70) for the nq neighbour lists the last enqueue_topk left on the device
 int32_t enqueue_aggregate(locrec_knn_index *ix, int64_t nq, int K)
 {
-    hipStream_t s = ix->stream;
-    const int64_t tmax = std::min<int64_t>((int64_t)K * std::max<int64_t>(1, ix->max_r_nnz), kAggCap);
-    const int M = pow2ceil((int)std::max<int64_t>(2, tmax));
+    const KnnAggPlan plan = aggregate_plan(ix, K);
+    const int M = plan.M;
     LOCREC_TRY(ix->agg_place.reserve((size_t)nq * M));
     LOCREC_TRY(ix->agg_est.reserve((size_t)nq * M));
     LOCREC_TRY(ix->agg_n.reserve((size_t)nq));
     LOCREC_TRY(ix->agg_overflow.reserve((size_t)nq));
-    // Two passes.  The LDS a block reserves decides how many blocks share a CU, and the typical
-    // query needs far less than the worst case: pass 1 runs every query with room for 2048 rating
-    // rows (3 blocks of 512 threads per CU instead of one of 1024), pass 2 redoes with the full
-    // capacity only the queries pass 1 flagged (its other blocks exit at once).
-    const int M1 = std::min(M, 2048);
-    const int threads1 = (M1 < M && K <= 512) ? 512 : kAggThreads;
-    // 32-bit sort keys where the compact place index and the position fit them
-    const int64_t nplaces = (int64_t)ix->cplace_ids.size();
-    auto key32 = [&](int cap) { return ceil_log2i(nplaces + 2) + ceil_log2i(cap) <= 32; };
-    // (per position: the key, the product rating x similarity, the neighbour's number - 14 or 18 bytes: four 512-thread
-    // blocks of 2,048 positions share a CU's LDS)
-    auto lds_of = [&](int cap) { return (size_t)cap * (key32(cap) ? 14 : 18) + 8 + (size_t)K * 16 + (size_t)(K + 1) * 4 + 16; };
-    const size_t lds_full = lds_of(M);
-    auto launch = [&](int cap, int threads, int redo) -> int32_t {
-        const size_t lds = lds_of(cap);
-        if (key32(cap)) {
-            if (lds > 64 * 1024)
-                LOCREC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(knn_aggregate<uint32_t>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(knn_aggregate<uint32_t>, dim3((unsigned)nq), dim3(threads), lds, s, ix->out_rows.p, ix->out_sims.p,
-                               ix->out_cnt.p, K, ix->r_ptr.p, ix->r_pidx.p, ix->r_rating.p, ix->cplace_dev.p, cap,
-                               ix->agg_place.p, ix->agg_est.p, ix->agg_n.p, ix->agg_overflow.p, (int64_t)M, redo, ceil_log2i(cap));
-        } else {
-            if (lds > 64 * 1024)
-                LOCREC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(knn_aggregate<uint64_t>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(knn_aggregate<uint64_t>, dim3((unsigned)nq), dim3(threads), lds, s, ix->out_rows.p, ix->out_sims.p,
-                               ix->out_cnt.p, K, ix->r_ptr.p, ix->r_pidx.p, ix->r_rating.p, ix->cplace_dev.p, cap,
-                               ix->agg_place.p, ix->agg_est.p, ix->agg_n.p, ix->agg_overflow.p, (int64_t)M, redo, 16);
-        }
-        return LOCREC_OK;
-    };
-    (void)lds_full;
-    LOCREC_TRY(launch(M1, threads1, 0));
-    if (M1 < M) LOCREC_TRY(launch(M, kAggThreads, 1));
-    LOCREC_HIP_TRY(hipGetLastError());
+    LOCREC_TRY(launch_aggregate_plan(ix, plan, nq, K));
     ix->agg_M = M;
     ix->have_agg = true;
     return LOCREC_OK;
@@ -2308,20 +2341,13 @@ extern "C" int32_t locrec_knn_recommend_neighbours(locrec_knn_index *ix, int64_t
         LOCREC_HIP_TRY(hipMemcpyAsync(ix->out_rows.p, rows.data(), (size_t)K * 4, hipMemcpyHostToDevice, s));
         LOCREC_HIP_TRY(hipMemcpyAsync(ix->out_sims.p, similarities, (size_t)K * 8, hipMemcpyHostToDevice, s));
         LOCREC_HIP_TRY(hipMemcpyAsync(ix->out_cnt.p, &cnt, 8, hipMemcpyHostToDevice, s));
-        const int64_t tmax = std::min<int64_t>((int64_t)K * std::max<int64_t>(1, ix->max_r_nnz), kAggCap);
-        const int M = pow2ceil((int)std::max<int64_t>(2, tmax));
+        const KnnAggPlan plan = aggregate_plan(ix, K);
+        const int M = plan.M;
         LOCREC_TRY(ix->agg_place.reserve((size_t)M));
         LOCREC_TRY(ix->agg_est.reserve((size_t)M));
         LOCREC_TRY(ix->agg_n.reserve(1));
         LOCREC_TRY(ix->agg_overflow.reserve(1));
-        const size_t lds = (size_t)M * 18 + 8 + (size_t)K * 16 + (size_t)(K + 1) * 4 + 16;
-        if (lds > 64 * 1024)
-            LOCREC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(knn_aggregate<uint64_t>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(knn_aggregate<uint64_t>, dim3(1), dim3(kAggThreads), lds, s, ix->out_rows.p, ix->out_sims.p,
-                           ix->out_cnt.p, K, ix->r_ptr.p, ix->r_pidx.p, ix->r_rating.p, ix->cplace_dev.p, M,
-                           ix->agg_place.p, ix->agg_est.p, ix->agg_n.p, ix->agg_overflow.p, (int64_t)M, 0, 16);
-        LOCREC_HIP_TRY(hipGetLastError());
+        LOCREC_TRY(launch_aggregate_plan(ix, plan, 1, K));
         int64_t nout = 0;
         int32_t overflow = 0;
         std::vector<int64_t> hp((size_t)M);
@@ -2364,26 +2390,18 @@ extern "C" int32_t locrec_knn_recommend(locrec_knn_index *ix, int64_t person_id,
     LOCREC_TRY(enqueue_topk(ix, nullptr, row, 1, ix->fp.nnz[row], ix->fc.nnz[row], pw, cw, keff));
     const auto tp1 = std::chrono::steady_clock::now();
     const int K = (int)keff;
-    const int64_t tmax = std::min<int64_t>((int64_t)K * std::max<int64_t>(1, ix->max_r_nnz), kAggCap);
-    const int M = pow2ceil((int)std::max<int64_t>(2, tmax));
+    const KnnAggPlan plan = aggregate_plan(ix, K);
+    const int M = plan.M;
     LOCREC_TRY(ix->agg_place.reserve((size_t)M));
     LOCREC_TRY(ix->agg_est.reserve((size_t)M));
     LOCREC_TRY(ix->agg_n.reserve(1));
     LOCREC_TRY(ix->agg_overflow.reserve(1));
-    const size_t lds = (size_t)M * 18 + 8 + (size_t)K * 16 + (size_t)(K + 1) * 4 + 16;
-    if (lds > 64 * 1024)
-        LOCREC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(knn_aggregate<uint64_t>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     // a request on the stream path: knn_aggregate writes its result into the pinned staging buffer itself
     unsigned char *agg_host = nullptr;
     if (ix->single_pending && !ix->last_scan_fast && (size_t)M * 16 + 64 <= locrec_knn_index::kStageBytes && stage_of(ix) &&
         ix->h_stage_dev && !ix->no_pack)
         agg_host = ix->h_stage_dev;
-    hipLaunchKernelGGL(knn_aggregate<uint64_t>, dim3(1), dim3(kAggThreads), lds, s, ix->out_rows.p, ix->out_sims.p,
-                       ix->out_cnt.p, K, ix->r_ptr.p, ix->r_pidx.p, ix->r_rating.p, ix->cplace_dev.p, M,
-                       ix->agg_place.p, ix->agg_est.p, ix->agg_n.p, ix->agg_overflow.p, (int64_t)M, 0, 16, agg_host,
-                       ix->sel1.p + 4, M);
-    LOCREC_HIP_TRY(hipGetLastError());
+    LOCREC_TRY(launch_aggregate_plan(ix, plan, 1, K, agg_host, ix->sel1.p + 4, M));
     const auto tp2 = std::chrono::steady_clock::now();
     // one batched read-back: counts, flags and the (at most M) rows
     int64_t nout = 0;

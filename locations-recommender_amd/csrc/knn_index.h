@@ -235,6 +235,8 @@ struct locrec_knn_index {
     // batched makeRecommendations0: offsets of the compacted rows and the compacted rows themselves
     DevBuf<int64_t> agg_off, agg_dense_place;
     DevBuf<double> agg_dense_est;
+    bool agg_sort = false;      // LOCREC_KNN_AGG_SORT: A/B, the sort form (knn_aggregate) for every aggregation
+    DevBuf<unsigned long long> agg_stats;  // [3] queries by form since the last locrec_knn_aggregate_stats (knn_aggregate.h)
     int agg_M = 0;              // per-query capacity of agg_place / agg_est of the last batched aggregation
     bool have_agg = false;      // a batched aggregation is resident (locrec_knn_fetch_recommend)
     int32_t agg_first = 0;      // its first internal row (range form), or -1 when rows came from agg_rows

@@ -158,6 +158,14 @@ class KnnIndex:
                                                        c.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(ns)))
         return np.stack([p, c], axis=1)
 
+    def aggregate_stats(self):
+        """Queries the LDS aggregation has served on this index since the previous call (locrec_knn_aggregate_stats):
+        {buckets, sort, flagged} - summed by knn_aggregate_buckets, summed by knn_aggregate (a redone query, an index with
+        too many places, LOCREC_KNN_AGG_SORT), left flagged for the host.  Reads and resets the device counters."""
+        v = (C.c_int64 * 3)()
+        L.check(L.lib().locrec_knn_aggregate_stats(self._h, v))
+        return {"buckets": int(v[0]), "sort": int(v[1]), "flagged": int(v[2])}
+
     def ht_last_hits(self, nq):
         """What the hit pre-pass of the last batched head / tail scan - of nq queries - left on the device
         (locrec_knn_ht_last_hits): {query_tile, tiles, slice0, nslices, tile_base int64[tiles + 1],
