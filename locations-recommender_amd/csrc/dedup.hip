@@ -32,16 +32,30 @@ constexpr int64_t kMaxPairBudget = (int64_t)1 << 30;
 constexpr int32_t kLdsCells = 1280;            // DP row cells of 64 lanes x u16 that fit the 160 KiB of a CU
 constexpr int64_t kLdsMaxLong = 65535;         // ... whose values (<= the longer name's length) fit u16
 constexpr int64_t kScratchBytes = (int64_t)256 << 20;  // global DP rows of the names beyond that, per launch
+constexpr int32_t kMaxThreshold = std::numeric_limits<int32_t>::max() - 1;  // every kernel computes k + 1 in int32
 
 // LOCREC_DEDUP_PAIR_BUDGET: candidate pairs per chunk (the result does not depend on it; read at every call so that a
 // test can force many chunks).  LOCREC_DEDUP_FULL_DP=1: every candidate goes through the full matrix of
 // Levenshtein.scala - no length pre-test, no band, no early exit - the A/B partner of the banded kernel.
+// LOCREC_DEDUP_SCRATCH_BYTES: bytes of global DP rows per launch of tier (c), 4 .. 256 MiB (the default); one pair at
+// least per launch.  The result does not depend on it; read at every call so that a test can force many launches.
 int64_t pair_budget()
 {
     int64_t b = kDefaultPairBudget;
     if (const char *e = std::getenv("LOCREC_DEDUP_PAIR_BUDGET")) b = atoll(e);
     return std::min(std::max<int64_t>(b, 1), kMaxPairBudget);
 }
+
+int64_t scratch_bytes()
+{
+    int64_t b = kScratchBytes;
+    if (const char *e = std::getenv("LOCREC_DEDUP_SCRATCH_BYTES")) b = atoll(e);
+    return std::min(std::max<int64_t>(b, 4), kScratchBytes);
+}
+
+// A threshold of INT32_MAX ("names do not matter") is served as INT32_MAX - 1: no name has that many units, so no
+// result changes, and k + 1 stays an int32.
+int32_t clamp_threshold(int32_t k) { return std::min(k, kMaxThreshold); }
 
 bool full_dp_forced()
 {
@@ -317,7 +331,7 @@ int32_t lev_pairs(int64_t m, const uint32_t *pa, const uint32_t *pb, const int64
     }
     if (lp.long_pairs) {
         const int64_t row_bytes = (int64_t)lp.long_cells * 4;
-        const int64_t per_launch = std::max<int64_t>(1, std::min<int64_t>((int64_t)lp.long_pairs, kScratchBytes / row_bytes));
+        const int64_t per_launch = std::max<int64_t>(1, std::min<int64_t>((int64_t)lp.long_pairs, scratch_bytes() / row_bytes));
         DevBuf<int32_t> scratch;
         LOCREC_TRY(scratch.alloc((size_t)(per_launch * (int64_t)lp.long_cells)));
         for (int64_t first = 0; first < (int64_t)lp.long_pairs; first += per_launch) {
@@ -466,7 +480,7 @@ try {
     LOCREC_TRY(bind_names(A, n, a_offsets, a_units, mem, "first", s));
     LOCREC_TRY(bind_names(B, n, b_offsets, b_units, mem, "second", s));
     LOCREC_TRY(o.bind(out_distances, n, mem));
-    const int32_t k = max_difference < 0 ? -1 : max_difference;
+    const int32_t k = max_difference < 0 ? -1 : clamp_threshold(max_difference);
     LOCREC_TRY(lev_pairs(n, nullptr, nullptr, A.off.p, A.units.p, B.off.p, B.units.p, k, full_dp_forced(), o.p, s));
     LOCREC_TRY(o.deliver(n, s));
     LOCREC_HIP_TRY(hipStreamSynchronize(s));
@@ -572,7 +586,7 @@ try {
         LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (rk0 / rk1 are released here)
     }
 
-    const int32_t k = max_name_difference;
+    const int32_t k = clamp_threshold(max_name_difference);
     int64_t total_same = 0;
     if (max_meters >= 0.0 && k >= 0) {
         const Grid g = make_grid(max_meters);
