@@ -361,6 +361,63 @@ int32_t locrec_knn_pool_stats(int64_t *out_waves, int64_t *out_member_tiles, int
                               int64_t *out_host_syncs);
 
 /*
+ * KNN for visitors: rating vectors that are no rows of the index - a person who arrived after the cut of the visit
+ * table the index was built from, or whose visits have changed since.  nv visitors as two CSR families (nv + 1 row
+ * pointers each, indices in the index's ORIGINAL place / category numbering, strictly ascending) in `mem`
+ * (LOCREC_MEM_HOST, or LOCREC_MEM_DEVICE: on the index's device); every other array is a host array.
+ * For a visitor v and an index built from the persons P, every result equals what locrec_knn_query_batch,
+ * locrec_knn_recommend_batch and locrec_knn_recommend_ranked_batch return for v on an index built from P + {v}, with v
+ * under an id no person has: neighbour ids, counts and similarity bits, place ids and row counts are identical,
+ * estimated ratings within 1e-6 relative.  So v is a candidate of nobody, nobody is left out as "self", v has no
+ * rating rows, ties fall by (similarity desc, person_id asc) among P, a list holds at most min(k_nearest, n) entries
+ * and "every positive neighbour" begins at k_nearest >= n.  An entry at an index >= the index's place / category
+ * dimension is legal (the reference's builder would have given every vector the larger size): it enters the vector's
+ * length and no dot product.
+ * Output layouts, padding (-1 / 0.0), the capacity protocol and the chunking of huge nv x k_nearest results are those
+ * of the three person calls.  exclude_offsets[nv + 1] / exclude_place_ids: per visitor a list of place ids its ranking
+ * leaves out (locrec_rank_recommendations_batch_excluding's lists; a caller who wants only new places passes the
+ * visitor's rated places), or NULL, NULL.
+ * Refusals, all before any result is written, *out_bad_visitor (may be NULL) = the first offending visitor, or -1 when
+ * no single visitor is at fault: NULL arguments and negative counts; the requires on the weights and k_nearest with
+ * their messages; then per visitor what create refuses in a row - row pointers that turn back, negative, unsorted or
+ * repeated indices, a non-finite value, a zero norm, 2^21 or more entries (LOCREC_E_INVALID_ARG) - an empty place or
+ * category vector (LOCREC_E_NOT_FOUND, "No such person: ..."), and, on an index that renumbers its place dimensions
+ * by popularity (integer data by construction), a place value that is no integer below 65536 (LOCREC_E_INVALID_ARG:
+ * its dot products would be summed in another order than BLAS.dot's; category dimensions are never renumbered, so
+ * category values may be any finite numbers).  An index without the renumbering takes any finite values and stays
+ * bit-exact.  nv == 0 succeeds with empty outputs.
+ * All calls are synchronous.  Afterwards nothing is resident for locrec_knn_fetch_*, and every other call on the
+ * handle returns what it returned before.
+ * stats: this thread's last visitors call: out[0] tiles of 16 visitors, [1] tiles served without a top-K
+ * (k_nearest >= n), [2] tiles through the tiled selection, [3] entries beyond the index's dimensions, [4] 1 if the
+ * index renumbers its place dimensions, [5] launches of the stage kernel, [6] launches of the scan kernel, [7] waits
+ * for the stream.
+ */
+int32_t locrec_knn_visitors_query_batch(
+    locrec_knn_index *index, int64_t nv,
+    const int64_t *p_rowptr, const int32_t *p_idx, const double *p_val,
+    const int64_t *c_rowptr, const int32_t *c_idx, const double *c_val, int32_t mem,
+    double place_weight, double category_weight, int64_t k_nearest,
+    int64_t *out_person_ids, double *out_similarities, int64_t *out_counts, int64_t *out_bad_visitor);
+int32_t locrec_knn_visitors_recommend_batch(
+    locrec_knn_index *index, int64_t nv,
+    const int64_t *p_rowptr, const int32_t *p_idx, const double *p_val,
+    const int64_t *c_rowptr, const int32_t *c_idx, const double *c_val, int32_t mem,
+    double place_weight, double category_weight, int64_t k_nearest,
+    int64_t *out_offsets, int64_t *out_place_ids, double *out_estimated_ratings, int64_t *inout_capacity,
+    int64_t *out_bad_visitor);
+int32_t locrec_knn_visitors_recommend_ranked_batch(
+    locrec_knn_index *index, int64_t nv,
+    const int64_t *p_rowptr, const int32_t *p_idx, const double *p_val,
+    const int64_t *c_rowptr, const int32_t *c_idx, const double *c_val, int32_t mem,
+    double place_weight, double category_weight, int64_t k_nearest,
+    int64_t n_places, const int64_t *place_ids, const int64_t *place_region_ids,
+    const int64_t *target_region_ids, int64_t max_recommendations,
+    const int64_t *exclude_offsets, const int64_t *exclude_place_ids,
+    int64_t *out_place_ids, double *out_estimated_ratings, int64_t *out_counts, int64_t *out_bad_visitor);
+int32_t locrec_knn_visitors_stats(int64_t out[8]);
+
+/*
  * One request with its candidate scan split over several GPUs (SURVEY.md 8e "KNN single request,
  * latency mode").  Every GPU holds the whole index (132 MB at cfg2, 1.3 GB at cfg4: nothing next to
  * 288 GB) and scans candidate shard shard_index of shard_count, a contiguous range of the

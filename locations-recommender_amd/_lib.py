@@ -135,6 +135,17 @@ SIGNATURES = {
     "locrec_knn_pool_recommend_ranked_batch": [C.c_void_p, C.c_int64, _i32p, _i64p, C.c_double, C.c_double, C.c_int64,
                                                C.c_int64, _i64p, _i64p, _i64p, C.c_int64, _i64p, _f64p, _i64p, _i64p],
     "locrec_knn_pool_stats": [_i64p, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p],
+    # visitors: the six vector arrays are void* because they may be device pointers (mem)
+    "locrec_knn_visitors_query_batch": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int64, _i64p, _f64p, _i64p, _i64p],
+    "locrec_knn_visitors_recommend_batch": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int64, _i64p, _i64p, _f64p,
+                                            _i64p, _i64p],
+    "locrec_knn_visitors_recommend_ranked_batch": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int64,
+                                                   C.c_int64, _i64p, _i64p, _i64p, C.c_int64, _i64p, _i64p,
+                                                   _i64p, _f64p, _i64p, _i64p],
+    "locrec_knn_visitors_stats": [_i64p],
     "locrec_set_devices": [C.c_int32, _i32p],
     "locrec_knn_replicas_create": [C.c_int32, _i32p, C.c_int64, _i64p, _i64p, _i32p, _f64p, C.c_int32, _i64p, _i32p, _f64p, C.c_int32,
                                    _i64p, _i64p, _i64p, C.POINTER(C.c_void_p)],

@@ -9,7 +9,9 @@
 // locrec_ prefix, and the public names defined here forward to them for K <= LOCREC_KNN_BATCH_MAX_K (and, in the
 // recommend calls, for K >= N - 1): those calls run exactly the code they ran before.  Calls between these functions
 // inside knn.hip stay on the originals, which is right: the functions here serve K > LOCREC_KNN_BATCH_MAX_K themselves.
-// Any other K takes the tiled top-K of knn_large.hip (knn_anyk.h).
+// Any other K takes the tiled top-K of knn_large.hip (knn_anyk.h).  locrec_knn_destroy is renamed the same way: the public
+// one (knn_visitors_api.h) drops the handle's side record for visitors - what the hashed handle has no member for - and
+// forwards.
 //
 // The tiled path keeps its device buffers in handle members that already exist (the handle's layout is hashed too):
 //   lkb_S                     a tile's similarities, transposed, and the masked row-major tile of the aggregation
@@ -26,6 +28,7 @@
 #define locrec_knn_query_shard knn_query_shard_lds
 #define locrec_knn_recommend_batch knn_recommend_batch_lds
 #define locrec_knn_recommend_range_async knn_recommend_range_async_lds
+#define locrec_knn_destroy knn_destroy_handle
 
 #include "knn.hip"
 
@@ -35,6 +38,7 @@
 #undef locrec_knn_query_shard
 #undef locrec_knn_recommend_batch
 #undef locrec_knn_recommend_range_async
+#undef locrec_knn_destroy
 
 #include "knn_anyk.h"
 
@@ -498,6 +502,11 @@ extern "C" int32_t locrec_knn_pool_stats(int64_t *out_waves, int64_t *out_member
     if (out_host_syncs) *out_host_syncs = st.host_syncs;
     return LOCREC_OK;
 }
+
+// =====================================================================================================
+// Visitors: rating vectors that are no rows of the index (locrec_knn_visitors_*), and locrec_knn_destroy in front of
+// knn.hip's, which drops the handle's side record (knn_visitors_side.h) first.
+#include "knn_visitors_api.h"
 
 // Measurement and tests only (include/locrec.h): what the hit pre-pass of the last batched head / tail scan left in the
 // handle's workspaces (knn_ht_prepass.h).  knn.hip and the handle's layout are hashed (see the head of this file), so

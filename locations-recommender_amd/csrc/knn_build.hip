@@ -30,6 +30,7 @@
 
 #include "knn_build_open.h"
 #include "knn_index.h"
+#include "knn_visitors_side.h"
 #include "offline.h"
 
 namespace {
@@ -989,6 +990,8 @@ int32_t knn_build_device(int64_t n, const int64_t *ids, const int64_t *p_ptr, co
     }
     LOCREC_TRY(b.ratings_and_transpose());
     lap("ratings (CSR + transpose)");
+    // the handle's side record for visitors (knn_visitors_side.h) keeps the renumbering; empty without plan.use_pop
+    LOCREC_TRY(knn_visitors_attach(ix.get(), b.new_of_old));
     *out = ix.release();
     return LOCREC_OK;
 }

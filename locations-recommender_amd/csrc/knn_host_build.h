@@ -4,6 +4,7 @@
 #pragma once
 
 #include "knn_build_open.h"
+#include "knn_visitors_side.h"
 
 // Per-row format fallback (see knn_build.hip): the wide rows are all padding in the packed SELL images.  The image is
 // built from every row (build_family_device) and the wide rows' element groups are blanked afterwards.
@@ -366,6 +367,8 @@ static int32_t knn_create_host(
         LOCREC_HIP_TRY(hipStreamSynchronize(ix->stream));
     }
     lap("rid + norms + sync");
+    // the handle's side record for visitors (knn_visitors_side.h) keeps the renumbering; empty without plan.use_pop
+    LOCREC_TRY(locrec::knn_visitors_attach_host(ix.get(), new_of_old));
     *out = ix.release();
     return LOCREC_OK;
 } LOCREC_CATCH_ALL

@@ -1254,3 +1254,6 @@ int32_t knn_topk_recommend_batch(locrec_knn_index *ix, const int32_t *rows, int6
 
 // a pool of indexes: the kernels above for every member's tile in shared launches (locrec_knn_pool_*, knn_batch.hip)
 #include "knn_pool.h"
+
+// visitors: rating vectors that are no rows of the index, through the tile scan above (locrec_knn_visitors_*, knn_batch.hip)
+#include "knn_visitors.h"

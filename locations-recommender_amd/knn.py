@@ -301,6 +301,111 @@ class KnnIndex:
                      L.ptr(oi, C.c_int64), L.ptr(osc, C.c_double), L.ptr(cnt, C.c_int64)))
         return oi, osc, cnt
 
+    # visitors: rating vectors that are no rows of the index (locrec_knn_visitors_*)
+    VISITOR_STATS = ("tiles", "tiles_all", "tiles_topk", "beyond", "renumbered", "stage_launches", "scan_launches",
+                     "host_syncs")
+
+    @staticmethod
+    def _visitor_args(p_rowptr, p_idx, p_val, c_rowptr, c_idx, c_val):
+        """(nv, the six pointers, mem, what keeps them alive): numpy arrays -> LOCREC_MEM_HOST, CUDA tensors of the ABI's
+        dtypes on the current device -> LOCREC_MEM_DEVICE, read where they lie."""
+        arrays = [p_rowptr, p_idx, p_val, c_rowptr, c_idx, c_val]
+        on_device = [getattr(a, "is_cuda", False) for a in arrays]
+        if any(on_device):
+            import torch
+            if not all(on_device):
+                raise L.IllegalArgumentException("requirement failed: the six vector arrays are all host arrays or all device tensors")
+            dtypes = [torch.int64, torch.int32, torch.float64] * 2
+            for a, dt in zip(arrays, dtypes):
+                if a.dtype != dt or not a.is_contiguous():
+                    raise L.IllegalArgumentException("requirement failed: contiguous device tensors of the ABI's dtypes "
+                                                     "(int64 row pointers, int32 indices, float64 values) are required")
+            L.require_current_device(arrays)
+            torch.cuda.current_stream().synchronize()  # the library reads the arrays on its own stream
+            ptrs = [C.c_void_p(a.data_ptr()) if a.numel() > 0 else None for a in arrays]
+            nv = int(p_rowptr.numel()) - 1
+            if int(c_rowptr.numel()) - 1 != nv:
+                raise L.IllegalArgumentException("requirement failed: one place and one category vector per visitor")
+            return max(nv, 0), ptrs, L.MEM_DEVICE, arrays
+        keep = [L.as_i64(p_rowptr), L.as_i32(p_idx), L.as_f64(p_val), L.as_i64(c_rowptr), L.as_i32(c_idx), L.as_f64(c_val)]
+        nv = len(keep[0]) - 1
+        if len(keep[3]) - 1 != nv or nv < 0:
+            raise L.IllegalArgumentException("requirement failed: one place and one category vector per visitor")
+        if len(keep[1]) != len(keep[2]) or len(keep[4]) != len(keep[5]):
+            raise L.IllegalArgumentException("requirement failed: Sparse vectors require that the dimension of the "
+                                             "indices match the dimension of the values.")
+        ptrs = [C.c_void_p(a.ctypes.data) if a.size else None for a in keep]
+        return nv, ptrs, L.MEM_HOST, keep
+
+    @staticmethod
+    def _visitor_call(fn, *args):
+        """fn(*args, &bad): a refused call raises with `bad_visitor` set on the exception (-1: no single visitor)."""
+        bad = C.c_int64(-1)
+        try:
+            L.check(fn(*args, C.byref(bad)))
+        except L.IllegalArgumentException as e:
+            e.bad_visitor = bad.value
+            raise
+
+    def visitors_query_batch(self, p_rowptr, p_idx, p_val, c_rowptr, c_idx, c_val, pw, cw, k):
+        """findSimilarPersons for visitors - rating vectors (CSR, the index's original numbering) that are no rows of
+        the index: (person_ids[nv, k], similarities[nv, k], counts[nv]) in query_batch's layout, each row what
+        query_batch returns for the visitor on an index built with it."""
+        nv, ptrs, mem, keep = self._visitor_args(p_rowptr, p_idx, p_val, c_rowptr, c_idx, c_val)
+        kk = max(int(k), 0)
+        ids, sims, cnt = np.empty((nv, kk), np.int64), np.empty((nv, kk), np.float64), np.empty(nv, np.int64)
+        self._visitor_call(L.lib().locrec_knn_visitors_query_batch, self._h, nv, *ptrs, mem, float(pw), float(cw), int(k),
+                           L.ptr(ids, C.c_int64), L.ptr(sims, C.c_double), L.ptr(cnt, C.c_int64))
+        return ids, sims, cnt
+
+    def visitors_recommend_batch(self, p_rowptr, p_idx, p_val, c_rowptr, c_idx, c_val, pw, cw, k):
+        """makeRecommendations for visitors: (offsets[nv + 1], place_ids, estimated_ratings) in recommend_batch's layout.
+        Nothing stays resident after a visitors call, so a result that does not fit the output arrays is computed AGAIN
+        by a second call (stage, scan and aggregation for the whole batch): the arrays start at 65,536 rows and remember
+        the largest result this object has returned, so only a handle's first large request pays twice."""
+        nv, ptrs, mem, keep = self._visitor_args(p_rowptr, p_idx, p_val, c_rowptr, c_idx, c_val)
+        off = np.zeros(nv + 1, np.int64)
+        room = max(getattr(self, "_visitor_room", 0), 1 << 16)  # what the largest call so far returned: one pass as a rule
+        cap = C.c_int64(room)
+        places, est = np.empty(room, np.int64), np.empty(room, np.float64)
+        for _ in range(2):  # a call whose room is too small sizes the result, the second fills it
+            self._visitor_call(L.lib().locrec_knn_visitors_recommend_batch, self._h, nv, *ptrs, mem, float(pw), float(cw),
+                               int(k), L.ptr(off, C.c_int64), L.ptr(places, C.c_int64), L.ptr(est, C.c_double), C.byref(cap))
+            if cap.value <= len(places):
+                break
+            places, est = np.empty(cap.value, np.int64), np.empty(cap.value, np.float64)
+            cap = C.c_int64(len(places))
+        self._visitor_room = max(room, int(off[-1]))
+        return off, places[:off[-1]].copy(), est[:off[-1]].copy()
+
+    def visitors_recommend_ranked_batch(self, p_rowptr, p_idx, p_val, c_rowptr, c_idx, c_val, pw, cw, k, place_ids,
+                                        place_region_ids, target_region_ids, max_recommendations, exclude=None):
+        """The visitors' request to its end: per visitor the places of its target region, top max_recommendations by
+        estimated rating, in recommend_ranked_batch's layout.  exclude = (offsets[nv + 1], place_ids): per visitor the
+        places its ranking leaves out (its rated places, for "only new places")."""
+        nv, ptrs, mem, keep = self._visitor_args(p_rowptr, p_idx, p_val, c_rowptr, c_idx, c_val)
+        pl, reg, tgt, width, (oi, osc, cnt) = self._ranked_args(nv, place_ids, place_region_ids, target_region_ids,
+                                                                max_recommendations)
+        ex_off = ex_ids = None
+        if exclude is not None:
+            ex_off, ex_ids = L.as_i64(exclude[0]), L.as_i64(exclude[1])
+            if len(ex_off) != nv + 1:
+                raise L.IllegalArgumentException("requirement failed: one exclusion list per visitor (nv + 1 offsets)")
+            if nv >= 0 and len(ex_off) and ex_off[-1] > len(ex_ids):
+                raise L.IllegalArgumentException("requirement failed: the exclusion offsets end beyond the listed ids")
+        self._visitor_call(L.lib().locrec_knn_visitors_recommend_ranked_batch, self._h, nv, *ptrs, mem, float(pw), float(cw),
+                           int(k), len(pl), L.ptr(pl, C.c_int64), L.ptr(reg, C.c_int64), L.ptr(tgt, C.c_int64), width,
+                           L.ptr(ex_off, C.c_int64), L.ptr(ex_ids, C.c_int64), L.ptr(oi, C.c_int64), L.ptr(osc, C.c_double),
+                           L.ptr(cnt, C.c_int64))
+        return oi, osc, cnt
+
+    @classmethod
+    def visitors_stats(cls):
+        """What this thread's last visitors call did (locrec_knn_visitors_stats)."""
+        v = (C.c_int64 * 8)()
+        L.check(L.lib().locrec_knn_visitors_stats(v))
+        return dict(zip(cls.VISITOR_STATS, (int(x) for x in v)))
+
     def query_shard(self, person_id, pw, cw, k, shard_index, shard_count):
         """Local top-K of candidate shard shard_index of shard_count (include/locrec.h)."""
         cap = int(max(1, min(k, max(1, self.n))))
@@ -542,6 +647,32 @@ class KnnRecommender:
         with self._index.lock:
             off, places, est = self._index.recommend_batch(ids, self.placeWeight, self.categoryWeight, self.kNearest)
         return pd.DataFrame({"person_id": np.repeat(ids, np.diff(off)), "place_id": places, "estimated_rating": est})
+
+    @staticmethod
+    def _visitor_csr(placeVector, categoryVector):
+        for v in (placeVector, categoryVector):
+            if not isinstance(v, SparseVector):
+                raise L.IllegalArgumentException("requirement failed: a visitor is a pair of SparseVectors")
+        return (np.array([0, len(placeVector.indices)], np.int64), placeVector.indices, placeVector.values,
+                np.array([0, len(categoryVector.indices)], np.int64), categoryVector.indices, categoryVector.values)
+
+    def findSimilarPersonsForVisitor(self, placeVector, categoryVector):
+        """findSimilarPersons for somebody the frames do not know: the two rating vectors instead of a person id ->
+        (person_id, similarity), what findSimilarPersons returns for that person once the frames hold it."""
+        import pandas as pd
+        with self._index.lock:
+            ids, sims, cnt = self._index.visitors_query_batch(*self._visitor_csr(placeVector, categoryVector),
+                                                              self.placeWeight, self.categoryWeight,
+                                                              min(self.kNearest, max(1, self._index.n)))
+        return pd.DataFrame({"person_id": ids[0, :cnt[0]], "similarity": sims[0, :cnt[0]]})
+
+    def makeRecommendationsForVisitor(self, placeVector, categoryVector):
+        """makeRecommendations for somebody the frames do not know -> (place_id, estimated_rating)."""
+        import pandas as pd
+        with self._index.lock:
+            off, places, est = self._index.visitors_recommend_batch(*self._visitor_csr(placeVector, categoryVector),
+                                                                    self.placeWeight, self.categoryWeight, self.kNearest)
+        return pd.DataFrame({"place_id": places, "estimated_rating": est})
 
     def makeRecommendations(self, personId):
         """(place_id, estimated_rating) (KnnRecommender.scala:22-25,51-70)."""

@@ -227,6 +227,44 @@ def knn_recommend_places_batch(data_dir, region_ids, requests, place_weight, cat
         ix.close()  # drops the reference only
 
 
+def knn_visitor_requests(data_dir, region_ids, visits, target_region_ids, place_weight, category_weight, k_nearest,
+                         max_recommendations=10, new_places=False):
+    """Requests of persons the region set's index does not hold - they arrived after the cut of the visit table it was
+    built from, or their visits have changed since.  visits: mapping with visitor_id, place_id, category_id (one row a
+    place visit; host arrays or CUDA tensors); target_region_ids: a mapping visitor id -> region, one region for all, or
+    one region per visitor in ascending visitor id.  The index comes from the handle cache under
+    knn_make_recommendations' key, the vectors from prep.visitor_vectors, the answer from ONE ranked visitors call.
+    -> a list of (visitor_id, place_ids, estimated_ratings), ascending visitor id.
+    new_places=True: the places a visitor has rated are left out."""
+    from . import _cache, prep
+    from .knn import KnnIndex
+    _cache.require_gpu_backend("knn_visitor_requests")
+    ids, vectors, rated = prep.visitor_vectors(visits["visitor_id"], visits["place_id"], visits["category_id"])
+    host_ids = np.asarray(ids.cpu().numpy() if hasattr(ids, "cpu") else ids, np.int64)
+    if hasattr(target_region_ids, "keys"):
+        targets = np.asarray([target_region_ids[int(v)] for v in host_ids], np.int64)
+    elif np.ndim(target_region_ids) == 0:
+        targets = np.full(len(host_ids), int(target_region_ids), np.int64)
+    else:
+        targets = np.asarray(target_region_ids, np.int64)
+    if len(targets) != len(host_ids):
+        raise L.IllegalArgumentException("requirement failed: one target region per visitor is required")
+    exclude = None
+    if new_places:
+        exclude = tuple(np.asarray(a.cpu().numpy() if hasattr(a, "cpu") else a, np.int64) for a in rated)
+    place_ids, place_regions = load_places(data_dir)
+    key = _cache.files_key([generate_file_name(region_ids, data_dir, f)
+                            for f in ("place_rating_vectors", "category_rating_vectors", "place_ratings")])
+    ix = KnnIndex.through_cache(key, lambda: knn_index_from_parquet(data_dir, region_ids))
+    try:
+        with ix.lock:
+            oi, osc, cnt = ix.visitors_recommend_ranked_batch(*vectors, place_weight, category_weight, k_nearest, place_ids,
+                                                              place_regions, targets, max_recommendations, exclude=exclude)
+    finally:
+        ix.close()  # drops the reference only
+    return [(int(v), oi[i, :cnt[i]].copy(), osc[i, :cnt[i]].copy()) for i, v in enumerate(host_ids)]
+
+
 def sg_recommend_places_batch(data_dir, region_ids, requests, epsilon, max_iterations, alpha=0.15, max_recommendations=10,
                               on_device=True, new_places=False):
     """Many requests of one region pair (StochasticRecommenderMain.scala:53-75): requests is a sequence of

@@ -268,6 +268,24 @@ def knn_index_from_visits(person_ids, place_ids, category_ids, places_top_n=VISI
     return KnnIndex(ids, p_ptr, p_idx, p_val, p_dim, c_ptr, c_idx, c_val, c_dim, p_ptr, pe, pr)
 
 
+def visitor_vectors(visitor_ids, place_ids, category_ids, places_top_n=VISITED_PLACES_TOP_N,
+                    categories_top_n=VISITED_CATEGORIES_TOP_N):
+    """The same pipeline for visitors - persons an index does not hold (KnnIndex.visitors_*): their place visits
+    (visitor_id, place_id, category_id) -> calc_ratings -> calc_rating_vectors, device in, device out.
+    -> (visitor ids ascending, (p_rowptr, p_idx, p_val, c_rowptr, c_idx, c_val), (rated_offsets, rated_place_ids)):
+    the CSR vectors a visitors call takes (a vector index is the entity id itself) and each visitor's rated place ids,
+    the exclusion lists of "only new places"."""
+    pp, pe, pr = calc_ratings(visitor_ids, place_ids, places_top_n)
+    cp, ce, cr = calc_ratings(visitor_ids, category_ids, categories_top_n)
+    ids, p_ptr, p_idx, p_val, _ = calc_rating_vectors(pp, pe, pr)
+    ids_c, c_ptr, c_idx, c_val, _ = calc_rating_vectors(cp, ce, cr)
+    if not (len(ids) == len(ids_c) and bool((ids == ids_c).all())):
+        raise L.IllegalArgumentException("place and category visits name different persons")
+    cont = (lambda a: a.contiguous()) if _is_tensor(ids) else np.ascontiguousarray
+    # the rating rows are ordered by (person, place), one per entry of the place vector: the vector's row pointers
+    return ids, tuple(cont(a) for a in (p_ptr, p_idx, p_val, c_ptr, c_idx, c_val)), (cont(p_ptr), cont(pe))
+
+
 # ---- the stochastic graph from place visits (StochasticGraphBuilderMain.scala:47-66) ----------------------
 
 def calc_count_edges(source_ids, target_ids, top_n):
