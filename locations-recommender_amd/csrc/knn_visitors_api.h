@@ -95,7 +95,8 @@ extern "C" int32_t locrec_knn_visitors_query_batch(locrec_knn_index *ix, int64_t
         return LOCREC_OK;
     }
     hipStream_t s = ix->stream;
-    const int64_t chunk = locrec::knn_visitors_chunk(k);
+    // (the switch is read at every call: tests run chunks of a few visitors beside the default in one process)
+    const int64_t chunk = locrec::knn_visitors_chunk(k, locrec::knn_visitors_chunk_budget(std::getenv("LOCREC_KNN_VISITORS_CHUNK_BYTES")));
     int32_t rc = LOCREC_OK;
     for (int64_t v0 = 0; v0 < nv && rc == LOCREC_OK; v0 += chunk) {
         const int64_t cn = std::min(chunk, nv - v0);

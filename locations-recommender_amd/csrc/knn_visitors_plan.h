@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <cstdlib>
 
 #include "knn_pool_plan.h"
 
@@ -22,11 +23,22 @@ inline int64_t knn_visitors_keff(int64_t k, int64_t n) { return std::min<int64_t
 constexpr int64_t kVisitorsEntryBytes = 20;
 constexpr int64_t kVisitorsChunkBytes = (int64_t)2 << 30;
 
-// visitors per chunk of a neighbour-list call: nv x K entries stay within 2 GiB; whole tiles where a chunk holds one
-inline int64_t knn_visitors_chunk(int64_t k)
+// visitors per chunk of a neighbour-list call: nv x K entries stay within the budget (2 GiB); whole tiles where a chunk
+// holds one; one visitor at least
+inline int64_t knn_visitors_chunk(int64_t k, int64_t budget = kVisitorsChunkBytes)
 {
-    const int64_t c = std::max<int64_t>(1, kVisitorsChunkBytes / (std::max<int64_t>(1, k) * kVisitorsEntryBytes));
+    const int64_t c = std::max<int64_t>(1, budget / (std::max<int64_t>(1, k) * kVisitorsEntryBytes));
     return c >= kLkbQt ? c / kLkbQt * kLkbQt : c;
+}
+// the budget from the text of LOCREC_KNN_VISITORS_CHUNK_BYTES (tests: chunks of a few visitors without gigabytes of
+// results): null, empty or no number: the default; clamped to [1, 2 GiB].  The result does not depend on it.
+inline int64_t knn_visitors_chunk_budget(const char *text)
+{
+    if (!text || !*text) return kVisitorsChunkBytes;
+    char *end = nullptr;
+    const long long b = std::strtoll(text, &end, 10);
+    if (end == text) return kVisitorsChunkBytes;
+    return std::min<int64_t>(kVisitorsChunkBytes, std::max<int64_t>(1, (int64_t)b));
 }
 
 // the most rows (16 bytes each) a recommendation call may leave resident: one per visitor and place; refused beyond 48 GB

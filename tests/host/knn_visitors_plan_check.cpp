@@ -49,7 +49,31 @@ int main()
     CHECK(knn_visitors_chunk(6710887) == 15);           // ... and no longer
     CHECK(knn_visitors_chunk(107374182) == 1 && knn_visitors_chunk(107374183) == 1);   // one list beyond 2 GiB: still served
     CHECK(knn_visitors_chunk(1) == ((int64_t)2 << 30) / 20 / 16 * 16);
+    // the budget as an argument (LOCREC_KNN_VISITORS_CHUNK_BYTES): brute force at 100 bytes, at 320 x K (one tile, to the
+    // byte) and at the default, which is what the one-argument form takes
+    for (int64_t k : {1, 2, 5, 50, 304, 305, 2960, 2965, 2000000, 6710886, 6710887}) {
+        for (int64_t budget : {(int64_t)100, 320 * k - 1, 320 * k, 320 * k + 19, 2 * 320 * k - 1, 2 * 320 * k, (int64_t)2 << 30}) {
+            int64_t brute = 0;  // the most visitors whose lists fit, by counting
+            while ((brute + 1) * k * 20 <= budget && brute < 70000) ++brute;
+            const int64_t c = knn_visitors_chunk(k, budget);
+            CHECK(c >= 1 && (c < 16 || c % 16 == 0));
+            if (brute < 70000) CHECK(c == (brute >= 16 ? brute / 16 * 16 : brute >= 1 ? brute : 1));
+            CHECK(c == 1 || c * k * 20 <= budget);
+        }
+        CHECK(knn_visitors_chunk(k, 320 * k) == 16 && knn_visitors_chunk(k, 320 * k - 1) == 15);
+        CHECK(knn_visitors_chunk(k, 100 * k) == 5 && knn_visitors_chunk(k, 640 * k) == 32 && knn_visitors_chunk(k, 640 * k - 1) == 16);
+        CHECK(knn_visitors_chunk(k, (int64_t)2 << 30) == knn_visitors_chunk(k));
+    }
+    CHECK(knn_visitors_chunk(1, 100) == 5 && knn_visitors_chunk(5, 100) == 1 && knn_visitors_chunk(6, 100) == 1);
+    // the switch's text: unset, empty and no number are the default; clamped to [1, 2 GiB]
+    CHECK(knn_visitors_chunk_budget(nullptr) == kVisitorsChunkBytes && knn_visitors_chunk_budget("") == kVisitorsChunkBytes);
+    CHECK(knn_visitors_chunk_budget("x") == kVisitorsChunkBytes && knn_visitors_chunk_budget("100") == 100);
+    CHECK(knn_visitors_chunk_budget("0") == 1 && knn_visitors_chunk_budget("-5") == 1);
+    CHECK(knn_visitors_chunk_budget("2147483648") == kVisitorsChunkBytes && knn_visitors_chunk_budget("2147483647") == 2147483647);
+    CHECK(knn_visitors_chunk_budget("99999999999999999999999") == kVisitorsChunkBytes);
     // rows a recommendation call may leave: refused beyond 48 GB
+    CHECK(knn_visitors_worst_row_bytes(49152, 65536) == kVisitorsMaxRowBytes);          // 3 x 2^30 rows: served ...
+    CHECK(knn_visitors_worst_row_bytes(49153, 65536) > kVisitorsMaxRowBytes);           // ... one visitor more: refused
     CHECK(knn_visitors_worst_row_bytes(1024, 100000) == (int64_t)1024 * 100000 * 16);
     CHECK(knn_visitors_worst_row_bytes(33, 0) == 33 * 16);
     CHECK(knn_visitors_worst_row_bytes(32212, 100000) <= kVisitorsMaxRowBytes && knn_visitors_worst_row_bytes(32212, 100001) > kVisitorsMaxRowBytes);
