@@ -656,6 +656,63 @@ int32_t locrec_sg_recommend_ranked_batch_stats(
     int64_t *out_tiles, int64_t *out_groups, int64_t *out_emitted_rows,
     int64_t *out_readback_bytes, int64_t *out_host_syncs);
 
+/*
+ * SG for visitors: makeRecommendations for persons the graph has no vertex for - they arrived after the cut the graph
+ * was built from, or their visits have changed since - without rebuilding it.  Visitor v is given by its out-edges
+ * (target_ids[e], weights[e]), e in [edge_offsets[v], edge_offsets[v + 1]): the person -> place and person -> category
+ * edges build_balanced_edges would give it.  All arrays are host arrays; visitors carry no id.
+ * With G the resident graph (N vertices), every visitor gets what makeRecommendations(V) returns on G + v: G's edge
+ * list followed by (V, t_k, w_k) in the given order, V an id no edge of G has.  vertexCount is N + 1 there, V itself is
+ * never a row, and V's own squared difference enters isConverged.  A visitor's result depends on G and its own edges
+ * only: not on the other visitors of the call, its position or the tile it falls into, bit for bit.
+ * A person who IS a vertex of G and comes back as a visitor keeps that vertex in G, as the ordinary source-only
+ * vertex it is: its old edges still count as edges of G (nothing points at a person, so they reach no result).
+ * Outputs and the capacity protocol are those of locrec_sg_recommend_batch (nv positions; a visitor given twice is
+ * computed twice).  Up to 16 visitors share each sweep of the graph, whatever its size.
+ * Refused before any device work and before anything but *out_bad_visitor is written; *out_bad_visitor (may be NULL)
+ * is the first offending visitor, -1 otherwise:
+ *   LOCREC_E_INVALID_ARG  NULL arguments, negative counts, edge_offsets that do not start at 0 or that turn back;
+ *                         the constructor's two require()s; sharded, fused or persistent handles
+ *                         (locrec_sg_recommend_batch's texts); a target that is a source-only vertex of G (the layout
+ *                         has no row for it); a target repeated inside one visitor; a non-finite weight
+ *   LOCREC_E_NOT_FOUND    a visitor without edges; a target id that is no vertex of G ("No such vertex in the graph:
+ *                         <id>")
+ * Any finite weight, zero included, is served (the reference does not check stochasticity either).  nv == 0 succeeds
+ * with empty outputs.  Afterwards the handle serves single, batched, ranked and pooled requests exactly as before.
+ */
+int32_t locrec_sg_visitors_recommend_batch(
+    locrec_sg_graph *graph, int64_t nv, const int64_t *edge_offsets, const int64_t *target_ids, const double *weights,
+    double alpha, double epsilon, int64_t max_iterations,
+    int64_t *out_offsets, int64_t *out_ids, double *out_probabilities, int64_t *inout_capacity,
+    int64_t *out_iterations, int32_t *out_converged, int64_t *out_bad_visitor);
+/*
+ * locrec_sg_recommend_ranked_batch_excluding for visitors: the same tiles to their end, per visitor the places of ITS
+ * target region, top max_recommendations by probability, emitted and ranked on the device; x never crosses PCIe.  Row i
+ * holds bit for bit what locrec_rank_recommendations_batch_excluding returns for the rows
+ * locrec_sg_visitors_recommend_batch returns for visitor i.  excluded_offsets == NULL: nothing is left out (n_excluded
+ * and excluded_ids are not read).  Refusals are those of locrec_sg_visitors_recommend_batch and of
+ * locrec_sg_recommend_ranked_batch_excluding; the result does not depend on LOCREC_SG_RANKED_ROW_BUDGET.
+ * locrec_sg_recommend_ranked_batch_stats reports on this call too.
+ */
+int32_t locrec_sg_visitors_recommend_ranked_batch(
+    locrec_sg_graph *graph, int64_t nv, const int64_t *edge_offsets, const int64_t *target_ids, const double *weights,
+    double alpha, double epsilon, int64_t max_iterations,
+    int64_t n_places, const int64_t *place_ids, const int64_t *place_region_ids,
+    const int64_t *target_region_ids, int64_t max_recommendations,
+    const int64_t *excluded_offsets, int64_t n_excluded, const int64_t *excluded_ids,
+    int64_t *out_ids, double *out_probabilities, int64_t *out_counts,
+    int64_t *out_row_counts, int64_t *out_iterations, int32_t *out_converged, int64_t *out_bad_visitor);
+/*
+ * What this thread's last locrec_sg_visitors_* call did: tiles, visitors, staged edges, lines of the largest tile's
+ * weight table, set-up launches, finalize launches, convergence polls, waits for the stream.
+ */
+int32_t locrec_sg_visitors_stats(int64_t out[8]);
+/*
+ * What each of n ids is to the graph (host arrays, no device work): 0 = no vertex, 1 = a source-only vertex (no edge
+ * points at it: a visitor may not name it), 2 = a live vertex (a visitor's edge may point at it).
+ */
+int32_t locrec_sg_vertex_kinds(const locrec_sg_graph *graph, int64_t n, const int64_t *vertex_ids, int32_t *out_kinds);
+
 /* Device-resident form (bench.py): enqueue the iteration, read back later. */
 int32_t locrec_sg_iterate_async(
     locrec_sg_graph *graph, int64_t vertex_id,

@@ -103,6 +103,13 @@ SIGNATURES = {
                                                    C.c_int64, _i64p, _i64p, _i64p, C.c_int64, _i64p, C.c_int64, _i64p,
                                                    _i64p, _f64p, _i64p, _i64p, _i64p, _i32p],
     "locrec_sg_recommend_ranked_batch_stats": [_i64p, _i64p, _i64p, _i64p, _i64p],
+    "locrec_sg_visitors_recommend_batch": [C.c_void_p, C.c_int64, _i64p, _i64p, _f64p, C.c_double, C.c_double, C.c_int64,
+                                           _i64p, _i64p, _f64p, _i64p, _i64p, _i32p, _i64p],
+    "locrec_sg_visitors_recommend_ranked_batch": [C.c_void_p, C.c_int64, _i64p, _i64p, _f64p, C.c_double, C.c_double, C.c_int64,
+                                                  C.c_int64, _i64p, _i64p, _i64p, C.c_int64, _i64p, C.c_int64, _i64p,
+                                                  _i64p, _f64p, _i64p, _i64p, _i64p, _i32p, _i64p],
+    "locrec_sg_visitors_stats": [_i64p],
+    "locrec_sg_vertex_kinds": [C.c_void_p, C.c_int64, _i64p, _i32p],
     "locrec_sg_iterate_async": [C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int64],
     "locrec_sg_sweeps_async": [C.c_void_p, C.c_int64, C.c_double, C.c_int64],
     "locrec_sg_fetch": [C.c_void_p, _i64p, _f64p, _i64p, _i64p, _i32p],

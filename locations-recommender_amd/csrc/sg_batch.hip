@@ -19,8 +19,8 @@
 namespace {
 
 // 16 fp64 columns = one 128-byte line per gathered x row.  VGPRs (hipcc -Rpass-analysis=kernel-resource-usage, gfx950):
-// sg_sweep_batch 92 / 60 (uint16 columns, dictionary / fp64 weights), 80 / 130 (int32 columns), sg_finalize_batch 153;
-// no scratch.
+// sg_sweep_batch 92 / 60 (uint16 columns, dictionary / fp64 weights), 80 / 130 (int32 columns), sg_finalize_batch 153,
+// sg_finalize_visitors (sg_visitors.h) 118; no scratch.
 constexpr int kBatchB = 16;
 
 struct SgBatchState {
@@ -165,6 +165,29 @@ __device__ __forceinline__ void batch_add_row(double (&s)[kBatchB], const double
     }
 }
 
+// The tables of a visitors tile (sg_visitors.h): slot[r] is live row r's line of w, or -1 when no visitor of the tile
+// points at r; w[slot][b] is the weight of column b's visitor's edge to r, +0.0 where it has none
+struct SgVisTables {
+    const int32_t *slot;
+    const double *w;
+};
+
+// A visitors tile: sigma'(r) = sigma(r) + x_V(b) * w_{b->r} in every column, the product last (where a fold over the
+// graph's edges followed by the visitor's puts it).  x_V(b) is column b's private row.  One 4-byte load a row otherwise.
+template <bool VIS>
+__device__ __forceinline__ void batch_add_visitors(double (&s)[kBatchB], int row, int T, const SgVisTables &vt,
+                                                   const double *__restrict__ x_in)
+{
+    if constexpr (VIS) {
+        const int32_t sl = vt.slot[row];
+        if (sl >= 0) {
+            const double *w = vt.w + (size_t)sl * kBatchB;
+#pragma unroll
+            for (int b = 0; b < kBatchB; ++b) s[b] = s[b] + x_in[(size_t)(T + 1 + b) * kBatchB + b] * w[b];
+        }
+    }
+}
+
 // x' of one live row in every column (:115-126), its diff^2 into the column's sum; done columns are not written
 __device__ __forceinline__ void batch_combine(const SgBatchReq &rq, uint32_t act, int row, const double (&s)[kBatchB],
                                               const double *__restrict__ x_in, double *__restrict__ x_out, double (&d2)[kBatchB])
@@ -192,11 +215,14 @@ __device__ __forceinline__ void batch_combine(const SgBatchReq &rq, uint32_t act
 }
 
 // Batched sg_finalize_body: the same rows per thread / wave, the same order of every sum, per column.  bx is the block's
-// index among the kParts blocks of its graph.
+// index among the kParts blocks of its graph.  VIS: the tile's columns are visitors (vt, batch_add_visitors); every other
+// instantiation compiles to what it was.
+template <bool VIS = false>
 __device__ __forceinline__ void sg_finalize_batch_body(
     const SgBatchReq &rq, const int bx, int32_t n_short, const int4 *__restrict__ lrows, int32_t nlrows, int32_t n_crows,
     const double *__restrict__ partial, const double *__restrict__ x_in, double *__restrict__ x_out,
-    const double *__restrict__ parts_prev, double *__restrict__ parts_out, SgBatchState *st, int32_t first)
+    const double *__restrict__ parts_prev, double *__restrict__ parts_out, SgBatchState *st, int32_t first,
+    const SgVisTables vt = SgVisTables{nullptr, nullptr})
 {
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -231,6 +257,7 @@ __device__ __forceinline__ void sg_finalize_batch_body(
         for (int b = 0; b < kBatchB; ++b) s[b] = 0.0;
         for (int j = 0; j < r.z; ++j) batch_add_row(s, partial + (size_t)(r.y + j) * kBatchB);
         if (r.w) batch_add_row(s, partial + (size_t)(r.y + r.z) * kBatchB);
+        batch_add_visitors<VIS>(s, r.x, T, vt, x_in);
         batch_combine(rq, act, r.x, s, x_in, x_out, d2);
     }
     // one wave per long row: each lane adds its strided partials in ascending order, a butterfly, then the remainder
@@ -243,7 +270,10 @@ __device__ __forceinline__ void sg_finalize_batch_body(
 #pragma unroll
         for (int b = 0; b < kBatchB; ++b) s[b] = wave_butterfly_sum(s[b]);
         if (r.w) batch_add_row(s, partial + (size_t)(r.y + r.z) * kBatchB);
-        if (lane == 0) batch_combine(rq, act, r.x, s, x_in, x_out, d2);
+        if (lane == 0) {
+            batch_add_visitors<VIS>(s, r.x, T, vt, x_in);
+            batch_combine(rq, act, r.x, s, x_in, x_out, d2);
+        }
     }
     // the short rows: three partial slots each
     for (int l = bx * 256 + (int)threadIdx.x; l < n_short; l += kParts * 256) {
@@ -254,6 +284,7 @@ __device__ __forceinline__ void sg_finalize_batch_body(
         batch_add_row(s, p);
         batch_add_row(s, p + kBatchB);
         batch_add_row(s, p + 2 * kBatchB);
+        batch_add_visitors<VIS>(s, l, T, vt, x_in);
         batch_combine(rq, act, l, s, x_in, x_out, d2);
     }
     if (bx == 0 && threadIdx.x == 0) {
@@ -555,18 +586,38 @@ int32_t sg_batch_verdict(int64_t sweeps, Total &&total, double eps2, int64_t max
     return LOCREC_OK;
 }
 
-// Every tile of the distinct targets: its set-up, its rounds and polls, then consume(ctx, t0, nb) - after the tile's last
+// What the columns of a batch's tiles are: distinct vertices of the graph (here), or visitors (SgVisitorTiles, sg_visitors.h)
+struct SgPersonTiles {
+    const std::vector<int32_t> &uniq;
+    size_t count() const { return uniq.size(); }
+    int tile_max(const locrec_sg_graph *g) const { return sg_batch_tile_max(g); }
+    void rows(const locrec_sg_graph *g, size_t t0, int nb, double alpha, double eps2, std::vector<SlotRange> &pointed,
+              SgBatchBegin &b, SgBatchReq &rq) const
+    {
+        sg_batch_tile_rows(g, uniq, t0, nb, alpha, eps2, pointed, b, rq);
+    }
+    void set_up(const locrec_sg_graph *, hipStream_t, size_t) const {}  // (launches behind the tile's sg_begin_batch: none)
+    void polled() const {}                                              // (a convergence word was read: SgBatchCtx counts it)
+    void finalize(const locrec_sg_graph *g, hipStream_t s, const SgBatchReq &rq, const double *x_in, double *x_out,
+                  const double *parts_prev, double *parts_out, SgBatchState *bstate, int32_t first) const
+    {
+        hipLaunchKernelGGL(sg_finalize_batch, dim3(kParts), dim3(256), 0, s, rq, g->n_short, g->lrows.p, g->nlrows, g->n_crows,
+                           g->XL.p, x_in, x_out, parts_prev, parts_out, bstate, first);
+    }
+};
+
+// Every tile of the batch's columns: its set-up, its rounds and polls, then consume(ctx, t0, nb) - after the tile's last
 // round and before the next tile's set-up overwrites x.  At the end the last tile's slots go back to D.
-template <class Consume>
-int32_t sg_batch_tiles(locrec_sg_graph *g, const std::vector<int32_t> &uniq, double alpha, double epsilon,
-                       int64_t max_iterations, SgBatchCtx &ctx, Consume &&consume)
+template <class Tiles, class Consume>
+int32_t sg_batch_tiles_of(locrec_sg_graph *g, Tiles &&tiles, double alpha, double epsilon, int64_t max_iterations,
+                          SgBatchCtx &ctx, Consume &&consume)
 {
     if (max_iterations > INT32_MAX) max_iterations = INT32_MAX;
     LOCREC_HIP_TRY(hipSetDevice(g->device));
     hipStream_t s = g->stream;
     const int32_t T = g->nlive;
     const int64_t xstride = sg_batch_xstride(g);
-    const int tile_max = sg_batch_tile_max(g);
+    const int tile_max = tiles.tile_max(g);
     LOCREC_TRY(sg_batch_buffers(g, s));
     SgBatchState *bstate = reinterpret_cast<SgBatchState *>(g->fused_conv.p);
     const double eps2 = epsilon * epsilon;  // :40
@@ -577,7 +628,7 @@ int32_t sg_batch_tiles(locrec_sg_graph *g, const std::vector<int32_t> &uniq, dou
     const v2d *wv2 = reinterpret_cast<const v2d *>(g->w2.p);
     const v4h *wi = reinterpret_cast<const v4h *>(g->widx.p);
     const size_t lds = g->ndict > 0 ? (size_t)g->ndict * sizeof(double) : 0;
-    const size_t nu = uniq.size();
+    const size_t nu = tiles.count();
     ctx.s = s;
     ctx.T = T;
     ctx.xstride = xstride;
@@ -591,8 +642,9 @@ int32_t sg_batch_tiles(locrec_sg_graph *g, const std::vector<int32_t> &uniq, dou
     auto run_tile = [&](size_t t0, int nb) -> int32_t {
         SgBatchBegin b;
         SgBatchReq rq;
-        sg_batch_tile_rows(g, uniq, t0, nb, alpha, eps2, pointed, b, rq);
+        tiles.rows(g, t0, nb, alpha, eps2, pointed, b, rq);
         hipLaunchKernelGGL(sg_begin_batch, dim3(kBeginBlocks), dim3(256), 0, s, b);
+        tiles.set_up(g, s, t0);
         // step() (:92-106) for every column; the host looks at "all columns done" on the single request's schedule
         auto launch_round = [&](int64_t i) {
             const int par = (int)(i & 1);
@@ -609,9 +661,8 @@ int32_t sg_batch_tiles(locrec_sg_graph *g, const std::vector<int32_t> &uniq, dou
                 }
 #undef LOCREC_SWEEP_BATCH
             }
-            hipLaunchKernelGGL(sg_finalize_batch, dim3(kParts), dim3(256), 0, s, rq, g->n_short, g->lrows.p, g->nlrows,
-                               g->n_crows, g->XL.p, x_in, x_out, g->D2W.p + (size_t)(par ^ 1) * kParts * kBatchB,
-                               g->D2W.p + (size_t)par * kParts * kBatchB, bstate, i == 0 ? 1 : 0);
+            tiles.finalize(g, s, rq, x_in, x_out, g->D2W.p + (size_t)(par ^ 1) * kParts * kBatchB,
+                           g->D2W.p + (size_t)par * kParts * kBatchB, bstate, i == 0 ? 1 : 0);
         };
         int64_t next_check = 4;
         for (int64_t i = 0; i < max_iterations;) {
@@ -629,6 +680,7 @@ int32_t sg_batch_tiles(locrec_sg_graph *g, const std::vector<int32_t> &uniq, dou
                     LOCREC_HIP_TRY(hipStreamSynchronize(s));
                 }
                 ++ctx.polls;
+                tiles.polled();
                 if (all_done) break;
                 next_check += next_check < 8 ? 2 : (next_check < 16 ? 4 : kCheckEvery);
             }
@@ -645,6 +697,14 @@ int32_t sg_batch_tiles(locrec_sg_graph *g, const std::vector<int32_t> &uniq, dou
         LOCREC_HIP_TRY(hipGetLastError());
     }
     return status;
+}
+
+// ... of the distinct targets uniq
+template <class Consume>
+int32_t sg_batch_tiles(locrec_sg_graph *g, const std::vector<int32_t> &uniq, double alpha, double epsilon,
+                       int64_t max_iterations, SgBatchCtx &ctx, Consume &&consume)
+{
+    return sg_batch_tiles_of(g, SgPersonTiles{uniq}, alpha, epsilon, max_iterations, ctx, consume);
 }
 
 // ---- the host's side of a tile's read-back: the packed image (the state at 0, the block sums at kBatchPackHead, then
@@ -790,6 +850,34 @@ int32_t sg_batch_output(int64_t n_targets, At &&at, int64_t *out_offsets, int64_
     return LOCREC_OK;
 }
 
+// A tile's read-back for the unranked entries: one pack launch into pinned memory, then the rows of every column (:84-88)
+int32_t sg_batch_read_back(locrec_sg_graph *g, SgBatchCtx &ctx, const std::vector<int32_t> &uniq, size_t t0, int nb, SgBatchRows &res)
+{
+    hipStream_t s = ctx.s;
+    const int32_t T = ctx.T;
+    const size_t pack_bytes = sg_batch_pack_bytes(T);
+    unsigned char *stg = g->no_pack ? nullptr : g->stage(pack_bytes);
+    void *stg_dev = nullptr;
+    std::vector<unsigned char> own;
+    const unsigned char *host = nullptr;
+    if (stg && hipHostGetDevicePointer(&stg_dev, stg, 0) == hipSuccess) {
+        hipLaunchKernelGGL(sg_pack_batch, dim3(sg_batch_pack_blocks(T)), dim3(256), 0, s, ctx.bstate, g->D2W.p, g->PA4.p,
+                           ctx.xstride, T + 1, static_cast<unsigned char *>(stg_dev));
+        LOCREC_HIP_TRY(hipStreamSynchronize(s));
+        host = stg;
+    } else {
+        (void)hipGetLastError();
+        own.resize(pack_bytes);
+        std::vector<double> both;
+        LOCREC_TRY(sg_batch_copy_enqueue(g, s, own.data(), both));
+        LOCREC_HIP_TRY(hipStreamSynchronize(s));
+        sg_batch_copy_assemble(T, own.data(), both);
+        host = own.data();
+    }
+    LOCREC_HIP_TRY(hipGetLastError());
+    return sg_batch_host_rows(g, host, uniq, t0, nb, ctx.eps2, ctx.max_iterations, res);
+}
+
 }  // namespace
 
 extern "C" int32_t locrec_sg_recommend_batch(locrec_sg_graph *g, int64_t n_targets, const int64_t *vertex_ids, double alpha,
@@ -809,32 +897,7 @@ extern "C" int32_t locrec_sg_recommend_batch(locrec_sg_graph *g, int64_t n_targe
     }
     SgBatchRows res;
     res.resize(uniq.size());
-    // a tile's read-back: one pack launch into pinned memory, then the rows of every column (:84-88)
-    auto read_back = [&](SgBatchCtx &ctx, size_t t0, int nb) -> int32_t {
-        hipStream_t s = ctx.s;
-        const int32_t T = ctx.T;
-        const size_t pack_bytes = sg_batch_pack_bytes(T);
-        unsigned char *stg = g->no_pack ? nullptr : g->stage(pack_bytes);
-        void *stg_dev = nullptr;
-        std::vector<unsigned char> own;
-        const unsigned char *host = nullptr;
-        if (stg && hipHostGetDevicePointer(&stg_dev, stg, 0) == hipSuccess) {
-            hipLaunchKernelGGL(sg_pack_batch, dim3(sg_batch_pack_blocks(T)), dim3(256), 0, s, ctx.bstate, g->D2W.p, g->PA4.p,
-                               ctx.xstride, T + 1, static_cast<unsigned char *>(stg_dev));
-            LOCREC_HIP_TRY(hipStreamSynchronize(s));
-            host = stg;
-        } else {
-            (void)hipGetLastError();
-            own.resize(pack_bytes);
-            std::vector<double> both;
-            LOCREC_TRY(sg_batch_copy_enqueue(g, s, own.data(), both));
-            LOCREC_HIP_TRY(hipStreamSynchronize(s));
-            sg_batch_copy_assemble(T, own.data(), both);
-            host = own.data();
-        }
-        LOCREC_HIP_TRY(hipGetLastError());
-        return sg_batch_host_rows(g, host, uniq, t0, nb, ctx.eps2, ctx.max_iterations, res);
-    };
+    auto read_back = [&](SgBatchCtx &ctx, size_t t0, int nb) -> int32_t { return sg_batch_read_back(g, ctx, uniq, t0, nb, res); };
     SgBatchCtx ctx;
     LOCREC_TRY(sg_batch_tiles(g, uniq, alpha, epsilon, max_iterations, ctx, read_back));
     return sg_batch_output(n_targets, [&](int64_t i) { return SgBatchRowRef{&res, (size_t)uniq_of[(size_t)i]}; }, out_offsets,
@@ -844,3 +907,4 @@ extern "C" int32_t locrec_sg_recommend_batch(locrec_sg_graph *g, int64_t n_targe
 #include "sg_ranked.h"
 #include "sg_pool.h"
 #include "sg_pool_ranked.h"
+#include "sg_visitors.h"

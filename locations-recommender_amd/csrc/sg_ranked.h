@@ -440,6 +440,26 @@ struct SgRkCall {
     }
 };
 
+template <class Tiles>
+int32_t sg_ranked_batch_columns(locrec_sg_graph *g, SgRankedStats &stats, int64_t n, const std::vector<int32_t> &uniq,
+                                const std::vector<int32_t> &uniq_of, Tiles &&tiles, double alpha, double epsilon,
+                                int64_t max_iterations, int64_t N, int64_t n_places, const int64_t *place_ids,
+                                const int64_t *place_region_ids, const int64_t *target_region_ids, bool with_lists,
+                                const int64_t *excluded_offsets, int64_t n_excluded, const int64_t *excluded_ids, int64_t *out_ids,
+                                double *out_probabilities, int64_t *out_counts, int64_t *out_row_counts, int64_t *out_iterations,
+                                int32_t *out_converged);
+
+// The exclusion lists' checks (host arrays), before any device work
+int32_t sg_rk_check_lists(int64_t n_targets, const int64_t *excluded_offsets, int64_t n_excluded, const int64_t *excluded_ids)
+{
+    if (n_excluded < 0 || n_excluded >= ((int64_t)1 << 31)) return fail(LOCREC_E_INVALID_ARG, "excluded id count out of range [0, 2^31)");
+    if (n_targets > 0 && (!excluded_offsets || (n_excluded > 0 && !excluded_ids))) return fail(LOCREC_E_INVALID_ARG, "null array");
+    bool ok = n_targets == 0 || (excluded_offsets[0] >= 0 && excluded_offsets[n_targets] <= n_excluded);
+    for (int64_t i = 0; ok && i < n_targets; ++i) ok = excluded_offsets[i] <= excluded_offsets[i + 1];
+    if (!ok) return fail(LOCREC_E_INVALID_ARG, "excluded_offsets must be non-decreasing inside [0, n_excluded]");
+    return LOCREC_OK;
+}
+
 // both entries of the ranked batch; with_lists: position i leaves out excluded_ids[excluded_offsets[i] ..
 // excluded_offsets[i + 1]) (host arrays, refused before any device work when they are not offsets into n_excluded ids)
 int32_t sg_recommend_ranked_batch(locrec_sg_graph *g, int64_t n_targets, const int64_t *vertex_ids, double alpha, double epsilon,
@@ -456,22 +476,32 @@ int32_t sg_recommend_ranked_batch(locrec_sg_graph *g, int64_t n_targets, const i
     int64_t N = 0;
     LOCREC_TRY(sg_rk_check_args(n_targets, n_places, place_ids, place_region_ids, target_region_ids, max_recommendations, out_ids,
                                 out_probabilities, out_counts, N));
-    if (with_lists) {
-        if (n_excluded < 0 || n_excluded >= ((int64_t)1 << 31)) return fail(LOCREC_E_INVALID_ARG, "excluded id count out of range [0, 2^31)");
-        if (n_targets > 0 && (!excluded_offsets || (n_excluded > 0 && !excluded_ids))) return fail(LOCREC_E_INVALID_ARG, "null array");
-        bool ok = n_targets == 0 || (excluded_offsets[0] >= 0 && excluded_offsets[n_targets] <= n_excluded);
-        for (int64_t i = 0; ok && i < n_targets; ++i) ok = excluded_offsets[i] <= excluded_offsets[i + 1];
-        if (!ok) return fail(LOCREC_E_INVALID_ARG, "excluded_offsets must be non-decreasing inside [0, n_excluded]");
-    }
+    if (with_lists) LOCREC_TRY(sg_rk_check_lists(n_targets, excluded_offsets, n_excluded, excluded_ids));
     std::vector<int32_t> uniq, uniq_of;
     LOCREC_TRY(sg_batch_targets(g, n_targets, vertex_ids, epsilon, max_iterations, uniq, uniq_of));
     if (n_targets == 0) return LOCREC_OK;
+    return sg_ranked_batch_columns(g, stats, n_targets, uniq, uniq_of, SgPersonTiles{uniq}, alpha, epsilon, max_iterations, N, n_places,
+                                   place_ids, place_region_ids, target_region_ids, with_lists, excluded_offsets, n_excluded,
+                                   excluded_ids, out_ids, out_probabilities, out_counts, out_row_counts, out_iterations,
+                                   out_converged);
+}
+
+// The ranked batch behind its checks, for n >= 1 positions over the columns `tiles` runs: position i asks column uniq_of[i],
+// whose target vertex is uniq[...] (-1: a visitor, which is no vertex and so never a row of its own result)
+template <class Tiles>
+int32_t sg_ranked_batch_columns(locrec_sg_graph *g, SgRankedStats &stats, int64_t n, const std::vector<int32_t> &uniq,
+                                const std::vector<int32_t> &uniq_of, Tiles &&tiles, double alpha, double epsilon,
+                                int64_t max_iterations, int64_t N, int64_t n_places, const int64_t *place_ids,
+                                const int64_t *place_region_ids, const int64_t *target_region_ids, bool with_lists,
+                                const int64_t *excluded_offsets, int64_t n_excluded, const int64_t *excluded_ids, int64_t *out_ids,
+                                double *out_probabilities, int64_t *out_counts, int64_t *out_row_counts, int64_t *out_iterations,
+                                int32_t *out_converged)
+{
     LOCREC_HIP_TRY(hipSetDevice(g->device));
     hipStream_t s = g->stream;
-    const int64_t n = n_targets;
     const size_t nu = uniq.size();
     const int32_t T = g->nlive;
-    const int tile_max = sg_batch_tile_max(g);
+    const int tile_max = tiles.tile_max(g);
 
     // ---- the emit rows
     SgRkRows er;
@@ -479,7 +509,7 @@ int32_t sg_recommend_ranked_batch(locrec_sg_graph *g, int64_t n_targets, const i
     const int64_t m = er.m;
     const int64_t *sid = er.sid;
     const std::vector<int32_t> &srow = er.srow;
-    auto emit_row_of = [&](int32_t tv) -> int32_t { return sg_rk_row_of(g, er, tv); };
+    auto emit_row_of = [&](int32_t tv) -> int32_t { return tv < 0 ? -1 : sg_rk_row_of(g, er, tv); };
     const int64_t words = std::max<int64_t>(1, (m + 63) / 64);
 
     // ---- the requests in emit order (by tile, then input position: a pool's with one member), the distinct target regions
@@ -598,7 +628,7 @@ int32_t sg_recommend_ranked_batch(locrec_sg_graph *g, int64_t n_targets, const i
         return sg_rk_verdicts(pinned ? stg : own, nb, ctx.eps2, ctx.max_iterations, &rc.res_it[t0], &rc.res_conv[t0]);
     };
     SgBatchCtx ctx;
-    const int32_t status = sg_batch_tiles(g, uniq, alpha, epsilon, max_iterations, ctx, after_tile);
+    const int32_t status = sg_batch_tiles_of(g, tiles, alpha, epsilon, max_iterations, ctx, after_tile);
     return rc.finish(status, ctx.polls, order, member_of, uniq_of, out_ids, out_probabilities, out_counts, out_row_counts,
                      out_iterations, out_converged);
 }

@@ -288,6 +288,42 @@ def sg_recommend_places_batch(data_dir, region_ids, requests, epsilon, max_itera
         g.close()
 
 
+def sg_visitor_requests(data_dir, region_ids, visits, target_region_ids, epsilon, max_iterations, max_recommendations=10,
+                        new_places=False, beta_person_place=1.0, beta_person_category=1.0, alpha=0.15):
+    """knn_visitor_requests' SG sibling: requests of persons the region set's graph has no vertex for - they arrived
+    after the cut of the visit table it was built from, or their visits have changed since.  visits: mapping with
+    visitor_id, place_id, category_id (one row a place visit); target_region_ids: a mapping visitor id -> region, one
+    region for all, or one region per visitor in ascending visitor id.  The graph comes from the handle cache under
+    sg_make_recommendations' key, the edges from prep.visitor_edges (the betas are those the graph was built with; visits
+    to places and categories the graph has no live vertex for are dropped), the answer from ONE ranked visitors call.
+    -> a list of (visitor_id, place_ids, probabilities), ascending visitor id.
+    new_places=True: a visitor's own targets are left out."""
+    from . import _cache, prep
+    from .stochastic import SgGraph
+    _cache.require_gpu_backend("sg_visitor_requests")
+    place_ids, place_regions = load_places(data_dir)
+    key = _cache.files_key([generate_file_name(region_ids, data_dir, "stochastic_graph")])
+    g = SgGraph.through_cache(key, lambda: sg_graph_from_parquet(data_dir, region_ids))
+    try:
+        with g.lock:
+            ids, offsets, edge_targets, weights, _ = prep.visitor_edges(
+                visits["visitor_id"], visits["place_id"], visits["category_id"], beta_person_place, beta_person_category, graph=g)
+            if hasattr(target_region_ids, "keys"):
+                targets = np.asarray([target_region_ids[int(v)] for v in ids], np.int64)
+            elif np.ndim(target_region_ids) == 0:
+                targets = np.full(len(ids), int(target_region_ids), np.int64)
+            else:
+                targets = np.asarray(target_region_ids, np.int64)
+            if len(targets) != len(ids):
+                raise L.IllegalArgumentException("requirement failed: one target region per visitor is required")
+            oi, op, cnt, _, _ = g.visitors_recommend_ranked_batch(
+                offsets, edge_targets, weights, alpha, epsilon, max_iterations, place_ids, place_regions, targets,
+                max_recommendations, exclude=(offsets, edge_targets) if new_places else None)
+    finally:
+        g.close()  # drops the reference only
+    return [(int(v), oi[i, :cnt[i]].copy(), op[i, :cnt[i]].copy()) for i, v in enumerate(ids)]
+
+
 def _sg_visited_lists(data_dir, region_ids, vertex_ids):
     """The exclusion lists of new_places for vertices of one region set: out_neighbours over its edge Parquet."""
     from .stochastic import out_neighbours

@@ -371,6 +371,34 @@ def generate_stochastic_graph(place_visits, beta_person_place, beta_person_categ
     return build_with_balanced_weights(betas, families)
 
 
+def visitor_edges(visitor_ids, place_ids, category_ids, beta_person_place, beta_person_category, graph=None):
+    """The out-edges of visitors - persons a graph has no vertex for (SgGraph.visitors_*) - from their place visits
+    (visitor_id, place_id, category_id), one row a visit: the person -> place and person -> category families of
+    generate_stochastic_graph (calc_count_edges with the builder's top-N constants), balanced with their betas by
+    build_with_balanced_weights - the values a person of the graph gets - and merged per visitor, places first.
+    graph: an SgGraph; a visit to a place the graph has no live vertex for is dropped before the places are counted, a
+    visit to such a category before the categories are (an edge may only point at a live vertex).
+    -> (visitor ids ascending, edge_offsets[nv + 1], target_ids, balanced_weights, dropped[nv, 2]): host arrays; dropped
+    counts the visit rows left out of the place and of the category family.  A visitor all of whose visits are dropped
+    keeps its position, without edges (a visitors call refuses it)."""
+    host = lambda a: np.asarray(a.cpu().numpy() if _is_tensor(a) else a, np.int64)
+    v, p, c = host(visitor_ids), host(place_ids), host(category_ids)
+    if not (len(v) == len(p) == len(c)):
+        raise L.IllegalArgumentException("visit columns of different lengths")
+    ids = np.unique(v)
+    dropped = np.zeros((len(ids), 2), np.int64)
+    families = []
+    for k, (targets, top_n) in enumerate(((p, LIKED_PLACES_TOP_N), (c, LIKED_CATEGORIES_TOP_N))):
+        keep = np.ones(len(v), bool) if graph is None else graph.vertex_kinds(targets) == 2
+        dropped[:, k] = np.bincount(np.searchsorted(ids, v[~keep]), minlength=len(ids))
+        families.append(calc_count_edges(v[keep], targets[keep], top_n))
+    s, t, w = build_with_balanced_weights([float(beta_person_place), float(beta_person_category)], families)
+    order = np.argsort(s, kind="stable")  # per visitor: its places by id, then its categories by id
+    offsets = np.zeros(len(ids) + 1, np.int64)
+    np.cumsum(np.bincount(np.searchsorted(ids, s), minlength=len(ids)), out=offsets[1:])
+    return ids, offsets, np.ascontiguousarray(t[order]), np.ascontiguousarray(w[order]), dropped
+
+
 def sg_graph_from_visits(place_visits, beta_person_place, beta_person_category):
     """Place visits -> the four edge families -> balanced edge list -> SgGraph: the SG counterpart of
     knn_index_from_visits.  With CUDA tensors the edge list stays in device memory and the graph's layout is built

@@ -206,6 +206,95 @@ class SgGraph:
         L.check(L.lib().locrec_sg_recommend_ranked_batch_stats(*[C.byref(i) for i in x]))
         return dict(zip(cls.RANKED_BATCH_STATS, (i.value for i in x)))
 
+    # ---- visitors: persons this graph has no vertex for (include/locrec.h, "SG for visitors") ----
+    VISITORS_STATS = ("tiles", "visitors", "staged_edges", "table_slots", "set_up_launches", "finalize_launches", "polls",
+                      "waits")
+
+    @staticmethod
+    def _visitor_edges(edge_offsets, target_ids, weights):
+        off, t, w = L.as_i64(edge_offsets), L.as_i64(target_ids), L.as_f64(weights)
+        if len(off) < 1 or len(t) != len(w) or (len(off) > 1 and off[-1] > len(t)):
+            raise L.IllegalArgumentException("visitor edges: offsets of nv + 1 entries into target ids and weights of one length")
+        return off, t, w
+
+    def visitors_recommend_batch(self, edge_offsets, target_ids, weights, alpha, epsilon, max_iterations):
+        """makeRecommendations for visitors (locrec_sg_visitors_recommend_batch): visitor v is the out-edges
+        (target_ids[e], weights[e]), e in edge_offsets[v]:edge_offsets[v + 1] - prep.visitor_edges builds them - and gets
+        what recommend(V) returns on this graph's edge list followed by those edges under a new id V.
+        -> (offsets[nv + 1], ids, probabilities, iterations[nv], converged[nv]).  A refused call raises with `bad_visitor`
+        set on the exception: the first offending visitor, or -1."""
+        off, t, w = self._visitor_edges(edge_offsets, target_ids, weights)
+        nv = len(off) - 1
+        out_off = np.zeros(nv + 1, np.int64)
+        its, conv = np.zeros(nv, np.int64), np.zeros(nv, np.int32)
+        per = self.info()["vertices"] if int(max_iterations) == 0 else self.live_count()
+        room = min(nv * max(1, per), 1 << 24)
+        cap = C.c_int64(room)
+        ids, probs = np.empty(room, np.int64), np.empty(room, np.float64)
+        bad = C.c_int64(-1)
+        for _ in range(2):  # a call whose room is too small sizes the result, the second fills it
+            try:
+                L.check(L.lib().locrec_sg_visitors_recommend_batch(
+                    self._h, nv, L.ptr(off, C.c_int64), L.ptr(t, C.c_int64), L.ptr(w, C.c_double), float(alpha), float(epsilon),
+                    int(max_iterations), L.ptr(out_off, C.c_int64), L.ptr(ids, C.c_int64), L.ptr(probs, C.c_double),
+                    C.byref(cap), L.ptr(its, C.c_int64), L.ptr(conv, C.c_int32), C.byref(bad)))
+            except L.IllegalArgumentException as e:
+                e.bad_visitor = bad.value
+                raise
+            if cap.value <= len(ids):
+                break
+            ids, probs = np.empty(cap.value, np.int64), np.empty(cap.value, np.float64)
+            cap = C.c_int64(len(ids))
+        return out_off, ids[:out_off[-1]], probs[:out_off[-1]], its, conv.astype(bool)
+
+    def visitors_recommend_ranked_batch(self, edge_offsets, target_ids, weights, alpha, epsilon, max_iterations, place_ids,
+                                        place_region_ids, target_region_ids, max_recommendations, exclude=None):
+        """The visitors call to its end (locrec_sg_visitors_recommend_ranked_batch): per visitor the places of its target
+        region, top max_recommendations by probability, emitted and ranked on the device.
+        exclude=(offsets[nv + 1], ids): visitor i leaves out ids[offsets[i]:offsets[i + 1]].
+        -> (ids[nv, W], probabilities[nv, W], counts[nv], iterations[nv], converged[nv]) as recommend_ranked_batch returns
+        them.  A refused call raises with `bad_visitor` set, as visitors_recommend_batch does."""
+        off, t, w = self._visitor_edges(edge_offsets, target_ids, weights)
+        nv = len(off) - 1
+        pl, reg, tgt = L.as_i64(place_ids), L.as_i64(place_region_ids), L.as_i64(target_region_ids)
+        if len(reg) != len(pl) or len(tgt) != nv:
+            raise L.IllegalArgumentException("one region per place and one target region per visitor are required")
+        xoff = xids = None
+        if exclude is not None:
+            xoff, xids = L.as_i64(exclude[0]), L.as_i64(exclude[1])
+            if len(xoff) != nv + 1:
+                raise L.IllegalArgumentException("one exclusion list per visitor is required: offsets of nv + 1 entries")
+        stride = max(0, min(int(max_recommendations), self.info()["vertices"]))
+        oi, op = np.full((nv, stride), -1, np.int64), np.zeros((nv, stride), np.float64)
+        cnt, rows, its, conv = (np.zeros(nv, np.int64), np.zeros(nv, np.int64), np.zeros(nv, np.int64), np.zeros(nv, np.int32))
+        bad = C.c_int64(-1)
+        try:
+            L.check(L.lib().locrec_sg_visitors_recommend_ranked_batch(
+                self._h, nv, L.ptr(off, C.c_int64), L.ptr(t, C.c_int64), L.ptr(w, C.c_double), float(alpha), float(epsilon),
+                int(max_iterations), len(pl), L.ptr(pl, C.c_int64), L.ptr(reg, C.c_int64), L.ptr(tgt, C.c_int64), stride,
+                L.ptr(xoff, C.c_int64), 0 if xids is None else len(xids), L.ptr(xids, C.c_int64), L.ptr(oi, C.c_int64),
+                L.ptr(op, C.c_double), L.ptr(cnt, C.c_int64), L.ptr(rows, C.c_int64), L.ptr(its, C.c_int64),
+                L.ptr(conv, C.c_int32), C.byref(bad)))
+        except L.IllegalArgumentException as e:
+            e.bad_visitor = bad.value
+            raise
+        width = max(0, min(stride, int(rows.max()) if nv else 0))
+        return (np.ascontiguousarray(oi[:, :width]), np.ascontiguousarray(op[:, :width]), cnt, its, conv.astype(bool))
+
+    @classmethod
+    def visitors_stats(cls):
+        """What this thread's last visitors call did (locrec_sg_visitors_stats)."""
+        x = (C.c_int64 * 8)()
+        L.check(L.lib().locrec_sg_visitors_stats(x))
+        return dict(zip(cls.VISITORS_STATS, (int(i) for i in x)))
+
+    def vertex_kinds(self, vertex_ids):
+        """Per id: 0 = no vertex of this graph, 1 = a source-only vertex, 2 = a live vertex (locrec_sg_vertex_kinds)."""
+        v = L.as_i64(vertex_ids)
+        out = np.zeros(len(v), np.int32)
+        L.check(L.lib().locrec_sg_vertex_kinds(self._h, len(v), L.ptr(v, C.c_int64), L.ptr(out, C.c_int32)))
+        return out
+
     def iterate_async(self, vertex_id, alpha, epsilon, max_iterations):
         L.check(L.lib().locrec_sg_iterate_async(self._h, int(vertex_id), float(alpha), float(epsilon),
                                                 int(max_iterations)))
@@ -448,6 +537,22 @@ class StochasticRecommender:
                 print(f"Converged in {iterations} iterations")
             else:
                 print(f"Number of iterations {iterations} reached the maximum {self.maxIterations}")
+        return pd.DataFrame({"id": ids, "probability": probs})
+
+    def makeRecommendationsForVisitor(self, edges):
+        """Additive: makeRecommendations for a person the graph has no vertex for.  edges: frame with columns target_id,
+        balanced_weight - the person's out-edges (prep.visitor_edges).  -> (id, probability): what makeRecommendations
+        returns for a new vertex on stochasticEdges followed by those edges."""
+        import pandas as pd
+        t, w = np.asarray(edges["target_id"]), np.asarray(edges["balanced_weight"])
+        with self._graph.lock:
+            off, ids, probs, iterations, converged = self._graph.visitors_recommend_batch(
+                [0, len(t)], t, w, ALPHA, self.epsilon, self.maxIterations)
+        if not self.quiet:  # the two println()s of step(), StochasticRecommender.scala:94,100
+            if converged[0]:
+                print(f"Converged in {iterations[0]} iterations")
+            else:
+                print(f"Number of iterations {iterations[0]} reached the maximum {self.maxIterations}")
         return pd.DataFrame({"id": ids, "probability": probs})
 
     def makeRecommendationsBatch(self, vertexIds):
