@@ -113,6 +113,81 @@ int main()
             if (check_stage(nv, off, row, w)) return 1;
         }
     }
+    // one tile of 255, 256 and 257 edges (a stride of the set-up kernel's loops, one short and one over): 16 visitors
+    // with 16 rows each out of T = 600, visitor 9 with 15, 16 or 17
+    for (int edges : {255, 256, 257}) {
+        std::vector<int64_t> off = {0};
+        std::vector<int32_t> row;
+        std::vector<double> w;
+        for (int v = 0; v < 16; ++v) {
+            const int k = v == 9 ? edges - 240 : 16;
+            for (int j = 0; j < k; ++j) {
+                row.push_back((int32_t)((v * 37 + j * 41) % 600));  // (41 and 600 are coprime: no row twice in a visitor)
+                w.push_back(1.0 / k);
+            }
+            off.push_back((int64_t)row.size());
+            CHECK(sg_visitors_first_repeat(row.data() + off[(size_t)v], k) == -1);
+        }
+        SgVisitorsStage st;
+        sg_visitors_stage(16, off.data(), row.data(), w.data(), st);
+        CHECK(st.tiles() == 1 && st.edges() == edges && st.tile_ptr[1] == edges && st.max_slots <= edges);
+        if (check_stage(16, off, row, w)) return 1;
+    }
+    // one visitor that names every row of T = 600, in any order: as many lines as rows and as edges, slot == row
+    {
+        std::vector<int64_t> off = {0, 600};
+        std::vector<int32_t> row;
+        std::vector<double> w;
+        for (int j = 0; j < 600; ++j) {
+            row.push_back((int32_t)((j * 7 + 3) % 600));
+            w.push_back(1.0 / 600);
+        }
+        SgVisitorsStage st;
+        sg_visitors_stage(1, off.data(), row.data(), w.data(), st);
+        CHECK(st.max_slots == 600 && st.edges() == 600 && st.weight_table() == 600 * 16);
+        for (int j = 0; j < 600; ++j) CHECK(st.row[(size_t)j] == j && st.slot[(size_t)j] == j && st.col[(size_t)j] == 0);
+        if (check_stage(1, off, row, w)) return 1;
+    }
+    // three tiles whose tables follow each other: 16 visitors at all 40 rows of A = {0, 14, ..}; 16 visitors at B = {7, 21,
+    // ..} only, each row of B named by one of them; three visitors with three rows of A, one of B and one of neither
+    {
+        std::vector<int64_t> off = {0};
+        std::vector<int32_t> row;
+        std::vector<double> w;
+        auto add = [&](std::initializer_list<int32_t> rows, double x) {
+            for (int32_t r : rows) {
+                row.push_back(r);
+                w.push_back(x);
+            }
+        };
+        for (int v = 0; v < 16; ++v) {
+            for (int k = 0; k < 40; ++k) add({(int32_t)(14 * ((k + v) % 40))}, 0.025 + v);
+            off.push_back((int64_t)row.size());
+        }
+        for (int v = 0; v < 16; ++v) {
+            for (int k = v; k < 40; k += 16) add({(int32_t)(7 + 14 * k)}, 0.5);
+            off.push_back((int64_t)row.size());
+        }
+        const int32_t neither[3] = {13, 27, 41};
+        for (int v = 0; v < 3; ++v) {
+            add({(int32_t)(14 * (5 * v + 20)), (int32_t)(14 * (5 * v + 1)), (int32_t)(14 * (39 - v)), (int32_t)(7 + 14 * (30 + v)), neither[v]}, 0.2);
+            off.push_back((int64_t)row.size());
+        }
+        SgVisitorsStage st;
+        sg_visitors_stage(35, off.data(), row.data(), w.data(), st);
+        CHECK((st.tile_ptr == std::vector<int64_t>{0, 640, 680, 695}) && (st.tile_slots == std::vector<int32_t>{40, 40, 15}));
+        CHECK(st.max_slots == 40 && st.weight_table() == 640);
+        for (int i = 0; i < 640; ++i)  // tile 0: every (slot, column) pair once, the columns of a line ascending
+            CHECK(st.row[(size_t)i] == 14 * (i / 16) && st.slot[(size_t)i] == i / 16 && st.col[(size_t)i] == i % 16);
+        for (int k = 0; k < 40; ++k)  // tile 1: as many lines, one column each
+            CHECK(st.row[(size_t)(640 + k)] == 7 + 14 * k && st.slot[(size_t)(640 + k)] == k && st.col[(size_t)(640 + k)] == k % 16);
+        // tile 2: 15 lines over rows of A, B and neither, in ascending order of the rows
+        CHECK((std::vector<int32_t>(st.row.begin() + 680, st.row.end()) ==
+               std::vector<int32_t>{13, 14, 27, 41, 84, 154, 280, 350, 420, 427, 441, 455, 518, 532, 546}));
+        CHECK((std::vector<int32_t>(st.col.begin() + 680, st.col.end()) == std::vector<int32_t>{0, 0, 1, 2, 1, 2, 0, 1, 2, 0, 1, 2, 2, 1, 0}));
+        for (int i = 0; i < 15; ++i) CHECK(st.slot[(size_t)(680 + i)] == i);
+        if (check_stage(35, off, row, w)) return 1;
+    }
     printf("%d cases pass\n", cases);
     return 0;
 }
