@@ -418,6 +418,53 @@ int32_t locrec_knn_visitors_recommend_ranked_batch(
 int32_t locrec_knn_visitors_stats(int64_t out[8]);
 
 /*
+ * One mixed batch of visitors over a pool of indexes: visitors fan out over region sets exactly as persons do.  Visitor
+ * i asks member index_of_visitor[i] (a host array; a position of locrec_knn_pool_create's list); the six vector arrays
+ * are ONE CSR over all nv visitors in call order, in `mem` (LOCREC_MEM_HOST, or LOCREC_MEM_DEVICE: on the pool's device),
+ * in one numbering for all members: an entry beyond a member's dimensions is legal for that member, as above.  Output
+ * layouts, padding, the capacity protocol, the NULL rules and the exclusion lists are those of
+ * locrec_knn_visitors_recommend_batch / _recommend_ranked_batch, and visitor i's rows and ranked row equal, bit for bit,
+ * what those calls return for that vector on member index_of_visitor[i] alone.  Visitors carry no id: a vector given
+ * twice is computed twice, and a visitor's result depends on its own vector and its member only.
+ * A member of n > 0 persons shares the pool's launches when k_nearest > LOCREC_KNN_BATCH_MAX_K and k_nearest >= n (its
+ * own visitors call would serve every tile without a top-K): ONE stage launch checks and stages every visitor of every
+ * member, then every kernel of the large-K batch is launched once per wave of tiles for all members, with one read-back
+ * of tile counts and one wait per wave.  A member without persons has no rows.  Any other asked member's visitors are
+ * gathered in call order into a CSR of their own (device arrays: device to device) and served by its own
+ * locrec_knn_visitors_* call.
+ * Checks, all before any result is written and in this order, *out_bad_visitor (may be NULL) = the first offending
+ * position, or -1: a NULL pool (nothing at all is written); NULL arguments and negative counts, `mem`, the ranked
+ * arguments and the exclusion offsets with the per-index calls' texts; every index position (LOCREC_E_INVALID_ARG,
+ * "visitor <i> names index <k> of a pool of <m>"); the requires on the weights and k_nearest; a member without a record
+ * for visitors; then the per-visitor refusals of the per-index calls with their messages - the integer rule only for
+ * visitors of members that renumber their place dimensions - where the first offender is the smallest position in call
+ * order across members, the place family first; then a call whose rows may exceed 48 GB in total ("... split it").
+ * nv == 0 succeeds with empty outputs.  All calls are synchronous.  Afterwards every asked member has nothing resident
+ * for locrec_knn_fetch_* and serves persons, visitors and the pool's person calls as before.
+ * stats: this thread's last pool-visitors call: out[0] waves, [1] member tiles, [2] launches of the stage kernel (1),
+ * [3] of the fill kernel (2 a wave), [4] of the scan kernel (1 a wave), [5] of the segment aggregation (1 a wave), [6] of
+ * the sum / count / emit kernels (3 a wave), [7] members served by their own call, [8] entries beyond the members'
+ * dimensions, [9] rows emitted on the device, [10] bytes read back, [11] waits for the pool's stream.
+ */
+int32_t locrec_knn_pool_visitors_recommend_batch(
+    locrec_knn_pool *pool, int64_t nv, const int32_t *index_of_visitor,
+    const int64_t *p_rowptr, const int32_t *p_idx, const double *p_val,
+    const int64_t *c_rowptr, const int32_t *c_idx, const double *c_val, int32_t mem,
+    double place_weight, double category_weight, int64_t k_nearest,
+    int64_t *out_offsets, int64_t *out_place_ids, double *out_estimated_ratings, int64_t *inout_capacity,
+    int64_t *out_bad_visitor);
+int32_t locrec_knn_pool_visitors_recommend_ranked_batch(
+    locrec_knn_pool *pool, int64_t nv, const int32_t *index_of_visitor,
+    const int64_t *p_rowptr, const int32_t *p_idx, const double *p_val,
+    const int64_t *c_rowptr, const int32_t *c_idx, const double *c_val, int32_t mem,
+    double place_weight, double category_weight, int64_t k_nearest,
+    int64_t n_places, const int64_t *place_ids, const int64_t *place_region_ids,
+    const int64_t *target_region_ids, int64_t max_recommendations,
+    const int64_t *exclude_offsets, const int64_t *exclude_place_ids,
+    int64_t *out_place_ids, double *out_estimated_ratings, int64_t *out_counts, int64_t *out_bad_visitor);
+int32_t locrec_knn_pool_visitors_stats(int64_t out[12]);
+
+/*
  * One request with its candidate scan split over several GPUs (SURVEY.md 8e "KNN single request,
  * latency mode").  Every GPU holds the whole index (132 MB at cfg2, 1.3 GB at cfg4: nothing next to
  * 288 GB) and scans candidate shard shard_index of shard_count, a contiguous range of the

@@ -153,6 +153,15 @@ SIGNATURES = {
                                                    C.c_int64, _i64p, _i64p, _i64p, C.c_int64, _i64p, _i64p,
                                                    _i64p, _f64p, _i64p, _i64p],
     "locrec_knn_visitors_stats": [_i64p],
+    # a mixed batch of visitors over a pool: index_of_visitor is a host array, the six vector arrays are in `mem`
+    "locrec_knn_pool_visitors_recommend_batch": [C.c_void_p, C.c_int64, _i32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int64, _i64p,
+                                                 _i64p, _f64p, _i64p, _i64p],
+    "locrec_knn_pool_visitors_recommend_ranked_batch": [C.c_void_p, C.c_int64, _i32p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double,
+                                                        C.c_int64, C.c_int64, _i64p, _i64p, _i64p, C.c_int64, _i64p, _i64p,
+                                                        _i64p, _f64p, _i64p, _i64p],
+    "locrec_knn_pool_visitors_stats": [_i64p],
     "locrec_set_devices": [C.c_int32, _i32p],
     "locrec_knn_replicas_create": [C.c_int32, _i32p, C.c_int64, _i64p, _i64p, _i32p, _f64p, C.c_int32, _i64p, _i32p, _f64p, C.c_int32,
                                    _i64p, _i64p, _i64p, C.POINTER(C.c_void_p)],

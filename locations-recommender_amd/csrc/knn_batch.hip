@@ -220,15 +220,18 @@ extern "C" int32_t locrec_knn_recommend_batch(locrec_knn_index *ix, int64_t nq, 
 // K >= n - 1: the shipped --k-nearest 2000000) takes the shared launches of knn_pool.h; every other member's sub-batch
 // is handed to its own public call.  The pool keeps all its state here: nothing is added to locrec_knn_index.
 #include "knn_pool_api.h"
+#include "knn_pool_visitors_api.h"
 
 struct locrec_knn_pool {
     int device = 0;
     hipStream_t stream = nullptr;
     std::vector<locrec_knn_index *> members;  // not owned
     locrec::KnnPoolShared *shared = nullptr;
+    locrec::KnnPoolVisitors *visitors = nullptr;  // the visitors' stage (locrec_knn_pool_visitors_*), made at the first such call
     DevBuf<int64_t> rk_in, rk_out;  // the ranked form's inputs (places table, targets, segments) and outputs
     ~locrec_knn_pool()
     {
+        locrec::knn_pool_visitors_destroy(visitors);
         locrec::knn_pool_shared_destroy(shared);
         if (stream) (void)hipStreamDestroy(stream);
     }
@@ -507,6 +510,9 @@ extern "C" int32_t locrec_knn_pool_stats(int64_t *out_waves, int64_t *out_member
 // Visitors: rating vectors that are no rows of the index (locrec_knn_visitors_*), and locrec_knn_destroy in front of
 // knn.hip's, which drops the handle's side record (knn_visitors_side.h) first.
 #include "knn_visitors_api.h"
+
+// One mixed batch of visitors over a pool of indexes (locrec_knn_pool_visitors_*): the pool's waves with the visitors' front.
+#include "knn_pool_visitors_entry.h"
 
 // Measurement and tests only (include/locrec.h): what the hit pre-pass of the last batched head / tail scan left in the
 // handle's workspaces (knn_ht_prepass.h).  knn.hip and the handle's layout are hashed (see the head of this file), so

@@ -1257,3 +1257,7 @@ int32_t knn_topk_recommend_batch(locrec_knn_index *ix, const int32_t *rows, int6
 
 // visitors: rating vectors that are no rows of the index, through the tile scan above (locrec_knn_visitors_*, knn_batch.hip)
 #include "knn_visitors.h"
+
+// a mixed batch of visitors over a pool of indexes: the pool's waves with the visitors' stage and scan
+// (locrec_knn_pool_visitors_*, knn_batch.hip)
+#include "knn_pool_visitors.h"

@@ -32,6 +32,8 @@
 // hipcc -Rpass-analysis=kernel-resource-usage, gfx950: VGPRs / LDS bytes (static) / scratch / occupancy (waves per SIMD)
 //   lkv_stage    26 /  0 / 0 / 8
 //   lkv_scan    112 / 64 / 0 / 4   (+ the bitmap, dynamic: at most 32 KB) - lkb_scan's figures
+// (unchanged with their bodies as functions - lkv_stage_body, lkv_scan_body - which the pool's kernels call too:
+// knn_pool_visitors.h)
 
 #include <mutex>
 #include <unordered_map>
@@ -60,12 +62,9 @@ struct LkvStage {
     unsigned long long *report;  // [0] min over refusals of visitor << 8 | family << 4 | code; [1] entries beyond the dimensions
 };
 
-// grid (visitor blocks, 2 families)
-__global__ __launch_bounds__(256) void lkv_stage(const LkvStage a)
+// family f of visitor v against an index of `dim` dimensions in that family; map: the renumbering of the family, or null
+__device__ __forceinline__ void lkv_stage_body(const LkvStage &a, int64_t v, int f, int32_t dim, const int32_t *map)
 {
-    const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int f = blockIdx.y;
-    if (v >= a.nv) return;
     const int64_t b = a.ptr[f][v], e = a.ptr[f][v + 1];
     unsigned code = 0;
     int32_t kept = 0, beyond = 0;
@@ -77,8 +76,6 @@ __global__ __launch_bounds__(256) void lkv_stage(const LkvStage a)
     } else if (e == b) {
         code = kVisErrEmpty;
     } else {
-        const int32_t *map = f == 0 ? a.new_of_old : nullptr;
-        const int32_t dim = a.dim[f];
         int32_t prev = -1;
         for (int64_t i = b; i < e && !code; ++i) {
             const int32_t ix = a.idx[f][i];
@@ -109,22 +106,34 @@ __global__ __launch_bounds__(256) void lkv_stage(const LkvStage a)
     a.norm[f][v] = sqrt(sum);
 }
 
+// grid (visitor blocks, 2 families)
+__global__ __launch_bounds__(256) void lkv_stage(const LkvStage a)
+{
+    const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int f = blockIdx.y;
+    if (v >= a.nv) return;
+    lkv_stage_body(a, v, f, a.dim[f], f == 0 ? a.new_of_old : nullptr);
+}
+
 struct LkvScan {
     LkbScan P;                    // (its qrow is not read)
     const double *vnorm_p, *vnorm_c;  // the vector lengths of the tile's visitors: slot t's at [t]
     int32_t nt;                   // visitors in the tile
 };
 
-// row block blockIdx.x of the tile: lkb_scan_body with the queries' norms from the stage; every row is a candidate
-__global__ __launch_bounds__(256) void lkv_scan(const LkvScan V)
+// row block bx of the tile P: lkb_scan_body with the queries' norms from the stage; every row is a candidate.  kByStage
+// false: slot t's norms at [t], nt slots; true (the pool's form, knn_pool_visitors.h): slot t's norms at [P.qrow[t]], the
+// visitor's position in the stage (a wave-uniform load), -1: no visitor in the slot
+template <bool kByStage>
+__device__ __forceinline__ void lkv_scan_body(const LkbScan &P, int32_t *cand, const double *vnorm_p, const double *vnorm_c, int nt,
+                                              int bx)
 {
-    const LkbScan &P = V.P;
     __shared__ int s_cand[kLkbQt];
     extern __shared__ uint32_t s_bits[];
     if (threadIdx.x < kLkbQt) s_cand[threadIdx.x] = 0;
     for (uint32_t i = threadIdx.x; i < (P.bit_mask + 1u) / 32u; i += blockDim.x) s_bits[i] = P.bits[i];
     __syncthreads();
-    const int row = blockIdx.x * blockDim.x + threadIdx.x;
+    const int row = bx * blockDim.x + threadIdx.x;
     if (row < P.nrows) {
         double dp[kLkbQt], dc[kLkbQt];
 #pragma unroll
@@ -155,14 +164,25 @@ __global__ __launch_bounds__(256) void lkv_scan(const LkvScan V)
         for (int t = 0; t < kLkbQt; ++t) {
             double sx = 0.0;
             bool have = false;
-            if (t < V.nt) have = lkb_similarity(dp[t], dc[t], cnp, cnc, V.vnorm_p[t], V.vnorm_c[t], P.pw, P.cw, sx);
+            if (kByStage) {
+                const int32_t v = P.qrow[t];
+                if (v >= 0) have = lkb_similarity(dp[t], dc[t], cnp, cnc, vnorm_p[v], vnorm_c[v], P.pw, P.cw, sx);
+            } else {
+                if (t < nt) have = lkb_similarity(dp[t], dc[t], cnp, cnc, vnorm_p[t], vnorm_c[t], P.pw, P.cw, sx);
+            }
             if (!have) sx = 0.0;
             P.S[P.transposed ? (int64_t)t * P.nrows + row : (int64_t)row * kLkbQt + t] = sx;
             if (have) atomicAdd(&s_cand[t], 1);
         }
     }
     __syncthreads();
-    if (threadIdx.x < kLkbQt && s_cand[threadIdx.x]) atomicAdd(&P.cand[threadIdx.x], s_cand[threadIdx.x]);
+    if (threadIdx.x < kLkbQt && s_cand[threadIdx.x]) atomicAdd(&cand[threadIdx.x], s_cand[threadIdx.x]);
+}
+
+// grid (row blocks of the tile)
+__global__ __launch_bounds__(256) void lkv_scan(const LkvScan V)
+{
+    lkv_scan_body<false>(V.P, V.P.cand, V.vnorm_p, V.vnorm_c, V.nt, (int)blockIdx.x);
 }
 
 // the handles' side records; never destroyed with the process (no device call after the runtime is gone)
@@ -246,6 +266,28 @@ void knn_visitors_drop(const locrec_knn_index *ix)
         if (it == lkv_registry().end()) return;
         old = std::move(it->second);
         lkv_registry().erase(it);
+    }
+}
+
+// the refusal the stage's report word stands for (lkv_stage, lkv_stage_pool): *bad = the visitor, the family's message
+static int32_t lkv_refuse(unsigned long long word, int64_t *bad)
+{
+    const char *const fam[2] = {"place", "category"};
+    const long long who = (long long)(word >> 8);
+    const char *name = fam[(word >> 4) & 1];
+    if (bad) *bad = who;
+    switch ((int)(word & 0xF)) {
+    case kVisErrPtr: return fail(LOCREC_E_INVALID_ARG, "%s rowptr not monotone at visitor %lld", name, who);
+    case kVisErrLong: return fail(LOCREC_E_INVALID_ARG, "%s vector of visitor %lld has 2^21 or more entries", name, who);
+    case kVisErrEmpty: return fail(LOCREC_E_NOT_FOUND, "No such person: visitor %lld has no %s vector", who, name);
+    case kVisErrNegative: return fail(LOCREC_E_INVALID_ARG, "%s index of visitor %lld is negative", name, who);
+    case kVisErrOrder: return fail(LOCREC_E_INVALID_ARG, "%s indices of visitor %lld not strictly ascending", name, who);
+    case kVisErrFinite: return fail(LOCREC_E_INVALID_ARG, "%s value of visitor %lld is not finite", name, who);
+    case kVisErrFraction:
+        return fail(LOCREC_E_INVALID_ARG,
+                    "%s value of visitor %lld is not an integer count below 65536: the index renumbers its place dimensions",
+                    name, who);
+    default: return fail(LOCREC_E_INVALID_ARG, "%s vector of visitor %lld has zero norm", name, who);
     }
 }
 
@@ -357,24 +399,7 @@ int32_t knn_visitors_stage(locrec_knn_index *ix, KnnVisitorSide &side, const Knn
     LOCREC_HIP_TRY(hipStreamSynchronize(s));
     ++st.host_syncs;
     st.renumbered = side.renumbered() ? 1 : 0;
-    if (report[0] != ~0ull) {
-        const long long who = (long long)(report[0] >> 8);
-        const char *name = fam[(report[0] >> 4) & 1];
-        if (bad) *bad = who;
-        switch ((int)(report[0] & 0xF)) {
-        case kVisErrPtr: return fail(LOCREC_E_INVALID_ARG, "%s rowptr not monotone at visitor %lld", name, who);
-        case kVisErrLong: return fail(LOCREC_E_INVALID_ARG, "%s vector of visitor %lld has 2^21 or more entries", name, who);
-        case kVisErrEmpty: return fail(LOCREC_E_NOT_FOUND, "No such person: visitor %lld has no %s vector", who, name);
-        case kVisErrNegative: return fail(LOCREC_E_INVALID_ARG, "%s index of visitor %lld is negative", name, who);
-        case kVisErrOrder: return fail(LOCREC_E_INVALID_ARG, "%s indices of visitor %lld not strictly ascending", name, who);
-        case kVisErrFinite: return fail(LOCREC_E_INVALID_ARG, "%s value of visitor %lld is not finite", name, who);
-        case kVisErrFraction:
-            return fail(LOCREC_E_INVALID_ARG,
-                        "%s value of visitor %lld is not an integer count below 65536: the index renumbers its place dimensions",
-                        name, who);
-        default: return fail(LOCREC_E_INVALID_ARG, "%s vector of visitor %lld has zero norm", name, who);
-        }
-    }
+    if (report[0] != ~0ull) return lkv_refuse(report[0], bad);
     st.beyond = (int64_t)report[1];
     return LOCREC_OK;
 }

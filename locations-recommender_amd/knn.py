@@ -576,6 +576,85 @@ class KnnPool:
                 raise
         return oi, osc, cnt
 
+    # visitors over the pool: rating vectors that are no rows of any member (locrec_knn_pool_visitors_*)
+    VISITOR_STATS = ("waves", "member_tiles", "stage_launches", "fill_launches", "scan_launches", "aggregate_launches",
+                     "finish_launches", "delegated_members", "beyond", "emitted_rows", "readback_bytes", "host_syncs")
+
+    @staticmethod
+    def _visitor_pool_args(index_of, p_rowptr, p_idx, p_val, c_rowptr, c_idx, c_val):
+        """KnnIndex._visitor_args and the index positions (a host array whatever `mem` is): one per visitor."""
+        nv, ptrs, mem, keep = KnnIndex._visitor_args(p_rowptr, p_idx, p_val, c_rowptr, c_idx, c_val)
+        gi = L.as_i32(index_of.cpu().numpy() if hasattr(index_of, "cpu") else index_of)
+        if len(gi) != nv:
+            raise L.IllegalArgumentException("requirement failed: one index position per visitor is required")
+        return nv, gi, ptrs, mem, keep
+
+    def _visitor_pool_call(self, fn, *args):
+        """fn(*args, &bad) under every member's lock: a refused call raises with `bad_visitor` set (-1: no single visitor)."""
+        bad = C.c_int64(-1)
+        try:
+            L.check(fn(*args, C.byref(bad)))
+        except L.IllegalArgumentException as e:
+            e.bad_visitor = bad.value
+            raise
+
+    def visitors_recommend_batch(self, index_of, p_rowptr, p_idx, p_val, c_rowptr, c_idx, c_val, pw, cw, k):
+        """makeRecommendations of indexes[index_of[i]] for visitor i - row i of ONE CSR over all visitors (numpy arrays or
+        CUDA tensors, as KnnIndex.visitors_recommend_batch takes them) - every i in one call:
+        (offsets[nv + 1], place_ids, estimated_ratings), visitor i's rows exactly what
+        indexes[index_of[i]].visitors_recommend_batch returns for that vector.  A refused call raises with `bad_visitor`
+        set: the first offending position in call order.  The output arrays remember the largest result this object has
+        returned (recommend_batch's two-pass protocol)."""
+        nv, gi, ptrs, mem, keep = self._visitor_pool_args(index_of, p_rowptr, p_idx, p_val, c_rowptr, c_idx, c_val)
+        off = np.zeros(nv + 1, np.int64)
+        room = max(getattr(self, "_visitor_room", 0), 1 << 16)
+        cap = C.c_int64(room)
+        places, est = np.empty(room, np.int64), np.empty(room, np.float64)
+        with self._locked():
+            for _ in range(2):  # a call whose room is too small sizes the result, the second fills it
+                self._visitor_pool_call(L.lib().locrec_knn_pool_visitors_recommend_batch, self._h, nv, L.ptr(gi, C.c_int32),
+                                        *ptrs, mem, float(pw), float(cw), int(k), L.ptr(off, C.c_int64),
+                                        L.ptr(places, C.c_int64), L.ptr(est, C.c_double), C.byref(cap))
+                if cap.value <= len(places):
+                    break
+                places, est = np.empty(cap.value, np.int64), np.empty(cap.value, np.float64)
+                cap = C.c_int64(len(places))
+        self._visitor_room = max(room, int(off[-1]))
+        return off, places[:off[-1]].copy(), est[:off[-1]].copy()
+
+    def visitors_recommend_ranked_batch(self, index_of, p_rowptr, p_idx, p_val, c_rowptr, c_idx, c_val, pw, cw, k, place_ids,
+                                        place_region_ids, target_region_ids, max_recommendations, exclude=None):
+        """The pool's visitors to their end (locrec_knn_pool_visitors_recommend_ranked_batch): visitor i gets the places of
+        target_region_ids[i], top max_recommendations by estimated rating, in KnnIndex.visitors_recommend_ranked_batch's
+        layout and equal to that call on its member alone.  exclude = (offsets[nv + 1], place_ids): per visitor the places
+        its ranking leaves out."""
+        nv, gi, ptrs, mem, keep = self._visitor_pool_args(index_of, p_rowptr, p_idx, p_val, c_rowptr, c_idx, c_val)
+        pl, reg, tgt = L.as_i64(place_ids), L.as_i64(place_region_ids), L.as_i64(target_region_ids)
+        if len(reg) != len(pl) or len(tgt) != nv:
+            raise L.IllegalArgumentException("one region per place and one target region per person are required")
+        width = max(0, min(int(max_recommendations), len(pl)))   # a visitor has at most one row per place
+        oi, osc, cnt = np.empty((nv, width), np.int64), np.empty((nv, width), np.float64), np.zeros(nv, np.int64)
+        ex_off = ex_ids = None
+        if exclude is not None:
+            ex_off, ex_ids = L.as_i64(exclude[0]), L.as_i64(exclude[1])
+            if len(ex_off) != nv + 1:
+                raise L.IllegalArgumentException("requirement failed: one exclusion list per visitor (nv + 1 offsets)")
+            if len(ex_off) and ex_off[-1] > len(ex_ids):
+                raise L.IllegalArgumentException("requirement failed: the exclusion offsets end beyond the listed ids")
+        with self._locked():
+            self._visitor_pool_call(L.lib().locrec_knn_pool_visitors_recommend_ranked_batch, self._h, nv, L.ptr(gi, C.c_int32),
+                                    *ptrs, mem, float(pw), float(cw), int(k), len(pl), L.ptr(pl, C.c_int64),
+                                    L.ptr(reg, C.c_int64), L.ptr(tgt, C.c_int64), width, L.ptr(ex_off, C.c_int64),
+                                    L.ptr(ex_ids, C.c_int64), L.ptr(oi, C.c_int64), L.ptr(osc, C.c_double), L.ptr(cnt, C.c_int64))
+        return oi, osc, cnt
+
+    @classmethod
+    def visitors_stats(cls):
+        """What this thread's last pool-visitors call did (locrec_knn_pool_visitors_stats)."""
+        v = (C.c_int64 * 12)()
+        L.check(L.lib().locrec_knn_pool_visitors_stats(v))
+        return dict(zip(cls.VISITOR_STATS, (int(x) for x in v)))
+
     @classmethod
     def stats(cls):
         """What this thread's last pool call did (locrec_knn_pool_stats)."""

@@ -265,6 +265,124 @@ def knn_visitor_requests(data_dir, region_ids, visits, target_region_ids, place_
     return [(int(v), oi[i, :cnt[i]].copy(), osc[i, :cnt[i]].copy()) for i, v in enumerate(host_ids)]
 
 
+def _per_visitor(values, host_ids, what):
+    """A mapping visitor id -> value, one value for all, or one per visitor in ascending visitor id -> int64[nv]."""
+    if hasattr(values, "keys"):
+        out = np.asarray([values[int(v)] for v in host_ids], np.int64)
+    elif np.ndim(values) == 0:
+        out = np.full(len(host_ids), int(values), np.int64)
+    else:
+        out = np.asarray(values.cpu().numpy() if hasattr(values, "cpu") else values, np.int64)
+    if len(out) != len(host_ids):
+        raise L.IllegalArgumentException(f"requirement failed: one {what} region per visitor is required")
+    return out
+
+
+def _csr_rows(rowptr, arrays, rows):
+    """The listed rows of a CSR (rowptr and its element arrays; numpy arrays or tensors of one device) as a CSR of their
+    own, in the given order."""
+    if hasattr(rowptr, "is_cuda"):
+        import torch as xp
+        at = xp.as_tensor(np.asarray(rows, np.int64), device=rowptr.device)
+        zeros, arange, repeat = (lambda n: xp.zeros(n, dtype=xp.int64, device=rowptr.device),
+                                 lambda n: xp.arange(n, dtype=xp.int64, device=rowptr.device), xp.repeat_interleave)
+    else:
+        xp, at = np, np.asarray(rows, np.int64)
+        rowptr = np.asarray(rowptr, np.int64)
+        zeros, arange, repeat = (lambda n: np.zeros(n, np.int64)), (lambda n: np.arange(n, dtype=np.int64)), np.repeat
+    lens = (rowptr[1:] - rowptr[:-1])[at]
+    ptr = zeros(len(rows) + 1)
+    ptr[1:] = xp.cumsum(lens, 0)
+    take = repeat(rowptr[:-1][at] - ptr[:-1], lens) + arange(int(ptr[-1]))
+    return ptr, tuple(a[take] for a in arrays)
+
+
+def knn_visitor_requests_pooled(data_dir, visits, home_region_ids, target_region_ids, place_weight, category_weight, k_nearest,
+                                max_recommendations=10, new_places=False, pooled=True):
+    """knn_visitor_requests for a queue of cold-start persons that fans out over region sets as persons do: visits as in
+    knn_visitor_requests; home_region_ids and target_region_ids per visitor - a mapping visitor id -> region, one region
+    for all, or one per visitor in ascending visitor id.  Every visitor's index is the one of [home, target] from the
+    handle cache (one handle per distinct region set, _knn_resolve_request_lines), the vectors come from ONE
+    prep.visitor_vectors call - one numbering for all members - and ONE KnnPool.visitors_recommend_ranked_batch call serves
+    everybody.
+    -> a list in ascending visitor id of (visitor_id, place_ids, estimated_ratings); where a visitor's region set cannot
+    be opened the entry is the exception instance; where the stage refuses a visitor the exception is recorded and the call
+    repeated without the visitor (_call_without_bad_lines' contract).
+    new_places=True: the places a visitor has rated are left out.
+    pooled=False: one KnnIndex.visitors_recommend_ranked_batch call per distinct index instead of the pool call - the same
+    result bit for bit; what such a queue cost before the pool."""
+    from . import _cache, prep
+    from .knn import KnnPool
+    _cache.require_gpu_backend("knn_visitor_requests_pooled")
+    ids, vectors, rated = prep.visitor_vectors(visits["visitor_id"], visits["place_id"], visits["category_id"])
+    host_ids = np.asarray(ids.cpu().numpy() if hasattr(ids, "cpu") else ids, np.int64)
+    homes = _per_visitor(home_region_ids, host_ids, "home")
+    regions = _per_visitor(target_region_ids, host_ids, "target")
+    lists = tuple(np.asarray(a.cpu().numpy() if hasattr(a, "cpu") else a, np.int64) for a in rated) if new_places else None
+    out, targets, indexes = _knn_resolve_request_lines(
+        data_dir, None, list(range(len(host_ids))), resolve=lambda i: (int(host_ids[i]), int(homes[i]), int(regions[i])))
+    try:
+        if targets:
+            place_ids, place_regions = load_places(data_dir)
+            pool = KnnPool(indexes) if pooled else None
+            try:
+                def call(gi, _, live):
+                    if len(live) == len(host_ids):
+                        vec, ex = vectors, lists
+                    else:  # (without the visitors whose region set has no index, or whom the stage refused)
+                        p_ptr, (p_idx, p_val) = _csr_rows(vectors[0], vectors[1:3], live)
+                        c_ptr, (c_idx, c_val) = _csr_rows(vectors[3], vectors[4:6], live)
+                        vec = (p_ptr, p_idx, p_val, c_ptr, c_idx, c_val)
+                        ex = None
+                        if lists is not None:
+                            e_ptr, (e_ids,) = _csr_rows(lists[0], lists[1:2], live)
+                            ex = (e_ptr, e_ids)
+                    tgt = regions[np.asarray(live, np.int64)]
+                    if pool is not None:
+                        return pool.visitors_recommend_ranked_batch(gi, *vec, place_weight, category_weight, k_nearest, place_ids,
+                                                                    place_regions, tgt, max_recommendations, exclude=ex)
+                    return _knn_visitors_per_index(indexes, gi, vec, place_weight, category_weight, k_nearest, place_ids,
+                                                   place_regions, tgt, max_recommendations, ex)
+                live, rows = _call_without_bad_lines(out, targets, call)
+            finally:
+                if pool is not None:
+                    pool.close()
+            if live:
+                oi, osc, cnt = rows
+                for j, i in enumerate(live):
+                    out[i] = (int(host_ids[i]), np.array(oi[j, :cnt[j]]), np.array(osc[j, :cnt[j]]))
+    finally:
+        for ix in indexes:
+            ix.close()  # drops the reference only
+    return out
+
+
+def _knn_visitors_per_index(indexes, index_of, vectors, pw, cw, k, place_ids, place_regions, regions, max_recommendations, exclude):
+    """KnnPool.visitors_recommend_ranked_batch's result from one KnnIndex.visitors_recommend_ranked_batch call per distinct
+    index on that index's visitors in call order; a refused visitor raises with bad_visitor = its position in the call."""
+    n = len(index_of)
+    width = max(0, min(int(max_recommendations), len(place_ids)))
+    oi, osc, cnt = np.full((n, width), -1, np.int64), np.zeros((n, width), np.float64), np.zeros(n, np.int64)
+    for k_ix in np.unique(index_of):
+        at = np.flatnonzero(index_of == k_ix)
+        p_ptr, (p_idx, p_val) = _csr_rows(vectors[0], vectors[1:3], at)
+        c_ptr, (c_idx, c_val) = _csr_rows(vectors[3], vectors[4:6], at)
+        ex = None
+        if exclude is not None:
+            e_ptr, (e_ids,) = _csr_rows(exclude[0], exclude[1:2], at)
+            ex = (e_ptr, e_ids)
+        try:
+            with indexes[k_ix].lock:
+                oi[at], osc[at], cnt[at] = indexes[k_ix].visitors_recommend_ranked_batch(
+                    p_ptr, p_idx, p_val, c_ptr, c_idx, c_val, pw, cw, k, place_ids, place_regions, regions[at],
+                    max_recommendations, exclude=ex)
+        except L.IllegalArgumentException as e:
+            if getattr(e, "bad_visitor", -1) >= 0:
+                e.bad_visitor = int(at[e.bad_visitor])
+            raise
+    return oi, osc, cnt
+
+
 def sg_recommend_places_batch(data_dir, region_ids, requests, epsilon, max_iterations, alpha=0.15, max_recommendations=10,
                               on_device=True, new_places=False):
     """Many requests of one region pair (StochasticRecommenderMain.scala:53-75): requests is a sequence of
@@ -884,9 +1002,10 @@ def _sg_resolve_request_lines(data_dir, persons, lines):
     return _resolve_request_lines(persons, lines, open_graph)
 
 
-def _knn_resolve_request_lines(data_dir, persons, lines):
+def _knn_resolve_request_lines(data_dir, persons, lines, resolve=None):
     """_sg_resolve_request_lines for the KNN main: the index of [home, target] from the handle cache under
-    knn_make_recommendations' key, one handle per distinct region set.  -> (out, targets, indexes)."""
+    knn_make_recommendations' key, one handle per distinct region set.  -> (out, targets, indexes).
+    resolve: what turns a line into (person_id, home_region_id, target_region_id) in place of parsing it."""
     from . import _cache
     from .knn import KnnIndex
 
@@ -895,10 +1014,10 @@ def _knn_resolve_request_lines(data_dir, persons, lines):
                       for f in ("place_rating_vectors", "category_rating_vectors", "place_ratings"))
         return names, lambda: KnnIndex.through_cache(_cache.files_key(list(names)),
                                                      lambda: knn_index_from_parquet(data_dir, region_ids))
-    return _resolve_request_lines(persons, lines, open_index)
+    return _resolve_request_lines(persons, lines, open_index, resolve)
 
 
-def _resolve_request_lines(persons, lines, open_handle):
+def _resolve_request_lines(persons, lines, open_handle, resolve=None):
     """Every line parsed and resolved on its own; open_handle([home, target]) -> (the region set's name, a function that
     takes its handle from the cache), called once per distinct name - a failure is remembered and raised for every line
     of that region set.  -> (out, targets, handles) as _sg_resolve_request_lines describes them."""
@@ -907,7 +1026,7 @@ def _resolve_request_lines(persons, lines, open_handle):
     try:
         for i, line in enumerate(lines):
             try:
-                target = calc_recommender_target(persons, parse_input(line))
+                target = resolve(line) if resolve is not None else calc_recommender_target(persons, parse_input(line))
                 name, take = open_handle([target[1], target[2]])
                 if name in failed:
                     raise failed[name]
@@ -941,7 +1060,7 @@ def _call_without_bad_lines(out, targets, call):
         try:
             rows = call(gi, v, live)
         except L.IllegalArgumentException as e:
-            bad = getattr(e, "bad_request", -1)
+            bad = getattr(e, "bad_request", getattr(e, "bad_visitor", -1))  # (a visitors call names the position so)
             if bad < 0:
                 raise
             out[live.pop(bad)] = e  # the line's vertex is not in its graph: recorded, the call repeated without it
