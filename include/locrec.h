@@ -892,6 +892,49 @@ int32_t locrec_sg_pool_recommend_ranked_batch(
 int32_t locrec_sg_pool_recommend_ranked_batch_stats(
     int64_t *out_tile_waves, int64_t *out_tiles, int64_t *out_rounds, int64_t *out_groups,
     int64_t *out_emit_launches, int64_t *out_emitted_rows, int64_t *out_readback_bytes, int64_t *out_host_syncs);
+/*
+ * Visitors across a pool: ONE CSR of visitors (locrec_sg_visitors_recommend_batch's), visitor v asked of member
+ * graph_index[v].  Visitor v's rows, iterations and converged flag equal bit for bit what
+ * locrec_sg_visitors_recommend_batch returns for it on its member alone; the ranked call's row, count and row count equal
+ * locrec_sg_visitors_recommend_ranked_batch's on its member alone.  A visitor's result depends on its member and its own
+ * edges only - not on the other visitors, the other members, its position, its tile or its wave; a visitor given twice
+ * is computed twice.  Offsets, the capacity protocol and the NULL rules are locrec_sg_recommend_batch's; the ranked
+ * outputs are locrec_sg_pool_recommend_ranked_batch's (ONE places table serves all members);
+ * excluded_offsets == NULL: nothing is left out; the result does not depend on LOCREC_SG_RANKED_ROW_BUDGET.
+ * Every member's tile of 16 visitors (wave k of a member: its visitors 16k .. 16k+15 in call order) shares the launches
+ * of a round: per call one staging, per wave one set-up pair and one read-back or emit, per round one sweep launch per
+ * layout class present and one finalize launch, whatever the number of members.  A member nobody asks costs nothing.
+ * All checks run before any device work; on a refusal nothing is written but *out_bad_visitor (may be NULL; -1 on
+ * success), in this order:
+ *   1. NULL and count checks, the CSR's shape, the constructor's two require()s (locrec_sg_visitors_recommend_batch's
+ *      texts; *out_bad_visitor = -1)
+ *   2. the ranked call's own arguments and exclusion lists (locrec_sg_recommend_ranked_batch_excluding's)
+ *   3. every graph index: LOCREC_E_INVALID_ARG, locrec_sg_pool_recommend_batch's text, the visitor's position
+ *   4. the visitors in call order, each against its own member: no edges, a non-finite weight, an unknown id, a
+ *      source-only target, a target repeated (locrec_sg_visitors_recommend_batch's codes and texts): the first offender
+ *      in call order, whichever member it belongs to
+ * nv == 0 succeeds with empty outputs.  Afterwards every member serves single, batched, ranked and visitors requests as
+ * a fresh handle would, and the pool its person calls; person calls and visitor calls may alternate on one pool.
+ * stats: this thread's last pool visitors call: tile waves, member tiles, visitors, staged edges, stagings, sg_begin_pool
+ * launches, set-up launches, rounds, sweep launches, finalize launches, convergence polls, read-backs or emits (one a
+ * wave).  locrec_sg_pool_recommend_ranked_batch_stats reports on the ranked call too.
+ */
+int32_t locrec_sg_pool_visitors_recommend_batch(
+    locrec_sg_pool *pool, int64_t nv, const int32_t *graph_index,
+    const int64_t *edge_offsets, const int64_t *target_ids, const double *weights,
+    double alpha, double epsilon, int64_t max_iterations,
+    int64_t *out_offsets, int64_t *out_ids, double *out_probabilities, int64_t *inout_capacity,
+    int64_t *out_iterations, int32_t *out_converged, int64_t *out_bad_visitor);
+int32_t locrec_sg_pool_visitors_recommend_ranked_batch(
+    locrec_sg_pool *pool, int64_t nv, const int32_t *graph_index,
+    const int64_t *edge_offsets, const int64_t *target_ids, const double *weights,
+    double alpha, double epsilon, int64_t max_iterations,
+    int64_t n_places, const int64_t *place_ids, const int64_t *place_region_ids,
+    const int64_t *target_region_ids, int64_t max_recommendations,
+    const int64_t *excluded_offsets, int64_t n_excluded, const int64_t *excluded_ids,
+    int64_t *out_ids, double *out_probabilities, int64_t *out_counts,
+    int64_t *out_row_counts, int64_t *out_iterations, int32_t *out_converged, int64_t *out_bad_visitor);
+int32_t locrec_sg_pool_visitors_stats(int64_t out[12]);
 
 int32_t locrec_sg_set_stream(locrec_sg_graph *graph, void *hip_stream);
 int32_t locrec_sg_synchronize(locrec_sg_graph *graph);

@@ -135,6 +135,12 @@ SIGNATURES = {
                                               C.c_int64, _i64p, _i64p, _i64p, C.c_int64, _i64p, _f64p, _i64p, _i64p, _i64p, _i32p,
                                               _i64p],
     "locrec_sg_pool_recommend_ranked_batch_stats": [_i64p, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p],
+    "locrec_sg_pool_visitors_recommend_batch": [C.c_void_p, C.c_int64, _i32p, _i64p, _i64p, _f64p, C.c_double, C.c_double,
+                                                C.c_int64, _i64p, _i64p, _f64p, _i64p, _i64p, _i32p, _i64p],
+    "locrec_sg_pool_visitors_recommend_ranked_batch": [C.c_void_p, C.c_int64, _i32p, _i64p, _i64p, _f64p, C.c_double, C.c_double,
+                                                       C.c_int64, C.c_int64, _i64p, _i64p, _i64p, C.c_int64, _i64p, C.c_int64,
+                                                       _i64p, _i64p, _f64p, _i64p, _i64p, _i64p, _i32p, _i64p],
+    "locrec_sg_pool_visitors_stats": [_i64p],
     "locrec_knn_pool_create": [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p)],
     "locrec_knn_pool_destroy": [C.c_void_p],
     "locrec_knn_pool_recommend_batch": [C.c_void_p, C.c_int64, _i32p, _i64p, C.c_double, C.c_double, C.c_int64,

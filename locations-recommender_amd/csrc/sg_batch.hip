@@ -908,3 +908,4 @@ extern "C" int32_t locrec_sg_recommend_batch(locrec_sg_graph *g, int64_t n_targe
 #include "sg_pool.h"
 #include "sg_pool_ranked.h"
 #include "sg_visitors.h"
+#include "sg_pool_visitors.h"

@@ -19,6 +19,9 @@
 //   read-back     ONE sg_pack_pool launch per tile wave: every graph's packed image (sg_pack_batch's) at the graph's offset
 //                 of the pool's pinned buffer, one synchronisation; then sg_batch_host_rows per graph.  What happens to a
 //                 finished wave is a parameter of sg_pool_waves: the ranked pool (sg_pool_ranked.h) emits and ranks instead
+//   columns       what a member's columns are is a parameter too (sg_pool_waves_of's tiles policy): the distinct vertices
+//                 asked of it (SgPoolPersonTiles), or its visitors (SgPoolVisitorTiles, sg_pool_visitors.h), which add one
+//                 set-up launch per wave and finalize with their own kernel
 //
 // The bodies are sg_batch.hip's (sg_sweep_batch_body and friends), on each graph's own batch buffers (PA4 / XL / D2W /
 // fused_conv) - the order of operations per column is the batch's, which is the single request's: request i's rows are
@@ -109,6 +112,9 @@ SgPoolStats &sg_pool_stats()
 
 inline size_t sg_pool_align(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
+// a member's row of a visitors wave, beside its SgPoolTile row: sizeof(SgPoolVisRow), sg_pool_visitors.h (asserted there)
+constexpr size_t kSgPoolVisRowBytes = 88;
+
 }  // namespace
 
 struct locrec_sg_pool {
@@ -117,11 +123,12 @@ struct locrec_sg_pool {
     hipEvent_t done = nullptr;              // end of a call's launches: the members' own streams wait for it
     std::vector<locrec_sg_graph *> graphs;  // not owned
     bool no_pack = false;                   // a member was created under LOCREC_SG_NO_PACK: plain copies
-    // the tables of a tile wave: one host image and one device buffer (SgPoolTile rows, SgBatchBegin rows, then the four
-    // classes' SgPoolView rows), one copy per wave; sized by the number of members
+    // the tables of a tile wave: one host image and one device buffer (SgPoolTile rows, SgBatchBegin rows, the four
+    // classes' SgPoolView rows, then - a visitors call only - the SgPoolVisRow rows), one copy per wave; sized by the
+    // number of members
     std::vector<unsigned char> tab_host;
     DevBuf<unsigned char> tab_dev;
-    size_t off_begin = 0, off_views = 0;
+    size_t off_begin = 0, off_views = 0, off_vis = 0;
     unsigned char *h_pack = nullptr;  // pinned: every member's packed image side by side
     unsigned char *h_pack_dev = nullptr;
     size_t h_pack_bytes = 0;
@@ -184,7 +191,8 @@ extern "C" int32_t locrec_sg_pool_create(locrec_sg_graph *const *graphs, int32_t
     const size_t n = (size_t)n_graphs;
     pool->off_begin = sg_pool_align(n * sizeof(SgPoolTile));
     pool->off_views = pool->off_begin + sg_pool_align(n * sizeof(SgBatchBegin));
-    pool->tab_host.assign(pool->off_views + n * sizeof(SgPoolView), 0);
+    pool->off_vis = pool->off_views + sg_pool_align(n * sizeof(SgPoolView));
+    pool->tab_host.assign(pool->off_vis + n * kSgPoolVisRowBytes, 0);
     LOCREC_TRY(pool->tab_dev.alloc(pool->tab_host.size()));
     LOCREC_TRY(pool->poll_word.alloc(1));
     pool->pack_room(pack_bytes);  // (a tile wave holds at most every member once)
@@ -242,19 +250,39 @@ struct SgPoolWave {
     unsigned pack_blocks;
 };
 
+// What the columns of a pool call's tiles are: distinct vertices of the members (here), or visitors (SgPoolVisitorTiles,
+// sg_pool_visitors.h).  Member gi has mem[gi].uniq.size() columns either way.
+struct SgPoolPersonTiles {
+    int tile_max(const locrec_sg_graph *g) const { return sg_batch_tile_max(g); }
+    // the set-up and finalize rows of member gi's tile of wave k: its columns t0 .. t0 + nb
+    void rows(int32_t, const locrec_sg_graph *g, SgPoolMember &m, size_t, size_t t0, int nb, double alpha, double eps2, SgBatchBegin &b,
+              SgBatchReq &rq) const
+    {
+        sg_batch_tile_rows(g, m.uniq, t0, nb, alpha, eps2, m.pointed, b, rq);
+    }
+    void member_row(locrec_sg_pool *, unsigned, int32_t, size_t) const {}  // (rows of the wave's table beside SgPoolTile's: none)
+    // bytes of the wave's table that travel to the device
+    size_t table_bytes(const locrec_sg_pool *pool, size_t nviews, unsigned) const { return pool->off_views + nviews * sizeof(SgPoolView); }
+    void set_up(locrec_sg_pool *, hipStream_t, unsigned) const {}  // (launches behind the wave's sg_begin_pool: none)
+    void finalize(locrec_sg_pool *, hipStream_t s, unsigned nw, const SgPoolTile *tiles_dev, int par, int32_t first) const
+    {
+        hipLaunchKernelGGL(sg_finalize_pool, dim3(kParts, nw), dim3(256), 0, s, tiles_dev, par, first);
+    }
+};
+
 // Every tile wave of a call: set-up, rounds and polls, then consume(wave) - after the wave's last round and before the
 // next wave's set-up overwrites x and the tables; it returns with the stream synchronised.  `act` lists the members with
-// requests.
-template <class Consume>
-int32_t sg_pool_waves(locrec_sg_pool *pool, const std::vector<int32_t> &act, std::vector<SgPoolMember> &mem, double alpha,
-                      double epsilon, int64_t max_iterations, SgPoolStats &stats, Consume &&consume)
+// requests, `tp` says what their columns are.
+template <class Tiles, class Consume>
+int32_t sg_pool_waves_of(locrec_sg_pool *pool, const std::vector<int32_t> &act, std::vector<SgPoolMember> &mem, Tiles &&tp,
+                         double alpha, double epsilon, int64_t max_iterations, SgPoolStats &stats, Consume &&consume)
 {
     hipStream_t s = pool->stream;
     const double eps2 = epsilon * epsilon;  // :40
     const bool poll = epsilon > 0 && max_iterations > 4;
     size_t nwaves = 0;
     for (const int32_t gi : act) {
-        const size_t tm = (size_t)sg_batch_tile_max(pool->graphs[(size_t)gi]);
+        const size_t tm = (size_t)tp.tile_max(pool->graphs[(size_t)gi]);
         nwaves = std::max(nwaves, (mem[(size_t)gi].uniq.size() + tm - 1) / tm);
     }
     SgPoolTile *tiles = reinterpret_cast<SgPoolTile *>(pool->tab_host.data());
@@ -269,7 +297,7 @@ int32_t sg_pool_waves(locrec_sg_pool *pool, const std::vector<int32_t> &act, std
         wave.clear();
         wave_nb.clear();
         for (const int32_t gi : act) {
-            const size_t tm = (size_t)sg_batch_tile_max(pool->graphs[(size_t)gi]), nu = mem[(size_t)gi].uniq.size();
+            const size_t tm = (size_t)tp.tile_max(pool->graphs[(size_t)gi]), nu = mem[(size_t)gi].uniq.size();
             if (k * tm < nu) {
                 wave.push_back(gi);
                 wave_nb.push_back((int)std::min(tm, nu - k * tm));
@@ -291,9 +319,10 @@ int32_t sg_pool_waves(locrec_sg_pool *pool, const std::vector<int32_t> &act, std
         for (unsigned j = 0; j < nw; ++j) {
             locrec_sg_graph *g = pool->graphs[(size_t)wave[j]];
             SgPoolMember &m = mem[(size_t)wave[j]];
-            const size_t t0 = k * (size_t)sg_batch_tile_max(g);
+            const size_t t0 = k * (size_t)tp.tile_max(g);
             SgPoolTile &t = tiles[j];
-            sg_batch_tile_rows(g, m.uniq, t0, wave_nb[j], alpha, eps2, m.pointed, begins[j], t.rq);
+            tp.rows(wave[j], g, m, k, t0, wave_nb[j], alpha, eps2, begins[j], t.rq);
+            tp.member_row(pool, j, wave[j], k);
             t.lrows = g->lrows.p;
             t.partial = g->XL.p;
             t.xbuf = g->PA4.p;
@@ -329,9 +358,9 @@ int32_t sg_pool_waves(locrec_sg_pool *pool, const std::vector<int32_t> &act, std
             }
         }
         const size_t nviews = (size_t)(class_at[3] + class_n[3]);
-        LOCREC_HIP_TRY(hipMemcpyAsync(pool->tab_dev.p, pool->tab_host.data(), pool->off_views + nviews * sizeof(SgPoolView),
-                                      hipMemcpyHostToDevice, s));
+        LOCREC_HIP_TRY(hipMemcpyAsync(pool->tab_dev.p, pool->tab_host.data(), tp.table_bytes(pool, nviews, nw), hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(sg_begin_pool, dim3(kBeginBlocks, nw), dim3(256), 0, s, begins_dev);
+        tp.set_up(pool, s, nw);
         ++stats.tile_waves;
         auto launch_round = [&](int64_t i) {
             const int par = (int)(i & 1);
@@ -346,7 +375,7 @@ int32_t sg_pool_waves(locrec_sg_pool *pool, const std::vector<int32_t> &act, std
             LOCREC_SWEEP_POOL(2, false, true)
             LOCREC_SWEEP_POOL(3, false, false)
 #undef LOCREC_SWEEP_POOL
-            hipLaunchKernelGGL(sg_finalize_pool, dim3(kParts, nw), dim3(256), 0, s, tiles_dev, par, i == 0 ? 1 : 0);
+            tp.finalize(pool, s, nw, tiles_dev, par, i == 0 ? 1 : 0);
             ++stats.finalize_launches;
             ++stats.rounds;
         };
@@ -377,6 +406,27 @@ int32_t sg_pool_waves(locrec_sg_pool *pool, const std::vector<int32_t> &act, std
     return LOCREC_OK;
 }
 
+// ... of the members' distinct targets
+template <class Consume>
+int32_t sg_pool_waves(locrec_sg_pool *pool, const std::vector<int32_t> &act, std::vector<SgPoolMember> &mem, double alpha,
+                      double epsilon, int64_t max_iterations, SgPoolStats &stats, Consume &&consume)
+{
+    return sg_pool_waves_of(pool, act, mem, SgPoolPersonTiles{}, alpha, epsilon, max_iterations, stats, consume);
+}
+
+// Every graph index of a call (its requests, or its visitors) names a member.  *out_bad: the position of the first that does not
+int32_t sg_pool_graph_indices(const locrec_sg_pool *pool, int64_t n, const int32_t *graph_index, int64_t *out_bad)
+{
+    const int32_t ng = (int32_t)pool->graphs.size();
+    for (int64_t i = 0; i < n; ++i)
+        if (graph_index[i] < 0 || graph_index[i] >= ng) {
+            if (out_bad) *out_bad = i;
+            return fail(LOCREC_E_INVALID_ARG, "request %lld names graph %d: the pool holds graphs 0 .. %d", (long long)i,
+                        graph_index[i], ng - 1);
+        }
+    return LOCREC_OK;
+}
+
 // Every graph index, then isVertexExist (:70-77) for every request, before any device work: the members' distinct
 // targets, the members with requests (`act`, in order of appearance) and request -> its entry of its member's uniq.  On a
 // refusal nothing is written but *out_bad_request (when given): the position of the first offending request; else -1.
@@ -385,12 +435,7 @@ int32_t sg_pool_requests(const locrec_sg_pool *pool, int64_t n_requests, const i
                          int64_t *out_bad_request)
 {
     const int32_t ng = (int32_t)pool->graphs.size();
-    for (int64_t i = 0; i < n_requests; ++i)
-        if (graph_index[i] < 0 || graph_index[i] >= ng) {
-            if (out_bad_request) *out_bad_request = i;
-            return fail(LOCREC_E_INVALID_ARG, "request %lld names graph %d: the pool holds graphs 0 .. %d", (long long)i,
-                        graph_index[i], ng - 1);
-        }
+    LOCREC_TRY(sg_pool_graph_indices(pool, n_requests, graph_index, out_bad_request));
     mem = std::vector<SgPoolMember>((size_t)ng);
     act.clear();
     uniq_of.assign((size_t)n_requests, 0);
@@ -456,6 +501,42 @@ int32_t sg_pool_end_call(locrec_sg_pool *pool, const std::vector<int32_t> &act, 
     return LOCREC_OK;
 }
 
+// A wave's read-back for the unranked entries: one pack launch and one synchronisation for all its graphs, then the rows
+// of every member's columns.  own: the plain-copy path's images.
+template <class Tiles>
+int32_t sg_pool_read_back(locrec_sg_pool *pool, const SgPoolWave &w, std::vector<SgPoolMember> &mem, Tiles &&tp, double eps2,
+                          int64_t max_iterations, SgPoolStats &stats, std::vector<unsigned char> &own)
+{
+    hipStream_t s = pool->stream;
+    const bool packed = !pool->no_pack && pool->h_pack_dev != nullptr;
+    const unsigned nw = (unsigned)w.members.size();
+    const unsigned char *host = nullptr;
+    if (packed && pool->h_pack_bytes >= w.pack_bytes) {
+        hipLaunchKernelGGL(sg_pack_pool, dim3(w.pack_blocks, nw), dim3(256), 0, s, w.tiles_dev, pool->h_pack_dev);
+        LOCREC_HIP_TRY(hipStreamSynchronize(s));
+        host = pool->h_pack;
+    } else {
+        own.resize(w.pack_bytes);
+        for (unsigned j = 0; j < nw; ++j)
+            LOCREC_TRY(sg_batch_copy_enqueue(pool->graphs[(size_t)w.members[j]], s, own.data() + w.tiles[j].pack_off,
+                                             mem[(size_t)w.members[j]].both));
+        LOCREC_HIP_TRY(hipStreamSynchronize(s));
+        for (unsigned j = 0; j < nw; ++j)
+            sg_batch_copy_assemble(pool->graphs[(size_t)w.members[j]]->nlive, own.data() + w.tiles[j].pack_off,
+                                   mem[(size_t)w.members[j]].both);
+        host = own.data();
+    }
+    LOCREC_HIP_TRY(hipGetLastError());
+    stats.readback_bytes += (int64_t)w.pack_bytes;
+    for (unsigned j = 0; j < nw; ++j) {
+        locrec_sg_graph *g = pool->graphs[(size_t)w.members[j]];
+        SgPoolMember &m = mem[(size_t)w.members[j]];
+        LOCREC_TRY(sg_batch_host_rows(g, host + w.tiles[j].pack_off, m.uniq, w.k * (size_t)tp.tile_max(g), w.nb[j], eps2,
+                                      max_iterations, m.res));
+    }
+    return LOCREC_OK;
+}
+
 }  // namespace
 
 extern "C" int32_t locrec_sg_pool_recommend_batch(locrec_sg_pool *pool, int64_t n_requests, const int32_t *graph_index,
@@ -481,38 +562,10 @@ extern "C" int32_t locrec_sg_pool_recommend_batch(locrec_sg_pool *pool, int64_t 
     if (max_iterations > INT32_MAX) max_iterations = INT32_MAX;
     LOCREC_TRY(sg_pool_begin_call(pool, act, mem));
     for (const int32_t gi : act) mem[(size_t)gi].res.resize(mem[(size_t)gi].uniq.size());
-    hipStream_t s = pool->stream;
     const double eps2 = epsilon * epsilon;  // :40
-    const bool packed = !pool->no_pack && pool->h_pack_dev != nullptr;
     std::vector<unsigned char> own;  // the plain-copy path's images
-    // the wave's read-back: one pack launch and one synchronisation for all its graphs
     auto read_back = [&](const SgPoolWave &w) -> int32_t {
-        const unsigned nw = (unsigned)w.members.size();
-        const unsigned char *host = nullptr;
-        if (packed && pool->h_pack_bytes >= w.pack_bytes) {
-            hipLaunchKernelGGL(sg_pack_pool, dim3(w.pack_blocks, nw), dim3(256), 0, s, w.tiles_dev, pool->h_pack_dev);
-            LOCREC_HIP_TRY(hipStreamSynchronize(s));
-            host = pool->h_pack;
-        } else {
-            own.resize(w.pack_bytes);
-            for (unsigned j = 0; j < nw; ++j)
-                LOCREC_TRY(sg_batch_copy_enqueue(pool->graphs[(size_t)w.members[j]], s, own.data() + w.tiles[j].pack_off,
-                                                 mem[(size_t)w.members[j]].both));
-            LOCREC_HIP_TRY(hipStreamSynchronize(s));
-            for (unsigned j = 0; j < nw; ++j)
-                sg_batch_copy_assemble(pool->graphs[(size_t)w.members[j]]->nlive, own.data() + w.tiles[j].pack_off,
-                                       mem[(size_t)w.members[j]].both);
-            host = own.data();
-        }
-        LOCREC_HIP_TRY(hipGetLastError());
-        stats.readback_bytes += (int64_t)w.pack_bytes;
-        for (unsigned j = 0; j < nw; ++j) {
-            locrec_sg_graph *g = pool->graphs[(size_t)w.members[j]];
-            SgPoolMember &m = mem[(size_t)w.members[j]];
-            LOCREC_TRY(sg_batch_host_rows(g, host + w.tiles[j].pack_off, m.uniq, w.k * (size_t)sg_batch_tile_max(g), w.nb[j], eps2,
-                                          max_iterations, m.res));
-        }
-        return LOCREC_OK;
+        return sg_pool_read_back(pool, w, mem, SgPoolPersonTiles{}, eps2, max_iterations, stats, own);
     };
     const int32_t status = sg_pool_waves(pool, act, mem, alpha, epsilon, max_iterations, stats, read_back);
     LOCREC_TRY(sg_pool_end_call(pool, act, mem, status));

@@ -3,6 +3,7 @@
 // behind sg_ranked.h and sg_pool.h: the sweeps, finalizes, set-up, polls and the restore launch are sg_pool_waves', the
 // emit, state, membership and popcount bodies and the host's SgRkCall are sg_ranked.h's - per column and per request the order
 // of operations is the ranked batch's, so request i equals locrec_sg_recommend_ranked_batch on its member alone bit for bit.
+// The entry's body behind its checks is sg_pool_ranked_columns, which the pool's visitors entry (sg_pool_visitors.h) runs too.
 //
 //   emit rows       per member with requests its own numbering (sg_rk_rows): sorted ids, their emit rows and eid, kept
 //                   resident by the pool per member and numbering (with / without the source-only vertices), built at the
@@ -156,6 +157,205 @@ struct SgRkPoolActive {
 
 inline size_t rk_units(size_t bytes) { return (bytes + 7) / 8; }  // 8-byte units
 
+// The ranked pool behind its checks and sg_pool_begin_call, for n >= 1 positions over the columns `tp` runs: position i asks
+// member graph_index[i] for its column uniq_of[i], whose target vertex is mem[..].uniq[..] (-1: a visitor, which is no
+// vertex and so never a row of its own result).  with_lists: position i leaves out excluded_ids[excluded_offsets[i] ..
+// excluded_offsets[i + 1]) (host arrays, checked).  ps: the waves' counters.
+template <class Tiles>
+int32_t sg_pool_ranked_columns(locrec_sg_pool *pool, SgRkPoolStats &stats, SgPoolStats &ps, const std::vector<int32_t> &act,
+                               std::vector<SgPoolMember> &mem, const int64_t n, const int32_t *graph_index,
+                               const std::vector<int32_t> &uniq_of, Tiles &&tp, double alpha, double epsilon, int64_t max_iterations,
+                               int64_t N, int64_t n_places, const int64_t *place_ids, const int64_t *place_region_ids,
+                               const int64_t *target_region_ids, bool with_lists, const int64_t *excluded_offsets, int64_t n_excluded,
+                               const int64_t *excluded_ids, int64_t *out_ids, double *out_probabilities, int64_t *out_counts,
+                               int64_t *out_row_counts, int64_t *out_iterations, int32_t *out_converged)
+{
+    hipStream_t s = pool->stream;
+    const size_t na = act.size();
+    const double eps2 = epsilon * epsilon;  // :40
+    auto row_of = [](const locrec_sg_graph *g, const SgRkRows &rows, int32_t tv) { return tv < 0 ? -1 : sg_rk_row_of(g, rows, tv); };
+    // ---- the members with requests: their emit rows, the distinct regions asked of each, the (member, region) pairs
+    const bool dead_rows = sg_rk_dead_rows(alpha, max_iterations);
+    std::vector<SgRkPoolActive> am(na);
+    std::vector<int32_t> act_of(pool->graphs.size(), -1);
+    std::vector<size_t> nu(na);
+    std::vector<int> tile_max(na);
+    for (size_t a = 0; a < na; ++a) {
+        SgRkPoolActive &x = am[a];
+        x.gi = act[a];
+        act_of[(size_t)x.gi] = (int32_t)a;
+        LOCREC_TRY(sg_rk_pool_image(pool, x.gi, dead_rows, s, x.im));
+        x.words = std::max<int64_t>(1, (x.im->rows.m + 63) / 64);
+        x.tile_max = tile_max[a] = tp.tile_max(pool->graphs[(size_t)x.gi]);
+        nu[a] = mem[(size_t)x.gi].uniq.size();
+    }
+    std::vector<int32_t> member_of((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        member_of[(size_t)i] = act_of[(size_t)graph_index[i]];
+        am[(size_t)member_of[(size_t)i]].regions.push_back(target_region_ids[i]);
+    }
+    size_t P = 0, bit_words = 0;
+    for (SgRkPoolActive &x : am) {
+        std::sort(x.regions.begin(), x.regions.end());
+        x.regions.erase(std::unique(x.regions.begin(), x.regions.end()), x.regions.end());
+        x.pair_base = P;
+        x.bits_off = bit_words;
+        P += x.regions.size();
+        bit_words += x.regions.size() * (size_t)x.words;
+    }
+
+    // ---- the requests in emit order
+    SgRkPoolOrder order;
+    sg_rk_pool_order(nu, tile_max, member_of, uniq_of, order);
+    const size_t NU = order.ubase[na];
+    std::vector<int32_t> req((size_t)(3 * n));  // column, target's emit row, bitmap (among its member's)
+    std::vector<int32_t> pair_k((size_t)n);
+    for (int64_t k = 0; k < n; ++k) {
+        const int64_t i = order.ord[(size_t)k];
+        const SgRkPoolActive &x = am[(size_t)member_of[(size_t)i]];
+        const int32_t u = uniq_of[(size_t)i];
+        const size_t r = (size_t)(std::lower_bound(x.regions.begin(), x.regions.end(), target_region_ids[i]) - x.regions.begin());
+        req[(size_t)k] = u % x.tile_max;
+        req[(size_t)(n + k)] = row_of(pool->graphs[(size_t)x.gi], x.im->rows, mem[(size_t)x.gi].uniq[(size_t)u]);
+        req[(size_t)(2 * n + k)] = (int32_t)r;
+        pair_k[(size_t)k] = (int32_t)(x.pair_base + r);
+    }
+
+    // ---- device buffers.  d64, in 8-byte units; the head is ONE upload:
+    //   place ids, place regions | the members' regions | targets | pairs | member table | requests ||
+    //   seg_begin | seg_len | col_rows | caps
+    const size_t u_pid = 0, u_preg = u_pid + (size_t)n_places, u_regions = u_preg + (size_t)n_places, u_tgt = u_regions + P,
+                 u_pairs = u_tgt + (size_t)n, u_memtab = u_pairs + rk_units(P * sizeof(SgRkPoolPair)),
+                 u_req = u_memtab + rk_units(na * sizeof(SgRkPoolMembers)), u_head = u_req + rk_units((size_t)(3 * n) * 4),
+                 u_seg_begin = u_head, u_seg_len = u_seg_begin + (size_t)n, u_col_rows = u_seg_len + (size_t)n,
+                 u_caps = u_col_rows + NU, u_end = u_caps + P;
+    DevBuf<int64_t> d64;
+    DevBuf<unsigned long long> d_bits;
+    LOCREC_TRY(d64.alloc(u_end));
+    LOCREC_TRY(d_bits.alloc(bit_words));
+    int64_t *d_pid = d64.p + u_pid, *d_preg = d64.p + u_preg, *d_regions = d64.p + u_regions, *d_tgt = d64.p + u_tgt,
+            *d_seg_begin = d64.p + u_seg_begin, *d_seg_len = d64.p + u_seg_len, *d_col_rows = d64.p + u_col_rows,
+            *d_caps = d64.p + u_caps;
+    const SgRkPoolPair *d_pairs = reinterpret_cast<const SgRkPoolPair *>(d64.p + u_pairs);
+    const SgRkPoolMembers *d_memtab = reinterpret_cast<const SgRkPoolMembers *>(d64.p + u_memtab);
+    const int32_t *d_req = reinterpret_cast<const int32_t *>(d64.p + u_req);
+    std::vector<int64_t> head(u_head, 0);
+    if (n_places > 0) {
+        std::copy(place_ids, place_ids + n_places, head.begin() + (ptrdiff_t)u_pid);
+        std::copy(place_region_ids, place_region_ids + n_places, head.begin() + (ptrdiff_t)u_preg);
+    }
+    {
+        SgRkPoolPair *pairs = reinterpret_cast<SgRkPoolPair *>(head.data() + u_pairs);
+        SgRkPoolMembers *memtab = reinterpret_cast<SgRkPoolMembers *>(head.data() + u_memtab);
+        for (size_t a = 0; a < na; ++a) {
+            const SgRkPoolActive &x = am[a];
+            std::copy(x.regions.begin(), x.regions.end(), head.begin() + (ptrdiff_t)(u_regions + x.pair_base));
+            for (size_t r = 0; r < x.regions.size(); ++r)
+                pairs[x.pair_base + r] = SgRkPoolPair{(int64_t)(x.bits_off + r * (size_t)x.words), x.words};
+            memtab[a] = SgRkPoolMembers{x.im->ids.p, x.im->srow.p, d_regions + x.pair_base, d_bits.p + x.bits_off, x.im->rows.m,
+                                        (int64_t)x.regions.size(), x.words};
+        }
+        for (int64_t k = 0; k < n; ++k) head[u_tgt + (size_t)k] = target_region_ids[order.ord[(size_t)k]];
+        std::memcpy(head.data() + u_req, req.data(), req.size() * 4);
+    }
+    LOCREC_HIP_TRY(hipMemcpyAsync(d64.p, head.data(), u_head * 8, hipMemcpyHostToDevice, s));
+    LOCREC_HIP_TRY(hipMemsetAsync(d_seg_len, 0, ((size_t)n + NU) * 8, s));  // the segments' lengths and the columns' rows
+    LOCREC_HIP_TRY(hipMemsetAsync(d_bits.p, 0, std::max<size_t>(bit_words, 1) * 8, s));
+    if (n_places > 0)
+        hipLaunchKernelGGL(sg_rk_members_pool, dim3(rk_grid(n_places).x, (unsigned)na), dim3(kRkThreads), 0, s, n_places, d_pid,
+                           d_preg, d_memtab);
+    hipLaunchKernelGGL(sg_rk_popcount_pool, dim3((unsigned)P), dim3(kRkThreads), 0, s, d_pairs, d_bits.p,
+                       reinterpret_cast<unsigned long long *>(d_caps));
+
+    // ---- the groups (request k's room: its pair's cap); a wave's row table has a row per member and group part
+    SgRkCall rc{.stats = stats, .s = s, .n = n, .N = N, .n_places = n_places, .d_pid = d_pid, .d_preg = d_preg, .d_tgt = d_tgt,
+                .d_seg_begin = d_seg_begin, .d_seg_len = d_seg_len};
+    LOCREC_TRY(rc.plan(d_caps, P, pair_k.data(), NU));
+    const std::vector<int64_t> &group_end = rc.groups.group_end;
+    DevBuf<int64_t> d_ex;
+    if (with_lists) LOCREC_TRY(rc.upload_lists(order.ord, excluded_offsets, n_excluded, excluded_ids, d_ex));
+    DevBuf<unsigned char> d_state, d_tab;
+    LOCREC_TRY(d_tab.alloc(sg_rk_pool_table_rows(nu, tile_max, order, group_end) * sizeof(SgRkPoolRow)));
+    const bool pinned = !pool->no_pack && pool->h_pack_dev != nullptr && pool->h_pack_bytes >= na * kRkPoolStateStride;
+    if (!pinned) LOCREC_TRY(d_state.alloc(na * kRkPoolStateStride));
+    std::vector<unsigned char> own_state(pinned ? 0 : na * kRkPoolStateStride);
+
+    std::vector<SgRkPoolRow> tab;  // the wave's rows: part p's at tab[p * nw ..)
+    std::vector<int64_t> cuts;
+    std::vector<size_t> present;  // the wave's members, as positions of act
+    auto emit_and_rank = [&](const SgPoolWave &w) -> int32_t {
+        const unsigned nw = (unsigned)w.members.size();
+        stats.tiles += nw;
+        // the wave's requests are one run of the emit order; the groups that end inside it cut it into parts
+        unsigned emit_blocks = 1;
+        present.clear();
+        for (const int32_t gi : w.members) {
+            present.push_back((size_t)act_of[(size_t)gi]);
+            emit_blocks = std::max(emit_blocks, (unsigned)((am[present.back()].im->rows.m + kRkThreads - 1) / kRkThreads));
+        }
+        sg_rk_wave_cuts(present, w.k, tile_max, order, group_end, cuts);
+        const size_t parts = cuts.size() - 1;
+        tab.assign(parts * nw, SgRkPoolRow{});
+        for (unsigned j = 0; j < nw; ++j) {
+            const size_t a = present[j];
+            const SgRkPoolActive &x = am[a];
+            const locrec_sg_graph *g = pool->graphs[(size_t)x.gi];
+            const std::vector<int32_t> &uniq = mem[(size_t)x.gi].uniq;
+            const size_t t0 = w.k * (size_t)x.tile_max;
+            SgRkPoolRow row{};
+            row.tl.nb = w.nb[j];
+            row.tl.T = g->nlive;
+            row.tl.ne = (int32_t)x.im->rows.m;
+            row.tl.xstride = w.tiles[j].xstride;
+            for (int c = 0; c < kBatchB; ++c)
+                row.tl.col_trow[c] = c < w.nb[j] ? row_of(g, x.im->rows, uniq[t0 + (size_t)c]) : -1;
+            row.st = w.tiles[j].st;
+            row.xbuf = w.tiles[j].xbuf;
+            row.parts = w.tiles[j].parts;
+            row.eid = x.im->ids.p + x.im->rows.m;
+            row.bits = d_bits.p + x.bits_off;
+            row.col_rows = reinterpret_cast<unsigned long long *>(d_col_rows) + order.ubase[a] + t0;
+            row.words = x.words;
+            row.state_off = (int64_t)(j * kRkPoolStateStride);
+            const int64_t tb = order.tile_begin(a, w.k, x.tile_max), te = order.tile_end(a, w.k, x.tile_max);
+            for (size_t p = 0; p < parts; ++p) {
+                row.tl.count_cols = p == 0 ? 1 : 0;
+                row.k0 = (int32_t)std::min(std::max(tb, cuts[p]), te);
+                row.k1 = (int32_t)std::max(std::min(te, cuts[p + 1]), (int64_t)row.k0);
+                tab[p * nw + j] = row;
+            }
+        }
+        LOCREC_HIP_TRY(hipMemcpyAsync(d_tab.p, tab.data(), tab.size() * sizeof(SgRkPoolRow), hipMemcpyHostToDevice, s));
+        const SgRkPoolRow *d_rows_tab = reinterpret_cast<const SgRkPoolRow *>(d_tab.p);
+        // the states first: they do not wait for the emit
+        hipLaunchKernelGGL(sg_rk_state_pool, dim3(nw), dim3(64 * kBatchB), 0, s, d_rows_tab, pinned ? pool->h_pack_dev : d_state.p);
+        if (!pinned)
+            LOCREC_HIP_TRY(hipMemcpyAsync(own_state.data(), d_state.p, nw * kRkPoolStateStride, hipMemcpyDeviceToHost, s));
+        for (size_t p = 0; p < parts; ++p) {
+            hipLaunchKernelGGL(sg_rk_emit_pool, dim3(emit_blocks, nw), dim3(kRkThreads), 0, s, d_rows_tab + p * nw, d_req, d_req + n,
+                               d_req + 2 * n, d_seg_begin, reinterpret_cast<unsigned long long *>(d_seg_len), rc.groups.max_rows,
+                               rc.d_row_ids, rc.d_row_probs);
+            ++stats.emit_launches;
+            if (cuts[p + 1] == group_end[rc.group]) LOCREC_TRY(rc.flush_group());
+        }
+        LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (also: nothing reads the wave's tables any more)
+        LOCREC_HIP_TRY(hipGetLastError());
+        ++stats.host_syncs;
+        stats.readback_bytes += (int64_t)(nw * kRkStateBytes);
+        const unsigned char *host = pinned ? pool->h_pack : own_state.data();
+        for (unsigned j = 0; j < nw; ++j) {
+            const size_t f = order.ubase[present[j]] + w.k * (size_t)tile_max[present[j]];  // the tile's first column
+            LOCREC_TRY(sg_rk_verdicts(host + j * kRkPoolStateStride, w.nb[j], eps2, max_iterations, &rc.res_it[f], &rc.res_conv[f]));
+        }
+        return LOCREC_OK;
+    };
+    const int32_t status = sg_pool_waves_of(pool, act, mem, tp, alpha, epsilon, max_iterations, ps, emit_and_rank);
+    stats.tile_waves = ps.tile_waves;
+    stats.rounds = ps.rounds;
+    return rc.finish(status, ps.polls, order, member_of, uniq_of, out_ids, out_probabilities, out_counts, out_row_counts,
+                     out_iterations, out_converged);
+}
+
 }  // namespace
 
 extern "C" int32_t locrec_sg_pool_recommend_ranked_batch(
@@ -178,193 +378,12 @@ extern "C" int32_t locrec_sg_pool_recommend_ranked_batch(
     if (n_requests == 0) return LOCREC_OK;
     if (max_iterations > INT32_MAX) max_iterations = INT32_MAX;
     LOCREC_TRY(sg_pool_begin_call(pool, act, mem));  // (sorts act: member order)
-    hipStream_t s = pool->stream;
-    const int64_t n = n_requests;
-    const size_t na = act.size();
-    const double eps2 = epsilon * epsilon;  // :40
     // from here on the members' slots are the call's: whatever happens, sg_pool_end_call gives them back
-    auto run = [&]() -> int32_t {
-        // ---- the members with requests: their emit rows, the distinct regions asked of each, the (member, region) pairs
-        const bool dead_rows = sg_rk_dead_rows(alpha, max_iterations);
-        std::vector<SgRkPoolActive> am(na);
-        std::vector<int32_t> act_of(pool->graphs.size(), -1);
-        std::vector<size_t> nu(na);
-        std::vector<int> tile_max(na);
-        for (size_t a = 0; a < na; ++a) {
-            SgRkPoolActive &x = am[a];
-            x.gi = act[a];
-            act_of[(size_t)x.gi] = (int32_t)a;
-            LOCREC_TRY(sg_rk_pool_image(pool, x.gi, dead_rows, s, x.im));
-            x.words = std::max<int64_t>(1, (x.im->rows.m + 63) / 64);
-            x.tile_max = tile_max[a] = sg_batch_tile_max(pool->graphs[(size_t)x.gi]);
-            nu[a] = mem[(size_t)x.gi].uniq.size();
-        }
-        std::vector<int32_t> member_of((size_t)n);
-        for (int64_t i = 0; i < n; ++i) {
-            member_of[(size_t)i] = act_of[(size_t)graph_index[i]];
-            am[(size_t)member_of[(size_t)i]].regions.push_back(target_region_ids[i]);
-        }
-        size_t P = 0, bit_words = 0;
-        for (SgRkPoolActive &x : am) {
-            std::sort(x.regions.begin(), x.regions.end());
-            x.regions.erase(std::unique(x.regions.begin(), x.regions.end()), x.regions.end());
-            x.pair_base = P;
-            x.bits_off = bit_words;
-            P += x.regions.size();
-            bit_words += x.regions.size() * (size_t)x.words;
-        }
-
-        // ---- the requests in emit order
-        SgRkPoolOrder order;
-        sg_rk_pool_order(nu, tile_max, member_of, uniq_of, order);
-        const size_t NU = order.ubase[na];
-        std::vector<int32_t> req((size_t)(3 * n));  // column, target's emit row, bitmap (among its member's)
-        std::vector<int32_t> pair_k((size_t)n);
-        for (int64_t k = 0; k < n; ++k) {
-            const int64_t i = order.ord[(size_t)k];
-            const SgRkPoolActive &x = am[(size_t)member_of[(size_t)i]];
-            const int32_t u = uniq_of[(size_t)i];
-            const size_t r = (size_t)(std::lower_bound(x.regions.begin(), x.regions.end(), target_region_ids[i]) - x.regions.begin());
-            req[(size_t)k] = u % x.tile_max;
-            req[(size_t)(n + k)] = sg_rk_row_of(pool->graphs[(size_t)x.gi], x.im->rows, mem[(size_t)x.gi].uniq[(size_t)u]);
-            req[(size_t)(2 * n + k)] = (int32_t)r;
-            pair_k[(size_t)k] = (int32_t)(x.pair_base + r);
-        }
-
-        // ---- device buffers.  d64, in 8-byte units; the head is ONE upload:
-        //   place ids, place regions | the members' regions | targets | pairs | member table | requests ||
-        //   seg_begin | seg_len | col_rows | caps
-        const size_t u_pid = 0, u_preg = u_pid + (size_t)n_places, u_regions = u_preg + (size_t)n_places, u_tgt = u_regions + P,
-                     u_pairs = u_tgt + (size_t)n, u_memtab = u_pairs + rk_units(P * sizeof(SgRkPoolPair)),
-                     u_req = u_memtab + rk_units(na * sizeof(SgRkPoolMembers)), u_head = u_req + rk_units((size_t)(3 * n) * 4),
-                     u_seg_begin = u_head, u_seg_len = u_seg_begin + (size_t)n, u_col_rows = u_seg_len + (size_t)n,
-                     u_caps = u_col_rows + NU, u_end = u_caps + P;
-        DevBuf<int64_t> d64;
-        DevBuf<unsigned long long> d_bits;
-        LOCREC_TRY(d64.alloc(u_end));
-        LOCREC_TRY(d_bits.alloc(bit_words));
-        int64_t *d_pid = d64.p + u_pid, *d_preg = d64.p + u_preg, *d_regions = d64.p + u_regions, *d_tgt = d64.p + u_tgt,
-                *d_seg_begin = d64.p + u_seg_begin, *d_seg_len = d64.p + u_seg_len, *d_col_rows = d64.p + u_col_rows,
-                *d_caps = d64.p + u_caps;
-        const SgRkPoolPair *d_pairs = reinterpret_cast<const SgRkPoolPair *>(d64.p + u_pairs);
-        const SgRkPoolMembers *d_memtab = reinterpret_cast<const SgRkPoolMembers *>(d64.p + u_memtab);
-        const int32_t *d_req = reinterpret_cast<const int32_t *>(d64.p + u_req);
-        std::vector<int64_t> head(u_head, 0);
-        if (n_places > 0) {
-            std::copy(place_ids, place_ids + n_places, head.begin() + (ptrdiff_t)u_pid);
-            std::copy(place_region_ids, place_region_ids + n_places, head.begin() + (ptrdiff_t)u_preg);
-        }
-        {
-            SgRkPoolPair *pairs = reinterpret_cast<SgRkPoolPair *>(head.data() + u_pairs);
-            SgRkPoolMembers *memtab = reinterpret_cast<SgRkPoolMembers *>(head.data() + u_memtab);
-            for (size_t a = 0; a < na; ++a) {
-                const SgRkPoolActive &x = am[a];
-                std::copy(x.regions.begin(), x.regions.end(), head.begin() + (ptrdiff_t)(u_regions + x.pair_base));
-                for (size_t r = 0; r < x.regions.size(); ++r)
-                    pairs[x.pair_base + r] = SgRkPoolPair{(int64_t)(x.bits_off + r * (size_t)x.words), x.words};
-                memtab[a] = SgRkPoolMembers{x.im->ids.p, x.im->srow.p, d_regions + x.pair_base, d_bits.p + x.bits_off, x.im->rows.m,
-                                            (int64_t)x.regions.size(), x.words};
-            }
-            for (int64_t k = 0; k < n; ++k) head[u_tgt + (size_t)k] = target_region_ids[order.ord[(size_t)k]];
-            std::memcpy(head.data() + u_req, req.data(), req.size() * 4);
-        }
-        LOCREC_HIP_TRY(hipMemcpyAsync(d64.p, head.data(), u_head * 8, hipMemcpyHostToDevice, s));
-        LOCREC_HIP_TRY(hipMemsetAsync(d_seg_len, 0, ((size_t)n + NU) * 8, s));  // the segments' lengths and the columns' rows
-        LOCREC_HIP_TRY(hipMemsetAsync(d_bits.p, 0, std::max<size_t>(bit_words, 1) * 8, s));
-        if (n_places > 0)
-            hipLaunchKernelGGL(sg_rk_members_pool, dim3(rk_grid(n_places).x, (unsigned)na), dim3(kRkThreads), 0, s, n_places, d_pid,
-                               d_preg, d_memtab);
-        hipLaunchKernelGGL(sg_rk_popcount_pool, dim3((unsigned)P), dim3(kRkThreads), 0, s, d_pairs, d_bits.p,
-                           reinterpret_cast<unsigned long long *>(d_caps));
-
-        // ---- the groups (request k's room: its pair's cap); a wave's row table has a row per member and group part
-        SgRkCall rc{.stats = stats, .s = s, .n = n, .N = N, .n_places = n_places, .d_pid = d_pid, .d_preg = d_preg, .d_tgt = d_tgt,
-                    .d_seg_begin = d_seg_begin, .d_seg_len = d_seg_len};
-        LOCREC_TRY(rc.plan(d_caps, P, pair_k.data(), NU));
-        const std::vector<int64_t> &group_end = rc.groups.group_end;
-        DevBuf<unsigned char> d_state, d_tab;
-        LOCREC_TRY(d_tab.alloc(sg_rk_pool_table_rows(nu, tile_max, order, group_end) * sizeof(SgRkPoolRow)));
-        const bool pinned = !pool->no_pack && pool->h_pack_dev != nullptr && pool->h_pack_bytes >= na * kRkPoolStateStride;
-        if (!pinned) LOCREC_TRY(d_state.alloc(na * kRkPoolStateStride));
-        std::vector<unsigned char> own_state(pinned ? 0 : na * kRkPoolStateStride);
-
-        std::vector<SgRkPoolRow> tab;  // the wave's rows: part p's at tab[p * nw ..)
-        std::vector<int64_t> cuts;
-        std::vector<size_t> present;  // the wave's members, as positions of act
-        auto emit_and_rank = [&](const SgPoolWave &w) -> int32_t {
-            const unsigned nw = (unsigned)w.members.size();
-            stats.tiles += nw;
-            // the wave's requests are one run of the emit order; the groups that end inside it cut it into parts
-            unsigned emit_blocks = 1;
-            present.clear();
-            for (const int32_t gi : w.members) {
-                present.push_back((size_t)act_of[(size_t)gi]);
-                emit_blocks = std::max(emit_blocks, (unsigned)((am[present.back()].im->rows.m + kRkThreads - 1) / kRkThreads));
-            }
-            sg_rk_wave_cuts(present, w.k, tile_max, order, group_end, cuts);
-            const size_t parts = cuts.size() - 1;
-            tab.assign(parts * nw, SgRkPoolRow{});
-            for (unsigned j = 0; j < nw; ++j) {
-                const size_t a = present[j];
-                const SgRkPoolActive &x = am[a];
-                const locrec_sg_graph *g = pool->graphs[(size_t)x.gi];
-                const std::vector<int32_t> &uniq = mem[(size_t)x.gi].uniq;
-                const size_t t0 = w.k * (size_t)x.tile_max;
-                SgRkPoolRow row{};
-                row.tl.nb = w.nb[j];
-                row.tl.T = g->nlive;
-                row.tl.ne = (int32_t)x.im->rows.m;
-                row.tl.xstride = w.tiles[j].xstride;
-                for (int c = 0; c < kBatchB; ++c)
-                    row.tl.col_trow[c] = c < w.nb[j] ? sg_rk_row_of(g, x.im->rows, uniq[t0 + (size_t)c]) : -1;
-                row.st = w.tiles[j].st;
-                row.xbuf = w.tiles[j].xbuf;
-                row.parts = w.tiles[j].parts;
-                row.eid = x.im->ids.p + x.im->rows.m;
-                row.bits = d_bits.p + x.bits_off;
-                row.col_rows = reinterpret_cast<unsigned long long *>(d_col_rows) + order.ubase[a] + t0;
-                row.words = x.words;
-                row.state_off = (int64_t)(j * kRkPoolStateStride);
-                const int64_t tb = order.tile_begin(a, w.k, x.tile_max), te = order.tile_end(a, w.k, x.tile_max);
-                for (size_t p = 0; p < parts; ++p) {
-                    row.tl.count_cols = p == 0 ? 1 : 0;
-                    row.k0 = (int32_t)std::min(std::max(tb, cuts[p]), te);
-                    row.k1 = (int32_t)std::max(std::min(te, cuts[p + 1]), (int64_t)row.k0);
-                    tab[p * nw + j] = row;
-                }
-            }
-            LOCREC_HIP_TRY(hipMemcpyAsync(d_tab.p, tab.data(), tab.size() * sizeof(SgRkPoolRow), hipMemcpyHostToDevice, s));
-            const SgRkPoolRow *d_rows_tab = reinterpret_cast<const SgRkPoolRow *>(d_tab.p);
-            // the states first: they do not wait for the emit
-            hipLaunchKernelGGL(sg_rk_state_pool, dim3(nw), dim3(64 * kBatchB), 0, s, d_rows_tab, pinned ? pool->h_pack_dev : d_state.p);
-            if (!pinned)
-                LOCREC_HIP_TRY(hipMemcpyAsync(own_state.data(), d_state.p, nw * kRkPoolStateStride, hipMemcpyDeviceToHost, s));
-            for (size_t p = 0; p < parts; ++p) {
-                hipLaunchKernelGGL(sg_rk_emit_pool, dim3(emit_blocks, nw), dim3(kRkThreads), 0, s, d_rows_tab + p * nw, d_req, d_req + n,
-                                   d_req + 2 * n, d_seg_begin, reinterpret_cast<unsigned long long *>(d_seg_len), rc.groups.max_rows,
-                                   rc.d_row_ids, rc.d_row_probs);
-                ++stats.emit_launches;
-                if (cuts[p + 1] == group_end[rc.group]) LOCREC_TRY(rc.flush_group());
-            }
-            LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (also: nothing reads the wave's tables any more)
-            LOCREC_HIP_TRY(hipGetLastError());
-            ++stats.host_syncs;
-            stats.readback_bytes += (int64_t)(nw * kRkStateBytes);
-            const unsigned char *host = pinned ? pool->h_pack : own_state.data();
-            for (unsigned j = 0; j < nw; ++j) {
-                const size_t f = order.ubase[present[j]] + w.k * (size_t)tile_max[present[j]];  // the tile's first column
-                LOCREC_TRY(sg_rk_verdicts(host + j * kRkPoolStateStride, w.nb[j], eps2, max_iterations, &rc.res_it[f], &rc.res_conv[f]));
-            }
-            return LOCREC_OK;
-        };
-        SgPoolStats ps;
-        const int32_t status = sg_pool_waves(pool, act, mem, alpha, epsilon, max_iterations, ps, emit_and_rank);
-        stats.tile_waves = ps.tile_waves;
-        stats.rounds = ps.rounds;
-        return rc.finish(status, ps.polls, order, member_of, uniq_of, out_ids, out_probabilities, out_counts, out_row_counts,
-                         out_iterations, out_converged);
-    };
-    const int32_t status = run();
+    SgPoolStats ps;
+    const int32_t status = sg_pool_ranked_columns(pool, stats, ps, act, mem, n_requests, graph_index, uniq_of, SgPoolPersonTiles{}, alpha,
+                                                  epsilon, max_iterations, N, n_places, place_ids, place_region_ids, target_region_ids,
+                                                  false, nullptr, 0, nullptr, out_ids, out_probabilities, out_counts, out_row_counts,
+                                                  out_iterations, out_converged);
     // (a failed run may have left launches in flight that read the call's buffers, freed at run's end by hipFree, which
     // waits for the device)
     return sg_pool_end_call(pool, act, mem, status);

@@ -349,6 +349,7 @@ struct SgRkCall {
     std::vector<int64_t> h_oid, h_cnt, res_it;  // the ranked rows in emit order; res_*: per distinct target, flat
     std::vector<double> h_osc;
     std::vector<int32_t> res_conv;
+    std::vector<int64_t> h_ex;  // the lists' begins and lengths in emit order, as uploaded
 
     // Reads the n_caps caps back and forms the groups: request k's segment has room caps[cap_of[k]], a group's segments
     // share the row buffer.  nu: distinct targets.
@@ -374,6 +375,29 @@ struct SgRkCall {
         h_cnt.assign((size_t)n, 0);
         res_it.resize(nu);
         res_conv.resize(nu);
+        return LOCREC_OK;
+    }
+
+    // The exclusion lists, uploaded once into d_ex (which outlives the call's launches): begins and lengths in emit order
+    // (ord: emit position -> input position), then the ids
+    int32_t upload_lists(const std::vector<int64_t> &ord, const int64_t *excluded_offsets, int64_t n_excluded,
+                         const int64_t *excluded_ids, DevBuf<int64_t> &d_ex)
+    {
+        std::vector<int64_t> &xr = h_ex;  // (lives as long as the call: the copy below may read it later)
+        xr.resize((size_t)(2 * n));
+        for (int64_t k = 0; k < n; ++k) {
+            const int64_t i = ord[(size_t)k];
+            xr[(size_t)k] = excluded_offsets[i];
+            xr[(size_t)(n + k)] = excluded_offsets[i + 1] - excluded_offsets[i];
+        }
+        LOCREC_TRY(d_ex.alloc((size_t)(2 * n + n_excluded)));
+        LOCREC_HIP_TRY(hipMemcpyAsync(d_ex.p, xr.data(), (size_t)(2 * n) * 8, hipMemcpyHostToDevice, s));
+        if (n_excluded > 0)
+            LOCREC_HIP_TRY(hipMemcpyAsync(d_ex.p + 2 * n, excluded_ids, (size_t)n_excluded * 8, hipMemcpyHostToDevice, s));
+        d_ex_begin = d_ex.p;
+        d_ex_len = d_ex.p + n;
+        d_ex_ids = d_ex.p + 2 * n;
+        n_ex = n_excluded;
         return LOCREC_OK;
     }
 
@@ -568,24 +592,8 @@ int32_t sg_ranked_batch_columns(locrec_sg_graph *g, SgRankedStats &stats, int64_
     SgRkCall rc{.stats = stats, .s = s, .n = n, .N = N, .n_places = n_places, .d_pid = d_pid, .d_preg = d_preg, .d_tgt = d_tgt,
                 .d_seg_begin = d_seg_begin, .d_seg_len = d_seg_len};
     LOCREC_TRY(rc.plan(d_caps, (size_t)R, req.data() + 2 * n, nu));
-    DevBuf<int64_t> d_ex;  // the lists, uploaded once: begins and lengths in emit order, then the ids
-    std::vector<int64_t> xr;
-    if (with_lists) {
-        xr.resize((size_t)(2 * n));
-        for (int64_t k = 0; k < n; ++k) {
-            const int64_t i = ord[(size_t)k];
-            xr[(size_t)k] = excluded_offsets[i];
-            xr[(size_t)(n + k)] = excluded_offsets[i + 1] - excluded_offsets[i];
-        }
-        LOCREC_TRY(d_ex.alloc((size_t)(2 * n + n_excluded)));
-        LOCREC_HIP_TRY(hipMemcpyAsync(d_ex.p, xr.data(), (size_t)(2 * n) * 8, hipMemcpyHostToDevice, s));
-        if (n_excluded > 0)
-            LOCREC_HIP_TRY(hipMemcpyAsync(d_ex.p + 2 * n, excluded_ids, (size_t)n_excluded * 8, hipMemcpyHostToDevice, s));
-        rc.d_ex_begin = d_ex.p;
-        rc.d_ex_len = d_ex.p + n;
-        rc.d_ex_ids = d_ex.p + 2 * n;
-        rc.n_ex = n_excluded;
-    }
+    DevBuf<int64_t> d_ex;  // the lists
+    if (with_lists) LOCREC_TRY(rc.upload_lists(ord, excluded_offsets, n_excluded, excluded_ids, d_ex));
     DevBuf<unsigned char> d_state;
     LOCREC_TRY(d_state.alloc(kRkStateBytes));
 

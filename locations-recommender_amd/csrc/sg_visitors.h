@@ -50,8 +50,8 @@ struct SgVisSetUp {
     int32_t lines;   // this tile's weight lines
 };
 
-// one block: the edges of a tile are a few hundred
-__global__ __launch_bounds__(256) void sg_vis_set_up(const SgVisSetUp a)
+// one block: the edges of a tile are a few hundred.  sg_vis_set_up_pool (sg_pool_visitors.h) runs the same body per member.
+__device__ __forceinline__ void sg_vis_set_up_body(const SgVisSetUp &a)
 {
     for (int i = a.p0 + (int)threadIdx.x; i < a.p1; i += 256) a.slot[a.e_row[i]] = -1;
     for (int i = (int)threadIdx.x; i < a.lines * kBatchB; i += 256) a.w[i] = 0.0;
@@ -63,6 +63,8 @@ __global__ __launch_bounds__(256) void sg_vis_set_up(const SgVisSetUp a)
     }
 }
 
+__global__ __launch_bounds__(256) void sg_vis_set_up(const SgVisSetUp a) { sg_vis_set_up_body(a); }
+
 __global__ __launch_bounds__(256) void sg_finalize_visitors(
     const SgBatchReq rq, int32_t n_short, const int4 *__restrict__ lrows, int32_t nlrows, int32_t n_crows,
     const double *__restrict__ partial, const double *__restrict__ x_in, double *__restrict__ x_out,
@@ -70,6 +72,71 @@ __global__ __launch_bounds__(256) void sg_finalize_visitors(
 {
     sg_finalize_batch_body<true>(rq, (int)blockIdx.x, n_short, lrows, nlrows, n_crows, partial, x_in, x_out, parts_prev, parts_out,
                                  st, first, vt);
+}
+
+// The shape of a visitors call's CSR and the constructor's two require()s (before any per-visitor check)
+int32_t sg_visitors_check_shape(int64_t nv, const int64_t *offsets, const int64_t *target_ids, const double *weights, double epsilon,
+                                int64_t max_iterations)
+{
+    if (nv < 0 || (nv > 0 && !offsets)) return fail(LOCREC_E_INVALID_ARG, "bad arguments");
+    if (nv > 0) {
+        bool ok = offsets[0] == 0;
+        for (int64_t v = 0; ok && v < nv; ++v) ok = offsets[v] <= offsets[v + 1];
+        if (!ok) return fail(LOCREC_E_INVALID_ARG, "edge_offsets must start at 0 and be non-decreasing");
+        if (offsets[nv] > kSgVisitorsMaxEdges) return fail(LOCREC_E_INVALID_ARG, "2^31 visitor edges or more");
+        if (offsets[nv] > 0 && (!target_ids || !weights)) return fail(LOCREC_E_INVALID_ARG, "null array");
+    }
+    return sg_batch_requires(epsilon, max_iterations);
+}
+
+// Visitor v of a call against the graph it is asked of: it has edges, every weight is finite, every target is a vertex
+// with a row of the layout, none is named twice.  live[e] <- the live row of every edge of v.
+int32_t sg_visitor_check(const locrec_sg_graph *g, int64_t v, const int64_t *offsets, const int64_t *target_ids, const double *weights,
+                         int32_t *live)
+{
+    if (offsets[v] == offsets[v + 1]) return fail(LOCREC_E_NOT_FOUND, "visitor %lld has no edges", (long long)v);
+    for (int64_t e = offsets[v]; e < offsets[v + 1]; ++e) {
+        if (!std::isfinite(weights[e]))
+            return fail(LOCREC_E_INVALID_ARG, "visitor %lld: the weight of its edge to %lld is not finite", (long long)v,
+                        (long long)target_ids[e]);
+        const int32_t tv = sg_vertex_index(g, target_ids[e]);
+        if (tv < 0) return fail(LOCREC_E_NOT_FOUND, "No such vertex in the graph: %lld", (long long)target_ids[e]);
+        if (g->live_of[tv] < 0)
+            return fail(LOCREC_E_INVALID_ARG, "visitor %lld: vertex %lld has no inbound edge in the graph (the layout has no row for it)",
+                        (long long)v, (long long)target_ids[e]);
+        live[(size_t)e] = g->live_of[tv];
+    }
+    const int64_t rep = sg_visitors_first_repeat(live + offsets[v], offsets[v + 1] - offsets[v]);
+    if (rep >= 0)
+        return fail(LOCREC_E_INVALID_ARG, "visitor %lld names the target %lld twice", (long long)v,
+                    (long long)target_ids[offsets[v] + rep]);
+    return LOCREC_OK;
+}
+
+// The set-up and finalize rows of a tile of nb visitors on g: every column has its private row, nothing is re-pointed
+void sg_vis_tile_rows(const locrec_sg_graph *g, int nb, double alpha, double eps2, std::vector<SlotRange> &pointed, SgBatchBegin &b,
+                      SgBatchReq &rq)
+{
+    const int32_t T = g->nlive;
+    sg_batch_restore_row(g, pointed, b);  // what a single request left pointing at its Q: back to D
+    pointed.clear();
+    b.x = g->PA4.p;
+    b.parts = g->D2W.p;
+    b.st = reinterpret_cast<SgBatchState *>(g->fused_conv.p);
+    b.x0 = 1.0 / (double)(g->nv + 1);  // :51-54 on G + v
+    b.nx = sg_batch_xstride(g);
+    b.nb = nb;
+    rq = SgBatchReq{};
+    rq.nb = nb;
+    rq.T = T;
+    rq.alpha = alpha;
+    rq.oma = 1 - alpha;  // :121
+    rq.eps2 = eps2;
+    for (int j = 0; j < nb; ++j) {
+        rq.target_x[j] = T + 1 + j;
+        rq.n_plain_dead[j] = (int32_t)(g->nv - T);
+        rq.q_in_use[j] = 1;
+    }
 }
 
 // A call's visitors, checked and staged; the device side of the stage and the tables
@@ -86,36 +153,13 @@ struct SgVisitorsCall {
                             double epsilon, int64_t max_iterations, int64_t *bad)
     {
         nv = n;
-        if (nv < 0 || (nv > 0 && !offsets)) return fail(LOCREC_E_INVALID_ARG, "bad arguments");
-        if (nv > 0) {
-            bool ok = offsets[0] == 0;
-            for (int64_t v = 0; ok && v < nv; ++v) ok = offsets[v] <= offsets[v + 1];
-            if (!ok) return fail(LOCREC_E_INVALID_ARG, "edge_offsets must start at 0 and be non-decreasing");
-            if (offsets[nv] > kSgVisitorsMaxEdges) return fail(LOCREC_E_INVALID_ARG, "2^31 visitor edges or more");
-            if (offsets[nv] > 0 && (!target_ids || !weights)) return fail(LOCREC_E_INVALID_ARG, "null array");
-        }
-        LOCREC_TRY(sg_batch_requires(epsilon, max_iterations));
+        LOCREC_TRY(sg_visitors_check_shape(nv, offsets, target_ids, weights, epsilon, max_iterations));
         if (const char *why = sg_batch_refusal(g)) return fail(LOCREC_E_INVALID_ARG, "%s", why);
         const int64_t ne = nv > 0 ? offsets[nv] : 0;
         std::vector<int32_t> live((size_t)ne);
         for (int64_t v = 0; v < nv; ++v) {
             *bad = v;
-            if (offsets[v] == offsets[v + 1]) return fail(LOCREC_E_NOT_FOUND, "visitor %lld has no edges", (long long)v);
-            for (int64_t e = offsets[v]; e < offsets[v + 1]; ++e) {
-                if (!std::isfinite(weights[e]))
-                    return fail(LOCREC_E_INVALID_ARG, "visitor %lld: the weight of its edge to %lld is not finite", (long long)v,
-                                (long long)target_ids[e]);
-                const int32_t tv = sg_vertex_index(g, target_ids[e]);
-                if (tv < 0) return fail(LOCREC_E_NOT_FOUND, "No such vertex in the graph: %lld", (long long)target_ids[e]);
-                if (g->live_of[tv] < 0)
-                    return fail(LOCREC_E_INVALID_ARG, "visitor %lld: vertex %lld has no inbound edge in the graph (the layout has no row for it)",
-                                (long long)v, (long long)target_ids[e]);
-                live[(size_t)e] = g->live_of[tv];
-            }
-            const int64_t rep = sg_visitors_first_repeat(live.data() + offsets[v], offsets[v + 1] - offsets[v]);
-            if (rep >= 0)
-                return fail(LOCREC_E_INVALID_ARG, "visitor %lld names the target %lld twice", (long long)v,
-                            (long long)target_ids[offsets[v] + rep]);
+            LOCREC_TRY(sg_visitor_check(g, v, offsets, target_ids, weights, live.data()));
         }
         *bad = -1;
         sg_visitors_stage(nv, offsets, live.data(), weights, st);
@@ -150,26 +194,7 @@ struct SgVisitorTiles {
     void rows(const locrec_sg_graph *g, size_t, int nb, double alpha, double eps2, std::vector<SlotRange> &pointed, SgBatchBegin &b,
               SgBatchReq &rq) const
     {
-        const int32_t T = g->nlive;
-        sg_batch_restore_row(g, pointed, b);  // what a single request left pointing at its Q: back to D
-        pointed.clear();
-        b.x = g->PA4.p;
-        b.parts = g->D2W.p;
-        b.st = reinterpret_cast<SgBatchState *>(g->fused_conv.p);
-        b.x0 = 1.0 / (double)(g->nv + 1);  // :51-54 on G + v
-        b.nx = sg_batch_xstride(g);
-        b.nb = nb;
-        rq = SgBatchReq{};
-        rq.nb = nb;
-        rq.T = T;
-        rq.alpha = alpha;
-        rq.oma = 1 - alpha;  // :121
-        rq.eps2 = eps2;
-        for (int j = 0; j < nb; ++j) {
-            rq.target_x[j] = T + 1 + j;
-            rq.n_plain_dead[j] = (int32_t)(g->nv - T);
-            rq.q_in_use[j] = 1;
-        }
+        sg_vis_tile_rows(g, nb, alpha, eps2, pointed, b, rq);
     }
     void set_up(const locrec_sg_graph *, hipStream_t s, size_t t0) const
     {

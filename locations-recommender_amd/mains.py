@@ -442,6 +442,97 @@ def sg_visitor_requests(data_dir, region_ids, visits, target_region_ids, epsilon
     return [(int(v), oi[i, :cnt[i]].copy(), op[i, :cnt[i]].copy()) for i, v in enumerate(ids)]
 
 
+def sg_visitor_requests_pooled(data_dir, visits, home_region_ids, target_region_ids, epsilon, max_iterations, max_recommendations=10,
+                               new_places=False, beta_person_place=1.0, beta_person_category=1.0, alpha=0.15, pooled=True):
+    """sg_visitor_requests for a queue of cold-start persons that fans out over region sets as persons do - the SG sibling
+    of knn_visitor_requests_pooled: visits as in sg_visitor_requests; home_region_ids and target_region_ids per visitor - a
+    mapping visitor id -> region, one region for all, or one per visitor in ascending visitor id.  Every visitor's graph is
+    the one of [home, target] from the handle cache (one handle per distinct region set), its edges come from
+    prep.visitor_edges against ITS member's graph - a visit to a place one member lacks may be live in another - and ONE
+    SgPool.visitors_recommend_ranked_batch call serves everybody.
+    -> a list in ascending visitor id of (visitor_id, place_ids, probabilities); where a visitor's region set cannot be
+    opened the entry is the exception instance; where the stage refuses a visitor - one left without edges in its graph -
+    the exception is recorded and the call repeated without the visitor (_call_without_bad_lines' contract).
+    new_places=True: a visitor's own targets are left out.
+    pooled=False: one SgGraph.visitors_recommend_ranked_batch call per distinct graph instead of the pool call - the same
+    result bit for bit; what such a queue cost before the pool."""
+    from . import _cache, prep
+    from .stochastic import SgPool
+    _cache.require_gpu_backend("sg_visitor_requests_pooled")
+    host = lambda a: np.asarray(a.cpu().numpy() if hasattr(a, "cpu") else a, np.int64)
+    v, p, c = host(visits["visitor_id"]), host(visits["place_id"]), host(visits["category_id"])
+    host_ids = np.unique(v)
+    homes = _per_visitor(home_region_ids, host_ids, "home")
+    regions = _per_visitor(target_region_ids, host_ids, "target")
+    out, targets, graphs = _sg_resolve_request_lines(
+        data_dir, None, list(range(len(host_ids))), resolve=lambda i: (int(host_ids[i]), int(homes[i]), int(regions[i])))
+    try:
+        if targets:
+            place_ids, place_regions = load_places(data_dir)
+            # every visitor's edges against its own member's graph: one prep.visitor_edges call per member
+            edges = {}
+            for k, g in enumerate(graphs):
+                mine = [i for i in sorted(targets) if targets[i][1] == k]
+                rows = np.isin(v, host_ids[mine])
+                with g.lock:
+                    _, off, t, w, _ = prep.visitor_edges(v[rows], p[rows], c[rows], beta_person_place, beta_person_category, graph=g)
+                for j, i in enumerate(mine):  # (ascending visitor id on both sides)
+                    edges[i] = (t[off[j]:off[j + 1]], w[off[j]:off[j + 1]])
+            pool = SgPool(graphs) if pooled else None
+            try:
+                def call(gi, _, live):
+                    off = np.zeros(len(live) + 1, np.int64)
+                    np.cumsum([len(edges[i][0]) for i in live], out=off[1:])
+                    t = np.concatenate([edges[i][0] for i in live]).astype(np.int64)
+                    w = np.concatenate([edges[i][1] for i in live]).astype(np.float64)
+                    serve = pool.visitors_recommend_ranked_batch if pool is not None else \
+                        (lambda *a, **kw: _sg_visitors_per_graph(graphs, *a, **kw))
+                    return serve(gi, off, t, w, alpha, epsilon, max_iterations, place_ids, place_regions,
+                                 regions[np.asarray(live, np.int64)], max_recommendations, exclude=(off, t) if new_places else None)
+                live, rows = _call_without_bad_lines(out, targets, call)
+            finally:
+                if pool is not None:
+                    pool.close()
+            if live:
+                oi, op, cnt, _, _ = rows
+                for j, i in enumerate(live):
+                    out[i] = (int(host_ids[i]), np.array(oi[j, :cnt[j]]), np.array(op[j, :cnt[j]]))
+    finally:
+        for g in graphs:
+            g.close()  # drops the reference only
+    return out
+
+
+def _sg_visitors_per_graph(graphs, graph_index, offsets, target_ids, weights, alpha, epsilon, max_iterations, place_ids,
+                           place_regions, regions, max_recommendations, exclude=None):
+    """SgPool.visitors_recommend_ranked_batch's result from one SgGraph.visitors_recommend_ranked_batch call per distinct
+    graph on that graph's visitors in call order; a refused visitor raises with bad_visitor = its position in the call (the
+    smallest over the graphs, as the pool call reports it)."""
+    n = len(graph_index)
+    width = max(0, int(max_recommendations))
+    oi, op = np.full((n, width), -1, np.int64), np.zeros((n, width), np.float64)
+    cnt, its, conv = np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, bool)
+    refused = None
+    for k in np.unique(graph_index):
+        at = np.flatnonzero(graph_index == k)
+        off, (t, w) = _csr_rows(offsets, (target_ids, weights), at)
+        try:
+            with graphs[k].lock:
+                r = graphs[k].visitors_recommend_ranked_batch(off, t, w, alpha, epsilon, max_iterations, place_ids, place_regions,
+                                                              regions[at], max_recommendations, exclude=(off, t) if exclude else None)
+        except L.IllegalArgumentException as e:
+            if getattr(e, "bad_visitor", -1) < 0:
+                raise
+            e.bad_visitor = int(at[e.bad_visitor])
+            if refused is None or e.bad_visitor < refused.bad_visitor:
+                refused = e
+            continue
+        oi[at, :r[0].shape[1]], op[at, :r[1].shape[1]], cnt[at], its[at], conv[at] = r
+    if refused is not None:
+        raise refused
+    return oi, op, cnt, its, conv
+
+
 def _sg_visited_lists(data_dir, region_ids, vertex_ids):
     """The exclusion lists of new_places for vertices of one region set: out_neighbours over its edge Parquet."""
     from .stochastic import out_neighbours
@@ -986,20 +1077,20 @@ def sg_recommender_requests_ranked(data_dir, persons, lines, epsilon, max_iterat
     return out
 
 
-def _sg_resolve_request_lines(data_dir, persons, lines):
+def _sg_resolve_request_lines(data_dir, persons, lines, resolve=None):
     """The line-resolution loop of sg_recommender_requests and sg_recommender_requests_ranked: every line is parsed and
     resolved on its own (Try { ... } per line, :44-49) and the graph of [home, target] comes from the handle cache, one
     handle per distinct region set.
     -> (out, targets, graphs): out aligned with lines, the exception instance at every bad line and None elsewhere;
     targets[i] = ((person_id, home_region_id, target_region_id), index into graphs) for every good line i.  The caller
-    closes the graphs."""
+    closes the graphs.  resolve: what turns a line into that triple in place of parsing it."""
     from . import _cache
     from .stochastic import SgGraph
 
     def open_graph(region_ids):
         name = generate_file_name(region_ids, data_dir, "stochastic_graph")
         return name, lambda: SgGraph.through_cache(_cache.files_key([name]), lambda: sg_graph_from_parquet(data_dir, region_ids))
-    return _resolve_request_lines(persons, lines, open_graph)
+    return _resolve_request_lines(persons, lines, open_graph, resolve)
 
 
 def _knn_resolve_request_lines(data_dir, persons, lines, resolve=None):

@@ -504,6 +504,110 @@ class SgPool:
         L.check(L.lib().locrec_sg_pool_recommend_ranked_batch_stats(*[C.byref(i) for i in x]))
         return dict(zip(cls.RANKED_STATS, (i.value for i in x)))
 
+    # ---- visitors across the pool (include/locrec.h, "Visitors across a pool") ----
+    VISITORS_STATS = ("tile_waves", "member_tiles", "visitors", "staged_edges", "stagings", "begin_launches", "set_up_launches",
+                      "rounds", "sweep_launches", "finalize_launches", "polls", "consumes")
+
+    def _sizes_of_members(self):
+        if self._sizes is None:  # (a handle's vertex and live counts never change)
+            self._sizes = (np.array([g.info()["vertices"] for g in self.graphs], np.int64),
+                           np.array([g.live_count() for g in self.graphs], np.int64))
+        return self._sizes
+
+    def _visitors(self, graph_index, edge_offsets, target_ids, weights):
+        gi = L.as_i32(graph_index)
+        off, t, w = SgGraph._visitor_edges(edge_offsets, target_ids, weights)
+        if len(gi) != len(off) - 1:
+            raise L.IllegalArgumentException("one graph index per visitor is required")
+        return gi, off, t, w
+
+    def _member_locks(self, held):
+        for g in self.graphs:  # every member's lock, in member order
+            if getattr(g, "lock", None) is not None:
+                held.enter_context(g.lock)
+
+    def visitors_recommend_batch(self, graph_index, edge_offsets, target_ids, weights, alpha, epsilon, max_iterations):
+        """makeRecommendations for visitors of many graphs in one call (locrec_sg_pool_visitors_recommend_batch): visitor v,
+        given as in SgGraph.visitors_recommend_batch, is asked of graphs[graph_index[v]] and gets exactly what that member's
+        own visitors_recommend_batch returns for it.
+        -> (offsets[nv + 1], ids, probabilities, iterations[nv], converged[nv]).  A refused call raises with `bad_visitor`
+        set on the exception: the position of the first offending visitor, or -1."""
+        import contextlib
+        gi, off, t, w = self._visitors(graph_index, edge_offsets, target_ids, weights)
+        nv = len(gi)
+        out_off = np.zeros(nv + 1, np.int64)
+        its, conv = np.zeros(nv, np.int64), np.zeros(nv, np.int32)
+        with contextlib.ExitStack() as held:
+            self._member_locks(held)
+            known = (gi >= 0) & (gi < len(self.graphs))
+            counts = np.bincount(gi[known], minlength=len(self.graphs))
+            per = self._sizes_of_members()[0 if int(max_iterations) == 0 else 1]
+            room = min(max(int(np.dot(counts, np.maximum(per, 1))), 1), 1 << 24)
+            cap = C.c_int64(room)
+            ids, probs = np.empty(room, np.int64), np.empty(room, np.float64)
+            bad = C.c_int64(-1)
+            for _ in range(2):  # a call whose room is too small sizes the result, the second fills it
+                try:
+                    L.check(L.lib().locrec_sg_pool_visitors_recommend_batch(
+                        self._h, nv, L.ptr(gi, C.c_int32), L.ptr(off, C.c_int64), L.ptr(t, C.c_int64), L.ptr(w, C.c_double),
+                        float(alpha), float(epsilon), int(max_iterations), L.ptr(out_off, C.c_int64), L.ptr(ids, C.c_int64),
+                        L.ptr(probs, C.c_double), C.byref(cap), L.ptr(its, C.c_int64), L.ptr(conv, C.c_int32), C.byref(bad)))
+                except L.IllegalArgumentException as e:
+                    e.bad_visitor = bad.value
+                    raise
+                if cap.value <= len(ids):
+                    break
+                ids, probs = np.empty(cap.value, np.int64), np.empty(cap.value, np.float64)
+                cap = C.c_int64(len(ids))
+        return out_off, ids[:out_off[-1]], probs[:out_off[-1]], its, conv.astype(bool)
+
+    def visitors_recommend_ranked_batch(self, graph_index, edge_offsets, target_ids, weights, alpha, epsilon, max_iterations,
+                                        place_ids, place_region_ids, target_region_ids, max_recommendations, exclude=None):
+        """The pool's visitors call to its end (locrec_sg_pool_visitors_recommend_ranked_batch): per visitor the places of
+        its target region that its member reaches, top max_recommendations by probability, emitted and ranked on the device.
+        exclude=(offsets[nv + 1], ids): visitor i leaves out ids[offsets[i]:offsets[i + 1]].
+        -> (ids[nv, W], probabilities[nv, W], counts[nv], iterations[nv], converged[nv]) as SgGraph's
+        visitors_recommend_ranked_batch returns them; visitor i equals that call on its member alone.  self.row_counts holds
+        makeRecommendations' own row count per visitor.  A refused call raises with `bad_visitor` set."""
+        import contextlib
+        gi, off, t, w = self._visitors(graph_index, edge_offsets, target_ids, weights)
+        nv = len(gi)
+        pl, reg, tgt = L.as_i64(place_ids), L.as_i64(place_region_ids), L.as_i64(target_region_ids)
+        if len(reg) != len(pl) or len(tgt) != nv:
+            raise L.IllegalArgumentException("one region per place and one target region per visitor are required")
+        xoff = xids = None
+        if exclude is not None:
+            xoff, xids = L.as_i64(exclude[0]), L.as_i64(exclude[1])
+            if len(xoff) != nv + 1:
+                raise L.IllegalArgumentException("one exclusion list per visitor is required: offsets of nv + 1 entries")
+        with contextlib.ExitStack() as held:
+            self._member_locks(held)
+            # no visitor has more rows than its graph has vertices: the stride of the call, cut to W afterwards
+            stride = max(0, min(int(max_recommendations), int(self._sizes_of_members()[0].max())))
+            oi, op = np.full((nv, stride), -1, np.int64), np.zeros((nv, stride), np.float64)
+            cnt, rows, its, conv = (np.zeros(nv, np.int64), np.zeros(nv, np.int64), np.zeros(nv, np.int64), np.zeros(nv, np.int32))
+            bad = C.c_int64(-1)
+            try:
+                L.check(L.lib().locrec_sg_pool_visitors_recommend_ranked_batch(
+                    self._h, nv, L.ptr(gi, C.c_int32), L.ptr(off, C.c_int64), L.ptr(t, C.c_int64), L.ptr(w, C.c_double),
+                    float(alpha), float(epsilon), int(max_iterations), len(pl), L.ptr(pl, C.c_int64), L.ptr(reg, C.c_int64),
+                    L.ptr(tgt, C.c_int64), stride, L.ptr(xoff, C.c_int64), 0 if xids is None else len(xids),
+                    L.ptr(xids, C.c_int64), L.ptr(oi, C.c_int64), L.ptr(op, C.c_double), L.ptr(cnt, C.c_int64),
+                    L.ptr(rows, C.c_int64), L.ptr(its, C.c_int64), L.ptr(conv, C.c_int32), C.byref(bad)))
+            except L.IllegalArgumentException as e:
+                e.bad_visitor = bad.value
+                raise
+        self.row_counts = rows
+        width = max(0, min(stride, int(rows.max()) if nv else 0))
+        return (np.ascontiguousarray(oi[:, :width]), np.ascontiguousarray(op[:, :width]), cnt, its, conv.astype(bool))
+
+    @classmethod
+    def visitors_stats(cls):
+        """What this thread's last visitors call on a pool did (locrec_sg_pool_visitors_stats)."""
+        x = (C.c_int64 * 12)()
+        L.check(L.lib().locrec_sg_pool_visitors_stats(x))
+        return dict(zip(cls.VISITORS_STATS, (int(i) for i in x)))
+
 
 class StochasticRecommender:
     """new StochasticRecommender(stochasticEdges, epsilon, maxIterations).makeRecommendations(vertexId)
