@@ -172,6 +172,14 @@ int32_t locrec_knn_ht_multiplied_words(const locrec_knn_index *index, int64_t *o
 int32_t locrec_knn_ht_slice_counts(const locrec_knn_index *index, int64_t capacity, int32_t *out_place, int32_t *out_category,
                                    int64_t *out_slices);
 
+/* Measurement and tests only: the LDS model of the head / tail image's element order (csrc/knn_ht_order.h), computed
+ * over the stored image by a small kernel on demand.  Counted are the positions in front of every slice's element
+ * counts, both families, for each of the four groups of 16 lanes that one LDS cycle serves: *out_group_reads = such
+ * (slice, position, group) reads, *out_cycles = the cycles they take when different panel rows on one slot (index mod
+ * 16) cost a cycle each and equal rows share one.  cycles - group_reads = modelled bank-conflict cycles per plane read.
+ * Zeros without the image.  Synchronises the handle's stream. */
+int32_t locrec_knn_ht_lds_model(locrec_knn_index *index, int64_t *out_group_reads, int64_t *out_cycles);
+
 /* Measurement and tests only: the queries the LDS aggregation (csrc/knn_aggregate.h; K <= LOCREC_KNN_BATCH_MAX_K) has
  * served on this handle since the previous call of this function: out[0] summed by the bucket form
  * (knn_aggregate_buckets), out[1] summed by the sort form (knn_aggregate: the redo pass of a flagged query, an index with

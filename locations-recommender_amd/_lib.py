@@ -59,6 +59,7 @@ SIGNATURES = {
     "locrec_knn_ht_image_info": [C.c_void_p, _i64p, _i64p, _i64p],
     "locrec_knn_ht_multiplied_words": [C.c_void_p, _i64p],
     "locrec_knn_ht_slice_counts": [C.c_void_p, C.c_int64, _i32p, _i32p, _i64p],
+    "locrec_knn_ht_lds_model": [C.c_void_p, _i64p, _i64p],
     "locrec_knn_aggregate_stats": [C.c_void_p, _i64p],
     "locrec_knn_ht_last_hits": [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _i32p, _i64p, _i32p, _i32p, _i64p,
                                 C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _i64p],

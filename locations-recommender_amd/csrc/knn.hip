@@ -51,6 +51,7 @@
 #include <unordered_map>
 
 #include "knn_agg_plan.h"
+#include "knn_ht_order.h"
 #include "knn_index.h"
 
 namespace {
@@ -257,6 +258,7 @@ int32_t build_ht(locrec_knn_index *ix, const HostFamily &hq, const HostFamily &h
         wv.assign((size_t)nslices, 0);
         std::vector<int32_t> &ex = h_ex[which - 1];
         ex.assign((size_t)nslices, 0);
+        std::vector<int32_t> exact((size_t)nslices, 0);  // (ex before LOCREC_KNN_HT_ROUND4 rounds it)
         auto len_of = [&](int64_t r) { return limit ? (*limit)[r] : (int32_t)(h.ptr[r + 1] - h.ptr[r]); };
         for (int32_t sl = 0; sl < nslices; ++sl) {
             int w = 0, x = 0;
@@ -265,6 +267,7 @@ int32_t build_ht(locrec_knn_index *ix, const HostFamily &hq, const HostFamily &h
                 if (!ix->row_is_wide((int32_t)r)) x = std::max(x, len_of(r));  // (a wide row's stand-in is padding only)
             }
             ex[sl] = ix->ht_round4 ? (x + 3) & ~3 : x;
+            exact[sl] = x;
             w = (w + 3) & ~3;
             wv[sl] = w;
             off[sl + 1] = off[sl] + (int64_t)w * 64;
@@ -279,6 +282,18 @@ int32_t build_ht(locrec_knn_index *ix, const HostFamily &hq, const HostFamily &h
                 sell[base + (int64_t)(j >> 2) * 256 + lane * 4 + (j & 3)] =
                     ((uint32_t)h.val[b + j] << 16) | ((uint32_t)h.idx[b + j] << rsh);
         }
+        // the order of a row's elements in front of the slice's exact count, one lane group at a time (knn_ht_order.h:
+        // the routine kb_ht_order runs in the device build)
+        for (int32_t sl = 0; sl < nslices && !ix->ht_ascending; ++sl)
+            for (int g = 0; g < locrec::kHtOrderGroups; ++g) {
+                uint32_t blank = 0u;
+                for (int i = 0; i < locrec::kHtOrderLanes; ++i) {
+                    const int64_t r = (int64_t)sl * 64 + locrec::ht_order_lane(g, i);
+                    if (r < n && ix->row_is_wide((int32_t)r)) blank |= 1u << i;
+                }
+                locrec::HtOrderSlice img{sell.data() + off[sl], g};
+                locrec::ht_order_group(img, exact[sl], blank);
+            }
         elements = off[nslices];
         LOCREC_TRY(d_sell.upload(sell, s));
         LOCREC_TRY(d_off.upload(off.data(), (size_t)nslices, s));
@@ -1475,6 +1490,7 @@ void knn_read_env(locrec_knn_index *ix)
     ix->no_pack = std::getenv("LOCREC_KNN_NO_PACK") != nullptr;
     ix->no_seed = std::getenv("LOCREC_KNN_NO_SEED") != nullptr;  // A/B: knn_scan_ht without the threshold-seeding pass
     ix->ht_round4 = std::getenv("LOCREC_KNN_HT_ROUND4") != nullptr;  // A/B: knn_scan_ht multiplies whole groups of four again
+    ix->ht_ascending = std::getenv("LOCREC_KNN_HT_ASCENDING") != nullptr;  // A/B: the head / tail image without knn_ht_order.h
     ix->no_tile_special = std::getenv("LOCREC_KNN_NO_TILE_SPECIAL") != nullptr;  // A/B: special queries of a batch one by one
     if (const char *e = std::getenv("LOCREC_KNN_SEED_MIN_SLICES")) ix->seed_min_slices = std::max(1, std::atoi(e));  // tests
     if (const char *e = std::getenv("LOCREC_KNN_SEED_SAMPLE")) ix->seed_sample_slices = std::max(8, std::atoi(e));     // tuning
@@ -1613,6 +1629,44 @@ extern "C" int32_t locrec_knn_ht_multiplied_words(const locrec_knn_index *ix, in
 {
     if (!ix || !out_words) return fail(LOCREC_E_INVALID_ARG, "NULL argument");
     *out_words = ix->ht.ready && !ix->no_ht ? ix->ht.mult_words : 0;
+    return LOCREC_OK;
+} LOCREC_CATCH_ALL
+
+namespace {
+// the LDS model of knn_ht_order.h over the stored image: per slice and lane group, the positions in front of the
+// descriptor's counts, both families.  out[0] += group reads, out[1] += modelled cycles.
+__global__ void knn_ht_lds_model(int32_t nslices, const uint4 *desc, const uint32_t *p_sell, const uint32_t *c_sell,
+                                 unsigned long long *out)
+{
+    const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (id >= (int64_t)nslices * locrec::kHtOrderGroups) return;
+    const uint4 d = desc[id / locrec::kHtOrderGroups];
+    const int g = (int)(id % locrec::kHtOrderGroups), np = (int)(d.w & 0xFFFFu), nc = (int)(d.w >> 16);
+    const locrec::HtOrderSlice ip{const_cast<uint32_t *>(p_sell) + (int64_t)d.x * 4, g};  // (only read)
+    const locrec::HtOrderSlice ic{const_cast<uint32_t *>(c_sell) + (int64_t)d.y * 4, g};
+    atomicAdd(out, (unsigned long long)(np + nc));
+    atomicAdd(out + 1, (unsigned long long)(locrec::ht_order_cycles(ip, np) + locrec::ht_order_cycles(ic, nc)));
+}
+}  // namespace
+
+extern "C" int32_t locrec_knn_ht_lds_model(locrec_knn_index *ix, int64_t *out_group_reads, int64_t *out_cycles) try
+{
+    if (!ix || !out_group_reads || !out_cycles) return fail(LOCREC_E_INVALID_ARG, "NULL argument");
+    *out_group_reads = *out_cycles = 0;
+    if (!ix->ht.ready || ix->no_ht || ix->nslices <= 0) return LOCREC_OK;
+    LOCREC_HIP_TRY(hipSetDevice(ix->device));
+    DevBuf<unsigned long long> acc;
+    LOCREC_TRY(acc.alloc(2));
+    LOCREC_HIP_TRY(hipMemsetAsync(acc.p, 0, 2 * sizeof(unsigned long long), ix->stream));
+    const int64_t threads = (int64_t)ix->nslices * locrec::kHtOrderGroups;
+    hipLaunchKernelGGL(knn_ht_lds_model, dim3((unsigned)((threads + 63) / 64)), dim3(64), 0, ix->stream, ix->nslices,
+                       ix->ht.desc.p, ix->ht.p_sell.p, ix->ht.c_sell.p, acc.p);
+    LOCREC_HIP_TRY(hipGetLastError());
+    unsigned long long h[2] = {0, 0};
+    LOCREC_HIP_TRY(hipMemcpyAsync(h, acc.p, sizeof h, hipMemcpyDeviceToHost, ix->stream));
+    LOCREC_HIP_TRY(hipStreamSynchronize(ix->stream));
+    *out_group_reads = (int64_t)h[0];
+    *out_cycles = (int64_t)h[1];
     return LOCREC_OK;
 } LOCREC_CATCH_ALL
 

@@ -29,6 +29,7 @@
 #include <numeric>
 
 #include "knn_build_open.h"
+#include "knn_ht_order.h"
 #include "knn_index.h"
 #include "knn_visitors_side.h"
 #include "offline.h"
@@ -412,6 +413,71 @@ __global__ void kb_desc(int64_t n, int32_t nslices, const int64_t *off_p, const 
     }
     desc[sl] = make_uint4((uint32_t)(off_p[sl] / 4), (uint32_t)(off_c[sl] / 4), (uint32_t)(w_p[sl] / 4) | ((uint32_t)(w_c[sl] / 4) << 16),
                           (uint32_t)mp | ((uint32_t)mc << 16));
+}
+
+// The order of a row's elements in front of the slice's exact count (knn_ht_order.h), in place.  len / skip as in
+// kb_desc; the count is the exact one also under LOCREC_KNN_HT_ROUND4, so the elements stay in front of it.
+//
+// One wave per slice, of which lanes 0 .. 3 run the routine, one lane group each: it is serial, branchy code, and 64
+// groups side by side in one wave would execute one after the other (measured: 0.2 s at cfg2 as one thread per group on
+// whole waves).  It reads every word many times, one dependent read after the other, so the wave first copies the
+// slice's words into LDS, where the routine's tables are too (HtOrderWork: scratch memory otherwise, and the waves of a
+// launch hold more of it than the caches do).  One launch serves the slices with lo < count <= hi, 4 x hi positions x 16
+// words of LDS per wave (a group's words rotated by its number, so that the four touch different banks); hi = 0: the slices beyond
+// every stage, their words in global memory.  The routine is compiled for size (minsize, here and in knn_ht_order.h):
+// unrolled and inlined it was 166 KB, several times the instruction cache, and every lane waited for its instructions.
+// Its work is linear in the count (kHtOrderLook), so a slice of count 512 costs 32 x one of count 16, on one lane.
+constexpr int kHtOrderWindow[4][2] = {{0, 16}, {16, 32}, {32, 128}, {128, 0}};  // lo, hi
+
+struct HtOrderStage {   // one type for both places, so that the kernel holds the routine once
+    uint32_t *w;        // the stage: hi * 16 words (a power of two); nullptr = the words stay in the image
+    uint32_t mask, skew;
+    HtOrderSlice image;
+    __device__ uint32_t get(int i, int pos) const
+    {
+        return w ? w[((uint32_t)(pos * kHtOrderLanes + i) + skew) & mask] : image.get(i, pos);
+    }
+    __device__ void set(int i, int pos, uint32_t v) const
+    {
+        if (w) w[((uint32_t)(pos * kHtOrderLanes + i) + skew) & mask] = v;
+        else image.set(i, pos, v);
+    }
+};
+
+__global__ __launch_bounds__(64) __attribute__((minsize)) void kb_ht_order(int64_t n, const int64_t *off, const int32_t *len, const unsigned char *skip,
+                                                  uint32_t *sell, int32_t lo, int32_t hi)
+{
+    extern __shared__ uint32_t kb_order_stage[];
+    const int64_t sl = blockIdx.x;
+    const int t = threadIdx.x;
+    const int64_t r = sl * 64 + t;
+    const bool wide = r < n && skip && skip[r];
+    int cnt = r < n && !wide ? len[r] : 0;
+    for (int d = 1; d < 64; d <<= 1) cnt = max(cnt, __shfl_xor(cnt, d));
+    if (cnt <= lo || (hi > 0 && cnt > hi)) return;  // (the whole wave)
+    const unsigned long long wide_lanes = __ballot(wide);
+    uint32_t blank = 0u;  // of lane group t
+    for (int i = 0; i < kHtOrderLanes; ++i)
+        if (t < kHtOrderGroups && ((wide_lanes >> ht_order_lane(t, i)) & 1ull)) blank |= 1u << i;
+    uint32_t *base = sell + off[sl];
+    const int words = hi * kHtOrderLanes;
+    HtOrderWork *work = reinterpret_cast<HtOrderWork *>(kb_order_stage + kHtOrderGroups * words);  // (behind the stage)
+    for (int g = 0; g < kHtOrderGroups && hi > 0; ++g) {
+        const HtOrderSlice img{base, g};
+        const HtOrderStage st{kb_order_stage + g * words, (uint32_t)(words - 1), (uint32_t)g, img};
+        for (int e = t; e < cnt * kHtOrderLanes; e += 64) st.set(e & 15, e >> 4, img.get(e & 15, e >> 4));
+    }
+    __syncthreads();
+    if (t < kHtOrderGroups) {
+        HtOrderStage st{hi > 0 ? kb_order_stage + t * words : nullptr, (uint32_t)(words - 1), (uint32_t)t, HtOrderSlice{base, t}};
+        ht_order_group(st, cnt, blank, work[t]);
+    }
+    __syncthreads();
+    for (int g = 0; g < kHtOrderGroups && hi > 0; ++g) {
+        const HtOrderSlice img{base, g};
+        const HtOrderStage st{kb_order_stage + g * words, (uint32_t)(words - 1), (uint32_t)g, img};
+        for (int e = t; e < cnt * kHtOrderLanes; e += 64) img.set(e & 15, e >> 4, st.get(e & 15, e >> 4));
+    }
 }
 
 __global__ void kb_pad_rid(int64_t n, int64_t npad, const uint32_t *rid, uint32_t *out)
@@ -836,6 +902,7 @@ int32_t Build::head_tail_image()
     LOCREC_TRY(ht.desc.alloc((size_t)std::max(1, ix->nslices)));
     LOCREC_LAUNCH(kb_desc, grid_for(ix->nslices), dim3(256), 0, s, n, ix->nslices, ht.p_off.p, ht.p_w.p, ht.c_off.p, ht.c_w.p,
                   nhead.p, nnz_c.p, skip, ix->ht_round4 ? 1 : 0, ht.desc.p);
+    uint32_t max_p = 0, max_c = 0;  // the largest counts of any slice
     {
         // words per tile knn_scan_ht multiplies (locrec_knn_ht_multiplied_words): 64 lanes x the slices' counts
         std::vector<uint4> hd((size_t)ix->nslices);
@@ -846,7 +913,19 @@ int32_t Build::head_tail_image()
         for (const uint4 &d : hd) {
             ht.mult_words += 64 * (int64_t)((d.w & 0xFFFFu) + (d.w >> 16));
             ht.slice_cnt.push_back(d.w);
+            max_p = std::max(max_p, d.w & 0xFFFFu);
+            max_c = std::max(max_c, d.w >> 16);
         }
+    }
+    // the order of the elements inside every lane group (knn_ht_order.h), one launch per range of counts that has a slice:
+    // the fewer positions a slice has, the more waves fit a CU's LDS (LOCREC_KNN_HT_ASCENDING: the A/B switch)
+    for (int wdw = 0; wdw < 4 && !ix->ht_ascending && ix->nslices > 0; ++wdw) {
+        const int lo = kHtOrderWindow[wdw][0], hi = kHtOrderWindow[wdw][1];
+        const size_t lds = (size_t)kHtOrderGroups * ((size_t)hi * kHtOrderLanes * 4 + sizeof(HtOrderWork));
+        if ((int)max_p > lo)
+            LOCREC_LAUNCH(kb_ht_order, dim3((unsigned)ix->nslices), dim3(64), lds, s, n, ht.p_off.p, nhead.p, skip, ht.p_sell.p, lo, hi);
+        if ((int)max_c > lo)
+            LOCREC_LAUNCH(kb_ht_order, dim3((unsigned)ix->nslices), dim3(64), lds, s, n, ht.c_off.p, nnz_c.p, skip, ht.c_sell.p, lo, hi);
     }
     LOCREC_TRY(ht.cold.alloc(cfg::kHtColdBytes));
     // postings of the tail places: (place, row) keys, radix-sorted -> rows ascending inside a place

@@ -172,6 +172,7 @@ struct locrec_knn_index {
     bool no_direct8 = false, direct8_attr = false;  // knn_scan1_direct8 (LOCREC_KNN_NO_DIRECT8)
     bool no_seed = false;         // LOCREC_KNN_NO_SEED
     bool ht_round4 = false;       // LOCREC_KNN_HT_ROUND4: A/B, the descriptors' element counts rounded up to whole groups
+    bool ht_ascending = false;    // LOCREC_KNN_HT_ASCENDING: A/B, a row's head elements in ascending order (no knn_ht_order.h)
     // read by knn_read_env like the ones above (the only place of the KNN sources that looks at the environment)
     bool force_generic = false;   // LOCREC_KNN_FORCE_GENERIC
     bool no_pack16 = false;       // LOCREC_KNN_NO_PACK16

@@ -158,6 +158,14 @@ class KnnIndex:
                                                        c.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(ns)))
         return np.stack([p, c], axis=1)
 
+    def ht_lds_model(self):
+        """{group_reads, cycles} of the head / tail image under the LDS model of its element order
+        (locrec_knn_ht_lds_model): reads of one position by one group of 16 lanes, and the cycles they take when
+        different panel rows on one slot cost a cycle each.  cycles - group_reads = modelled conflict cycles."""
+        r, c = C.c_int64(), C.c_int64()
+        L.check(L.lib().locrec_knn_ht_lds_model(self._h, C.byref(r), C.byref(c)))
+        return {"group_reads": r.value, "cycles": c.value}
+
     def aggregate_stats(self):
         """Queries the LDS aggregation has served on this index since the previous call (locrec_knn_aggregate_stats):
         {buckets, sort, flagged} - summed by knn_aggregate_buckets, summed by knn_aggregate (a redone query, an index with
