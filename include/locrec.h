@@ -316,6 +316,24 @@ int32_t locrec_knn_fetch_ranked_unvisited(
     int64_t n_places, const int64_t *place_ids, const int64_t *place_region_ids,
     const int64_t *target_region_ids, int64_t max_recommendations,
     int64_t *out_place_ids, double *out_estimated_ratings, int64_t *out_counts);
+/*
+ * Within reach: locrec_knn_recommend_ranked_batch with a circle per position
+ * (locrec_rank_recommendations_batch_near's semantics, requires and refusals; host arrays, checked before the
+ * index is looked at).  place_latitudes / place_longitudes: one per row of the place table; center_*,
+ * radius_meters: one per position.  unvisited != 0: the _unvisited form's lists as well.  out_meters (nq x
+ * max_recommendations, may be NULL): the distance of each output row, padding 0.0.  Both resident row forms and
+ * the second ranker call for host-assembled overflow queries go through the near ranker; a repeated person is
+ * ranked per position with its own circle.  Afterwards the plain calls return what they did before.
+ */
+int32_t locrec_knn_recommend_ranked_batch_near(
+    locrec_knn_index *index, int64_t nq, const int64_t *person_ids,
+    double place_weight, double category_weight, int64_t k_nearest,
+    int64_t n_places, const int64_t *place_ids, const int64_t *place_region_ids,
+    const double *place_latitudes, const double *place_longitudes,
+    const int64_t *target_region_ids,
+    const double *center_latitudes, const double *center_longitudes, const double *radius_meters,
+    int64_t max_recommendations, int32_t unvisited,
+    int64_t *out_place_ids, double *out_estimated_ratings, double *out_meters, int64_t *out_counts);
 
 /*
  * A pool of resident indexes that serves ONE mixed batch of (index, person[, target region]) requests - the queue of
@@ -701,6 +719,27 @@ int32_t locrec_sg_recommend_ranked_batch_excluding(
     const int64_t *target_region_ids, int64_t max_recommendations,
     const int64_t *excluded_offsets, int64_t n_excluded, const int64_t *excluded_ids,
     int64_t *out_ids, double *out_probabilities, int64_t *out_counts,
+    int64_t *out_row_counts, int64_t *out_iterations, int32_t *out_converged);
+/*
+ * Within reach: locrec_sg_recommend_ranked_batch_excluding with a circle per position
+ * (locrec_rank_recommendations_batch_near's semantics, requires and refusals; host arrays, checked before the
+ * graph is looked at).  excluded_offsets == NULL: no lists.  place_latitudes / place_longitudes: one per row of
+ * the place table; center_*, radius_meters: one per position.  out_meters (n_targets x max_recommendations, may
+ * be NULL): the distance of each output row, padding 0.0.  The emit and the segments' room see only the region;
+ * the group's ranker call applies the circle: out_row_counts, iterations and converged are the plain call's, and
+ * the result does not depend on LOCREC_SG_RANKED_ROW_BUDGET.  A repeated vertex is iterated once and ranked per
+ * position with its own circle.
+ */
+int32_t locrec_sg_recommend_ranked_batch_near(
+    locrec_sg_graph *graph, int64_t n_targets, const int64_t *vertex_ids,
+    double alpha, double epsilon, int64_t max_iterations,
+    int64_t n_places, const int64_t *place_ids, const int64_t *place_region_ids,
+    const double *place_latitudes, const double *place_longitudes,
+    const int64_t *target_region_ids,
+    const double *center_latitudes, const double *center_longitudes, const double *radius_meters,
+    int64_t max_recommendations,
+    const int64_t *excluded_offsets, int64_t n_excluded, const int64_t *excluded_ids,
+    int64_t *out_ids, double *out_probabilities, double *out_meters, int64_t *out_counts,
     int64_t *out_row_counts, int64_t *out_iterations, int32_t *out_converged);
 /*
  * What this thread's last locrec_sg_recommend_ranked_batch (or _excluding) did (any pointer may be NULL): tiles iterated,
@@ -1226,6 +1265,35 @@ int32_t locrec_rank_recommendations_batch_excluding(int64_t n_segments, const in
                                                     const int64_t *excluded_offsets, int64_t n_excluded,
                                                     const int64_t *excluded_ids, int32_t mem, int64_t *out_ids,
                                                     double *out_scores, int64_t *out_counts);
+
+/*
+ * Within reach: the same with a circle per segment.  Segment s keeps a row iff its id is a place of the target
+ * region AND some listing of that place in that region has
+ * locrec_distance_meters((center_latitudes[s], center_longitudes[s]), listing) <= radius_meters[s] - Spark's
+ * places.where(region_id === target && distance <= radius) JOIN rows ON id, a place counting once.  The order,
+ * the padding, the radix path above LOCREC_RANK_BATCH_MAX_N and the two environment switches are
+ * locrec_rank_recommendations_batch's.  radius_meters[s] >= 0 or +inf; +inf keeps every place of the region
+ * (with every radius +inf the ids, scores, counts and stats are the plain / excluding call's bit for bit);
+ * radius 0 keeps a place whose coordinates equal the centre.  A place listed several times in the region
+ * passes if any listing passes; the listing that counts is the first inside the radius in the table's input
+ * order.  out_meters (the shape of out_scores; may be NULL) gets that listing's distance with the bits of
+ * locrec_distance_meters, padding 0.0.  excluded_offsets == NULL: no lists (n_excluded, excluded_ids unused);
+ * otherwise locrec_rank_recommendations_batch_excluding's lists, combined with the circle.  `mem` covers every
+ * array.  LOCREC_E_INVALID_ARG and nothing written, the message naming the argument: a radius that is NaN or
+ * negative; a centre or a row of the place table with a latitude outside [-90, 90] or a longitude outside
+ * [-180, 180] (NaN fails); NULL coordinate arrays with n_places > 0.  Host arrays are checked on the host
+ * before any device work, device arrays on the device before any row is read.  At most 3 host
+ * synchronisations.  Not built: a circle that reaches into a second region.
+ */
+int32_t locrec_rank_recommendations_batch_near(
+    int64_t n_segments, const int64_t *offsets, int64_t n, const int64_t *ids, const double *scores,
+    int64_t n_places, const int64_t *place_ids, const int64_t *place_region_ids,
+    const double *place_latitudes, const double *place_longitudes,
+    const int64_t *target_region_ids,
+    const double *center_latitudes, const double *center_longitudes, const double *radius_meters,
+    int64_t max_recommendations,
+    const int64_t *excluded_offsets, int64_t n_excluded, const int64_t *excluded_ids,
+    int32_t mem, int64_t *out_ids, double *out_scores, double *out_meters, int64_t *out_counts);
 
 /* What the last ranked batch of this thread did (locrec_rank_recommendations_batch and the ranked KNN
  * batches): segments served by one block, segments split into chunks, those chunks, segments that took

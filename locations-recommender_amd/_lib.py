@@ -75,6 +75,9 @@ SIGNATURES = {
     "locrec_knn_recommend_ranked_batch_unvisited": [C.c_void_p, C.c_int64, _i64p, C.c_double, C.c_double, C.c_int64,
                                                     C.c_int64, _i64p, _i64p, _i64p, C.c_int64, _i64p, _f64p, _i64p],
     "locrec_knn_fetch_ranked_unvisited": [C.c_void_p, C.c_int64, C.c_int64, _i64p, _i64p, _i64p, C.c_int64, _i64p, _f64p, _i64p],
+    "locrec_knn_recommend_ranked_batch_near": [C.c_void_p, C.c_int64, _i64p, C.c_double, C.c_double, C.c_int64,
+                                               C.c_int64, _i64p, _i64p, _f64p, _f64p, _i64p, _f64p, _f64p, _f64p, C.c_int64,
+                                               C.c_int32, _i64p, _f64p, _f64p, _i64p],
     "locrec_knn_query_shard": [C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int64, C.c_int32, C.c_int32,
                                _i64p, _f64p, _i64p],
     "locrec_knn_recommend_neighbours": [C.c_void_p, C.c_int64, _i64p, _f64p, _i64p, _f64p, _i64p],
@@ -103,6 +106,9 @@ SIGNATURES = {
     "locrec_sg_recommend_ranked_batch_excluding": [C.c_void_p, C.c_int64, _i64p, C.c_double, C.c_double, C.c_int64,
                                                    C.c_int64, _i64p, _i64p, _i64p, C.c_int64, _i64p, C.c_int64, _i64p,
                                                    _i64p, _f64p, _i64p, _i64p, _i64p, _i32p],
+    "locrec_sg_recommend_ranked_batch_near": [C.c_void_p, C.c_int64, _i64p, C.c_double, C.c_double, C.c_int64,
+                                              C.c_int64, _i64p, _i64p, _f64p, _f64p, _i64p, _f64p, _f64p, _f64p, C.c_int64,
+                                              _i64p, C.c_int64, _i64p, _i64p, _f64p, _f64p, _i64p, _i64p, _i64p, _i32p],
     "locrec_sg_recommend_ranked_batch_stats": [_i64p, _i64p, _i64p, _i64p, _i64p],
     "locrec_sg_visitors_recommend_batch": [C.c_void_p, C.c_int64, _i64p, _i64p, _f64p, C.c_double, C.c_double, C.c_int64,
                                            _i64p, _i64p, _f64p, _i64p, _i64p, _i32p, _i64p],
@@ -216,6 +222,10 @@ SIGNATURES = {
     "locrec_rank_recommendations_batch_excluding": [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                                     C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
                                                     C.c_void_p, C.c_void_p, C.c_void_p],
+    "locrec_rank_recommendations_batch_near": [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p],
     "locrec_rank_recommendations_batch_stats": [_i64p, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p],
     # the place deduplicator (dedup.hip)
     "locrec_lev_distances": [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p],

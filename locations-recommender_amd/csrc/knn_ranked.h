@@ -12,6 +12,10 @@
 // The unvisited forms (locrec_knn_recommend_ranked_batch_unvisited, locrec_knn_fetch_ranked_unvisited) recommend only new
 // places: both ranker calls get, per segment, the place ids of the person's rating rows as an exclusion list - begins and
 // lengths into ix->r_place, filled on the device from ix->r_ptr (knn_rk_rated_ranges, 8 VGPRs, no LDS, no scratch).
+// The near form (locrec_knn_recommend_ranked_batch_near) recommends within reach: per position a centre and a radius, per
+// place row its coordinates, uploaded behind the RankIo's other inputs; both ranker calls are the near ranker's
+// (rank_segments_device_near), the hosted segments taking their positions' circles, and out_meters comes back with the
+// rows.  Its host arrays are checked before the index is looked at.
 #pragma once
 
 #include "rank_batch.h"
@@ -60,14 +64,23 @@ int32_t knn_rk_rated_lists(locrec_knn_index *ix, const std::vector<int32_t> &row
     return LOCREC_OK;
 }
 
+// The circles of a near call (host arrays): per row of the place table its coordinates, per segment a centre and a
+// radius; meters: the output rows' distances (NULL: not wanted).  The near entry has checked them.
+struct KnnRankNear {
+    const double *place_lat, *place_lon, *center_lat, *center_lon, *radius;
+    double *meters;
+};
+
 // segment c of the result = the resident rows of processing slot slots[c], ranked for targets[c] (host arrays).
 // known_len: the segments' row counts where the caller has them from a fetch that already settled the rows (the batch
 // form: locrec_knn_recommend_batch sizes its result through locrec_knn_fetch_recommend); NULL: that fetch is made here.
 // unvisited: every segment leaves out the places its person has rated (both ranker calls get the lists).
+// near: every segment keeps only the places inside its circle (both ranker calls are the near ranker's).
 int32_t knn_rank_resident(locrec_knn_index *ix, const std::vector<int64_t> &slots, const int64_t *known_len, bool unvisited,
                           int64_t n_places,
                           const int64_t *place_ids, const int64_t *place_region_ids, const int64_t *targets,
-                          int64_t max_recommendations, int64_t *out_ids, double *out_scores, int64_t *out_counts)
+                          int64_t max_recommendations, int64_t *out_ids, double *out_scores, int64_t *out_counts,
+                          const KnnRankNear *near = nullptr)
 {
     const int64_t nseg = (int64_t)slots.size(), nq = ix->last_nq;
     const int64_t N = std::max<int64_t>(0, max_recommendations);
@@ -107,9 +120,19 @@ int32_t knn_rank_resident(locrec_knn_index *ix, const std::vector<int64_t> &slot
     if (nseg == 0) return LOCREC_OK;
     // one allocation for the call's inputs and one for its outputs (every hipMalloc / hipFree costs a wait)
     DevBuf<int64_t> d_in, d_out;
-    LOCREC_TRY(d_in.alloc(RankIo::in_words(n_places, nseg) + (unvisited ? knn_rk_ex_words(nseg) : 0)));
-    LOCREC_TRY(d_out.alloc(RankIo::out_words(nseg, N)));
-    const RankIo io(d_in.p, d_out.p, n_places, nseg, N);
+    const bool circ = near != nullptr;
+    LOCREC_TRY(d_in.alloc(RankIo::in_words(n_places, nseg, circ) + (unvisited ? knn_rk_ex_words(nseg) : 0)));
+    LOCREC_TRY(d_out.alloc(RankIo::out_words(nseg, N, circ)));
+    const RankIo io(d_in.p, d_out.p, n_places, nseg, N, nullptr, circ);
+    if (circ) {
+        if (n_places > 0) {
+            LOCREC_HIP_TRY(hipMemcpyAsync(io.plat, near->place_lat, (size_t)n_places * 8, hipMemcpyHostToDevice, s));
+            LOCREC_HIP_TRY(hipMemcpyAsync(io.plon, near->place_lon, (size_t)n_places * 8, hipMemcpyHostToDevice, s));
+        }
+        LOCREC_HIP_TRY(hipMemcpyAsync(io.clat, near->center_lat, (size_t)nseg * 8, hipMemcpyHostToDevice, s));
+        LOCREC_HIP_TRY(hipMemcpyAsync(io.clon, near->center_lon, (size_t)nseg * 8, hipMemcpyHostToDevice, s));
+        LOCREC_HIP_TRY(hipMemcpyAsync(io.rad, near->radius, (size_t)nseg * 8, hipMemcpyHostToDevice, s));
+    }
     if (n_places > 0) {
         LOCREC_HIP_TRY(hipMemcpyAsync(io.pid, place_ids, (size_t)n_places * 8, hipMemcpyHostToDevice, s));
         LOCREC_HIP_TRY(hipMemcpyAsync(io.preg, place_region_ids, (size_t)n_places * 8, hipMemcpyHostToDevice, s));
@@ -122,17 +145,17 @@ int32_t knn_rank_resident(locrec_knn_index *ix, const std::vector<int64_t> &slot
     if (unvisited) {
         std::vector<int32_t> rows((size_t)nseg);
         for (int64_t c = 0; c < nseg; ++c) rows[(size_t)c] = row_of_slot(slots[(size_t)c]);
-        LOCREC_TRY(knn_rk_rated_lists(ix, rows, d_in.p + RankIo::in_words(n_places, nseg), s, ex));
+        LOCREC_TRY(knn_rk_rated_lists(ix, rows, d_in.p + RankIo::in_words(n_places, nseg, circ), s, ex));
     }
     LOCREC_TRY(io.rank(lkb ? ix->lkb_place.p : ix->agg_place.p, lkb ? ix->lkb_est.p : ix->agg_est.p, 0, s, ex));
-    LOCREC_TRY(io.read_back(out_ids, out_scores, out_counts, s));
+    LOCREC_TRY(io.read_back(out_ids, out_scores, out_counts, s, circ ? near->meters : nullptr));
     RankBatchStats total = rank_batch_stats();
     ++total.host_syncs;
     if (!hosted.empty()) {
         // rows of the overflow queries: assembled on the host once per slot, uploaded, ranked as their own segments
         const int64_t nh = (int64_t)hosted.size();
         std::vector<int64_t> rp, tb((size_t)nh), tl((size_t)nh), tt((size_t)nh);
-        std::vector<double> re;
+        std::vector<double> re, tc(circ ? 3 * (size_t)nh : 0);  // tc: the circles of the hosted segments
         std::vector<int64_t> slot_begin((size_t)nq, -1), slot_len((size_t)nq, 0);
         for (int64_t i = 0; i < nh; ++i) {
             const int64_t q = slots[(size_t)hosted[(size_t)i]];
@@ -150,14 +173,20 @@ int32_t knn_rank_resident(locrec_knn_index *ix, const std::vector<int64_t> &slot
             tb[(size_t)i] = slot_begin[(size_t)q];
             tl[(size_t)i] = slot_len[(size_t)q];
             tt[(size_t)i] = targets[hosted[(size_t)i]];
+            if (circ) {
+                tc[(size_t)i] = near->center_lat[hosted[(size_t)i]];
+                tc[(size_t)(nh + i)] = near->center_lon[hosted[(size_t)i]];
+                tc[(size_t)(2 * nh + i)] = near->radius[hosted[(size_t)i]];
+            }
         }
         DevBuf<int64_t> d_rp, d_hin, d_hout;
         DevBuf<double> d_re;
         LOCREC_TRY(d_rp.upload(rp, s));
         LOCREC_TRY(d_re.upload(re, s));
-        LOCREC_TRY(d_hin.alloc(RankIo::in_words(0, nh) + (unvisited ? knn_rk_ex_words(nh) : 0)));
-        LOCREC_TRY(d_hout.alloc(RankIo::out_words(nh, N)));
-        const RankIo hio(d_hin.p, d_hout.p, n_places, nh, N, &io);  // (the places table is already there)
+        LOCREC_TRY(d_hin.alloc(RankIo::in_words(0, nh, circ) + (unvisited ? knn_rk_ex_words(nh) : 0)));
+        LOCREC_TRY(d_hout.alloc(RankIo::out_words(nh, N, circ)));
+        const RankIo hio(d_hin.p, d_hout.p, n_places, nh, N, &io, circ);  // (the places table is already there)
+        if (circ) LOCREC_HIP_TRY(hipMemcpyAsync(hio.clat, tc.data(), 3 * (size_t)nh * 8, hipMemcpyHostToDevice, s));  // (lat | lon | radius)
         LOCREC_HIP_TRY(hipMemcpyAsync(hio.tgt, tt.data(), (size_t)nh * 8, hipMemcpyHostToDevice, s));
         LOCREC_HIP_TRY(hipMemcpyAsync(hio.base, tb.data(), (size_t)nh * 8, hipMemcpyHostToDevice, s));
         LOCREC_HIP_TRY(hipMemcpyAsync(hio.len, tl.data(), (size_t)nh * 8, hipMemcpyHostToDevice, s));
@@ -165,10 +194,10 @@ int32_t knn_rank_resident(locrec_knn_index *ix, const std::vector<int64_t> &slot
         if (unvisited) {
             std::vector<int32_t> rows((size_t)nh);
             for (int64_t i = 0; i < nh; ++i) rows[(size_t)i] = row_of_slot(slots[(size_t)hosted[(size_t)i]]);
-            LOCREC_TRY(knn_rk_rated_lists(ix, rows, d_hin.p + RankIo::in_words(0, nh), s, hex));
+            LOCREC_TRY(knn_rk_rated_lists(ix, rows, d_hin.p + RankIo::in_words(0, nh, circ), s, hex));
         }
         LOCREC_TRY(hio.rank(d_rp.p, d_re.p, nh, s, hex));
-        LOCREC_TRY(hio.read_back_to(hosted, out_ids, out_scores, out_counts, s));
+        LOCREC_TRY(hio.read_back_to(hosted, out_ids, out_scores, out_counts, s, circ ? near->meters : nullptr));
         const RankBatchStats &h = rank_batch_stats();
         // (the overflow queries were empty one-block segments of the first call: counted where their rows were ranked)
         if (!h.sorted) {
@@ -203,7 +232,7 @@ int32_t knn_fetch_ranked(locrec_knn_index *ix, int64_t nq, bool unvisited, int64
 int32_t knn_recommend_ranked_batch(locrec_knn_index *ix, int64_t nq, const int64_t *person_ids, double pw, double cw, int64_t k,
                                    bool unvisited, int64_t n_places, const int64_t *place_ids, const int64_t *place_region_ids,
                                    const int64_t *target_region_ids, int64_t max_recommendations, int64_t *out_place_ids,
-                                   double *out_estimated_ratings, int64_t *out_counts)
+                                   double *out_estimated_ratings, int64_t *out_counts, const KnnRankNear *near = nullptr)
 {
     // the batch itself, with its requires and "No such person": the rows stay on the device (capacity 0: sizes only)
     std::vector<int64_t> off((size_t)std::max<int64_t>(nq, 0) + 1, 0);
@@ -223,7 +252,7 @@ int32_t knn_recommend_ranked_batch(locrec_knn_index *ix, int64_t nq, const int64
     std::vector<int64_t> len((size_t)nq);
     for (int64_t i = 0; i < nq; ++i) len[(size_t)i] = off[(size_t)i + 1] - off[(size_t)i];
     return knn_rank_resident(ix, slots, len.data(), unvisited, n_places, place_ids, place_region_ids, target_region_ids,
-                             max_recommendations, out_place_ids, out_estimated_ratings, out_counts);
+                             max_recommendations, out_place_ids, out_estimated_ratings, out_counts, near);
 }
 
 }  // namespace
@@ -265,4 +294,21 @@ extern "C" int32_t locrec_knn_recommend_ranked_batch_unvisited(locrec_knn_index 
 {
     return knn_recommend_ranked_batch(ix, nq, person_ids, pw, cw, k, true, n_places, place_ids, place_region_ids,
                                       target_region_ids, max_recommendations, out_place_ids, out_estimated_ratings, out_counts);
+} LOCREC_CATCH_ALL
+
+extern "C" int32_t locrec_knn_recommend_ranked_batch_near(
+    locrec_knn_index *ix, int64_t nq, const int64_t *person_ids, double pw, double cw, int64_t k, int64_t n_places,
+    const int64_t *place_ids, const int64_t *place_region_ids, const double *place_latitudes, const double *place_longitudes,
+    const int64_t *target_region_ids, const double *center_latitudes, const double *center_longitudes, const double *radius_meters,
+    int64_t max_recommendations, int32_t unvisited, int64_t *out_place_ids, double *out_estimated_ratings, double *out_meters,
+    int64_t *out_counts) try
+{
+    // the circles' requires first: before the index is looked at
+    if (nq < 0 || n_places < 0 || n_places >= ((int64_t)1 << 31)) return fail(LOCREC_E_INVALID_ARG, "query or place count out of range");
+    if ((nq > 0 && (!center_latitudes || !center_longitudes || !radius_meters)) || (n_places > 0 && (!place_latitudes || !place_longitudes)))
+        return fail(LOCREC_E_INVALID_ARG, "null coordinate or radius array");
+    LOCREC_TRY(rank_near_check_host(nq, center_latitudes, center_longitudes, radius_meters, n_places, place_latitudes, place_longitudes));
+    const KnnRankNear near = {place_latitudes, place_longitudes, center_latitudes, center_longitudes, radius_meters, out_meters};
+    return knn_recommend_ranked_batch(ix, nq, person_ids, pw, cw, k, unvisited != 0, n_places, place_ids, place_region_ids,
+                                      target_region_ids, max_recommendations, out_place_ids, out_estimated_ratings, out_counts, &near);
 } LOCREC_CATCH_ALL

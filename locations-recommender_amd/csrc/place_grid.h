@@ -99,7 +99,7 @@ __device__ __forceinline__ uint64_t cell_key(int64_t region_rank, int32_t band, 
 }
 
 // keys of the gridded side, to be sorted with their rows
-__global__ void pr_place_keys(int64_t np, const double *lat, const double *lon, const int64_t *region, const int64_t *regions,
+[[maybe_unused]] __global__ void pr_place_keys(int64_t np, const double *lat, const double *lon, const int64_t *region, const int64_t *regions,
                               int32_t nr, Grid g, uint64_t *keys, uint32_t *rows)
 {
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -162,7 +162,7 @@ struct LocationError {
 // Side A: a row that takes part (ts == nullptr, or ts[i] >= from) and whose region is listed - the list is side B's -
 // meets a row of side B: it marks its region, and its Location must be valid (the reference's UDF constructs both
 // Locations for every joined pair)
-__global__ void check_side_a(int64_t n, const int64_t *ts, int64_t from, const double *lat, const double *lon,
+[[maybe_unused]] __global__ void check_side_a(int64_t n, const int64_t *ts, int64_t from, const double *lat, const double *lon,
                              const int64_t *region, const int64_t *regions, int32_t nr, uint32_t *marked, LocationError *err)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -174,7 +174,7 @@ __global__ void check_side_a(int64_t n, const int64_t *ts, int64_t from, const d
 }
 
 // Side B: checked where a row of side A marked the region
-__global__ void check_side_b(int64_t n, const double *lat, const double *lon, const int64_t *region, const int64_t *regions,
+[[maybe_unused]] __global__ void check_side_b(int64_t n, const double *lat, const double *lon, const int64_t *region, const int64_t *regions,
                              int32_t nr, const uint32_t *marked, LocationError *err)
 {
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -55,6 +55,29 @@ struct RankExclude {
     int64_t n = 0;
 };
 
+// the circles of one ranker call (center_lat NULL: none): per segment a centre in degrees and a radius in metres, per
+// row of the place table its coordinates
+struct RankNear {
+    const double *center_lat = nullptr, *center_lon = nullptr, *radius = nullptr, *place_lat = nullptr, *place_lon = nullptr;
+};
+
+// "Within reach": the same with a circle per segment, and lists only when ex.begin is given.  Segment s keeps a row iff
+// its id is a place of the target region and some listing of that place in that region lies within radius[s] metres of
+// the centre - distance_meters (place_grid.h) <= radius, +inf keeping every place.  out_meters (NULL: not wanted; the
+// shape of out_scores) gets the distance of the first such listing in the table's input order, padding 0.0.  A radius
+// that is NaN or negative, or a centre or a place row outside Location's ranges, is refused with the segments in the
+// plan step, before any row is read.  With near.center_lat NULL this is the plain / excluding entry.
+int32_t rank_segments_device_near(int64_t n_segments, const int64_t *seg_begin, const int64_t *seg_len, const int64_t *ids,
+                                  const double *scores, int64_t n_places, const int64_t *place_ids,
+                                  const int64_t *place_region_ids, const int64_t *target_region_ids, int64_t max_recommendations,
+                                  const RankExclude &ex, const RankNear &near, int64_t *out_ids, double *out_scores,
+                                  double *out_meters, int64_t *out_counts, const unsigned long long *invalid_flag,
+                                  int64_t host_assembled, hipStream_t s);
+
+// the same requires for host arrays, before any device work (the public entries and the KNN / SG near calls)
+int32_t rank_near_check_host(int64_t n_segments, const double *center_lat, const double *center_lon, const double *radius,
+                             int64_t n_places, const double *place_lat, const double *place_lon);
+
 // One ranker call's device arrays, carved out of one input and one output allocation of 8-byte words:
 //   in   [place ids | place regions | targets | bases | lengths]   (without the places table when it is places_of's)
 //   out  [ids | scores | counts]
@@ -63,24 +86,43 @@ struct RankIo {
     int64_t n_places, nseg, N;
     int64_t *pid, *preg, *tgt, *base, *len, *oid, *ocnt;
     double *osc;
-    static size_t in_words(int64_t n_places, int64_t nseg) { return 2 * (size_t)n_places + 3 * (size_t)nseg; }
-    static size_t out_words(int64_t nseg, int64_t N) { return 2 * (size_t)(nseg * N) + (size_t)nseg; }
-    RankIo(int64_t *in, int64_t *out, int64_t n_places_, int64_t nseg_, int64_t N_, const RankIo *places_of = nullptr)
+    // with circles (near): [... | lengths | centre lat | centre lon | radius | place lat | place lon] (again without the
+    // places' words when they are places_of's) and [ids | scores | counts | meters]
+    bool near = false;
+    double *clat = nullptr, *clon = nullptr, *rad = nullptr, *plat = nullptr, *plon = nullptr, *omet = nullptr;
+    static size_t in_words(int64_t n_places, int64_t nseg, bool near = false)
+    {
+        return (near ? 4 : 2) * (size_t)n_places + (near ? 6 : 3) * (size_t)nseg;
+    }
+    static size_t out_words(int64_t nseg, int64_t N, bool near = false) { return (near ? 3 : 2) * (size_t)(nseg * N) + (size_t)nseg; }
+    RankIo(int64_t *in, int64_t *out, int64_t n_places_, int64_t nseg_, int64_t N_, const RankIo *places_of = nullptr,
+           bool near_ = false)
         : n_places(n_places_), nseg(nseg_), N(N_), pid(places_of ? places_of->pid : in), preg(places_of ? places_of->preg : in + n_places),
           tgt(places_of ? in : in + 2 * n_places), base(tgt + nseg), len(base + nseg), oid(out), ocnt(out + 2 * nseg * N),
-          osc(reinterpret_cast<double *>(out + nseg * N))
+          osc(reinterpret_cast<double *>(out + nseg * N)), near(near_)
     {
+        if (!near) return;
+        clat = reinterpret_cast<double *>(len + nseg);
+        clon = clat + nseg;
+        rad = clon + nseg;
+        plat = places_of ? places_of->plat : rad + nseg;
+        plon = places_of ? places_of->plon : plat + n_places;
+        omet = reinterpret_cast<double *>(ocnt + nseg);
     }
     int32_t rank(const int64_t *ids, const double *scores, int64_t host_assembled, hipStream_t s, const RankExclude &ex = {}) const
     {
+        if (near)
+            return rank_segments_device_near(nseg, base, len, ids, scores, n_places, pid, preg, tgt, N, ex, {clat, clon, rad, plat, plon},
+                                             oid, osc, omet, ocnt, nullptr, host_assembled, s);
         if (ex.begin)
             return rank_segments_device_excluding(nseg, base, len, ids, scores, n_places, pid, preg, tgt, N, ex.begin, ex.len, ex.n,
                                                   ex.ids, oid, osc, ocnt, nullptr, host_assembled, s);
         return rank_segments_device(nseg, base, len, ids, scores, n_places, pid, preg, tgt, N, oid, osc, ocnt, nullptr, host_assembled, s);
     }
     // nseg x N ids and scores and nseg counts to host arrays of that shape, then the call's one wait
-    int32_t read_back(int64_t *ids, double *scores, int64_t *counts, hipStream_t s) const
+    int32_t read_back(int64_t *ids, double *scores, int64_t *counts, hipStream_t s, double *meters = nullptr) const
     {
+        if (N > 0 && meters) LOCREC_HIP_TRY(hipMemcpyAsync(meters, omet, (size_t)(nseg * N) * 8, hipMemcpyDeviceToHost, s));
         if (N > 0) {
             LOCREC_HIP_TRY(hipMemcpyAsync(ids, oid, (size_t)(nseg * N) * 8, hipMemcpyDeviceToHost, s));
             LOCREC_HIP_TRY(hipMemcpyAsync(scores, osc, (size_t)(nseg * N) * 8, hipMemcpyDeviceToHost, s));
@@ -90,12 +132,14 @@ struct RankIo {
         return LOCREC_OK;
     }
     // the same, segment c's N rows and count going to position to[c] of the caller's arrays
-    int32_t read_back_to(const std::vector<int64_t> &to, int64_t *ids, double *scores, int64_t *counts, hipStream_t s) const
+    int32_t read_back_to(const std::vector<int64_t> &to, int64_t *ids, double *scores, int64_t *counts, hipStream_t s,
+                         double *meters = nullptr) const
     {
         std::vector<int64_t> hid((size_t)(nseg * N)), hcnt((size_t)nseg);
-        std::vector<double> hsc((size_t)(nseg * N));
-        LOCREC_TRY(read_back(hid.data(), hsc.data(), hcnt.data(), s));
+        std::vector<double> hsc((size_t)(nseg * N)), hmet(meters ? (size_t)(nseg * N) : 0);
+        LOCREC_TRY(read_back(hid.data(), hsc.data(), hcnt.data(), s, meters ? hmet.data() : nullptr));
         for (int64_t c = 0; c < nseg; ++c) {
+            if (meters) std::copy(hmet.begin() + c * N, hmet.begin() + (c + 1) * N, meters + to[(size_t)c] * N);
             std::copy(hid.begin() + c * N, hid.begin() + (c + 1) * N, ids + to[(size_t)c] * N);
             std::copy(hsc.begin() + c * N, hsc.begin() + (c + 1) * N, scores + to[(size_t)c] * N);
             counts[to[(size_t)c]] = hcnt[(size_t)c];

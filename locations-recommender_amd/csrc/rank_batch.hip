@@ -28,6 +28,17 @@
 //                                 would be kept pays it.  The table is global memory: a list has no length limit.  With
 //                                 every list empty the plain kernels run.
 //
+//   circles                       (rank_segments_device_near, locrec_rank_recommendations_batch_near) per segment a
+//                                 centre and a radius in metres, per place row its coordinates: a row is kept only if
+//                                 some listing of its place in the target region lies within the radius by
+//                                 distance_meters (place_grid.h).  The region table's sorts carry the input row of
+//                                 every table position, so a search's lower bound leads to the listings' coordinates in
+//                                 input order.  rb_check_near refuses bad radii and coordinates in the plan step;
+//                                 rb_select_near / rb_count_near / rb_scatter_near test a row after the membership (and
+//                                 the list, read at run time: a NULL table is none), rb_merge_near and
+//                                 rb_emit_sorted_near write out_meters for the rows they emit - evaluated again for
+//                                 those N rows, not carried through the list.
+//
 // A call waits for the stream once (the plan's totals and the validity of the segments, before any kernel reads a row)
 // and, on the global path, once more for the number of kept rows - whatever the number of segments.  Its work buffers
 // are local to the call: each hipFree at the end waits for the device as well (about twenty a call, again whatever the
@@ -42,13 +53,21 @@
 //   rb_select_ex    27 / 20512 / 0 / 7        rb_expand_excluded  11 / 0 / 0 / 8
 //   rb_count_ex     12 / 4 / 0 / 8
 //   rb_scatter_ex   24 / 16 / 0 / 8
-// The list is 20 bytes an entry: 20.5 KB of LDS a block, seven blocks of 256 threads a CU by LDS.
+//   rb_select_near  113 / 20512 / 0 / 4       rb_merge_near        115 / 20512 / 0 / 4
+//   rb_count_near   91 / 4 / 0 / 5            rb_emit_sorted_near  94 / 16 / 0 / 5
+//   rb_scatter_near 96 / 16 / 0 / 5           rb_check_near        12 / 0 / 0 / 8
+// The list is 20 bytes an entry: 20.5 KB of LDS a block, seven blocks of 256 threads a CU by LDS.  The _near kernels are
+// bound by registers instead: the fp64 sin / cos / asin of distance_meters take the select body from 27 to 113 VGPRs
+// (4 waves a SIMD, no scratch).  The fused form is kept all the same ("Within reach"): a separate pass
+// that marks the kept rows would read every id again, write and read a flag per row and add two launches to a call
+// that is made of launch latency, while only a row that passed the region join - and the latitude reject - evaluates.
 
 #include "dev_prims.h"
 
 #include <algorithm>
 
 #include "common.h"
+#include "place_grid.h"
 #include "prep_cols.h"
 #include "rank_batch.h"
 
@@ -238,14 +257,82 @@ __device__ __forceinline__ int64_t rb_segment_of(const uint32_t *first, int64_t 
     return a - 1;
 }
 
+// ---- the circle --------------------------------------------------------------------------------------------------------
+// What a _near kernel knows beside its siblings' arguments: segment s keeps a row only if some listing of its place in the
+// target region lies within rad[s] metres of (clat[s], clon[s]).  Table position t is input row trow[t] of the place
+// table (the value the region table's two sorts carry), so the listings of one (region, id) stand in input order and
+// the first one inside the circle is the one that counts.  meters (NULL: not wanted): the output rows' distances.
+struct RbNear {
+    const double *clat, *clon, *rad, *plat, *plon;
+    const uint32_t *trow;
+    const int32_t *lo, *hi;
+    const uint64_t *table_ids;
+    double *meters;
+};
+
+// The circle of one segment.  band: the radius as degrees of latitude with make_grid's margins - a listing further
+// north or south than that is outside whatever its longitude (distance >= R |dlat|; the margin of 1e-9 relative and
+// 1e-12 degrees is far above distance_meters' rounding), so the reject is on the safe side and the exact test decides
+// everything else.  An infinite radius keeps every listing without evaluating anything.
+struct RbCircle {
+    double lat, lon, rad, band;
+    bool all;
+};
+
+__device__ __forceinline__ RbCircle rb_circle_of(const RbNear &nr, int64_t s)
+{
+    RbCircle c;
+    c.lat = nr.clat[s];
+    c.lon = nr.clon[s];
+    c.rad = nr.rad[s];
+    c.all = c.rad == INFINITY;
+    c.band = c.rad / kEarthRadiusMeters * (180.0 / kPi) * (1.0 + 1e-9) + 1e-12;
+    return c;
+}
+
+// table position a is the first listing of `key` (a < thi): is one of its listings inside the circle?  *meters: the
+// distance of the first that is - bit for bit distance_meters of (centre, listing), as locrec_distance_meters has it.
+__device__ __forceinline__ bool rb_within(const RbNear &nr, const RbCircle &c, int32_t a, int32_t thi, uint64_t key, double *meters)
+{
+    for (; a < thi && nr.table_ids[a] == key; ++a) {
+        const uint32_t j = nr.trow[a];
+        const double plat = nr.plat[j];
+        if (!c.all && fabs(plat - c.lat) > c.band) continue;
+        const double d = distance_meters(c.lat, c.lon, plat, nr.plon[j]);
+        if (d <= c.rad || c.all) {
+            *meters = d;
+            return true;
+        }
+    }
+    return false;
+}
+
+// the distance an output row of segment s reports for the kept id `key`
+__device__ __forceinline__ double rb_meters_of(const RbNear &nr, const RbCircle &c, int64_t s, uint64_t key)
+{
+    const int32_t thi = nr.hi[s];
+    int32_t a = nr.lo[s], b = thi;
+    while (a < b) {
+        const int32_t mid = (int32_t)(((uint32_t)a + (uint32_t)b) >> 1);
+        if (nr.table_ids[mid] < key) a = mid + 1; else b = mid;
+    }
+    double d = 0.0;
+    rb_within(nr, c, a, thi, key, &d);
+    return d;
+}
+
 // the sorted list's first w entries -> output row s (padded to N)
+template <bool NEAR>
 __device__ __forceinline__ void rb_emit_row(const RbList &L, int w, int N, int64_t s, int64_t begin, const double *scores,
-                                            int64_t *out_ids, double *out_scores, int64_t *out_counts)
+                                            int64_t *out_ids, double *out_scores, int64_t *out_counts, const RbNear &nr)
 {
     for (int j = threadIdx.x; j < N; j += kRbThreads) {
         const int64_t o = s * (int64_t)N + j;
         out_ids[o] = j < w ? id_of_key(L.id[j]) : -1;
         out_scores[o] = j < w ? scores[begin + L.row[j]] : 0.0;
+        if constexpr (NEAR) {
+            if (nr.meters) nr.meters[o] = j < w ? rb_meters_of(nr, rb_circle_of(nr, s), s, L.id[j]) : 0.0;
+        }
     }
     if (threadIdx.x == 0) out_counts[s] = w;
 }
@@ -277,15 +364,17 @@ __device__ __forceinline__ bool rb_excluded(const uint64_t *xkeys, uint32_t a, u
     return a < end && xkeys[a] == key;
 }
 
-// The three kernels that test a row are bodies with the exclusion as a template parameter: the plain kernels keep
-// their signatures and, with EX false, their code; the _ex kernels take the pair table as well.
-template <bool EX>
+// The three kernels that test a row are bodies with the exclusion and the circle as template parameters: the plain
+// kernels keep their signatures and, with EX and NEAR false, their code; the _ex kernels take the pair table as well;
+// the _near kernels take the circle and read the lists at run time (xkeys NULL: none), so they are three and not six.
+template <bool EX, bool NEAR>
 __device__ __forceinline__ void rb_select_body(int64_t n_seg, const uint32_t *first, const uint32_t *pfirst,
                                                const int64_t *seg_begin, const int64_t *seg_len, const int32_t *lo,
                                                const int32_t *hi, const uint64_t *table_ids, const int64_t *ids,
                                                const double *scores, int64_t chunk, int N, uint64_t *pk, uint64_t *pid,
                                                uint32_t *prow, int32_t *pcount, int64_t *out_ids, double *out_scores,
-                                               int64_t *out_counts, const uint32_t *xfirst, const uint64_t *xkeys)
+                                               int64_t *out_counts, const uint32_t *xfirst, const uint64_t *xkeys,
+                                               const RbNear &nr)
 {
     __shared__ RbList L;
     const uint32_t w = blockIdx.x;
@@ -295,11 +384,15 @@ __device__ __forceinline__ void rb_select_body(int64_t n_seg, const uint32_t *fi
     const int32_t tlo = lo[s], thi = hi[s];
     uint32_t xa = 0, xb = 0;
     if constexpr (EX) {
-        xa = xfirst[s];
-        xb = xfirst[s + 1];
+        if (!NEAR || xkeys) {
+            xa = xfirst[s];
+            xb = xfirst[s + 1];
+        }
     }
     const int64_t r0 = (int64_t)c * chunk;
     const int64_t r1 = thi > tlo ? min(len, nch == 1 ? len : r0 + chunk) : 0;  // no place in the region: nothing to read
+    RbCircle cir = {};
+    if constexpr (NEAR) cir = rb_circle_of(nr, s);
     if (threadIdx.x == 0) {
         L.count = 0;
         L.have_thr = 0;
@@ -316,13 +409,17 @@ __device__ __forceinline__ void rb_select_body(int64_t n_seg, const uint32_t *fi
             }
             bool keep = a < thi && table_ids[a] == key;
             if constexpr (EX) keep = keep && !rb_excluded(xkeys, xa, xb, key);
+            if constexpr (NEAR) {
+                double d;
+                keep = keep && (cir.all || rb_within(nr, cir, a, thi, key, &d));
+            }
             if (keep) rb_push(L, score_desc_key(scores[begin + r]), key, (uint32_t)r);
         }
     }
     __syncthreads();
     const int wn = rb_compact(L, N);
     if (nch == 1) {
-        rb_emit_row(L, wn, N, s, begin, scores, out_ids, out_scores, out_counts);
+        rb_emit_row<NEAR>(L, wn, N, s, begin, scores, out_ids, out_scores, out_counts, nr);
         return;
     }
     const int64_t slot = (int64_t)pfirst[s] + c;
@@ -341,8 +438,8 @@ __global__ __launch_bounds__(kRbThreads) void rb_select(int64_t n_seg, const uin
                                                         uint64_t *pid, uint32_t *prow, int32_t *pcount, int64_t *out_ids,
                                                         double *out_scores, int64_t *out_counts)
 {
-    rb_select_body<false>(n_seg, first, pfirst, seg_begin, seg_len, lo, hi, table_ids, ids, scores, chunk, N, pk, pid, prow,
-                          pcount, out_ids, out_scores, out_counts, nullptr, nullptr);
+    rb_select_body<false, false>(n_seg, first, pfirst, seg_begin, seg_len, lo, hi, table_ids, ids, scores, chunk, N, pk, pid, prow,
+                                 pcount, out_ids, out_scores, out_counts, nullptr, nullptr, RbNear{});
 }
 
 __global__ __launch_bounds__(kRbThreads) void rb_select_ex(int64_t n_seg, const uint32_t *first, const uint32_t *pfirst,
@@ -353,14 +450,26 @@ __global__ __launch_bounds__(kRbThreads) void rb_select_ex(int64_t n_seg, const 
                                                            double *out_scores, int64_t *out_counts, const uint32_t *xfirst,
                                                            const uint64_t *xkeys)
 {
-    rb_select_body<true>(n_seg, first, pfirst, seg_begin, seg_len, lo, hi, table_ids, ids, scores, chunk, N, pk, pid, prow,
-                         pcount, out_ids, out_scores, out_counts, xfirst, xkeys);
+    rb_select_body<true, false>(n_seg, first, pfirst, seg_begin, seg_len, lo, hi, table_ids, ids, scores, chunk, N, pk, pid, prow,
+                                pcount, out_ids, out_scores, out_counts, xfirst, xkeys, RbNear{});
 }
 
-__global__ __launch_bounds__(kRbThreads) void rb_merge(const uint32_t *first, const uint32_t *pfirst, const int64_t *seg_begin,
-                                                       const double *scores, int N, const uint64_t *pk, const uint64_t *pid,
-                                                       const uint32_t *prow, const int32_t *pcount, int64_t *out_ids,
-                                                       double *out_scores, int64_t *out_counts)
+__global__ __launch_bounds__(kRbThreads) void rb_select_near(int64_t n_seg, const uint32_t *first, const uint32_t *pfirst,
+                                                             const int64_t *seg_begin, const int64_t *seg_len, const int64_t *ids,
+                                                             const double *scores, int64_t chunk, int N, uint64_t *pk,
+                                                             uint64_t *pid, uint32_t *prow, int32_t *pcount, int64_t *out_ids,
+                                                             double *out_scores, int64_t *out_counts, const uint32_t *xfirst,
+                                                             const uint64_t *xkeys, RbNear nr)
+{
+    rb_select_body<true, true>(n_seg, first, pfirst, seg_begin, seg_len, nr.lo, nr.hi, nr.table_ids, ids, scores, chunk, N, pk, pid,
+                               prow, pcount, out_ids, out_scores, out_counts, xfirst, xkeys, nr);
+}
+
+template <bool NEAR>
+__device__ __forceinline__ void rb_merge_body(const uint32_t *first, const uint32_t *pfirst, const int64_t *seg_begin,
+                                              const double *scores, int N, const uint64_t *pk, const uint64_t *pid,
+                                              const uint32_t *prow, const int32_t *pcount, int64_t *out_ids, double *out_scores,
+                                              int64_t *out_counts, const RbNear &nr)
 {
     __shared__ RbList L;
     const int64_t s = blockIdx.x;
@@ -382,17 +491,33 @@ __global__ __launch_bounds__(kRbThreads) void rb_merge(const uint32_t *first, co
     }
     __syncthreads();
     const int wn = rb_compact(L, N);
-    rb_emit_row(L, wn, N, s, seg_begin[s], scores, out_ids, out_scores, out_counts);
+    rb_emit_row<NEAR>(L, wn, N, s, seg_begin[s], scores, out_ids, out_scores, out_counts, nr);
+}
+
+__global__ __launch_bounds__(kRbThreads) void rb_merge(const uint32_t *first, const uint32_t *pfirst, const int64_t *seg_begin,
+                                                       const double *scores, int N, const uint64_t *pk, const uint64_t *pid,
+                                                       const uint32_t *prow, const int32_t *pcount, int64_t *out_ids,
+                                                       double *out_scores, int64_t *out_counts)
+{
+    rb_merge_body<false>(first, pfirst, seg_begin, scores, N, pk, pid, prow, pcount, out_ids, out_scores, out_counts, RbNear{});
+}
+
+__global__ __launch_bounds__(kRbThreads) void rb_merge_near(const uint32_t *first, const uint32_t *pfirst, const int64_t *seg_begin,
+                                                            const double *scores, int N, const uint64_t *pk, const uint64_t *pid,
+                                                            const uint32_t *prow, const int32_t *pcount, int64_t *out_ids,
+                                                            double *out_scores, int64_t *out_counts, RbNear nr)
+{
+    rb_merge_body<true>(first, pfirst, seg_begin, scores, N, pk, pid, prow, pcount, out_ids, out_scores, out_counts, nr);
 }
 
 // ---- the global path --------------------------------------------------------------------------------------------------
 
 // kept rows of one work item
-template <bool EX>
+template <bool EX, bool NEAR>
 __device__ __forceinline__ void rb_count_body(int64_t n_seg, const uint32_t *first, const int64_t *seg_begin,
                                               const int64_t *seg_len, const int32_t *lo, const int32_t *hi,
                                               const uint64_t *table_ids, const int64_t *ids, int64_t chunk, uint32_t *cnt,
-                                              uint32_t n_items, const uint32_t *xfirst, const uint64_t *xkeys)
+                                              uint32_t n_items, const uint32_t *xfirst, const uint64_t *xkeys, const RbNear &nr)
 {
     __shared__ uint32_t total;
     const uint32_t w = blockIdx.x;
@@ -410,9 +535,13 @@ __device__ __forceinline__ void rb_count_body(int64_t n_seg, const uint32_t *fir
     const int64_t r1 = thi > tlo ? min(len, nch == 1 ? len : r0 + chunk) : 0;
     uint32_t xa = 0, xb = 0;
     if constexpr (EX) {
-        xa = xfirst[s];
-        xb = xfirst[s + 1];
+        if (!NEAR || xkeys) {
+            xa = xfirst[s];
+            xb = xfirst[s + 1];
+        }
     }
+    RbCircle cir = {};
+    if constexpr (NEAR) cir = rb_circle_of(nr, s);
     uint32_t mine = 0;
     for (int64_t r = r0 + threadIdx.x; r < r1; r += kRbThreads) {
         const uint64_t key = ordered_key(ids[begin + r]);
@@ -423,6 +552,10 @@ __device__ __forceinline__ void rb_count_body(int64_t n_seg, const uint32_t *fir
         }
         bool keep = a < thi && table_ids[a] == key;
         if constexpr (EX) keep = keep && !rb_excluded(xkeys, xa, xb, key);
+        if constexpr (NEAR) {
+            double d;
+            keep = keep && (cir.all || rb_within(nr, cir, a, thi, key, &d));
+        }
         if (keep) ++mine;
     }
     if (mine) atomicAdd(&total, mine);
@@ -435,7 +568,8 @@ __global__ __launch_bounds__(kRbThreads) void rb_count(int64_t n_seg, const uint
                                                        const uint64_t *table_ids, const int64_t *ids, int64_t chunk,
                                                        uint32_t *cnt, uint32_t n_items)
 {
-    rb_count_body<false>(n_seg, first, seg_begin, seg_len, lo, hi, table_ids, ids, chunk, cnt, n_items, nullptr, nullptr);
+    rb_count_body<false, false>(n_seg, first, seg_begin, seg_len, lo, hi, table_ids, ids, chunk, cnt, n_items, nullptr, nullptr,
+                                RbNear{});
 }
 
 __global__ __launch_bounds__(kRbThreads) void rb_count_ex(int64_t n_seg, const uint32_t *first, const int64_t *seg_begin,
@@ -444,17 +578,25 @@ __global__ __launch_bounds__(kRbThreads) void rb_count_ex(int64_t n_seg, const u
                                                           uint32_t *cnt, uint32_t n_items, const uint32_t *xfirst,
                                                           const uint64_t *xkeys)
 {
-    rb_count_body<true>(n_seg, first, seg_begin, seg_len, lo, hi, table_ids, ids, chunk, cnt, n_items, xfirst, xkeys);
+    rb_count_body<true, false>(n_seg, first, seg_begin, seg_len, lo, hi, table_ids, ids, chunk, cnt, n_items, xfirst, xkeys, RbNear{});
+}
+
+__global__ __launch_bounds__(kRbThreads) void rb_count_near(int64_t n_seg, const uint32_t *first, const int64_t *seg_begin,
+                                                            const int64_t *seg_len, const int64_t *ids, int64_t chunk,
+                                                            uint32_t *cnt, uint32_t n_items, const uint32_t *xfirst,
+                                                            const uint64_t *xkeys, RbNear nr)
+{
+    rb_count_body<true, true>(n_seg, first, seg_begin, seg_len, nr.lo, nr.hi, nr.table_ids, ids, chunk, cnt, n_items, xfirst, xkeys, nr);
 }
 
 // the kept rows of one work item, in row order, at base[w] ..: segment, row, id key, and the row's own position as the
 // payload of the first sort
-template <bool EX>
+template <bool EX, bool NEAR>
 __device__ __forceinline__ void rb_scatter_body(int64_t n_seg, const uint32_t *first, const int64_t *seg_begin,
                                                 const int64_t *seg_len, const int32_t *lo, const int32_t *hi,
                                                 const uint64_t *table_ids, const int64_t *ids, int64_t chunk,
                                                 const uint32_t *base, uint32_t *kseg, uint32_t *krow, uint64_t *keys,
-                                                uint32_t *vals, const uint32_t *xfirst, const uint64_t *xkeys)
+                                                uint32_t *vals, const uint32_t *xfirst, const uint64_t *xkeys, const RbNear &nr)
 {
     __shared__ uint32_t wave_cnt[kRbThreads / 64];
     const uint32_t w = blockIdx.x;
@@ -467,9 +609,13 @@ __device__ __forceinline__ void rb_scatter_body(int64_t n_seg, const uint32_t *f
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t xa = 0, xb = 0;
     if constexpr (EX) {
-        xa = xfirst[s];
-        xb = xfirst[s + 1];
+        if (!NEAR || xkeys) {
+            xa = xfirst[s];
+            xb = xfirst[s + 1];
+        }
     }
+    RbCircle cir = {};
+    if constexpr (NEAR) cir = rb_circle_of(nr, s);
     uint32_t pos = base[w];
     for (int64_t t0 = r0; t0 < r1; t0 += kRbThreads) {
         const int64_t r = t0 + threadIdx.x;
@@ -484,6 +630,10 @@ __device__ __forceinline__ void rb_scatter_body(int64_t n_seg, const uint32_t *f
             }
             keep = a < thi && table_ids[a] == key;
             if constexpr (EX) keep = keep && !rb_excluded(xkeys, xa, xb, key);
+            if constexpr (NEAR) {
+                double d;
+                keep = keep && (cir.all || rb_within(nr, cir, a, thi, key, &d));
+            }
         }
         const unsigned long long m = __ballot(keep);
         __syncthreads();  // the previous tile's wave_cnt has been read
@@ -511,8 +661,8 @@ __global__ __launch_bounds__(kRbThreads) void rb_scatter(int64_t n_seg, const ui
                                                          const uint32_t *base, uint32_t *kseg, uint32_t *krow,
                                                          uint64_t *keys, uint32_t *vals)
 {
-    rb_scatter_body<false>(n_seg, first, seg_begin, seg_len, lo, hi, table_ids, ids, chunk, base, kseg, krow, keys, vals, nullptr,
-                           nullptr);
+    rb_scatter_body<false, false>(n_seg, first, seg_begin, seg_len, lo, hi, table_ids, ids, chunk, base, kseg, krow, keys, vals,
+                                  nullptr, nullptr, RbNear{});
 }
 
 __global__ __launch_bounds__(kRbThreads) void rb_scatter_ex(int64_t n_seg, const uint32_t *first, const int64_t *seg_begin,
@@ -522,8 +672,18 @@ __global__ __launch_bounds__(kRbThreads) void rb_scatter_ex(int64_t n_seg, const
                                                             uint64_t *keys, uint32_t *vals, const uint32_t *xfirst,
                                                             const uint64_t *xkeys)
 {
-    rb_scatter_body<true>(n_seg, first, seg_begin, seg_len, lo, hi, table_ids, ids, chunk, base, kseg, krow, keys, vals, xfirst,
-                          xkeys);
+    rb_scatter_body<true, false>(n_seg, first, seg_begin, seg_len, lo, hi, table_ids, ids, chunk, base, kseg, krow, keys, vals, xfirst,
+                                 xkeys, RbNear{});
+}
+
+__global__ __launch_bounds__(kRbThreads) void rb_scatter_near(int64_t n_seg, const uint32_t *first, const int64_t *seg_begin,
+                                                              const int64_t *seg_len, const int64_t *ids, int64_t chunk,
+                                                              const uint32_t *base, uint32_t *kseg, uint32_t *krow,
+                                                              uint64_t *keys, uint32_t *vals, const uint32_t *xfirst,
+                                                              const uint64_t *xkeys, RbNear nr)
+{
+    rb_scatter_body<true, true>(n_seg, first, seg_begin, seg_len, nr.lo, nr.hi, nr.table_ids, ids, chunk, base, kseg, krow, keys, vals,
+                                xfirst, xkeys, nr);
 }
 
 __global__ void rb_score_keys(int64_t m, const uint32_t *vals, const uint32_t *kseg, const uint32_t *krow,
@@ -542,11 +702,11 @@ __global__ void rb_segment_keys(int64_t m, const uint32_t *vals, const uint32_t 
 }
 
 // output row s, slots [256 jt, 256 jt + 256): the first N of the segment's run in the sorted rows, then the padding
-__global__ __launch_bounds__(kRbThreads) void rb_emit_sorted(int64_t tiles, int64_t N, int64_t m, const uint32_t *seg_sorted,
-                                                             const uint32_t *vals, const uint32_t *krow,
-                                                             const int64_t *seg_begin, const int64_t *ids,
-                                                             const double *scores, int64_t *out_ids, double *out_scores,
-                                                             int64_t *out_counts)
+template <bool NEAR>
+__device__ __forceinline__ void rb_emit_sorted_body(int64_t tiles, int64_t N, int64_t m, const uint32_t *seg_sorted,
+                                                    const uint32_t *vals, const uint32_t *krow, const int64_t *seg_begin,
+                                                    const int64_t *ids, const double *scores, int64_t *out_ids,
+                                                    double *out_scores, int64_t *out_counts, const RbNear &nr)
 {
     __shared__ int64_t range[2];
     const int64_t s = blockIdx.x / tiles, jt = blockIdx.x % tiles;
@@ -568,20 +728,69 @@ __global__ __launch_bounds__(kRbThreads) void rb_emit_sorted(int64_t tiles, int6
             const int64_t r = seg_begin[s] + krow[vals[lb + j]];
             out_ids[o] = ids[r];
             out_scores[o] = scores[r];
+            if constexpr (NEAR) {
+                if (nr.meters) nr.meters[o] = rb_meters_of(nr, rb_circle_of(nr, s), s, ordered_key(ids[r]));
+            }
         } else {
             out_ids[o] = -1;
             out_scores[o] = 0.0;
+            if constexpr (NEAR) {
+                if (nr.meters) nr.meters[o] = 0.0;
+            }
         }
     }
     if (jt == 0 && threadIdx.x == 0) out_counts[s] = min(have, N);
 }
 
-// both internal entries; ex_begin NULL: the plain one
+__global__ __launch_bounds__(kRbThreads) void rb_emit_sorted(int64_t tiles, int64_t N, int64_t m, const uint32_t *seg_sorted,
+                                                             const uint32_t *vals, const uint32_t *krow,
+                                                             const int64_t *seg_begin, const int64_t *ids,
+                                                             const double *scores, int64_t *out_ids, double *out_scores,
+                                                             int64_t *out_counts)
+{
+    rb_emit_sorted_body<false>(tiles, N, m, seg_sorted, vals, krow, seg_begin, ids, scores, out_ids, out_scores, out_counts, RbNear{});
+}
+
+__global__ __launch_bounds__(kRbThreads) void rb_emit_sorted_near(int64_t tiles, int64_t N, int64_t m, const uint32_t *seg_sorted,
+                                                                  const uint32_t *vals, const uint32_t *krow,
+                                                                  const int64_t *seg_begin, const int64_t *ids,
+                                                                  const double *scores, int64_t *out_ids, double *out_scores,
+                                                                  int64_t *out_counts, RbNear nr)
+{
+    rb_emit_sorted_body<true>(tiles, N, m, seg_sorted, vals, krow, seg_begin, ids, scores, out_ids, out_scores, out_counts, nr);
+}
+
+// The circles' and the place table's requires, in the plan step before any row is read: a radius that is NaN or below 0
+// (bit 1 of *flags), a centre (bit 2) or a place row (bit 3) that fails Location's require.
+__global__ void rb_check_near(int64_t n_seg, const double *clat, const double *clon, const double *rad, int64_t np,
+                              const double *plat, const double *plon, unsigned long long *flags)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long bad = 0;
+    if (i < n_seg) {
+        if (!(rad[i] >= 0.0)) bad |= 2ull;
+        if (!location_ok(clat[i], clon[i])) bad |= 4ull;
+    }
+    if (i < np && !location_ok(plat[i], plon[i])) bad |= 8ull;
+    if (bad) atomicOr(flags, bad);
+}
+
+// the refusal of rb_check_near's bits, naming the argument
+int32_t rb_near_refusal(unsigned long long bits)
+{
+    if (bits & 2ull) return fail(LOCREC_E_INVALID_ARG, "radius_meters must be >= 0 (or +inf) and not NaN");
+    if (bits & 4ull)
+        return fail(LOCREC_E_INVALID_ARG, "center_latitudes must be within [-90.0, 90.0] and center_longitudes within [-180.0, 180.0]");
+    return fail(LOCREC_E_INVALID_ARG, "place_latitudes must be within [-90.0, 90.0] and place_longitudes within [-180.0, 180.0]");
+}
+
+// the internal entries; ex_begin NULL: no lists; nq NULL: no circle (out_meters unused)
 int32_t rank_segments(int64_t n_seg, const int64_t *seg_begin, const int64_t *seg_len, const int64_t *ids, const double *scores,
                       int64_t n_places, const int64_t *place_ids, const int64_t *place_region_ids,
                       const int64_t *target_region_ids, int64_t max_recommendations, const int64_t *ex_begin,
                       const int64_t *ex_len, int64_t n_excluded, const int64_t *ex_ids, int64_t *out_ids, double *out_scores,
-                      int64_t *out_counts, const unsigned long long *invalid_flag, int64_t host_assembled, hipStream_t s)
+                      int64_t *out_counts, const unsigned long long *invalid_flag, int64_t host_assembled, hipStream_t s,
+                      const RankNear *nq = nullptr, double *out_meters = nullptr)
 {
     RankBatchStats &st = rank_batch_stats();
     st = RankBatchStats();
@@ -598,6 +807,17 @@ int32_t rank_segments(int64_t n_seg, const int64_t *seg_begin, const int64_t *se
         if (invalid_flag) {
             LOCREC_READ_BACK(bad, invalid_flag, s);
             ++st.host_syncs;
+        }
+        if (nq && !bad) {  // ... and the circles' requires
+            DevBuf<unsigned long long> flags;
+            LOCREC_TRY(flags.alloc(1));
+            LOCREC_HIP_TRY(hipMemsetAsync(flags.p, 0, sizeof(unsigned long long), s));
+            LOCREC_LAUNCH(rb_check_near, grid_for(std::max(n_seg, n_places)), dim3(256), 0, s, n_seg, nq->center_lat, nq->center_lon,
+                          nq->radius, n_places, nq->place_lat, nq->place_lon, flags.p);
+            unsigned long long bits = 0;
+            LOCREC_READ_BACK(bits, flags.p, s);
+            ++st.host_syncs;
+            if (bits) return rb_near_refusal(bits);
         }
         if (bad) return fail(LOCREC_E_INVALID_ARG, "segments must be non-decreasing offsets inside [0, n]");
         LOCREC_HIP_TRY(hipMemsetAsync(out_counts, 0, (size_t)n_seg * sizeof(int64_t), s));
@@ -623,6 +843,8 @@ int32_t rank_segments(int64_t n_seg, const int64_t *seg_begin, const int64_t *se
         LOCREC_LAUNCH(gather_id_keys, grid_for(n_places), dim3(256), 0, s, n_places, place_ids, r0, k0);
     }
     const uint64_t *table_regions = k1, *table_ids = k0;
+    // (table position t is input row trow[t]: the second pass's values, in r0 - what leads a listing to its coordinates)
+    const uint32_t *trow = n_places > 0 ? reinterpret_cast<const uint32_t *>(k1 + n_places) : nullptr;
     // the plan: every segment's range of the table and its chunks
     const size_t seg8 = ((size_t)n_seg + 2) / 2;  // u32[n_seg + 1] in 8-byte units
     LOCREC_TRY(plan.alloc(5 + (ex_begin ? 8 : 6) * seg8));
@@ -640,10 +862,14 @@ int32_t rank_segments(int64_t n_seg, const int64_t *seg_begin, const int64_t *se
     LOCREC_LAUNCH(rb_plan, grid_for(n_seg + 1), dim3(256), 0, s, n_seg, seg_begin, seg_len, target_region_ids, n_places,
                   table_regions, chunk, invalid_flag, nch.p, split_nch.p, lo.p, hi.p, hdr.p, ex_begin, ex_len, n_excluded,
                   xlen.p);
+    if (nq)
+        LOCREC_LAUNCH(rb_check_near, grid_for(std::max(n_seg, n_places)), dim3(256), 0, s, n_seg, nq->center_lat, nq->center_lon,
+                      nq->radius, n_places, nq->place_lat, nq->place_lon, hdr.p);
     unsigned long long h[5] = {0, 0, 0, 0, 0};  // (the fifth word travels only when there are lists)
     LOCREC_HIP_TRY(hipMemcpyAsync(h, hdr.p, (ex_begin ? 5 : 4) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     LOCREC_HIP_TRY(hipStreamSynchronize(s));
     ++st.host_syncs;
+    if (h[0] & ~1ull) return rb_near_refusal(h[0]);
     if (h[0])
         return fail(LOCREC_E_INVALID_ARG, ex_begin ? "segments and exclusion lists must be non-decreasing offsets inside their "
                                                      "arrays, each segment shorter than 2^31 rows"
@@ -652,6 +878,8 @@ int32_t rank_segments(int64_t n_seg, const int64_t *seg_begin, const int64_t *se
         return fail(LOCREC_E_INVALID_ARG, "%llu chunks: raise LOCREC_RANK_BATCH_CHUNK or split the batch", h[1]);
     if (h[4] >= (unsigned long long)kMaxRows) return fail(LOCREC_E_INVALID_ARG, "2^31 excluded ids or more in all: split the batch");
     const uint32_t items = (uint32_t)h[1];
+    RbNear nr = {};
+    if (nq) nr = {nq->center_lat, nq->center_lon, nq->radius, nq->place_lat, nq->place_lon, trow, lo.p, hi.p, table_ids, out_meters};
     LOCREC_PRIM(tmp, prim::exclusive_sum(p_, bytes_, nch.p, first.p, (size_t)n_seg + 1, s));
     // the pair table of the exclusion lists (every list empty: the plain kernels, and the plain call's result and stats)
     const int64_t n_pairs = (int64_t)h[4];
@@ -704,7 +932,11 @@ int32_t rank_segments(int64_t n_seg, const int64_t *seg_begin, const int64_t *se
             prow.p = reinterpret_cast<uint32_t *>(pid.p + pn);
             pcount.p = reinterpret_cast<int32_t *>(pid.p + pn + pn8);
         }
-        if (xkeys)
+        if (nq)
+            LOCREC_LAUNCH(rb_select_near, dim3(items), dim3(kRbThreads), 0, s, n_seg, first.p, pfirst.p, seg_begin, seg_len, ids,
+                          scores, chunk, (int)N, pk.p, pid.p, prow.p, pcount.p, out_ids, out_scores, out_counts,
+                          xkeys ? xfirst.p : nullptr, xkeys, nr);
+        else if (xkeys)
             LOCREC_LAUNCH(rb_select_ex, dim3(items), dim3(kRbThreads), 0, s, n_seg, first.p, pfirst.p, seg_begin, seg_len, lo.p,
                           hi.p, table_ids, ids, scores, chunk, (int)N, pk.p, pid.p, prow.p, pcount.p, out_ids, out_scores,
                           out_counts, xfirst.p, xkeys);
@@ -712,7 +944,10 @@ int32_t rank_segments(int64_t n_seg, const int64_t *seg_begin, const int64_t *se
             LOCREC_LAUNCH(rb_select, dim3(items), dim3(kRbThreads), 0, s, n_seg, first.p, pfirst.p, seg_begin, seg_len, lo.p,
                           hi.p, table_ids, ids, scores, chunk, (int)N, pk.p, pid.p, prow.p, pcount.p, out_ids, out_scores,
                           out_counts);
-        if (h[3] > 0)
+        if (h[3] > 0 && nq)
+            LOCREC_LAUNCH(rb_merge_near, dim3((unsigned)n_seg), dim3(kRbThreads), 0, s, first.p, pfirst.p, seg_begin, scores,
+                          (int)N, pk.p, pid.p, prow.p, pcount.p, out_ids, out_scores, out_counts, nr);
+        else if (h[3] > 0)
             LOCREC_LAUNCH(rb_merge, dim3((unsigned)n_seg), dim3(kRbThreads), 0, s, first.p, pfirst.p, seg_begin, scores,
                           (int)N, pk.p, pid.p, prow.p, pcount.p, out_ids, out_scores, out_counts);
         // (the partial lists are freed below: hipFree waits for the kernels that read them)
@@ -725,7 +960,10 @@ int32_t rank_segments(int64_t n_seg, const int64_t *seg_begin, const int64_t *se
     DevBuf<uint32_t> cnt, base;
     LOCREC_TRY(cnt.alloc((size_t)items + 1));
     LOCREC_TRY(base.alloc((size_t)items + 1));
-    if (xkeys)
+    if (nq)
+        LOCREC_LAUNCH(rb_count_near, dim3(items + 1), dim3(kRbThreads), 0, s, n_seg, first.p, seg_begin, seg_len, ids, chunk, cnt.p,
+                      items, xkeys ? xfirst.p : nullptr, xkeys, nr);
+    else if (xkeys)
         LOCREC_LAUNCH(rb_count_ex, dim3(items + 1), dim3(kRbThreads), 0, s, n_seg, first.p, seg_begin, seg_len, lo.p, hi.p,
                       table_ids, ids, chunk, cnt.p, items, xfirst.p, xkeys);
     else
@@ -751,7 +989,10 @@ int32_t rank_segments(int64_t n_seg, const int64_t *seg_begin, const int64_t *se
     LOCREC_TRY(q0.alloc(mm));
     LOCREC_TRY(q1.alloc(mm));
     if (m > 0) {
-        if (xkeys)
+        if (nq)
+            LOCREC_LAUNCH(rb_scatter_near, dim3(items), dim3(kRbThreads), 0, s, n_seg, first.p, seg_begin, seg_len, ids, chunk,
+                          base.p, kseg.p, krow.p, q0.p, v0.p, xkeys ? xfirst.p : nullptr, xkeys, nr);
+        else if (xkeys)
             LOCREC_LAUNCH(rb_scatter_ex, dim3(items), dim3(kRbThreads), 0, s, n_seg, first.p, seg_begin, seg_len, lo.p, hi.p,
                           table_ids, ids, chunk, base.p, kseg.p, krow.p, q0.p, v0.p, xfirst.p, xkeys);
         else
@@ -764,8 +1005,12 @@ int32_t rank_segments(int64_t n_seg, const int64_t *seg_begin, const int64_t *se
         LOCREC_LAUNCH(rb_segment_keys, grid_for(m), dim3(256), 0, s, m, v0.p, kseg.p, s0.p);
         LOCREC_PRIM(tmp, prim::sort_pairs(p_, bytes_, s0.p, s1.p, v0.p, v1.p, (int)m, 0, 32, s));
     }
-    LOCREC_LAUNCH(rb_emit_sorted, dim3((unsigned)(n_seg * tiles)), dim3(kRbThreads), 0, s, tiles, N, m, s1.p, v1.p, krow.p,
-                  seg_begin, ids, scores, out_ids, out_scores, out_counts);
+    if (nq)
+        LOCREC_LAUNCH(rb_emit_sorted_near, dim3((unsigned)(n_seg * tiles)), dim3(kRbThreads), 0, s, tiles, N, m, s1.p, v1.p, krow.p,
+                      seg_begin, ids, scores, out_ids, out_scores, out_counts, nr);
+    else
+        LOCREC_LAUNCH(rb_emit_sorted, dim3((unsigned)(n_seg * tiles)), dim3(kRbThreads), 0, s, tiles, N, m, s1.p, v1.p, krow.p,
+                      seg_begin, ids, scores, out_ids, out_scores, out_counts);
     return LOCREC_OK;
 }
 
@@ -777,12 +1022,18 @@ bool rb_host_offsets_ok(const int64_t *offsets, int64_t n_segments, int64_t n)
     return ok;
 }
 
-// both public entries; with_lists false: the plain one (excluded_* unused)
+// The circles of a public call (host or device arrays like the rest); NULL: the plain and the excluding entry.
+struct RbPublicNear {
+    const double *place_lat, *place_lon, *center_lat, *center_lon, *radius;
+    double *out_meters;
+};
+
+// the public entries; with_lists false: no lists (excluded_* unused); pn NULL: no circle
 int32_t rb_public_call(int64_t n_segments, const int64_t *offsets, int64_t n, const int64_t *ids, const double *scores,
                        int64_t n_places, const int64_t *place_ids, const int64_t *place_region_ids,
                        const int64_t *target_region_ids, int64_t max_recommendations, bool with_lists,
                        const int64_t *excluded_offsets, int64_t n_excluded, const int64_t *excluded_ids, int32_t mem,
-                       int64_t *out_ids, double *out_scores, int64_t *out_counts)
+                       int64_t *out_ids, double *out_scores, int64_t *out_counts, const RbPublicNear *pn = nullptr)
 {
     rank_batch_stats() = RankBatchStats();
     LOCREC_TRY(mem_ok(mem));
@@ -797,10 +1048,13 @@ int32_t rb_public_call(int64_t n_segments, const int64_t *offsets, int64_t n, co
         (n_places > 0 && (!place_ids || !place_region_ids)) || (N > 0 && (!out_ids || !out_scores)) ||
         (with_lists && (!excluded_offsets || (n_excluded > 0 && !excluded_ids))))
         return fail(LOCREC_E_INVALID_ARG, "null array");
+    if (pn && (!pn->center_lat || !pn->center_lon || !pn->radius || (n_places > 0 && (!pn->place_lat || !pn->place_lon))))
+        return fail(LOCREC_E_INVALID_ARG, "null coordinate or radius array");
     if (mem == LOCREC_MEM_HOST) {
         if (!rb_host_offsets_ok(offsets, n_segments, n)) return fail(LOCREC_E_INVALID_ARG, "offsets must be non-decreasing inside [0, n]");
         if (with_lists && !rb_host_offsets_ok(excluded_offsets, n_segments, n_excluded))
             return fail(LOCREC_E_INVALID_ARG, "excluded_offsets must be non-decreasing inside [0, n_excluded]");
+        if (pn) LOCREC_TRY(rank_near_check_host(n_segments, pn->center_lat, pn->center_lon, pn->radius, n_places, pn->place_lat, pn->place_lon));
     }
     LOCREC_TRY(ensure_device());
     hipStream_t s = nullptr;
@@ -817,6 +1071,18 @@ int32_t rb_public_call(int64_t n_segments, const int64_t *offsets, int64_t n, co
     LOCREC_TRY(oid.bind(out_ids, n_segments * N, mem));
     LOCREC_TRY(osc.bind(out_scores, n_segments * N, mem));
     LOCREC_TRY(ocnt.bind(out_counts, n_segments, mem));
+    In<double> plat, plon, clat, clon, rad;
+    Out<double> omet;
+    RankNear nq;
+    if (pn) {
+        LOCREC_TRY(plat.bind(pn->place_lat, n_places, mem, s));
+        LOCREC_TRY(plon.bind(pn->place_lon, n_places, mem, s));
+        LOCREC_TRY(clat.bind(pn->center_lat, n_segments, mem, s));
+        LOCREC_TRY(clon.bind(pn->center_lon, n_segments, mem, s));
+        LOCREC_TRY(rad.bind(pn->radius, n_segments, mem, s));
+        if (pn->out_meters) LOCREC_TRY(omet.bind(pn->out_meters, n_segments * N, mem));
+        nq = {clat.p, clon.p, rad.p, plat.p, plon.p};
+    }
     DevBuf<int64_t> seg_begin, seg_len, ex_begin, ex_len;
     DevBuf<unsigned long long> invalid;
     LOCREC_TRY(seg_begin.alloc((size_t)n_segments));
@@ -833,7 +1099,8 @@ int32_t rb_public_call(int64_t n_segments, const int64_t *offsets, int64_t n, co
                       invalid.p);
     }
     LOCREC_TRY(rank_segments(n_segments, seg_begin.p, seg_len.p, rid.p, rsc.p, n_places, pid.p, preg.p, tgt.p, N, ex_begin.p,
-                             ex_len.p, n_excluded, xid.p, oid.p, osc.p, ocnt.p, invalid.p, 0, s));
+                             ex_len.p, n_excluded, xid.p, oid.p, osc.p, ocnt.p, invalid.p, 0, s, pn ? &nq : nullptr, omet.p));
+    if (pn && pn->out_meters) LOCREC_TRY(omet.deliver(n_segments * N, s));
     LOCREC_TRY(oid.deliver(n_segments * N, s));
     LOCREC_TRY(osc.deliver(n_segments * N, s));
     LOCREC_TRY(ocnt.deliver(n_segments, s));
@@ -871,7 +1138,51 @@ int32_t rank_segments_device_excluding(int64_t n_seg, const int64_t *seg_begin, 
                          host_assembled, s);
 }
 
+int32_t rank_near_check_host(int64_t n_seg, const double *center_lat, const double *center_lon, const double *radius,
+                             int64_t n_places, const double *place_lat, const double *place_lon)
+{
+    auto ok = [](double lat, double lon) { return lat >= -90.0 && lat <= 90.0 && lon >= -180.0 && lon <= 180.0; };
+    unsigned long long bits = 0;
+    for (int64_t i = 0; i < n_seg; ++i) {
+        if (!(radius[i] >= 0.0)) bits |= 2ull;
+        if (!ok(center_lat[i], center_lon[i])) bits |= 4ull;
+    }
+    for (int64_t j = 0; j < n_places; ++j)
+        if (!ok(place_lat[j], place_lon[j])) bits |= 8ull;
+    return bits ? rb_near_refusal(bits) : LOCREC_OK;
+}
+
+int32_t rank_segments_device_near(int64_t n_seg, const int64_t *seg_begin, const int64_t *seg_len, const int64_t *ids,
+                                  const double *scores, int64_t n_places, const int64_t *place_ids,
+                                  const int64_t *place_region_ids, const int64_t *target_region_ids, int64_t max_recommendations,
+                                  const RankExclude &ex, const RankNear &near, int64_t *out_ids, double *out_scores,
+                                  double *out_meters, int64_t *out_counts, const unsigned long long *invalid_flag,
+                                  int64_t host_assembled, hipStream_t s)
+{
+    if (n_seg > 0 && ex.begin && (!ex.len || (ex.n > 0 && !ex.ids))) return fail(LOCREC_E_INVALID_ARG, "null exclusion array");
+    if (n_seg > 0 && near.center_lat &&
+        (!near.center_lon || !near.radius || (n_places > 0 && (!near.place_lat || !near.place_lon))))
+        return fail(LOCREC_E_INVALID_ARG, "null coordinate or radius array");
+    return rank_segments(n_seg, seg_begin, seg_len, ids, scores, n_places, place_ids, place_region_ids, target_region_ids,
+                         max_recommendations, ex.begin, ex.len, ex.n, ex.ids, out_ids, out_scores, out_counts, invalid_flag,
+                         host_assembled, s, near.center_lat ? &near : nullptr, out_meters);
+}
+
 }  // namespace locrec
+
+extern "C" int32_t locrec_rank_recommendations_batch_near(
+    int64_t n_segments, const int64_t *offsets, int64_t n, const int64_t *ids, const double *scores, int64_t n_places,
+    const int64_t *place_ids, const int64_t *place_region_ids, const double *place_latitudes, const double *place_longitudes,
+    const int64_t *target_region_ids, const double *center_latitudes, const double *center_longitudes, const double *radius_meters,
+    int64_t max_recommendations, const int64_t *excluded_offsets, int64_t n_excluded, const int64_t *excluded_ids, int32_t mem,
+    int64_t *out_ids, double *out_scores, double *out_meters, int64_t *out_counts)
+try {
+    const RbPublicNear pn = {place_latitudes, place_longitudes, center_latitudes, center_longitudes, radius_meters, out_meters};
+    return rb_public_call(n_segments, offsets, n, ids, scores, n_places, place_ids, place_region_ids, target_region_ids,
+                          max_recommendations, excluded_offsets != nullptr, excluded_offsets, excluded_offsets ? n_excluded : 0,
+                          excluded_ids, mem, out_ids, out_scores, out_counts, &pn);
+}
+LOCREC_CATCH_ALL
 
 extern "C" int32_t locrec_rank_recommendations_batch(int64_t n_segments, const int64_t *offsets, int64_t n, const int64_t *ids,
                                                      const double *scores, int64_t n_places, const int64_t *place_ids,

@@ -25,6 +25,10 @@
 //   exclusion lists locrec_sg_recommend_ranked_batch_excluding: a caller-given list of ids per position (the places a
 //                   person has been to), uploaded once in emit order; a group's ranker call is the excluding entry with
 //                   the sub-range of its segments.  The emit and the segments' room do not see the lists.
+//   circles         locrec_sg_recommend_ranked_batch_near: a centre and a radius per position and the place rows'
+//                   coordinates, uploaded once (the circles in emit order); a group's ranker call is the near entry with
+//                   the sub-range of its segments, and out_meters comes back with the group's rows.  As with the lists,
+//                   the emit and the segments' room see only the region.
 //   host            the pool's entry (sg_pool_ranked.h) shares sg_rk_check_args, sg_rk_verdicts, SgRkCall (groups, ranker
 //                   call, read-backs, scatter) and sg_rk_plan.h's order and groups: this entry is a pool of one member
 //
@@ -327,6 +331,13 @@ int32_t sg_rk_verdicts(const unsigned char *image, int nb, double eps2, int64_t 
     return LOCREC_OK;
 }
 
+// The circles of a near call (host arrays, checked by the entry): per row of the place table its coordinates, per input
+// position a centre and a radius; meters: the output rows' distances (NULL: not wanted).
+struct SgRkNear {
+    const double *place_lat, *place_lon, *center_lat, *center_lon, *radius;
+    double *meters;
+};
+
 // What both ranked entries hold from the caps' read-back to the call's end.  The first members are the entry's: its
 // stream and, in its own buffer, the places table, the targets, the segments' begins and lengths (the columns' row
 // counts lie behind the lengths).
@@ -340,6 +351,10 @@ struct SgRkCall {
     // leaves out d_ex_ids[d_ex_begin[k] .. + d_ex_len[k]); a group's ranker call gets the sub-range of its segments
     const int64_t *d_ex_begin = nullptr, *d_ex_len = nullptr, *d_ex_ids = nullptr;
     int64_t n_ex = 0;
+    // per-request circles in emit order and the place rows' coordinates (near.center_lat NULL: none): like the lists,
+    // only the group's ranker call sees them
+    RankNear near;
+    std::vector<double> h_near, h_omet;  // the centres and radii as uploaded; the ranked rows' distances in emit order
     int64_t Nd = 0;
     SgRkGroups groups;
     size_t group = 0;               // the group that is being filled
@@ -367,7 +382,8 @@ struct SgRkCall {
         Nd = std::min(N, groups.max_cap);  // no request has more rows than the largest region: the rest is padding
         LOCREC_HIP_TRY(hipMemcpyAsync(d_seg_begin, groups.seg_begin.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
         LOCREC_TRY(d_rows.alloc(2 * (size_t)groups.max_rows));
-        LOCREC_TRY(d_out.alloc((size_t)(2 * groups.max_req * Nd + groups.max_req)));
+        LOCREC_TRY(d_out.alloc((size_t)((near.center_lat ? 3 : 2) * groups.max_req * Nd + groups.max_req)));
+        if (near.center_lat) h_omet.resize((size_t)(n * Nd));
         d_row_ids = d_rows.p;
         d_row_probs = reinterpret_cast<double *>(d_rows.p + groups.max_rows);
         h_oid.resize((size_t)(n * Nd));
@@ -401,6 +417,31 @@ struct SgRkCall {
         return LOCREC_OK;
     }
 
+    // The circles, uploaded once into d_nr (which outlives the call's launches): the place rows' coordinates, then the
+    // centres and radii in emit order.  Before plan(): the output buffer's size depends on it.
+    int32_t upload_circles(const std::vector<int64_t> &ord, const SgRkNear &nr, DevBuf<double> &d_nr)
+    {
+        h_near.resize((size_t)(3 * n));
+        for (int64_t k = 0; k < n; ++k) {
+            const int64_t i = ord[(size_t)k];
+            h_near[(size_t)k] = nr.center_lat[i];
+            h_near[(size_t)(n + k)] = nr.center_lon[i];
+            h_near[(size_t)(2 * n + k)] = nr.radius[i];
+        }
+        LOCREC_TRY(d_nr.alloc((size_t)(2 * n_places + 3 * n)));
+        if (n_places > 0) {
+            LOCREC_HIP_TRY(hipMemcpyAsync(d_nr.p, nr.place_lat, (size_t)n_places * 8, hipMemcpyHostToDevice, s));
+            LOCREC_HIP_TRY(hipMemcpyAsync(d_nr.p + n_places, nr.place_lon, (size_t)n_places * 8, hipMemcpyHostToDevice, s));
+        }
+        LOCREC_HIP_TRY(hipMemcpyAsync(d_nr.p + 2 * n_places, h_near.data(), (size_t)(3 * n) * 8, hipMemcpyHostToDevice, s));
+        near.place_lat = d_nr.p;
+        near.place_lon = d_nr.p + n_places;
+        near.center_lat = d_nr.p + 2 * n_places;
+        near.center_lon = near.center_lat + n;
+        near.radius = near.center_lon + n;
+        return LOCREC_OK;
+    }
+
     // ranks the filled group and brings its rows to the host
     int32_t flush_group()
     {
@@ -410,7 +451,14 @@ struct SgRkCall {
         if (Nd == 0) return LOCREC_OK;  // every count is 0
         int64_t *d_oid = d_out.p, *d_ocnt = d_out.p + 2 * groups.max_req * Nd;
         double *d_osc = reinterpret_cast<double *>(d_out.p + groups.max_req * Nd);
-        if (d_ex_begin)
+        double *d_omet = reinterpret_cast<double *>(d_ocnt + groups.max_req);
+        if (near.center_lat) {
+            RankExclude ex;
+            if (d_ex_begin) ex = {d_ex_begin + ka, d_ex_len + ka, d_ex_ids, n_ex};
+            const RankNear nr = {near.center_lat + ka, near.center_lon + ka, near.radius + ka, near.place_lat, near.place_lon};
+            LOCREC_TRY(rank_segments_device_near(nseg, d_seg_begin + ka, d_seg_len + ka, d_row_ids, d_row_probs, n_places, d_pid, d_preg,
+                                                 d_tgt + ka, Nd, ex, nr, d_oid, d_osc, d_omet, d_ocnt, nullptr, 0, s));
+        } else if (d_ex_begin)
             LOCREC_TRY(rank_segments_device_excluding(nseg, d_seg_begin + ka, d_seg_len + ka, d_row_ids, d_row_probs, n_places, d_pid,
                                                       d_preg, d_tgt + ka, Nd, d_ex_begin + ka, d_ex_len + ka, n_ex, d_ex_ids, d_oid,
                                                       d_osc, d_ocnt, nullptr, 0, s));
@@ -424,9 +472,11 @@ struct SgRkCall {
         LOCREC_HIP_TRY(hipMemcpyAsync(h_oid.data() + ka * Nd, d_oid, (size_t)(nseg * Nd) * 8, hipMemcpyDeviceToHost, s));
         LOCREC_HIP_TRY(hipMemcpyAsync(h_osc.data() + ka * Nd, d_osc, (size_t)(nseg * Nd) * 8, hipMemcpyDeviceToHost, s));
         LOCREC_HIP_TRY(hipMemcpyAsync(h_cnt.data() + ka, d_ocnt, (size_t)nseg * 8, hipMemcpyDeviceToHost, s));
+        if (near.center_lat)
+            LOCREC_HIP_TRY(hipMemcpyAsync(h_omet.data() + ka * Nd, d_omet, (size_t)(nseg * Nd) * 8, hipMemcpyDeviceToHost, s));
         LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (the next group's rows overwrite these)
         ++stats.host_syncs;
-        stats.readback_bytes += nseg * (16 * Nd + 8);
+        stats.readback_bytes += nseg * ((near.center_lat ? 24 : 16) * Nd + 8);
         return LOCREC_OK;
     }
 
@@ -434,7 +484,7 @@ struct SgRkCall {
     // then the caller's order and stride.  Input position i asks member member_of[i] for its distinct target uniq_of[i].
     int32_t finish(int32_t status, int64_t polls, const SgRkPoolOrder &order, const std::vector<int32_t> &member_of,
                    const std::vector<int32_t> &uniq_of, int64_t *out_ids, double *out_probabilities, int64_t *out_counts,
-                   int64_t *out_row_counts, int64_t *out_iterations, int32_t *out_converged)
+                   int64_t *out_row_counts, int64_t *out_iterations, int32_t *out_converged, double *out_meters = nullptr)
     {
         stats.readback_bytes += polls * 4;
         stats.host_syncs += polls;
@@ -455,6 +505,10 @@ struct SgRkCall {
                 std::copy(h_osc.begin() + k * Nd, h_osc.begin() + k * Nd + c, out_probabilities + i * N);
                 std::fill(out_ids + i * N + c, out_ids + (i + 1) * N, (int64_t)-1);
                 std::fill(out_probabilities + i * N + c, out_probabilities + (i + 1) * N, 0.0);
+                if (out_meters) {
+                    std::copy(h_omet.begin() + k * Nd, h_omet.begin() + k * Nd + c, out_meters + i * N);
+                    std::fill(out_meters + i * N + c, out_meters + (i + 1) * N, 0.0);
+                }
             }
             if (out_row_counts) out_row_counts[i] = tail[(size_t)n + f];
             if (out_iterations) out_iterations[i] = res_it[f];
@@ -471,7 +525,7 @@ int32_t sg_ranked_batch_columns(locrec_sg_graph *g, SgRankedStats &stats, int64_
                                 const int64_t *place_region_ids, const int64_t *target_region_ids, bool with_lists,
                                 const int64_t *excluded_offsets, int64_t n_excluded, const int64_t *excluded_ids, int64_t *out_ids,
                                 double *out_probabilities, int64_t *out_counts, int64_t *out_row_counts, int64_t *out_iterations,
-                                int32_t *out_converged);
+                                int32_t *out_converged, const SgRkNear *near = nullptr);
 
 // The exclusion lists' checks (host arrays), before any device work
 int32_t sg_rk_check_lists(int64_t n_targets, const int64_t *excluded_offsets, int64_t n_excluded, const int64_t *excluded_ids)
@@ -491,7 +545,7 @@ int32_t sg_recommend_ranked_batch(locrec_sg_graph *g, int64_t n_targets, const i
                                   const int64_t *place_region_ids, const int64_t *target_region_ids, int64_t max_recommendations,
                                   bool with_lists, const int64_t *excluded_offsets, int64_t n_excluded, const int64_t *excluded_ids,
                                   int64_t *out_ids, double *out_probabilities, int64_t *out_counts, int64_t *out_row_counts,
-                                  int64_t *out_iterations, int32_t *out_converged)
+                                  int64_t *out_iterations, int32_t *out_converged, const SgRkNear *near = nullptr)
 {
     SgRankedStats &stats = sg_ranked_stats();
     stats = SgRankedStats();
@@ -507,7 +561,7 @@ int32_t sg_recommend_ranked_batch(locrec_sg_graph *g, int64_t n_targets, const i
     return sg_ranked_batch_columns(g, stats, n_targets, uniq, uniq_of, SgPersonTiles{uniq}, alpha, epsilon, max_iterations, N, n_places,
                                    place_ids, place_region_ids, target_region_ids, with_lists, excluded_offsets, n_excluded,
                                    excluded_ids, out_ids, out_probabilities, out_counts, out_row_counts, out_iterations,
-                                   out_converged);
+                                   out_converged, near);
 }
 
 // The ranked batch behind its checks, for n >= 1 positions over the columns `tiles` runs: position i asks column uniq_of[i],
@@ -519,7 +573,7 @@ int32_t sg_ranked_batch_columns(locrec_sg_graph *g, SgRankedStats &stats, int64_
                                 const int64_t *place_region_ids, const int64_t *target_region_ids, bool with_lists,
                                 const int64_t *excluded_offsets, int64_t n_excluded, const int64_t *excluded_ids, int64_t *out_ids,
                                 double *out_probabilities, int64_t *out_counts, int64_t *out_row_counts, int64_t *out_iterations,
-                                int32_t *out_converged)
+                                int32_t *out_converged, const SgRkNear *near)
 {
     LOCREC_HIP_TRY(hipSetDevice(g->device));
     hipStream_t s = g->stream;
@@ -591,6 +645,8 @@ int32_t sg_ranked_batch_columns(locrec_sg_graph *g, SgRankedStats &stats, int64_
     // ---- the groups (request k's room: its region's cap), the group's buffers
     SgRkCall rc{.stats = stats, .s = s, .n = n, .N = N, .n_places = n_places, .d_pid = d_pid, .d_preg = d_preg, .d_tgt = d_tgt,
                 .d_seg_begin = d_seg_begin, .d_seg_len = d_seg_len};
+    DevBuf<double> d_nr;  // the circles
+    if (near) LOCREC_TRY(rc.upload_circles(ord, *near, d_nr));
     LOCREC_TRY(rc.plan(d_caps, (size_t)R, req.data() + 2 * n, nu));
     DevBuf<int64_t> d_ex;  // the lists
     if (with_lists) LOCREC_TRY(rc.upload_lists(ord, excluded_offsets, n_excluded, excluded_ids, d_ex));
@@ -638,10 +694,34 @@ int32_t sg_ranked_batch_columns(locrec_sg_graph *g, SgRankedStats &stats, int64_
     SgBatchCtx ctx;
     const int32_t status = sg_batch_tiles_of(g, tiles, alpha, epsilon, max_iterations, ctx, after_tile);
     return rc.finish(status, ctx.polls, order, member_of, uniq_of, out_ids, out_probabilities, out_counts, out_row_counts,
-                     out_iterations, out_converged);
+                     out_iterations, out_converged, near ? near->meters : nullptr);
 }
 
 }  // namespace
+
+extern "C" int32_t locrec_sg_recommend_ranked_batch_near(
+    locrec_sg_graph *g, int64_t n_targets, const int64_t *vertex_ids, double alpha, double epsilon, int64_t max_iterations,
+    int64_t n_places, const int64_t *place_ids, const int64_t *place_region_ids, const double *place_latitudes,
+    const double *place_longitudes, const int64_t *target_region_ids, const double *center_latitudes,
+    const double *center_longitudes, const double *radius_meters, int64_t max_recommendations, const int64_t *excluded_offsets,
+    int64_t n_excluded, const int64_t *excluded_ids, int64_t *out_ids, double *out_probabilities, double *out_meters,
+    int64_t *out_counts, int64_t *out_row_counts, int64_t *out_iterations, int32_t *out_converged) try
+{
+    // the circles' and the lists' requires first: before the graph is looked at
+    if (n_targets < 0 || n_places < 0 || n_places >= ((int64_t)1 << 31)) return fail(LOCREC_E_INVALID_ARG, "target or place count out of range");
+    if ((n_targets > 0 && (!center_latitudes || !center_longitudes || !radius_meters)) ||
+        (n_places > 0 && (!place_latitudes || !place_longitudes)))
+        return fail(LOCREC_E_INVALID_ARG, "null coordinate or radius array");
+    LOCREC_TRY(rank_near_check_host(n_targets, center_latitudes, center_longitudes, radius_meters, n_places, place_latitudes,
+                                    place_longitudes));
+    const bool with_lists = excluded_offsets != nullptr;
+    if (with_lists) LOCREC_TRY(sg_rk_check_lists(n_targets, excluded_offsets, n_excluded, excluded_ids));
+    const SgRkNear near = {place_latitudes, place_longitudes, center_latitudes, center_longitudes, radius_meters, out_meters};
+    return sg_recommend_ranked_batch(g, n_targets, vertex_ids, alpha, epsilon, max_iterations, n_places, place_ids, place_region_ids,
+                                     target_region_ids, max_recommendations, with_lists, excluded_offsets, with_lists ? n_excluded : 0,
+                                     excluded_ids, out_ids, out_probabilities, out_counts, out_row_counts, out_iterations,
+                                     out_converged, &near);
+} LOCREC_CATCH_ALL
 
 extern "C" int32_t locrec_sg_recommend_ranked_batch(locrec_sg_graph *g, int64_t n_targets, const int64_t *vertex_ids, double alpha,
                                                     double epsilon, int64_t max_iterations, int64_t n_places,

@@ -299,6 +299,28 @@ class KnnIndex:
                      L.ptr(cnt, C.c_int64)))
         return oi, osc, cnt
 
+    def recommend_ranked_batch_near(self, person_ids, pw, cw, k, place_ids, place_region_ids, place_latitudes, place_longitudes,
+                                    target_region_ids, center_latitudes, center_longitudes, radius_meters, max_recommendations,
+                                    unvisited=False):
+        """recommend_ranked_batch within reach (locrec_knn_recommend_ranked_batch_near): person i's ranking keeps only the
+        places of its target region with a listing no further than radius_meters[i] (>= 0 or +inf) from
+        (center_latitudes[i], center_longitudes[i]) - prep.rank_recommendations_batch_near's rule.  unvisited=True: only
+        new places as well.  -> (place_ids[nq, W], estimated_ratings[nq, W], meters[nq, W], counts[nq])."""
+        q = L.as_i64(person_ids)
+        pl, reg, tgt, width, (oi, osc, cnt) = self._ranked_args(len(q), place_ids, place_region_ids, target_region_ids,
+                                                                max_recommendations)
+        plat, plon = L.as_f64(place_latitudes), L.as_f64(place_longitudes)
+        clat, clon, rad = L.as_f64(center_latitudes), L.as_f64(center_longitudes), L.as_f64(radius_meters)
+        if len(plat) != len(pl) or len(plon) != len(pl) or not len(clat) == len(clon) == len(rad) == len(q):
+            raise L.IllegalArgumentException("one coordinate pair per place and one centre and radius per person are required")
+        om = np.zeros((len(q), width), np.float64)
+        L.check(L.lib().locrec_knn_recommend_ranked_batch_near(
+            self._h, len(q), L.ptr(q, C.c_int64), float(pw), float(cw), int(k), len(pl), L.ptr(pl, C.c_int64),
+            L.ptr(reg, C.c_int64), L.ptr(plat, C.c_double), L.ptr(plon, C.c_double), L.ptr(tgt, C.c_int64),
+            L.ptr(clat, C.c_double), L.ptr(clon, C.c_double), L.ptr(rad, C.c_double), width, int(bool(unvisited)),
+            L.ptr(oi, C.c_int64), L.ptr(osc, C.c_double), L.ptr(om, C.c_double), L.ptr(cnt, C.c_int64)))
+        return oi, osc, om, cnt
+
     def fetch_ranked(self, nq, place_ids, place_region_ids, target_region_ids, max_recommendations, unvisited=False):
         """The same last stage for the range recommend_range_async left on the device (locrec_knn_fetch_ranked, or
         locrec_knn_fetch_ranked_unvisited): target_region_ids[i] belongs to internal row first + i."""

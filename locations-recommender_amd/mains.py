@@ -1077,6 +1077,95 @@ def sg_recommender_requests_ranked(data_dir, persons, lines, epsilon, max_iterat
     return out
 
 
+def _near_request_circles(lines, positions, radius_meters):
+    """The circles of a near request list -> (lat[n], lon[n], radius[n]) float64: positions = (lat[n], lon[n]), the radius a
+    scalar or one value per line."""
+    lat, lon = (np.asarray(p, np.float64) for p in positions)
+    rad = np.asarray(radius_meters, np.float64)
+    rad = np.full(len(lines), float(rad)) if rad.ndim == 0 else rad
+    if not len(lat) == len(lon) == len(rad) == len(lines):
+        raise L.IllegalArgumentException("one position per line and a scalar radius or one per line are required")
+    return lat, lon, rad
+
+
+def _near_requests(kind, resolve_lines, per_handle, data_dir, persons, lines, positions, radius_meters, max_recommendations):
+    """What both near request functions share: the lines resolved as ever, the place table with its coordinates
+    (load_places_full), one near ranked batch per distinct handle (per_handle(handle, person_ids, regions, places, lat,
+    lon, rad, target of the handle's first line) -> (ids, scores, meters, counts) for the lines of that handle), a bad
+    line recorded and the call repeated without it.  -> per line ((person, home, target), ids, scores, meters) or the exception instance."""
+    from . import _cache
+    _cache.require_gpu_backend(kind)
+    lat, lon, rad = _near_request_circles(lines, positions, radius_meters)
+    out, targets, handles = resolve_lines(data_dir, persons, lines)
+    try:
+        if targets:
+            places = load_places_full(data_dir)
+            width = max(0, int(max_recommendations))
+
+            def call(gi, v, live):
+                at_lines = np.asarray(live, np.int64)
+                regions = np.asarray([targets[i][0][2] for i in live], np.int64)
+                n = len(live)
+                oi, osc, om = np.full((n, width), -1, np.int64), np.zeros((n, width), np.float64), np.zeros((n, width), np.float64)
+                cnt = np.zeros(n, np.int64)
+                for k in np.unique(gi):
+                    at = np.flatnonzero(gi == k)
+                    try:
+                        with handles[k].lock:
+                            r = per_handle(handles[k], v[at], regions[at], places, lat[at_lines[at]], lon[at_lines[at]],
+                                           rad[at_lines[at]], targets[live[at[0]]][0])
+                    except L.IllegalArgumentException as e:
+                        head, _, unknown = str(e).rpartition(": ")
+                        if head in ("No such person", "No such vertex in the graph"):
+                            e.bad_request = int(at[np.flatnonzero(v[at] == int(unknown))[0]])
+                        raise
+                    w = r[0].shape[1]
+                    oi[at, :w], osc[at, :w], om[at, :w], cnt[at] = r
+                return oi, osc, om, cnt
+            live, rows = _call_without_bad_lines(out, targets, call)
+            if live:
+                oi, osc, om, cnt = rows
+                for k, i in enumerate(live):
+                    out[i] = (targets[i][0], np.array(oi[k, :cnt[k]]), np.array(osc[k, :cnt[k]]), np.array(om[k, :cnt[k]]))
+    finally:
+        for h in handles:
+            h.close()  # drops the reference only
+    return out
+
+
+def knn_recommender_requests_near(data_dir, persons, lines, positions, radius_meters, place_weight, category_weight, k_nearest,
+                                  max_recommendations=10, new_places=False):
+    """knn_recommender_requests within reach: line i is resolved as ever (parse_input, calc_recommender_target) and ranked
+    among the places of its target region no further than radius_meters (a scalar or one value per line; >= 0 or +inf)
+    from positions = (lat[n], lon[n])[i] - KnnIndex.recommend_ranked_batch_near, one call per distinct index, the place
+    table from load_places_full.  new_places=True: without the places the person has rated.
+    -> a list aligned with lines: ((person_id, home_region_id, target_region_id), place_ids, estimated_ratings, meters)
+    or the exception instance; a line whose person its index lacks is recorded and the call repeated without it."""
+    def per_index(ix, person_ids, regions, places, lat, lon, rad, _target):
+        return ix.recommend_ranked_batch_near(person_ids, place_weight, category_weight, k_nearest, places["id"],
+                                              places["region_id"], places["latitude"], places["longitude"], regions, lat, lon,
+                                              rad, max_recommendations, unvisited=new_places)
+    return _near_requests("knn_recommender_requests_near", _knn_resolve_request_lines, per_index, data_dir, persons, lines,
+                          positions, radius_meters, max_recommendations)
+
+
+def sg_recommender_requests_near(data_dir, persons, lines, positions, radius_meters, epsilon, max_iterations,
+                                 max_recommendations=10, new_places=False):
+    """sg_recommender_requests within reach, as knn_recommender_requests_near: SgGraph.recommend_ranked_batch_near, one call
+    per distinct graph.  new_places=True: without the targets of the person's out-edges in its region set's edge Parquet.
+    -> a list aligned with lines: ((person_id, home_region_id, target_region_id), ids, probabilities, meters) or the
+    exception instance; a line whose vertex its graph lacks is recorded and the call repeated without it."""
+    from .stochastic import ALPHA
+
+    def per_graph(g, vertex_ids, regions, places, lat, lon, rad, target):
+        excluded = _sg_visited_lists(data_dir, [target[1], target[2]], vertex_ids) if new_places else None
+        return g.recommend_ranked_batch_near(vertex_ids, ALPHA, epsilon, max_iterations, places["id"], places["region_id"],
+                                             places["latitude"], places["longitude"], regions, lat, lon, rad,
+                                             max_recommendations, excluded=excluded)[:4]
+    return _near_requests("sg_recommender_requests_near", _sg_resolve_request_lines, per_graph, data_dir, persons, lines,
+                          positions, radius_meters, max_recommendations)
+
+
 def _sg_resolve_request_lines(data_dir, persons, lines, resolve=None):
     """The line-resolution loop of sg_recommender_requests and sg_recommender_requests_ranked: every line is parsed and
     resolved on its own (Try { ... } per line, :44-49) and the graph of [home, target] comes from the handle cache, one

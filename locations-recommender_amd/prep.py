@@ -10,6 +10,7 @@ SURVEY.md 8f rows f-2 and f-4) behind the names of the reference's builder objec
     rank_recommendations         printRecommendations of both mains       knn/KnnRecommenderMain.scala:90-101
     rank_recommendations_batch   ... for every segment of a batch's rows   (the same lines, per person)
     rank_recommendations_batch_excluding   ... leaving out a list of ids per segment (no counterpart: only new places)
+    rank_recommendations_batch_near        ... within a radius of a centre per segment (no counterpart: within reach)
     calc_person_likes_place_edges / calc_person_likes_category_edges / calc_category_selected_place_edges
                                  the three counted edge families          stochastic/PersonLikesPlace.scala:12-37 (and siblings)
     calc_place_similar_place_edges  PlaceSimilarPlace.calcPlaceSimilarPlaceEdges
@@ -238,6 +239,45 @@ def rank_recommendations_batch_excluding(offsets, ids, scores, place_ids, place_
     if nseg == 0 or width == 0:
         oc[:nseg] = 0
     return oi[:nseg * width].reshape(nseg, width), osc[:nseg * width].reshape(nseg, width), oc[:nseg]
+
+
+def rank_recommendations_batch_near(offsets, ids, scores, place_ids, place_region_ids, place_latitudes, place_longitudes,
+                                    target_region_ids, center_latitudes, center_longitudes, radius_meters,
+                                    max_recommendations, excluded_offsets=None, excluded_ids=None):
+    """rank_recommendations_batch within reach (locrec_rank_recommendations_batch_near): segment s ranks its rows whose
+    id is a place of target_region_ids[s] with a listing there no further than radius_meters[s] (>= 0 or +inf) from
+    (center_latitudes[s], center_longitudes[s]) by distance_meters - and, with excluded_offsets / excluded_ids, whose id
+    is not in its list (rank_recommendations_batch_excluding's).  Host or device arrays, all of one kind.
+    -> (ids[S, W], scores[S, W], meters[S, W], counts[S]): rank_recommendations_batch's layout, meters the distance of
+    each row's first listing inside the circle (padding 0.0)."""
+    if not _is_tensor(offsets):
+        offsets = np.asarray(offsets, np.int64)
+    lists = excluded_offsets is not None
+    cols = [offsets, ids, scores, place_ids, place_region_ids, place_latitudes, place_longitudes, target_region_ids,
+            center_latitudes, center_longitudes, radius_meters] + ([excluded_offsets, excluded_ids] if lists else [])
+    c = _Cols(*cols)
+    nseg, n, npl = len(target_region_ids), len(ids), len(place_ids)
+    assert len(offsets) == nseg + 1 and len(scores) == n and len(place_region_ids) == npl
+    assert len(place_latitudes) == npl and len(place_longitudes) == npl
+    assert len(center_latitudes) == nseg and len(center_longitudes) == nseg and len(radius_meters) == nseg
+    assert not lists or len(excluded_offsets) == nseg + 1
+    longest = int((offsets[1:] - offsets[:-1]).max()) if nseg else 0
+    width = max(0, min(int(max_recommendations), longest, n))
+    o = c.col(offsets, np.int64)
+    a = [c.col(ids, np.int64), c.col(scores, np.float64)]
+    p = [c.col(place_ids, np.int64), c.col(place_region_ids, np.int64), c.col(place_latitudes, np.float64),
+         c.col(place_longitudes, np.float64)]
+    t = c.col(target_region_ids, np.int64)
+    q = [c.col(x, np.float64) for x in (center_latitudes, center_longitudes, radius_meters)]
+    x = [c.col(excluded_offsets, np.int64), c.col(excluded_ids, np.int64)] if lists else [None, None]
+    (oi, oip), (osc, oscp), (om, omp), (oc, ocp) = (c.out(nseg * width, np.int64), c.out(nseg * width, np.float64),
+                                                    c.out(nseg * width, np.float64), c.out(nseg, np.int64))
+    L.check(L.lib().locrec_rank_recommendations_batch_near(nseg, o, n, a[0], a[1], npl, *p, t, *q, width, x[0],
+                                                           len(excluded_ids) if lists else 0, x[1], c.mem, oip, oscp, omp, ocp))
+    if nseg == 0 or width == 0:
+        oc[:nseg] = 0
+    shape = (nseg, width)
+    return oi[:nseg * width].reshape(shape), osc[:nseg * width].reshape(shape), om[:nseg * width].reshape(shape), oc[:nseg]
 
 
 def rank_recommendations_batch_stats():

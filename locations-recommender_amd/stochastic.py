@@ -199,6 +199,49 @@ class SgGraph:
         width = max(0, min(stride, int(rows.max()) if n else 0))
         return (np.ascontiguousarray(oi[:, :width]), np.ascontiguousarray(op[:, :width]), cnt, its, conv.astype(bool))
 
+    def recommend_ranked_batch_near(self, vertex_ids, alpha, epsilon, max_iterations, place_ids, place_region_ids,
+                                    place_latitudes, place_longitudes, target_region_ids, center_latitudes, center_longitudes,
+                                    radius_meters, max_recommendations, excluded=None, on_device=True):
+        """recommend_ranked_batch within reach (locrec_sg_recommend_ranked_batch_near): position i keeps only the places
+        of its target region with a listing no further than radius_meters[i] (>= 0 or +inf) from (center_latitudes[i],
+        center_longitudes[i]) - prep.rank_recommendations_batch_near's rule - and, with excluded=(offsets, ids), none of
+        its list.  on_device=False: recommend_batch's host rows through prep.rank_recommendations_batch_near (the same
+        result; the A/B partner).
+        -> (ids[n, W], probabilities[n, W], meters[n, W], counts[n], iterations[n], converged[n])."""
+        xoff = xids = None
+        if excluded is not None:
+            xoff, xids = L.as_i64(excluded[0]), L.as_i64(excluded[1])
+            if len(xoff) != len(vertex_ids) + 1:
+                raise L.IllegalArgumentException("one exclusion list per vertex is required: offsets of n + 1 entries")
+        if not on_device:
+            from . import prep
+            off, ids, probs, its, conv = self.recommend_batch(vertex_ids, alpha, epsilon, max_iterations)
+            oi, op, om, cnt = prep.rank_recommendations_batch_near(off, ids, probs, place_ids, place_region_ids, place_latitudes,
+                                                                   place_longitudes, target_region_ids, center_latitudes,
+                                                                   center_longitudes, radius_meters, max_recommendations, xoff, xids)
+            return oi, op, om, cnt, its, conv
+        v, pl, reg, tgt = L.as_i64(vertex_ids), L.as_i64(place_ids), L.as_i64(place_region_ids), L.as_i64(target_region_ids)
+        plat, plon = L.as_f64(place_latitudes), L.as_f64(place_longitudes)
+        clat, clon, rad = L.as_f64(center_latitudes), L.as_f64(center_longitudes), L.as_f64(radius_meters)
+        n = len(v)
+        if len(reg) != len(pl) or len(tgt) != n:
+            raise L.IllegalArgumentException("one region per place and one target region per vertex are required")
+        if len(plat) != len(pl) or len(plon) != len(pl) or not len(clat) == len(clon) == len(rad) == n:
+            raise L.IllegalArgumentException("one coordinate pair per place and one centre and radius per vertex are required")
+        stride = max(0, min(int(max_recommendations), self.info()["vertices"]))
+        oi, op, om = np.full((n, stride), -1, np.int64), np.zeros((n, stride), np.float64), np.zeros((n, stride), np.float64)
+        cnt, rows, its, conv = (np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, np.int32))
+        L.check(L.lib().locrec_sg_recommend_ranked_batch_near(
+            self._h, n, L.ptr(v, C.c_int64), float(alpha), float(epsilon), int(max_iterations), len(pl), L.ptr(pl, C.c_int64),
+            L.ptr(reg, C.c_int64), L.ptr(plat, C.c_double), L.ptr(plon, C.c_double), L.ptr(tgt, C.c_int64),
+            L.ptr(clat, C.c_double), L.ptr(clon, C.c_double), L.ptr(rad, C.c_double), stride,
+            L.ptr(xoff, C.c_int64), 0 if xids is None else len(xids), L.ptr(xids, C.c_int64),
+            L.ptr(oi, C.c_int64), L.ptr(op, C.c_double), L.ptr(om, C.c_double), L.ptr(cnt, C.c_int64), L.ptr(rows, C.c_int64),
+            L.ptr(its, C.c_int64), L.ptr(conv, C.c_int32)))
+        width = max(0, min(stride, int(rows.max()) if n else 0))
+        return (np.ascontiguousarray(oi[:, :width]), np.ascontiguousarray(op[:, :width]), np.ascontiguousarray(om[:, :width]),
+                cnt, its, conv.astype(bool))
+
     @classmethod
     def ranked_batch_stats(cls):
         """What this thread's last on-device recommend_ranked_batch did (locrec_sg_recommend_ranked_batch_stats)."""
