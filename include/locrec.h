@@ -1303,6 +1303,66 @@ int32_t locrec_rank_recommendations_batch_stats(int64_t *out_one_block, int64_t 
                                                 int64_t *out_sorted, int64_t *out_membership_form,
                                                 int64_t *out_host_assembled, int64_t *out_host_syncs);
 
+/*
+ * Offline evaluation (csrc/eval.hip; no counterpart in the reference, which has no metric anywhere): the two ends
+ * of the hold-out protocol around the builds and the ranked batches above.
+ *
+ * locrec_eval_ranked_batch scores ranked rows against one list of relevant ids per segment.  rec_ids / rec_counts
+ * are what every *_ranked_batch call returns: row s (stride `width`) holds rec_counts[s] ids and then padding, which
+ * is never read - a relevant id -1 does not match it.  The relevant lists are CSR: segment s's is
+ * rel_ids[rel_offsets[s] .. rel_offsets[s + 1]), unsorted, with repeats and with ids no row has, as it comes; ids are
+ * arbitrary int64 and match per (segment, id).  cutoffs: a HOST array of n_cutoffs (1 .. LOCREC_EVAL_MAX_CUTOFFS)
+ * values > 0, in any order, repeated or beyond `width` if the caller likes.  For segment s and cutoff k, with
+ * c = rec_counts[s], L = min(k, c), R = the distinct ids of the list, position r < L a HIT iff rec_ids[s][r] is in the
+ * list and no earlier position of the row holds the same id, h(r) = hits at positions <= r, d[r] = 1 / log2(r + 2):
+ *   hits = h(L - 1)   precision = hits / k   recall = hits / R   rr = 1 / (first hit position + 1), 0 without a hit
+ *   ap = (sum over hits of h(r) / (r + 1)) / min(R, k)   ndcg = (sum over hits of d[r]) / (sum of d[r], r < min(R, k))
+ * A segment with R == 0 gets zeros and is not evaluated.  `mem` covers rec_ids, rec_counts, rel_offsets, rel_ids,
+ * out_relevant [n_segments], out_hits [n_segments x n_cutoffs] and out_metrics [n_segments x n_cutoffs x 5, in the
+ * order above]; the last two may be NULL, and then nothing per segment but out_relevant leaves the device.  HOST
+ * outputs: out_means [n_cutoffs x 6] - the means of the five metrics over the evaluated segments and the share of
+ * them with hits > 0, zeros when none is evaluated; out_coverage [n_cutoffs] - the distinct ids at positions
+ * < min(k, c) of ALL segments; *out_evaluated - the segments with R > 0.
+ * LOCREC_E_INVALID_ARG and nothing written, the message naming the argument: n_cutoffs outside 1 .. 8, a cutoff
+ * <= 0, width < 0, n_segments, n_rel or n_segments x width >= 2^31, rel_offsets that are not non-decreasing inside
+ * [0, n_rel] (locrec_rank_recommendations_batch's rules), a rec_counts entry outside [0, width], a NULL out_means,
+ * out_coverage, out_evaluated or out_relevant.  Host arrays are checked on the host before any device work, device
+ * arrays on the device before anything is read through them.  n_segments == 0: zeros and no device work;
+ * width == 0: every count is 0, so the metrics and the coverage are zeros and no row is read (out_relevant and
+ * *out_evaluated still say what the lists hold).  Rows and lists have no length limit; two host synchronisations
+ * whatever n_segments; the same input gives the same bits in every output (fixed summation trees, integer atomics
+ * only).  Cutoffs above 2^53 lose bits in precision's division.
+ */
+#define LOCREC_EVAL_MAX_CUTOFFS 8
+int32_t locrec_eval_ranked_batch(int64_t n_segments, int64_t width, const int64_t *rec_ids, const int64_t *rec_counts,
+                                 const int64_t *rel_offsets, int64_t n_rel, const int64_t *rel_ids,
+                                 int32_t n_cutoffs, const int64_t *cutoffs, int32_t mem,
+                                 int64_t *out_relevant, int64_t *out_hits, double *out_metrics,
+                                 double *out_means, int64_t *out_coverage, int64_t *out_evaluated);
+
+/* What the last locrec_eval_ranked_batch of this thread did: the (segment, id) entries of the relevant table after
+ * de-duplication, the segments evaluated, the host synchronisations, and the path - 1: the wave-per-segment walk
+ * (the only one), 0: no device work (no segments, or a refusal on the host). */
+int32_t locrec_eval_ranked_batch_stats(int64_t *out_table_entries, int64_t *out_evaluated, int64_t *out_host_syncs,
+                                       int64_t *out_path);
+
+/*
+ * A visit table (the columns of locrec_calc_place_visits, n < 2^31 rows in `mem`) cut at a time.
+ * Train: the rows with timestamp < cut_timestamp, their numbers ascending in out_train_rows (room for n entries, in
+ * `mem`; NULL: only counted) - the row list a gather takes; *out_train_count (HOST) their number.
+ * Held out: the distinct (person, region, place) triples among the rows with timestamp >= cut_timestamp whose person
+ * has at least one train row - with new_places_only != 0 only those whose (person, place) has no train row -
+ * sorted by person, then region, then place, ascending as signed int64.  *inout_held_count (HOST): capacity in,
+ * number of triples out, with locrec_calc_place_visits' protocol: it may exceed the capacity, then the first
+ * `capacity` triples are written; any of the three outputs NULL only counts.  At most four host synchronisations
+ * whatever n.
+ */
+int32_t locrec_holdout_split(int64_t n, const int64_t *person_ids, const int64_t *timestamps, const int64_t *place_ids,
+                             const int64_t *region_ids, int64_t cut_timestamp, int32_t new_places_only, int32_t mem,
+                             int32_t *out_train_rows, int64_t *out_train_count,
+                             int64_t *out_person_ids, int64_t *out_region_ids, int64_t *out_place_ids,
+                             int64_t *inout_held_count);
+
 /* ===================================================================== */
 /* The place deduplicator (deduplicator/PlaceDeduplicator.scala,          */
 /* deduplicator/Levenshtein.scala).  Stateless, on the current device,    */

@@ -227,6 +227,12 @@ SIGNATURES = {
                                                C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p],
     "locrec_rank_recommendations_batch_stats": [_i64p, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p],
+    # offline evaluation (eval.hip): cutoffs, means, coverage and the counts are host arrays
+    "locrec_eval_ranked_batch": [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, _i64p,
+                                 C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, _f64p, _i64p, _i64p],
+    "locrec_eval_ranked_batch_stats": [_i64p, _i64p, _i64p, _i64p],
+    "locrec_holdout_split": [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                             C.c_void_p, _i64p, C.c_void_p, C.c_void_p, C.c_void_p, _i64p],
     # the place deduplicator (dedup.hip)
     "locrec_lev_distances": [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p],
     "locrec_find_duplicate_places": [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -98,6 +98,17 @@ inline hipError_t sum_by_key(void *temp, size_t &bytes, Keys keys, Values values
                                   rocprim::equal_to<K>(), s);
 }
 
+// the smallest value of every run of equal keys, the first key of every run, the number of runs
+template <class Keys, class Values, class UniqueOut, class MinsOut, class RunsOut>
+inline hipError_t min_by_key(void *temp, size_t &bytes, Keys keys, Values values, size_t n, UniqueOut unique_out, MinsOut mins_out,
+                             RunsOut runs_out, hipStream_t s)
+{
+    using K = typename std::iterator_traits<Keys>::value_type;
+    using V = typename std::iterator_traits<Values>::value_type;
+    return rocprim::reduce_by_key(temp, bytes, keys, values, n, unique_out, mins_out, runs_out, rocprim::minimum<V>(),
+                                  rocprim::equal_to<K>(), s);
+}
+
 template <class T>
 using counting_iterator = rocprim::counting_iterator<T>;
 

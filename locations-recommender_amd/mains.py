@@ -1271,3 +1271,91 @@ def _sg_requests_per_graph(graphs, graph_index, vertex_ids, alpha, epsilon, max_
     ids = np.concatenate([p[0] for p in parts]) if n else np.empty(0, np.int64)
     probs = np.concatenate([p[1] for p in parts]) if n else np.empty(0, np.float64)
     return off, ids, probs, its, conv
+
+
+# ---- offline evaluation: split at a time, build from the train visits, rank, score (csrc/eval.hip) -------------------
+
+def _holdout_requests(place_visits, cut_timestamp, new_places):
+    """holdout_split, and the requests its triples ask for: one per (person, region) with held-out places, as host
+    arrays in the triples' order."""
+    from . import prep
+    train, held = prep.holdout_split(place_visits, cut_timestamp, new_places_only=new_places)
+    held = {k: _host(v, np.int64) for k, v in held.items()}   # the ranked calls take and return host arrays
+    hp, hr = held["person_id"], held["region_id"]
+    first = np.ones(len(hp), bool)
+    first[1:] = (hp[1:] != hp[:-1]) | (hr[1:] != hr[:-1])
+    return train, held, hp[first], hr[first]
+
+
+def _evaluate_in_batches(rank, held, persons, regions, cutoffs, batch):
+    """rank(persons, regions, n) -> (ids[S, W], counts[S]) for every batch of the requests, each scored by
+    prep.evaluate_ranked.  The batches combine exactly: the metric SUMS (mean x evaluated) and the evaluated counts add
+    up, never means of means; the coverage is the size of the union of the batches' recommended ids per cutoff.
+    -> dict(means[n_cutoffs, 6], coverage[n_cutoffs], evaluated, relevant[n_requests], person_ids, region_ids)."""
+    from . import prep
+    cut = np.atleast_1d(np.asarray(cutoffs, np.int64))
+    batch = max(1, int(batch))
+    sums, evaluated, relevant = np.zeros((len(cut), 6)), 0, [np.empty(0, np.int64)]
+    seen = [np.empty(0, np.int64) for _ in cut]
+    for b in range(0, len(persons), batch):
+        p, r = persons[b:b + batch], regions[b:b + batch]
+        ids, counts = rank(p, r, int(cut.max()))
+        off, rel = prep.relevant_lists(held, p, r)
+        e = prep.evaluate_ranked(ids, counts, off, rel, cut)
+        sums += e["means"] * e["evaluated"]
+        evaluated += e["evaluated"]
+        relevant.append(e["relevant"])
+        live = np.arange(ids.shape[1])[None, :] < counts[:, None]
+        for j, k in enumerate(cut):
+            seen[j] = np.union1d(seen[j], ids[:, :k][live[:, :k]])
+    return {"means": sums / evaluated if evaluated else sums, "coverage": np.array([len(s) for s in seen], np.int64),
+            "evaluated": evaluated, "relevant": np.concatenate(relevant), "person_ids": persons, "region_ids": regions}
+
+
+def knn_holdout_evaluation(place_visits, places, cut_timestamp, place_weight, category_weight, k_nearest, cutoffs,
+                           new_places=True, batch=16384):
+    """The hold-out protocol for the KNN recommender: the visit table (calc_place_visits' mapping, host or device) is
+    cut at cut_timestamp, the index built from the train visits (prep.knn_index_from_visits), every train person ranked
+    for each region it has held-out places in (recommend_ranked_batch, unvisited=new_places, `batch` requests a call)
+    and the rows scored against those places at `cutoffs`.  new_places: only places the person has no train visit at
+    are relevant - and recommended.  places: mapping with id and region_id.  -> _evaluate_in_batches' dict."""
+    from . import prep
+    train, held, persons, regions = _holdout_requests(place_visits, cut_timestamp, new_places)
+    if len(persons) == 0:
+        return _evaluate_in_batches(None, held, persons, regions, cutoffs, batch)
+    pl, reg = _host(places["id"], np.int64), _host(places["region_id"], np.int64)
+    ix = prep.knn_index_from_visits(train["person_id"], train["place_id"], train["category_id"])
+    try:
+        def rank(p, r, n):
+            ids, _, counts = ix.recommend_ranked_batch(p, place_weight, category_weight, k_nearest, pl, reg, r, n,
+                                                       unvisited=bool(new_places))
+            return ids, counts
+        return _evaluate_in_batches(rank, held, persons, regions, cutoffs, batch)
+    finally:
+        ix.close()
+
+
+def sg_holdout_evaluation(place_visits, places, cut_timestamp, alpha, epsilon, max_iterations, beta_person_place,
+                          beta_person_category, cutoffs, new_places=True, batch=16384):
+    """The same protocol for the stochastic recommender: the graph is built from the train visits as
+    prep.sg_graph_from_visits builds it (the edge list is kept, for the lists below), every train person's vertex ranked
+    for each region it has held-out places in (recommend_ranked_batch), with new_places leaving out the person's
+    out-neighbours - the places it has been to (stochastic.out_neighbours).  -> _evaluate_in_batches' dict."""
+    from . import prep
+    from .stochastic import SgGraph, out_neighbours
+    train, held, persons, regions = _holdout_requests(place_visits, cut_timestamp, new_places)
+    if len(persons) == 0:
+        return _evaluate_in_batches(None, held, persons, regions, cutoffs, batch)
+    pl, reg = _host(places["id"], np.int64), _host(places["region_id"], np.int64)
+    s, t, w = prep.generate_stochastic_graph(train, beta_person_place, beta_person_category)
+    g = SgGraph.from_device(s.contiguous(), t.contiguous(), w.contiguous()) if prep._is_tensor(s) else SgGraph(s, t, w)
+    try:
+        hs, ht = (_host(s, np.int64), _host(t, np.int64)) if new_places else (None, None)
+
+        def rank(p, r, n):
+            excluded = out_neighbours(hs, ht, p) if new_places else None
+            ids, _, counts, _, _ = g.recommend_ranked_batch(p, alpha, epsilon, max_iterations, pl, reg, r, n, excluded=excluded)
+            return ids, counts
+        return _evaluate_in_batches(rank, held, persons, regions, cutoffs, batch)
+    finally:
+        g.close()

@@ -456,6 +456,108 @@ def sg_graph_from_visits(place_visits, beta_person_place, beta_person_category):
 PLACE_VISIT_COLUMNS = ("person_id", "timestamp", "place_id", "region_id", "category_id")   # PlaceVisits.scala:40-46
 
 
+# ---- offline evaluation (csrc/eval.hip; the reference has no counterpart) ---------------------------------------
+
+EVAL_MAX_CUTOFFS = 8
+EVAL_METRICS = ("precision", "recall", "rr", "ap", "ndcg")            # the last axis of `metrics`
+EVAL_MEANS = EVAL_METRICS + ("hit_rate",)                             # the columns of `means`
+EVAL_STATS = ("table_entries", "evaluated", "host_syncs", "path")
+HELD_COLUMNS = ("person_id", "region_id", "place_id")
+
+
+def holdout_split(place_visits, cut_timestamp, new_places_only=True):
+    """A visit table (calc_place_visits' mapping) cut at a time (locrec_holdout_split).
+    -> (train_place_visits, held): the five columns of the rows with timestamp < cut_timestamp in input order, and
+    dict(person_id, region_id, place_id) - the distinct triples among the rows at or behind the cut whose person has a
+    train row (new_places_only: and whose (person, place) has none), sorted by person, region, place.  Device in,
+    device out."""
+    cols = [place_visits[k] for k in ("person_id", "timestamp", "place_id", "region_id")]
+    c = _Cols(*cols)
+    n = len(cols[0])
+    a = [c.col(x, np.int64) for x in cols]
+    (rows, rowsp), outs = c.out(n, np.int32), [c.out(n, np.int64) for _ in HELD_COLUMNS]   # no more triples than rows
+    nt, nh = C.c_int64(), C.c_int64(n)
+    L.check(L.lib().locrec_holdout_split(n, *a, int(cut_timestamp), int(bool(new_places_only)), c.mem, rowsp, C.byref(nt),
+                                         *[o[1] for o in outs], C.byref(nh)))
+    rows = rows[:nt.value].long() if c.device else rows[:nt.value].astype(np.int64)
+    take = (lambda x: x[rows]) if c.device else (lambda x: np.asarray(x)[rows])
+    train = {k: take(place_visits[k]) for k in PLACE_VISIT_COLUMNS}
+    return train, {k: o[0][:nh.value] for k, o in zip(HELD_COLUMNS, outs)}
+
+
+def relevant_lists(held, person_ids, target_region_ids):
+    """Per request i the held-out places of person_ids[i] in target_region_ids[i], from holdout_split's sorted triples.
+    -> (offsets[n + 1], place_ids): evaluate_ranked's relevant lists, where `held` lies (numpy or torch).  A search over
+    the sorted triples - persons and regions are ranked among the triples' own, so that one int64 orders a
+    (person, region) pair - without a loop over the requests."""
+    hp, hr, hl = held["person_id"], held["region_id"], held["place_id"]
+    if _is_tensor(hp):
+        import torch as xp
+        i64 = lambda a: xp.as_tensor(a, dtype=xp.int64, device=hp.device)
+        search = lambda s, v, right=False: xp.searchsorted(s, v, right=right)
+        unique, arange, repeat = xp.unique, (lambda m: xp.arange(m, device=hp.device)), xp.repeat_interleave
+        zeros = lambda m: xp.zeros(m, dtype=xp.int64, device=hp.device)
+        clip = lambda a, hi: xp.clamp(a, max=hi)
+    else:
+        xp = np
+        i64 = lambda a: np.asarray(a, np.int64)
+        search = lambda s, v, right=False: np.searchsorted(s, v, "right" if right else "left")
+        unique, arange, repeat, zeros = np.unique, np.arange, np.repeat, (lambda m: np.zeros(m, np.int64))
+        clip = lambda a, hi: np.minimum(a, hi)
+    p, r = i64(person_ids), i64(target_region_ids)
+    assert len(p) == len(r)
+    offsets = zeros(len(p) + 1)
+    if len(hp) == 0 or len(p) == 0:
+        return offsets, hl[:0]
+    up, ur = unique(hp), unique(hr)
+    rank = lambda u, v: clip(search(u, v), len(u) - 1)
+    hkey = rank(up, hp) * len(ur) + rank(ur, hr)          # ascending: the triples are sorted by (person, region)
+    pi, ri = rank(up, p), rank(ur, r)
+    known = (up[pi] == p) & (ur[ri] == r)
+    key = pi * len(ur) + ri
+    lo, hi = search(hkey, key), search(hkey, key, right=True)
+    lengths = (hi - lo) * known
+    offsets[1:] = xp.cumsum(lengths, 0)
+    total = int(offsets[-1])
+    return offsets, hl[repeat(lo - offsets[:-1], lengths) + arange(total)]
+
+
+def evaluate_ranked(rec_ids, rec_counts, rel_offsets, rel_ids, cutoffs, per_segment=False):
+    """Ranked rows against relevant lists (locrec_eval_ranked_batch): rec_ids[S, W] / rec_counts[S] as every
+    *_ranked_batch call returns them, the lists as CSR (relevant_lists), cutoffs 1 to EVAL_MAX_CUTOFFS positive ints.
+    Host or device arrays, all of one kind.
+    -> dict(means[n_cutoffs, 6] (EVAL_MEANS, over the evaluated segments), coverage[n_cutoffs], evaluated,
+    relevant[S]) - with per_segment=True also hits[S, n_cutoffs] and metrics[S, n_cutoffs, 5] (EVAL_METRICS), where
+    the inputs lie; without it nothing per segment but `relevant` is copied."""
+    if not _is_tensor(rec_ids):
+        rec_ids = np.asarray(rec_ids, np.int64)
+    if rec_ids.ndim != 2:
+        raise L.IllegalArgumentException("rec_ids must be a matrix of one row per segment")
+    c = _Cols(rec_ids, rec_counts, rel_offsets, rel_ids)
+    nseg, width = int(rec_ids.shape[0]), int(rec_ids.shape[1])
+    if len(rec_counts) != nseg or len(rel_offsets) != nseg + 1:
+        raise L.IllegalArgumentException("one count per row and offsets of n + 1 entries are required")
+    cut = np.ascontiguousarray(np.atleast_1d(cutoffs), np.int64)
+    nc = len(cut)
+    a = [c.col(rec_ids.reshape(-1), np.int64), c.col(rec_counts, np.int64), c.col(rel_offsets, np.int64), c.col(rel_ids, np.int64)]
+    (rel, relp) = c.out(nseg, np.int64)
+    (hits, hitsp), (met, metp) = (c.out(nseg * nc, np.int64), c.out(nseg * nc * 5, np.float64)) if per_segment else ((None, None),) * 2
+    means, cov, ev = np.zeros((max(nc, 1), 6)), np.zeros(max(nc, 1), np.int64), C.c_int64()
+    L.check(L.lib().locrec_eval_ranked_batch(nseg, width, *a[:3], len(rel_ids), a[3], nc, L.ptr(cut, C.c_int64), c.mem, relp, hitsp,
+                                             metp, L.ptr(means, C.c_double), L.ptr(cov, C.c_int64), C.byref(ev)))
+    out = {"means": means[:nc], "coverage": cov[:nc], "evaluated": int(ev.value), "relevant": rel[:nseg]}
+    if per_segment:
+        out["hits"], out["metrics"] = hits[:nseg * nc].reshape(nseg, nc), met[:nseg * nc * 5].reshape(nseg, nc, 5)
+    return out
+
+
+def evaluate_ranked_stats():
+    """What the last evaluate_ranked of this thread did (locrec_eval_ranked_batch_stats), as a dict."""
+    v = [C.c_int64() for _ in EVAL_STATS]
+    L.check(L.lib().locrec_eval_ranked_batch_stats(*[C.byref(x) for x in v]))
+    return dict(zip(EVAL_STATS, (x.value for x in v)))
+
+
 def max_timestamp(timestamps):
     """max(timestamp) of PlaceVisits.calcVisitsFromTimestamp (PlaceVisits.scala:53-56) as an int.  No visits:
     IllegalArgumentException (the reference dereferences a null there)."""
