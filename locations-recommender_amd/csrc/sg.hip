@@ -56,17 +56,18 @@
 
 #include "common.h"
 #include "dev_prims.h"
+#include "sg_layout_plan.h"
 
 namespace {
 
 using namespace locrec;
 
-constexpr int kSlots = 256;       // edge slots per piece (64 lanes x 4)
+constexpr int kSlots = kSgPlanSlots;  // edge slots per piece (64 lanes x 4)
 constexpr int kParts = 64;        // finalize blocks == diff^2 partial sums
 constexpr int kMaxGraphRounds = 512;   // iterations per replayed hipGraph (even)
 constexpr size_t kMaxRoundGraphs = 48; // cached hipGraphExec_t per handle
 constexpr int kBeginBlocks = 32;  // blocks of a request's set-up launch (sg_begin), per graph
-constexpr int kLongRow = 8;       // rows with more full pieces are summed by a whole wave
+constexpr int kLongRow = kSgPlanLongRow;  // rows with more full pieces are summed by a whole wave
 constexpr int kWaveRowLoads = 16; // partial loads a lane of such a wave has in flight (one round covers 1,024 pieces)
 constexpr int kCheckEvery = 16;   // host looks at `done` this often when epsilon > 0
 // pieces per wave of sg_sweep.  Measured per cfg3 ITERATION (sweep + finalize, no events):
@@ -74,7 +75,7 @@ constexpr int kCheckEvery = 16;   // host looks at `done` this often when epsilo
 // per CU) 2 -> 20.7, 4 -> 16.9, 6 -> 15.9, 8 -> 16.2 us.  Many short waves win: each wave is one
 // dependent chain (stream loads -> gather -> butterfly -> store) and only more waves hide it.
 constexpr int kPiecesPerWave = 1;
-constexpr int kDictMax = 8192;     // distinct edge weights the dictionary form of the sweep takes (64 KB of LDS)
+constexpr int kDictMax = kSgPlanDictMax;  // distinct edge weights the dictionary form of the sweep takes (64 KB of LDS)
 
 struct SgState {
     int32_t done;    // sticky: a converged sweep has been observed
@@ -1241,13 +1242,6 @@ __global__ __launch_bounds__(512) void sg_persistent(const PersistParams P)
     }
 }
 
-int ceil_log2(int v)
-{
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return l;
-}
-
 }  // namespace
 
 struct locrec_sg_graph {
@@ -1398,479 +1392,7 @@ static void sg_read_env(locrec_sg_graph *g)
     g->env_persist = std::getenv("LOCREC_SG_PERSIST") != nullptr;            // the persistent form (an experiment)
 }
 
-// shard_index / shard_count: this handle holds the edges whose SOURCE vertex (its index in the
-// sorted vertex set) is congruent to shard_index modulo shard_count -- "rows of P sharded"; the
-// vertex set, the live set and the x layout are built from ALL edges and identical on every shard.
-static int32_t sg_create_impl(int64_t ne, const int64_t *src, const int64_t *dst, const double *w,
-                              int32_t shard_index, int32_t shard_count, bool by_target, locrec_sg_graph **out)
-{
-    if (!out) return fail(LOCREC_E_INVALID_ARG, "out_graph is NULL");
-    *out = nullptr;
-    if (ne < 0 || (ne > 0 && (!src || !dst || !w)))
-        return fail(LOCREC_E_INVALID_ARG, "bad edge arrays");
-    LOCREC_TRY(ensure_device());
-    std::unique_ptr<locrec_sg_graph> g(new (std::nothrow) locrec_sg_graph);
-    if (!g) return fail(LOCREC_E_OOM, "host allocation failed");
-    LOCREC_HIP_TRY(hipGetDevice(&g->device));
-    LOCREC_HIP_TRY(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
-    g->own_stream = true;
-    g->ne = ne;
-    sg_read_env(g.get());
-
-    // vertexes = distinct(source_id U target_id), StochasticRecommender.scala:42-49
-    std::vector<int64_t> &vid = g->vid;
-    try {
-        vid.resize((size_t)(2 * ne));
-    } catch (...) {
-        return fail(LOCREC_E_OOM, "host allocation failed");
-    }
-    // Ids that sit close together (the generator's and most real id spaces: categories, places, persons numbered
-    // one after the other) are ranked through a table over [min, max] - three linear passes - instead of sorting
-    // 2E ids and bisecting twice per edge (0.5 s of the 0.55 s locrec_sg_create took at cfg3); any other id space
-    // takes the sort.  Both give the same ascending `vid` and the same indices.
-    int64_t id_lo = INT64_MAX, id_hi = INT64_MIN;
-    for (int64_t e = 0; e < ne; ++e) {
-        id_lo = std::min(id_lo, std::min(src[e], dst[e]));
-        id_hi = std::max(id_hi, std::max(src[e], dst[e]));
-    }
-    const uint64_t id_span = ne > 0 ? (uint64_t)id_hi - (uint64_t)id_lo : 0;  // (max - min, exact in unsigned arithmetic)
-    const bool dense_ids = ne > 0 && id_span < (uint64_t)(8 * ne) + (1u << 20) && !g->env_no_dense_ids;
-    std::vector<int32_t> rank_of;  // dense_ids: id - id_lo -> vertex index
-    if (dense_ids) {
-        try {
-            rank_of.assign((size_t)id_span + 1, 0);
-        } catch (...) {
-            return fail(LOCREC_E_OOM, "host allocation failed");
-        }
-        for (int64_t e = 0; e < ne; ++e) {
-            rank_of[(size_t)((uint64_t)src[e] - (uint64_t)id_lo)] = 1;
-            rank_of[(size_t)((uint64_t)dst[e] - (uint64_t)id_lo)] = 1;
-        }
-        size_t k = 0;
-        for (size_t i = 0; i <= (size_t)id_span; ++i)
-            if (rank_of[i]) {
-                rank_of[i] = (int32_t)k;
-                vid[k++] = (int64_t)((uint64_t)id_lo + i);
-            }
-        vid.resize(k);
-        vid.shrink_to_fit();
-    } else {
-        for (int64_t e = 0; e < ne; ++e) {
-            vid[2 * e] = src[e];
-            vid[2 * e + 1] = dst[e];
-        }
-        std::sort(vid.begin(), vid.end());
-        vid.erase(std::unique(vid.begin(), vid.end()), vid.end());
-    }
-    const int64_t nv = (int64_t)vid.size();
-    if (nv >= ((int64_t)1 << 31) - 2) return fail(LOCREC_E_INVALID_ARG, "too many vertices");
-    g->nv = nv;
-
-    if (shard_count < 1 || shard_index < 0 || shard_index >= shard_count)
-        return fail(LOCREC_E_INVALID_ARG, "bad shard specification");
-    g->shard_index = shard_index;
-    g->shard_count = shard_count;
-    std::vector<int32_t> cs((size_t)ne), ct((size_t)ne);
-    std::vector<int32_t> deg((size_t)nv + 1, 0);   // in-degree over this shard's edges (piece plan)
-    std::vector<int32_t> gdeg((size_t)nv + 1, 0);  // in-degree over all edges (live set, row classes)
-    for (int64_t e = 0; e < ne; ++e) {
-        if (dense_ids) {
-            cs[e] = rank_of[(size_t)((uint64_t)src[e] - (uint64_t)id_lo)];
-            ct[e] = rank_of[(size_t)((uint64_t)dst[e] - (uint64_t)id_lo)];
-        } else {
-            cs[e] = (int32_t)(std::lower_bound(vid.begin(), vid.end(), src[e]) - vid.begin());
-            ct[e] = (int32_t)(std::lower_bound(vid.begin(), vid.end(), dst[e]) - vid.begin());
-        }
-        ++gdeg[ct[e]];
-    }
-    std::vector<int32_t>().swap(rank_of);
-    // live vertices, rows with at most two full pieces first (ascending id inside each class): the
-    // first `n_short` rows are then treated uniformly (three row-major partial slots each)
-    g->live_of.assign((size_t)nv, -1);
-    int32_t n_short_global = 0;
-    for (int pass = 0; pass < 2; ++pass) {
-        for (int64_t v = 0; v < nv; ++v)
-            if (gdeg[v] > 0 && (gdeg[v] / kSlots > 2) == (pass == 1)) {
-                g->live_of[v] = (int32_t)g->live_vertex.size();
-                g->live_vertex.push_back((int32_t)v);
-            }
-        if (pass == 0) n_short_global = (int32_t)g->live_vertex.size();
-    }
-    const int32_t T = (int32_t)g->live_vertex.size();
-    g->nlive = T;
-    const int32_t slot_d = T;
-    // which edges this handle keeps: rows of P (sources, by vertex index) or rows of P^T (targets, by
-    // LIVE index: the live rows are sorted by degree, so a stride spreads the heavy ones evenly)
-    auto owned = [&](int64_t e) {
-        return by_target ? g->live_of[ct[e]] % shard_count == shard_index : cs[e] % shard_count == shard_index;
-    };
-    for (int64_t e = 0; e < ne; ++e)
-        if (owned(e)) ++deg[ct[e]];
-
-    // piece plan over the live rows: full pieces first (row order), then remainder pieces by class 6..0
-    std::vector<RowMeta> meta((size_t)T);
-    std::vector<int32_t> long_rows;
-    int64_t nfull_total = 0;
-    int64_t nseg_cls[7] = {0, 0, 0, 0, 0, 0, 0};
-    std::vector<int8_t> rcls((size_t)T, -1);
-    for (int32_t l = 0; l < T; ++l) {
-        const int d = deg[g->live_vertex[l]];
-        RowMeta m{0, 0, -1};
-        m.nfull = d / kSlots;
-        m.full_begin = (int32_t)nfull_total;
-        nfull_total += m.nfull;
-        const int rem = d % kSlots;
-        if (rem > 0) {
-            const int c = ceil_log2((rem + 3) / 4);
-            rcls[l] = (int8_t)c;
-            ++nseg_cls[c];
-        }
-        if (m.nfull > kLongRow) long_rows.push_back(l);
-        meta[l] = m;
-    }
-    int64_t piece_begin_cls[7], part_begin_cls[7];
-    int64_t np = nfull_total, npart = nfull_total;
-    for (int c = 6; c >= 0; --c) {
-        const int segs_per_piece = 64 >> c;
-        const int64_t pieces = (nseg_cls[c] + segs_per_piece - 1) / segs_per_piece;
-        piece_begin_cls[c] = np;
-        part_begin_cls[c] = npart;
-        np += pieces;
-        npart += pieces * segs_per_piece;
-    }
-    if (np >= ((int64_t)1 << 31) / kSlots) return fail(LOCREC_E_INVALID_ARG, "graph too large for int32 slot ids");
-    g->npieces = (int32_t)np;
-    g->nlong = (int32_t)long_rows.size();
-
-    std::vector<int32_t> col((size_t)np * kSlots, slot_d);
-    std::vector<double> wv((size_t)np * kSlots, 0.0);
-    std::vector<int2> pinfo((size_t)np);
-    for (int64_t p = 0; p < nfull_total; ++p) pinfo[p] = make_int2((int)p, 6);
-    for (int c = 6; c >= 0; --c) {
-        const int segs_per_piece = 64 >> c;
-        const int64_t pieces = (nseg_cls[c] + segs_per_piece - 1) / segs_per_piece;
-        for (int64_t i = 0; i < pieces; ++i)
-            pinfo[piece_begin_cls[c] + i] = make_int2((int)(part_begin_cls[c] + i * segs_per_piece), c);
-    }
-    std::vector<int64_t> cursor((size_t)T, 0);      // edges placed so far in the row
-    std::vector<int64_t> rem_slot0((size_t)T, -1);  // absolute slot of remainder element 0
-    {
-        int64_t seg_used[7] = {0, 0, 0, 0, 0, 0, 0};
-        for (int32_t l = 0; l < T; ++l) {
-            const int c = rcls[l];
-            if (c < 0) continue;
-            const int segs_per_piece = 64 >> c;
-            const int64_t s = seg_used[c]++;
-            const int64_t piece = piece_begin_cls[c] + s / segs_per_piece;
-            const int seg = (int)(s % segs_per_piece);
-            meta[l].rem = (int32_t)(part_begin_cls[c] + s);
-            rem_slot0[l] = piece * kSlots + (int64_t)seg * (4 << c);
-        }
-    }
-    // scatter the edges in edge-list order (stable within a row); remember where the
-    // out-edges of source-only vertices landed
-    auto wofs = [](int64_t slot) {
-        const int64_t piece = slot / kSlots;
-        const int k = (int)(slot % kSlots);
-        const int lane = k >> 2, j = k & 3;
-        return piece * kSlots + (j >> 1) * 128 + lane * 2 + (j & 1);
-    };
-    g->dead_ptr.assign((size_t)nv + 1, 0);
-    for (int64_t e = 0; e < ne; ++e)
-        if (owned(e) && g->live_of[cs[e]] < 0) ++g->dead_ptr[cs[e] + 1];
-    for (int64_t v = 0; v < nv; ++v) g->dead_ptr[v + 1] += g->dead_ptr[v];
-    g->dead_slots.resize((size_t)g->dead_ptr[nv]);
-    std::vector<int64_t> dcur(g->dead_ptr.begin(), g->dead_ptr.end() - 1);
-    for (int64_t e = 0; e < ne; ++e) {
-        if (!owned(e)) continue;
-        const int32_t l = g->live_of[ct[e]];
-        const int64_t k = cursor[l]++;
-        const RowMeta &m = meta[l];
-        int64_t slot;
-        if (k < (int64_t)m.nfull * kSlots)
-            slot = (int64_t)m.full_begin * kSlots + k;
-        else
-            slot = rem_slot0[l] + (k - (int64_t)m.nfull * kSlots);
-        const int32_t sl = g->live_of[cs[e]];
-        if (sl >= 0) {
-            col[slot] = sl;
-        } else {
-            col[slot] = slot_d;
-            g->dead_slots[dcur[cs[e]]++] = (int32_t)slot;
-        }
-        wv[wofs(slot)] = w[e];
-    }
-
-    g->use16 = T + 2 <= 65536 && !g->env_no_col16;
-    g->device_sweep_bytes = 0;
-    if (!g->no_pack) {
-        void *hp = nullptr, *dp = nullptr;
-        if (hipHostMalloc(&hp, 64, hipHostMallocDefault) == hipSuccess && hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) {
-            g->h_poll = static_cast<int32_t *>(hp);
-            g->h_poll_dev = static_cast<int32_t *>(dp);
-        } else {
-            (void)hipGetLastError();
-            if (hp) (void)hipHostFree(hp);
-            g->no_pack = true;
-        }
-    }
-    if (g->env_gs > 0) {
-        int dev = 0, ncu = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-        g->gs_blocks = g->env_gs * std::max(1, ncu);
-    }
-    if (g->use16) {
-        std::vector<unsigned short> col16(col.size());
-        for (size_t i = 0; i < col.size(); ++i) col16[i] = (unsigned short)col[i];
-        LOCREC_TRY(g->col16.upload(col16, g->stream));
-        LOCREC_HIP_TRY(hipStreamSynchronize(g->stream));
-    } else {
-        LOCREC_TRY(g->col4.upload(reinterpret_cast<const int4 *>(col.data()), (size_t)np * 64, g->stream));
-    }
-    LOCREC_TRY(g->w2.upload(reinterpret_cast<const double2 *>(wv.data()), (size_t)np * 128, g->stream));
-    // The dictionary of the edge weights, built on the device from the weights just uploaded: their bit patterns sorted
-    // (rocPRIM radix sort) and run-length encoded; when there are at most kDictMax distinct ones the table is ordered by
-    // FREQUENCY (the lanes of a wave mostly ask for the common values: the 32 most common ones then sit in 32 different
-    // LDS bank pairs) and every slot's index found by bisection in the sorted values (sg_build_widx).  (A host pass with a
-    // hash table took 37 ms of a 100 ms create at cfg3; this takes ~2.)
-    if (!g->env_no_dict && np > 0) {
-        const size_t nslots = (size_t)np * kSlots;
-        hipStream_t s = g->stream;
-        DevBuf<uint64_t> ka, kb;
-        DevBuf<unsigned int> counts;
-        DevBuf<int32_t> nuniq;
-        DevBuf<unsigned char> tmp;
-        LOCREC_TRY(g->widx.alloc(nslots));  // (before the temporaries: what stays resident is allocated first)
-        LOCREC_TRY(g->dict.alloc(kDictMax));
-        LOCREC_TRY(ka.alloc(nslots));
-        LOCREC_TRY(kb.alloc(nslots));
-        LOCREC_TRY(counts.alloc(nslots));
-        LOCREC_TRY(nuniq.alloc(1));
-        LOCREC_HIP_TRY(hipMemcpyAsync(ka.p, g->w2.p, nslots * 8, hipMemcpyDeviceToDevice, s));
-        size_t b1 = 0, b2 = 0;
-        LOCREC_HIP_TRY(prim::sort_keys(nullptr, b1, ka.p, kb.p, nslots, 0u, 64u, s));
-        LOCREC_HIP_TRY(prim::run_length_encode(nullptr, b2, kb.p, nslots, ka.p, counts.p, nuniq.p, s));
-        LOCREC_TRY(tmp.alloc(std::max(b1, b2)));
-        LOCREC_HIP_TRY(prim::sort_keys(tmp.p, b1, ka.p, kb.p, nslots, 0u, 64u, s));
-        LOCREC_HIP_TRY(prim::run_length_encode(tmp.p, b2, kb.p, nslots, ka.p, counts.p, nuniq.p, s));
-        int32_t nu = 0;
-        LOCREC_HIP_TRY(hipMemcpyAsync(&nu, nuniq.p, sizeof(nu), hipMemcpyDeviceToHost, s));
-        LOCREC_HIP_TRY(hipStreamSynchronize(s));
-        if (nu >= 1 && nu <= kDictMax) {
-            std::vector<uint64_t> vals((size_t)nu);
-            std::vector<unsigned int> cnt((size_t)nu);
-            LOCREC_HIP_TRY(hipMemcpyAsync(vals.data(), ka.p, (size_t)nu * 8, hipMemcpyDeviceToHost, s));
-            LOCREC_HIP_TRY(hipMemcpyAsync(cnt.data(), counts.p, (size_t)nu * 4, hipMemcpyDeviceToHost, s));
-            LOCREC_HIP_TRY(hipStreamSynchronize(s));
-            std::vector<int32_t> order((size_t)nu);
-            std::iota(order.begin(), order.end(), 0);
-            std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return cnt[(size_t)a] > cnt[(size_t)b]; });
-            std::vector<double> dict_h((size_t)nu);
-            std::vector<unsigned short> rank_h((size_t)nu);  // position in the sorted values -> table index
-            for (int32_t r = 0; r < nu; ++r) {
-                std::memcpy(&dict_h[(size_t)r], &vals[(size_t)order[(size_t)r]], 8);
-                rank_h[(size_t)order[(size_t)r]] = (unsigned short)r;
-            }
-            DevBuf<unsigned short> rank;
-            LOCREC_HIP_TRY(hipMemcpyAsync(g->dict.p, dict_h.data(), (size_t)nu * 8, hipMemcpyHostToDevice, s));
-            LOCREC_TRY(rank.upload(rank_h, s));
-            hipLaunchKernelGGL(sg_build_widx, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, s,
-                               reinterpret_cast<const double *>(g->w2.p), (int64_t)nslots, ka.p, rank.p, nu, g->widx.p);
-            LOCREC_HIP_TRY(hipGetLastError());
-            LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (locals)
-            g->ndict = nu;
-        } else {
-            g->widx.release();
-            g->dict.release();
-        }
-    }
-    LOCREC_TRY(g->pinfo.upload(pinfo, g->stream));
-    LOCREC_TRY(g->xbuf.alloc((size_t)(2 * (T + 2))));
-    LOCREC_TRY(g->parts.alloc(2 * kParts));
-    LOCREC_TRY(g->state.alloc(1));
-    if (g->dead_slots.size() > (size_t)INT32_MAX) return fail(LOCREC_E_INVALID_ARG, "too many out-edges of source-only vertices");
-    LOCREC_TRY(g->dead_slots_dev.upload(g->dead_slots, g->stream));
-    g->layout_bytes = np * kSlots * 12 + np * 8 + (int64_t)T * 12;
-    // what one sweep + finalize really moves in THIS layout: columns (2 or 4 B) and fp64 weights of
-    // every slot (padding included), piece descriptors, one partial written and read back per
-    // segment, x read and x' written once per live vertex
-    // (dictionary form: a uint16 index per slot instead of the fp64 weight; the value table is read once per block)
-    g->device_sweep_bytes = np * kSlots * (int64_t)((g->use16 ? 2 : 4) + (g->ndict > 0 ? 2 : 8)) + np * 8 + npart * 16 + (int64_t)T * 16;
-    {
-        // row-major partial slots (l*3 + j for rows with <= 2 full pieces, a contiguous run behind
-        // them for the others); seg_out maps a segment (old contiguous numbering: pinfo.x + seg) to
-        // its slot, lane_out does the same per leader lane for the persistent kernel
-        std::vector<int32_t> long_begin((size_t)T, -1);
-        std::vector<int4> lrows;
-        int64_t pa = 3 * (int64_t)T;
-        g->n_short = n_short_global;
-        for (int32_t l = 0; l < T; ++l) {
-            if (l >= n_short_global) {  // a long row somewhere: it lives in the long area on every shard
-                long_begin[l] = (int32_t)pa;
-                lrows.push_back(make_int4(l, (int)pa, meta[l].nfull, meta[l].rem >= 0 ? 1 : 0));
-                pa += meta[l].nfull + 1;
-            }
-        }
-        std::vector<int32_t> lane_out((size_t)np * 64, -1);
-        std::vector<int32_t> seg_out((size_t)npart, -1);
-        std::vector<int32_t> rem_owner((size_t)npart, -1);  // old partial index -> live row
-        for (int32_t l = 0; l < T; ++l) {
-            const RowMeta &m = meta[l];
-            for (int j = 0; j < m.nfull; ++j) {  // full piece id == its old partial index
-                const int32_t slot = long_begin[l] >= 0 ? long_begin[l] + j : 3 * l + j;
-                lane_out[(size_t)(m.full_begin + j) * 64] = slot;
-                seg_out[m.full_begin + j] = slot;
-            }
-            if (m.rem >= 0) rem_owner[m.rem] = l;
-        }
-        for (int64_t p = nfull_total; p < np; ++p) {
-            const int c = pinfo[p].y, base = pinfo[p].x;
-            for (int sgm = 0; sgm < (64 >> c); ++sgm) {
-                const int32_t l = rem_owner[base + sgm];
-                if (l < 0) continue;
-                const int32_t slot = long_begin[l] >= 0 ? long_begin[l] + meta[l].nfull : 3 * l + 2;
-                lane_out[(size_t)p * 64 + ((size_t)sgm << c)] = slot;
-                seg_out[base + sgm] = slot;
-            }
-        }
-        // fused iteration (sg_sweep_fused): its own slot map - four slots per class-A row, a run per longer row with the X
-        // slot at its end - and the second piece list: the edges whose SOURCE is a longer row, grouped by target row
-        // into one pow2 segment each (at most 256 of them per row, or the handle keeps the two-launch form).  Built only
-        // where it is asked for: an experiment (LOCREC_SG_FUSED), not the product path.
-        if (shard_count == 1 && g->env_fused) {
-            const int32_t n_long = T - n_short_global;
-            std::vector<int32_t> seg_fa((size_t)npart, -1), xslot((size_t)T, -1), lbegin((size_t)T, -1);
-            std::vector<int4> lrows_f;
-            int64_t pa4 = 4 * (int64_t)n_short_global;
-            for (int32_t l = n_short_global; l < T; ++l) {
-                lbegin[l] = (int32_t)pa4;
-                lrows_f.push_back(make_int4(l, (int)pa4, meta[l].nfull, meta[l].rem >= 0 ? 1 : 0));
-                pa4 += meta[l].nfull + 2;
-            }
-            for (int32_t l = 0; l < T; ++l) {
-                const RowMeta &m = meta[l];
-                for (int j = 0; j < m.nfull; ++j) seg_fa[m.full_begin + j] = l < n_short_global ? 4 * l + j : lbegin[l] + j;
-                xslot[l] = l < n_short_global ? 4 * l + 3 : lbegin[l] + m.nfull + 1;
-            }
-            for (int64_t p = nfull_total; p < np; ++p) {
-                const int c = pinfo[p].y, base = pinfo[p].x;
-                for (int sgm = 0; sgm < (64 >> c); ++sgm) {
-                    const int32_t l = rem_owner[base + sgm];
-                    if (l >= 0) seg_fa[base + sgm] = l < n_short_global ? 4 * l + 2 : lbegin[l] + meta[l].nfull;
-                }
-            }
-            std::stable_partition(lrows_f.begin(), lrows_f.end(), [](const int4 &r) { return r.z > kLongRow; });
-            // the second piece list
-            std::vector<int32_t> cnt2((size_t)T, 0);
-            for (int64_t e = 0; e < ne; ++e) {
-                const int32_t sl = g->live_of[cs[e]];
-                if (sl >= n_short_global) ++cnt2[g->live_of[ct[e]]];
-            }
-            bool ok = pa4 < ((int64_t)1 << 30);
-            int64_t seg_n[7] = {0, 0, 0, 0, 0, 0, 0};
-            std::vector<int8_t> cls2((size_t)T, -1);
-            for (int32_t l = 0; l < T && ok; ++l) {
-                if (cnt2[l] == 0) continue;
-                if (cnt2[l] > kSlots) { ok = false; break; }
-                int c = 0;
-                while ((4 << c) < cnt2[l]) ++c;
-                cls2[l] = (int8_t)c;
-                ++seg_n[c];
-            }
-            g->fused_ok = ok;
-            g->use_fused = ok;
-            if (ok) {
-                int64_t piece0[7], segbase[7], np2 = 0, nseg2 = 0;
-                for (int c = 0; c < 7; ++c) {
-                    piece0[c] = np2;
-                    segbase[c] = nseg2;
-                    const int64_t per = 64 >> c, pcs = (seg_n[c] + per - 1) / per;
-                    np2 += pcs;
-                    nseg2 += pcs * per;
-                }
-                std::vector<int32_t> col2((size_t)np2 * kSlots, -1), seg2((size_t)nseg2, -1);
-                std::vector<double> wv2((size_t)np2 * kSlots, 0.0);
-                std::vector<int2> pinfo2((size_t)np2);
-                for (int c = 0; c < 7; ++c)
-                    for (int64_t p = piece0[c]; p < (c < 6 ? piece0[c + 1] : np2); ++p)
-                        pinfo2[p] = make_int2((int)(segbase[c] + (p - piece0[c]) * (64 >> c)), c);
-                std::vector<int64_t> slot0((size_t)T, -1);
-                int64_t used[7] = {0, 0, 0, 0, 0, 0, 0};
-                for (int32_t l = 0; l < T; ++l) {
-                    const int c = cls2[l];
-                    if (c < 0) continue;
-                    const int64_t sidx = used[c]++, per = 64 >> c;
-                    slot0[l] = (piece0[c] + sidx / per) * kSlots + (sidx % per) * (4 << c);
-                    seg2[segbase[c] + sidx] = xslot[l];
-                }
-                std::vector<int32_t> cur2((size_t)T, 0);
-                for (int64_t e = 0; e < ne; ++e) {  // edge-list order inside a row, like the main pieces
-                    const int32_t sl = g->live_of[cs[e]];
-                    if (sl < n_short_global) continue;
-                    const int32_t l = g->live_of[ct[e]];
-                    const int64_t slot = slot0[l] + cur2[l]++;
-                    col2[slot] = sl;
-                    wv2[wofs(slot)] = w[e];
-                }
-                g->pa4 = (int32_t)std::max<int64_t>(1, pa4);
-                g->npieces2 = (int32_t)np2;
-                g->nduty = std::max(1, (n_short_global + 63) / 64);
-                LOCREC_TRY(g->seg_fa.upload(seg_fa, g->stream));
-                LOCREC_TRY(g->lrows_f.upload(lrows_f, g->stream));
-                LOCREC_TRY(g->col2.upload(col2, g->stream));
-                LOCREC_TRY(g->seg2.upload(seg2, g->stream));
-                LOCREC_TRY(g->pinfo2.upload(pinfo2, g->stream));
-                LOCREC_TRY(g->w2b.upload(reinterpret_cast<const double2 *>(wv2.data()), (size_t)np2 * 128, g->stream));
-                LOCREC_TRY(g->PA4.alloc((size_t)4 * g->pa4));
-                LOCREC_TRY(g->XL.alloc((size_t)4 * std::max(1, n_long)));
-                LOCREC_TRY(g->D2W.alloc((size_t)4 * (g->nduty + kParts)));
-                LOCREC_TRY(g->fused_conv.alloc(2));
-                // (slots no kernel writes - a remainder or X slot of a row without one - stay 0.0 for good)
-                LOCREC_HIP_TRY(hipMemsetAsync(g->PA4.p, 0, g->PA4.bytes(), g->stream));
-                LOCREC_HIP_TRY(hipMemsetAsync(g->XL.p, 0, g->XL.bytes(), g->stream));
-                LOCREC_HIP_TRY(hipMemsetAsync(g->D2W.p, 0, g->D2W.bytes(), g->stream));
-                LOCREC_HIP_TRY(hipStreamSynchronize(g->stream));  // (the vectors are locals)
-                if (g->use_fused && !g->fused_one_stream)
-                    LOCREC_HIP_TRY(hipStreamCreateWithFlags(&g->stream2, hipStreamNonBlocking));
-            }
-        }
-        if (pa >= ((int64_t)1 << 30)) return fail(LOCREC_E_INVALID_ARG, "graph too large for int32 partial slots");
-        // rows summed by a whole wave first, then the ones a single thread sums (slot order is
-        // not affected: every entry carries its own first slot)
-        std::stable_partition(lrows.begin(), lrows.end(), [](const int4 &r) { return r.z > kLongRow; });
-        g->n_crows = 0;
-        for (const int4 &r : lrows) g->n_crows += r.z > kLongRow ? 1 : 0;
-        g->pa_stride = (int32_t)pa;
-        g->nlrows = (int32_t)lrows.size();
-        LOCREC_TRY(g->seg_out.upload(seg_out, g->stream));
-        LOCREC_TRY(g->lrows.upload(lrows, g->stream));
-        LOCREC_TRY(g->PA.alloc((size_t)(2 * pa)));
-        LOCREC_HIP_TRY(hipMemsetAsync(g->PA.p, 0, (size_t)(2 * pa) * sizeof(double), g->stream));
-        LOCREC_HIP_TRY(hipStreamSynchronize(g->stream));
-        int dev = 0, ncu = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-        const int64_t waves = (int64_t)ncu * 8;
-        const int64_t need = waves > 0 ? (np + waves - 1) / waves : 1 << 30;
-        const size_t lds = (size_t)(T + 2) * 8;
-        g->persist_pw = need <= 4 ? 4 : need <= 12 ? 12 : 0;  // 8 and 16 spill registers: not built
-        g->persist_ok = shard_count == 1 && g->persist_pw > 0 && lds <= 128 * 1024 && ncu > 0 && pa < ((int64_t)1 << 30) &&
-                        g->env_persist;  // opt-in: see the note above sg_persistent
-        if (g->persist_ok) {
-            g->persist_blocks = ncu;
-            g->persist_lds = lds;
-            LOCREC_TRY(g->lane_out.upload(lane_out, g->stream));
-            LOCREC_TRY(g->barrier.alloc(1));
-            if (debug_env("LOCREC_SG_DEBUG_PHASES")) LOCREC_TRY(g->dbg.alloc(4));
-            LOCREC_HIP_TRY(hipStreamSynchronize(g->stream));
-        }
-    }
-    LOCREC_HIP_TRY(hipStreamSynchronize(g->stream));
-    std::vector<int32_t>().swap(g->dead_slots);  // resident on the device now (dead_slots_dev); dead_ptr stays on the host
-    *out = g.release();
-    return LOCREC_OK;
-}
+#include "sg_host_build.h"  // sg_create_impl: the host build, over sg_host_layout.h and sg_build_shared.h
 
 extern "C" int32_t locrec_sg_create(int64_t ne, const int64_t *src, const int64_t *dst, const double *w,
                                     locrec_sg_graph **out) try

@@ -2,10 +2,10 @@
 // an edge list that already lives in device memory (the SG counterpart of locrec_knn_create_from_device).
 //
 // This file is the SG translation unit: it includes sg_batch.hip whole (which includes sg.hip whole), so it sees the
-// handle and its constants.  sg.hip stays as it is (its bytes key the committed counter record, bench.PMC_SOURCES), so
-// the part of sg_create_impl behind the host scatter (work buffers, dictionary, maps) is restated here over device
-// arrays instead of being shared; the contract is that both builders leave the SAME handle, element for element
-// ("Device build"; tests/test_gpu_sg_device_build.py compares them).
+// handle and its constants.  The contract is that both builders leave the SAME handle, element for element (DESIGN.md
+// 4, "Device build"; tests/test_gpu_sg_device_build.py compares them).  They share every layout rule (sg_layout_plan.h)
+// and what happens to the handle once columns and weights are resident: the poll word, the weight dictionary and the
+// closing figures are sg_build_shared.h's, called from here and from the host build (sg_host_build.h).
 //
 // The host side is sg_create_device_impl at the end: named phases over one Build, in the order they run.  What the host
 // decides or computes about the layout - the plan from the scan's totals with its two refusals, the id-table and
@@ -22,9 +22,6 @@
 #include "sg_layout_plan.h"
 
 namespace {
-
-static_assert(kSgPlanSlots == kSlots && kSgPlanLongRow == kLongRow && kSgPlanDictMax == kDictMax,
-              "sg_layout_plan.h carries sg.hip's constants");
 
 constexpr int kDbThreads = 256;
 
@@ -380,12 +377,12 @@ struct Build {
     DevBuf<int32_t> slot_of_edge;  // scatter_edges: the slot of every edge whose source is not live
     DevBuf<int32_t> bad;           // scatter_edges' verdict (lives as long as the Build)
     DevBuf<int64_t> dead_ptr;      // dead_slots
-    int ncu = 0;                   // poll_word_and_grid
+    int ncu = 0;                   // sg_compute_units_and_grid, for finish_handle
 
     // the phases, in the order sg_create_device_impl runs them
     int32_t open(locrec_sg_graph **out, bool *built_on_host);
     int32_t rank_vertices(), sort_rows(), live_order(), piece_plan(), alloc_resident(), row_maps(), scatter_edges(), dead_slots();
-    int32_t host_tables(), poll_word_and_grid(), dictionary(), finish_handle();
+    int32_t host_tables(), finish_handle();
 };
 
 // argument and pointer checks, the handle with its switches and stream.  *built_on_host: the call is already answered
@@ -680,87 +677,10 @@ int32_t Build::host_tables()
     return LOCREC_OK;
 }
 
-// from here on the rest of sg_create_impl, over the arrays that are already resident: the poll word of the packed
-// requests, the compute units (persist_pw below) and the grid of the grid-stride sweep
-int32_t Build::poll_word_and_grid()
-{
-    g->device_sweep_bytes = 0;
-    if (!g->no_pack) {
-        void *hp = nullptr, *dp = nullptr;
-        if (hipHostMalloc(&hp, 64, hipHostMallocDefault) == hipSuccess && hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) {
-            g->h_poll = static_cast<int32_t *>(hp);
-            g->h_poll_dev = static_cast<int32_t *>(dp);
-        } else {
-            (void)hipGetLastError();
-            if (hp) (void)hipHostFree(hp);
-            g->no_pack = true;
-        }
-    }
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, g->device) != hipSuccess)
-        (void)hipGetLastError();  // (tolerated: ncu = 0 below; the dictionary's launch check must not report it)
-    if (g->env_gs > 0) g->gs_blocks = g->env_gs * std::max(1, ncu);
-    return LOCREC_OK;
-}
-
-// the weight dictionary, exactly as sg_create_impl builds it from the uploaded weights (see the comment there)
-int32_t Build::dictionary()
-{
-    if (g->env_no_dict || plan.np == 0) return LOCREC_OK;
-    const size_t nslots = (size_t)plan.nslots();
-    DevBuf<uint64_t> ka, kb;
-    DevBuf<unsigned int> counts;
-    DevBuf<int32_t> nuniq;
-    DevBuf<unsigned char> storage;
-    LOCREC_TRY(g->widx.alloc(nslots));  // (before the temporaries: what stays resident is allocated first)
-    LOCREC_TRY(g->dict.alloc(kDictMax));
-    LOCREC_TRY(ka.alloc(nslots));
-    LOCREC_TRY(kb.alloc(nslots));
-    LOCREC_TRY(counts.alloc(nslots));
-    LOCREC_TRY(nuniq.alloc(1));
-    LOCREC_HIP_TRY(hipMemcpyAsync(ka.p, g->w2.p, nslots * 8, hipMemcpyDeviceToDevice, s));
-    size_t b1 = 0, b2 = 0;  // (not LOCREC_PRIM: both calls are sized before the one allocation, as sg_create_impl does)
-    LOCREC_HIP_TRY(prim::sort_keys(nullptr, b1, ka.p, kb.p, nslots, 0u, 64u, s));
-    LOCREC_HIP_TRY(prim::run_length_encode(nullptr, b2, kb.p, nslots, ka.p, counts.p, nuniq.p, s));
-    LOCREC_TRY(storage.alloc(std::max(b1, b2)));
-    LOCREC_HIP_TRY(prim::sort_keys(storage.p, b1, ka.p, kb.p, nslots, 0u, 64u, s));
-    LOCREC_HIP_TRY(prim::run_length_encode(storage.p, b2, kb.p, nslots, ka.p, counts.p, nuniq.p, s));
-    int32_t nu = 0;
-    LOCREC_READ_BACK(nu, nuniq.p, s);
-    if (sg_dict_fits(nu)) {
-        std::vector<uint64_t> vals((size_t)nu);
-        std::vector<unsigned int> cnt((size_t)nu);
-        LOCREC_HIP_TRY(hipMemcpyAsync(vals.data(), ka.p, (size_t)nu * 8, hipMemcpyDeviceToHost, s));
-        LOCREC_HIP_TRY(hipMemcpyAsync(cnt.data(), counts.p, (size_t)nu * 4, hipMemcpyDeviceToHost, s));
-        LOCREC_HIP_TRY(hipStreamSynchronize(s));
-        std::vector<int32_t> order((size_t)nu);
-        std::iota(order.begin(), order.end(), 0);
-        std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return cnt[(size_t)a] > cnt[(size_t)b]; });
-        std::vector<double> dict_h((size_t)nu);
-        std::vector<unsigned short> rank_h((size_t)nu);  // position in the sorted values -> table index
-        for (int32_t r = 0; r < nu; ++r) {
-            std::memcpy(&dict_h[(size_t)r], &vals[(size_t)order[(size_t)r]], 8);
-            rank_h[(size_t)order[(size_t)r]] = (unsigned short)r;
-        }
-        DevBuf<unsigned short> rank;
-        LOCREC_HIP_TRY(hipMemcpyAsync(g->dict.p, dict_h.data(), (size_t)nu * 8, hipMemcpyHostToDevice, s));
-        LOCREC_TRY(rank.upload(rank_h, s));
-        LOCREC_LAUNCH(sg_build_widx, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, s,
-                      reinterpret_cast<const double *>(g->w2.p), (int64_t)nslots, ka.p, rank.p, nu, g->widx.p);
-        LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (locals)
-        g->ndict = nu;
-    } else {
-        g->widx.release();
-        g->dict.release();
-    }
-    return LOCREC_OK;
-}
-
 // the byte figures bench.py reports, persist_pw, the phase times
 int32_t Build::finish_handle()
 {
-    g->layout_bytes = sg_layout_bytes(plan.np, T);
-    g->device_sweep_bytes = sg_device_sweep_bytes(plan.np, plan.npart, T, g->use16, g->ndict > 0);
-    g->persist_pw = sg_persist_pw(plan.np, ncu);
+    sg_closing_figures(g.get(), plan.np, plan.npart, ncu);
     g->persist_ok = false;  // (LOCREC_SG_PERSIST handles come from the host build)
     return clock.read(g_db_stats.ms);
 }
@@ -786,9 +706,10 @@ int32_t sg_create_device_impl(int64_t ne, const int64_t *src, const int64_t *dst
     LOCREC_TRY(b.scatter_edges());
     LOCREC_TRY(b.dead_slots());
     LOCREC_TRY(b.host_tables());
-    LOCREC_TRY(b.poll_word_and_grid());
+    sg_poll_word(b.g.get());  // from here on what the host build does too, over the resident arrays (sg_build_shared.h)
+    b.ncu = sg_compute_units_and_grid(b.g.get());
     LOCREC_TRY(b.clock.mark(kDbDict));
-    LOCREC_TRY(b.dictionary());
+    LOCREC_TRY(sg_weight_dictionary(b.g.get(), b.plan.np));
     LOCREC_TRY(b.clock.mark(-1));
     LOCREC_TRY(b.finish_handle());
     *out = b.g.release();

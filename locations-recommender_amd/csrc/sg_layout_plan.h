@@ -1,8 +1,9 @@
-// sg_layout_plan.h -- every decision and every piece of arithmetic of the stochastic graph's layout that the device build
-// (sg_create_device.hip) makes on the host, and the three per-row rules its kernels share with it ("Device
-// build": the piece plan of sg_create_impl in closed form).  Plain C++ with constants of its own, nothing from HIP and
-// no device call: tests/host/sg_layout_plan_check.cpp compiles it alone and compares it with a row-by-row walk of the
-// layout, under a host sanitizer; sg_create_device.hip asserts the constants against sg.hip's.
+// sg_layout_plan.h -- the one statement of every rule of the stochastic graph's layout: the constants, the three per-row
+// rules, the piece plan in closed form from a scan's totals, the smaller decisions and the byte figures.
+// Both builders take them from here - the host build (sg_host_layout.h) and the device build (sg_create_device.hip,
+// whose kernels share the per-row rules) - and sg.hip's kSlots, kLongRow and kDictMax are these constants.  Plain C++,
+// nothing from HIP and no device call: tests/host/sg_layout_plan_check.cpp compiles it alone and compares it with a
+// row-by-row walk of the layout, under a host sanitizer.
 #pragma once
 
 #include <cstdint>
@@ -15,14 +16,14 @@
 
 namespace locrec {
 
-constexpr int kSgPlanSlots = 256;     // sg.hip's kSlots: edge slots per piece
+constexpr int kSgPlanSlots = 256;     // sg.hip's kSlots: edge slots per piece (64 lanes x 4)
 constexpr int kSgPlanLongRow = 8;     // kLongRow: rows with more full pieces are summed by a whole wave
-constexpr int kSgPlanDictMax = 8192;  // kDictMax: distinct weights the dictionary form takes
+constexpr int kSgPlanDictMax = 8192;  // kDictMax: distinct weights the dictionary form takes (64 KB of LDS)
 constexpr int kSgPlanClasses = 7;     // remainder classes 0 .. 6: a segment of 4 << c slots, 64 >> c segments per piece
 
 // ---- per row: what the kernels ask too ------------------------------------------------------------------------------
 
-// the remainder class of sg_create_impl: ceil_log2((rem + 3) / 4), rem in 1 .. 255
+// the remainder class: ceil_log2((rem + 3) / 4), the smallest c whose segment of 4 << c slots holds rem in 1 .. 256
 LOCREC_SG_PLAN_FN int sg_remainder_class(int rem)
 {
     const int v = (rem + 3) / 4;
@@ -76,9 +77,10 @@ inline SgLayoutPlan sg_layout_plan(const int32_t rows_of_class[kSgPlanClasses], 
         pl.np += pieces;
         pl.npart += pieces * segs_per_piece;
     }
-    // the long area: a run of nfull + 1 slots per row from n_short on, in row order.  sg_create_impl keeps a running
-    // pa; row l's run starts at 3T + (full pieces of the long rows before it) + (l - n_short), which is
-    // long_base + full_begin[l] + l with the base below, and the area ends at pa.
+    // the long area: a run of nfull + 1 slots per row from n_short on, in row order.  Row l's run starts at
+    // 3T + (full pieces of the long rows before it) + (l - n_short), which is long_base + full_begin[l] + l with the
+    // base below, and the area ends at pa.  (On a shard n_short follows the degrees over all edges and the pieces the
+    // shard's own: a row of the long area may have no full piece there.)
     pl.pa = 3 * (int64_t)T + ((int64_t)nfull_total - full_before_short) + ((int64_t)T - n_short);
     if (pl.np >= ((int64_t)1 << 31) / kSgPlanSlots) {
         pl.status = SgPlanStatus::too_many_slots;
@@ -120,7 +122,7 @@ inline int sg_radix_bits(int64_t n)
 
 inline int64_t sg_layout_bytes(int64_t np, int32_t T) { return np * kSgPlanSlots * 12 + np * 8 + (int64_t)T * 12; }
 
-// what one sweep + finalize moves in this layout (see sg_create_impl): columns and weights (or their dictionary index) of
+// what one sweep + finalize really moves in this layout (padding included): columns and weights (or their dictionary index) of
 // every slot, piece descriptors, one partial written and read back per segment, x read and x' written once per live row
 inline int64_t sg_device_sweep_bytes(int64_t np, int64_t npart, int32_t T, bool use16, bool dictionary)
 {

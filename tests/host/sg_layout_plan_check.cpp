@@ -1,7 +1,8 @@
 // sg_layout_plan_check.cpp -- the host arithmetic of the stochastic graph's device build (csrc/sg_layout_plan.h) against
 // a walk of the layout.  walk() lays a list of in-degrees out one row after the other, the way DESIGN.md section 4 and
 // sg_create_impl state it: a running count of full pieces, one segment counter per remainder class, the classes from 6
-// down to 0 with a new piece whenever a class's counter fills one, a running pa behind the three slots of every row.  The
+// down to 0 with a new piece whenever a class's counter fills one, a running pa behind the three slots of every row (for
+// a shard's handle too: the area from the degrees over all shards, the pieces from the shard's own).  The
 // header's closed forms must give the same numbers from the eight totals alone, and every graph's figures are also
 // literals worked out by hand.  The refusals and the small rules stand against literals.  Stand-alone, so that it runs
 // under a host sanitizer:
@@ -31,6 +32,7 @@ static long cases = 0;
 
 struct Row {
     int degree = 0, nfull = 0, rem = 0, cls = -1;
+    int area_degree = 0;      // what decides the row's area: the degree itself, on a shard the degree over all shards
     int64_t full_begin = 0;   // first full piece
     int64_t rem_part = -1;    // the segment of the remainder, -1 without one
     int64_t rem_slot0 = -1;   // absolute slot of remainder element 0
@@ -45,16 +47,19 @@ struct Walk {
     int64_t piece_begin[7], part_begin[7];
 };
 
-// degrees: the in-degree of every vertex, ascending vertex; a vertex without inbound edges is not a row
-static Walk walk(const std::vector<int> &degrees)
+// degrees: the in-degree of every vertex, ascending vertex; a vertex without inbound edges is not a row.  A shard's
+// handle: `degrees` count the shard's own edges and all_degrees the edges of all shards - a vertex is a row, and a row
+// of the long area, by all_degrees, while its pieces follow degrees (which may be 0)
+static Walk walk(const std::vector<int> &degrees, const std::vector<int> &all_degrees)
 {
     Walk w;
     // live order: rows with at most two full pieces (of 256 slots) first, ascending vertex inside each kind
     for (int pass = 0; pass < 2; ++pass) {
-        for (const int d : degrees)
-            if (d > 0 && (d / 256 <= 2) == (pass == 0)) {
+        for (size_t v = 0; v < degrees.size(); ++v)
+            if (all_degrees[v] > 0 && (all_degrees[v] / 256 <= 2) == (pass == 0)) {
                 Row r;
-                r.degree = d;
+                r.degree = degrees[v];
+                r.area_degree = all_degrees[v];
                 w.rows.push_back(r);
             }
         if (pass == 0) w.n_short = (int32_t)w.rows.size();
@@ -111,9 +116,9 @@ struct Expect {
 };
 
 // the header's plan from the walk's totals, against the walk row by row and against the literals
-static SgLayoutPlan check_graph(const std::vector<int> &degrees, const Expect &x)
+static SgLayoutPlan check_graph(const std::vector<int> &degrees, const Expect &x, const std::vector<int> *all_degrees = nullptr)
 {
-    const Walk w = walk(degrees);
+    const Walk w = walk(degrees, all_degrees ? *all_degrees : degrees);
     CHECK(w.T == x.T && w.n_short == x.n_short && w.nfull_total == x.nfull_total && w.wave_rows == x.wave_rows);
     CHECK(w.np == x.np && w.npart == x.npart && w.pa == x.pa);
     const SgLayoutPlan pl = sg_layout_plan(w.rows_of_class, (int32_t)w.nfull_total, (int32_t)w.full_before_short, w.T, w.n_short);
@@ -125,7 +130,7 @@ static SgLayoutPlan check_graph(const std::vector<int> &degrees, const Expect &x
     int32_t wave_rows = 0;
     for (int32_t l = 0; l < w.T; ++l) {
         const Row &r = w.rows[(size_t)l];
-        CHECK(sg_in_long_area(r.degree) == (l >= w.n_short));
+        CHECK(sg_in_long_area(r.area_degree) == (l >= w.n_short));
         if (r.rem > 0) CHECK(sg_remainder_class(r.rem) == r.cls);
         if (l >= w.n_short) CHECK(sg_long_begin(pl.long_base, (int32_t)r.full_begin, l) == r.long_begin);
         wave_rows += sg_wave_row(r.nfull) ? 1 : 0;
@@ -209,6 +214,26 @@ static void check_mixed_graphs()
     CHECK(pl.status == SgPlanStatus::ok && pl.np == 43 && pl.npart == 226);
 }
 
+// a shard's handle: the area from the degrees over all shards, the pieces from the shard's own
+static void check_sharded_totals()
+{
+    // all: 10, 800, 256, 3000, 513, 769 -> live order 10, 256, 513 | 800, 3000, 769 (as in the mixed graph above).
+    // This shard holds 4, 300, 0, 2600, 513, 100 of them: full pieces 0 0 2 | 1 10 0, classes 0 - 0 | 4 4 5; a row
+    // without an edge here (256) and long-area rows with one full piece or none (800, 769) keep their places.
+    const std::vector<int> all = {10, 800, 256, 3000, 513, 769}, own = {4, 300, 0, 2600, 513, 100};
+    // pieces: 13 full + class 5: 1, class 4: 1, class 0: 1 = 16; parts 13 + 2 + 4 + 64 = 83; pa = 18 + (1+1) + (10+1) + (0+1)
+    SgLayoutPlan pl = check_graph(own, {6, 3, 13, 16, 83, 32, 13, 1}, &all);
+    const int32_t piece[7] = {15, 15, 15, 15, 14, 13, 13}, part[7] = {19, 19, 19, 19, 15, 13, 13};
+    for (int c = 0; c < 7; ++c) CHECK(pl.piece_begin[c] == piece[c] && pl.part_begin[c] == part[c]);
+    CHECK(sg_long_begin(pl.long_base, 2, 3) == 18 && sg_long_begin(pl.long_base, 3, 4) == 20 && sg_long_begin(pl.long_base, 13, 5) == 31);
+    // a shard without a single edge of the graph: every row keeps its three slots, the long area one slot per row
+    const std::vector<int> nothing = {0, 0, 0, 0, 0, 0};
+    pl = check_graph(nothing, {6, 3, 0, 0, 0, 21, 15, 0}, &all);
+    CHECK(sg_long_begin(pl.long_base, 0, 3) == 18 && sg_long_begin(pl.long_base, 0, 5) == 20);
+    // the other way round does not occur (a shard's degree never exceeds the total), and the whole graph is its own shard
+    check_graph(all, {6, 3, 20, 24, 109, 38, 12, 1}, &all);
+}
+
 // ---- the refusals, from totals alone --------------------------------------------------------------------------------
 
 static void check_refusals()
@@ -274,6 +299,7 @@ int main()
     check_single_rows();
     check_full_class_pieces();
     check_mixed_graphs();
+    check_sharded_totals();
     check_refusals();
     check_small_rules();
     std::printf("%ld cases pass\n", cases);

@@ -118,6 +118,29 @@ def test_sg_sharded_in_the_library(pkg, oracle, devices, by_target):
     whole.close()
 
 
+@pytest.mark.parametrize("by_target", [False, True], ids=["all_reduce", "all_gather"])
+def test_sg_sharded_layout_graph(pkg, by_target):
+    """Three shards of sg_build_cases.layout_graph() - rows of the long area and whole-wave rows, whose shards hold only
+    a part of their edges - against the unsharded handle, with test_sg_sharded_in_the_library's fixed-sweep comparison."""
+    import sg_build_cases as cases
+    gr = cases.layout_graph()
+    src, dst, w = gr["source"], gr["target"], gr["weight"]
+    whole = pkg.SgGraph(src, dst, w)
+    g = pkg.SgSharded([0] * 3, src, dst, w, by_target=by_target)
+    for vertex in gr["requests"][1:3]:      # a whole-wave row, and a source-only hub
+        g.sweeps_async(vertex, 0.15, 25)
+        ids, probs, it, conv = g.fetch()
+        whole.sweeps_async(vertex, 0.15, 25)
+        wi, wp, wit, wconv = whole.fetch()
+        assert (it, conv) == (25, False) and np.array_equal(ids, wi)
+        if by_target:
+            assert np.array_equal(probs, wp)
+        else:
+            np.testing.assert_allclose(probs, wp, rtol=1e-9, atol=0)
+    g.close()
+    whole.close()
+
+
 def test_sg_sharded_cfg3_eight_logical_shards(pkg, oracle):
     """configs[4]'s literal form at configs[2]'s full size through the in-library driver: 8 logical shards, all-gather
     form, 100 sweeps - bit-identical to the unsharded handle, 1e-6 against the oracle."""

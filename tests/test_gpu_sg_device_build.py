@@ -207,6 +207,20 @@ def test_inputs_unchanged_repeatable_and_memory_returned(pkg, layout):
     assert L.device_bytes_in_use() == before
 
 
+def test_host_build_repeatable_and_memory_returned(pkg, layout):
+    """The same of locrec_sg_create: two builds of one edge list are one layout, and closing them returns every byte."""
+    from locations_recommender_amd import _lib as L
+    before = L.device_bytes_in_use()
+    first = pkg.SgGraph(layout["source"], layout["target"], layout["weight"])
+    second = pkg.SgGraph(layout["source"], layout["target"], layout["weight"])
+    assert facts(first) == facts(second)
+    for v in layout["requests"]:
+        same_result(first.recommend(v, ALPHA, 0.0, 7), second.recommend(v, ALPHA, 0.0, 7), v)
+    first.close()
+    second.close()
+    assert L.device_bytes_in_use() == before
+
+
 def test_wrong_device_or_host_memory_is_refused(pkg):
     s = torch.tensor([1, 2], dtype=torch.int64)
     w = torch.tensor([1.0, 1.0], dtype=torch.float64)

@@ -1,7 +1,9 @@
 """Every kernel launch of the offline device steps is checked where it is made: the seven units, and the headers they
 share, launch through csrc/offline.h's LOCREC_LAUNCH (launch, then hipGetLastError with the call site's file and line) and
 nowhere write hipLaunchKernelGGL themselves.  knn_host_build.h is exempt: a fragment of the scans' translation unit, it
-checks its one launch by hand."""
+checks its one launch by hand.  So is sg_build_shared.h, which the device build (sg_create_device.hip, one of the units)
+calls for the weight dictionary: sg.hip includes it in front of its kernels, where offline.h - which defines kernels -
+cannot come, so its one launch is LOCREC_LAUNCH written out."""
 import os
 import re
 
