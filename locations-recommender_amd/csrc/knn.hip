@@ -51,6 +51,7 @@
 #include <unordered_map>
 
 #include "knn_agg_plan.h"
+#include "knn_anyk.h"
 #include "knn_ht_order.h"
 #include "knn_index.h"
 
@@ -59,7 +60,6 @@ namespace {
 using namespace locrec;
 
 constexpr uint32_t kEmpty = 0xFFFFFFFFu;
-constexpr int kMergeCap = 8192;      // entries one merge block sorts in LDS
 constexpr int kAggCap = 4096;        // rating rows one aggregation block sorts in LDS (28 B each)
 constexpr int kDirectMaxBytes = cfg::kDirectMaxBytes;
 constexpr int kLdsSoftLimit = 64 * 1024;
@@ -229,6 +229,62 @@ int32_t build_family_device(locrec_knn_index *ix, const HostFamily &h, DevFamily
     return LOCREC_OK;
 }
 
+// The tail of the head / tail image: postings of the tail places, the rows' hit totals and sums of squares.  nh: head
+// elements of every row; pe / ce: elements of the two head images (build_ht).
+int32_t build_ht_tail(locrec_knn_index *ix, const HostFamily &hq, const HostFamily &hc, const std::vector<int32_t> &nh, int32_t H,
+                      int qt, int64_t pe, int64_t ce)
+{
+    const int64_t n = ix->n;
+    const int32_t nslices = ix->nslices;
+    hipStream_t s = ix->stream;
+    locrec::HtIndex &ht = ix->ht;
+    // postings of the tail places: rows ascending inside a place
+    const int64_t nt = std::max<int64_t>(0, (int64_t)hq.dim - H);
+    std::vector<int64_t> pptr((size_t)nt + 1, 0);
+    for (int64_t r = 0; r < n; ++r)
+        for (int64_t e = hq.ptr[r] + nh[r]; e < hq.ptr[r + 1]; ++e) ++pptr[hq.idx[e] - H + 1];
+    for (int64_t t = 0; t < nt; ++t) pptr[t + 1] += pptr[t];
+    std::vector<uint32_t> post((size_t)pptr[nt]);
+    {
+        std::vector<int64_t> cur(pptr.begin(), pptr.end() - 1);
+        for (int64_t r = 0; r < n; ++r)
+            for (int64_t e = hq.ptr[r] + nh[r]; e < hq.ptr[r + 1]; ++e)
+                post[(size_t)cur[hq.idx[e] - H]++] = ((uint32_t)r << 8) | (uint32_t)hq.val[e];
+    }
+    std::vector<int64_t> th((size_t)n, 0);
+    ht.tail_hits_ps.assign((size_t)n + 1, 0);
+    for (int64_t r = 0; r < n; ++r) {
+        int64_t t = 0;
+        for (int64_t e = hq.ptr[r] + nh[r]; e < hq.ptr[r + 1]; ++e) t += pptr[hq.idx[e] - H + 1] - pptr[hq.idx[e] - H];
+        th[r] = t;
+        ht.tail_hits_ps[r + 1] = ht.tail_hits_ps[r] + t;
+    }
+    {
+        // sums of squares of both vectors of a row (exact integers < 65536 under PACK16): the scan derives
+        // the f32 inverse norms of its bound and - for a survivor - the exact fp64 norms from them
+        std::vector<uint32_t> ss((size_t)nslices * 64, 0u);  // whole slices: the scan loads them unconditionally
+        for (int64_t r = 0; r < n; ++r) {
+            double sp = 0, sc = 0;
+            for (int64_t e = hq.ptr[r]; e < hq.ptr[r + 1]; ++e) sp += hq.val[e] * hq.val[e];
+            for (int64_t e = hc.ptr[r]; e < hc.ptr[r + 1]; ++e) sc += hc.val[e] * hc.val[e];
+            ss[r] = (uint32_t)sp | ((uint32_t)sc << 16);
+        }
+        LOCREC_TRY(ht.ss.upload(ss, s));
+        LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    }
+    LOCREC_TRY(ht.post_ptr.upload(pptr, s));
+    LOCREC_TRY(ht.post.upload(post, s));
+    LOCREC_TRY(ht.tail_hits.upload(th, s));
+    LOCREC_HIP_TRY(hipStreamSynchronize(s));
+    // bytes one query-vs-all pass reads in this layout: head and category elements, every posting
+    // once per query that holds its place is NOT per-candidate work - count the stored tail once
+    ht.scan_bytes = (pe + ce) * 4 + (int64_t)post.size() * 4 + (int64_t)nslices * 24 + n * 8;
+    ht.h = H;
+    ht.qt = qt;
+    ht.ready = true;
+    return LOCREC_OK;
+}
+
 // Head / tail image (knn_ht.h).  hq: place family with the dimensions renumbered by popularity, rows
 // in row order, indices ascending; hc: category family.  H: head dimensions; qt: query tile the
 // element format is built for (panel row = 2 * qt bytes).
@@ -320,51 +376,7 @@ int32_t build_ht(locrec_knn_index *ix, const HostFamily &hq, const HostFamily &h
         LOCREC_TRY(ht.cold.alloc(sizeof(HtCold)));
         LOCREC_HIP_TRY(hipStreamSynchronize(s));
     }
-    // postings of the tail places: rows ascending inside a place
-    const int64_t nt = std::max<int64_t>(0, (int64_t)hq.dim - H);
-    std::vector<int64_t> pptr((size_t)nt + 1, 0);
-    for (int64_t r = 0; r < n; ++r)
-        for (int64_t e = hq.ptr[r] + nh[r]; e < hq.ptr[r + 1]; ++e) ++pptr[hq.idx[e] - H + 1];
-    for (int64_t t = 0; t < nt; ++t) pptr[t + 1] += pptr[t];
-    std::vector<uint32_t> post((size_t)pptr[nt]);
-    {
-        std::vector<int64_t> cur(pptr.begin(), pptr.end() - 1);
-        for (int64_t r = 0; r < n; ++r)
-            for (int64_t e = hq.ptr[r] + nh[r]; e < hq.ptr[r + 1]; ++e)
-                post[(size_t)cur[hq.idx[e] - H]++] = ((uint32_t)r << 8) | (uint32_t)hq.val[e];
-    }
-    std::vector<int64_t> th((size_t)n, 0);
-    ht.tail_hits_ps.assign((size_t)n + 1, 0);
-    for (int64_t r = 0; r < n; ++r) {
-        int64_t t = 0;
-        for (int64_t e = hq.ptr[r] + nh[r]; e < hq.ptr[r + 1]; ++e) t += pptr[hq.idx[e] - H + 1] - pptr[hq.idx[e] - H];
-        th[r] = t;
-        ht.tail_hits_ps[r + 1] = ht.tail_hits_ps[r] + t;
-    }
-    {
-        // sums of squares of both vectors of a row (exact integers < 65536 under PACK16): the scan derives
-        // the f32 inverse norms of its bound and - for a survivor - the exact fp64 norms from them
-        std::vector<uint32_t> ss((size_t)nslices * 64, 0u);  // whole slices: the scan loads them unconditionally
-        for (int64_t r = 0; r < n; ++r) {
-            double sp = 0, sc = 0;
-            for (int64_t e = hq.ptr[r]; e < hq.ptr[r + 1]; ++e) sp += hq.val[e] * hq.val[e];
-            for (int64_t e = hc.ptr[r]; e < hc.ptr[r + 1]; ++e) sc += hc.val[e] * hc.val[e];
-            ss[r] = (uint32_t)sp | ((uint32_t)sc << 16);
-        }
-        LOCREC_TRY(ht.ss.upload(ss, s));
-        LOCREC_HIP_TRY(hipStreamSynchronize(s));
-    }
-    LOCREC_TRY(ht.post_ptr.upload(pptr, s));
-    LOCREC_TRY(ht.post.upload(post, s));
-    LOCREC_TRY(ht.tail_hits.upload(th, s));
-    LOCREC_HIP_TRY(hipStreamSynchronize(s));
-    // bytes one query-vs-all pass reads in this layout: head and category elements, every posting
-    // once per query that holds its place is NOT per-candidate work - count the stored tail once
-    ht.scan_bytes = (pe + ce) * 4 + (int64_t)post.size() * 4 + (int64_t)nslices * 24 + n * 8;
-    ht.h = H;
-    ht.qt = qt;
-    ht.ready = true;
-    return LOCREC_OK;
+    return build_ht_tail(ix, hq, hc, nh, H, qt, pe, ce);
 }
 
 // KnnRecommender.scala:17-20
@@ -708,9 +720,7 @@ int32_t launch_scan_ht(locrec_knn_index *ix, const Plan &pl, const ScanParams &P
     LOCREC_HIP_TRY(hipMemcpyAsync(ht.cold.p, &c, sizeof c, hipMemcpyHostToDevice, s));
     auto kern = seed_pass ? knn_scan_ht<16, 8, true>
                           : pl.waves == 6 ? knn_scan_ht<16, 6> : pl.waves == 12 ? knn_scan_ht<16, 12> : knn_scan_ht<16, 8>;
-    if (lds > 64 * 1024)
-        LOCREC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    LOCREC_TRY(knn_raise_lds_limit(kern, lds));
 #define LOCREC_HT_ARGS                                                                                               \
     reinterpret_cast<const u32x4 *>(ht.p_sell.p), reinterpret_cast<const u32x4 *>(ht.c_sell.p),                         \
         reinterpret_cast<const HtSliceDesc *>(ht.desc.p), ht.ss.p, ht.rid.p, ht.hits.p, ht.off.p, ht.tile_base.p,       \
@@ -728,9 +738,7 @@ template <int MODE, int QT, int W>
 int32_t launch_scan_t(KernelProfile &prof, const ScanParams &P, dim3 grid, size_t lds, hipStream_t s)
 {
     auto kern = knn_scan<MODE, QT, W>;
-    if (lds > 64 * 1024)
-        LOCREC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    LOCREC_TRY(knn_raise_lds_limit(kern, lds));
     LOCREC_LAUNCH_PROFILED(prof, kern, grid, dim3(W * 64), lds, s, P);
     return LOCREC_OK;
 }
@@ -909,21 +917,13 @@ int32_t enqueue_dense_impl(locrec_knn_index *ix, int32_t qrow, double pw, double
     int blocks = std::max(1, std::min(256, (ix->cand_slice1 - ix->cand_slice0 + kScan1Waves - 1) / kScan1Waves));
     if (const char *e = debug_env("LOCREC_DEBUG_SCAN1_BLOCKS")) blocks = std::max(1, std::atoi(e));
     if (direct8) {
-        if (!ix->direct8_attr) {
-            LOCREC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(knn_scan1_direct8),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, kDirect8MaxBytes));
-            ix->direct8_attr = true;
-        }
+        LOCREC_TRY(knn_raise_lds_limit(knn_scan1_direct8, kDirect8MaxBytes, &ix->direct8_attr));
         LOCREC_LAUNCH_PROFILED(ix->prof, knn_scan1_direct8, dim3(blocks), dim3(kScan1Waves * 64), d8_bytes, s, P);
     } else if (mode) {
-        if (cur > 64 * 1024)
-            LOCREC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(knn_scan1<1>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)cur));
+        LOCREC_TRY(knn_raise_lds_limit(knn_scan1<1>, cur));
         LOCREC_LAUNCH_PROFILED(ix->prof, knn_scan1<1>, dim3(blocks), dim3(kScan1Waves * 64), cur, s, P);
     } else {
-        if (cur > 64 * 1024)
-            LOCREC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(knn_scan1<0>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)cur));
+        LOCREC_TRY(knn_raise_lds_limit(knn_scan1<0>, cur));
         LOCREC_LAUNCH_PROFILED(ix->prof, knn_scan1<0>, dim3(blocks), dim3(kScan1Waves * 64), cur, s, P);
     }
     if (!ix->wide_rows.empty()) {
@@ -968,11 +968,7 @@ int32_t enqueue_single(locrec_knn_index *ix, int32_t qrow, double pw, double cw,
                        ix->rid.p, row0, row1, ix->sel1.p, ix->list1_s.p, ix->list1_r.p, ix->sel1.p + 3, (int64_t)0);
     ix->hist1_dirty = nohist;  // knn_select1 cleans up behind itself
     const size_t flds = (size_t)kCollectCap * 12;
-    if (!ix->final1_attr) {
-        LOCREC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(knn_final1),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)flds));
-        ix->final1_attr = true;
-    }
+    LOCREC_TRY(knn_raise_lds_limit(knn_final1, flds, &ix->final1_attr));
     hipLaunchKernelGGL(knn_final1, dim3(1), dim3(256), flds, s, ix->list1_s.p, ix->list1_r.p, ix->sel1.p + 3, K,
                        ix->ids_by_rank.p, ix->row_of_rid.p, ix->out_ids.p, ix->out_sims.p, ix->out_rows.p,
                        ix->out_cnt.p, ix->sel1.p + 4, host, static_cast<const int64_t *>(nullptr));
@@ -991,329 +987,13 @@ int32_t enqueue_single(locrec_knn_index *ix, int32_t qrow, double pw, double cw,
     return LOCREC_OK;
 }
 
-// Enqueue scan + merge for nq queries given as device rows (qrows_dev) or a row range.
-// Candidate slices from which ONE request takes the stream path (scan -> select -> collect -> sort).  It used to be
-// 64; a region-sized index (the reference builds one recommender per region: ~3 k persons = ~50 slices) then fell
-// to the tiled path: 0.092 ms per query at 2,000 persons against ~0.05 ms on the stream path.
-constexpr int kSingleMinSlices = 4;
+}  // namespace
 
-int32_t enqueue_topk(locrec_knn_index *ix, const int32_t *qrows_dev, int32_t qrow0, int64_t nq,
-                     int max_nnz_p, int max_nnz_c, double pw, double cw, int64_t k, bool mark_absent = false)
-{
-    hipStream_t s = ix->stream;
-    const int K = (int)k;
-    ix->single_pending = false;
-    ix->single_direct = false;
-    ix->last_scan_fast = false;
-    ix->have_agg = false;  // the neighbour lists a resident batched aggregation was built from are overwritten
-    ix->have_lkb = false;
-    const int range_slices = ix->cand_slice1 - ix->cand_slice0;
-    if (nq == 1 && !ix->no_single && range_slices >= kSingleMinSlices && !mark_absent) {
-        int32_t qrow = qrow0;
-        if (qrows_dev) LOCREC_HIP_TRY(hipMemcpy(&qrow, qrows_dev, sizeof(int32_t), hipMemcpyDeviceToHost));
-        bool used = false;
-        LOCREC_TRY(enqueue_single(ix, qrow, pw, cw, k, &used));
-        if (used) return LOCREC_OK;
-    }
-    Plan pl;
-    // head / tail form (knn_ht.h) when the index has it and this batch fits its pre-pass: every tile's
-    // (query, tail place) pairs fit kHtMaxEntries and its hits a 32-bit offset
-    bool use_ht = false;
-    int64_t ht_total = 0;
-    if (ix->ht.ready && !ix->no_ht && (!qrows_dev || (int64_t)ix->qrows_host.size() == nq)) {
-        const int qt = ix->ht.qt;
-        bool ok = true;
-        for (int64_t t0 = 0; ok && t0 < nq; t0 += qt) {
-            int64_t ent = 0, hits = 0;
-            for (int64_t i = t0; i < std::min(nq, t0 + qt); ++i) {
-                const int32_t r = qrows_dev ? ix->qrows_host[(size_t)i] : qrow0 + (int32_t)i;
-                ent += ix->ht.tail_nnz[(size_t)r];
-                hits += ix->ht.tail_hits_ps[(size_t)r + 1] - ix->ht.tail_hits_ps[(size_t)r];
-            }
-            ok = ent <= kHtMaxEntries && hits < ((int64_t)1 << 32);
-            ht_total += hits;
-        }
-        use_ht = ok && ix->ht.desc.p && make_plan_ht(ix, K, pl);
-    }
-    // a WIDE row as the query (per-row format fallback): its values do not fit the packed panels, so it is served like a
-    // query that is too long for any tile - the dense CSR scan + sort into its slot - while the rest runs tiled
-    bool wide_query = false;
-    if (!ix->wide_rows.empty()) {
-        if (qrows_dev && (int64_t)ix->qrows_host.size() != nq) {
-            ix->qrows_host.resize((size_t)nq);
-            LOCREC_HIP_TRY(hipMemcpy(ix->qrows_host.data(), qrows_dev, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost));
-        }
-        for (int64_t i = 0; i < nq && !wide_query; ++i)
-            wide_query = ix->row_is_wide(qrows_dev ? ix->qrows_host[(size_t)i] : qrow0 + (int32_t)i);
-    }
-    if (wide_query || (!use_ht && !make_plan(ix, nq, max_nnz_p, max_nnz_c, K, pl))) {
-        // Some query of the batch is too long for an LDS tile even on its own (rank()-with-ties can emit rows of
-        // any length).  Those queries are served by the dense-query scan + sort path (knn_scan_dense,
-        // knn_large.hip) into their slots of the result arrays; the rest of the batch runs tiled with a
-        // stand-in row in their places.
-        std::vector<int32_t> rows((size_t)nq);
-        if (qrows_dev) {
-            if ((int64_t)ix->qrows_host.size() == nq) rows = ix->qrows_host;
-            else LOCREC_HIP_TRY(hipMemcpy(rows.data(), qrows_dev, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost));
-        } else {
-            for (int64_t i = 0; i < nq; ++i) rows[(size_t)i] = qrow0 + (int32_t)i;
-        }
-        std::vector<int64_t> longq;
-        int32_t stand_in = -1;
-        int mp = 1, mc = 1;
-        for (int64_t i = 0; i < nq; ++i) {
-            const int32_t r = rows[(size_t)i];
-            Plan one;
-            if (ix->row_is_wide(r) || !make_plan(ix, 1, ix->fp.nnz[r], ix->fc.nnz[r], K, one)) {
-                longq.push_back(i);
-            } else {
-                if (stand_in < 0) stand_in = r;
-                mp = std::max(mp, ix->fp.nnz[r]);
-                mc = std::max(mc, ix->fc.nnz[r]);
-            }
-        }
-        if (longq.empty())
-            return fail(LOCREC_E_INVALID_ARG, "query tile does not fit in LDS (k=%d, nnz=%d/%d)", K, max_nnz_p, max_nnz_c);
-        if (stand_in >= 0 && nq > 1) {
-            for (int64_t i : longq) rows[(size_t)i] = stand_in;
-            LOCREC_TRY(ix->qrows_patch.reserve((size_t)nq));
-            LOCREC_HIP_TRY(hipMemcpyAsync(ix->qrows_patch.p, rows.data(), (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, s));
-            LOCREC_HIP_TRY(hipStreamSynchronize(s));  // (rows is a local)
-            std::vector<int32_t> saved;
-            saved.swap(ix->qrows_host);
-            ix->qrows_host = rows;
-            const int32_t st = enqueue_topk(ix, ix->qrows_patch.p, 0, nq, mp, mc, pw, cw, k, mark_absent);
-            ix->qrows_host.swap(saved);
-            LOCREC_TRY(st);
-        } else {
-            LOCREC_TRY(ix->out_ids.reserve((size_t)nq * K));
-            LOCREC_TRY(ix->out_sims.reserve((size_t)nq * K));
-            LOCREC_TRY(ix->out_rows.reserve((size_t)nq * K));
-            LOCREC_TRY(ix->out_cnt.reserve((size_t)nq));
-            ix->last_scan_fast = false;
-        }
-        const std::vector<int32_t> *orig = qrows_dev && (int64_t)ix->qrows_host.size() == nq ? &ix->qrows_host : nullptr;
-        // The special queries, 16 at a time: one pass of every candidate's plain CSR row against dense tables of the
-        // tile's queries (knn_large.hip: exact for every row in every format) gives S[row][16]; each column then takes
-        // the single request's selection (histogram -> deciding bin -> collect -> sort) straight into its slot.  One
-        // by one through the dense scan + full radix sort this was ~1 ms per query - 16 wide queries doubled a cfg2 step.
-        const bool whole_range = ix->cand_slice0 == 0 && ix->cand_slice1 == ix->nslices;
-        std::vector<int32_t> srow(longq.size());
-        for (size_t j = 0; j < longq.size(); ++j) {
-            const int64_t i = longq[j];
-            int32_t r = orig ? (*orig)[(size_t)i] : qrow0 + (int32_t)i;
-            if (qrows_dev && !orig) LOCREC_HIP_TRY(hipMemcpy(&r, qrows_dev + i, sizeof(int32_t), hipMemcpyDeviceToHost));
-            srow[j] = r;
-        }
-        if (whole_range && K <= kCollectCap / 2 && !ix->no_tile_special) {
-            // per-column workspaces of a tile; knn_select1 leaves histograms and counters clean behind itself, the first
-            // use cleans them here
-            if (!ix->tile_hist.p) {
-                LOCREC_TRY(ix->tile_hist.alloc((size_t)16 * kHistBins));
-                LOCREC_TRY(ix->tile_sel.alloc(16 * 8));
-                LOCREC_TRY(ix->tile_list_s.alloc((size_t)16 * kCollectCap));
-                LOCREC_TRY(ix->tile_list_r.alloc((size_t)16 * kCollectCap));
-                LOCREC_TRY(ix->tile_slots.alloc(16));
-                LOCREC_TRY(ix->tile_ovf.alloc(16));
-                LOCREC_HIP_TRY(hipMemsetAsync(ix->tile_hist.p, 0, ix->tile_hist.bytes(), s));
-                LOCREC_HIP_TRY(hipMemsetAsync(ix->tile_sel.p, 0, ix->tile_sel.bytes(), s));
-            }
-            const size_t flds = (size_t)kCollectCap * 12;
-            if (!ix->final1_attr) {
-                LOCREC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(knn_final1),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)flds));
-                ix->final1_attr = true;
-            }
-            const int32_t nrows = (int32_t)ix->n;
-            for (size_t j0 = 0; j0 < longq.size(); j0 += 16) {
-                const int nt = (int)std::min<size_t>(16, longq.size() - j0);
-                LOCREC_TRY(knn_large_scan_tile(ix, srow.data() + j0, nt, pw, cw));
-                // all columns of the tile at once: histograms, deciding bins, collect lists, sorted lists into the slots
-                // (four launches per tile; one set per column was 64 launches and 0.6 ms of a cfg2 step with 16 wide queries)
-                int64_t slots[16] = {0};
-                for (int t = 0; t < nt; ++t) slots[t] = longq[j0 + (size_t)t];
-                LOCREC_HIP_TRY(hipMemcpyAsync(ix->tile_slots.p, slots, (size_t)nt * sizeof(int64_t), hipMemcpyHostToDevice, s));
-                const double *cols = nullptr;
-                LOCREC_TRY(knn_large_tile_hists(ix, nt, ix->tile_hist.p, &cols));
-                hipLaunchKernelGGL(knn_select1, dim3((unsigned)nt), dim3(1024), 0, s, ix->tile_hist.p, K, ix->tile_sel.p);
-                hipLaunchKernelGGL(knn_collect1, dim3((unsigned)std::max(1, (nrows + 255) / 256), (unsigned)nt), dim3(256), 0, s, cols,
-                                   ix->rid.p, 0, nrows, ix->tile_sel.p, ix->tile_list_s.p, ix->tile_list_r.p, ix->tile_sel.p + 3,
-                                   (int64_t)nrows);
-                hipLaunchKernelGGL(knn_final1, dim3((unsigned)nt), dim3(256), flds, s, ix->tile_list_s.p, ix->tile_list_r.p,
-                                   ix->tile_sel.p + 3, K, ix->ids_by_rank.p, ix->row_of_rid.p, ix->out_ids.p, ix->out_sims.p,
-                                   ix->out_rows.p, ix->out_cnt.p, ix->tile_ovf.p, static_cast<unsigned char *>(nullptr),
-                                   ix->tile_slots.p);
-                LOCREC_HIP_TRY(hipGetLastError());
-                // a deciding bin with more entries than the collect list holds (a pathological tie mass): that slot
-                // takes the full sort instead
-                int32_t ovf[16] = {0};
-                LOCREC_HIP_TRY(hipMemcpyAsync(ovf, ix->tile_ovf.p, (size_t)nt * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-                LOCREC_HIP_TRY(hipStreamSynchronize(s));
-                for (int t = 0; t < nt; ++t)
-                    if (ovf[t]) LOCREC_TRY(knn_large_topk_device(ix, srow[j0 + (size_t)t], pw, cw, k, longq[j0 + (size_t)t]));
-            }
-        } else {
-            for (size_t j = 0; j < longq.size(); ++j) LOCREC_TRY(knn_large_topk_device(ix, srow[j], pw, cw, k, longq[j]));
-        }
-        ix->single_pending = false;
-        ix->last_nq = nq;
-        ix->last_k = k;
-        ix->have_result = true;
-        return LOCREC_OK;
-    }
-    const int ntiles = (int)((nq + pl.qt - 1) / pl.qt);
-    // enough blocks to fill the chip; when that needs more chunks than one merge block can sort
-    // (a single request), the merge runs in two levels
-    const int max_chunks = std::max(1, kMergeCap / K);
-    // target number of blocks.  The row scan was tuned at 2048 (4 rounds of 512 resident blocks).  The head /
-    // tail scan does better with ONE chunk per tile at the bench batch (1024 blocks = exactly two rounds):
-    // a chunk more per tile means another K*ln(N/K) list insertions and another list to merge
-    // (cfg2: 23.2 -> 19.0 ms per 16,384-query batch).
-    int want = std::max(1, ((use_ht ? 1024 : 2048) + ntiles - 1) / ntiles);
-    if (ix->env_blocks > 0) want = std::max(1, (ix->env_blocks + ntiles - 1) / ntiles);  // tuning
-    int nchunks = std::min(std::min(want, max_chunks * max_chunks), std::max(1, range_slices / 8));
-    int spc = (range_slices + nchunks - 1) / nchunks;
-    spc = std::max(pl.waves, (spc + pl.waves - 1) / pl.waves * pl.waves);
-    nchunks = std::max(1, (range_slices + spc - 1) / spc);
-    const int ngroups = nchunks > max_chunks ? (nchunks + max_chunks - 1) / max_chunks : 0;
+#include "knn_topk_host.h"  // enqueue_topk: one stream, special queries, the tiled scan - named phases over knn_topk_plan.h
 
-    LOCREC_TRY(ix->part_s.reserve((size_t)nq * nchunks * K));
-    LOCREC_TRY(ix->part_rid.reserve((size_t)nq * nchunks * K));
-    LOCREC_TRY(ix->part_cnt.reserve((size_t)nq * nchunks));
-    if (ngroups) {
-        LOCREC_TRY(ix->part2_s.reserve((size_t)nq * ngroups * K));
-        LOCREC_TRY(ix->part2_rid.reserve((size_t)nq * ngroups * K));
-        LOCREC_TRY(ix->part2_cnt.reserve((size_t)nq * ngroups));
-    }
-    LOCREC_TRY(ix->out_ids.reserve((size_t)nq * K));
-    LOCREC_TRY(ix->out_sims.reserve((size_t)nq * K));
-    LOCREC_TRY(ix->out_rows.reserve((size_t)nq * K));
-    LOCREC_TRY(ix->out_cnt.reserve((size_t)nq));
+namespace {
 
-    ScanParams P{};
-    P.fp = pl.fp;
-    P.fc = pl.fc;
-    P.rid = ix->rid.p;
-    P.qrows = qrows_dev;
-    P.qrow0 = qrow0;
-    P.nq = (int32_t)nq;
-    P.nrows = (int32_t)ix->n;
-    P.slice0 = ix->cand_slice0;
-    P.nslices = ix->cand_slice1;
-    P.slices_per_chunk = spc;
-    P.nchunks = nchunks;
-    P.K = K;
-    P.S = pl.S;
-    P.pw = pw;
-    P.cw = cw;
-    P.part_s = ix->part_s.p;
-    P.part_rid = ix->part_rid.p;
-    P.part_cnt = ix->part_cnt.p;
-    P.off_cand_s = pl.off_cand_s;
-    P.off_cand_rid = pl.off_cand_rid;
-    P.off_misc = pl.off_misc;
-    P.off_queue = pl.off_queue;
-    if (!ix->scan_overflow.p) {
-        LOCREC_TRY(ix->scan_overflow.alloc(2));  // [0] this launch, [1] cumulative
-        LOCREC_HIP_TRY(hipMemsetAsync(ix->scan_overflow.p, 0, 2 * sizeof(int32_t), s));
-    }
-    LOCREC_HIP_TRY(hipMemsetAsync(ix->scan_overflow.p, 0, sizeof(int32_t), s));
-    P.overflow = ix->scan_overflow.p;
-    P.fast = (pl.mode != 0 && !ix->no_fast) ? 1 : 0;
-    P.flush_mask = kFlushEvery - 1;
-    P.enter_threads = kEnterFastThreads;
-    if (ix->env_flush > 0) P.flush_mask = ix->env_flush - 1;      // tuning
-    if (ix->env_enter >= 0) P.enter_threads = ix->env_enter;
-    ix->last_scan_fast = P.fast != 0;
-    P.lds_bytes = (int32_t)pl.lds;
-    P.poison = (debug_env("LOCREC_DEBUG_POISON") ? 1 : 0) | (debug_env("LOCREC_DEBUG_NOFILTER") ? 2 : 0) |
-               (debug_env("LOCREC_DEBUG_NOEPILOGUE") ? 4 : 0);
-    if (P.poison) {
-        (void)hipMemsetAsync(ix->part_s.p, 0xA5, ix->part_s.bytes(), s);
-        (void)hipMemsetAsync(ix->part_rid.p, 0xA5, ix->part_rid.bytes(), s);
-        (void)hipMemsetAsync(ix->part_cnt.p, 0xA5, ix->part_cnt.bytes(), s);
-    }
-
-    if (use_ht) {
-        LOCREC_TRY(enqueue_ht_prepass(ix, qrows_dev, qrow0, nq, pl.qt, ht_total));
-        P.ht.hits = ix->ht.hits.p;
-        P.ht.off = ix->ht.off.p;
-        P.ht.tile_base = ix->ht.tile_base.p;
-        P.ht.off_stride = ix->cand_slice1 - ix->cand_slice0 + 1;
-        P.ht.off_tail = pl.off_tail;
-        P.ht.h = ix->ht.h;
-        P.ht.c_rows = ix->fc.dim;
-    }
-    const bool dedicated = use_ht && !ix->ht.v1 && pl.qt == 16 && ix->ht.h <= cfg::kHtHead;  // (its plane stride is a constant)
-    // threshold seeding (knn_ht.h, SEED): worth a launch of its own when the scan is long - ~256 sampled slices
-    // per tile cost 1 - 2 % of a cfg2 scan and remove its cold start
-    const bool seeded = dedicated && pl.waves == 8 && range_slices >= ix->seed_min_slices && !ix->no_seed;
-    if (seeded)
-        LOCREC_TRY(launch_scan_ht(ix, pl, P, dim3(1u, (unsigned)ntiles), s, true, false,
-                                  std::max(1, range_slices / ix->seed_sample_slices)));
-    if (dedicated)
-        LOCREC_TRY(launch_scan_ht(ix, pl, P, dim3((unsigned)nchunks, (unsigned)ntiles), s, false, seeded));
-    else
-        LOCREC_TRY(launch_scan(ix->prof, pl, P, dim3((unsigned)nchunks, (unsigned)ntiles), s));
-    ix->last_plan_kernel = !use_ht ? 1 : dedicated ? 2 : 3;
-    ix->last_plan_mode = pl.mode;
-    ix->last_plan_qt = pl.qt;
-    ix->last_plan_waves = pl.waves;
-    const double *fs = ix->part_s.p;
-    const uint32_t *fr = ix->part_rid.p;
-    const int32_t *fc = ix->part_cnt.p;
-    int flists = nchunks;
-    if (ngroups) {
-        const int M1 = pow2ceil(std::max(2, max_chunks * K));
-        const size_t l1 = (size_t)M1 * 12;
-        if (l1 > 64 * 1024)
-            LOCREC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(knn_merge_partial),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)l1));
-        hipLaunchKernelGGL(knn_merge_partial, dim3((unsigned)ngroups, (unsigned)nq), dim3(256), l1, s, ix->part_s.p,
-                           ix->part_rid.p, ix->part_cnt.p, nchunks, K, max_chunks, M1, ix->part2_s.p,
-                           ix->part2_rid.p, ix->part2_cnt.p, ngroups);
-        fs = ix->part2_s.p;
-        fr = ix->part2_rid.p;
-        fc = ix->part2_cnt.p;
-        flists = ngroups;
-    }
-    const int M = pow2ceil(std::max(2, flists * K));
-    const size_t mlds = (size_t)M * 12;
-    if (mlds > 64 * 1024)
-        LOCREC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(knn_merge),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlds));
-    hipLaunchKernelGGL(knn_merge, dim3((unsigned)nq), dim3(256), mlds, s, fs, fr, fc, flists, K, M,
-                       ix->ids_by_rank.p, ix->row_of_rid.p, ix->out_ids.p, ix->out_sims.p, ix->out_rows.p,
-                       ix->out_cnt.p);
-    if (!ix->wide_rows.empty()) {
-        // the index's wide rows as candidates (they are padding in the packed images): merged into every K-list
-        const int32_t nw = (int32_t)ix->wide_rows.size();
-        int cap = 2;
-        while (cap < K + nw) cap <<= 1;
-        // LDS: the merged list, the query's category table and its place hash (2 x the longest query of the batch, at most
-        // 8192 slots; a longer query merges rows instead)
-        int hash_cap = 64;
-        while (hash_cap < 2 * max_nnz_p && hash_cap < 8192) hash_cap <<= 1;
-        const int c_dim = std::max(1, ix->fc.dim);
-        const size_t slds = (size_t)cap * 12 + (size_t)c_dim * 8 + (size_t)hash_cap * 12;
-        if (slds > 64 * 1024)
-            LOCREC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(knn_side_topk),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)slds));
-        hipLaunchKernelGGL(knn_side_topk, dim3((unsigned)nq), dim3(256), slds, s, side_csr_of(ix), ix->wide_rows_dev.p, nw, qrows_dev,
-                           qrow0, ix->cand_slice0 * 64, (int32_t)std::min<int64_t>(ix->n, (int64_t)ix->cand_slice1 * 64), pw, cw, K,
-                           ix->rid.p, ix->ids_by_rank.p, ix->row_of_rid.p, ix->out_ids.p, ix->out_sims.p, ix->out_rows.p,
-                           ix->out_cnt.p, c_dim, hash_cap);
-    }
-    if (mark_absent)
-        hipLaunchKernelGGL(knn_mark_absent, dim3((unsigned)nq), dim3(64), 0, s, ix->fp.norm.p, ix->fc.norm.p, qrows_dev,
-                           qrow0, (int32_t)nq, K, ix->out_ids.p, ix->out_sims.p, ix->out_rows.p, ix->out_cnt.p);
-    LOCREC_HIP_TRY(hipGetLastError());
-    ix->last_nq = nq;
-    ix->last_k = k;
-    ix->have_result = true;
-    ix->last_tiled = {qrows_dev, qrow0, nq, max_nnz_p, max_nnz_c, pw, cw, k, mark_absent};
-    return LOCREC_OK;
-}
+static_assert(kHistBins == cfg::kHistBins && kCollectCap == cfg::kCollectCap, "knn_single.h and knn_index.h disagree");
 
 // The fast insertion path of the last tiled scan dropped a survivor (a wave queue overflowed):
 // redo the scan with synchronous insertion.
@@ -1322,8 +1002,9 @@ int32_t rerun_tiled_sync(locrec_knn_index *ix)
     const bool saved = ix->no_fast, saved_single = ix->no_single;
     ix->no_fast = true;
     ix->no_single = true;
-    const auto r = ix->last_tiled;
-    const int32_t st = enqueue_topk(ix, r.qrows_dev, r.qrow0, r.nq, r.max_p, r.max_c, r.pw, r.cw, r.k, r.mark_absent);
+    const auto r = ix->last_tiled;  // (a copy: the call writes last_tiled)
+    const QueryRows q = r.qrows_dev ? QueryRows::list(r.qrows_dev, r.qrows) : QueryRows::range(r.qrow0, r.nq);
+    const int32_t st = enqueue_topk(ix, q, r.max_p, r.max_c, r.pw, r.cw, r.k, r.mark_absent);
     ix->no_fast = saved;
     ix->no_single = saved_single;
     return st;
@@ -1336,7 +1017,7 @@ int32_t rerun_single_tiled(locrec_knn_index *ix)
     const bool saved = ix->no_single;
     ix->no_single = true;
     const int32_t row = ix->single_qrow;
-    const int32_t st = enqueue_topk(ix, nullptr, row, 1, ix->fp.nnz[row], ix->fc.nnz[row], ix->single_pw, ix->single_cw,
+    const int32_t st = enqueue_topk(ix, QueryRows::range(row, 1), ix->fp.nnz[row], ix->fc.nnz[row], ix->single_pw, ix->single_cw,
                                     ix->last_k);
     ix->no_single = saved;
     return st;
@@ -1799,15 +1480,10 @@ extern "C" int32_t locrec_knn_row_person_ids(locrec_knn_index *ix, int64_t first
     return LOCREC_OK;
 } LOCREC_CATCH_ALL
 
-extern "C" int32_t locrec_knn_topk_range_async(locrec_knn_index *ix, int64_t first, int64_t nq,
-                                               double pw, double cw, int64_t k) try
+namespace {
+// locrec_knn_topk_range_async (knn_batch.hip) behind its checks, K <= LOCREC_KNN_BATCH_MAX_K: the per-query LDS lists
+int32_t topk_range_lds(locrec_knn_index *ix, int64_t first, int64_t nq, double pw, double cw, int64_t k)
 {
-    if (!ix) return fail(LOCREC_E_INVALID_ARG, "index is NULL");
-    ix->have_result = false;
-    LOCREC_TRY(check_params(pw, cw, k));
-    if (k > LOCREC_KNN_BATCH_MAX_K) return fail(LOCREC_E_INVALID_ARG, "k_nearest %lld exceeds the batch limit %d", (long long)k, LOCREC_KNN_BATCH_MAX_K);
-    if (first < 0 || nq <= 0 || first + nq > ix->n) return fail(LOCREC_E_INVALID_ARG, "row range out of bounds");
-    LOCREC_HIP_TRY(hipSetDevice(ix->device));
     // rows are sorted by (nnz_place, nnz_category): the last row of the range has the largest nnz_place
     int max_p = 0, max_c = 0;
     bool any_absent = false;
@@ -1816,9 +1492,9 @@ extern "C" int32_t locrec_knn_topk_range_async(locrec_knn_index *ix, int64_t fir
         max_p = std::max(max_p, ix->fp.nnz[r]);
         max_c = std::max(max_c, ix->fc.nnz[r]);
     }
-    LOCREC_TRY(enqueue_topk(ix, nullptr, (int32_t)first, nq, std::max(1, max_p), std::max(1, max_c), pw, cw, k, any_absent));
-    return LOCREC_OK;
-} LOCREC_CATCH_ALL
+    return enqueue_topk(ix, QueryRows::range((int32_t)first, nq), std::max(1, max_p), std::max(1, max_c), pw, cw, k, any_absent);
+}
+}  // namespace
 
 // Flush intervals replayed with synchronous insertion inside knn_scan since the index was created
 // (include/locrec.h).
@@ -1899,25 +1575,19 @@ extern "C" int32_t locrec_knn_fetch_topk(locrec_knn_index *ix, int64_t nq, int64
     return LOCREC_OK;
 } LOCREC_CATCH_ALL
 
-extern "C" int32_t locrec_knn_query_batch(locrec_knn_index *ix, int64_t nq, const int64_t *person_ids,
-                                          double pw, double cw, int64_t k, int64_t *out_ids,
-                                          double *out_sims, int64_t *out_counts) try
+namespace {
+
+// locrec_knn_query_batch (knn_batch.hip) behind its checks, K <= LOCREC_KNN_BATCH_MAX_K: rows[i] = the row of person i
+int32_t query_batch_lds(locrec_knn_index *ix, const std::vector<int32_t> &rows, double pw, double cw, int64_t k, int64_t *out_ids,
+                        double *out_sims, int64_t *out_counts)
 {
-    if (!ix) return fail(LOCREC_E_INVALID_ARG, "index is NULL");
-    ix->have_result = false;
-    LOCREC_TRY(check_params(pw, cw, k));
-    if (k > LOCREC_KNN_BATCH_MAX_K) return fail(LOCREC_E_INVALID_ARG, "k_nearest %lld exceeds the batch limit %d", (long long)k, LOCREC_KNN_BATCH_MAX_K);
-    if (nq < 0 || (nq > 0 && !person_ids)) return fail(LOCREC_E_INVALID_ARG, "bad query list");
-    if (nq == 0) return LOCREC_OK;
-    LOCREC_HIP_TRY(hipSetDevice(ix->device));
-    // queries are processed in row order so that a tile holds queries of similar length
-    std::vector<int32_t> rows((size_t)nq);
+    const int64_t nq = (int64_t)rows.size();
     int max_p = 0, max_c = 0;
     for (int64_t i = 0; i < nq; ++i) {
-        LOCREC_TRY(find_query_row(ix, person_ids[i], &rows[i]));
         max_p = std::max(max_p, ix->fp.nnz[rows[i]]);
         max_c = std::max(max_c, ix->fc.nnz[rows[i]]);
     }
+    // queries are processed in row order so that a tile holds queries of similar length
     std::vector<int32_t> ord((size_t)nq);
     std::iota(ord.begin(), ord.end(), 0);
     std::sort(ord.begin(), ord.end(), [&](int32_t a, int32_t b) { return rows[a] < rows[b]; });
@@ -1926,8 +1596,7 @@ extern "C" int32_t locrec_knn_query_batch(locrec_knn_index *ix, int64_t nq, cons
     LOCREC_TRY(ix->qrows.reserve((size_t)nq));
     LOCREC_HIP_TRY(hipMemcpyAsync(ix->qrows.p, sorted_rows.data(), (size_t)nq * 4, hipMemcpyHostToDevice, ix->stream));
     LOCREC_HIP_TRY(hipStreamSynchronize(ix->stream));
-    ix->qrows_host = sorted_rows;
-    LOCREC_TRY(enqueue_topk(ix, ix->qrows.p, 0, nq, max_p, max_c, pw, cw, k));
+    LOCREC_TRY(enqueue_topk(ix, QueryRows::list(ix->qrows.p, sorted_rows), max_p, max_c, pw, cw, k));
     std::vector<int64_t> t_ids((size_t)nq * k), t_cnt((size_t)nq);
     std::vector<double> t_sims((size_t)nq * k);
     LOCREC_TRY(locrec_knn_fetch_topk(ix, nq, k, t_ids.data(), t_sims.data(), t_cnt.data()));
@@ -1938,14 +1607,13 @@ extern "C" int32_t locrec_knn_query_batch(locrec_knn_index *ix, int64_t nq, cons
         if (out_counts) out_counts[dst] = t_cnt[i];
     }
     return LOCREC_OK;
-} LOCREC_CATCH_ALL
+}
 
-extern "C" int32_t locrec_knn_all_pairs_topk(locrec_knn_index *ix, double pw, double cw, int64_t k,
-                                             int64_t *out_ids, double *out_sims, int64_t *out_counts) try
+// locrec_knn_all_pairs_topk (knn_batch.hip) behind its checks, K <= LOCREC_KNN_BATCH_MAX_K: ranges of rows through
+// topk_range_lds
+int32_t all_pairs_topk_lds(locrec_knn_index *ix, double pw, double cw, int64_t k, int64_t *out_ids, double *out_sims,
+                           int64_t *out_counts)
 {
-    if (!ix) return fail(LOCREC_E_INVALID_ARG, "index is NULL");
-    LOCREC_TRY(check_params(pw, cw, k));
-    if (k > LOCREC_KNN_BATCH_MAX_K) return fail(LOCREC_E_INVALID_ARG, "k_nearest %lld exceeds the batch limit %d", (long long)k, LOCREC_KNN_BATCH_MAX_K);
     const int64_t n = ix->n;
     // bounded batches keep the workspaces small; results are scattered back to input order
     const int64_t batch = 65536;
@@ -1955,7 +1623,9 @@ extern "C" int32_t locrec_knn_all_pairs_topk(locrec_knn_index *ix, double pw, do
     std::vector<double> t_sims;
     for (int64_t first = 0; first < n; first += batch) {
         const int64_t nq = std::min(batch, n - first);
-        LOCREC_TRY(locrec_knn_topk_range_async(ix, first, nq, pw, cw, k));
+        ix->have_result = false;
+        LOCREC_HIP_TRY(hipSetDevice(ix->device));
+        LOCREC_TRY(topk_range_lds(ix, first, nq, pw, cw, k));
         t_ids.resize((size_t)nq * k);
         t_sims.resize((size_t)nq * k);
         t_cnt.resize((size_t)nq);
@@ -1968,7 +1638,28 @@ extern "C" int32_t locrec_knn_all_pairs_topk(locrec_knn_index *ix, double pw, do
         }
     }
     return LOCREC_OK;
-} LOCREC_CATCH_ALL
+}
+
+// one request's K <= LOCREC_KNN_BATCH_MAX_K neighbours over the handle's candidate range (locrec_knn_query,
+// locrec_knn_query_shard), behind their checks
+int32_t query_one_lds(locrec_knn_index *ix, int32_t row, double pw, double cw, int64_t keff, int64_t *out_ids, double *out_sims,
+                      int64_t *inout_count)
+{
+    LOCREC_TRY(enqueue_topk(ix, QueryRows::range(row, 1), ix->fp.nnz[row], ix->fc.nnz[row], pw, cw, keff));
+    std::vector<int64_t> ids((size_t)keff);
+    std::vector<double> sims((size_t)keff);
+    int64_t cnt = 0;
+    LOCREC_TRY(locrec_knn_fetch_topk(ix, 1, keff, ids.data(), sims.data(), &cnt));
+    const int64_t cap = *inout_count;
+    for (int64_t i = 0; i < std::min(cap, cnt); ++i) {
+        if (out_ids) out_ids[i] = ids[i];
+        if (out_sims) out_sims[i] = sims[i];
+    }
+    *inout_count = cnt;
+    return LOCREC_OK;
+}
+
+}  // namespace
 
 extern "C" int32_t locrec_knn_query(locrec_knn_index *ix, int64_t person_id, double pw, double cw,
                                     int64_t k, int64_t *out_ids, double *out_sims, int64_t *inout_count) try
@@ -1983,18 +1674,7 @@ extern "C" int32_t locrec_knn_query(locrec_knn_index *ix, int64_t person_id, dou
     LOCREC_HIP_TRY(hipSetDevice(ix->device));
     if (keff > LOCREC_KNN_BATCH_MAX_K)  // e.g. the shipped --k-nearest 2000000: sort every candidate
         return knn_large_topk(ix, row, pw, cw, keff, out_ids, out_sims, inout_count);
-    LOCREC_TRY(enqueue_topk(ix, nullptr, row, 1, ix->fp.nnz[row], ix->fc.nnz[row], pw, cw, keff));
-    std::vector<int64_t> ids((size_t)keff);
-    std::vector<double> sims((size_t)keff);
-    int64_t cnt = 0;
-    LOCREC_TRY(locrec_knn_fetch_topk(ix, 1, keff, ids.data(), sims.data(), &cnt));
-    const int64_t cap = *inout_count;
-    for (int64_t i = 0; i < std::min(cap, cnt); ++i) {
-        if (out_ids) out_ids[i] = ids[i];
-        if (out_sims) out_sims[i] = sims[i];
-    }
-    *inout_count = cnt;
-    return LOCREC_OK;
+    return query_one_lds(ix, row, pw, cw, keff, out_ids, out_sims, inout_count);
 } LOCREC_CATCH_ALL
 
 namespace {
@@ -2018,8 +1698,7 @@ int32_t launch_aggregate(locrec_knn_index *ix, const KnnAggLaunch &l, int64_t nq
     const void *fn = l.form == kAggBuckets ? reinterpret_cast<const void *>(knn_aggregate_buckets)
                      : l.key32             ? reinterpret_cast<const void *>(knn_aggregate<uint32_t>)
                                            : reinterpret_cast<const void *>(knn_aggregate<uint64_t>);
-    if (l.lds > 64 * 1024)
-        LOCREC_HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds));
+    LOCREC_TRY(knn_raise_lds_limit(fn, l.lds));
     const dim3 grid((unsigned)nq), block((unsigned)l.threads);
     if (l.form == kAggBuckets)
         hipLaunchKernelGGL(knn_aggregate_buckets, grid, block, l.lds, s, ix->out_rows.p, ix->out_sims.p, ix->out_cnt.p, K,
@@ -2068,9 +1747,10 @@ int32_t enqueue_aggregate(locrec_knn_index *ix, int64_t nq, int K)
 }
 
 // Batched makeRecommendations beyond the LDS lists (K > LOCREC_KNN_BATCH_MAX_K; the shipped --k-nearest 2000000,
-// bin/knn_recommender.sh:35).  K >= N - 1 selects every positive-similarity person: tiles of 16 queries without any
-// top-K (knn_large.hip, knn_large_recommend_batch).  A K in between (more than 1024 but fewer than all) keeps the
-// top-K semantics: such a batch is served query by query by the single-request large-K path when it is fetched.
+// bin/knn_recommender.sh:35) for rows in processing order, resident on the device afterwards (lkb_place / lkb_est /
+// lkb_off).  K >= N - 1 selects every positive-similarity person: tiles of 16 queries without any top-K
+// (knn_large_recommend_batch).  A K in between keeps the top-K semantics: the tiled selection in front of the same
+// aggregation (knn_topk_recommend_batch, knn_anyk.h).
 int32_t enqueue_large_k_batch(locrec_knn_index *ix, const std::vector<int32_t> &rows, double pw, double cw, int64_t k)
 {
     const int64_t nq = (int64_t)rows.size();
@@ -2081,18 +1761,14 @@ int32_t enqueue_large_k_batch(locrec_knn_index *ix, const std::vector<int32_t> &
     ix->last_nq = nq;
     ix->last_k = k;
     ix->single_pending = false;
-    ix->have_result = false;  // (no neighbour lists are produced: locrec_knn_fetch_topk has nothing to read)
-    if (k >= ix->n - 1) {
-        const int64_t worst = nq * (int64_t)std::max<size_t>(1, ix->cplace_ids.size()) * 16;
-        if (worst > ((int64_t)48 << 30))
-            return fail(LOCREC_E_INVALID_ARG, "a batch of %lld queries at K = %lld may return %lld GB of rows: split it",
-                        (long long)nq, (long long)k, (long long)(worst >> 30));
-        ix->lkb_deferred = false;
-        return knn_large_recommend_batch(ix, rows.data(), nq, pw, cw);
-    }
-    ix->lkb_deferred = true;
-    ix->have_lkb = true;
-    return LOCREC_OK;
+    ix->have_result = false;  // (no neighbour lists are left for locrec_knn_fetch_topk)
+    ix->have_agg = false;
+    const int64_t worst = nq * (int64_t)std::max<size_t>(1, ix->cplace_ids.size()) * 16;
+    if (worst > ((int64_t)48 << 30))
+        return fail(LOCREC_E_INVALID_ARG, "a batch of %lld queries at K = %lld may return %lld GB of rows: split it",
+                    (long long)nq, (long long)k, (long long)(worst >> 30));
+    if (k >= ix->n - 1) return knn_large_recommend_batch(ix, rows.data(), nq, pw, cw);
+    return knn_topk_recommend_batch(ix, rows.data(), nq, pw, cw, k);
 }
 
 // rows of a resident large-K batch (processing order), to host arrays
@@ -2101,30 +1777,6 @@ int32_t fetch_large_k_batch(locrec_knn_index *ix, int64_t nq, int64_t *out_offse
 {
     hipStream_t s = ix->stream;
     const int64_t cap = *inout_capacity;
-    if (ix->lkb_deferred) {
-        std::vector<std::vector<int64_t>> bp((size_t)nq);
-        std::vector<std::vector<double>> be((size_t)nq);
-        out_offsets[0] = 0;
-        for (int64_t q = 0; q < nq; ++q) {
-            const int32_t row = ix->agg_rows[(size_t)q];
-            int64_t c = 0;
-            if (ix->fp.nnz[(size_t)row] > 0 && ix->fc.nnz[(size_t)row] > 0) {
-                LOCREC_TRY(knn_large_recommend(ix, row, ix->agg_pw, ix->agg_cw, ix->last_k, nullptr, nullptr, &c));
-                bp[(size_t)q].resize((size_t)c);
-                be[(size_t)q].resize((size_t)c);
-                LOCREC_TRY(knn_large_recommend(ix, row, ix->agg_pw, ix->agg_cw, ix->last_k, bp[(size_t)q].data(), be[(size_t)q].data(), &c));
-            }
-            out_offsets[q + 1] = out_offsets[q] + c;
-        }
-        *inout_capacity = out_offsets[nq];
-        if (out_offsets[nq] > cap || out_offsets[nq] == 0) return LOCREC_OK;
-        if (!out_places || !out_ratings) return fail(LOCREC_E_INVALID_ARG, "NULL output buffer");
-        for (int64_t q = 0; q < nq; ++q) {
-            std::copy(bp[(size_t)q].begin(), bp[(size_t)q].end(), out_places + out_offsets[q]);
-            std::copy(be[(size_t)q].begin(), be[(size_t)q].end(), out_ratings + out_offsets[q]);
-        }
-        return LOCREC_OK;
-    }
     for (int64_t q = 0; q <= nq; ++q) out_offsets[q] = ix->lkb_off[(size_t)q];
     const int64_t total = out_offsets[nq];
     *inout_capacity = total;
@@ -2138,30 +1790,20 @@ int32_t fetch_large_k_batch(locrec_knn_index *ix, int64_t nq, int64_t *out_offse
 
 }  // namespace
 
-// Batched makeRecommendations (the additive surface of SURVEY.md 8b): findSimilarPersons + the
-// similarity-weighted aggregation for the persons at internal rows [first, first + nq); everything
-// stays on the device until locrec_knn_fetch_recommend.
-extern "C" int32_t locrec_knn_recommend_range_async(locrec_knn_index *ix, int64_t first, int64_t nq,
-                                                    double pw, double cw, int64_t k) try
+// locrec_knn_recommend_range_async (knn_batch.hip) behind its checks, K <= LOCREC_KNN_BATCH_MAX_K: findSimilarPersons + the
+// similarity-weighted aggregation for the persons at internal rows [first, first + nq); everything stays on the device
+// until locrec_knn_fetch_recommend.
+namespace {
+int32_t recommend_range_lds(locrec_knn_index *ix, int64_t first, int64_t nq, double pw, double cw, int64_t k)
 {
-    if (!ix) return fail(LOCREC_E_INVALID_ARG, "index is NULL");
-    ix->have_agg = false;
-    ix->have_lkb = false;
-    if (k > LOCREC_KNN_BATCH_MAX_K) {
-        LOCREC_TRY(check_params(pw, cw, k));
-        if (first < 0 || nq <= 0 || first + nq > ix->n) return fail(LOCREC_E_INVALID_ARG, "row range out of bounds");
-        LOCREC_HIP_TRY(hipSetDevice(ix->device));
-        std::vector<int32_t> rows((size_t)nq);
-        std::iota(rows.begin(), rows.end(), (int32_t)first);
-        return enqueue_large_k_batch(ix, rows, pw, cw, k);
-    }
-    LOCREC_TRY(locrec_knn_topk_range_async(ix, first, nq, pw, cw, k));
+    LOCREC_TRY(topk_range_lds(ix, first, nq, pw, cw, k));
     ix->agg_first = (int32_t)first;
     ix->agg_rows.clear();
     ix->agg_pw = pw;
     ix->agg_cw = cw;
     return enqueue_aggregate(ix, nq, (int)k);
-} LOCREC_CATCH_ALL
+}
+}  // namespace
 
 extern "C" int32_t locrec_knn_fetch_recommend(locrec_knn_index *ix, int64_t nq, int64_t *out_offsets,
                                               int64_t *out_places, double *out_ratings, int64_t *inout_capacity) try
@@ -2243,28 +1885,15 @@ extern "C" int32_t locrec_knn_fetch_recommend(locrec_knn_index *ix, int64_t nq, 
     return LOCREC_OK;
 } LOCREC_CATCH_ALL
 
-// makeRecommendations for a list of persons; rows of person i are
-// [out_offsets[i], out_offsets[i + 1]) of out_places / out_ratings, ordered by place id.
-extern "C" int32_t locrec_knn_recommend_batch(locrec_knn_index *ix, int64_t nq, const int64_t *person_ids,
-                                              double pw, double cw, int64_t k, int64_t *out_offsets,
-                                              int64_t *out_places, double *out_ratings, int64_t *inout_capacity) try
+// locrec_knn_recommend_batch (knn_batch.hip) behind its checks, K <= LOCREC_KNN_BATCH_MAX_K or K >= N - 1: rows[i] = the row
+// of person i; rows of person i are [out_offsets[i], out_offsets[i + 1]) of out_places / out_ratings, ordered by place id.
+namespace {
+int32_t recommend_batch_lds(locrec_knn_index *ix, const std::vector<int32_t> &rows, double pw, double cw, int64_t k,
+                            int64_t *out_offsets, int64_t *out_places, double *out_ratings, int64_t *inout_capacity)
 {
-    if (!ix) return fail(LOCREC_E_INVALID_ARG, "index is NULL");
-    ix->have_result = false;
-    ix->have_agg = false;
-    ix->have_lkb = false;
-    LOCREC_TRY(check_params(pw, cw, k));
-    if (nq < 0 || (nq > 0 && !person_ids) || !out_offsets || !inout_capacity) return fail(LOCREC_E_INVALID_ARG, "bad arguments");
-    if (nq == 0) {
-        out_offsets[0] = 0;
-        *inout_capacity = 0;
-        return LOCREC_OK;
-    }
-    LOCREC_HIP_TRY(hipSetDevice(ix->device));
-    std::vector<int32_t> rows((size_t)nq);
+    const int64_t nq = (int64_t)rows.size();
     int max_p = 0, max_c = 0;
     for (int64_t i = 0; i < nq; ++i) {
-        LOCREC_TRY(find_query_row(ix, person_ids[i], &rows[i]));
         max_p = std::max(max_p, ix->fp.nnz[rows[i]]);
         max_c = std::max(max_c, ix->fc.nnz[rows[i]]);
     }
@@ -2279,15 +1908,14 @@ extern "C" int32_t locrec_knn_recommend_batch(locrec_knn_index *ix, int64_t nq, 
         const std::vector<int32_t> sorted_rows = ix->agg_rows;
         LOCREC_TRY(enqueue_large_k_batch(ix, sorted_rows, pw, cw, k));
     } else {
-    LOCREC_TRY(ix->qrows.reserve((size_t)nq));
-    LOCREC_HIP_TRY(hipMemcpyAsync(ix->qrows.p, ix->agg_rows.data(), (size_t)nq * 4, hipMemcpyHostToDevice, ix->stream));
-    LOCREC_HIP_TRY(hipStreamSynchronize(ix->stream));
-    ix->qrows_host = ix->agg_rows;
-    LOCREC_TRY(enqueue_topk(ix, ix->qrows.p, 0, nq, max_p, max_c, pw, cw, k));
-    ix->agg_first = -1;
-    ix->agg_pw = pw;
-    ix->agg_cw = cw;
-    LOCREC_TRY(enqueue_aggregate(ix, nq, (int)k));
+        LOCREC_TRY(ix->qrows.reserve((size_t)nq));
+        LOCREC_HIP_TRY(hipMemcpyAsync(ix->qrows.p, ix->agg_rows.data(), (size_t)nq * 4, hipMemcpyHostToDevice, ix->stream));
+        LOCREC_HIP_TRY(hipStreamSynchronize(ix->stream));
+        LOCREC_TRY(enqueue_topk(ix, QueryRows::list(ix->qrows.p, ix->agg_rows), max_p, max_c, pw, cw, k));
+        ix->agg_first = -1;
+        ix->agg_pw = pw;
+        ix->agg_cw = cw;
+        LOCREC_TRY(enqueue_aggregate(ix, nq, (int)k));
     }
     std::vector<int64_t> t_off((size_t)nq + 1);
     int64_t tcap = 0;
@@ -2311,46 +1939,8 @@ extern "C" int32_t locrec_knn_recommend_batch(locrec_knn_index *ix, int64_t nq, 
         std::copy(te.begin() + t_off[i], te.begin() + t_off[i + 1], out_ratings + dst);
     }
     return LOCREC_OK;
-} LOCREC_CATCH_ALL
-
-// findSimilarPersons (:27-49) restricted to one shard of the candidates: the local top-K of a
-// request whose candidate scan is split over several GPUs (every GPU holds the whole index).
-extern "C" int32_t locrec_knn_query_shard(locrec_knn_index *ix, int64_t person_id, double pw, double cw,
-                                          int64_t k, int32_t shard_index, int32_t shard_count,
-                                          int64_t *out_ids, double *out_sims, int64_t *inout_count) try
-{
-    if (!ix) return fail(LOCREC_E_INVALID_ARG, "index is NULL");
-    if (!inout_count) return fail(LOCREC_E_INVALID_ARG, "inout_count is NULL");
-    LOCREC_TRY(check_params(pw, cw, k));
-    if (shard_count < 1 || shard_index < 0 || shard_index >= shard_count)
-        return fail(LOCREC_E_INVALID_ARG, "shard %d of %d", shard_index, shard_count);
-    int32_t row = 0;
-    LOCREC_TRY(find_query_row(ix, person_id, &row));
-    const int64_t keff = std::min<int64_t>(k, std::max<int64_t>(1, ix->n - 1));
-    if (keff > LOCREC_KNN_BATCH_MAX_K)
-        return fail(LOCREC_E_INVALID_ARG, "k_nearest %lld exceeds the limit %d of a sharded request", (long long)k,
-                    LOCREC_KNN_BATCH_MAX_K);
-    LOCREC_HIP_TRY(hipSetDevice(ix->device));
-    int32_t s0 = 0, s1 = 0;
-    shard_slice_range(ix, shard_index, shard_count, &s0, &s1);
-    if (s0 >= s1) {  // more shards than slices: this one is empty
-        *inout_count = 0;
-        return LOCREC_OK;
-    }
-    CandRangeGuard guard(ix, s0, s1);  // also covers the reruns inside locrec_knn_fetch_topk
-    LOCREC_TRY(enqueue_topk(ix, nullptr, row, 1, ix->fp.nnz[row], ix->fc.nnz[row], pw, cw, keff));
-    std::vector<int64_t> ids((size_t)keff);
-    std::vector<double> sims((size_t)keff);
-    int64_t cnt = 0;
-    LOCREC_TRY(locrec_knn_fetch_topk(ix, 1, keff, ids.data(), sims.data(), &cnt));
-    const int64_t cap = *inout_count;
-    for (int64_t i = 0; i < std::min(cap, cnt); ++i) {
-        if (out_ids) out_ids[i] = ids[i];
-        if (out_sims) out_sims[i] = sims[i];
-    }
-    *inout_count = cnt;
-    return LOCREC_OK;
-} LOCREC_CATCH_ALL
+}
+}  // namespace
 
 // makeRecommendations0 (:51-70) for a given list of similar persons (e.g. the merged local lists
 // of a sharded request), in the given order.
@@ -2441,7 +2031,7 @@ extern "C" int32_t locrec_knn_recommend(locrec_knn_index *ix, int64_t person_id,
     hipStream_t s = ix->stream;
     static const bool dbg_timing = debug_env("LOCREC_DEBUG_TIMING") != nullptr;
     const auto tp0 = std::chrono::steady_clock::now();
-    LOCREC_TRY(enqueue_topk(ix, nullptr, row, 1, ix->fp.nnz[row], ix->fc.nnz[row], pw, cw, keff));
+    LOCREC_TRY(enqueue_topk(ix, QueryRows::range(row, 1), ix->fp.nnz[row], ix->fc.nnz[row], pw, cw, keff));
     const auto tp1 = std::chrono::steady_clock::now();
     const int K = (int)keff;
     const KnnAggPlan plan = aggregate_plan(ix, K);

@@ -1,46 +1,21 @@
-// knn_batch.hip -- the batched KNN entry points at any K: findSimilarPersons / makeRecommendations for many persons
-// when k_nearest exceeds the per-query LDS lists (LOCREC_KNN_BATCH_MAX_K), e.g. the shipped --k-nearest 2000000
-// (bin/knn_recommender.sh:35) below N - 1.
+// knn_batch.hip -- the KNN translation unit: knn.hip whole, then the six batch entry points - findSimilarPersons /
+// makeRecommendations for many persons - at any K, e.g. the shipped --k-nearest 2000000 (bin/knn_recommender.sh:35)
+// below N - 1; then the ranked forms, the pools and the visitors' calls.
 //
-// This file is the KNN translation unit: it includes knn.hip whole and defines the six batch entry points that carried
-// the limit (or served 1024 < K < N - 1 one query at a time) in front of it.  knn.hip itself stays as it is: its bytes
-// are part of the hash that ties the committed rocprofv3 counter record to the kernels it measured (bench.py
-// PMC_SOURCES).  So knn.hip's definitions are renamed on the way in (the macros below) to internal names outside the
-// locrec_ prefix, and the public names defined here forward to them for K <= LOCREC_KNN_BATCH_MAX_K (and, in the
-// recommend calls, for K >= N - 1): those calls run exactly the code they ran before.  Calls between these functions
-// inside knn.hip stay on the originals, which is right: the functions here serve K > LOCREC_KNN_BATCH_MAX_K themselves.
-// Any other K takes the tiled top-K of knn_large.hip (knn_anyk.h).  locrec_knn_destroy is renamed the same way: the public
-// one (knn_visitors_api.h) drops the handle's side record for visitors - what the hashed handle has no member for - and
-// forwards.
+// Each entry point is defined once, here: it checks its arguments and then dispatches on K.  Up to
+// LOCREC_KNN_BATCH_MAX_K (the per-query LDS lists) a call takes knn.hip's body of its name with _lds (behind the checks);
+// any larger K takes the tiled top-K of knn_large.hip (knn_anyk.h) - in the recommend calls K >= N - 1 ("every positive
+// neighbour") takes knn.hip's body too, which needs no top-K at all.
 //
-// The tiled path keeps its device buffers in handle members that already exist (the handle's layout is hashed too):
+// The tiled path keeps its device buffers in the handle:
 //   lkb_S                     a tile's similarities, transposed, and the masked row-major tile of the aggregation
 //   lk_keys / lk_vals (+ _out) the tile's segments, ping-pong of the merge passes
 //   tile_hist / tile_sel      one histogram and one selection record per column (shared with enqueue_topk)
 //   out_*                     the neighbour lists, as every batch leaves them for locrec_knn_fetch_topk
 //   lkb_*                     the place-major aggregation and its resident result (locrec_knn_fetch_recommend)
-// They are grow-only and freed with the handle.  The deferred one-by-one branch of fetch_large_k_batch (knn.hip) is
-// no longer reachable - no call here sets lkb_deferred - and stays only because knn.hip's bytes are hashed.
-
-#define locrec_knn_query_batch knn_query_batch_lds
-#define locrec_knn_topk_range_async knn_topk_range_async_lds
-#define locrec_knn_all_pairs_topk knn_all_pairs_topk_lds
-#define locrec_knn_query_shard knn_query_shard_lds
-#define locrec_knn_recommend_batch knn_recommend_batch_lds
-#define locrec_knn_recommend_range_async knn_recommend_range_async_lds
-#define locrec_knn_destroy knn_destroy_handle
+// They are grow-only and freed with the handle.
 
 #include "knn.hip"
-
-#undef locrec_knn_query_batch
-#undef locrec_knn_topk_range_async
-#undef locrec_knn_all_pairs_topk
-#undef locrec_knn_query_shard
-#undef locrec_knn_recommend_batch
-#undef locrec_knn_recommend_range_async
-#undef locrec_knn_destroy
-
-#include "knn_anyk.h"
 
 namespace {
 
@@ -87,28 +62,6 @@ int32_t any_k_rows(locrec_knn_index *ix, const std::vector<int32_t> &rows, doubl
     return LOCREC_OK;
 }
 
-// makeRecommendations with 1024 < K < N - 1 for rows (processing order), resident on the device like
-// enqueue_large_k_batch leaves the K >= N - 1 batch
-int32_t enqueue_any_k_recommend(locrec_knn_index *ix, const std::vector<int32_t> &rows, double pw, double cw, int64_t k)
-{
-    const int64_t nq = (int64_t)rows.size();
-    ix->agg_rows = rows;
-    ix->agg_first = -1;
-    ix->agg_pw = pw;
-    ix->agg_cw = cw;
-    ix->last_nq = nq;
-    ix->last_k = k;
-    ix->single_pending = false;
-    ix->have_result = false;  // (no neighbour lists are left for locrec_knn_fetch_topk)
-    ix->have_agg = false;
-    const int64_t worst = nq * (int64_t)std::max<size_t>(1, ix->cplace_ids.size()) * 16;
-    if (worst > ((int64_t)48 << 30))
-        return fail(LOCREC_E_INVALID_ARG, "a batch of %lld queries at K = %lld may return %lld GB of rows: split it",
-                    (long long)nq, (long long)k, (long long)(worst >> 30));
-    ix->lkb_deferred = false;
-    return knn_topk_recommend_batch(ix, rows.data(), nq, pw, cw, k);
-}
-
 // the recommend calls take the tiled top-K for LOCREC_KNN_BATCH_MAX_K < K < N - 1
 bool any_k_recommend(const locrec_knn_index *ix, int64_t k) { return k > LOCREC_KNN_BATCH_MAX_K && k < ix->n - 1; }
 
@@ -117,8 +70,7 @@ bool any_k_recommend(const locrec_knn_index *ix, int64_t k) { return k > LOCREC_
 extern "C" int32_t locrec_knn_query_batch(locrec_knn_index *ix, int64_t nq, const int64_t *person_ids, double pw, double cw,
                                           int64_t k, int64_t *out_ids, double *out_sims, int64_t *out_counts) try
 {
-    if (!ix || k <= LOCREC_KNN_BATCH_MAX_K)
-        return knn_query_batch_lds(ix, nq, person_ids, pw, cw, k, out_ids, out_sims, out_counts);
+    if (!ix) return fail(LOCREC_E_INVALID_ARG, "index is NULL");
     ix->have_result = false;
     LOCREC_TRY(check_params(pw, cw, k));
     if (nq < 0 || (nq > 0 && !person_ids)) return fail(LOCREC_E_INVALID_ARG, "bad query list");
@@ -126,17 +78,19 @@ extern "C" int32_t locrec_knn_query_batch(locrec_knn_index *ix, int64_t nq, cons
     LOCREC_HIP_TRY(hipSetDevice(ix->device));
     std::vector<int32_t> rows((size_t)nq);
     for (int64_t i = 0; i < nq; ++i) LOCREC_TRY(find_query_row(ix, person_ids[i], &rows[(size_t)i]));
+    if (k <= LOCREC_KNN_BATCH_MAX_K) return query_batch_lds(ix, rows, pw, cw, k, out_ids, out_sims, out_counts);
     return any_k_rows(ix, rows, pw, cw, k, false, out_ids, out_sims, out_counts);
 } LOCREC_CATCH_ALL
 
 extern "C" int32_t locrec_knn_topk_range_async(locrec_knn_index *ix, int64_t first, int64_t nq, double pw, double cw,
                                                int64_t k) try
 {
-    if (!ix || k <= LOCREC_KNN_BATCH_MAX_K) return knn_topk_range_async_lds(ix, first, nq, pw, cw, k);
+    if (!ix) return fail(LOCREC_E_INVALID_ARG, "index is NULL");
     ix->have_result = false;
     LOCREC_TRY(check_params(pw, cw, k));
     if (first < 0 || nq <= 0 || first + nq > ix->n) return fail(LOCREC_E_INVALID_ARG, "row range out of bounds");
     LOCREC_HIP_TRY(hipSetDevice(ix->device));
+    if (k <= LOCREC_KNN_BATCH_MAX_K) return topk_range_lds(ix, first, nq, pw, cw, k);
     // (the whole range stays resident until locrec_knn_fetch_topk: nq x k entries)
     std::vector<int32_t> rows((size_t)nq);
     std::iota(rows.begin(), rows.end(), (int32_t)first);
@@ -146,20 +100,23 @@ extern "C" int32_t locrec_knn_topk_range_async(locrec_knn_index *ix, int64_t fir
 extern "C" int32_t locrec_knn_all_pairs_topk(locrec_knn_index *ix, double pw, double cw, int64_t k, int64_t *out_ids,
                                              double *out_sims, int64_t *out_counts) try
 {
-    if (!ix || k <= LOCREC_KNN_BATCH_MAX_K) return knn_all_pairs_topk_lds(ix, pw, cw, k, out_ids, out_sims, out_counts);
+    if (!ix) return fail(LOCREC_E_INVALID_ARG, "index is NULL");
     LOCREC_TRY(check_params(pw, cw, k));
+    if (k <= LOCREC_KNN_BATCH_MAX_K) return all_pairs_topk_lds(ix, pw, cw, k, out_ids, out_sims, out_counts);
     LOCREC_HIP_TRY(hipSetDevice(ix->device));
     // every person as the query, in the order of person_ids[] given at create
     std::vector<int32_t> rows(ix->row_of_input.begin(), ix->row_of_input.end());
     return any_k_rows(ix, rows, pw, cw, k, true, out_ids, out_sims, out_counts);
 } LOCREC_CATCH_ALL
 
+// findSimilarPersons (:27-49) restricted to one shard of the candidates: the local top-K of a request whose candidate
+// scan is split over several GPUs (every GPU holds the whole index).
 extern "C" int32_t locrec_knn_query_shard(locrec_knn_index *ix, int64_t person_id, double pw, double cw, int64_t k,
                                           int32_t shard_index, int32_t shard_count, int64_t *out_ids, double *out_sims,
                                           int64_t *inout_count) try
 {
-    if (!ix || !inout_count || std::min<int64_t>(k, std::max<int64_t>(1, ix->n - 1)) <= LOCREC_KNN_BATCH_MAX_K)
-        return knn_query_shard_lds(ix, person_id, pw, cw, k, shard_index, shard_count, out_ids, out_sims, inout_count);
+    if (!ix) return fail(LOCREC_E_INVALID_ARG, "index is NULL");
+    if (!inout_count) return fail(LOCREC_E_INVALID_ARG, "inout_count is NULL");
     LOCREC_TRY(check_params(pw, cw, k));
     if (shard_count < 1 || shard_index < 0 || shard_index >= shard_count)
         return fail(LOCREC_E_INVALID_ARG, "shard %d of %d", shard_index, shard_count);
@@ -173,41 +130,55 @@ extern "C" int32_t locrec_knn_query_shard(locrec_knn_index *ix, int64_t person_i
         *inout_count = 0;
         return LOCREC_OK;
     }
+    CandRangeGuard guard(ix, s0, s1);  // also covers the reruns inside locrec_knn_fetch_topk
+    if (keff <= LOCREC_KNN_BATCH_MAX_K) return query_one_lds(ix, row, pw, cw, keff, out_ids, out_sims, inout_count);
     // the single request's full sort over this shard's candidates (lk_gather_keys honours the slice range)
-    CandRangeGuard guard(ix, s0, s1);
     return knn_large_topk(ix, row, pw, cw, keff, out_ids, out_sims, inout_count);
 } LOCREC_CATCH_ALL
 
+// Batched makeRecommendations (the additive surface of SURVEY.md 8b) for the persons at internal rows [first, first + nq);
+// everything stays on the device until locrec_knn_fetch_recommend.
 extern "C" int32_t locrec_knn_recommend_range_async(locrec_knn_index *ix, int64_t first, int64_t nq, double pw, double cw,
                                                     int64_t k) try
 {
-    if (!ix || !any_k_recommend(ix, k)) return knn_recommend_range_async_lds(ix, first, nq, pw, cw, k);
+    if (!ix) return fail(LOCREC_E_INVALID_ARG, "index is NULL");
     ix->have_agg = false;
     ix->have_lkb = false;
+    if (k <= LOCREC_KNN_BATCH_MAX_K) ix->have_result = false;  // (a larger K forgets the lists once its checks have passed)
     LOCREC_TRY(check_params(pw, cw, k));
     if (first < 0 || nq <= 0 || first + nq > ix->n) return fail(LOCREC_E_INVALID_ARG, "row range out of bounds");
     LOCREC_HIP_TRY(hipSetDevice(ix->device));
+    if (k <= LOCREC_KNN_BATCH_MAX_K) return recommend_range_lds(ix, first, nq, pw, cw, k);
     std::vector<int32_t> rows((size_t)nq);
     std::iota(rows.begin(), rows.end(), (int32_t)first);
-    return enqueue_any_k_recommend(ix, rows, pw, cw, k);
+    return enqueue_large_k_batch(ix, rows, pw, cw, k);  // (K >= N - 1 or the tiled top-K: any_k_recommend)
 } LOCREC_CATCH_ALL
 
+// makeRecommendations for a list of persons; rows of person i are [out_offsets[i], out_offsets[i + 1]) of out_places /
+// out_ratings, ordered by place id.
 extern "C" int32_t locrec_knn_recommend_batch(locrec_knn_index *ix, int64_t nq, const int64_t *person_ids, double pw,
                                               double cw, int64_t k, int64_t *out_offsets, int64_t *out_places,
                                               double *out_ratings, int64_t *inout_capacity) try
 {
-    if (!ix || !any_k_recommend(ix, k) || nq <= 0 || !person_ids || !out_offsets || !inout_capacity)
-        return knn_recommend_batch_lds(ix, nq, person_ids, pw, cw, k, out_offsets, out_places, out_ratings, inout_capacity);
+    if (!ix) return fail(LOCREC_E_INVALID_ARG, "index is NULL");
     ix->have_result = false;
     ix->have_agg = false;
     ix->have_lkb = false;
     LOCREC_TRY(check_params(pw, cw, k));
+    if (nq < 0 || (nq > 0 && !person_ids) || !out_offsets || !inout_capacity) return fail(LOCREC_E_INVALID_ARG, "bad arguments");
+    if (nq == 0) {
+        out_offsets[0] = 0;
+        *inout_capacity = 0;
+        return LOCREC_OK;
+    }
     LOCREC_HIP_TRY(hipSetDevice(ix->device));
     std::vector<int32_t> rows((size_t)nq);
     for (int64_t i = 0; i < nq; ++i) LOCREC_TRY(find_query_row(ix, person_ids[i], &rows[(size_t)i]));
+    if (!any_k_recommend(ix, k))
+        return recommend_batch_lds(ix, rows, pw, cw, k, out_offsets, out_places, out_ratings, inout_capacity);
     // in input order (the tiled path keeps no order of its own): the resident rows go straight to the caller's arrays, or
     // only the offsets and the total when they do not fit
-    LOCREC_TRY(enqueue_any_k_recommend(ix, rows, pw, cw, k));
+    LOCREC_TRY(enqueue_large_k_batch(ix, rows, pw, cw, k));
     return locrec_knn_fetch_recommend(ix, nq, out_offsets, out_places, out_ratings, inout_capacity);
 } LOCREC_CATCH_ALL
 
@@ -218,7 +189,7 @@ extern "C" int32_t locrec_knn_recommend_batch(locrec_knn_index *ix, int64_t nq, 
 // A pool of resident indexes that serves ONE mixed batch of (index, person[, target region]) requests
 // (locrec_knn_pool_*).  A member in the "every positive neighbour" regime (K > LOCREC_KNN_BATCH_MAX_K and
 // K >= n - 1: the shipped --k-nearest 2000000) takes the shared launches of knn_pool.h; every other member's sub-batch
-// is handed to its own public call.  The pool keeps all its state here: nothing is added to locrec_knn_index.
+// is handed to its own public call.  The pool keeps all its state here.
 #include "knn_pool_api.h"
 #include "knn_pool_visitors_api.h"
 
@@ -507,16 +478,14 @@ extern "C" int32_t locrec_knn_pool_stats(int64_t *out_waves, int64_t *out_member
 }
 
 // =====================================================================================================
-// Visitors: rating vectors that are no rows of the index (locrec_knn_visitors_*), and locrec_knn_destroy in front of
-// knn.hip's, which drops the handle's side record (knn_visitors_side.h) first.
+// Visitors: rating vectors that are no rows of the index (locrec_knn_visitors_*), over the handle's visitor state.
 #include "knn_visitors_api.h"
 
 // One mixed batch of visitors over a pool of indexes (locrec_knn_pool_visitors_*): the pool's waves with the visitors' front.
 #include "knn_pool_visitors_entry.h"
 
 // Measurement and tests only (include/locrec.h): what the hit pre-pass of the last batched head / tail scan left in the
-// handle's workspaces (knn_ht_prepass.h).  knn.hip and the handle's layout are hashed (see the head of this file), so
-// enqueue_ht_prepass records nothing of its own: the shape is what the handle already says about its last scan - the
+// handle's workspaces (knn_ht_prepass.h).  enqueue_ht_prepass records nothing of its own: the shape is what the handle already says about its last scan - the
 // plan (kernel 2 or 3: the batch took the head / tail form, so its pre-pass ran), the number of queries, the query tile
 // and the candidate slices - and the caller names the batch by its size, as it does for locrec_knn_fetch_topk.  Those
 // workspaces are written by the pre-pass alone, so what is copied is always a pre-pass's own output.

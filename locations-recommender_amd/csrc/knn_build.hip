@@ -1069,8 +1069,9 @@ int32_t knn_build_device(int64_t n, const int64_t *ids, const int64_t *p_ptr, co
     }
     LOCREC_TRY(b.ratings_and_transpose());
     lap("ratings (CSR + transpose)");
-    // the handle's side record for visitors (knn_visitors_side.h) keeps the renumbering; empty without plan.use_pop
-    LOCREC_TRY(knn_visitors_attach(ix.get(), b.new_of_old));
+    // the handle's visitor state (knn_index.h: KnnVisitorSide) keeps the renumbering; empty without plan.use_pop
+    std::swap(ix->visitors.new_of_old.p, b.new_of_old.p);
+    std::swap(ix->visitors.new_of_old.n, b.new_of_old.n);
     *out = ix.release();
     return LOCREC_OK;
 }

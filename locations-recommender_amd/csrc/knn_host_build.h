@@ -367,8 +367,11 @@ static int32_t knn_create_host(
         LOCREC_HIP_TRY(hipStreamSynchronize(ix->stream));
     }
     lap("rid + norms + sync");
-    // the handle's side record for visitors (knn_visitors_side.h) keeps the renumbering; empty without plan.use_pop
-    LOCREC_TRY(locrec::knn_visitors_attach_host(ix.get(), new_of_old));
+    // the handle's visitor state (knn_index.h: KnnVisitorSide) keeps the renumbering; empty without plan.use_pop
+    if (!new_of_old.empty()) {
+        LOCREC_TRY(ix->visitors.new_of_old.upload(new_of_old, ix->stream));
+        LOCREC_HIP_TRY(hipStreamSynchronize(ix->stream));
+    }
     *out = ix.release();
     return LOCREC_OK;
 } LOCREC_CATCH_ALL

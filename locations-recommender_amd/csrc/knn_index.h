@@ -17,6 +17,8 @@ constexpr int kHtHead = 512;            // its default head width
 __host__ __device__ constexpr int ht_plane_rows(int h) { return h > kHtHead ? h : kHtHead; }
 constexpr int kHtCatRows = 64;          // rows reserved for the category panel (c_dim <= 64)
 constexpr int kHtNP = 4;                // place groups knn_scan_ht always loads per slice (images are padded for it)
+constexpr int kHistBins = 4096;         // bins of a similarity histogram (knn_single.h, knn_large.hip: asserted there)
+constexpr int kCollectCap = 8192;       // entries of a collect list (knn_single.h)
 constexpr int kHtColdBytes = 512;       // device buffer of the launch's HtCold (>= sizeof(HtCold), asserted in knn.hip)
 }  // namespace cfg
 
@@ -71,6 +73,27 @@ struct HtIndex {
     DevBuf<uint32_t> hits, off;
     DevBuf<int64_t> tile_base;
     DevBuf<int32_t> err;
+};
+
+// What a handle needs to serve visitors (rating vectors that are no rows of the index; knn_visitors.h): the builders
+// leave new_of_old as their last step, everything else grows with the visitors calls and is freed with the handle.
+struct KnnVisitorSide {
+    // the popularity renumbering of the place dimensions (old index -> stored index), p null: the index stores the
+    // caller's indices
+    DevBuf<int32_t> new_of_old;
+    bool renumbered() const { return new_of_old.p != nullptr; }
+    // the stage (grow-only): the visitors' vectors as the scan's fill reads them, their lengths, their vector norms
+    DevBuf<int64_t> bounds_p, bounds_c;
+    DevBuf<int32_t> idx_p, idx_c, lens;
+    DevBuf<double> val_p, val_c, norm_p, norm_c;
+    DevBuf<unsigned long long> report;  // [2]: the first refusal, the entries beyond the dimensions
+    // host arrays on their way in (grow-only)
+    DevBuf<int64_t> in_ptr_p, in_ptr_c;
+    DevBuf<int32_t> in_idx_p, in_idx_c;
+    DevBuf<double> in_val_p, in_val_c;
+    std::vector<int32_t> h_lens;        // host copy of lens: [2][nv]
+    // the ranked form's call-local arrays (grow-only)
+    DevBuf<int64_t> rk_in, rk_out;
 };
 
 }  // namespace locrec
@@ -132,7 +155,6 @@ struct locrec_knn_index {
     DevBuf<int64_t> lkb_place;
     std::vector<int64_t> lkb_off;   // [nq + 1] offsets of the resident result, in processing order
     bool have_lkb = false;          // a batched large-K result is resident (locrec_knn_fetch_recommend)
-    bool lkb_deferred = false;      // ... or 1024 < K < N - 1: the queries are served one by one at fetch time
     // per-row format fallback (knn_build.hip): rows that by themselves break the head / tail form's legality (a count of
     // 256 or more, a sum of squares of 65,536 or more) are all padding in the packed images; the side kernels of knn.hip
     // score them from the plain CSR.  Empty when the index has none (or too many: then the whole index is demoted).
@@ -157,7 +179,6 @@ struct locrec_knn_index {
     // workspaces (grow-only)
     DevBuf<int32_t> qrows;
     DevBuf<int32_t> qrows_patch;  // a batch's query rows with the too-long ones replaced (enqueue_topk)
-    std::vector<int32_t> qrows_host;  // host image of qrows (list forms): the head / tail pre-pass is sized from it
     DevBuf<double> part_s;
     DevBuf<uint32_t> part_rid;
     DevBuf<int32_t> part_cnt;
@@ -218,10 +239,11 @@ struct locrec_knn_index {
     bool no_fast = false;         // LOCREC_KNN_NO_FAST: synchronous insertion in every slice
     bool last_scan_fast = false;
     DevBuf<int32_t> scan_overflow;  // queue overflows of the last tiled scan (fast path)
-    struct TiledRequest {
+    struct TiledRequest {  // the last tiled scan, as rerun_tiled_sync repeats it
         const int32_t *qrows_dev;
         int32_t qrow0;
         int64_t nq;
+        std::vector<int32_t> qrows;  // the host image of qrows_dev (empty for a range)
         int max_p, max_c;
         double pw, cw;
         int64_t k;
@@ -243,6 +265,7 @@ struct locrec_knn_index {
     int32_t agg_first = 0;      // its first internal row (range form), or -1 when rows came from agg_rows
     std::vector<int32_t> agg_rows;  // query rows of the batch form, in processing order
     double agg_pw = 0, agg_cw = 0;
+    locrec::KnnVisitorSide visitors;  // visitor state of the handle (locrec_knn_visitors_*, the pools' visitors calls)
     KernelProfile prof;
     // plan of the last batched scan (locrec_knn_scan_plan): kernel 1 = knn_scan (row scan over a hashed /
     // direct query panel), 2 = knn_scan_ht (dense head panel + inverted tail), 3 = knn_scan MODE 3; mode 0/1/2 = GENERIC/PACK32/PACK16
@@ -252,6 +275,34 @@ struct locrec_knn_index {
 };
 
 namespace locrec {
+
+// Raise a kernel's dynamic LDS limit when a launch needs more than the 64 KiB every kernel may use without asking.
+// once: a handle's "already set" flag, for a kernel whose need is a constant - set at the first launch, never again.
+template <class Kern>
+inline int32_t knn_raise_lds_limit(Kern kern, size_t lds, bool *once = nullptr)
+{
+    if (once ? *once : lds <= 64 * 1024) return LOCREC_OK;
+    LOCREC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (once) *once = true;
+    return LOCREC_OK;
+}
+
+// The per-column workspaces of a tile of 16 queries (enqueue_topk's special queries, knn_large.hip's tiled selection):
+// histograms, selection records, collect lists, result slots, overflow flags.  Every selection leaves the histograms and
+// the selection records clean behind itself; the first use cleans them here.
+inline int32_t knn_tile_workspaces(locrec_knn_index *ix)
+{
+    if (ix->tile_hist.p) return LOCREC_OK;
+    LOCREC_TRY(ix->tile_hist.alloc((size_t)16 * cfg::kHistBins));
+    LOCREC_TRY(ix->tile_sel.alloc(16 * 8));
+    LOCREC_TRY(ix->tile_list_s.alloc((size_t)16 * cfg::kCollectCap));
+    LOCREC_TRY(ix->tile_list_r.alloc((size_t)16 * cfg::kCollectCap));
+    LOCREC_TRY(ix->tile_slots.alloc(16));
+    LOCREC_TRY(ix->tile_ovf.alloc(16));
+    LOCREC_HIP_TRY(hipMemsetAsync(ix->tile_hist.p, 0, ix->tile_hist.bytes(), ix->stream));
+    LOCREC_HIP_TRY(hipMemsetAsync(ix->tile_sel.p, 0, ix->tile_sel.bytes(), ix->stream));
+    return LOCREC_OK;
+}
 
 // knn.hip: the LOCREC_KNN_* tuning switches of a new handle
 void knn_read_env(locrec_knn_index *ix);

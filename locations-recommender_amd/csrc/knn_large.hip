@@ -1114,24 +1114,12 @@ __global__ __launch_bounds__(256) void lkt_mask_rows(const double *ST, int32_t n
 
 namespace locrec {
 
-// the per-column workspaces of a tile, as enqueue_topk (knn.hip) allocates them for its special queries: histograms
-// and selection records are left clean by every selection
+// the per-column workspaces of a tile (knn_index.h: shared with enqueue_topk's special queries), and lkt_sort_runs' LDS
+static_assert(kLkHistBins == cfg::kHistBins, "knn_large.hip restates cfg::kHistBins");
 static int32_t lkt_tile_workspaces(locrec_knn_index *ix)
 {
-    hipStream_t s = ix->stream;
-    if (!ix->tile_hist.p) {
-        LOCREC_TRY(ix->tile_hist.alloc((size_t)16 * kLkHistBins));
-        LOCREC_TRY(ix->tile_sel.alloc(16 * 8));
-        LOCREC_TRY(ix->tile_list_s.alloc((size_t)16 * 8192));
-        LOCREC_TRY(ix->tile_list_r.alloc((size_t)16 * 8192));
-        LOCREC_TRY(ix->tile_slots.alloc(16));
-        LOCREC_TRY(ix->tile_ovf.alloc(16));
-        LOCREC_HIP_TRY(hipMemsetAsync(ix->tile_hist.p, 0, ix->tile_hist.bytes(), s));
-        LOCREC_HIP_TRY(hipMemsetAsync(ix->tile_sel.p, 0, ix->tile_sel.bytes(), s));
-    }
-    LOCREC_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(lkt_sort_runs), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       kLktRun * 12));
-    return LOCREC_OK;
+    LOCREC_TRY(knn_tile_workspaces(ix));
+    return knn_raise_lds_limit(lkt_sort_runs, (size_t)kLktRun * 12);
 }
 
 // The top-K of the nt columns of the tile knn_large_scan_tile just left in ix->lkb_S: selection, collect, sort, merge.

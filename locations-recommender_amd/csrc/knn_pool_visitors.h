@@ -179,10 +179,10 @@ int32_t knn_pool_visitors_stage(KnnPoolVisitors *pv, int device, hipStream_t s, 
     LOCREC_TRY(pv->report.reserve(2));
     LOCREC_TRY(pv->member_of.reserve(psz.member_of));
     LOCREC_TRY(pv->members.reserve(psz.members * sizeof(KpvMember)));
-    // the members' table (a member nobody asks has no side record here: its row is never read) and the visitors' members
+    // the members' table (the row of a member nobody asks is never read) and the visitors' members
     std::vector<KpvMember> tab(members.size());
     for (size_t m = 0; m < members.size(); ++m) {
-        tab[m].new_of_old = members[m].side ? members[m].side->new_of_old.p : nullptr;
+        tab[m].new_of_old = members[m].asked ? members[m].ix->visitors.new_of_old.p : nullptr;
         tab[m].dim[0] = members[m].ix->fp.dim;
         tab[m].dim[1] = members[m].ix->fc.dim;
     }

@@ -2,7 +2,6 @@
 // knn_large.hip) as the entry points of knn_batch.hip (locrec_knn_pool_visitors_*, knn_pool_visitors_entry.h) see it.
 #pragma once
 
-#include <memory>
 #include <vector>
 
 #include "knn_index.h"
@@ -35,10 +34,10 @@ struct KnnPoolVisitors;
 KnnPoolVisitors *knn_pool_visitors_create();
 void knn_pool_visitors_destroy(KnnPoolVisitors *pv);
 
-// an asked member during one call: the side record is held for the call (its new_of_old is read by the stage)
+// a member during one call: an asked one's visitor state (its new_of_old) is read by the stage, nobody touches the others'
 struct KnnPoolVisitorsMember {
     locrec_knn_index *ix;
-    std::shared_ptr<KnnVisitorSide> side;  // null: nobody asks the member
+    bool asked;
 };
 
 // Checks and stages every visitor of every member in ONE launch (lkv_stage_pool) on the pool's stream: visitor i is

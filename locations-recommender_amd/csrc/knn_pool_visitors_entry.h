@@ -16,8 +16,7 @@ static_assert(locrec::kPoolVisitorsBatchMaxK == LOCREC_KNN_BATCH_MAX_K, "knn_poo
 
 namespace {
 
-// One pool-visitors call: its visitors sorted out (knn_pool_visitors_plan.h), the asked members with their side records
-// held, the sharing members' batches and every visitor's rows in the pool's buffers
+// One pool-visitors call: its visitors sorted out (knn_pool_visitors_plan.h), the asked members marked, the sharing members' batches and every visitor's rows in the pool's buffers
 struct KnnPoolVisitorsCall : locrec::KnnPoolVisitorsPlan {
     std::vector<locrec::KnnPoolVisitorsMember> members;
     std::vector<locrec::KnnPoolVisitorsBatch> batches;
@@ -52,19 +51,11 @@ int32_t knn_pool_visitors_begin(locrec_knn_pool *pool, const locrec::KnnVisitorV
     if (nv == 0) return LOCREC_OK;
     call.members.resize((size_t)nm);
     for (int32_t m = 0; m < nm; ++m) call.members[(size_t)m].ix = pool->members[(size_t)m];
-    for (int64_t i = 0; i < nv; ++i) {
-        locrec::KnnPoolVisitorsMember &m = call.members[(size_t)index_of[i]];
-        if (m.side) continue;
-        m.side = locrec::knn_visitors_side(m.ix);
-        if (!m.side) {
-            if (out_bad) *out_bad = i;
-            return fail(LOCREC_E_INVALID_ARG, "index %d of the pool has no record for visitors", index_of[i]);
-        }
-    }
+    for (int64_t i = 0; i < nv; ++i) call.members[(size_t)index_of[i]].asked = true;
     LOCREC_HIP_TRY(hipSetDevice(pool->device));
     if (!pool->visitors) pool->visitors = locrec::knn_pool_visitors_create();
     for (const auto &m : call.members)
-        if (m.side) knn_visitors_forget(m.ix);
+        if (m.asked) knn_visitors_forget(m.ix);
     LOCREC_TRY(locrec::knn_pool_visitors_stage(pool->visitors, pool->device, pool->stream, call.members, index_of, v, out_bad));
     std::vector<locrec::KnnPoolVisitorsWay> way((size_t)nm);
     for (int32_t m = 0; m < nm; ++m) way[(size_t)m] = locrec::knn_pool_visitors_way(k, pool->members[(size_t)m]->n);

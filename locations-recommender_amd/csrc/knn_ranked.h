@@ -8,7 +8,7 @@
 // settled when it returns.  Queries whose aggregation overflowed its block (agg_overflow) have no resident rows:
 // knn_large_recommend assembles them on the host, as the row fetch does - in one pass, their row counts being known
 // from the fetch - and they are uploaded and ranked as segments of a second ranker call (counted as host-assembled in
-// the stats).  (The fetch's own count-and-discard passes over those queries are inside knn.hip, whose bytes are hashed.)
+// the stats).  (The fetch's own count-and-discard passes over those queries stay as they are: locrec_knn_fetch_recommend.)
 // The unvisited forms (locrec_knn_recommend_ranked_batch_unvisited, locrec_knn_fetch_ranked_unvisited) recommend only new
 // places: both ranker calls get, per segment, the place ids of the person's rating rows as an exclusion list - begins and
 // lengths into ix->r_place, filled on the device from ix->r_ptr (knn_rk_rated_ranges, 8 VGPRs, no LDS, no scratch).
@@ -93,7 +93,6 @@ int32_t knn_rank_resident(locrec_knn_index *ix, const std::vector<int64_t> &slot
     LOCREC_HIP_TRY(hipSetDevice(ix->device));
     hipStream_t s = ix->stream;
     const bool lkb = ix->have_lkb;
-    if (lkb && ix->lkb_deferred) return fail(LOCREC_E_INVALID_ARG, "the batch's rows are not resident");
     std::vector<int32_t> ovf((size_t)nq, 0);
     if (!lkb) {
         LOCREC_HIP_TRY(hipMemcpyAsync(ovf.data(), ix->agg_overflow.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s));

@@ -1,6 +1,6 @@
 // knn_visitors.h -- KNN for visitors: rating vectors that are no rows of the index (locrec_knn_visitors_*,
-// knn_visitors_api.h).  Included at the end of knn_large.hip: the kernels and the tile drivers, and the registry of the
-// handles' side records (knn_visitors_side.h).
+// knn_visitors_api.h).  Included at the end of knn_large.hip: the kernels and the tile drivers over the handle's
+// visitor state (knn_index.h: KnnVisitorSide; knn_visitors_side.h).
 //
 // For a visitor v and an index built from the persons P every result equals what the person calls return for v on an
 // index built from P + {v}: v is a candidate of nobody, nobody is left out as "self", v has no rating rows.  The path is
@@ -34,9 +34,6 @@
 //   lkv_scan    112 / 64 / 0 / 4   (+ the bitmap, dynamic: at most 32 KB) - lkb_scan's figures
 // (unchanged with their bodies as functions - lkv_stage_body, lkv_scan_body - which the pool's kernels call too:
 // knn_pool_visitors.h)
-
-#include <mutex>
-#include <unordered_map>
 
 #include "knn_visitors_side.h"
 
@@ -185,29 +182,6 @@ __global__ __launch_bounds__(256) void lkv_scan(const LkvScan V)
     lkv_scan_body<false>(V.P, V.P.cand, V.vnorm_p, V.vnorm_c, V.nt, (int)blockIdx.x);
 }
 
-// the handles' side records; never destroyed with the process (no device call after the runtime is gone)
-std::mutex &lkv_registry_mutex()
-{
-    static std::mutex *m = new std::mutex;
-    return *m;
-}
-std::unordered_map<const locrec_knn_index *, std::shared_ptr<locrec::KnnVisitorSide>> &lkv_registry()
-{
-    static auto *r = new std::unordered_map<const locrec_knn_index *, std::shared_ptr<locrec::KnnVisitorSide>>;
-    return *r;
-}
-
-void lkv_register(const locrec_knn_index *ix, std::shared_ptr<locrec::KnnVisitorSide> side)
-{
-    std::shared_ptr<locrec::KnnVisitorSide> old;  // (freed outside the lock)
-    {
-        std::lock_guard<std::mutex> g(lkv_registry_mutex());
-        auto &slot = lkv_registry()[ix];
-        old = std::move(slot);
-        slot = std::move(side);
-    }
-}
-
 int32_t lkv_device_array(const void *p, int device, const char *what)
 {
     hipPointerAttribute_t a;
@@ -228,45 +202,6 @@ KnnVisitorsStats &knn_visitors_stats()
 {
     thread_local KnnVisitorsStats st;
     return st;
-}
-
-int32_t knn_visitors_attach(const locrec_knn_index *ix, DevBuf<int32_t> &new_of_old)
-{
-    auto side = std::make_shared<KnnVisitorSide>();
-    std::swap(side->new_of_old.p, new_of_old.p);
-    std::swap(side->new_of_old.n, new_of_old.n);
-    lkv_register(ix, std::move(side));
-    return LOCREC_OK;
-}
-
-int32_t knn_visitors_attach_host(const locrec_knn_index *ix, const std::vector<int32_t> &new_of_old)
-{
-    auto side = std::make_shared<KnnVisitorSide>();
-    if (!new_of_old.empty()) {
-        LOCREC_TRY(side->new_of_old.upload(new_of_old, ix->stream));
-        LOCREC_HIP_TRY(hipStreamSynchronize(ix->stream));
-    }
-    lkv_register(ix, std::move(side));
-    return LOCREC_OK;
-}
-
-std::shared_ptr<KnnVisitorSide> knn_visitors_side(const locrec_knn_index *ix)
-{
-    std::lock_guard<std::mutex> g(lkv_registry_mutex());
-    const auto it = lkv_registry().find(ix);
-    return it == lkv_registry().end() ? nullptr : it->second;
-}
-
-void knn_visitors_drop(const locrec_knn_index *ix)
-{
-    std::shared_ptr<KnnVisitorSide> old;
-    {
-        std::lock_guard<std::mutex> g(lkv_registry_mutex());
-        const auto it = lkv_registry().find(ix);
-        if (it == lkv_registry().end()) return;
-        old = std::move(it->second);
-        lkv_registry().erase(it);
-    }
 }
 
 // the refusal the stage's report word stands for (lkv_stage, lkv_stage_pool): *bad = the visitor, the family's message

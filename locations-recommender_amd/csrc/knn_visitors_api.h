@@ -1,4 +1,4 @@
-// knn_visitors_api.h -- the entry points for visitors (locrec_knn_visitors_*) and locrec_knn_destroy; a fragment of
+// knn_visitors_api.h -- the entry points for visitors (locrec_knn_visitors_*); a fragment of
 // knn_batch.hip's translation unit (behind knn.hip, knn_ranked.h).  The kernels and the tile drivers are knn_visitors.h's
 // (compiled with knn_large.hip), every size and regime decision knn_visitors_plan.h's.
 //
@@ -9,15 +9,6 @@
 
 #include "knn_visitors_side.h"
 #include "rank_batch.h"
-
-extern "C" int32_t locrec_knn_destroy(locrec_knn_index *ix) try
-{
-    if (!ix) return LOCREC_OK;
-    (void)hipSetDevice(ix->device);
-    if (ix->stream) (void)hipStreamSynchronize(ix->stream);
-    locrec::knn_visitors_drop(ix);
-    return knn_destroy_handle(ix);
-} LOCREC_CATCH_ALL
 
 namespace {
 
@@ -30,15 +21,14 @@ void knn_visitors_forget(locrec_knn_index *ix)
     ix->last_scan_fast = false;
     ix->have_agg = false;
     ix->have_lkb = false;
-    ix->lkb_deferred = false;
 }
 
 // The beginning of every visitors call: the arguments (outputs_ok: the entry's own; more_args: further argument checks of
-// the entry, before the requires), check_params, then the stage with its per-visitor refusals.  *side stays null when
-// there is nothing to do (nv == 0, or an index without persons).
+// the entry, before the requires), check_params, then the stage with its per-visitor refusals into the handle's visitor state
+// (ix->visitors).
 template <class F>
 int32_t knn_visitors_begin(locrec_knn_index *ix, const locrec::KnnVisitorVectors &v, double pw, double cw, int64_t k, bool outputs_ok,
-                           int64_t *out_bad, F more_args, std::shared_ptr<locrec::KnnVisitorSide> &side)
+                           int64_t *out_bad, F more_args)
 {
     if (out_bad) *out_bad = -1;
     locrec::knn_visitors_stats() = locrec::KnnVisitorsStats();
@@ -51,18 +41,14 @@ int32_t knn_visitors_begin(locrec_knn_index *ix, const locrec::KnnVisitorVectors
     LOCREC_TRY(more_args());
     LOCREC_TRY(check_params(pw, cw, k));
     if (v.nv == 0) return LOCREC_OK;
-    side = locrec::knn_visitors_side(ix);
-    if (!side) return fail(LOCREC_E_INVALID_ARG, "the index has no record for visitors");
     LOCREC_HIP_TRY(hipSetDevice(ix->device));
-    const int32_t rc = locrec::knn_visitors_stage(ix, *side, v, out_bad);
-    if (rc != LOCREC_OK) side.reset();
-    return rc;
+    return locrec::knn_visitors_stage(ix, ix->visitors, v, out_bad);
 }
 
 int32_t knn_visitors_no_more_args() { return LOCREC_OK; }
 
 // the recommendation rows of the staged visitors, resident in lkb_place / lkb_est / lkb_off (an index without persons: none)
-int32_t knn_visitors_rows(locrec_knn_index *ix, locrec::KnnVisitorSide &side, int64_t nv, double pw, double cw, int64_t k)
+int32_t knn_visitors_rows(locrec_knn_index *ix, int64_t nv, double pw, double cw, int64_t k)
 {
     const int64_t worst = locrec::knn_visitors_worst_row_bytes(nv, (int64_t)ix->cplace_ids.size());
     if (worst > locrec::kVisitorsMaxRowBytes)
@@ -72,7 +58,7 @@ int32_t knn_visitors_rows(locrec_knn_index *ix, locrec::KnnVisitorSide &side, in
         ix->lkb_off.assign((size_t)nv + 1, 0);
         return LOCREC_OK;
     }
-    return locrec::knn_visitors_recommend(ix, side, nv, pw, cw, k);
+    return locrec::knn_visitors_recommend(ix, ix->visitors, nv, pw, cw, k);
 }
 
 }  // namespace
@@ -83,10 +69,9 @@ extern "C" int32_t locrec_knn_visitors_query_batch(locrec_knn_index *ix, int64_t
                                                    int64_t *out_ids, double *out_sims, int64_t *out_counts,
                                                    int64_t *out_bad_visitor) try
 {
-    std::shared_ptr<locrec::KnnVisitorSide> side;
     const locrec::KnnVisitorVectors v{nv, p_rowptr, p_idx, p_val, c_rowptr, c_idx, c_val, mem};
     LOCREC_TRY(knn_visitors_begin(ix, v, pw, cw, k, nv <= 0 || (out_ids && out_sims && out_counts), out_bad_visitor,
-                                  knn_visitors_no_more_args, side));
+                                  knn_visitors_no_more_args));
     if (nv == 0) return LOCREC_OK;
     if (ix->n == 0) {  // nobody to be similar to
         std::fill(out_ids, out_ids + nv * k, (int64_t)-1);
@@ -100,7 +85,7 @@ extern "C" int32_t locrec_knn_visitors_query_batch(locrec_knn_index *ix, int64_t
     int32_t rc = LOCREC_OK;
     for (int64_t v0 = 0; v0 < nv && rc == LOCREC_OK; v0 += chunk) {
         const int64_t cn = std::min(chunk, nv - v0);
-        rc = locrec::knn_visitors_topk(ix, *side, v0, cn, pw, cw, k);
+        rc = locrec::knn_visitors_topk(ix, ix->visitors, v0, cn, pw, cw, k);
         if (rc != LOCREC_OK) break;
         LOCREC_HIP_TRY(hipMemcpyAsync(out_ids + v0 * k, ix->out_ids.p, (size_t)(cn * k) * 8, hipMemcpyDeviceToHost, s));
         LOCREC_HIP_TRY(hipMemcpyAsync(out_sims + v0 * k, ix->out_sims.p, (size_t)(cn * k) * 8, hipMemcpyDeviceToHost, s));
@@ -117,15 +102,14 @@ extern "C" int32_t locrec_knn_visitors_recommend_batch(locrec_knn_index *ix, int
                                                        int64_t k, int64_t *out_offsets, int64_t *out_places, double *out_ratings,
                                                        int64_t *inout_capacity, int64_t *out_bad_visitor) try
 {
-    std::shared_ptr<locrec::KnnVisitorSide> side;
     const locrec::KnnVisitorVectors v{nv, p_rowptr, p_idx, p_val, c_rowptr, c_idx, c_val, mem};
-    LOCREC_TRY(knn_visitors_begin(ix, v, pw, cw, k, out_offsets && inout_capacity, out_bad_visitor, knn_visitors_no_more_args, side));
+    LOCREC_TRY(knn_visitors_begin(ix, v, pw, cw, k, out_offsets && inout_capacity, out_bad_visitor, knn_visitors_no_more_args));
     if (nv == 0) {
         out_offsets[0] = 0;
         *inout_capacity = 0;
         return LOCREC_OK;
     }
-    LOCREC_TRY(knn_visitors_rows(ix, *side, nv, pw, cw, k));
+    LOCREC_TRY(knn_visitors_rows(ix, nv, pw, cw, k));
     hipStream_t s = ix->stream;
     std::copy(ix->lkb_off.begin(), ix->lkb_off.begin() + nv + 1, out_offsets);
     const int64_t total = out_offsets[nv], cap = *inout_capacity;
@@ -147,7 +131,6 @@ extern "C" int32_t locrec_knn_visitors_recommend_ranked_batch(
     int64_t *out_counts, int64_t *out_bad_visitor) try
 {
     const int64_t N = std::max<int64_t>(0, max_recommendations);
-    std::shared_ptr<locrec::KnnVisitorSide> side;
     const locrec::KnnVisitorVectors v{nv, p_rowptr, p_idx, p_val, c_rowptr, c_idx, c_val, mem};
     int64_t n_ex = 0;
     const auto rank_args = [&]() -> int32_t {
@@ -165,9 +148,9 @@ extern "C" int32_t locrec_knn_visitors_recommend_ranked_batch(
         if (n_ex > 0 && !exclude_place_ids) return fail(LOCREC_E_INVALID_ARG, "NULL argument");
         return LOCREC_OK;
     };
-    LOCREC_TRY(knn_visitors_begin(ix, v, pw, cw, k, true, out_bad_visitor, rank_args, side));
+    LOCREC_TRY(knn_visitors_begin(ix, v, pw, cw, k, true, out_bad_visitor, rank_args));
     if (nv == 0) return LOCREC_OK;
-    LOCREC_TRY(knn_visitors_rows(ix, *side, nv, pw, cw, k));
+    LOCREC_TRY(knn_visitors_rows(ix, nv, pw, cw, k));
     hipStream_t s = ix->stream;
     if (ix->lkb_off[(size_t)nv] == 0) {  // no rows at all (an index without persons or ratings has no row buffer either)
         std::fill(out_place_ids, out_place_ids + nv * N, (int64_t)-1);
@@ -192,6 +175,7 @@ extern "C" int32_t locrec_knn_visitors_recommend_ranked_batch(
         }
     }
     if (n_ex > 0) std::copy(exclude_place_ids, exclude_place_ids + n_ex, hin.begin() + (ptrdiff_t)(io_words + 2 * (size_t)nv));
+    locrec::KnnVisitorSide *side = &ix->visitors;
     LOCREC_TRY(side->rk_in.reserve(hin.size()));
     LOCREC_TRY(side->rk_out.reserve(RankIo::out_words(nv, N)));
     const RankIo io(side->rk_in.p, side->rk_out.p, n_places, nv, N);

@@ -1,46 +1,15 @@
-// knn_visitors_side.h -- what a KNN handle needs to serve visitors (rating vectors that are no rows of the index) and has
-// no member for: the handle's layout is part of the hash that ties the committed counter record to the kernels it
-// measured, so it lives in a side record per handle - a registry keyed by the handle's address, under a mutex
-// (knn_visitors.h, compiled with knn_large.hip).  Both builders attach the record as the last step of a successful
-// build; locrec_knn_destroy (knn_batch.hip) drops it.
+// knn_visitors_side.h -- the visitors' path over a KNN handle (rating vectors that are no rows of the index): what
+// knn_visitors.h (compiled with knn_large.hip) offers the entry points of knn_batch.hip's unit.  The state itself -
+// KnnVisitorSide: the new_of_old renumbering and the stage buffers - is the handle's member `visitors` (knn_index.h);
+// both builders leave new_of_old there as the last step of a successful build, and it is freed with the handle.
 #pragma once
 
-#include <memory>
 #include <vector>
 
 #include "knn_index.h"
 #include "knn_visitors_plan.h"
 
 namespace locrec {
-
-struct KnnVisitorSide {
-    // the popularity renumbering of the place dimensions (old index -> stored index), p null: the index stores the
-    // caller's indices
-    DevBuf<int32_t> new_of_old;
-    bool renumbered() const { return new_of_old.p != nullptr; }
-    // the stage (grow-only): the visitors' vectors as the scan's fill reads them, their lengths, their vector norms
-    DevBuf<int64_t> bounds_p, bounds_c;
-    DevBuf<int32_t> idx_p, idx_c, lens;
-    DevBuf<double> val_p, val_c, norm_p, norm_c;
-    DevBuf<unsigned long long> report;  // [2]: the first refusal, the entries beyond the dimensions
-    // host arrays on their way in (grow-only)
-    DevBuf<int64_t> in_ptr_p, in_ptr_c;
-    DevBuf<int32_t> in_idx_p, in_idx_c;
-    DevBuf<double> in_val_p, in_val_c;
-    std::vector<int32_t> h_lens;        // host copy of lens: [2][nv]
-    // the ranked form's call-local arrays (grow-only)
-    DevBuf<int64_t> rk_in, rk_out;
-};
-
-// The record of a freshly built handle; replaces whatever is registered under the same address (a handle that was freed
-// without locrec_knn_destroy can leave nothing behind: only a finished build attaches).  new_of_old: p_dim device words
-// that become the record's (taken out of the DevBuf), or empty.
-int32_t knn_visitors_attach(const locrec_knn_index *ix, DevBuf<int32_t> &new_of_old);
-// the same from the host builder's map (empty: no renumbering)
-int32_t knn_visitors_attach_host(const locrec_knn_index *ix, const std::vector<int32_t> &new_of_old);
-// the handle's record, or null (a handle no builder of this library finished)
-std::shared_ptr<KnnVisitorSide> knn_visitors_side(const locrec_knn_index *ix);
-void knn_visitors_drop(const locrec_knn_index *ix);
 
 // what the last visitors call of this thread did (locrec_knn_visitors_stats)
 struct KnnVisitorsStats {

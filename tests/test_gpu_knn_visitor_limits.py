@@ -508,13 +508,14 @@ def test_inputs_are_read_only(pkg, index300):
         assert a.cpu().numpy().tobytes() == b.cpu().numpy().tobytes()
 
 
-# ---- j. the registry of side records --------------------------------------------------------------------------------------------
+# ---- j. the handles' visitor state ----------------------------------------------------------------------------------------------
 
 def test_side_records_of_handles_that_come_and_go(pkg):
-    """Bites: `lkv_registry().erase(it)` read as `erase(lkv_registry().begin())` in knn_visitors_drop (tried: closing the first
-    handle drops another's record: "the index has no record for visitors"), or dropped (the record and its device
-    arrays outlive the handle: device_bytes_in_use does not return); a record keyed by anything that two live handles
-    share (the second build's renumbering serves the first's visitors: other neighbours)."""
+    """Every handle owns its visitor state - the renumbering its builder left and the stage buffers - as a member
+    (knn_index.h: KnnVisitorSide), so handles that come and go, whatever addresses they get, serve their own visitors and
+    take their buffers with them.  Bites: the builder leaving `new_of_old` anywhere two live handles share, or not at all
+    (the second build's renumbering, or none, serves the first's visitors: other neighbours, `renumbered` 0); state that is
+    not freed with the handle (device_bytes_in_use does not return)."""
     from locations_recommender_amd import _lib as L, synth
     start = L.device_bytes_in_use()
     _, visitors = vc.base()

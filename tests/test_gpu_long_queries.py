@@ -128,3 +128,51 @@ def test_dense_query_scan_agrees_on_ordinary_data(pkg, oracle, monkeypatch):
             oids, osims = oracle.knn_similar(d, pid, 0.3, 0.7, 25)
             assert np.array_equal(ids, oids) and np.array_equal(sims, osims), (integer, negative, row)
         ix.close()
+
+
+@pytest.fixture(scope="module")
+def batch_sequence(oracle):
+    """The calls of test_no_state_is_carried_between_batches and the oracle's answers, computed once for both runs."""
+    d, long_rows = dataset_with_long_rows(5)
+    rng = np.random.default_rng(1)
+    others = np.setdiff1d(np.arange(len(d["person_ids"])), long_rows)
+    picked = rng.choice(others, 77, replace=False)
+    first = np.r_[picked[:37], long_rows]                     # 40 persons, the three long rows among them
+    second = picked[37:]                                      # 40 OTHER persons, no long row: same length, other rows
+    spot = np.unique(np.r_[np.arange(0, len(d["person_ids"]), 37), long_rows])
+    singles = [long_rows[1], int(second[0])]                  # a long row and a short one
+    k = 20
+    want = {"first": oracle.knn_similar_batch(d, first, 0.5, 0.5, k, nthreads=8),
+            "second": oracle.knn_similar_batch(d, second, 0.5, 0.5, k, nthreads=8),
+            "spot": oracle.knn_similar_batch(d, spot, 0.5, 0.5, k, nthreads=8),
+            "singles": [oracle.knn_similar(d, int(d["person_ids"][r]), 0.5, 0.5, k) for r in singles]}
+    return d, first, second, spot, singles, k, want
+
+
+@pytest.mark.parametrize("no_single", [False, True])
+def test_no_state_is_carried_between_batches(pkg, batch_sequence, monkeypatch, no_single):
+    """One index, in this order: a list batch with the three long rows, a list batch of the same length with other rows
+    and no long row, a range-form batch (all_pairs_topk), the first batch again, then single requests of a long and a
+    short row - every answer the oracle's bit for bit.  A batch's rows reach enqueue_topk with the call (QueryRows,
+    csrc/knn_topk_host.h) and nothing of them stays in the handle: a batch that was sized, split or patched from an
+    earlier batch's rows would answer for the wrong persons here.  Once more with LOCREC_KNN_NO_SINGLE, so that the
+    one-query cases take the tiled and the special phases as well."""
+    d, first, second, spot, singles, k, want = batch_sequence
+    if no_single:
+        monkeypatch.setenv("LOCREC_KNN_NO_SINGLE", "1")
+    ix = make_index(pkg, d)
+
+    def same(got, name):
+        oids, osims, ocnt = want[name]
+        ids, sims, cnt = got
+        assert np.array_equal(cnt, ocnt) and np.array_equal(ids, oids) and np.array_equal(sims, osims), name
+
+    same(ix.query_batch(d["person_ids"][first], 0.5, 0.5, k), "first")
+    same(ix.query_batch(d["person_ids"][second], 0.5, 0.5, k), "second")
+    ids, sims, cnt = ix.all_pairs_topk(0.5, 0.5, k)
+    same((ids[spot], sims[spot], cnt[spot]), "spot")
+    same(ix.query_batch(d["person_ids"][first], 0.5, 0.5, k), "first")
+    for row, (oids, osims) in zip(singles, want["singles"]):
+        ids, sims = ix.query(int(d["person_ids"][row]), 0.5, 0.5, k)
+        assert np.array_equal(ids, oids) and np.array_equal(sims, osims), row
+    ix.close()
