@@ -334,6 +334,28 @@ int32_t locrec_knn_recommend_ranked_batch_near(
     const double *center_latitudes, const double *center_longitudes, const double *radius_meters,
     int64_t max_recommendations, int32_t unvisited,
     int64_t *out_place_ids, double *out_estimated_ratings, double *out_meters, int64_t *out_counts);
+/*
+ * By category: locrec_knn_recommend_ranked_batch_near with the circles optional (all five coordinate arrays NULL:
+ * none, out_meters unused) and an allow-list of categories and a cap per category for every position
+ * (locrec_rank_recommendations_batch_by_category's semantics, requires and refusals; host arrays, checked before
+ * the index is looked at).  place_category_ids: one per row of the place table; allowed_offsets (nq + 1 entries,
+ * NULL: no lists), allowed_category_ids (n_allowed entries) and max_per_category (one per position, NULL: no caps)
+ * as there.  unvisited != 0: the _unvisited form's lists as well.  Both resident row forms and the second ranker
+ * call for host-assembled overflow queries go through the by-category ranker; a repeated person is ranked per
+ * position with its own list and cap.  With no lists and no cap below max_recommendations the result is the plain,
+ * unvisited or near call's.
+ */
+int32_t locrec_knn_recommend_ranked_batch_by_category(
+    locrec_knn_index *index, int64_t nq, const int64_t *person_ids,
+    double place_weight, double category_weight, int64_t k_nearest,
+    int64_t n_places, const int64_t *place_ids, const int64_t *place_region_ids,
+    const double *place_latitudes, const double *place_longitudes, const int64_t *place_category_ids,
+    const int64_t *target_region_ids,
+    const double *center_latitudes, const double *center_longitudes, const double *radius_meters,
+    int64_t max_recommendations, int32_t unvisited,
+    const int64_t *allowed_offsets, int64_t n_allowed, const int64_t *allowed_category_ids,
+    const int64_t *max_per_category,
+    int64_t *out_place_ids, double *out_estimated_ratings, double *out_meters, int64_t *out_counts);
 
 /*
  * A pool of resident indexes that serves ONE mixed batch of (index, person[, target region]) requests - the queue of
@@ -739,6 +761,30 @@ int32_t locrec_sg_recommend_ranked_batch_near(
     const double *center_latitudes, const double *center_longitudes, const double *radius_meters,
     int64_t max_recommendations,
     const int64_t *excluded_offsets, int64_t n_excluded, const int64_t *excluded_ids,
+    int64_t *out_ids, double *out_probabilities, double *out_meters, int64_t *out_counts,
+    int64_t *out_row_counts, int64_t *out_iterations, int32_t *out_converged);
+/*
+ * By category: locrec_sg_recommend_ranked_batch_near with the circles optional (all five coordinate arrays NULL:
+ * none, out_meters unused) and an allow-list of categories and a cap per category for every position
+ * (locrec_rank_recommendations_batch_by_category's semantics, requires and refusals; host arrays, checked before
+ * the graph is looked at).  place_category_ids: one per row of the place table; allowed_offsets (n_targets + 1
+ * entries, NULL: no lists), allowed_category_ids (n_allowed entries) and max_per_category (one per position, NULL:
+ * no caps) as there.  Lists and caps are uploaded once in emit order and every group's ranker call gets the
+ * sub-range of its segments: out_row_counts, iterations and converged are the plain call's, and the result does not
+ * depend on LOCREC_SG_RANKED_ROW_BUDGET.  A repeated vertex is iterated once and ranked per position with its own
+ * list and cap.
+ */
+int32_t locrec_sg_recommend_ranked_batch_by_category(
+    locrec_sg_graph *graph, int64_t n_targets, const int64_t *vertex_ids,
+    double alpha, double epsilon, int64_t max_iterations,
+    int64_t n_places, const int64_t *place_ids, const int64_t *place_region_ids,
+    const double *place_latitudes, const double *place_longitudes, const int64_t *place_category_ids,
+    const int64_t *target_region_ids,
+    const double *center_latitudes, const double *center_longitudes, const double *radius_meters,
+    int64_t max_recommendations,
+    const int64_t *excluded_offsets, int64_t n_excluded, const int64_t *excluded_ids,
+    const int64_t *allowed_offsets, int64_t n_allowed, const int64_t *allowed_category_ids,
+    const int64_t *max_per_category,
     int64_t *out_ids, double *out_probabilities, double *out_meters, int64_t *out_counts,
     int64_t *out_row_counts, int64_t *out_iterations, int32_t *out_converged);
 /*
@@ -1293,6 +1339,51 @@ int32_t locrec_rank_recommendations_batch_near(
     const double *center_latitudes, const double *center_longitudes, const double *radius_meters,
     int64_t max_recommendations,
     const int64_t *excluded_offsets, int64_t n_excluded, const int64_t *excluded_ids,
+    int32_t mem, int64_t *out_ids, double *out_scores, double *out_meters, int64_t *out_counts);
+
+/*
+ * By category: the same with an allow-list of categories and a cap per category for every segment - Spark's
+ * places.where(region_id === target && [distance <= radius] && [category_id isin allowed]) JOIN rows ON id, a
+ * place counting once, then row_number() OVER (PARTITION BY category ORDER BY score DESC, id, input row) <= cap,
+ * then ORDER BY score DESC, id, input row LIMIT max_recommendations.  This is
+ * locrec_rank_recommendations_batch_near's argument list with three changes: the five coordinate arrays and
+ * out_meters are optional (all five NULL: no circles, out_meters unused); place_category_ids, allowed_offsets,
+ * n_allowed, allowed_category_ids and max_per_category are added; `mem` covers every array.
+ * place_category_ids: one int64 per row of the place table, any value.  A place listed several times in the
+ * target region passes if some listing passes every predicate given (region, circle, allow-list); the listing
+ * that counts is the first passing one in the table's input order: its category is the row's category for the
+ * cap, its distance the row's out_meters.  The allow-lists are a CSR, segment s's being
+ * allowed_category_ids[allowed_offsets[s] .. allowed_offsets[s + 1]) of n_allowed < 2^31 entries:
+ * allowed_offsets == NULL is no lists (n_allowed, allowed_category_ids unused), an empty list allows every
+ * category, a list may be unsorted, repeat a category and name categories no place has, and a list none of whose
+ * categories occurs in the region gives count 0; allowed_offsets takes the rules and the refusal of
+ * excluded_offsets, inside [0, n_allowed].  max_per_category: one int64 >= 1 per segment, NULL: no caps.  A row is
+ * eligible iff fewer than max_per_category[s] kept rows of its category precede it in the order (score desc, id
+ * asc, input row asc); the output is the first max_recommendations eligible rows in that order.  Rows are rows: an
+ * id repeated inside a segment counts twice.  A cap >= max_recommendations is no cap.  With no lists and every cap
+ * NULL or >= max_recommendations the call runs the plain, excluding or near call's kernels and its ids, score
+ * bits, counts, out_meters and stats are theirs bit for bit.
+ * Up to LOCREC_RANK_BATCH_MAX_N a capped segment is selected in an LDS list whose entries carry their category: a
+ * compaction orders the buffer by (category, score, id, row), drops every entry with `cap` entries of its category
+ * in front of it, then keeps the best max_recommendations of the rest - exact, since the eligible rows in front of
+ * a row can only grow; a larger limit takes one more radix pass by (segment, category) behind the three.  Any limit
+ * gives the same answer.
+ * LOCREC_E_INVALID_ARG and nothing written, the message naming the argument: a max_per_category <= 0;
+ * place_category_ids NULL with n_places > 0 and lists or caps given; allowed_offsets that break the offset rules;
+ * n_allowed outside [0, 2^31); allowed_category_ids NULL with n_allowed > 0; and every refusal of
+ * locrec_rank_recommendations_batch_near.  Host arrays are checked on the host before any device work, device
+ * arrays on the device before any row is read.  At most 3 host synchronisations.
+ */
+int32_t locrec_rank_recommendations_batch_by_category(
+    int64_t n_segments, const int64_t *offsets, int64_t n, const int64_t *ids, const double *scores,
+    int64_t n_places, const int64_t *place_ids, const int64_t *place_region_ids,
+    const double *place_latitudes, const double *place_longitudes, const int64_t *place_category_ids,
+    const int64_t *target_region_ids,
+    const double *center_latitudes, const double *center_longitudes, const double *radius_meters,
+    int64_t max_recommendations,
+    const int64_t *excluded_offsets, int64_t n_excluded, const int64_t *excluded_ids,
+    const int64_t *allowed_offsets, int64_t n_allowed, const int64_t *allowed_category_ids,
+    const int64_t *max_per_category,
     int32_t mem, int64_t *out_ids, double *out_scores, double *out_meters, int64_t *out_counts);
 
 /* What the last ranked batch of this thread did (locrec_rank_recommendations_batch and the ranked KNN

@@ -78,6 +78,10 @@ SIGNATURES = {
     "locrec_knn_recommend_ranked_batch_near": [C.c_void_p, C.c_int64, _i64p, C.c_double, C.c_double, C.c_int64,
                                                C.c_int64, _i64p, _i64p, _f64p, _f64p, _i64p, _f64p, _f64p, _f64p, C.c_int64,
                                                C.c_int32, _i64p, _f64p, _f64p, _i64p],
+    "locrec_knn_recommend_ranked_batch_by_category": [C.c_void_p, C.c_int64, _i64p, C.c_double, C.c_double, C.c_int64,
+                                                      C.c_int64, _i64p, _i64p, _f64p, _f64p, _i64p, _i64p, _f64p, _f64p, _f64p,
+                                                      C.c_int64, C.c_int32, _i64p, C.c_int64, _i64p, _i64p, _i64p, _f64p, _f64p,
+                                                      _i64p],
     "locrec_knn_query_shard": [C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int64, C.c_int32, C.c_int32,
                                _i64p, _f64p, _i64p],
     "locrec_knn_recommend_neighbours": [C.c_void_p, C.c_int64, _i64p, _f64p, _i64p, _f64p, _i64p],
@@ -109,6 +113,10 @@ SIGNATURES = {
     "locrec_sg_recommend_ranked_batch_near": [C.c_void_p, C.c_int64, _i64p, C.c_double, C.c_double, C.c_int64,
                                               C.c_int64, _i64p, _i64p, _f64p, _f64p, _i64p, _f64p, _f64p, _f64p, C.c_int64,
                                               _i64p, C.c_int64, _i64p, _i64p, _f64p, _f64p, _i64p, _i64p, _i64p, _i32p],
+    "locrec_sg_recommend_ranked_batch_by_category": [C.c_void_p, C.c_int64, _i64p, C.c_double, C.c_double, C.c_int64,
+                                                     C.c_int64, _i64p, _i64p, _f64p, _f64p, _i64p, _i64p, _f64p, _f64p, _f64p,
+                                                     C.c_int64, _i64p, C.c_int64, _i64p, _i64p, C.c_int64, _i64p, _i64p, _i64p,
+                                                     _f64p, _f64p, _i64p, _i64p, _i64p, _i32p],
     "locrec_sg_recommend_ranked_batch_stats": [_i64p, _i64p, _i64p, _i64p, _i64p],
     "locrec_sg_visitors_recommend_batch": [C.c_void_p, C.c_int64, _i64p, _i64p, _f64p, C.c_double, C.c_double, C.c_int64,
                                            _i64p, _i64p, _f64p, _i64p, _i64p, _i32p, _i64p],
@@ -226,6 +234,11 @@ SIGNATURES = {
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p],
+    "locrec_rank_recommendations_batch_by_category": [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p],
     "locrec_rank_recommendations_batch_stats": [_i64p, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p],
     # offline evaluation (eval.hip): cutoffs, means, coverage and the counts are host arrays
     "locrec_eval_ranked_batch": [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, _i64p,

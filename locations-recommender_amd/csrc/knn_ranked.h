@@ -16,6 +16,10 @@
 // place row its coordinates, uploaded behind the RankIo's other inputs; both ranker calls are the near ranker's
 // (rank_segments_device_near), the hosted segments taking their positions' circles, and out_meters comes back with the
 // rows.  Its host arrays are checked before the index is looked at.
+// The by-category form (locrec_knn_recommend_ranked_batch_by_category) adds an allow-list of categories and a cap per
+// category to every position, with the circles optional: the place categories, the lists and the caps are uploaded
+// behind the other inputs (RankCatHost), both ranker calls are rank_segments_device_by_category, and the hosted
+// segments take their positions' lists and caps.
 #pragma once
 
 #include "rank_batch.h"
@@ -80,7 +84,7 @@ int32_t knn_rank_resident(locrec_knn_index *ix, const std::vector<int64_t> &slot
                           int64_t n_places,
                           const int64_t *place_ids, const int64_t *place_region_ids, const int64_t *targets,
                           int64_t max_recommendations, int64_t *out_ids, double *out_scores, int64_t *out_counts,
-                          const KnnRankNear *near = nullptr)
+                          const KnnRankNear *near = nullptr, const RankCatHost *catq = nullptr)
 {
     const int64_t nseg = (int64_t)slots.size(), nq = ix->last_nq;
     const int64_t N = std::max<int64_t>(0, max_recommendations);
@@ -120,9 +124,14 @@ int32_t knn_rank_resident(locrec_knn_index *ix, const std::vector<int64_t> &slot
     // one allocation for the call's inputs and one for its outputs (every hipMalloc / hipFree costs a wait)
     DevBuf<int64_t> d_in, d_out;
     const bool circ = near != nullptr;
-    LOCREC_TRY(d_in.alloc(RankIo::in_words(n_places, nseg, circ) + (unvisited ? knn_rk_ex_words(nseg) : 0)));
+    const RankCatHost none;
+    const RankCatHost &cth = catq ? *catq : none;
+    const size_t ex_at = RankIo::in_words(n_places, nseg, circ), cat_at = ex_at + (unvisited ? knn_rk_ex_words(nseg) : 0);
+    LOCREC_TRY(d_in.alloc(cat_at + cth.words(n_places, nseg, true)));
     LOCREC_TRY(d_out.alloc(RankIo::out_words(nseg, N, circ)));
-    const RankIo io(d_in.p, d_out.p, n_places, nseg, N, nullptr, circ);
+    RankIo io(d_in.p, d_out.p, n_places, nseg, N, nullptr, circ);
+    std::vector<int64_t> cat_stage, hcat_stage;
+    LOCREC_TRY(cth.upload(n_places, nseg, nullptr, d_in.p + cat_at, nullptr, s, cat_stage, io.cat));
     if (circ) {
         if (n_places > 0) {
             LOCREC_HIP_TRY(hipMemcpyAsync(io.plat, near->place_lat, (size_t)n_places * 8, hipMemcpyHostToDevice, s));
@@ -144,7 +153,7 @@ int32_t knn_rank_resident(locrec_knn_index *ix, const std::vector<int64_t> &slot
     if (unvisited) {
         std::vector<int32_t> rows((size_t)nseg);
         for (int64_t c = 0; c < nseg; ++c) rows[(size_t)c] = row_of_slot(slots[(size_t)c]);
-        LOCREC_TRY(knn_rk_rated_lists(ix, rows, d_in.p + RankIo::in_words(n_places, nseg, circ), s, ex));
+        LOCREC_TRY(knn_rk_rated_lists(ix, rows, d_in.p + ex_at, s, ex));
     }
     LOCREC_TRY(io.rank(lkb ? ix->lkb_place.p : ix->agg_place.p, lkb ? ix->lkb_est.p : ix->agg_est.p, 0, s, ex));
     LOCREC_TRY(io.read_back(out_ids, out_scores, out_counts, s, circ ? near->meters : nullptr));
@@ -182,9 +191,11 @@ int32_t knn_rank_resident(locrec_knn_index *ix, const std::vector<int64_t> &slot
         DevBuf<double> d_re;
         LOCREC_TRY(d_rp.upload(rp, s));
         LOCREC_TRY(d_re.upload(re, s));
-        LOCREC_TRY(d_hin.alloc(RankIo::in_words(0, nh, circ) + (unvisited ? knn_rk_ex_words(nh) : 0)));
+        const size_t hex_at = RankIo::in_words(0, nh, circ), hcat_at = hex_at + (unvisited ? knn_rk_ex_words(nh) : 0);
+        LOCREC_TRY(d_hin.alloc(hcat_at + cth.words(n_places, nh, false)));
         LOCREC_TRY(d_hout.alloc(RankIo::out_words(nh, N, circ)));
-        const RankIo hio(d_hin.p, d_hout.p, n_places, nh, N, &io, circ);  // (the places table is already there)
+        RankIo hio(d_hin.p, d_hout.p, n_places, nh, N, &io, circ);  // (the places table is already there)
+        LOCREC_TRY(cth.upload(n_places, nh, hosted.data(), d_hin.p + hcat_at, &io.cat, s, hcat_stage, hio.cat));
         if (circ) LOCREC_HIP_TRY(hipMemcpyAsync(hio.clat, tc.data(), 3 * (size_t)nh * 8, hipMemcpyHostToDevice, s));  // (lat | lon | radius)
         LOCREC_HIP_TRY(hipMemcpyAsync(hio.tgt, tt.data(), (size_t)nh * 8, hipMemcpyHostToDevice, s));
         LOCREC_HIP_TRY(hipMemcpyAsync(hio.base, tb.data(), (size_t)nh * 8, hipMemcpyHostToDevice, s));
@@ -193,7 +204,7 @@ int32_t knn_rank_resident(locrec_knn_index *ix, const std::vector<int64_t> &slot
         if (unvisited) {
             std::vector<int32_t> rows((size_t)nh);
             for (int64_t i = 0; i < nh; ++i) rows[(size_t)i] = row_of_slot(slots[(size_t)hosted[(size_t)i]]);
-            LOCREC_TRY(knn_rk_rated_lists(ix, rows, d_hin.p + RankIo::in_words(0, nh, circ), s, hex));
+            LOCREC_TRY(knn_rk_rated_lists(ix, rows, d_hin.p + hex_at, s, hex));
         }
         LOCREC_TRY(hio.rank(d_rp.p, d_re.p, nh, s, hex));
         LOCREC_TRY(hio.read_back_to(hosted, out_ids, out_scores, out_counts, s, circ ? near->meters : nullptr));
@@ -231,7 +242,8 @@ int32_t knn_fetch_ranked(locrec_knn_index *ix, int64_t nq, bool unvisited, int64
 int32_t knn_recommend_ranked_batch(locrec_knn_index *ix, int64_t nq, const int64_t *person_ids, double pw, double cw, int64_t k,
                                    bool unvisited, int64_t n_places, const int64_t *place_ids, const int64_t *place_region_ids,
                                    const int64_t *target_region_ids, int64_t max_recommendations, int64_t *out_place_ids,
-                                   double *out_estimated_ratings, int64_t *out_counts, const KnnRankNear *near = nullptr)
+                                   double *out_estimated_ratings, int64_t *out_counts, const KnnRankNear *near = nullptr,
+                                   const RankCatHost *catq = nullptr)
 {
     // the batch itself, with its requires and "No such person": the rows stay on the device (capacity 0: sizes only)
     std::vector<int64_t> off((size_t)std::max<int64_t>(nq, 0) + 1, 0);
@@ -251,7 +263,7 @@ int32_t knn_recommend_ranked_batch(locrec_knn_index *ix, int64_t nq, const int64
     std::vector<int64_t> len((size_t)nq);
     for (int64_t i = 0; i < nq; ++i) len[(size_t)i] = off[(size_t)i + 1] - off[(size_t)i];
     return knn_rank_resident(ix, slots, len.data(), unvisited, n_places, place_ids, place_region_ids, target_region_ids,
-                             max_recommendations, out_place_ids, out_estimated_ratings, out_counts, near);
+                             max_recommendations, out_place_ids, out_estimated_ratings, out_counts, near, catq);
 }
 
 }  // namespace
@@ -310,4 +322,33 @@ extern "C" int32_t locrec_knn_recommend_ranked_batch_near(
     const KnnRankNear near = {place_latitudes, place_longitudes, center_latitudes, center_longitudes, radius_meters, out_meters};
     return knn_recommend_ranked_batch(ix, nq, person_ids, pw, cw, k, unvisited != 0, n_places, place_ids, place_region_ids,
                                       target_region_ids, max_recommendations, out_place_ids, out_estimated_ratings, out_counts, &near);
+} LOCREC_CATCH_ALL
+
+extern "C" int32_t locrec_knn_recommend_ranked_batch_by_category(
+    locrec_knn_index *ix, int64_t nq, const int64_t *person_ids, double pw, double cw, int64_t k, int64_t n_places,
+    const int64_t *place_ids, const int64_t *place_region_ids, const double *place_latitudes, const double *place_longitudes,
+    const int64_t *place_category_ids, const int64_t *target_region_ids, const double *center_latitudes,
+    const double *center_longitudes, const double *radius_meters, int64_t max_recommendations, int32_t unvisited,
+    const int64_t *allowed_offsets, int64_t n_allowed, const int64_t *allowed_category_ids, const int64_t *max_per_category,
+    int64_t *out_place_ids, double *out_estimated_ratings, double *out_meters, int64_t *out_counts) try
+{
+    // the circles', the lists' and the caps' requires first: before the index is looked at
+    if (nq < 0 || n_places < 0 || n_places >= ((int64_t)1 << 31)) return fail(LOCREC_E_INVALID_ARG, "query or place count out of range");
+    const bool circles = place_latitudes || place_longitudes || center_latitudes || center_longitudes || radius_meters;
+    if (circles) {
+        if ((nq > 0 && (!center_latitudes || !center_longitudes || !radius_meters)) || (n_places > 0 && (!place_latitudes || !place_longitudes)))
+            return fail(LOCREC_E_INVALID_ARG, "null coordinate or radius array");
+        LOCREC_TRY(rank_near_check_host(nq, center_latitudes, center_longitudes, radius_meters, n_places, place_latitudes, place_longitudes));
+    }
+    RankCatHost cat;
+    cat.place_cat = place_category_ids;
+    cat.allowed_offsets = allowed_offsets;
+    cat.n_allowed = allowed_offsets ? n_allowed : 0;
+    cat.allowed_ids = allowed_category_ids;
+    cat.caps = max_per_category;
+    LOCREC_TRY(cat.check(nq, n_places));
+    const KnnRankNear near = {place_latitudes, place_longitudes, center_latitudes, center_longitudes, radius_meters, out_meters};
+    return knn_recommend_ranked_batch(ix, nq, person_ids, pw, cw, k, unvisited != 0, n_places, place_ids, place_region_ids,
+                                      target_region_ids, max_recommendations, out_place_ids, out_estimated_ratings, out_counts,
+                                      circles ? &near : nullptr, &cat);
 } LOCREC_CATCH_ALL

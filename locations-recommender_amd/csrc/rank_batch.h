@@ -78,6 +78,96 @@ int32_t rank_segments_device_near(int64_t n_segments, const int64_t *seg_begin, 
 int32_t rank_near_check_host(int64_t n_segments, const double *center_lat, const double *center_lon, const double *radius,
                              int64_t n_places, const double *place_lat, const double *place_lon);
 
+// the categories of one ranker call (place_cat NULL: none): per row of the place table its category, per segment an
+// allow-list allow_ids[allow_begin[s] .. + allow_len[s]) in the mould of the exclusion lists (allow_begin NULL: no
+// lists; an empty list allows every category) and a cap on the rows of one category (caps NULL: no caps)
+struct RankCategory {
+    const int64_t *place_cat = nullptr, *allow_begin = nullptr, *allow_len = nullptr, *allow_ids = nullptr;
+    int64_t n_allowed = 0;
+    const int64_t *caps = nullptr;
+    // (the public entry's second validity word: its allowed_offsets broke the offset rules)
+    const unsigned long long *allow_invalid = nullptr;
+};
+
+// "By category": the same with an allow-list and a cap per segment, circles only when near.center_lat is given and
+// exclusion lists only when ex.begin is.  A listing of a place in the target region passes if its category is in the
+// segment's list (no list, or an empty one: any) and it lies inside the circle; the first passing listing in the
+// table's input order is the one that counts: its category is the row's for the cap, its distance the row's
+// out_meters.  A row is eligible iff fewer than caps[s] kept rows of its category precede it in the order (score desc,
+// id asc, input row asc); the output is the first max_recommendations eligible rows.  caps[s] >= 1, checked with the
+// lists' ranges in the plan step.  With no list entry and every cap >= max_recommendations the existing kernels run
+// and the result and the stats are the plain / excluding / near entry's.
+int32_t rank_segments_device_by_category(int64_t n_segments, const int64_t *seg_begin, const int64_t *seg_len, const int64_t *ids,
+                                         const double *scores, int64_t n_places, const int64_t *place_ids,
+                                         const int64_t *place_region_ids, const int64_t *target_region_ids,
+                                         int64_t max_recommendations, const RankExclude &ex, const RankNear &near,
+                                         const RankCategory &cat, int64_t *out_ids, double *out_scores, double *out_meters,
+                                         int64_t *out_counts, const unsigned long long *invalid_flag, int64_t host_assembled,
+                                         hipStream_t s);
+
+// the lists' and caps' requires for host arrays, before any device work: allow_offsets NULL: no lists, caps NULL: none
+int32_t rank_category_check_host(int64_t n_segments, const int64_t *allowed_offsets, int64_t n_allowed, const int64_t *caps);
+
+// The categories of a KNN / SG call, host arrays as the public entry takes them (allowed_offsets NULL: no lists, caps NULL:
+// no caps, both NULL: none).  Its words lie behind a RankIo's inputs:
+//   [place categories | begins | lengths | caps | listed categories]   (a second call of the same request - the KNN calls'
+// host-assembled segments, an SG group - shares the first one's place categories and listed categories: table_of)
+struct RankCatHost {
+    const int64_t *place_cat = nullptr, *allowed_offsets = nullptr;
+    int64_t n_allowed = 0;
+    const int64_t *allowed_ids = nullptr, *caps = nullptr;
+    bool given() const { return allowed_offsets || caps; }
+    // the requires of the public entry, before any device work
+    int32_t check(int64_t n_segments, int64_t n_places) const
+    {
+        if (!given()) return LOCREC_OK;
+        if (allowed_offsets && (n_allowed < 0 || n_allowed >= ((int64_t)1 << 31)))
+            return fail(LOCREC_E_INVALID_ARG, "n_allowed out of range [0, 2^31)");
+        if (allowed_offsets && n_allowed > 0 && !allowed_ids) return fail(LOCREC_E_INVALID_ARG, "allowed_category_ids is NULL with n_allowed > 0");
+        if (n_places > 0 && !place_cat) return fail(LOCREC_E_INVALID_ARG, "place_category_ids is NULL with allow-lists or caps given");
+        return rank_category_check_host(n_segments, allowed_offsets, n_allowed, caps);
+    }
+    size_t words(int64_t n_places, int64_t nseg, bool with_tables) const
+    {
+        if (!given()) return 0;
+        return 3 * (size_t)nseg + (with_tables ? (size_t)n_places + (size_t)(allowed_offsets ? n_allowed : 0) : 0);
+    }
+    // Fills the words at `at` for the call's segments seg[0 .. nseg) of the request (seg NULL: 0 .. nseg) -> the ranker's
+    // block.  stage: host staging of the copies, the caller's until the stream has been waited for.
+    int32_t upload(int64_t n_places, int64_t nseg, const int64_t *seg, int64_t *at, const RankCategory *table_of, hipStream_t s,
+                   std::vector<int64_t> &stage, RankCategory &out) const
+    {
+        out = RankCategory();
+        if (!given()) return LOCREC_OK;
+        int64_t *begin = at, *len = at + nseg, *cap = at + 2 * nseg, *tables = at + 3 * nseg;
+        stage.assign(3 * (size_t)nseg, 0);
+        for (int64_t c = 0; c < nseg; ++c) {
+            const int64_t g = seg ? seg[c] : c;
+            stage[(size_t)c] = allowed_offsets ? allowed_offsets[g] : 0;
+            stage[(size_t)(nseg + c)] = allowed_offsets ? allowed_offsets[g + 1] - allowed_offsets[g] : 0;
+            stage[(size_t)(2 * nseg + c)] = caps ? caps[g] : 0;
+        }
+        LOCREC_HIP_TRY(hipMemcpyAsync(at, stage.data(), 3 * (size_t)nseg * 8, hipMemcpyHostToDevice, s));
+        if (table_of) {
+            out.place_cat = table_of->place_cat;
+            out.allow_ids = table_of->allow_ids;
+        } else {
+            if (n_places > 0) LOCREC_HIP_TRY(hipMemcpyAsync(tables, place_cat, (size_t)n_places * 8, hipMemcpyHostToDevice, s));
+            if (allowed_offsets && n_allowed > 0)
+                LOCREC_HIP_TRY(hipMemcpyAsync(tables + n_places, allowed_ids, (size_t)n_allowed * 8, hipMemcpyHostToDevice, s));
+            out.place_cat = tables;
+            out.allow_ids = tables + n_places;
+        }
+        if (allowed_offsets) {
+            out.allow_begin = begin;
+            out.allow_len = len;
+            out.n_allowed = n_allowed;
+        }
+        if (caps) out.caps = cap;
+        return LOCREC_OK;
+    }
+};
+
 // One ranker call's device arrays, carved out of one input and one output allocation of 8-byte words:
 //   in   [place ids | place regions | targets | bases | lengths]   (without the places table when it is places_of's)
 //   out  [ids | scores | counts]
@@ -109,8 +199,14 @@ struct RankIo {
         plon = places_of ? places_of->plon : plat + n_places;
         omet = reinterpret_cast<double *>(ocnt + nseg);
     }
+    // by category: the block RankCatHost::upload made of the words behind the inputs (nothing given: none)
+    RankCategory cat;
     int32_t rank(const int64_t *ids, const double *scores, int64_t host_assembled, hipStream_t s, const RankExclude &ex = {}) const
     {
+        if (cat.allow_begin || cat.caps)
+            return rank_segments_device_by_category(nseg, base, len, ids, scores, n_places, pid, preg, tgt, N, ex,
+                                                    near ? RankNear{clat, clon, rad, plat, plon} : RankNear{}, cat, oid, osc, omet, ocnt,
+                                                    nullptr, host_assembled, s);
         if (near)
             return rank_segments_device_near(nseg, base, len, ids, scores, n_places, pid, preg, tgt, N, ex, {clat, clon, rad, plat, plon},
                                              oid, osc, omet, ocnt, nullptr, host_assembled, s);

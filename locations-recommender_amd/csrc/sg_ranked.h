@@ -25,6 +25,9 @@
 //   exclusion lists locrec_sg_recommend_ranked_batch_excluding: a caller-given list of ids per position (the places a
 //                   person has been to), uploaded once in emit order; a group's ranker call is the excluding entry with
 //                   the sub-range of its segments.  The emit and the segments' room do not see the lists.
+//   categories      locrec_sg_recommend_ranked_batch_by_category: an allow-list and a cap per position and the place rows'
+//                   categories, uploaded once (lists and caps in emit order, RankCatHost); a group's ranker call is
+//                   rank_segments_device_by_category with the sub-range of its segments, the circles optional.
 //   circles         locrec_sg_recommend_ranked_batch_near: a centre and a radius per position and the place rows'
 //                   coordinates, uploaded once (the circles in emit order); a group's ranker call is the near entry with
 //                   the sub-range of its segments, and out_meters comes back with the group's rows.  As with the lists,
@@ -365,6 +368,10 @@ struct SgRkCall {
     std::vector<double> h_osc;
     std::vector<int32_t> res_conv;
     std::vector<int64_t> h_ex;  // the lists' begins and lengths in emit order, as uploaded
+    // per-request allow-lists and caps in emit order and the place rows' categories (nothing given: none): like the
+    // circles, uploaded once, and only the group's ranker call sees them
+    RankCategory cat;
+    std::vector<int64_t> h_cat;
 
     // Reads the n_caps caps back and forms the groups: request k's segment has room caps[cap_of[k]], a group's segments
     // share the row buffer.  nu: distinct targets.
@@ -442,6 +449,14 @@ struct SgRkCall {
         return LOCREC_OK;
     }
 
+    // The categories, uploaded once into d_cat (which outlives the call's launches): begins, lengths and caps in emit
+    // order, then the place rows' categories and the listed categories
+    int32_t upload_categories(const std::vector<int64_t> &ord, const RankCatHost &ch, DevBuf<int64_t> &d_cat)
+    {
+        LOCREC_TRY(d_cat.alloc(std::max<size_t>(1, ch.words(n_places, n, true))));
+        return ch.upload(n_places, n, ord.data(), d_cat.p, nullptr, s, h_cat, cat);
+    }
+
     // ranks the filled group and brings its rows to the host
     int32_t flush_group()
     {
@@ -452,7 +467,21 @@ struct SgRkCall {
         int64_t *d_oid = d_out.p, *d_ocnt = d_out.p + 2 * groups.max_req * Nd;
         double *d_osc = reinterpret_cast<double *>(d_out.p + groups.max_req * Nd);
         double *d_omet = reinterpret_cast<double *>(d_ocnt + groups.max_req);
-        if (near.center_lat) {
+        if (cat.allow_begin || cat.caps) {
+            RankExclude ex;
+            if (d_ex_begin) ex = {d_ex_begin + ka, d_ex_len + ka, d_ex_ids, n_ex};
+            RankNear nr;
+            if (near.center_lat) nr = {near.center_lat + ka, near.center_lon + ka, near.radius + ka, near.place_lat, near.place_lon};
+            RankCategory ct = cat;  // the group's sub-range of the lists and caps
+            if (ct.allow_begin) {
+                ct.allow_begin += ka;
+                ct.allow_len += ka;
+            }
+            if (ct.caps) ct.caps += ka;
+            LOCREC_TRY(rank_segments_device_by_category(nseg, d_seg_begin + ka, d_seg_len + ka, d_row_ids, d_row_probs, n_places, d_pid,
+                                                        d_preg, d_tgt + ka, Nd, ex, nr, ct, d_oid, d_osc,
+                                                        near.center_lat ? d_omet : nullptr, d_ocnt, nullptr, 0, s));
+        } else if (near.center_lat) {
             RankExclude ex;
             if (d_ex_begin) ex = {d_ex_begin + ka, d_ex_len + ka, d_ex_ids, n_ex};
             const RankNear nr = {near.center_lat + ka, near.center_lon + ka, near.radius + ka, near.place_lat, near.place_lon};
@@ -468,7 +497,7 @@ struct SgRkCall {
         const RankBatchStats &rs = rank_batch_stats();
         stats.host_syncs += rs.host_syncs;
         // the ranker's plan header (one word more with lists), the global path's row count
-        stats.readback_bytes += (d_ex_begin ? 40 : 32) + (rs.sorted ? 4 : 0);
+        stats.readback_bytes += (cat.allow_begin || cat.caps ? 56 : d_ex_begin ? 40 : 32) + (rs.sorted ? 4 : 0);
         LOCREC_HIP_TRY(hipMemcpyAsync(h_oid.data() + ka * Nd, d_oid, (size_t)(nseg * Nd) * 8, hipMemcpyDeviceToHost, s));
         LOCREC_HIP_TRY(hipMemcpyAsync(h_osc.data() + ka * Nd, d_osc, (size_t)(nseg * Nd) * 8, hipMemcpyDeviceToHost, s));
         LOCREC_HIP_TRY(hipMemcpyAsync(h_cnt.data() + ka, d_ocnt, (size_t)nseg * 8, hipMemcpyDeviceToHost, s));
@@ -525,7 +554,7 @@ int32_t sg_ranked_batch_columns(locrec_sg_graph *g, SgRankedStats &stats, int64_
                                 const int64_t *place_region_ids, const int64_t *target_region_ids, bool with_lists,
                                 const int64_t *excluded_offsets, int64_t n_excluded, const int64_t *excluded_ids, int64_t *out_ids,
                                 double *out_probabilities, int64_t *out_counts, int64_t *out_row_counts, int64_t *out_iterations,
-                                int32_t *out_converged, const SgRkNear *near = nullptr);
+                                int32_t *out_converged, const SgRkNear *near = nullptr, const RankCatHost *cat = nullptr);
 
 // The exclusion lists' checks (host arrays), before any device work
 int32_t sg_rk_check_lists(int64_t n_targets, const int64_t *excluded_offsets, int64_t n_excluded, const int64_t *excluded_ids)
@@ -545,7 +574,8 @@ int32_t sg_recommend_ranked_batch(locrec_sg_graph *g, int64_t n_targets, const i
                                   const int64_t *place_region_ids, const int64_t *target_region_ids, int64_t max_recommendations,
                                   bool with_lists, const int64_t *excluded_offsets, int64_t n_excluded, const int64_t *excluded_ids,
                                   int64_t *out_ids, double *out_probabilities, int64_t *out_counts, int64_t *out_row_counts,
-                                  int64_t *out_iterations, int32_t *out_converged, const SgRkNear *near = nullptr)
+                                  int64_t *out_iterations, int32_t *out_converged, const SgRkNear *near = nullptr,
+                                  const RankCatHost *cat = nullptr)
 {
     SgRankedStats &stats = sg_ranked_stats();
     stats = SgRankedStats();
@@ -561,7 +591,7 @@ int32_t sg_recommend_ranked_batch(locrec_sg_graph *g, int64_t n_targets, const i
     return sg_ranked_batch_columns(g, stats, n_targets, uniq, uniq_of, SgPersonTiles{uniq}, alpha, epsilon, max_iterations, N, n_places,
                                    place_ids, place_region_ids, target_region_ids, with_lists, excluded_offsets, n_excluded,
                                    excluded_ids, out_ids, out_probabilities, out_counts, out_row_counts, out_iterations,
-                                   out_converged, near);
+                                   out_converged, near, cat);
 }
 
 // The ranked batch behind its checks, for n >= 1 positions over the columns `tiles` runs: position i asks column uniq_of[i],
@@ -573,7 +603,7 @@ int32_t sg_ranked_batch_columns(locrec_sg_graph *g, SgRankedStats &stats, int64_
                                 const int64_t *place_region_ids, const int64_t *target_region_ids, bool with_lists,
                                 const int64_t *excluded_offsets, int64_t n_excluded, const int64_t *excluded_ids, int64_t *out_ids,
                                 double *out_probabilities, int64_t *out_counts, int64_t *out_row_counts, int64_t *out_iterations,
-                                int32_t *out_converged, const SgRkNear *near)
+                                int32_t *out_converged, const SgRkNear *near, const RankCatHost *cat)
 {
     LOCREC_HIP_TRY(hipSetDevice(g->device));
     hipStream_t s = g->stream;
@@ -648,8 +678,9 @@ int32_t sg_ranked_batch_columns(locrec_sg_graph *g, SgRankedStats &stats, int64_
     DevBuf<double> d_nr;  // the circles
     if (near) LOCREC_TRY(rc.upload_circles(ord, *near, d_nr));
     LOCREC_TRY(rc.plan(d_caps, (size_t)R, req.data() + 2 * n, nu));
-    DevBuf<int64_t> d_ex;  // the lists
+    DevBuf<int64_t> d_ex, d_cat;  // the lists; the categories
     if (with_lists) LOCREC_TRY(rc.upload_lists(ord, excluded_offsets, n_excluded, excluded_ids, d_ex));
+    if (cat && cat->given()) LOCREC_TRY(rc.upload_categories(ord, *cat, d_cat));
     DevBuf<unsigned char> d_state;
     LOCREC_TRY(d_state.alloc(kRkStateBytes));
 
@@ -721,6 +752,42 @@ extern "C" int32_t locrec_sg_recommend_ranked_batch_near(
                                      target_region_ids, max_recommendations, with_lists, excluded_offsets, with_lists ? n_excluded : 0,
                                      excluded_ids, out_ids, out_probabilities, out_counts, out_row_counts, out_iterations,
                                      out_converged, &near);
+} LOCREC_CATCH_ALL
+
+extern "C" int32_t locrec_sg_recommend_ranked_batch_by_category(
+    locrec_sg_graph *g, int64_t n_targets, const int64_t *vertex_ids, double alpha, double epsilon, int64_t max_iterations,
+    int64_t n_places, const int64_t *place_ids, const int64_t *place_region_ids, const double *place_latitudes,
+    const double *place_longitudes, const int64_t *place_category_ids, const int64_t *target_region_ids,
+    const double *center_latitudes, const double *center_longitudes, const double *radius_meters, int64_t max_recommendations,
+    const int64_t *excluded_offsets, int64_t n_excluded, const int64_t *excluded_ids, const int64_t *allowed_offsets,
+    int64_t n_allowed, const int64_t *allowed_category_ids, const int64_t *max_per_category, int64_t *out_ids,
+    double *out_probabilities, double *out_meters, int64_t *out_counts, int64_t *out_row_counts, int64_t *out_iterations,
+    int32_t *out_converged) try
+{
+    // the circles', the lists' and the caps' requires first: before the graph is looked at
+    if (n_targets < 0 || n_places < 0 || n_places >= ((int64_t)1 << 31)) return fail(LOCREC_E_INVALID_ARG, "target or place count out of range");
+    const bool circles = place_latitudes || place_longitudes || center_latitudes || center_longitudes || radius_meters;
+    if (circles) {
+        if ((n_targets > 0 && (!center_latitudes || !center_longitudes || !radius_meters)) ||
+            (n_places > 0 && (!place_latitudes || !place_longitudes)))
+            return fail(LOCREC_E_INVALID_ARG, "null coordinate or radius array");
+        LOCREC_TRY(rank_near_check_host(n_targets, center_latitudes, center_longitudes, radius_meters, n_places, place_latitudes,
+                                        place_longitudes));
+    }
+    const bool with_lists = excluded_offsets != nullptr;
+    if (with_lists) LOCREC_TRY(sg_rk_check_lists(n_targets, excluded_offsets, n_excluded, excluded_ids));
+    RankCatHost cat;
+    cat.place_cat = place_category_ids;
+    cat.allowed_offsets = allowed_offsets;
+    cat.n_allowed = allowed_offsets ? n_allowed : 0;
+    cat.allowed_ids = allowed_category_ids;
+    cat.caps = max_per_category;
+    LOCREC_TRY(cat.check(n_targets, n_places));
+    const SgRkNear near = {place_latitudes, place_longitudes, center_latitudes, center_longitudes, radius_meters, out_meters};
+    return sg_recommend_ranked_batch(g, n_targets, vertex_ids, alpha, epsilon, max_iterations, n_places, place_ids, place_region_ids,
+                                     target_region_ids, max_recommendations, with_lists, excluded_offsets, with_lists ? n_excluded : 0,
+                                     excluded_ids, out_ids, out_probabilities, out_counts, out_row_counts, out_iterations,
+                                     out_converged, circles ? &near : nullptr, &cat);
 } LOCREC_CATCH_ALL
 
 extern "C" int32_t locrec_sg_recommend_ranked_batch(locrec_sg_graph *g, int64_t n_targets, const int64_t *vertex_ids, double alpha,

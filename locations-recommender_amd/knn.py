@@ -321,6 +321,44 @@ class KnnIndex:
             L.ptr(oi, C.c_int64), L.ptr(osc, C.c_double), L.ptr(om, C.c_double), L.ptr(cnt, C.c_int64)))
         return oi, osc, om, cnt
 
+    def recommend_ranked_batch_by_category(self, person_ids, pw, cw, k, place_ids, place_region_ids, target_region_ids,
+                                           max_recommendations, place_category_ids, allowed=None, max_per_category=None,
+                                           circles=None, unvisited=False):
+        """recommend_ranked_batch by category (locrec_knn_recommend_ranked_batch_by_category): place_category_ids gives the
+        category of every row of the place table, allowed=(offsets[nq + 1], category_ids) one allow-list per person (an
+        empty list allows every category), max_per_category[i] >= 1 caps the rows of one category in person i's ranking -
+        prep.rank_recommendations_batch_by_category's rules.  circles=(place_latitudes, place_longitudes,
+        center_latitudes, center_longitudes, radius_meters): within reach as well; unvisited=True: only new places as
+        well.  -> (place_ids[nq, W], estimated_ratings[nq, W], meters[nq, W] or None without circles, counts[nq])."""
+        q = L.as_i64(person_ids)
+        pl, reg, tgt, width, (oi, osc, cnt) = self._ranked_args(len(q), place_ids, place_region_ids, target_region_ids,
+                                                                max_recommendations)
+        pcat = L.as_i64(place_category_ids)
+        if len(pcat) != len(pl):
+            raise L.IllegalArgumentException("one category per place is required")
+        aoff = aids = caps = om = None
+        if allowed is not None:
+            aoff, aids = L.as_i64(allowed[0]), L.as_i64(allowed[1])
+            if len(aoff) != len(q) + 1:
+                raise L.IllegalArgumentException("one allow-list per person is required: offsets of nq + 1 entries")
+        if max_per_category is not None:
+            caps = L.as_i64(max_per_category)
+            if len(caps) != len(q):
+                raise L.IllegalArgumentException("one cap per person is required")
+        c = [None] * 5
+        if circles is not None:
+            c = [L.as_f64(x) for x in circles]
+            if len(c[0]) != len(pl) or len(c[1]) != len(pl) or not len(c[2]) == len(c[3]) == len(c[4]) == len(q):
+                raise L.IllegalArgumentException("one coordinate pair per place and one centre and radius per person are required")
+            om = np.zeros((len(q), width), np.float64)
+        L.check(L.lib().locrec_knn_recommend_ranked_batch_by_category(
+            self._h, len(q), L.ptr(q, C.c_int64), float(pw), float(cw), int(k), len(pl), L.ptr(pl, C.c_int64),
+            L.ptr(reg, C.c_int64), L.ptr(c[0], C.c_double), L.ptr(c[1], C.c_double), L.ptr(pcat, C.c_int64), L.ptr(tgt, C.c_int64),
+            L.ptr(c[2], C.c_double), L.ptr(c[3], C.c_double), L.ptr(c[4], C.c_double), width, int(bool(unvisited)),
+            L.ptr(aoff, C.c_int64), 0 if aids is None else len(aids), L.ptr(aids, C.c_int64), L.ptr(caps, C.c_int64),
+            L.ptr(oi, C.c_int64), L.ptr(osc, C.c_double), L.ptr(om, C.c_double), L.ptr(cnt, C.c_int64)))
+        return oi, osc, om, cnt
+
     def fetch_ranked(self, nq, place_ids, place_region_ids, target_region_ids, max_recommendations, unvisited=False):
         """The same last stage for the range recommend_range_async left on the device (locrec_knn_fetch_ranked, or
         locrec_knn_fetch_ranked_unvisited): target_region_ids[i] belongs to internal row first + i."""

@@ -204,6 +204,69 @@ def rank_recommendations_batch(offsets, ids, scores, place_ids, place_region_ids
     return out_ids, out_scores, counts
 
 
+def rank_recommendations_by_category(offsets, ids, scores, place_ids, place_region_ids, target_region_ids, max_recommendations,
+                                     place_category_ids, allowed=None, max_per_category=None, circles=None, excluded=None,
+                                     distance=None):
+    """The numpy restatement of prep.rank_recommendations_batch_by_category, with its arguments and its result layout
+    (ids[S, W], scores[S, W], meters[S, W] or None, counts[S]).  Per segment: the place table cut to the listings that
+    pass every predicate given (target region, allow-list, circle); rank_recommendations at limit = segment length for
+    the order; then a greedy walk with a counter per category, a row's category and distance being those of the first
+    passing listing of its place.  distance: the haversine of four arrays (default prep.distance_meters)."""
+    offsets, ids, scores = np.asarray(offsets, np.int64), np.asarray(ids, np.int64), np.asarray(scores, np.float64)
+    place_ids, regions = np.asarray(place_ids, np.int64), np.asarray(place_region_ids, np.int64)
+    cats = np.asarray(place_category_ids, np.int64)
+    nseg = len(target_region_ids)
+    if len(offsets) != nseg + 1 or (nseg and (offsets[0] < 0 or offsets[-1] > len(ids) or np.any(np.diff(offsets) < 0))):
+        raise L.IllegalArgumentException("offsets must be non-decreasing inside [0, n]")
+    if max_per_category is not None and np.any(np.asarray(max_per_category, np.int64) < 1):
+        raise L.IllegalArgumentException("max_per_category must be >= 1 for every segment")
+    if circles is not None and distance is None:
+        from . import prep
+        distance = prep.distance_meters
+    longest = int(np.diff(offsets).max()) if nseg else 0
+    width = max(0, min(int(max_recommendations), longest))
+    out_ids, out_scores = np.full((nseg, width), -1, np.int64), np.zeros((nseg, width), np.float64)
+    out_meters = np.zeros((nseg, width), np.float64) if circles is not None else None
+    counts = np.zeros(nseg, np.int64)
+    for s in range(nseg):
+        a, b = offsets[s], offsets[s + 1]
+        si, ss = ids[a:b], scores[a:b]
+        if excluded is not None:
+            xo, xi = np.asarray(excluded[0], np.int64), np.asarray(excluded[1], np.int64)
+            keep = ~np.isin(si, xi[xo[s]:xo[s + 1]])
+            si, ss = si[keep], ss[keep]
+        rows = np.flatnonzero(regions == int(target_region_ids[s]))
+        if allowed is not None:
+            ao, ai = np.asarray(allowed[0], np.int64), np.asarray(allowed[1], np.int64)
+            if ao[s + 1] > ao[s]:
+                rows = rows[np.isin(cats[rows], ai[ao[s]:ao[s + 1]])]
+        meters = np.zeros(len(rows))
+        if circles is not None and len(rows):
+            plat, plon, clat, clon, rad = (np.asarray(x, np.float64) for x in circles)
+            meters = np.asarray(distance(np.full(len(rows), clat[s]), np.full(len(rows), clon[s]), plat[rows], plon[rows]), np.float64)
+            rows, meters = rows[meters <= rad[s]], meters[meters <= rad[s]]
+        ri, rs = rank_recommendations(si, ss, place_ids[rows], regions[rows], target_region_ids[s], len(si))
+        first = {}
+        for j, pid in enumerate(place_ids[rows].tolist()):    # the listing that counts: the first passing one
+            first.setdefault(pid, j)
+        cap = int(max_per_category[s]) if max_per_category is not None else None
+        used, w = {}, 0
+        for i, sc in zip(ri.tolist(), rs):
+            if w == width:
+                break
+            j = first[i]
+            c = int(cats[rows[j]])
+            if cap is not None and used.get(c, 0) >= cap:
+                continue
+            used[c] = used.get(c, 0) + 1
+            out_ids[s, w], out_scores[s, w] = i, sc
+            if out_meters is not None:
+                out_meters[s, w] = meters[j]
+            w += 1
+        counts[s] = w
+    return out_ids, out_scores, out_meters, counts
+
+
 def knn_recommend_places_batch(data_dir, region_ids, requests, place_weight, category_weight, k_nearest,
                                max_recommendations=10, new_places=False):
     """Many requests of one region pair to their end (KnnRecommenderMain.scala:53-67 and :90-101): requests is a
@@ -1088,14 +1151,18 @@ def _near_request_circles(lines, positions, radius_meters):
     return lat, lon, rad
 
 
-def _near_requests(kind, resolve_lines, per_handle, data_dir, persons, lines, positions, radius_meters, max_recommendations):
+def _near_requests(kind, resolve_lines, per_handle, data_dir, persons, lines, positions, radius_meters, max_recommendations,
+                   with_lines=False):
     """What both near request functions share: the lines resolved as ever, the place table with its coordinates
     (load_places_full), one near ranked batch per distinct handle (per_handle(handle, person_ids, regions, places, lat,
     lon, rad, target of the handle's first line) -> (ids, scores, meters, counts) for the lines of that handle), a bad
-    line recorded and the call repeated without it.  -> per line ((person, home, target), ids, scores, meters) or the exception instance."""
+    line recorded and the call repeated without it.  -> per line ((person, home, target), ids, scores, meters) or the exception instance.
+    with_lines: per_handle also gets the positions of its lines in `lines` (the by-category functions' lists and caps are
+    per line), and positions None is no circles: lat, lon and rad are None and so are the meters."""
     from . import _cache
     _cache.require_gpu_backend(kind)
-    lat, lon, rad = _near_request_circles(lines, positions, radius_meters)
+    circles = positions is not None
+    lat, lon, rad = _near_request_circles(lines, positions, radius_meters) if circles else (None, None, None)
     out, targets, handles = resolve_lines(data_dir, persons, lines)
     try:
         if targets:
@@ -1112,21 +1179,26 @@ def _near_requests(kind, resolve_lines, per_handle, data_dir, persons, lines, po
                     at = np.flatnonzero(gi == k)
                     try:
                         with handles[k].lock:
-                            r = per_handle(handles[k], v[at], regions[at], places, lat[at_lines[at]], lon[at_lines[at]],
-                                           rad[at_lines[at]], targets[live[at[0]]][0])
+                            la = at_lines[at]
+                            r = per_handle(handles[k], v[at], regions[at], places, *((lat[la], lon[la], rad[la]) if circles
+                                                                                     else (None, None, None)),
+                                           targets[live[at[0]]][0], *((la,) if with_lines else ()))
                     except L.IllegalArgumentException as e:
                         head, _, unknown = str(e).rpartition(": ")
                         if head in ("No such person", "No such vertex in the graph"):
                             e.bad_request = int(at[np.flatnonzero(v[at] == int(unknown))[0]])
                         raise
                     w = r[0].shape[1]
-                    oi[at, :w], osc[at, :w], om[at, :w], cnt[at] = r
+                    oi[at, :w], osc[at, :w], cnt[at] = r[0], r[1], r[3]
+                    if circles:
+                        om[at, :w] = r[2]
                 return oi, osc, om, cnt
             live, rows = _call_without_bad_lines(out, targets, call)
             if live:
                 oi, osc, om, cnt = rows
                 for k, i in enumerate(live):
-                    out[i] = (targets[i][0], np.array(oi[k, :cnt[k]]), np.array(osc[k, :cnt[k]]), np.array(om[k, :cnt[k]]))
+                    out[i] = (targets[i][0], np.array(oi[k, :cnt[k]]), np.array(osc[k, :cnt[k]]),
+                              np.array(om[k, :cnt[k]]) if circles else None)
     finally:
         for h in handles:
             h.close()  # drops the reference only
@@ -1164,6 +1236,86 @@ def sg_recommender_requests_near(data_dir, persons, lines, positions, radius_met
                                              max_recommendations, excluded=excluded)[:4]
     return _near_requests("sg_recommender_requests_near", _sg_resolve_request_lines, per_graph, data_dir, persons, lines,
                           positions, radius_meters, max_recommendations)
+
+
+def _category_request_lists(lines, categories, max_per_category):
+    """The lists and caps of a by-category request list.  categories: None, one list of category ids for every line, or
+    one list per line (an empty list allows every category); max_per_category: None, a scalar or one value per line.
+    -> (allowed (offsets[n + 1], ids) or None, caps[n] or None), per line."""
+    n = len(lines)
+    allowed = caps = None
+    if categories is not None:
+        per_line = len(categories) > 0 and all(np.ndim(c) == 1 for c in categories)
+        lists = [np.asarray(c, np.int64) for c in categories] if per_line else [np.asarray(categories, np.int64).reshape(-1)] * n
+        if len(lists) != n:
+            raise L.IllegalArgumentException("one list of categories for every line or one per line is required")
+        off = np.zeros(n + 1, np.int64)
+        np.cumsum([len(x) for x in lists], out=off[1:])
+        allowed = (off, np.concatenate(lists + [np.empty(0, np.int64)]).astype(np.int64))
+    if max_per_category is not None:
+        caps = np.asarray(max_per_category, np.int64)
+        caps = np.full(n, int(caps), np.int64) if caps.ndim == 0 else caps
+        if len(caps) != n:
+            raise L.IllegalArgumentException("a scalar max_per_category or one per line is required")
+    return allowed, caps
+
+
+def _category_sub_lists(allowed, caps, at):
+    """The lists and caps of the lines `at`, as a CSR of their own."""
+    sub_allowed = None
+    if allowed is not None:
+        off, ids = allowed
+        lists = [ids[off[i]:off[i + 1]] for i in at]
+        sub_off = np.zeros(len(at) + 1, np.int64)
+        np.cumsum([len(x) for x in lists], out=sub_off[1:])
+        sub_allowed = (sub_off, np.concatenate(lists + [np.empty(0, np.int64)]).astype(np.int64))
+    return sub_allowed, None if caps is None else caps[at]
+
+
+def knn_recommender_requests_by_category(data_dir, persons, lines, place_weight, category_weight, k_nearest,
+                                         max_recommendations=10, categories=None, max_per_category=None, new_places=False,
+                                         positions=None, radius_meters=None):
+    """knn_recommender_requests by category: line i is resolved as ever and ranked among the places of its target region
+    whose category_id (places_sample) is in `categories` - None: any; one list of ids for every line, or one list per
+    line - with at most max_per_category (None: no cap; a scalar or one value per line) places of one category -
+    KnnIndex.recommend_ranked_batch_by_category, one call per distinct index.  positions = (lat[n], lon[n]) and
+    radius_meters: within reach as well, as knn_recommender_requests_near.  new_places=True: without the places the
+    person has rated.
+    -> a list aligned with lines: ((person_id, home_region_id, target_region_id), place_ids, estimated_ratings, meters or
+    None without positions) or the exception instance."""
+    allowed, caps = _category_request_lists(lines, categories, max_per_category)
+
+    def per_index(ix, person_ids, regions, places, lat, lon, rad, _target, at):
+        sub_allowed, sub_caps = _category_sub_lists(allowed, caps, at)
+        circles = None if lat is None else (places["latitude"], places["longitude"], lat, lon, rad)
+        return ix.recommend_ranked_batch_by_category(person_ids, place_weight, category_weight, k_nearest, places["id"],
+                                                     places["region_id"], regions, max_recommendations, places["category_id"],
+                                                     allowed=sub_allowed, max_per_category=sub_caps, circles=circles,
+                                                     unvisited=new_places)
+    return _near_requests("knn_recommender_requests_by_category", _knn_resolve_request_lines, per_index, data_dir, persons,
+                          lines, positions, radius_meters, max_recommendations, with_lines=True)
+
+
+def sg_recommender_requests_by_category(data_dir, persons, lines, epsilon, max_iterations, max_recommendations=10,
+                                        categories=None, max_per_category=None, new_places=False, positions=None,
+                                        radius_meters=None):
+    """sg_recommender_requests by category, as knn_recommender_requests_by_category:
+    SgGraph.recommend_ranked_batch_by_category, one call per distinct graph.  new_places=True: without the targets of the
+    person's out-edges in its region set's edge Parquet.
+    -> a list aligned with lines: ((person_id, home_region_id, target_region_id), ids, probabilities, meters or None) or
+    the exception instance."""
+    from .stochastic import ALPHA
+    allowed, caps = _category_request_lists(lines, categories, max_per_category)
+
+    def per_graph(g, vertex_ids, regions, places, lat, lon, rad, target, at):
+        sub_allowed, sub_caps = _category_sub_lists(allowed, caps, at)
+        excluded = _sg_visited_lists(data_dir, [target[1], target[2]], vertex_ids) if new_places else None
+        circles = None if lat is None else (places["latitude"], places["longitude"], lat, lon, rad)
+        return g.recommend_ranked_batch_by_category(vertex_ids, ALPHA, epsilon, max_iterations, places["id"], places["region_id"],
+                                                    regions, max_recommendations, places["category_id"], allowed=sub_allowed,
+                                                    max_per_category=sub_caps, circles=circles, excluded=excluded)[:4]
+    return _near_requests("sg_recommender_requests_by_category", _sg_resolve_request_lines, per_graph, data_dir, persons, lines,
+                          positions, radius_meters, max_recommendations, with_lines=True)
 
 
 def _sg_resolve_request_lines(data_dir, persons, lines, resolve=None):

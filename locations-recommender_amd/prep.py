@@ -11,6 +11,7 @@ SURVEY.md 8f rows f-2 and f-4) behind the names of the reference's builder objec
     rank_recommendations_batch   ... for every segment of a batch's rows   (the same lines, per person)
     rank_recommendations_batch_excluding   ... leaving out a list of ids per segment (no counterpart: only new places)
     rank_recommendations_batch_near        ... within a radius of a centre per segment (no counterpart: within reach)
+    rank_recommendations_batch_by_category ... with an allow-list of categories and a cap per category (no counterpart)
     calc_person_likes_place_edges / calc_person_likes_category_edges / calc_category_selected_place_edges
                                  the three counted edge families          stochastic/PersonLikesPlace.scala:12-37 (and siblings)
     calc_place_similar_place_edges  PlaceSimilarPlace.calcPlaceSimilarPlaceEdges
@@ -278,6 +279,55 @@ def rank_recommendations_batch_near(offsets, ids, scores, place_ids, place_regio
         oc[:nseg] = 0
     shape = (nseg, width)
     return oi[:nseg * width].reshape(shape), osc[:nseg * width].reshape(shape), om[:nseg * width].reshape(shape), oc[:nseg]
+
+
+def rank_recommendations_batch_by_category(offsets, ids, scores, place_ids, place_region_ids, target_region_ids,
+                                           max_recommendations, place_category_ids, allowed=None, max_per_category=None,
+                                           circles=None, excluded=None):
+    """rank_recommendations_batch by category (locrec_rank_recommendations_batch_by_category): place_category_ids gives
+    the category of every row of the place table; allowed=(offsets, category_ids) is one allow-list per segment (CSR; an
+    empty list allows every category); max_per_category[s] >= 1 caps the rows of one category in segment s's output - a
+    row is eligible iff fewer than the cap kept rows of its category precede it in the order (score desc, id asc, input
+    row asc), and the output is the first max_recommendations eligible rows.  circles=(place_latitudes,
+    place_longitudes, center_latitudes, center_longitudes, radius_meters) adds rank_recommendations_batch_near's circles,
+    excluded=(offsets, ids) rank_recommendations_batch_excluding's lists.  A place listed several times in the target
+    region passes if some listing passes every predicate given; the first passing listing in input order gives the
+    category and the distance.  Host or device arrays, all of one kind.
+    -> (ids[S, W], scores[S, W], meters[S, W] or None without circles, counts[S]) in rank_recommendations_batch's layout."""
+    if not _is_tensor(offsets):
+        offsets = np.asarray(offsets, np.int64)
+    groups = [g for g in (allowed, circles, excluded) if g is not None]
+    cols = [offsets, ids, scores, place_ids, place_region_ids, target_region_ids, place_category_ids]
+    cols += [x for g in groups for x in g] + ([max_per_category] if max_per_category is not None else [])
+    c = _Cols(*cols)
+    nseg, n, npl = len(target_region_ids), len(ids), len(place_ids)
+    assert len(offsets) == nseg + 1 and len(scores) == n and len(place_region_ids) == npl and len(place_category_ids) == npl
+    assert allowed is None or len(allowed[0]) == nseg + 1
+    assert excluded is None or len(excluded[0]) == nseg + 1
+    assert max_per_category is None or len(max_per_category) == nseg
+    assert circles is None or ([len(x) for x in circles] == [npl, npl, nseg, nseg, nseg])
+    longest = int((offsets[1:] - offsets[:-1]).max()) if nseg else 0
+    width = max(0, min(int(max_recommendations), longest, n))
+    o = c.col(offsets, np.int64)
+    a = [c.col(ids, np.int64), c.col(scores, np.float64)]
+    p = [c.col(place_ids, np.int64), c.col(place_region_ids, np.int64)]
+    pc = c.col(place_category_ids, np.int64)
+    t = c.col(target_region_ids, np.int64)
+    q = [c.col(x, np.float64) for x in circles] if circles is not None else [None] * 5
+    x = [c.col(excluded[0], np.int64), c.col(excluded[1], np.int64)] if excluded is not None else [None, None]
+    al = [c.col(allowed[0], np.int64), c.col(allowed[1], np.int64)] if allowed is not None else [None, None]
+    caps = c.col(max_per_category, np.int64) if max_per_category is not None else None
+    (oi, oip), (osc, oscp), (oc, ocp) = c.out(nseg * width, np.int64), c.out(nseg * width, np.float64), c.out(nseg, np.int64)
+    om, omp = c.out(nseg * width, np.float64) if circles is not None else (None, None)
+    L.check(L.lib().locrec_rank_recommendations_batch_by_category(
+        nseg, o, n, a[0], a[1], npl, p[0], p[1], q[0], q[1], pc, t, q[2], q[3], q[4], width,
+        x[0], len(excluded[1]) if excluded is not None else 0, x[1],
+        al[0], len(allowed[1]) if allowed is not None else 0, al[1], caps, c.mem, oip, oscp, omp, ocp))
+    if nseg == 0 or width == 0:
+        oc[:nseg] = 0
+    shape = (nseg, width)
+    return (oi[:nseg * width].reshape(shape), osc[:nseg * width].reshape(shape),
+            om[:nseg * width].reshape(shape) if om is not None else None, oc[:nseg])
 
 
 def rank_recommendations_batch_stats():

@@ -242,6 +242,64 @@ class SgGraph:
         return (np.ascontiguousarray(oi[:, :width]), np.ascontiguousarray(op[:, :width]), np.ascontiguousarray(om[:, :width]),
                 cnt, its, conv.astype(bool))
 
+    def recommend_ranked_batch_by_category(self, vertex_ids, alpha, epsilon, max_iterations, place_ids, place_region_ids,
+                                           target_region_ids, max_recommendations, place_category_ids, allowed=None,
+                                           max_per_category=None, circles=None, excluded=None, on_device=True):
+        """recommend_ranked_batch by category (locrec_sg_recommend_ranked_batch_by_category): place_category_ids gives the
+        category of every row of the place table, allowed=(offsets[n + 1], category_ids) one allow-list per position (an
+        empty list allows every category), max_per_category[i] >= 1 caps the rows of one category in position i's ranking
+        - prep.rank_recommendations_batch_by_category's rules.  circles=(place_latitudes, place_longitudes,
+        center_latitudes, center_longitudes, radius_meters) and excluded=(offsets, ids) as in recommend_ranked_batch_near.
+        on_device=False: recommend_batch's host rows through prep.rank_recommendations_batch_by_category (the same result;
+        the A/B partner).
+        -> (ids[n, W], probabilities[n, W], meters[n, W] or None without circles, counts[n], iterations[n], converged[n])."""
+        n = len(vertex_ids)
+        xoff = xids = aoff = aids = caps = None
+        if excluded is not None:
+            xoff, xids = L.as_i64(excluded[0]), L.as_i64(excluded[1])
+            if len(xoff) != n + 1:
+                raise L.IllegalArgumentException("one exclusion list per vertex is required: offsets of n + 1 entries")
+        if allowed is not None:
+            aoff, aids = L.as_i64(allowed[0]), L.as_i64(allowed[1])
+            if len(aoff) != n + 1:
+                raise L.IllegalArgumentException("one allow-list per vertex is required: offsets of n + 1 entries")
+        if max_per_category is not None:
+            caps = L.as_i64(max_per_category)
+            if len(caps) != n:
+                raise L.IllegalArgumentException("one cap per vertex is required")
+        if not on_device:
+            from . import prep
+            off, ids, probs, its, conv = self.recommend_batch(vertex_ids, alpha, epsilon, max_iterations)
+            oi, op, om, cnt = prep.rank_recommendations_batch_by_category(
+                off, ids, probs, place_ids, place_region_ids, target_region_ids, max_recommendations, place_category_ids,
+                allowed=None if aoff is None else (aoff, aids), max_per_category=caps, circles=circles,
+                excluded=None if xoff is None else (xoff, xids))
+            return oi, op, om, cnt, its, conv
+        v, pl, reg, tgt = L.as_i64(vertex_ids), L.as_i64(place_ids), L.as_i64(place_region_ids), L.as_i64(target_region_ids)
+        pcat = L.as_i64(place_category_ids)
+        if len(reg) != len(pl) or len(tgt) != n or len(pcat) != len(pl):
+            raise L.IllegalArgumentException("one region and one category per place and one target region per vertex are required")
+        c = [None] * 5
+        stride = max(0, min(int(max_recommendations), self.info()["vertices"]))
+        oi, op, om = np.full((n, stride), -1, np.int64), np.zeros((n, stride), np.float64), None
+        if circles is not None:
+            c = [L.as_f64(x) for x in circles]
+            if len(c[0]) != len(pl) or len(c[1]) != len(pl) or not len(c[2]) == len(c[3]) == len(c[4]) == n:
+                raise L.IllegalArgumentException("one coordinate pair per place and one centre and radius per vertex are required")
+            om = np.zeros((n, stride), np.float64)
+        cnt, rows, its, conv = (np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, np.int32))
+        L.check(L.lib().locrec_sg_recommend_ranked_batch_by_category(
+            self._h, n, L.ptr(v, C.c_int64), float(alpha), float(epsilon), int(max_iterations), len(pl), L.ptr(pl, C.c_int64),
+            L.ptr(reg, C.c_int64), L.ptr(c[0], C.c_double), L.ptr(c[1], C.c_double), L.ptr(pcat, C.c_int64), L.ptr(tgt, C.c_int64),
+            L.ptr(c[2], C.c_double), L.ptr(c[3], C.c_double), L.ptr(c[4], C.c_double), stride,
+            L.ptr(xoff, C.c_int64), 0 if xids is None else len(xids), L.ptr(xids, C.c_int64),
+            L.ptr(aoff, C.c_int64), 0 if aids is None else len(aids), L.ptr(aids, C.c_int64), L.ptr(caps, C.c_int64),
+            L.ptr(oi, C.c_int64), L.ptr(op, C.c_double), L.ptr(om, C.c_double), L.ptr(cnt, C.c_int64), L.ptr(rows, C.c_int64),
+            L.ptr(its, C.c_int64), L.ptr(conv, C.c_int32)))
+        width = max(0, min(stride, int(rows.max()) if n else 0))
+        return (np.ascontiguousarray(oi[:, :width]), np.ascontiguousarray(op[:, :width]),
+                None if om is None else np.ascontiguousarray(om[:, :width]), cnt, its, conv.astype(bool))
+
     @classmethod
     def ranked_batch_stats(cls):
         """What this thread's last on-device recommend_ranked_batch did (locrec_sg_recommend_ranked_batch_stats)."""
